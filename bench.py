@@ -7,7 +7,8 @@ HBM when the timed region starts, pushed through the model that infera_load_mode
 --gpus N each rank owns its own 10M-row range of an (N x 10M)-row table (row-range sharding, weak
 scaling, no data-path collective); value = all rows of all ranks / max-over-ranks time.
 
-Besides the driver-contract fields the JSON line carries
+A plain run sets up, warms up, times --steps steps and prints the driver-contract fields (with --dump-outputs DIR it first writes
+what the last step computed to DIR/*.npy).  With --full the JSON line also carries
   * `roofline`     -- the dominant kernel against the gfx950 peak that bounds it (HIP events on the launching stream);
   * `end_to_end`   -- the metric as SURVEY.md 8(d) defines it: rows/s through the SQL surface's `infera_predict`
                       (T worker threads x 2048-row chunks of a columnar table in HOST memory: gather -> pinned staging
@@ -39,6 +40,7 @@ import torch.distributed as dist  # noqa: E402
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md "Peak FP32 (matrix)"
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # dense bf16 (the headline figure with 2:1 sparsity is never used)
 HBM_PEAK_GBS = 8000.0
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all ranks' files together
 
 
 def parse_args():
@@ -68,7 +70,20 @@ def parse_args():
                     help="testing only: every rank uses this one HIP device (lets the N>1 control path run on a 1-GPU box)")
     ap.add_argument("--no-registered", action="store_true", help="skip the scan over the REGISTERED host table (the opt-in zero-copy path)")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="where the full (uncompacted) result object is written")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline figure: the roofline of the dominant "
+                         "kernel, the other BASELINE configs (default run), the host path end to end (staged and registered), the CPU "
+                         "baselines and the NaN check of the output.  Off: the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (the output array a caller of the device-resident "
+                         "path receives) as DIR/output.npy, float32, DIR/output_rank<r>.npy per rank when N > 1; an output over "
+                         f"{DUMP_LIMIT_BYTES >> 20} MB in all is cut to a fixed, seeded sample of its rows")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.host_path:
+        ap.error("--dump-outputs writes the device-resident path's output; --host-path has none")
+    return args
 
 
 def cpu_budget() -> dict:
@@ -772,6 +787,30 @@ def emit(full: dict, detail_path: str) -> None:
     print(line, file=_LINE_OUT or sys.stdout, flush=True)
 
 
+def dump_sample_rows(rows: int, out_cols: int, world: int):
+    """The rows --dump-outputs keeps of a rows x out_cols float32 output: None (all of them) when they fit this rank's share of
+    DUMP_LIMIT_BYTES, else a fixed sample (seed 0, ascending, no repeats) that does."""
+    budget = DUMP_LIMIT_BYTES // world - 4096  # (room for the .npy header)
+    if rows * out_cols * 4 <= budget:
+        return None
+    return np.unique(np.random.default_rng(0).integers(0, rows, size=budget // (out_cols * 4)))
+
+
+def dump_outputs(d_out, rows: int, out_cols: int, out_dir: str, rank: int, world: int) -> str:
+    """--dump-outputs: what the last timed step wrote (rows x out_cols float32, the array infera_hip_predict_device hands its caller) ->
+    out_dir/output.npy (output_rank<r>.npy when N > 1).  Over this rank's share of DUMP_LIMIT_BYTES only a fixed sample of rows is kept
+    (seed 0, ascending row order): the same rows on every run, so that two builds of the library compare output for output."""
+    y = d_out.download((rows, out_cols))
+    keep = dump_sample_rows(rows, out_cols, world)
+    if keep is not None:
+        y = y[keep]
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, ("output" if world == 1 else f"output_rank{rank}") + ".npy")
+    np.save(path, y)
+    print(f"bench.py: wrote {path} ({y.shape[0]} of {rows} rows x {out_cols})", file=sys.stderr, flush=True)
+    return path
+
+
 def relaunch_command(gpus: int, host_path: bool, argv: list, env: dict):
     """`python bench.py --gpus N` with N > 1 and NO launcher around it (the shape the driver uses at N = 1) is one process
     with no WORLD_SIZE: it used to scan one shard on GPU 0 and print "n_gpus": 1.  Returns the `torch.distributed.run` command that runs the
@@ -893,12 +932,45 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed = shard.max_over_ranks(elapsed)
+    if args.dump_outputs:
+        dump_outputs(d_out, rows, out_cols, args.dump_outputs, rank, world)
+    bf16x6 = "bf16x6" in str(plan.get("conv_precision", ""))
+
+    def headline() -> dict:
+        return {
+            "metric": "rows/sec through infera_predict (device-resident table scan; PCIe-inclusive rate in end_to_end)",
+            "value": rows * world * args.steps / elapsed,
+            "value_is": "device_resident -- the bench contract's definition (inputs in HBM when the timed region starts).  BASELINE.json's metric as "
+                        "SURVEY.md 8(d) defines it (host table in, result vector out, PCIe included) is end_to_end.rows_per_s in this same line; "
+                        "ratios to the CPU baseline are only ever taken from that one",
+            "unit": "rows/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "bf16x6 (f32 operands cut exactly into three bf16 parts, six bf16 MFMAs per product, f32 accumulate: the default form of the stem "
+                     "and the tiled convolutions; the head on the exact-f32 instruction)" if bf16x6 else "f32",
+            "data": "synthetic (counter-based splitmix64 table, seed 42; random-init weights seed 1234)",
+            "config": {"workload": wl_name, "rows_per_gpu": rows, "features": cols, "parallelism": f"row-range x{world}",
+                       "precision": str(plan.get("conv_precision", plan.get("precision", "fp32"))).split(" ")[0],
+                       "entry": "infera_hip_predict_device (inputs resident in HBM)",
+                       "kernel": plan.get("fused_kernel", ",".join(sorted(set(plan["exec"]) - {"skipped"})))},
+        }
+
+    if not args.full:  # a plain run: the headline figure and nothing else (the end_to_end / roofline / CPU figures are --full's)
+        if rank == 0:
+            emit(headline(), args.detail)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # roofline of the dominant kernel: HIP events on the launching stream around back-to-back launches
     iters = max(3, min(args.steps, 10))
     ms = capi.time_predict_device("bench", d_in, rows, cols, d_out, iters)
     kernel_s = ms / 1e3 / iters
-    bf16x6 = "bf16x6" in str(plan.get("conv_precision", ""))
     achieved, peak, unit = roofline_of(bound, bf16x6, flops_row, bytes_row, rows, kernel_s)
 
     # HBM traffic per launch: PMC counters cannot be read from inside this process; they are collected by
@@ -1012,32 +1084,10 @@ def main():
                 others[key]["end_to_end"] = {"error": f"{type(exc).__name__}: {exc}"}
 
     if rank == 0:
-        total_rows = rows * world * args.steps
-        full = {
-            "metric": "rows/sec through infera_predict (device-resident table scan; PCIe-inclusive rate in end_to_end)",
-            "value": total_rows / elapsed,
-            "value_is": "device_resident -- the bench contract's definition (inputs in HBM when the timed region starts).  BASELINE.json's metric as "
-                        "SURVEY.md 8(d) defines it (host table in, result vector out, PCIe included) is end_to_end.rows_per_s in this same line; "
-                        "ratios to the CPU baseline are only ever taken from that one",
-            "unit": "rows/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "bf16x6 (f32 operands cut exactly into three bf16 parts, six bf16 MFMAs per product, f32 accumulate: the default form of the stem "
-                     "and the tiled convolutions; the head on the exact-f32 instruction)" if bf16x6 else "f32",
-            "data": "synthetic (counter-based splitmix64 table, seed 42; random-init weights seed 1234)",
-            "config": {"workload": wl_name, "rows_per_gpu": rows, "features": cols, "parallelism": f"row-range x{world}",
-                       "precision": str(plan.get("conv_precision", plan.get("precision", "fp32"))).split(" ")[0],
-                       "entry": "infera_hip_predict_device (inputs resident in HBM)",
-                       "kernel": plan.get("fused_kernel", ",".join(sorted(set(plan["exec"]) - {"skipped"})))},
-            "roofline": {"bound": bound, "achieved": achieved, "peak": peak, "unit": unit, "frac": achieved / peak,
-                         "traffic": traffic, "traffic_source": traffic_source, "algorithmic_bytes": bytes_row * rows,
-                         "kernel_ms": kernel_s * 1e3, "rows_per_s": rows / kernel_s, "algorithmic_per_row": {"flop": flops_row, "bytes": bytes_row}},
-        }
+        full = headline()
+        full["roofline"] = {"bound": bound, "achieved": achieved, "peak": peak, "unit": unit, "frac": achieved / peak,
+                            "traffic": traffic, "traffic_source": traffic_source, "algorithmic_bytes": bytes_row * rows,
+                            "kernel_ms": kernel_s * 1e3, "rows_per_s": rows / kernel_s, "algorithmic_per_row": {"flop": flops_row, "bytes": bytes_row}}
         if bf16x6:
             full["roofline"]["peak_is"] = ("dense bf16 MFMA peak / 6 (six matrix instructions per fp32 product: three exact bf16 parts per operand, the three "
                                            "smallest partial products dropped); the stem + max-pool kernel runs in the same arithmetic, the 512 -> 1000 head on the exact-fp32 instruction")

@@ -1,11 +1,24 @@
 import os
+import shutil
 import sys
+import tempfile
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+# The library reads INFERA_CACHE_DIR once per process, and its default ($TMPDIR/infera_cache) is shared by every user of the machine:
+# tests that clear or fill the model cache get a directory of their own, set before the library is first loaded (children inherit it).
+_SESSION_CACHE = None
+if "INFERA_CACHE_DIR" not in os.environ:
+    _SESSION_CACHE = os.environ["INFERA_CACHE_DIR"] = tempfile.mkdtemp(prefix="infera_test_cache_")
+
+
+def pytest_unconfigure(config):
+    if _SESSION_CACHE:
+        shutil.rmtree(_SESSION_CACHE, ignore_errors=True)
 
 
 def pytest_configure(config):
@@ -57,10 +70,10 @@ def gpu_api(built):
 
 @pytest.fixture(scope="session")
 def default_bench_run():
-    """bench.py's default invocation, run ONCE per session: the contract test reads its fields, the perf test (collected last) its ratios."""
+    """bench.py's default workload with --full, run ONCE per session: the contract test reads its fields, the perf test (collected last) its ratios."""
     env = dict(os.environ)
     env.pop("INFERA_DEVICES", None)
-    return run_bench(["--steps", "5", "--warmup", "2", "--cpu-seconds", "3", "--e2e-reps", "2"], env=env)  # (asserts ONE line, <= 4096 bytes)
+    return run_bench(["--full", "--steps", "5", "--warmup", "2", "--cpu-seconds", "3", "--e2e-reps", "2"], env=env)  # (asserts ONE line, <= 4096 bytes)
 
 
 @pytest.fixture(scope="session")

@@ -1,8 +1,79 @@
-"""bench.py's default invocation (what the driver runs: no flags beyond --steps / --warmup) on one GPU.  The ONE stdout line must fit the
+"""bench.py's default workload with --full on one GPU.  The ONE stdout line must fit the
 driver's capture window (<= 4 KB: round 3's 20.9 KB line parsed as null) and carry the contract fields + roofline + cpu_baseline (three legs:
 reference-shaped port, register-blocked port, torch-CPU) + end_to_end + the other two GPU configs of BASELINE.json; the full object goes to
---detail / stderr."""
+--detail / stderr.  The plain run (what the driver runs: no flags beyond --gpus / --steps / --warmup) carries the contract fields alone, and
+--dump-outputs writes what its last timed step computed."""
+import os
+import sys
+
+import numpy as np
 import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")
+FULL_ONLY = ("roofline", "end_to_end", "end_to_end_registered", "cpu_baseline", "other_workloads", "value_end_to_end")
+
+
+def _oracle_rows(tmp_path, model_blob, rows: int):
+    """The CPU oracle on the first `rows` rows of bench.py's table (seed 42, row 0: what capi.synth_fill generates on the device)."""
+    from infera_amd import onnx_writer as W
+    from infera_amd import synth
+    from oracle import oracle
+
+    return oracle.Model(W.write(str(tmp_path / "model.onnx"), model_blob)).predict(synth.table(42, 0, rows, 128))
+
+
+def _within_parity_bar(got, want):
+    """tests/test_parity_gpu.py's bar: |hip - oracle| <= 1e-4 * |oracle| + 1e-6."""
+    return float((np.abs(got - want) - (1e-4 * np.abs(want) + 1e-6)).max()) <= 0.0
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_the_headline_alone_and_dumps_the_last_step(gpu_api, tmp_path):
+    """No --full: set up, warm up, time --steps steps, print the contract line -- no roofline, host path, CPU legs or other workloads.
+    --dump-outputs: C2's whole 10M x 1 result (40 MB, under the 64 MB cap), equal to the oracle on its first rows."""
+    from infera_amd import onnx_writer as W
+    from tests.conftest import run_bench
+
+    env = dict(os.environ)
+    env.pop("INFERA_DEVICES", None)
+    out = tmp_path / "out"
+    d, full = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], env=env)
+    for k in CONTRACT:
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "rows/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["config"]["workload"].startswith("C2:") and d["config"]["rows_per_gpu"] == 10_000_000 and d["value_is"] == "device_resident"
+    assert d["metric"] == full["metric"] and d["metric"].startswith("rows/sec through infera_predict")
+    assert abs(d["value"] - 10_000_000 / (d["ms_per_step"] / 1e3)) / d["value"] < 1e-5
+    assert not [k for k in FULL_ONLY if k in d or k in full], (sorted(d), sorted(full))
+    assert sorted(os.listdir(out)) == ["output.npy"]
+    y = np.load(out / "output.npy")
+    assert y.dtype == np.float32 and y.shape == (10_000_000, 1)
+    assert _within_parity_bar(y[:4096], _oracle_rows(tmp_path, W.mlp((128, 256, 64, 1)), 4096))
+
+
+@pytest.mark.gpu
+def test_dump_outputs_samples_an_output_over_64_mb(gpu_api, tmp_path):
+    """C4 over 2M rows writes 2M x 10 floats (80 MB): the dump keeps bench.dump_sample_rows' fixed rows, under 64 MB, each one the oracle's."""
+    from infera_amd import onnx_writer as W
+    from tests.conftest import run_bench
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rows = 2_000_000
+    env = dict(os.environ)
+    env.pop("INFERA_DEVICES", None)
+    out = tmp_path / "out"
+    d, _ = run_bench(["--workload", "logreg", "--rows", str(rows), "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)], env=env)
+    assert d["steps"] == 2 and d["config"]["rows_per_gpu"] == rows
+    keep = bench.dump_sample_rows(rows, 10, 1)
+    assert keep is not None and os.path.getsize(out / "output.npy") <= 64 << 20
+    y = np.load(out / "output.npy")
+    assert y.dtype == np.float32 and y.shape == (len(keep), 10)
+    first = keep < 4096
+    assert first.sum() > 1000
+    assert _within_parity_bar(y[first], _oracle_rows(tmp_path, W.logreg_softmax(128, 10), 4096)[keep[first]])
 
 
 @pytest.mark.gpu

@@ -154,7 +154,7 @@ def test_load_errors(api, tmp_path):
     with pytest.raises(api.InferaError, match="^ONNX error: "):
         api.load_model("x", str(bad))
     with pytest.raises(api.InferaError, match="^HTTP request failed: "):
-        api.load_model("x", "https://example.invalid/model.onnx")
+        api.load_model("x", "https://127.0.0.1:1/model.onnx")  # a closed loopback port: the failure stays on this host
     assert "x" not in api.get_loaded_models()
 
 

@@ -150,3 +150,24 @@ def test_bench_relaunches_itself_when_gpus_is_asked_without_a_launcher():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], env=dict(os.environ, WORLD_SIZE="2", RANK="0"),
                        capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and "--gpus 4 but WORLD_SIZE=2" in p.stderr
+
+
+def test_bench_dump_sample_is_fixed_and_fits():
+    """--dump-outputs: an output within the 64 MB cap is written whole; a larger one is cut to the same rows on every run (ascending, no
+    repeats), with all ranks' files together under the cap."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert bench.dump_sample_rows(10_000_000, 1, 1) is None  # C2: 40 MB, whole
+    assert bench.dump_sample_rows(1024, 1000, 1) is None     # C5: 4 MB
+    for rows, cols, world in ((50_000_000, 10, 1), (2_000_000, 10, 1), (12_500_000, 1, 8)):
+        k = bench.dump_sample_rows(rows, cols, world)
+        assert k is not None and np.array_equal(k, bench.dump_sample_rows(rows, cols, world))
+        assert np.all(np.diff(k) > 0) and k[0] >= 0 and k[-1] < rows
+        assert world * (k.size * cols * 4 + 4096) <= bench.DUMP_LIMIT_BYTES
+        assert k.size > 0.5 * (bench.DUMP_LIMIT_BYTES // world) // (cols * 4), (rows, cols, world, k.size)
+    # a bad --steps is refused before anything runs (the line's ms_per_step is the time of ONE of --steps timed steps)
+    import subprocess
+
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--steps must be >= 1" in p.stderr

@@ -95,13 +95,14 @@ def _free_port():
 
 
 @pytest.mark.gpu
-def test_bench_two_ranks_sharing_one_gpu(gpu_api):
+def test_bench_two_ranks_sharing_one_gpu(gpu_api, tmp_path):
     """bench.py's N>1 control path (gloo barrier, max over ranks, per-rank row ranges, concurrent host scans)."""
     from tests.conftest import run_bench
 
     env = dict(os.environ)
     env.pop("INFERA_DEVICES", None)
-    line, full = run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--rows", str(2048 * 300), "--share-device", "0", "--e2e-threads", "4", "--e2e-reps", "3"],
+    line, full = run_bench(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--rows", str(2048 * 300), "--share-device", "0", "--e2e-threads", "4", "--e2e-reps", "3",
+                            "--dump-outputs", str(tmp_path / "out")],
                            env=env, launcher=[sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                               "--master-port", str(_free_port())], timeout=900)
     assert line["n_gpus"] == 2 and line["steps"] == 3 and line["scaling"] == "weak" and line["value"] > 0
@@ -110,6 +111,9 @@ def test_bench_two_ranks_sharing_one_gpu(gpu_api):
     e = full["end_to_end"]
     assert e["ranks"] == 2 and e["threads_per_rank"] == 4 and len(e["scan_seconds"]) == 3 and e["rows_per_s"] > 0
     assert "cpu_baseline" not in line and "cpu_baseline" not in full  # rank 0 at N=1 only
+    # --dump-outputs: every rank writes its own shard's result
+    assert sorted(os.listdir(tmp_path / "out")) == ["output_rank0.npy", "output_rank1.npy"]
+    assert all(np.load(tmp_path / "out" / f"output_rank{r}.npy").shape == (2048 * 300, 1) for r in (0, 1))
 
 
 @pytest.mark.gpu
@@ -134,7 +138,7 @@ def test_bench_eight_ranks_sharing_one_gpu_is_what_the_driver_will_launch(gpu_ap
         env.pop(k, None)
     # NO launcher: a plain `python bench.py --gpus 8` -- the shape the driver uses at N = 1 -- must run 8 ranks all the same
     # (bench.py re-executes itself under torch.distributed.run); the 2-rank test above keeps the driver's own launcher shape covered
-    line, full = run_bench(["--gpus", "8", "--steps", "3", "--warmup", "1", "--rows", str(rows), "--share-device", "0", "--e2e-reps", str(reps)],
+    line, full = run_bench(["--full", "--gpus", "8", "--steps", "3", "--warmup", "1", "--rows", str(rows), "--share-device", "0", "--e2e-reps", str(reps)],
                            env=env, timeout=1500)
     wall = time.time() - t0
     assert wall < 900, wall  # (the driver's own limit per bench run is well above this; 8 ranks on one GPU take ~2 minutes)

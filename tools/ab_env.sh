@@ -8,7 +8,7 @@ tag=$1; re=$2; shift 2
 O=gpurun_out/$tag; mkdir -p $O; : > $O/ab.txt
 for i in 1 2; do
   for cfg in "$@"; do
-    ( cd /tmp && env $cfg timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/p_ab -o t -- python $OLDPWD/bench.py --workload resnet18 --steps 6 --warmup 2 --no-end-to-end --no-cpu-baseline --detail /tmp/d.json > /tmp/line_ab.json 2>/dev/null )
+    ( cd /tmp && env $cfg timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/p_ab -o t -- python $OLDPWD/bench.py --full --workload resnet18 --steps 6 --warmup 2 --no-end-to-end --no-cpu-baseline --detail /tmp/d.json > /tmp/line_ab.json 2>/dev/null )
     python tools/rocpd_summary.py $(find /tmp/p_ab -name "*.db") 2>/dev/null | grep -E "$re" | sed 's/void infera_hip::kern::(anonymous namespace):://; s/(float const.*float c[a-z]*//; s/infera_hip::kern::(anonymous namespace):://' | cut -c1-150 | sed "s|^|$cfg  |" >> $O/ab.txt
     python -c "
 import json; d=json.loads(open('/tmp/line_ab.json').read().strip().splitlines()[-1]); print('$cfg  pass ms', d['ms_per_step'], 'frac', d['roofline']['frac'])" >> $O/ab.txt

@@ -18,7 +18,7 @@ mkdir -p "$(dirname "$OUT")"
   for round in 1 2 3; do
     for m in "0 0" "1 0" "0 1" "1 1"; do
       set -- $m
-      line=$(INFERA_DENSE16S_MODE=$1 INFERA_DENSE16S_NT=$2 python bench.py --workload logreg --no-cpu-baseline --no-end-to-end --steps 20 --warmup 3 2>/dev/null | tail -1)
+      line=$(INFERA_DENSE16S_MODE=$1 INFERA_DENSE16S_NT=$2 python bench.py --full --workload logreg --no-cpu-baseline --no-end-to-end --steps 20 --warmup 3 2>/dev/null | tail -1)
       echo "round $round park $1 nt $2: $(echo "$line" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print("ms_per_step %.4f kernel_ms %.4f achieved %.1f GB/s frac %.4f" % (d["ms_per_step"], r["kernel_ms"], r["achieved"], r["frac"]))')"
     done
   done

@@ -6,9 +6,9 @@ set -u
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r06_final; mkdir -p $O
 # unprofiled lines first (the box's own numbers), then the profiled passes
-( timeout 900 python bench.py --steps 20 --warmup 5 --detail $O/line_mlp_detail.json > $O/line_mlp.json 2> /dev/null; echo "rc=$? bytes=$(wc -c < $O/line_mlp.json)" ) > $O/bench_rc.txt 2>&1
-( timeout 600 python bench.py --workload logreg --steps 20 --warmup 3 --no-cpu-baseline --no-end-to-end --detail $O/line_logreg_detail.json > $O/line_logreg.json 2> /dev/null )
-( timeout 600 python bench.py --workload resnet18 --steps 10 --warmup 3 --no-cpu-baseline --no-end-to-end --detail $O/line_resnet18_detail.json > $O/line_resnet18.json 2> /dev/null )
+( timeout 900 python bench.py --full --steps 20 --warmup 5 --detail $O/line_mlp_detail.json > $O/line_mlp.json 2> /dev/null; echo "rc=$? bytes=$(wc -c < $O/line_mlp.json)" ) > $O/bench_rc.txt 2>&1
+( timeout 600 python bench.py --full --workload logreg --steps 20 --warmup 3 --no-cpu-baseline --no-end-to-end --detail $O/line_logreg_detail.json > $O/line_logreg.json 2> /dev/null )
+( timeout 600 python bench.py --full --workload resnet18 --steps 10 --warmup 3 --no-cpu-baseline --no-end-to-end --detail $O/line_resnet18_detail.json > $O/line_resnet18.json 2> /dev/null )
 bash tools/profile_bench.sh r06_final/mlp --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end --no-other-workloads > $O/prof_mlp.log 2>&1
 bash tools/profile_bench.sh r06_final/logreg --workload logreg --steps 20 --warmup 3 --no-cpu-baseline --no-end-to-end > $O/prof_logreg.log 2>&1
 bash tools/profile_bench.sh r06_final/resnet18 --workload resnet18 --steps 5 --warmup 2 --no-cpu-baseline --no-end-to-end > $O/prof_resnet.log 2>&1

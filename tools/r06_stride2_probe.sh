@@ -9,7 +9,7 @@ O=${1:-gpurun_out/r06_stride2_probe.txt}
 : > $O
 for i in 1 2 3; do
   for cfg in "X=0" "INFERA_CONV_PROBE_SW1=1"; do
-    env $cfg INFERA_CONV_PROBE=1 python bench.py --workload resnet18 --steps 10 --warmup 3 --no-end-to-end --no-cpu-baseline --detail /tmp/d.json 2>/dev/null | tail -1 | \
+    env $cfg INFERA_CONV_PROBE=1 python bench.py --full --workload resnet18 --steps 10 --warmup 3 --no-end-to-end --no-cpu-baseline --detail /tmp/d.json 2>/dev/null | tail -1 | \
       python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$cfg  round $i  pass ms %.4f  frac %.4f' % (d['ms_per_step'], d['roofline']['frac']))" >> $O
   done
 done

@@ -8,7 +8,7 @@ out=gpurun_out/${tag}_stem_ab.txt
   for rep in 1 2; do
   for cfg in "INFERA_STEM_POOL2=0" "INFERA_STEM_POOL2=1 INFERA_STEM_POOL2_DESYNC=0" "INFERA_STEM_POOL2=1 INFERA_STEM_POOL2_DESYNC=1" "INFERA_STEM_POOL2=1 INFERA_STEM_POOL2_DESYNC=2"; do
     echo "== $cfg"
-    env $cfg python bench.py --workload resnet18 --steps 10 --warmup 3 --no-cpu-baseline --no-end-to-end 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('img/s', round(d['value']), 'ms', round(d['ms_per_step'],3), 'frac', round(d['roofline']['frac'],4))"
+    env $cfg python bench.py --full --workload resnet18 --steps 10 --warmup 3 --no-cpu-baseline --no-end-to-end 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('img/s', round(d['value']), 'ms', round(d['ms_per_step'],3), 'frac', round(d['roofline']['frac'],4))"
   done
   done
   cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
