@@ -214,6 +214,14 @@ void PassRunner::launch_plain(size_t i) {
       kern::copy_cols(stream, buf(x.in0), buf(x.out), nr, x.K, p.buf_per_row[size_t(x.in0)], x.col_off, x.K, 0);
       break;
     case StepKind::ArgMax: kern::argmax_rows(stream, buf(x.in0), buf(x.out), nr, x.K); break;
+    case StepKind::TreeEnsemble:
+      kern::tree_walk(stream, buf(x.in0), int(p.buf_per_row[size_t(x.in0)]), d.tab, x.tree_nodes, x.tree_count, d.W, int(x.tree_W), int(x.tree_slices),
+                      buf(x.out), nr);
+      break;
+    case StepKind::TreeReduce:
+      kern::tree_reduce(stream, buf(x.in0), d.bias, d.cst, buf(x.out), nr, int(x.tree_W), int(x.tree_slices), x.tree_count, x.tree_average, x.tree_mode,
+                        x.tree_signed);
+      break;
   }
 }
 

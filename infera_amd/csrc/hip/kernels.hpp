@@ -50,6 +50,14 @@ void gather_columns_device(hipStream_t s, const ColumnTable &tab, int ncols, int
 // synthetic table fill (SURVEY.md 8d generator), row-major [rows, ncols]
 void synth_fill(hipStream_t s, float *dst, uint64_t seed, uint64_t row0, uint64_t rows, uint64_t ncols);
 
+// ---- tree ensembles (trees.hip) ---------------------------------------------------------------
+// part[S][rows][W] = per-slice sums of the leaves the rows of x [rows, F] reach; tab = host/trees.hpp TreePack::tab (records, roots, slices)
+void tree_walk(hipStream_t s, const float *x, int F, const uint32_t *tab, int64_t n_nodes, int64_t n_trees, const float *leaves, int W, int S,
+               float *part, int64_t rows);
+// the slices summed in slice order (/ n_trees under AVERAGE, + base) -> scores [rows, W], or a host/plan.hpp TreeOut form
+void tree_reduce(hipStream_t s, const float *part, const float *base, const float *labels, float *y, int64_t rows, int W, int S, int64_t n_trees,
+                 bool average, int mode, bool is_signed);
+
 // ---- dense layer, fp32 MFMA (dense.hip) -------------------------------------------------------
 // Y[rows, M] = act(X[rows, K] . W[K, M] + bias[M]); W row-major, bias may be null.
 // softmax_fused: apply a row softmax over the M outputs in the epilogue (requires M <= 256).

@@ -3,6 +3,8 @@
 #include "runtime.hpp"
 #include "../host/onnx_model.hpp"
 
+#include <cstring>
+
 namespace infera_hip {
 namespace rt {
 namespace {
@@ -178,6 +180,11 @@ void upload_to_device(const LoadedModel &m, DeviceModel &dm) {
     if (!d.cst) d.cst = upload(s.cst, us);  // (a split stem keeps its bf16 blob there: convolutions have no constants)
     d.scale = upload(s.scale, us);
     d.shift = upload(s.shift, us);
+    if (!s.tree_tab.empty()) {
+      std::vector<float> words(s.tree_tab.size());  // (same bits: upload() moves floats)
+      std::memcpy(words.data(), s.tree_tab.data(), words.size() * 4);
+      d.tab = reinterpret_cast<uint32_t *>(upload(words, us));
+    }
   }
 }
 
@@ -192,6 +199,7 @@ DeviceModel::~DeviceModel() {
   for (auto &d : steps) {
     for (float *p : {d.W, d.bias, d.cst, d.scale, d.shift})
       if (p) (void)hipFree(p);
+    if (d.tab) (void)hipFree(d.tab);
   }
   if (mlp3_packed) (void)hipFree(mlp3_packed);
   for (float *p : chain_packed)

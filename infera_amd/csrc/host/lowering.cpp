@@ -22,6 +22,7 @@
 
 #include "common.hpp"
 #include "plan.hpp"
+#include "trees.hpp"
 
 namespace infera_hip {
 
@@ -1367,8 +1368,67 @@ struct Lowerer {
     }
     unsupported(n, "only (constant table, index activation) or (activation, constant contiguous indices)");
   }
+  // TreeEnsembleRegressor / TreeEnsembleClassifier: a TreeEnsemble step (walk, per-slice partial sums) and a TreeReduce step (slices
+  // summed in fixed order, AVERAGE, base_values, binary expansion or the label), then post_transform on the scores
+  void tree_ensemble(const NodeDef &n) {
+    TreePack tp;
+    const Val &x = get(n, 0);
+    if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, features] activations");
+    try {
+      tp = pack_tree_ensemble(n, x.shape[1]);
+    } catch (const TreeError &e) {
+      unsupported(n, e.what());
+    }
+    const int xbuf = x.buf;
+    const int64_t rows = x.shape[0];
+    Step w;
+    w.kind = StepKind::TreeEnsemble;
+    w.in0 = xbuf;
+    w.tree_tab = std::move(tp.tab);
+    w.W = std::move(tp.leaves);
+    w.tree_count = tp.trees;
+    w.tree_nodes = tp.nodes;
+    w.tree_max_depth = tp.max_depth;
+    w.tree_W = tp.W;
+    w.tree_E = tp.E;
+    w.tree_slices = tp.slices;
+    w.tree_average = tp.average;
+    w.tree_signed = tp.is_signed;
+    const std::string tmp = n.outputs[0] + "\x01";
+    const bool cls = tp.classifier;
+    const bool want_label = cls && wanted(n, 0), want_scores = cls ? wanted(n, 1) : true;
+    w.tree_mode = want_scores ? (tp.binary ? kTreeBinaryScores : kTreeScores) : (tp.binary ? kTreeBinaryLabel : kTreeLabel);
+    NodeDef walk = n;
+    walk.outputs = {tmp + "partial"};
+    const int part = emit(std::move(w), walk, {rows, 2 * tp.slices * tp.W}).out;  // (f64 partials as f32 pairs)
+    auto reduce = [&](int mode, const std::string &out, int64_t cols) {
+      Step r;
+      r.kind = StepKind::TreeReduce;
+      r.in0 = part;
+      r.tree_W = tp.W;
+      r.tree_E = tp.E;
+      r.tree_slices = tp.slices;
+      r.tree_count = tp.trees;
+      r.tree_average = tp.average;
+      r.tree_signed = tp.is_signed;
+      r.tree_mode = mode;
+      r.bias = tp.base;
+      r.cst = tp.labels;
+      NodeDef d = n;
+      d.outputs = {out};
+      return emit(std::move(r), d, cols ? std::vector<int64_t>{rows, cols} : std::vector<int64_t>{rows}).out;
+    };
+    if (want_label) int_bufs.insert(reduce(tp.binary ? kTreeBinaryLabel : kTreeLabel, n.outputs[0], 0));
+    if (want_scores) {
+      const std::string raw = tmp + "raw";
+      uses[raw] = 1;
+      reduce(tp.binary ? kTreeBinaryScores : kTreeScores, raw, tp.E);
+      ml_post_transform(n, raw, cls ? n.outputs[1] : n.outputs[0]);
+    }
+  }
   void ml_node(const NodeDef &n) {
     if (n.op == "ArrayFeatureExtractor") return array_feature_extractor(n);
+    if (n.op == "TreeEnsembleRegressor" || n.op == "TreeEnsembleClassifier") return tree_ensemble(n);
     const Val &x = get(n, 0);
     if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, features] activations");
     const int64_t F = x.shape[1];
@@ -1567,7 +1627,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -1580,6 +1640,13 @@ std::string Plan::describe_json() const {
     if (s.in1 >= 0) o << ",\"in1\":" << s.in1;
     if (s.kind == StepKind::Dense) o << ",\"K\":" << s.K << ",\"M\":" << s.M << ",\"bias\":" << (s.bias.empty() ? "false" : "true");
     if (s.kind == StepKind::Conv2d) o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"k\":[" << s.kh << "," << s.kw << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
+    if (s.kind == StepKind::TreeEnsemble || s.kind == StepKind::TreeReduce) {
+      static const char *modes[] = {"scores", "label", "binary_scores", "binary_label"};
+      o << ",\"E\":" << s.tree_E << ",\"slices\":" << s.tree_slices << ",\"output\":\"" << modes[s.tree_mode] << "\"";
+      if (s.kind == StepKind::TreeEnsemble)
+        o << ",\"trees\":" << s.tree_count << ",\"nodes\":" << s.tree_nodes << ",\"max_depth\":" << s.tree_max_depth << ",\"walk_width\":" << s.tree_W
+          << ",\"aggregate\":\"" << (s.tree_average ? "AVERAGE" : "SUM") << "\"";
+    }
     if (s.act != Act::None) o << ",\"act\":\"" << acts[int(s.act)] << "\"";
     o << ",\"origin\":" << json_str(s.origin) << "}";
   }

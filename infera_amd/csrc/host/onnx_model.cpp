@@ -172,17 +172,14 @@ std::shared_ptr<TensorData> read_tensor(Wire w) {
       t->dtype = kFloat;  // narrowed: the whole path computes in f32
       if (raw) {
         if (rawlen / 8 != n || rawlen % 8) throw size_err();
-        t->f32.resize(n);
-        for (size_t i = 0; i < n; i++) {
-          double d;
-          std::memcpy(&d, raw + i * 8, 8);
-          t->f32[i] = float(d);
-        }
+        t->f64.resize(n);
+        std::memcpy(t->f64.data(), raw, rawlen);
       } else {
         if (ddata.size() != n) throw size_err();
-        t->f32.resize(n);
-        for (size_t i = 0; i < n; i++) t->f32[i] = float(ddata[i]);
+        t->f64 = std::move(ddata);
       }
+      t->f32.resize(n);
+      for (size_t i = 0; i < n; i++) t->f32[i] = float(t->f64[i]);
       break;
     case kInt64:
     case kInt32:
@@ -213,7 +210,7 @@ std::shared_ptr<TensorData> read_tensor(Wire w) {
   return t;
 }
 
-// AttributeProto: name=1 f=2 i=3 s=4 t=5 floats=7 ints=8 type=20
+// AttributeProto: name=1 f=2 i=3 s=4 t=5 floats=7 ints=8 strings=9 type=20
 Attribute read_attribute(Wire w) {
   Attribute a;
   bool saw_f = false, saw_i = false;
@@ -232,6 +229,7 @@ Attribute read_attribute(Wire w) {
       case 5: if (wt != 2) return false; a.t = read_tensor(c.sub()); return true;
       case 7: read_packed_or_single_f32(c, wt, a.floats); return true;
       case 8: read_packed_or_single_i64(c, wt, a.ints); return true;
+      case 9: if (wt != 2) return false; a.strings.push_back(c.str()); return true;
       case 20: if (wt != 0) return false; a.type = int(c.varint()); return true;
       default: return false;
     }
@@ -239,6 +237,7 @@ Attribute read_attribute(Wire w) {
   if (a.type == 0) {  // writers older than IR 3 omit `type`
     if (!a.ints.empty()) a.type = 7;
     else if (!a.floats.empty()) a.type = 6;
+    else if (!a.strings.empty()) a.type = 8;
     else if (a.t) a.type = 4;
     else if (!a.s.empty()) a.type = 3;
     else if (saw_f) a.type = 1;

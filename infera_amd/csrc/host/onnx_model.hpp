@@ -22,6 +22,7 @@ struct TensorData {
   std::vector<int64_t> dims;
   std::vector<float> f32;
   std::vector<int64_t> i64;
+  std::vector<double> f64;  // kDouble payloads as read (f32 above holds them narrowed): load-time conversions that must round their own way
   // Element count = payload length.  The decoder has verified it equals Π dims (overflow-checked), so a
   // declared shape can never claim more elements than the file holds.
   size_t count() const { return dtype == kInt64 ? i64.size() : f32.size(); }
@@ -29,12 +30,13 @@ struct TensorData {
 
 struct Attribute {
   std::string name;
-  int type = 0;  // AttributeProto.AttributeType: 1 FLOAT 2 INT 3 STRING 4 TENSOR 6 FLOATS 7 INTS
+  int type = 0;  // AttributeProto.AttributeType: 1 FLOAT 2 INT 3 STRING 4 TENSOR 6 FLOATS 7 INTS 8 STRINGS
   float f = 0.f;
   int64_t i = 0;
   std::string s;
   std::vector<int64_t> ints;
   std::vector<float> floats;
+  std::vector<std::string> strings;
   std::shared_ptr<TensorData> t;
 };
 

@@ -42,7 +42,12 @@ enum class StepKind : int {
   LRN = 13,         // across-channel local response normalisation: y = x / (act_b' ... see lrn_* fields) over [N,C,S]
   ChannelShuffle = 14,  // out[n, j*g + i, p] = in0[n, i*(C/g) + j, p]   (Reshape [N,g,C/g,..] -> Transpose(0,2,1,..) -> Reshape; groups in `groups`)
   PadCols = 12,     // out[r, 0:K] = in0[r, :], zeros up to M columns   (row length -> multiple of 4 for the 16-byte loads of the MFMA kernels)
+  TreeEnsemble = 15,  // ai.onnx.ml tree walk: out = per-slice partial sums, f64 as f32 pairs: [rows][2 * tree_slices * tree_W] (slice-major inside the pass, trees.hip)
+  TreeReduce = 16,    // in0 = those partials -> scores [rows, E] (AVERAGE, base_values, binary expansion) or the class label [rows]
 };
+
+// TreeReduce output modes (Step::tree_mode)
+enum TreeOut : int { kTreeScores = 0, kTreeLabel = 1, kTreeBinaryScores = 2, kTreeBinaryLabel = 3 };
 
 struct Step {
   StepKind kind = StepKind::Unary;
@@ -73,6 +78,11 @@ struct Step {
   // LRN: window `lrn_size` channels, y = x / (lrn_bias + lrn_alpha / lrn_size * sum x^2)^lrn_beta
   int64_t lrn_size = 0;
   float lrn_alpha = 1e-4f, lrn_beta = 0.75f, lrn_bias = 1.f;
+  // TreeEnsemble / TreeReduce (host/trees.hpp packs the tables; W = leaf table [leaves][tree_W], cst = class labels, bias = base_values)
+  std::vector<uint32_t> tree_tab;  // nodes (2 words each) | root node per tree | first tree per slice (tree_slices + 1 entries)
+  int64_t tree_count = 0, tree_nodes = 0, tree_max_depth = 0, tree_W = 0, tree_E = 0, tree_slices = 1;
+  int tree_mode = kTreeScores;
+  bool tree_average = false, tree_signed = false;  // AVERAGE aggregation; binary form with a negative weight ([-s, s], label s > 0)
   std::string origin;  // ONNX node names/ops this step came from (diagnostics)
 };
 

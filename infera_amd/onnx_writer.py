@@ -523,3 +523,149 @@ def sklearn_pipeline(features: int = 30, classes: int = 3, kind: str = "classifi
         o_label, o_prob = value_info("label", ["N"], INT64), value_info(prob, ["N", classes])
         outs = [o_label, o_prob] if output == "label" else [o_prob, o_label]
     return model("sklearn_pipeline", nodes, [], [value_info("X", ["N", features])], outs, opset=13, ml_opset=1)
+
+
+# ------------------------------------------------------------------------------------------
+# ai.onnx.ml tree ensembles (TreeEnsembleRegressor / TreeEnsembleClassifier, opsets 1 and 3)
+# ------------------------------------------------------------------------------------------
+
+TREE_MODES = ("BRANCH_LEQ", "BRANCH_LT", "BRANCH_GTE", "BRANCH_GT", "BRANCH_EQ", "BRANCH_NEQ")
+DOUBLE = 11
+
+
+def tensor_f64(name: str, arr) -> bytes:
+    """A DOUBLE TensorProto (raw_data): the *_as_tensor attributes of ai.onnx.ml opset 3."""
+    a = np.asarray(arr, dtype=np.float64).ravel()
+    return _vi(1, a.size) + _vi(2, DOUBLE) + _ld(9, a.astype("<f8").tobytes()) + _s(8, name)
+
+
+def attr_tensor(name: str, t: bytes) -> bytes:
+    return _s(1, name) + _ld(5, t) + _vi(20, 4)
+
+
+def tree_ensemble_spec(features: int = 30, trees: int = 10, depth: int = 6, kind: str = "regressor", targets: int = 1,
+                       labels: Sequence[int] | None = None, aggregate: str = "SUM", post: str = "NONE", ragged: bool = False,
+                       modes: Sequence[str] = ("BRANCH_LEQ",), missing: bool = False, as_tensor: bool = False,
+                       binary: str | None = None, base_values: bool = False, thresholds=None, pow2_leaves: bool = False,
+                       seed: int = 7) -> dict:
+    """Seeded tree ensemble as the attribute arrays an exporter writes.  Node ids are local to each tree and shuffled, and the
+    node entries of all trees are interleaved.  ragged: trees of a random shape with one path of `depth` levels (forest-like);
+    else full trees of `depth` levels (GBDT-like).  thresholds: a pool of values (e.g. values of the table) to draw from, else
+    U(-1, 1).  as_tensor: thresholds, weights and base values as double tensors, each threshold moved by a quarter f32 ulp off
+    its pool value (round-to-nearest would move it back and flip decisions).  binary: None, "signed" (GBDT/XGBoost log-odds
+    leaves, some negative) or "positive" (weights >= 0, NONE only): the single-column classifier form with two classes.
+    pow2_leaves: E = 1 leaves with distinct powers of two (every leaf choice readable from an exact sum; few leaves only)."""
+    rng = np.random.default_rng(seed)
+    cls = kind == "classifier"
+    E = len(labels) if cls and labels is not None else (2 if cls and binary else (3 if cls else targets))
+    labels = list(labels) if labels is not None else list(range(E))
+    pool = None if thresholds is None else np.asarray(thresholds, dtype=np.float32).ravel()
+    nodes = []  # (tree, id, feature, mode, value, true, false, missing)
+    leaves = []  # (tree, id, class/target, weight)
+    pow2 = 0
+    for t in range(trees):
+        shape = []  # per node: (depth, children or None)
+        def grow(d, spine):
+            i = len(shape)
+            shape.append(None)
+            split = d < depth and (not ragged or spine or (len(shape) < 4000 and rng.random() < (0.9 if d < 3 else 0.55)))
+            if split:
+                go_left = bool(rng.integers(2))
+                a = grow(d + 1, spine and go_left)
+                b = grow(d + 1, spine and not go_left)
+                shape[i] = (a, b)
+            return i
+        grow(0, True)
+        ids = rng.permutation(len(shape)) * 3 + 1  # local, shuffled, sparse
+        tid = t * 2 + 5
+        for i, ch in enumerate(shape):
+            if ch is None:
+                nodes.append((tid, int(ids[i]), 0, "LEAF", 0.0, 0, 0, 0))
+                if pow2_leaves:
+                    leaves.append((tid, int(ids[i]), 0, float(2.0 ** pow2)))
+                    pow2 += 1
+                    continue
+                r = rng.random()
+                if r < 0.08:
+                    continue  # a leaf with no entry contributes 0
+                if binary:
+                    w = rng.normal(0, 0.5) if binary == "signed" else rng.uniform(0, 1.0 / trees)
+                    leaves.append((tid, int(ids[i]), 1, float(w)))
+                    continue
+                for j in range(E):
+                    w = rng.uniform(0, 1) if cls else rng.normal(0, 1)
+                    leaves.append((tid, int(ids[i]), j, float(w)))
+                if r > 0.9:  # a repeated entry for one target: summed
+                    leaves.append((tid, int(ids[i]), int(rng.integers(E)), float(rng.normal(0, 0.5))))
+                continue
+            f = int(rng.integers(features))
+            v = float(pool[rng.integers(pool.size)]) if pool is not None else float(np.float32(rng.uniform(-1, 1)))
+            if as_tensor:
+                sp = float(np.spacing(np.float32(abs(v)) if v != 0 else np.float32(1e-30)))
+                v = v + (0.25 if rng.integers(2) else -0.25) * sp
+            mode = str(modes[rng.integers(len(modes))])
+            mv = int(rng.integers(2)) if missing else 0
+            nodes.append((tid, int(ids[i]), f, mode, v, int(ids[ch[0]]), int(ids[ch[1]]), mv))
+    order = rng.permutation(len(nodes))
+    nodes = [nodes[i] for i in order]
+    lorder = rng.permutation(len(leaves))
+    leaves = [leaves[i] for i in lorder]
+    spec = {
+        "kind": kind, "features": features, "E": E, "labels": labels, "aggregate": aggregate, "post": post,
+        "as_tensor": as_tensor, "missing": missing,
+        "nodes_treeids": [n[0] for n in nodes], "nodes_nodeids": [n[1] for n in nodes], "nodes_featureids": [n[2] for n in nodes],
+        "nodes_modes": [n[3] for n in nodes], "nodes_values": np.array([n[4] for n in nodes], dtype=np.float64),
+        "nodes_truenodeids": [n[5] for n in nodes], "nodes_falsenodeids": [n[6] for n in nodes],
+        "nodes_missing_value_tracks_true": [n[7] for n in nodes],
+        "leaf_treeids": [l[0] for l in leaves], "leaf_nodeids": [l[1] for l in leaves], "leaf_ids": [l[2] for l in leaves],
+        "leaf_weights": np.array([l[3] for l in leaves], dtype=np.float64),
+        "base_values": None,
+    }
+    if not as_tensor:  # f32 attributes: the values ARE f32
+        spec["nodes_values"] = spec["nodes_values"].astype(np.float32).astype(np.float64)
+        spec["leaf_weights"] = spec["leaf_weights"].astype(np.float32).astype(np.float64)
+    if base_values:
+        spec["base_values"] = np.array(rng.normal(0, 0.5, 1 if binary else E), dtype=np.float32).astype(np.float64)
+    return spec
+
+
+def tree_ensemble_from_spec(spec: dict, scaler: tuple | None = None, output: str = "label", ml_opset: int | None = None) -> bytes:
+    """The ONNX model of a tree_ensemble_spec() dict: [Scaler(offset, scale) ->] TreeEnsembleRegressor (output Y [N, E]) or
+    TreeEnsembleClassifier (label int64 [N], probabilities [N, E]; `output` = which of the two is graph output 0)."""
+    cls = spec["kind"] == "classifier"
+    F, E = spec["features"], spec["E"]
+    nodes, x = [], "X"
+    if scaler is not None:
+        nodes.append(node("Scaler", [x], ["Xs"], [attr_floats("offset", scaler[0]), attr_floats("scale", scaler[1])], domain=ML_DOMAIN))
+        x = "Xs"
+    at = bool(spec["as_tensor"])
+    def floats(name, vals):
+        return attr_tensor(name + "_as_tensor", tensor_f64("", vals)) if at else attr_floats(name, np.asarray(vals, dtype=np.float32))
+    attrs = [attr_ints("nodes_treeids", spec["nodes_treeids"]), attr_ints("nodes_nodeids", spec["nodes_nodeids"]),
+             attr_ints("nodes_featureids", spec["nodes_featureids"]), attr_strings("nodes_modes", spec["nodes_modes"]),
+             floats("nodes_values", spec["nodes_values"]), attr_ints("nodes_truenodeids", spec["nodes_truenodeids"]),
+             attr_ints("nodes_falsenodeids", spec["nodes_falsenodeids"]),
+             attr_s("aggregate_function", spec["aggregate"]), attr_s("post_transform", spec["post"])]
+    if spec["missing"]:
+        attrs.append(attr_ints("nodes_missing_value_tracks_true", spec["nodes_missing_value_tracks_true"]))
+    p = "class_" if cls else "target_"
+    attrs += [attr_ints(p + "treeids", spec["leaf_treeids"]), attr_ints(p + "nodeids", spec["leaf_nodeids"]),
+              attr_ints(p + "ids", spec["leaf_ids"]), floats(p + "weights", spec["leaf_weights"])]
+    if spec["base_values"] is not None:
+        attrs.append(floats("base_values", spec["base_values"]))
+    if cls:
+        attrs.append(attr_ints("classlabels_int64s", spec["labels"]))
+        nodes.append(node("TreeEnsembleClassifier", [x], ["label", "probabilities"], attrs, domain=ML_DOMAIN))
+        o_label, o_prob = value_info("label", ["N"], INT64), value_info("probabilities", ["N", E])
+        outs = [o_label, o_prob] if output == "label" else [o_prob, o_label]
+    else:
+        attrs.append(attr_i("n_targets", E))
+        nodes.append(node("TreeEnsembleRegressor", [x], ["Y"], attrs, domain=ML_DOMAIN))
+        outs = [value_info("Y", ["N", E])]
+    return model("tree_ensemble", nodes, [], [value_info("X", ["N", F])], outs, opset=13,
+                 ml_opset=ml_opset if ml_opset is not None else (3 if at else 1))
+
+
+def tree_ensemble(scaler: tuple | None = None, output: str = "label", **kw) -> bytes:
+    """Seeded TreeEnsembleRegressor / TreeEnsembleClassifier model (keywords: tree_ensemble_spec)."""
+    return tree_ensemble_from_spec(tree_ensemble_spec(**kw), scaler=scaler, output=output)
