@@ -222,6 +222,13 @@ void PassRunner::launch_plain(size_t i) {
       kern::tree_reduce(stream, buf(x.in0), d.bias, d.cst, buf(x.out), nr, int(x.tree_W), int(x.tree_slices), x.tree_count, x.tree_average, x.tree_mode,
                         x.tree_signed);
       break;
+    case StepKind::SvmKernel:
+      kern::svm_kernel(stream, buf(x.in0), int(p.buf_per_row[size_t(x.in0)]), int(x.svm_F_pad), x.svm_kernel, d.bias, d.W, d.shift, d.scale, d.tab,
+                       buf(x.out), nr, int(x.svm_slices), int(x.svm_Q), int(x.svm_QW), x.svm_gamma, x.svm_coef0, x.svm_degree);
+      break;
+    case StepKind::SvmReduce:
+      kern::svm_reduce(stream, buf(x.in0), d.tab, d.bias, d.cst, d.scale, d.shift, buf(x.out), nr, int(x.svm_Q), int(x.svm_classes), x.svm_mode);
+      break;
   }
 }
 

@@ -58,6 +58,14 @@ void tree_walk(hipStream_t s, const float *x, int F, const uint32_t *tab, int64_
 void tree_reduce(hipStream_t s, const float *part, const float *base, const float *labels, float *y, int64_t rows, int W, int S, int64_t n_trees,
                  bool average, int mode, bool is_signed);
 
+// ---- support-vector machines (svm.hip) ---------------------------------------------------------
+// part[S][rows][Q] = per-slice sums  sum_s coef[q][s] * K(x, s)  for x [rows, F]; tables: host/svm.hpp SvmPack (kernel: SvmKernelType)
+void svm_kernel(hipStream_t s, const float *x, int F, int F_pad, int kernel, const float *center, const float *sv, const float *sv_norm, const float *coef,
+                const uint32_t *slice_tile, float *part, int64_t rows, int S, int Q, int QW, float gamma, float coef0, int degree);
+// the slices of each class summed in slice order, + rho -> a host/plan.hpp SvmOut form
+void svm_reduce(hipStream_t s, const float *part, const uint32_t *class_slice, const float *rho, const float *labels, const float *prob_a,
+                const float *prob_b, float *y, int64_t rows, int Q, int C, int mode);
+
 // ---- dense layer, fp32 MFMA (dense.hip) -------------------------------------------------------
 // Y[rows, M] = act(X[rows, K] . W[K, M] + bias[M]); W row-major, bias may be null.
 // softmax_fused: apply a row softmax over the M outputs in the epilogue (requires M <= 256).

@@ -411,9 +411,9 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
         if (std::find(e.reads.begin(), e.reads.end(), 0) == e.reads.end()) continue;
         // ... and that kernel streams it about once (a windowed kernel would fetch a small image over PCIe once per tap)
         const StepKind sk = st[size_t(e.idx)].kind;
-        // (a tree walk reads its row tile once per tree slice, and wide rows feature by feature)
+        // (a tree walk reads its row tile once per tree slice, and wide rows feature by feature; an SVM once per SV slice)
         const bool windowed = (sk == StepKind::Conv2d && m.exec[size_t(e.idx)] != ExecKind::ConvPatch) || sk == StepKind::Pool2d || sk == StepKind::LRN ||
-                              sk == StepKind::TreeEnsemble;
+                              sk == StepKind::TreeEnsemble || sk == StepKind::SvmKernel;
         m.in_single_reader = !windowed;
         break;
       }

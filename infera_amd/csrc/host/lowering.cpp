@@ -22,6 +22,7 @@
 
 #include "common.hpp"
 #include "plan.hpp"
+#include "svm.hpp"
 #include "trees.hpp"
 
 namespace infera_hip {
@@ -1426,9 +1427,78 @@ struct Lowerer {
       ml_post_transform(n, raw, cls ? n.outputs[1] : n.outputs[0]);
     }
   }
+  // SVMRegressor / SVMClassifier: an SvmKernel step (X . S^T on the matrix cores, the kernel function, times the coefficients: per-slice
+  // partial sums) and an SvmReduce step (slices summed in fixed order, rho, then the value, one-class sign, pairwise decisions, votes and
+  // label, or Platt + pairwise coupling), then post_transform on the scores
+  void svm(const NodeDef &n) {
+    SvmPack sp;
+    const Val &x = get(n, 0);
+    if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, features] activations");
+    try {
+      sp = pack_svm(n, x.shape[1]);
+    } catch (const SvmError &e) {
+      unsupported(n, e.what());
+    }
+    const int64_t rows = x.shape[0], C = sp.classes, P = C * (C - 1) / 2;
+    const bool cls = sp.classifier;
+    const bool want_label = cls && wanted(n, 0), want_scores = cls ? wanted(n, 1) : true;
+    const int score_mode = !cls ? (sp.one_class ? kSvmOneClass : kSvmValue) : sp.probabilities ? kSvmProb : kSvmDecision;
+    const int64_t score_cols = !cls ? 1 : sp.probabilities ? C : (C == 2 ? 2 : P);
+    auto fields = [&](Step &s, int mode) {
+      s.svm_kernel = sp.kernel;
+      s.svm_mode = mode;
+      s.svm_degree = sp.degree;
+      s.svm_gamma = sp.gamma;
+      s.svm_coef0 = sp.coef0;
+      s.svm_F = sp.F;
+      s.svm_F_pad = sp.F_pad;
+      s.svm_n_sv = sp.n_sv;
+      s.svm_tiles = sp.tiles;
+      s.svm_Q = sp.Q;
+      s.svm_QW = sp.QW;
+      s.svm_prob = sp.probabilities;
+      s.svm_slices = sp.slices;
+      s.svm_classes = C;
+    };
+    Step k;
+    k.kind = StepKind::SvmKernel;
+    k.in0 = x.buf;
+    fields(k, want_scores ? score_mode : kSvmLabel);
+    k.W = std::move(sp.sv);
+    k.scale = std::move(sp.coef);
+    k.shift = std::move(sp.sv_norm);
+    k.bias = std::move(sp.center);
+    k.tree_tab = std::move(sp.slice_tile);
+    const std::string tmp = n.outputs[0] + "\x01";
+    NodeDef kn = n;
+    kn.outputs = {tmp + "partial"};
+    const int part = emit(std::move(k), kn, {rows, sp.slices * sp.Q}).out;
+    auto reduce = [&](int mode, const std::string &out, int64_t cols) {
+      Step r;
+      r.kind = StepKind::SvmReduce;
+      r.in0 = part;
+      fields(r, mode);
+      r.bias = sp.rho;
+      r.cst = sp.labels;
+      r.scale = sp.prob_a;
+      r.shift = sp.prob_b;
+      r.tree_tab = sp.class_slice;
+      NodeDef d = n;
+      d.outputs = {out};
+      return emit(std::move(r), d, cols ? std::vector<int64_t>{rows, cols} : std::vector<int64_t>{rows}).out;
+    };
+    if (want_label) int_bufs.insert(reduce(kSvmLabel, n.outputs[0], 0));
+    if (want_scores) {
+      const std::string raw = tmp + "raw";
+      uses[raw] = 1;
+      reduce(score_mode, raw, score_cols);
+      ml_post_transform(n, raw, cls ? n.outputs[1] : n.outputs[0]);
+    }
+  }
   void ml_node(const NodeDef &n) {
     if (n.op == "ArrayFeatureExtractor") return array_feature_extractor(n);
     if (n.op == "TreeEnsembleRegressor" || n.op == "TreeEnsembleClassifier") return tree_ensemble(n);
+    if (n.op == "SVMRegressor" || n.op == "SVMClassifier") return svm(n);
     const Val &x = get(n, 0);
     if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, features] activations");
     const int64_t F = x.shape[1];
@@ -1622,12 +1692,13 @@ double Plan::flops_per_row() const {
   for (const auto &s : steps) {
     if (s.kind == StepKind::Dense) f += 2.0 * double(s.K) * double(s.M);
     else if (s.kind == StepKind::Conv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
+    else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm_n_sv) * double(s.svm_F + s.svm_Q);  // X . S^T, then the coefficients
   }
   return f;
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -1646,6 +1717,11 @@ std::string Plan::describe_json() const {
       if (s.kind == StepKind::TreeEnsemble)
         o << ",\"trees\":" << s.tree_count << ",\"nodes\":" << s.tree_nodes << ",\"max_depth\":" << s.tree_max_depth << ",\"walk_width\":" << s.tree_W
           << ",\"aggregate\":\"" << (s.tree_average ? "AVERAGE" : "SUM") << "\"";
+    }
+    if (s.kind == StepKind::SvmKernel || s.kind == StepKind::SvmReduce) {
+      static const char *kernels[] = {"LINEAR", "POLY", "RBF", "SIGMOID"}, *modes[] = {"value", "one_class", "label", "decision", "probabilities"};
+      o << ",\"kernel\":\"" << kernels[s.svm_kernel] << "\",\"support_vectors\":" << s.svm_n_sv << ",\"F\":" << s.svm_F << ",\"classes\":" << s.svm_classes
+        << ",\"slices\":" << s.svm_slices << ",\"output\":\"" << modes[s.svm_mode] << "\",\"probabilities\":" << (s.svm_prob ? "true" : "false");
     }
     if (s.act != Act::None) o << ",\"act\":\"" << acts[int(s.act)] << "\"";
     o << ",\"origin\":" << json_str(s.origin) << "}";

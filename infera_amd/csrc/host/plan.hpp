@@ -44,10 +44,18 @@ enum class StepKind : int {
   PadCols = 12,     // out[r, 0:K] = in0[r, :], zeros up to M columns   (row length -> multiple of 4 for the 16-byte loads of the MFMA kernels)
   TreeEnsemble = 15,  // ai.onnx.ml tree walk: out = per-slice partial sums, f64 as f32 pairs: [rows][2 * tree_slices * tree_W] (slice-major inside the pass, trees.hip)
   TreeReduce = 16,    // in0 = those partials -> scores [rows, E] (AVERAGE, base_values, binary expansion) or the class label [rows]
+  SvmKernel = 17,     // ai.onnx.ml SVM: out = per-slice sums  sum_s coef[q][s] * K(x, s)  over each SV slice: [svm_slices][rows][svm_Q] (svm.hip)
+  SvmReduce = 18,     // in0 = those partials -> regressor value / one-class sign, pairwise decisions, label or probabilities (SvmOut)
 };
 
 // TreeReduce output modes (Step::tree_mode)
 enum TreeOut : int { kTreeScores = 0, kTreeLabel = 1, kTreeBinaryScores = 2, kTreeBinaryLabel = 3 };
+
+// SvmReduce output modes (Step::svm_mode): regressor value [rows, 1], one-class +-1 [rows, 1], class label [rows], pairwise
+// decisions [rows, P] (binary: [d, -d]), probabilities [rows, C]
+enum SvmOut : int { kSvmValue = 0, kSvmOneClass = 1, kSvmLabel = 2, kSvmDecision = 3, kSvmProb = 4 };
+// SVM kernel types (Step::svm_kernel)
+enum SvmKernelType : int { kSvmLinear = 0, kSvmPoly = 1, kSvmRbf = 2, kSvmSigmoid = 3 };
 
 struct Step {
   StepKind kind = StepKind::Unary;
@@ -83,6 +91,14 @@ struct Step {
   int64_t tree_count = 0, tree_nodes = 0, tree_max_depth = 0, tree_W = 0, tree_E = 0, tree_slices = 1;
   int tree_mode = kTreeScores;
   bool tree_average = false, tree_signed = false;  // AVERAGE aggregation; binary form with a negative weight ([-s, s], label s > 0)
+  // SvmKernel / SvmReduce (host/svm.hpp packs the tables).  SvmKernel: W = support vectors in MFMA fragment order, scale = coefficients
+  // in the stage-2 layout, shift = |s|^2 (RBF), bias = the load-time center (RBF), tree_tab = first SV tile per slice (svm_slices + 1).
+  // SvmReduce: bias = rho, cst = class labels, scale / shift = prob_a / prob_b, tree_tab = first slice per class (svm_classes + 1).
+  int svm_kernel = kSvmLinear, svm_mode = kSvmValue, svm_degree = 1;
+  float svm_gamma = 0.f, svm_coef0 = 0.f;
+  int64_t svm_F = 0, svm_F_pad = 0, svm_n_sv = 0, svm_tiles = 0, svm_Q = 1, svm_slices = 1, svm_classes = 1;
+  int64_t svm_QW = 1;      // stage-2 width (host/svm.hpp SvmPack::QW)
+  bool svm_prob = false;  // the model has prob_a / prob_b
   std::string origin;  // ONNX node names/ops this step came from (diagnostics)
 };
 

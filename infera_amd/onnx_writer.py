@@ -669,3 +669,80 @@ def tree_ensemble_from_spec(spec: dict, scaler: tuple | None = None, output: str
 def tree_ensemble(scaler: tuple | None = None, output: str = "label", **kw) -> bytes:
     """Seeded TreeEnsembleRegressor / TreeEnsembleClassifier model (keywords: tree_ensemble_spec)."""
     return tree_ensemble_from_spec(tree_ensemble_spec(**kw), scaler=scaler, output=output)
+
+
+# ------------------------------------------------------------------------------------------
+# ai.onnx.ml support-vector machines (SVMRegressor / SVMClassifier)
+# ------------------------------------------------------------------------------------------
+
+SVM_KERNELS = ("LINEAR", "POLY", "RBF", "SIGMOID")
+
+
+def svm_spec(features: int = 30, n_sv: int = 256, kind: str = "classifier", classes: int = 3, kernel: str = "RBF",
+             probabilities: bool = False, post: str = "NONE", per_class: Sequence[int] | None = None,
+             labels: Sequence[int] | None = None, gamma: float | None = None, coef0: float = 0.5, degree: int = 3,
+             offset: float = 0.0, seed: int = 7) -> dict:
+    """Seeded SVM as the attribute arrays an exporter writes (libsvm's one-vs-one layout for the classifier).  kind: "regressor",
+    "one_class" or "classifier".  per_class: SVs per class block (default: n_sv spread unevenly over the classes).  Support vectors
+    are offset + N(0, 1) in f32; gamma defaults to 1 / features.  Every value is f32, as the attributes store it."""
+    rng = np.random.default_rng(seed)
+    cls = kind == "classifier"
+    C = classes if cls else 1
+    if cls and per_class is None:
+        w = rng.uniform(0.5, 1.5, C)
+        per_class = np.maximum(1, np.floor(w / w.sum() * n_sv)).astype(int)
+        per_class[-1] = max(1, n_sv - int(per_class[:-1].sum()))
+    per_class = [int(v) for v in per_class] if cls else [n_sv]
+    n_sv = int(sum(per_class))
+    f32 = lambda a: np.asarray(a, dtype=np.float32)  # noqa: E731
+    g = float(np.float32(1.0 / features if gamma is None else gamma))
+    Q = C - 1 if cls else 1
+    P = C * (C - 1) // 2 if cls else 1
+    spec = {
+        "kind": kind, "features": features, "kernel": kernel, "post": post, "classes": C,
+        "labels": list(labels) if labels is not None else list(range(C)),
+        "vectors_per_class": per_class, "n_sv": n_sv,
+        "support_vectors": f32(offset + rng.normal(0, 1, (n_sv, features))),
+        "coefficients": f32(rng.normal(0, 1, (Q, n_sv))),
+        "rho": f32(rng.normal(0, 0.5, P)),
+        "kernel_params": f32([g, coef0, degree]),
+        "prob_a": f32(-rng.uniform(0.5, 2.0, P)) if (cls and probabilities) else None,
+        "prob_b": f32(rng.normal(0, 0.2, P)) if (cls and probabilities) else None,
+    }
+    if kind == "one_class":
+        spec["coefficients"] = f32(np.abs(spec["coefficients"]))
+    return spec
+
+
+def svm_from_spec(spec: dict, scaler: tuple | None = None, output: str = "label") -> bytes:
+    """The ONNX model of an svm_spec() dict (or of the same keys taken from a fitted estimator): [Scaler(offset, scale) ->]
+    SVMRegressor (output Y [N, 1]) or SVMClassifier (label int64 [N], probabilities [N, *]; `output` = which is graph output 0)."""
+    cls = spec["kind"] == "classifier"
+    F = spec["features"]
+    nodes, x = [], "X"
+    if scaler is not None:
+        nodes.append(node("Scaler", [x], ["Xs"], [attr_floats("offset", scaler[0]), attr_floats("scale", scaler[1])], domain=ML_DOMAIN))
+        x = "Xs"
+    attrs = [attr_s("kernel_type", spec["kernel"]), attr_floats("kernel_params", spec["kernel_params"]),
+             attr_floats("support_vectors", np.asarray(spec["support_vectors"], dtype=np.float32).ravel()),
+             attr_floats("coefficients", np.asarray(spec["coefficients"], dtype=np.float32).ravel()),
+             attr_floats("rho", np.asarray(spec["rho"], dtype=np.float32).ravel()), attr_s("post_transform", spec["post"])]
+    if cls:
+        attrs += [attr_ints("vectors_per_class", spec["vectors_per_class"]), attr_ints("classlabels_ints", spec["labels"])]
+        if spec.get("prob_a") is not None:
+            attrs += [attr_floats("prob_a", spec["prob_a"]), attr_floats("prob_b", spec["prob_b"])]
+        C = spec["classes"]
+        cols = C if spec.get("prob_a") is not None else (2 if C == 2 else C * (C - 1) // 2)
+        nodes.append(node("SVMClassifier", [x], ["label", "probabilities"], attrs, domain=ML_DOMAIN))
+        o_label, o_prob = value_info("label", ["N"], INT64), value_info("probabilities", ["N", cols])
+        outs = [o_label, o_prob] if output == "label" else [o_prob, o_label]
+    else:
+        attrs += [attr_i("n_supports", spec["n_sv"]), attr_i("one_class", 1 if spec["kind"] == "one_class" else 0)]
+        nodes.append(node("SVMRegressor", [x], ["Y"], attrs, domain=ML_DOMAIN))
+        outs = [value_info("Y", ["N", 1])]
+    return model("svm", nodes, [], [value_info("X", ["N", F])], outs, opset=13, ml_opset=1)
+
+
+def svm(scaler: tuple | None = None, output: str = "label", **kw) -> bytes:
+    """Seeded SVMRegressor / SVMClassifier model (keywords: svm_spec)."""
+    return svm_from_spec(svm_spec(**kw), scaler=scaler, output=output)
