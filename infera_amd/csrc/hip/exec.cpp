@@ -229,6 +229,10 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::SvmReduce:
       kern::svm_reduce(stream, buf(x.in0), d.tab, d.bias, d.cst, d.scale, d.shift, buf(x.out), nr, int(x.svm_Q), int(x.svm_classes), x.svm_mode);
       break;
+    case StepKind::Prep:
+      kern::prep(stream, buf(x.in0), int(x.prep_F_in), d.tab, d.scale, d.W, int(x.W.size() / 2), buf(x.out), int(x.prep_F), nr, int(x.prep_R),
+                 x.prep_strict ? ctx.prep_err : nullptr);
+      break;
   }
 }
 
@@ -241,6 +245,12 @@ void exec_plan(const LoadedModel &m, const DeviceModel &dm, ThreadCtx &ctx, cons
     return;
   }
   const int64_t rows_pass = prepare_scratch(m, ctx, rows);
+  // a plan with a zeros = 0 OneHotEncoder: the call's failure word, cleared on the call's stream and read back with the result
+  const bool strict = !p.prep_strict_nodes.empty();
+  if (strict) {
+    ctx.ensure_prep_err();
+    HIP_TRY(hipMemsetAsync(ctx.prep_err, 0, sizeof(int), ctx.stream));
+  }
   // a column-major chunk [K][rows] cannot be cut into row passes (pass r0 would start at a row-major offset with stride nr):
   // callers check single_pass() first and stage such calls row-major instead; this guards every kernel family at once
   if (in_colmajor && rows_pass != rows) throw InferaError::onnx("internal: column-major input needs a single pass");
@@ -276,6 +286,14 @@ void exec_plan(const LoadedModel &m, const DeviceModel &dm, ThreadCtx &ctx, cons
         if (ls) (void)hipStreamSynchronize(ls);
       throw;
     }
+  }
+  if (strict) {
+    int word = 0;
+    HIP_TRY(hipMemcpyAsync(&word, ctx.prep_err, sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    if (word > 0)
+      throw InferaError::onnx(p.prep_strict_nodes[size_t(std::min<int>(word, int(p.prep_strict_nodes.size()))) - 1] +
+                              ": a value is not in cats_int64s (zeros = 0)");
   }
 }
 

@@ -94,7 +94,8 @@ struct HostCall {
   ThreadCtx &ctx;
   const DeviceModel &dm;
   const size_t in_row, out_row, widest;  // bytes per row
-  const bool use_graph = Config::get().use_hipgraph;
+  // (not for a plan with a zeros = 0 OneHotEncoder: its failure word is read back inside exec_plan, which a capture cannot)
+  const bool use_graph = Config::get().use_hipgraph && m.plan.prep_strict_nodes.empty();
 
   HostCall(const LoadedModel &model, const FillFn &f, const DeviceFillFn *df, float *out, int64_t n, bool cm, int sl, ThreadCtx &c)
       : m(model), fill(f), dfill(df), h_out(out), rows(n), col_major(cm), slot(sl), ctx(c), dm(device_model(model, sl)),

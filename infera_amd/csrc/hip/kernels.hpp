@@ -66,6 +66,12 @@ void svm_kernel(hipStream_t s, const float *x, int F, int F_pad, int kernel, con
 void svm_reduce(hipStream_t s, const float *part, const uint32_t *class_slice, const float *rho, const float *labels, const float *prob_a,
                 const float *prob_b, float *y, int64_t rows, int Q, int C, int mode);
 
+// ---- preprocessing regions (prep.hip) -----------------------------------------------------------
+// y[r, j] = column program j (host/prep.hpp PrepPack: desc, cst, tab of ntab pairs) over x[r, 0:F_in], R rows per block tile; err: the call's failure
+// word (plans with a zeros = 0 OneHotEncoder only, else null), set to the encoder's 1-based id on a value outside its categories
+void prep(hipStream_t s, const float *x, int F_in, const uint32_t *desc, const float *cst, const float *tab, int ntab, float *y, int F, int64_t rows,
+          int R, int *err);
+
 // ---- dense layer, fp32 MFMA (dense.hip) -------------------------------------------------------
 // Y[rows, M] = act(X[rows, K] . W[K, M] + bias[M]); W row-major, bias may be null.
 // softmax_fused: apply a row softmax over the M outputs in the epilogue (requires M <= 256).

@@ -203,6 +203,14 @@ struct ThreadCtx {
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), bytes));
     cap = bytes;
   }
+  // the failure word of a call through a plan with a zeros = 0 OneHotEncoder (exec_plan clears, prep.hip sets, exec_plan reads it)
+  int *prep_err = nullptr;
+  size_t prep_err_cap = 0;
+  void ensure_prep_err() {
+    float *p = reinterpret_cast<float *>(prep_err);
+    ensure_dev(p, prep_err_cap, sizeof(int));
+    prep_err = reinterpret_cast<int *>(p);
+  }
 };
 
 // ---- context.cpp ------------------------------------------------------------------------------------------------------------

@@ -22,6 +22,7 @@
 
 #include "common.hpp"
 #include "plan.hpp"
+#include "prep.hpp"
 #include "svm.hpp"
 #include "trees.hpp"
 
@@ -32,8 +33,17 @@ namespace {
 using onnx::NodeDef;
 using onnx::TensorData;
 
+// A value inside a preprocessing region (host/prep.hpp): not computed yet -- one column program per column over the rows of buffer
+// `src`.  It becomes a buffer (one Prep step, a SliceCols, or the source itself) where something outside the region reads it.
+struct PrepVal {
+  int src = -1;
+  std::vector<PrepCol> cols;
+  std::vector<std::string> origin;  // the ONNX nodes absorbed so far
+};
+
 struct Val {
   bool is_const = false;
+  std::shared_ptr<const PrepVal> pv;  // set: a preprocessing-region value (buf = -1)
   std::shared_ptr<TensorData> c;
   int buf = -1;
   std::vector<int64_t> shape;  // activations: dim0 = -1 (symbolic rows) or fixed batch
@@ -107,7 +117,13 @@ struct Lowerer {
     return int(plan.buf_shape.size()) - 1;
   }
 
+  // input i of n; a preprocessing-region value is materialised first (get_raw: as it is)
   const Val &get(const NodeDef &n, size_t i) {
+    const Val &v = get_raw(n, i);
+    if (v.pv) materialize(n.inputs[i], &n);
+    return v;
+  }
+  const Val &get_raw(const NodeDef &n, size_t i) {
     if (i >= n.inputs.size() || n.inputs[i].empty()) unsupported(n, "missing input " + std::to_string(i));
     auto it = vals.find(n.inputs[i]);
     if (it != vals.end()) return it->second;
@@ -843,15 +859,26 @@ struct Lowerer {
   }
 
   void alias(const NodeDef &n, const std::vector<int64_t> &new_shape) {
-    const Val &a = get(n, 0);
+    const Val &a = get_raw(n, 0);
     if (prod(new_shape, 1) != prod(a.shape, 1) || new_shape.empty() || new_shape[0] != a.shape[0])
       unsupported(n, "reshape " + shape_str(a.shape) + " -> " + shape_str(new_shape) + " does not preserve the row axis");
+    if (a.pv) {  // (a preprocessing-region value: the same columns under another shape)
+      Val v = a;
+      v.shape = new_shape;
+      if (n.op != "Identity") {
+        PrepVal p = *a.pv;
+        add_origin(p, n);
+        v.pv = std::make_shared<const PrepVal>(std::move(p));
+      }
+      vals[n.outputs[0]] = v;
+      return;
+    }
     int buf = a.buf;
     set_act(n, buf, new_shape, true);
   }
 
   void reshape_like(const NodeDef &n) {
-    const Val &a = get(n, 0);
+    const Val &a = get_raw(n, 0);
     if (a.is_const) {
       if (n.op == "Identity") { vals[n.outputs[0]] = a; return; }
       if ((n.op == "Unsqueeze" || n.op == "Squeeze") && a.shape.size() <= 1) {  // scalar <-> [1] in shape sub-graphs
@@ -1495,10 +1522,25 @@ struct Lowerer {
       ml_post_transform(n, raw, cls ? n.outputs[1] : n.outputs[0]);
     }
   }
+  // ZipMap (probabilities -> a sequence of maps), when its output is the one served: the C ABI carries f32 rows, so the probabilities
+  // [rows, C] it reads are served, one column per class in classlabels order (get_model_info says so)
+  void zipmap(const NodeDef &n) {
+    const Val &x = get(n, 0);
+    if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, classes] probabilities");
+    size_t labels = 0;
+    if (const onnx::Attribute *a = n.attr("classlabels_int64s")) labels = a->ints.size();
+    if (const onnx::Attribute *a = n.attr("classlabels_strings")) labels = std::max(labels, a->strings.size());
+    if (int64_t(labels) != x.shape[1])
+      unsupported(n, "classlabels hold " + std::to_string(labels) + " labels for " + std::to_string(x.shape[1]) + " probability columns");
+    const std::vector<int64_t> shape = x.shape;
+    set_act(n, x.buf, shape, true);
+    if (n.outputs[0] == m.outputs[out_index].name) plan.output_zipmap = true;
+  }
   void ml_node(const NodeDef &n) {
     if (n.op == "ArrayFeatureExtractor") return array_feature_extractor(n);
     if (n.op == "TreeEnsembleRegressor" || n.op == "TreeEnsembleClassifier") return tree_ensemble(n);
     if (n.op == "SVMRegressor" || n.op == "SVMClassifier") return svm(n);
+    if (n.op == "ZipMap") return zipmap(n);
     const Val &x = get(n, 0);
     if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, features] activations");
     const int64_t F = x.shape[1];
@@ -1567,11 +1609,426 @@ struct Lowerer {
     }
   }
 
+  // ---- ai.onnx.ml preprocessing regions (host/prep.hpp).  A region is a connected set of Imputer / Scaler / Binarizer / OneHotEncoder /
+  // LabelEncoder / FeatureVectorizer / ArrayFeatureExtractor (constant indices) / Cast / Reshape / Flatten / Squeeze / Concat / Identity
+  // nodes and graph inputs that holds at least one thing nothing else serves: one of the five encoder nodes, a non-contiguous
+  // ArrayFeatureExtractor or an integer graph input.  Graphs without one lower exactly as before.  Inside a region every value is a
+  // list of column programs over one source buffer (PrepVal); where anything else reads a region value it becomes ONE Prep step.
+  std::vector<char> region;                           // node index -> lowered as part of a region
+  std::vector<std::shared_ptr<PrepTable>> prep_tables;  // LabelEncoder tables and strict one-hot category sets, by id
+  int64_t prep_cats = 0, prep_keys = 0;                 // one-hot categories / LabelEncoder keys in all (caps)
+
+  static bool prep_encoder(const std::string &op) {
+    return op == "Imputer" || op == "Binarizer" || op == "OneHotEncoder" || op == "LabelEncoder" || op == "FeatureVectorizer";
+  }
+  bool const_name(const std::string &v, const std::map<std::string, size_t> &prod_of) const {
+    if (m.initializers.count(v)) return true;
+    auto it = prod_of.find(v);
+    return it != prod_of.end() && m.nodes[it->second].op == "Constant";
+  }
+  // marks `region`; returns the graph inputs that start inside a region
+  std::set<std::string> find_regions(const std::vector<char> &live) {
+    const size_t N = m.nodes.size(), M = m.inputs.size();
+    std::map<std::string, size_t> prod_of;
+    for (size_t i = 0; i < N; i++)
+      for (const auto &o : m.nodes[i].outputs) prod_of[o] = i;
+    std::map<std::string, size_t> input_of;
+    for (size_t j = 0; j < M; j++) input_of[m.inputs[j].name] = j;
+    std::set<std::string> act;  // names that hold row data
+    for (const auto &v : m.inputs) act.insert(v.name);
+    std::vector<char> elig(N, 0), trig(N + M, 0);
+    std::vector<size_t> uf(N + M);
+    std::iota(uf.begin(), uf.end(), size_t(0));
+    std::function<size_t(size_t)> find = [&](size_t a) { return uf[a] == a ? a : uf[a] = find(uf[a]); };
+    auto from_region = [&](const std::string &v) {  // a graph input or an eligible node's output
+      auto p = prod_of.find(v);
+      return input_of.count(v) || (p != prod_of.end() && elig[p->second]);
+    };
+    for (size_t i = 0; i < N; i++) {
+      if (!live[i]) continue;
+      const NodeDef &n = m.nodes[i];
+      bool any_act = false;
+      for (const auto &in : n.inputs) any_act = any_act || act.count(in);
+      if (!any_act) continue;
+      if (n.op != "Shape")
+        for (const auto &o : n.outputs) act.insert(o);
+      const bool ml = n.domain == "ai.onnx.ml", std_dom = n.domain.empty() || n.domain == "ai.onnx";
+      const bool data_act = !n.inputs.empty() && act.count(n.inputs[0]);
+      bool e = false, t = false;
+      if (ml && n.op == "ArrayFeatureExtractor") {
+        e = data_act && n.inputs.size() == 2 && const_name(n.inputs[1], prod_of);
+        if (e) {  // non-contiguous constant indices: nothing else serves them
+          auto ci = m.initializers.find(n.inputs[1]);
+          if (ci != m.initializers.end() && ci->second->dtype == onnx::kInt64) {
+            const auto &v = ci->second->i64;
+            for (size_t k = 1; k < v.size(); k++) t = t || v[k] != v[0] + int64_t(k);
+          } else {
+            t = true;  // (a Constant node's list: checked when lowered)
+          }
+        }
+      } else if (ml && (prep_encoder(n.op) || n.op == "Scaler")) {
+        e = data_act;
+        t = e && n.op != "Scaler";
+      } else if (std_dom && (n.op == "Cast" || n.op == "Reshape" || n.op == "Flatten" || n.op == "Squeeze" || n.op == "Identity")) {
+        e = data_act;
+      } else if (std_dom && n.op == "Concat") {
+        e = true;
+        for (const auto &in : n.inputs) e = e && act.count(in) && from_region(in);
+      }
+      if (!e) continue;
+      elig[i] = 1;
+      if (t) trig[i] = 1;
+      for (const auto &in : n.inputs) {
+        if (!act.count(in)) continue;
+        auto ij = input_of.find(in);
+        auto p = prod_of.find(in);
+        if (ij != input_of.end()) uf[find(i)] = find(N + ij->second);
+        else if (p != prod_of.end() && elig[p->second]) uf[find(i)] = find(p->second);
+      }
+    }
+    for (size_t j = 0; j < M; j++)
+      if (m.inputs[j].elem_type == onnx::kInt64 || m.inputs[j].elem_type == onnx::kInt32) trig[N + j] = 1;
+    std::vector<char> hot(N + M, 0);
+    for (size_t a = 0; a < N + M; a++)
+      if (trig[a]) hot[find(a)] = 1;
+    region.assign(N, 0);
+    for (size_t i = 0; i < N; i++) region[i] = elig[i] && hot[find(i)];
+    std::set<std::string> ins;
+    for (size_t j = 0; j < M; j++)
+      if (hot[find(N + j)]) ins.insert(m.inputs[j].name);
+    return ins;
+  }
+
+  // identity columns over buffer `buf` (a region value's source); is_int: whole numbers already
+  static PrepVal prep_identity(int buf, int64_t off, int64_t width, bool trunc, bool is_int) {
+    PrepVal p;
+    p.src = buf;
+    for (int64_t j = 0; j < width; j++) {
+      PrepCol c;
+      c.src = off + j;
+      c.trunc = trunc;
+      c.is_int = is_int || trunc;
+      p.cols.push_back(c);
+    }
+    return p;
+  }
+  void set_prep(const std::string &name, PrepVal p, std::vector<int64_t> shape) {
+    if (int64_t(p.cols.size()) > kPrepMaxOut)
+      throw InferaError::onnx("value '" + name + "' has " + std::to_string(p.cols.size()) + " columns; a preprocessing step writes at most " +
+                              std::to_string(kPrepMaxOut));
+    Val v;
+    v.pv = std::make_shared<const PrepVal>(std::move(p));
+    v.shape = std::move(shape);
+    vals[name] = v;
+  }
+  // input i of a region node as columns: a region value as it is, an activation as identity columns over its buffer.  Columns that
+  // already went past `stage` (an Imputer behind a Scaler, ...) are materialised first, and the program starts again on that buffer.
+  PrepVal prep_in(const NodeDef &n, size_t i, int stage) {
+    const Val *v = &get_raw(n, i);
+    if (v->is_const) unsupported(n, "expected row data, got a constant");
+    if (v->pv) {
+      bool clash = false;
+      for (const PrepCol &c : v->pv->cols) clash = clash || c.stage() >= stage;
+      if (!clash) return *v->pv;
+      v = &get(n, i);
+    }
+    if (v->padded()) unsupported(n, "the output of a Pad node can only feed a Conv");
+    PrepVal p = prep_identity(v->buf, 0, plan.buf_per_row[size_t(v->buf)], false, int_bufs.count(v->buf) > 0);
+    return p;
+  }
+  static void add_origin(PrepVal &p, const NodeDef &n) {
+    const std::string o = n.op + (n.name.empty() ? "" : ":" + n.name);
+    if (std::find(p.origin.begin(), p.origin.end(), o) == p.origin.end()) p.origin.push_back(o);
+  }
+  // the region value `name` becomes a buffer: the source itself, a SliceCols, or one Prep step
+  void materialize(const std::string &name, const NodeDef *at) {
+    Val &v = vals[name];
+    const std::shared_ptr<const PrepVal> keep = v.pv;
+    const PrepVal &p = *keep;
+    const std::vector<int64_t> shape = v.shape;
+    const int64_t F = int64_t(p.cols.size()), src_w = plan.buf_per_row[size_t(p.src)];
+    bool plain = true, contiguous = true;
+    for (int64_t j = 0; j < F; j++) {
+      plain = plain && p.cols[size_t(j)].plain();
+      contiguous = contiguous && p.cols[size_t(j)].src == p.cols[0].src + j;
+    }
+    Val r;
+    r.shape = shape;
+    if (plain && contiguous && p.cols[0].src == 0 && F == src_w) {  // the source as it is
+      r.buf = p.src;
+      v = r;
+      buf_names[r.buf].push_back(name);
+      alias_edges[r.buf]++;
+      return;
+    }
+    Step s;
+    s.in0 = p.src;
+    if (plain && contiguous) {
+      s.kind = StepKind::SliceCols;
+      s.col_off = p.cols[0].src;
+      s.K = F;
+    } else {
+      PrepPack pk;
+      try {
+        pk = pack_prep(p.cols, prep_tables, src_w);
+      } catch (const PrepError &e) {
+        if (at) unsupported(*at, std::string("preprocessing step: ") + e.what());
+        throw InferaError::onnx("output '" + name + "': preprocessing step: " + e.what());
+      }
+      s.kind = StepKind::Prep;
+      s.prep_F_in = pk.F_in;
+      s.prep_F = pk.F;
+      s.prep_R = pk.R;
+      s.prep_onehot = pk.onehot;
+      s.prep_lookup = pk.lookup;
+      s.prep_strict = pk.strict;
+      s.tree_tab = std::move(pk.desc);
+      s.scale = std::move(pk.cst);
+      s.W = std::move(pk.tab);
+    }
+    s.out = new_buf({shape[0], F});
+    for (const auto &o : p.origin) s.origin += (s.origin.empty() ? "" : "+") + o;
+    if (s.origin.empty()) s.origin = "input:" + name;  // (only a graph input's columns as they are absorb no node)
+    plan.steps.push_back(std::move(s));
+    producer[plan.steps.back().out] = int(plan.steps.size()) - 1;
+    r.buf = plan.steps.back().out;
+    bool all_int = true;
+    for (const PrepCol &c : p.cols) all_int = all_int && c.is_int;
+    if (all_int) int_bufs.insert(r.buf);
+    v = r;
+    buf_names[r.buf].push_back(name);
+  }
+
+  std::vector<int64_t> afe_indices(const NodeDef &n) {
+    const Val &ix = get_raw(n, 1);
+    if (!ix.is_const || ix.c->dtype != onnx::kInt64 || ix.c->i64.empty()) unsupported(n, "indices must be a constant int64 list");
+    return ix.c->i64;
+  }
+  // columns of region values with one source side by side (Concat / FeatureVectorizer); false: the sources differ
+  bool prep_concat(const NodeDef &n, std::vector<int64_t> out_shape) {
+    PrepVal out;
+    for (size_t i = 0; i < n.inputs.size(); i++) {
+      const Val &v = get_raw(n, i);
+      if (v.is_const || !v.pv) return false;
+      if (i && v.pv->src != out.src) return false;
+      if (!i) out.src = v.pv->src;
+    }
+    for (size_t i = 0; i < n.inputs.size(); i++) {
+      const PrepVal &p = *get_raw(n, i).pv;
+      out.cols.insert(out.cols.end(), p.cols.begin(), p.cols.end());
+      for (const auto &o : p.origin)
+        if (std::find(out.origin.begin(), out.origin.end(), o) == out.origin.end()) out.origin.push_back(o);
+    }
+    add_origin(out, n);
+    out_shape[1] = int64_t(out.cols.size()) / std::max<int64_t>(1, prod(out_shape, 2));
+    set_prep(n.outputs[0], std::move(out), out_shape);
+    return true;
+  }
+  void prep_node(const NodeDef &n) {
+    const std::string &op = n.op;
+    if (op == "Identity" || op == "Reshape" || op == "Flatten" || op == "Squeeze") return reshape_like(n);
+    if (op == "Cast") {
+      const Val &a = get_raw(n, 0);
+      const int64_t to = n.attr_i("to", onnx::kFloat);
+      if (!a.pv || !(to == onnx::kInt64 || to == onnx::kInt32)) return cast(n);  // (to float: an alias)
+      PrepVal p = *a.pv;
+      bool clash = false;  // a column that is not whole yet and went past the truncation stage: materialised first
+      for (const PrepCol &c : p.cols) clash = clash || (!c.is_int && c.stage() >= 1);
+      if (clash) p = prep_in(n, 0, 1);
+      for (PrepCol &c : p.cols)
+        if (!c.is_int) c.trunc = true, c.is_int = true;
+      add_origin(p, n);
+      return set_prep(n.outputs[0], std::move(p), a.shape);
+    }
+    if (op == "Concat") {
+      const Val &first = get_raw(n, 0);
+      const int64_t rank = int64_t(first.shape.size());
+      int64_t axis = n.attr_i("axis", 1);
+      if (axis < 0) axis += rank;
+      bool flat = axis >= 1 && axis < rank;  // a flat concatenation of rows: every axis between the row axis and `axis` has extent 1
+      std::vector<int64_t> out_shape = first.shape;
+      for (size_t i = 0; i < n.inputs.size() && flat; i++) {
+        const Val &v = get_raw(n, i);
+        flat = !v.is_const && int64_t(v.shape.size()) == rank;
+        for (int64_t d = 1; d < rank && flat; d++) flat = d == axis || v.shape[size_t(d)] == first.shape[size_t(d)];
+        for (int64_t d = 1; d < axis && flat; d++) flat = v.shape[size_t(d)] == 1;
+      }
+      if (flat && axis != 1) {  // [N, 1, a] ++ [N, 1, b] -> [N, 1, a + b]
+        int64_t total = 0;
+        for (size_t i = 0; i < n.inputs.size(); i++) total += get_raw(n, i).shape[size_t(axis)];
+        out_shape[size_t(axis)] = total;
+        PrepVal p = prep_in(n, 0, 5);
+        for (size_t i = 1; i < n.inputs.size(); i++) {
+          PrepVal q = prep_in(n, i, 5);
+          if (q.src != p.src) unsupported(n, "a preprocessing Concat over the last axis reads one source");
+          p.cols.insert(p.cols.end(), q.cols.begin(), q.cols.end());
+          for (const auto &o : q.origin)
+            if (std::find(p.origin.begin(), p.origin.end(), o) == p.origin.end()) p.origin.push_back(o);
+        }
+        add_origin(p, n);
+        return set_prep(n.outputs[0], std::move(p), out_shape);
+      }
+      if (axis == 1 && flat && prep_concat(n, out_shape)) return;
+      return concat(n);
+    }
+    if (op == "FeatureVectorizer") {
+      const std::vector<int64_t> *dims = n.attr_ints("inputdimensions");
+      if (!dims || dims->size() != n.inputs.size())
+        unsupported(n, "inputdimensions must hold one entry per input (" + std::to_string(n.inputs.size()) + ")");
+      int64_t total = 0;
+      for (size_t i = 0; i < n.inputs.size(); i++) {
+        const Val &v = get_raw(n, i);
+        if (v.is_const || v.shape.empty()) unsupported(n, "inputs must be row data");
+        const int64_t w = prod(v.shape, 1);
+        if ((*dims)[i] != w)
+          unsupported(n, "inputdimensions[" + std::to_string(i) + "] = " + std::to_string((*dims)[i]) + " but input '" + n.inputs[i] + "' has " +
+                             std::to_string(w) + " columns");
+        total += w;
+      }
+      const std::vector<int64_t> out_shape = {get_raw(n, 0).shape[0], total};
+      // (each input as [rows, width]; the sources differ: materialised and copied side by side)
+      const Val &v0 = get_raw(n, 0);
+      bool one_src = v0.pv != nullptr;
+      for (size_t i = 1; i < n.inputs.size() && one_src; i++) {
+        const Val &v = get_raw(n, i);
+        one_src = v.pv && v.pv->src == v0.pv->src;
+      }
+      if (one_src) {
+        PrepVal out = prep_in(n, 0, 5);
+        for (size_t i = 1; i < n.inputs.size(); i++) {
+          PrepVal q = prep_in(n, i, 5);
+          out.cols.insert(out.cols.end(), q.cols.begin(), q.cols.end());
+          for (const auto &o : q.origin)
+            if (std::find(out.origin.begin(), out.origin.end(), o) == out.origin.end()) out.origin.push_back(o);
+        }
+        add_origin(out, n);
+        return set_prep(n.outputs[0], std::move(out), out_shape);
+      }
+      std::vector<std::string> flat;
+      for (size_t i = 0; i < n.inputs.size(); i++) {
+        const Val &v = get(n, i);
+        const std::string f = n.outputs[0] + "\x01" + std::to_string(i);
+        Val a = v;
+        a.shape = {v.shape[0], prod(v.shape, 1)};
+        vals[f] = a;
+        uses[f] = 1;
+        flat.push_back(f);
+      }
+      NodeDef c = std_node(n, "Concat", flat, n.outputs[0]);
+      set_i(c, "axis", 1);
+      return concat(c);
+    }
+    // the per-column nodes: rows of [N, F] (LabelEncoder: any shape)
+    const Val &x = get_raw(n, 0);
+    const std::vector<int64_t> xshape = x.shape;
+    if (x.is_const) unsupported(n, "expected row data, got a constant");
+    if (op != "LabelEncoder" && xshape.size() != 2) unsupported(n, "only [rows, features] inputs");
+    const int64_t F = prod(xshape, 1);
+    PrepVal p;
+    std::vector<int64_t> out_shape = xshape;
+    if (op == "ArrayFeatureExtractor") {
+      const std::vector<int64_t> ix = afe_indices(n);
+      const PrepVal in = prep_in(n, 0, 5);
+      p.src = in.src;
+      p.origin = in.origin;
+      for (int64_t k : ix) {
+        if (k < 0) unsupported(n, "negative column index " + std::to_string(k));
+        if (k >= F) unsupported(n, "column index " + std::to_string(k) + " out of range for " + std::to_string(F) + " columns");
+        p.cols.push_back(in.cols[size_t(k)]);
+      }
+      out_shape = {xshape[0], int64_t(ix.size())};
+    } else if (op == "Imputer") {
+      ImputerSpec sp;
+      try {
+        sp = parse_imputer(n, F);
+      } catch (const PrepError &e) {
+        unsupported(n, e.what());
+      }
+      p = prep_in(n, 0, 2);
+      for (int64_t j = 0; j < F; j++) {
+        PrepCol &c = p.cols[size_t(j)];
+        c.impute = true;
+        c.imp_nan = std::isnan(sp.replaced);
+        c.repl = sp.replaced;
+        c.imp = sp.imputed[size_t(j)];
+        c.is_int = c.is_int && std::nearbyint(c.imp) == c.imp;
+      }
+    } else if (op == "Scaler") {
+      const std::vector<float> off = ml_floats(n, "offset", F, 0.f, true), sc = ml_floats(n, "scale", F, 1.f, true);
+      p = prep_in(n, 0, 3);
+      for (int64_t j = 0; j < F; j++) {
+        PrepCol &c = p.cols[size_t(j)];
+        c.affine = true;
+        c.off = off[size_t(j)];
+        c.scale = sc[size_t(j)];
+        c.is_int = false;
+      }
+    } else if (op == "Binarizer") {
+      const float thr = parse_binarizer(n);
+      p = prep_in(n, 0, 4);
+      for (PrepCol &c : p.cols) c.kind = kPrepBin, c.c = thr, c.is_int = true;
+    } else if (op == "OneHotEncoder") {
+      OneHotSpec sp;
+      try {
+        sp = parse_onehot(n);
+      } catch (const PrepError &e) {
+        unsupported(n, e.what());
+      }
+      const int64_t C = int64_t(sp.cats.size());
+      prep_cats += C;
+      if (prep_cats > kPrepMaxCats) unsupported(n, "more than " + std::to_string(kPrepMaxCats) + " one-hot categories in all");
+      if (F * C > kPrepMaxOut)
+        unsupported(n, std::to_string(F) + " x " + std::to_string(C) + " one-hot columns; a preprocessing step writes at most " + std::to_string(kPrepMaxOut));
+      int table = -1, strict = 0;
+      if (!sp.zeros) {
+        prep_tables.push_back(std::make_shared<PrepTable>(onehot_table(sp.cats)));
+        table = int(prep_tables.size()) - 1;
+        plan.prep_strict_nodes.push_back("node '" + (n.name.empty() ? n.op : n.name) + "' (" + n.op + ")");
+        strict = int(std::min<size_t>(plan.prep_strict_nodes.size(), size_t(kPrepMaxStrictIds)));
+      }
+      const PrepVal in = prep_in(n, 0, 4);
+      p.src = in.src;
+      p.origin = in.origin;
+      for (const PrepCol &base : in.cols)
+        for (int64_t k = 0; k < C; k++) {
+          PrepCol c = base;
+          c.kind = kPrepOneHot;
+          c.c = sp.cats[size_t(k)];
+          c.is_int = true;
+          if (k == 0) c.table = table, c.strict = strict;
+          p.cols.push_back(c);
+        }
+      out_shape = {xshape[0], F, C};
+    } else if (op == "LabelEncoder") {
+      bool int_values = false;
+      PrepTable t;
+      try {
+        t = parse_label_encoder(n, &int_values);
+      } catch (const PrepError &e) {
+        unsupported(n, e.what());
+      }
+      prep_keys += int64_t(t.keys.size()) + (t.has_nan ? 1 : 0);
+      if (prep_keys > kPrepMaxKeys) unsupported(n, "more than " + std::to_string(kPrepMaxKeys) + " LabelEncoder keys in all");
+      const float dflt = t.dflt;
+      prep_tables.push_back(std::make_shared<PrepTable>(std::move(t)));
+      p = prep_in(n, 0, 4);
+      for (PrepCol &c : p.cols) c.kind = kPrepLookup, c.c = dflt, c.table = int(prep_tables.size()) - 1, c.is_int = int_values;
+    } else {
+      unsupported(n, "unsupported operator");
+    }
+    add_origin(p, n);
+    set_prep(n.outputs[0], std::move(p), out_shape);
+  }
+
   Plan run() {
     plan.opset = m.opset;
     const onnx::ValueDef &in = m.inputs[0];
     if (!in.has_shape) throw InferaError::onnx("input '" + in.name + "' has no declared shape");
-    if (in.elem_type != 0 && in.elem_type != onnx::kFloat) throw InferaError::onnx("input '" + in.name + "' is not f32");
+    // (integer inputs: their values arrive as f32 and are truncated toward zero where a preprocessing region first reads them)
+    auto served_type = [](int t) { return t == 0 || t == onnx::kFloat || t == onnx::kInt64 || t == onnx::kInt32; };
+    for (const auto &v : m.inputs)
+      if (!served_type(v.elem_type))
+        throw InferaError::onnx("input '" + v.name + "' is not f32, int64 or int32 (element type " + std::to_string(v.elem_type) + ")");
     if (in.dims.size() < 2) throw InferaError::onnx("input rank " + std::to_string(in.dims.size()) + " has no row axis + feature axis; rank >= 2 is required");
     for (size_t i = 1; i < in.dims.size(); i++)
       if (in.dims[i] <= 0) throw InferaError::onnx("only the leading (row/batch) dimension of the input may be symbolic, got " + shape_str(in.dims));
@@ -1584,7 +2041,7 @@ struct Lowerer {
       // input must be an f32 [rows, k_i] matrix with the same leading dimension.
       int64_t total = 0;
       for (const auto &v : m.inputs) {
-        if (!v.has_shape || v.dims.size() != 2 || v.dims[1] <= 0 || (v.elem_type != 0 && v.elem_type != onnx::kFloat) ||
+        if (!v.has_shape || v.dims.size() != 2 || v.dims[1] <= 0 || !served_type(v.elem_type) ||
             (v.dims[0] > 0 ? v.dims[0] : -1) != plan.input_shape[0])
           throw InferaError::onnx("multi-input models need f32 [rows, k] inputs with one common leading dimension; input '" + v.name + "' is " +
                                   (v.has_shape ? shape_str(v.dims) : std::string("unshaped")));
@@ -1601,6 +2058,7 @@ struct Lowerer {
         buf_names[v.buf].push_back(in.name);
       }
     }
+    auto int_input = [](const onnx::ValueDef &v) { return v.elem_type == onnx::kInt64 || v.elem_type == onnx::kInt32; };
     // Only the first output is served (engine.rs:146-149): nodes that do not feed it are dead -- a second
     // output (e.g. the probabilities next to a label) must neither cost kernels nor block loading.
     std::vector<char> live(m.nodes.size(), 0);
@@ -1622,11 +2080,27 @@ struct Lowerer {
       if (live[i])
         for (const auto &in_name : m.nodes[i].inputs) uses[in_name]++;
     uses[m.outputs[out_index].name]++;
+    // preprocessing regions: their graph inputs start as identity columns over the input buffer (integer inputs truncated)
+    const std::set<std::string> region_inputs = find_regions(live);
+    {
+      int64_t off = 0;
+      for (const auto &v : m.inputs) {
+        const int64_t w = m.inputs.size() == 1 ? prod(plan.input_shape, 1) : v.dims[1];
+        if (region_inputs.count(v.name)) {
+          if (m.inputs.size() == 1 && plan.input_shape.size() != 2 && int_input(v))
+            throw InferaError::onnx("integer input '" + v.name + "' must be [rows, k]");
+          PrepVal p = prep_identity(0, off, w, int_input(v), false);
+          if (int_input(v)) p.origin.push_back("input:" + v.name);
+          set_prep(v.name, std::move(p), m.inputs.size() == 1 ? plan.input_shape : std::vector<int64_t>{plan.input_shape[0], w});
+        }
+        off += w;
+      }
+    }
 
     if (m.inputs.size() > 1) {
       int64_t off = 0;
       for (const auto &v : m.inputs) {
-        if (uses.count(v.name) && uses[v.name] > 0) {
+        if (uses.count(v.name) && uses[v.name] > 0 && !region_inputs.count(v.name)) {
           Step s;
           s.kind = StepKind::SliceCols;
           s.in0 = 0;
@@ -1649,7 +2123,8 @@ struct Lowerer {
       if (!live[ni]) continue;
       const auto &n = m.nodes[ni];
       if (n.outputs.empty()) throw InferaError::onnx("node " + n.op + " has no outputs");
-      if (n.domain == "ai.onnx.ml") ml_node(n);
+      if (region[ni]) prep_node(n);
+      else if (n.domain == "ai.onnx.ml") ml_node(n);
       else if (!n.domain.empty() && n.domain != "ai.onnx") unsupported(n, "operator domain '" + n.domain + "'");
       else lower_node(n);
     }
@@ -1657,6 +2132,7 @@ struct Lowerer {
     const onnx::ValueDef &out = m.outputs[out_index];
     auto it = vals.find(out.name);
     if (it == vals.end()) throw InferaError::onnx("output '" + out.name + "' is never produced");
+    if (it->second.pv) materialize(out.name, nullptr);
     if (it->second.is_const) throw InferaError::onnx("output '" + out.name + "' is a constant; nothing to run");
     if (it->second.padded()) throw InferaError::onnx("output '" + out.name + "' is a Pad result; padding is only folded into a following Conv");
     if (out.elem_type != 0 && out.elem_type != onnx::kFloat) {
@@ -1698,7 +2174,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -1723,6 +2199,9 @@ std::string Plan::describe_json() const {
       o << ",\"kernel\":\"" << kernels[s.svm_kernel] << "\",\"support_vectors\":" << s.svm_n_sv << ",\"F\":" << s.svm_F << ",\"classes\":" << s.svm_classes
         << ",\"slices\":" << s.svm_slices << ",\"output\":\"" << modes[s.svm_mode] << "\",\"probabilities\":" << (s.svm_prob ? "true" : "false");
     }
+    if (s.kind == StepKind::Prep)
+      o << ",\"F_in\":" << s.prep_F_in << ",\"F\":" << s.prep_F << ",\"onehot_cols\":" << s.prep_onehot << ",\"lookup_cols\":" << s.prep_lookup
+        << ",\"rows_per_tile\":" << s.prep_R << ",\"strict\":" << (s.prep_strict ? "true" : "false");
     if (s.act != Act::None) o << ",\"act\":\"" << acts[int(s.act)] << "\"";
     o << ",\"origin\":" << json_str(s.origin) << "}";
   }

@@ -46,6 +46,7 @@ enum class StepKind : int {
   TreeReduce = 16,    // in0 = those partials -> scores [rows, E] (AVERAGE, base_values, binary expansion) or the class label [rows]
   SvmKernel = 17,     // ai.onnx.ml SVM: out = per-slice sums  sum_s coef[q][s] * K(x, s)  over each SV slice: [svm_slices][rows][svm_Q] (svm.hip)
   SvmReduce = 18,     // in0 = those partials -> regressor value / one-class sign, pairwise decisions, label or probabilities (SvmOut)
+  Prep = 19,          // ai.onnx.ml preprocessing region: out[r, j] = column program j over in0[r, :] (host/prep.hpp, prep.hip)
 };
 
 // TreeReduce output modes (Step::tree_mode)
@@ -99,6 +100,10 @@ struct Step {
   int64_t svm_F = 0, svm_F_pad = 0, svm_n_sv = 0, svm_tiles = 0, svm_Q = 1, svm_slices = 1, svm_classes = 1;
   int64_t svm_QW = 1;      // stage-2 width (host/svm.hpp SvmPack::QW)
   bool svm_prob = false;  // the model has prob_a / prob_b
+  // Prep (host/prep.hpp PrepPack): tree_tab = column descriptors (4 words each), scale = per-column constants (4 each), W = key/value pairs.
+  // prep_R = rows per block tile; prep_strict: a zeros = 0 OneHotEncoder sets the call's failure word
+  int64_t prep_F_in = 0, prep_F = 0, prep_R = 1, prep_onehot = 0, prep_lookup = 0;
+  bool prep_strict = false;
   std::string origin;  // ONNX node names/ops this step came from (diagnostics)
 };
 
@@ -112,6 +117,10 @@ struct Plan {
   int64_t opset = 1;
   std::string output_name;         // the served graph output
   std::string output_declared_type;  // "" for f32; "int64" / "int32" when the graph declares an integer output that is served as f32 VALUES
+  bool output_zipmap = false;        // the served output is a ZipMap's: its input [rows, C] is served, one column per class label
+  // "node 'name' (OneHotEncoder)" of each zeros = 0 one-hot encoder (1-based ids in the Prep descriptors); a call whose failure word is set
+  // fails naming it
+  std::vector<std::string> prep_strict_nodes;
 
   int64_t in_per_row() const { return buf_per_row[0]; }
   int64_t out_per_row() const { return buf_per_row[out_buf]; }

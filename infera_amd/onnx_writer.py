@@ -633,11 +633,23 @@ def tree_ensemble_from_spec(spec: dict, scaler: tuple | None = None, output: str
     """The ONNX model of a tree_ensemble_spec() dict: [Scaler(offset, scale) ->] TreeEnsembleRegressor (output Y [N, E]) or
     TreeEnsembleClassifier (label int64 [N], probabilities [N, E]; `output` = which of the two is graph output 0)."""
     cls = spec["kind"] == "classifier"
-    F, E = spec["features"], spec["E"]
+    F = spec["features"]
     nodes, x = [], "X"
     if scaler is not None:
         nodes.append(node("Scaler", [x], ["Xs"], [attr_floats("offset", scaler[0]), attr_floats("scale", scaler[1])], domain=ML_DOMAIN))
         x = "Xs"
+    nd, (o_first, o_second) = _tree_node(spec, x)
+    nodes.append(nd)
+    outs = ([o_first, o_second] if output == "label" else [o_second, o_first]) if cls else [o_first]
+    return model("tree_ensemble", nodes, [], [value_info("X", ["N", F])], outs, opset=13,
+                 ml_opset=ml_opset if ml_opset is not None else (3 if spec["as_tensor"] else 1))
+
+
+def _tree_node(spec: dict, x: str, outputs: Sequence[str] = ("label", "probabilities")) -> tuple[bytes, tuple]:
+    """The TreeEnsemble node of a tree_ensemble_spec() dict reading `x`, and the value infos of its (label, scores) outputs (regressor:
+    (Y, None))."""
+    cls = spec["kind"] == "classifier"
+    E = spec["E"]
     at = bool(spec["as_tensor"])
     def floats(name, vals):
         return attr_tensor(name + "_as_tensor", tensor_f64("", vals)) if at else attr_floats(name, np.asarray(vals, dtype=np.float32))
@@ -655,15 +667,10 @@ def tree_ensemble_from_spec(spec: dict, scaler: tuple | None = None, output: str
         attrs.append(floats("base_values", spec["base_values"]))
     if cls:
         attrs.append(attr_ints("classlabels_int64s", spec["labels"]))
-        nodes.append(node("TreeEnsembleClassifier", [x], ["label", "probabilities"], attrs, domain=ML_DOMAIN))
-        o_label, o_prob = value_info("label", ["N"], INT64), value_info("probabilities", ["N", E])
-        outs = [o_label, o_prob] if output == "label" else [o_prob, o_label]
-    else:
-        attrs.append(attr_i("n_targets", E))
-        nodes.append(node("TreeEnsembleRegressor", [x], ["Y"], attrs, domain=ML_DOMAIN))
-        outs = [value_info("Y", ["N", E])]
-    return model("tree_ensemble", nodes, [], [value_info("X", ["N", F])], outs, opset=13,
-                 ml_opset=ml_opset if ml_opset is not None else (3 if at else 1))
+        nd = node("TreeEnsembleClassifier", [x], list(outputs), attrs, domain=ML_DOMAIN)
+        return nd, (value_info(outputs[0], ["N"], INT64), value_info(outputs[1], ["N", E]))
+    attrs.append(attr_i("n_targets", E))
+    return node("TreeEnsembleRegressor", [x], ["Y"], attrs, domain=ML_DOMAIN), (value_info("Y", ["N", E]), None)
 
 
 def tree_ensemble(scaler: tuple | None = None, output: str = "label", **kw) -> bytes:
@@ -723,6 +730,15 @@ def svm_from_spec(spec: dict, scaler: tuple | None = None, output: str = "label"
     if scaler is not None:
         nodes.append(node("Scaler", [x], ["Xs"], [attr_floats("offset", scaler[0]), attr_floats("scale", scaler[1])], domain=ML_DOMAIN))
         x = "Xs"
+    nd, (o_first, o_second) = _svm_node(spec, x)
+    nodes.append(nd)
+    outs = ([o_first, o_second] if output == "label" else [o_second, o_first]) if cls else [o_first]
+    return model("svm", nodes, [], [value_info("X", ["N", F])], outs, opset=13, ml_opset=1)
+
+
+def _svm_node(spec: dict, x: str, outputs: Sequence[str] = ("label", "probabilities")) -> tuple[bytes, tuple]:
+    """The SVM node of an svm_spec() dict reading `x`, and the value infos of its (label, scores) outputs (regressor: (Y, None))."""
+    cls = spec["kind"] == "classifier"
     attrs = [attr_s("kernel_type", spec["kernel"]), attr_floats("kernel_params", spec["kernel_params"]),
              attr_floats("support_vectors", np.asarray(spec["support_vectors"], dtype=np.float32).ravel()),
              attr_floats("coefficients", np.asarray(spec["coefficients"], dtype=np.float32).ravel()),
@@ -733,16 +749,317 @@ def svm_from_spec(spec: dict, scaler: tuple | None = None, output: str = "label"
             attrs += [attr_floats("prob_a", spec["prob_a"]), attr_floats("prob_b", spec["prob_b"])]
         C = spec["classes"]
         cols = C if spec.get("prob_a") is not None else (2 if C == 2 else C * (C - 1) // 2)
-        nodes.append(node("SVMClassifier", [x], ["label", "probabilities"], attrs, domain=ML_DOMAIN))
-        o_label, o_prob = value_info("label", ["N"], INT64), value_info("probabilities", ["N", cols])
-        outs = [o_label, o_prob] if output == "label" else [o_prob, o_label]
-    else:
-        attrs += [attr_i("n_supports", spec["n_sv"]), attr_i("one_class", 1 if spec["kind"] == "one_class" else 0)]
-        nodes.append(node("SVMRegressor", [x], ["Y"], attrs, domain=ML_DOMAIN))
-        outs = [value_info("Y", ["N", 1])]
-    return model("svm", nodes, [], [value_info("X", ["N", F])], outs, opset=13, ml_opset=1)
+        nd = node("SVMClassifier", [x], list(outputs), attrs, domain=ML_DOMAIN)
+        return nd, (value_info(outputs[0], ["N"], INT64), value_info(outputs[1], ["N", cols]))
+    attrs += [attr_i("n_supports", spec["n_sv"]), attr_i("one_class", 1 if spec["kind"] == "one_class" else 0)]
+    return node("SVMRegressor", [x], ["Y"], attrs, domain=ML_DOMAIN), (value_info("Y", ["N", 1]), None)
 
 
 def svm(scaler: tuple | None = None, output: str = "label", **kw) -> bytes:
     """Seeded SVMRegressor / SVMClassifier model (keywords: svm_spec)."""
     return svm_from_spec(svm_spec(**kw), scaler=scaler, output=output)
+
+
+# ------------------------------------------------------------------------------------------
+# ai.onnx.ml preprocessing (Imputer, Scaler, OneHotEncoder, LabelEncoder, Binarizer, ArrayFeatureExtractor, Concat, ZipMap)
+# ------------------------------------------------------------------------------------------
+
+def value_info_zipmap(name: str, key_type: int = INT64) -> bytes:
+    """A ZipMap output: sequence(map(key_type, float))."""
+    tensor_f = _ld(1, _vi(1, FLOAT))
+    map_t = _ld(5, _vi(1, key_type) + _ld(2, tensor_f))
+    return _s(1, name) + _ld(2, _ld(4, _ld(1, map_t)))
+
+
+def prep_spec(numeric: int = 6, categorical: int = 8, cats_total: int = 100, ordinal: int = 2, ordinal_keys: int = 20,
+              binarized: int = 0, strict: bool = False, seed: int = 11) -> dict:
+    """Seeded ColumnTransformer-like preprocessing: `numeric` columns through Imputer (NaN -> a value) and Scaler, `categorical` columns
+    one-hot encoded with `cats_total` integer categories in all (some negative), `ordinal` columns through a LabelEncoder of
+    `ordinal_keys` integer keys each (alternately keys_int64s and keys_floats), `binarized` columns through a Binarizer.  The columns of
+    each group are scattered over the input (non-contiguous ArrayFeatureExtractor indices).  strict: OneHotEncoder zeros = 0."""
+    rng = np.random.default_rng(seed)
+    F_in = numeric + categorical + ordinal + binarized
+    perm = [int(v) for v in rng.permutation(F_in)]
+    groups, at = {}, 0
+    for g, n in (("numeric", numeric), ("categorical", categorical), ("ordinal", ordinal), ("binarized", binarized)):
+        groups[g] = perm[at:at + n]
+        at += n
+    per = np.full(categorical, cats_total // max(categorical, 1))
+    per[:cats_total - int(per.sum())] += 1
+    f32 = lambda a: np.asarray(a, dtype=np.float32)  # noqa: E731
+    cats = [sorted(int(v) for v in rng.choice(np.arange(-20, 40), int(c), replace=False)) for c in per]
+    ordinal_tabs = []
+    for i in range(ordinal):
+        keys = sorted(int(v) for v in rng.choice(np.arange(-10, 50), ordinal_keys, replace=False))
+        ordinal_tabs.append({"keys": keys, "values": f32(rng.permutation(ordinal_keys)), "default": -1.0, "floats": i % 2 == 1})
+    return {
+        "features": F_in, "groups": groups, "strict": strict,
+        "imputed": f32(rng.normal(0, 1, numeric)), "offset": f32(rng.normal(0, 1, numeric)), "scale": f32(rng.uniform(0.5, 2, numeric)),
+        "cats": cats, "ordinal": ordinal_tabs, "thresholds": f32(rng.normal(0, 0.5, binarized)),
+    }
+
+
+def prep_width(spec: dict) -> int:
+    """F': the columns prep_from_spec's Concat produces."""
+    return len(spec["groups"]["numeric"]) + sum(len(c) for c in spec["cats"]) + len(spec["ordinal"]) + len(spec["groups"]["binarized"])
+
+
+def prep_nodes(spec: dict, x: str = "X", out: str = "features", after_onehot: str = "Reshape", cast: bool = True,
+               concat_axis: int = 1) -> tuple[list, list]:
+    """The preprocessing nodes of a prep_spec() dict, laid out as skl2onnx writes a ColumnTransformer: one ArrayFeatureExtractor per
+    column group (numeric) or column (categorical / ordinal), Imputer -> Scaler, [Cast(int64) ->] OneHotEncoder -> Reshape([-1, C])
+    (or Flatten / Squeeze(axis 1)), LabelEncoder, Binarizer, then Concat.  Returns (nodes, initializers)."""
+    nodes, inits, parts = [], [], []
+    g = spec["groups"]
+
+    def afe(cols, name):
+        inits.append(tensor(name + "_idx", np.asarray(cols, dtype=np.int64)))
+        nodes.append(node("ArrayFeatureExtractor", [x, name + "_idx"], [name + "_cols"], name=name + "_afe", domain=ML_DOMAIN))
+        return name + "_cols"
+
+    if g["numeric"]:
+        v = afe(g["numeric"], "num")
+        nodes.append(node("Imputer", [v], ["num_imp"], [attr_floats("imputed_value_floats", spec["imputed"]),
+                                                        attr_f("replaced_value_float", float("nan"))], name="num_imputer", domain=ML_DOMAIN))
+        nodes.append(node("Scaler", ["num_imp"], ["num_scaled"], [attr_floats("offset", spec["offset"]), attr_floats("scale", spec["scale"])],
+                          name="num_scaler", domain=ML_DOMAIN))
+        parts.append("num_scaled")
+    for i, (col, cats) in enumerate(zip(g["categorical"], spec["cats"])):
+        v = afe([col], f"cat{i}")
+        if cast:
+            nodes.append(node("Cast", [v], [f"cat{i}_int"], [attr_i("to", INT64)], name=f"cat{i}_cast"))
+            v = f"cat{i}_int"
+        nodes.append(node("OneHotEncoder", [v], [f"cat{i}_oh"], [attr_ints("cats_int64s", cats), attr_i("zeros", 0 if spec["strict"] else 1)],
+                          name=f"cat{i}_onehot", domain=ML_DOMAIN))
+        if after_onehot == "Reshape":
+            inits.append(tensor(f"cat{i}_shape", np.asarray([-1, len(cats)], dtype=np.int64)))
+            nodes.append(node("Reshape", [f"cat{i}_oh", f"cat{i}_shape"], [f"cat{i}_flat"], name=f"cat{i}_reshape"))
+        elif after_onehot == "Flatten":
+            nodes.append(node("Flatten", [f"cat{i}_oh"], [f"cat{i}_flat"], [attr_i("axis", 1)], name=f"cat{i}_flatten"))
+        else:
+            inits.append(tensor(f"cat{i}_axes", np.asarray([1], dtype=np.int64)))
+            nodes.append(node("Squeeze", [f"cat{i}_oh", f"cat{i}_axes"], [f"cat{i}_flat"], name=f"cat{i}_squeeze"))
+        parts.append(f"cat{i}_flat")
+    for i, (col, t) in enumerate(zip(g["ordinal"], spec["ordinal"])):
+        v = afe([col], f"ord{i}")
+        keys = attr_floats("keys_floats", t["keys"]) if t["floats"] else attr_ints("keys_int64s", t["keys"])
+        nodes.append(node("LabelEncoder", [v], [f"ord{i}_enc"], [keys, attr_floats("values_floats", t["values"]),
+                                                                 attr_f("default_float", t["default"])], name=f"ord{i}_encoder", domain=ML_DOMAIN))
+        parts.append(f"ord{i}_enc")
+    for i, (col, thr) in enumerate(zip(g["binarized"], spec["thresholds"])):
+        v = afe([col], f"bin{i}")
+        nodes.append(node("Binarizer", [v], [f"bin{i}_b"], [attr_f("threshold", float(thr))], name=f"bin{i}_binarizer", domain=ML_DOMAIN))
+        parts.append(f"bin{i}_b")
+    nodes.append(node("Concat", parts, [out], [attr_i("axis", concat_axis)], name="concat"))
+    return nodes, inits
+
+
+def prep_from_spec(spec: dict, head=None, zipmap: bool = False, **layout) -> bytes:
+    """The ONNX model of a prep_spec() dict: the preprocessing nodes (prep_nodes, `layout` keywords) and, when given, an estimator `head`
+    reading their output (a callable (x, F') -> (nodes, initializers, outputs): tree_head / svm_head / linear_head).  Without a head the
+    graph serves the preprocessed rows [N, F'].  zipmap: a ZipMap on the head's probabilities, output 'output_probability'."""
+    nodes, inits = prep_nodes(spec, **layout)
+    Fp = prep_width(spec)
+    if head is None:
+        outs = [value_info("features", ["N", Fp])]
+    else:
+        hn, hi, outs = head("features", Fp)
+        nodes, inits = nodes + hn, inits + hi
+    if zipmap:
+        nodes.append(node("ZipMap", ["probabilities"], ["output_probability"], [attr_ints("classlabels_int64s", head.labels)], name="zipmap",
+                          domain=ML_DOMAIN))
+        outs = [outs[0], value_info_zipmap("output_probability")]
+    return model("prep", nodes, inits, [value_info("X", ["N", spec["features"]])], outs, opset=13, ml_opset=3)
+
+
+class _Head:
+    """An estimator graph reading the preprocessed rows: call (x, F) -> (nodes, initializers, outputs [label, probabilities] or [Y])."""
+
+    def __init__(self, build, labels=None):
+        self.build, self.labels = build, labels
+
+    def __call__(self, x: str, F: int):
+        return self.build(x, F)
+
+
+def tree_head(spec: dict) -> _Head:
+    """A tree_ensemble_spec()-style dict (its "features" = F') as a head."""
+    def build(x, F):
+        assert spec["features"] == F, (spec["features"], F)
+        nd, (a, b) = _tree_node(spec, x)
+        return [nd], [], [a, b] if b is not None else [a]
+    return _Head(build, list(spec.get("labels", [])))
+
+
+def svm_head(spec: dict) -> _Head:
+    """An svm_spec()-style dict (its "features" = F') as a head."""
+    def build(x, F):
+        assert spec["features"] == F, (spec["features"], F)
+        nd, (a, b) = _svm_node(spec, x)
+        return [nd], [], [a, b] if b is not None else [a]
+    return _Head(build, list(spec.get("labels", [])))
+
+
+def linear_head(coef, intercepts, labels: Sequence[int], post: str = "SOFTMAX") -> _Head:
+    """LinearClassifier(coefficients [C, F'], intercepts [C]) as a head."""
+    coef = np.asarray(coef, dtype=np.float32)
+
+    def build(x, F):
+        assert coef.shape[1] == F, (coef.shape, F)
+        nd = node("LinearClassifier", [x], ["label", "probabilities"],
+                  [attr_floats("coefficients", coef.ravel()), attr_floats("intercepts", np.asarray(intercepts, np.float32)),
+                   attr_ints("classlabels_ints", labels), attr_s("post_transform", post)], domain=ML_DOMAIN)
+        return [nd], [], [value_info("label", ["N"], INT64), value_info("probabilities", ["N", len(labels)])]
+    return _Head(build, list(labels))
+
+
+def sklearn_tree_spec(est, F: int) -> dict:
+    """A fitted RandomForestClassifier / RandomForestRegressor / GradientBoostingRegressor as a tree_ensemble_spec()-style dict."""
+    cls = hasattr(est, "classes_")
+    gb = hasattr(est, "init_")
+    trees = [e[0].tree_ for e in est.estimators_] if gb else [e.tree_ for e in est.estimators_]
+    E = len(est.classes_) if cls else 1
+    scale = float(est.learning_rate) if gb else 1.0
+    keys = ("nodes_treeids", "nodes_nodeids", "nodes_featureids", "nodes_modes", "nodes_values", "nodes_truenodeids", "nodes_falsenodeids")
+    nd = {k: [] for k in keys}
+    lt, ln, lid, lw = [], [], [], []
+    for t, tr in enumerate(trees):
+        for i in range(tr.node_count):
+            leaf = tr.children_left[i] < 0
+            for k, v in zip(keys, (t, i, 0 if leaf else int(tr.feature[i]), "LEAF" if leaf else "BRANCH_LEQ",
+                                   0.0 if leaf else float(tr.threshold[i]), 0 if leaf else int(tr.children_left[i]),
+                                   0 if leaf else int(tr.children_right[i]))):
+                nd[k].append(v)
+            if leaf:
+                v = tr.value[i].ravel()
+                if cls:
+                    v = v / v.sum()
+                for j in range(E):
+                    lt.append(t), ln.append(i), lid.append(j), lw.append(float(v[j]) * scale)
+    spec = {"kind": "classifier" if cls else "regressor", "features": F, "E": E,
+            "labels": [int(c) for c in est.classes_] if cls else [0], "aggregate": "SUM" if gb else "AVERAGE", "post": "NONE",
+            "as_tensor": True, "missing": False, "leaf_treeids": lt, "leaf_nodeids": ln, "leaf_ids": lid, "leaf_weights": np.array(lw),
+            "base_values": np.array([float(est.init_.constant_.ravel()[0])]) if gb else None}
+    spec.update(nd)
+    spec["nodes_values"] = np.array(spec["nodes_values"])
+    return spec
+
+
+def sklearn_svm_spec(est, F: int) -> dict:
+    """A fitted SVC as an svm_spec()-style dict (libsvm's one-vs-one layout)."""
+    spec = {"kind": "classifier", "features": F, "kernel": est.kernel.upper(), "post": "NONE", "n_sv": int(est.support_vectors_.shape[0]),
+            "support_vectors": np.asarray(est.support_vectors_, dtype=np.float32),
+            "coefficients": np.asarray(est._dual_coef_, dtype=np.float32), "rho": np.asarray(est._intercept_, dtype=np.float32).ravel(),
+            "kernel_params": np.asarray([est._gamma, est.coef0, est.degree], dtype=np.float32), "prob_a": None, "prob_b": None,
+            "classes": len(est.classes_), "labels": [int(c) for c in est.classes_], "vectors_per_class": [int(v) for v in est.n_support_]}
+    return spec
+
+
+def sklearn_column_transformer(ct, estimator_graph=None, zipmap: bool = False, after_onehot: str = "Reshape", cast: bool = True,
+                               concat_axis: int = 1) -> bytes:
+    """A fitted sklearn ColumnTransformer [+ estimator] as ONNX, laid out the way skl2onnx writes it (from the operator specifications
+    and the converter's known layout, not from skl2onnx itself): per transformer an ArrayFeatureExtractor of its columns, then
+    Pipeline(SimpleImputer, StandardScaler) -> Imputer -> Scaler; OneHotEncoder -> per column [Cast(int64) ->] OneHotEncoder ->
+    Reshape([-1, C]); OrdinalEncoder -> per column LabelEncoder; Binarizer; 'passthrough'; all joined by Concat.  The input is one f32
+    matrix X [N, n_features_in_].  estimator_graph: a head (tree_head / svm_head / linear_head) over the F' transformed columns, else
+    the transformed rows are the output.  zipmap: a ZipMap on the head's probabilities."""
+    nodes, inits, parts, Fp = [], [], [], 0
+    uid = [0]
+
+    def fresh(p):
+        uid[0] += 1
+        return f"{p}{uid[0]}"
+
+    def afe(cols):
+        n = fresh("afe")
+        inits.append(tensor(n + "_idx", np.asarray(cols, dtype=np.int64)))
+        nodes.append(node("ArrayFeatureExtractor", ["X", n + "_idx"], [n], name=n, domain=ML_DOMAIN))
+        return n
+
+    def cols_of(sel):
+        idx = np.arange(ct.n_features_in_)[sel] if not isinstance(sel, (list, tuple)) or isinstance(sel, slice) else np.asarray(sel)
+        return [int(c) for c in np.atleast_1d(idx)]
+
+    for name, tr, sel in ct.transformers_:
+        if tr == "drop":
+            continue
+        cols = cols_of(sel)
+        if not cols:
+            continue
+        steps = [s for _, s in tr.steps] if hasattr(tr, "steps") else [tr]
+        kinds = [type(s).__name__ for s in steps]
+        if tr == "passthrough":
+            parts.append(afe(cols))
+            Fp += len(cols)
+        elif set(kinds) <= {"SimpleImputer", "StandardScaler"}:
+            v = afe(cols)
+            for s in steps:
+                o = fresh(type(s).__name__)
+                if type(s).__name__ == "SimpleImputer":
+                    nodes.append(node("Imputer", [v], [o], [attr_floats("imputed_value_floats", np.asarray(s.statistics_, np.float32)),
+                                                            attr_f("replaced_value_float", float("nan"))], name=o, domain=ML_DOMAIN))
+                else:
+                    mean = s.mean_ if s.with_mean else np.zeros(len(cols))
+                    sc = 1.0 / s.scale_ if s.with_std else np.ones(len(cols))
+                    nodes.append(node("Scaler", [v], [o], [attr_floats("offset", np.asarray(mean, np.float32)),
+                                                          attr_floats("scale", np.asarray(sc, np.float32))], name=o, domain=ML_DOMAIN))
+                v = o
+            parts.append(v)
+            Fp += len(cols)
+        elif kinds == ["OneHotEncoder"]:
+            enc = steps[0]
+            if getattr(enc, "drop_idx_", None) is not None or getattr(enc, "infrequent_categories_", None) is not None:
+                raise TypeError(f"transformer {name!r}: OneHotEncoder with drop= or infrequent categories is not written by this builder")
+            for j, c in enumerate(cols):
+                v = afe([c])
+                if cast:
+                    o = fresh("cast")
+                    nodes.append(node("Cast", [v], [o], [attr_i("to", INT64)], name=o))
+                    v = o
+                cats = [int(k) for k in enc.categories_[j]]
+                o = fresh("onehot")
+                nodes.append(node("OneHotEncoder", [v], [o], [attr_ints("cats_int64s", cats),
+                                                             attr_i("zeros", 0 if enc.handle_unknown == "error" else 1)], name=o, domain=ML_DOMAIN))
+                f = fresh("flat")
+                if after_onehot == "Reshape":
+                    inits.append(tensor(f + "_shape", np.asarray([-1, len(cats)], dtype=np.int64)))
+                    nodes.append(node("Reshape", [o, f + "_shape"], [f], name=f))
+                elif after_onehot == "Flatten":
+                    nodes.append(node("Flatten", [o], [f], [attr_i("axis", 1)], name=f))
+                else:
+                    inits.append(tensor(f + "_axes", np.asarray([1], dtype=np.int64)))
+                    nodes.append(node("Squeeze", [o, f + "_axes"], [f], name=f))
+                parts.append(f)
+                Fp += len(cats)
+        elif kinds == ["OrdinalEncoder"]:
+            enc = steps[0]
+            unknown = getattr(enc, "unknown_value", None)
+            for j, c in enumerate(cols):
+                v = afe([c])
+                cats = [int(k) for k in enc.categories_[j]]
+                o = fresh("ordinal")
+                nodes.append(node("LabelEncoder", [v], [o], [attr_ints("keys_int64s", cats),
+                                                            attr_floats("values_floats", np.arange(len(cats), dtype=np.float32)),
+                                                            attr_f("default_float", float(unknown) if unknown is not None else -1.0)],
+                                  name=o, domain=ML_DOMAIN))
+                parts.append(o)
+                Fp += 1
+        elif kinds == ["Binarizer"]:
+            v = afe(cols)
+            o = fresh("binarizer")
+            nodes.append(node("Binarizer", [v], [o], [attr_f("threshold", float(steps[0].threshold))], name=o, domain=ML_DOMAIN))
+            parts.append(o)
+            Fp += len(cols)
+        else:
+            raise TypeError(f"transformer {name!r}: {kinds} is not written by this builder")
+    nodes.append(node("Concat", parts, ["features"], [attr_i("axis", concat_axis)], name="concat"))
+    if estimator_graph is None:
+        outs = [value_info("features", ["N", Fp])]
+    else:
+        hn, hi, outs = estimator_graph("features", Fp)
+        nodes, inits = nodes + hn, inits + hi
+    if zipmap:
+        nodes.append(node("ZipMap", ["probabilities"], ["output_probability"], [attr_ints("classlabels_int64s", estimator_graph.labels)],
+                          name="zipmap", domain=ML_DOMAIN))
+        outs = [outs[0], value_info_zipmap("output_probability")]
+    return model("column_transformer", nodes, inits, [value_info("X", ["N", int(ct.n_features_in_)])], outs, opset=13, ml_opset=3)
