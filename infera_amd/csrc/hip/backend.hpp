@@ -51,7 +51,7 @@ double h2d_probe_gbs(int device_ordinal, size_t bytes, int iters, int threads);
 // Constants of one plan step resident in one GPU's HBM.
 struct DeviceStep {
   float *W = nullptr, *bias = nullptr, *cst = nullptr, *scale = nullptr, *shift = nullptr;
-  uint32_t *tab = nullptr;  // Step::tree_tab
+  uint32_t *tab = nullptr;  // the word table of a TreeEnsemble, SvmKernel, SvmReduce or Prep step (model.cpp upload_ml_tables)
 };
 
 // How the executor runs a step.

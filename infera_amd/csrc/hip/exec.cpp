@@ -3,6 +3,9 @@
 // (engine.rs:142-145).  Also the device-resident entry points (infera_hip_predict_device).
 #include <cstdlib>
 
+#include "../host/prep.hpp"
+#include "../host/svm.hpp"
+#include "../host/trees.hpp"
 #include "runtime.hpp"
 
 namespace infera_hip {
@@ -214,25 +217,32 @@ void PassRunner::launch_plain(size_t i) {
       kern::copy_cols(stream, buf(x.in0), buf(x.out), nr, x.K, p.buf_per_row[size_t(x.in0)], x.col_off, x.K, 0);
       break;
     case StepKind::ArgMax: kern::argmax_rows(stream, buf(x.in0), buf(x.out), nr, x.K); break;
-    case StepKind::TreeEnsemble:
-      kern::tree_walk(stream, buf(x.in0), int(p.buf_per_row[size_t(x.in0)]), d.tab, x.tree_nodes, x.tree_count, d.W, int(x.tree_W), int(x.tree_slices),
-                      buf(x.out), nr);
+    // (the ai.onnx.ml steps: which device pointer holds which table is decided in model.cpp upload_ml_tables)
+    case StepKind::TreeEnsemble: {
+      const TreePack &t = *x.tree;
+      kern::tree_walk(stream, buf(x.in0), int(p.buf_per_row[size_t(x.in0)]), d.tab, t.nodes, t.trees, d.W, int(t.W), int(t.slices), buf(x.out), nr);
       break;
-    case StepKind::TreeReduce:
-      kern::tree_reduce(stream, buf(x.in0), d.bias, d.cst, buf(x.out), nr, int(x.tree_W), int(x.tree_slices), x.tree_count, x.tree_average, x.tree_mode,
-                        x.tree_signed);
+    }
+    case StepKind::TreeReduce: {
+      const TreePack &t = *x.tree;
+      kern::tree_reduce(stream, buf(x.in0), d.bias, d.cst, buf(x.out), nr, int(t.W), int(t.slices), t.trees, t.average, x.out_mode, t.is_signed);
       break;
-    case StepKind::SvmKernel:
-      kern::svm_kernel(stream, buf(x.in0), int(p.buf_per_row[size_t(x.in0)]), int(x.svm_F_pad), x.svm_kernel, d.bias, d.W, d.shift, d.scale, d.tab,
-                       buf(x.out), nr, int(x.svm_slices), int(x.svm_Q), int(x.svm_QW), x.svm_gamma, x.svm_coef0, x.svm_degree);
+    }
+    case StepKind::SvmKernel: {
+      const SvmPack &v = *x.svm;
+      kern::svm_kernel(stream, buf(x.in0), int(p.buf_per_row[size_t(x.in0)]), int(v.F_pad), v.kernel, d.bias, d.W, d.shift, d.scale, d.tab, buf(x.out),
+                       nr, int(v.slices), int(v.Q), int(v.QW), v.gamma, v.coef0, v.degree);
       break;
+    }
     case StepKind::SvmReduce:
-      kern::svm_reduce(stream, buf(x.in0), d.tab, d.bias, d.cst, d.scale, d.shift, buf(x.out), nr, int(x.svm_Q), int(x.svm_classes), x.svm_mode);
+      kern::svm_reduce(stream, buf(x.in0), d.tab, d.bias, d.cst, d.scale, d.shift, buf(x.out), nr, int(x.svm->Q), int(x.svm->classes), x.out_mode);
       break;
-    case StepKind::Prep:
-      kern::prep(stream, buf(x.in0), int(x.prep_F_in), d.tab, d.scale, d.W, int(x.W.size() / 2), buf(x.out), int(x.prep_F), nr, int(x.prep_R),
-                 x.prep_strict ? ctx.prep_err : nullptr);
+    case StepKind::Prep: {
+      const PrepPack &q = *x.prep;
+      kern::prep(stream, buf(x.in0), int(q.F_in), d.tab, d.scale, d.W, int(q.tab.size() / 2), buf(x.out), int(q.F), nr, int(q.R),
+                 q.strict ? ctx.prep_err : nullptr);
       break;
+    }
   }
 }
 

@@ -2,6 +2,9 @@
 // each selected GPU, once.  (engine.rs:49-55: the reference builds a Tract plan here; nothing model-dependent is left per chunk.)
 #include "runtime.hpp"
 #include "../host/onnx_model.hpp"
+#include "../host/prep.hpp"
+#include "../host/svm.hpp"
+#include "../host/trees.hpp"
 
 #include <cstring>
 
@@ -23,6 +26,12 @@ float *upload(const std::vector<float> &v, hipStream_t stream) {
     hip_fail(e, "hipMemcpy(weights)");
   }
   return d;
+}
+uint32_t *upload(const std::vector<uint32_t> &v, hipStream_t stream) {
+  if (v.empty()) return nullptr;
+  std::vector<float> words(v.size());  // (same bits: the float upload moves them)
+  std::memcpy(words.data(), v.data(), words.size() * 4);
+  return reinterpret_cast<uint32_t *>(upload(words, stream));
 }
 
 }  // namespace
@@ -137,6 +146,41 @@ bool upload_conv_patch(const LoadedModel &m, DeviceStep &d, size_t i, hipStream_
   return false;
 }
 
+// The tables of an ai.onnx.ml step (host/trees.hpp, svm.hpp, prep.hpp packs), each into the DeviceStep pointer launch_plain (exec.cpp)
+// passes to its kernel; false: not such a step
+bool upload_ml_tables(const Step &s, DeviceStep &d, hipStream_t us) {
+  switch (s.kind) {
+    case StepKind::TreeEnsemble:
+      d.tab = upload(s.tree->tab, us);
+      d.W = upload(s.tree->leaves, us);
+      return true;
+    case StepKind::TreeReduce:
+      d.bias = upload(s.tree->base, us);
+      d.cst = upload(s.tree->labels, us);
+      return true;
+    case StepKind::SvmKernel:
+      d.W = upload(s.svm->sv, us);
+      d.scale = upload(s.svm->coef, us);
+      d.shift = upload(s.svm->sv_norm, us);
+      d.bias = upload(s.svm->center, us);
+      d.tab = upload(s.svm->slice_tile, us);
+      return true;
+    case StepKind::SvmReduce:
+      d.bias = upload(s.svm->rho, us);
+      d.cst = upload(s.svm->labels, us);
+      d.scale = upload(s.svm->prob_a, us);
+      d.shift = upload(s.svm->prob_b, us);
+      d.tab = upload(s.svm->class_slice, us);
+      return true;
+    case StepKind::Prep:
+      d.tab = upload(s.prep->desc, us);
+      d.scale = upload(s.prep->cst, us);
+      d.W = upload(s.prep->tab, us);
+      return true;
+    default: return false;
+  }
+}
+
 }  // namespace
 
 void upload_to_device(const LoadedModel &m, DeviceModel &dm) {
@@ -165,6 +209,7 @@ void upload_to_device(const LoadedModel &m, DeviceModel &dm) {
         break;
       }
       default:
+        if (upload_ml_tables(s, d, us)) continue;
         if (s.kind == StepKind::Conv2d) {
           const kern::ConvGeom g = conv_geom(s);
           if (!kern::conv2d_generic_supported(g))
@@ -180,11 +225,6 @@ void upload_to_device(const LoadedModel &m, DeviceModel &dm) {
     if (!d.cst) d.cst = upload(s.cst, us);  // (a split stem keeps its bf16 blob there: convolutions have no constants)
     d.scale = upload(s.scale, us);
     d.shift = upload(s.shift, us);
-    if (!s.tree_tab.empty()) {
-      std::vector<float> words(s.tree_tab.size());  // (same bits: upload() moves floats)
-      std::memcpy(words.data(), s.tree_tab.data(), words.size() * 4);
-      d.tab = reinterpret_cast<uint32_t *>(upload(words, us));
-    }
   }
 }
 

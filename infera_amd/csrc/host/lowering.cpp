@@ -39,6 +39,14 @@ struct PrepVal {
   int src = -1;
   std::vector<PrepCol> cols;
   std::vector<std::string> origin;  // the ONNX nodes absorbed so far
+  void add_origin(const std::string &o) {
+    if (std::find(origin.begin(), origin.end(), o) == origin.end()) origin.push_back(o);
+  }
+  // q's columns after these (q reads the same source)
+  void append(const PrepVal &q) {
+    cols.insert(cols.end(), q.cols.begin(), q.cols.end());
+    for (const auto &o : q.origin) add_origin(o);
+  }
 };
 
 struct Val {
@@ -73,6 +81,31 @@ std::string shape_str(const std::vector<int64_t> &s) {
 
 [[noreturn]] void unsupported(const NodeDef &n, const std::string &why) {
   throw InferaError::onnx("node '" + (n.name.empty() ? n.op : n.name) + "' (" + n.op + "): " + why);
+}
+
+// "Op:name" (or "Op"): how a step's origin names a node
+std::string node_label(const NodeDef &n) { return n.op + (n.name.empty() ? "" : ":" + n.name); }
+
+Val const_val(std::shared_ptr<TensorData> t) {
+  Val v;
+  v.is_const = true;
+  v.c = std::move(t);
+  v.shape = v.c->dims;
+  return v;
+}
+Val const_f32(std::vector<float> f, std::vector<int64_t> dims) {
+  auto t = std::make_shared<TensorData>();
+  t->dtype = onnx::kFloat;
+  t->dims = std::move(dims);
+  t->f32 = std::move(f);
+  return const_val(std::move(t));
+}
+Val const_i64(std::vector<int64_t> i, std::vector<int64_t> dims) {
+  auto t = std::make_shared<TensorData>();
+  t->dtype = onnx::kInt64;
+  t->dims = std::move(dims);
+  t->i64 = std::move(i);
+  return const_val(std::move(t));
 }
 
 struct Lowerer {
@@ -128,13 +161,7 @@ struct Lowerer {
     auto it = vals.find(n.inputs[i]);
     if (it != vals.end()) return it->second;
     auto ci = m.initializers.find(n.inputs[i]);
-    if (ci != m.initializers.end()) {
-      Val v;
-      v.is_const = true;
-      v.c = ci->second;
-      v.shape = ci->second->dims;
-      return vals[n.inputs[i]] = v;
-    }
+    if (ci != m.initializers.end()) return vals[n.inputs[i]] = const_val(ci->second);
     unsupported(n, "input '" + n.inputs[i] + "' is not produced by any earlier node");
   }
   bool has_input(const NodeDef &n, size_t i) const { return i < n.inputs.size() && !n.inputs[i].empty(); }
@@ -171,13 +198,27 @@ struct Lowerer {
     if (it == producer.end()) return nullptr;
     return &plan.steps[size_t(it->second)];
   }
+  // The last step, if it wrote `buf` and nothing but this node reads `buf`: it can be folded into this node and removed (drop_tail)
+  const Step *sole_tail(int buf) {
+    auto pit = producer.find(buf);
+    if (buf <= 0 || pit == producer.end() || pit->second != int(plan.steps.size()) - 1 || live_uses(buf) != 1) return nullptr;
+    return &plan.steps.back();
+  }
+  void drop_tail() {
+    producer.erase(plan.steps.back().out);
+    plan.steps.pop_back();
+  }
 
-  Step &emit(Step s, const NodeDef &n, const std::vector<int64_t> &out_shape) {
-    s.out = new_buf(out_shape);
-    s.origin = n.op + (n.name.empty() ? "" : ":" + n.name);
+  // Appends `s` writing a new buffer of `shape`; returns the buffer.
+  int push_step(Step s, const std::vector<int64_t> &shape) {
+    s.out = new_buf(shape);
     plan.steps.push_back(std::move(s));
     producer[plan.steps.back().out] = int(plan.steps.size()) - 1;
-    set_act(n, plan.steps.back().out, out_shape);
+    return plan.steps.back().out;
+  }
+  Step &emit(Step s, const NodeDef &n, const std::vector<int64_t> &out_shape) {
+    s.origin = node_label(n);
+    set_act(n, push_step(std::move(s), out_shape), out_shape);
     return plan.steps.back();
   }
 
@@ -204,41 +245,33 @@ struct Lowerer {
     std::vector<double> fs(size_t(K), 1.0), ft(size_t(K), 0.0);
     bool folded = false;
     std::string folded_origin;
-    for (;;) {
-      auto pit = producer.find(in_buf);
-      if (in_buf <= 0 || pit == producer.end() || pit->second != int(plan.steps.size()) - 1 || live_uses(in_buf) != 1) break;
-      const Step &p = plan.steps.back();
+    while (const Step *tail = sole_tail(in_buf)) {
+      const Step &p = *tail;
       if (p.kind == StepKind::AffineChannel && p.act == Act::None && p.S == 1 && p.C == K) {  // BatchNormalization of the features
         for (int64_t k = 0; k < K; k++) {
           ft[size_t(k)] += fs[size_t(k)] * double(p.shift[size_t(k)]);
           fs[size_t(k)] *= double(p.scale[size_t(k)]);
         }
-        folded = true;
-        folded_origin = p.origin + (folded_origin.empty() ? "" : "+" + folded_origin);
-        in_buf = p.in0;
-        producer.erase(pit);
-        plan.steps.pop_back();
-        continue;
-      }
-      if (p.kind != StepKind::BinaryConst || p.act != Act::None || int64_t(p.cst.size()) != K) break;
-      if (p.bop != '+' && p.bop != '-' && p.bop != '*' && !(p.bop == '/' && !p.const_left)) break;
-      for (int64_t k = 0; k < K; k++) {
-        const double c = p.cst[size_t(k)], sk = fs[size_t(k)], tk = ft[size_t(k)];
-        switch (p.bop) {
-          case '+': ft[size_t(k)] = sk * c + tk; break;
-          case '-':
-            if (p.const_left) { fs[size_t(k)] = -sk; ft[size_t(k)] = sk * c + tk; }  // c - u
-            else ft[size_t(k)] = tk - sk * c;
-            break;
-          case '*': fs[size_t(k)] = sk * c; break;
-          default: fs[size_t(k)] = sk / c; break;
+      } else {
+        if (p.kind != StepKind::BinaryConst || p.act != Act::None || int64_t(p.cst.size()) != K) break;
+        if (p.bop != '+' && p.bop != '-' && p.bop != '*' && !(p.bop == '/' && !p.const_left)) break;
+        for (int64_t k = 0; k < K; k++) {
+          const double c = p.cst[size_t(k)], sk = fs[size_t(k)], tk = ft[size_t(k)];
+          switch (p.bop) {
+            case '+': ft[size_t(k)] = sk * c + tk; break;
+            case '-':
+              if (p.const_left) { fs[size_t(k)] = -sk; ft[size_t(k)] = sk * c + tk; }  // c - u
+              else ft[size_t(k)] = tk - sk * c;
+              break;
+            case '*': fs[size_t(k)] = sk * c; break;
+            default: fs[size_t(k)] = sk / c; break;
+          }
         }
       }
       folded = true;
       folded_origin = p.origin + (folded_origin.empty() ? "" : "+" + folded_origin);
       in_buf = p.in0;
-      producer.erase(pit);
-      plan.steps.pop_back();
+      drop_tail();
     }
     // A wide layer over rows whose length is not a multiple of 4 floats (30 features, ...): copy the rows into a
     // zero-padded matrix first so the MFMA kernels can read them in 16-byte quads; the padded k carry zero weights.
@@ -251,11 +284,8 @@ struct Lowerer {
       p.in0 = in_buf;
       p.K = K;
       p.M = Kp;
-      p.out = new_buf({a_shape[0], Kp});
-      p.origin = n.op + (n.name.empty() ? "" : ":" + n.name) + "[pad]";
-      plan.steps.push_back(std::move(p));
-      producer[plan.steps.back().out] = int(plan.steps.size()) - 1;
-      in_buf = plan.steps.back().out;
+      p.origin = node_label(n) + "[pad]";
+      in_buf = push_step(std::move(p), {a_shape[0], Kp});
     }
     Step s;
     s.kind = StepKind::Dense;
@@ -339,20 +369,9 @@ struct Lowerer {
     if (a.is_const && b.is_const) {  // fold
       const auto &x = cf32(n, a), &y = cf32(n, b);
       if (a.shape != b.shape && x.size() != 1 && y.size() != 1) unsupported(n, "constant folding needs equal shapes or a scalar");
-      auto t = std::make_shared<TensorData>();
-      t->dtype = onnx::kFloat;
-      t->dims = x.size() >= y.size() ? a.shape : b.shape;
-      size_t cnt = std::max(x.size(), y.size());
-      t->f32.resize(cnt);
-      for (size_t i = 0; i < cnt; i++) {
-        float u = x[x.size() == 1 ? 0 : i], v = y[y.size() == 1 ? 0 : i];
-        t->f32[i] = fold_bop(op, u, v);
-      }
-      Val v;
-      v.is_const = true;
-      v.c = t;
-      v.shape = t->dims;
-      vals[n.outputs[0]] = v;
+      std::vector<float> f(std::max(x.size(), y.size()));
+      for (size_t i = 0; i < f.size(); i++) f[i] = fold_bop(op, x[x.size() == 1 ? 0 : i], y[y.size() == 1 ? 0 : i]);
+      vals[n.outputs[0]] = const_f32(std::move(f), x.size() >= y.size() ? a.shape : b.shape);
       return;
     }
     if (!a.is_const && !b.is_const && op == '*' && a.shape == b.shape) {
@@ -360,12 +379,9 @@ struct Lowerer {
       // which then folds into the epilogue of the convolution / layer that produced x when nothing else reads it
       for (int side = 0; side < 2; side++) {
         const Val &x = side ? b : a, &sg = side ? a : b;
-        auto pit = producer.find(sg.buf);
-        if (sg.buf <= 0 || pit == producer.end() || pit->second != int(plan.steps.size()) - 1 || live_uses(sg.buf) != 1) continue;
-        const Step &ps = plan.steps.back();
-        if (ps.kind != StepKind::Unary || ps.act != Act::Sigmoid || ps.in0 != x.buf) continue;
-        producer.erase(pit);
-        plan.steps.pop_back();
+        const Step *ps = sole_tail(sg.buf);
+        if (!ps || ps->kind != StepKind::Unary || ps->act != Act::Sigmoid || ps->in0 != x.buf) continue;
+        drop_tail();
         alias_edges[x.buf]++;  // the Sigmoid node no longer consumes x
         apply_unary(n, side ? 1 : 0, Act::Swish, 0.f, 0.f, "Swish");
         return;
@@ -450,7 +466,7 @@ struct Lowerer {
           else if (op == '*') sc[k] = c;
           else sc[k] = 1.0 / c;
         }
-        const std::string label = n.op + (n.name.empty() ? "" : ":" + n.name);
+        const std::string label = node_label(n);
         Step *p = fusable_producer(n, const_left ? 1 : 0);
         if (p && p->kind == StepKind::AffineChannel && p->act == Act::None && size_t(p->S) == S && size_t(p->C) == C) {
           for (size_t k = 0; k < C; k++) {
@@ -501,15 +517,7 @@ struct Lowerer {
 
   // ---- constant folding of the integer (shape) sub-graphs exporters emit around Reshape ----
   void set_const_i64(const NodeDef &n, std::vector<int64_t> v, std::vector<int64_t> dims) {
-    auto t = std::make_shared<TensorData>();
-    t->dtype = onnx::kInt64;
-    t->dims = std::move(dims);
-    t->i64 = std::move(v);
-    Val o;
-    o.is_const = true;
-    o.c = t;
-    o.shape = t->dims;
-    vals[n.outputs[0]] = o;
+    vals[n.outputs[0]] = const_i64(std::move(v), std::move(dims));
   }
   void fold_int_binary(const NodeDef &n, char op, const Val &a, const Val &b) {
     const auto &x = a.c->i64, &y = b.c->i64;
@@ -556,7 +564,7 @@ struct Lowerer {
         if (v[i] != v[0] + int64_t(i)) unsupported(n, "only a contiguous column range");
       if (v[0] < 0 || v[0] + int64_t(v.size()) > d.shape[1]) unsupported(n, "column index out of range");
       const Val src = d;
-      emit_slice_cols(n, src, v[0], v[0] + int64_t(v.size()), n.outputs[0]);
+      emit_slice_cols(node_label(n), src, v[0], v[0] + int64_t(v.size()), n.outputs[0]);
       if (ix.shape.empty()) {  // scalar index: the axis disappears ([rows] instead of [rows, 1])
         Val &o = vals[n.outputs[0]];
         o.shape = {src.shape[0]};
@@ -576,21 +584,15 @@ struct Lowerer {
       for (auto i : ix.c->i64) o.push_back(d.c->i64[at(i)]);
       set_const_i64(n, std::move(o), ix.shape);
     } else {
-      auto t = std::make_shared<TensorData>();
-      t->dtype = onnx::kFloat;
-      t->dims = ix.shape;
-      for (auto i : ix.c->i64) t->f32.push_back(d.c->f32[at(i)]);
-      Val o;
-      o.is_const = true;
-      o.c = t;
-      o.shape = t->dims;
-      vals[n.outputs[0]] = o;
+      std::vector<float> o;
+      for (auto i : ix.c->i64) o.push_back(d.c->f32[at(i)]);
+      vals[n.outputs[0]] = const_f32(std::move(o), ix.shape);
     }
   }
   // feature-axis slice of a [rows, K] activation: out = in[:, b:e]
   // ... or a channel range of an [N,C,H,W] activation: channels [b, e) are one contiguous block of every sample, in
   // NCHW and (whole quads) in the channel-quad layout alike
-  void emit_slice_cols(const NodeDef &n, const Val &a, int64_t b, int64_t e, const std::string &out_name) {
+  void emit_slice_cols(const std::string &origin, const Val &a, int64_t b, int64_t e, const std::string &out_name) {
     const int64_t inner = prod(a.shape, 2);
     std::vector<int64_t> oshape = a.shape;
     oshape[1] = e - b;
@@ -599,12 +601,9 @@ struct Lowerer {
     s.in0 = a.buf;
     s.col_off = b * inner;
     s.K = (e - b) * inner;
-    s.out = new_buf(oshape);
-    s.origin = n.op + (n.name.empty() ? "" : ":" + n.name);
-    plan.steps.push_back(std::move(s));
-    producer[plan.steps.back().out] = int(plan.steps.size()) - 1;
+    s.origin = origin;
     Val v;
-    v.buf = plan.steps.back().out;
+    v.buf = push_step(std::move(s), oshape);
     v.shape = oshape;
     vals[out_name] = v;
     buf_names[v.buf].push_back(out_name);
@@ -628,7 +627,7 @@ struct Lowerer {
     int64_t off = 0;
     for (int64_t i = 0; i < nout; i++) {
       if (sizes[size_t(i)] <= 0) unsupported(n, "empty split piece");
-      if (!n.outputs[size_t(i)].empty() && uses.count(n.outputs[size_t(i)])) emit_slice_cols(n, src, off, off + sizes[size_t(i)], n.outputs[size_t(i)]);
+      if (!n.outputs[size_t(i)].empty() && uses.count(n.outputs[size_t(i)])) emit_slice_cols(node_label(n), src, off, off + sizes[size_t(i)], n.outputs[size_t(i)]);
       off += sizes[size_t(i)];
     }
   }
@@ -655,7 +654,7 @@ struct Lowerer {
       e = std::clamp<int64_t>(e, b, K);
       if (e == b) unsupported(n, "empty slice");
       const Val src = d;
-      emit_slice_cols(n, src, b, e, n.outputs[0]);
+      emit_slice_cols(node_label(n), src, b, e, n.outputs[0]);
       return;
     }
     if (!d.is_const || d.c->dtype != onnx::kInt64 || d.shape.size() != 1) unsupported(n, "only 1-D constant integer data is folded");
@@ -691,15 +690,9 @@ struct Lowerer {
         for (float f : a.c->f32) o.push_back(int64_t(f));
         set_const_i64(n, std::move(o), a.shape);
       } else {
-        auto t = std::make_shared<TensorData>();
-        t->dtype = onnx::kFloat;
-        t->dims = a.shape;
-        for (int64_t i : a.c->i64) t->f32.push_back(float(i));
-        Val o;
-        o.is_const = true;
-        o.c = t;
-        o.shape = t->dims;
-        vals[n.outputs[0]] = o;
+        std::vector<float> o;
+        for (int64_t i : a.c->i64) o.push_back(float(i));
+        vals[n.outputs[0]] = const_f32(std::move(o), a.shape);
       }
       return;
     }
@@ -867,7 +860,7 @@ struct Lowerer {
       v.shape = new_shape;
       if (n.op != "Identity") {
         PrepVal p = *a.pv;
-        add_origin(p, n);
+        p.add_origin(node_label(n));
         v.pv = std::make_shared<const PrepVal>(std::move(p));
       }
       vals[n.outputs[0]] = v;
@@ -1202,11 +1195,8 @@ struct Lowerer {
     for (int64_t i = 3; i < rank; i++) bshape.push_back(a.shape[size_t(i)]);
     std::vector<int64_t> vshape = a.shape;
     std::swap(vshape[1], vshape[2]);
-    s.out = new_buf(bshape);
-    s.origin = n.op + (n.name.empty() ? "" : ":" + n.name);
-    plan.steps.push_back(std::move(s));
-    producer[plan.steps.back().out] = int(plan.steps.size()) - 1;
-    set_act(n, plan.steps.back().out, vshape);
+    s.origin = node_label(n);
+    set_act(n, push_step(std::move(s), bshape), vshape);
   }
   // Sum of any number of equal-shaped activations: a chain of residual adds
   void sum(const NodeDef &n) {
@@ -1280,20 +1270,12 @@ struct Lowerer {
     else if (op == "LRN") lrn(n);
     else if (op == "Transpose") transpose(n);
     else if (op == "Constant") {
-      Val v;
-      v.is_const = true;
-      if (auto *a = n.attr("value"); a && a->t) {
-        v.c = a->t;
-      } else {  // scalar / 1-D attribute forms (opset 12+)
-        auto t = std::make_shared<TensorData>();
-        if (auto *f = n.attr("value_float")) { t->dtype = onnx::kFloat; t->f32 = {f->f}; }
-        else if (auto *i = n.attr("value_int")) { t->dtype = onnx::kInt64; t->i64 = {i->i}; }
-        else if (auto *is = n.attr_ints("value_ints")) { t->dtype = onnx::kInt64; t->i64 = *is; t->dims = {int64_t(is->size())}; }
-        else unsupported(n, "only the value / value_float / value_int / value_ints forms are supported");
-        v.c = t;
-      }
-      v.shape = v.c->dims;
-      vals[n.outputs[0]] = v;
+      if (auto *a = n.attr("value"); a && a->t) vals[n.outputs[0]] = const_val(a->t);
+      // scalar / 1-D attribute forms (opset 12+)
+      else if (auto *f = n.attr("value_float")) vals[n.outputs[0]] = const_f32({f->f}, {});
+      else if (auto *i = n.attr("value_int")) set_const_i64(n, {i->i}, {});
+      else if (auto *is = n.attr_ints("value_ints")) set_const_i64(n, *is, {int64_t(is->size())});
+      else unsupported(n, "only the value / value_float / value_int / value_ints forms are supported");
     } else {
       unsupported(n, "unsupported operator");
     }
@@ -1303,17 +1285,6 @@ struct Lowerer {
   // the reference, engine.rs:49-56).  Each is rewritten into the standard operators above, so a Scaler folds into the
   // linear model behind it and a LinearClassifier's scores go through the Dense (+Softmax) kernels; semantics follow
   // the ONNX-ML operator specification (tract's sources are not in /root/reference).
-  Val const_f32(std::vector<float> v, std::vector<int64_t> dims) {
-    auto t = std::make_shared<TensorData>();
-    t->dtype = onnx::kFloat;
-    t->dims = std::move(dims);
-    t->f32 = std::move(v);
-    Val o;
-    o.is_const = true;
-    o.c = t;
-    o.shape = t->dims;
-    return o;
-  }
   static NodeDef std_node(const NodeDef &from, const char *op, std::vector<std::string> in, std::string out) {
     NodeDef d;
     d.op = op;
@@ -1353,13 +1324,28 @@ struct Lowerer {
       lower_node(d);
     } else unsupported(n, "post_transform " + pt);
   }
+  // output 0 of n = a0 + step * index (the label of an evenly spaced class table; not both a0 = 0 and step = 1): a Mul and / or an Add on the
+  // whole-numbered `index`.  (Tables of int64 labels pass their a0 and step as doubles: float(double(v)) == float(v) for |v| < 2^53.)
+  void label_from_index(const NodeDef &n, std::string index, double a0, double step) {
+    const std::string tmp = n.outputs[0] + "\x01";
+    if (step != 1.0) {
+      vals[tmp + "step"] = const_f32({float(step)}, {});
+      const std::string nxt = a0 == 0.0 ? n.outputs[0] : tmp + "scaled";
+      if (nxt != n.outputs[0]) uses[nxt] = 1;
+      lower_node(std_node(n, "Mul", {index, tmp + "step"}, nxt));
+      index = nxt;
+    }
+    if (a0 != 0.0) {
+      vals[tmp + "first"] = const_f32({float(a0)}, {});
+      lower_node(std_node(n, "Add", {index, tmp + "first"}, n.outputs[0]));
+    }
+  }
   // ArrayFeatureExtractor: Y = X[..., indices].  Two forms occur in exported pipelines: a constant class table indexed
   // by the ArgMax of the scores (label lookup; the table must be evenly spaced, then it is one multiply-add on the
   // index), and a contiguous column range picked out of the feature matrix.
   void array_feature_extractor(const NodeDef &n) {
     const Val &x = get(n, 0);
     const Val &ix = get(n, 1);
-    const std::string tmp = n.outputs[0] + "\x01";
     if (x.is_const && !ix.is_const) {
       if (!int_bufs.count(ix.buf)) unsupported(n, "indices must be whole numbers (an ArgMax output)");
       if (x.shape.size() != 1) unsupported(n, "only a 1-D class table");
@@ -1370,19 +1356,8 @@ struct Lowerer {
       const double a0 = tab[0], step = tab[1] - tab[0];
       for (size_t i = 0; i < tab.size(); i++)
         if (tab[i] != a0 + step * double(i)) unsupported(n, "class table must be evenly spaced (label = a + b * index)");
-      std::string cur = n.inputs[1];
-      if (step == 1.0 && a0 == 0.0) { lower_node(std_node(n, "Identity", {cur}, n.outputs[0])); return; }
-      if (step != 1.0) {
-        vals[tmp + "step"] = const_f32({float(step)}, {});
-        const std::string nxt = a0 == 0.0 ? n.outputs[0] : tmp + "scaled";
-        if (nxt != n.outputs[0]) uses[nxt] = 1;
-        lower_node(std_node(n, "Mul", {cur, tmp + "step"}, nxt));
-        cur = nxt;
-      }
-      if (a0 != 0.0) {
-        vals[tmp + "first"] = const_f32({float(a0)}, {});
-        lower_node(std_node(n, "Add", {cur, tmp + "first"}, n.outputs[0]));
-      }
+      if (step == 1.0 && a0 == 0.0) lower_node(std_node(n, "Identity", {n.inputs[1]}, n.outputs[0]));
+      else label_from_index(n, n.inputs[1], a0, step);
       return;
     }
     if (!x.is_const && ix.is_const && x.shape.size() == 2 && ix.c->dtype == onnx::kInt64 && !ix.c->i64.empty()) {
@@ -1391,136 +1366,79 @@ struct Lowerer {
         if (v[i] != v[0] + int64_t(i)) unsupported(n, "only a contiguous column range");
       if (v[0] < 0 || v[0] + int64_t(v.size()) > x.shape[1]) unsupported(n, "column index out of range");
       const Val src = x;
-      emit_slice_cols(n, src, v[0], v[0] + int64_t(v.size()), n.outputs[0]);
+      emit_slice_cols(node_label(n), src, v[0], v[0] + int64_t(v.size()), n.outputs[0]);
       return;
     }
     unsupported(n, "only (constant table, index activation) or (activation, constant contiguous indices)");
   }
-  // TreeEnsembleRegressor / TreeEnsembleClassifier: a TreeEnsemble step (walk, per-slice partial sums) and a TreeReduce step (slices
-  // summed in fixed order, AVERAGE, base_values, binary expansion or the label), then post_transform on the scores
-  void tree_ensemble(const NodeDef &n) {
-    TreePack tp;
-    const Val &x = get(n, 0);
-    if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, features] activations");
-    try {
-      tp = pack_tree_ensemble(n, x.shape[1]);
-    } catch (const TreeError &e) {
-      unsupported(n, e.what());
-    }
-    const int xbuf = x.buf;
-    const int64_t rows = x.shape[0];
-    Step w;
-    w.kind = StepKind::TreeEnsemble;
-    w.in0 = xbuf;
-    w.tree_tab = std::move(tp.tab);
-    w.W = std::move(tp.leaves);
-    w.tree_count = tp.trees;
-    w.tree_nodes = tp.nodes;
-    w.tree_max_depth = tp.max_depth;
-    w.tree_W = tp.W;
-    w.tree_E = tp.E;
-    w.tree_slices = tp.slices;
-    w.tree_average = tp.average;
-    w.tree_signed = tp.is_signed;
-    const std::string tmp = n.outputs[0] + "\x01";
-    const bool cls = tp.classifier;
+  // The two-stage head of a tree ensemble / SVM node: kernel step `k` writes its partials [rows, part_cols]; a copy of `r` (the reduce
+  // step's kind and pack) turns them into a classifier's label (output 0, when read) with `label_mode`, and another into the raw scores
+  // [rows, score_cols] with `score_mode`, which post_transform turns into the scores output
+  void ml_head(const NodeDef &n, bool cls, Step k, int64_t part_cols, Step r, int label_mode, int score_mode, int64_t score_cols) {
+    const int64_t rows = get_raw(n, 0).shape[0];
     const bool want_label = cls && wanted(n, 0), want_scores = cls ? wanted(n, 1) : true;
-    w.tree_mode = want_scores ? (tp.binary ? kTreeBinaryScores : kTreeScores) : (tp.binary ? kTreeBinaryLabel : kTreeLabel);
-    NodeDef walk = n;
-    walk.outputs = {tmp + "partial"};
-    const int part = emit(std::move(w), walk, {rows, 2 * tp.slices * tp.W}).out;  // (f64 partials as f32 pairs)
-    auto reduce = [&](int mode, const std::string &out, int64_t cols) {
-      Step r;
-      r.kind = StepKind::TreeReduce;
-      r.in0 = part;
-      r.tree_W = tp.W;
-      r.tree_E = tp.E;
-      r.tree_slices = tp.slices;
-      r.tree_count = tp.trees;
-      r.tree_average = tp.average;
-      r.tree_signed = tp.is_signed;
-      r.tree_mode = mode;
-      r.bias = tp.base;
-      r.cst = tp.labels;
+    const std::string tmp = n.outputs[0] + "\x01";
+    k.out_mode = want_scores ? score_mode : label_mode;
+    NodeDef kn = n;
+    kn.outputs = {tmp + "partial"};
+    r.in0 = emit(std::move(k), kn, {rows, part_cols}).out;
+    auto reduce = [&](int mode, const std::string &out, const std::vector<int64_t> &shape) {
+      Step s = r;
+      s.out_mode = mode;
       NodeDef d = n;
       d.outputs = {out};
-      return emit(std::move(r), d, cols ? std::vector<int64_t>{rows, cols} : std::vector<int64_t>{rows}).out;
+      return emit(std::move(s), d, shape).out;
     };
-    if (want_label) int_bufs.insert(reduce(tp.binary ? kTreeBinaryLabel : kTreeLabel, n.outputs[0], 0));
+    if (want_label) int_bufs.insert(reduce(label_mode, n.outputs[0], {rows}));
     if (want_scores) {
       const std::string raw = tmp + "raw";
       uses[raw] = 1;
-      reduce(tp.binary ? kTreeBinaryScores : kTreeScores, raw, tp.E);
+      reduce(score_mode, raw, {rows, score_cols});
       ml_post_transform(n, raw, cls ? n.outputs[1] : n.outputs[0]);
     }
+  }
+  // TreeEnsembleRegressor / TreeEnsembleClassifier: a TreeEnsemble step (walk, per-slice partial sums) and a TreeReduce step (slices
+  // summed in fixed order, AVERAGE, base_values, binary expansion or the label), then post_transform on the scores
+  void tree_ensemble(const NodeDef &n) {
+    std::shared_ptr<const TreePack> tp;
+    const Val &x = get(n, 0);
+    if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, features] activations");
+    try {
+      tp = std::make_shared<const TreePack>(pack_tree_ensemble(n, x.shape[1]));
+    } catch (const TreeError &e) {
+      unsupported(n, e.what());
+    }
+    Step w, r;
+    w.kind = StepKind::TreeEnsemble;
+    w.in0 = x.buf;
+    r.kind = StepKind::TreeReduce;
+    w.tree = r.tree = tp;
+    // (the partials are f64, as f32 pairs)
+    ml_head(n, tp->classifier, std::move(w), 2 * tp->slices * tp->W, std::move(r), tp->binary ? kTreeBinaryLabel : kTreeLabel,
+            tp->binary ? kTreeBinaryScores : kTreeScores, tp->E);
   }
   // SVMRegressor / SVMClassifier: an SvmKernel step (X . S^T on the matrix cores, the kernel function, times the coefficients: per-slice
   // partial sums) and an SvmReduce step (slices summed in fixed order, rho, then the value, one-class sign, pairwise decisions, votes and
   // label, or Platt + pairwise coupling), then post_transform on the scores
   void svm(const NodeDef &n) {
-    SvmPack sp;
+    std::shared_ptr<const SvmPack> sp;
     const Val &x = get(n, 0);
     if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, features] activations");
     try {
-      sp = pack_svm(n, x.shape[1]);
+      sp = std::make_shared<const SvmPack>(pack_svm(n, x.shape[1]));
     } catch (const SvmError &e) {
       unsupported(n, e.what());
     }
-    const int64_t rows = x.shape[0], C = sp.classes, P = C * (C - 1) / 2;
-    const bool cls = sp.classifier;
-    const bool want_label = cls && wanted(n, 0), want_scores = cls ? wanted(n, 1) : true;
-    const int score_mode = !cls ? (sp.one_class ? kSvmOneClass : kSvmValue) : sp.probabilities ? kSvmProb : kSvmDecision;
-    const int64_t score_cols = !cls ? 1 : sp.probabilities ? C : (C == 2 ? 2 : P);
-    auto fields = [&](Step &s, int mode) {
-      s.svm_kernel = sp.kernel;
-      s.svm_mode = mode;
-      s.svm_degree = sp.degree;
-      s.svm_gamma = sp.gamma;
-      s.svm_coef0 = sp.coef0;
-      s.svm_F = sp.F;
-      s.svm_F_pad = sp.F_pad;
-      s.svm_n_sv = sp.n_sv;
-      s.svm_tiles = sp.tiles;
-      s.svm_Q = sp.Q;
-      s.svm_QW = sp.QW;
-      s.svm_prob = sp.probabilities;
-      s.svm_slices = sp.slices;
-      s.svm_classes = C;
-    };
-    Step k;
+    const int64_t C = sp->classes, P = C * (C - 1) / 2;
+    const bool cls = sp->classifier;
+    const int score_mode = !cls ? (sp->one_class ? kSvmOneClass : kSvmValue) : sp->probabilities ? kSvmProb : kSvmDecision;
+    const int64_t score_cols = !cls ? 1 : sp->probabilities ? C : (C == 2 ? 2 : P);
+    Step k, r;
     k.kind = StepKind::SvmKernel;
     k.in0 = x.buf;
-    fields(k, want_scores ? score_mode : kSvmLabel);
-    k.W = std::move(sp.sv);
-    k.scale = std::move(sp.coef);
-    k.shift = std::move(sp.sv_norm);
-    k.bias = std::move(sp.center);
-    k.tree_tab = std::move(sp.slice_tile);
-    const std::string tmp = n.outputs[0] + "\x01";
-    NodeDef kn = n;
-    kn.outputs = {tmp + "partial"};
-    const int part = emit(std::move(k), kn, {rows, sp.slices * sp.Q}).out;
-    auto reduce = [&](int mode, const std::string &out, int64_t cols) {
-      Step r;
-      r.kind = StepKind::SvmReduce;
-      r.in0 = part;
-      fields(r, mode);
-      r.bias = sp.rho;
-      r.cst = sp.labels;
-      r.scale = sp.prob_a;
-      r.shift = sp.prob_b;
-      r.tree_tab = sp.class_slice;
-      NodeDef d = n;
-      d.outputs = {out};
-      return emit(std::move(r), d, cols ? std::vector<int64_t>{rows, cols} : std::vector<int64_t>{rows}).out;
-    };
-    if (want_label) int_bufs.insert(reduce(kSvmLabel, n.outputs[0], 0));
-    if (want_scores) {
-      const std::string raw = tmp + "raw";
-      uses[raw] = 1;
-      reduce(score_mode, raw, score_cols);
-      ml_post_transform(n, raw, cls ? n.outputs[1] : n.outputs[0]);
-    }
+    r.kind = StepKind::SvmReduce;
+    k.svm = r.svm = sp;
+    ml_head(n, cls, std::move(k), sp->slices * sp->Q, std::move(r), kSvmLabel, score_mode, score_cols);
   }
   // ZipMap (probabilities -> a sequence of maps), when its output is the one served: the C ABI carries f32 rows, so the probabilities
   // [rows, C] it reads are served, one column per class in classlabels order (get_model_info says so)
@@ -1575,23 +1493,13 @@ struct Lowerer {
         const int64_t a0 = labels[0], step = labels[1] - labels[0];
         for (size_t i = 0; i < labels.size(); i++)
           if (labels[i] != a0 + step * int64_t(i)) unsupported(n, "classlabels_ints must be evenly spaced (label = a + b * index)");
-        std::string cur = (step == 1 && a0 == 0) ? n.outputs[0] : tmp + "index";
-        if (cur != n.outputs[0]) uses[cur] = 1;
-        NodeDef am = std_node(n, "ArgMax", {raw}, cur);
+        const std::string index = (step == 1 && a0 == 0) ? n.outputs[0] : tmp + "index";
+        if (index != n.outputs[0]) uses[index] = 1;
+        NodeDef am = std_node(n, "ArgMax", {raw}, index);
         set_i(am, "axis", 1);
         set_i(am, "keepdims", 0);
         lower_node(am);
-        if (step != 1) {
-          vals[tmp + "step"] = const_f32({float(step)}, {});
-          const std::string nxt = a0 == 0 ? n.outputs[0] : tmp + "scaled";
-          if (nxt != n.outputs[0]) uses[nxt] = 1;
-          lower_node(std_node(n, "Mul", {cur, tmp + "step"}, nxt));
-          cur = nxt;
-        }
-        if (a0 != 0) {
-          vals[tmp + "first"] = const_f32({float(a0)}, {});
-          lower_node(std_node(n, "Add", {cur, tmp + "first"}, n.outputs[0]));
-        }
+        if (step != 1 || a0 != 0) label_from_index(n, index, double(a0), double(step));
       }
       if (want_scores) ml_post_transform(n, raw, cls ? n.outputs[1] : n.outputs[0]);
     } else if (n.op == "Normalizer") {
@@ -1736,10 +1644,6 @@ struct Lowerer {
     PrepVal p = prep_identity(v->buf, 0, plan.buf_per_row[size_t(v->buf)], false, int_bufs.count(v->buf) > 0);
     return p;
   }
-  static void add_origin(PrepVal &p, const NodeDef &n) {
-    const std::string o = n.op + (n.name.empty() ? "" : ":" + n.name);
-    if (std::find(p.origin.begin(), p.origin.end(), o) == p.origin.end()) p.origin.push_back(o);
-  }
   // the region value `name` becomes a buffer: the source itself, a SliceCols, or one Prep step
   void materialize(const std::string &name, const NodeDef *at) {
     Val &v = vals[name];
@@ -1768,30 +1672,17 @@ struct Lowerer {
       s.col_off = p.cols[0].src;
       s.K = F;
     } else {
-      PrepPack pk;
       try {
-        pk = pack_prep(p.cols, prep_tables, src_w);
+        s.prep = std::make_shared<const PrepPack>(pack_prep(p.cols, prep_tables, src_w));
       } catch (const PrepError &e) {
         if (at) unsupported(*at, std::string("preprocessing step: ") + e.what());
         throw InferaError::onnx("output '" + name + "': preprocessing step: " + e.what());
       }
       s.kind = StepKind::Prep;
-      s.prep_F_in = pk.F_in;
-      s.prep_F = pk.F;
-      s.prep_R = pk.R;
-      s.prep_onehot = pk.onehot;
-      s.prep_lookup = pk.lookup;
-      s.prep_strict = pk.strict;
-      s.tree_tab = std::move(pk.desc);
-      s.scale = std::move(pk.cst);
-      s.W = std::move(pk.tab);
     }
-    s.out = new_buf({shape[0], F});
     for (const auto &o : p.origin) s.origin += (s.origin.empty() ? "" : "+") + o;
     if (s.origin.empty()) s.origin = "input:" + name;  // (only a graph input's columns as they are absorb no node)
-    plan.steps.push_back(std::move(s));
-    producer[plan.steps.back().out] = int(plan.steps.size()) - 1;
-    r.buf = plan.steps.back().out;
+    r.buf = push_step(std::move(s), {shape[0], F});
     bool all_int = true;
     for (const PrepCol &c : p.cols) all_int = all_int && c.is_int;
     if (all_int) int_bufs.insert(r.buf);
@@ -1804,6 +1695,18 @@ struct Lowerer {
     if (!ix.is_const || ix.c->dtype != onnx::kInt64 || ix.c->i64.empty()) unsupported(n, "indices must be a constant int64 list");
     return ix.c->i64;
   }
+  // the inputs of n as they are (stage 5: nothing is materialised), their columns side by side in *out; false: an input reads another
+  // source than input 0
+  bool prep_side_by_side(const NodeDef &n, PrepVal *out) {
+    *out = prep_in(n, 0, 5);
+    for (size_t i = 1; i < n.inputs.size(); i++) {
+      const PrepVal q = prep_in(n, i, 5);
+      if (q.src != out->src) return false;
+      out->append(q);
+    }
+    out->add_origin(node_label(n));
+    return true;
+  }
   // columns of region values with one source side by side (Concat / FeatureVectorizer); false: the sources differ
   bool prep_concat(const NodeDef &n, std::vector<int64_t> out_shape) {
     PrepVal out;
@@ -1813,13 +1716,8 @@ struct Lowerer {
       if (i && v.pv->src != out.src) return false;
       if (!i) out.src = v.pv->src;
     }
-    for (size_t i = 0; i < n.inputs.size(); i++) {
-      const PrepVal &p = *get_raw(n, i).pv;
-      out.cols.insert(out.cols.end(), p.cols.begin(), p.cols.end());
-      for (const auto &o : p.origin)
-        if (std::find(out.origin.begin(), out.origin.end(), o) == out.origin.end()) out.origin.push_back(o);
-    }
-    add_origin(out, n);
+    for (size_t i = 0; i < n.inputs.size(); i++) out.append(*get_raw(n, i).pv);
+    out.add_origin(node_label(n));
     out_shape[1] = int64_t(out.cols.size()) / std::max<int64_t>(1, prod(out_shape, 2));
     set_prep(n.outputs[0], std::move(out), out_shape);
     return true;
@@ -1837,7 +1735,7 @@ struct Lowerer {
       if (clash) p = prep_in(n, 0, 1);
       for (PrepCol &c : p.cols)
         if (!c.is_int) c.trunc = true, c.is_int = true;
-      add_origin(p, n);
+      p.add_origin(node_label(n));
       return set_prep(n.outputs[0], std::move(p), a.shape);
     }
     if (op == "Concat") {
@@ -1857,15 +1755,8 @@ struct Lowerer {
         int64_t total = 0;
         for (size_t i = 0; i < n.inputs.size(); i++) total += get_raw(n, i).shape[size_t(axis)];
         out_shape[size_t(axis)] = total;
-        PrepVal p = prep_in(n, 0, 5);
-        for (size_t i = 1; i < n.inputs.size(); i++) {
-          PrepVal q = prep_in(n, i, 5);
-          if (q.src != p.src) unsupported(n, "a preprocessing Concat over the last axis reads one source");
-          p.cols.insert(p.cols.end(), q.cols.begin(), q.cols.end());
-          for (const auto &o : q.origin)
-            if (std::find(p.origin.begin(), p.origin.end(), o) == p.origin.end()) p.origin.push_back(o);
-        }
-        add_origin(p, n);
+        PrepVal p;
+        if (!prep_side_by_side(n, &p)) unsupported(n, "a preprocessing Concat over the last axis reads one source");
         return set_prep(n.outputs[0], std::move(p), out_shape);
       }
       if (axis == 1 && flat && prep_concat(n, out_shape)) return;
@@ -1893,17 +1784,8 @@ struct Lowerer {
         const Val &v = get_raw(n, i);
         one_src = v.pv && v.pv->src == v0.pv->src;
       }
-      if (one_src) {
-        PrepVal out = prep_in(n, 0, 5);
-        for (size_t i = 1; i < n.inputs.size(); i++) {
-          PrepVal q = prep_in(n, i, 5);
-          out.cols.insert(out.cols.end(), q.cols.begin(), q.cols.end());
-          for (const auto &o : q.origin)
-            if (std::find(out.origin.begin(), out.origin.end(), o) == out.origin.end()) out.origin.push_back(o);
-        }
-        add_origin(out, n);
-        return set_prep(n.outputs[0], std::move(out), out_shape);
-      }
+      PrepVal cat;
+      if (one_src && prep_side_by_side(n, &cat)) return set_prep(n.outputs[0], std::move(cat), out_shape);
       std::vector<std::string> flat;
       for (size_t i = 0; i < n.inputs.size(); i++) {
         const Val &v = get(n, i);
@@ -2016,7 +1898,7 @@ struct Lowerer {
     } else {
       unsupported(n, "unsupported operator");
     }
-    add_origin(p, n);
+    p.add_origin(node_label(n));
     set_prep(n.outputs[0], std::move(p), out_shape);
   }
 
@@ -2098,24 +1980,13 @@ struct Lowerer {
     }
 
     if (m.inputs.size() > 1) {
+      Val all;  // the [rows, sum of k] input buffer
+      all.buf = 0;
+      all.shape = plan.input_shape;
       int64_t off = 0;
       for (const auto &v : m.inputs) {
-        if (uses.count(v.name) && uses[v.name] > 0 && !region_inputs.count(v.name)) {
-          Step s;
-          s.kind = StepKind::SliceCols;
-          s.in0 = 0;
-          s.col_off = off;
-          s.K = v.dims[1];
-          s.out = new_buf({plan.input_shape[0], v.dims[1]});
-          s.origin = "input:" + v.name;
-          plan.steps.push_back(std::move(s));
-          producer[plan.steps.back().out] = int(plan.steps.size()) - 1;
-          Val a;
-          a.buf = plan.steps.back().out;
-          a.shape = {plan.input_shape[0], v.dims[1]};
-          vals[v.name] = a;
-          buf_names[a.buf].push_back(v.name);
-        }
+        if (uses.count(v.name) && uses[v.name] > 0 && !region_inputs.count(v.name))
+          emit_slice_cols("input:" + v.name, all, off, off + v.dims[1], v.name);
         off += v.dims[1];
       }
     }
@@ -2168,7 +2039,7 @@ double Plan::flops_per_row() const {
   for (const auto &s : steps) {
     if (s.kind == StepKind::Dense) f += 2.0 * double(s.K) * double(s.M);
     else if (s.kind == StepKind::Conv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
-    else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm_n_sv) * double(s.svm_F + s.svm_Q);  // X . S^T, then the coefficients
+    else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
   }
   return f;
 }
@@ -2189,19 +2060,21 @@ std::string Plan::describe_json() const {
     if (s.kind == StepKind::Conv2d) o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"k\":[" << s.kh << "," << s.kw << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
     if (s.kind == StepKind::TreeEnsemble || s.kind == StepKind::TreeReduce) {
       static const char *modes[] = {"scores", "label", "binary_scores", "binary_label"};
-      o << ",\"E\":" << s.tree_E << ",\"slices\":" << s.tree_slices << ",\"output\":\"" << modes[s.tree_mode] << "\"";
+      const TreePack &t = *s.tree;
+      o << ",\"E\":" << t.E << ",\"slices\":" << t.slices << ",\"output\":\"" << modes[s.out_mode] << "\"";
       if (s.kind == StepKind::TreeEnsemble)
-        o << ",\"trees\":" << s.tree_count << ",\"nodes\":" << s.tree_nodes << ",\"max_depth\":" << s.tree_max_depth << ",\"walk_width\":" << s.tree_W
-          << ",\"aggregate\":\"" << (s.tree_average ? "AVERAGE" : "SUM") << "\"";
+        o << ",\"trees\":" << t.trees << ",\"nodes\":" << t.nodes << ",\"max_depth\":" << t.max_depth << ",\"walk_width\":" << t.W
+          << ",\"aggregate\":\"" << (t.average ? "AVERAGE" : "SUM") << "\"";
     }
     if (s.kind == StepKind::SvmKernel || s.kind == StepKind::SvmReduce) {
       static const char *kernels[] = {"LINEAR", "POLY", "RBF", "SIGMOID"}, *modes[] = {"value", "one_class", "label", "decision", "probabilities"};
-      o << ",\"kernel\":\"" << kernels[s.svm_kernel] << "\",\"support_vectors\":" << s.svm_n_sv << ",\"F\":" << s.svm_F << ",\"classes\":" << s.svm_classes
-        << ",\"slices\":" << s.svm_slices << ",\"output\":\"" << modes[s.svm_mode] << "\",\"probabilities\":" << (s.svm_prob ? "true" : "false");
+      const SvmPack &v = *s.svm;
+      o << ",\"kernel\":\"" << kernels[v.kernel] << "\",\"support_vectors\":" << v.n_sv << ",\"F\":" << v.F << ",\"classes\":" << v.classes
+        << ",\"slices\":" << v.slices << ",\"output\":\"" << modes[s.out_mode] << "\",\"probabilities\":" << (v.probabilities ? "true" : "false");
     }
     if (s.kind == StepKind::Prep)
-      o << ",\"F_in\":" << s.prep_F_in << ",\"F\":" << s.prep_F << ",\"onehot_cols\":" << s.prep_onehot << ",\"lookup_cols\":" << s.prep_lookup
-        << ",\"rows_per_tile\":" << s.prep_R << ",\"strict\":" << (s.prep_strict ? "true" : "false");
+      o << ",\"F_in\":" << s.prep->F_in << ",\"F\":" << s.prep->F << ",\"onehot_cols\":" << s.prep->onehot << ",\"lookup_cols\":" << s.prep->lookup
+        << ",\"rows_per_tile\":" << s.prep->R << ",\"strict\":" << (s.prep->strict ? "true" : "false");
     if (s.act != Act::None) o << ",\"act\":\"" << acts[int(s.act)] << "\"";
     o << ",\"origin\":" << json_str(s.origin) << "}";
   }

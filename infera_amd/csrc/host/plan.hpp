@@ -7,12 +7,17 @@
 #pragma once
 
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "onnx_model.hpp"
 
 namespace infera_hip {
+
+struct TreePack;  // host/trees.hpp
+struct SvmPack;   // host/svm.hpp
+struct PrepPack;  // host/prep.hpp
 
 // Kinds 1..5 may be fused into the epilogue of a Dense / Conv2d step (the MFMA kernels resolve them at
 // compile time); the rest run in the elementwise kernels (fused into Binary*/AffineChannel or as a Unary step).
@@ -42,20 +47,20 @@ enum class StepKind : int {
   LRN = 13,         // across-channel local response normalisation: y = x / (act_b' ... see lrn_* fields) over [N,C,S]
   ChannelShuffle = 14,  // out[n, j*g + i, p] = in0[n, i*(C/g) + j, p]   (Reshape [N,g,C/g,..] -> Transpose(0,2,1,..) -> Reshape; groups in `groups`)
   PadCols = 12,     // out[r, 0:K] = in0[r, :], zeros up to M columns   (row length -> multiple of 4 for the 16-byte loads of the MFMA kernels)
-  TreeEnsemble = 15,  // ai.onnx.ml tree walk: out = per-slice partial sums, f64 as f32 pairs: [rows][2 * tree_slices * tree_W] (slice-major inside the pass, trees.hip)
+  TreeEnsemble = 15,  // ai.onnx.ml tree walk: out = per-slice partial sums, f64 as f32 pairs: [rows][2 * slices * W] of the TreePack (slice-major inside the pass, trees.hip)
   TreeReduce = 16,    // in0 = those partials -> scores [rows, E] (AVERAGE, base_values, binary expansion) or the class label [rows]
-  SvmKernel = 17,     // ai.onnx.ml SVM: out = per-slice sums  sum_s coef[q][s] * K(x, s)  over each SV slice: [svm_slices][rows][svm_Q] (svm.hip)
+  SvmKernel = 17,     // ai.onnx.ml SVM: out = per-slice sums  sum_s coef[q][s] * K(x, s)  over each SV slice: [slices][rows][Q] (SvmPack, svm.hip)
   SvmReduce = 18,     // in0 = those partials -> regressor value / one-class sign, pairwise decisions, label or probabilities (SvmOut)
   Prep = 19,          // ai.onnx.ml preprocessing region: out[r, j] = column program j over in0[r, :] (host/prep.hpp, prep.hip)
 };
 
-// TreeReduce output modes (Step::tree_mode)
+// TreeEnsemble / TreeReduce output modes (Step::out_mode)
 enum TreeOut : int { kTreeScores = 0, kTreeLabel = 1, kTreeBinaryScores = 2, kTreeBinaryLabel = 3 };
 
-// SvmReduce output modes (Step::svm_mode): regressor value [rows, 1], one-class +-1 [rows, 1], class label [rows], pairwise
+// SvmKernel / SvmReduce output modes (Step::out_mode): regressor value [rows, 1], one-class +-1 [rows, 1], class label [rows], pairwise
 // decisions [rows, P] (binary: [d, -d]), probabilities [rows, C]
 enum SvmOut : int { kSvmValue = 0, kSvmOneClass = 1, kSvmLabel = 2, kSvmDecision = 3, kSvmProb = 4 };
-// SVM kernel types (Step::svm_kernel)
+// SVM kernel types (SvmPack::kernel)
 enum SvmKernelType : int { kSvmLinear = 0, kSvmPoly = 1, kSvmRbf = 2, kSvmSigmoid = 3 };
 
 struct Step {
@@ -87,23 +92,12 @@ struct Step {
   // LRN: window `lrn_size` channels, y = x / (lrn_bias + lrn_alpha / lrn_size * sum x^2)^lrn_beta
   int64_t lrn_size = 0;
   float lrn_alpha = 1e-4f, lrn_beta = 0.75f, lrn_bias = 1.f;
-  // TreeEnsemble / TreeReduce (host/trees.hpp packs the tables; W = leaf table [leaves][tree_W], cst = class labels, bias = base_values)
-  std::vector<uint32_t> tree_tab;  // nodes (2 words each) | root node per tree | first tree per slice (tree_slices + 1 entries)
-  int64_t tree_count = 0, tree_nodes = 0, tree_max_depth = 0, tree_W = 0, tree_E = 0, tree_slices = 1;
-  int tree_mode = kTreeScores;
-  bool tree_average = false, tree_signed = false;  // AVERAGE aggregation; binary form with a negative weight ([-s, s], label s > 0)
-  // SvmKernel / SvmReduce (host/svm.hpp packs the tables).  SvmKernel: W = support vectors in MFMA fragment order, scale = coefficients
-  // in the stage-2 layout, shift = |s|^2 (RBF), bias = the load-time center (RBF), tree_tab = first SV tile per slice (svm_slices + 1).
-  // SvmReduce: bias = rho, cst = class labels, scale / shift = prob_a / prob_b, tree_tab = first slice per class (svm_classes + 1).
-  int svm_kernel = kSvmLinear, svm_mode = kSvmValue, svm_degree = 1;
-  float svm_gamma = 0.f, svm_coef0 = 0.f;
-  int64_t svm_F = 0, svm_F_pad = 0, svm_n_sv = 0, svm_tiles = 0, svm_Q = 1, svm_slices = 1, svm_classes = 1;
-  int64_t svm_QW = 1;      // stage-2 width (host/svm.hpp SvmPack::QW)
-  bool svm_prob = false;  // the model has prob_a / prob_b
-  // Prep (host/prep.hpp PrepPack): tree_tab = column descriptors (4 words each), scale = per-column constants (4 each), W = key/value pairs.
-  // prep_R = rows per block tile; prep_strict: a zeros = 0 OneHotEncoder sets the call's failure word
-  int64_t prep_F_in = 0, prep_F = 0, prep_R = 1, prep_onehot = 0, prep_lookup = 0;
-  bool prep_strict = false;
+  // TreeEnsemble / TreeReduce, SvmKernel / SvmReduce, Prep: the packed tables and their sizes (a kernel step and its reduce step share
+  // one pack); hip/model.cpp upload_ml_tables decides which device pointer holds which table
+  std::shared_ptr<const TreePack> tree;
+  std::shared_ptr<const SvmPack> svm;
+  std::shared_ptr<const PrepPack> prep;
+  int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut
   std::string origin;  // ONNX node names/ops this step came from (diagnostics)
 };
 

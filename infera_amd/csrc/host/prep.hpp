@@ -77,8 +77,8 @@ PrepTable onehot_table(const std::vector<float> &cats);
 struct PrepPack {
   std::vector<uint32_t> desc;
   std::vector<float> cst, tab;
-  int64_t F_in = 0, F = 0, R = 1, onehot = 0, lookup = 0;
-  bool strict = false;
+  int64_t F_in = 0, F = 0, R = 1, onehot = 0, lookup = 0;  // R: rows per block tile
+  bool strict = false;  // a zeros = 0 OneHotEncoder sets the call's failure word
 };
 PrepPack pack_prep(const std::vector<PrepCol> &cols, const std::vector<std::shared_ptr<PrepTable>> &tables, int64_t F_in);
 

@@ -46,7 +46,8 @@ struct SvmPack {
   int64_t classes = 1;  // C (regressor: 1)
   int64_t Q = 1;        // coefficient rows per SV: C - 1, or 1 for the regressor
   int64_t QW = 1;       // stage-2 width: 1, 2, 4, 8 (VALU) or a multiple of 32 (MFMA)
-  bool classifier = false, one_class = false, probabilities = false;
+  bool classifier = false, one_class = false;
+  bool probabilities = false;  // the model has prob_a / prob_b
 };
 
 // Validates node `n` (input [rows, F]) and packs it.  Throws SvmError with the reason.

@@ -44,7 +44,9 @@ struct TreePack {
   int64_t trees = 0, nodes = 0, max_depth = 0, slices = 1;
   int64_t W = 1;  // columns accumulated per row: E, or 1 for the binary single-column form
   int64_t E = 1;  // scores per row served
-  bool classifier = false, binary = false, is_signed = false, average = false;
+  bool classifier = false, binary = false;
+  bool is_signed = false;  // binary form with a negative weight ([-s, s], label s > 0)
+  bool average = false;    // AVERAGE aggregation
 };
 
 // f32 threshold with the same decision as comparing an f32 x against the double d: mode 0 (<=, >) rounds toward -inf, 1 (<, >=)
