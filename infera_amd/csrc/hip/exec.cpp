@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "../host/prep.hpp"
+#include "../host/recurrent.hpp"
 #include "../host/svm.hpp"
 #include "../host/trees.hpp"
 #include "runtime.hpp"
@@ -241,6 +242,13 @@ void PassRunner::launch_plain(size_t i) {
       const PrepPack &q = *x.prep;
       kern::prep(stream, buf(x.in0), int(q.F_in), d.tab, d.scale, d.W, int(q.tab.size() / 2), buf(x.out), int(q.F), nr, int(q.R),
                  q.strict ? ctx.prep_err : nullptr);
+      break;
+    }
+    case StepKind::Recurrent: {
+      const RnnPack &r = *x.rnn;
+      if (!kern::rnn(stream, buf(x.in0), d.W, d.bias, d.shift, d.cst, d.scale, buf(x.out), nr, r.op, int(r.T), int(r.F), int(r.H), int(r.D), r.reverse,
+                     r.lbr, r.relu, x.out_mode, in_colmajor && x.in0 == 0))
+        throw InferaError::onnx("recurrent kernel launch failed: '" + x.origin + "' could not be given its LDS");
       break;
     }
   }

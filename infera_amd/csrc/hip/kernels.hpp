@@ -72,6 +72,12 @@ void svm_reduce(hipStream_t s, const float *part, const uint32_t *class_slice, c
 void prep(hipStream_t s, const float *x, int F_in, const uint32_t *desc, const float *cst, const float *tab, int ntab, float *y, int F, int64_t rows,
           int R, int *err);
 
+// ---- recurrent layers (rnn.hip) -------------------------------------------------------------------
+// LSTM / GRU / RNN over x [rows, T, F] (x_colmajor: ONE column-major chunk [T * F][rows]); tables: host/recurrent.hpp RnnPack (op: RnnOp).
+// mode (RnnOut): y = Y [rows, T, D, H], or the last state Y_h / Y_c [rows, D, H].  false: the kernel could not be given its LDS
+bool rnn(hipStream_t s, const float *x, const float *wr, const float *bias, const float *bias2, const float *h0, const float *c0, float *y, int64_t rows,
+         int op, int T, int F, int H, int D, bool reverse, bool lbr, bool relu, int mode, bool x_colmajor);
+
 // ---- dense layer, fp32 MFMA (dense.hip) -------------------------------------------------------
 // Y[rows, M] = act(X[rows, K] . W[K, M] + bias[M]); W row-major, bias may be null.
 // softmax_fused: apply a row softmax over the M outputs in the epilogue (requires M <= 256).

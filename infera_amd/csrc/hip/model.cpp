@@ -3,6 +3,7 @@
 #include "runtime.hpp"
 #include "../host/onnx_model.hpp"
 #include "../host/prep.hpp"
+#include "../host/recurrent.hpp"
 #include "../host/svm.hpp"
 #include "../host/trees.hpp"
 
@@ -176,6 +177,13 @@ bool upload_ml_tables(const Step &s, DeviceStep &d, hipStream_t us) {
       d.tab = upload(s.prep->desc, us);
       d.scale = upload(s.prep->cst, us);
       d.W = upload(s.prep->tab, us);
+      return true;
+    case StepKind::Recurrent:
+      d.W = upload(s.rnn->wr, us);
+      d.bias = upload(s.rnn->bias, us);
+      d.shift = upload(s.rnn->bias2, us);
+      d.cst = upload(s.rnn->h0, us);
+      d.scale = upload(s.rnn->c0, us);
       return true;
     default: return false;
   }

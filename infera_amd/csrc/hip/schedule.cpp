@@ -413,7 +413,8 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
         const StepKind sk = st[size_t(e.idx)].kind;
         // (a tree walk reads its row tile once per tree slice, and wide rows feature by feature; an SVM once per SV slice)
         const bool windowed = (sk == StepKind::Conv2d && m.exec[size_t(e.idx)] != ExecKind::ConvPatch) || sk == StepKind::Pool2d || sk == StepKind::LRN ||
-                              sk == StepKind::TreeEnsemble || sk == StepKind::SvmKernel;
+                              sk == StepKind::TreeEnsemble || sk == StepKind::SvmKernel ||
+                              sk == StepKind::Recurrent;  // (one dependent fetch per time step: from HBM, not over PCIe)
         m.in_single_reader = !windowed;
         break;
       }
@@ -434,6 +435,8 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
           kern::dense_colmajor_supported(int(st[i0].K), int(st[i0].M)))
         m.in_colmajor_ok = true;
     }
+    // ... and the recurrent kernel stages x_t from either order with the same loads (rnn.hip)
+    if (!eff.empty() && in_readers == 1 && eff[0].reads[0] == 0 && st[size_t(eff[0].idx)].kind == StepKind::Recurrent) m.in_colmajor_ok = true;
   }
 }
 

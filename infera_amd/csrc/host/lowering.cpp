@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "plan.hpp"
 #include "prep.hpp"
+#include "recurrent.hpp"
 #include "svm.hpp"
 #include "trees.hpp"
 
@@ -54,7 +55,10 @@ struct Val {
   std::shared_ptr<const PrepVal> pv;  // set: a preprocessing-region value (buf = -1)
   std::shared_ptr<TensorData> c;
   int buf = -1;
-  std::vector<int64_t> shape;  // activations: dim0 = -1 (symbolic rows) or fixed batch
+  std::vector<int64_t> shape;  // activations: dim[ra] = -1 (symbolic rows) or fixed batch
+  // row-axis tag: where the row axis stands in `shape`.  The buffer is always [rows, the other axes in the order of `shape`]; 0 for
+  // everything but the time-major values around a recurrent layer ([T, rows, F], Y [T, D, rows, H], Y_h [D, rows, H])
+  int ra = 0;
   // zero padding (top, left, bottom, right) a Pad node asked for and the consuming Conv still has to apply; `shape`
   // is the UNPADDED tensor that `buf` holds
   int64_t pend[4] = {0, 0, 0, 0};
@@ -173,10 +177,11 @@ struct Lowerer {
 
   // Binds the node's first output to `buf`.  `folded` = the node itself emitted no step (alias or
   // fused into its producer), i.e. it is an edge inside the buffer rather than a consumer of it.
-  void set_act(const NodeDef &n, int buf, const std::vector<int64_t> &shape, bool folded = false) {
+  void set_act(const NodeDef &n, int buf, const std::vector<int64_t> &shape, bool folded = false, int ra = 0) {
     Val v;
     v.buf = buf;
     v.shape = shape;
+    v.ra = ra;
     vals[n.outputs[0]] = v;
     buf_names[buf].push_back(n.outputs[0]);
     if (folded) alias_edges[buf]++;
@@ -534,7 +539,7 @@ struct Lowerer {
     const Val &a = get(n, 0);
     std::vector<int64_t> d = a.shape;
     // the symbolic row count is carried as 0, which Reshape reads as "copy this dim from the input"
-    if (!a.is_const && !d.empty() && d[0] < 0) d[0] = 0;
+    if (!a.is_const && !d.empty() && d[size_t(a.ra)] < 0) d[size_t(a.ra)] = 0;
     int64_t r = int64_t(d.size()), st = n.attr_i("start", 0), en = n.attr_i("end", r);
     if (st < 0) st += r;
     if (en < 0) en += r;
@@ -571,6 +576,15 @@ struct Lowerer {
       }
       return;
     }
+    // one time step of a [rows, T, C] (or time-major [T, rows, C]) activation: a contiguous range of every row
+    if (!d.is_const && time_steppable(d) && ix.is_const && ix.c->dtype == onnx::kInt64 && ix.c->i64.size() == 1 && ix.shape.size() <= 1) {
+      int64_t axis = n.attr_i("axis", 0);
+      if (axis < 0) axis += 3;
+      if (axis != 1 - d.ra) unsupported(n, "only one step of the time axis (axis " + std::to_string(1 - d.ra) + ") keeps rows independent");
+      const Val src = d;
+      return time_step(n, src, ix.c->i64[0], ix.shape.empty());
+    }
+    if (!d.is_const && d.ra != 0) unsupported(n, "only one step of the time axis of a [T, rows, C] activation");
     if (!d.is_const || !ix.is_const || ix.c->dtype != onnx::kInt64) unsupported(n, "only constant data with constant indices is folded");
     if (d.shape.size() > 1 || n.attr_i("axis", 0) != 0) unsupported(n, "only 1-D data / axis 0");
     const int64_t len = d.c->dtype == onnx::kInt64 ? int64_t(d.c->i64.size()) : int64_t(d.c->f32.size());
@@ -588,6 +602,44 @@ struct Lowerer {
       for (auto i : ix.c->i64) o.push_back(d.c->f32[at(i)]);
       vals[n.outputs[0]] = const_f32(std::move(o), ix.shape);
     }
+  }
+  // May one time step be cut out of `a` as a contiguous column range?  Only a rank-3 value [rows, T, C] / [T, rows, C] whose buffer is
+  // registered as a flat [rows, per_row] matrix: what a recurrent step writes, or a Reshape of a flat table.  Every other rank-3 activation
+  // (Conv1d tensors, which may live in the channel-quad layout) keeps the channel-slice path and its layout rules.
+  bool time_steppable(const Val &a) const {
+    return !a.is_const && a.buf >= 0 && a.shape.size() == 3 && a.ra <= 1 && plan.buf_shape[size_t(a.buf)].size() == 2;
+  }
+  // Step `t` of the time axis of a rank-3 activation `a` (rows first or time-major) as output 0 of n: a SliceCols of C columns, or -- the
+  // schedule fold -- nothing at all when `a` is the whole forward Y of a unidirectional recurrent step that nothing else reads and t is
+  // the last step: that step then stores Y_h (H values per row, not T * H).  drop_axis: the time axis disappears (a scalar Gather index)
+  void time_step(const NodeDef &n, const Val &a, int64_t t, bool drop_axis) {
+    const int64_t T = a.shape[size_t(1 - a.ra)], C = a.shape[2], N = a.shape[size_t(a.ra)];
+    if (t < 0) t += T;
+    if (t < 0 || t >= T) unsupported(n, "time step out of range");
+    Val v;
+    v.ra = drop_axis ? 0 : a.ra;
+    v.shape = drop_axis ? std::vector<int64_t>{N, C} : a.ra ? std::vector<int64_t>{1, N, C} : std::vector<int64_t>{N, 1, C};
+    auto pit = producer.find(a.buf);
+    Step *p = pit == producer.end() ? nullptr : &plan.steps[size_t(pit->second)];
+    if (p && p->kind == StepKind::Recurrent && p->out == a.buf && p->out_mode == kRnnY && p->rnn->D == 1 && !p->rnn->reverse && t == T - 1 &&
+        C == p->rnn->H && live_uses(a.buf) == 1) {
+      p->out_mode = kRnnYh;
+      p->origin += "+" + node_label(n);
+      plan.buf_per_row[size_t(a.buf)] = C;
+      plan.buf_shape[size_t(a.buf)] = {N, C};
+      v.buf = a.buf;
+      alias_edges[v.buf]++;
+    } else {
+      Step s;
+      s.kind = StepKind::SliceCols;
+      s.in0 = a.buf;
+      s.col_off = t * C;
+      s.K = C;
+      s.origin = node_label(n);
+      v.buf = push_step(std::move(s), {N, C});
+    }
+    vals[n.outputs[0]] = v;
+    buf_names[v.buf].push_back(n.outputs[0]);
   }
   // feature-axis slice of a [rows, K] activation: out = in[:, b:e]
   // ... or a channel range of an [N,C,H,W] activation: channels [b, e) are one contiguous block of every sample, in
@@ -647,13 +699,17 @@ struct Lowerer {
       }
       if (st.size() != 1 || en.size() != 1 || ax.size() > 1 || (!sp.empty() && sp[0] != 1)) unsupported(n, "one axis, step 1");
       const int64_t axis = ax.empty() ? 0 : (ax[0] < 0 ? ax[0] + int64_t(d.shape.size()) : ax[0]);
-      if (axis != 1) unsupported(n, "only axis 1 (features / channels)");
-      const int64_t K = d.shape[1];
+      const int64_t time_axis = time_steppable(d) ? 1 - d.ra : -1;
+      if (d.ra != 0 && axis != time_axis) unsupported(n, "only one step of the time axis of a [T, rows, C] activation");
+      if (axis != 1 && d.ra == 0) unsupported(n, "only axis 1 (features / channels)");
+      const int64_t K = d.shape[size_t(axis)];
       int64_t b = st[0] < 0 ? st[0] + K : st[0], e = en[0] < 0 ? en[0] + K : en[0];
       b = std::clamp<int64_t>(b, 0, K);
       e = std::clamp<int64_t>(e, b, K);
       if (e == b) unsupported(n, "empty slice");
       const Val src = d;
+      if (axis == time_axis && e - b == 1) return time_step(n, src, b, false);  // (the last step of a recurrent layer's Y: folded)
+      if (d.ra != 0) unsupported(n, "only one step of the time axis of a [T, rows, C] activation");
       emit_slice_cols(node_label(n), src, b, e, n.outputs[0]);
       return;
     }
@@ -886,6 +942,7 @@ struct Lowerer {
       }
       unsupported(n, "reshaping constants is not supported");
     }
+    if (a.ra != 0) return reshape_tagged(n);
     std::vector<int64_t> out;
     const int64_t rank = int64_t(a.shape.size());
     if (n.op == "Identity" || n.op == "Dropout") {
@@ -950,6 +1007,94 @@ struct Lowerer {
       }
     }
     alias(n, out);
+  }
+
+  // Identity / Squeeze / Unsqueeze / Reshape of a value whose row axis is not axis 0: an alias when the axes in front of the row axis keep
+  // their total extent (then the other axes keep their order in the rows-first buffer), else rejected -- it would need data moved
+  void reshape_tagged(const NodeDef &n) {
+    const Val a = get_raw(n, 0);
+    const int64_t rank = int64_t(a.shape.size());
+    std::vector<int64_t> out;
+    int ra = a.ra;
+    auto const_axes = [&]() {
+      std::vector<int64_t> axes;
+      if (has_input(n, 1)) axes = const_ints(n, 1, "axes");
+      else if (auto *p = n.attr_ints("axes")) axes = *p;
+      return axes;
+    };
+    if (n.op == "Identity" || n.op == "Dropout") {
+      out = a.shape;
+    } else if (n.op == "Squeeze") {
+      const std::vector<int64_t> axes = const_axes();
+      ra = -1;
+      for (int64_t i = 0; i < rank; i++) {
+        bool drop = axes.empty() && a.shape[size_t(i)] == 1 && i != a.ra;
+        for (auto ax : axes) drop = drop || (ax < 0 ? ax + rank : ax) == i;
+        if (drop && i == a.ra) unsupported(n, "cannot squeeze the row axis");
+        if (drop && a.shape[size_t(i)] != 1) unsupported(n, "axis " + std::to_string(i) + " of " + shape_str(a.shape) + " is not 1");
+        if (i == a.ra) ra = int(out.size());
+        if (!drop) out.push_back(a.shape[size_t(i)]);
+      }
+    } else if (n.op == "Unsqueeze") {
+      const std::vector<int64_t> axes = const_axes();
+      const int64_t nr = rank + int64_t(axes.size());
+      size_t src = 0;
+      for (int64_t i = 0; i < nr; i++) {
+        bool ins = false;
+        for (auto ax : axes) ins = ins || (ax < 0 ? ax + nr : ax) == i;
+        if (!ins && src >= a.shape.size()) unsupported(n, "axes out of range");
+        if (!ins && int(src) == a.ra) ra = int(i);
+        out.push_back(ins ? 1 : a.shape[src++]);
+      }
+      if (src != a.shape.size()) unsupported(n, "axes out of range");
+    } else if (n.op == "Reshape") {
+      std::vector<int64_t> tgt = has_input(n, 1) ? const_ints(n, 1, "shape") : n.attr_ints("shape") ? *n.attr_ints("shape") : std::vector<int64_t>{};
+      if (tgt.empty()) unsupported(n, "missing shape");
+      const int64_t per_row = prod(a.shape, 0) / a.shape[size_t(a.ra)], rows = a.shape[size_t(a.ra)];
+      int q = -1, neg = -1;
+      for (size_t i = 0; i < tgt.size(); i++) {
+        if (tgt[i] == 0) {
+          if (i >= a.shape.size()) unsupported(n, "0 entry out of range");
+          if (int(i) == a.ra) q = int(i);
+          else tgt[i] = a.shape[i];
+        } else if (tgt[i] == -1) {
+          if (neg >= 0) unsupported(n, "more than one -1");
+          neg = int(i);
+        } else if (tgt[i] < 0) unsupported(n, "negative extent");
+      }
+      auto known = [&]() {  // product of the entries that are neither the row axis nor the -1
+        int64_t p = 1;
+        for (size_t i = 0; i < tgt.size(); i++)
+          if (int(i) != q && int(i) != neg) p *= tgt[i];
+        return p;
+      };
+      if (q < 0 && rows > 0) {  // a fixed batch: the entry that equals it behind the same leading extent
+        int64_t lead = 1;
+        const int64_t pre = prod(a.shape, 0, size_t(a.ra));
+        for (size_t i = 0; i < tgt.size() && q < 0; i++) {
+          if (lead == pre && tgt[i] == rows) q = int(i);
+          else if (tgt[i] > 0) lead *= tgt[i];
+        }
+      }
+      if (q < 0 && rows < 0 && neg >= 0 && known() == per_row) q = neg, neg = -1;  // (the -1 stands for the symbolic row count)
+      if (q < 0) unsupported(n, "target shape " + shape_str(tgt) + " does not keep the row axis of " + shape_str(a.shape));
+      if (neg >= 0) {
+        const int64_t k = known();
+        if (k == 0 || per_row % k) unsupported(n, "cannot infer -1");
+        tgt[size_t(neg)] = per_row / k;
+      }
+      tgt[size_t(q)] = rows;
+      out = tgt;
+      ra = q;
+    } else {
+      unsupported(n, "on a time-major value (row axis " + std::to_string(a.ra) + " of " + shape_str(a.shape) + ") it would need data moved");
+    }
+    int64_t rest = 1;
+    for (size_t i = 0; i < out.size(); i++)
+      if (int(i) != ra) rest *= out[i];
+    if (rest != plan.buf_per_row[size_t(a.buf)] || prod(out, 0, size_t(ra)) != prod(a.shape, 0, size_t(a.ra)))
+      unsupported(n, "reshape " + shape_str(a.shape) + " -> " + shape_str(out) + " (row axis " + std::to_string(a.ra) + ") would need data moved");
+    set_act(n, a.buf, out, true, ra);
   }
 
   void softmax(const NodeDef &n, bool logsm) {
@@ -1178,11 +1323,34 @@ struct Lowerer {
       vals[n.outputs[0]] = const_f32(std::move(t), {Cc, R});
       return;
     }
-    const bool shuffle = rank >= 4 && perm[0] == 0 && perm[1] == 2 && perm[2] == 1 && [&] {
+    const bool shuffle = a.ra == 0 && rank >= 4 && perm[0] == 0 && perm[1] == 2 && perm[2] == 1 && [&] {
       for (int64_t i = 3; i < rank; i++)
         if (perm[size_t(i)] != i) return false;
       return true;
     }();
+    if (!shuffle && (a.ra != 0 || rank == 3)) {
+      // (time-major values, and the rank-3 rows-first values a Transpose(1,0,2) makes time-major; other tensors are not touched) a permutation that only moves (or keeps) the row axis and leaves the other axes in the order they lie in memory: an alias with a
+      // new row-axis tag (the Transposes exporters put around time-major recurrent layers)
+      for (int64_t i = 0; i < rank; i++)
+        if (perm[size_t(i)] < 0 || perm[size_t(i)] >= rank) unsupported(n, "perm entry out of range");
+      int ra = -1;
+      int64_t last = -1;
+      bool in_order = true;
+      std::vector<int64_t> out;
+      for (int64_t i = 0; i < rank; i++) {
+        const int64_t src = perm[size_t(i)];
+        out.push_back(a.shape[size_t(src)]);
+        if (src == a.ra) { ra = int(i); continue; }
+        if (a.shape[size_t(src)] == 1) continue;
+        in_order = in_order && src > last;
+        last = src;
+      }
+      if (ra < 0 || !in_order)
+        unsupported(n, "on activations only the channel shuffle (0,2,1,3,...) or a permutation that moves nothing but the row axis is supported: this one would need data moved");
+      const int buf = a.buf;
+      set_act(n, buf, out, true, ra);
+      return;
+    }
     if (!shuffle) unsupported(n, "on activations only the channel shuffle (0,2,1,3,...) keeps rows independent and is supported");
     Step s;
     s.kind = StepKind::ChannelShuffle;
@@ -1233,7 +1401,12 @@ struct Lowerer {
         auto it = vals.find(in_name);
         if (it != vals.end() && it->second.padded()) unsupported(n, "the output of a Pad node can only feed a Conv (its padding is folded into the convolution)");
       }
-    if (op == "MatMul") dense(n, false);
+    static const std::set<std::string> reads_time_major = {"Transpose", "Squeeze", "Unsqueeze", "Reshape", "Identity", "Dropout", "Flatten", "Shape",
+                                                           "Gather", "Slice", "LSTM", "GRU", "RNN"};
+    check_row_axis(n, reads_time_major.count(op) > 0);
+    if (op == "LSTM" || op == "GRU" || op == "RNN") recurrent(n);
+    else if (op == "ConstantOfShape" || op == "Expand") constant_fill(n);
+    else if (op == "MatMul") dense(n, false);
     else if (op == "Gemm") dense(n, true);
     else if (op == "Add") binary(n, '+');
     else if (op == "Sub") binary(n, '-');
@@ -1278,6 +1451,106 @@ struct Lowerer {
       else unsupported(n, "only the value / value_float / value_int / value_ints forms are supported");
     } else {
       unsupported(n, "unsupported operator");
+    }
+  }
+
+  // every operator but the few that understand the row-axis tag reads rows-first values only
+  void check_row_axis(const NodeDef &n, bool understands) {
+    if (understands) return;
+    for (const auto &in_name : n.inputs) {
+      auto it = vals.find(in_name);
+      if (it != vals.end() && !it->second.is_const && it->second.ra != 0)
+        unsupported(n, "input '" + in_name + "' " + shape_str(it->second.shape) + " is time-major (its row axis is axis " + std::to_string(it->second.ra) +
+                           "); only a Transpose / Squeeze / Reshape that moves no data, one time step or a recurrent layer can read it");
+    }
+  }
+  // ConstantOfShape / Expand over constants: the sub-graph exporters write for a zero (or constant) initial state of a recurrent layer,
+  // [D, rows, H] with the row count taken from Shape(X).  The symbolic row count (0 in a folded shape) becomes extent 1: one row, the same
+  // for all.  (An extent that is 0 in the model file itself -- an empty tensor -- cannot be told from the folded row count and would become
+  // one element too; the only consumer of these constants, a recurrent layer's initial state, checks the shape it gets.)
+  void constant_fill(const NodeDef &n) {
+    const bool expand = n.op == "Expand";
+    std::vector<int64_t> dims = const_ints(n, expand ? 1 : 0, "shape");
+    for (auto &d : dims) {
+      if (d == 0) d = 1;
+      if (d < 0) unsupported(n, "negative extent");
+    }
+    std::vector<int64_t> src_dims;
+    std::vector<float> src{0.f};
+    if (expand) {
+      const Val &v = get(n, 0);
+      if (!v.is_const || v.c->dtype != onnx::kFloat) unsupported(n, "only constant f32 data is expanded");
+      src = v.c->f32;
+      src_dims = v.shape;
+    } else if (const onnx::Attribute *a = n.attr("value"); a && a->t) {
+      if (a->t->count() != 1) unsupported(n, "value must hold one element");
+      if (a->t->dtype != onnx::kFloat) unsupported(n, "only an f32 fill value");
+      src = a->t->f32;
+    }
+    if (src_dims.size() > dims.size()) dims.insert(dims.begin(), src_dims.size() - dims.size(), 1);
+    while (src_dims.size() < dims.size()) src_dims.insert(src_dims.begin(), 1);
+    for (size_t i = 0; i < dims.size(); i++) {
+      if (src_dims[i] != 1 && dims[i] != 1 && src_dims[i] != dims[i]) unsupported(n, shape_str(src_dims) + " does not broadcast to " + shape_str(dims));
+      if (dims[i] == 1) dims[i] = src_dims[i];
+    }
+    const int64_t total = prod(dims);
+    if (total > (int64_t(1) << 24)) unsupported(n, "constant too large");
+    std::vector<float> o(static_cast<size_t>(total));
+    for (int64_t flat = 0; flat < total; flat++) {
+      int64_t rem = flat, idx = 0, stride = 1;
+      for (size_t i = dims.size(); i-- > 0;) {
+        const int64_t coord = rem % dims[i];
+        rem /= dims[i];
+        if (src_dims[i] != 1) idx += coord * stride;
+        stride *= src_dims[i];
+      }
+      o[size_t(flat)] = src[size_t(idx)];
+    }
+    vals[n.outputs[0]] = const_f32(std::move(o), dims);
+  }
+  // LSTM / GRU / RNN: one Recurrent step per output that is read.  X is [T, rows, F] (layout 0: time-major, row-axis tag 1) or
+  // [rows, T, F] (layout 1); the step writes Y as [rows, T, D, H] and the last states as [rows, D, H], and the values carry ONNX's shapes
+  // with the row-axis tag that makes them so
+  void recurrent(const NodeDef &n) {
+    if (n.inputs.size() < 3 || n.inputs[0].empty() || n.inputs[1].empty() || n.inputs[2].empty())
+      unsupported(n, "unsupported operator form: needs the three inputs X, W, R");
+    const Val x = get(n, 0);
+    const int64_t layout = n.attr_i("layout", 0) == 1 ? 1 : 0;
+    if (x.is_const || x.shape.size() != 3 || x.ra != 1 - layout)
+      unsupported(n, std::string("unsupported operator form: X must be ") + (layout ? "[rows, T, F] (layout 1)" : "[T, rows, F] (layout 0: a Transpose(1,0,2) of the rows-first input)") +
+                         ", got " + shape_str(x.shape) + " with the row axis at " + std::to_string(x.ra));
+    auto arg = [&](size_t i) {
+      RnnInput r;
+      if (!has_input(n, i)) return r;
+      r.present = true;
+      const Val &v = get(n, i);
+      if (v.is_const) r.c = v.c.get();
+      return r;
+    };
+    const bool lstm = n.op == "LSTM";
+    std::shared_ptr<const RnnPack> rp;
+    try {
+      rp = std::make_shared<const RnnPack>(pack_recurrent(n, x.shape[size_t(layout)], x.shape[2], arg(1), arg(2), arg(3), arg(4), arg(5),
+                                                          lstm ? arg(6) : RnnInput{}, lstm ? arg(7) : RnnInput{}));
+    } catch (const RnnError &e) {
+      unsupported(n, e.what());
+    }
+    const int64_t N = x.shape[size_t(x.ra)], T = rp->T, D = rp->D, H = rp->H;
+    for (size_t o = 0; o < (lstm ? 3u : 2u); o++) {
+      if (!wanted(n, o)) continue;
+      Step s;
+      s.kind = StepKind::Recurrent;
+      s.in0 = x.buf;
+      s.rnn = rp;
+      s.out_mode = o == 0 ? kRnnY : o == 1 ? kRnnYh : kRnnYc;
+      s.origin = node_label(n);
+      Val v;
+      v.buf = push_step(std::move(s), {N, o == 0 ? T * D * H : D * H});
+      if (o == 0) v.shape = layout ? std::vector<int64_t>{N, T, D, H} : std::vector<int64_t>{T, D, N, H};
+      else v.shape = layout ? std::vector<int64_t>{N, D, H} : std::vector<int64_t>{D, N, H};
+      v.ra = layout ? 0 : (o == 0 ? 2 : 1);
+      vals[n.outputs[o]] = v;
+      buf_names[v.buf].push_back(n.outputs[o]);
     }
   }
 
@@ -1994,6 +2267,7 @@ struct Lowerer {
       if (!live[ni]) continue;
       const auto &n = m.nodes[ni];
       if (n.outputs.empty()) throw InferaError::onnx("node " + n.op + " has no outputs");
+      if (region[ni] || n.domain == "ai.onnx.ml") check_row_axis(n, false);
       if (region[ni]) prep_node(n);
       else if (n.domain == "ai.onnx.ml") ml_node(n);
       else if (!n.domain.empty() && n.domain != "ai.onnx") unsupported(n, "operator domain '" + n.domain + "'");
@@ -2006,6 +2280,9 @@ struct Lowerer {
     if (it->second.pv) materialize(out.name, nullptr);
     if (it->second.is_const) throw InferaError::onnx("output '" + out.name + "' is a constant; nothing to run");
     if (it->second.padded()) throw InferaError::onnx("output '" + out.name + "' is a Pad result; padding is only folded into a following Conv");
+    if (it->second.ra != 0)
+      throw InferaError::onnx("output '" + out.name + "' " + shape_str(it->second.shape) + " is time-major (its row axis is axis " + std::to_string(it->second.ra) +
+                              "); results are served rows first: transpose it in the graph (Transpose(1,0,2)) or use layout = 1");
     if (out.elem_type != 0 && out.elem_type != onnx::kFloat) {
       // integer outputs (ArgMax labels, Cast to int) are returned as f32 VALUES: the C ABI carries f32 only
       // (rust.h:28-49; the reference itself rejects non-f32 outputs at engine.rs:150-152)
@@ -2040,12 +2317,13 @@ double Plan::flops_per_row() const {
     if (s.kind == StepKind::Dense) f += 2.0 * double(s.K) * double(s.M);
     else if (s.kind == StepKind::Conv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
+    else if (s.kind == StepKind::Recurrent) f += 2.0 * double(s.rnn->T * s.rnn->D * s.rnn->G * s.rnn->H) * double(s.rnn->F + s.rnn->H);
   }
   return f;
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -2075,6 +2353,14 @@ std::string Plan::describe_json() const {
     if (s.kind == StepKind::Prep)
       o << ",\"F_in\":" << s.prep->F_in << ",\"F\":" << s.prep->F << ",\"onehot_cols\":" << s.prep->onehot << ",\"lookup_cols\":" << s.prep->lookup
         << ",\"rows_per_tile\":" << s.prep->R << ",\"strict\":" << (s.prep->strict ? "true" : "false");
+    if (s.kind == StepKind::Recurrent) {
+      static const char *ops[] = {"LSTM", "GRU", "RNN"}, *modes[] = {"Y", "Y_h", "Y_c"};
+      const RnnPack &r = *s.rnn;
+      o << ",\"op\":\"" << ops[r.op] << "\",\"T\":" << r.T << ",\"F\":" << r.F << ",\"H\":" << r.H << ",\"D\":" << r.D << ",\"direction\":\""
+        << (r.D == 2 ? "bidirectional" : r.reverse ? "reverse" : "forward") << "\",\"output\":\"" << modes[s.out_mode] << "\"";
+      if (r.op == kRnnGru) o << ",\"linear_before_reset\":" << (r.lbr ? 1 : 0);
+      if (r.op == kRnnPlain) o << ",\"activation\":\"" << (r.relu ? "Relu" : "Tanh") << "\"";
+    }
     if (s.act != Act::None) o << ",\"act\":\"" << acts[int(s.act)] << "\"";
     o << ",\"origin\":" << json_str(s.origin) << "}";
   }

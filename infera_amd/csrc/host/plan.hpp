@@ -18,6 +18,7 @@ namespace infera_hip {
 struct TreePack;  // host/trees.hpp
 struct SvmPack;   // host/svm.hpp
 struct PrepPack;  // host/prep.hpp
+struct RnnPack;   // host/recurrent.hpp
 
 // Kinds 1..5 may be fused into the epilogue of a Dense / Conv2d step (the MFMA kernels resolve them at
 // compile time); the rest run in the elementwise kernels (fused into Binary*/AffineChannel or as a Unary step).
@@ -52,6 +53,7 @@ enum class StepKind : int {
   SvmKernel = 17,     // ai.onnx.ml SVM: out = per-slice sums  sum_s coef[q][s] * K(x, s)  over each SV slice: [slices][rows][Q] (SvmPack, svm.hip)
   SvmReduce = 18,     // in0 = those partials -> regressor value / one-class sign, pairwise decisions, label or probabilities (SvmOut)
   Prep = 19,          // ai.onnx.ml preprocessing region: out[r, j] = column program j over in0[r, :] (host/prep.hpp, prep.hip)
+  Recurrent = 20,     // ONNX LSTM / GRU / RNN over in0 [rows, T, F]: out = Y [rows, T, D, H] or the last state [rows, D, H] (RnnOut; RnnPack, rnn.hip)
 };
 
 // TreeEnsemble / TreeReduce output modes (Step::out_mode)
@@ -97,7 +99,8 @@ struct Step {
   std::shared_ptr<const TreePack> tree;
   std::shared_ptr<const SvmPack> svm;
   std::shared_ptr<const PrepPack> prep;
-  int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut
+  std::shared_ptr<const RnnPack> rnn;
+  int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut
   std::string origin;  // ONNX node names/ops this step came from (diagnostics)
 };
 

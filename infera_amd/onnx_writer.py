@@ -761,6 +761,180 @@ def svm(scaler: tuple | None = None, output: str = "label", **kw) -> bytes:
 
 
 # ------------------------------------------------------------------------------------------
+# recurrent layers (LSTM, GRU, RNN) in the forms exporters write them
+# ------------------------------------------------------------------------------------------
+
+_RNN_GATES = {"LSTM": 4, "GRU": 3, "RNN": 1}
+
+
+def recurrent_spec(op: str = "LSTM", T: int = 24, F: int = 8, H: int = 64, layers: int = 1, direction: str = "forward",
+                   linear_before_reset: int = 1, activation: str = "Tanh", initial: float = 0.0, bias: bool = True,
+                   r_scale: float = 1.0, seed: int = 11) -> dict:
+    """Seeded stack of ONNX recurrent layers: per layer W [D, G*H, F_in], R [D, G*H, H], B [D, 2*G*H] in ONNX gate order (LSTM i,o,f,c;
+    GRU z,r,h), U(+-1/sqrt(H)) like PyTorch.  initial != 0: a constant initial state N(0, initial) per layer (h0, and c0 for LSTM), one
+    row [D, H].  r_scale scales R (Relu RNNs: keep its spectral norm below 1)."""
+    rng = np.random.default_rng(seed)
+    G, D = _RNN_GATES[op], 2 if direction == "bidirectional" else 1
+    k = 1.0 / np.sqrt(H)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)  # noqa: E731
+    ls = []
+    for i in range(layers):
+        fin = F if i == 0 else D * H
+        ls.append({"W": f32(rng.uniform(-k, k, (D, G * H, fin))), "R": f32(rng.uniform(-k, k, (D, G * H, H)) * r_scale),
+                   "B": f32(rng.uniform(-k, k, (D, 2 * G * H))) if bias else None,
+                   "h0": f32(rng.normal(0, initial, (D, H))) if initial else None,
+                   "c0": f32(rng.normal(0, initial, (D, H))) if initial and op == "LSTM" else None})
+    return {"op": op, "T": T, "F": F, "H": H, "D": D, "direction": direction, "linear_before_reset": linear_before_reset,
+            "activation": activation, "layers": ls}
+
+
+def torch_recurrent_spec(module) -> dict:
+    """The recurrent_spec() dict of a torch.nn.LSTM / GRU / RNN (any num_layers, bidirectional or not).  PyTorch stores the gates as
+    i,f,g,o (LSTM) and r,z,n (GRU); ONNX wants i,o,f,c and z,r,h: the permutation lives here.  GRU: linear_before_reset = 1."""
+    op = type(module).__name__
+    H, D = module.hidden_size, 2 if module.bidirectional else 1
+    order = {"LSTM": [0, 3, 1, 2], "GRU": [1, 0, 2], "RNN": [0]}[op]
+
+    def gates(a):
+        a = a.detach().cpu().numpy().astype(np.float32)
+        return np.concatenate([a[g * H:(g + 1) * H] for g in order], axis=0)
+
+    ls = []
+    for i in range(module.num_layers):
+        sfx = [f"_l{i}", f"_l{i}_reverse"][:D]
+        W = np.stack([gates(getattr(module, "weight_ih" + x)) for x in sfx])
+        R = np.stack([gates(getattr(module, "weight_hh" + x)) for x in sfx])
+        B = np.stack([np.concatenate([gates(getattr(module, "bias_ih" + x)), gates(getattr(module, "bias_hh" + x))]) for x in sfx]) if module.bias else None
+        ls.append({"W": W, "R": R, "B": B, "h0": None, "c0": None})
+    act = "Relu" if op == "RNN" and module.nonlinearity == "relu" else "Tanh"
+    return {"op": op, "T": None, "F": module.input_size, "H": H, "D": D, "direction": "bidirectional" if D == 2 else "forward",
+            "linear_before_reset": 1, "activation": act, "layers": ls}
+
+
+def recurrent_from_spec(spec: dict, T: int | None = None, form: str = "batch_first", tail: str = "seq", flat: bool = False,
+                        head: tuple | None = None, scaler: tuple | None = None, initial: str = "const", opset: int = 14,
+                        extra_attrs: Sequence[bytes] = (), last_index: int = -1, state_outputs: bool = False) -> bytes:
+    """The ONNX model of a recurrent_spec() / torch_recurrent_spec() dict, input X [N, T, F] (flat: [N, T*F] -> Reshape).
+    form: "batch_first" (Transpose(1,0,2) -> time-major layers -> Transpose back, what PyTorch writes for batch_first=True) or "layout1"
+    (layout = 1, no Transpose).  Layers are stacked through Squeeze(axes 1) (one direction) or Transpose(0,2,1,3) + Reshape [0,0,-1].
+    tail: "seq" -> Y [N, T, D*H]; "last_gather" / "last_slice" -> step `last_index` of it [N, D*H]; "y_h" / "y_c" -> the last layer's final
+    state [N, D*H] (Squeeze(axes 0) for one direction, Transpose(1,0,2) + Reshape for two).  head = (W [D*H, M], b [M], act or None): a Gemm
+    (+ activation) behind a 2-D tail.  scaler = (offset, scale) over the flat T*F columns (needs flat).  initial: how a layer's constant initial
+    state is written: "const" ([D, 1, H] initializer), "expand" (Shape(X) -> Gather -> Unsqueeze -> Concat -> Expand) or "fill" (the
+    same shape sub-graph -> ConstantOfShape: a state of one value, as PyTorch writes its zeros).  state_outputs: the
+    last layer's Y_h (and Y_c) are graph outputs too, under the names "Y_h" / "Y_c"."""
+    op, H, D, F = spec["op"], spec["H"], spec["D"], spec["F"]
+    T = spec["T"] if T is None else T
+    nodes, inits = [], []
+    i64 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.int64)))  # noqa: E731
+    x = "X"
+    if scaler is not None:
+        nodes.append(node("Scaler", [x], ["Xs"], [attr_floats("offset", scaler[0]), attr_floats("scale", scaler[1])], domain=ML_DOMAIN))
+        x = "Xs"
+    if flat:
+        i64("flat_shape", [-1, T, F])
+        nodes.append(node("Reshape", [x, "flat_shape"], ["X3"]))
+        x = "X3"
+    lay1 = form == "layout1"
+    if not lay1:
+        nodes.append(node("Transpose", [x], ["Xt"], [attr_ints("perm", [1, 0, 2])]))
+        x = "Xt"
+    i64("ax0", [0]); i64("ax1", [1]); i64("merge", [0, 0, -1])  # noqa: E702
+    yh = yc = None
+    for i, L in enumerate(spec["layers"]):
+        p = f"l{i}_"
+        inits += [tensor(p + "W", L["W"]), tensor(p + "R", L["R"])]
+        ins = [x, p + "W", p + "R", "", "", "", ""]
+        if L["B"] is not None:
+            inits.append(tensor(p + "B", L["B"]))
+            ins[3] = p + "B"
+        for slot, key in ((5, "h0"), (6, "c0")):
+            if L.get(key) is None:
+                continue
+            v = L[key].reshape(1, D, H) if lay1 else L[key].reshape(D, 1, H)
+            inits.append(tensor(p + key, v))
+            ins[slot] = p + key
+            if initial == "expand":  # broadcast over the row count of X, as exporters spell it
+                i64(p + key + "_d", [D]); i64(p + key + "_h", [H]); i64(p + key + "_i", 0 if lay1 else 1)  # noqa: E702
+                pieces = [p + key + "_n", p + key + "_d", p + key + "_h"] if lay1 else [p + key + "_d", p + key + "_n", p + key + "_h"]
+                nodes += [node("Shape", [x], [p + key + "_s"]), node("Gather", [p + key + "_s", p + key + "_i"], [p + key + "_g"], [attr_i("axis", 0)]),
+                          node("Unsqueeze", [p + key + "_g", "ax0"], [p + key + "_n"]), node("Concat", pieces, [p + key + "_shape"], [attr_i("axis", 0)]),
+                          node("Expand", [p + key, p + key + "_shape"], [p + key + "_x"])]
+                ins[slot] = p + key + "_x"
+            elif initial == "fill":  # one value for the whole state (PyTorch's zeros): ConstantOfShape over the same shape sub-graph
+                fill = np.asarray(L[key], dtype=np.float32).ravel()
+                if not np.all(fill == fill[0]):
+                    raise ValueError("initial='fill' needs a state of one value")
+                i64(p + key + "_d", [D]); i64(p + key + "_h", [H]); i64(p + key + "_i", 0 if lay1 else 1)  # noqa: E702
+                pieces = [p + key + "_n", p + key + "_d", p + key + "_h"] if lay1 else [p + key + "_d", p + key + "_n", p + key + "_h"]
+                nodes += [node("Shape", [x], [p + key + "_s"]), node("Gather", [p + key + "_s", p + key + "_i"], [p + key + "_g"], [attr_i("axis", 0)]),
+                          node("Unsqueeze", [p + key + "_g", "ax0"], [p + key + "_n"]), node("Concat", pieces, [p + key + "_shape"], [attr_i("axis", 0)]),
+                          node("ConstantOfShape", [p + key + "_shape"], [p + key + "_x"], [attr_tensor("value", tensor("", fill[:1]))])]
+                ins[slot] = p + key + "_x"
+        while ins and ins[-1] == "":
+            ins.pop()
+        attrs = [attr_i("hidden_size", H), attr_s("direction", spec["direction"])] + list(extra_attrs)
+        if lay1:
+            attrs.append(attr_i("layout", 1))
+        if op == "GRU":
+            attrs.append(attr_i("linear_before_reset", spec["linear_before_reset"]))
+        if op == "RNN" and spec["activation"] != "Tanh":
+            attrs.append(attr_strings("activations", [spec["activation"]] * D))
+        yh, yc = p + "Yh", p + "Yc"
+        nodes.append(node(op, ins, [p + "Y", yh] + ([yc] if op == "LSTM" else []), attrs, name=f"rnn{i}"))
+        if lay1:  # [N, T, D, H] -> [N, T, D*H]
+            nodes.append(node("Reshape", [p + "Y", "merge"], [p + "S"]))
+        elif D == 1:  # [T, 1, N, H] -> [T, N, H]
+            nodes.append(node("Squeeze", [p + "Y", "ax1"], [p + "S"]))
+        else:  # [T, 2, N, H] -> [T, N, 2, H] -> [T, N, 2H]
+            nodes += [node("Transpose", [p + "Y"], [p + "Yt"], [attr_ints("perm", [0, 2, 1, 3])]), node("Reshape", [p + "Yt", "merge"], [p + "S"])]
+        x = p + "S"
+    C = D * H
+    if tail in ("y_h", "y_c"):
+        st = yh if tail == "y_h" else yc
+        i64("flat2", [-1, C])
+        if lay1:
+            nodes.append(node("Reshape", [st, "flat2"], ["out2"]))
+        elif D == 1:
+            nodes.append(node("Squeeze", [st, "ax0"], ["out2"]))
+        else:
+            nodes += [node("Transpose", [st], ["st_t"], [attr_ints("perm", [1, 0, 2])]), node("Reshape", ["st_t", "flat2"], ["out2"])]
+        out, dims = "out2", ["N", C]
+    else:
+        if not lay1:
+            nodes.append(node("Transpose", [x], ["seq"], [attr_ints("perm", [1, 0, 2])]))
+            x = "seq"
+        out, dims = x, ["N", T, C]
+        if tail == "last_gather":
+            i64("last", last_index)
+            nodes.append(node("Gather", [x, "last"], ["out2"], [attr_i("axis", 1)]))
+            out, dims = "out2", ["N", C]
+        elif tail == "last_slice":
+            b = last_index % T
+            i64("sl_b", [b]); i64("sl_e", [b + 1])  # noqa: E702
+            nodes += [node("Slice", [x, "sl_b", "sl_e", "ax1"], ["sl"]), node("Squeeze", ["sl", "ax1"], ["out2"])]
+            out, dims = "out2", ["N", C]
+    if head is not None:
+        Wd, bd, act = head
+        inits += [tensor("head_W", np.asarray(Wd, dtype=np.float32)), tensor("head_b", np.asarray(bd, dtype=np.float32))]
+        nodes.append(node("Gemm", [out, "head_W", "head_b"], ["score"]))
+        out, dims = "score", ["N", int(np.asarray(Wd).shape[1])]
+        if act:
+            nodes.append(node(act, [out], ["prob"]))
+            out = "prob"
+    in_dims = ["N", T * F] if (flat or scaler is not None) else ["N", T, F]
+    outs = [value_info(out, dims)]
+    if state_outputs:
+        sdims = ["N", D, H] if lay1 else [D, "N", H]
+        nodes.append(node("Identity", [yh], ["Y_h"]))
+        outs.append(value_info("Y_h", sdims))
+        if op == "LSTM":
+            nodes.append(node("Identity", [yc], ["Y_c"]))
+            outs.append(value_info("Y_c", sdims))
+    return model("recurrent", nodes, inits, [value_info("X", in_dims)], outs, opset=opset, ml_opset=1 if scaler is not None else None)
+
+
+# ------------------------------------------------------------------------------------------
 # ai.onnx.ml preprocessing (Imputer, Scaler, OneHotEncoder, LabelEncoder, Binarizer, ArrayFeatureExtractor, Concat, ZipMap)
 # ------------------------------------------------------------------------------------------
 
