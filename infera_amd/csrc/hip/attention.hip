@@ -1,0 +1,172 @@
+// attention.hip -- self-attention of a Transformer encoder on gfx950 (semantics: INTEGRATION.md section 2.6; caps: host/attention.hpp).
+// Ahead-of-time kernels; every size is a run-time argument but the number of 16-column fragments of a head (1, 2, 4 or 8: dh <= 128).
+//
+// attention_kernel: for each table row and head, out = softmax(scale . Q K^T + mask) V over the row's T steps.  A workgroup owns one
+// (row, head) and up to 64 queries of it: one wave per 16-query tile (min(4, ceil(T / 16)) waves).  Keys / values are walked in tiles of
+// 32 in a fixed order with a running maximum and sum per query (online softmax), so T is not bounded by LDS; each K / V tile is staged
+// in LDS once for all waves of the workgroup (16-byte global loads where dh, the row strides and the pointers allow, else word loads).
+// Both products run on v_mfma_f32_16x16x4_f32 (exact f32, a fixed k order per output):
+//   S^T[key][query] = K . Q^T:  A = K tile from LDS (lane (m, kq) reads the 16 bytes of key m at columns 16 c + 4 kq), B = Q^T held in
+//       registers for the whole kernel.  The accumulator leaves lane (n, kq) with the scores of query n against keys 4 kq .. 4 kq + 3.
+//   O^T[d][query]  += V^T . P^T: MFMA i of a 16-key tile takes as its four k indices the keys {4 kq + i}: lane (n, kq) then supplies
+//       P[n][4 kq + i], which IS its accumulator register i -- the P fragment needs no re-layout through LDS or lane moves at all; only
+//       the order in which the 16 keys of a tile are summed is permuted (fixed, so still deterministic).  A = V[4 kq + i][16 dt + m].
+// LDS rows are padded by 4 words (stride dhp + 4) so that the 16 key rows a K read touches, and the 4 key rows a V read touches, start
+// in different banks; whether the 16-byte K reads are then free of conflicts was not checked with counters.
+// Only 1, 2, 4 and 8 column fragments are instantiated: dh in 33..48 runs the 4-fragment kernel and dh in 65..112 the 8-fragment one,
+// with zero columns in the rest -- up to 2 x the MFMAs and LDS such a head needs (dh = 40 does the work of 64, dh = 80 that of 128).
+// The scale is applied to the f32 scores (s = scale * (q . k) + mask), wherever the graph applied it.  Keys beyond T and keys whose mask
+// entry is -inf are excluded BEFORE the maximum and get weight exactly 0 (no large negative number); padded head columns are zero in
+// Q, K and V.  The per-query sum is kept as four per-lane partial sums (one per kq) added once at the end.  No atomics, nothing depends
+// on the grid: a row's bits depend on the model and the row only, and a NaN stays in its own row (rows never share a workgroup).
+//
+// Short windows: T = 24 runs 2 waves per workgroup, T <= 16 one; a 2048-row chunk with 4 heads is still 8192 workgroups, so the chip is
+// full, but each wave's MFMAs wait on its own shuffles and exponentials with little to overlap.  Packing several rows into one
+// workgroup for small T and double buffering of the K / V tiles were considered and NOT built, so there is no A/B for them; what was
+// measured is this one form (tools/transformer_time.py, profiles/r11_transformer.txt): its rate, its fraction of the f32 MFMA peak, and
+// its time beside torch-ROCm's float32 scaled_dot_product_attention on the same tensors: 0.10 of the peak at T = 24 and 0.30 at T = 128
+// (dh = 16: four MFMAs per product between shuffles and expf, nothing overlapped), 0.64 x / 0.83 x torch's time -- slower on neither.
+#include "device_common.hpp"
+
+#include "../host/attention.hpp"
+
+namespace infera_hip::kern {
+
+namespace {
+
+constexpr int kAttnKeyTile = 32, kAttnMaxWaves = 4;
+
+struct AttnArgs {
+  const float *q, *k, *v, *mask;
+  float *y;
+  int T, H, dh, ldq, ldk, ldv, offq, offk, offv;
+  float scale;
+  bool vec;
+};
+
+template <int DT>
+__global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs a) {
+  constexpr int DP = DT * 16, LS = DP + 4, QPR = DP / 4;
+  __shared__ __attribute__((aligned(16))) float ks[kAttnKeyTile * LS];
+  __shared__ __attribute__((aligned(16))) float vs[kAttnKeyTile * LS];
+  const int tid = int(threadIdx.x), nth = int(blockDim.x), nw = nth >> 6, wave = tid >> 6, lane = tid & 63, n = lane & 15, kq = lane >> 4;
+  const int64_t row = int64_t(blockIdx.x) / a.H;
+  const int head = int(int64_t(blockIdx.x) - row * a.H), T = a.T, dh = a.dh;
+  const int qi = (int(blockIdx.y) * nw + wave) * 16 + n;
+  const float *qp = a.q + row * T * a.ldq + a.offq + head * dh;
+  const float *kp = a.k + row * T * a.ldk + a.offk + head * dh;
+  const float *vp = a.v + row * T * a.ldv + a.offv + head * dh;
+
+  // up to four consecutive head columns of one step: zero beyond dh
+  auto load4 = [&](const float *p, int d) -> f32x4 {
+    f32x4 r = {0.f, 0.f, 0.f, 0.f};
+    if (a.vec) {
+      if (d < dh) r = *reinterpret_cast<const f32x4 *>(p + d);  // (dh % 4 == 0: a quad is inside or outside as a whole)
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (d + j < dh) r[j] = p[d + j];
+    }
+    return r;
+  };
+
+  f32x4 qr[DT], o[DT];
+#pragma unroll
+  for (int c = 0; c < DT; c++) {
+    qr[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (qi < T) qr[c] = load4(qp + int64_t(qi) * a.ldq, 16 * c + 4 * kq);
+    o[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  float m_run = -INFINITY, l_run = 0.f;
+
+  for (int k0 = 0; k0 < T; k0 += kAttnKeyTile) {
+    __syncthreads();  // the previous tile has been read by every wave
+    for (int e = tid; e < kAttnKeyTile * QPR; e += nth) {
+      const int key = e / QPR, d = (e - key * QPR) * 4;
+      f32x4 kk = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+      if (k0 + key < T) {
+        kk = load4(kp + int64_t(k0 + key) * a.ldk, d);
+        vv = load4(vp + int64_t(k0 + key) * a.ldv, d);
+      }
+      *reinterpret_cast<f32x4 *>(ks + key * LS + d) = kk;
+      *reinterpret_cast<f32x4 *>(vs + key * LS + d) = vv;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int sub = 0; sub < kAttnKeyTile / 16; sub++) {
+      if (k0 + 16 * sub >= T) break;
+      f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < DT; c++) {
+        const f32x4 kf = *reinterpret_cast<const f32x4 *>(ks + (16 * sub + n) * LS + 16 * c + 4 * kq);
+#pragma unroll
+        for (int j = 0; j < 4; j++) s = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[j], qr[c][j], s, 0, 0, 0);
+      }
+      float sc[4], mx = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int key = k0 + 16 * sub + 4 * kq + i;
+        sc[i] = -INFINITY;
+        if (key < T) {
+          sc[i] = s[i] * a.scale;
+          if (a.mask && qi < T) sc[i] += a.mask[int64_t(qi) * T + key];
+        }
+        mx = fmaxf(mx, sc[i]);
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 16));
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      const float m_new = fmaxf(m_run, mx);
+      const float corr = m_new == -INFINITY ? 1.f : expf(m_run - m_new);
+      float p[4], ps = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        p[i] = sc[i] == -INFINITY ? 0.f : expf(sc[i] - m_new);
+        ps += p[i];
+      }
+      l_run = l_run * corr + ps;
+      m_run = m_new;
+#pragma unroll
+      for (int dt = 0; dt < DT; dt++) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) o[dt][i] *= corr;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          o[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(vs[(16 * sub + 4 * kq + i) * LS + 16 * dt + n], p[i], o[dt], 0, 0, 0);
+      }
+    }
+  }
+  l_run += __shfl_xor(l_run, 16);
+  l_run += __shfl_xor(l_run, 32);
+  if (qi >= T) return;
+  float *yp = a.y + (row * T + qi) * int64_t(a.H) * dh + head * dh;
+#pragma unroll
+  for (int dt = 0; dt < DT; dt++)
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int d = 16 * dt + 4 * kq + i;
+      if (d < dh) yp[d] = o[dt][i] / l_run;
+    }
+}
+
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+bool attention(hipStream_t s, const float *q, const float *k, const float *v, const float *mask, float *y, int64_t rows, int T, int heads, int dh,
+               const int64_t ld[3], const int64_t off[3], float scale) {
+  if (rows <= 0) return true;
+  if (T < 1 || T > kAttnMaxT || dh < 1 || dh > kAttnMaxDh || heads < 1 || heads > kAttnMaxHeads || rows * heads > INT32_MAX) return false;
+  AttnArgs a{q, k, v, mask, y, T, heads, dh, int(ld[0]), int(ld[1]), int(ld[2]), int(off[0]), int(off[1]), int(off[2]), scale, false};
+  a.vec = dh % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v);
+  for (int i = 0; i < 3; i++) a.vec = a.vec && ld[i] % 4 == 0 && off[i] % 4 == 0;
+  const int tiles = (T + 15) / 16, nw = tiles < kAttnMaxWaves ? tiles : kAttnMaxWaves;
+  const dim3 grid(unsigned(rows * heads), unsigned((tiles + nw - 1) / nw)), block(unsigned(64 * nw));
+  const int dt = (dh + 15) / 16;
+  if (dt <= 1) hipLaunchKernelGGL(attention_kernel<1>, grid, block, 0, s, a);
+  else if (dt <= 2) hipLaunchKernelGGL(attention_kernel<2>, grid, block, 0, s, a);
+  else if (dt <= 4) hipLaunchKernelGGL(attention_kernel<4>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(attention_kernel<8>, grid, block, 0, s, a);
+  return true;
+}
+
+}  // namespace infera_hip::kern

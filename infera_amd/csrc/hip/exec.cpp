@@ -142,15 +142,15 @@ bool PassRunner::launch_fused(size_t i, size_t *skip) {
     case ExecKind::Skipped: return true;
     case ExecKind::Mlp3Head: {
       std::string why;
-      if (!kern::mlp3(stream, m.mlp3_shape, buf(x.in0), dm.mlp3_packed, buf(st[i + 2].out), nr, dm.num_cus, &why, cm))
+      if (!kern::mlp3(stream, m.mlp3_shape, buf(x.in0), dm.mlp3_packed, buf(st[i + 2].out), nr * x.rep, dm.num_cus, &why, cm))
         throw InferaError::onnx("fused MLP kernel launch failed: " + why);
       return true;
     }
     case ExecKind::ChainHead: {
       const LoadedModel::ChainRun &run = *m.chain_at(i);
       std::string why;
-      if (!kern::chain(stream, run.shape, buf(x.in0), dm.chain_packed[size_t(&run - m.chains.data())], buf(st[i + size_t(run.nsteps) - 1].out), nr,
-                       dm.num_cus, &why, cm))
+      if (!kern::chain(stream, run.shape, buf(x.in0), dm.chain_packed[size_t(&run - m.chains.data())], buf(st[i + size_t(run.nsteps) - 1].out),
+                       nr * st[i + size_t(run.pad)].rep, dm.num_cus, &why, cm))
         throw InferaError::onnx("fused chain kernel launch failed: " + why);
       return true;
     }
@@ -165,7 +165,7 @@ bool PassRunner::launch_fused(size_t i, size_t *skip) {
       kern::dense(stream, buf(x.in0), d.W, d.bias, buf(st[i + 1].out), nr, int(x.K), int(x.M), act_of(x), st[i + 1].log_softmax ? 2 : 1, cm);
       return true;
     case ExecKind::ConvTiled: launch_conv_tiled(i); return true;
-    case ExecKind::DenseTiled: kern::conv2d_tiled(stream, buf(x.in0), d.W, d.bias, nullptr, buf(x.out), nr, dense_as_conv(x), act_of(x)); return true;
+    case ExecKind::DenseTiled: kern::conv2d_tiled(stream, buf(x.in0), d.W, d.bias, nullptr, buf(x.out), nr * x.rep, dense_as_conv(x), act_of(x)); return true;
     case ExecKind::ConvDepthwise: kern::conv2d_depthwise(stream, buf(x.in0), d.W, d.bias, buf(x.out), nr, conv_geom(x), act_of(x)); return true;
     case ExecKind::ConvPatch: launch_conv_patch(i); return true;
     default: return false;
@@ -176,7 +176,8 @@ void PassRunner::launch_plain(size_t i) {
   const Step &x = st[i];
   const DeviceStep &d = dm.steps[i];
   switch (x.kind) {
-    case StepKind::Dense: kern::dense(stream, buf(x.in0), d.W, d.bias, buf(x.out), nr, int(x.K), int(x.M), act_of(x), 0, in_colmajor && x.in0 == 0); break;
+    // (a window Dense, rep > 1: its [rows, rep, K] buffer is the [rows * rep, K] matrix)
+    case StepKind::Dense: kern::dense(stream, buf(x.in0), d.W, d.bias, buf(x.out), nr * x.rep, int(x.K), int(x.M), act_of(x), 0, in_colmajor && x.in0 == 0); break;
     case StepKind::Unary: kern::unary(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], act_of(x)); break;
     case StepKind::AffineChannel:
       kern::affine_channel(stream, buf(x.in0), d.scale, d.shift, buf(x.out), nr, x.C, x.S, act_of(x), cq(x.in0));
@@ -206,7 +207,7 @@ void PassRunner::launch_plain(size_t i) {
       kern::copy_cols(stream, buf(x.in0), buf(x.out), nr, p.buf_per_row[size_t(x.in0)], p.buf_per_row[size_t(x.in0)], 0,
                       p.buf_per_row[size_t(x.out)], x.col_off);
       break;
-    case StepKind::PadCols: kern::pad_cols(stream, buf(x.in0), buf(x.out), nr, x.K, x.M); break;
+    case StepKind::PadCols: kern::pad_cols(stream, buf(x.in0), buf(x.out), nr * x.rep, x.K, x.M); break;
     case StepKind::LRN:
       kern::lrn(stream, buf(x.in0), buf(x.out), nr, int(x.C), int(x.S), int(x.lrn_size), x.lrn_alpha, x.lrn_beta, x.lrn_bias,
                 cq(x.in0));
@@ -251,6 +252,16 @@ void PassRunner::launch_plain(size_t i) {
         throw InferaError::onnx("recurrent kernel launch failed: '" + x.origin + "' could not be given its LDS");
       break;
     }
+    case StepKind::LayerNorm:
+      if (!kern::layernorm(stream, buf(x.in0), d.scale, d.shift, buf(x.out), nr * x.rep, int(x.K), x.ln_eps))
+        throw InferaError::onnx("LayerNorm kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+      break;
+    case StepKind::Attention:
+      if (!kern::attention(stream, buf(x.in0), buf(x.in1), buf(x.in2), d.cst, buf(x.out), nr, int(x.attn_T), int(x.attn_heads), int(x.attn_dh), x.attn_ld,
+                           x.attn_off, x.attn_scale))
+        throw InferaError::onnx("attention kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+      break;
+    case StepKind::MeanTime: kern::mean_time(stream, buf(x.in0), buf(x.out), nr, int(x.rep), int(x.K)); break;
   }
 }
 

@@ -78,6 +78,17 @@ void prep(hipStream_t s, const float *x, int F_in, const uint32_t *desc, const f
 bool rnn(hipStream_t s, const float *x, const float *wr, const float *bias, const float *bias2, const float *h0, const float *c0, float *y, int64_t rows,
          int op, int T, int F, int H, int D, bool reverse, bool lbr, bool relu, int mode, bool x_colmajor);
 
+// ---- Transformer encoders (attention.hip, layernorm.hip) -------------------------------------------------------------------------
+// y [rows, T, heads * dh] = softmax(scale . Q K^T + mask) V per row and head; q / k / v: [rows, T, ld[i]] with head g at columns
+// off[i] + g * dh of a step (the same pointer three times for a packed projection); mask: [T, T] or null, -inf = no weight.
+// false: a size is beyond the caps of host/attention.hpp (the lowering refuses those at load)
+bool attention(hipStream_t s, const float *q, const float *k, const float *v, const float *mask, float *y, int64_t rows, int T, int heads, int dh,
+               const int64_t ld[3], const int64_t off[3], float scale);
+// y = (x - mean) / sqrt(var + eps) * gamma + beta over each of nvec vectors of E elements (beta may be null); false: E beyond the cap
+bool layernorm(hipStream_t s, const float *x, const float *gamma, const float *beta, float *y, int64_t nvec, int E, float eps);
+// y[r, e] = mean over t of x[r, t, e]
+void mean_time(hipStream_t s, const float *x, float *y, int64_t rows, int T, int E);
+
 // ---- dense layer, fp32 MFMA (dense.hip) -------------------------------------------------------
 // Y[rows, M] = act(X[rows, K] . W[K, M] + bias[M]); W row-major, bias may be null.
 // softmax_fused: apply a row softmax over the M outputs in the epilogue (requires M <= 256).

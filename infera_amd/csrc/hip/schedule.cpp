@@ -32,6 +32,7 @@ std::vector<EffStep> effective_steps(const LoadedModel &m) {
       default: {
         EffStep e{int(i), {st[i].in0}, st[i].out};
         if (st[i].in1 >= 0) e.reads.push_back(st[i].in1);
+        if (st[i].in2 >= 0) e.reads.push_back(st[i].in2);
         out.push_back(e);
       }
     }
@@ -52,6 +53,7 @@ struct Scheduler {
     for (const auto &s : st) {
       if (s.in0 >= 0) uses[size_t(s.in0)]++;
       if (s.in1 >= 0) uses[size_t(s.in1)]++;
+      if (s.in2 >= 0) uses[size_t(s.in2)]++;
     }
     uses[size_t(m.plan.out_buf)]++;
   }
@@ -75,7 +77,7 @@ void Scheduler::fuse_tabular() {
     // Dense -> Dense -> Dense with private intermediates: whole-chain fused kernel
     if (cfg.fused_mlp && !have_mlp3 && i + 2 < n && st[i].kind == StepKind::Dense && st[i + 1].kind == StepKind::Dense &&
         st[i + 2].kind == StepKind::Dense && st[i + 1].in0 == st[i].out && st[i + 2].in0 == st[i + 1].out &&
-        uses[size_t(st[i].out)] == 1 && uses[size_t(st[i + 1].out)] == 1) {
+        uses[size_t(st[i].out)] == 1 && uses[size_t(st[i + 1].out)] == 1 && st[i].rep == st[i + 1].rep && st[i].rep == st[i + 2].rep) {
       kern::Mlp3Shape sh{int(st[i].K), int(st[i].M), int(st[i + 1].M), int(st[i + 2].M), int(st[i].act), int(st[i + 1].act),
                          int(st[i + 2].act)};
       std::string why;
@@ -99,7 +101,7 @@ void Scheduler::fuse_tabular() {
       size_t j = i;
       int pad = 0;
       if (st[j].kind == StepKind::PadCols && j + 1 < n && st[j + 1].kind == StepKind::Dense && st[j + 1].in0 == st[j].out &&
-          uses[size_t(st[j].out)] == 1 && m.exec[j + 1] == ExecKind::Normal) {
+          uses[size_t(st[j].out)] == 1 && m.exec[j + 1] == ExecKind::Normal && st[j].rep == st[j + 1].rep) {
         pad = 1;
         j++;
       }
@@ -107,7 +109,7 @@ void Scheduler::fuse_tabular() {
       sh.k0 = pad ? int(st[i].K) : int(st[j].K);
       const size_t d0 = j;
       while (j < n && st[j].kind == StepKind::Dense && m.exec[j] == ExecKind::Normal && int(st[j].act) <= kMaxMfmaFusedAct &&
-             st[j].K <= 128 && st[j].M <= 128 && (j == d0 || (st[j].in0 == st[j - 1].out && uses[size_t(st[j - 1].out)] == 1))) {
+             st[j].K <= 128 && st[j].M <= 128 && (j == d0 || (st[j].in0 == st[j - 1].out && uses[size_t(st[j - 1].out)] == 1 && st[j].rep == st[d0].rep))) {
         sh.dims.push_back(int(st[j].M));
         sh.acts.push_back(int(st[j].act));
         sh.pa.push_back(st[j].act_a);
@@ -116,12 +118,12 @@ void Scheduler::fuse_tabular() {
       }
       const size_t layers = j - d0;
       // a single layer with 17..32 outputs over rows the aligned kernels cannot read would fall to the generic kernel
-      const bool tail_next = layers >= 1 && j < n && st[j].in0 == st[j - 1].out && uses[size_t(st[j - 1].out)] == 1 &&
+      const bool tail_next = layers >= 1 && j < n && st[d0].rep == 1 && st[j].in0 == st[j - 1].out && uses[size_t(st[j - 1].out)] == 1 &&
                              (st[j].kind == StepKind::Softmax || st[j].kind == StepKind::ArgMax);
       // ... and a single 17..128-wide layer whose Softmax / ArgMax would otherwise cost two more passes over its scores
       const bool lone_gap = layers == 1 && !pad && st[d0].M > 16 && ((st[d0].M <= 32 && st[d0].K % 8 != 0) || tail_next);  // (layers == 1: d0 is a Dense step)
       if (layers >= 2 || (layers == 1 && pad) || lone_gap) {
-        if (j < n && st[j].in0 == st[j - 1].out && uses[size_t(st[j - 1].out)] == 1 && m.exec[j] == ExecKind::Normal) {
+        if (j < n && st[d0].rep == 1 && st[j].in0 == st[j - 1].out && uses[size_t(st[j - 1].out)] == 1 && m.exec[j] == ExecKind::Normal) {
           if (st[j].kind == StepKind::Softmax && st[j].sm_norm == 0 && st[j].sm_outer == 1 && st[j].sm_inner == 1 && st[j].sm_len == st[j - 1].M) {
             sh.sm = st[j].log_softmax ? 2 : 1;
             j++;
@@ -148,7 +150,7 @@ void Scheduler::fuse_tabular() {
     }
     // Dense + row Softmax over exactly its M outputs: softmax in the GEMM epilogue
     if (i + 1 < n && st[i].kind == StepKind::Dense && st[i + 1].kind == StepKind::Softmax && st[i + 1].in0 == st[i].out &&
-        uses[size_t(st[i].out)] == 1 && st[i + 1].sm_outer == 1 && st[i + 1].sm_inner == 1 && st[i + 1].sm_len == st[i].M &&
+        uses[size_t(st[i].out)] == 1 && st[i].rep == 1 && st[i + 1].sm_outer == 1 && st[i + 1].sm_inner == 1 && st[i + 1].sm_len == st[i].M &&
         kern::dense_can_fuse_softmax(int(st[i].K), int(st[i].M)) && st[i + 1].sm_norm == 0) {
       m.exec[i] = ExecKind::DenseSoftmax;
       m.exec[i + 1] = ExecKind::Skipped;
@@ -159,7 +161,7 @@ void Scheduler::fuse_tabular() {
     // the scores never reach memory.  Both buffers stay planned: the launch falls back to the two kernels when the
     // input pointer it meets at run time cannot feed a kernel with that epilogue (dense_can_fuse_argmax).
     if (i + 1 < n && st[i].kind == StepKind::Dense && st[i + 1].kind == StepKind::ArgMax && st[i + 1].in0 == st[i].out &&
-        uses[size_t(st[i].out)] == 1 && st[i + 1].K == st[i].M && st[i].M <= 64 &&
+        uses[size_t(st[i].out)] == 1 && st[i].rep == 1 && st[i + 1].K == st[i].M && st[i].M <= 64 &&
         kern::dense_can_fuse_argmax(nullptr, int(st[i].K), int(st[i].M))) {
       m.exec[i] = ExecKind::DenseArgMax;
       i += 1;
@@ -414,6 +416,7 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
         // (a tree walk reads its row tile once per tree slice, and wide rows feature by feature; an SVM once per SV slice)
         const bool windowed = (sk == StepKind::Conv2d && m.exec[size_t(e.idx)] != ExecKind::ConvPatch) || sk == StepKind::Pool2d || sk == StepKind::LRN ||
                               sk == StepKind::TreeEnsemble || sk == StepKind::SvmKernel ||
+                              sk == StepKind::Attention ||  // (every query tile walks all keys and values)
                               sk == StepKind::Recurrent;  // (one dependent fetch per time step: from HBM, not over PCIe)
         m.in_single_reader = !windowed;
         break;
@@ -437,6 +440,16 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
     }
     // ... and the recurrent kernel stages x_t from either order with the same loads (rnn.hip)
     if (!eff.empty() && in_readers == 1 && eff[0].reads[0] == 0 && st[size_t(eff[0].idx)].kind == StepKind::Recurrent) m.in_colmajor_ok = true;
+    // a window Dense (behind its PadCols or not) reads its [rows, T, K] input as the [rows * T, K] matrix: a column-major chunk
+    // [T * K][rows] is no such matrix, so the host path hands these plans their input row-major (transposed first)
+    auto window_dense_at = [&](size_t i) {
+      if (st[i].kind == StepKind::PadCols && i + 1 < n) i++;
+      return st[i].kind == StepKind::Dense && st[i].rep > 1;
+    };
+    if (!eff.empty() && eff[0].reads[0] == 0 && window_dense_at(size_t(eff[0].idx))) {
+      m.in_colmajor_ok = false;
+      m.in_colmajor_max_rows = INT64_MAX;
+    }
   }
 }
 

@@ -1,0 +1,14 @@
+// attention.hpp -- the caps of the Transformer-encoder kernels (hip/attention.hip, hip/layernorm.hip), shared by the lowering (which refuses
+// by name what the kernels cannot serve: INTEGRATION.md section 2.6) and the launchers.
+#pragma once
+
+#include <cstdint>
+
+namespace infera_hip {
+
+constexpr int64_t kAttnMaxT = 1024;   // window length: the [T, T] mask constant and the 32-bit score indices
+constexpr int64_t kAttnMaxDh = 128;   // head width: Q and the output tile of a wave live in registers (8 + 8 fragments of 16 columns)
+constexpr int64_t kAttnMaxHeads = 1024;
+constexpr int64_t kLnMaxE = 4096;     // LayerNorm vector length: one vector is held in the registers of one wave (64 floats per lane)
+
+}  // namespace infera_hip

@@ -20,6 +20,7 @@
 #include <numeric>
 #include <sstream>
 
+#include "attention.hpp"
 #include "common.hpp"
 #include "plan.hpp"
 #include "prep.hpp"
@@ -223,8 +224,19 @@ struct Lowerer {
   }
   Step &emit(Step s, const NodeDef &n, const std::vector<int64_t> &out_shape) {
     s.origin = node_label(n);
-    set_act(n, push_step(std::move(s), out_shape), out_shape);
+    // a rank-3 value computed elementwise from a window [rows, T, C] that a step wrote into a flat [rows, T * C] buffer (a recurrent,
+    // window Dense, LayerNorm or attention step) is a window itself, not an [N, C, L] tensor: its buffer stays flat, so time steps can
+    // be cut out of it.  (Values computed from the model input keep the [N, C, 1, L] registration a Conv1d behind them relies on.)
+    const bool eltwise = s.kind == StepKind::Unary || s.kind == StepKind::BinaryConst || s.kind == StepKind::BinaryAct || s.kind == StepKind::AffineChannel;
+    const bool window = eltwise && out_shape.size() == 3 && s.in0 > 0 && plan.buf_shape[size_t(s.in0)].size() == 2;
+    set_act(n, push_step(std::move(s), window ? flat_shape(out_shape) : out_shape), out_shape);
     return plan.steps.back();
+  }
+  static std::vector<int64_t> flat_shape(const std::vector<int64_t> &shape) { return {shape[0], prod(shape, 1)}; }
+  // ... the same for a step whose output is a window by construction
+  void emit_window(Step s, const NodeDef &n, const std::vector<int64_t> &out_shape) {
+    if (s.origin.empty()) s.origin = node_label(n);
+    set_act(n, push_step(std::move(s), flat_shape(out_shape)), out_shape);
   }
 
   // ------------------------------------------------------------------------------------------
@@ -232,7 +244,12 @@ struct Lowerer {
     const Val &a = get(n, 0);
     const Val &b = get(n, 1);
     if (a.is_const) unsupported(n, "constant left operand is not supported");
-    if (!b.is_const) unsupported(n, "right operand must be a constant weight matrix");
+    if (!b.is_const) {
+      auto why = attn_fail.find(&n);
+      if (why != attn_fail.end()) unsupported(n, "unsupported operator form: " + why->second);
+      unsupported(n, "right operand must be a constant weight matrix");
+    }
+    if (!gemm && a.shape.size() == 3 && a.ra == 0 && b.shape.size() == 2) return dense_window(n);
     if (a.shape.size() != 2 || b.shape.size() != 2) unsupported(n, "only [rows,K] x [K,M] is supported, got " + shape_str(a.shape) + " x " + shape_str(b.shape));
     bool tA = gemm && n.attr_i("transA", 0) != 0, tB = gemm && n.attr_i("transB", 0) != 0;
     if (tA) unsupported(n, "transA=1 mixes table rows and is not supported");
@@ -326,6 +343,39 @@ struct Lowerer {
     }
     Step &e = emit(std::move(s), n, {a_shape[0], M});
     if (folded) e.origin = folded_origin + "+" + e.origin;
+  }
+
+  // MatMul of a window [rows, T, K] by a constant [K, M]: the flat buffer IS the [rows * T, K] matrix, so this is a Dense step with a
+  // repeat count (Step::rep), served by the Dense kernels over rows * T rows.  The bias Add and the activation behind it fuse as usual.
+  void dense_window(const NodeDef &n) {
+    const Val a = get(n, 0);
+    const Val &b = get(n, 1);
+    const auto &w = cf32(n, b);
+    const int64_t N = a.shape[0], T = a.shape[1], K = b.shape[0], M = b.shape[1];
+    if (T <= 0 || a.shape[2] != K) unsupported(n, "inner dimensions differ: " + shape_str(a.shape) + " x " + shape_str(b.shape));
+    if (K <= 0 || M <= 0 || int64_t(w.size()) != K * M) unsupported(n, "weight matrix " + shape_str(b.shape) + " does not match its data");
+    prod({T, std::max(K, M) + 3});  // (throws when T * K or T * M leaves int64)
+    int in_buf = a.buf;
+    const int64_t Kp = (M > 32 && K % 4 != 0 && !(K > 128 && M <= 64)) ? (K + 3) / 4 * 4 : K;  // (the rule of dense())
+    if (Kp != K) {
+      Step p;
+      p.kind = StepKind::PadCols;
+      p.in0 = in_buf;
+      p.K = K;
+      p.M = Kp;
+      p.rep = T;
+      p.origin = node_label(n) + "[pad]";
+      in_buf = push_step(std::move(p), {N, T * Kp});
+    }
+    Step s;
+    s.kind = StepKind::Dense;
+    s.in0 = in_buf;
+    s.K = Kp;
+    s.M = M;
+    s.rep = T;
+    s.W.assign(size_t(Kp * M), 0.f);
+    std::copy(w.begin(), w.end(), s.W.begin());
+    emit_window(std::move(s), n, {N, T, M});
   }
 
   // Broadcast a constant against an activation's per-row shape; returns per_row floats.
@@ -811,6 +861,10 @@ struct Lowerer {
   }
   void reduce_mean(const NodeDef &n) {
     const Val &a = get(n, 0);
+    if (!a.is_const && a.shape.size() == 2) {
+      const Val x = a;
+      if (decomposed_layer_norm(n, x)) return;
+    }
     if (a.is_const || a.shape.size() < 3) unsupported(n, "only spatial means of [N,C,...] activations");
     std::vector<int64_t> axes;
     if (has_input(n, 1)) axes = const_ints(n, 1, "axes");
@@ -821,6 +875,17 @@ struct Lowerer {
       const int64_t na = ax < 0 ? ax + rank : ax;
       if (na < 0 || na >= rank) unsupported(n, "axis " + std::to_string(ax) + " is out of range for rank " + std::to_string(rank));
       red[size_t(na)] = true;
+    }
+    if (rank == 3 && a.ra == 0 && red[1] && !red[0] && !red[2]) {  // the mean over the time axis of a window [rows, T, E] -> [rows, E]
+      Step s;
+      s.kind = StepKind::MeanTime;
+      s.in0 = a.buf;
+      s.rep = a.shape[1];
+      s.K = a.shape[2];
+      const int64_t N = a.shape[0], E = a.shape[2];
+      if (n.attr_i("keepdims", 1) != 0) emit_window(std::move(s), n, {N, 1, E});
+      else emit(std::move(s), n, {N, E});
+      return;
     }
     for (int64_t i = 0; i < rank; i++)
       if (red[size_t(i)] != (i >= 2)) unsupported(n, "axes must be exactly the spatial axes");
@@ -1366,6 +1431,552 @@ struct Lowerer {
     s.origin = node_label(n);
     set_act(n, push_step(std::move(s), bshape), vshape);
   }
+
+  // ---- the decomposed LayerNorm older exporters write, on [rows, E] (where nothing else serves it):
+  //   ReduceMean(-1) -> Sub -> Pow(2) | Mul(d, d) -> ReduceMean(-1) -> Add(eps) -> Sqrt -> Div [-> Mul(gamma)] [-> Add(beta)]
+  // matched forward from the first ReduceMean when it is met; the nodes behind it emit nothing and the last one's output is the step's.
+  const NodeDef *only_reader(const std::string &v) const {
+    auto it = consumers_of.find(v);
+    if (it == consumers_of.end() || it->second.empty()) return nullptr;
+    for (size_t c : it->second)
+      if (c != it->second[0]) return nullptr;
+    for (const auto &o : m.outputs)
+      if (o.name == v) return nullptr;
+    return &m.nodes[it->second[0]];
+  }
+  bool last_axis_mean(const NodeDef &n, int64_t rank) {
+    if (n.op != "ReduceMean" || n.attr_i("keepdims", 1) == 0) return false;
+    std::vector<int64_t> axes;
+    if (has_input(n, 1)) {
+      const Val *c = find_value(n.inputs[1]);
+      if (!c || !c->is_const || c->c->dtype != onnx::kInt64) return false;
+      axes = c->c->i64;
+    } else if (auto *p = n.attr_ints("axes")) axes = *p;
+    return axes.size() == 1 && (axes[0] == -1 || axes[0] == rank - 1);
+  }
+  // the f32 constant other operand of a two-input node reading `v`, or null
+  const Val *const_operand(const NodeDef &n, const std::string &v, bool second_only = false) {
+    if (n.inputs.size() != 2) return nullptr;
+    const bool left = n.inputs[0] == v;
+    if (!left && (second_only || n.inputs[1] != v)) return nullptr;
+    const Val *c = find_value(n.inputs[left ? 1 : 0]);
+    return c && c->is_const && c->c->dtype == onnx::kFloat ? c : nullptr;
+  }
+  bool decomposed_layer_norm(const NodeDef &mean, const Val &x) {
+    const int64_t rank = int64_t(x.shape.size()), E = x.shape.back();
+    if (rank != 2 || x.ra != 0 || E < 1 || E > kLnMaxE || !last_axis_mean(mean, rank)) return false;
+    std::vector<const NodeDef *> nodes;
+    const NodeDef *sub = only_reader(mean.outputs[0]);
+    if (!sub || sub->op != "Sub" || sub->inputs.size() != 2 || sub->inputs[0] != mean.inputs[0] || sub->inputs[1] != mean.outputs[0]) return false;
+    const std::string &d = sub->outputs[0];
+    for (const auto &o : m.outputs)
+      if (o.name == d) return false;
+    auto dit = consumers_of.find(d);
+    if (dit == consumers_of.end()) return false;
+    const std::set<size_t> readers(dit->second.begin(), dit->second.end());
+    if (readers.size() != 2) return false;
+    const NodeDef *sq = nullptr, *div = nullptr;
+    for (size_t c : readers) {
+      const NodeDef &r = m.nodes[c];
+      if (r.op == "Div" && r.inputs.size() == 2 && r.inputs[0] == d) div = &r;
+      else if (r.op == "Mul" && r.inputs.size() == 2 && r.inputs[0] == d && r.inputs[1] == d) sq = &r;
+      else if (r.op == "Pow") {
+        const Val *e = const_operand(r, d, true);
+        if (e && e->c->f32.size() == 1 && e->c->f32[0] == 2.f) sq = &r;
+      }
+    }
+    if (!sq || !div) return false;
+    const NodeDef *var = only_reader(sq->outputs[0]);
+    if (!var || !last_axis_mean(*var, rank)) return false;
+    const NodeDef *add = only_reader(var->outputs[0]);
+    const Val *eps = add && add->op == "Add" ? const_operand(*add, var->outputs[0]) : nullptr;
+    if (!eps || eps->c->f32.size() != 1 || !(eps->c->f32[0] >= 0.f) || !std::isfinite(eps->c->f32[0])) return false;
+    const NodeDef *sq_rt = only_reader(add->outputs[0]);
+    if (!sq_rt || sq_rt->op != "Sqrt" || only_reader(sq_rt->outputs[0]) != div || div->inputs[1] != sq_rt->outputs[0]) return false;
+    Step s;
+    s.kind = StepKind::LayerNorm;
+    s.in0 = x.buf;
+    s.K = E;
+    s.rep = 1;
+    s.ln_eps = eps->c->f32[0];
+    s.scale.assign(size_t(E), 1.f);
+    nodes = {sub, sq, var, add, sq_rt, div};
+    const NodeDef *last = div;
+    if (const NodeDef *mul = only_reader(div->outputs[0]); mul && mul->op == "Mul") {
+      const Val *g = const_operand(*mul, div->outputs[0]);
+      if (g && int64_t(g->c->f32.size()) == E && g->shape.size() <= 2 && (g->shape.size() < 2 || g->shape[0] == 1)) {
+        s.scale = g->c->f32;
+        nodes.push_back(last = mul);
+      }
+    }
+    if (const NodeDef *bad = only_reader(last->outputs[0]); bad && bad->op == "Add") {
+      const Val *b = const_operand(*bad, last->outputs[0]);
+      if (b && int64_t(b->c->f32.size()) == E && b->shape.size() <= 2 && (b->shape.size() < 2 || b->shape[0] == 1)) {
+        s.shift = b->c->f32;
+        nodes.push_back(last = bad);
+      }
+    }
+    for (const NodeDef *q : nodes) absorbed[size_t(q - m.nodes.data())] = 1;
+    s.origin = node_label(mean) + "+...+" + node_label(*last);
+    const std::vector<int64_t> shape = x.shape;
+    Val v;
+    v.buf = push_step(std::move(s), shape);
+    v.shape = shape;
+    vals[last->outputs[0]] = v;
+    buf_names[v.buf].push_back(last->outputs[0]);
+    return true;
+  }
+
+  // LayerNormalization (opset 17) over the last axis of [rows, E] / [rows, T, E]: one LayerNorm step (hip/layernorm.hip)
+  void layer_norm(const NodeDef &n) {
+    const Val a = get(n, 0);
+    const int64_t rank = int64_t(a.shape.size());
+    if (a.is_const || rank < 2) unsupported(n, "unsupported operator form: the input must be a [rows, E] or [rows, T, E] activation");
+    int64_t axis = n.attr_i("axis", -1);
+    if (axis < 0) axis += rank;
+    if (axis != rank - 1)
+      unsupported(n, "unsupported operator form: only normalisation over the last axis (axis = -1) is supported, got axis " + std::to_string(n.attr_i("axis", -1)) +
+                         " of " + shape_str(a.shape));
+    for (size_t o = 1; o < n.outputs.size(); o++)
+      if (!n.outputs[o].empty() && uses.count(n.outputs[o]) && uses[n.outputs[o]] > 0)
+        unsupported(n, std::string("unsupported operator form: output ") + (o == 1 ? "Mean" : "InvStdDev") + " is consumed; only Y is served");
+    if (!has_input(n, 1)) unsupported(n, "unsupported operator form: Scale is required");
+    const int64_t E = a.shape[size_t(rank - 1)];
+    if (E < 1 || E > kLnMaxE) unsupported(n, "unsupported operator form: E = " + std::to_string(E) + " is beyond the LayerNorm kernel's cap of " + std::to_string(kLnMaxE));
+    Step s;
+    s.kind = StepKind::LayerNorm;
+    s.in0 = a.buf;
+    s.K = E;
+    s.rep = prod(a.shape, 1) / E;
+    s.scale = cf32(n, get(n, 1));
+    if (has_input(n, 2)) s.shift = cf32(n, get(n, 2));
+    if (int64_t(s.scale.size()) != E || (!s.shift.empty() && int64_t(s.shift.size()) != E)) unsupported(n, "unsupported operator form: Scale / B must have E = " + std::to_string(E) + " elements");
+    s.ln_eps = n.attr_f("epsilon", 1e-5f);
+    if (!(s.ln_eps >= 0.f) || !std::isfinite(s.ln_eps)) unsupported(n, "unsupported operator form: epsilon must be a finite number >= 0");
+    if (rank == 3) emit_window(std::move(s), n, a.shape);
+    else emit(std::move(s), n, a.shape);
+  }
+
+  // ---- self-attention ----------------------------------------------------------------------------
+  // The batch-first graph exporters write is matched structurally before the walk (find_attention: by operator, perm and which operands
+  // are constants), anchored at the merge Reshape; the nodes inside emit nothing, and the anchor validates shapes and constants and emits
+  // ONE Attention step (lower_attention).  A MatMul of two activations that starts no such pattern is rejected with the reason kept here.
+  struct AttnScale {
+    char op;  // '*' or '/'
+    std::string cst;
+  };
+  struct AttnSide {
+    std::string src, shape;   // the [N, T, E] value the head split reads (behind an absorbed Split / Slice: its input) and the Reshape's target
+    const NodeDef *cut = nullptr;  // that Split / Slice on the last axis
+    size_t cut_out = 0;
+  };
+  struct AttnMatch {
+    AttnSide side[3];  // Q, K, V
+    std::vector<AttnScale> scales;
+    std::string mask;
+    const NodeDef *qk = nullptr;
+    std::vector<size_t> nodes;
+  };
+  std::map<size_t, AttnMatch> attn_at;            // anchor node index -> the pattern it closes
+  std::vector<char> absorbed;                // nodes inside a recognised pattern (attention, or the decomposed LayerNorm): they emit nothing
+  std::map<const NodeDef *, std::string> attn_fail;  // MatMul(activation, activation) nodes outside one: why
+  std::map<std::string, std::vector<size_t>> consumers_of;  // live consumers of every value
+  std::map<std::string, size_t> producer_of;
+
+  void find_attention(const std::vector<char> &live) {
+    const size_t N = m.nodes.size();
+    absorbed.assign(N, 0);
+    for (size_t i = 0; i < N; i++) {
+      if (!live[i]) continue;
+      for (const auto &o : m.nodes[i].outputs) producer_of[o] = i;
+      for (const auto &in : m.nodes[i].inputs) consumers_of[in].push_back(i);
+    }
+    std::set<std::string> graph_outs;
+    for (const auto &o : m.outputs) graph_outs.insert(o.name);
+    // values that hold row data: computed from a graph input (Shape's result is not); everything else folds to a constant
+    std::set<std::string> row_data;
+    for (const auto &v : m.inputs) row_data.insert(v.name);
+    for (size_t i = 0; i < N; i++) {
+      if (!live[i] || m.nodes[i].op == "Shape") continue;
+      bool any = false;
+      for (const auto &in : m.nodes[i].inputs) any = any || row_data.count(in);
+      if (any)
+        for (const auto &o : m.nodes[i].outputs) row_data.insert(o);
+    }
+    auto is_const = [&](const std::string &v) { return row_data.count(v) == 0; };
+    auto perm_of = [&](const NodeDef &t) {
+      std::vector<int64_t> p;
+      if (auto *q = t.attr_ints("perm")) p = *q;
+      return p;
+    };
+    // the node that alone reads `v` (null: several readers, none, or a graph output)
+    auto sole_reader = [&](const std::string &v) -> const NodeDef * {
+      auto it = consumers_of.find(v);
+      if (it == consumers_of.end() || it->second.size() != 1 || graph_outs.count(v)) return nullptr;
+      return &m.nodes[it->second[0]];
+    };
+    auto producer = [&](const std::string &v) -> const NodeDef * {
+      auto it = producer_of.find(v);
+      return it == producer_of.end() ? nullptr : &m.nodes[it->second];
+    };
+    const std::string generic = "MatMul of two activations outside a recognised self-attention pattern (Reshape [N,T,h,dh] -> Transpose(0,2,1,3), Q K^T, "
+                                "scale, constant mask, Softmax(-1), P V, Transpose(0,2,1,3) -> Reshape [N,T,E]); the right operand must otherwise be a constant weight matrix";
+    for (size_t qi = 0; qi < N; qi++) {
+      const NodeDef &qk = m.nodes[qi];
+      if (!live[qi] || qk.op != "MatMul" || !(qk.domain.empty() || qk.domain == "ai.onnx") || qk.inputs.size() != 2 || is_const(qk.inputs[0]) || is_const(qk.inputs[1])) continue;
+      if (absorbed[qi]) continue;  // (the P V product of a pattern already matched)
+      AttnMatch am;
+      am.qk = &qk;
+      am.nodes.push_back(qi);
+      std::string why;
+      // constant scalar Mul / Div hops towards the producer: v = the value behind them
+      auto strip_scales = [&](std::string v) {
+        for (;;) {
+          const NodeDef *p = producer(v);
+          if (!p || (p->op != "Mul" && p->op != "Div") || p->inputs.size() != 2 || sole_reader(v) == nullptr) return v;
+          const bool c0 = is_const(p->inputs[0]), c1 = is_const(p->inputs[1]);
+          if (c0 == c1 || (p->op == "Div" && c0)) return v;
+          am.scales.push_back({p->op == "Mul" ? '*' : '/', p->inputs[c0 ? 0 : 1]});
+          am.nodes.push_back(producer_of[v]);
+          v = p->inputs[c0 ? 1 : 0];
+        }
+      };
+      // one operand back to its head split; kt: the K^T operand
+      auto match_head = [&](const std::string &operand, AttnSide &side, bool kt) -> bool {
+        std::string v = strip_scales(operand);
+        const NodeDef *t = producer(v);
+        if (!t || t->op != "Transpose" || !sole_reader(v)) return why = generic, false;
+        std::vector<int64_t> perm = perm_of(*t);
+        if (perm.size() == 3)
+          return why = "PyTorch nn.MultiheadAttention's time-major export (heads folded into the row axis, [T, N*h, dh]) is not supported yet; "
+                       "export batch-first projections with the head split Reshape [N,T,h,dh] -> Transpose(0,2,1,3)", false;
+        if (perm == std::vector<int64_t>{2, 0, 3, 1, 4})
+          return why = "the packed head split [N,T,3,h,dh] -> Transpose(2,0,3,1,4) is not supported yet; split Q, K and V on the last axis first", false;
+        am.nodes.push_back(producer_of[v]);
+        if (kt && perm == std::vector<int64_t>{0, 1, 3, 2}) {  // (0,2,1,3) first, then the last two axes
+          v = strip_scales(t->inputs[0]);
+          t = producer(v);
+          if (!t || t->op != "Transpose" || !sole_reader(v) || perm_of(*t) != std::vector<int64_t>{0, 2, 1, 3}) return why = generic, false;
+          am.nodes.push_back(producer_of[v]);
+        } else if (perm != (kt ? std::vector<int64_t>{0, 2, 3, 1} : std::vector<int64_t>{0, 2, 1, 3})) {
+          return why = generic, false;
+        }
+        v = t->inputs[0];
+        const NodeDef *r = producer(v);
+        if (!r || r->op != "Reshape" || r->inputs.size() != 2 || !sole_reader(v)) {
+          if (r && r->op == "Transpose" && perm_of(*r) == std::vector<int64_t>{2, 0, 3, 1, 4})
+            return why = "the packed head split [N,T,3,h,dh] -> Transpose(2,0,3,1,4) is not supported yet; split Q, K and V on the last axis first", false;
+          return why = generic, false;
+        }
+        am.nodes.push_back(producer_of[v]);
+        side.src = r->inputs[0];
+        side.shape = r->inputs[1];
+        const NodeDef *c = producer(side.src);
+        if (c && (c->op == "Split" || c->op == "Slice") && (c->domain.empty() || c->domain == "ai.onnx")) {
+          int64_t axis = -100;
+          if (c->op == "Split") axis = c->attr_i("axis", 0);
+          else if (c->inputs.size() >= 4 && is_const(c->inputs[3])) {
+            auto ci = m.initializers.find(c->inputs[3]);
+            if (ci != m.initializers.end() && ci->second->dtype == onnx::kInt64 && ci->second->i64.size() == 1) axis = ci->second->i64[0];
+          }
+          if (axis == 2 || axis == -1) {
+            side.cut = c;
+            side.cut_out = size_t(std::find(c->outputs.begin(), c->outputs.end(), side.src) - c->outputs.begin());
+            side.src = c->inputs[0];
+            am.nodes.push_back(producer_of[r->inputs[0]]);
+          }
+        }
+        return true;
+      };
+      bool ok = true;
+      // forward: scale / mask hops, Softmax, P V, merge
+      std::string cur = qk.outputs[0];
+      const NodeDef *sm = nullptr;
+      while (ok && !sm) {
+        const NodeDef *c = sole_reader(cur);
+        if (!c || !(c->domain.empty() || c->domain == "ai.onnx")) { ok = false; why = generic; break; }
+        const size_t ci = consumers_of[cur][0];
+        if ((c->op == "Mul" || c->op == "Div" || c->op == "Add") && c->inputs.size() == 2) {
+          const bool left = c->inputs[0] == cur;
+          const std::string &other = c->inputs[left ? 1 : 0];
+          if (!is_const(other)) {
+            ok = false;
+            why = c->op == "Add" ? "the attention mask '" + other + "' is not a constant (a mask computed in the graph or depending on the row is not supported)"
+                                 : "the scale '" + other + "' of the attention scores is not a constant (a scale computed from the rows is not supported)";
+            break;
+          }
+          if (c->op == "Add") {
+            if (!am.mask.empty()) { ok = false; why = "more than one mask is added to the attention scores"; break; }
+            am.mask = other;
+          } else {
+            if (c->op == "Div" && !left) { ok = false; why = generic; break; }
+            am.scales.push_back({c->op == "Mul" ? '*' : '/', other});
+          }
+          am.nodes.push_back(ci);
+          cur = c->outputs[0];
+        } else if (c->op == "Softmax") {
+          const int64_t axis = c->attr_i("axis", m.opset >= 13 ? -1 : 1);
+          if (axis != -1 && axis != 3) {
+            ok = false;
+            why = "Softmax over axis " + std::to_string(axis) + " inside an attention pattern: only the key axis (-1) is supported";
+            break;
+          }
+          sm = c;
+          am.nodes.push_back(ci);
+        } else {
+          ok = false;
+          why = generic;
+        }
+      }
+      size_t anchor = 0;
+      if (ok) {
+        const NodeDef *pv = sole_reader(sm->outputs[0]);
+        if (!pv || pv->op != "MatMul" || pv->inputs.size() != 2 || pv->inputs[0] != sm->outputs[0] || is_const(pv->inputs[1])) ok = false, why = generic;
+        if (ok) {
+          am.nodes.push_back(consumers_of[sm->outputs[0]][0]);
+          ok = match_head(pv->inputs[1], am.side[2], false);
+        }
+        if (ok) {
+          const NodeDef *t = sole_reader(pv->outputs[0]);
+          if (!t || t->op != "Transpose" || perm_of(*t) != std::vector<int64_t>{0, 2, 1, 3}) ok = false, why = generic;
+          else {
+            am.nodes.push_back(consumers_of[pv->outputs[0]][0]);
+            const NodeDef *r = sole_reader(t->outputs[0]);
+            if (!r || r->op != "Reshape" || r->inputs.size() != 2 || r->inputs[0] != t->outputs[0]) ok = false, why = generic;
+            else anchor = consumers_of[t->outputs[0]][0];
+          }
+        }
+      }
+      ok = ok && match_head(qk.inputs[0], am.side[0], false) && match_head(qk.inputs[1], am.side[1], true);
+      // (nothing else serves a product of two activations, so the load fails here, naming this node, rather than at whichever
+      // Transpose / Split of the unrecognised pattern the walk would meet first)
+      if (!ok && (why.empty() || why == generic)) {
+        // the two export forms named as not supported yet, wherever their Transpose sits behind the operands of Q K^T
+        for (const std::string &operand : qk.inputs) {
+          std::string v = operand;
+          for (int hop = 0; hop < 12; hop++) {
+            const NodeDef *p = producer(v);
+            if (!p || p->inputs.empty()) break;
+            if (p->op == "Transpose") {
+              const std::vector<int64_t> perm = perm_of(*p);
+              if (perm == std::vector<int64_t>{2, 0, 3, 1, 4})
+                why = "the packed head split [N,T,3,h,dh] -> Transpose(2,0,3,1,4) is not supported yet; split Q, K and V on the last axis first";
+              else if (perm.size() == 3 && why.find("packed") == std::string::npos)
+                why = "PyTorch nn.MultiheadAttention's time-major export (heads folded into the row axis, [T, N*h, dh]) is not supported yet; "
+                      "export batch-first projections with the head split Reshape [N,T,h,dh] -> Transpose(0,2,1,3)";
+            }
+            v = p->inputs[0];
+          }
+        }
+      }
+      if (!ok) unsupported(qk, "unsupported operator form: " + (why.empty() ? generic : why));
+      for (size_t i : am.nodes) absorbed[i] = 1;
+      attn_at[anchor] = std::move(am);
+    }
+    // a Split / Slice stays absorbed only when patterns read all of it
+    for (auto &kv : attn_at)
+      for (const AttnSide &sd : kv.second.side) {
+        if (!sd.cut) continue;
+        for (const auto &o : sd.cut->outputs) {
+          auto it = consumers_of.find(o);
+          bool all = !graph_outs.count(o);
+          if (it != consumers_of.end())
+            for (size_t c : it->second) all = all && absorbed[c];
+          if (!all) absorbed[size_t(sd.cut - m.nodes.data())] = 0;
+        }
+      }
+  }
+
+  const Val *find_value(const std::string &name) {
+    auto it = vals.find(name);
+    if (it != vals.end()) return &it->second;
+    auto ci = m.initializers.find(name);
+    if (ci != m.initializers.end()) return &(vals[name] = const_val(ci->second));
+    return nullptr;
+  }
+
+  void lower_attention(const AttnMatch &am, const NodeDef &anchor) {
+    const NodeDef &qk = *am.qk;
+    auto bad = [&](const std::string &why) { unsupported(qk, "unsupported operator form: " + why); };
+    static const char *names[3] = {"Q", "K", "V"};
+    struct View {
+      int buf;
+      int64_t N, T, E, ld, off;
+    } vw[3];
+    int64_t heads = 0, dh = 0;
+    for (int i = 0; i < 3; i++) {
+      const AttnSide &sd = am.side[i];
+      const Val *src = find_value(sd.src);
+      if (!src) bad(std::string(names[i]) + " reads '" + sd.src + "', which no earlier node produces");
+      if (src->pv) materialize(sd.src, &qk), src = find_value(sd.src);
+      if (src->is_const || src->ra != 0 || src->shape.size() != 3 || src->padded())
+        bad(std::string(names[i]) + " must be a rows-first [N, T, E] activation, got " + shape_str(src->shape) + (src->ra ? " (time-major)" : ""));
+      View &v = vw[i];
+      v = {src->buf, src->shape[0], src->shape[1], src->shape[2], src->shape[2], 0};
+      if (sd.cut && !absorbed[size_t(sd.cut - m.nodes.data())]) bad("the " + sd.cut->op + " that feeds " + names[i] + " also feeds nodes outside the attention pattern");
+      if (sd.cut && sd.cut->op == "Split") {
+        const NodeDef &c = *sd.cut;
+        std::vector<int64_t> sizes;
+        if (has_input(c, 1)) sizes = const_ints(c, 1, "split");
+        else if (auto *p = c.attr_ints("split")) sizes = *p;
+        const int64_t nout = int64_t(c.outputs.size());
+        if (sizes.empty()) {
+          const int64_t parts = c.attr_i("num_outputs", nout), each = (v.ld + parts - 1) / parts;
+          for (int64_t k = 0; k < parts; k++) sizes.push_back(std::min(each, v.ld - k * each));
+        }
+        if (int64_t(sizes.size()) != nout || std::accumulate(sizes.begin(), sizes.end(), int64_t(0)) != v.ld) unsupported(c, "split sizes do not cover the axis");
+        for (int64_t s : sizes)
+          if (s <= 0) unsupported(c, "empty split piece");
+        v.off = std::accumulate(sizes.begin(), sizes.begin() + int64_t(sd.cut_out), int64_t(0));
+        v.E = sizes[sd.cut_out];
+      } else if (sd.cut) {
+        const NodeDef &c = *sd.cut;
+        const std::vector<int64_t> st = const_ints(c, 1, "starts"), en = const_ints(c, 2, "ends");
+        if (st.size() != 1 || en.size() != 1 || (has_input(c, 4) && const_ints(c, 4, "steps") != std::vector<int64_t>{1})) unsupported(c, "one axis, step 1");
+        int64_t b = st[0] < 0 ? st[0] + v.ld : st[0], e = en[0] < 0 ? en[0] + v.ld : en[0];
+        b = std::clamp<int64_t>(b, 0, v.ld);
+        e = std::clamp<int64_t>(e, b, v.ld);
+        if (e == b) unsupported(c, "empty slice");
+        v.off = b;
+        v.E = e - b;
+      }
+      // the head split [N, T, h, dh]
+      const Val *sh = find_value(sd.shape);
+      if (!sh || !sh->is_const || sh->c->dtype != onnx::kInt64) bad("the head split of " + std::string(names[i]) + " needs a constant target shape");
+      std::vector<int64_t> tgt = sh->c->i64;
+      if (tgt.size() != 4) bad("the head split of " + std::string(names[i]) + " must reshape to [N, T, h, dh], got a target of " + std::to_string(tgt.size()) + " entries");
+      if (tgt[1] == 0) tgt[1] = v.T;
+      if (tgt[2] == 0) tgt[2] = v.E;
+      int neg = -1;
+      for (int k = 1; k < 4; k++) {
+        if (tgt[size_t(k)] == -1 && neg < 0) neg = k;
+        else if (tgt[size_t(k)] <= 0) bad("the head split of " + std::string(names[i]) + " has the extent " + std::to_string(tgt[size_t(k)]) + " in " + shape_str(sh->c->i64));
+      }
+      if (!(tgt[0] == 0 || tgt[0] == -1 || (tgt[0] == v.N && v.N > 0)) || (tgt[0] == -1 && neg >= 0))
+        bad("the head split target " + shape_str(sh->c->i64) + " does not keep the row axis");
+      int64_t h = tgt[2], d = tgt[3], t = tgt[1];
+      if (neg == 1) t = v.T;
+      if (t != v.T) bad("the head split " + shape_str(sh->c->i64) + " of " + names[i] + " " + shape_str(src->shape) + " does not keep the T steps (heads folded over time are not supported)");
+      if (neg == 2 && v.E % d == 0) h = v.E / d;
+      if (neg == 3 && v.E % h == 0) d = v.E / h;
+      if (h <= 0 || d <= 0 || v.E / h != d || v.E % h != 0)
+        bad("E = " + std::to_string(v.E) + " is not divisible by h = " + std::to_string(tgt[2] > 0 ? tgt[2] : h) + " (head split " + shape_str(sh->c->i64) + ")");
+      if (i == 0) heads = h, dh = d;
+      else if (h != heads || d != dh) bad(std::string(names[i]) + " is split into " + std::to_string(h) + " heads of " + std::to_string(d) + ", Q into " + std::to_string(heads) + " of " + std::to_string(dh));
+    }
+    if (vw[1].T != vw[0].T || vw[2].T != vw[0].T)
+      bad("Q, K and V have different window lengths T (" + std::to_string(vw[0].T) + ", " + std::to_string(vw[1].T) + ", " + std::to_string(vw[2].T) +
+          "): cross-attention is not supported");
+    const int64_t N = vw[0].N, T = vw[0].T, E = vw[0].E;
+    if (T < 1 || T > kAttnMaxT) bad("T = " + std::to_string(T) + " is beyond the attention kernel's cap of " + std::to_string(kAttnMaxT) + " steps");
+    if (dh > kAttnMaxDh) bad("dh = " + std::to_string(dh) + " is beyond the attention kernel's cap of " + std::to_string(kAttnMaxDh) + " columns per head");
+    if (heads > kAttnMaxHeads) bad("h = " + std::to_string(heads) + " is beyond the attention kernel's cap of " + std::to_string(kAttnMaxHeads) + " heads");
+    for (const View &v : vw)
+      if (v.ld * T > kMaxPerRow) bad("window too large");
+    // the scale: every constant scalar Mul / Div on Q, K^T and the scores, folded into one factor applied to the f32 scores
+    double scale = 1.0;
+    for (const AttnScale &sc : am.scales) {
+      const Val *c = find_value(sc.cst);
+      if (!c || !c->is_const || c->c->dtype != onnx::kFloat || c->c->f32.size() != 1 || !(c->c->f32[0] > 0.f) || !std::isfinite(c->c->f32[0]))
+        bad("the scale '" + sc.cst + "' must be one positive finite f32 constant");
+      scale = sc.op == '*' ? scale * double(c->c->f32[0]) : scale / double(c->c->f32[0]);
+    }
+    if (!(float(scale) > 0.f) || !std::isfinite(float(scale))) bad("the folded scale is not a positive finite f32 number");
+    Step s;
+    s.kind = StepKind::Attention;
+    if (!am.mask.empty()) {
+      const Val *c = find_value(am.mask);
+      if (!c || !c->is_const || c->c->dtype != onnx::kFloat) bad("the attention mask '" + am.mask + "' must be an f32 constant");
+      std::vector<int64_t> d = c->shape;
+      while (d.size() > 2 && d[0] == 1) d.erase(d.begin());
+      while (d.size() < 2) d.insert(d.begin(), 1);
+      if (d.size() != 2 || (d[0] != 1 && d[0] != T) || (d[1] != 1 && d[1] != T) || int64_t(c->c->f32.size()) != d[0] * d[1])
+        bad("the attention mask " + shape_str(c->shape) + " does not broadcast to [T, T] = [" + std::to_string(T) + "," + std::to_string(T) +
+            "] (a mask that depends on the row or the head is not supported)");
+      s.cst.resize(size_t(T * T));
+      for (int64_t q = 0; q < T; q++) {
+        bool any = false;
+        for (int64_t k = 0; k < T; k++) {
+          const float mv = c->c->f32[size_t((d[0] == 1 ? 0 : q) * d[1] + (d[1] == 1 ? 0 : k))];
+          if (std::isnan(mv) || mv == INFINITY) bad("the attention mask holds NaN or +inf");
+          any = any || mv != -INFINITY;
+          s.cst[size_t(q * T + k)] = mv;
+        }
+        if (!any) bad("row " + std::to_string(q) + " of the attention mask is -inf everywhere (a fully masked query has no softmax)");
+      }
+    }
+    {  // the merge Reshape must give [N, T, E]
+      const std::vector<int64_t> tgt = const_ints(anchor, 1, "shape");
+      bool okm = tgt.size() == 3 && (tgt[0] == 0 || tgt[0] == -1 || (tgt[0] == N && N > 0)) && (tgt[1] == 0 || tgt[1] == T || tgt[1] == -1) &&
+                 (tgt[2] == E || tgt[2] == -1) && !(tgt[0] == -1 && (tgt[1] == -1 || tgt[2] == -1)) && !(tgt[1] == -1 && tgt[2] == -1);
+      if (!okm) bad("the merge Reshape '" + node_label(anchor) + "' must give [N, T, E] = [N," + std::to_string(T) + "," + std::to_string(E) + "], got " + shape_str(tgt));
+    }
+    s.attn_T = T;
+    s.attn_heads = heads;
+    s.attn_dh = dh;
+    s.attn_scale = float(scale);
+    // Three window Dense projections of ONE value, each read by this pattern alone: merged into one Dense of width 3E, so the value is
+    // read once and the kernel reads one packed [rows, T, 3E] buffer
+    const std::set<size_t> mine(am.nodes.begin(), am.nodes.end());  // (another pattern over the same q, k, v must still find its buffers)
+    auto private_proj = [&](const View &v) -> int {
+      auto pit = producer.find(v.buf);
+      if (v.buf <= 0 || pit == producer.end() || v.off != 0 || v.ld != E) return -1;
+      const Step &p = plan.steps[size_t(pit->second)];
+      if (p.kind != StepKind::Dense || p.rep != T || p.act != Act::None || p.out != v.buf || p.M != E) return -1;
+      for (const auto &nm : buf_names[v.buf]) {
+        if (nm == m.outputs[out_index].name) return -1;
+        auto it = consumers_of.find(nm);
+        if (it == consumers_of.end()) continue;
+        for (size_t c : it->second) {  // readers: THIS pattern's nodes, Shape, and nodes folded into the step (its bias Add)
+          const NodeDef &cn = m.nodes[c];
+          auto ov = cn.outputs.empty() ? vals.end() : vals.find(cn.outputs[0]);
+          const bool folded = ov != vals.end() && !ov->second.is_const && ov->second.buf == v.buf;
+          if (!mine.count(c) && cn.op != "Shape" && !folded) return -1;
+        }
+      }
+      return pit->second;
+    };
+    const int pq = private_proj(vw[0]), pk = private_proj(vw[1]), pv = private_proj(vw[2]);
+    if (pq >= 0 && pk >= 0 && pv >= 0 && pq != pk && pk != pv && pq != pv && plan.steps[size_t(pq)].in0 == plan.steps[size_t(pk)].in0 &&
+        plan.steps[size_t(pq)].in0 == plan.steps[size_t(pv)].in0 && plan.steps[size_t(pq)].K == plan.steps[size_t(pk)].K &&
+        plan.steps[size_t(pq)].K == plan.steps[size_t(pv)].K) {
+      const int idx[3] = {pq, pk, pv};
+      const int64_t K = plan.steps[size_t(pq)].K;
+      Step d = plan.steps[size_t(pq)];
+      d.M = 3 * E;
+      d.W.assign(size_t(K * 3 * E), 0.f);
+      bool any_bias = false;
+      for (int i : idx) any_bias = any_bias || !plan.steps[size_t(i)].bias.empty();
+      d.bias.assign(any_bias ? size_t(3 * E) : 0, 0.f);
+      d.origin.clear();
+      for (int j = 0; j < 3; j++) {
+        const Step &p = plan.steps[size_t(idx[j])];
+        for (int64_t k = 0; k < K; k++) std::copy_n(p.W.begin() + k * E, E, d.W.begin() + k * 3 * E + j * E);
+        if (!p.bias.empty()) std::copy(p.bias.begin(), p.bias.end(), d.bias.begin() + j * E);
+        d.origin += (j ? "|" : "") + p.origin;
+      }
+      const int first = std::min({pq, pk, pv});
+      d.out = vw[0].buf;
+      plan.steps[size_t(first)] = std::move(d);
+      for (int i : {std::max({pq, pk, pv}), pq + pk + pv - first - std::max({pq, pk, pv})}) plan.steps.erase(plan.steps.begin() + i);
+      producer.clear();
+      for (size_t i = 0; i < plan.steps.size(); i++) producer[plan.steps[i].out] = int(i);
+      plan.buf_per_row[size_t(vw[0].buf)] = T * 3 * E;
+      plan.buf_shape[size_t(vw[0].buf)] = {N, T * 3 * E};
+      for (int j = 1; j < 3; j++) {  // the K and V buffers have no writer and no reader any more: they take no scratch
+        plan.buf_per_row[size_t(vw[j].buf)] = 0;
+        plan.buf_shape[size_t(vw[j].buf)] = {N, 0};
+      }
+      for (int j = 0; j < 3; j++) vw[j].buf = vw[0].buf, vw[j].ld = 3 * E, vw[j].off = j * E;
+    }
+    s.in0 = vw[0].buf;
+    s.in1 = vw[1].buf;
+    s.in2 = vw[2].buf;
+    for (int j = 0; j < 3; j++) s.attn_ld[j] = vw[j].ld, s.attn_off[j] = vw[j].off;
+    s.origin = node_label(qk) + "+...+" + node_label(anchor);
+    emit_window(std::move(s), anchor, {N, T, E});
+  }
+
   // Sum of any number of equal-shaped activations: a chain of residual adds
   void sum(const NodeDef &n) {
     if (n.inputs.empty()) unsupported(n, "no inputs");
@@ -1428,6 +2039,7 @@ struct Lowerer {
     else if (op == "Cast") cast(n);
     else if (op == "Concat") concat(n);
     else if (op == "ReduceMean") reduce_mean(n);
+    else if (op == "LayerNormalization") layer_norm(n);
     else if (op == "ArgMax") argmax(n);
     else if (op == "Identity" || op == "Dropout" || op == "Flatten" || op == "Reshape" || op == "Squeeze" || op == "Unsqueeze") reshape_like(n);
     else if (op == "Softmax") softmax(n, false);
@@ -2237,6 +2849,7 @@ struct Lowerer {
     uses[m.outputs[out_index].name]++;
     // preprocessing regions: their graph inputs start as identity columns over the input buffer (integer inputs truncated)
     const std::set<std::string> region_inputs = find_regions(live);
+    find_attention(live);
     {
       int64_t off = 0;
       for (const auto &v : m.inputs) {
@@ -2270,7 +2883,13 @@ struct Lowerer {
       if (region[ni] || n.domain == "ai.onnx.ml") check_row_axis(n, false);
       if (region[ni]) prep_node(n);
       else if (n.domain == "ai.onnx.ml") ml_node(n);
-      else if (!n.domain.empty() && n.domain != "ai.onnx") unsupported(n, "operator domain '" + n.domain + "'");
+      else if (!n.domain.empty() && n.domain != "ai.onnx") {
+        if (n.op == "Attention" || n.op == "MultiHeadAttention" || n.op == "SkipLayerNormalization")
+          unsupported(n, "unsupported operator form: the contrib fused operator of domain '" + n.domain +
+                             "' is not supported; export the standard-domain graph (MatMul / Softmax / LayerNormalization)");
+        unsupported(n, "operator domain '" + n.domain + "'");
+      } else if (attn_at.count(ni)) lower_attention(attn_at.at(ni), n);
+      else if (absorbed[ni]) continue;
       else lower_node(n);
     }
     // one output is served: the first (engine.rs:146-149) unless the load call selected another
@@ -2314,7 +2933,8 @@ Plan lower_model(const onnx::Model &m, const std::string &output_select) { retur
 double Plan::flops_per_row() const {
   double f = 0;
   for (const auto &s : steps) {
-    if (s.kind == StepKind::Dense) f += 2.0 * double(s.K) * double(s.M);
+    if (s.kind == StepKind::Dense) f += 2.0 * double(s.rep) * double(s.K) * double(s.M);
+    else if (s.kind == StepKind::Attention) f += 4.0 * double(s.attn_T) * double(s.attn_T) * double(s.attn_heads * s.attn_dh);
     else if (s.kind == StepKind::Conv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
     else if (s.kind == StepKind::Recurrent) f += 2.0 * double(s.rnn->T * s.rnn->D * s.rnn->G * s.rnn->H) * double(s.rnn->F + s.rnn->H);
@@ -2323,7 +2943,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -2334,7 +2954,14 @@ std::string Plan::describe_json() const {
     if (i) o << ",";
     o << "{\"kind\":\"" << kinds[int(s.kind)] << "\",\"in\":" << s.in0 << ",\"out\":" << s.out;
     if (s.in1 >= 0) o << ",\"in1\":" << s.in1;
+    if (s.in2 >= 0) o << ",\"in2\":" << s.in2;
     if (s.kind == StepKind::Dense) o << ",\"K\":" << s.K << ",\"M\":" << s.M << ",\"bias\":" << (s.bias.empty() ? "false" : "true");
+    if (s.kind == StepKind::Dense && s.rep > 1) o << ",\"T\":" << s.rep;
+    if (s.kind == StepKind::LayerNorm) o << ",\"E\":" << s.K << ",\"T\":" << s.rep << ",\"epsilon\":" << double(s.ln_eps) << ",\"bias\":" << (s.shift.empty() ? "false" : "true");
+    if (s.kind == StepKind::MeanTime) o << ",\"E\":" << s.K << ",\"T\":" << s.rep;
+    if (s.kind == StepKind::Attention)
+      o << ",\"T\":" << s.attn_T << ",\"heads\":" << s.attn_heads << ",\"dh\":" << s.attn_dh << ",\"scale\":" << double(s.attn_scale) << ",\"mask\":" << (s.cst.empty() ? "false" : "true")
+        << ",\"packed_qkv\":" << (s.in0 == s.in1 && s.in1 == s.in2 ? "true" : "false");
     if (s.kind == StepKind::Conv2d) o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"k\":[" << s.kh << "," << s.kw << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
     if (s.kind == StepKind::TreeEnsemble || s.kind == StepKind::TreeReduce) {
       static const char *modes[] = {"scores", "label", "binary_scores", "binary_label"};

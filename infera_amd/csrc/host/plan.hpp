@@ -54,6 +54,9 @@ enum class StepKind : int {
   SvmReduce = 18,     // in0 = those partials -> regressor value / one-class sign, pairwise decisions, label or probabilities (SvmOut)
   Prep = 19,          // ai.onnx.ml preprocessing region: out[r, j] = column program j over in0[r, :] (host/prep.hpp, prep.hip)
   Recurrent = 20,     // ONNX LSTM / GRU / RNN over in0 [rows, T, F]: out = Y [rows, T, D, H] or the last state [rows, D, H] (RnnOut; RnnPack, rnn.hip)
+  LayerNorm = 21,     // y = (x - mean) / sqrt(var + eps) * scale[K] + shift[K] over each of the `rep` vectors of K elements of a row (layernorm.hip)
+  Attention = 22,     // self-attention over the T steps of a row: out [rows, T, heads * dh] = softmax(attn_scale . Q K^T + mask) V per head (attention.hip)
+  MeanTime = 23,      // out[r, e] = mean over t of in0[r, t, e]   (ReduceMean over the time axis of [rows, T = rep, K])
 };
 
 // TreeEnsemble / TreeReduce output modes (Step::out_mode)
@@ -72,6 +75,9 @@ struct Step {
   float act_a = 0.f, act_b = 0.f;    // LeakyRelu alpha / Clip lo,hi
   // Dense
   int64_t K = 0, M = 0;
+  // Dense over a window: in0 is [rows, rep, K] and the layer runs on each of its rows * rep vectors (the buffer IS that matrix).
+  // LayerNorm / MeanTime: vectors (time steps) per row
+  int64_t rep = 1;
   std::vector<float> W;     // [K, M] row-major (Gemm transB / alpha already folded)
   std::vector<float> bias;  // [M] or empty (Gemm beta folded)
   // AffineChannel: scale/shift per channel, S = elements per channel
@@ -101,6 +107,11 @@ struct Step {
   std::shared_ptr<const PrepPack> prep;
   std::shared_ptr<const RnnPack> rnn;
   int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut
+  // Attention: Q = in0, K = in1, V = in2 (the same buffer three times when the projections are merged), each [rows, T, ld] with the head
+  // block of head g at columns off + g * dh of a step; mask (cst): [T, T] added to the scaled scores, -inf = no weight, empty = none
+  int in2 = -1;
+  int64_t attn_T = 0, attn_heads = 0, attn_dh = 0, attn_ld[3] = {0, 0, 0}, attn_off[3] = {0, 0, 0};
+  float attn_scale = 1.f, ln_eps = 1e-5f;
   std::string origin;  // ONNX node names/ops this step came from (diagnostics)
 };
 

@@ -935,6 +935,331 @@ def recurrent_from_spec(spec: dict, T: int | None = None, form: str = "batch_fir
 
 
 # ------------------------------------------------------------------------------------------
+# Transformer encoders (window Dense, LayerNormalization, self-attention, mean over time)
+# ------------------------------------------------------------------------------------------
+
+def transformer_spec(T: int = 24, F: int = 8, E: int = 64, h: int = 4, ff: int = 256, layers: int = 2, norm_first: bool = False,
+                     act: str = "Relu", outputs: int = 1, causal: bool = False, final_norm: bool | None = None, eps: float = 1e-5,
+                     weight_scale: float = 1.0, seed: int = 21) -> dict:
+    """Seeded Transformer encoder: input projection F -> E, positional constant [T, E], `layers` encoder layers (self-attention with h heads,
+    feed-forward E -> ff -> E, LayerNorm and residuals; norm_first: pre-norm), optional final LayerNorm (default: with norm_first), head
+    E -> outputs.  All matrices are [in, out]; U(+-1/sqrt(fan_in)) like PyTorch's Linear, scaled by weight_scale."""
+    rng = np.random.default_rng(seed)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)  # noqa: E731
+
+    def lin(i, o):
+        k = weight_scale / np.sqrt(i)
+        return f32(rng.uniform(-k, k, (i, o))), f32(rng.uniform(-k, k, (o,)))
+
+    def ln():
+        return f32(1.0 + 0.1 * rng.standard_normal(E)), f32(0.1 * rng.standard_normal(E))
+
+    ls = []
+    for _ in range(layers):
+        L = {}
+        for nm, (i, o) in (("q", (E, E)), ("k", (E, E)), ("v", (E, E)), ("o", (E, E)), ("1", (E, ff)), ("2", (ff, E))):
+            L["W" + nm], L["b" + nm] = lin(i, o)
+        L["g1"], L["be1"] = ln()
+        L["g2"], L["be2"] = ln()
+        ls.append(L)
+    Win, bin_ = lin(F, E)
+    Wh, bh = lin(E, outputs)
+    if final_norm is None:
+        final_norm = norm_first
+    return {"T": T, "F": F, "E": E, "h": h, "ff": ff, "norm_first": norm_first, "act": act, "eps": eps, "causal": causal, "layers": ls,
+            "Win": Win, "bin": bin_, "pos": f32(0.5 * rng.standard_normal((T, E))), "final_norm": ln() if final_norm else None,
+            "head_W": Wh, "head_b": bh}
+
+
+def from_torch_encoder(encoder, T: int, head=None, causal: bool = False) -> dict:
+    """The transformer_spec() dict of a torch.nn.TransformerEncoder(batch_first=True): in_proj_weight [3E, E] is split into Wq, Wk, Wv and
+    every Linear transposed to [in, out].  No input projection and no positional constant (F = E); head: a torch.nn.Linear or None."""
+    sd = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in encoder.state_dict().items()}
+    l0 = encoder.layers[0]
+    E, h, ff = l0.self_attn.embed_dim, l0.self_attn.num_heads, l0.linear1.out_features
+    act = "Gelu" if "gelu" in getattr(l0.activation, "__name__", type(l0.activation).__name__).lower() else "Relu"
+    ls = []
+    for i in range(len(encoder.layers)):
+        p = f"layers.{i}."
+        W, b = sd[p + "self_attn.in_proj_weight"], sd[p + "self_attn.in_proj_bias"]
+        L = {"Wq": W[:E].T.copy(), "Wk": W[E:2 * E].T.copy(), "Wv": W[2 * E:].T.copy(), "bq": b[:E].copy(), "bk": b[E:2 * E].copy(), "bv": b[2 * E:].copy(),
+             "Wo": sd[p + "self_attn.out_proj.weight"].T.copy(), "bo": sd[p + "self_attn.out_proj.bias"],
+             "W1": sd[p + "linear1.weight"].T.copy(), "b1": sd[p + "linear1.bias"], "W2": sd[p + "linear2.weight"].T.copy(), "b2": sd[p + "linear2.bias"],
+             "g1": sd[p + "norm1.weight"], "be1": sd[p + "norm1.bias"], "g2": sd[p + "norm2.weight"], "be2": sd[p + "norm2.bias"]}
+        ls.append(L)
+    fin = (sd["norm.weight"], sd["norm.bias"]) if "norm.weight" in sd else None
+    spec = {"T": T, "F": E, "E": E, "h": h, "ff": ff, "norm_first": bool(l0.norm_first), "act": act, "eps": float(l0.norm1.eps), "causal": causal,
+            "layers": ls, "Win": None, "bin": None, "pos": None, "final_norm": fin, "head_W": None, "head_b": None}
+    if head is not None:
+        spec["head_W"] = head.weight.detach().cpu().numpy().astype(np.float32).T.copy()
+        spec["head_b"] = head.bias.detach().cpu().numpy().astype(np.float32)
+    return spec
+
+
+def attention_nodes(nodes: list, inits: list, p: str, q: str, k: str, v: str, x_for_shape: str, T: int, E: int, h: int, scale: str = "scores_div",
+                    k_transpose: str = "direct", mask=None, shape: str = "const", scale_value: float | None = None, softmax_axis: int = -1) -> str:
+    """Appends the batch-first self-attention sub-graph over q, k, v [N, T, E] (names) and returns the name of its [N, T, E] result.
+    scale: "scores_div" (Div by sqrt(dh)), "scores_mul", "q" (Mul of Q) or "sqrt_both" (Q and K^T by sqrt(scale) each, what
+    scaled_dot_product_attention exports); k_transpose: "direct" (0,2,3,1) or "two_step" ((0,2,1,3) then (0,1,3,2)); mask: None or an f32
+    array added to the scores; shape: "const" targets or the exporter's Shape -> Gather -> Unsqueeze -> Concat sub-graph."""
+    dh = E // h
+    sv = (1.0 / math.sqrt(dh)) if scale_value is None else scale_value
+    i64 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.int64)))  # noqa: E731
+    f32 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.float32)))  # noqa: E731
+    if shape == "const":
+        i64(p + "split", [0, T, h, dh])
+        i64(p + "merge", [0, T, E])
+        split_shape = merge_shape = None
+    else:
+        i64(p + "i0", 0); i64(p + "ax0", [0]); i64(p + "thd", [T, h, dh]); i64(p + "te", [T, E])  # noqa: E702
+        nodes += [node("Shape", [x_for_shape], [p + "shp"]), node("Gather", [p + "shp", p + "i0"], [p + "n"], [attr_i("axis", 0)]),
+                  node("Unsqueeze", [p + "n", p + "ax0"], [p + "n1"]),
+                  node("Concat", [p + "n1", p + "thd"], [p + "split"], [attr_i("axis", 0)]),
+                  node("Concat", [p + "n1", p + "te"], [p + "merge"], [attr_i("axis", 0)])]
+    heads = {}
+    for nm, src in (("q", q), ("k", k), ("v", v)):
+        nodes.append(node("Reshape", [src, p + "split"], [p + nm + "4"], name=p + "split_" + nm))
+        if nm == "k" and k_transpose == "direct":
+            nodes.append(node("Transpose", [p + "k4"], [p + "kh"], [attr_ints("perm", [0, 2, 3, 1])], name=p + "tr_k"))
+        elif nm == "k":
+            nodes += [node("Transpose", [p + "k4"], [p + "kh0"], [attr_ints("perm", [0, 2, 1, 3])], name=p + "tr_k0"),
+                      node("Transpose", [p + "kh0"], [p + "kh"], [attr_ints("perm", [0, 1, 3, 2])], name=p + "tr_k")]
+        else:
+            nodes.append(node("Transpose", [p + nm + "4"], [p + nm + "h"], [attr_ints("perm", [0, 2, 1, 3])], name=p + "tr_" + nm))
+        heads[nm] = p + nm + "h"
+    if scale == "q":
+        f32(p + "sc", sv)
+        nodes.append(node("Mul", [heads["q"], p + "sc"], [p + "qs"], name=p + "scale_q"))
+        heads["q"] = p + "qs"
+    elif scale == "sqrt_both":
+        f32(p + "sc", math.sqrt(sv))
+        nodes += [node("Mul", [heads["q"], p + "sc"], [p + "qs"], name=p + "scale_q"), node("Mul", [heads["k"], p + "sc"], [p + "ks"], name=p + "scale_k")]
+        heads["q"], heads["k"] = p + "qs", p + "ks"
+    nodes.append(node("MatMul", [heads["q"], heads["k"]], [p + "s0"], name=p + "qk"))
+    cur = p + "s0"
+    if scale == "scores_div":
+        f32(p + "sc", 1.0 / sv)
+        nodes.append(node("Div", [cur, p + "sc"], [p + "s1"], name=p + "scale"))
+        cur = p + "s1"
+    elif scale == "scores_mul":
+        f32(p + "sc", sv)
+        nodes.append(node("Mul", [cur, p + "sc"], [p + "s1"], name=p + "scale"))
+        cur = p + "s1"
+    if mask is not None:
+        f32(p + "mask", mask)
+        nodes.append(node("Add", [cur, p + "mask"], [p + "s2"], name=p + "mask_add"))
+        cur = p + "s2"
+    nodes += [node("Softmax", [cur], [p + "p"], [attr_i("axis", softmax_axis)], name=p + "softmax"),
+              node("MatMul", [p + "p", heads["v"]], [p + "o4"], name=p + "pv"),
+              node("Transpose", [p + "o4"], [p + "ot"], [attr_ints("perm", [0, 2, 1, 3])], name=p + "tr_o"),
+              node("Reshape", [p + "ot", p + "merge"], [p + "o"], name=p + "merge_heads")]
+    return p + "o"
+
+
+def causal_mask(T: int, rank: int = 2) -> np.ndarray:
+    mk = np.triu(np.full((T, T), -np.inf, dtype=np.float32), 1)
+    return mk.reshape((1,) * (rank - 2) + (T, T))
+
+
+def attention_only(T: int, E: int, h: int, form: str = "packed", **kw) -> bytes:
+    """Self-attention alone over a flat input: form "packed": X [N, T*3E] -> Reshape [N, T, 3E] -> Split on the last axis -> q, k, v;
+    "three": inputs Q, K, V [N, T*E] each (the call's columns in that order), each reshaped to [N, T, E].  Output [N, T, E]."""
+    nodes, inits = [], []
+    if form == "packed":
+        inits += [tensor("x_shape", np.asarray([-1, T, 3 * E], dtype=np.int64)), tensor("sp", np.asarray([E, E, E], dtype=np.int64))]
+        nodes += [node("Reshape", ["X", "x_shape"], ["X3"]), node("Split", ["X3", "sp"], ["q", "k", "v"], [attr_i("axis", 2)], name="split_qkv")]
+        ins = [value_info("X", ["N", T * 3 * E])]
+        xs = "X3"
+    else:
+        inits.append(tensor("x_shape", np.asarray([-1, T, E], dtype=np.int64)))
+        for nm in "qkv":
+            nodes.append(node("Reshape", [nm.upper(), "x_shape"], [nm]))
+        ins = [value_info(nm, ["N", T * E]) for nm in "QKV"]
+        xs = "q"
+    out = attention_nodes(nodes, inits, "a_", "q", "k", "v", xs, T, E, h, **kw)
+    return model("attention", nodes, inits, ins, [value_info(out, ["N", T, E])], opset=20)
+
+
+def attention_reference(q, k, v, h: int, scale: float | None = None, mask=None) -> np.ndarray:
+    """float64 numpy restatement of softmax(scale . Q K^T + mask) V per head over q, k, v [N, T, E] -> [N, T, E]."""
+    q, k, v = (np.asarray(a, dtype=np.float64) for a in (q, k, v))
+    N, T, E = q.shape
+    dh = E // h
+    sp = lambda a: a.reshape(N, T, h, dh).transpose(0, 2, 1, 3)  # noqa: E731
+    s = sp(q) @ sp(k).transpose(0, 1, 3, 2) * ((1.0 / math.sqrt(dh)) if scale is None else scale)
+    if mask is not None:
+        s = s + np.asarray(mask, dtype=np.float64).reshape(T, T)
+    s = s - s.max(axis=-1, keepdims=True)
+    pr = np.exp(s)
+    pr /= pr.sum(axis=-1, keepdims=True)
+    return (pr @ sp(v)).transpose(0, 2, 1, 3).reshape(N, T, E)
+
+
+def layernorm_reference(x, g, b, eps: float) -> np.ndarray:
+    x = np.asarray(x, dtype=np.float64)
+    d = x - x.mean(axis=-1, keepdims=True)
+    y = d / np.sqrt((d * d).mean(axis=-1, keepdims=True) + eps) * np.asarray(g, dtype=np.float64)
+    return y if b is None else y + np.asarray(b, dtype=np.float64)
+
+
+def transformer_reference(spec: dict, x, heads: Sequence[str] = ("mean",)) -> dict:
+    """float64 numpy restatement of transformer_from_spec(spec): x [N, T*F] or [N, T, F] -> {output name: array}."""
+    from math import erf
+    T, F, E, h = spec["T"], spec["F"], spec["E"], spec["h"]
+    f64 = lambda a: np.asarray(a, dtype=np.float64)  # noqa: E731
+    x = f64(x).reshape(-1, T, F)
+    if spec["Win"] is not None:
+        x = x @ f64(spec["Win"]) + f64(spec["bin"])
+    if spec["pos"] is not None:
+        x = x + f64(spec["pos"]).reshape(1, T, E)
+    mask = causal_mask(T) if spec.get("causal") else None
+    act = (lambda a: np.maximum(a, 0.0)) if spec["act"] == "Relu" else (lambda a: 0.5 * a * (1.0 + np.vectorize(erf)(a / math.sqrt(2.0))))
+    ln = lambda a, g, b: layernorm_reference(a, g, b, spec["eps"])  # noqa: E731
+    for L in spec["layers"]:
+        a_in = ln(x, L["g1"], L["be1"]) if spec["norm_first"] else x
+        a = attention_reference(a_in @ f64(L["Wq"]) + f64(L["bq"]), a_in @ f64(L["Wk"]) + f64(L["bk"]), a_in @ f64(L["Wv"]) + f64(L["bv"]), h, mask=mask)
+        x = x + (a @ f64(L["Wo"]) + f64(L["bo"]))
+        if not spec["norm_first"]:
+            x = ln(x, L["g1"], L["be1"])
+        f_in = ln(x, L["g2"], L["be2"]) if spec["norm_first"] else x
+        x = x + (act(f_in @ f64(L["W1"]) + f64(L["b1"])) @ f64(L["W2"]) + f64(L["b2"]))
+        if not spec["norm_first"]:
+            x = ln(x, L["g2"], L["be2"])
+    if spec["final_norm"] is not None:
+        x = ln(x, spec["final_norm"][0], spec["final_norm"][1])
+    out = {}
+    for hd in heads:
+        v = {"mean": x.mean(axis=1), "first": x[:, 0], "last": x[:, -1], "seq": x}[hd]
+        if spec["head_W"] is not None:
+            v = v @ f64(spec["head_W"]) + f64(spec["head_b"])
+        out["pooled" if hd == "mean" else hd] = v
+    return out
+
+
+def layernorm_nodes(nodes: list, inits: list, x: str, g, b, out: str, name: str, eps: float, form: str = "op") -> str:
+    """Appends LayerNorm over the last axis of x: form "op" (LayerNormalization, opset 17) or the decomposed spelling older exporters write,
+    ReduceMean(-1) -> Sub -> Pow(2) ("decomposed") or Mul(d, d) ("decomposed_mul") -> ReduceMean(-1) -> Add(eps) -> Sqrt -> Div -> Mul -> Add."""
+    f32 = lambda nm, v: inits.append(tensor(nm, np.asarray(v, dtype=np.float32)))  # noqa: E731
+    f32(name + "_g", g)
+    if b is not None:
+        f32(name + "_b", b)
+    if form == "op":
+        nodes.append(node("LayerNormalization", [x, name + "_g"] + ([name + "_b"] if b is not None else []), [out], [attr_i("axis", -1), attr_f("epsilon", eps)], name=name))
+        return out
+    inits.append(tensor(name + "_ax", np.asarray([-1], dtype=np.int64)))
+    f32(name + "_eps", eps)
+    p = name + "_"
+    nodes += [node("ReduceMean", [x, name + "_ax"], [p + "mu"], [attr_i("keepdims", 1)], name=p + "mean"), node("Sub", [x, p + "mu"], [p + "d"], name=p + "sub")]
+    if form == "decomposed":
+        f32(name + "_two", 2.0)
+        nodes.append(node("Pow", [p + "d", name + "_two"], [p + "sq"], name=p + "pow"))
+    else:
+        nodes.append(node("Mul", [p + "d", p + "d"], [p + "sq"], name=p + "square"))
+    nodes += [node("ReduceMean", [p + "sq", name + "_ax"], [p + "var"], [attr_i("keepdims", 1)], name=p + "var"),
+              node("Add", [p + "var", name + "_eps"], [p + "ve"], name=p + "eps"), node("Sqrt", [p + "ve"], [p + "sd"], name=p + "sqrt"),
+              node("Div", [p + "d", p + "sd"], [p + "nrm"], name=p + "div"), node("Mul", [p + "nrm", name + "_g"], [p + "sc"] if b is not None else [out], name=p + "gamma")]
+    if b is not None:
+        nodes.append(node("Add", [p + "sc", name + "_b"], [out], name=p + "beta"))
+    return out
+
+
+def transformer_from_spec(spec: dict, flat: bool = True, qkv: str = "separate", scale: str = "scores_div", k_transpose: str = "direct",
+                          mask_rank: int = 2, shape: str = "const", gelu: str = "op", heads: Sequence[str] = ("mean",), keepdims: int = 0,
+                          opset: int = 20, layernorm: str = "op", pos_rank: int = 3) -> bytes:
+    """The ONNX model of a transformer_spec() / from_torch_encoder() dict, input X [N, T, F] (flat: [N, T*F] -> Reshape).
+    qkv: "separate" (three MatMul + Add), "packed_split" / "packed_slice" (one [E, 3E] projection, then Split / three Slices on the last axis);
+    scale, k_transpose, shape: see attention_nodes; a causal spec adds the [T, T] mask (mask_rank 4: [1, 1, T, T]); gelu: "op" (opset 20) or
+    "decomposed" (Div(sqrt 2) -> Erf -> Add(1) -> Mul(x) -> Mul(0.5)).  heads: the graph outputs, any of "mean" (mean over time -> Linear,
+    output "pooled"), "first" / "last" (that step -> Linear), "seq" (the full sequence [N, T, E] -> per-step Linear); without a head matrix
+    in the spec the encoder output itself is served.  layernorm: see layernorm_nodes ("op" is the default); pos_rank: the positional constant as [1, T, E] or [T, E]."""
+    T, F, E, h, ff = spec["T"], spec["F"], spec["E"], spec["h"], spec["ff"]
+    nodes, inits = [], []
+    i64 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.int64)))  # noqa: E731
+    f32 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.float32)))  # noqa: E731
+
+    def linear(x, W, b, out, name):
+        f32(name + "_W", W)
+        f32(name + "_b", b)
+        nodes.append(node("MatMul", [x, name + "_W"], [out + "_mm"], name=name))
+        nodes.append(node("Add", [out + "_mm", name + "_b"], [out], name=name + "_bias"))
+        return out
+
+    def layer_norm(x, g, b, out, name):
+        return layernorm_nodes(nodes, inits, x, g, b, out, name, spec["eps"], layernorm)
+
+    x = "X"
+    if flat:
+        i64("flat_shape", [-1, T, F])
+        nodes.append(node("Reshape", [x, "flat_shape"], ["X3"]))
+        x = "X3"
+    if spec["Win"] is not None:
+        x = linear(x, spec["Win"], spec["bin"], "emb", "in_proj")
+    if spec["pos"] is not None:
+        f32("pos", np.asarray(spec["pos"]).reshape((1, T, E) if pos_rank == 3 else (T, E)))
+        nodes.append(node("Add", [x, "pos"], ["emb_pos"], name="pos_add"))
+        x = "emb_pos"
+    mask = causal_mask(T, mask_rank) if spec.get("causal") else None
+    for i, L in enumerate(spec["layers"]):
+        p = f"l{i}_"
+        a_in = layer_norm(x, L["g1"], L["be1"], p + "n1", p + "norm1") if spec["norm_first"] else x
+        if qkv == "separate":
+            q, k, v = (linear(a_in, L["W" + c], L["b" + c], p + c, p + c + "_proj") for c in "qkv")
+        else:
+            linear(a_in, np.concatenate([L["Wq"], L["Wk"], L["Wv"]], axis=1), np.concatenate([L["bq"], L["bk"], L["bv"]]), p + "qkv", p + "qkv_proj")
+            q, k, v = p + "q", p + "k", p + "v"
+            if qkv == "packed_split":
+                i64(p + "sp", [E, E, E])
+                nodes.append(node("Split", [p + "qkv", p + "sp"], [q, k, v], [attr_i("axis", -1)], name=p + "split_qkv"))
+            else:
+                i64(p + "ax2", [2])
+                for j, nm in enumerate((q, k, v)):
+                    i64(nm + "_b", [j * E]); i64(nm + "_e", [(j + 1) * E])  # noqa: E702
+                    nodes.append(node("Slice", [p + "qkv", nm + "_b", nm + "_e", p + "ax2"], [nm], name=nm + "_slice"))
+        a = attention_nodes(nodes, inits, p + "a_", q, k, v, a_in, T, E, h, scale=scale, k_transpose=k_transpose, mask=mask, shape=shape)
+        a = linear(a, L["Wo"], L["bo"], p + "ao", p + "out_proj")
+        nodes.append(node("Add", [x, a], [p + "r1"], name=p + "res1"))
+        x = p + "r1"
+        if not spec["norm_first"]:
+            x = layer_norm(x, L["g1"], L["be1"], p + "n1", p + "norm1")
+        f_in = layer_norm(x, L["g2"], L["be2"], p + "n2", p + "norm2") if spec["norm_first"] else x
+        hdn = linear(f_in, L["W1"], L["b1"], p + "f1", p + "ff1")
+        if spec["act"] == "Gelu" and gelu == "decomposed":
+            f32(p + "sqrt2", math.sqrt(2.0)); f32(p + "one", 1.0); f32(p + "half", 0.5)  # noqa: E702
+            nodes += [node("Div", [hdn, p + "sqrt2"], [p + "g0"]), node("Erf", [p + "g0"], [p + "g1"]), node("Add", [p + "g1", p + "one"], [p + "g2"]),
+                      node("Mul", [hdn, p + "g2"], [p + "g3"]), node("Mul", [p + "g3", p + "half"], [p + "fa"])]
+        else:
+            nodes.append(node(spec["act"], [hdn], [p + "fa"], name=p + "act"))
+        f = linear(p + "fa", L["W2"], L["b2"], p + "f2", p + "ff2")
+        nodes.append(node("Add", [x, f], [p + "r2"], name=p + "res2"))
+        x = p + "r2"
+        if not spec["norm_first"]:
+            x = layer_norm(x, L["g2"], L["be2"], p + "n2", p + "norm2")
+    if spec["final_norm"] is not None:
+        x = layer_norm(x, spec["final_norm"][0], spec["final_norm"][1], "enc", "final_norm")
+    M = None if spec["head_W"] is None else int(np.asarray(spec["head_W"]).shape[1])
+    outs = []
+    for hd in heads:
+        if hd == "mean":
+            i64("t_axis", [1])
+            nodes.append(node("ReduceMean", [x, "t_axis"], ["mean_t"], [attr_i("keepdims", keepdims)], name="mean_over_time"))
+            v, dims, name = "mean_t", (["N", 1, E] if keepdims else ["N", E]), "pooled"
+        elif hd in ("first", "last"):
+            i64(hd + "_i", 0 if hd == "first" else -1)
+            nodes.append(node("Gather", [x, hd + "_i"], [hd + "_t"], [attr_i("axis", 1)], name=hd + "_step"))
+            v, dims, name = hd + "_t", ["N", E], hd
+        else:
+            v, dims, name = x, ["N", T, E], "seq"
+        if M is not None:
+            linear(v, spec["head_W"], spec["head_b"], name, name + "_head")
+            dims = dims[:-1] + [M]
+        else:
+            nodes.append(node("Identity", [v], [name]))
+        outs.append(value_info(name, dims))
+    in_dims = ["N", T * F] if flat else ["N", T, F]
+    return model("transformer", nodes, inits, [value_info("X", in_dims)], outs, opset=opset)
+
+
+# ------------------------------------------------------------------------------------------
 # ai.onnx.ml preprocessing (Imputer, Scaler, OneHotEncoder, LabelEncoder, Binarizer, ArrayFeatureExtractor, Concat, ZipMap)
 # ------------------------------------------------------------------------------------------
 
