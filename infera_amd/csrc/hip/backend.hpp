@@ -108,6 +108,8 @@ class LoadedModel {
   std::vector<int> conv_fold;  // per ConvTiled step: the 1x1 projection-shortcut step computed inside it as extra K stages (conv_split.hip SecondInput), or -1
   std::vector<char> conv_split6;  // ConvTiled steps on conv2d_split6 (default; INFERA_PRECISION=fp32 leaves them on the exact-fp32 kernels)
   std::vector<char> stem_split6;  // ConvPatch + fused MaxPool steps that run conv2d_stem_split6 (same arithmetic)
+  // QDense steps whose input / output buffer holds quantised bytes instead of the f32 values they stand for (schedule.cpp byte_buffers)
+  std::vector<char> q_in_bytes, q_out_bytes;
   std::vector<int> slot_of_buf;        // scratch slot per activation buffer (-1: external in/out)
   std::vector<int64_t> slot_per_row;   // floats per row of each scratch slot
   int64_t scratch_per_row = 0;         // sum over slots

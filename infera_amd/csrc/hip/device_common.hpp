@@ -77,6 +77,11 @@ __device__ __forceinline__ void dispatch_act(int kind, F &&f) {
   }
 }
 
+// q = sat(rne(v / scale) + zp) as a float (QuantizeLinear: an IEEE quotient, ties to even, the type's range [lo, hi])
+__device__ __forceinline__ float quantise(float v, float scale, float zp, float lo, float hi) {
+  return fminf(fmaxf(rintf(__fdiv_rn(v, scale)) + zp, lo), hi);
+}
+
 __device__ __forceinline__ float apply_bop(float x, float c, char op, bool const_left) {
   const float l = const_left ? c : x, r = const_left ? x : c;
   switch (op) {

@@ -33,6 +33,13 @@ __global__ __launch_bounds__(kBlock) void unary_kernel(const float *__restrict__
   for (int64_t i = (n4 << 2) + int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) y[i] = apply_act(x[i], act);
 }
 
+// y = (sat(rne(x / s) + zp) - zp) * s, the product rounded on its own
+__global__ __launch_bounds__(kBlock) void fake_quant_kernel(const float *__restrict__ x, float *__restrict__ y, int64_t n, float scale, float zp, float lo,
+                                                           float hi) {
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) y[i] = (quantise(x[i], scale, zp, lo, hi) - zp) * scale;  // (a difference times a scale: nothing to contract)
+}
+
 __global__ __launch_bounds__(kBlock) void binary_const_kernel(const float *__restrict__ x, const float *__restrict__ c,
                                                              float *__restrict__ y, int64_t n, int64_t per_row, char op,
                                                              bool const_left, ActParam act) {
@@ -384,6 +391,11 @@ __global__ __launch_bounds__(kBlock) void synth_fill_kernel(float *__restrict__ 
 void unary(hipStream_t s, const float *x, float *y, int64_t n, ActParam act) {
   if (n <= 0) return;
   hipLaunchKernelGGL(unary_kernel, dim3(grid_for((n + 3) / 4)), dim3(kBlock), 0, s, x, y, n, act);
+}
+
+void fake_quant(hipStream_t s, const float *x, float *y, int64_t n, float scale, int zp, int qmin, int qmax) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(fake_quant_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, x, y, n, scale, float(zp), float(qmin), float(qmax));
 }
 
 void binary_const(hipStream_t s, const float *x, const float *c, float *y, int64_t rows, int64_t per_row, char op,

@@ -262,6 +262,28 @@ void PassRunner::launch_plain(size_t i) {
         throw InferaError::onnx("attention kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
       break;
     case StepKind::MeanTime: kern::mean_time(stream, buf(x.in0), buf(x.out), nr, int(x.rep), int(x.K)); break;
+    case StepKind::FakeQuant:
+      kern::fake_quant(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], x.qx.scale, x.qx.zp, x.qx.qmin(), x.qx.qmax());
+      break;
+    case StepKind::QDense: {  // (which device pointer holds which table: model.cpp upload_qdense)
+      kern::QDenseLaunch q;
+      q.X = buf(x.in0);
+      q.Y = buf(x.out);
+      q.Wp = d.W;
+      q.mult = d.scale;
+      q.bias = d.bias;
+      q.c0 = reinterpret_cast<const int *>(d.shift);
+      q.wz = reinterpret_cast<const int *>(d.cst);
+      q.rows = nr * x.rep;
+      q.K = int(x.K), q.M = int(x.M);
+      q.x_scale = x.qx.scale, q.x_zp = x.qx.zp, q.x_min = x.qx.qmin(), q.x_max = x.qx.qmax(), q.x_shift = x.qx.shift();
+      q.y_on = x.qy.on;
+      q.y_scale = x.qy.scale, q.y_zp = x.qy.zp, q.y_min = x.qy.qmin(), q.y_max = x.qy.qmax(), q.y_shift = x.qy.shift();
+      q.act = int(x.act), q.act_a = x.act_a, q.act_b = x.act_b;
+      q.in_bytes = m.q_in_bytes[i] != 0, q.out_bytes = m.q_out_bytes[i] != 0;
+      kern::qdense(stream, q);
+      break;
+    }
   }
 }
 

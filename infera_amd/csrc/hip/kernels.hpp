@@ -18,6 +18,8 @@ struct ActParam {
 
 // ---- elementwise / reductions (eltwise.hip) --------------------------------------------------
 void unary(hipStream_t s, const float *x, float *y, int64_t n, ActParam act);
+// y = (sat(rne(x / scale) + zp) - zp) * scale with the range [qmin, qmax]   (QuantizeLinear -> DequantizeLinear)
+void fake_quant(hipStream_t s, const float *x, float *y, int64_t n, float scale, int zp, int qmin, int qmax);
 // y[r, i] = act(x[r, i] (op) c[i])   (const_left: c (op) x)
 void binary_const(hipStream_t s, const float *x, const float *c, float *y, int64_t rows, int64_t per_row, char op,
                   bool const_left, ActParam act);
@@ -102,6 +104,34 @@ bool dense_colmajor_supported(int K, int M);
 bool dense_can_fuse_softmax(int K, int M);
 // softmax_mode 3: Y[rows] = float(index of the first maximum of the M scores) -- only where this returns true
 bool dense_can_fuse_argmax(const float *X, int K, int M);
+
+// ---- quantised dense layer, int8 MFMA (qdense.hip) --------------------------------------------
+// One QDense step (host/plan.hpp) over `rows` rows.  X: f32 [rows, K], or (in_bytes) the signed bytes xq - x_shift; Y: f32 [rows, M], or
+// (out_bytes, y_on only) the signed bytes q - y_shift.  Wp = qdense_pack() of the shifted weights; mult / c0 / wz / bias hold
+// qdense_padded_m(M) entries: mult[m] = x_scale * w_scale[m]; c0[m] = every row-independent integer term (qdense.hip; the int32 bias
+// included); wz[m] = the shifted weight zero points, null when all are 0; bias = the f32 bias or null.
+struct QDenseLaunch {
+  const void *X = nullptr;
+  void *Y = nullptr;
+  const float *Wp = nullptr, *mult = nullptr, *bias = nullptr;
+  const int *c0 = nullptr, *wz = nullptr;
+  int64_t rows = 0;
+  int K = 0, M = 0;
+  float x_scale = 1.f;
+  int x_zp = 0, x_min = 0, x_max = 255, x_shift = 128;
+  int y_on = 0;
+  float y_scale = 1.f;
+  int y_zp = 0, y_min = 0, y_max = 255, y_shift = 128;
+  int act = 0;  // plan.hpp Act: None, Relu or Clip(a, b)
+  float act_a = 0.f, act_b = 0.f;
+  bool in_bytes = false, out_bytes = false;
+  int KT = 0, MTp = 0;  // (set by the launcher)
+  bool x_vec = false;
+};
+int qdense_padded_m(int M);
+size_t qdense_packed_floats(int K, int M);
+void qdense_pack(int K, int M, const int8_t *W, float *packed);  // W: [K, M] signed bytes
+void qdense(hipStream_t s, QDenseLaunch p);
 
 // ---- whole-chain fused MLP (mlp_fused.hip) -----------------------------------------------------
 // A chain D0 -> D1 -> D2 -> D3 evaluated in one persistent kernel; activations never leave

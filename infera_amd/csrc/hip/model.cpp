@@ -147,6 +147,30 @@ bool upload_conv_patch(const LoadedModel &m, DeviceStep &d, size_t i, hipStream_
   return false;
 }
 
+// A QDense step (hip/qdense.hip): W = the weight fragments, scale = mult, shift = c0 (int32 bits), cst = the shifted weight zero points
+// (int32 bits; none when all are 0), bias = the f32 bias.  c0[m] = -xz * colsum[m] + K * xz * wz[m] + the int32 bias, mod 2^32
+void upload_qdense(const Step &s, DeviceStep &d, hipStream_t us) {
+  const int K = int(s.K), M = int(s.M), Mp = kern::qdense_padded_m(M);
+  std::vector<float> packed(kern::qdense_packed_floats(K, M));
+  kern::qdense_pack(K, M, s.qW.data(), packed.data());
+  d.W = upload(packed, us);
+  d.scale = upload(zero_padded(s.q_mult, size_t(Mp)), us);
+  const int64_t xz = int64_t(s.qx.zp) - s.qx.shift();
+  std::vector<uint32_t> c0(size_t(Mp), 0), wz(size_t(Mp), 0);
+  bool any_wz = false;
+  for (int j = 0; j < M; j++) {
+    int64_t colsum = 0;
+    for (int k = 0; k < K; k++) colsum += s.qW[size_t(k) * M + j];
+    const int64_t z = s.q_wzp[size_t(j)];
+    c0[size_t(j)] = uint32_t(uint64_t(-xz * colsum + int64_t(K) * xz * z + (s.q_bias.empty() ? 0 : int64_t(s.q_bias[size_t(j)]))));
+    wz[size_t(j)] = uint32_t(int32_t(z));
+    any_wz = any_wz || z != 0;
+  }
+  d.shift = reinterpret_cast<float *>(upload(c0, us));
+  if (any_wz) d.cst = reinterpret_cast<float *>(upload(wz, us));
+  if (!s.bias.empty()) d.bias = upload(zero_padded(s.bias, size_t(Mp)), us);
+}
+
 // The tables of an ai.onnx.ml step (host/trees.hpp, svm.hpp, prep.hpp packs), each into the DeviceStep pointer launch_plain (exec.cpp)
 // passes to its kernel; false: not such a step
 bool upload_ml_tables(const Step &s, DeviceStep &d, hipStream_t us) {
@@ -218,6 +242,10 @@ void upload_to_device(const LoadedModel &m, DeviceModel &dm) {
       }
       default:
         if (upload_ml_tables(s, d, us)) continue;
+        if (s.kind == StepKind::QDense) {
+          upload_qdense(s, d, us);
+          continue;
+        }
         if (s.kind == StepKind::Conv2d) {
           const kern::ConvGeom g = conv_geom(s);
           if (!kern::conv2d_generic_supported(g))

@@ -66,6 +66,7 @@ struct Scheduler {
   void fuse_residual_adds();         // a block's Add (+ activation) into the epilogue of its last producer
   void choose_conv_arithmetic();     // bf16 x three exact parts (default) or exact fp32
   void fold_projection_shortcuts();  // a block's 1x1 shortcut as extra K stages of its second convolution
+  void byte_buffers();               // QDense -> QDense edges that carry the quantised bytes
   void classify_io(const std::vector<EffStep> &eff);   // may the result be stored into pinned memory, the input be read from it / column-major?
   void place_scratch(const std::vector<EffStep> &eff); // scratch slots by liveness
 };
@@ -386,6 +387,32 @@ void Scheduler::fold_projection_shortcuts() {
 
 }
 
+// The output of a QDense step that only QDense steps read, each quantising its input exactly as the producer quantised its result, is
+// stored as the bytes q (shifted to signed) at the start of the same buffer, and the readers skip their own rounding: re-quantising
+// (q - zp) * s with the same s returns q, so the results are bit-identical (tests/test_quantized_gpu.py) and the edge moves a quarter of
+// the bytes.  INFERA_QDENSE_BYTES=0 (read when a model is scheduled): f32 on every edge.
+void Scheduler::byte_buffers() {
+  m.q_in_bytes.assign(n, 0);
+  m.q_out_bytes.assign(n, 0);
+  if (!ScheduleKnobs::read().qdense_bytes) return;
+  for (size_t i = 0; i < n; i++) {
+    const Step &p = st[i];
+    if (p.kind != StepKind::QDense || !p.qy.on || p.out == m.plan.out_buf) continue;
+    int readers = 0;
+    bool ok = true;
+    for (size_t j = 0; j < n; j++) {
+      const Step &c = st[j];
+      if (c.in0 != p.out && c.in1 != p.out && c.in2 != p.out) continue;
+      readers++;
+      ok = ok && j > i && c.kind == StepKind::QDense && c.in0 == p.out && c.qx == p.qy && c.K == p.M && c.rep == p.rep;
+    }
+    if (!ok || readers == 0) continue;
+    m.q_out_bytes[i] = 1;
+    for (size_t j = i + 1; j < n; j++)
+      if (st[j].in0 == p.out) m.q_in_bytes[j] = 1;
+  }
+}
+
 void Scheduler::classify_io(const std::vector<EffStep> &eff) {
   {  // the served output: one writer (a fused streaming kernel that only stores it), no reader
     int writers = 0, readers = 0;
@@ -493,6 +520,7 @@ void schedule(LoadedModel &m) {
   s.fuse_residual_adds();
   s.choose_conv_arithmetic();
   s.fold_projection_shortcuts();
+  s.byte_buffers();
   const auto eff = effective_steps(m);
   s.classify_io(eff);
   s.place_scratch(eff);
@@ -534,6 +562,14 @@ std::string LoadedModel::describe_json() const {
       dk += std::string(dk.empty() ? "" : ",") + json_str(kern::dense_kernel_family(int64_t(1) << 20, int(x.K), int(x.M), sm, false, true));
     }
     if (!dk.empty()) o << ",\"dense_kernels\":[" << dk << "]";
+  }
+  {  // per QDense step: does its input / output edge carry bytes
+    std::string q;
+    for (size_t i = 0; i < exec.size(); i++)
+      if (plan.steps[i].kind == StepKind::QDense)
+        q += std::string(q.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"in_bytes\":" + (q_in_bytes[i] ? "true" : "false") + ",\"out_bytes\":" +
+             (q_out_bytes[i] ? "true" : "false") + "}";
+    if (!q.empty()) o << ",\"qdense\":[" << q << "]";
   }
   if (!chains.empty()) {
     o << ",\"chain_kernels\":[";

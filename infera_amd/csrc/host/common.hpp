@@ -122,6 +122,7 @@ struct ScheduleKnobs {
                     //   EXACTLY into three bf16 parts, six partial products per product, fp32 accumulate (conv_split.hip) -- no scales, no precondition
                     //   on the data.  INFERA_PRECISION=fp32: the exact-fp32 matrix instruction instead (conv.hip's tiled / weight-stationary kernels)
   bool conv_fold_shortcut;  // INFERA_CONV_FOLD_SHORTCUT=0|1 (default 1)  a ResNet block's 1x1 projection shortcut as extra K stages of the block's second convolution
+  bool qdense_bytes;  // INFERA_QDENSE_BYTES=0|1 (default 1)  a QDense result read only by QDense steps that quantise it the same way travels as bytes (0: as f32; same bits)
   static ScheduleKnobs read();
 };
 // Read per launch inside the kernel launchers, for the bit-identity TESTS only (no effect on results; defaults are the shipped paths):

@@ -63,6 +63,10 @@ struct Val {
   // zero padding (top, left, bottom, right) a Pad node asked for and the consuming Conv still has to apply; `shape`
   // is the UNPADDED tensor that `buf` holds
   int64_t pend[4] = {0, 0, 0, 0};
+  // set: the value is a QUANTISED activation (uint8 / int8 in the graph).  q_done: `buf` holds the dequantised values (q - zp) * s (a
+  // QLinearMatMul's result); else `buf` is the f32 tensor a QuantizeLinear read and the rounding is still to be done by whoever reads this
+  std::shared_ptr<const Quant> q;
+  bool q_done = false;
   bool padded() const { return pend[0] || pend[1] || pend[2] || pend[3]; }
 };
 
@@ -244,6 +248,7 @@ struct Lowerer {
     const Val &a = get(n, 0);
     const Val &b = get(n, 1);
     if (a.is_const) unsupported(n, "constant left operand is not supported");
+    if (b.is_const && b.c->q_data && qdense_from_qdq(n, gemm)) return;
     if (!b.is_const) {
       auto why = attn_fail.find(&n);
       if (why != attn_fail.end()) unsupported(n, "unsupported operator form: " + why->second);
@@ -494,6 +499,13 @@ struct Lowerer {
       const auto &cv = cf32(n, cst);
       bool over_m = p && p->kind == StepKind::Dense && p->bias.empty() && p->act == Act::None && int64_t(cv.size()) == p->M &&
                     (cst.shape.size() == 1 || (cst.shape.size() == 2 && cst.shape[0] == 1));
+      if (p && p->kind == StepKind::QDense && !p->qy.on && p->act == Act::None && p->bias.empty() && p->q_bias.empty() && int64_t(cv.size()) == p->M &&
+          (cst.shape.size() == 1 || (cst.shape.size() == 2 && cst.shape[0] == 1))) {
+        qdense_take_bias(n, *p, cst);
+        p->origin += "+Add";
+        set_act(n, act.buf, act_shape, true);
+        return;
+      }
       if (over_m) {
         p->bias = cv;
         p->origin += "+Add";
@@ -954,7 +966,8 @@ struct Lowerer {
       const bool mfma_step = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d;
       const bool takes_act = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d || p->kind == StepKind::AffineChannel ||
                              p->kind == StepKind::BinaryConst || p->kind == StepKind::BinaryAct;
-      if (p->act == Act::None && takes_act && (!mfma_step || mfma_fusable(act))) {
+      const bool qdense_act = p->kind == StepKind::QDense && !p->qy.on && (act == Act::Relu || act == Act::Clip);  // on `real`, before the requantisation
+      if (p->act == Act::None && (takes_act || qdense_act) && (!mfma_step || mfma_fusable(act))) {
         p->act = act;
         p->act_a = pa;
         p->act_b = pb;
@@ -2004,6 +2017,268 @@ struct Lowerer {
     emit(std::move(s), n, shape);
   }
 
+
+  // ------------------------------------------------------------------------------------------
+  // Quantised graphs.  A QuantizeLinear of an activation emits nothing: its output is a quantised value over the
+  // same buffer (Val::q).  DequantizeLinear of a constant folds to f32 and remembers its integers; of a quantised activation it becomes
+  // a FakeQuant step -- or the output quantisation of the QDense step in front of it.  MatMul / Gemm between a FakeQuant (or a
+  // quantised QDense) and dequantised int8 weights, and QLinearMatMul, become QDense.
+  [[noreturn]] void bad_form(const NodeDef &n, const std::string &why) { unsupported(n, "unsupported operator form: " + why); }
+
+  // the constant scale / zero point inputs (`si`, `zi`) of a quantisation node: one scale per tensor, or one per index of an axis
+  struct QArgs {
+    std::vector<float> scale;
+    std::vector<int64_t> zp;
+    int elem = onnx::kUint8;  // the quantised element type (the zero point's; uint8 without one)
+  };
+  QArgs quant_args(const NodeDef &n, size_t si, size_t zi, const char *what) {
+    QArgs qa;
+    if (n.attr_i("block_size", 0) != 0) bad_form(n, "block_size (blocked quantisation) is not supported");
+    const Val &sv = get(n, si);
+    if (!sv.is_const) bad_form(n, std::string("the ") + what + " scale is not a constant");
+    if (sv.c->dtype != onnx::kFloat) bad_form(n, std::string("the ") + what + " scale must be f32");
+    qa.scale = sv.c->f32;
+    if (qa.scale.empty()) bad_form(n, std::string("the ") + what + " scale is empty");
+    for (float v : qa.scale)
+      if (!std::isfinite(v) || !(v > 0.f)) bad_form(n, std::string("the ") + what + " scale must be finite and positive");
+    if (has_input(n, zi)) {
+      const Val &zv = get(n, zi);
+      if (!zv.is_const) bad_form(n, std::string("the ") + what + " zero point is not a constant");
+      if (zv.c->elem != onnx::kUint8 && zv.c->elem != onnx::kInt8 && zv.c->elem != onnx::kInt32)
+        bad_form(n, std::string("the ") + what + " zero point has element type " + std::to_string(zv.c->elem) + "; only uint8, int8 (and int32 for a bias) are supported");
+      if (zv.c->i64.size() != qa.scale.size()) bad_form(n, std::string("the ") + what + " scale and zero point differ in size");
+      qa.zp = zv.c->i64;
+      qa.elem = zv.c->elem;
+    } else {
+      qa.zp.assign(qa.scale.size(), 0);
+    }
+    return qa;
+  }
+  Quant act_quant(const NodeDef &n, const QArgs &qa, const char *what) {
+    if (qa.scale.size() != 1) bad_form(n, std::string("per-axis quantisation of an activation (") + what + ") is not supported");
+    if (qa.elem != onnx::kUint8 && qa.elem != onnx::kInt8) bad_form(n, std::string(what) + " has element type " + std::to_string(qa.elem) + "; only uint8 and int8 are supported");
+    Quant q;
+    q.on = true;
+    q.scale = qa.scale[0];
+    q.zp = int(qa.zp[0]);
+    q.is_signed = qa.elem == onnx::kInt8;
+    return q;
+  }
+
+  std::map<std::string, const NodeDef *> quant_node;  // quantised value -> the node that made it
+  void set_quant(const NodeDef &n, int buf, const std::vector<int64_t> &shape, int ra, const Quant &q, bool done, bool folded) {
+    set_act(n, buf, shape, folded, ra);
+    Val &v = vals[n.outputs[0]];
+    v.q = std::make_shared<const Quant>(q);
+    v.q_done = done;
+    quant_node[n.outputs[0]] = &n;
+  }
+
+  void quantize_linear(const NodeDef &n) {
+    const Val x = get(n, 0);
+    if (x.is_const) bad_form(n, "quantising a constant is not supported");
+    if (x.q) bad_form(n, "the input is a quantised tensor already");
+    if (auto *a = n.attr("output_dtype"); a && a->i != 0 && a->i != onnx::kUint8 && a->i != onnx::kInt8)
+      bad_form(n, "output_dtype " + std::to_string(a->i) + "; only uint8 and int8 are supported");
+    const Quant q = act_quant(n, quant_args(n, 1, 2, "activation"), "the activation");
+    set_quant(n, x.buf, x.shape, x.ra, q, false, true);
+  }
+
+  void dequantize_linear(const NodeDef &n) {
+    const Val x = get_raw(n, 0);
+    if (x.pv) bad_form(n, "the input is not a quantised tensor");
+    const QArgs qa = quant_args(n, 1, 2, x.is_const ? "constant's" : "activation");
+    if (x.is_const) {
+      const TensorData &t = *x.c;
+      if (t.elem != onnx::kUint8 && t.elem != onnx::kInt8 && t.elem != onnx::kInt32)
+        bad_form(n, "the data has element type " + std::to_string(t.elem) + "; only uint8, int8 (and int32 for a bias) are supported");
+      if (has_input(n, 2) && qa.elem != t.elem) bad_form(n, "the zero point's element type differs from the data's");
+      int64_t axis = n.attr_i("axis", 1);
+      const int64_t rank = int64_t(t.dims.size());
+      int64_t outer = 1, len = 1, inner = int64_t(t.i64.size());
+      if (qa.scale.size() > 1) {
+        if (axis < 0) axis += rank;
+        if (axis < 0 || axis >= rank || int64_t(qa.scale.size()) != t.dims[size_t(axis)]) bad_form(n, "the scale does not match the axis it quantises");
+        len = t.dims[size_t(axis)];
+        inner = prod(t.dims, size_t(axis) + 1);
+        outer = prod(t.dims, 0, size_t(axis));
+      }
+      auto out = std::make_shared<TensorData>();
+      out->dtype = out->elem = onnx::kFloat;
+      out->dims = t.dims;
+      out->f32.resize(t.i64.size());
+      for (int64_t o = 0; o < outer; o++)
+        for (int64_t j = 0; j < len; j++)
+          for (int64_t i = 0; i < inner; i++) {
+            const size_t at = size_t((o * len + j) * inner + i);
+            out->f32[at] = float(t.i64[at] - qa.zp[size_t(qa.scale.size() > 1 ? j : 0)]) * qa.scale[size_t(qa.scale.size() > 1 ? j : 0)];
+          }
+      out->q_data = x.c;
+      out->q_scale = qa.scale;
+      out->q_zp = qa.zp;
+      out->q_axis = axis;
+      vals[n.outputs[0]] = const_val(std::move(out));
+      return;
+    }
+    if (!x.q) bad_form(n, "the input is not a quantised tensor");
+    const Quant q = act_quant(n, qa, "the activation");
+    if (!(q == *x.q)) bad_form(n, "it dequantises with another scale, zero point or type than the tensor was quantised with");
+    if (x.q_done) {  // a QLinearMatMul's result: the buffer holds these values already
+      set_act(n, x.buf, x.shape, true, x.ra);
+      return;
+    }
+    if (Step *p = fusable_producer(n, 0); p && p->kind == StepKind::QDense && !p->qy.on && (p->act == Act::None || p->act == Act::Relu || p->act == Act::Clip)) {
+      p->qy = q;
+      qdense_canonical_act(*p);
+      p->origin += "+" + node_label(n);
+      set_act(n, x.buf, x.shape, true, x.ra);
+      return;
+    }
+    Step s;
+    s.kind = StepKind::FakeQuant;
+    s.in0 = x.buf;
+    s.qx = q;
+    if (x.ra != 0) bad_form(n, "quantisation of a time-major value");
+    emit(std::move(s), n, x.shape);
+  }
+
+  // A Relu in front of a quantisation whose range starts at 0 (zp == qmin) changes nothing: sat() does the same.  Dropping it makes
+  // the QDQ spelling (which writes the Relu) and the QLinear spelling (which cannot) one plan.
+  static void qdense_canonical_act(Step &s) {
+    if (s.qy.on && s.act == Act::Relu && s.qy.zp == s.qy.qmin()) s.act = Act::None;
+  }
+
+  void qdense_check_k(const NodeDef &n, const Step &s) {
+    int64_t mb = 0;
+    for (int32_t b : s.q_bias) mb = std::max<int64_t>(mb, std::llabs(int64_t(b)));
+    if (!qdense_k_fits(s.K, mb))
+      bad_form(n, "K = " + std::to_string(s.K) + " is beyond the cap of the int32 accumulator (K * 255 * 255 + max|bias| must stay below 2^31)");
+  }
+
+  // the bias of a QDense step: DequantizeLinear(int32, scale = x_scale * w_scale[m], zero point 0) is added to the accumulator as it
+  // is; any other f32 constant after the scaling
+  void qdense_take_bias(const NodeDef &n, Step &s, const Val &c) {
+    const auto &cv = cf32(n, c);
+    const TensorData &t = *c.c;
+    bool as_int = t.q_data && t.q_data->elem == onnx::kInt32 && int64_t(t.q_data->i64.size()) == s.M && (t.q_scale.size() == 1 || int64_t(t.q_scale.size()) == s.M);
+    for (int64_t j = 0; as_int && j < s.M; j++) {
+      const size_t qi = t.q_scale.size() == 1 ? 0 : size_t(j);
+      const int64_t v = t.q_data->i64[size_t(j)];
+      as_int = t.q_zp[qi] == 0 && t.q_scale[qi] == s.q_mult[size_t(j)] && v >= INT32_MIN && v <= INT32_MAX;
+    }
+    if (as_int) {
+      s.q_bias.resize(size_t(s.M));
+      for (int64_t j = 0; j < s.M; j++) s.q_bias[size_t(j)] = int32_t(t.q_data->i64[size_t(j)]);
+      qdense_check_k(n, s);
+    } else {
+      s.bias = cv;
+    }
+  }
+
+  // the QDense step of X[.., K] (quantised as xq) times the integer matrix `w` ([K, M], or [M, K] under trans) with scales ws and zero
+  // points wz (one, or M of them)
+  Step make_qdense(const NodeDef &n, int in_buf, int64_t rep, const TensorData &w, bool trans, const std::vector<float> &ws, const std::vector<int64_t> &wz,
+                   const Quant &xq) {
+    if (w.elem != onnx::kUint8 && w.elem != onnx::kInt8) bad_form(n, "the weights have element type " + std::to_string(w.elem) + "; only uint8 and int8 are supported");
+    if (w.dims.size() != 2) bad_form(n, "the weights must be a [K, M] matrix");
+    const int64_t K = trans ? w.dims[1] : w.dims[0], M = trans ? w.dims[0] : w.dims[1];
+    if (K <= 0 || M <= 0 || int64_t(w.i64.size()) != K * M) bad_form(n, "weight matrix " + shape_str(w.dims) + " does not match its data");
+    if ((ws.size() != 1 && int64_t(ws.size()) != M) || wz.size() != ws.size()) bad_form(n, "the weights' scale must be one value or one per output column");
+    Step s;
+    s.kind = StepKind::QDense;
+    s.in0 = in_buf;
+    s.K = K;
+    s.M = M;
+    s.rep = rep;
+    s.qx = xq;
+    s.q_w_signed = w.elem == onnx::kInt8;
+    s.q_per_channel = ws.size() > 1;
+    const int shift = s.q_w_signed ? 0 : 128;
+    s.qW.resize(size_t(K * M));
+    for (int64_t k = 0; k < K; k++)
+      for (int64_t j = 0; j < M; j++) s.qW[size_t(k * M + j)] = int8_t((trans ? w.i64[size_t(j * K + k)] : w.i64[size_t(k * M + j)]) - shift);
+    s.q_wzp.resize(size_t(M));
+    s.q_mult.resize(size_t(M));
+    for (int64_t j = 0; j < M; j++) {
+      const size_t qi = ws.size() == 1 ? 0 : size_t(j);
+      s.q_wzp[size_t(j)] = int32_t(wz[qi] - shift);
+      s.q_mult[size_t(j)] = xq.scale * ws[qi];
+    }
+    qdense_check_k(n, s);
+    return s;
+  }
+
+  // MatMul / Gemm whose weights were dequantised from int8 / uint8 and whose input was just quantised: QDense.  false: not that
+  // pattern (a weight-only model, a per-row weight scale ...) -- the float layer on the dequantised weights serves it
+  bool qdense_from_qdq(const NodeDef &n, bool gemm) {
+    const Val a = get(n, 0);
+    const Val &b = get(n, 1);
+    const TensorData &bt = *b.c;
+    if (a.is_const || a.ra != 0 || b.shape.size() != 2) return false;
+    if (bt.q_data->elem != onnx::kUint8 && bt.q_data->elem != onnx::kInt8) return false;
+    const bool window = !gemm && a.shape.size() == 3;
+    if (!window && a.shape.size() != 2) return false;
+    const bool tB = gemm && n.attr_i("transB", 0) != 0;
+    if (gemm && (n.attr_i("transA", 0) != 0 || n.attr_f("alpha", 1.f) != 1.f || n.attr_f("beta", 1.f) != 1.f)) return false;
+    if (bt.q_scale.size() > 1 && bt.q_axis != (tB ? 0 : 1)) return false;  // (scales along K: no integer form)
+    auto pit = producer.find(a.buf);
+    if (pit == producer.end()) return false;
+    const Step &ps = plan.steps[size_t(pit->second)];
+    Quant xq;
+    if (ps.kind == StepKind::FakeQuant) xq = ps.qx;
+    else if (ps.kind == StepKind::QDense && ps.qy.on) xq = ps.qy;
+    else return false;
+    const int64_t K = tB ? b.shape[1] : b.shape[0], M = tB ? b.shape[0] : b.shape[1];
+    if (a.shape.back() != K) unsupported(n, "inner dimensions differ: " + shape_str(a.shape) + " x " + shape_str(b.shape));
+    int in_buf = a.buf;
+    std::string head;
+    if (ps.kind == StepKind::FakeQuant) {  // the layer rounds its input itself: read what the FakeQuant read (and drop it when nothing else reads it)
+      in_buf = ps.in0;
+      head = ps.origin + "+";
+      if (sole_tail(a.buf)) drop_tail();
+    }
+    const int64_t rep = window ? a.shape[1] : 1;
+    if (window) prod({rep, std::max(K, M) + 3});
+    Step s = make_qdense(n, in_buf, rep, *bt.q_data, tB, bt.q_scale, bt.q_zp, xq);
+    if (gemm && has_input(n, 2)) {
+      const Val &c = get(n, 2);
+      if (int64_t(cf32(n, c).size()) != M) unsupported(n, "bias C must have M elements");
+      qdense_take_bias(n, s, c);
+    }
+    s.origin = head + node_label(n);
+    if (window) emit_window(std::move(s), n, {a.shape[0], rep, M});
+    else {
+      const std::string origin = s.origin;
+      emit(std::move(s), n, {a.shape[0], M}).origin = origin;
+    }
+    return true;
+  }
+
+  // QLinearMatMul(a, a_scale, a_zp, b, b_scale, b_zp, y_scale, y_zp): the same step, spelled in one node; its result stays a quantised value
+  void qlinear_matmul(const NodeDef &n) {
+    if (n.inputs.size() != 8) bad_form(n, "needs its eight inputs");
+    const Val a = get_raw(n, 0);
+    if (a.is_const || a.pv || !a.q) bad_form(n, "input a must be a quantised activation (the output of QuantizeLinear or QLinearMatMul)");
+    const Quant xq = act_quant(n, quant_args(n, 1, 2, "input a's"), "input a");
+    if (!(xq == *a.q)) bad_form(n, "a_scale / a_zero_point differ from what input a was quantised with");
+    const Val &b = get(n, 3);
+    if (!b.is_const) bad_form(n, "input b must be a constant weight matrix");
+    const QArgs qb = quant_args(n, 4, 5, "weights'");
+    if (qb.elem != b.c->elem) bad_form(n, "the weights' zero point's element type differs from the data's");
+    const Quant yq = act_quant(n, quant_args(n, 6, 7, "output's"), "the output");
+    const bool window = a.shape.size() == 3;
+    if ((!window && a.shape.size() != 2) || a.ra != 0) bad_form(n, "input a must be [rows, K] or [rows, T, K]");
+    if (b.shape.size() != 2 || a.shape.back() != b.shape[0]) unsupported(n, "inner dimensions differ: " + shape_str(a.shape) + " x " + shape_str(b.shape));
+    const int64_t rep = window ? a.shape[1] : 1, M = b.shape[1];
+    if (window) prod({rep, std::max(b.shape[0], M) + 3});
+    Step s = make_qdense(n, a.buf, rep, *b.c, false, qb.scale, qb.zp, xq);
+    s.qy = yq;
+    s.origin = node_label(n);
+    const std::vector<int64_t> shape = window ? std::vector<int64_t>{a.shape[0], rep, M} : std::vector<int64_t>{a.shape[0], M};
+    const int out = push_step(std::move(s), window ? flat_shape(shape) : shape);
+    set_quant(n, out, shape, 0, yq, true, false);
+  }
+
   // ------------------------------------------------------------------------------------------
   void lower_node(const NodeDef &n) {
     const std::string &op = n.op;
@@ -2015,7 +2290,17 @@ struct Lowerer {
     static const std::set<std::string> reads_time_major = {"Transpose", "Squeeze", "Unsqueeze", "Reshape", "Identity", "Dropout", "Flatten", "Shape",
                                                            "Gather", "Slice", "LSTM", "GRU", "RNN"};
     check_row_axis(n, reads_time_major.count(op) > 0);
-    if (op == "LSTM" || op == "GRU" || op == "RNN") recurrent(n);
+    if (op == "DynamicQuantizeLinear")
+      bad_form(n, "its scale spans all rows of a call, so a row's result would depend on its chunk; quantise statically (QuantizeLinear with constant scales)");
+    if (op != "DequantizeLinear" && op != "QLinearMatMul")
+      for (const auto &in_name : n.inputs) {
+        auto it = vals.find(in_name);
+        if (it != vals.end() && it->second.q) bad_form(n, "it reads the quantised tensor '" + in_name + "'; only DequantizeLinear and QLinearMatMul do");
+      }
+    if (op == "QuantizeLinear") quantize_linear(n);
+    else if (op == "DequantizeLinear") dequantize_linear(n);
+    else if (op == "QLinearMatMul") qlinear_matmul(n);
+    else if (op == "LSTM" || op == "GRU" || op == "RNN") recurrent(n);
     else if (op == "ConstantOfShape" || op == "Expand") constant_fill(n);
     else if (op == "MatMul") dense(n, false);
     else if (op == "Gemm") dense(n, true);
@@ -2897,6 +3182,7 @@ struct Lowerer {
     auto it = vals.find(out.name);
     if (it == vals.end()) throw InferaError::onnx("output '" + out.name + "' is never produced");
     if (it->second.pv) materialize(out.name, nullptr);
+    if (it->second.q) bad_form(*quant_node.at(out.name), "its quantised result is the graph output '" + out.name + "'; end the graph with DequantizeLinear");
     if (it->second.is_const) throw InferaError::onnx("output '" + out.name + "' is a constant; nothing to run");
     if (it->second.padded()) throw InferaError::onnx("output '" + out.name + "' is a Pad result; padding is only folded into a following Conv");
     if (it->second.ra != 0)
@@ -2933,7 +3219,7 @@ Plan lower_model(const onnx::Model &m, const std::string &output_select) { retur
 double Plan::flops_per_row() const {
   double f = 0;
   for (const auto &s : steps) {
-    if (s.kind == StepKind::Dense) f += 2.0 * double(s.rep) * double(s.K) * double(s.M);
+    if (s.kind == StepKind::Dense || s.kind == StepKind::QDense) f += 2.0 * double(s.rep) * double(s.K) * double(s.M);
     else if (s.kind == StepKind::Attention) f += 4.0 * double(s.attn_T) * double(s.attn_T) * double(s.attn_heads * s.attn_dh);
     else if (s.kind == StepKind::Conv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
@@ -2943,7 +3229,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -2957,6 +3243,22 @@ std::string Plan::describe_json() const {
     if (s.in2 >= 0) o << ",\"in2\":" << s.in2;
     if (s.kind == StepKind::Dense) o << ",\"K\":" << s.K << ",\"M\":" << s.M << ",\"bias\":" << (s.bias.empty() ? "false" : "true");
     if (s.kind == StepKind::Dense && s.rep > 1) o << ",\"T\":" << s.rep;
+    auto qtype = [](const Quant &q) { return !q.on ? "f32" : q.is_signed ? "int8" : "uint8"; };
+    if (s.kind == StepKind::FakeQuant) o << ",\"type\":\"" << qtype(s.qx) << "\",\"scale\":" << double(s.qx.scale) << ",\"zero_point\":" << s.qx.zp;
+    if (s.kind == StepKind::QDense) {
+      o << ",\"K\":" << s.K << ",\"M\":" << s.M << ",\"bias\":\"" << (!s.q_bias.empty() ? "int32" : !s.bias.empty() ? "f32" : "none") << "\",\"x_type\":\"" << qtype(s.qx)
+        << "\",\"w_type\":\"" << (s.q_w_signed ? "int8" : "uint8") << "\",\"y_type\":\"" << qtype(s.qy) << "\",\"per_channel\":" << (s.q_per_channel ? "true" : "false");
+      if (s.rep > 1) o << ",\"T\":" << s.rep;
+      // what the parser read, for checks without a GPU: sums over the weights in their own type and over the int32 bias
+      long long wsum = 0, whash = 0, bsum = 0;
+      for (size_t k = 0; k < s.qW.size(); k++) {
+        const long long w = s.qW[k] + (s.q_w_signed ? 0 : 128);
+        wsum += w;
+        whash += w * (long long)(k % 251 + 1);
+      }
+      for (int32_t b : s.q_bias) bsum += b;
+      o << ",\"w_sum\":" << wsum << ",\"w_hash\":" << whash << ",\"bias_sum\":" << bsum << ",\"x_zero_point\":" << s.qx.zp;
+    }
     if (s.kind == StepKind::LayerNorm) o << ",\"E\":" << s.K << ",\"T\":" << s.rep << ",\"epsilon\":" << double(s.ln_eps) << ",\"bias\":" << (s.shift.empty() ? "false" : "true");
     if (s.kind == StepKind::MeanTime) o << ",\"E\":" << s.K << ",\"T\":" << s.rep;
     if (s.kind == StepKind::Attention)

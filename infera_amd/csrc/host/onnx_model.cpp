@@ -156,6 +156,7 @@ std::shared_ptr<TensorData> read_tensor(Wire w) {
   if (n == 0)  // an empty tensor must not smuggle an absurd extent past the payload check either
     for (auto d : t->dims)
       if (d > (int64_t(1) << 31)) throw size_err();
+  t->elem = dtype;
   switch (dtype) {
     case kFloat:
       t->dtype = kFloat;
@@ -204,6 +205,24 @@ std::shared_ptr<TensorData> read_tensor(Wire w) {
         t->i64 = std::move(idata);
       }
       break;
+    case kUint8:
+    case kInt8: {  // quantised weights and zero points: one byte per element in raw_data, one int32 per element in int32_data
+      t->dtype = kInt64;
+      const int64_t lo = dtype == kInt8 ? -128 : 0, hi = dtype == kInt8 ? 127 : 255;
+      if (raw) {
+        if (rawlen != n) throw size_err();
+        t->i64.resize(n);
+        for (size_t i = 0; i < n; i++) t->i64[i] = dtype == kInt8 ? int64_t(int8_t(raw[i])) : int64_t(raw[i]);
+      } else {
+        if (idata.size() != n) throw size_err();
+        for (auto &v : idata) {
+          v = int64_t(int32_t(uint32_t(uint64_t(v))));  // (an int32 field: negative values arrive sign-extended to 64 bits)
+          if (v < lo || v > hi) throw InferaError::onnx("tensor '" + t->name + "': int32_data holds a value outside the " + (dtype == kInt8 ? "int8" : "uint8") + " range");
+        }
+        t->i64 = std::move(idata);
+      }
+      break;
+    }
     default:
       throw InferaError::onnx("tensor '" + t->name + "': unsupported data_type " + std::to_string(dtype));
   }

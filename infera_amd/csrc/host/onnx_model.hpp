@@ -14,15 +14,22 @@
 
 namespace infera_hip::onnx {
 
-enum DataType : int { kFloat = 1, kInt32 = 6, kInt64 = 7, kDouble = 11 };
+enum DataType : int { kFloat = 1, kUint8 = 2, kInt8 = 3, kInt32 = 6, kInt64 = 7, kDouble = 11 };
 
 struct TensorData {
   std::string name;
-  int dtype = 0;  // kFloat or kInt64 after decoding (int32 widened, double narrowed)
+  int dtype = 0;  // kFloat or kInt64 after decoding (uint8 / int8 / int32 widened, double narrowed)
+  int elem = 0;   // the data_type as the file declares it (quantised graphs tell uint8, int8 and int32 apart)
   std::vector<int64_t> dims;
   std::vector<float> f32;
   std::vector<int64_t> i64;
   std::vector<double> f64;  // kDouble payloads as read (f32 above holds them narrowed): load-time conversions that must round their own way
+  // An f32 constant folded from DequantizeLinear(q_data, q_scale, q_zp) along q_axis (one scale: per tensor) remembers what it came from, so
+  // a MatMul / Gemm that reads it can run on the integers (host/lowering.cpp, QDense)
+  std::shared_ptr<const TensorData> q_data;
+  std::vector<float> q_scale;
+  std::vector<int64_t> q_zp;
+  int64_t q_axis = 0;
   // Element count = payload length.  The decoder has verified it equals Π dims (overflow-checked), so a
   // declared shape can never claim more elements than the file holds.
   size_t count() const { return dtype == kInt64 ? i64.size() : f32.size(); }

@@ -57,7 +57,23 @@ enum class StepKind : int {
   LayerNorm = 21,     // y = (x - mean) / sqrt(var + eps) * scale[K] + shift[K] over each of the `rep` vectors of K elements of a row (layernorm.hip)
   Attention = 22,     // self-attention over the T steps of a row: out [rows, T, heads * dh] = softmax(attn_scale . Q K^T + mask) V per head (attention.hip)
   MeanTime = 23,      // out[r, e] = mean over t of in0[r, t, e]   (ReduceMean over the time axis of [rows, T = rep, K])
+  FakeQuant = 24,     // y = (sat(rne(x / s) + zp) - zp) * s   (QuantizeLinear -> DequantizeLinear on an activation; Step::qx)
+  QDense = 25,        // quantised MatMul / Gemm on the int8 matrix cores, f32 in and out (Step::qx, qy, qW ...; qdense.hip)
 };
+
+// Constant per-tensor quantisation of an activation: q = sat(rne(x / scale) + zp) in uint8 or int8
+struct Quant {
+  bool on = false;
+  float scale = 1.f;
+  int zp = 0;
+  bool is_signed = false;  // int8 (else uint8)
+  int qmin() const { return is_signed ? -128 : 0; }
+  int qmax() const { return is_signed ? 127 : 255; }
+  int shift() const { return is_signed ? 0 : 128; }  // q - shift() is the signed byte the matrix instruction reads
+  bool operator==(const Quant &o) const { return on == o.on && scale == o.scale && zp == o.zp && is_signed == o.is_signed; }
+};
+// Largest K of a QDense step with |bias| <= max_bias: K * 255 * 255 + max|bias| stays below 2^31, so the int32 accumulator is exact
+inline bool qdense_k_fits(int64_t K, int64_t max_bias) { return K * 255 * 255 + max_bias < (int64_t(1) << 31); }
 
 // TreeEnsemble / TreeReduce output modes (Step::out_mode)
 enum TreeOut : int { kTreeScores = 0, kTreeLabel = 1, kTreeBinaryScores = 2, kTreeBinaryLabel = 3 };
@@ -112,6 +128,14 @@ struct Step {
   int in2 = -1;
   int64_t attn_T = 0, attn_heads = 0, attn_dh = 0, attn_ld[3] = {0, 0, 0}, attn_off[3] = {0, 0, 0};
   float attn_scale = 1.f, ln_eps = 1e-5f;
+  // FakeQuant: qx.  QDense: qx = how the f32 input is quantised, qy = how the result is (off: the step returns `real`, f32);
+  // qW [K, M] = the weights as signed bytes (uint8 data shifted by 128), q_wzp[M] = their zero points shifted the same way, q_mult[M] =
+  // x_scale * w_scale[m] in f32, q_bias[M] = the int32 bias added to the accumulator (else `bias`: f32, added after the scaling)
+  Quant qx, qy;
+  std::vector<int8_t> qW;
+  std::vector<int32_t> q_wzp, q_bias;
+  std::vector<float> q_mult;
+  bool q_w_signed = true, q_per_channel = false;
   std::string origin;  // ONNX node names/ops this step came from (diagnostics)
 };
 

@@ -55,9 +55,23 @@ def _s(field: int, s: str) -> bytes:
     return _ld(field, s.encode())
 
 
-def tensor(name: str, arr: np.ndarray, float_data: bool = False) -> bytes:
-    """TensorProto: dims=1, data_type=2, float_data=4, int64_data=7, name=8, raw_data=9."""
+UINT8, INT8, INT32 = 2, 3, 6
+_SMALL_INTS = {np.dtype(np.uint8): (UINT8, "u1"), np.dtype(np.int8): (INT8, "i1"), np.dtype(np.int32): (INT32, "<i4")}
+
+
+def tensor(name: str, arr: np.ndarray, float_data: bool = False, int32_data: bool = False) -> bytes:
+    """TensorProto: dims=1, data_type=2, float_data=4, int32_data=5, int64_data=7, name=8, raw_data=9.  uint8 / int8 / int32 arrays
+    (quantised graphs) go into raw_data, or one varint each into int32_data."""
+    arr = np.asarray(arr)
     out = b"".join(_vi(1, int(d)) for d in arr.shape)
+    if arr.dtype in _SMALL_INTS:
+        code, fmt = _SMALL_INTS[arr.dtype]
+        out += _vi(2, code)
+        if int32_data:
+            out += _ld(5, b"".join(_varint(int(v)) for v in arr.reshape(-1)))
+        else:
+            out += _ld(9, arr.astype(fmt).tobytes())
+        return out + _s(8, name)
     if arr.dtype == np.float32:
         out += _vi(2, FLOAT)
         if float_data:
@@ -1562,3 +1576,232 @@ def sklearn_column_transformer(ct, estimator_graph=None, zipmap: bool = False, a
                           name="zipmap", domain=ML_DOMAIN))
         outs = [outs[0], value_info_zipmap("output_probability")]
     return model("column_transformer", nodes, inits, [value_info("X", ["N", int(ct.n_features_in_)])], outs, opset=13, ml_opset=3)
+
+
+# ------------------------------------------------------------------------------------------
+# statically quantised MLPs (QDQ and QLinearMatMul spellings) and their numpy references
+# ------------------------------------------------------------------------------------------
+
+def _qrange(t: str) -> tuple[int, int]:
+    return (-128, 127) if t == "int8" else (0, 255)
+
+
+def _calibrate(lo: float, hi: float, t: str) -> tuple[np.float32, int]:
+    """Asymmetric per-tensor parameters whose range covers [min(lo, 0), max(hi, 0)]."""
+    qmin, qmax = _qrange(t)
+    lo, hi = min(float(lo), 0.0), max(float(hi), 0.0)
+    scale = np.float32(max(hi - lo, 1e-6) / (qmax - qmin))
+    zp = int(np.clip(np.rint(qmin - lo / float(scale)), qmin, qmax))
+    return scale, zp
+
+
+def _float_act(h, act):
+    if act == "Relu":
+        return np.maximum(h, 0)
+    if isinstance(act, tuple):  # ("Clip", lo, hi)
+        return np.clip(h, act[1], act[2])
+    return h
+
+
+def quantized_mlp_spec(dims: Sequence[int] = (128, 256, 64, 1), acts: Sequence | None = None, x_type: str = "uint8", w_type: str = "int8",
+                       per_channel: bool = True, w_zero_points: bool = False, bias: str | None = "int32", seed: int = 1234,
+                       x_zero_point: int | None = None, tail: str = "", calib_rows: int = 256) -> dict:
+    """A Gemm chain with the weights of mlp() quantised the way ONNX Runtime's quantize_static does: weights per tensor or per output
+    channel (symmetric, or with zero points where w_zero_points), activations per tensor, their ranges taken from the float network
+    on `calib_rows` rows of the synthetic table.  acts[l]: "" | "Relu" | ("Clip", lo, hi).  bias: "int32" (scale x_scale * w_scale,
+    zero point 0), "f32" or None.  spec["q"][l] = (scale, zero point) of the input of layer l; [-1]: of the network's result."""
+    nl = len(dims) - 1
+    acts = list(acts) if acts is not None else ["Relu"] * (nl - 1) + [""]
+    assert len(acts) == nl and w_type in ("int8", "uint8") and x_type in ("int8", "uint8") and bias in ("int32", "f32", None)
+    from .synth import table
+    ws = _WeightStream(seed)
+    h = table(seed + 1, 0, calib_rows, dims[0]).astype(np.float64)
+    q = [_calibrate(h.min(), h.max(), x_type)]
+    if x_zero_point is not None:
+        q[0] = (q[0][0], int(x_zero_point))
+    wmin, wmax = _qrange(w_type)
+    layers = []
+    for l in range(nl):
+        k, m = dims[l], dims[l + 1]
+        w = ws.take((k, m), k).astype(np.float64)
+        b = ws.take((m,), k).astype(np.float64)
+        cols = w if per_channel else w.reshape(-1, 1)
+        if w_zero_points:
+            lo, hi = np.minimum(cols.min(0), 0), np.maximum(cols.max(0), 0)
+            w_scale = (np.maximum(hi - lo, 1e-6) / (wmax - wmin)).astype(np.float32)
+            w_zp = np.clip(np.rint(wmin - lo / w_scale), wmin, wmax).astype(np.int64)
+        else:
+            w_scale = (np.maximum(np.abs(cols).max(0), 1e-6) / 127.0).astype(np.float32)
+            w_zp = np.full(w_scale.shape, 0 if w_type == "int8" else 128, np.int64)
+        wq = np.clip(np.rint(w / w_scale.astype(np.float64)) + w_zp, wmin, wmax).astype(np.int64)
+        layer = {"wq": wq, "w_scale": w_scale, "w_zp": w_zp, "bias_q": None, "bias_f": None}
+        if bias == "int32":
+            layer["bias_scale"] = (q[l][0] * w_scale).astype(np.float32)  # the f32 product, as the loader forms it
+            layer["bias_q"] = np.rint(b / np.broadcast_to(layer["bias_scale"].astype(np.float64), (m,))).astype(np.int64)
+        elif bias == "f32":
+            layer["bias_f"] = b.astype(np.float32)
+        layers.append(layer)
+        h = _float_act(h @ ((wq - w_zp) * w_scale.astype(np.float64)) + (b if bias else 0.0), acts[l])
+        q.append(_calibrate(h.min(), h.max(), x_type))
+    return {"dims": list(dims), "acts": acts, "x_type": x_type, "w_type": w_type, "per_channel": per_channel, "layers": layers, "q": q, "tail": tail}
+
+
+def _np_qtype(t: str):
+    return np.int8 if t == "int8" else np.uint8
+
+
+def quantized_from_spec(spec: dict, form: str = "qdq", layer: str = "matmul_add", weight_only: bool = False, int32_data: bool = False,
+                        batch: int | str = "N", window: int = 0) -> bytes:
+    """The network of a quantized_mlp_spec as a QDQ graph (QuantizeLinear / DequantizeLinear around float MatMul + Add or Gemm; layer =
+    "matmul_add" | "gemm" | "gemm_transb") or in the QOperator spelling (form="qlinear": QuantizeLinear -> QLinearMatMul ... ->
+    DequantizeLinear; no bias, and only activations that the next quantisation's range already applies).  weight_only: only the
+    weights are quantised.  window = T > 0: the input [N, T * dims[0]] is reshaped to [N, T, dims[0]] and every layer runs on each of its T vectors (MatMul forms)."""
+    dims, acts, layers, q = spec["dims"], spec["acts"], spec["layers"], spec["q"]
+    xt, wt = _np_qtype(spec["x_type"]), _np_qtype(spec["w_type"])
+    qmin = _qrange(spec["x_type"])[0]
+    nodes, inits = [], []
+
+    def scalar(name, v, dtype):
+        inits.append(tensor(name, np.array(v, dtype), int32_data=int32_data and dtype != np.float32))
+        return name
+
+    def wparams(l):
+        L = layers[l]
+        pc = spec["per_channel"]
+        inits.append(tensor(f"W{l}_scale", L["w_scale"].astype(np.float32) if pc else np.array(L["w_scale"][0], np.float32)))
+        inits.append(tensor(f"W{l}_zp", L["w_zp"].astype(wt) if pc else np.array(L["w_zp"][0], wt), int32_data=int32_data))
+        return f"W{l}_scale", f"W{l}_zp"
+
+    cur = "X"
+    if window:
+        inits.append(tensor("window_shape", np.array([-1, window, dims[0]], np.int64)))
+        nodes.append(node("Reshape", ["X", "window_shape"], ["X3"], name="window"))
+        cur = "X3"
+    if form == "qlinear":
+        assert not weight_only
+        nodes.append(node("QuantizeLinear", [cur, scalar("q0_scale", q[0][0], np.float32), scalar("q0_zp", q[0][1], xt)], ["Xq"], name="quant_in"))
+        cur = "Xq"
+        for l, L in enumerate(layers):
+            if L["bias_q"] is not None or L["bias_f"] is not None:
+                raise ValueError("QLinearMatMul carries no bias")
+            if acts[l] and not (acts[l] == "Relu" and q[l + 1][1] == qmin):
+                raise ValueError("the QLinear spelling cannot express activation %r before zero point %d" % (acts[l], q[l + 1][1]))
+            inits.append(tensor(f"W{l}", L["wq"].astype(wt), int32_data=int32_data))
+            wsn, wzn = wparams(l)
+            nodes.append(node("QLinearMatMul", [cur, f"q{l}_scale", f"q{l}_zp", f"W{l}", wsn, wzn, scalar(f"q{l + 1}_scale", q[l + 1][0], np.float32),
+                                                scalar(f"q{l + 1}_zp", q[l + 1][1], xt)], [f"H{l}q"], name=f"qmm{l}"))
+            cur = f"H{l}q"
+        out = "Yf" if spec["tail"] else "Y"
+        nodes.append(node("DequantizeLinear", [cur, f"q{len(layers)}_scale", f"q{len(layers)}_zp"], [out], name="dequant_out"))
+        cur = out
+    else:
+        def fake_quant(x, i, out):
+            sn, zn = scalar(f"q{i}_scale", q[i][0], np.float32), scalar(f"q{i}_zp", q[i][1], xt)
+            nodes.append(node("QuantizeLinear", [x, sn, zn], [f"{out}_q"], name=f"quant{i}"))
+            nodes.append(node("DequantizeLinear", [f"{out}_q", sn, zn], [out], name=f"dequant{i}"))
+            return out
+        if not weight_only:
+            cur = fake_quant(cur, 0, "X_dq")
+        for l, L in enumerate(layers):
+            k, m = dims[l], dims[l + 1]
+            trans = layer == "gemm_transb"
+            inits.append(tensor(f"W{l}", np.ascontiguousarray(L["wq"].T if trans else L["wq"]).astype(wt), int32_data=int32_data))
+            wsn, wzn = wparams(l)
+            axis = 0 if trans else 1
+            nodes.append(node("DequantizeLinear", [f"W{l}", wsn, wzn], [f"W{l}_dq"], [attr_i("axis", axis)], name=f"dequant_w{l}"))
+            bname = None
+            if L["bias_q"] is not None and not weight_only:
+                inits.append(tensor(f"B{l}", L["bias_q"].astype(np.int32), int32_data=int32_data))
+                bs = L["bias_scale"]
+                inits.append(tensor(f"B{l}_scale", bs.astype(np.float32) if bs.size > 1 else np.array(bs.reshape(-1)[0], np.float32)))
+                inits.append(tensor(f"B{l}_zp", np.zeros(bs.shape if bs.size > 1 else (), np.int32)))
+                nodes.append(node("DequantizeLinear", [f"B{l}", f"B{l}_scale", f"B{l}_zp"], [f"B{l}_dq"], [attr_i("axis", 0)], name=f"dequant_b{l}"))
+                bname = f"B{l}_dq"
+            elif L["bias_q"] is not None or L["bias_f"] is not None:
+                bf = L["bias_f"] if L["bias_f"] is not None else (L["bias_q"] * np.broadcast_to(L["bias_scale"], (m,))).astype(np.float32)
+                inits.append(tensor(f"B{l}", bf.astype(np.float32)))
+                bname = f"B{l}"
+            z = f"Z{l}"
+            if layer == "matmul_add":
+                nodes.append(node("MatMul", [cur, f"W{l}_dq"], [z if bname else f"ZB{l}"], name=f"matmul{l}"))
+                if bname:
+                    nodes.append(node("Add", [z, bname], [f"ZB{l}"], name=f"add{l}"))
+            else:
+                nodes.append(node("Gemm", [cur, f"W{l}_dq"] + ([bname] if bname else []), [f"ZB{l}"], [attr_i("transB", 1)] if trans else [], name=f"gemm{l}"))
+            cur = f"ZB{l}"
+            if acts[l] == "Relu":
+                nodes.append(node("Relu", [cur], [f"A{l}"], name=f"relu{l}"))
+                cur = f"A{l}"
+            elif acts[l]:
+                inits += [tensor(f"clip{l}_lo", np.array(acts[l][1], np.float32)), tensor(f"clip{l}_hi", np.array(acts[l][2], np.float32))]
+                nodes.append(node("Clip", [cur, f"clip{l}_lo", f"clip{l}_hi"], [f"A{l}"], name=f"clip{l}"))
+                cur = f"A{l}"
+            if not weight_only:
+                last = l == len(layers) - 1
+                cur = fake_quant(cur, l + 1, ("Yf" if spec["tail"] else "Y") if last else f"H{l}")
+        if weight_only and not spec["tail"]:
+            nodes.append(node("Identity", [cur], ["Y"]))
+    if spec["tail"]:
+        nodes.append(node(spec["tail"], [cur], ["Y"], [attr_i("axis", 1)] if spec["tail"] == "Softmax" else [], name="tail"))
+    return model("qmlp_" + "x".join(map(str, dims)), nodes, inits, [value_info("X", [batch, max(window, 1) * dims[0]])],
+                 [value_info("Y", [batch] + ([window] if window else []) + [dims[-1]])], opset=13)
+
+
+def _tail_reference(h, tail):
+    if tail == "Sigmoid":
+        return 1.0 / (1.0 + np.exp(-h))
+    if tail == "Softmax":
+        e = np.exp(h - h.max(axis=1, keepdims=True))
+        return e / e.sum(axis=1, keepdims=True)
+    return h
+
+
+def quantized_reference(spec: dict, x: np.ndarray, mode: str = "int", weight_only: bool = False, tail: bool = True) -> np.ndarray:
+    """What a quantized_mlp_spec network computes on x.  "int": the QDense definition layer by layer -- f32
+    scalars, an int64 accumulator; "f64" / "f32": the QDQ graph evaluated in that float type.  The tail (Sigmoid / Softmax) is applied
+    in float64 in "int" and "f64" mode.  weight_only: the graph with only its weights quantised (float modes)."""
+    f32 = np.float32
+    qmin, qmax = _qrange(spec["x_type"])
+    layers, q, acts = spec["layers"], spec["q"], spec["acts"]
+    if mode == "int":
+        h = np.asarray(x, f32)
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            for l, L in enumerate(layers):
+                xs, xz = f32(q[l][0]), q[l][1]
+                ys, yz = f32(q[l + 1][0]), q[l + 1][1]
+                xq = np.clip(np.rint(h / xs) + f32(xz), f32(qmin), f32(qmax)).astype(np.int64)
+                acc = (xq - xz) @ (L["wq"] - L["w_zp"][None, :])
+                if L["bias_q"] is not None:
+                    acc = acc + L["bias_q"][None, :]
+                assert np.abs(acc).max(initial=0) < 2 ** 31
+                mult = (xs * L["w_scale"]).astype(f32)
+                real = acc.astype(f32) * mult[None, :]
+                if L["bias_f"] is not None:
+                    real = (real + L["bias_f"][None, :].astype(f32)).astype(f32)
+                real = _float_act(real, acts[l]).astype(f32)
+                qq = np.clip(np.rint(real / ys) + f32(yz), f32(qmin), f32(qmax))
+                h = ((qq - f32(yz)) * ys).astype(f32)
+        return _tail_reference(h.astype(np.float64), spec["tail"]).astype(f32) if tail and spec["tail"] else h
+    ft = np.float64 if mode == "f64" else f32
+    assert mode in ("f64", "f32")
+
+    def fq(h, i):
+        s, z = ft(q[i][0]), ft(q[i][1])
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            return ((np.clip(np.rint(h / s) + z, ft(qmin), ft(qmax)) - z) * s).astype(ft)
+    h = np.asarray(x, f32).astype(ft)
+    if not weight_only:
+        h = fq(h, 0)
+    for l, L in enumerate(layers):
+        w = ((L["wq"] - L["w_zp"][None, :]).astype(ft) * L["w_scale"].astype(ft)[None, :]).astype(ft)
+        h = (h @ w).astype(ft)
+        if L["bias_q"] is not None:
+            h = (h + (L["bias_q"].astype(ft) * np.broadcast_to(L["bias_scale"], L["bias_q"].shape).astype(ft))[None, :]).astype(ft)
+        elif L["bias_f"] is not None:
+            h = (h + L["bias_f"].astype(ft)[None, :]).astype(ft)
+        h = _float_act(h, acts[l]).astype(ft)
+        if not weight_only:
+            h = fq(h, l + 1)
+    if tail and spec["tail"]:
+        h = _tail_reference(h.astype(np.float64) if mode == "f64" else h, spec["tail"])
+    return h.astype(f32)
