@@ -284,6 +284,22 @@ void PassRunner::launch_plain(size_t i) {
       kern::qdense(stream, q);
       break;
     }
+    case StepKind::QConv2d: {  // (the same device-step slots as QDense: model.cpp upload_qconv)
+      kern::QConvLaunch q = qconv_launch(x);
+      q.X = buf(x.in0);
+      q.Y = buf(x.out);
+      q.Wfrag = d.W;
+      q.mult = d.scale;
+      q.bias = d.bias;
+      q.c0 = reinterpret_cast<const int *>(d.shift);
+      q.wz = reinterpret_cast<const int *>(d.cst);
+      q.rows = nr;
+      q.in_cq = cq(x.in0), q.out_cq = cq(x.out);
+      const char *stage = getenv("INFERA_QCONV_STAGE");  // 0: quantise per tap from global memory, no LDS window (read per launch: tests, A/B)
+      q.force_direct = stage && atoi(stage) == 0;
+      kern::qconv(stream, q);
+      break;
+    }
   }
 }
 

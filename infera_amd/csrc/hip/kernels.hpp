@@ -133,6 +133,34 @@ size_t qdense_packed_floats(int K, int M);
 void qdense_pack(int K, int M, const int8_t *W, float *packed);  // W: [K, M] signed bytes
 void qdense(hipStream_t s, QDenseLaunch p);
 
+// ---- quantised convolution, int8 MFMA (qconv.hip) -----------------------------------------------
+// One QConv2d step (host/plan.hpp) over `rows` images.  X: f32 [rows, C, H, W], or (in_cq) channel-quad planes [rows, C/4, H*W, 4]; Y
+// likewise ([rows, M, OH, OW] / out_cq).  Wfrag = qconv_pack() of the shifted weights; mult / c0 / wz / bias as for QDenseLaunch, with
+// qconv_padded_m(M) entries and K = C * kh * kw.
+struct QConvLaunch {
+  const float *X = nullptr;
+  float *Y = nullptr;
+  const float *Wfrag = nullptr, *mult = nullptr, *bias = nullptr;
+  const int *c0 = nullptr, *wz = nullptr;
+  int64_t rows = 0;
+  int C = 0, H = 0, W = 0, M = 0, OH = 0, OW = 0, kh = 1, kw = 1, sh = 1, sw = 1, pt = 0, pl = 0, dh = 1, dw = 1;
+  bool in_cq = false, out_cq = false;
+  float x_scale = 1.f;
+  int x_zp = 0, x_min = 0, x_max = 255, x_shift = 128;
+  int y_on = 0;
+  float y_scale = 1.f;
+  int y_zp = 0, y_min = 0, y_max = 255;
+  int act = 0;  // plan.hpp Act: None, Relu or Clip(a, b)
+  float act_a = 0.f, act_b = 0.f;
+  bool force_direct = false;  // quantise per tap from global memory even where the staged window fits (A/B, tests)
+  int CT = 0, TG = 0, MTp = 0, Hpad = 0, Wpad = 0, lds_entries = 0;  // (set by the launcher)
+};
+int qconv_padded_m(int M);
+size_t qconv_packed_floats(int C, int taps, int M);
+void qconv_pack(int C, int taps, int M, const int8_t *W, float *packed);  // W: [K, M] signed bytes, k = (c, tap)
+bool qconv_stages_in_lds(QConvLaunch p);  // does the launch stage its quantised input window in LDS (else: per tap from global memory)
+void qconv(hipStream_t s, QConvLaunch p);
+
 // ---- whole-chain fused MLP (mlp_fused.hip) -----------------------------------------------------
 // A chain D0 -> D1 -> D2 -> D3 evaluated in one persistent kernel; activations never leave
 // registers.  `packed` holds the fragment-major weights produced by mlp3_pack().

@@ -149,11 +149,25 @@ bool upload_conv_patch(const LoadedModel &m, DeviceStep &d, size_t i, hipStream_
 
 // A QDense step (hip/qdense.hip): W = the weight fragments, scale = mult, shift = c0 (int32 bits), cst = the shifted weight zero points
 // (int32 bits; none when all are 0), bias = the f32 bias.  c0[m] = -xz * colsum[m] + K * xz * wz[m] + the int32 bias, mod 2^32
+void upload_quant_tables(const Step &s, DeviceStep &d, int Mp, hipStream_t us);
 void upload_qdense(const Step &s, DeviceStep &d, hipStream_t us) {
-  const int K = int(s.K), M = int(s.M), Mp = kern::qdense_padded_m(M);
+  const int K = int(s.K), M = int(s.M);
   std::vector<float> packed(kern::qdense_packed_floats(K, M));
   kern::qdense_pack(K, M, s.qW.data(), packed.data());
   d.W = upload(packed, us);
+  upload_quant_tables(s, d, kern::qdense_padded_m(M), us);
+}
+// A QConv2d step (hip/qconv.hip): the same slots, the weight fragments in the kernel's (channel chunk, tap, channel) order
+void upload_qconv(const Step &s, DeviceStep &d, hipStream_t us) {
+  const int taps = int(s.kh * s.kw);
+  std::vector<float> packed(kern::qconv_packed_floats(int(s.C), taps, int(s.M)));
+  kern::qconv_pack(int(s.C), taps, int(s.M), s.qW.data(), packed.data());
+  d.W = upload(packed, us);
+  upload_quant_tables(s, d, kern::qconv_padded_m(int(s.M)), us);
+}
+// mult, c0, wz and the f32 bias of a QDense / QConv2d step, each padded to Mp entries
+void upload_quant_tables(const Step &s, DeviceStep &d, int Mp, hipStream_t us) {
+  const int K = int(s.K), M = int(s.M);
   d.scale = upload(zero_padded(s.q_mult, size_t(Mp)), us);
   const int64_t xz = int64_t(s.qx.zp) - s.qx.shift();
   std::vector<uint32_t> c0(size_t(Mp), 0), wz(size_t(Mp), 0);
@@ -244,6 +258,10 @@ void upload_to_device(const LoadedModel &m, DeviceModel &dm) {
         if (upload_ml_tables(s, d, us)) continue;
         if (s.kind == StepKind::QDense) {
           upload_qdense(s, d, us);
+          continue;
+        }
+        if (s.kind == StepKind::QConv2d) {
+          upload_qconv(s, d, us);
           continue;
         }
         if (s.kind == StepKind::Conv2d) {

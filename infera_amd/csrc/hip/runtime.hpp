@@ -264,6 +264,17 @@ inline kern::ConvGeom conv_geom(const Step &s) {
   return kern::ConvGeom{int(s.C), int(s.H), int(s.Wd), int(s.Mo), int(s.OH), int(s.OW), int(s.kh), int(s.kw),
                         int(s.sh), int(s.sw), int(s.pt), int(s.pl), int(s.dh), int(s.dw), int(s.groups)};
 }
+// the geometry and quantisation of a QConv2d step (pointers, rows and layouts: exec.cpp)
+inline kern::QConvLaunch qconv_launch(const Step &x) {
+  kern::QConvLaunch q;
+  q.C = int(x.C), q.H = int(x.H), q.W = int(x.Wd), q.M = int(x.Mo), q.OH = int(x.OH), q.OW = int(x.OW);
+  q.kh = int(x.kh), q.kw = int(x.kw), q.sh = int(x.sh), q.sw = int(x.sw), q.pt = int(x.pt), q.pl = int(x.pl), q.dh = int(x.dh), q.dw = int(x.dw);
+  q.x_scale = x.qx.scale, q.x_zp = x.qx.zp, q.x_min = x.qx.qmin(), q.x_max = x.qx.qmax(), q.x_shift = x.qx.shift();
+  q.y_on = x.qy.on;
+  q.y_scale = x.qy.scale, q.y_zp = x.qy.zp, q.y_min = x.qy.qmin(), q.y_max = x.qy.qmax();
+  q.act = int(x.act), q.act_a = x.act_a, q.act_b = x.act_b;
+  return q;
+}
 inline kern::PoolTail pool_tail(const Step &q) { return kern::PoolTail{int(q.OH), int(q.OW), int(q.pt), int(q.pl)}; }
 // A Dense layer is a 1x1 convolution over 1x1 "images": with H = W = 1 the channel-quad layout IS the row-major
 // [rows, K] matrix, so the tiled conv kernel (packed weights through LDS, unit-pipelined MFMA stream) serves it.

@@ -188,13 +188,17 @@ void Scheduler::decide_layout() {
   // buffers that keep the caller's NCHW order: the input, and elementwise preprocessing of it (in-graph normalisation)
   m.nchw_buf.assign(m.plan.buf_shape.size(), 0);
   m.nchw_buf[0] = 1;
-  auto elementwise = [](const Step &s) { return s.kind == StepKind::Unary || s.kind == StepKind::BinaryConst || s.kind == StepKind::AffineChannel; };
+  auto elementwise = [](const Step &s) {
+    return s.kind == StepKind::Unary || s.kind == StepKind::BinaryConst || s.kind == StepKind::AffineChannel || s.kind == StepKind::FakeQuant;
+  };
+  auto convolution = [](const Step &s) { return s.kind == StepKind::Conv2d || s.kind == StepKind::QConv2d; };
   for (const auto &s : st)
     if (elementwise(s) && s.in0 >= 0 && m.nchw_buf[size_t(s.in0)] && is4d(s.out) && s.out != m.plan.out_buf) m.nchw_buf[size_t(s.out)] = 1;
   for (const auto &s : st) {
-    any_conv = any_conv || s.kind == StepKind::Conv2d;
+    any_conv = any_conv || convolution(s);
     // (CopyCols = channel concat: a contiguous per-row block in NCHW and in channel-quad planes alike)
-    const bool layout_free = s.kind == StepKind::Conv2d || s.kind == StepKind::Pool2d || s.kind == StepKind::GlobalAvgPool ||
+    // (FakeQuant: elementwise with one scale per tensor, the same bits in either layout; QConv2d reads and writes either, qconv.hip)
+    const bool layout_free = convolution(s) || s.kind == StepKind::FakeQuant || s.kind == StepKind::Pool2d || s.kind == StepKind::GlobalAvgPool ||
                              s.kind == StepKind::BinaryAct || s.kind == StepKind::Unary || s.kind == StepKind::AffineChannel ||
                              s.kind == StepKind::CopyCols || s.kind == StepKind::SliceCols || s.kind == StepKind::LRN ||
                              s.kind == StepKind::ChannelShuffle ||
@@ -208,7 +212,7 @@ void Scheduler::decide_layout() {
     for (int b : {s.in0, s.in1}) {
       if (b < 0) continue;
       if (m.nchw_buf[size_t(b)] && is4d(b) && spatial(b) > 1) {  // NCHW tensors are read by convolutions and by their own elementwise chain only
-        if (!(s.kind == StepKind::Conv2d || (elementwise(s) && b == s.in0 && m.nchw_buf[size_t(s.out)])))
+        if (!(convolution(s) || (elementwise(s) && b == s.in0 && m.nchw_buf[size_t(s.out)])))
           refuse("'" + s.origin + "' reads the NCHW input tensor and is neither a convolution nor elementwise preprocessing");
         continue;
       }
@@ -223,8 +227,11 @@ void Scheduler::decide_layout() {
   }
   if (spatial(m.plan.out_buf) > 1) refuse("the served output is a [C,H,W] tensor (results leave in the caller's NCHW order)");
   // channel-quad planes need whole quads in every internal 4-D tensor (the caller's input stays NCHW)
+  // (a buffer no step writes any more -- that of a FakeQuant its QConv2d absorbed -- has no layout)
+  std::vector<char> written(m.plan.buf_shape.size(), 0);
+  for (const auto &s : st) written[size_t(s.out)] = 1;
   for (size_t b = 1; b < m.plan.buf_shape.size(); b++)
-    if (m.plan.buf_shape[b].size() == 4 && m.plan.buf_shape[b][1] % 4 != 0 && !m.nchw_buf[b]) {
+    if (written[b] && m.plan.buf_shape[b].size() == 4 && m.plan.buf_shape[b][1] % 4 != 0 && !m.nchw_buf[b]) {
       // a [N,C,1,1] tensor has no layout to speak of (a conv head with 10 classes behind the global pool): plain order
       if (spatial(int(b)) == 1) m.nchw_buf[b] = 1;
       else refuse("an internal [N,C,H,W] tensor has " + std::to_string(m.plan.buf_shape[b][1]) + " channels (not whole quads)");
@@ -441,7 +448,7 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
         // ... and that kernel streams it about once (a windowed kernel would fetch a small image over PCIe once per tap)
         const StepKind sk = st[size_t(e.idx)].kind;
         // (a tree walk reads its row tile once per tree slice, and wide rows feature by feature; an SVM once per SV slice)
-        const bool windowed = (sk == StepKind::Conv2d && m.exec[size_t(e.idx)] != ExecKind::ConvPatch) || sk == StepKind::Pool2d || sk == StepKind::LRN ||
+        const bool windowed = (sk == StepKind::Conv2d && m.exec[size_t(e.idx)] != ExecKind::ConvPatch) || sk == StepKind::QConv2d || sk == StepKind::Pool2d || sk == StepKind::LRN ||
                               sk == StepKind::TreeEnsemble || sk == StepKind::SvmKernel ||
                               sk == StepKind::Attention ||  // (every query tile walks all keys and values)
                               sk == StepKind::Recurrent;  // (one dependent fetch per time step: from HBM, not over PCIe)
@@ -570,6 +577,19 @@ std::string LoadedModel::describe_json() const {
         q += std::string(q.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"in_bytes\":" + (q_in_bytes[i] ? "true" : "false") + ",\"out_bytes\":" +
              (q_out_bytes[i] ? "true" : "false") + "}";
     if (!q.empty()) o << ",\"qdense\":[" << q << "]";
+  }
+  {  // per QConv2d step: the layouts it reads and writes, and whether it stages its quantised input window in LDS
+    std::string q;
+    for (size_t i = 0; i < exec.size(); i++) {
+      const Step &x = plan.steps[i];
+      if (x.kind != StepKind::QConv2d) continue;
+      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)], out_cq = cq_mode && !nchw_buf[size_t(x.out)];
+      q += std::string(q.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"C\":" + std::to_string(x.C) + ",\"M\":" + std::to_string(x.Mo) + ",\"k\":[" +
+           std::to_string(x.kh) + "," + std::to_string(x.kw) + "],\"out_hw\":[" + std::to_string(x.OH) + "," + std::to_string(x.OW) + "],\"in_layout\":\"" +
+           (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\",\"input_window\":\"" +
+           (kern::qconv_stages_in_lds(qconv_launch(x)) ? "lds" : "global") + "\"}";
+    }
+    if (!q.empty()) o << ",\"qconv\":[" << q << "]";
   }
   if (!chains.empty()) {
     o << ",\"chain_kernels\":[";

@@ -966,7 +966,7 @@ struct Lowerer {
       const bool mfma_step = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d;
       const bool takes_act = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d || p->kind == StepKind::AffineChannel ||
                              p->kind == StepKind::BinaryConst || p->kind == StepKind::BinaryAct;
-      const bool qdense_act = p->kind == StepKind::QDense && !p->qy.on && (act == Act::Relu || act == Act::Clip);  // on `real`, before the requantisation
+      const bool qdense_act = quantised_layer(*p) && !p->qy.on && (act == Act::Relu || act == Act::Clip);  // on `real`, before the requantisation
       if (p->act == Act::None && (takes_act || qdense_act) && (!mfma_step || mfma_fusable(act))) {
         p->act = act;
         p->act_a = pa;
@@ -1252,24 +1252,32 @@ struct Lowerer {
     const bool one_d = a.shape.size() == 3 && w.shape.size() == 3;  // Conv1d: [N,C,L] as [N,C,1,L], kernel [M,C/g,k] as [M,C/g,1,k]
     if (a.is_const || (a.shape.size() != 4 && !one_d)) unsupported(n, "only [N,C,L] / [N,C,H,W] activations");
     if (!w.is_const || (w.shape.size() != 4 && !one_d)) unsupported(n, "weights must be a constant [M,C/g,kh,kw] (or [M,C/g,k])");
+    if (w.c->q_data && qconv_from_qdq(n)) return;
     Step s;
     s.kind = StepKind::Conv2d;
     s.in0 = a.buf;
-    s.C = a.shape[1]; s.H = one_d ? 1 : a.shape[2]; s.Wd = one_d ? a.shape[2] : a.shape[3];
-    s.Mo = w.shape[0]; s.kh = one_d ? 1 : w.shape[2]; s.kw = one_d ? w.shape[2] : w.shape[3];
-    s.groups = n.attr_i("group", 1);
-    if (s.groups < 1 || s.C != w.shape[1] * s.groups || s.Mo % s.groups) unsupported(n, "channel/group mismatch");
-    spatial(n, s, s.H, s.Wd, a.pend);
+    conv_geometry(n, s, a, w.shape);
     s.W = cf32(n, w);
     if (has_input(n, 2)) {
       s.bias = cf32(n, get(n, 2));
       if (int64_t(s.bias.size()) != s.Mo) unsupported(n, "bias size mismatch");
     }
+    emit(std::move(s), n, conv_out_shape(s, a));
+  }
+  // the geometry fields of a Conv / QLinearConv node over activation `a` with a kernel of shape `ws` ([M,C/g,kh,kw], or [M,C/g,k]: Conv1d)
+  void conv_geometry(const NodeDef &n, Step &s, const Val &a, const std::vector<int64_t> &ws) {
+    const bool one_d = a.shape.size() == 3;
+    s.C = a.shape[1]; s.H = one_d ? 1 : a.shape[2]; s.Wd = one_d ? a.shape[2] : a.shape[3];
+    s.Mo = ws[0]; s.kh = one_d ? 1 : ws[2]; s.kw = one_d ? ws[2] : ws[3];
+    s.groups = n.attr_i("group", 1);
+    if (s.groups < 1 || s.C != ws[1] * s.groups || s.Mo % s.groups) unsupported(n, "channel/group mismatch");
+    spatial(n, s, s.H, s.Wd, a.pend);
     s.K = (s.C / s.groups) * s.kh * s.kw;
     s.M = s.Mo;
-    std::vector<int64_t> shape = {a.shape[0], s.Mo, s.OH, s.OW};
-    if (one_d) shape = {a.shape[0], s.Mo, s.OW};
-    emit(std::move(s), n, shape);
+  }
+  static std::vector<int64_t> conv_out_shape(const Step &s, const Val &a) {
+    if (a.shape.size() == 3) return {a.shape[0], s.Mo, s.OW};
+    return {a.shape[0], s.Mo, s.OH, s.OW};
   }
 
   void batchnorm(const NodeDef &n) {
@@ -2127,7 +2135,7 @@ struct Lowerer {
       set_act(n, x.buf, x.shape, true, x.ra);
       return;
     }
-    if (Step *p = fusable_producer(n, 0); p && p->kind == StepKind::QDense && !p->qy.on && (p->act == Act::None || p->act == Act::Relu || p->act == Act::Clip)) {
+    if (Step *p = fusable_producer(n, 0); p && quantised_layer(*p) && !p->qy.on && (p->act == Act::None || p->act == Act::Relu || p->act == Act::Clip)) {
       p->qy = q;
       qdense_canonical_act(*p);
       p->origin += "+" + node_label(n);
@@ -2141,6 +2149,9 @@ struct Lowerer {
     if (x.ra != 0) bad_form(n, "quantisation of a time-major value");
     emit(std::move(s), n, x.shape);
   }
+
+  // QDense and QConv2d share their quantisation fields and the helpers below
+  static bool quantised_layer(const Step &s) { return s.kind == StepKind::QDense || s.kind == StepKind::QConv2d; }
 
   // A Relu in front of a quantisation whose range starts at 0 (zp == qmin) changes nothing: sat() does the same.  Dropping it makes
   // the QDQ spelling (which writes the Relu) and the QLinear spelling (which cannot) one plan.
@@ -2181,15 +2192,23 @@ struct Lowerer {
                    const Quant &xq) {
     if (w.elem != onnx::kUint8 && w.elem != onnx::kInt8) bad_form(n, "the weights have element type " + std::to_string(w.elem) + "; only uint8 and int8 are supported");
     if (w.dims.size() != 2) bad_form(n, "the weights must be a [K, M] matrix");
-    const int64_t K = trans ? w.dims[1] : w.dims[0], M = trans ? w.dims[0] : w.dims[1];
-    if (K <= 0 || M <= 0 || int64_t(w.i64.size()) != K * M) bad_form(n, "weight matrix " + shape_str(w.dims) + " does not match its data");
-    if ((ws.size() != 1 && int64_t(ws.size()) != M) || wz.size() != ws.size()) bad_form(n, "the weights' scale must be one value or one per output column");
     Step s;
     s.kind = StepKind::QDense;
     s.in0 = in_buf;
-    s.K = K;
-    s.M = M;
+    s.K = trans ? w.dims[1] : w.dims[0];
+    s.M = trans ? w.dims[0] : w.dims[1];
     s.rep = rep;
+    take_quant_weights(n, s, w, trans, ws, wz, xq);
+    return s;
+  }
+  // the quantisation fields of a QDense / QConv2d step whose K and M are set: `w` holds K * M integers as [K, M] (or [M, K] under trans: a
+  // Gemm's transB, a convolution's [M, C, kh, kw])
+  void take_quant_weights(const NodeDef &n, Step &s, const TensorData &w, bool trans, const std::vector<float> &ws, const std::vector<int64_t> &wz, const Quant &xq) {
+    if (w.elem != onnx::kUint8 && w.elem != onnx::kInt8) bad_form(n, "the weights have element type " + std::to_string(w.elem) + "; only uint8 and int8 are supported");
+    const int64_t K = s.K, M = s.M;
+    if (K <= 0 || M <= 0 || int64_t(w.i64.size()) != K * M) bad_form(n, "weight tensor " + shape_str(w.dims) + " does not match its data");
+    if ((ws.size() != 1 && int64_t(ws.size()) != M) || wz.size() != ws.size())
+      bad_form(n, "the weights' scale must be one value or one per output " + std::string(s.kind == StepKind::QConv2d ? "channel" : "column"));
     s.qx = xq;
     s.q_w_signed = w.elem == onnx::kInt8;
     s.q_per_channel = ws.size() > 1;
@@ -2205,7 +2224,6 @@ struct Lowerer {
       s.q_mult[size_t(j)] = xq.scale * ws[qi];
     }
     qdense_check_k(n, s);
-    return s;
   }
 
   // MatMul / Gemm whose weights were dequantised from int8 / uint8 and whose input was just quantised: QDense.  false: not that
@@ -2226,7 +2244,7 @@ struct Lowerer {
     const Step &ps = plan.steps[size_t(pit->second)];
     Quant xq;
     if (ps.kind == StepKind::FakeQuant) xq = ps.qx;
-    else if (ps.kind == StepKind::QDense && ps.qy.on) xq = ps.qy;
+    else if (quantised_layer(ps) && ps.qy.on) xq = ps.qy;
     else return false;
     const int64_t K = tB ? b.shape[1] : b.shape[0], M = tB ? b.shape[0] : b.shape[1];
     if (a.shape.back() != K) unsupported(n, "inner dimensions differ: " + shape_str(a.shape) + " x " + shape_str(b.shape));
@@ -2279,6 +2297,129 @@ struct Lowerer {
     set_quant(n, out, shape, 0, yq, true, false);
   }
 
+  // A QConv2d step over activation `a` (read from in_buf, quantised as xq) with the integer kernel `w` [M, C, kh, kw] (or [M, C, k])
+  Step make_qconv(const NodeDef &n, const Val &a, int in_buf, const TensorData &w, const std::vector<float> &ws, const std::vector<int64_t> &wz, const Quant &xq) {
+    Step s;
+    s.kind = StepKind::QConv2d;
+    s.in0 = in_buf;
+    conv_geometry(n, s, a, w.dims);
+    take_quant_weights(n, s, w, true, ws, wz, xq);  // [M, K] with k = (c, ky, kx) -> qW [K, M]
+    return s;
+  }
+
+  // Conv whose kernel was dequantised from int8 / uint8 (per tensor or per output channel) and whose input was just quantised: QConv2d.
+  // false: not that pattern (weight-only quantisation, a grouped or depthwise layer, scales along another axis) -- the float
+  // convolution on the dequantised kernel serves it
+  bool qconv_from_qdq(const NodeDef &n) {
+    const Val a = get(n, 0);
+    const Val &w = get(n, 1);
+    const TensorData &wt = *w.c;
+    if (a.ra != 0 || n.attr_i("group", 1) != 1) return false;
+    if (wt.q_data->elem != onnx::kUint8 && wt.q_data->elem != onnx::kInt8) return false;
+    if (wt.q_scale.size() > 1 && wt.q_axis != 0) return false;
+    // a BatchNormalization behind the layer folds into FLOAT weights (batchnorm()); it is not folded into integer ones
+    for (const NodeDef &c : m.nodes)
+      if (c.op == "BatchNormalization" && !c.inputs.empty() && c.inputs[0] == n.outputs[0]) return false;
+    auto pit = producer.find(a.buf);
+    if (pit == producer.end()) return false;
+    const Step &ps = plan.steps[size_t(pit->second)];
+    Quant xq;
+    if (ps.kind == StepKind::FakeQuant) xq = ps.qx;
+    else if (quantised_layer(ps) && ps.qy.on) xq = ps.qy;
+    else return false;
+    int in_buf = a.buf;
+    std::string head;
+    if (ps.kind == StepKind::FakeQuant) {  // the layer rounds its input itself (as QDense does)
+      in_buf = ps.in0;
+      head = ps.origin + "+";
+      if (sole_tail(a.buf)) drop_tail();
+    }
+    Step s = make_qconv(n, a, in_buf, *wt.q_data, wt.q_scale, wt.q_zp, xq);
+    if (has_input(n, 2)) {
+      const Val &c = get(n, 2);
+      if (int64_t(cf32(n, c).size()) != s.M) unsupported(n, "bias size mismatch");
+      qdense_take_bias(n, s, c);
+    }
+    const std::string origin = head + node_label(n);
+    const std::vector<int64_t> shape = conv_out_shape(s, a);
+    emit(std::move(s), n, shape).origin = origin;
+    return true;
+  }
+
+  // QLinearConv(x, x_scale, x_zp, w, w_scale, w_zp, y_scale, y_zp[, B]): QConv2d spelled in one node; its result stays a quantised value.
+  // A grouped / depthwise one keeps float semantics, as its QDQ spelling does: FakeQuant -> Conv2d on the dequantised kernel -> FakeQuant
+  void qlinear_conv(const NodeDef &n) {
+    if (n.inputs.size() < 8) bad_form(n, "needs at least its eight inputs (x, x_scale, x_zero_point, w, w_scale, w_zero_point, y_scale, y_zero_point)");
+    const Val a = get_raw(n, 0);
+    if (a.is_const || a.pv || !a.q) bad_form(n, "input x must be a quantised activation (the output of QuantizeLinear, QLinearConv or QLinearMatMul)");
+    const Quant xq = act_quant(n, quant_args(n, 1, 2, "input x's"), "input x");
+    if (!(xq == *a.q)) bad_form(n, "x_scale / x_zero_point differ from what input x was quantised with");
+    const Val &w = get(n, 3);
+    if (!w.is_const) bad_form(n, "input w must be a constant kernel");
+    const QArgs qw = quant_args(n, 4, 5, "weights'");
+    if (qw.elem != w.c->elem) bad_form(n, "the weights' zero point's element type differs from the data's");
+    const Quant yq = act_quant(n, quant_args(n, 6, 7, "output's"), "the output");
+    const bool one_d = a.shape.size() == 3 && w.shape.size() == 3;
+    if (a.ra != 0 || (a.shape.size() != 4 && !one_d)) bad_form(n, "input x must be [N,C,L] or [N,C,H,W]");
+    if (w.shape.size() != 4 && !one_d) bad_form(n, "the kernel must be [M,C/g,kh,kw] (or [M,C/g,k])");
+    if (w.c->elem != onnx::kUint8 && w.c->elem != onnx::kInt8) bad_form(n, "the weights have element type " + std::to_string(w.c->elem) + "; only uint8 and int8 are supported");
+    const int64_t M = w.shape[0];
+    if ((qw.scale.size() != 1 && int64_t(qw.scale.size()) != M)) bad_form(n, "the weights' scale must be one value or one per output channel");
+    std::vector<int64_t> bq;
+    if (has_input(n, 8)) {
+      const Val &b = get(n, 8);
+      if (!b.is_const) bad_form(n, "the bias B is not a constant");
+      if (b.c->elem != onnx::kInt32) bad_form(n, "the bias B has element type " + std::to_string(b.c->elem) + "; QLinearConv carries an int32 bias");
+      if (int64_t(b.c->i64.size()) != M) bad_form(n, "the bias B must have one value per output channel");
+      bq = b.c->i64;
+    }
+    if (n.attr_i("group", 1) == 1) {
+      Step s = make_qconv(n, a, a.buf, *w.c, qw.scale, qw.zp, xq);
+      s.qy = yq;
+      if (!bq.empty()) {
+        s.q_bias.assign(bq.begin(), bq.end());
+        qdense_check_k(n, s);
+      }
+      s.origin = node_label(n);
+      const std::vector<int64_t> shape = conv_out_shape(s, a);
+      set_quant(n, push_step(std::move(s), shape), shape, 0, yq, true, false);
+      return;
+    }
+    int in_buf = a.buf;
+    if (!a.q_done) {  // the values the float layer reads: what the quantisation in front leaves of x
+      Step f;
+      f.kind = StepKind::FakeQuant;
+      f.in0 = a.buf;
+      f.qx = xq;
+      f.origin = node_label(n) + "[input]";
+      in_buf = push_step(std::move(f), a.shape);
+    }
+    Step s;
+    s.kind = StepKind::Conv2d;
+    s.in0 = in_buf;
+    conv_geometry(n, s, a, w.shape);
+    s.W.resize(w.c->i64.size());
+    const int64_t per_m = s.K;
+    if (int64_t(w.c->i64.size()) != per_m * M) bad_form(n, "weight tensor " + shape_str(w.shape) + " does not match its data");
+    for (int64_t mo = 0; mo < M; mo++) {
+      const size_t qi = qw.scale.size() == 1 ? 0 : size_t(mo);
+      for (int64_t k = 0; k < per_m; k++) s.W[size_t(mo * per_m + k)] = float(w.c->i64[size_t(mo * per_m + k)] - qw.zp[qi]) * qw.scale[qi];
+    }
+    if (!bq.empty()) {
+      s.bias.resize(size_t(M));
+      for (int64_t mo = 0; mo < M; mo++) s.bias[size_t(mo)] = float(bq[size_t(mo)]) * (xq.scale * qw.scale[qw.scale.size() == 1 ? 0 : size_t(mo)]);
+    }
+    s.origin = node_label(n) + "[float]";
+    const std::vector<int64_t> shape = conv_out_shape(s, a);
+    const int conv_out = push_step(std::move(s), shape);
+    Step f;
+    f.kind = StepKind::FakeQuant;
+    f.in0 = conv_out;
+    f.qx = yq;
+    f.origin = node_label(n) + "[output]";
+    set_quant(n, push_step(std::move(f), shape), shape, 0, yq, true, false);
+  }
+
   // ------------------------------------------------------------------------------------------
   void lower_node(const NodeDef &n) {
     const std::string &op = n.op;
@@ -2292,14 +2433,15 @@ struct Lowerer {
     check_row_axis(n, reads_time_major.count(op) > 0);
     if (op == "DynamicQuantizeLinear")
       bad_form(n, "its scale spans all rows of a call, so a row's result would depend on its chunk; quantise statically (QuantizeLinear with constant scales)");
-    if (op != "DequantizeLinear" && op != "QLinearMatMul")
+    if (op != "DequantizeLinear" && op != "QLinearMatMul" && op != "QLinearConv")
       for (const auto &in_name : n.inputs) {
         auto it = vals.find(in_name);
-        if (it != vals.end() && it->second.q) bad_form(n, "it reads the quantised tensor '" + in_name + "'; only DequantizeLinear and QLinearMatMul do");
+        if (it != vals.end() && it->second.q) bad_form(n, "it reads the quantised tensor '" + in_name + "'; only DequantizeLinear, QLinearMatMul and QLinearConv do");
       }
     if (op == "QuantizeLinear") quantize_linear(n);
     else if (op == "DequantizeLinear") dequantize_linear(n);
     else if (op == "QLinearMatMul") qlinear_matmul(n);
+    else if (op == "QLinearConv") qlinear_conv(n);
     else if (op == "LSTM" || op == "GRU" || op == "RNN") recurrent(n);
     else if (op == "ConstantOfShape" || op == "Expand") constant_fill(n);
     else if (op == "MatMul") dense(n, false);
@@ -3208,7 +3350,17 @@ struct Lowerer {
         if (out.dims[i] > 0 && plan.output_shape[i] > 0 && out.dims[i] != plan.output_shape[i])
           throw InferaError::onnx("declared output shape " + shape_str(out.dims) + " conflicts with inferred " + shape_str(plan.output_shape));
     }
+    drop_unread_fake_quants();
     return std::move(plan);
+  }
+  // A FakeQuant whose every reader was a quantised layer that rounds its input itself (two convolutions of a residual block reading one
+  // tensor) is read by nothing: its step goes.  (One with a single such reader went when that reader was lowered, sole_tail.)
+  void drop_unread_fake_quants() {
+    std::set<int> read = {plan.out_buf};
+    for (const Step &s : plan.steps)
+      for (int b : {s.in0, s.in1, s.in2}) read.insert(b);
+    plan.steps.erase(std::remove_if(plan.steps.begin(), plan.steps.end(), [&](const Step &s) { return s.kind == StepKind::FakeQuant && !read.count(s.out); }),
+                     plan.steps.end());
   }
 };
 
@@ -3221,7 +3373,7 @@ double Plan::flops_per_row() const {
   for (const auto &s : steps) {
     if (s.kind == StepKind::Dense || s.kind == StepKind::QDense) f += 2.0 * double(s.rep) * double(s.K) * double(s.M);
     else if (s.kind == StepKind::Attention) f += 4.0 * double(s.attn_T) * double(s.attn_T) * double(s.attn_heads * s.attn_dh);
-    else if (s.kind == StepKind::Conv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
+    else if (s.kind == StepKind::Conv2d || s.kind == StepKind::QConv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
     else if (s.kind == StepKind::Recurrent) f += 2.0 * double(s.rnn->T * s.rnn->D * s.rnn->G * s.rnn->H) * double(s.rnn->F + s.rnn->H);
   }
@@ -3229,7 +3381,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -3245,7 +3397,7 @@ std::string Plan::describe_json() const {
     if (s.kind == StepKind::Dense && s.rep > 1) o << ",\"T\":" << s.rep;
     auto qtype = [](const Quant &q) { return !q.on ? "f32" : q.is_signed ? "int8" : "uint8"; };
     if (s.kind == StepKind::FakeQuant) o << ",\"type\":\"" << qtype(s.qx) << "\",\"scale\":" << double(s.qx.scale) << ",\"zero_point\":" << s.qx.zp;
-    if (s.kind == StepKind::QDense) {
+    if (s.kind == StepKind::QDense || s.kind == StepKind::QConv2d) {
       o << ",\"K\":" << s.K << ",\"M\":" << s.M << ",\"bias\":\"" << (!s.q_bias.empty() ? "int32" : !s.bias.empty() ? "f32" : "none") << "\",\"x_type\":\"" << qtype(s.qx)
         << "\",\"w_type\":\"" << (s.q_w_signed ? "int8" : "uint8") << "\",\"y_type\":\"" << qtype(s.qy) << "\",\"per_channel\":" << (s.q_per_channel ? "true" : "false");
       if (s.rep > 1) o << ",\"T\":" << s.rep;
@@ -3265,6 +3417,9 @@ std::string Plan::describe_json() const {
       o << ",\"T\":" << s.attn_T << ",\"heads\":" << s.attn_heads << ",\"dh\":" << s.attn_dh << ",\"scale\":" << double(s.attn_scale) << ",\"mask\":" << (s.cst.empty() ? "false" : "true")
         << ",\"packed_qkv\":" << (s.in0 == s.in1 && s.in1 == s.in2 ? "true" : "false");
     if (s.kind == StepKind::Conv2d) o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"k\":[" << s.kh << "," << s.kw << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
+    if (s.kind == StepKind::QConv2d)
+      o << ",\"C\":" << s.C << ",\"k\":[" << s.kh << "," << s.kw << "],\"strides\":[" << s.sh << "," << s.sw << "],\"pads\":[" << s.pt << "," << s.pl << "," << s.pb << "," << s.pr
+        << "],\"dilations\":[" << s.dh << "," << s.dw << "],\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
     if (s.kind == StepKind::TreeEnsemble || s.kind == StepKind::TreeReduce) {
       static const char *modes[] = {"scores", "label", "binary_scores", "binary_label"};
       const TreePack &t = *s.tree;

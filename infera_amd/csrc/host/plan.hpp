@@ -59,6 +59,7 @@ enum class StepKind : int {
   MeanTime = 23,      // out[r, e] = mean over t of in0[r, t, e]   (ReduceMean over the time axis of [rows, T = rep, K])
   FakeQuant = 24,     // y = (sat(rne(x / s) + zp) - zp) * s   (QuantizeLinear -> DequantizeLinear on an activation; Step::qx)
   QDense = 25,        // quantised MatMul / Gemm on the int8 matrix cores, f32 in and out (Step::qx, qy, qW ...; qdense.hip)
+  QConv2d = 26,       // quantised convolution (groups == 1): the QDense definition per output pixel, padding = real 0; the Conv2d geometry fields + the QDense quantisation fields (qconv.hip)
 };
 
 // Constant per-tensor quantisation of an activation: q = sat(rne(x / scale) + zp) in uint8 or int8
@@ -130,7 +131,8 @@ struct Step {
   float attn_scale = 1.f, ln_eps = 1e-5f;
   // FakeQuant: qx.  QDense: qx = how the f32 input is quantised, qy = how the result is (off: the step returns `real`, f32);
   // qW [K, M] = the weights as signed bytes (uint8 data shifted by 128), q_wzp[M] = their zero points shifted the same way, q_mult[M] =
-  // x_scale * w_scale[m] in f32, q_bias[M] = the int32 bias added to the accumulator (else `bias`: f32, added after the scaling)
+  // x_scale * w_scale[m] in f32, q_bias[M] = the int32 bias added to the accumulator (else `bias`: f32, added after the scaling).
+  // QConv2d: the same fields with K = C * kh * kw, M = Mo and row k = (c, ky, kx) of qW in ONNX order
   Quant qx, qy;
   std::vector<int8_t> qW;
   std::vector<int32_t> q_wzp, q_bias;

@@ -1805,3 +1805,403 @@ def quantized_reference(spec: dict, x: np.ndarray, mode: str = "int", weight_onl
     if tail and spec["tail"]:
         h = _tail_reference(h.astype(np.float64) if mode == "f64" else h, spec["tail"])
     return h.astype(f32)
+
+
+# ------------------------------------------------------------------------------------------
+# statically quantised convolutional nets (QDQ and QLinearConv spellings) and their numpy references
+# ------------------------------------------------------------------------------------------
+
+def _conv_taps(x, w, strides, pads, dilations, groups, fill):
+    """sum over (c, ky, kx) of x[n, c, oh * sh - pt + ky * dh, ...] * w[m, c, ky, kx], `fill` in the padding; x [N,C,H,W], w [M,C/g,kh,kw],
+    in the dtype of x (int64: exact)."""
+    n, c, h, wd = x.shape
+    m, cg, kh, kw = w.shape
+    (sh, sw), (pt, pl, pb, pr), (dh, dw) = strides, pads, dilations
+    xp = np.full((n, c, h + pt + pb, wd + pl + pr), fill, x.dtype)
+    xp[:, :, pt:pt + h, pl:pl + wd] = x
+    oh = (h + pt + pb - (dh * (kh - 1) + 1)) // sh + 1
+    ow = (wd + pl + pr - (dw * (kw - 1) + 1)) // sw + 1
+    out = np.zeros((n, m, oh, ow), x.dtype)
+    mg = m // groups
+    for g in range(groups):
+        for ky in range(kh):
+            for kx in range(kw):
+                xs = xp[:, g * cg:(g + 1) * cg, ky * dh:ky * dh + (oh - 1) * sh + 1:sh, kx * dw:kx * dw + (ow - 1) * sw + 1:sw]
+                out[:, g * mg:(g + 1) * mg] += np.einsum("nchw,mc->nmhw", xs, w[g * mg:(g + 1) * mg, :, ky, kx], optimize=True)
+    return out
+
+
+def _max_pool(x, k, s, p):
+    n, c, h, wd = x.shape
+    xp = np.full((n, c, h + 2 * p, wd + 2 * p), -np.inf, x.dtype)
+    xp[:, :, p:p + h, p:p + wd] = x
+    oh, ow = (h + 2 * p - k) // s + 1, (wd + 2 * p - k) // s + 1
+    out = np.full((n, c, oh, ow), -np.inf, x.dtype)
+    for ky in range(k):
+        for kx in range(k):
+            out = np.maximum(out, xp[:, :, ky:ky + (oh - 1) * s + 1:s, kx:kx + (ow - 1) * s + 1:s])
+    return out
+
+
+class _QConvBuilder:
+    """Builds the op list of a quantized_conv_spec while it runs the float network on the calibration images (ranges -> scales)."""
+
+    def __init__(self, in_shape, x_type, w_type, per_channel, w_zero_points, seed, calib_rows, x_zero_point=None, x_range=1.0):
+        from .synth import table
+        self.x_type, self.w_type, self.per_channel, self.w_zero_points = x_type, w_type, per_channel, w_zero_points
+        self.ws = _WeightStream(seed)
+        self.one_d = len(in_shape) == 2
+        shape4 = (in_shape[0], 1, in_shape[1]) if self.one_d else tuple(in_shape)
+        h = (x_range * table(seed + 1, 0, calib_rows, int(np.prod(in_shape)))).astype(np.float64).reshape((calib_rows,) + shape4)
+        q = _calibrate(h.min(), h.max(), x_type)
+        if x_zero_point is not None:
+            q = (q[0], int(x_zero_point))
+        self.val = {"X": h}   # float activations of the calibration images
+        self.q = {"X": q}     # (scale, zero point) of every value
+        self.ops = []
+        self.in_shape = list(in_shape)
+
+    def _quant_weights(self, w):
+        """w [M, ...] float64 -> wq, w_scale[M or 1], w_zp[M or 1] (per output channel = axis 0)"""
+        wmin, wmax = _qrange(self.w_type)
+        rows = w.reshape(w.shape[0], -1) if self.per_channel else w.reshape(1, -1)
+        if self.w_zero_points:
+            lo, hi = np.minimum(rows.min(1), 0), np.maximum(rows.max(1), 0)
+            w_scale = (np.maximum(hi - lo, 1e-6) / (wmax - wmin)).astype(np.float32)
+            w_zp = np.clip(np.rint(wmin - lo / w_scale), wmin, wmax).astype(np.int64)
+        else:
+            w_scale = (np.maximum(np.abs(rows).max(1), 1e-6) / 127.0).astype(np.float32)
+            w_zp = np.full(w_scale.shape, 0 if self.w_type == "int8" else 128, np.int64)
+        bshape = (-1,) + (1,) * (w.ndim - 1)
+        wq = np.clip(np.rint(w / w_scale.astype(np.float64).reshape(bshape)) + w_zp.reshape(bshape), wmin, wmax).astype(np.int64)
+        return wq, w_scale, w_zp
+
+    def _bias(self, op, b, xs, bias):
+        m = b.shape[0]
+        op["bias_q"] = op["bias_f"] = None
+        if bias == "int32":
+            op["bias_scale"] = (np.float32(xs) * op["w_scale"]).astype(np.float32)  # the f32 product, as the loader forms it
+            op["bias_q"] = np.rint(b / np.broadcast_to(op["bias_scale"].astype(np.float64), (m,))).astype(np.int64)
+            return op["bias_q"] * np.broadcast_to(op["bias_scale"].astype(np.float64), (m,))
+        if bias == "f32":
+            op["bias_f"] = b.astype(np.float32)
+            return op["bias_f"].astype(np.float64)
+        return np.zeros(m)
+
+    def conv(self, src, out, m, k, stride=1, pads=0, dilation=1, groups=1, act="", bias="int32", weights=None):
+        h = self.val[src]
+        c = h.shape[1]
+        kh, kw = (1, k) if self.one_d and np.isscalar(k) else ((k, k) if np.isscalar(k) else tuple(k))
+        pair = lambda v: (1, v) if self.one_d and np.isscalar(v) else ((v, v) if np.isscalar(v) else tuple(v))  # noqa: E731
+        strides, dil = pair(stride), pair(dilation)
+        pads = (0, pads, 0, pads) if self.one_d and np.isscalar(pads) else ((pads,) * 4 if np.isscalar(pads) else tuple(pads))
+        fan = c // groups * kh * kw
+        if weights is None:
+            w = self.ws.take((m, c // groups, kh, kw), fan).astype(np.float64)
+            b = self.ws.take((m,), fan).astype(np.float64)
+        else:
+            w, b = (np.asarray(a, np.float64) for a in weights)
+        wq, w_scale, w_zp = self._quant_weights(w)
+        op = {"op": "conv", "in": src, "out": out, "wq": wq, "w_scale": w_scale, "w_zp": w_zp, "strides": strides, "pads": pads, "dilations": dil,
+              "group": groups, "act": act}
+        bf = self._bias(op, b, self.q[src][0], bias)
+        bshape = (-1, 1, 1, 1)
+        wd = (wq - w_zp.reshape(bshape)) * w_scale.astype(np.float64).reshape(bshape)
+        y = _float_act(_conv_taps(h, wd, strides, pads, dil, groups, 0.0) + bf.reshape(1, -1, 1, 1), act)
+        self._finish(op, out, y)
+
+    def _finish(self, op, out, y):
+        self.val[out] = y
+        self.q[out] = _calibrate(y.min(), y.max(), self.x_type)
+        self.ops.append(op)
+
+    def maxpool(self, src, out, k, s, p):
+        self.val[out], self.q[out] = _max_pool(self.val[src], k, s, p), self.q[src]
+        self.ops.append({"op": "maxpool", "in": src, "out": out, "k": k, "s": s, "p": p})
+
+    def add(self, a, b, out, act="Relu"):
+        self._finish({"op": "add", "in": [a, b], "out": out, "act": act}, out, _float_act(self.val[a] + self.val[b], act))
+
+    def gmaxpool(self, src, out):
+        self.val[out], self.q[out] = self.val[src].max(axis=(2, 3)), self.q[src]
+        self.ops.append({"op": "gmaxpool", "in": src, "out": out})
+
+    def gemm(self, src, out, m):
+        h = self.val[src]
+        k = h.shape[1]
+        w = self.ws.take((m, k), k).astype(np.float64)
+        wq, w_scale, w_zp = self._quant_weights(w)
+        op = {"op": "gemm", "in": src, "out": out, "wq": wq, "w_scale": w_scale, "w_zp": w_zp, "bias_q": None, "bias_f": None, "act": ""}
+        self._finish(op, out, h @ ((wq - w_zp[:, None]) * w_scale.astype(np.float64)[:, None]).T)
+
+    def spec(self, name):
+        out = self.ops[-1]["out"]
+        shape = list(self.val[out].shape[1:])
+        if self.one_d and len(shape) == 3:
+            shape = [shape[0], shape[2]]
+        return {"name": name, "x_type": self.x_type, "w_type": self.w_type, "per_channel": self.per_channel, "in_shape": self.in_shape, "out_shape": shape,
+                "ops": self.ops, "q": self.q, "out": out}
+
+
+def quantized_conv_spec(kind: str = "layer", in_shape: Sequence[int] = (3, 9, 9), m: int = 8, k=3, stride=1, pads=0, dilation=1, groups: int = 1, act="Relu",
+                        bias: str | None = "int32", pooled: bool = False, x_type: str = "uint8", w_type: str = "int8", per_channel: bool = True,
+                        w_zero_points: bool = False, x_zero_point: int | None = None, seed: int = 1234, calib_rows: int = 4, width: int = 8,
+                        classes: int = 10, x_range: float = 1.0) -> dict:
+    """A convolutional net quantised the way ONNX Runtime's quantize_static does (weights per tensor or per output channel, activations
+    per tensor from the float net's ranges on `calib_rows` images of the synthetic table).
+    kind "layer": ONE convolution [N] + in_shape ([C,H,W], or [C,L]: Conv1d) -> m channels (k, stride, pads, dilation: a number or one
+      per axis, pads (top, left, bottom, right)); pooled: GlobalMaxPool -> Flatten behind it (the served output is [N, m]).
+    kind "resnet": stem conv -> MaxPool 3x3/2 -> two basic blocks (the second with stride 2 and a 1x1 projection) -> GlobalMaxPool ->
+      Flatten -> Gemm; `width` channels, 2 * width after the second block.
+    kind "resnet18": the topology of resnet18() with BatchNormalization folded into the convolutions (as quantisers do first) and a
+      global MAX pool, `width` channels in the first stage.
+    spec["ops"]: the operations in order; spec["q"][name] = (scale, zero point) of every value."""
+    assert x_type in ("int8", "uint8") and w_type in ("int8", "uint8") and bias in ("int32", "f32", None)
+    b = _QConvBuilder(in_shape, x_type, w_type, per_channel, w_zero_points, seed, calib_rows, x_zero_point, x_range)
+    if kind == "layer":
+        b.conv("X", "C0", m, k, stride, pads, dilation, groups, act, bias)
+        if pooled:
+            b.gmaxpool("C0", "P0")
+        return b.spec("qconv_layer")
+    assert len(in_shape) == 3
+
+    def block(x, cout, stride, tag):
+        cin = b.val[x].shape[1]
+        b.conv(x, tag + "a", cout, 3, stride, 1, act="Relu")
+        b.conv(tag + "a", tag + "b", cout, 3, 1, 1, act="")
+        sc = x
+        if stride != 1 or cin != cout:
+            b.conv(x, tag + "p", cout, 1, stride, 0, act="")
+            sc = tag + "p"
+        b.add(tag + "b", sc, tag)
+        return tag
+
+    if kind == "resnet":
+        b.conv("X", "stem", width, 3, 1, 1, act="Relu")
+        b.maxpool("stem", "pool", 3, 2, 1)
+        x = block(block("pool", width, 1, "b1"), 2 * width, 2, "b2")
+    else:
+        assert kind == "resnet18"
+        ws, eps = b.ws, 1e-5
+        orig_conv = b.conv
+
+        def conv_bn(src, out, mo, kk, stride=1, pads=0, dilation=1, groups=1, act="", bias="int32", weights=None):  # resnet18()'s stream, folded
+            cin = b.val[src].shape[1]
+            w = ws.take((mo, cin, kk, kk), cin * kk * kk).astype(np.float64)
+            scale, beta, mean = 1.0 + 0.1 * ws.take((mo,), 1), 0.1 * ws.take((mo,), 1), 0.1 * ws.take((mo,), 1)
+            var = 1.0 + 0.5 * np.abs(ws.take((mo,), 1))
+            f = scale.astype(np.float64) / np.sqrt(var.astype(np.float64) + eps)
+            orig_conv(src, out, mo, kk, stride, pads, act=act, weights=(w * f[:, None, None, None], beta - mean * f))
+        b.conv = conv_bn
+        b.conv("X", "stem", width, 7, 2, 3, act="Relu")
+        b.maxpool("stem", "pool", 3, 2, 1)
+        x, i = "pool", 0
+        for stage, cout in enumerate([width, width * 2, width * 4, width * 8]):
+            for blk in range(2):
+                i += 1
+                x = block(x, cout, 2 if (stage > 0 and blk == 0) else 1, f"b{i}")
+    b.gmaxpool(x, "gp")
+    b.gemm("gp", "fc", classes)
+    return b.spec("qconv_" + kind)
+
+
+def quantized_conv_from_spec(spec: dict, form: str = "qdq", weight_only: bool = False, batch: int | str = "N") -> bytes:
+    """A quantized_conv_spec net as a QDQ graph (QuantizeLinear / DequantizeLinear around float Conv / MaxPool / Add / Gemm nodes) or in the
+    QOperator spelling (form="qlinear": QLinearConv / QLinearMatMul on quantised tensors; MaxPool, the residual Add and the global pool
+    between DequantizeLinear and QuantizeLinear; an int32 bias or none, and only activations the output range already applies).
+    weight_only (QDQ): only the weights are quantised."""
+    xt, wt = _np_qtype(spec["x_type"]), _np_qtype(spec["w_type"])
+    qmin = _qrange(spec["x_type"])[0]
+    q = spec["q"]
+    nodes, inits, made = [], [], set()
+    one_d = len(spec["in_shape"]) == 2
+    fname, qname = {"X": "X"}, {}   # value -> the float tensor / the quantised tensor that holds it
+
+    def const(name, arr):
+        if name not in made:
+            made.add(name)
+            inits.append(tensor(name, arr))
+        return name
+
+    def qparams(v):
+        return const(f"{v}_scale", np.array(q[v][0], np.float32)), const(f"{v}_zp", np.array(q[v][1], xt))
+
+    def quantise(v):  # the quantised tensor of value v
+        if v not in qname:
+            nodes.append(node("QuantizeLinear", [fname[v], *qparams(v)], [f"{v}_q"], name=f"quant_{v}"))
+            qname[v] = f"{v}_q"
+        return qname[v]
+
+    def dequantise(v, raw=None):  # the float tensor of value v (raw: the float tensor BEFORE its quantisation)
+        if raw is not None:
+            fname[v] = raw
+            if weight_only:
+                return raw
+            qname.pop(v, None)
+            del fname[v]
+            nodes.append(node("QuantizeLinear", [raw, *qparams(v)], [f"{v}_q"], name=f"quant_{v}"))
+            qname[v] = f"{v}_q"
+        if v not in fname:
+            nodes.append(node("DequantizeLinear", [qname[v], *qparams(v)], [f"{v}_dq"], name=f"dequant_{v}"))
+            fname[v] = f"{v}_dq"
+        return fname[v]
+
+    def wparams(o, op):
+        pc = spec["per_channel"]
+        return (const(f"{o}_w_scale", op["w_scale"].astype(np.float32) if pc else np.array(op["w_scale"][0], np.float32)),
+                const(f"{o}_w_zp", op["w_zp"].astype(wt) if pc else np.array(op["w_zp"][0], wt)))
+
+    def conv_attrs(op):
+        if one_d:
+            return [attr_ints("kernel_shape", [op["wq"].shape[3]]), attr_ints("strides", [op["strides"][1]]), attr_ints("pads", [op["pads"][1], op["pads"][3]]),
+                    attr_ints("dilations", [op["dilations"][1]]), attr_i("group", op["group"])]
+        return [attr_ints("kernel_shape", list(op["wq"].shape[2:])), attr_ints("strides", list(op["strides"])), attr_ints("pads", list(op["pads"])),
+                attr_ints("dilations", list(op["dilations"])), attr_i("group", op["group"])]
+
+    def activation(op, cur, o):
+        if op["act"] == "Relu":
+            nodes.append(node("Relu", [cur], [f"{o}_act"], name=f"relu_{o}"))
+            return f"{o}_act"
+        if op["act"]:
+            lo, hi = const(f"{o}_lo", np.array(op["act"][1], np.float32)), const(f"{o}_hi", np.array(op["act"][2], np.float32))
+            nodes.append(node("Clip", [cur, lo, hi], [f"{o}_act"], name=f"clip_{o}"))
+            return f"{o}_act"
+        return cur
+
+    if form == "qdq" and not weight_only:
+        dequantise("X", raw="X")
+    for op in spec["ops"]:
+        o, kind = op["out"], op["op"]
+        if kind in ("conv", "gemm"):
+            wq = op["wq"][:, :, 0, :] if one_d and kind == "conv" else op["wq"]
+            if form == "qlinear":
+                if op["bias_f"] is not None:
+                    raise ValueError("QLinearConv carries an int32 bias")
+                if op["act"] and not (op["act"] == "Relu" and q[o][1] == qmin):
+                    raise ValueError("the QLinear spelling cannot express activation %r before zero point %d" % (op["act"], q[o][1]))
+                src = op["in"]
+                xq = quantise(src)
+                if kind == "conv":
+                    ins = [xq, *qparams(src), const(f"{o}_w", wq.astype(wt)), *wparams(o, op), *qparams(o)]
+                    if op["bias_q"] is not None:
+                        ins.append(const(f"{o}_b", op["bias_q"].astype(np.int32)))
+                    nodes.append(node("QLinearConv", ins, [f"{o}_q"], conv_attrs(op), name=f"qconv_{o}"))
+                else:
+                    ins = [xq, *qparams(src), const(f"{o}_w", np.ascontiguousarray(wq.T).astype(wt)), *wparams(o, op), *qparams(o)]
+                    nodes.append(node("QLinearMatMul", ins, [f"{o}_q"], name=f"qmm_{o}"))
+                qname[o] = f"{o}_q"
+                continue
+            src = dequantise(op["in"])
+            ws_, wz_ = wparams(o, op)
+            nodes.append(node("DequantizeLinear", [const(f"{o}_w", wq.astype(wt)), ws_, wz_], [f"{o}_w_dq"], [attr_i("axis", 0)], name=f"dequant_w_{o}"))
+            ins = [src, f"{o}_w_dq"]
+            if op["bias_q"] is not None and not weight_only:
+                bs = op["bias_scale"]
+                const(f"{o}_b_scale", bs.astype(np.float32) if bs.size > 1 else np.array(bs.reshape(-1)[0], np.float32))
+                const(f"{o}_b_zp", np.zeros(bs.shape if bs.size > 1 else (), np.int32))
+                nodes.append(node("DequantizeLinear", [const(f"{o}_b", op["bias_q"].astype(np.int32)), f"{o}_b_scale", f"{o}_b_zp"], [f"{o}_b_dq"],
+                                  [attr_i("axis", 0)], name=f"dequant_b_{o}"))
+                ins.append(f"{o}_b_dq")
+            elif op["bias_q"] is not None or op["bias_f"] is not None:
+                bf = op["bias_f"] if op["bias_f"] is not None else (op["bias_q"] * np.broadcast_to(op["bias_scale"], op["bias_q"].shape)).astype(np.float32)
+                ins.append(const(f"{o}_b", bf.astype(np.float32)))
+            if kind == "conv":
+                nodes.append(node("Conv", ins, [f"{o}_raw"], conv_attrs(op), name=f"conv_{o}"))
+            else:
+                nodes.append(node("Gemm", ins, [f"{o}_raw"], [attr_i("transB", 1)], name=f"gemm_{o}"))
+            dequantise(o, raw=activation(op, f"{o}_raw", o))
+        elif kind == "maxpool":
+            nodes.append(node("MaxPool", [dequantise(op["in"])], [f"{o}_raw"], [attr_ints("kernel_shape", [op["k"]] * 2), attr_ints("strides", [op["s"]] * 2),
+                                                                               attr_ints("pads", [op["p"]] * 4)], name=f"pool_{o}"))
+            if form == "qdq":
+                dequantise(o, raw=f"{o}_raw")
+            else:
+                fname[o] = f"{o}_raw"
+        elif kind == "add":
+            nodes.append(node("Add", [dequantise(op["in"][0]), dequantise(op["in"][1])], [f"{o}_sum"], name=f"add_{o}"))
+            raw = activation(op, f"{o}_sum", o)
+            if form == "qdq":
+                dequantise(o, raw=raw)
+            else:
+                fname[o] = raw
+                quantise(o)
+                del fname[o]
+        elif kind == "gmaxpool":
+            nodes.append(node("GlobalMaxPool", [dequantise(op["in"])], [f"{o}_gp"], name=f"gpool_{o}"))
+            nodes.append(node("Flatten", [f"{o}_gp"], [f"{o}_flat"], [attr_i("axis", 1)], name=f"flatten_{o}"))
+            fname[o] = f"{o}_flat"
+            if form == "qdq" and o != spec["out"]:
+                dequantise(o, raw=f"{o}_flat")
+    nodes.append(node("Identity", [dequantise(spec["out"])], ["Y"], name="served"))
+    return model(spec["name"], nodes, inits, [value_info("X", [batch] + list(spec["in_shape"]))], [value_info("Y", [batch] + list(spec["out_shape"]))], opset=13)
+
+
+def quantized_conv_reference(spec: dict, x: np.ndarray, mode: str = "int", weight_only: bool = False) -> np.ndarray:
+    """What a quantized_conv_spec net computes on x [N] + in_shape.  "int": the QConv2d / QDense definition step by
+    step -- f32 scalars, an int64 accumulator checked to fit int32, padding = the zero point, the residual Add one f32 addition of two
+    dequantised values followed by its FakeQuant; grouped convolutions in float32 on the dequantised values (their float fallback).
+    "f64": the QDQ graph evaluated in float64 (weight_only: with only its weights quantised)."""
+    f32 = np.float32
+    qmin, qmax = _qrange(spec["x_type"])
+    q = spec["q"]
+    one_d = len(spec["in_shape"]) == 2
+    x = np.asarray(x, f32)
+    x = x.reshape((x.shape[0],) + ((spec["in_shape"][0], 1, spec["in_shape"][1]) if one_d else tuple(spec["in_shape"])))
+    ft = f32 if mode == "int" else np.float64
+    assert mode in ("int", "f64")
+
+    def fq(h, v):
+        if weight_only:
+            return h
+        s, z = ft(q[v][0]), ft(q[v][1])
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            return ((np.clip(np.rint(h / s) + z, ft(qmin), ft(qmax)) - z) * s).astype(ft)
+
+    def bshape(op):
+        return (1, -1, 1, 1) if op["op"] == "conv" else (1, -1)
+
+    def float_layer(op, h):
+        wb = (-1, 1, 1, 1) if op["op"] == "conv" else (-1, 1)
+        w = ((op["wq"] - op["w_zp"].reshape(wb)).astype(ft) * op["w_scale"].astype(ft).reshape(wb)).astype(ft)
+        y = _conv_taps(h, w, op["strides"], op["pads"], op["dilations"], op["group"], ft(0)) if op["op"] == "conv" else (h @ w.T).astype(ft)
+        if op["bias_q"] is not None:
+            y = (y + (op["bias_q"].astype(ft) * np.broadcast_to(op["bias_scale"], op["bias_q"].shape).astype(ft)).reshape(bshape(op))).astype(ft)
+        elif op["bias_f"] is not None:
+            y = (y + op["bias_f"].astype(ft).reshape(bshape(op))).astype(ft)
+        return _float_act(y, op["act"]).astype(ft)
+
+    def int_layer(op, h):
+        src, o = op["in"], op["out"]
+        xs, xz, ys, yz = f32(q[src][0]), q[src][1], f32(q[o][0]), q[o][1]
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            xq = np.clip(np.rint(h / xs) + f32(xz), f32(qmin), f32(qmax)).astype(np.int64)
+            wb = (-1, 1, 1, 1) if op["op"] == "conv" else (-1, 1)
+            wz = op["wq"] - op["w_zp"].reshape(wb)
+            acc = _conv_taps(xq - xz, wz, op["strides"], op["pads"], op["dilations"], 1, 0) if op["op"] == "conv" else (xq - xz) @ wz.T
+            if op["bias_q"] is not None:
+                acc = acc + op["bias_q"].reshape(bshape(op))
+            assert np.abs(acc).max(initial=0) < 2 ** 31
+            real = acc.astype(f32) * (xs * op["w_scale"]).astype(f32).reshape(bshape(op))
+            if op["bias_f"] is not None:
+                real = (real + op["bias_f"].astype(f32).reshape(bshape(op))).astype(f32)
+            real = _float_act(real, op["act"]).astype(f32)
+            qq = np.clip(np.rint(real / ys) + f32(yz), f32(qmin), f32(qmax))
+            return ((qq - f32(yz)) * ys).astype(f32)
+
+    val = {"X": x if mode == "int" else fq(x.astype(ft), "X")}
+    for op in spec["ops"]:
+        o, kind = op["out"], op["op"]
+        if kind in ("conv", "gemm"):
+            h = val[op["in"]]
+            if mode == "int" and (kind == "gemm" or op["group"] == 1):
+                val[o] = int_layer(op, h)
+            else:  # (in "int" mode: a grouped layer's float fallback, on the values its input quantisation leaves)
+                val[o] = fq(float_layer(op, fq(h, op["in"]) if mode == "int" else h), o)
+        elif kind == "maxpool":
+            val[o] = _max_pool(val[op["in"]], op["k"], op["s"], op["p"])
+        elif kind == "add":
+            val[o] = fq(_float_act((val[op["in"][0]] + val[op["in"][1]]).astype(ft), op["act"]).astype(ft), o)
+        elif kind == "gmaxpool":
+            val[o] = val[op["in"]].max(axis=(2, 3))
+    out = val[spec["out"]].astype(f32)
+    return out.reshape((out.shape[0],) + tuple(spec["out_shape"]))
