@@ -110,6 +110,8 @@ class LoadedModel {
   std::vector<char> stem_split6;  // ConvPatch + fused MaxPool steps that run conv2d_stem_split6 (same arithmetic)
   // QDense steps whose input / output buffer holds quantised bytes instead of the f32 values they stand for (schedule.cpp byte_buffers)
   std::vector<char> q_in_bytes, q_out_bytes;
+  // HDense steps whose input / output buffer holds halves instead of f32 values (schedule.cpp half_buffers)
+  std::vector<char> h_in_half, h_out_half;
   std::vector<int> slot_of_buf;        // scratch slot per activation buffer (-1: external in/out)
   std::vector<int64_t> slot_per_row;   // floats per row of each scratch slot
   int64_t scratch_per_row = 0;         // sum over slots

@@ -40,6 +40,12 @@ __global__ __launch_bounds__(kBlock) void fake_quant_kernel(const float *__restr
   for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) y[i] = (quantise(x[i], scale, zp, lo, hi) - zp) * scale;  // (a difference times a scale: nothing to contract)
 }
 
+// y = float(half_rne(x)): v_cvt_f16_f32 rounds to nearest even and keeps subnormal halves (the packed convert, cvt_pkrtz, truncates)
+__global__ __launch_bounds__(kBlock) void round_half_kernel(const float *__restrict__ x, float *__restrict__ y, int64_t n) {
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += stride) y[i] = float(_Float16(x[i]));
+}
+
 __global__ __launch_bounds__(kBlock) void binary_const_kernel(const float *__restrict__ x, const float *__restrict__ c,
                                                              float *__restrict__ y, int64_t n, int64_t per_row, char op,
                                                              bool const_left, ActParam act) {
@@ -396,6 +402,11 @@ void unary(hipStream_t s, const float *x, float *y, int64_t n, ActParam act) {
 void fake_quant(hipStream_t s, const float *x, float *y, int64_t n, float scale, int zp, int qmin, int qmax) {
   if (n <= 0) return;
   hipLaunchKernelGGL(fake_quant_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, x, y, n, scale, float(zp), float(qmin), float(qmax));
+}
+
+void round_half(hipStream_t s, const float *x, float *y, int64_t n) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(round_half_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, x, y, n);
 }
 
 void binary_const(hipStream_t s, const float *x, const float *c, float *y, int64_t rows, int64_t per_row, char op,

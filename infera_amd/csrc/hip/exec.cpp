@@ -284,6 +284,21 @@ void PassRunner::launch_plain(size_t i) {
       kern::qdense(stream, q);
       break;
     }
+    case StepKind::RoundHalf: kern::round_half(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)]); break;
+    case StepKind::HDense: {  // (model.cpp upload_hdense: W = the weight fragments, bias = the widened half bias)
+      kern::HDenseLaunch h;
+      h.X = buf(x.in0);
+      h.Y = buf(x.out);
+      h.Wp = d.W;
+      h.bias = d.bias;
+      h.rows = nr * x.rep;
+      h.K = int(x.K), h.M = int(x.M);
+      h.bias_mode = x.h_bias_mode;
+      h.act = int(x.act), h.act_a = x.act_a, h.act_b = x.act_b;
+      h.in_half = m.h_in_half[i] != 0, h.out_half = m.h_out_half[i] != 0;
+      kern::hdense(stream, h);
+      break;
+    }
     case StepKind::QConv2d: {  // (the same device-step slots as QDense: model.cpp upload_qconv)
       kern::QConvLaunch q = qconv_launch(x);
       q.X = buf(x.in0);

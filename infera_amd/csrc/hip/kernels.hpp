@@ -20,6 +20,8 @@ struct ActParam {
 void unary(hipStream_t s, const float *x, float *y, int64_t n, ActParam act);
 // y = (sat(rne(x / scale) + zp) - zp) * scale with the range [qmin, qmax]   (QuantizeLinear -> DequantizeLinear)
 void fake_quant(hipStream_t s, const float *x, float *y, int64_t n, float scale, int zp, int qmin, int qmax);
+// y = float(half_rne(x)): the IEEE binary16 conversion (ties to even, subnormal halves kept, |x| >= 65520 -> +-inf, NaN stays NaN)
+void round_half(hipStream_t s, const float *x, float *y, int64_t n);
 // y[r, i] = act(x[r, i] (op) c[i])   (const_left: c (op) x)
 void binary_const(hipStream_t s, const float *x, const float *c, float *y, int64_t rows, int64_t per_row, char op,
                   bool const_left, ActParam act);
@@ -160,6 +162,28 @@ size_t qconv_packed_floats(int C, int taps, int M);
 void qconv_pack(int C, int taps, int M, const int8_t *W, float *packed);  // W: [K, M] signed bytes, k = (c, tap)
 bool qconv_stages_in_lds(QConvLaunch p);  // does the launch stage its quantised input window in LDS (else: per tap from global memory)
 void qconv(hipStream_t s, QConvLaunch p);
+
+// ---- float16 dense layer, f16 MFMA (hdense.hip) -----------------------------------------------
+// One HDense step (host/plan.hpp) over `rows` rows.  X: f32 [rows, K] (rounded to half on load), or (in_half) halves; Y: f32 [rows, M]
+// holding half values, or (out_half) the halves themselves.  Wp = hdense_pack() of the weights' bit patterns; bias = the half bias widened
+// to f32, hdense_padded_m(M) entries (bias_mode = plan.hpp HalfBias: 0 none, 1 Gemm, 2 MatMul -> Add).
+struct HDenseLaunch {
+  const void *X = nullptr;
+  void *Y = nullptr;
+  const float *Wp = nullptr, *bias = nullptr;
+  int64_t rows = 0;
+  int K = 0, M = 0;
+  int bias_mode = 0;
+  int act = 0;  // plan.hpp Act: None, Relu, Sigmoid, Tanh, LeakyRelu(a) or Clip(a, b)
+  float act_a = 0.f, act_b = 0.f;
+  bool in_half = false, out_half = false;
+  int KT = 0, MTp = 0;  // (set by the launcher)
+  bool x_vec = false, y_vec = false;
+};
+int hdense_padded_m(int M);
+size_t hdense_packed_floats(int K, int M);
+void hdense_pack(int K, int M, const uint16_t *W, float *packed);  // W: [K, M] half bit patterns
+void hdense(hipStream_t s, HDenseLaunch p);
 
 // ---- whole-chain fused MLP (mlp_fused.hip) -----------------------------------------------------
 // A chain D0 -> D1 -> D2 -> D3 evaluated in one persistent kernel; activations never leave

@@ -165,6 +165,19 @@ void upload_qconv(const Step &s, DeviceStep &d, hipStream_t us) {
   d.W = upload(packed, us);
   upload_quant_tables(s, d, kern::qconv_padded_m(int(s.M)), us);
 }
+// An HDense step (hip/hdense.hip): W = the weight fragments (half bit patterns), bias = the half bias widened to f32 and padded
+void upload_hdense(const Step &s, DeviceStep &d, hipStream_t us) {
+  const int K = int(s.K), M = int(s.M);
+  std::vector<float> packed(kern::hdense_packed_floats(K, M));
+  kern::hdense_pack(K, M, s.hW.data(), packed.data());
+  d.W = upload(packed, us);
+  if (s.h_bias_mode != kHalfBiasNone) {
+    std::vector<float> b(size_t(kern::hdense_padded_m(M)), 0.f);
+    for (size_t j = 0; j < s.h_bias.size(); j++) b[j] = onnx::half_to_float(s.h_bias[j]);
+    d.bias = upload(b, us);
+  }
+}
+
 // mult, c0, wz and the f32 bias of a QDense / QConv2d step, each padded to Mp entries
 void upload_quant_tables(const Step &s, DeviceStep &d, int Mp, hipStream_t us) {
   const int K = int(s.K), M = int(s.M);
@@ -256,6 +269,10 @@ void upload_to_device(const LoadedModel &m, DeviceModel &dm) {
       }
       default:
         if (upload_ml_tables(s, d, us)) continue;
+        if (s.kind == StepKind::HDense) {
+          upload_hdense(s, d, us);
+          continue;
+        }
         if (s.kind == StepKind::QDense) {
           upload_qdense(s, d, us);
           continue;

@@ -67,6 +67,7 @@ struct Scheduler {
   void choose_conv_arithmetic();     // bf16 x three exact parts (default) or exact fp32
   void fold_projection_shortcuts();  // a block's 1x1 shortcut as extra K stages of its second convolution
   void byte_buffers();               // QDense -> QDense edges that carry the quantised bytes
+  void half_buffers();               // HDense -> HDense edges that carry halves
   void classify_io(const std::vector<EffStep> &eff);   // may the result be stored into pinned memory, the input be read from it / column-major?
   void place_scratch(const std::vector<EffStep> &eff); // scratch slots by liveness
 };
@@ -189,7 +190,8 @@ void Scheduler::decide_layout() {
   m.nchw_buf.assign(m.plan.buf_shape.size(), 0);
   m.nchw_buf[0] = 1;
   auto elementwise = [](const Step &s) {
-    return s.kind == StepKind::Unary || s.kind == StepKind::BinaryConst || s.kind == StepKind::AffineChannel || s.kind == StepKind::FakeQuant;
+    return s.kind == StepKind::Unary || s.kind == StepKind::BinaryConst || s.kind == StepKind::AffineChannel || s.kind == StepKind::FakeQuant ||
+           s.kind == StepKind::RoundHalf;
   };
   auto convolution = [](const Step &s) { return s.kind == StepKind::Conv2d || s.kind == StepKind::QConv2d; };
   for (const auto &s : st)
@@ -197,8 +199,8 @@ void Scheduler::decide_layout() {
   for (const auto &s : st) {
     any_conv = any_conv || convolution(s);
     // (CopyCols = channel concat: a contiguous per-row block in NCHW and in channel-quad planes alike)
-    // (FakeQuant: elementwise with one scale per tensor, the same bits in either layout; QConv2d reads and writes either, qconv.hip)
-    const bool layout_free = convolution(s) || s.kind == StepKind::FakeQuant || s.kind == StepKind::Pool2d || s.kind == StepKind::GlobalAvgPool ||
+    // (FakeQuant, RoundHalf: elementwise with no per-element constant, the same bits in either layout; QConv2d reads and writes either, qconv.hip)
+    const bool layout_free = convolution(s) || s.kind == StepKind::FakeQuant || s.kind == StepKind::RoundHalf || s.kind == StepKind::Pool2d || s.kind == StepKind::GlobalAvgPool ||
                              s.kind == StepKind::BinaryAct || s.kind == StepKind::Unary || s.kind == StepKind::AffineChannel ||
                              s.kind == StepKind::CopyCols || s.kind == StepKind::SliceCols || s.kind == StepKind::LRN ||
                              s.kind == StepKind::ChannelShuffle ||
@@ -420,6 +422,31 @@ void Scheduler::byte_buffers() {
   }
 }
 
+// The output of an HDense step that only HDense steps read is stored as the halves themselves (2 bytes per element, at the start of the
+// same buffer) and the readers load them instead of rounding f32 values: the f32 buffer would hold exactly these halves, so the results
+// are bit-identical (tests/test_half_gpu.py).  INFERA_HDENSE_HALF=0 (read when a model is scheduled): f32 on every edge.
+void Scheduler::half_buffers() {
+  m.h_in_half.assign(n, 0);
+  m.h_out_half.assign(n, 0);
+  if (!ScheduleKnobs::read().hdense_half) return;
+  for (size_t i = 0; i < n; i++) {
+    const Step &p = st[i];
+    if (p.kind != StepKind::HDense || p.out == m.plan.out_buf) continue;
+    int readers = 0;
+    bool ok = true;
+    for (size_t j = 0; j < n; j++) {
+      const Step &c = st[j];
+      if (c.in0 != p.out && c.in1 != p.out && c.in2 != p.out) continue;
+      readers++;
+      ok = ok && j > i && c.kind == StepKind::HDense && c.in0 == p.out && c.K == p.M && c.rep == p.rep;
+    }
+    if (!ok || readers == 0) continue;
+    m.h_out_half[i] = 1;
+    for (size_t j = i + 1; j < n; j++)
+      if (st[j].in0 == p.out) m.h_in_half[j] = 1;
+  }
+}
+
 void Scheduler::classify_io(const std::vector<EffStep> &eff) {
   {  // the served output: one writer (a fused streaming kernel that only stores it), no reader
     int writers = 0, readers = 0;
@@ -528,6 +555,7 @@ void schedule(LoadedModel &m) {
   s.choose_conv_arithmetic();
   s.fold_projection_shortcuts();
   s.byte_buffers();
+  s.half_buffers();
   const auto eff = effective_steps(m);
   s.classify_io(eff);
   s.place_scratch(eff);
@@ -590,6 +618,14 @@ std::string LoadedModel::describe_json() const {
            (kern::qconv_stages_in_lds(qconv_launch(x)) ? "lds" : "global") + "\"}";
     }
     if (!q.empty()) o << ",\"qconv\":[" << q << "]";
+  }
+  {  // per HDense step: what its input / output edge carries
+    std::string h;
+    for (size_t i = 0; i < exec.size(); i++)
+      if (plan.steps[i].kind == StepKind::HDense)
+        h += std::string(h.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"in\":\"" + (h_in_half[i] ? "half" : "f32") + "\",\"out\":\"" +
+             (h_out_half[i] ? "half" : "f32") + "\"}";
+    if (!h.empty()) o << ",\"hdense\":[" << h << "]";
   }
   if (!chains.empty()) {
     o << ",\"chain_kernels\":[";

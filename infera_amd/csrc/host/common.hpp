@@ -123,6 +123,8 @@ struct ScheduleKnobs {
                     //   on the data.  INFERA_PRECISION=fp32: the exact-fp32 matrix instruction instead (conv.hip's tiled / weight-stationary kernels)
   bool conv_fold_shortcut;  // INFERA_CONV_FOLD_SHORTCUT=0|1 (default 1)  a ResNet block's 1x1 projection shortcut as extra K stages of the block's second convolution
   bool qdense_bytes;  // INFERA_QDENSE_BYTES=0|1 (default 1)  a QDense result read only by QDense steps that quantise it the same way travels as bytes (0: as f32; same bits)
+  bool hdense_half;  // INFERA_HDENSE_HALF=0|1 (default 1)  an HDense result read only by HDense steps travels as halves, 2 bytes per element (0: as f32; same bits)
+  bool hdense;       // INFERA_HDENSE=0|1 (default 1; read when a model is LOWERED)  float16 MatMul / Gemm layers become HDense steps (0: the float path, Dense + RoundHalf; same bits on exact data)
   static ScheduleKnobs read();
 };
 // Read per launch inside the kernel launchers, for the bit-identity TESTS only (no effect on results; defaults are the shipped paths):

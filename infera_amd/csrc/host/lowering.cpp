@@ -67,6 +67,9 @@ struct Val {
   // QLinearMatMul's result); else `buf` is the f32 tensor a QuantizeLinear read and the rounding is still to be done by whoever reads this
   std::shared_ptr<const Quant> q;
   bool q_done = false;
+  // an ACTIVATION the graph types float16: `buf` holds f32 values that are halves once the plan's RoundHalf steps
+  // have run (insert_half_roundings).  A constant is half when its tensor says so (TensorData::elem)
+  bool half = false;
   bool padded() const { return pend[0] || pend[1] || pend[2] || pend[3]; }
 };
 
@@ -125,6 +128,11 @@ struct Lowerer {
   std::map<int, int> producer;  // buffer id -> index of the step that wrote it
   std::map<int, std::vector<std::string>> buf_names;  // value names that denote each buffer
   std::map<int, int> alias_edges;  // nodes folded away whose input AND output denote the buffer
+  std::set<int> half_bufs;  // buffers written by float16-typed nodes: their steps' results are rounded to half (insert_half_roundings)
+  bool cur_half = false;    // the node being lowered is float16-typed
+  // INFERA_HDENSE=0 (read when a model is loaded): float16 MatMul / Gemm layers stay on the float path (Dense + RoundHalf) -- the
+  // switch the bit-identity tests compare the HDense kernel against
+  const bool hdense_enabled = ScheduleKnobs::read().hdense;
   std::set<int> int_bufs;  // buffers whose f32 values are whole numbers by construction (ArgMax, integer Cast, label arithmetic)
 
   Lowerer(const onnx::Model &model, const std::string &output_select_in) : m(model) {
@@ -249,6 +257,7 @@ struct Lowerer {
     const Val &b = get(n, 1);
     if (a.is_const) unsupported(n, "constant left operand is not supported");
     if (b.is_const && b.c->q_data && qdense_from_qdq(n, gemm)) return;
+    if (b.is_const && hdense(n, gemm)) return;
     if (!b.is_const) {
       auto why = attn_fail.find(&n);
       if (why != attn_fail.end()) unsupported(n, "unsupported operator form: " + why->second);
@@ -506,7 +515,16 @@ struct Lowerer {
         set_act(n, act.buf, act_shape, true);
         return;
       }
-      if (over_m) {
+      if (p && p->kind == StepKind::HDense && p->h_bias_mode == kHalfBiasNone && p->act == Act::None && cst.c->elem == onnx::kFloat16 && int64_t(cv.size()) == p->M &&
+          (cst.shape.size() == 1 || (cst.shape.size() == 2 && cst.shape[0] == 1))) {
+        p->h_bias = half_bits(cv);
+        p->h_bias_mode = kHalfBiasMatmulAdd;
+        p->origin += "+Add";
+        set_act(n, act.buf, act_shape, true);
+        return;
+      }
+      // (a float16 MatMul -> Add rounds the product before the sum: two steps, each rounded, not one Dense with a bias)
+      if (over_m && !cur_half) {
         p->bias = cv;
         p->origin += "+Add";
         set_act(n, act.buf, act_shape, true);
@@ -799,9 +817,17 @@ struct Lowerer {
   void cast(const NodeDef &n) {
     const Val &a = get(n, 0);
     const int64_t to = n.attr_i("to", onnx::kFloat);
-    const bool to_int = to == onnx::kInt64 || to == onnx::kInt32, to_f = to == onnx::kFloat || to == onnx::kDouble;
-    if (!to_int && !to_f) unsupported(n, "only casts to f32/f64/int32/int64");
+    const bool to_int = to == onnx::kInt64 || to == onnx::kInt32, to_h = to == onnx::kFloat16, to_f = to == onnx::kFloat || to == onnx::kDouble || to_h;
+    if (!to_int && !to_f) unsupported(n, "only casts to f32/f64/f16/int32/int64");
     if (a.is_const) {
+      if (a.c->dtype == onnx::kFloat && to_f) {  // between float types: the same values, rounded when the target is float16
+        auto t = std::make_shared<TensorData>(*a.c);
+        t->elem = to_h ? onnx::kFloat16 : onnx::kFloat;
+        if (to_h)
+          for (float &f : t->f32) f = onnx::round_to_half(f);
+        vals[n.outputs[0]] = const_val(std::move(t));
+        return;
+      }
       if ((a.c->dtype == onnx::kInt64) == to_int) { vals[n.outputs[0]] = a; return; }
       if (to_int) {
         std::vector<int64_t> o;
@@ -809,9 +835,29 @@ struct Lowerer {
         set_const_i64(n, std::move(o), a.shape);
       } else {
         std::vector<float> o;
-        for (int64_t i : a.c->i64) o.push_back(float(i));
+        for (int64_t i : a.c->i64) o.push_back(to_h ? onnx::round_to_half(float(i)) : float(i));
         vals[n.outputs[0]] = const_f32(std::move(o), a.shape);
+        if (to_h) vals[n.outputs[0]].c->elem = onnx::kFloat16;
       }
+      return;
+    }
+    if (to_h) {  // an activation becomes float16: one rounding (none when it is half already)
+      if (a.half) { alias(n, a.shape); mark_half(n.outputs[0]); return; }
+      if (a.ra != 0) bad_form(n, "a cast of a time-major value to float16");
+      Step s;
+      s.kind = StepKind::RoundHalf;
+      s.in0 = a.buf;
+      std::vector<int64_t> shape = a.shape;
+      emit(std::move(s), n, shape);
+      mark_half(n.outputs[0]);
+      return;
+    }
+    if (a.half && to_f) {
+      // float16 -> float: the same values under a float name.  Float operators behind it must not fuse into the step that made the half
+      // value (its result is rounded first), so the buffer forgets its producer
+      const int buf = a.buf;
+      alias(n, a.shape);
+      producer.erase(buf);
       return;
     }
     // activations are always f32 here: a float cast is an alias, an integer cast truncates toward zero and
@@ -967,7 +1013,8 @@ struct Lowerer {
       const bool takes_act = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d || p->kind == StepKind::AffineChannel ||
                              p->kind == StepKind::BinaryConst || p->kind == StepKind::BinaryAct;
       const bool qdense_act = quantised_layer(*p) && !p->qy.on && (act == Act::Relu || act == Act::Clip);  // on `real`, before the requantisation
-      if (p->act == Act::None && (takes_act || qdense_act) && (!mfma_step || mfma_fusable(act))) {
+      const bool hdense_act = p->kind == StepKind::HDense && cur_half && int(act) >= 1 && int(act) <= kMaxMfmaFusedAct;  // r = half(act(float(r)))
+      if (p->act == Act::None && (takes_act || qdense_act || hdense_act) && (!mfma_step || mfma_fusable(act))) {
         p->act = act;
         p->act_a = pa;
         p->act_b = pb;
@@ -2421,6 +2468,153 @@ struct Lowerer {
   }
 
   // ------------------------------------------------------------------------------------------
+  // float16 graphs.  Activations stay f32 buffers; a value the graph types float16 carries Val::half, and the
+  // result of every plan step that yields such a value is rounded once to half by a RoundHalf step (insert_half_roundings, after all
+  // fusions have been made).  MatMul / Gemm on half weights become HDense, which rounds for itself.
+  static std::vector<uint16_t> half_bits(const std::vector<float> &v) {
+    std::vector<uint16_t> o(v.size());
+    for (size_t i = 0; i < v.size(); i++) o[i] = onnx::float_to_half(v[i]);
+    return o;
+  }
+  void mark_half(const std::string &name) {
+    auto it = vals.find(name);
+    if (it == vals.end()) return;
+    Val &v = it->second;
+    if (v.is_const) {
+      if (v.c->dtype != onnx::kFloat || v.c->elem == onnx::kFloat16) return;
+      auto t = std::make_shared<TensorData>(*v.c);  // a folded half constant: rounded as the operator's half result would be
+      for (float &f : t->f32) f = onnx::round_to_half(f);
+      t->elem = onnx::kFloat16;
+      t->q_data.reset();
+      v.c = std::move(t);
+      return;
+    }
+    v.half = true;
+    if (v.buf >= 0) half_bufs.insert(v.buf);
+  }
+  // lowers one node (by `body`) under the float16 typing rules: a node whose floating inputs are half yields half values
+  template <class F>
+  void lower_typed(const NodeDef &n, F body) {
+    int n_half = 0, n_float_act = 0;
+    for (const auto &in_name : n.inputs) {
+      if (in_name.empty()) continue;
+      const Val *v = nullptr;
+      Val from_init;
+      if (auto it = vals.find(in_name); it != vals.end()) v = &it->second;
+      else if (auto ci = m.initializers.find(in_name); ci != m.initializers.end()) v = &(from_init = const_val(ci->second));
+      if (!v) continue;
+      if (v->is_const) n_half += v->c->dtype == onnx::kFloat && v->c->elem == onnx::kFloat16;
+      else if (v->half) n_half++;
+      else if (!int_bufs.count(v->buf) && !v->q) n_float_act++;
+    }
+    if (n_half && n_float_act) bad_form(n, "it mixes float16 and float activations; cast one side (Cast) so that the operator has one type");
+    static const std::set<std::string> own_type = {"Cast", "ArgMax", "ArgMin", "Shape", "Size"};  // (their result type is not their input's)
+    cur_half = n_half > 0 && !own_type.count(n.op);
+    body();
+    if (cur_half)
+      for (const auto &o : n.outputs) mark_half(o);
+    cur_half = false;
+  }
+
+  // does the result of this step need a rounding to be a half value, given half inputs?  Not when it only selects, moves or negates them
+  static bool half_exact(const Step &s) {
+    auto is_half_value = [](float v) { return std::isinf(v) || onnx::round_to_half(v) == v; };
+    switch (s.kind) {
+      case StepKind::RoundHalf:
+      case StepKind::HDense:
+      case StepKind::CopyCols:
+      case StepKind::SliceCols:
+      case StepKind::PadCols:
+      case StepKind::ChannelShuffle:
+      case StepKind::ArgMax: return true;
+      case StepKind::Pool2d:
+      case StepKind::GlobalAvgPool: return s.is_max && s.act == Act::None;
+      case StepKind::Unary:
+        return s.act == Act::Relu || s.act == Act::Neg || s.act == Act::Abs || (s.act == Act::Clip && is_half_value(s.act_a) && is_half_value(s.act_b));
+      default: return false;
+    }
+  }
+  // A RoundHalf step behind every step that writes a float16-typed buffer and is not exact on halves; the readers (and the served
+  // output) move to the rounded buffer.  Runs once, after the last node: fusions into a producing step (an activation, a folded
+  // BatchNormalization, a scaler) have happened by then, so a fused step is rounded once, at its result.
+  void insert_half_roundings() {
+    if (half_bufs.empty()) return;
+    std::map<int, size_t> last_writer;
+    for (size_t i = 0; i < plan.steps.size(); i++) last_writer[plan.steps[i].out] = i;
+    std::map<int, int> moved;
+    auto at = [&](int b) { auto it = moved.find(b); return it == moved.end() ? b : it->second; };
+    std::vector<Step> out;
+    for (size_t i = 0; i < plan.steps.size(); i++) {
+      Step s = std::move(plan.steps[i]);
+      s.in0 = at(s.in0), s.in1 = at(s.in1), s.in2 = at(s.in2);
+      const bool round = half_bufs.count(s.out) && last_writer[s.out] == i && !half_exact(s);
+      Step r;
+      if (round) {
+        r.kind = StepKind::RoundHalf;
+        r.in0 = s.out;
+        r.origin = s.origin + "[half]";
+        plan.buf_shape.push_back(plan.buf_shape[size_t(s.out)]);
+        plan.buf_per_row.push_back(plan.buf_per_row[size_t(s.out)]);
+        r.out = int(plan.buf_shape.size()) - 1;
+        moved[s.out] = r.out;
+      }
+      out.push_back(std::move(s));
+      if (round) out.push_back(std::move(r));
+    }
+    plan.steps = std::move(out);
+    plan.out_buf = at(plan.out_buf);
+  }
+
+  // MatMul / Gemm of a float16 activation by constant float16 weights: the HDense step (plan.hpp, hip/hdense.hip).  false: not that
+  // form (alpha / beta other than 1, a float bias, INFERA_HDENSE=0 ...) -- the float path serves it: Dense on the widened weights + RoundHalf
+  bool hdense(const NodeDef &n, bool gemm) {
+    if (!cur_half || !hdense_enabled) return false;
+    const Val a = get(n, 0);
+    const Val &b = get(n, 1);
+    if (a.is_const || !a.half || a.ra != 0 || b.c->dtype != onnx::kFloat || b.c->elem != onnx::kFloat16 || b.shape.size() != 2) return false;
+    const bool window = !gemm && a.shape.size() == 3;
+    if (!window && a.shape.size() != 2) return false;
+    if (gemm && (n.attr_i("transA", 0) != 0 || n.attr_f("alpha", 1.f) != 1.f || n.attr_f("beta", 1.f) != 1.f)) return false;
+    const bool tB = gemm && n.attr_i("transB", 0) != 0;
+    const int64_t K = tB ? b.shape[1] : b.shape[0], M = tB ? b.shape[0] : b.shape[1];
+    if (K <= 0 || M <= 0 || int64_t(b.c->f32.size()) != prod({K, M}) || K > (int64_t(1) << 24) || M > (int64_t(1) << 24)) return false;
+    if (a.shape.back() != K) unsupported(n, "inner dimensions differ: " + shape_str(a.shape) + " x " + shape_str(b.shape));
+    Step s;
+    s.kind = StepKind::HDense;
+    s.K = K;
+    s.M = M;
+    if (gemm && has_input(n, 2)) {
+      const Val &c = get(n, 2);
+      if (!c.is_const || c.c->dtype != onnx::kFloat || c.c->elem != onnx::kFloat16 || (int64_t(c.c->f32.size()) != M && c.c->f32.size() != 1)) return false;
+      s.h_bias.resize(size_t(M));
+      for (int64_t j = 0; j < M; j++) s.h_bias[size_t(j)] = onnx::float_to_half(c.c->f32[c.c->f32.size() == 1 ? 0 : size_t(j)]);
+      s.h_bias_mode = kHalfBiasGemm;
+    }
+    const auto &w = b.c->f32;
+    s.hW.resize(size_t(K * M));
+    for (int64_t k = 0; k < K; k++)
+      for (int64_t j = 0; j < M; j++) s.hW[size_t(k * M + j)] = onnx::float_to_half(tB ? w[size_t(j * K + k)] : w[size_t(k * M + j)]);
+    int in_buf = a.buf;
+    std::string head;
+    if (const Step *t = sole_tail(a.buf); t && t->kind == StepKind::RoundHalf) {  // the layer rounds its input on load: read what the RoundHalf read
+      in_buf = t->in0;
+      head = t->origin + "+";
+      drop_tail();
+    }
+    s.in0 = in_buf;
+    const int64_t rep = window ? a.shape[1] : 1;
+    if (window) prod({rep, std::max(K, M) + 3});
+    s.rep = rep;
+    s.origin = head + node_label(n);
+    if (window) emit_window(std::move(s), n, {a.shape[0], rep, M});
+    else {
+      const std::string origin = s.origin;
+      emit(std::move(s), n, {a.shape[0], M}).origin = origin;
+    }
+    return true;
+  }
+
+  // ------------------------------------------------------------------------------------------
   void lower_node(const NodeDef &n) {
     const std::string &op = n.op;
     if (op != "Conv")
@@ -3220,8 +3414,9 @@ struct Lowerer {
     if (!in.has_shape) throw InferaError::onnx("input '" + in.name + "' has no declared shape");
     // (integer inputs: their values arrive as f32 and are truncated toward zero where a preprocessing region first reads them)
     auto served_type = [](int t) { return t == 0 || t == onnx::kFloat || t == onnx::kInt64 || t == onnx::kInt32; };
+    const bool half_input = m.inputs.size() == 1 && in.elem_type == onnx::kFloat16;  // (served as f32 values that are rounded to half first)
     for (const auto &v : m.inputs)
-      if (!served_type(v.elem_type))
+      if (!served_type(v.elem_type) && !half_input)
         throw InferaError::onnx("input '" + v.name + "' is not f32, int64 or int32 (element type " + std::to_string(v.elem_type) + ")");
     if (in.dims.size() < 2) throw InferaError::onnx("input rank " + std::to_string(in.dims.size()) + " has no row axis + feature axis; rank >= 2 is required");
     for (size_t i = 1; i < in.dims.size(); i++)
@@ -3247,6 +3442,16 @@ struct Lowerer {
       Val v;
       v.buf = new_buf(plan.input_shape);
       v.shape = plan.input_shape;
+      if (half_input) {  // the C ABI hands over f32: the input is rounded first (an HDense layer that reads it does so on load and drops this step)
+        plan.input_declared_type = "float16";
+        Step r;
+        r.kind = StepKind::RoundHalf;
+        r.in0 = v.buf;
+        r.origin = "input:" + in.name;
+        v.buf = push_step(std::move(r), plan.input_shape);
+        v.half = true;
+        half_bufs.insert(v.buf);
+      }
       if (m.inputs.size() == 1) {
         vals[in.name] = v;
         buf_names[v.buf].push_back(in.name);
@@ -3315,9 +3520,9 @@ struct Lowerer {
           unsupported(n, "unsupported operator form: the contrib fused operator of domain '" + n.domain +
                              "' is not supported; export the standard-domain graph (MatMul / Softmax / LayerNormalization)");
         unsupported(n, "operator domain '" + n.domain + "'");
-      } else if (attn_at.count(ni)) lower_attention(attn_at.at(ni), n);
+      } else if (attn_at.count(ni)) lower_typed(n, [&] { lower_attention(attn_at.at(ni), n); });
       else if (absorbed[ni]) continue;
-      else lower_node(n);
+      else lower_typed(n, [&] { lower_node(n); });
     }
     // one output is served: the first (engine.rs:146-149) unless the load call selected another
     const onnx::ValueDef &out = m.outputs[out_index];
@@ -3330,7 +3535,9 @@ struct Lowerer {
     if (it->second.ra != 0)
       throw InferaError::onnx("output '" + out.name + "' " + shape_str(it->second.shape) + " is time-major (its row axis is axis " + std::to_string(it->second.ra) +
                               "); results are served rows first: transpose it in the graph (Transpose(1,0,2)) or use layout = 1");
-    if (out.elem_type != 0 && out.elem_type != onnx::kFloat) {
+    if (out.elem_type == onnx::kFloat16 && it->second.half) {
+      plan.output_declared_type = "float16";  // (half values are f32 values: served exactly)
+    } else if (out.elem_type != 0 && out.elem_type != onnx::kFloat) {
       // integer outputs (ArgMax labels, Cast to int) are returned as f32 VALUES: the C ABI carries f32 only
       // (rust.h:28-49; the reference itself rejects non-f32 outputs at engine.rs:150-152)
       const bool int_valued = int_bufs.count(it->second.buf) > 0;
@@ -3350,6 +3557,7 @@ struct Lowerer {
         if (out.dims[i] > 0 && plan.output_shape[i] > 0 && out.dims[i] != plan.output_shape[i])
           throw InferaError::onnx("declared output shape " + shape_str(out.dims) + " conflicts with inferred " + shape_str(plan.output_shape));
     }
+    insert_half_roundings();
     drop_unread_fake_quants();
     return std::move(plan);
   }
@@ -3371,7 +3579,7 @@ Plan lower_model(const onnx::Model &m, const std::string &output_select) { retur
 double Plan::flops_per_row() const {
   double f = 0;
   for (const auto &s : steps) {
-    if (s.kind == StepKind::Dense || s.kind == StepKind::QDense) f += 2.0 * double(s.rep) * double(s.K) * double(s.M);
+    if (s.kind == StepKind::Dense || s.kind == StepKind::QDense || s.kind == StepKind::HDense) f += 2.0 * double(s.rep) * double(s.K) * double(s.M);
     else if (s.kind == StepKind::Attention) f += 4.0 * double(s.attn_T) * double(s.attn_T) * double(s.attn_heads * s.attn_dh);
     else if (s.kind == StepKind::Conv2d || s.kind == StepKind::QConv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
@@ -3381,12 +3589,15 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
   o << "{\"input_shape\":" << json_int_array(input_shape) << ",\"output_shape\":" << json_int_array(output_shape)
-    << ",\"flops_per_row\":" << (long long)flops_per_row() << ",\"steps\":[";
+    << ",\"flops_per_row\":" << (long long)flops_per_row();
+  if (!input_declared_type.empty()) o << ",\"input_type\":" << json_str(input_declared_type);
+  if (output_declared_type == "float16") o << ",\"output_type\":" << json_str(output_declared_type);  // (integer outputs: infera_get_model_info says so)
+  o << ",\"steps\":[";
   for (size_t i = 0; i < steps.size(); i++) {
     const Step &s = steps[i];
     if (i) o << ",";
@@ -3410,6 +3621,18 @@ std::string Plan::describe_json() const {
       }
       for (int32_t b : s.q_bias) bsum += b;
       o << ",\"w_sum\":" << wsum << ",\"w_hash\":" << whash << ",\"bias_sum\":" << bsum << ",\"x_zero_point\":" << s.qx.zp;
+    }
+    if (s.kind == StepKind::HDense) {
+      static const char *modes[] = {"none", "gemm", "matmul_add"};
+      o << ",\"K\":" << s.K << ",\"M\":" << s.M << ",\"bias\":\"" << modes[s.h_bias_mode] << "\"";
+      if (s.rep > 1) o << ",\"T\":" << s.rep;
+      long long wsum = 0, whash = 0, bsum = 0;  // over the 16-bit patterns the parser read
+      for (size_t k = 0; k < s.hW.size(); k++) {
+        wsum += s.hW[k];
+        whash += (long long)(s.hW[k]) * (long long)(k % 251 + 1);
+      }
+      for (uint16_t b : s.h_bias) bsum += b;
+      o << ",\"w_sum\":" << wsum << ",\"w_hash\":" << whash << ",\"bias_sum\":" << bsum;
     }
     if (s.kind == StepKind::LayerNorm) o << ",\"E\":" << s.K << ",\"T\":" << s.rep << ",\"epsilon\":" << double(s.ln_eps) << ",\"bias\":" << (s.shift.empty() ? "false" : "true");
     if (s.kind == StepKind::MeanTime) o << ",\"E\":" << s.K << ",\"T\":" << s.rep;

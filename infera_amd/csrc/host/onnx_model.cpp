@@ -223,6 +223,23 @@ std::shared_ptr<TensorData> read_tensor(Wire w) {
       }
       break;
     }
+    case kFloat16:  // two bytes per element in raw_data (little endian), one 16-bit pattern per element in int32_data; widened exactly
+      t->dtype = kFloat;
+      t->f32.resize(0);
+      if (raw) {
+        if (rawlen / 2 != n || rawlen % 2) throw size_err();
+        t->f32.resize(n);
+        for (size_t i = 0; i < n; i++) t->f32[i] = half_to_float(uint16_t(raw[2 * i] | (uint16_t(raw[2 * i + 1]) << 8)));
+      } else {
+        if (idata.size() != n) throw size_err();
+        t->f32.resize(n);
+        for (size_t i = 0; i < n; i++) {
+          const int64_t v = int64_t(int32_t(uint32_t(uint64_t(idata[i]))));
+          if (v < 0 || v > 65535) throw InferaError::onnx("tensor '" + t->name + "': int32_data holds a value outside the float16 bit patterns (0 ... 65535)");
+          t->f32[i] = half_to_float(uint16_t(v));
+        }
+      }
+      break;
     default:
       throw InferaError::onnx("tensor '" + t->name + "': unsupported data_type " + std::to_string(dtype));
   }

@@ -7,6 +7,7 @@
 #pragma once
 
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <string>
@@ -14,12 +15,50 @@
 
 namespace infera_hip::onnx {
 
-enum DataType : int { kFloat = 1, kUint8 = 2, kInt8 = 3, kInt32 = 6, kInt64 = 7, kDouble = 11 };
+enum DataType : int { kFloat = 1, kUint8 = 2, kInt8 = 3, kInt32 = 6, kInt64 = 7, kFloat16 = 10, kDouble = 11 };
+
+// IEEE binary16 <-> binary32 on the host: widening is exact (subnormals, infinities, NaN); narrowing rounds to nearest, ties to even,
+// keeps subnormal halves, sends |x| >= 65520 to +-inf and a NaN to a quiet NaN of the same sign
+inline float half_to_float(uint16_t h) {
+  const uint32_t sign = uint32_t(h & 0x8000u) << 16, e = (h >> 10) & 0x1Fu, f = h & 0x3FFu;
+  uint32_t u;
+  if (e == 0x1F) u = sign | 0x7F800000u | (f << 13);
+  else if (e != 0) u = sign | ((e + 112) << 23) | (f << 13);
+  else if (f == 0) u = sign;
+  else {  // a subnormal half: f * 2^-24, exact in f32
+    float v = float(f) * 5.9604644775390625e-8f;
+    std::memcpy(&u, &v, 4);
+    u |= sign;
+  }
+  float out;
+  std::memcpy(&out, &u, 4);
+  return out;
+}
+inline uint16_t float_to_half(float x) {
+  uint32_t u;
+  std::memcpy(&u, &x, 4);
+  const uint16_t sign = uint16_t((u >> 16) & 0x8000u);
+  const uint32_t a = u & 0x7FFFFFFFu;
+  if (a > 0x7F800000u) return uint16_t(sign | 0x7E00u | ((a >> 13) & 0x3FFu));
+  if (a >= 0x477FF000u) return uint16_t(sign | 0x7C00u);  // |x| >= 65520 (and inf)
+  if (a < 0x38800000u) {  // below the smallest normal half: a multiple of 2^-24 after rounding
+    float v;
+    std::memcpy(&v, &a, 4);
+    // adding 0.5 places the value so that the f32 addition rounds it (ties to even) to a multiple of 2^-24: the low mantissa bits are the half
+    v += 0.5f;
+    uint32_t w;
+    std::memcpy(&w, &v, 4);
+    return uint16_t(sign | (w - 0x3F000000u));
+  }
+  const uint32_t r = a + 0xFFFu + ((a >> 13) & 1u);  // ties to even on the 13 dropped bits (a carry moves into the exponent, as it should)
+  return uint16_t(sign | ((r - 0x38000000u) >> 13));
+}
+inline float round_to_half(float x) { return half_to_float(float_to_half(x)); }
 
 struct TensorData {
   std::string name;
-  int dtype = 0;  // kFloat or kInt64 after decoding (uint8 / int8 / int32 widened, double narrowed)
-  int elem = 0;   // the data_type as the file declares it (quantised graphs tell uint8, int8 and int32 apart)
+  int dtype = 0;  // kFloat or kInt64 after decoding (uint8 / int8 / int32 widened, double narrowed, float16 widened exactly)
+  int elem = 0;   // the data_type as the file declares it (quantised graphs tell uint8, int8 and int32 apart; kFloat16: a half tensor, its f32 values are halves)
   std::vector<int64_t> dims;
   std::vector<float> f32;
   std::vector<int64_t> i64;

@@ -60,7 +60,11 @@ enum class StepKind : int {
   FakeQuant = 24,     // y = (sat(rne(x / s) + zp) - zp) * s   (QuantizeLinear -> DequantizeLinear on an activation; Step::qx)
   QDense = 25,        // quantised MatMul / Gemm on the int8 matrix cores, f32 in and out (Step::qx, qy, qW ...; qdense.hip)
   QConv2d = 26,       // quantised convolution (groups == 1): the QDense definition per output pixel, padding = real 0; the Conv2d geometry fields + the QDense quantisation fields (qconv.hip)
+  RoundHalf = 27,     // y = float(half_rne(x)): an f32 value rounded once to IEEE binary16 (the float path of a float16 graph)
+  HDense = 28,        // float16 MatMul / Gemm on the f16 matrix cores: half operands, f32 accumulation, half results served as f32 values (Step::hW, h_bias_mode; hdense.hip)
 };
+// how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
+enum HalfBias : int { kHalfBiasNone = 0, kHalfBiasGemm = 1, kHalfBiasMatmulAdd = 2 };
 
 // Constant per-tensor quantisation of an activation: q = sat(rne(x / scale) + zp) in uint8 or int8
 struct Quant {
@@ -138,6 +142,9 @@ struct Step {
   std::vector<int32_t> q_wzp, q_bias;
   std::vector<float> q_mult;
   bool q_w_signed = true, q_per_channel = false;
+  // HDense: hW [K, M] = the weights' 16-bit patterns, h_bias [M] = the bias's (empty: none), h_bias_mode = HalfBias
+  std::vector<uint16_t> hW, h_bias;
+  int h_bias_mode = kHalfBiasNone;
   std::string origin;  // ONNX node names/ops this step came from (diagnostics)
 };
 
@@ -150,7 +157,8 @@ struct Plan {
   int64_t fixed_batch = -1;  // > 0 when the model's leading dim is a constant (e.g. linear.onnx [1,3])
   int64_t opset = 1;
   std::string output_name;         // the served graph output
-  std::string output_declared_type;  // "" for f32; "int64" / "int32" when the graph declares an integer output that is served as f32 VALUES
+  std::string output_declared_type;  // "" for f32; "int64" / "int32" / "float16" when the graph declares such an output that is served as f32 VALUES
+  std::string input_declared_type;   // "float16" when the graph declares a half input: the f32 values of a call are rounded to half first
   bool output_zipmap = false;        // the served output is a ZipMap's: its input [rows, C] is served, one column per class label
   // "node 'name' (OneHotEncoder)" of each zeros = 0 one-hot encoder (1-based ids in the Prep descriptors); a call whose failure word is set
   // fails naming it

@@ -56,6 +56,7 @@ def _s(field: int, s: str) -> bytes:
 
 
 UINT8, INT8, INT32 = 2, 3, 6
+FLOAT16, BFLOAT16 = 10, 16
 _SMALL_INTS = {np.dtype(np.uint8): (UINT8, "u1"), np.dtype(np.int8): (INT8, "i1"), np.dtype(np.int32): (INT32, "<i4")}
 
 
@@ -71,6 +72,13 @@ def tensor(name: str, arr: np.ndarray, float_data: bool = False, int32_data: boo
             out += _ld(5, b"".join(_varint(int(v)) for v in arr.reshape(-1)))
         else:
             out += _ld(9, arr.astype(fmt).tobytes())
+        return out + _s(8, name)
+    if arr.dtype == np.float16:  # two bytes per element in raw_data, or one 16-bit pattern per element in int32_data
+        out += _vi(2, FLOAT16)
+        if int32_data:
+            out += _ld(5, b"".join(_varint(int(v)) for v in arr.reshape(-1).view(np.uint16)))
+        else:
+            out += _ld(9, arr.astype("<f2").tobytes())
         return out + _s(8, name)
     if arr.dtype == np.float32:
         out += _vi(2, FLOAT)
@@ -2205,3 +2213,251 @@ def quantized_conv_reference(spec: dict, x: np.ndarray, mode: str = "int", weigh
             val[o] = val[op["in"]].max(axis=(2, 3))
     out = val[spec["out"]].astype(f32)
     return out.reshape((out.shape[0],) + tuple(spec["out_shape"]))
+
+
+# ------------------------------------------------------------------------------------------
+# float16 models: half MLPs and a small half CNN, their exact numpy references and derived bounds
+# ------------------------------------------------------------------------------------------
+_f16, _f64 = np.float16, np.float64
+
+
+def _h(v):
+    """v rounded once to IEEE half (numpy's astype: nearest even), as float64."""
+    with np.errstate(over="ignore"):
+        return np.asarray(v).astype(_f16).astype(_f64)
+
+
+def _half_act(r, act):
+    """act(r) for half values r (float64), BEFORE its rounding to half.  LeakyRelu multiplies in f32, as the device does (alpha is an f32
+    attribute: the f32 product rounded to half is the definition); the others are evaluated in float64."""
+    if not act:
+        return r
+    kind = act[0]
+    if kind == "Relu":
+        return np.maximum(r, 0.0)
+    if kind == "LeakyRelu":
+        return np.where(r >= 0, r, (np.float32(act[1]) * r.astype(np.float32)).astype(_f64))
+    if kind == "Clip":
+        return np.minimum(np.maximum(r, _f64(_f16(act[1]))), _f64(_f16(act[2])))
+    if kind == "Sigmoid":
+        with np.errstate(over="ignore"):
+            return 1.0 / (1.0 + np.exp(-r))
+    if kind == "Tanh":
+        return np.tanh(r)
+    raise ValueError(kind)
+
+
+def _as_act(a):
+    return None if not a else ((a,) if isinstance(a, str) else tuple(a))
+
+
+def half_mlp_spec(dims: Sequence[int] = (128, 256, 64, 1), act="Relu", tail: str = "", seed: int = 1234, grid: bool = False, bias: bool = True,
+                  acts: Sequence | None = None) -> dict:
+    """A float16 MLP: layers[l] = {w [K, M] float16, b [M] float16 | None, act}.  `act` follows every layer but the last (acts: one per
+    layer instead); an act is "Relu" | "Sigmoid" | "Tanh" | ("LeakyRelu", alpha) | ("Clip", lo, hi).  Generic: weights and biases uniform
+    in +-1/sqrt(K), rounded to half.  grid=True: weights and biases are multiples of 1/2 in [-1, 1] and inputs (half_inputs) multiples of
+    1/8, so every product of layer l is a multiple of spec["q"][l] and sums below 2^24 q are exact in f32 in any order."""
+    n = len(dims) - 1
+    acts = [_as_act(a) for a in (acts if acts is not None else [act] * (n - 1) + [None])]
+    rng = np.random.default_rng(seed)
+    layers, q, q_in = [], [], 0.125
+    for l in range(n):
+        K, M = int(dims[l]), int(dims[l + 1])
+        if grid:
+            w = (rng.integers(-2, 3, size=(K, M)) / 2.0).astype(_f16)
+            b = (rng.integers(-2, 3, size=M) / 2.0).astype(_f16) if bias else None
+        else:
+            w = (rng.uniform(-1, 1, size=(K, M)) / math.sqrt(K)).astype(_f16)
+            b = (rng.uniform(-1, 1, size=M) / math.sqrt(K)).astype(_f16) if bias else None
+        layers.append({"w": w, "b": b, "act": acts[l]})
+        q.append(q_in * 0.5)
+        q_in = q[-1] * (float(acts[l][1]) if acts[l] and acts[l][0] == "LeakyRelu" else 1.0)
+    return {"dims": tuple(int(d) for d in dims), "layers": layers, "tail": tail, "grid": grid, "q": q if grid else None, "seed": seed}
+
+
+def half_inputs(spec: dict, rows: int, seed: int = 0) -> np.ndarray:
+    """f32 inputs [rows, K0]: multiples of 1/8 in [-1, 1] for a grid spec, standard normal values else."""
+    rng = np.random.default_rng(1000 + seed)
+    k = spec["dims"][0] if "dims" in spec else int(np.prod(spec["in_shape"]))
+    if spec["grid"]:
+        return (rng.integers(-8, 9, size=(rows, k)) / 8.0).astype(np.float32)
+    return rng.standard_normal((rows, k)).astype(np.float32)
+
+
+def _half_act_nodes(nodes, inits, act, src, dst, name):
+    kind = act[0]
+    if kind == "LeakyRelu":
+        nodes.append(node("LeakyRelu", [src], [dst], [attr_f("alpha", float(act[1]))], name=name))
+    elif kind == "Clip":
+        inits.append(tensor(name + "_lo", np.array(act[1], _f16)))
+        inits.append(tensor(name + "_hi", np.array(act[2], _f16)))
+        nodes.append(node("Clip", [src, name + "_lo", name + "_hi"], [dst], name=name))
+    else:
+        nodes.append(node(kind, [src], [dst], name=name))
+
+
+def half_from_spec(spec: dict, io: str = "float", spelling: str = "gemm", int32_data: bool = False, alpha: float = 1.0, layer_outputs: bool = False,
+                   window: int = 0) -> bytes:
+    """The ONNX model of a half_mlp_spec.  io="float": float input and output around Cast nodes (what keep_io_types produces);
+    "half": float16 graph input and output.  spelling: Gemm, or MatMul -> Add.  layer_outputs: every layer's result is a graph output too
+    ("h0", "h1", ...; served through name#output).  window = T > 0: the input is [N, T, K] and the MatMul spelling runs per time step."""
+    dims = spec["dims"]
+    nodes, inits, outs = [], [], []
+    t_io = FLOAT if io == "float" else FLOAT16
+    in_dims = ["N", window, dims[0]] if window else ["N", dims[0]]
+    cur = "X"
+    if io == "float":
+        nodes.append(node("Cast", ["X"], ["x_h"], [attr_i("to", FLOAT16)], name="cast_in"))
+        cur = "x_h"
+    for l, L in enumerate(spec["layers"]):
+        inits.append(tensor(f"W{l}", L["w"], int32_data=int32_data))
+        if L["b"] is not None:
+            inits.append(tensor(f"B{l}", L["b"], int32_data=int32_data))
+        out = f"d{l}"
+        if spelling == "gemm" and not window:
+            attrs = [attr_f("alpha", alpha)] if alpha != 1.0 else []
+            nodes.append(node("Gemm", [cur, f"W{l}"] + ([f"B{l}"] if L["b"] is not None else []), [out], attrs, name=f"gemm{l}"))
+        else:
+            nodes.append(node("MatMul", [cur, f"W{l}"], [f"m{l}" if L["b"] is not None else out], name=f"matmul{l}"))
+            if L["b"] is not None:
+                nodes.append(node("Add", [f"m{l}", f"B{l}"], [out], name=f"add{l}"))
+        cur = out
+        if L["act"]:
+            _half_act_nodes(nodes, inits, L["act"], cur, f"a{l}", f"act{l}")
+            cur = f"a{l}"
+        if layer_outputs:
+            nodes.append(node("Identity", [cur], [f"h{l}"], name=f"tap{l}"))
+            outs.append(value_info(f"h{l}", (["N", window] if window else ["N"]) + [dims[l + 1]], FLOAT16))
+    if spec["tail"]:
+        nodes.append(node(spec["tail"], [cur], ["t"], [attr_i("axis", -1)] if spec["tail"] == "Softmax" else [], name="tail"))
+        cur = "t"
+    if io == "float":
+        nodes.append(node("Cast", [cur], ["Y"], [attr_i("to", FLOAT)], name="cast_out"))
+    else:
+        nodes.append(node("Identity", [cur], ["Y"], name="out"))
+    out_dims = (["N", window] if window else ["N"]) + [dims[-1]]
+    return model("half_mlp", nodes, inits, [value_info("X", in_dims, t_io)], [value_info("Y", out_dims, t_io)] + outs)
+
+
+def _half_layer(L, h, spelling, S=None):
+    """One layer of the definition on half values h (float64): the result before the activation's own rounding."""
+    acc = h @ L["w"].astype(_f64)
+    if L["b"] is None:
+        return _h(acc)
+    b = L["b"].astype(_f64)
+    return _h(acc + b) if spelling == "gemm" else _h(_h(acc) + b)
+
+
+def half_reference(spec: dict, x: np.ndarray, spelling: str = "gemm", layers: bool = False):
+    """The definition of the half plan in float64: the input rounded to half, per layer r = half(acc + b) (gemm) or
+    half(half(acc) + b) (matmul_add), then r = half(act(r)); a tail (Softmax, Sigmoid ...) in float64 and rounded once.  Exact on grid
+    specs; on generic data the device's f32 sum differs (half_bounds).  layers=True: the list of every layer's result as well."""
+    h = _h(np.asarray(x, np.float32))
+    per = []
+    for L in spec["layers"]:
+        h = _half_layer(L, h, spelling)
+        if L["act"]:
+            h = _h(_half_act(h, L["act"]))
+        per.append(h.astype(np.float32))
+    if spec["tail"]:
+        h = _h(_tail_reference(h, spec["tail"]))
+    out = h.astype(np.float32)
+    return (out, per) if layers else out
+
+
+def half_sums(spec: dict, x: np.ndarray, spelling: str = "gemm") -> list:
+    """max over rows and columns of sum_k |x_k w_k| + |b| at every layer of the reference (grid specs: compare with 2^24 q)."""
+    h = _h(np.asarray(x, np.float32))
+    out = []
+    for L in spec["layers"]:
+        S = np.abs(h) @ np.abs(L["w"].astype(_f64)) + (0 if L["b"] is None else np.abs(L["b"].astype(_f64)))
+        out.append(float(S.max()))
+        h = _half_layer(L, h, spelling)
+        if L["act"]:
+            h = _h(_half_act(h, L["act"]))
+    return out
+
+
+def half_bounds(spec: dict, x: np.ndarray, spelling: str = "gemm", layer: int = 0):
+    """(lo, hi): float32 arrays of half values between which every element of layer `layer`'s result must lie when its input is x, for
+    ANY order of the f32 sum.  With e the exact sum (+ bias for gemm), S = sum |x_k w_k| (+ |b|) and gamma = K 2^-24 the computed f32
+    value lies in [e - gamma S, e + gamma S]; rounding to half and Relu / LeakyRelu / Clip are monotone, so the bounds pass through them.
+    Sigmoid / Tanh: the argument interval, and 2 f32 ulps on the value for the device's exp / tanh."""
+    L = spec["layers"][layer]
+    h = _h(np.asarray(x, np.float32))
+    w = L["w"].astype(_f64)
+    K = w.shape[0]
+    gamma = K * 2.0 ** -24
+    e, S = h @ w, np.abs(h) @ np.abs(w)
+    if L["b"] is None:
+        lo, hi = _h(e - gamma * S), _h(e + gamma * S)
+    elif spelling == "gemm":
+        b = L["b"].astype(_f64)
+        S = S + np.abs(b)
+        lo, hi = _h(e + b - gamma * S), _h(e + b + gamma * S)
+    else:
+        b = L["b"].astype(_f64)
+        lo, hi = _h(_h(e - gamma * S) + b), _h(_h(e + gamma * S) + b)
+    if L["act"]:
+        lo, hi = _half_act(lo, L["act"]), _half_act(hi, L["act"])
+        if L["act"][0] in ("Sigmoid", "Tanh"):
+            lo = lo - 2 * np.spacing(np.abs(lo).astype(np.float32)).astype(_f64)
+            hi = hi + 2 * np.spacing(np.abs(hi).astype(np.float32)).astype(_f64)
+        lo, hi = _h(lo), _h(hi)
+    return lo.astype(np.float32), hi.astype(np.float32)
+
+
+def half_cnn_spec(in_shape: Sequence[int] = (8, 9, 9), m1: int = 8, m2: int = 16, classes: int = 5, seed: int = 21, grid: bool = True) -> dict:
+    """Conv3x3 -> Relu -> MaxPool 2/2 -> Conv2x2 -> Relu -> GlobalAveragePool -> Gemm in float16.  (9 x 9 -> 7 x 7 -> 3 x 3 -> 2 x 2: the
+    average is over four values, exact on the grid.)"""
+    rng = np.random.default_rng(seed)
+    c = int(in_shape[0])
+
+    def draw(shape, fan):
+        if grid:
+            return (rng.integers(-2, 3, size=shape) / 2.0).astype(_f16)
+        return (rng.uniform(-1, 1, size=shape) / math.sqrt(fan)).astype(_f16)
+
+    return {"in_shape": tuple(int(d) for d in in_shape), "grid": grid, "seed": seed,
+            "w1": draw((m1, c, 3, 3), c * 9), "b1": draw((m1,), c * 9), "w2": draw((m2, m1, 2, 2), m1 * 4), "b2": draw((m2,), m1 * 4),
+            "w3": draw((m2, classes), m2), "b3": draw((classes,), m2), "q": [1 / 16, 1 / 32, 1 / 256] if grid else None}
+
+
+def half_cnn_from_spec(spec: dict, io: str = "float") -> bytes:
+    c, hh, ww = spec["in_shape"]
+    t_io = FLOAT if io == "float" else FLOAT16
+    nodes, cur = [], "X"
+    if io == "float":
+        nodes.append(node("Cast", ["X"], ["x_h"], [attr_i("to", FLOAT16)], name="cast_in"))
+        cur = "x_h"
+    inits = [tensor(k.upper(), spec[k]) for k in ("w1", "b1", "w2", "b2", "w3", "b3")]
+    nodes += [node("Conv", [cur, "W1", "B1"], ["c1"], [attr_ints("kernel_shape", [3, 3])], name="conv1"), node("Relu", ["c1"], ["r1"], name="relu1"),
+              node("MaxPool", ["r1"], ["p1"], [attr_ints("kernel_shape", [2, 2]), attr_ints("strides", [2, 2])], name="pool1"),
+              node("Conv", ["p1", "W2", "B2"], ["c2"], [attr_ints("kernel_shape", [2, 2])], name="conv2"), node("Relu", ["c2"], ["r2"], name="relu2"),
+              node("GlobalAveragePool", ["r2"], ["g"], name="gap"), node("Flatten", ["g"], ["f"], [attr_i("axis", 1)], name="flatten"),
+              node("Gemm", ["f", "W3", "B3"], ["d"], name="head")]
+    if io == "float":
+        nodes.append(node("Cast", ["d"], ["Y"], [attr_i("to", FLOAT)], name="cast_out"))
+    else:
+        nodes.append(node("Identity", ["d"], ["Y"], name="out"))
+    return model("half_cnn", nodes, inits, [value_info("X", ["N", c, hh, ww], t_io)], [value_info("Y", ["N", spec["w3"].shape[1]], t_io)])
+
+
+def half_cnn_reference(spec: dict, x: np.ndarray, sums: bool = False):
+    """The half CNN in float64, every plan step's result rounded once to half (the float path's contract); sums=True: also
+    max sum |x w| + |b| of the three layers."""
+    n = x.shape[0]
+    h = _h(np.asarray(x, np.float32)).reshape((n,) + spec["in_shape"])
+    S = []
+
+    def conv(h, w, b):
+        w64, b64 = w.astype(_f64), b.astype(_f64)
+        S.append(float((_conv_taps(np.abs(h), np.abs(w64), (1, 1), (0, 0, 0, 0), (1, 1), 1, 0.0) + np.abs(b64)[None, :, None, None]).max()))
+        return np.maximum(_h(_conv_taps(h, w64, (1, 1), (0, 0, 0, 0), (1, 1), 1, 0.0) + b64[None, :, None, None]), 0.0)
+
+    h = _max_pool(conv(h, spec["w1"], spec["b1"]), 2, 2, 0)
+    h = _h(conv(h, spec["w2"], spec["b2"]).mean(axis=(2, 3)))
+    w3, b3 = spec["w3"].astype(_f64), spec["b3"].astype(_f64)
+    S.append(float((np.abs(h) @ np.abs(w3) + np.abs(b3)).max()))
+    out = _h(h @ w3 + b3).astype(np.float32)
+    return (out, S) if sums else out
