@@ -3,6 +3,7 @@
 // (engine.rs:142-145).  Also the device-resident entry points (infera_hip_predict_device).
 #include <cstdlib>
 
+#include "../host/nearest.hpp"
 #include "../host/prep.hpp"
 #include "../host/recurrent.hpp"
 #include "../host/svm.hpp"
@@ -186,7 +187,8 @@ void PassRunner::launch_plain(size_t i) {
       kern::binary_const(stream, buf(x.in0), d.cst, buf(x.out), nr, p.buf_per_row[size_t(x.out)], x.bop, x.const_left, act_of(x));
       break;
     case StepKind::BinaryAct:
-      if (x.S > 1) kern::binary_gate(stream, buf(x.in0), buf(x.in1), buf(x.out), nr, x.C, x.S, x.bop, act_of(x), cq(x.in0));
+      if (x.K > 0) kern::binary_rowscalar(stream, buf(x.in0), buf(x.in1), buf(x.out), nr * x.rep, x.K, x.bop, x.const_left, act_of(x));
+      else if (x.S > 1) kern::binary_gate(stream, buf(x.in0), buf(x.in1), buf(x.out), nr, x.C, x.S, x.bop, act_of(x), cq(x.in0));
       else kern::binary_act(stream, buf(x.in0), buf(x.in1), buf(x.out), nr * p.buf_per_row[size_t(x.out)], x.bop, act_of(x));
       break;
     case StepKind::Softmax: kern::softmax(stream, buf(x.in0), buf(x.out), nr, x.sm_outer, x.sm_len, x.sm_inner, x.sm_norm ? 1 + x.sm_norm : int(x.log_softmax)); break;
@@ -284,6 +286,16 @@ void PassRunner::launch_plain(size_t i) {
       kern::qdense(stream, q);
       break;
     }
+    case StepKind::RowReduce: kern::row_reduce(stream, buf(x.in0), buf(x.out), nr * x.rep, int(x.K), x.out_mode); break;
+    case StepKind::ArgMin: kern::argmin_rows(stream, buf(x.in0), buf(x.out), nr, x.K); break;
+    case StepKind::TopK: kern::topk_rows(stream, buf(x.in0), buf(x.out), nr, int(x.K), int(x.M), x.is_max, x.out_mode == 1); break;
+    case StepKind::Nearest: {  // (model.cpp upload_ml_tables: W = the set's fragments, shift = its norms, bias = the center, tab = the slices)
+      const NearestPack &q = *x.nearest;
+      if (!kern::nearest(stream, buf(x.in0), int(q.F), int(q.F_pad), d.bias, d.W, d.shift, d.tab, buf(x.out), nr, int(q.slices), int(q.M), int(x.M), x.out_mode))
+        throw InferaError::onnx("nearest kernel launch failed: '" + x.origin + "' could not be given its LDS");
+      break;
+    }
+    case StepKind::NearestReduce: kern::nearest_reduce(stream, buf(x.in0), buf(x.out), nr, int(x.nearest->slices), int(x.M), x.out_mode); break;
     case StepKind::RoundHalf: kern::round_half(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)]); break;
     case StepKind::HDense: {  // (model.cpp upload_hdense: W = the weight fragments, bias = the widened half bias)
       kern::HDenseLaunch h;

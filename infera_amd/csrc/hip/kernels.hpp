@@ -70,6 +70,24 @@ void svm_kernel(hipStream_t s, const float *x, int F, int F_pad, int kernel, con
 void svm_reduce(hipStream_t s, const float *part, const uint32_t *class_slice, const float *rho, const float *labels, const float *prob_a,
                 const float *prob_b, float *y, int64_t rows, int Q, int C, int mode);
 
+// ---- distance models (nearest.hip) -------------------------------------------------------------
+// x [rows, F] against the packed set of host/nearest.hpp NearestPack.  mode (NearestOut) kNearestMatrix / kNearestMatrixSqrt: out = d2 /
+// sqrt(d2) [rows, M]; kNearestSelect: out = the per-slice best lists [rows][S][2 * nearest_list_width(k)] (host/nearest.hpp) (values, then index patterns)
+// false: the kernel could not be given its LDS (F > 508 needs the opt-in beyond 64 KB)
+bool nearest(hipStream_t s, const float *x, int F, int F_pad, const float *center, const float *ref, const float *ref_norm, const uint32_t *slice_tile,
+             float *out, int64_t rows, int S, int M, int k, int mode);
+// the slices merged in slice order -> the label [rows], the k nearest indices or their (sqrt) distances [rows, k]
+void nearest_reduce(hipStream_t s, const float *part, float *y, int64_t rows, int S, int k, int mode);
+
+// ---- reductions along the feature axis (reduce.hip) ----------------------------------------------
+// y[v] = reduction op (host/plan.hpp ReduceOp) over the E elements of each of nvec vectors
+void row_reduce(hipStream_t s, const float *x, float *y, int64_t nvec, int E, int op);
+void argmin_rows(hipStream_t s, const float *x, float *y, int64_t rows, int64_t len);
+// y [rows, k] = the k smallest / largest of x [rows, M], sorted (equal values by lower index, NaN last): the values, or the indices as f32
+void topk_rows(hipStream_t s, const float *x, float *y, int64_t rows, int M, int k, bool largest, bool indices);
+// y[v, i] = act(a[v, i] (op) b[v])   (scalar_left: b[v] (op) a[v, i]) over nvec vectors of E elements
+void binary_rowscalar(hipStream_t s, const float *a, const float *b, float *y, int64_t nvec, int64_t E, char op, bool scalar_left, ActParam act);
+
 // ---- preprocessing regions (prep.hip) -----------------------------------------------------------
 // y[r, j] = column program j (host/prep.hpp PrepPack: desc, cst, tab of ntab pairs) over x[r, 0:F_in], R rows per block tile; err: the call's failure
 // word (plans with a zeros = 0 OneHotEncoder only, else null), set to the encoder's 1-based id on a value outside its categories

@@ -4,6 +4,7 @@
 #include "../host/onnx_model.hpp"
 #include "../host/prep.hpp"
 #include "../host/recurrent.hpp"
+#include "../host/nearest.hpp"
 #include "../host/svm.hpp"
 #include "../host/trees.hpp"
 
@@ -224,6 +225,13 @@ bool upload_ml_tables(const Step &s, DeviceStep &d, hipStream_t us) {
       d.shift = upload(s.svm->prob_b, us);
       d.tab = upload(s.svm->class_slice, us);
       return true;
+    case StepKind::Nearest:
+      d.W = upload(s.nearest->ref, us);
+      d.shift = upload(s.nearest->ref_norm, us);
+      d.bias = upload(s.nearest->center, us);
+      d.tab = upload(s.nearest->slice_tile, us);
+      return true;
+    case StepKind::NearestReduce: return true;
     case StepKind::Prep:
       d.tab = upload(s.prep->desc, us);
       d.scale = upload(s.prep->cst, us);

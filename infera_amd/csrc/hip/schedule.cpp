@@ -477,6 +477,9 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
         // (a tree walk reads its row tile once per tree slice, and wide rows feature by feature; an SVM once per SV slice)
         const bool windowed = (sk == StepKind::Conv2d && m.exec[size_t(e.idx)] != ExecKind::ConvPatch) || sk == StepKind::QConv2d || sk == StepKind::Pool2d || sk == StepKind::LRN ||
                               sk == StepKind::TreeEnsemble || sk == StepKind::SvmKernel ||
+                              sk == StepKind::Nearest ||  // (once per slice of the reference set)
+                              sk == StepKind::TopK ||     // (one lane per row: row-strided loads)
+                              (sk == StepKind::RowReduce && st[size_t(e.idx)].out_mode == kReduceLogSumExp) ||  // (two passes: the maximum, then the sum)
                               sk == StepKind::Attention ||  // (every query tile walks all keys and values)
                               sk == StepKind::Recurrent;  // (one dependent fetch per time step: from HBM, not over PCIe)
         m.in_single_reader = !windowed;

@@ -125,6 +125,7 @@ struct ScheduleKnobs {
   bool qdense_bytes;  // INFERA_QDENSE_BYTES=0|1 (default 1)  a QDense result read only by QDense steps that quantise it the same way travels as bytes (0: as f32; same bits)
   bool hdense_half;  // INFERA_HDENSE_HALF=0|1 (default 1)  an HDense result read only by HDense steps travels as halves, 2 bytes per element (0: as f32; same bits)
   bool hdense;       // INFERA_HDENSE=0|1 (default 1; read when a model is LOWERED)  float16 MatMul / Gemm layers become HDense steps (0: the float path, Dense + RoundHalf; same bits on exact data)
+  bool nearest;      // INFERA_NEAREST=0|1 (default 1; read when a model is LOWERED)  distance sub-graphs (KMeans, CDist) become one Nearest step (0: operator by operator -- RowReduce, Dense, BinaryAct; same bits on exact data)
   static ScheduleKnobs read();
 };
 // Read per launch inside the kernel launchers, for the bit-identity TESTS only (no effect on results; defaults are the shipped paths):

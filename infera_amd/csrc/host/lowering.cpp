@@ -22,6 +22,7 @@
 
 #include "attention.hpp"
 #include "common.hpp"
+#include "nearest.hpp"
 #include "plan.hpp"
 #include "prep.hpp"
 #include "recurrent.hpp"
@@ -51,6 +52,15 @@ struct PrepVal {
   }
 };
 
+struct NearestPending {
+  std::shared_ptr<const NearestPack> pack;
+  int in_buf = -1;
+  int64_t rows = -1;  // the row extent of the input's shape
+  bool rooted = false;
+  std::string origin;
+  std::map<int64_t, int> part_of_k;  // k -> the buffer of the best-k lists already emitted
+};
+
 struct Val {
   bool is_const = false;
   std::shared_ptr<const PrepVal> pv;  // set: a preprocessing-region value (buf = -1)
@@ -70,6 +80,9 @@ struct Val {
   // an ACTIVATION the graph types float16: `buf` holds f32 values that are halves once the plan's RoundHalf steps
   // have run (insert_half_roundings).  A constant is half when its tensor says so (TensorData::elem)
   bool half = false;
+  // set: the distances of the rows to a constant set (buf = -1), not computed yet -- whoever reads the value decides what the Nearest step
+  // serves (a label, the best k, the matrix); `rooted`: this value is sqrt(d2)
+  std::shared_ptr<struct NearestPending> nn;
   bool padded() const { return pend[0] || pend[1] || pend[2] || pend[3]; }
 };
 
@@ -133,6 +146,9 @@ struct Lowerer {
   // INFERA_HDENSE=0 (read when a model is loaded): float16 MatMul / Gemm layers stay on the float path (Dense + RoundHalf) -- the
   // switch the bit-identity tests compare the HDense kernel against
   const bool hdense_enabled = ScheduleKnobs::read().hdense;
+  // INFERA_NEAREST=0 (read when a model is loaded): distance sub-graphs lower operator by operator (RowReduce, Dense, BinaryAct ...), the
+  // plan the bit-identity tests compare the Nearest kernel against
+  const bool nearest_enabled = ScheduleKnobs::read().nearest;
   std::set<int> int_bufs;  // buffers whose f32 values are whole numbers by construction (ArgMax, integer Cast, label arithmetic)
 
   Lowerer(const onnx::Model &model, const std::string &output_select_in) : m(model) {
@@ -171,12 +187,18 @@ struct Lowerer {
   const Val &get(const NodeDef &n, size_t i) {
     const Val &v = get_raw(n, i);
     if (v.pv) materialize(n.inputs[i], &n);
+    if (v.nn) materialize_nearest(n.inputs[i]);
     return v;
   }
   const Val &get_raw(const NodeDef &n, size_t i) {
     if (i >= n.inputs.size() || n.inputs[i].empty()) unsupported(n, "missing input " + std::to_string(i));
     auto it = vals.find(n.inputs[i]);
-    if (it != vals.end()) return it->second;
+    if (it != vals.end()) {
+      // a pending distance value has no buffer: whoever reads it as a value (an alias included) reads the [rows, M] matrix.  (ArgMin, TopK
+      // and Sqrt look at it first, nearest_reader.)
+      if (it->second.nn) materialize_nearest(n.inputs[i]);
+      return it->second;
+    }
     auto ci = m.initializers.find(n.inputs[i]);
     if (ci != m.initializers.end()) return vals[n.inputs[i]] = const_val(ci->second);
     unsupported(n, "input '" + n.inputs[i] + "' is not produced by any earlier node");
@@ -477,6 +499,30 @@ struct Lowerer {
         s.S = prod(big.shape, 2);  // > 1 marks the broadcast form
         std::vector<int64_t> shape = big.shape;
         emit(std::move(s), n, shape);
+        return;
+      }
+      // one scalar per vector: [N, K] (op) [N, 1], [N, T, E] (op) [N, T, 1]; either order (a commuting operator keeps the vectors on the left)
+      auto is_row_scalar = [](const Val &big, const Val &small) {
+        const size_t r = big.shape.size();
+        if ((r != 2 && r != 3) || small.shape.size() != r || big.ra != 0 || small.ra != 0 || small.shape.back() != 1 || big.shape.back() < 1) return false;
+        for (size_t i = 0; i + 1 < r; i++)
+          if (small.shape[i] != big.shape[i]) return false;
+        return true;
+      };
+      const bool arith = commutes || op == '-' || op == '/';
+      if (a.shape != b.shape && arith && (is_row_scalar(a, b) || is_row_scalar(b, a))) {
+        const bool left = !is_row_scalar(a, b);  // the scalar is the left operand
+        const Val big = left ? b : a, small = left ? a : b;
+        Step s;
+        s.kind = StepKind::BinaryAct;
+        s.in0 = big.buf;
+        s.in1 = small.buf;
+        s.bop = op;
+        s.K = big.shape.back();
+        s.rep = prod(big.shape, 1) / s.K;
+        s.const_left = left && !commutes;
+        if (big.shape.size() == 3) emit_window(std::move(s), n, big.shape);
+        else emit(std::move(s), n, big.shape);
         return;
       }
       if (a.shape != b.shape) unsupported(n, "activation operands must have equal shapes (or [N,C,H,W] with [N,C,1,1]), got " + shape_str(a.shape) + " and " + shape_str(b.shape));
@@ -922,6 +968,7 @@ struct Lowerer {
     if (!a.is_const && a.shape.size() == 2) {
       const Val x = a;
       if (decomposed_layer_norm(n, x)) return;
+      return row_reduce(n);
     }
     if (a.is_const || a.shape.size() < 3) unsupported(n, "only spatial means of [N,C,...] activations");
     std::vector<int64_t> axes;
@@ -957,6 +1004,93 @@ struct Lowerer {
       for (int64_t i = 2; i < rank; i++) shape.push_back(1);
     emit(std::move(s), n, shape);
   }
+  // The Reduce* family over the last axis of [rows, F] or of a window [rows, T, E]: one RowReduce step (hip/reduce.hip)
+  void row_reduce(const NodeDef &n) {
+    static const std::map<std::string, int> ops = {{"ReduceSum", kReduceSum}, {"ReduceMean", kReduceMean}, {"ReduceMax", kReduceMax}, {"ReduceMin", kReduceMin},
+                                                   {"ReduceProd", kReduceProd}, {"ReduceL1", kReduceL1}, {"ReduceL2", kReduceL2},
+                                                   {"ReduceSumSquare", kReduceSumSquare}, {"ReduceLogSum", kReduceLogSum}, {"ReduceLogSumExp", kReduceLogSumExp}};
+    const Val a = get(n, 0);
+    const int64_t rank = int64_t(a.shape.size());
+    if (a.is_const || a.ra != 0 || (rank != 2 && rank != 3)) bad_form(n, "the input must be a [rows, F] or [rows, T, E] activation, got " + shape_str(a.shape));
+    std::vector<int64_t> axes;
+    if (has_input(n, 1)) axes = const_ints(n, 1, "axes");
+    else if (auto *p = n.attr_ints("axes")) axes = *p;
+    if (n.attr_i("noop_with_empty_axes", 0) != 0) bad_form(n, "noop_with_empty_axes = 1");
+    if (axes.empty()) bad_form(n, "empty axes reduce over every axis, the row axis included");
+    if (axes.size() != 1 || (axes[0] != -1 && axes[0] != rank - 1))
+      bad_form(n, "only the last axis of " + shape_str(a.shape) + " is reduced (the other axes mix rows or need a transpose)");
+    const int64_t E = a.shape.back();
+    if (E < 1 || E > kReduceMaxE) bad_form(n, "F = " + std::to_string(E) + " elements per reduced vector, above the cap of " + std::to_string(kReduceMaxE));
+    Step s;
+    s.kind = StepKind::RowReduce;
+    s.in0 = a.buf;
+    s.K = E;
+    s.rep = prod(a.shape, 1) / E;
+    s.out_mode = ops.at(n.op);
+    std::vector<int64_t> shape(a.shape.begin(), a.shape.end() - 1);
+    if (n.attr_i("keepdims", 1) != 0) shape.push_back(1);
+    if (shape.size() == 3) emit_window(std::move(s), n, shape);
+    else emit(std::move(s), n, shape);
+  }
+  // ArgMin: the twin of ArgMax
+  void argmin(const NodeDef &n) {
+    const Val &a = get(n, 0);
+    if (a.is_const || a.shape.size() != 2) unsupported(n, "only [rows, K] activations");
+    int64_t axis = n.attr_i("axis", 0);
+    if (axis < 0) axis += 2;
+    if (axis != 1) unsupported(n, "only axis 1 keeps rows independent");
+    if (n.attr_i("select_last_index", 0) != 0) unsupported(n, "select_last_index=1");
+    Step s;
+    s.kind = StepKind::ArgMin;
+    s.in0 = a.buf;
+    s.K = a.shape[1];
+    std::vector<int64_t> shape = {a.shape[0]};
+    if (n.attr_i("keepdims", 1) != 0) shape.push_back(1);
+    int_bufs.insert(emit(std::move(s), n, shape).out);
+  }
+  // k of a TopK node (a constant input from opset 10 on, an attribute before); -1: not a constant
+  int64_t topk_k(const NodeDef &n) {
+    if (has_input(n, 1)) {
+      const Val *v = find_value(n.inputs[1]);
+      return v && v->is_const && v->c->dtype == onnx::kInt64 && v->c->i64.size() == 1 ? v->c->i64[0] : -1;
+    }
+    return n.attr_i("k", -1);
+  }
+  // binds output o of n to a new buffer written by step s
+  int bind_output(const NodeDef &n, size_t o, Step s, const std::vector<int64_t> &shape, bool whole) {
+    Val v;
+    v.buf = push_step(std::move(s), shape);
+    v.shape = shape;
+    vals[n.outputs[o]] = v;
+    buf_names[v.buf].push_back(n.outputs[o]);
+    if (whole) int_bufs.insert(v.buf);
+    return v.buf;
+  }
+  // TopK over the last axis of [rows, M]: one step per output that is read (Values, Indices as f32 values)
+  void topk(const NodeDef &n) {
+    const Val a = get(n, 0);
+    if (a.is_const || a.shape.size() != 2 || a.ra != 0) bad_form(n, "the input must be a [rows, M] activation, got " + shape_str(a.shape));
+    int64_t axis = n.attr_i("axis", -1);
+    if (axis < 0) axis += 2;
+    if (axis != 1) bad_form(n, "only the last axis keeps rows independent, got axis " + std::to_string(n.attr_i("axis", -1)));
+    const int64_t k = topk_k(n), M = a.shape[1];
+    if (k < 0) bad_form(n, "k must be a constant");
+    if (k < 1 || k > kNearestMaxK) bad_form(n, "k = " + std::to_string(k) + " is outside 1 .. " + std::to_string(kNearestMaxK));
+    if (k > M) bad_form(n, "k = " + std::to_string(k) + " is above the row length M = " + std::to_string(M));
+    for (size_t o = 0; o < 2; o++) {
+      if (!wanted(n, o)) continue;
+      Step s;
+      s.kind = StepKind::TopK;
+      s.in0 = a.buf;
+      s.K = M;
+      s.M = k;
+      s.is_max = n.attr_i("largest", 1) != 0;
+      s.out_mode = int(o);
+      s.origin = node_label(n);
+      bind_output(n, o, std::move(s), {a.shape[0], k}, o == 1);
+    }
+  }
+
   void argmax(const NodeDef &n) {
     const Val &a = get(n, 0);
     if (a.is_const || a.shape.size() != 2) unsupported(n, "only [rows, classes] activations");
@@ -1857,7 +1991,10 @@ struct Lowerer {
 
   const Val *find_value(const std::string &name) {
     auto it = vals.find(name);
-    if (it != vals.end()) return &it->second;
+    if (it != vals.end()) {
+      if (it->second.nn) materialize_nearest(name);
+      return &it->second;
+    }
     auto ci = m.initializers.find(name);
     if (ci != m.initializers.end()) return &(vals[name] = const_val(ci->second));
     return nullptr;
@@ -2526,7 +2663,11 @@ struct Lowerer {
       case StepKind::SliceCols:
       case StepKind::PadCols:
       case StepKind::ChannelShuffle:
-      case StepKind::ArgMax: return true;
+      case StepKind::ArgMax:
+      case StepKind::ArgMin:
+      case StepKind::TopK:
+      case StepKind::NearestReduce: return true;
+      case StepKind::RowReduce: return s.out_mode == kReduceMax || s.out_mode == kReduceMin;
       case StepKind::Pool2d:
       case StepKind::GlobalAvgPool: return s.is_max && s.act == Act::None;
       case StepKind::Unary:
@@ -2632,6 +2773,7 @@ struct Lowerer {
         auto it = vals.find(in_name);
         if (it != vals.end() && it->second.q) bad_form(n, "it reads the quantised tensor '" + in_name + "'; only DequantizeLinear, QLinearMatMul and QLinearConv do");
       }
+    if ((op == "ArgMin" || op == "TopK" || op == "Sqrt" || op == "Identity") && nearest_reader(n)) return;
     if (op == "QuantizeLinear") quantize_linear(n);
     else if (op == "DequantizeLinear") dequantize_linear(n);
     else if (op == "QLinearMatMul") qlinear_matmul(n);
@@ -2660,6 +2802,11 @@ struct Lowerer {
     else if (op == "Cast") cast(n);
     else if (op == "Concat") concat(n);
     else if (op == "ReduceMean") reduce_mean(n);
+    else if (op == "ReduceSum" || op == "ReduceMax" || op == "ReduceMin" || op == "ReduceProd" || op == "ReduceL1" || op == "ReduceL2" ||
+             op == "ReduceSumSquare" || op == "ReduceLogSum" || op == "ReduceLogSumExp")
+      row_reduce(n);
+    else if (op == "ArgMin") argmin(n);
+    else if (op == "TopK") topk(n);
     else if (op == "LayerNormalization") layer_norm(n);
     else if (op == "ArgMax") argmax(n);
     else if (op == "Identity" || op == "Dropout" || op == "Flatten" || op == "Reshape" || op == "Squeeze" || op == "Unsqueeze") reshape_like(n);
@@ -3408,6 +3555,302 @@ struct Lowerer {
     set_prep(n.outputs[0], std::move(p), out_shape);
   }
 
+  // ---- distance models: |x - c|^2 of each row against a constant set C [M, F] ----------------------------
+  // Recognised before the walk (find_nearest) in the spellings exporters write,
+  //   rs = ReduceSumSquare(X, axes = [1], keepdims = 1);  g = Gemm(X, C, alpha = -2 [, transB]) | Mul(MatMul(X, C^T), -2);
+  //   D2 = Add(Add(rs, g), C2) | Add(rs, Add(g, C2))     (either operand order; C2[m] = |C[m]|^2 within rounding)
+  // when no intermediate has another reader; the contrib operator CDist(X, C) is the same value in one node.  The nodes emit nothing: the
+  // last one binds D2 to a pending value (Val::nn), and what reads it decides what the Nearest step serves -- ArgMin the label, TopK the
+  // best k, Sqrt the rooted distances, anything else (the graph output included) the [rows, M] matrix.
+  struct NearestMatch {
+    std::string x, d2, spelling;
+    std::shared_ptr<TensorData> c;
+    bool c_fm = false;  // C is stored [F, M]
+    std::vector<size_t> nodes;  // ascending; the last is the anchor
+  };
+  std::map<size_t, NearestMatch> nearest_at;  // anchor node index -> the pattern it closes
+
+  // a constant f32 tensor known before the walk: an initializer or a Constant node's value
+  std::shared_ptr<TensorData> const_tensor(const std::string &name) const {
+    auto ci = m.initializers.find(name);
+    if (ci != m.initializers.end()) return ci->second->dtype == onnx::kFloat ? ci->second : nullptr;
+    auto pi = producer_of.find(name);
+    if (pi == producer_of.end() || m.nodes[pi->second].op != "Constant") return nullptr;
+    const onnx::Attribute *a = m.nodes[pi->second].attr("value");
+    return a && a->t && a->t->dtype == onnx::kFloat ? a->t : nullptr;
+  }
+  const NodeDef *producer_node(const std::string &v, size_t *idx) const {
+    auto pi = producer_of.find(v);
+    if (pi == producer_of.end()) return nullptr;
+    *idx = pi->second;
+    return &m.nodes[pi->second];
+  }
+  // g = -2 X C^T read by one node: the set (and its orientation) and the nodes of the chain
+  bool match_minus_two_dot(const std::string &g, const std::string &x, NearestMatch *mt) {
+    size_t gi = 0;
+    const NodeDef *p = producer_node(g, &gi);
+    if (!p || !only_reader(g) || !p->domain.empty()) return false;
+    if (p->op == "Gemm") {
+      if (p->inputs.size() < 2 || p->inputs[0] != x || p->attr_i("transA", 0) != 0 || p->attr_f("alpha", 1.f) != -2.f) return false;
+      auto c = const_tensor(p->inputs[1]);
+      if (!c || c->dims.size() != 2) return false;
+      if (p->inputs.size() > 2 && !p->inputs[2].empty()) {
+        auto z = const_tensor(p->inputs[2]);
+        if (!z || std::any_of(z->f32.begin(), z->f32.end(), [](float v) { return v != 0.f; })) return false;
+      }
+      mt->c = c;
+      mt->c_fm = p->attr_i("transB", 0) == 0;
+      mt->spelling = "gemm";
+      mt->nodes.push_back(gi);
+      return true;
+    }
+    if (p->op != "Mul" || p->inputs.size() != 2) return false;
+    for (int side = 0; side < 2; side++) {
+      auto k = const_tensor(p->inputs[size_t(1 - side)]);
+      if (!k || k->f32.size() != 1 || k->f32[0] != -2.f) continue;
+      size_t mi = 0;
+      const NodeDef *mm = producer_node(p->inputs[size_t(side)], &mi);
+      if (!mm || mm->op != "MatMul" || !mm->domain.empty() || mm->inputs.size() != 2 || mm->inputs[0] != x || !only_reader(mm->outputs[0])) return false;
+      auto c = const_tensor(mm->inputs[1]);
+      if (!c || c->dims.size() != 2) return false;
+      mt->c = c;
+      mt->c_fm = true;
+      mt->spelling = "matmul_mul";
+      mt->nodes.push_back(mi);
+      mt->nodes.push_back(gi);
+      return true;
+    }
+    return false;
+  }
+  void find_nearest(const std::vector<char> &live) {
+    for (size_t i = 0; i < m.nodes.size(); i++) {
+      const NodeDef &rs = m.nodes[i];
+      if (!live[i] || absorbed[i] || region[i] || rs.op != "ReduceSumSquare" || !rs.domain.empty() || rs.inputs.empty() || rs.attr_i("keepdims", 1) == 0) continue;
+      std::vector<int64_t> axes;
+      if (rs.inputs.size() > 1 && !rs.inputs[1].empty()) {
+        auto ci = m.initializers.find(rs.inputs[1]);
+        if (ci == m.initializers.end() || ci->second->dtype != onnx::kInt64) continue;
+        axes = ci->second->i64;
+      } else if (auto *p = rs.attr_ints("axes")) axes = *p;
+      if (axes.size() != 1 || (axes[0] != 1 && axes[0] != -1)) continue;
+      NearestMatch mt;
+      mt.x = rs.inputs[0];
+      const NodeDef *a1 = only_reader(rs.outputs[0]);
+      if (!a1 || a1->op != "Add" || !a1->domain.empty() || a1->inputs.size() != 2 || a1->inputs[0] == a1->inputs[1]) continue;
+      const std::string other = a1->inputs[a1->inputs[0] == rs.outputs[0] ? 1 : 0];
+      std::shared_ptr<TensorData> c2;
+      mt.nodes.push_back(i);
+      mt.nodes.push_back(size_t(a1 - m.nodes.data()));
+      if (match_minus_two_dot(other, mt.x, &mt)) {  // (rs + g) + C2
+        const NodeDef *a2 = only_reader(a1->outputs[0]);
+        if (!a2 || a2->op != "Add" || !a2->domain.empty() || a2->inputs.size() != 2) continue;
+        c2 = const_tensor(a2->inputs[a2->inputs[0] == a1->outputs[0] ? 1 : 0]);
+        mt.nodes.push_back(size_t(a2 - m.nodes.data()));
+        mt.d2 = a2->outputs[0];
+      } else {  // rs + (g + C2)
+        size_t bi = 0;
+        const NodeDef *b = producer_node(other, &bi);
+        if (!b || b->op != "Add" || !b->domain.empty() || b->inputs.size() != 2 || !only_reader(other)) continue;
+        int gs = -1;
+        for (int side = 0; side < 2 && gs < 0; side++)
+          if ((c2 = const_tensor(b->inputs[size_t(1 - side)])) && match_minus_two_dot(b->inputs[size_t(side)], mt.x, &mt)) gs = side;
+        if (gs < 0) continue;
+        mt.nodes.push_back(bi);
+        mt.d2 = a1->outputs[0];
+      }
+      if (!c2 || !mt.c) continue;
+      const int64_t M = mt.c->dims[mt.c_fm ? 1 : 0], F = mt.c->dims[mt.c_fm ? 0 : 1];
+      if (M < 1 || F < 1 || int64_t(mt.c->f32.size()) != M * F || int64_t(c2->f32.size()) != M) continue;
+      if (!(c2->dims.size() == 1 || (c2->dims.size() == 2 && c2->dims[0] == 1))) continue;
+      bool norms = true;  // C2[m] = sum_f C[m, f]^2 within F 2^-23 of it
+      for (int64_t j = 0; j < M && norms; j++) {
+        double a = 0.0;
+        for (int64_t k = 0; k < F; k++) {
+          const double v = mt.c->f32[size_t(mt.c_fm ? k * M + j : j * F + k)];
+          a += v * v;
+        }
+        norms = std::fabs(double(c2->f32[size_t(j)]) - a) <= double(F) * std::ldexp(1.0, -23) * a;
+      }
+      if (!norms) continue;
+      std::sort(mt.nodes.begin(), mt.nodes.end());
+      bool fresh = true;
+      for (size_t q : mt.nodes) fresh = fresh && !absorbed[q] && !region[q] && !attn_at.count(q);
+      if (!fresh) continue;
+      for (size_t q : mt.nodes) absorbed[q] = 1;
+      nearest_at[mt.nodes.back()] = std::move(mt);
+    }
+  }
+  // the pending value of a recognised set; a form the kernel does not take (a time-major, half or quantised X, another width) returns false
+  bool bind_nearest(const NodeDef &anchor, const std::string &x_name, const std::string &out, const float *C, int64_t M, int64_t F, const std::string &spelling,
+                    bool rooted, const std::string &origin) {
+    const Val *xp = find_value(x_name);
+    if (!xp) unsupported(anchor, "input '" + x_name + "' is not produced by any earlier node");
+    if (xp->pv) materialize(x_name, &anchor);
+    if (xp->nn) materialize_nearest(x_name);
+    const Val x = *find_value(x_name);
+    if (x.is_const || x.q || x.half || x.ra != 0 || x.padded() || x.shape.size() != 2 || x.shape[1] != F) return false;
+    auto np = std::make_shared<NearestPending>();
+    try {
+      np->pack = std::make_shared<const NearestPack>(pack_nearest(C, M, F, spelling));
+    } catch (const NearestError &e) {
+      unsupported(anchor, e.what());
+    }
+    np->in_buf = x.buf;
+    np->rows = x.shape[0];
+    np->rooted = rooted;
+    np->origin = origin;
+    Val v;
+    v.nn = np;
+    v.shape = {x.shape[0], M};
+    vals[out] = v;
+    return true;
+  }
+  void lower_nearest(const NearestMatch &mt) {
+    const NodeDef &anchor = m.nodes[mt.nodes.back()];
+    const int64_t M = mt.c->dims[mt.c_fm ? 1 : 0], F = mt.c->dims[mt.c_fm ? 0 : 1];
+    std::vector<float> c(size_t(M * F));
+    for (int64_t j = 0; j < M; j++)
+      for (int64_t k = 0; k < F; k++) c[size_t(j * F + k)] = mt.c->f32[size_t(mt.c_fm ? k * M + j : j * F + k)];
+    if (bind_nearest(anchor, mt.x, mt.d2, c.data(), M, F, mt.spelling, false, node_label(m.nodes[mt.nodes.front()]) + "+...+" + node_label(anchor))) return;
+    for (size_t q : mt.nodes) lower_typed(m.nodes[q], [&] { lower_node(m.nodes[q]); });  // not the kernel's form: operator by operator
+  }
+  static void set_f(NodeDef &d, const char *k, float v) {
+    onnx::Attribute a;
+    a.name = k;
+    a.type = 1;
+    a.f = v;
+    d.attrs[k] = a;
+  }
+  // com.microsoft CDist(X, C, metric): the distances in one node (what skl2onnx writes for neighbour models under optim = 'cdist')
+  void cdist(const NodeDef &n) {
+    const std::string metric = n.attr_s("metric", "sqeuclidean");
+    if (metric != "sqeuclidean" && metric != "euclidean") bad_form(n, "metric '" + metric + "' (only sqeuclidean and euclidean)");
+    if (n.inputs.size() != 2) bad_form(n, "needs the two inputs X and the reference set");
+    const Val &cv = get(n, 1);
+    if (!cv.is_const || cv.c->dtype != onnx::kFloat || cv.shape.size() != 2) bad_form(n, "the reference set must be a constant f32 [M, F] matrix");
+    const int64_t M = cv.shape[0], F = cv.shape[1];
+    const bool rooted = metric == "euclidean";
+    const std::shared_ptr<TensorData> ct = cv.c;
+    if (int64_t(ct->f32.size()) != M * F || M < 1 || F < 1) bad_form(n, "the reference set " + shape_str(cv.shape) + " does not match its data");
+    const Val &x0 = get(n, 0);
+    if (x0.is_const || x0.shape.size() != 2 || x0.shape[1] != F) bad_form(n, "X must be a [rows, " + std::to_string(F) + "] activation, got " + shape_str(x0.shape));
+    if (nearest_enabled && bind_nearest(n, n.inputs[0], n.outputs[0], ct->f32.data(), M, F, "cdist", rooted, node_label(n))) return;
+    try {
+      (void)pack_nearest(ct->f32.data(), M, F, "cdist");  // (the caps hold for either lowering)
+    } catch (const NearestError &e) {
+      unsupported(n, e.what());
+    }
+    // operator by operator: |x|^2 - 2 x . C^T + |c|^2 [, Sqrt]
+    const std::string tmp = n.outputs[0] + "\x01";
+    std::vector<float> c2(static_cast<size_t>(M));
+    for (int64_t j = 0; j < M; j++) {
+      double a = 0.0;
+      for (int64_t k = 0; k < F; k++) a += double(ct->f32[size_t(j * F + k)]) * double(ct->f32[size_t(j * F + k)]);
+      c2[size_t(j)] = float(a);
+    }
+    vals[tmp + "c2"] = const_f32(std::move(c2), {M});
+    vals[tmp + "axes"] = const_i64({1}, {1});
+    for (const char *t : {"rs", "g", "z", "d2"}) uses[tmp + t] = 1;
+    NodeDef rs = std_node(n, "ReduceSumSquare", {n.inputs[0], tmp + "axes"}, tmp + "rs");
+    set_i(rs, "keepdims", 1);
+    lower_node(rs);
+    NodeDef g = std_node(n, "Gemm", {n.inputs[0], n.inputs[1]}, tmp + "g");
+    set_f(g, "alpha", -2.f);
+    set_i(g, "transB", 1);
+    lower_node(g);
+    lower_node(std_node(n, "Add", {tmp + "rs", tmp + "g"}, tmp + "z"));
+    lower_node(std_node(n, "Add", {tmp + "z", tmp + "c2"}, rooted ? tmp + "d2" : n.outputs[0]));
+    if (rooted) lower_node(std_node(n, "Sqrt", {tmp + "d2"}, n.outputs[0]));
+  }
+  // the [rows, M] matrix of a pending distance value, for a reader that takes it as it is
+  void materialize_nearest(const std::string &name) {
+    Val &v = vals.at(name);
+    const std::shared_ptr<NearestPending> np = v.nn;
+    Step s;
+    s.kind = StepKind::Nearest;
+    s.in0 = np->in_buf;
+    s.nearest = np->pack;
+    s.out_mode = np->rooted ? kNearestMatrixSqrt : kNearestMatrix;
+    s.origin = np->origin;
+    const std::vector<int64_t> shape = v.shape;
+    Val b;
+    b.buf = push_step(std::move(s), shape);
+    b.shape = shape;
+    vals[name] = b;
+    buf_names[b.buf].push_back(name);
+  }
+  // the best-k lists of a pending distance value (one Nearest step per k)
+  int nearest_lists(NearestPending &np, int64_t k) {
+    auto it = np.part_of_k.find(k);
+    if (it != np.part_of_k.end()) return it->second;
+    Step s;
+    s.kind = StepKind::Nearest;
+    s.in0 = np.in_buf;
+    s.nearest = np.pack;
+    s.M = k;
+    s.out_mode = kNearestSelect;
+    s.origin = np.origin;
+    return np.part_of_k[k] = push_step(std::move(s), {np.rows, np.pack->slices * 2 * nearest_list_width(k)});
+  }
+  // ArgMin / TopK / Sqrt / Identity reading a pending distance value: the Nearest step serves them itself.  false: not such a reader (or a form the
+  // selection does not take -- the matrix is computed and the operator runs on it)
+  bool nearest_reader(const NodeDef &n) {
+    if (n.inputs.empty()) return false;
+    auto it = vals.find(n.inputs[0]);
+    if (it == vals.end() || !it->second.nn) return false;
+    const Val d = it->second;
+    NearestPending &np = *d.nn;
+    if (n.op == "Identity") {  // the same pending value under another name
+      vals[n.outputs[0]] = d;
+      return true;
+    }
+    if (n.op == "Sqrt") {
+      if (np.rooted) return false;
+      auto r = std::make_shared<NearestPending>(np);
+      r->rooted = true;
+      r->origin += "+" + node_label(n);
+      r->part_of_k.clear();
+      Val v;
+      v.nn = r;
+      v.shape = d.shape;
+      vals[n.outputs[0]] = v;
+      return true;
+    }
+    if (n.op == "ArgMin") {
+      int64_t axis = n.attr_i("axis", 0);
+      if (axis < 0) axis += 2;
+      if (axis != 1 || n.attr_i("select_last_index", 0) != 0) return false;
+      Step s;
+      s.kind = StepKind::NearestReduce;
+      s.in0 = nearest_lists(np, 1);
+      s.nearest = np.pack;
+      s.M = 1;
+      s.out_mode = kNearestLabel;
+      s.origin = np.origin + "+" + node_label(n);
+      std::vector<int64_t> shape = {d.shape[0]};
+      if (n.attr_i("keepdims", 1) != 0) shape.push_back(1);
+      bind_output(n, 0, std::move(s), shape, true);
+      return true;
+    }
+    // TopK
+    int64_t axis = n.attr_i("axis", -1);
+    if (axis < 0) axis += 2;
+    const int64_t k = topk_k(n);
+    if (axis != 1 || n.attr_i("largest", 1) != 0 || k < 1 || k > kNearestMaxK || k > np.pack->M) return false;
+    for (size_t o = 0; o < 2; o++) {
+      if (!wanted(n, o)) continue;
+      Step s;
+      s.kind = StepKind::NearestReduce;
+      s.in0 = nearest_lists(np, k);
+      s.nearest = np.pack;
+      s.M = k;
+      s.out_mode = o == 1 ? kNearestIndices : np.rooted ? kNearestValuesSqrt : kNearestValues;
+      s.origin = np.origin + "+" + node_label(n);
+      bind_output(n, o, std::move(s), {d.shape[0], k}, o == 1);
+    }
+    return true;
+  }
+
   Plan run() {
     plan.opset = m.opset;
     const onnx::ValueDef &in = m.inputs[0];
@@ -3482,6 +3925,7 @@ struct Lowerer {
     // preprocessing regions: their graph inputs start as identity columns over the input buffer (integer inputs truncated)
     const std::set<std::string> region_inputs = find_regions(live);
     find_attention(live);
+    if (nearest_enabled) find_nearest(live);
     {
       int64_t off = 0;
       for (const auto &v : m.inputs) {
@@ -3515,12 +3959,14 @@ struct Lowerer {
       if (region[ni] || n.domain == "ai.onnx.ml") check_row_axis(n, false);
       if (region[ni]) prep_node(n);
       else if (n.domain == "ai.onnx.ml") ml_node(n);
+      else if (n.domain == "com.microsoft" && n.op == "CDist") lower_typed(n, [&] { cdist(n); });
       else if (!n.domain.empty() && n.domain != "ai.onnx") {
         if (n.op == "Attention" || n.op == "MultiHeadAttention" || n.op == "SkipLayerNormalization")
           unsupported(n, "unsupported operator form: the contrib fused operator of domain '" + n.domain +
                              "' is not supported; export the standard-domain graph (MatMul / Softmax / LayerNormalization)");
         unsupported(n, "operator domain '" + n.domain + "'");
       } else if (attn_at.count(ni)) lower_typed(n, [&] { lower_attention(attn_at.at(ni), n); });
+      else if (nearest_at.count(ni)) lower_nearest(nearest_at.at(ni));
       else if (absorbed[ni]) continue;
       else lower_typed(n, [&] { lower_node(n); });
     }
@@ -3529,6 +3975,7 @@ struct Lowerer {
     auto it = vals.find(out.name);
     if (it == vals.end()) throw InferaError::onnx("output '" + out.name + "' is never produced");
     if (it->second.pv) materialize(out.name, nullptr);
+    if (it->second.nn) materialize_nearest(out.name);
     if (it->second.q) bad_form(*quant_node.at(out.name), "its quantised result is the graph output '" + out.name + "'; end the graph with DequantizeLinear");
     if (it->second.is_const) throw InferaError::onnx("output '" + out.name + "' is a constant; nothing to run");
     if (it->second.padded()) throw InferaError::onnx("output '" + out.name + "' is a Pad result; padding is only folded into a following Conv");
@@ -3583,13 +4030,14 @@ double Plan::flops_per_row() const {
     else if (s.kind == StepKind::Attention) f += 4.0 * double(s.attn_T) * double(s.attn_T) * double(s.attn_heads * s.attn_dh);
     else if (s.kind == StepKind::Conv2d || s.kind == StepKind::QConv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
+    else if (s.kind == StepKind::Nearest) f += 2.0 * double(s.nearest->F) * double(s.nearest->M);
     else if (s.kind == StepKind::Recurrent) f += 2.0 * double(s.rnn->T * s.rnn->D * s.rnn->G * s.rnn->H) * double(s.rnn->F + s.rnn->H);
   }
   return f;
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -3636,6 +4084,19 @@ std::string Plan::describe_json() const {
     }
     if (s.kind == StepKind::LayerNorm) o << ",\"E\":" << s.K << ",\"T\":" << s.rep << ",\"epsilon\":" << double(s.ln_eps) << ",\"bias\":" << (s.shift.empty() ? "false" : "true");
     if (s.kind == StepKind::MeanTime) o << ",\"E\":" << s.K << ",\"T\":" << s.rep;
+    if (s.kind == StepKind::RowReduce) {
+      static const char *ops[] = {"Sum", "Mean", "Max", "Min", "Prod", "L1", "L2", "SumSquare", "LogSum", "LogSumExp"};
+      o << ",\"op\":\"" << ops[s.out_mode] << "\",\"E\":" << s.K << ",\"T\":" << s.rep;
+    }
+    if (s.kind == StepKind::ArgMin) o << ",\"K\":" << s.K;
+    if (s.kind == StepKind::TopK) o << ",\"M\":" << s.K << ",\"k\":" << s.M << ",\"largest\":" << (s.is_max ? "true" : "false") << ",\"output\":\"" << (s.out_mode ? "indices" : "values") << "\"";
+    if (s.kind == StepKind::BinaryAct && s.K > 0) o << ",\"row_scalar\":\"" << (s.const_left ? "left" : "right") << "\",\"E\":" << s.K << ",\"T\":" << s.rep;
+    if (s.kind == StepKind::Nearest || s.kind == StepKind::NearestReduce) {
+      static const char *modes[] = {"lists", "d2", "sqrt_d2", "label", "indices", "values", "sqrt_values"};
+      const NearestPack &q = *s.nearest;
+      o << ",\"nearest\":{\"F\":" << q.F << ",\"M\":" << q.M << ",\"k\":" << s.M << ",\"outputs\":\"" << modes[s.out_mode] << "\",\"slices\":" << q.slices
+        << ",\"slice_tile\":" << json_int_array(std::vector<int64_t>(q.slice_tile.begin(), q.slice_tile.end())) << ",\"spelling\":\"" << q.spelling << "\",\"centred\":true}";
+    }
     if (s.kind == StepKind::Attention)
       o << ",\"T\":" << s.attn_T << ",\"heads\":" << s.attn_heads << ",\"dh\":" << s.attn_dh << ",\"scale\":" << double(s.attn_scale) << ",\"mask\":" << (s.cst.empty() ? "false" : "true")
         << ",\"packed_qkv\":" << (s.in0 == s.in1 && s.in1 == s.in2 ? "true" : "false");

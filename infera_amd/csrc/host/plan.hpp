@@ -19,6 +19,7 @@ struct TreePack;  // host/trees.hpp
 struct SvmPack;   // host/svm.hpp
 struct PrepPack;  // host/prep.hpp
 struct RnnPack;   // host/recurrent.hpp
+struct NearestPack;  // host/nearest.hpp
 
 // Kinds 1..5 may be fused into the epilogue of a Dense / Conv2d step (the MFMA kernels resolve them at
 // compile time); the rest run in the elementwise kernels (fused into Binary*/AffineChannel or as a Unary step).
@@ -37,7 +38,7 @@ enum class StepKind : int {
   Unary = 1,        // elementwise activation
   AffineChannel = 2,// y = x*scale[c] + shift[c]  per channel              (unfused BatchNormalization)
   BinaryConst = 3,  // y = x (op) cst[per_row]  (constant pre-broadcast to one row)
-  BinaryAct = 4,    // y = a (op) b             (residual adds; S > 1: b is a per-channel gate [rows, C] broadcast over S positions)
+  BinaryAct = 4,    // y = a (op) b             (residual adds; S > 1: b is a per-channel gate [rows, C] broadcast over S positions; K > 0: b is one scalar per vector of K elements, [N, K] (op) [N, 1], const_left: the scalar is the left operand)
   Softmax = 5,      // softmax / log-softmax over `sm_len` with (outer, len, inner) strides inside a row
   Conv2d = 6,       // NCHW convolution as implicit GEMM (BatchNormalization folded when adjacent)
   Pool2d = 7,       // MaxPool / AveragePool
@@ -61,6 +62,11 @@ enum class StepKind : int {
   QDense = 25,        // quantised MatMul / Gemm on the int8 matrix cores, f32 in and out (Step::qx, qy, qW ...; qdense.hip)
   QConv2d = 26,       // quantised convolution (groups == 1): the QDense definition per output pixel, padding = real 0; the Conv2d geometry fields + the QDense quantisation fields (qconv.hip)
   RoundHalf = 27,     // y = float(half_rne(x)): an f32 value rounded once to IEEE binary16 (the float path of a float16 graph)
+  RowReduce = 29,     // out[r, v] = reduction `out_mode` (ReduceOp) over the K elements of vector v of in0 [rows, rep, K]   (the ONNX Reduce* family over the last axis; reduce.hip)
+  ArgMin = 30,        // out[r, 0] = float(index of the first minimum of in0[r, 0:K])
+  TopK = 31,          // the M (<= 16) smallest / largest (is_max) of in0[r, 0:K], sorted, equal values by lower index, NaN last: out [rows, M] = the values (out_mode 0) or the indices as f32 values (1)
+  Nearest = 32,       // distances of in0 [rows, F] to a constant set (NearestPack, nearest.hip): out = d2 / sqrt(d2) [rows, set size], or the per-slice best-M lists (out_mode: host/nearest.hpp NearestOut)
+  NearestReduce = 33, // in0 = those lists -> the label [rows], the M nearest indices or their distances [rows, M]
   HDense = 28,        // float16 MatMul / Gemm on the f16 matrix cores: half operands, f32 accumulation, half results served as f32 values (Step::hW, h_bias_mode; hdense.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
@@ -79,6 +85,13 @@ struct Quant {
 };
 // Largest K of a QDense step with |bias| <= max_bias: K * 255 * 255 + max|bias| stays below 2^31, so the int32 accumulator is exact
 inline bool qdense_k_fits(int64_t K, int64_t max_bias) { return K * 255 * 255 + max_bias < (int64_t(1) << 31); }
+
+// RowReduce operators (Step::out_mode)
+enum ReduceOp : int {
+  kReduceSum = 0, kReduceMean = 1, kReduceMax = 2, kReduceMin = 3, kReduceProd = 4, kReduceL1 = 5, kReduceL2 = 6, kReduceSumSquare = 7,
+  kReduceLogSum = 8, kReduceLogSumExp = 9,
+};
+constexpr int64_t kReduceMaxE = 65536;  // elements per reduced vector
 
 // TreeEnsemble / TreeReduce output modes (Step::out_mode)
 enum TreeOut : int { kTreeScores = 0, kTreeLabel = 1, kTreeBinaryScores = 2, kTreeBinaryLabel = 3 };
@@ -127,7 +140,8 @@ struct Step {
   std::shared_ptr<const SvmPack> svm;
   std::shared_ptr<const PrepPack> prep;
   std::shared_ptr<const RnnPack> rnn;
-  int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut
+  std::shared_ptr<const NearestPack> nearest;
+  int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut, RowReduce: ReduceOp, TopK: 0 values / 1 indices, Nearest*: NearestOut
   // Attention: Q = in0, K = in1, V = in2 (the same buffer three times when the projections are merged), each [rows, T, ld] with the head
   // block of head g at columns off + g * dh of a step; mask (cst): [T, T] added to the scaled scores, -inf = no weight, empty = none
   int in2 = -1;

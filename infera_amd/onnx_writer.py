@@ -2461,3 +2461,219 @@ def half_cnn_reference(spec: dict, x: np.ndarray, sums: bool = False):
     S.append(float((np.abs(h) @ np.abs(w3) + np.abs(b3)).max()))
     out = _h(h @ w3 + b3).astype(np.float32)
     return (out, S) if sums else out
+
+
+# ------------------------------------------------------------------------------------------
+# distance models (KMeans, nearest-neighbour search) and reductions along the feature axis.  skl2onnx, onnx
+# and onnxruntime are not dependencies: the graphs below restate what the exporter writes for these estimators.
+# ------------------------------------------------------------------------------------------
+
+MS_DOMAIN = "com.microsoft"
+NEAREST_SPELLINGS = ("gemm", "matmul_mul", "cdist")
+REDUCE_OPS = ("ReduceSum", "ReduceMean", "ReduceMax", "ReduceMin", "ReduceProd", "ReduceL1", "ReduceL2", "ReduceSumSquare", "ReduceLogSum",
+              "ReduceLogSumExp")
+
+
+def kmeans_spec(features: int = 30, centers: int = 8, seed: int = 1234, scale: float = 1.0, offset: float = 0.0) -> dict:
+    """Seeded reference set: `centers` Gaussian vectors of `features` columns (times `scale`, plus `offset`)."""
+    rng = np.random.default_rng(seed)
+    c = (rng.standard_normal((centers, features)) * scale + offset).astype(np.float32)
+    return {"features": int(features), "centers": c}
+
+
+def sklearn_kmeans_spec(est) -> dict:
+    """A fitted KMeans / MiniBatchKMeans (cluster_centers_) or NearestCentroid (centroids_) as a kmeans_spec()-style dict."""
+    c = np.asarray(getattr(est, "cluster_centers_", getattr(est, "centroids_", None)), dtype=np.float32)
+    return {"features": int(c.shape[1]), "centers": np.ascontiguousarray(c)}
+
+
+def sklearn_neighbors_spec(est) -> dict:
+    """A fitted NearestNeighbors / KNeighbors* (its training matrix _fit_X, Euclidean metric) as a kmeans_spec()-style dict."""
+    if getattr(est, "effective_metric_", "euclidean") not in ("euclidean", "minkowski", "sqeuclidean") or getattr(est, "p", 2) not in (2, None):
+        raise ValueError("only the Euclidean metric")
+    c = np.asarray(est._fit_X, dtype=np.float32)
+    return {"features": int(c.shape[1]), "centers": np.ascontiguousarray(c), "n_neighbors": int(getattr(est, "n_neighbors", 5))}
+
+
+def _model_ms(name, nodes, inits, inputs, outputs, opset=13) -> bytes:
+    return model(name, nodes, inits, inputs, outputs, opset=opset) + _ld(8, _s(1, MS_DOMAIN) + _vi(2, 1))
+
+
+def _distance_nodes(spec: dict, spelling: str, x: str, out: str, c2=None, order: str = "rs_first", metric: str = "sqeuclidean"):
+    """Nodes and initializers computing `out` = |x - c|^2 [N, M] in one spelling.  c2: the |c|^2 constant written into the graph (default:
+    the f32 norms); order: "rs_first" (rs + g) + C2 as skl2onnx writes it, or "c2_first" rs + (C2 + g)."""
+    C = np.asarray(spec["centers"], dtype=np.float32)
+    M = C.shape[0]
+    if spelling == "cdist":
+        return [node("CDist", [x, "nn_C"], [out], [attr_s("metric", metric)], name="cdist", domain=MS_DOMAIN)], [tensor("nn_C", C)]
+    if c2 is None:
+        c2 = (C.astype(np.float64) ** 2).sum(1).astype(np.float32)
+    inits = [tensor("nn_C2", np.asarray(c2, dtype=np.float32).reshape(1, M))]
+    nodes = [node("ReduceSumSquare", [x], ["nn_rs"], [attr_ints("axes", [1]), attr_i("keepdims", 1)], name="rs")]
+    if spelling == "gemm":
+        inits += [tensor("nn_C", C), tensor("nn_zero", np.zeros(1, np.float32))]
+        nodes.append(node("Gemm", [x, "nn_C", "nn_zero"], ["nn_g"], [attr_f("alpha", -2.0), attr_i("transB", 1)], name="gemm"))
+    elif spelling == "matmul_mul":
+        inits += [tensor("nn_Ct", np.ascontiguousarray(C.T)), tensor("nn_m2", np.array([-2.0], np.float32))]
+        nodes += [node("MatMul", [x, "nn_Ct"], ["nn_xc"], name="matmul"), node("Mul", ["nn_xc", "nn_m2"], ["nn_g"], name="mul")]
+    else:
+        raise ValueError(spelling)
+    if order == "rs_first":
+        nodes += [node("Add", ["nn_rs", "nn_g"], ["nn_z"], name="add_rs"), node("Add", ["nn_C2", "nn_z"], [out], name="add_c2")]
+    else:
+        nodes += [node("Add", ["nn_g", "nn_C2"], ["nn_z"], name="add_c2"), node("Add", ["nn_z", "nn_rs"], [out], name="add_rs")]
+    return nodes, inits
+
+
+def kmeans_from_spec(spec: dict, spelling: str = "gemm", output: str = "label", c2=None, order: str = "rs_first", extra_reader: bool = False) -> bytes:
+    """KMeans as skl2onnx writes it: outputs `label` = ArgMin(D2) [N] int64 (predict) and `scores` = Sqrt(D2) [N, M] (transform); `output`
+    names the first (served by default).  extra_reader: one more graph output reads the row norms, so the sub-graph is not the pattern."""
+    F, M = spec["features"], np.asarray(spec["centers"]).shape[0]
+    nodes, inits = _distance_nodes(spec, spelling, "X", "nn_d2", c2=c2, order=order)
+    nodes += [node("ArgMin", ["nn_d2"], ["label"], [attr_i("axis", 1), attr_i("keepdims", 0)], name="argmin"),
+              node("Sqrt", ["nn_d2"], ["scores"], name="sqrt")]
+    outs = [value_info("label", ["N"], INT64), value_info("scores", ["N", M])]
+    if output == "scores":
+        outs.reverse()
+    elif output == "d2":
+        outs.insert(0, value_info("nn_d2", ["N", M]))
+    if extra_reader:
+        outs.append(value_info("nn_rs", ["N", 1]))
+    return _model_ms("kmeans", nodes, inits, [value_info("X", ["N", F])], outs)
+
+
+def distance_reader_graph(spec: dict, readers: Sequence[tuple], spelling: str = "gemm") -> bytes:
+    """The distance sub-graph followed by a chain of single-input `readers` -- (op, attrs) or (op, attrs, constant second input) -- whose
+    last output "Y" is served: the forms exporters leave between D2 and its consumer (Identity, Flatten, Reshape ...)."""
+    F, M = spec["features"], np.asarray(spec["centers"]).shape[0]
+    nodes, inits = _distance_nodes(spec, spelling, "X", "nn_d2")
+    src, whole = "nn_d2", False
+    for n, r in enumerate(readers):
+        out = "Y" if n == len(readers) - 1 else f"rd_{n}"
+        ins = [src]
+        if len(r) > 2:
+            inits.append(tensor(f"rd_c{n}", np.asarray(r[2])))
+            ins.append(f"rd_c{n}")
+        nodes.append(node(r[0], ins, [out], list(r[1]), name=f"reader{n}"))
+        src, whole = out, r[0] == "ArgMin"
+    return _model_ms("distance_reader", nodes, inits, [value_info("X", ["N", F])], [value_info("Y", ["N"] if whole else ["N", M], INT64 if whole else FLOAT)])
+
+
+def knn_search_from_spec(spec: dict, k: int = 5, output: str = "indices", spelling: str = "cdist", metric: str = "euclidean") -> bytes:
+    """Nearest-neighbour SEARCH (the head of what skl2onnx writes for KNeighbors* / NearestNeighbors): TopK(largest = 0) over the
+    distances; outputs `indices` [N, k] int64 and `distances` [N, k].  The gemm spellings compute squared distances and root the values."""
+    F = spec["features"]
+    if spelling == "cdist":
+        nodes, inits = _distance_nodes(spec, spelling, "X", "nn_d", metric=metric)
+        val = "distances"
+    else:
+        nodes, inits = _distance_nodes(spec, spelling, "X", "nn_d")
+        val = "nn_v2" if metric == "euclidean" else "distances"
+    inits.append(tensor("nn_k", np.array([k], np.int64)))
+    nodes.append(node("TopK", ["nn_d", "nn_k"], [val, "indices"], [attr_i("axis", -1), attr_i("largest", 0), attr_i("sorted", 1)], name="topk"))
+    if val != "distances":
+        nodes.append(node("Sqrt", [val], ["distances"], name="sqrt_v"))
+    outs = [value_info("indices", ["N", k], INT64), value_info("distances", ["N", k])]
+    if output == "distances":
+        outs.reverse()
+    return _model_ms("knn", nodes, inits, [value_info("X", ["N", F])], outs)
+
+
+def nearest_reference(spec: dict, x, k: int = 1) -> dict:
+    """float64 restatement: d2 [N, M] (NaN rows stay NaN), label, the k nearest `indices` (stable: equal distances by lower index, NaN after
+    every number) and `values` (d2), `gap_out` = d2 of the (k+1)-th minus the k-th (inf when k = M), `gap_in` = the smallest gap between
+    neighbours inside the top k (inf when k = 1), and `mag` [N, M] = |xc|^2 + |cc|^2 + 2 sum |xc_f cc_f| with xc = x - mu, cc = c - mu
+    (mu = the mean of the set): the magnitude the error of the centred evaluation scales with."""
+    C = np.asarray(spec["centers"], dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    mu = C.mean(0).astype(np.float32).astype(np.float64)
+    xc, cc = x - mu, C - mu
+    M = C.shape[0]
+    d2 = np.empty((x.shape[0], M))
+    mag = np.empty((x.shape[0], M))
+    for r0 in range(0, x.shape[0], 256):
+        diff = x[r0:r0 + 256, None, :] - C[None, :, :]
+        d2[r0:r0 + 256] = (diff * diff).sum(-1)
+        mag[r0:r0 + 256] = (xc[r0:r0 + 256] ** 2).sum(1)[:, None] + (cc ** 2).sum(1)[None, :] + 2 * np.abs(xc[r0:r0 + 256, None, :] * cc[None, :, :]).sum(-1)
+    key = np.where(np.isnan(d2), np.inf, d2)
+    order = np.argsort(key, axis=1, kind="stable")
+    srt = np.take_along_axis(d2, order, 1)
+    ksrt = np.take_along_axis(key, order, 1)
+    with np.errstate(invalid="ignore"):  # (a NaN row: inf - inf)
+        gap_out = ksrt[:, k] - ksrt[:, k - 1] if k < M else np.full(x.shape[0], np.inf)
+        gap_in = np.diff(ksrt[:, :k], axis=1).min(1) if k > 1 else np.full(x.shape[0], np.inf)
+    return {"d2": d2, "label": order[:, 0], "indices": order[:, :k], "values": srt[:, :k], "gap_out": gap_out, "gap_in": gap_in, "mag": mag}
+
+
+def reduce_zoo(rank: int = 2, F: int = 5, T: int = 3, keepdims: int = 1, k: int = 3, axes_input: bool = False, opset: int = 13) -> tuple[bytes, list]:
+    """One graph output per reduction operator over the last axis of X ([N, F], or for rank 3 the window [N, T, F] of a flat [N, T * F] input), then -- rank 2 only --
+    ArgMin, TopK (both directions, values and indices) and the row-scalar broadcast in every operand order.  Returns (model, output names).
+    axes_input: `axes` as a constant input (the opset-18 form) instead of the attribute."""
+    dims = ["N", F] if rank == 2 else ["N", T, F]
+    red = dims[:-1] + ([1] if keepdims else [])
+    nodes, inits, outs = [], [], []
+    if rank == 3:  # the window arrives flat, [N, T * F] (what the C ABI and the SQL surface carry), and is reshaped in the graph
+        inits.append(tensor("win_shape", np.array([0, T, F], np.int64)))
+        nodes.append(node("Reshape", ["X_flat", "win_shape"], ["X"], name="window"))
+    if axes_input:
+        inits.append(tensor("axes", np.array([-1], np.int64)))
+    for op in REDUCE_OPS:
+        o = "r_" + op
+        if axes_input:
+            nodes.append(node(op, ["X", "axes"], [o], [attr_i("keepdims", keepdims)], name=op))
+        else:
+            nodes.append(node(op, ["X"], [o], [attr_ints("axes", [rank - 1]), attr_i("keepdims", keepdims)], name=op))
+        outs.append(value_info(o, red))
+    names = ["r_" + op for op in REDUCE_OPS]
+    # the row-scalar broadcast reads a keepdims = 1 reduction of its own
+    nodes.append(node("ReduceMax", ["X"], ["b_s"], [attr_ints("axes", [rank - 1]), attr_i("keepdims", 1)], name="b_scalar"))
+    for op in ("Add", "Sub", "Mul", "Div", "Min", "Max"):
+        for side, ins in (("r", ["X", "b_s"]), ("l", ["b_s", "X"])):
+            o = f"b_{op}_{side}"
+            nodes.append(node(op, ins, [o], name=o))
+            outs.append(value_info(o, dims))
+            names.append(o)
+    if rank == 2:
+        inits.append(tensor("topk_k", np.array([k], np.int64)))
+        nodes.append(node("ArgMin", ["X"], ["argmin"], [attr_i("axis", 1), attr_i("keepdims", 0)], name="argmin"))
+        outs.append(value_info("argmin", ["N"], INT64))
+        names.append("argmin")
+        for largest in (0, 1):
+            v, i = f"topk_v{largest}", f"topk_i{largest}"
+            nodes.append(node("TopK", ["X", "topk_k"], [v, i], [attr_i("axis", -1), attr_i("largest", largest)], name=f"topk{largest}"))
+            outs += [value_info(v, ["N", k]), value_info(i, ["N", k], INT64)]
+            names += [v, i]
+    x_in = value_info("X", dims) if rank == 2 else value_info("X_flat", ["N", T * F])
+    return model("reduce_zoo", nodes, inits, [x_in], outs, opset=opset), names
+
+
+def reduce_reference(x, k: int = 3) -> dict:
+    """float64 numpy values of every reduce_zoo() output (keepdims = 1 shapes; squeeze for keepdims = 0), with `mag_<op>` = the sum of
+    absolute terms the rounding error of the summed operators scales with."""
+    x = np.asarray(x, dtype=np.float64)
+    kd = dict(axis=-1, keepdims=True)
+    mx = x.max(**kd)
+    with np.errstate(all="ignore"):
+        out = {"r_ReduceSum": x.sum(**kd), "r_ReduceMean": x.mean(**kd), "r_ReduceMax": mx, "r_ReduceMin": x.min(**kd), "r_ReduceProd": x.prod(**kd),
+               "r_ReduceL1": np.abs(x).sum(**kd), "r_ReduceL2": np.sqrt((x * x).sum(**kd)), "r_ReduceSumSquare": (x * x).sum(**kd),
+               "r_ReduceLogSum": np.log(x.sum(**kd)), "r_ReduceLogSumExp": np.log(np.exp(x - mx).sum(**kd)) + mx}
+        s = mx
+        for op, f in (("Add", np.add), ("Sub", np.subtract), ("Mul", np.multiply), ("Div", np.divide), ("Min", np.minimum), ("Max", np.maximum)):
+            out[f"b_{op}_r"], out[f"b_{op}_l"] = f(x, s), f(s, x)
+    out["mag_sum"] = np.abs(x).sum(**kd)
+    if x.ndim == 2:
+        out["argmin"] = np.argmin(x, 1)
+        for largest in (0, 1):
+            order = np.argsort(-x if largest else x, axis=1, kind="stable")[:, :k]
+            out[f"topk_i{largest}"], out[f"topk_v{largest}"] = order, np.take_along_axis(x, order, 1)
+    return out
+
+
+def autoencoder(F: int = 12, H: int = 4, seed: int = 31) -> tuple[bytes, dict]:
+    """Reconstruction error mean((x - dec(enc(x)))^2, axis 1): Gemm(Relu) -> Gemm -> Sub -> Mul -> ReduceMean.  Returns (model, weights)."""
+    ws = _WeightStream(seed)
+    w = {"W1": ws.take((F, H), F), "b1": ws.take((H,), F), "W2": ws.take((H, F), H), "b2": ws.take((F,), H)}
+    nodes = [node("Gemm", ["X", "W1", "b1"], ["h0"], name="enc"), node("Relu", ["h0"], ["h"], name="relu"), node("Gemm", ["h", "W2", "b2"], ["rec"], name="dec"),
+             node("Sub", ["X", "rec"], ["diff"], name="sub"), node("Mul", ["diff", "diff"], ["sq"], name="mul"),
+             node("ReduceMean", ["sq"], ["err"], [attr_ints("axes", [1]), attr_i("keepdims", 0)], name="mean")]
+    return model("autoencoder", nodes, [tensor(k, v) for k, v in w.items()], [value_info("X", ["N", F])], [value_info("err", ["N"])], opset=13), w
