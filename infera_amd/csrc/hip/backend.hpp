@@ -48,10 +48,36 @@ std::string host_phase_json();
 // GB/s of plain pinned hipMemcpyAsync H2D on this box (threads x iters transfers of `bytes`); < 0 on failure
 double h2d_probe_gbs(int device_ordinal, size_t bytes, int iters, int threads);
 
-// Constants of one plan step resident in one GPU's HBM.
-struct DeviceStep {
-  float *W = nullptr, *bias = nullptr, *cst = nullptr, *scale = nullptr, *shift = nullptr;
-  uint32_t *tab = nullptr;  // the word table of a TreeEnsemble, SvmKernel, SvmReduce or Prep step (model.cpp upload_ml_tables)
+// Constants of one plan step resident in one GPU's HBM: per kernel family the tables its launcher takes, under the launcher's parameter names
+// and element types (kernels.hpp).  A family's struct is filled and handed to its kernel by the adjacent upload_* / launch_* pair in
+// steps.cpp; the memory belongs to DeviceModel::allocations.
+struct PlainTables {  // Dense, Conv2d (W: packed for the step's kernel), AffineChannel, BinaryConst, LayerNorm, Attention (cst: its mask)
+  const float *W = nullptr, *bias = nullptr, *cst = nullptr, *scale = nullptr, *shift = nullptr;
+  const float *stem_split = nullptr;  // a split stem's bf16 blob, beside the exact-fp32 one in W
+};
+struct QuantTables {  // QDense, QConv2d
+  const float *Wfrag = nullptr, *mult = nullptr, *bias = nullptr;
+  const int *c0 = nullptr, *wz = nullptr;
+};
+struct HalfTables { const float *Wp = nullptr, *bias = nullptr; };  // HDense
+struct TreeWalkTables { const uint32_t *tab = nullptr; const float *leaves = nullptr; };
+struct TreeReduceTables { const float *base = nullptr, *labels = nullptr; };
+struct SvmKernelTables { const float *sv = nullptr, *coef = nullptr, *sv_norm = nullptr, *center = nullptr; const uint32_t *slice_tile = nullptr; };
+struct SvmReduceTables { const float *rho = nullptr, *labels = nullptr, *prob_a = nullptr, *prob_b = nullptr; const uint32_t *class_slice = nullptr; };
+struct NearestTables { const float *ref = nullptr, *ref_norm = nullptr, *center = nullptr; const uint32_t *slice_tile = nullptr; };
+struct PrepTables { const uint32_t *desc = nullptr; const float *cst = nullptr, *tab = nullptr; };
+struct RnnTables { const float *wr = nullptr, *bias = nullptr, *bias2 = nullptr, *h0 = nullptr, *c0 = nullptr; };
+struct DeviceStep {  // (a step fills the one struct of its family)
+  PlainTables plain;
+  QuantTables quant;
+  HalfTables half;
+  TreeWalkTables tree_walk;
+  TreeReduceTables tree_reduce;
+  SvmKernelTables svm_kernel;
+  SvmReduceTables svm_reduce;
+  NearestTables nearest;
+  PrepTables prep;
+  RnnTables rnn;
 };
 
 // How the executor runs a step.
@@ -61,8 +87,9 @@ struct DeviceModel {
   int device = -1;  // HIP ordinal
   int num_cus = 0;
   std::vector<DeviceStep> steps;
-  float *mlp3_packed = nullptr;
-  std::vector<float *> chain_packed;  // parameter block per LoadedModel::chains entry
+  const float *mlp3_packed = nullptr;
+  std::vector<const float *> chain_packed;  // parameter block per LoadedModel::chains entry
+  std::vector<void *> allocations;          // every hipMalloc the pointers above point into (model.cpp upload_bytes); freed by the destructor
   ~DeviceModel();
 };
 
@@ -108,9 +135,9 @@ class LoadedModel {
   std::vector<int> conv_fold;  // per ConvTiled step: the 1x1 projection-shortcut step computed inside it as extra K stages (conv_split.hip SecondInput), or -1
   std::vector<char> conv_split6;  // ConvTiled steps on conv2d_split6 (default; INFERA_PRECISION=fp32 leaves them on the exact-fp32 kernels)
   std::vector<char> stem_split6;  // ConvPatch + fused MaxPool steps that run conv2d_stem_split6 (same arithmetic)
-  // QDense steps whose input / output buffer holds quantised bytes instead of the f32 values they stand for (schedule.cpp byte_buffers)
+  // QDense steps whose input / output buffer holds quantised bytes instead of the f32 values they stand for (schedule.cpp narrow_edges)
   std::vector<char> q_in_bytes, q_out_bytes;
-  // HDense steps whose input / output buffer holds halves instead of f32 values (schedule.cpp half_buffers)
+  // HDense steps whose input / output buffer holds halves instead of f32 values (schedule.cpp narrow_edges)
   std::vector<char> h_in_half, h_out_half;
   std::vector<int> slot_of_buf;        // scratch slot per activation buffer (-1: external in/out)
   std::vector<int64_t> slot_per_row;   // floats per row of each scratch slot

@@ -1,7 +1,8 @@
 // runtime.hpp -- what the translation units of the HIP backend share (internal; the public face is backend.hpp):
 //   context.cpp    device discovery, per-thread / leased execution contexts, slot dealing, slot health, counters
 //   schedule.cpp   plan -> kernels: fusion decisions, activation layout, scratch slots (device independent)
-//   model.cpp      weight packing + upload, build_model
+//   model.cpp      build_model, the upload loop and the upload primitive (every device allocation of a model)
+//   steps.cpp      per kernel family, side by side: the tables it keeps in HBM (packing + upload) and the launch that hands them to its kernel
 //   exec.cpp       the plan executor (device passes, lanes), the device-resident entry points
 //   host_path.cpp  the host ABI: staging, admission gate, waits, the big-row pipeline, hipGraph replay, fault re-deal
 //   zero_copy.cpp  registered host memory
@@ -264,15 +265,20 @@ inline kern::ConvGeom conv_geom(const Step &s) {
   return kern::ConvGeom{int(s.C), int(s.H), int(s.Wd), int(s.Mo), int(s.OH), int(s.OW), int(s.kh), int(s.kw),
                         int(s.sh), int(s.sw), int(s.pt), int(s.pl), int(s.dh), int(s.dw), int(s.groups)};
 }
-// the geometry and quantisation of a QConv2d step (pointers, rows and layouts: exec.cpp)
-inline kern::QConvLaunch qconv_launch(const Step &x) {
-  kern::QConvLaunch q;
-  q.C = int(x.C), q.H = int(x.H), q.W = int(x.Wd), q.M = int(x.Mo), q.OH = int(x.OH), q.OW = int(x.OW);
-  q.kh = int(x.kh), q.kw = int(x.kw), q.sh = int(x.sh), q.sw = int(x.sw), q.pt = int(x.pt), q.pl = int(x.pl), q.dh = int(x.dh), q.dw = int(x.dw);
+// the quantisation of a QDense / QConv2d step's input and result and its activation, as both launch structs carry them
+template <class Launch>
+void fill_quant(Launch &q, const Step &x) {
   q.x_scale = x.qx.scale, q.x_zp = x.qx.zp, q.x_min = x.qx.qmin(), q.x_max = x.qx.qmax(), q.x_shift = x.qx.shift();
   q.y_on = x.qy.on;
   q.y_scale = x.qy.scale, q.y_zp = x.qy.zp, q.y_min = x.qy.qmin(), q.y_max = x.qy.qmax();
   q.act = int(x.act), q.act_a = x.act_a, q.act_b = x.act_b;
+}
+// the geometry and quantisation of a QConv2d step (pointers, rows and layouts: steps.cpp)
+inline kern::QConvLaunch qconv_launch(const Step &x) {
+  kern::QConvLaunch q;
+  q.C = int(x.C), q.H = int(x.H), q.W = int(x.Wd), q.M = int(x.Mo), q.OH = int(x.OH), q.OW = int(x.OW);
+  q.kh = int(x.kh), q.kw = int(x.kw), q.sh = int(x.sh), q.sw = int(x.sw), q.pt = int(x.pt), q.pl = int(x.pl), q.dh = int(x.dh), q.dw = int(x.dw);
+  fill_quant(q, x);
   return q;
 }
 inline kern::PoolTail pool_tail(const Step &q) { return kern::PoolTail{int(q.OH), int(q.OW), int(q.pt), int(q.pl)}; }
@@ -295,6 +301,18 @@ void schedule(LoadedModel &m);
 
 // ---- model.cpp --------------------------------------------------------------------------------------------------------------
 void upload_to_device(const LoadedModel &m, DeviceModel &dm);
+// The upload primitive: `bytes` bytes into a new allocation on dm's device (current), recorded in dm.allocations; null for 0 bytes.  On an
+// explicit (non-blocking) stream: a legacy-stream hipMemcpy would try to synchronise with every blocking stream of the device, which is
+// illegal while another thread is capturing a hipGraph ("would make the legacy stream depend on a capturing blocking stream").
+void *upload_bytes(DeviceModel &dm, hipStream_t stream, const void *src, size_t bytes);
+// one model's upload to one device: up(v) = v's elements in HBM
+struct Upload {
+  const LoadedModel &m;
+  DeviceModel &dm;
+  hipStream_t stream;
+  template <class T>
+  const T *operator()(const std::vector<T> &v) const { return static_cast<const T *>(upload_bytes(dm, stream, v.data(), v.size() * sizeof(T))); }
+};
 
 // ---- exec.cpp ---------------------------------------------------------------------------------------------------------------
 // Rows per device pass for plans that need activation scratch (pure: no allocation).
@@ -304,6 +322,39 @@ int64_t prepare_scratch(const LoadedModel &m, ThreadCtx &ctx, int64_t rows);
 // in_colmajor: d_in is one column-major chunk [in_per_row][rows] (only with m.in_colmajor_ok, which implies a single pass)
 void exec_plan(const LoadedModel &m, const DeviceModel &dm, ThreadCtx &ctx, const float *d_in, float *d_out, int64_t rows, bool in_colmajor = false);
 const DeviceModel &device_model(const LoadedModel &m, int slot);
+
+// Rows r0 .. r0 + nr - 1 of one device pass through every step of the plan, on one stream, with one set of scratch slots.
+struct PassRunner {
+  const LoadedModel &m;
+  const DeviceModel &dm;
+  ThreadCtx &ctx;
+  const Plan &p;
+  const std::vector<Step> &st;
+  const float *d_in;
+  float *d_out;
+  const bool in_colmajor;
+  hipStream_t stream = nullptr;
+  int64_t r0 = 0, nr = 0;
+  std::vector<int64_t> slot_base;  // floats into the scratch, per slot
+
+  PassRunner(const LoadedModel &model, const DeviceModel &dmodel, ThreadCtx &c, const float *in, float *out, bool cm)
+      : m(model), dm(dmodel), ctx(c), p(model.plan), st(model.plan.steps), d_in(in), d_out(out), in_colmajor(cm), slot_base(model.slot_per_row.size(), 0) {}
+
+  float *buf(int b) const {
+    if (b == 0) return const_cast<float *>(d_in) + r0 * p.in_per_row();
+    if (b == p.out_buf) return d_out + r0 * p.out_per_row();
+    return ctx.scratch + slot_base[size_t(m.slot_of_buf[size_t(b)])];
+  }
+  bool cq(int b) const { return m.cq_mode && !m.nchw_buf[size_t(b)]; }  // a channel-quad tensor (not the caller's NCHW one)
+  // scratch slots sized for slot_rows rows, from scratch_off floats into the scratch
+  void run(hipStream_t s, int64_t first_row, int64_t rows, int64_t slot_rows, int64_t scratch_off);
+  // steps.cpp
+  bool launch_fused(size_t i, size_t *skip);  // steps schedule.cpp gave a fused / specialised kernel (true: handled)
+  void launch_plain(size_t i);                // one kernel per step, by step kind
+};
+
+// ---- steps.cpp --------------------------------------------------------------------------------------------------------------
+void upload_step(const Upload &up, size_t i);  // the tables of step i, by what runs it (nothing for a step without tables)
 
 }  // namespace rt
 }  // namespace infera_hip

@@ -1,7 +1,7 @@
 // schedule.cpp -- plan -> kernels (device independent, done once per infera_load_model): which steps fuse into which kernel, the
 // activation layout of convolutional plans, the arithmetic of the convolutions, where the served result and the input may live, and
-// the scratch slots of what is left.  This is the half of engine.rs:49-55 (`into_optimized().into_runnable()`) that decides; model.cpp
-// packs and uploads what is decided here, exec.cpp runs it.
+// the scratch slots of what is left.  This is the half of engine.rs:49-55 (`into_optimized().into_runnable()`) that decides; steps.cpp
+// packs, uploads and launches what is decided here, step by step (model.cpp's loop at load, exec.cpp's per pass).
 #include <sstream>
 
 #include "runtime.hpp"
@@ -66,8 +66,9 @@ struct Scheduler {
   void fuse_residual_adds();         // a block's Add (+ activation) into the epilogue of its last producer
   void choose_conv_arithmetic();     // bf16 x three exact parts (default) or exact fp32
   void fold_projection_shortcuts();  // a block's 1x1 shortcut as extra K stages of its second convolution
-  void byte_buffers();               // QDense -> QDense edges that carry the quantised bytes
-  void half_buffers();               // HDense -> HDense edges that carry halves
+  // QDense -> QDense edges that carry the quantised bytes, HDense -> HDense edges that carry halves
+  void narrow_edges(StepKind kind, bool enabled, bool needs_qy, bool (*same_format)(const Step &p, const Step &c), std::vector<char> &in_narrow,
+                    std::vector<char> &out_narrow);
   void classify_io(const std::vector<EffStep> &eff);   // may the result be stored into pinned memory, the input be read from it / column-major?
   void place_scratch(const std::vector<EffStep> &eff); // scratch slots by liveness
 };
@@ -396,54 +397,32 @@ void Scheduler::fold_projection_shortcuts() {
 
 }
 
-// The output of a QDense step that only QDense steps read, each quantising its input exactly as the producer quantised its result, is
-// stored as the bytes q (shifted to signed) at the start of the same buffer, and the readers skip their own rounding: re-quantising
-// (q - zp) * s with the same s returns q, so the results are bit-identical (tests/test_quantized_gpu.py) and the edge moves a quarter of
-// the bytes.  INFERA_QDENSE_BYTES=0 (read when a model is scheduled): f32 on every edge.
-void Scheduler::byte_buffers() {
-  m.q_in_bytes.assign(n, 0);
-  m.q_out_bytes.assign(n, 0);
-  if (!ScheduleKnobs::read().qdense_bytes) return;
+// An edge between two steps of one narrow-format kind may carry that format instead of the f32 values it stands for, at the start of the same
+// buffer, when only such steps read it and both ends agree on the format (`same_format`; `needs_qy`: the producer quantises its result).
+// QDense: the bytes q (shifted to signed), and the readers skip their own rounding -- re-quantising (q - zp) * s with the same s returns q, so
+// the results are bit-identical (tests/test_quantized_gpu.py) and the edge moves a quarter of the bytes; INFERA_QDENSE_BYTES=0: f32 on every
+// edge.  HDense: the halves themselves, which the readers load instead of rounding f32 values -- the f32 buffer would hold exactly these
+// halves (tests/test_half_gpu.py); INFERA_HDENSE_HALF=0.  (`enabled`: the knob, read when a model is scheduled.)
+void Scheduler::narrow_edges(StepKind kind, bool enabled, bool needs_qy, bool (*same_format)(const Step &p, const Step &c), std::vector<char> &in_narrow,
+                             std::vector<char> &out_narrow) {
+  in_narrow.assign(n, 0);
+  out_narrow.assign(n, 0);
+  if (!enabled) return;
   for (size_t i = 0; i < n; i++) {
     const Step &p = st[i];
-    if (p.kind != StepKind::QDense || !p.qy.on || p.out == m.plan.out_buf) continue;
+    if (p.kind != kind || (needs_qy && !p.qy.on) || p.out == m.plan.out_buf) continue;
     int readers = 0;
     bool ok = true;
     for (size_t j = 0; j < n; j++) {
       const Step &c = st[j];
       if (c.in0 != p.out && c.in1 != p.out && c.in2 != p.out) continue;
       readers++;
-      ok = ok && j > i && c.kind == StepKind::QDense && c.in0 == p.out && c.qx == p.qy && c.K == p.M && c.rep == p.rep;
+      ok = ok && j > i && c.kind == kind && c.in0 == p.out && same_format(p, c) && c.K == p.M && c.rep == p.rep;
     }
     if (!ok || readers == 0) continue;
-    m.q_out_bytes[i] = 1;
+    out_narrow[i] = 1;
     for (size_t j = i + 1; j < n; j++)
-      if (st[j].in0 == p.out) m.q_in_bytes[j] = 1;
-  }
-}
-
-// The output of an HDense step that only HDense steps read is stored as the halves themselves (2 bytes per element, at the start of the
-// same buffer) and the readers load them instead of rounding f32 values: the f32 buffer would hold exactly these halves, so the results
-// are bit-identical (tests/test_half_gpu.py).  INFERA_HDENSE_HALF=0 (read when a model is scheduled): f32 on every edge.
-void Scheduler::half_buffers() {
-  m.h_in_half.assign(n, 0);
-  m.h_out_half.assign(n, 0);
-  if (!ScheduleKnobs::read().hdense_half) return;
-  for (size_t i = 0; i < n; i++) {
-    const Step &p = st[i];
-    if (p.kind != StepKind::HDense || p.out == m.plan.out_buf) continue;
-    int readers = 0;
-    bool ok = true;
-    for (size_t j = 0; j < n; j++) {
-      const Step &c = st[j];
-      if (c.in0 != p.out && c.in1 != p.out && c.in2 != p.out) continue;
-      readers++;
-      ok = ok && j > i && c.kind == StepKind::HDense && c.in0 == p.out && c.K == p.M && c.rep == p.rep;
-    }
-    if (!ok || readers == 0) continue;
-    m.h_out_half[i] = 1;
-    for (size_t j = i + 1; j < n; j++)
-      if (st[j].in0 == p.out) m.h_in_half[j] = 1;
+      if (st[j].in0 == p.out) in_narrow[j] = 1;
   }
 }
 
@@ -557,8 +536,9 @@ void schedule(LoadedModel &m) {
   s.fuse_residual_adds();
   s.choose_conv_arithmetic();
   s.fold_projection_shortcuts();
-  s.byte_buffers();
-  s.half_buffers();
+  const ScheduleKnobs knobs = ScheduleKnobs::read();
+  s.narrow_edges(StepKind::QDense, knobs.qdense_bytes, true, [](const Step &p, const Step &c) { return c.qx == p.qy; }, m.q_in_bytes, m.q_out_bytes);
+  s.narrow_edges(StepKind::HDense, knobs.hdense_half, false, [](const Step &, const Step &) { return true; }, m.h_in_half, m.h_out_half);
   const auto eff = effective_steps(m);
   s.classify_io(eff);
   s.place_scratch(eff);

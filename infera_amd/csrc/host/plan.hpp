@@ -135,7 +135,7 @@ struct Step {
   int64_t lrn_size = 0;
   float lrn_alpha = 1e-4f, lrn_beta = 0.75f, lrn_bias = 1.f;
   // TreeEnsemble / TreeReduce, SvmKernel / SvmReduce, Prep: the packed tables and their sizes (a kernel step and its reduce step share
-  // one pack); hip/model.cpp upload_ml_tables decides which device pointer holds which table
+  // one pack); uploaded table by table into the family's struct of hip/backend.hpp (hip/steps.cpp)
   std::shared_ptr<const TreePack> tree;
   std::shared_ptr<const SvmPack> svm;
   std::shared_ptr<const PrepPack> prep;
