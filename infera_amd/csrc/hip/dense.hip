@@ -1200,9 +1200,9 @@ static void launch_skinny(hipStream_t s, const float *X, const float *W, const f
 
 bool dense_can_fuse_softmax(int K, int M) { return M <= 16 || (M <= 32 && K % 8 == 0 && K <= 512) || (M <= 64 && K > 128); }
 // ArgMax epilogues (softmax_mode 3) exist in the skinny and the two 16x16x4 streaming kernels; the latter need 16-byte rows
+// (asked of the decision function itself: INFERA_DENSE16W=0 takes the wide kernel, and with it the epilogue, away from K > 128)
 bool dense_can_fuse_argmax(const float *X, int K, int M) {
-  return narrow16g_ok(K, M) || skinny_ok(K, M) || narrow16w_ok(K, M) ||
-         (M <= 16 && K % 16 == 0 && K <= 1024 && (reinterpret_cast<uintptr_t>(X) & 15) == 0);
+  return dense_kernel_family(int64_t(1) << 20, K, M, 3, false, (reinterpret_cast<uintptr_t>(X) & 15) == 0)[0] != '\0';
 }
 
 // Layers whose kernels can read a column-major chunk (the host path's staging layout) themselves: the two as-it-lies streaming
