@@ -66,6 +66,8 @@ struct SvmKernelTables { const float *sv = nullptr, *coef = nullptr, *sv_norm = 
 struct SvmReduceTables { const float *rho = nullptr, *labels = nullptr, *prob_a = nullptr, *prob_b = nullptr; const uint32_t *class_slice = nullptr; };
 struct NearestTables { const float *ref = nullptr, *ref_norm = nullptr, *center = nullptr; const uint32_t *slice_tile = nullptr; };
 struct PrepTables { const uint32_t *desc = nullptr; const float *cst = nullptr, *tab = nullptr; };
+struct ConvTKernelTables { const float *W = nullptr, *bias = nullptr; const int *tab = nullptr; };  // ConvTranspose2d (W: packed for the step's kernel; tab: the phase tap tables)
+struct ResizeTables { const int *row_idx = nullptr, *col_idx = nullptr; const float *row_wgt = nullptr, *col_wgt = nullptr; };  // Resize2d
 struct RnnTables { const float *wr = nullptr, *bias = nullptr, *bias2 = nullptr, *h0 = nullptr, *c0 = nullptr; };
 struct DeviceStep {  // (a step fills the one struct of its family)
   PlainTables plain;
@@ -78,10 +80,12 @@ struct DeviceStep {  // (a step fills the one struct of its family)
   NearestTables nearest;
   PrepTables prep;
   RnnTables rnn;
+  ConvTKernelTables convt;
+  ResizeTables resize;
 };
 
 // How the executor runs a step.
-enum class ExecKind : int { Normal = 0, Skipped = 1, Mlp3Head = 2, DenseSoftmax = 3, ConvTiled = 4, ConvPatch = 5, ConvDepthwise = 6, DenseTiled = 7, DenseArgMax = 8, ChainHead = 9 };
+enum class ExecKind : int { Normal = 0, Skipped = 1, Mlp3Head = 2, DenseSoftmax = 3, ConvTiled = 4, ConvPatch = 5, ConvDepthwise = 6, DenseTiled = 7, DenseArgMax = 8, ChainHead = 9, ConvTPhase = 10 };
 
 struct DeviceModel {
   int device = -1;  // HIP ordinal

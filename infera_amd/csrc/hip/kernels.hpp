@@ -322,4 +322,25 @@ void lrn(hipStream_t s, const float *X, float *Y, int64_t rows, int C, int S, in
 void channel_shuffle(hipStream_t s, const float *X, float *Y, int64_t rows, int C, int S, int groups, bool cq);
 void global_avgpool(hipStream_t s, const float *X, float *Y, int64_t rows, int C, int S, bool cq, bool is_max = false);
 
+// ---- transposed convolution by stride phases (deconv.hip) and Resize (resize.hip) --------------
+// C, H, W = the input; M, OH, OW = the output; h_stride / w_stride = ints per row- / column-phase record of `tab` (host/deconv.hpp)
+struct ConvTGeom {
+  int C, H, W, M, OH, OW, kh, kw, sh, sw, pt, pl, groups, h_stride, w_stride;
+};
+// Generic kernel: any groups / dilation / layouts; Wg = convt2d_generic_pack() of the ONNX weights [C, M/g, kh, kw] -> [ky][kx][C][M/g]
+void convt2d_generic_pack(const ConvTGeom &g, const float *W, float *packed);
+void convt2d_generic(hipStream_t s, const float *X, const float *Wg, const float *bias, float *Y, const int *tab, int64_t rows, const ConvTGeom &g,
+                     ActParam act, bool in_cq, bool out_cq);
+// MFMA phase kernel: groups == 1, channel-quad input (C % 4 == 0), output channel-quad or NCHW per flag.  `tab` on the device = the axis
+// tables followed by the sh * sw phase offsets convt2d_phase_pack() fills (units of 256 floats into the packed weights)
+bool convt2d_phase_supported(const ConvTGeom &g, const int32_t *tab);
+size_t convt2d_phase_packed_floats(const ConvTGeom &g, const int32_t *tab);
+void convt2d_phase_pack(const ConvTGeom &g, const int32_t *tab, const float *W, float *packed, int32_t *phase_off);
+void convt2d_phase(hipStream_t s, const float *X, const float *Wp, const float *bias, float *Y, const int *tab, int64_t rows, const ConvTGeom &g,
+                   int64_t max_phase_pixels, ActParam act, bool out_cq);
+// Y[n, c, oh, ow] from the row / column tables: nearest: X[n, c, row_idx[oh], col_idx[ow]]; linear: horizontal interpolation of the rows
+// row_idx[2 oh], row_idx[2 oh + 1] with (col_wgt[2 ow], col_wgt[2 ow + 1]) = (1 - w, w), then the vertical one with row_wgt
+void resize2d(hipStream_t s, const float *X, float *Y, int64_t rows, int C, int H, int W, int OH, int OW, const int *row_idx, const int *col_idx,
+              const float *row_wgt, const float *col_wgt, bool linear, bool cq);
+
 }  // namespace infera_hip::kern

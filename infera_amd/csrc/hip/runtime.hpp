@@ -281,6 +281,8 @@ inline kern::QConvLaunch qconv_launch(const Step &x) {
   fill_quant(q, x);
   return q;
 }
+// the geometry of a ConvTranspose2d step as its kernels take it (host/deconv.hpp: the table strides)
+kern::ConvTGeom convt_geom(const Step &s);
 inline kern::PoolTail pool_tail(const Step &q) { return kern::PoolTail{int(q.OH), int(q.OW), int(q.pt), int(q.pl)}; }
 // A Dense layer is a 1x1 convolution over 1x1 "images": with H = W = 1 the channel-quad layout IS the row-major
 // [rows, K] matrix, so the tiled conv kernel (packed weights through LDS, unit-pipelined MFMA stream) serves it.

@@ -4,6 +4,7 @@
 // packs, uploads and launches what is decided here, step by step (model.cpp's loop at load, exec.cpp's per pass).
 #include <sstream>
 
+#include "../host/deconv.hpp"
 #include "runtime.hpp"
 
 namespace infera_hip {
@@ -63,6 +64,7 @@ struct Scheduler {
   void fuse_tabular();               // Dense x3 -> fused MLP, runs of small layers -> chain kernel, Dense + Softmax / ArgMax epilogues, tiled Dense
   void decide_layout();              // channel-quad planes for convolutional plans (+ the weight / constant permutations that follow from it)
   void assign_conv_kernels();        // patch / tiled / depthwise kernels, the stem's fused MaxPool
+  void assign_convt_kernels();       // transposed convolutions: the MFMA phase kernel where it applies, else the generic one
   void fuse_residual_adds();         // a block's Add (+ activation) into the epilogue of its last producer
   void choose_conv_arithmetic();     // bf16 x three exact parts (default) or exact fp32
   void fold_projection_shortcuts();  // a block's 1x1 shortcut as extra K stages of its second convolution
@@ -195,13 +197,44 @@ void Scheduler::decide_layout() {
            s.kind == StepKind::RoundHalf;
   };
   auto convolution = [](const Step &s) { return s.kind == StepKind::Conv2d || s.kind == StepKind::QConv2d; };
+  // (a transposed convolution reads and writes either layout, deconv.hip)
+  auto reads_nchw = [&](const Step &s) { return convolution(s) || s.kind == StepKind::ConvTranspose2d; };
+  // A served [C,H,W] result leaves in the caller's NCHW order.  When a transposed convolution -- the last layer of a decoder -- is its only
+  // writer and nothing reads it, that layer stores NCHW itself and the plan before it stays in channel quads; anything else keeps the plan NCHW.
+  bool out_by_convt = false;
+  if (spatial(m.plan.out_buf) > 1 && m.plan.out_buf != 0) {
+    int writers = 0, convt_writers = 0, readers = 0;
+    for (const auto &s : st) {
+      writers += s.out == m.plan.out_buf;
+      convt_writers += s.out == m.plan.out_buf && s.kind == StepKind::ConvTranspose2d;
+      readers += s.in0 == m.plan.out_buf || s.in1 == m.plan.out_buf || s.in2 == m.plan.out_buf;
+    }
+    out_by_convt = writers == 1 && convt_writers == 1 && readers == 0;
+    if (out_by_convt) m.nchw_buf[size_t(m.plan.out_buf)] = 1;
+  }
+  // Likewise a transposed convolution whose result only meets flat [rows, C*H*W] tensors element by element -- a reconstruction against the
+  // table's columns, which lie in NCHW element order: that layer stores NCHW and the plan before it stays in channel quads.
+  auto flat_pair = [&](const Step &s, int b) {  // s combines the [C,H,W] buffer b with a flat operand
+    return s.kind == StepKind::BinaryAct && s.in1 >= 0 && s.S <= 1 && s.K == 0 && s.in0 != s.in1 && (s.in0 == b || s.in1 == b) && !is4d(s.in0 == b ? s.in1 : s.in0);
+  };
+  for (const auto &c : st) {
+    if (c.kind != StepKind::ConvTranspose2d || c.out == m.plan.out_buf || !is4d(c.out) || spatial(c.out) <= 1) continue;
+    int writers = 0, readers = 0, flat_readers = 0;
+    for (const auto &s : st) {
+      writers += s.out == c.out;
+      const bool reads = s.in0 == c.out || s.in1 == c.out || s.in2 == c.out;
+      readers += reads;
+      flat_readers += reads && flat_pair(s, c.out);
+    }
+    if (writers == 1 && readers > 0 && readers == flat_readers) m.nchw_buf[size_t(c.out)] = 1;
+  }
   for (const auto &s : st)
     if (elementwise(s) && s.in0 >= 0 && m.nchw_buf[size_t(s.in0)] && is4d(s.out) && s.out != m.plan.out_buf) m.nchw_buf[size_t(s.out)] = 1;
   for (const auto &s : st) {
-    any_conv = any_conv || convolution(s);
+    any_conv = any_conv || reads_nchw(s);
     // (CopyCols = channel concat: a contiguous per-row block in NCHW and in channel-quad planes alike)
     // (FakeQuant, RoundHalf: elementwise with no per-element constant, the same bits in either layout; QConv2d reads and writes either, qconv.hip)
-    const bool layout_free = convolution(s) || s.kind == StepKind::FakeQuant || s.kind == StepKind::RoundHalf || s.kind == StepKind::Pool2d || s.kind == StepKind::GlobalAvgPool ||
+    const bool layout_free = reads_nchw(s) || s.kind == StepKind::Resize2d || s.kind == StepKind::FakeQuant || s.kind == StepKind::RoundHalf || s.kind == StepKind::Pool2d || s.kind == StepKind::GlobalAvgPool ||
                              s.kind == StepKind::BinaryAct || s.kind == StepKind::Unary || s.kind == StepKind::AffineChannel ||
                              s.kind == StepKind::CopyCols || s.kind == StepKind::SliceCols || s.kind == StepKind::LRN ||
                              s.kind == StepKind::ChannelShuffle ||
@@ -212,10 +245,17 @@ void Scheduler::decide_layout() {
     if (s.kind == StepKind::SliceCols && is4d(s.in0) && spatial(s.in0) > 1 && !m.nchw_buf[size_t(s.in0)] &&
         s.col_off % (4 * spatial(s.in0)) != 0)
       refuse("'" + s.origin + "' slices channels from an offset that is not a whole quad");
+    // an elementwise pair of a [C,H,W] tensor with a flat [rows, C*H*W] one (a decoder's reconstruction against the table's columns):
+    // the flat operand lies in NCHW element order
+    if (s.kind == StepKind::BinaryAct && s.in1 >= 0 && s.S <= 1 && s.K == 0) {
+      auto planes = [&](int b) { return is4d(b) && spatial(b) > 1 && !m.nchw_buf[size_t(b)]; };
+      if ((planes(s.in0) && !is4d(s.in1)) || (planes(s.in1) && !is4d(s.in0)))
+        refuse("'" + s.origin + "' combines a [C,H,W] tensor with a flat one in NCHW element order");
+    }
     for (int b : {s.in0, s.in1}) {
       if (b < 0) continue;
       if (m.nchw_buf[size_t(b)] && is4d(b) && spatial(b) > 1) {  // NCHW tensors are read by convolutions and by their own elementwise chain only
-        if (!(convolution(s) || (elementwise(s) && b == s.in0 && m.nchw_buf[size_t(s.out)])))
+        if (!(reads_nchw(s) || flat_pair(s, b) || (elementwise(s) && b == s.in0 && m.nchw_buf[size_t(s.out)])))
           refuse("'" + s.origin + "' reads the NCHW input tensor and is neither a convolution nor elementwise preprocessing");
         continue;
       }
@@ -228,7 +268,7 @@ void Scheduler::decide_layout() {
       }
     }
   }
-  if (spatial(m.plan.out_buf) > 1) refuse("the served output is a [C,H,W] tensor (results leave in the caller's NCHW order)");
+  if (spatial(m.plan.out_buf) > 1 && !out_by_convt) refuse("the served output is a [C,H,W] tensor (results leave in the caller's NCHW order)");
   // channel-quad planes need whole quads in every internal 4-D tensor (the caller's input stays NCHW)
   // (a buffer no step writes any more -- that of a FakeQuant its QConv2d absorbed -- has no layout)
   std::vector<char> written(m.plan.buf_shape.size(), 0);
@@ -297,6 +337,16 @@ void Scheduler::assign_conv_kernels() {
       if (kern::conv2d_tiled_supported(g)) m.exec[i] = ExecKind::ConvTiled;
       else if (kern::conv2d_depthwise_supported(g)) m.exec[i] = ExecKind::ConvDepthwise;
     }
+}
+
+void Scheduler::assign_convt_kernels() {
+  // INFERA_CONVT_MFMA=0 (read when a model is scheduled): every transposed convolution on the generic kernel (tests, A/B)
+  if (!m.cq_mode || !ScheduleKnobs::read().convt_mfma) return;
+  for (size_t i = 0; i < n; i++) {
+    const Step &s = st[i];
+    if (m.exec[i] != ExecKind::Normal || s.kind != StepKind::ConvTranspose2d || m.nchw_buf[size_t(s.in0)]) continue;
+    if (kern::convt2d_phase_supported(convt_geom(s), s.deconv->tab.data())) m.exec[i] = ExecKind::ConvTPhase;
+  }
 }
 
 void Scheduler::fuse_residual_adds() {
@@ -460,6 +510,7 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
                               sk == StepKind::TopK ||     // (one lane per row: row-strided loads)
                               (sk == StepKind::RowReduce && st[size_t(e.idx)].out_mode == kReduceLogSumExp) ||  // (two passes: the maximum, then the sum)
                               sk == StepKind::Attention ||  // (every query tile walks all keys and values)
+                              sk == StepKind::ConvTranspose2d || sk == StepKind::Resize2d ||  // (every input pixel is fetched once per tap / per copy)
                               sk == StepKind::Recurrent;  // (one dependent fetch per time step: from HBM, not over PCIe)
         m.in_single_reader = !windowed;
         break;
@@ -533,6 +584,7 @@ void schedule(LoadedModel &m) {
   s.fuse_tabular();
   s.decide_layout();
   s.assign_conv_kernels();
+  s.assign_convt_kernels();
   s.fuse_residual_adds();
   s.choose_conv_arithmetic();
   s.fold_projection_shortcuts();
@@ -548,7 +600,7 @@ void schedule(LoadedModel &m) {
 using namespace rt;
 
 std::string LoadedModel::describe_json() const {
-  static const char *ek[] = {"normal", "skipped", "mlp3_fused", "dense_softmax", "conv_tiled_cq", "conv_patch", "conv_depthwise", "dense_tiled", "dense_argmax", "chain_fused"};
+  static const char *ek[] = {"normal", "skipped", "mlp3_fused", "dense_softmax", "conv_tiled_cq", "conv_patch", "conv_depthwise", "dense_tiled", "dense_argmax", "chain_fused", "convt_phase"};
   std::ostringstream o;
   o << "{\"name\":" << json_str(name) << ",\"plan\":" << plan.describe_json() << ",\"exec\":[";
   for (size_t i = 0; i < exec.size(); i++)
@@ -609,6 +661,17 @@ std::string LoadedModel::describe_json() const {
         h += std::string(h.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"in\":\"" + (h_in_half[i] ? "half" : "f32") + "\",\"out\":\"" +
              (h_out_half[i] ? "half" : "f32") + "\"}";
     if (!h.empty()) o << ",\"hdense\":[" << h << "]";
+  }
+  {  // per ConvTranspose2d step: the kernel that runs it and the layouts it reads and writes
+    std::string c;
+    for (size_t i = 0; i < exec.size(); i++) {
+      const Step &x = plan.steps[i];
+      if (x.kind != StepKind::ConvTranspose2d) continue;
+      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)], out_cq = cq_mode && !nchw_buf[size_t(x.out)];
+      c += std::string(c.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"kernel\":\"" + (exec[i] == ExecKind::ConvTPhase ? "convt2d_phase" : "convt2d_generic") +
+           "\",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\"}";
+    }
+    if (!c.empty()) o << ",\"convt\":[" << c << "]";
   }
   if (!chains.empty()) {
     o << ",\"chain_kernels\":[";

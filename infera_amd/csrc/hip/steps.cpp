@@ -3,6 +3,7 @@
 // launch_plain (every pass, exec.cpp's loop) pick the pair by ExecKind / StepKind.  A new family adds its struct, its pair and its two cases.
 #include <cstdlib>
 
+#include "../host/deconv.hpp"
 #include "../host/nearest.hpp"
 #include "../host/onnx_model.hpp"
 #include "../host/prep.hpp"
@@ -13,6 +14,12 @@
 
 namespace infera_hip {
 namespace rt {
+
+kern::ConvTGeom convt_geom(const Step &s) {
+  return kern::ConvTGeom{int(s.C), int(s.H), int(s.Wd), int(s.Mo), int(s.OH), int(s.OW), int(s.kh), int(s.kw), int(s.sh), int(s.sw),
+                         int(s.pt), int(s.pl), int(s.groups), s.deconv->h_stride, s.deconv->w_stride};
+}
+
 namespace {
 
 // `v` padded with zeros to n floats (channel / feature counts rounded up to what a kernel's tiles need)
@@ -334,6 +341,46 @@ void launch_rnn(const PassRunner &r, const Step &x, const RnnTables &t) {
     throw InferaError::onnx("recurrent kernel launch failed: '" + x.origin + "' could not be given its LDS");
 }
 
+// ---- transposed convolutions (host/deconv.hpp DeconvPack, deconv.hip): the MFMA phase kernel's fragments and phase offsets, or the
+// generic kernel's [tap][C][M/g] weights; both read the pack's axis tables ----
+void upload_convt(const Upload &up, size_t i, ConvTKernelTables &t) {
+  const Step &s = up.m.plan.steps[i];
+  const kern::ConvTGeom g = convt_geom(s);
+  std::vector<int32_t> tab = s.deconv->tab;
+  if (up.m.exec[i] == ExecKind::ConvTPhase) {
+    std::vector<float> packed(kern::convt2d_phase_packed_floats(g, tab.data()));
+    std::vector<int32_t> off(size_t(g.sh) * g.sw, 0);
+    kern::convt2d_phase_pack(g, tab.data(), s.W.data(), packed.data(), off.data());
+    tab.insert(tab.end(), off.begin(), off.end());
+    t.W = up(packed);
+  } else {
+    std::vector<float> packed(s.W.size());
+    kern::convt2d_generic_pack(g, s.W.data(), packed.data());
+    t.W = up(packed);
+  }
+  t.bias = up(s.bias);
+  t.tab = up(tab);
+}
+void launch_convt(const PassRunner &r, size_t i, const ConvTKernelTables &t) {
+  const Step &x = r.st[i];
+  if (r.m.exec[i] == ExecKind::ConvTPhase)
+    kern::convt2d_phase(r.stream, r.buf(x.in0), t.W, t.bias, r.buf(x.out), t.tab, r.nr, convt_geom(x), x.deconv->max_phase_pixels, act_of(x), r.cq(x.out));
+  else
+    kern::convt2d_generic(r.stream, r.buf(x.in0), t.W, t.bias, r.buf(x.out), t.tab, r.nr, convt_geom(x), act_of(x), r.cq(x.in0), r.cq(x.out));
+}
+
+// ---- Resize / Upsample (resize.hip): the row and column source tables ----
+void upload_resize(const Step &s, ResizeTables &t, const Upload &up) {
+  t.row_idx = up(s.deconv->row_idx);
+  t.col_idx = up(s.deconv->col_idx);
+  t.row_wgt = up(s.deconv->row_wgt);
+  t.col_wgt = up(s.deconv->col_wgt);
+}
+void launch_resize(const PassRunner &r, const Step &x, const ResizeTables &t) {
+  kern::resize2d(r.stream, r.buf(x.in0), r.buf(x.out), r.nr, int(x.C), int(x.H), int(x.Wd), int(x.OH), int(x.OW), t.row_idx, t.col_idx, t.row_wgt, t.col_wgt,
+                 x.deconv->linear, r.cq(x.in0));
+}
+
 // ---- the plain family: the step's constants as the lowering left them (Conv2d: packed for the generic kernel); its launches are the head
 // of PassRunner::launch_plain, right below ----
 void upload_plain(const Step &s, PlainTables &t, const Upload &up) {
@@ -385,6 +432,8 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::Nearest: launch_nearest(*this, x, d.nearest); break;
     case StepKind::Prep: launch_prep(*this, x, d.prep); break;
     case StepKind::Recurrent: launch_rnn(*this, x, d.rnn); break;
+    case StepKind::ConvTranspose2d: launch_convt(*this, i, d.convt); break;
+    case StepKind::Resize2d: launch_resize(*this, x, d.resize); break;
     // the steps without tables
     case StepKind::Unary: kern::unary(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], act_of(x)); break;
     case StepKind::BinaryAct:
@@ -446,6 +495,8 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::Nearest: return upload_nearest(s, d.nearest, up);
     case StepKind::Prep: return upload_prep(s, d.prep, up);
     case StepKind::Recurrent: return upload_rnn(s, d.rnn, up);
+    case StepKind::ConvTranspose2d: return upload_convt(up, i, d.convt);
+    case StepKind::Resize2d: return upload_resize(s, d.resize, up);
     default: return;  // (no tables)
   }
 }

@@ -22,6 +22,7 @@
 
 #include "attention.hpp"
 #include "common.hpp"
+#include "deconv.hpp"
 #include "nearest.hpp"
 #include "plan.hpp"
 #include "prep.hpp"
@@ -608,6 +609,11 @@ struct Lowerer {
           set_act(n, act.buf, act_shape, true);
           return;
         }
+        if (p && p->kind == StepKind::ConvTranspose2d && p->act == Act::None && size_t(p->Mo) == C) {
+          convt_fold_affine(*p, sc, sh, label);
+          set_act(n, act.buf, act_shape, true);
+          return;
+        }
         if (p && p->kind == StepKind::Conv2d && p->act == Act::None && size_t(p->Mo) == C) {  // into the conv's weights and bias
           const size_t per_m = size_t(p->K);
           for (size_t mo = 0; mo < C; mo++)
@@ -1148,7 +1154,8 @@ struct Lowerer {
                              p->kind == StepKind::BinaryConst || p->kind == StepKind::BinaryAct;
       const bool qdense_act = quantised_layer(*p) && !p->qy.on && (act == Act::Relu || act == Act::Clip);  // on `real`, before the requantisation
       const bool hdense_act = p->kind == StepKind::HDense && cur_half && int(act) >= 1 && int(act) <= kMaxMfmaFusedAct;  // r = half(act(float(r)))
-      if (p->act == Act::None && (takes_act || qdense_act || hdense_act) && (!mfma_step || mfma_fusable(act))) {
+      const bool convt_act = p->kind == StepKind::ConvTranspose2d && int(act) >= 1 && int(act) <= kMaxMfmaFusedAct;  // kinds 1..5 in its epilogue
+      if (p->act == Act::None && (takes_act || qdense_act || hdense_act || convt_act) && (!mfma_step || mfma_fusable(act))) {
         p->act = act;
         p->act_a = pa;
         p->act_b = pb;
@@ -1461,6 +1468,181 @@ struct Lowerer {
     return {a.shape[0], s.Mo, s.OH, s.OW};
   }
 
+  // ---- ConvTranspose / Resize / Upsample: the operators that make a tensor spatially larger (host/deconv.hpp) ----
+  // scale / shift per output channel into a transposed convolution's weights [C, M/g, kh, kw] and bias, in f64, rounded once
+  static void convt_fold_affine(Step &p, const std::vector<double> &sc, const std::vector<double> &sh, const std::string &label) {
+    const int64_t Cg = p.C / p.groups, Mg = p.Mo / p.groups, taps = p.kh * p.kw;
+    for (int64_t c = 0; c < p.C; c++)
+      for (int64_t ml = 0; ml < Mg; ml++) {
+        const double f = sc[size_t((c / Cg) * Mg + ml)];
+        float *w = p.W.data() + (c * Mg + ml) * taps;
+        for (int64_t t = 0; t < taps; t++) w[t] = float(f * double(w[t]));
+      }
+    if (p.bias.empty()) p.bias.assign(size_t(p.Mo), 0.f);
+    for (int64_t mo = 0; mo < p.Mo; mo++) p.bias[size_t(mo)] = float(sc[size_t(mo)] * double(p.bias[size_t(mo)]) + sh[size_t(mo)]);
+    p.origin += "+" + label;
+  }
+  void conv_transpose(const NodeDef &n) {
+    const Val &a = get(n, 0);
+    if (a.is_const || (a.shape.size() != 3 && a.shape.size() != 4)) bad_form(n, "the input must be an [N,C,L] or [N,C,H,W] activation (rank 3 or 4), got " + shape_str(a.shape));
+    const bool one_d = a.shape.size() == 3;
+    const Val &w = get(n, 1);
+    if (!w.is_const || w.c->dtype != onnx::kFloat) bad_form(n, "W must be a constant f32 tensor");
+    if (has_input(n, 2) && (!get(n, 2).is_const || get(n, 2).c->dtype != onnx::kFloat)) bad_form(n, "B must be a constant f32 tensor");
+    if (w.shape.size() != a.shape.size()) bad_form(n, "W " + shape_str(w.shape) + " does not have the rank of the input " + shape_str(a.shape));
+    Step s;
+    s.kind = StepKind::ConvTranspose2d;
+    s.in0 = a.buf;
+    s.C = a.shape[1]; s.H = one_d ? 1 : a.shape[2]; s.Wd = one_d ? a.shape[2] : a.shape[3];
+    s.kh = one_d ? 1 : w.shape[2]; s.kw = one_d ? w.shape[2] : w.shape[3];
+    s.groups = n.attr_i("group", 1);
+    if (s.groups < 1 || s.C % s.groups != 0) bad_form(n, "C = " + std::to_string(s.C) + " is not a multiple of group = " + std::to_string(s.groups));
+    if (w.shape[0] != s.C || w.shape[1] < 1) bad_form(n, "W " + shape_str(w.shape) + " disagrees with C = " + std::to_string(s.C) + " input channels ([C, M/group, kh, kw])");
+    if (auto *ks = n.attr_ints("kernel_shape")) {
+      const bool ok = one_d ? (ks->size() == 1 && (*ks)[0] == s.kw) : (ks->size() == 2 && (*ks)[0] == s.kh && (*ks)[1] == s.kw);
+      if (!ok) bad_form(n, "kernel_shape disagrees with W " + shape_str(w.shape));
+    }
+    s.Mo = w.shape[1] * s.groups;
+    const size_t nsp = one_d ? 1 : 2;
+    auto two = [&](const char *name, int64_t dflt, int64_t &h, int64_t &wd) {
+      h = wd = dflt;
+      if (auto *p = n.attr_ints(name)) {
+        if (p->size() != nsp) bad_form(n, std::string(name) + " must have one entry per spatial axis");
+        if (one_d) wd = (*p)[0]; else { h = (*p)[0]; wd = (*p)[1]; }
+      }
+    };
+    int64_t oph, opw, osh = -1, osw = -1;
+    two("strides", 1, s.sh, s.sw);
+    two("dilations", 1, s.dh, s.dw);
+    two("output_padding", 0, oph, opw);
+    const bool has_os = n.attr_ints("output_shape") != nullptr;
+    if (has_os) two("output_shape", -1, osh, osw);
+    const int64_t lim = int64_t(1) << 20;
+    if (s.sh < 1 || s.sw < 1 || s.sh > lim || s.sw > lim) bad_form(n, "strides must be >= 1");
+    if (s.dh < 1 || s.dw < 1 || s.dh > lim || s.dw > lim) bad_form(n, "dilations must be >= 1");
+    if (s.kh < 1 || s.kw < 1 || s.kh > kConvTMaxKernel || s.kw > kConvTMaxKernel)
+      bad_form(n, "kernel extents must be 1.." + std::to_string(kConvTMaxKernel) + " (the cap of the transposed-convolution kernels' tap tables)");
+    if (oph < 0 || opw < 0 || oph >= std::max(s.sh, s.dh) || opw >= std::max(s.sw, s.dw))
+      bad_form(n, "output_padding must be smaller than max(stride, dilation) on its axis");
+    if (s.H > lim || s.Wd > lim) bad_form(n, "spatial extent out of range");
+    const std::string ap = n.attr_s("auto_pad", "NOTSET");
+    if (ap != "NOTSET" && ap != "VALID" && ap != "SAME_UPPER" && ap != "SAME_LOWER") bad_form(n, "auto_pad " + ap);
+    if (auto *p = n.attr_ints("pads")) {
+      if (p->size() != 2 * nsp) bad_form(n, "pads must have two entries per spatial axis");
+      if (one_d) { s.pl = (*p)[0]; s.pr = (*p)[1]; }
+      else { s.pt = (*p)[0]; s.pl = (*p)[1]; s.pb = (*p)[2]; s.pr = (*p)[3]; }
+    }
+    if (ap == "VALID") s.pt = s.pl = s.pb = s.pr = 0;
+    const bool same = ap == "SAME_UPPER" || ap == "SAME_LOWER";
+    if (has_os || same) {  // the total padding follows from the wanted extent, split as the operator specification says
+      if (one_d) osh = 1;  // (the H axis of the [N,C,1,L] form)
+      auto split = [&](int64_t in, int64_t st, int64_t k, int64_t d, int64_t op, int64_t want, int64_t &p0, int64_t &p1) {
+        if (!has_os) want = in * st;
+        const int64_t total = st * (in - 1) + op + (k - 1) * d + 1 - want;
+        if (total < 0) bad_form(n, "negative pads: the output extent " + std::to_string(want) + " cannot be reached (it needs a total padding of " + std::to_string(total) + ")");
+        p0 = ap == "SAME_UPPER" ? total / 2 : total - total / 2;
+        p1 = total - p0;
+      };
+      if (!one_d) split(s.H, s.sh, s.kh, s.dh, oph, osh, s.pt, s.pb);
+      split(s.Wd, s.sw, s.kw, s.dw, opw, osw, s.pl, s.pr);
+    }
+    if (s.pt < 0 || s.pl < 0 || s.pb < 0 || s.pr < 0) bad_form(n, "negative pads");
+    if (s.pt > lim || s.pl > lim || s.pb > lim || s.pr > lim) bad_form(n, "pads out of range");
+    s.OH = (s.H - 1) * s.sh - s.pt - s.pb + s.dh * (s.kh - 1) + oph + 1;
+    s.OW = (s.Wd - 1) * s.sw - s.pl - s.pr + s.dw * (s.kw - 1) + opw + 1;
+    if (s.OH < 1 || s.OW < 1) bad_form(n, "negative extents: the output would be " + std::to_string(s.OH) + " x " + std::to_string(s.OW));
+    s.W = w.c->f32;
+    if (int64_t(s.W.size()) != prod({s.C, w.shape[1], s.kh, s.kw})) bad_form(n, "W " + shape_str(w.shape) + " disagrees with its payload");
+    if (has_input(n, 2)) {
+      s.bias = get(n, 2).c->f32;
+      if (int64_t(s.bias.size()) != s.Mo) bad_form(n, "B has " + std::to_string(s.bias.size()) + " entries for M = " + std::to_string(s.Mo) + " output channels");
+    }
+    s.K = (s.C / s.groups) * s.kh * s.kw;
+    s.M = s.Mo;
+    auto pack = std::make_shared<DeconvPack>();
+    pack->out_pad_h = oph;
+    pack->out_pad_w = opw;
+    convt_build_phases(s, *pack);
+    s.deconv = pack;
+    std::vector<int64_t> shape = {a.shape[0], s.Mo, s.OH, s.OW};
+    if (one_d) shape = {a.shape[0], s.Mo, s.OW};
+    emit(std::move(s), n, shape);
+  }
+
+  void resize(const NodeDef &n) {
+    const bool upsample = n.op == "Upsample";
+    const Val &a = get(n, 0);
+    if (a.is_const || (a.shape.size() != 3 && a.shape.size() != 4)) bad_form(n, "the input must be an [N,C,L] or [N,C,H,W] activation, got " + shape_str(a.shape));
+    const bool one_d = a.shape.size() == 3;
+    const size_t rank = a.shape.size();
+    std::string mode = n.attr_s("mode", "nearest");
+    if (mode == "bilinear") mode = "linear";  // (the spelling of early Upsample exports)
+    if (mode != "nearest" && mode != "linear") bad_form(n, "mode " + mode + " (only nearest and linear)");
+    const bool old_form = upsample || m.opset < 11;  // Upsample and Resize-10: asymmetric coordinates, nearest by floor
+    const std::string coord = old_form ? "asymmetric" : n.attr_s("coordinate_transformation_mode", "half_pixel");
+    const std::string nearest_mode = old_form ? "floor" : n.attr_s("nearest_mode", "round_prefer_floor");
+    if (coord != "half_pixel" && coord != "pytorch_half_pixel" && coord != "asymmetric" && coord != "align_corners")
+      bad_form(n, "coordinate_transformation_mode " + coord);
+    if (nearest_mode != "round_prefer_floor" && nearest_mode != "round_prefer_ceil" && nearest_mode != "floor" && nearest_mode != "ceil")
+      bad_form(n, "nearest_mode " + nearest_mode);
+    if (n.attr_i("antialias", 0) != 0) bad_form(n, "antialias = 1");
+    if (n.attr_i("exclude_outside", 0) != 0) bad_form(n, "exclude_outside = 1");
+    if (n.attr_s("keep_aspect_ratio_policy", "stretch") != "stretch") bad_form(n, "keep_aspect_ratio_policy " + n.attr_s("keep_aspect_ratio_policy", "stretch"));
+    if (n.attrs.count("axes")) bad_form(n, "the axes attribute");
+    // scales (floats) or sizes (integers), one per axis of the input; roi is ignored
+    std::vector<double> scales;
+    std::vector<int64_t> sizes;
+    const size_t scales_at = (upsample || m.opset < 11) ? 1 : 2;
+    if (upsample && m.opset < 9) {
+      if (auto *at = n.attr("scales")) scales.assign(at->floats.begin(), at->floats.end());
+    } else if (has_input(n, scales_at)) {
+      const Val &v = get(n, scales_at);
+      if (!v.is_const || v.c->dtype != onnx::kFloat) bad_form(n, "scales must be a constant");
+      scales.assign(v.c->f32.begin(), v.c->f32.end());
+    }
+    if (!old_form && has_input(n, 3)) {
+      const Val &v = get(n, 3);
+      if (!v.is_const || v.c->dtype != onnx::kInt64) bad_form(n, "sizes must be a constant (or fold from the shape of the input)");
+      sizes = v.c->i64;
+    }
+    if (scales.empty() == sizes.empty()) bad_form(n, "exactly one of scales and sizes must be given");
+    if ((scales.empty() ? sizes.size() : scales.size()) != rank) bad_form(n, "scales / sizes must have one entry per axis of the input");
+    const int64_t in_h = one_d ? 1 : a.shape[2], in_w = one_d ? a.shape[2] : a.shape[3];
+    int64_t out_h = 1, out_w;
+    double scale_h = 1.0, scale_w;
+    const int64_t lim = int64_t(1) << 20;
+    auto axis = [&](size_t ax, int64_t in, int64_t &out, double &sc) {
+      if (!scales.empty()) {
+        sc = scales[ax];
+        if (!(sc > 0.0) || !std::isfinite(sc) || sc * double(in) > double(lim)) bad_form(n, "scale out of range");
+        out = int64_t(std::floor(double(in) * sc));
+      } else {
+        out = sizes[ax];
+        if (out < 1 || out > lim) bad_form(n, "size out of range");
+        sc = double(out) / double(in);
+      }
+      if (out < 1) bad_form(n, "empty spatial output");
+    };
+    if (!scales.empty() ? (scales[0] != 1.0 || scales[1] != 1.0) : (sizes[1] != a.shape[1] || (sizes[0] != 0 && sizes[0] != a.shape[0] && a.shape[0] > 0)))
+      bad_form(n, "scaling of the N or C axis");
+    if (!one_d) axis(2, in_h, out_h, scale_h);
+    axis(rank - 1, in_w, out_w, scale_w);
+    Step s;
+    s.kind = StepKind::Resize2d;
+    s.in0 = a.buf;
+    s.C = a.shape[1]; s.H = in_h; s.Wd = in_w; s.Mo = s.C; s.OH = out_h; s.OW = out_w;
+    auto pack = std::make_shared<DeconvPack>();
+    pack->linear = mode == "linear";
+    pack->coord_mode = coord;
+    pack->nearest_mode = nearest_mode;
+    resize_axis_table(in_h, out_h, scale_h, pack->linear, coord, nearest_mode, pack->row_idx, pack->row_wgt);
+    resize_axis_table(in_w, out_w, scale_w, pack->linear, coord, nearest_mode, pack->col_idx, pack->col_wgt);
+    s.deconv = pack;
+    std::vector<int64_t> shape = {a.shape[0], s.C, out_h, out_w};
+    if (one_d) shape = {a.shape[0], s.C, out_w};
+    emit(std::move(s), n, shape);
+  }
+
   void batchnorm(const NodeDef &n) {
     const Val &a = get(n, 0);
     if (a.is_const || a.shape.size() < 2) unsupported(n, "bad input");
@@ -1477,6 +1659,16 @@ struct Lowerer {
     }
     std::vector<int64_t> shape = a.shape;
     if (Step *p = fusable_producer(n, 0)) {
+      if (p->kind == StepKind::ConvTranspose2d && p->act == Act::None && p->Mo == C) {  // fold into the transposed convolution (f64, one rounding)
+        std::vector<double> dsc((size_t)C), dsh((size_t)C);
+        for (int64_t c = 0; c < C; c++) {
+          dsc[size_t(c)] = double(sc[size_t(c)]) / std::sqrt(double(var[size_t(c)]) + double(eps));
+          dsh[size_t(c)] = double(bi[size_t(c)]) - double(mu[size_t(c)]) * dsc[size_t(c)];
+        }
+        convt_fold_affine(*p, dsc, dsh, "BatchNormalization");
+        set_act(n, a.buf, shape, true);
+        return;
+      }
       if (p->kind == StepKind::Conv2d && p->act == Act::None) {  // fold into conv
         const int64_t per_m = p->K;
         for (int64_t mo = 0; mo < p->Mo; mo++)
@@ -2813,6 +3005,8 @@ struct Lowerer {
     else if (op == "Softmax") softmax(n, false);
     else if (op == "LogSoftmax") softmax(n, true);
     else if (op == "Conv") conv(n);
+    else if (op == "ConvTranspose") conv_transpose(n);
+    else if (op == "Resize" || op == "Upsample") resize(n);
     else if (op == "BatchNormalization") batchnorm(n);
     else if (op == "MaxPool") pool(n, true);
     else if (op == "AveragePool") pool(n, false);
@@ -4029,6 +4223,7 @@ double Plan::flops_per_row() const {
     if (s.kind == StepKind::Dense || s.kind == StepKind::QDense || s.kind == StepKind::HDense) f += 2.0 * double(s.rep) * double(s.K) * double(s.M);
     else if (s.kind == StepKind::Attention) f += 4.0 * double(s.attn_T) * double(s.attn_T) * double(s.attn_heads * s.attn_dh);
     else if (s.kind == StepKind::Conv2d || s.kind == StepKind::QConv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
+    else if (s.kind == StepKind::ConvTranspose2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.H) * double(s.Wd);  // (C/g) kh kw taps per input pixel and output channel
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
     else if (s.kind == StepKind::Nearest) f += 2.0 * double(s.nearest->F) * double(s.nearest->M);
     else if (s.kind == StepKind::Recurrent) f += 2.0 * double(s.rnn->T * s.rnn->D * s.rnn->G * s.rnn->H) * double(s.rnn->F + s.rnn->H);
@@ -4037,7 +4232,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -4101,6 +4296,27 @@ std::string Plan::describe_json() const {
       o << ",\"T\":" << s.attn_T << ",\"heads\":" << s.attn_heads << ",\"dh\":" << s.attn_dh << ",\"scale\":" << double(s.attn_scale) << ",\"mask\":" << (s.cst.empty() ? "false" : "true")
         << ",\"packed_qkv\":" << (s.in0 == s.in1 && s.in1 == s.in2 ? "true" : "false");
     if (s.kind == StepKind::Conv2d) o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"k\":[" << s.kh << "," << s.kw << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
+    if (s.kind == StepKind::ConvTranspose2d) {
+      const DeconvPack &q = *s.deconv;
+      o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"group\":" << s.groups << ",\"k\":[" << s.kh << "," << s.kw << "],\"strides\":[" << s.sh << "," << s.sw << "],\"pads\":[" << s.pt
+        << "," << s.pl << "," << s.pb << "," << s.pr << "],\"dilations\":[" << s.dh << "," << s.dw << "],\"output_padding\":[" << q.out_pad_h << "," << q.out_pad_w
+        << "],\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "],\"bias\":" << (s.bias.empty() ? "false" : "true") << ",\"phases\":[";
+      for (size_t a = 0; a < q.hphase.size(); a++)
+        for (size_t b = 0; b < q.wphase.size(); b++) {
+          const ConvTAxisPhase &hp = q.hphase[a], &wp = q.wphase[b];
+          o << (a + b ? "," : "") << "{\"phase\":[" << a << "," << b << "],\"first\":[" << hp.out0 << "," << wp.out0 << "],\"pixels\":[" << hp.count << "," << wp.count << "],\"taps\":[";
+          for (size_t i = 0; i < hp.tap.size(); i++)
+            for (size_t j = 0; j < wp.tap.size(); j++) o << (i + j ? "," : "") << "[" << hp.tap[i] << "," << wp.tap[j] << "]";
+          o << "],\"source_offsets\":[";  // per tap: the input pixel of the phase's pixel (j, i) is (j, i) + this
+          for (size_t i = 0; i < hp.tap.size(); i++)
+            for (size_t j = 0; j < wp.tap.size(); j++) o << (i + j ? "," : "") << "[" << hp.q[i] << "," << wp.q[j] << "]";
+          o << "]}";
+        }
+      o << "]";
+    }
+    if (s.kind == StepKind::Resize2d)
+      o << ",\"C\":" << s.C << ",\"mode\":\"" << (s.deconv->linear ? "linear" : "nearest") << "\",\"coordinate_transformation_mode\":\"" << s.deconv->coord_mode << "\""
+        << (s.deconv->linear ? std::string() : ",\"nearest_mode\":\"" + s.deconv->nearest_mode + "\"") << ",\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
     if (s.kind == StepKind::QConv2d)
       o << ",\"C\":" << s.C << ",\"k\":[" << s.kh << "," << s.kw << "],\"strides\":[" << s.sh << "," << s.sw << "],\"pads\":[" << s.pt << "," << s.pl << "," << s.pb << "," << s.pr
         << "],\"dilations\":[" << s.dh << "," << s.dw << "],\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";

@@ -20,6 +20,7 @@ struct SvmPack;   // host/svm.hpp
 struct PrepPack;  // host/prep.hpp
 struct RnnPack;   // host/recurrent.hpp
 struct NearestPack;  // host/nearest.hpp
+struct DeconvPack;   // host/deconv.hpp
 
 // Kinds 1..5 may be fused into the epilogue of a Dense / Conv2d step (the MFMA kernels resolve them at
 // compile time); the rest run in the elementwise kernels (fused into Binary*/AffineChannel or as a Unary step).
@@ -68,6 +69,8 @@ enum class StepKind : int {
   Nearest = 32,       // distances of in0 [rows, F] to a constant set (NearestPack, nearest.hip): out = d2 / sqrt(d2) [rows, set size], or the per-slice best-M lists (out_mode: host/nearest.hpp NearestOut)
   NearestReduce = 33, // in0 = those lists -> the label [rows], the M nearest indices or their distances [rows, M]
   HDense = 28,        // float16 MatMul / Gemm on the f16 matrix cores: half operands, f32 accumulation, half results served as f32 values (Step::hW, h_bias_mode; hdense.hip)
+  ConvTranspose2d = 34,  // transposed convolution by stride phases (the Conv2d geometry fields: C, H, Wd = the input, Mo, OH, OW = the output; W = the ONNX weights [C, M/g, kh, kw]; DeconvPack: the phase tap lists; deconv.hip)
+  Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
 enum HalfBias : int { kHalfBiasNone = 0, kHalfBiasGemm = 1, kHalfBiasMatmulAdd = 2 };
@@ -141,6 +144,7 @@ struct Step {
   std::shared_ptr<const PrepPack> prep;
   std::shared_ptr<const RnnPack> rnn;
   std::shared_ptr<const NearestPack> nearest;
+  std::shared_ptr<const DeconvPack> deconv;  // ConvTranspose2d: phase tap lists; Resize2d: source tables
   int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut, RowReduce: ReduceOp, TopK: 0 values / 1 indices, Nearest*: NearestOut
   // Attention: Q = in0, K = in1, V = in2 (the same buffer three times when the projections are merged), each [rows, T, ld] with the head
   // block of head g at columns off + g * dh of a step; mask (cst): [T, T] added to the scaled scores, -inf = no weight, empty = none

@@ -2677,3 +2677,390 @@ def autoencoder(F: int = 12, H: int = 4, seed: int = 31) -> tuple[bytes, dict]:
              node("Sub", ["X", "rec"], ["diff"], name="sub"), node("Mul", ["diff", "diff"], ["sq"], name="mul"),
              node("ReduceMean", ["sq"], ["err"], [attr_ints("axes", [1]), attr_i("keepdims", 0)], name="mean")]
     return model("autoencoder", nodes, [tensor(k, v) for k, v in w.items()], [value_info("X", ["N", F])], [value_info("err", ["N"])], opset=13), w
+
+
+# ------------------------------------------------------------------------------------------
+# decoders: ConvTranspose, Resize and Upsample with their float64 references.  The references are written
+# from the operator specification's definitions: they play the oracle's part for these operators.
+# ------------------------------------------------------------------------------------------
+
+def _pair(v) -> tuple:
+    return (int(v), int(v)) if np.isscalar(v) else tuple(int(t) for t in v)
+
+
+def _pads4(p) -> tuple:
+    if np.isscalar(p):
+        return (int(p),) * 4
+    p = tuple(int(t) for t in p)
+    return p if len(p) == 4 else (p[0], p[1], p[0], p[1])
+
+
+def conv_transpose_pads(in_hw, k, strides, dilations, output_padding, output_shape=None, auto_pad: str = "NOTSET", pads=(0, 0, 0, 0)) -> tuple:
+    """(pt, pl, pb, pr) of a ConvTranspose as the specification derives them from output_shape / auto_pad."""
+    if auto_pad == "VALID":
+        return (0, 0, 0, 0)
+    if output_shape is None and auto_pad == "NOTSET":
+        return _pads4(pads)
+    begin, end = [], []
+    for ax in range(2):
+        want = output_shape[ax] if output_shape is not None else in_hw[ax] * strides[ax]
+        total = strides[ax] * (in_hw[ax] - 1) + output_padding[ax] + (k[ax] - 1) * dilations[ax] + 1 - want
+        b = total // 2 if auto_pad == "SAME_UPPER" else total - total // 2
+        begin.append(b)
+        end.append(total - b)
+    return (begin[0], begin[1], end[0], end[1])
+
+
+def conv_transpose_reference(x, w, b=None, strides=1, pads=0, dilations=1, groups: int = 1, output_padding=0) -> np.ndarray:
+    """ONNX ConvTranspose in float64, from its definition: every input pixel (ih, iw) adds x * w[:, :, ky, kx] at output position
+    (ih * sh + ky * dh - pt, iw * sw + kx * dw - pl).  x [N,C,H,W] with w [C,M/g,kh,kw], or x [N,C,L] with w [C,M/g,k]."""
+    x, w = np.asarray(x, np.float64), np.asarray(w, np.float64)
+    if x.ndim == 3:
+        one = lambda v: v if np.isscalar(v) else v[0]
+        p = (pads, pads) if np.isscalar(pads) else tuple(pads)
+        y = conv_transpose_reference(x[:, :, None, :], w[:, :, None, :], b, (1, one(strides)), (0, p[0], 0, p[1]), (1, one(dilations)), groups,
+                                     (0, one(output_padding)))
+        return y[:, :, 0, :]
+    (sh, sw), (pt, pl, pb, pr), (dh, dw), (oph, opw) = _pair(strides), _pads4(pads), _pair(dilations), _pair(output_padding)
+    n, c, h, wd = x.shape
+    _, mg, kh, kw = w.shape
+    cg = c // groups
+    fh, fw = (h - 1) * sh + dh * (kh - 1) + 1 + oph, (wd - 1) * sw + dw * (kw - 1) + 1 + opw
+    full = np.zeros((n, mg * groups, fh, fw), np.float64)
+    for g in range(groups):
+        for ky in range(kh):
+            for kx in range(kw):
+                full[:, g * mg:(g + 1) * mg, ky * dh:ky * dh + (h - 1) * sh + 1:sh, kx * dw:kx * dw + (wd - 1) * sw + 1:sw] += np.einsum(
+                    "nchw,cm->nmhw", x[:, g * cg:(g + 1) * cg], w[g * cg:(g + 1) * cg, :, ky, kx], optimize=True)
+    out = full[:, :, pt:fh - pb, pl:fw - pr]
+    if b is not None:
+        out = out + np.asarray(b, np.float64)[None, :, None, None]
+    return out
+
+
+def resize_axis_reference(n_in: int, n_out: int, scale: float, mode: str, coord: str, nearest_mode: str = "round_prefer_floor"):
+    """One axis of Resize: nearest -> the source index per output coordinate; linear -> (i0, i1, w).  float64, the specification's formulas."""
+    o = np.arange(n_out, dtype=np.float64)
+    if coord == "half_pixel":
+        x = (o + 0.5) / scale - 0.5
+    elif coord == "pytorch_half_pixel":
+        x = (o + 0.5) / scale - 0.5 if n_out > 1 else np.zeros_like(o)
+    elif coord == "align_corners":
+        x = o * (n_in - 1) / (n_out - 1) if n_out > 1 else np.zeros_like(o)
+    elif coord == "asymmetric":
+        x = o / scale
+    else:
+        raise ValueError(coord)
+    if mode == "nearest":
+        r = {"round_prefer_floor": np.ceil(x - 0.5), "round_prefer_ceil": np.floor(x + 0.5), "floor": np.floor(x), "ceil": np.ceil(x)}[nearest_mode]
+        return np.clip(r, 0, n_in - 1).astype(np.int64)
+    x = np.clip(x, 0, n_in - 1)
+    i0 = np.floor(x).astype(np.int64)
+    return i0, np.minimum(i0 + 1, n_in - 1), x - i0
+
+
+def resize_reference(x, sizes=None, scales=None, mode: str = "nearest", coord: str = "half_pixel", nearest_mode: str = "round_prefer_floor") -> np.ndarray:
+    """ONNX Resize (nearest / linear) of x [N,C,H,W] or [N,C,L] in float64; `sizes` / `scales` cover the spatial axes only."""
+    x = np.asarray(x, np.float64)
+    if x.ndim == 3:
+        one = lambda v: None if v is None else (1, v if np.isscalar(v) else v[-1])
+        return resize_reference(x[:, :, None, :], one(sizes), one(scales), mode, coord, nearest_mode)[:, :, 0, :]
+    out = x
+    for ax in (2, 3):
+        n_in = x.shape[ax]
+        if scales is not None:
+            sc = float(_pair_f(scales)[ax - 2])
+            n_out = int(math.floor(n_in * sc))
+        else:
+            n_out = int(_pair(sizes)[ax - 2])
+            sc = n_out / n_in
+        t = resize_axis_reference(n_in, n_out, sc, mode, coord, nearest_mode)
+        if mode == "nearest":
+            out = np.take(out, t, axis=ax)
+        else:
+            i0, i1, w = t
+            shape = [1, 1, 1, 1]
+            shape[ax] = n_out
+            w = w.reshape(shape)
+            out = (1.0 - w) * np.take(out, i0, axis=ax) + w * np.take(out, i1, axis=ax)
+    return out
+
+
+def _pair_f(v) -> tuple:
+    return (float(v), float(v)) if np.isscalar(v) else tuple(float(t) for t in v)
+
+
+class _DecoderNet:
+    """Records a small convolutional graph twice: as ONNX nodes and as layer descriptors decoder_reference() evaluates in float64."""
+
+    def __init__(self, seed: int, integer: bool = False):
+        self.rng = np.random.default_rng(seed)
+        self.integer = integer
+        self.nodes, self.inits, self.layers, self.count = [], [], [], 0
+
+    def draw(self, shape, fan):
+        if self.integer:
+            return self.rng.integers(-8, 9, size=shape).astype(np.float32)
+        return (self.rng.uniform(-1, 1, size=shape) / math.sqrt(max(fan, 1))).astype(np.float32)
+
+    def _name(self, op):
+        self.count += 1
+        return f"{op}{self.count}"
+
+    def const(self, name, arr):
+        self.inits.append(tensor(name, arr))
+        return name
+
+    def conv(self, x, c, m, k=3, s=1, p=0, groups=1, bias=True, w=None, one_d=False):
+        nm = self._name("conv")
+        k2, s2, p4 = _pair(k), _pair(s), _pads4(p)
+        if one_d:
+            k2, s2, p4 = (1, k2[1]), (1, s2[1]), (0, p4[1], 0, p4[3])
+        w = self.draw((m, c // groups) + k2, (c // groups) * k2[0] * k2[1]) if w is None else w
+        b = self.draw((m,), (c // groups) * k2[0] * k2[1]) if bias else None
+        ins = [x, self.const(nm + "_W", w[:, :, 0, :] if one_d else w)] + ([self.const(nm + "_B", b)] if bias else [])
+        attrs = ([attr_ints("kernel_shape", [k2[1]]), attr_ints("strides", [s2[1]]), attr_ints("pads", [p4[1], p4[3]])] if one_d else
+                 [attr_ints("kernel_shape", k2), attr_ints("strides", s2), attr_ints("pads", p4)]) + [attr_i("group", groups)]
+        self.nodes.append(node("Conv", ins, [nm], attrs, name=nm))
+        self.layers.append(("conv", nm, [x], dict(w=w, b=b, strides=s2, pads=p4, groups=groups)))
+        return nm
+
+    def convt(self, x, c, m, k=2, s=2, p=0, d=1, groups=1, op=0, bias=True, w=None, one_d=False, output_shape=None, auto_pad="NOTSET", in_hw=None,
+              name=None):
+        nm = name or self._name("convt")
+        k2, s2, d2, op2 = _pair(k), _pair(s), _pair(d), _pair(op)
+        if one_d:
+            k2, s2, d2, op2 = (1, k2[1]), (1, s2[1]), (1, d2[1]), (0, op2[1])
+        w = self.draw((c, m // groups) + k2, (c // groups) * k2[0] * k2[1]) if w is None else w
+        b = self.draw((m,), (c // groups) * k2[0] * k2[1]) if bias else None
+        ins = [x, self.const(nm + "_W", w[:, :, 0, :] if one_d else w)] + ([self.const(nm + "_B", b)] if bias else [])
+        sel = (lambda v: [v[1]]) if one_d else (lambda v: list(v))
+        attrs = [attr_ints("strides", sel(s2)), attr_ints("dilations", sel(d2)), attr_i("group", groups)]
+        if any(op2):
+            attrs.append(attr_ints("output_padding", sel(op2)))
+        if output_shape is not None or auto_pad != "NOTSET":
+            if output_shape is not None:
+                attrs.append(attr_ints("output_shape", list(output_shape)))
+            if auto_pad != "NOTSET":
+                attrs.append(attr_s("auto_pad", auto_pad))
+            p4 = conv_transpose_pads(in_hw, k2, s2, d2, op2, output_shape, auto_pad)
+        else:
+            p4 = _pads4(p)
+            if one_d:
+                p4 = (0, p4[1], 0, p4[3])
+            attrs.append(attr_ints("pads", [p4[1], p4[3]] if one_d else p4))
+        self.nodes.append(node("ConvTranspose", ins, [nm], attrs, name=nm))
+        self.layers.append(("convt", nm, [x], dict(w=w, b=b, strides=s2, pads=p4, dilations=d2, groups=groups, output_padding=op2)))
+        return nm
+
+    def bn(self, x, c):
+        nm = self._name("bn")
+        sc, bi, mu = (self.rng.uniform(0.5, 1.5, c).astype(np.float32), self.rng.uniform(-0.5, 0.5, c).astype(np.float32),
+                      self.rng.uniform(-0.5, 0.5, c).astype(np.float32))
+        var = self.rng.uniform(0.5, 2.0, c).astype(np.float32)
+        ins = [x] + [self.const(f"{nm}_{k}", v) for k, v in (("scale", sc), ("bias", bi), ("mean", mu), ("var", var))]
+        self.nodes.append(node("BatchNormalization", ins, [nm], [attr_f("epsilon", 1e-5)], name=nm))
+        self.layers.append(("bn", nm, [x], dict(scale=sc, bias=bi, mean=mu, var=var, eps=float(np.float32(1e-5)))))
+        return nm
+
+    def act(self, x, op="Relu"):
+        nm = self._name(op.lower())
+        self.nodes.append(node(op, [x], [nm], name=nm))
+        self.layers.append((op.lower(), nm, [x], {}))
+        return nm
+
+    def concat(self, xs):
+        nm = self._name("concat")
+        self.nodes.append(node("Concat", list(xs), [nm], [attr_i("axis", 1)], name=nm))
+        self.layers.append(("concat", nm, list(xs), {}))
+        return nm
+
+    def resize(self, x, rank=4, scales=None, sizes=None, mode="nearest", coord="asymmetric", nearest_mode="floor", op="Resize", opset=13, attrs_extra=(),
+               lead=None):
+        nm = self._name("resize")
+        lead_s = [1.0, 1.0]
+        if scales is not None:
+            sp = list(_pair_f(scales))[-(rank - 2):]  # (the spatial axes: the last one alone for [N,C,L])
+            sc = self.const(nm + "_scales", np.asarray(lead_s + sp, np.float32) if lead is None else np.asarray(list(lead) + sp, np.float32))
+        if op == "Upsample":
+            attrs = [attr_s("mode", mode)]
+            if opset < 9:
+                attrs.append(attr_floats("scales", lead_s + sp))
+                ins = [x]
+            else:
+                ins = [x, sc]
+        elif opset < 11:
+            attrs, ins = [attr_s("mode", mode)], [x, sc]
+        else:
+            attrs = [attr_s("mode", mode), attr_s("coordinate_transformation_mode", coord), attr_s("nearest_mode", nearest_mode)]
+            if scales is not None:
+                ins = [x, "", sc]
+            else:
+                ins = [x, "", "", self.const(nm + "_sizes", np.asarray(list(lead if lead is not None else (0, sizes[0])) + list(sizes[1:]), np.int64))]
+        self.nodes.append(node(op, ins, [nm], list(attrs) + list(attrs_extra), name=nm))
+        old = op == "Upsample" or opset < 11
+        self.layers.append(("resize", nm, [x], dict(scales=None if scales is None else sp, sizes=None if sizes is None else list(sizes[1:]), mode=mode,
+                                                    coord="asymmetric" if old else coord, nearest_mode="floor" if old else nearest_mode)))
+        return nm
+
+    def finish(self, name, x_info, out, out_dims, opset=13, extra=None):
+        spec = {"layers": self.layers, "output": out}
+        spec.update(extra or {})
+        return model(name, self.nodes, self.inits, [x_info], [value_info(out, out_dims)], opset=opset), spec
+
+
+def decoder_reference(spec: dict, x, upto: str | None = None) -> np.ndarray:
+    """The graph a _DecoderNet recorded, in float64 (BatchNormalization as the operator defines it, unfolded)."""
+    vals = {"X": np.asarray(x, np.float64).reshape((len(x),) + tuple(spec["in_shape"]))}
+    for op, out, ins, p in spec["layers"]:
+        a = vals[ins[0]]
+        if op == "conv":
+            squeeze = a.ndim == 3
+            a4 = a[:, :, None, :] if squeeze else a
+            y = _conv_taps(a4, p["w"].astype(np.float64), p["strides"], p["pads"], (1, 1), p["groups"], 0.0)
+            if p["b"] is not None:
+                y = y + p["b"].astype(np.float64)[None, :, None, None]
+            y = y[:, :, 0, :] if squeeze else y
+        elif op == "convt":
+            squeeze = a.ndim == 3
+            a4 = a[:, :, None, :] if squeeze else a
+            y = conv_transpose_reference(a4, p["w"], p["b"], p["strides"], p["pads"], p["dilations"], p["groups"], p["output_padding"])
+            y = y[:, :, 0, :] if squeeze else y
+        elif op == "bn":
+            sh = (1, -1) + (1,) * (a.ndim - 2)
+            f = lambda k: p[k].astype(np.float64).reshape(sh)
+            y = (a - f("mean")) / np.sqrt(f("var") + p["eps"]) * f("scale") + f("bias")
+        elif op == "relu":
+            y = np.maximum(a, 0.0)
+        elif op == "sigmoid":
+            y = 1.0 / (1.0 + np.exp(-a))
+        elif op == "tanh":
+            y = np.tanh(a)
+        elif op == "softplus":
+            y = np.log1p(np.exp(a))
+        elif op == "concat":
+            y = np.concatenate([vals[i] for i in ins], axis=1)
+        elif op == "resize":
+            y = resize_reference(a, sizes=p["sizes"], scales=p["scales"], mode=p["mode"], coord=p["coord"], nearest_mode=p["nearest_mode"])
+        elif op == "reshape":
+            y = a.reshape((len(a),) + tuple(p["shape"]))
+        elif op == "sub":
+            y = a - vals[ins[1]]
+        elif op == "sumsquare":
+            y = (a * a).sum(axis=1)
+        else:
+            raise ValueError(op)
+        vals[out] = y
+        if out == upto:
+            break
+    return vals[upto or spec["output"]]
+
+
+def conv_transpose_model(geom: dict, pre: bool = False, post: bool = False, act: str | None = None, bn: bool = False, integer: bool = False,
+                         bias: bool = True, seed: int = 5, name: str = "convt") -> tuple[bytes, dict]:
+    """One ConvTranspose layer `name`.  geom: C, M, H, W (H absent: 1-D, input [N,C,W]), k, s, p (pads), d, g, op (output_padding), output_shape,
+    auto_pad.  pre: an identity 1x1 Conv in front (the layer then reads a channel-quad tensor where C is whole quads); post: an identity
+    1x1 ConvTranspose behind it (the layer then writes one).  integer: weights and bias are whole numbers in [-8, 8].  Returns (model, spec)."""
+    one_d = "H" not in geom
+    c, m, h, wd = geom["C"], geom["M"], geom.get("H", 1), geom["W"]
+    net = _DecoderNet(seed, integer)
+    cur = "X"
+    if pre:
+        eye = np.eye(c, dtype=np.float32)[:, :, None, None]
+        cur = net.conv(cur, c, c, 1, 1, 0, bias=False, w=eye, one_d=one_d)
+    cur = net.convt(cur, c, m, geom.get("k", 2), geom.get("s", 2), geom.get("p", 0), geom.get("d", 1), geom.get("g", 1), geom.get("op", 0), bias=bias,
+                    one_d=one_d, output_shape=geom.get("output_shape"), auto_pad=geom.get("auto_pad", "NOTSET"), in_hw=(h, wd), name=name)
+    if bn:
+        cur = net.bn(cur, m)
+    if act:
+        cur = net.act(cur, act)
+    if post:
+        eye = np.eye(m, dtype=np.float32)[:, :, None, None]
+        cur = net.convt(cur, m, m, 1, 1, 0, bias=False, w=eye, one_d=one_d)
+    in_shape = (c, wd) if one_d else (c, h, wd)
+    out_shape = decoder_reference({"layers": net.layers, "output": cur, "in_shape": in_shape}, np.zeros((1,) + in_shape)).shape[1:]
+    return net.finish("conv_transpose", value_info("X", ["N"] + list(in_shape)), cur, ["N"] + list(out_shape), extra={"in_shape": in_shape, "out_shape": out_shape})
+
+
+def resize_model(c: int = 3, hw=(4, 4), scales=None, sizes=None, mode: str = "nearest", coord: str = "half_pixel", nearest_mode: str = "round_prefer_floor",
+                 op: str = "Resize", opset: int = 13, pre: bool = False, post: bool = False, attrs_extra=(), lead=None) -> tuple[bytes, dict]:
+    """One Resize (or Upsample) node.  hw: (H, W), or (L,) for an [N,C,L] input; sizes: the output's (H, W) / (L,).  pre / post: identity 1x1 layers
+    around it as in conv_transpose_model (the node then runs on channel-quad tensors).  lead: the N and C entries of scales / sizes."""
+    one_d = len(hw) == 1
+    net = _DecoderNet(0)
+    cur = "X"
+    if pre:
+        cur = net.conv(cur, c, c, 1, 1, 0, bias=False, w=np.eye(c, dtype=np.float32)[:, :, None, None], one_d=one_d)
+    rank = 3 if one_d else 4
+    cur = net.resize(cur, rank, scales=scales, sizes=None if sizes is None else [c] + list(sizes), mode=mode, coord=coord, nearest_mode=nearest_mode, op=op, opset=opset,
+                     attrs_extra=attrs_extra, lead=lead)
+    if post:
+        cur = net.convt(cur, c, c, 1, 1, 0, bias=False, w=np.eye(c, dtype=np.float32)[:, :, None, None], one_d=one_d)
+    in_shape = (c,) + tuple(hw)
+    out_shape = decoder_reference({"layers": net.layers, "output": cur, "in_shape": in_shape}, np.zeros((1,) + in_shape)).shape[1:]
+    return net.finish("resize", value_info("X", ["N"] + list(in_shape)), cur, ["N"] + list(out_shape), opset=opset, extra={"in_shape": in_shape, "out_shape": out_shape})
+
+
+def conv_autoencoder(channels: Sequence[int] = (3, 16, 32), size: int = 16, seed: int = 41) -> tuple[bytes, dict]:
+    """Image autoencoder: stride-2 Conv 3x3 + Relu per level down, ConvTranspose k4 s2 p1 + BatchNormalization + Relu per level up, the last
+    level ConvTranspose + Sigmoid.  Returns (model, spec) for decoder_reference."""
+    net = _DecoderNet(seed)
+    cur = "X"
+    for a, b in zip(channels[:-1], channels[1:]):
+        cur = net.act(net.conv(cur, a, b, 3, 2, 1), "Relu")
+    rev = list(channels[::-1])
+    for i, (a, b) in enumerate(zip(rev[:-1], rev[1:])):
+        cur = net.convt(cur, a, b, 4, 2, 1)
+        cur = net.act(cur, "Sigmoid") if i == len(rev) - 2 else net.act(net.bn(cur, b), "Relu")
+    shape = (channels[0], size, size)
+    return net.finish("conv_autoencoder", value_info("X", ["N"] + list(shape)), cur, ["N"] + list(shape), extra={"in_shape": shape})
+
+
+def conv1d_autoencoder(T: int = 16, F: int = 4, hidden: Sequence[int] = (8, 16), seed: int = 43) -> tuple[bytes, dict]:
+    """Anomaly score of a window of sensor readings served from a flat table: the T * F columns (feature-major: column f * T + t) are reshaped
+    to [N, F, T] inside the model, encoded by stride-2 Conv1d + Relu, decoded by ConvTranspose1d k4 s2 p1, and the output is the
+    reconstruction error sum((x - rec)^2) per row (ReduceSumSquare)."""
+    net = _DecoderNet(seed)
+    net.const("shape_ft", np.asarray([0, F, T], np.int64))
+    net.nodes.append(node("Reshape", ["X", "shape_ft"], ["x3"], name="to_window"))
+    net.layers.append(("reshape", "x3", ["X"], dict(shape=(F, T))))
+    cur, chans = "x3", [F] + list(hidden)
+    for a, b in zip(chans[:-1], chans[1:]):
+        cur = net.act(net.conv(cur, a, b, 3, 2, 1, one_d=True), "Relu")
+    rev = chans[::-1]
+    for i, (a, b) in enumerate(zip(rev[:-1], rev[1:])):
+        cur = net.convt(cur, a, b, 4, 2, 1, one_d=True)
+        if i < len(rev) - 2:
+            cur = net.act(cur, "Relu")
+    net.const("shape_flat", np.asarray([0, F * T], np.int64))
+    net.nodes.append(node("Reshape", [cur, "shape_flat"], ["rec"], name="to_columns"))
+    net.layers.append(("reshape", "rec", [cur], dict(shape=(F * T,))))
+    net.nodes.append(node("Sub", ["X", "rec"], ["diff"], name="diff"))
+    net.layers.append(("sub", "diff", ["X", "rec"], {}))
+    net.nodes.append(node("ReduceSumSquare", ["diff"], ["err"], [attr_ints("axes", [1]), attr_i("keepdims", 0)], name="error"))
+    net.layers.append(("sumsquare", "err", ["diff"], {}))
+    return net.finish("conv1d_autoencoder", value_info("X", ["N", T * F]), "err", ["N"], opset=13, extra={"in_shape": (T * F,)})
+
+
+def unet_small(in_ch: int = 3, out_ch: int = 3, size: int = 16, base: int = 8, seed: int = 47) -> tuple[bytes, dict]:
+    """Two-level U-Net: stride-2 stem and encoder convolutions, ConvTranspose k2 s2 up, a Concat skip, and a ConvTranspose k2 s2 head back to
+    the input's resolution."""
+    net = _DecoderNet(seed)
+    e1 = net.act(net.conv("X", in_ch, base, 3, 2, 1), "Relu")             # size / 2
+    e2 = net.act(net.conv(e1, base, 2 * base, 3, 2, 1), "Relu")           # size / 4
+    bott = net.act(net.conv(e2, 2 * base, 2 * base, 3, 1, 1), "Relu")
+    up = net.act(net.convt(bott, 2 * base, base, 2, 2), "Relu")           # size / 2
+    dec = net.act(net.conv(net.concat([up, e1]), 2 * base, base, 3, 1, 1), "Relu")
+    head = net.convt(dec, base, out_ch, 2, 2)                             # size
+    return net.finish("unet_small", value_info("X", ["N", in_ch, size, size]), head, ["N", out_ch, size, size], extra={"in_shape": (in_ch, size, size)})
+
+
+def upsample_decoder(latent: Sequence[int] = (8, 4, 4), out_ch: int = 3, seed: int = 53) -> tuple[bytes, dict]:
+    """The nn.Upsample spelling of a decoder: (Resize nearest x2, asymmetric / floor -> Conv 3x3) twice."""
+    c, h, w = latent
+    net = _DecoderNet(seed)
+    cur = net.resize("X", 4, scales=(2.0, 2.0))
+    cur = net.act(net.conv(cur, c, c, 3, 1, 1), "Relu")
+    cur = net.resize(cur, 4, scales=(2.0, 2.0))
+    cur = net.conv(cur, c, out_ch, 3, 1, 1)
+    return net.finish("upsample_decoder", value_info("X", ["N", c, h, w]), cur, ["N", out_ch, 4 * h, 4 * w], extra={"in_shape": (c, h, w)})
