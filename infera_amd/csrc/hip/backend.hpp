@@ -68,6 +68,7 @@ struct NearestTables { const float *ref = nullptr, *ref_norm = nullptr, *center 
 struct PrepTables { const uint32_t *desc = nullptr; const float *cst = nullptr, *tab = nullptr; };
 struct ConvTKernelTables { const float *W = nullptr, *bias = nullptr; const int *tab = nullptr; };  // ConvTranspose2d (W: packed for the step's kernel; tab: the phase tap tables)
 struct ResizeTables { const int *row_idx = nullptr, *col_idx = nullptr; const float *row_wgt = nullptr, *col_wgt = nullptr; };  // Resize2d
+struct SpatialNormTables { const float *gamma = nullptr, *beta = nullptr; };  // SpatialNorm (per channel: the same in either layout)
 struct RnnTables { const float *wr = nullptr, *bias = nullptr, *bias2 = nullptr, *h0 = nullptr, *c0 = nullptr; };
 struct DeviceStep {  // (a step fills the one struct of its family)
   PlainTables plain;
@@ -82,6 +83,7 @@ struct DeviceStep {  // (a step fills the one struct of its family)
   RnnTables rnn;
   ConvTKernelTables convt;
   ResizeTables resize;
+  SpatialNormTables spatialnorm;
 };
 
 // How the executor runs a step.

@@ -343,4 +343,14 @@ void convt2d_phase(hipStream_t s, const float *X, const float *Wp, const float *
 void resize2d(hipStream_t s, const float *X, float *Y, int64_t rows, int C, int H, int W, int OH, int OW, const int *row_idx, const int *col_idx,
               const float *row_wgt, const float *col_wgt, bool linear, bool cq);
 
+// ---- InstanceNormalization / GroupNormalization (spatialnorm.hip; host/spatialnorm.hpp) --------------
+// X, Y: [rows, C, S] in NCHW order or (cq) channel-quad planes; G groups of C / G channels; gamma, beta: [C].  false: beyond the kernel's caps
+// fused: where spatialnorm_fused_unit(C, S, G, cq) names a unit -- one pass, y = act(d / sqrtf(var + eps) * gamma + beta)
+bool spatialnorm_fused(hipStream_t s, const float *X, const float *gamma, const float *beta, float *Y, int64_t rows, int C, int S, int G, bool cq, float eps,
+                       ActParam act);
+// general: stats [rows, G, 3] = (mean, resid, 1 / sqrtf(var + eps)), then y = act(((x - mean) - resid) * inv * gamma + beta)
+bool spatialnorm_stats(hipStream_t s, const float *X, float *stats, int64_t rows, int C, int S, int G, bool cq, float eps);
+bool spatialnorm_apply(hipStream_t s, const float *X, const float *stats, const float *gamma, const float *beta, float *Y, int64_t rows, int C, int S, int G,
+                       bool cq, ActParam act);
+
 }  // namespace infera_hip::kern

@@ -5,6 +5,7 @@
 #include <sstream>
 
 #include "../host/deconv.hpp"
+#include "../host/spatialnorm.hpp"
 #include "runtime.hpp"
 
 namespace infera_hip {
@@ -62,7 +63,8 @@ struct Scheduler {
   int64_t spatial(int b) const { return is4d(b) ? m.plan.buf_shape[size_t(b)][2] * m.plan.buf_shape[size_t(b)][3] : int64_t(1); }
 
   void fuse_tabular();               // Dense x3 -> fused MLP, runs of small layers -> chain kernel, Dense + Softmax / ArgMax epilogues, tiled Dense
-  void decide_layout();              // channel-quad planes for convolutional plans (+ the weight / constant permutations that follow from it)
+  // channel-quad planes for convolutional plans (+ the weight / constant permutations that follow from it; commit = false: the decision alone)
+  void decide_layout(bool commit = true);
   void assign_conv_kernels();        // patch / tiled / depthwise kernels, the stem's fused MaxPool
   void assign_convt_kernels();       // transposed convolutions: the MFMA phase kernel where it applies, else the generic one
   void fuse_residual_adds();         // a block's Add (+ activation) into the epilogue of its last producer
@@ -180,7 +182,7 @@ void Scheduler::fuse_tabular() {
       m.exec[i] = ExecKind::DenseTiled;
 }
 
-void Scheduler::decide_layout() {
+void Scheduler::decide_layout(bool commit) {
   // ---- layout decision for convolutional plans ----
   bool any_conv = false, ok = true;
   std::string nchw_reason;  // first thing that keeps a convolutional plan out of the channel-quad layout (logged: it costs ~10x)
@@ -238,6 +240,7 @@ void Scheduler::decide_layout() {
                              s.kind == StepKind::BinaryAct || s.kind == StepKind::Unary || s.kind == StepKind::AffineChannel ||
                              s.kind == StepKind::CopyCols || s.kind == StepKind::SliceCols || s.kind == StepKind::LRN ||
                              s.kind == StepKind::ChannelShuffle ||
+                             s.kind == StepKind::SpatialNorm || s.kind == StepKind::SpatialStats ||  // (gamma and beta are indexed by channel: no permutation)
                              s.kind == StepKind::BinaryConst;  // (its per-row constant is permuted to channel-quad order below)
     // A channel slice is one contiguous block per sample in channel-quad planes only when it starts on a quad
     // boundary (its length is covered by the whole-quads check on the output tensor below): channels 2..5 of an
@@ -280,6 +283,7 @@ void Scheduler::decide_layout() {
       else refuse("an internal [N,C,H,W] tensor has " + std::to_string(m.plan.buf_shape[b][1]) + " channels (not whole quads)");
     }
   m.cq_mode = any_conv && ok;
+  if (!commit) return;
   if (any_conv && !ok)
     log_msg(1, "model '" + m.name + "': convolutional plan stays in NCHW (generic kernels, roughly 10x slower): " + nchw_reason);
   if (m.cq_mode)
@@ -579,7 +583,39 @@ void Scheduler::place_scratch(const std::vector<EffStep> &eff) {
   for (auto v : m.slot_per_row) m.scratch_per_row += v;
 }
 
+// InstanceNormalization / GroupNormalization layers whose work unit does not fit the fused kernel in the layout their tensor gets -- a group
+// beyond kSpatialNormFusedMaxE floats, or groups that straddle channel quads -- become SpatialStats -> SpatialNorm(in1 = the stats): the general
+// plan.  INFERA_SPATIALNORM_FUSED=0 (read when a model is scheduled): every layer (tests, A/B).  Runs before everything that indexes steps.
+// (An input read by the pair is read twice: classify_io counts two readers, so it is no single streaming reader of a zero-copy table.)
+void expand_spatial_norms(LoadedModel &m) {
+  auto &st = m.plan.steps;
+  if (std::none_of(st.begin(), st.end(), [](const Step &s) { return s.kind == StepKind::SpatialNorm && s.in1 < 0; })) return;
+  Scheduler(m).decide_layout(false);  // (the stats buffers are flat [rows, 3 G] tensors: they do not change the decision)
+  const bool fused = ScheduleKnobs::read().spatialnorm_fused;
+  std::vector<Step> out;
+  for (Step &s : st) {
+    if (s.kind == StepKind::SpatialNorm && s.in1 < 0) {
+      const bool cq = m.cq_mode && !m.nchw_buf[size_t(s.in0)];
+      if (!fused || spatialnorm_fused_unit(s.C, s.S, s.groups, cq) == kSpatialUnitNone) {
+        Step a;
+        a.kind = StepKind::SpatialStats;
+        a.in0 = s.in0;
+        a.C = s.C, a.S = s.S, a.H = s.H, a.Wd = s.Wd, a.groups = s.groups, a.ln_eps = s.ln_eps;
+        a.origin = s.origin + "[stats]";
+        m.plan.buf_shape.push_back({m.plan.buf_shape[size_t(s.in0)][0], 3 * s.groups});
+        m.plan.buf_per_row.push_back(3 * s.groups);
+        a.out = int(m.plan.buf_shape.size()) - 1;
+        s.in1 = a.out;
+        out.push_back(std::move(a));
+      }
+    }
+    out.push_back(std::move(s));
+  }
+  st = std::move(out);
+}
+
 void schedule(LoadedModel &m) {
+  expand_spatial_norms(m);
   Scheduler s(m);
   s.fuse_tabular();
   s.decide_layout();
@@ -672,6 +708,21 @@ std::string LoadedModel::describe_json() const {
            "\",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\"}";
     }
     if (!c.empty()) o << ",\"convt\":[" << c << "]";
+  }
+  {  // per SpatialNorm / SpatialStats step: the kernel that runs it, its groups, the layouts it reads and writes and the fused activation
+    static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
+                                 "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
+    std::string c;
+    for (size_t i = 0; i < exec.size(); i++) {
+      const Step &x = plan.steps[i];
+      if (x.kind != StepKind::SpatialNorm && x.kind != StepKind::SpatialStats) continue;
+      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)];
+      const bool out_cq = x.kind == StepKind::SpatialStats ? in_cq : cq_mode && !nchw_buf[size_t(x.out)];
+      c += std::string(c.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"kernel\":\"" +
+           (x.kind == StepKind::SpatialStats ? "spatialnorm_stats" : x.in1 < 0 ? "spatialnorm_fused" : "spatialnorm_apply") + "\",\"groups\":" + std::to_string(x.groups) +
+           ",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\",\"act\":\"" + acts[int(x.act)] + "\"}";
+    }
+    if (!c.empty()) o << ",\"spatialnorm\":[" << c << "]";
   }
   if (!chains.empty()) {
     o << ",\"chain_kernels\":[";

@@ -8,6 +8,7 @@
 #include "../host/onnx_model.hpp"
 #include "../host/prep.hpp"
 #include "../host/recurrent.hpp"
+#include "../host/spatialnorm.hpp"
 #include "../host/svm.hpp"
 #include "../host/trees.hpp"
 #include "runtime.hpp"
@@ -381,6 +382,22 @@ void launch_resize(const PassRunner &r, const Step &x, const ResizeTables &t) {
                  x.deconv->linear, r.cq(x.in0));
 }
 
+// ---- InstanceNormalization / GroupNormalization (host/spatialnorm.hpp, spatialnorm.hip): gamma and beta per channel; SpatialStats has no tables ----
+void upload_spatialnorm(const Step &s, SpatialNormTables &t, const Upload &up) {
+  t.gamma = up(s.scale);
+  t.beta = up(s.shift);
+}
+void launch_spatialnorm(const PassRunner &r, const Step &x, const SpatialNormTables &t) {
+  if (r.cq(x.in0) != r.cq(x.out)) throw InferaError::onnx("SpatialNorm '" + x.origin + "' would have to change the tensor's layout; there is no such kernel");
+  const bool ok = x.in1 < 0 ? kern::spatialnorm_fused(r.stream, r.buf(x.in0), t.gamma, t.beta, r.buf(x.out), r.nr, int(x.C), int(x.S), int(x.groups), r.cq(x.in0), x.ln_eps, act_of(x))
+                            : kern::spatialnorm_apply(r.stream, r.buf(x.in0), r.buf(x.in1), t.gamma, t.beta, r.buf(x.out), r.nr, int(x.C), int(x.S), int(x.groups), r.cq(x.in0), act_of(x));
+  if (!ok) throw InferaError::onnx("SpatialNorm kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+void launch_spatialstats(const PassRunner &r, const Step &x) {
+  if (!kern::spatialnorm_stats(r.stream, r.buf(x.in0), r.buf(x.out), r.nr, int(x.C), int(x.S), int(x.groups), r.cq(x.in0), x.ln_eps))
+    throw InferaError::onnx("SpatialStats kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+
 // ---- the plain family: the step's constants as the lowering left them (Conv2d: packed for the generic kernel); its launches are the head
 // of PassRunner::launch_plain, right below ----
 void upload_plain(const Step &s, PlainTables &t, const Upload &up) {
@@ -434,6 +451,8 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::Recurrent: launch_rnn(*this, x, d.rnn); break;
     case StepKind::ConvTranspose2d: launch_convt(*this, i, d.convt); break;
     case StepKind::Resize2d: launch_resize(*this, x, d.resize); break;
+    case StepKind::SpatialNorm: launch_spatialnorm(*this, x, d.spatialnorm); break;
+    case StepKind::SpatialStats: launch_spatialstats(*this, x); break;
     // the steps without tables
     case StepKind::Unary: kern::unary(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], act_of(x)); break;
     case StepKind::BinaryAct:
@@ -497,6 +516,7 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::Recurrent: return upload_rnn(s, d.rnn, up);
     case StepKind::ConvTranspose2d: return upload_convt(up, i, d.convt);
     case StepKind::Resize2d: return upload_resize(s, d.resize, up);
+    case StepKind::SpatialNorm: return upload_spatialnorm(s, d.spatialnorm, up);
     default: return;  // (no tables)
   }
 }

@@ -110,7 +110,8 @@ ScheduleKnobs ScheduleKnobs::read() {
   if (prec != "bf16x6" && prec != "fp32") log_msg(1, "INFERA_PRECISION='" + prec + "' is not one of bf16x6 | fp32: using the default (bf16x6)");
   return ScheduleKnobs{env_flag("INFERA_STEM_POOL", true), env_flag("INFERA_CHAIN_XCM", true), env_flag("INFERA_DENSE_XCM", true), prec != "fp32",
                        env_flag("INFERA_CONV_FOLD_SHORTCUT", true), env_flag("INFERA_QDENSE_BYTES", true), env_flag("INFERA_HDENSE_HALF", true),
-                       env_flag("INFERA_HDENSE", true), env_flag("INFERA_NEAREST", true), env_flag("INFERA_CONVT_MFMA", true)};
+                       env_flag("INFERA_HDENSE", true), env_flag("INFERA_NEAREST", true), env_flag("INFERA_CONVT_MFMA", true),
+                       env_flag("INFERA_SPATIALNORM_FUSED", true)};
 }
 
 void log_msg(int level, const std::string &msg) {

@@ -23,6 +23,7 @@
 #include "attention.hpp"
 #include "common.hpp"
 #include "deconv.hpp"
+#include "spatialnorm.hpp"
 #include "nearest.hpp"
 #include "plan.hpp"
 #include "prep.hpp"
@@ -609,6 +610,15 @@ struct Lowerer {
           set_act(n, act.buf, act_shape, true);
           return;
         }
+        if (p && p->kind == StepKind::SpatialNorm && p->act == Act::None && size_t(p->C) == C && size_t(p->S) == S) {  // into gamma and beta
+          for (size_t k = 0; k < C; k++) {
+            p->shift[k] = float(sc[k] * double(p->shift[k]) + sh[k]);
+            p->scale[k] = float(sc[k] * double(p->scale[k]));
+          }
+          p->origin += "+" + label;
+          set_act(n, act.buf, act_shape, true);
+          return;
+        }
         if (p && p->kind == StepKind::ConvTranspose2d && p->act == Act::None && size_t(p->Mo) == C) {
           convt_fold_affine(*p, sc, sh, label);
           set_act(n, act.buf, act_shape, true);
@@ -1155,7 +1165,8 @@ struct Lowerer {
       const bool qdense_act = quantised_layer(*p) && !p->qy.on && (act == Act::Relu || act == Act::Clip);  // on `real`, before the requantisation
       const bool hdense_act = p->kind == StepKind::HDense && cur_half && int(act) >= 1 && int(act) <= kMaxMfmaFusedAct;  // r = half(act(float(r)))
       const bool convt_act = p->kind == StepKind::ConvTranspose2d && int(act) >= 1 && int(act) <= kMaxMfmaFusedAct;  // kinds 1..5 in its epilogue
-      if (p->act == Act::None && (takes_act || qdense_act || hdense_act || convt_act) && (!mfma_step || mfma_fusable(act))) {
+      const bool norm_act = p->kind == StepKind::SpatialNorm && mfma_fusable(act);  // the kinds the convolution epilogues take
+      if (p->act == Act::None && (takes_act || qdense_act || hdense_act || convt_act || norm_act) && (!mfma_step || mfma_fusable(act))) {
         p->act = act;
         p->act_a = pa;
         p->act_b = pb;
@@ -1697,6 +1708,150 @@ struct Lowerer {
     s.scale = std::move(scale);
     s.shift = std::move(shift);
     emit(std::move(s), n, shape);
+  }
+
+  // ---- InstanceNormalization / GroupNormalization (host/spatialnorm.hpp): one SpatialNorm step ----------------------
+  // `a` [N,C,L] / [N,C,H,W] normalised over each of G channel groups with per-channel scale / shift; the result is bound to `out_name`
+  void spatial_norm_step(const NodeDef &n, const Val &a, int64_t G, std::vector<float> scale, std::vector<float> shift, float eps, const std::string &origin,
+                         const std::string &out_name) {
+    if (const std::string why = spatialnorm_refusal(a.shape, G, int64_t(scale.size()), int64_t(shift.size()), eps); !why.empty()) bad_form(n, why);
+    if (plan.buf_shape[size_t(a.buf)].size() != 4) bad_form(n, "the input " + shape_str(a.shape) + " is a window of a flat table, not an [N,C,L] / [N,C,H,W] tensor");
+    Step s;
+    s.kind = StepKind::SpatialNorm;
+    s.in0 = a.buf;
+    s.C = a.shape[1];
+    s.S = prod(a.shape, 2);
+    s.H = a.shape.size() == 4 ? a.shape[2] : 1;
+    s.Wd = a.shape.back();
+    s.groups = G;
+    s.scale = std::move(scale);
+    s.shift = std::move(shift);
+    s.ln_eps = eps;
+    s.origin = origin;
+    const std::vector<int64_t> shape = a.shape;
+    Val v;
+    v.buf = push_step(std::move(s), shape);
+    v.shape = shape;
+    vals[out_name] = v;
+    buf_names[v.buf].push_back(out_name);
+  }
+  // the activation input of a normalisation node and its constant scale / B
+  Val spatial_norm_input(const NodeDef &n, std::vector<float> *scale, std::vector<float> *bias) {
+    const Val a = get(n, 0);
+    if (a.is_const) bad_form(n, "the input must be an activation");
+    if (a.ra != 0) bad_form(n, "the input " + shape_str(a.shape) + " is a time-major value (its row axis is axis " + std::to_string(a.ra) + ")");
+    for (size_t i = 1; i <= 2; i++) {
+      if (!has_input(n, i)) bad_form(n, "scale and B are required");
+      const Val &c = get(n, i);
+      if (!c.is_const || c.c->dtype != onnx::kFloat) bad_form(n, "scale and B must be constant f32 tensors");
+      *(i == 1 ? scale : bias) = c.c->f32;
+    }
+    return a;
+  }
+  void instance_norm(const NodeDef &n) {
+    std::vector<float> sc, bi;
+    const Val a = spatial_norm_input(n, &sc, &bi);
+    const int64_t C = a.shape.size() >= 2 ? a.shape[1] : 0;
+    spatial_norm_step(n, a, std::max<int64_t>(C, 1), std::move(sc), std::move(bi), n.attr_f("epsilon", 1e-5f), node_label(n), n.outputs[0]);
+  }
+  // GroupNormalization: scale / bias per group under opset 18 (broadcast over the group's channels here), per channel under opset 21;
+  // stash_type only names the precision of the statistics, which is f32 here
+  void group_norm(const NodeDef &n) {
+    std::vector<float> sc, bi, scale, shift;
+    const Val a = spatial_norm_input(n, &sc, &bi);
+    if (m.opset < 18) bad_form(n, "GroupNormalization needs opset 18 or later");
+    const int64_t G = n.attr_i("num_groups", 0), C = a.shape.size() >= 2 ? a.shape[1] : 0;
+    if (G < 1) bad_form(n, "the num_groups attribute is required");
+    if (C > 0 && C % G != 0) bad_form(n, "num_groups = " + std::to_string(G) + " does not divide C = " + std::to_string(C));
+    const bool per_group = m.opset < 21;
+    if (C > 0 && (!spatialnorm_per_channel(sc, C, G, per_group, &scale) || !spatialnorm_per_channel(bi, C, G, per_group, &shift) || sc.size() != bi.size()))
+      bad_form(n, "scale / bias have " + std::to_string(sc.size()) + " and " + std::to_string(bi.size()) + " entries: opset " + std::to_string(m.opset) + " takes " +
+                      (per_group ? "num_groups = " + std::to_string(G) + " (or C = " + std::to_string(C) + ")" : "C = " + std::to_string(C)));
+    spatial_norm_step(n, a, G, std::move(scale), std::move(shift), n.attr_f("epsilon", 1e-5f), node_label(n), n.outputs[0]);
+  }
+
+  // The exporter's spelling of nn.GroupNorm below opset 18: Reshape(x, [0, G, -1]) -> InstanceNormalization(scale[G], B[G]) -> Reshape(back to
+  // x's shape, a constant or the folded Shape(x)) [-> Mul(gamma [C,1,1])] [-> Add(beta)].  The chain is found structurally before the walk
+  // (find_group_norms: operators and sole readers), anchored at the first Reshape; shapes and constants are checked when the walk reaches
+  // the anchor (false: every node lowers by its own rule), and the nodes behind it emit nothing.
+  struct GnMatch {
+    size_t inorm = 0, back = 0;
+  };
+  std::map<size_t, GnMatch> gn_at;  // index of the first Reshape -> the chain behind it
+  void find_group_norms(const std::vector<char> &live) {
+    for (size_t i = 0; i < m.nodes.size(); i++) {
+      const NodeDef &r = m.nodes[i];
+      if (!live[i] || absorbed[i] || r.op != "Reshape" || r.inputs.size() != 2 || r.outputs.empty()) continue;
+      const NodeDef *in = only_reader(r.outputs[0]);
+      if (!in || in->op != "InstanceNormalization" || in->inputs.size() != 3 || in->inputs[0] != r.outputs[0] || consumers_of[r.outputs[0]].size() != 1) continue;
+      const NodeDef *back = only_reader(in->outputs[0]);
+      if (!back || back->op != "Reshape" || back->inputs.size() != 2 || back->inputs[0] != in->outputs[0] || consumers_of[in->outputs[0]].size() != 1) continue;
+      gn_at[i] = GnMatch{size_t(in - m.nodes.data()), size_t(back - m.nodes.data())};
+    }
+  }
+  // a constant that multiplies / shifts x [N,C,...] per channel: C values shaped [C,1,1] / [1,C,1,1] (one spatial axis: [C,1] / [1,C,1])
+  const std::vector<float> *per_channel_const(const Val *c, const std::vector<int64_t> &x_shape) {
+    if (!c || !c->is_const || c->c->dtype != onnx::kFloat) return nullptr;
+    const size_t r = x_shape.size(), cr = c->shape.size();
+    if (cr != r && cr != r - 1) return nullptr;
+    for (size_t i = 0; i < cr; i++)
+      if (c->shape[i] != (i + (r - cr) == 1 ? x_shape[1] : 1)) return nullptr;
+    return &c->c->f32;
+  }
+  bool exporter_group_norm(const GnMatch &gm, const NodeDef &first) {
+    const NodeDef &inorm = m.nodes[gm.inorm], &back = m.nodes[gm.back];
+    const Val *xp = find_value(first.inputs[0]);
+    if (!xp || xp->is_const || xp->pv || xp->ra != 0 || xp->buf < 0 || (xp->shape.size() != 3 && xp->shape.size() != 4)) return false;
+    const Val x = *xp;
+    const int64_t C = x.shape[1], S = prod(x.shape, 2);
+    const Val *t = find_value(first.inputs[1]);
+    if (C < 1 || S < 1 || !t || !t->is_const || t->c->dtype != onnx::kInt64 || t->c->i64.size() != 3) return false;
+    const auto &tg = t->c->i64;
+    const int64_t G = tg[1];
+    if (G < 1 || C % G != 0 || !(tg[0] == 0 || (tg[0] > 0 && tg[0] == x.shape[0])) || !(tg[2] == -1 || tg[2] == (C / G) * S)) return false;
+    const Val *sv = find_value(inorm.inputs[1]), *bv = find_value(inorm.inputs[2]);
+    if (!sv || !bv || !sv->is_const || !bv->is_const || sv->c->dtype != onnx::kFloat || bv->c->dtype != onnx::kFloat || int64_t(sv->c->f32.size()) != G ||
+        int64_t(bv->c->f32.size()) != G)
+      return false;
+    // the Reshape back: a constant that spells x's shape (0 = copy, -1 / the fixed batch in front), or Shape(x) not folded yet
+    if (const Val *bs = find_value(back.inputs[1])) {
+      if (!bs->is_const || bs->c->dtype != onnx::kInt64 || bs->c->i64.size() != x.shape.size()) return false;
+      const auto &b = bs->c->i64;
+      if (!(b[0] == 0 || b[0] == -1 || (b[0] > 0 && b[0] == x.shape[0]))) return false;
+      for (size_t i = 1; i < b.size(); i++)
+        if (b[i] != x.shape[i] && b[i] != 0) return false;
+    } else {
+      auto pit = producer_of.find(back.inputs[1]);
+      if (pit == producer_of.end()) return false;
+      const NodeDef &sh = m.nodes[pit->second];
+      const Val *of = sh.op == "Shape" && sh.inputs.size() == 1 && sh.attrs.empty() ? find_value(sh.inputs[0]) : nullptr;
+      if (!of || of->is_const || of->buf != x.buf || of->shape != x.shape) return false;
+    }
+    std::vector<const NodeDef *> nodes = {&inorm, &back};
+    const NodeDef *last = &back;
+    std::vector<float> gamma, beta;
+    if (const NodeDef *mul = only_reader(last->outputs[0]); mul && mul->op == "Mul" && consumers_of[last->outputs[0]].size() == 1)
+      if (const std::vector<float> *g = per_channel_const(const_operand(*mul, last->outputs[0]), x.shape)) {
+        gamma = *g;
+        nodes.push_back(last = mul);
+      }
+    if (const NodeDef *add = only_reader(last->outputs[0]); add && add->op == "Add" && consumers_of[last->outputs[0]].size() == 1)
+      if (const std::vector<float> *b = per_channel_const(const_operand(*add, last->outputs[0]), x.shape)) {
+        beta = *b;
+        nodes.push_back(last = add);
+      }
+    const float eps = inorm.attr_f("epsilon", 1e-5f);
+    if (!spatialnorm_refusal(x.shape, G, C, C, eps).empty() || plan.buf_shape[size_t(x.buf)].size() != 4) return false;
+    std::vector<float> scale, shift;
+    spatialnorm_fold_inner(sv->c->f32, bv->c->f32, gamma, beta, C, &scale, &shift);
+    std::string origin = node_label(first);
+    for (const NodeDef *q : nodes) {
+      absorbed[size_t(q - m.nodes.data())] = 1;
+      origin += "+" + node_label(*q);
+    }
+    spatial_norm_step(first, x, G, std::move(scale), std::move(shift), eps, origin, last->outputs[0]);
+    if (cur_half) mark_half(last->outputs[0]);
+    return true;
   }
 
   void pool(const NodeDef &n, bool is_max) {
@@ -2956,7 +3111,8 @@ struct Lowerer {
         if (it != vals.end() && it->second.padded()) unsupported(n, "the output of a Pad node can only feed a Conv (its padding is folded into the convolution)");
       }
     static const std::set<std::string> reads_time_major = {"Transpose", "Squeeze", "Unsqueeze", "Reshape", "Identity", "Dropout", "Flatten", "Shape",
-                                                           "Gather", "Slice", "LSTM", "GRU", "RNN"};
+                                                           "Gather", "Slice", "LSTM", "GRU", "RNN",
+                                                           "InstanceNormalization", "GroupNormalization"};  // (refused in their own words)
     check_row_axis(n, reads_time_major.count(op) > 0);
     if (op == "DynamicQuantizeLinear")
       bad_form(n, "its scale spans all rows of a call, so a row's result would depend on its chunk; quantise statically (QuantizeLinear with constant scales)");
@@ -3000,6 +3156,8 @@ struct Lowerer {
     else if (op == "ArgMin") argmin(n);
     else if (op == "TopK") topk(n);
     else if (op == "LayerNormalization") layer_norm(n);
+    else if (op == "InstanceNormalization") instance_norm(n);
+    else if (op == "GroupNormalization") group_norm(n);
     else if (op == "ArgMax") argmax(n);
     else if (op == "Identity" || op == "Dropout" || op == "Flatten" || op == "Reshape" || op == "Squeeze" || op == "Unsqueeze") reshape_like(n);
     else if (op == "Softmax") softmax(n, false);
@@ -4120,6 +4278,7 @@ struct Lowerer {
     const std::set<std::string> region_inputs = find_regions(live);
     find_attention(live);
     if (nearest_enabled) find_nearest(live);
+    find_group_norms(live);
     {
       int64_t off = 0;
       for (const auto &v : m.inputs) {
@@ -4162,6 +4321,7 @@ struct Lowerer {
       } else if (attn_at.count(ni)) lower_typed(n, [&] { lower_attention(attn_at.at(ni), n); });
       else if (nearest_at.count(ni)) lower_nearest(nearest_at.at(ni));
       else if (absorbed[ni]) continue;
+      else if (gn_at.count(ni)) lower_typed(n, [&] { if (!exporter_group_norm(gn_at.at(ni), n)) lower_node(n); });
       else lower_typed(n, [&] { lower_node(n); });
     }
     // one output is served: the first (engine.rs:146-149) unless the load call selected another
@@ -4232,7 +4392,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -4317,6 +4477,17 @@ std::string Plan::describe_json() const {
     if (s.kind == StepKind::Resize2d)
       o << ",\"C\":" << s.C << ",\"mode\":\"" << (s.deconv->linear ? "linear" : "nearest") << "\",\"coordinate_transformation_mode\":\"" << s.deconv->coord_mode << "\""
         << (s.deconv->linear ? std::string() : ",\"nearest_mode\":\"" + s.deconv->nearest_mode + "\"") << ",\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
+    if (s.kind == StepKind::SpatialNorm || s.kind == StepKind::SpatialStats)
+      o << ",\"C\":" << s.C << ",\"groups\":" << s.groups << ",\"E\":" << (s.C / s.groups) * s.S << ",\"hw\":[" << (s.H > 0 ? s.H : 1) << "," << (s.H > 0 ? s.Wd : s.S)
+        << "],\"epsilon\":" << double(s.ln_eps);
+    if (s.kind == StepKind::SpatialNorm) {  // gamma and beta as their f32 bit patterns: what the lowering folded, for checks without a GPU
+      auto bits = [](const std::vector<float> &v) {
+        std::vector<uint32_t> b(v.size());
+        if (!v.empty()) std::memcpy(b.data(), v.data(), v.size() * sizeof(float));
+        return json_int_array(b);
+      };
+      o << ",\"scale_bits\":" << bits(s.scale) << ",\"shift_bits\":" << bits(s.shift);
+    }
     if (s.kind == StepKind::QConv2d)
       o << ",\"C\":" << s.C << ",\"k\":[" << s.kh << "," << s.kw << "],\"strides\":[" << s.sh << "," << s.sw << "],\"pads\":[" << s.pt << "," << s.pl << "," << s.pb << "," << s.pr
         << "],\"dilations\":[" << s.dh << "," << s.dw << "],\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";

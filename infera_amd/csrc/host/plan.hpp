@@ -70,6 +70,8 @@ enum class StepKind : int {
   NearestReduce = 33, // in0 = those lists -> the label [rows], the M nearest indices or their distances [rows, M]
   HDense = 28,        // float16 MatMul / Gemm on the f16 matrix cores: half operands, f32 accumulation, half results served as f32 values (Step::hW, h_bias_mode; hdense.hip)
   ConvTranspose2d = 34,  // transposed convolution by stride phases (the Conv2d geometry fields: C, H, Wd = the input, Mo, OH, OW = the output; W = the ONNX weights [C, M/g, kh, kw]; DeconvPack: the phase tap lists; deconv.hip)
+  SpatialNorm = 36,   // InstanceNormalization / GroupNormalization over the (C / groups) * S elements of each of `groups` channel groups of in0 [rows, C, S]: y = act((x - mean) / sqrt(var + ln_eps) * scale[c] + shift[c]); in1 = -1: the fused kernel, else in1 = a SpatialStats result (host/spatialnorm.hpp, spatialnorm.hip)
+  SpatialStats = 37,  // out [rows, groups, 3] = (mean, resid, 1 / sqrt(var + ln_eps)) of each group of in0: the first half of the general SpatialNorm plan (the scheduler inserts it, schedule.cpp)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum

@@ -2903,6 +2903,72 @@ class _DecoderNet:
                                                     coord="asymmetric" if old else coord, nearest_mode="floor" if old else nearest_mode)))
         return nm
 
+    def silu(self, x):
+        """x * Sigmoid(x), as exporters spell SiLU / Swish"""
+        nm = self._name("silu")
+        self.nodes.append(node("Sigmoid", [x], [nm + "_sig"], name=nm + "_sig"))
+        self.nodes.append(node("Mul", [x, nm + "_sig"], [nm], name=nm))
+        self.layers.append(("silu", nm, [x], {}))
+        return nm
+
+    def add(self, a, b):
+        nm = self._name("add")
+        self.nodes.append(node("Add", [a, b], [nm], name=nm))
+        self.layers.append(("add", nm, [a, b], {}))
+        return nm
+
+    def _norm_params(self, n):
+        return self.rng.uniform(0.5, 1.5, n).astype(np.float32), self.rng.uniform(-0.5, 0.5, n).astype(np.float32)
+
+    def inorm(self, x, c, eps=1e-5, name=None):
+        """InstanceNormalization with per-channel scale and B"""
+        nm = name or self._name("inorm")
+        g, b = self._norm_params(c)
+        self.nodes.append(node("InstanceNormalization", [x, self.const(nm + "_scale", g), self.const(nm + "_B", b)], [nm], [attr_f("epsilon", eps)], name=nm))
+        self.layers.append(("inorm", nm, [x], dict(groups=c, gamma=g, beta=b, eps=float(np.float32(eps)))))
+        return nm
+
+    def gnorm(self, x, c, groups, form="op21", inner=None, eps=1e-5, name=None, back="const", affine="mul_add", x_shape=None):
+        """GroupNormalization.  form "op18": scale / bias per group (opset 18); "op21": per channel (opset 21); "exporter": what torch.onnx
+        writes for nn.GroupNorm below opset 18 -- Reshape [0, G, -1], InstanceNormalization with `inner` = (scale[G], B[G]) (None: ones and
+        zeros), Reshape back (`back`: a constant shape, or "shape": Shape(x); x_shape = x's extents behind the row axis), then Mul(gamma
+        [C,1,1]) and Add(beta) (`affine`: "mul_add", "mul", "none").  The layer records the per-channel gamma and beta of the whole spelling
+        in float64."""
+        nm = name or self._name("gnorm")
+        e32 = float(np.float32(eps))
+        if form in ("op18", "op21"):
+            g, b = self._norm_params(groups if form == "op18" else c)
+            self.nodes.append(node("GroupNormalization", [x, self.const(nm + "_scale", g), self.const(nm + "_bias", b)], [nm],
+                                   [attr_i("num_groups", groups), attr_f("epsilon", eps)], name=nm))
+            rep = c // groups if form == "op18" else 1
+            self.layers.append(("gnorm", nm, [x], dict(groups=groups, gamma=np.repeat(g, rep), beta=np.repeat(b, rep), eps=e32)))
+            return nm
+        if form != "exporter":
+            raise ValueError(form)
+        s, b = (np.ones(groups, np.float32), np.zeros(groups, np.float32)) if inner is None else (np.asarray(inner[0], np.float32), np.asarray(inner[1], np.float32))
+        gamma, beta = self._norm_params(c)
+        one = (1,) * len(x_shape[1:])
+        self.nodes.append(node("Reshape", [x, self.const(nm + "_to_groups", np.asarray([0, groups, -1], np.int64))], [nm + "_g"], name=nm + "_split"))
+        self.nodes.append(node("InstanceNormalization", [nm + "_g", self.const(nm + "_scale", s), self.const(nm + "_B", b)], [nm + "_n"], [attr_f("epsilon", eps)], name=nm + "_inorm"))
+        if back == "shape":
+            self.nodes.append(node("Shape", [x], [nm + "_shape"], name=nm + "_shape"))
+            shape_in = nm + "_shape"
+        else:
+            shape_in = self.const(nm + "_back", np.asarray([0] + list(x_shape), np.int64))
+        cur = nm if affine == "none" else nm + "_r"
+        self.nodes.append(node("Reshape", [nm + "_n", shape_in], [cur], name=nm + "_merge"))
+        if affine in ("mul", "mul_add"):
+            nxt = nm if affine == "mul" else nm + "_m"
+            self.nodes.append(node("Mul", [cur, self.const(nm + "_gamma", gamma.reshape((c,) + one))], [nxt], name=nm + "_mul"))
+            cur = nxt
+        if affine == "mul_add":
+            self.nodes.append(node("Add", [cur, self.const(nm + "_beta", beta.reshape((1, c) + one))], [nm], name=nm + "_add"))
+        g64 = gamma.astype(np.float64) if affine != "none" else np.ones(c)
+        b64 = beta.astype(np.float64) if affine == "mul_add" else np.zeros(c)
+        rep = c // groups
+        self.layers.append(("gnorm", nm, [x], dict(groups=groups, gamma=np.repeat(s.astype(np.float64), rep) * g64, beta=np.repeat(b.astype(np.float64), rep) * g64 + b64, eps=e32)))
+        return nm
+
     def finish(self, name, x_info, out, out_dims, opset=13, extra=None):
         spec = {"layers": self.layers, "output": out}
         spec.update(extra or {})
@@ -2944,6 +3010,12 @@ def decoder_reference(spec: dict, x, upto: str | None = None) -> np.ndarray:
             y = resize_reference(a, sizes=p["sizes"], scales=p["scales"], mode=p["mode"], coord=p["coord"], nearest_mode=p["nearest_mode"])
         elif op == "reshape":
             y = a.reshape((len(a),) + tuple(p["shape"]))
+        elif op in ("inorm", "gnorm"):
+            y = spatialnorm_reference(a, p["groups"], p["gamma"], p["beta"], p["eps"])
+        elif op == "silu":
+            y = a / (1.0 + np.exp(-a))
+        elif op == "add":
+            y = a + vals[ins[1]]
         elif op == "sub":
             y = a - vals[ins[1]]
         elif op == "sumsquare":
@@ -3042,9 +3114,13 @@ def conv1d_autoencoder(T: int = 16, F: int = 4, hidden: Sequence[int] = (8, 16),
     return net.finish("conv1d_autoencoder", value_info("X", ["N", T * F]), "err", ["N"], opset=13, extra={"in_shape": (T * F,)})
 
 
-def unet_small(in_ch: int = 3, out_ch: int = 3, size: int = 16, base: int = 8, seed: int = 47) -> tuple[bytes, dict]:
+def unet_small(in_ch: int = 3, out_ch: int = 3, size: int = 16, base: int = 8, seed: int = 47, norm: str | None = None, groups: int = 4) -> tuple[bytes, dict]:
     """Two-level U-Net: stride-2 stem and encoder convolutions, ConvTranspose k2 s2 up, a Concat skip, and a ConvTranspose k2 s2 head back to
-    the input's resolution."""
+    the input's resolution.  norm = "group": GroupNormalization (opset 21, `groups` groups) + SiLU in place of every bare activation."""
+    if norm == "group":
+        return _unet_small_group(in_ch, out_ch, size, base, seed, groups)
+    if norm is not None:
+        raise ValueError(norm)
     net = _DecoderNet(seed)
     e1 = net.act(net.conv("X", in_ch, base, 3, 2, 1), "Relu")             # size / 2
     e2 = net.act(net.conv(e1, base, 2 * base, 3, 2, 1), "Relu")           # size / 4
@@ -3064,3 +3140,86 @@ def upsample_decoder(latent: Sequence[int] = (8, 4, 4), out_ch: int = 3, seed: i
     cur = net.resize(cur, 4, scales=(2.0, 2.0))
     cur = net.conv(cur, c, out_ch, 3, 1, 1)
     return net.finish("upsample_decoder", value_info("X", ["N", c, h, w]), cur, ["N", out_ch, 4 * h, 4 * w], extra={"in_shape": (c, h, w)})
+
+
+# ------------------------------------------------------------------------------------------
+# InstanceNormalization / GroupNormalization
+# ------------------------------------------------------------------------------------------
+def spatialnorm_reference(x, groups: int, gamma, beta, eps: float) -> np.ndarray:
+    """x [N, C, ...] normalised over each of `groups` channel groups (and every spatial position), then gamma[c] * . + beta[c]: float64,
+    the biased variance, as InstanceNormalization (groups = C) and GroupNormalization define it."""
+    x = np.asarray(x, np.float64)
+    n, c = x.shape[:2]
+    g = x.reshape(n, groups, -1)
+    mean = g.mean(axis=2, keepdims=True)
+    d = g - mean
+    var = (d * d).mean(axis=2, keepdims=True)
+    y = (d / np.sqrt(var + float(eps))).reshape(x.shape)
+    sh = (1, c) + (1,) * (x.ndim - 2)
+    return y * np.asarray(gamma, np.float64).reshape(sh) + np.asarray(beta, np.float64).reshape(sh)
+
+
+def spatial_norm_model(c: int = 8, groups: int = 8, hw=(5, 7), op: str = "InstanceNormalization", form: str = "op21", act: str | None = None, pre: bool = False,
+                       post: bool = False, offset: float = 0.0, seed: int = 7, inner=None, back: str = "const", affine: str = "mul_add", eps: float = 1e-5,
+                       name: str = "norm") -> tuple[bytes, dict]:
+    """One normalisation layer `name` on [N, c, H, W] (hw = (L,): [N, c, L]).  op "InstanceNormalization" (groups is then c), or
+    "GroupNormalization" in `form` "op18" / "op21" / "exporter" (_DecoderNet.gnorm).  act: None, "Silu" (Sigmoid + Mul) or an activation
+    operator.  pre / post: the identity 1x1 Conv / ConvTranspose of conv_transpose_model around it, which put the layer on channel-quad
+    tensors.  offset: the common offset of the inputs spatial_norm_inputs draws.  Returns (model, spec) for decoder_reference."""
+    one_d = len(hw) == 1
+    net = _DecoderNet(seed)
+    cur = "X"
+    eye = np.eye(c, dtype=np.float32)[:, :, None, None]
+    if pre:
+        cur = net.conv(cur, c, c, 1, 1, 0, bias=False, w=eye, one_d=one_d)
+    if op == "InstanceNormalization":
+        cur, opset = net.inorm(cur, c, eps, name=name), 13
+    elif op == "GroupNormalization":
+        cur = net.gnorm(cur, c, groups, form, inner, eps, name=name, back=back, affine=affine, x_shape=(c,) + tuple(hw))
+        opset = {"op18": 18, "op21": 21, "exporter": 13}[form]
+    else:
+        raise ValueError(op)
+    if act == "Silu":
+        cur = net.silu(cur)
+    elif act:
+        cur = net.act(cur, act)
+    if post:
+        cur = net.convt(cur, c, c, 1, 1, 0, bias=False, w=eye, one_d=one_d)
+    shape = (c,) + tuple(hw)
+    return net.finish("spatial_norm", value_info("X", ["N"] + list(shape)), cur, ["N"] + list(shape), opset=opset,
+                      extra={"in_shape": shape, "out_shape": shape, "offset": float(offset)})
+
+
+def spatial_norm_inputs(spec: dict, rows: int, seed: int = 0) -> np.ndarray:
+    """x = offset + U(-1, 1), f32"""
+    rng = np.random.default_rng(seed)
+    return (spec.get("offset", 0.0) + rng.uniform(-1, 1, size=(rows,) + tuple(spec["in_shape"]))).astype(np.float32)
+
+
+def style_net_small(size: int = 16, base: int = 8, seed: int = 59) -> tuple[bytes, dict]:
+    """A fast-neural-style transformer in small: Conv 3x3 -> InstanceNormalization -> Relu, two residual blocks (Conv -> InstanceNorm -> Relu ->
+    Conv -> InstanceNorm, + the block's input), Upsample x2 + Conv 3x3 stride 2 -> InstanceNorm -> Relu, and a 3x3 stride-1 ConvTranspose (a
+    convolution that may store the served NCHW image itself) back to 3 x size x size."""
+    net = _DecoderNet(seed)
+    cur = net.act(net.inorm(net.conv("X", 3, base, 3, 1, 1), base), "Relu")
+    for _ in range(2):
+        h = net.act(net.inorm(net.conv(cur, base, base, 3, 1, 1), base), "Relu")
+        h = net.inorm(net.conv(h, base, base, 3, 1, 1), base)
+        cur = net.add(h, cur)
+    cur = net.resize(cur, 4, scales=(2.0, 2.0))
+    cur = net.act(net.inorm(net.conv(cur, base, base, 3, 2, 1), base), "Relu")
+    cur = net.convt(cur, base, 3, 3, 1, 1)
+    shape = (3, size, size)
+    return net.finish("style_net_small", value_info("X", ["N"] + list(shape)), cur, ["N"] + list(shape), extra={"in_shape": shape})
+
+
+def _unet_small_group(in_ch, out_ch, size, base, seed, groups) -> tuple[bytes, dict]:
+    net = _DecoderNet(seed)
+    gs = lambda x, c: net.silu(net.gnorm(x, c, groups, "op21"))
+    e1 = gs(net.conv("X", in_ch, base, 3, 2, 1), base)                    # size / 2
+    e2 = gs(net.conv(e1, base, 2 * base, 3, 2, 1), 2 * base)              # size / 4
+    bott = gs(net.conv(e2, 2 * base, 2 * base, 3, 1, 1), 2 * base)
+    up = gs(net.convt(bott, 2 * base, base, 2, 2), base)                  # size / 2
+    dec = gs(net.conv(net.concat([up, e1]), 2 * base, base, 3, 1, 1), base)
+    head = net.convt(dec, base, out_ch, 2, 2)                             # size
+    return net.finish("unet_small_group", value_info("X", ["N", in_ch, size, size]), head, ["N", out_ch, size, size], opset=21, extra={"in_shape": (in_ch, size, size)})
