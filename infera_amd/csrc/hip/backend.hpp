@@ -69,6 +69,7 @@ struct PrepTables { const uint32_t *desc = nullptr; const float *cst = nullptr, 
 struct ConvTKernelTables { const float *W = nullptr, *bias = nullptr; const int *tab = nullptr; };  // ConvTranspose2d (W: packed for the step's kernel; tab: the phase tap tables)
 struct ResizeTables { const int *row_idx = nullptr, *col_idx = nullptr; const float *row_wgt = nullptr, *col_wgt = nullptr; };  // Resize2d
 struct SpatialNormTables { const float *gamma = nullptr, *beta = nullptr; };  // SpatialNorm (per channel: the same in either layout)
+struct TokensTables { const float *prefix = nullptr, *pos = nullptr; };  // Tokens (row-major [P, E] and [T, E]: the window's own order)
 struct RnnTables { const float *wr = nullptr, *bias = nullptr, *bias2 = nullptr, *h0 = nullptr, *c0 = nullptr; };
 struct DeviceStep {  // (a step fills the one struct of its family)
   PlainTables plain;
@@ -84,6 +85,7 @@ struct DeviceStep {  // (a step fills the one struct of its family)
   ConvTKernelTables convt;
   ResizeTables resize;
   SpatialNormTables spatialnorm;
+  TokensTables tokens;
 };
 
 // How the executor runs a step.

@@ -353,4 +353,8 @@ bool spatialnorm_stats(hipStream_t s, const float *X, float *stats, int64_t rows
 bool spatialnorm_apply(hipStream_t s, const float *X, const float *stats, const float *gamma, const float *beta, float *Y, int64_t rows, int C, int S, int G,
                        bool cq, ActParam act);
 
+// ---- Tokens: [rows, C, S] of a convolutional step -> the window [rows, P + S, C] (tokens.hip; host/tokens.hpp) --------------
+// X: NCHW order or (cq) channel-quad planes; prefix [P, C] (P = 0: none), pos [P + S, C] or null: added in the store.  false: beyond the caps
+bool tokens(hipStream_t s, const float *X, const float *prefix, const float *pos, float *Y, int64_t rows, int C, int S, int P, bool cq);
+
 }  // namespace infera_hip::kern

@@ -201,6 +201,8 @@ void Scheduler::decide_layout(bool commit) {
   auto convolution = [](const Step &s) { return s.kind == StepKind::Conv2d || s.kind == StepKind::QConv2d; };
   // (a transposed convolution reads and writes either layout, deconv.hip)
   auto reads_nchw = [&](const Step &s) { return convolution(s) || s.kind == StepKind::ConvTranspose2d; };
+  // (so does the crossing to a window, tokens.hip; its flat result has no layout, and alone it does not make a plan convolutional)
+  auto reads_either = [&](const Step &s) { return reads_nchw(s) || s.kind == StepKind::Tokens; };
   // A served [C,H,W] result leaves in the caller's NCHW order.  When a transposed convolution -- the last layer of a decoder -- is its only
   // writer and nothing reads it, that layer stores NCHW itself and the plan before it stays in channel quads; anything else keeps the plan NCHW.
   bool out_by_convt = false;
@@ -236,7 +238,7 @@ void Scheduler::decide_layout(bool commit) {
     any_conv = any_conv || reads_nchw(s);
     // (CopyCols = channel concat: a contiguous per-row block in NCHW and in channel-quad planes alike)
     // (FakeQuant, RoundHalf: elementwise with no per-element constant, the same bits in either layout; QConv2d reads and writes either, qconv.hip)
-    const bool layout_free = reads_nchw(s) || s.kind == StepKind::Resize2d || s.kind == StepKind::FakeQuant || s.kind == StepKind::RoundHalf || s.kind == StepKind::Pool2d || s.kind == StepKind::GlobalAvgPool ||
+    const bool layout_free = reads_either(s) || s.kind == StepKind::Resize2d || s.kind == StepKind::FakeQuant || s.kind == StepKind::RoundHalf || s.kind == StepKind::Pool2d || s.kind == StepKind::GlobalAvgPool ||
                              s.kind == StepKind::BinaryAct || s.kind == StepKind::Unary || s.kind == StepKind::AffineChannel ||
                              s.kind == StepKind::CopyCols || s.kind == StepKind::SliceCols || s.kind == StepKind::LRN ||
                              s.kind == StepKind::ChannelShuffle ||
@@ -258,7 +260,7 @@ void Scheduler::decide_layout(bool commit) {
     for (int b : {s.in0, s.in1}) {
       if (b < 0) continue;
       if (m.nchw_buf[size_t(b)] && is4d(b) && spatial(b) > 1) {  // NCHW tensors are read by convolutions and by their own elementwise chain only
-        if (!(reads_nchw(s) || flat_pair(s, b) || (elementwise(s) && b == s.in0 && m.nchw_buf[size_t(s.out)])))
+        if (!(reads_either(s) || flat_pair(s, b) || (elementwise(s) && b == s.in0 && m.nchw_buf[size_t(s.out)])))
           refuse("'" + s.origin + "' reads the NCHW input tensor and is neither a convolution nor elementwise preprocessing");
         continue;
       }
@@ -723,6 +725,17 @@ std::string LoadedModel::describe_json() const {
            ",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\",\"act\":\"" + acts[int(x.act)] + "\"}";
     }
     if (!c.empty()) o << ",\"spatialnorm\":[" << c << "]";
+  }
+  {  // per Tokens step: the kernel that runs it and the layout it reads (its result is a flat window)
+    std::string c;
+    for (size_t i = 0; i < exec.size(); i++) {
+      const Step &x = plan.steps[i];
+      if (x.kind != StepKind::Tokens) continue;
+      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)] && x.S > 1;
+      c += std::string(c.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"kernel\":\"" + (in_cq ? "tokens_cq" : "tokens_nchw") + "\",\"in_layout\":\"" +
+           (in_cq ? "NC/4HW4" : "NCHW") + "\"}";
+    }
+    if (!c.empty()) o << ",\"tokens\":[" << c << "]";
   }
   if (!chains.empty()) {
     o << ",\"chain_kernels\":[";

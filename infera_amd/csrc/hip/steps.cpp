@@ -10,6 +10,7 @@
 #include "../host/recurrent.hpp"
 #include "../host/spatialnorm.hpp"
 #include "../host/svm.hpp"
+#include "../host/tokens.hpp"
 #include "../host/trees.hpp"
 #include "runtime.hpp"
 
@@ -398,6 +399,17 @@ void launch_spatialstats(const PassRunner &r, const Step &x) {
     throw InferaError::onnx("SpatialStats kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
 }
 
+// ---- Tokens (host/tokens.hpp, tokens.hip): the constant rows and the position table, either may be absent ----
+void upload_tokens(const Step &s, TokensTables &t, const Upload &up) {
+  t.prefix = s.prefix.empty() ? nullptr : up(s.prefix);
+  t.pos = s.cst.empty() ? nullptr : up(s.cst);
+}
+void launch_tokens(const PassRunner &r, const Step &x, const TokensTables &t) {
+  const bool cq = r.cq(x.in0) && x.S > 1;  // (an [N,C,1,1] tensor is the same floats in either layout)
+  if (!kern::tokens(r.stream, r.buf(x.in0), t.prefix, t.pos, r.buf(x.out), r.nr, int(x.C), int(x.S), int(x.rep - x.S), cq))
+    throw InferaError::onnx("Tokens kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+
 // ---- the plain family: the step's constants as the lowering left them (Conv2d: packed for the generic kernel); its launches are the head
 // of PassRunner::launch_plain, right below ----
 void upload_plain(const Step &s, PlainTables &t, const Upload &up) {
@@ -453,6 +465,7 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::Resize2d: launch_resize(*this, x, d.resize); break;
     case StepKind::SpatialNorm: launch_spatialnorm(*this, x, d.spatialnorm); break;
     case StepKind::SpatialStats: launch_spatialstats(*this, x); break;
+    case StepKind::Tokens: launch_tokens(*this, x, d.tokens); break;
     // the steps without tables
     case StepKind::Unary: kern::unary(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], act_of(x)); break;
     case StepKind::BinaryAct:
@@ -517,6 +530,7 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::ConvTranspose2d: return upload_convt(up, i, d.convt);
     case StepKind::Resize2d: return upload_resize(s, d.resize, up);
     case StepKind::SpatialNorm: return upload_spatialnorm(s, d.spatialnorm, up);
+    case StepKind::Tokens: return upload_tokens(s, d.tokens, up);
     default: return;  // (no tables)
   }
 }

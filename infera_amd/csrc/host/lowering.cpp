@@ -24,6 +24,7 @@
 #include "common.hpp"
 #include "deconv.hpp"
 #include "spatialnorm.hpp"
+#include "tokens.hpp"
 #include "nearest.hpp"
 #include "plan.hpp"
 #include "prep.hpp"
@@ -554,6 +555,16 @@ struct Lowerer {
     if (op == '+') {
       Step *p = fusable_producer(n, const_left ? 1 : 0);
       const auto &cv = cf32(n, cst);
+      // the position table [1, T, E] / [T, E] behind a Tokens step that nothing else reads: added in its store (one rounded addition, the
+      // bits of the BinaryConst this would be).  Not in a float16 graph, where the sum is rounded to half by its own step
+      if (p && p->kind == StepKind::Tokens && p->cst.empty() && !cur_half && tokens_producer(act) == p && cst.c->elem != onnx::kFloat16 &&
+          ((cst.shape.size() == 3 && cst.shape[0] == 1) || cst.shape.size() == 2) && cst.shape[cst.shape.size() - 2] == p->rep && cst.shape.back() == p->K &&
+          int64_t(cv.size()) == p->rep * p->K) {
+        p->cst = cv;
+        p->origin += "+" + node_label(n);
+        set_act(n, act.buf, act_shape, true);
+        return;
+      }
       bool over_m = p && p->kind == StepKind::Dense && p->bias.empty() && p->act == Act::None && int64_t(cv.size()) == p->M &&
                     (cst.shape.size() == 1 || (cst.shape.size() == 2 && cst.shape[0] == 1));
       if (p && p->kind == StepKind::QDense && !p->qy.on && p->act == Act::None && p->bias.empty() && p->q_bias.empty() && int64_t(cv.size()) == p->M &&
@@ -947,6 +958,7 @@ struct Lowerer {
       set_const_i64(n, std::move(o), {cnt});
       return;
     }
+    if (tokens_concat(n)) return;
     const Val &first = get(n, 0);
     if (first.is_const) unsupported(n, "mixing constants and activations");
     const int64_t rank = int64_t(first.shape.size());
@@ -1227,8 +1239,9 @@ struct Lowerer {
     } else if (n.op == "Flatten") {
       int64_t axis = n.attr_i("axis", 1);
       if (axis < 0) axis += rank;
-      if (axis != 1) unsupported(n, "only axis=1 keeps the row axis");
-      out = {a.shape[0], prod(a.shape, 1)};
+      if (axis == 2 && rank == 4 && token_view_of_flatten(n, a)) out = {a.shape[0], a.shape[1], prod(a.shape, 2)};
+      else if (axis != 1) unsupported(n, "only axis=1 keeps the row axis");
+      else out = {a.shape[0], prod(a.shape, 1)};
     } else if (n.op == "Reshape") {
       std::vector<int64_t> tgt;
       if (has_input(n, 1)) {
@@ -1942,6 +1955,8 @@ struct Lowerer {
         if (perm[size_t(i)] != i) return false;
       return true;
     }();
+    // (with C = 1 or S = 1 the crossing moves nothing: it stays the alias below, and only a class-token Concat makes it a step: tokens_concat)
+    if (rank == 3 && perm[0] == 0 && perm[1] == 2 && perm[2] == 1 && conv_tensor_view(a) && a.shape[1] != 1 && a.shape[2] != 1) return tokens_step(n, a);
     if (!shuffle && (a.ra != 0 || rank == 3)) {
       // (time-major values, and the rank-3 rows-first values a Transpose(1,0,2) makes time-major; other tensors are not touched) a permutation that only moves (or keeps) the row axis and leaves the other axes in the order they lie in memory: an alias with a
       // new row-axis tag (the Transposes exporters put around time-major recurrent layers)
@@ -1980,6 +1995,113 @@ struct Lowerer {
     s.origin = node_label(n);
     set_act(n, push_step(std::move(s), bshape), vshape);
   }
+
+  // ---- the crossing from the image path to the table path (host/tokens.hpp): Conv -> Flatten(2) / Reshape [N,E,S] ->
+  // Transpose(0,2,1) [-> Concat(class tokens, .)] [-> Add(position table)] is ONE Tokens step.  The Transpose emits it; a Concat and an
+  // Add behind it move their constants into its tables (tokens_concat, binary) ----
+  // Is the rank-3 rows-first value `a` the [N, C, S] tensor a step wrote -- itself ([N,C,L], held as [N,C,1,L]) or a view of [N,C,H,W]?
+  // (The model input and its views are not: buffer 0 has no producer.)
+  bool conv_tensor_view(const Val &a) const {
+    if (a.is_const || a.pv || a.nn || a.ra != 0 || a.buf <= 0 || a.shape.size() != 3 || !producer.count(a.buf)) return false;
+    const auto &bs = plan.buf_shape[size_t(a.buf)];
+    return bs.size() == 4 && bs[1] == a.shape[1] && bs[2] > 0 && bs[3] > 0 && bs[2] * bs[3] == a.shape[2];
+  }
+  // Flatten(axis = 2) of an [N,C,H,W] tensor a step wrote, read by Transpose(0,2,1) nodes only: the [N, C, H*W] view torch's flatten(2)
+  // stands for (the [N*C, H*W] matrix the operator specification gives has the same elements in the same order)
+  bool token_view_of_flatten(const NodeDef &n, const Val &a) const {
+    if (a.is_const || a.pv || a.ra != 0 || a.buf <= 0 || !producer.count(a.buf) || plan.buf_shape[size_t(a.buf)].size() != 4) return false;
+    auto it = consumers_of.find(n.outputs[0]);
+    if (it == consumers_of.end() || it->second.empty()) return false;
+    for (const auto &o : m.outputs)
+      if (o.name == n.outputs[0]) return false;
+    for (size_t c : it->second) {
+      const NodeDef &r = m.nodes[c];
+      const auto *perm = r.attr_ints("perm");
+      if (r.op != "Transpose" || !perm || *perm != std::vector<int64_t>{0, 2, 1}) return false;
+    }
+    return true;
+  }
+  void tokens_step(const NodeDef &n, const Val &a) {
+    const auto &bs = plan.buf_shape[size_t(a.buf)];
+    if (const std::string why = tokens_refusal(bs); !why.empty()) bad_form(n, why);
+    Step s;
+    s.kind = StepKind::Tokens;
+    s.in0 = a.buf;
+    s.C = s.K = a.shape[1];
+    s.S = s.rep = a.shape[2];
+    emit_window(std::move(s), n, {a.shape[0], a.shape[2], a.shape[1]});
+  }
+  // the Tokens step whose result `v` is, as that step left it
+  Step *tokens_producer(const Val &v) {
+    if (v.is_const || v.buf <= 0 || v.ra != 0 || v.shape.size() != 3) return nullptr;
+    auto it = producer.find(v.buf);
+    if (it == producer.end()) return nullptr;
+    Step &p = plan.steps[size_t(it->second)];
+    return p.kind == StepKind::Tokens && p.out == v.buf && v.shape[1] == p.rep && v.shape[2] == p.K ? &p : nullptr;
+  }
+  // Concat with a token value among its operands: constants per row in front of it become the step's prefix rows.  false: no operand is one
+  bool tokens_concat(const NodeDef &n) {
+    size_t at = SIZE_MAX;
+    for (size_t i = 0; i < n.inputs.size(); i++)
+      if (const Val *v = find_value(n.inputs[i]); v && tokens_producer(*v)) at = i;
+    // a crossing that moved nothing (C = 1 or S = 1) was left an alias of the convolutional tensor; constants joined to it make it a step
+    // here, written as this node's result (without a constant among the operands the Concat lowers as it always did)
+    bool promoted = false;
+    if (at == SIZE_MAX) {
+      bool any_const = false;
+      Val view;
+      for (size_t i = 0; i < n.inputs.size(); i++) {
+        const Val *v = find_value(n.inputs[i]);
+        if (!v) continue;
+        any_const = any_const || v->is_const;
+        if (v->is_const || v->shape.size() != 3 || (v->shape[1] != 1 && v->shape[2] != 1)) continue;
+        Val u = *v;
+        std::swap(u.shape[1], u.shape[2]);
+        if (conv_tensor_view(u)) { at = i; view = u; }
+      }
+      if (at == SIZE_MAX || !any_const) return false;
+      tokens_step(n, view);
+      promoted = true;
+    }
+    const Val tok = promoted ? *find_value(n.outputs[0]) : get(n, at);
+    Step *p = tokens_producer(tok);
+    int64_t axis = n.attr_i("axis", 1);
+    if (axis < 0) axis += 3;
+    if (axis != 1) bad_form(n, "axis = " + std::to_string(n.attr_i("axis", 1)) + ": constant rows join a token window [N, T, E] along the token axis (1) only");
+    if (at + 1 != n.inputs.size()) bad_form(n, "operand " + std::to_string(at + 1) + " stands behind the tokens; only class tokens in front of them are folded");
+    const int64_t N = tok.shape[0], E = p->K;
+    std::vector<float> rows = p->prefix;
+    for (size_t i = 0; i < at; i++) {
+      const Val &c = get(n, i);
+      if (!c.is_const) bad_form(n, "operand " + std::to_string(i) + " in front of the tokens is not a constant; only constant class tokens are folded");
+      if (c.c->dtype != onnx::kFloat) bad_form(n, "operand " + std::to_string(i) + " is not an f32 constant");
+      auto ex = expanded_lead.find(n.inputs[i]);
+      if (ex != expanded_lead.end()) {  // an Expand to [batch, p, E]: the batch entry is the folded row count (0) or the fixed batch
+        if (!(ex->second == 0 ? N < 0 : ex->second == N))
+          bad_form(n, "operand " + std::to_string(i) + " was expanded to " + std::to_string(ex->second) + " rows, the tokens have " + (N < 0 ? std::string("a symbolic row count") : std::to_string(N)));
+      } else if (!(N == 1 && c.shape.size() == 3 && c.shape[0] == 1)) {
+        bad_form(n, "operand " + std::to_string(i) + " " + shape_str(c.shape) + " is a constant that was not expanded over the rows (Expand); as it stands it joins a batch of 1 only");
+      }
+      int64_t np = 0, width = 0;
+      std::vector<float> r;
+      if (!tokens_prefix_rows(c.shape, c.c->f32, &np, &width, &r)) bad_form(n, "operand " + std::to_string(i) + " " + shape_str(c.shape) + " is not [1, p, E] / [p, E] constant rows, the same for every image");
+      if (const std::string why = tokens_prefix_refusal(int64_t(rows.size()) / E, np, width, E); !why.empty()) bad_form(n, why);
+      rows.insert(rows.end(), r.begin(), r.end());
+    }
+    if (!p->cst.empty()) bad_form(n, "the position table is already added to the tokens");
+    if (!promoted && live_uses(tok.buf) != 1) bad_form(n, "the tokens '" + n.inputs[at] + "' have a second reader");
+    const int64_t T = int64_t(rows.size()) / E + p->S;
+    if (prod({T, E}) > kMaxPerRow) throw InferaError::onnx("activation of " + std::to_string(T * E) + " elements per row is too large");
+    p->prefix = std::move(rows);
+    p->rep = T;
+    if (!promoted) p->origin += "+" + node_label(n);
+    plan.buf_per_row[size_t(tok.buf)] = T * E;
+    plan.buf_shape[size_t(tok.buf)] = {N, T * E};
+    if (promoted) vals[n.outputs[0]].shape = {N, T, E};  // (tokens_step registered the result under this node's name already)
+    else set_act(n, tok.buf, {N, T, E}, true);
+    return true;
+  }
+  std::map<std::string, int64_t> expanded_lead;  // results of Expand over constants -> the leading entry of the target shape as the graph had it
 
   // ---- the decomposed LayerNorm older exporters write, on [rows, E] (where nothing else serves it):
   //   ReduceMean(-1) -> Sub -> Pow(2) | Mul(d, d) -> ReduceMean(-1) -> Add(eps) -> Sqrt -> Div [-> Mul(gamma)] [-> Add(beta)]
@@ -3014,6 +3136,7 @@ struct Lowerer {
       case StepKind::ArgMin:
       case StepKind::TopK:
       case StepKind::NearestReduce: return true;
+      case StepKind::Tokens: return s.cst.empty();  // (movement alone; a half graph's position Add is never folded)
       case StepKind::RowReduce: return s.out_mode == kReduceMax || s.out_mode == kReduceMin;
       case StepKind::Pool2d:
       case StepKind::GlobalAvgPool: return s.is_max && s.act == Act::None;
@@ -3203,6 +3326,7 @@ struct Lowerer {
   void constant_fill(const NodeDef &n) {
     const bool expand = n.op == "Expand";
     std::vector<int64_t> dims = const_ints(n, expand ? 1 : 0, "shape");
+    const int64_t lead = dims.size() == 3 ? dims[0] : -1;  // (a [batch, p, E] target: tokens_concat)
     for (auto &d : dims) {
       if (d == 0) d = 1;
       if (d < 0) unsupported(n, "negative extent");
@@ -3238,6 +3362,7 @@ struct Lowerer {
       }
       o[size_t(flat)] = src[size_t(idx)];
     }
+    if (expand && dims.size() == 3 && lead >= 0) expanded_lead[n.outputs[0]] = lead;
     vals[n.outputs[0]] = const_f32(std::move(o), dims);
   }
   // LSTM / GRU / RNN: one Recurrent step per output that is read.  X is [T, rows, F] (layout 0: time-major, row-axis tag 1) or
@@ -4392,7 +4517,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -4487,6 +4612,17 @@ std::string Plan::describe_json() const {
         return json_int_array(b);
       };
       o << ",\"scale_bits\":" << bits(s.scale) << ",\"shift_bits\":" << bits(s.shift);
+    }
+    if (s.kind == StepKind::Tokens) {  // the tables as one hash over their f32 bit patterns: equal spellings give equal plans
+      uint64_t h = 1469598103934665603ull;
+      for (const auto *v : {&s.prefix, &s.cst})
+        for (float f : *v) {
+          uint32_t b;
+          std::memcpy(&b, &f, sizeof b);
+          h = (h ^ b) * 1099511628211ull;
+        }
+      o << ",\"C\":" << s.C << ",\"S\":" << s.S << ",\"prefix\":" << s.rep - s.S << ",\"pos\":" << (s.cst.empty() ? "false" : "true") << ",\"T\":" << s.rep << ",\"E\":" << s.K
+        << ",\"tables_hash\":" << (h >> 11);
     }
     if (s.kind == StepKind::QConv2d)
       o << ",\"C\":" << s.C << ",\"k\":[" << s.kh << "," << s.kw << "],\"strides\":[" << s.sh << "," << s.sw << "],\"pads\":[" << s.pt << "," << s.pl << "," << s.pb << "," << s.pr

@@ -72,6 +72,7 @@ enum class StepKind : int {
   ConvTranspose2d = 34,  // transposed convolution by stride phases (the Conv2d geometry fields: C, H, Wd = the input, Mo, OH, OW = the output; W = the ONNX weights [C, M/g, kh, kw]; DeconvPack: the phase tap lists; deconv.hip)
   SpatialNorm = 36,   // InstanceNormalization / GroupNormalization over the (C / groups) * S elements of each of `groups` channel groups of in0 [rows, C, S]: y = act((x - mean) / sqrt(var + ln_eps) * scale[c] + shift[c]); in1 = -1: the fused kernel, else in1 = a SpatialStats result (host/spatialnorm.hpp, spatialnorm.hip)
   SpatialStats = 37,  // out [rows, groups, 3] = (mean, resid, 1 / sqrt(var + ln_eps)) of each group of in0: the first half of the general SpatialNorm plan (the scheduler inserts it, schedule.cpp)
+  Tokens = 38,        // out [rows, rep = P + S, K = C] = the window of in0 [rows, C, S] (NCHW or channel quads): out[r, P + s, c] = in0[r, c, s] (+ cst[P + s, c]); rows p < P = prefix[p, c] (+ cst[p, c]) (host/tokens.hpp, tokens.hip)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
@@ -126,6 +127,7 @@ struct Step {
   char bop = '+';
   bool const_left = false;
   std::vector<float> cst;  // per_row elements
+  std::vector<float> prefix;  // Tokens: the P constant rows in front of the S positions, [P, C] (cst: the position table [P + S, C] or empty)
   // CopyCols: destination column offset (elements inside a row), length = in0's per_row.  SliceCols: SOURCE offset, length K
   int64_t col_off = 0;
   // Softmax

@@ -1187,15 +1187,16 @@ def layernorm_nodes(nodes: list, inits: list, x: str, g, b, out: str, name: str,
 
 def transformer_from_spec(spec: dict, flat: bool = True, qkv: str = "separate", scale: str = "scores_div", k_transpose: str = "direct",
                           mask_rank: int = 2, shape: str = "const", gelu: str = "op", heads: Sequence[str] = ("mean",), keepdims: int = 0,
-                          opset: int = 20, layernorm: str = "op", pos_rank: int = 3) -> bytes:
+                          opset: int = 20, layernorm: str = "op", pos_rank: int = 3, front: tuple | None = None) -> bytes:
     """The ONNX model of a transformer_spec() / from_torch_encoder() dict, input X [N, T, F] (flat: [N, T*F] -> Reshape).
     qkv: "separate" (three MatMul + Add), "packed_split" / "packed_slice" (one [E, 3E] projection, then Split / three Slices on the last axis);
     scale, k_transpose, shape: see attention_nodes; a causal spec adds the [T, T] mask (mask_rank 4: [1, 1, T, T]); gelu: "op" (opset 20) or
     "decomposed" (Div(sqrt 2) -> Erf -> Add(1) -> Mul(x) -> Mul(0.5)).  heads: the graph outputs, any of "mean" (mean over time -> Linear,
     output "pooled"), "first" / "last" (that step -> Linear), "seq" (the full sequence [N, T, E] -> per-step Linear); without a head matrix
-    in the spec the encoder output itself is served.  layernorm: see layernorm_nodes ("op" is the default); pos_rank: the positional constant as [1, T, E] or [T, E]."""
+    in the spec the encoder output itself is served.  layernorm: see layernorm_nodes ("op" is the default); pos_rank: the positional constant as [1, T, E] or [T, E].
+    front: (nodes, initializers, name of the [N, T, E] value they compute, graph inputs) -- the encoder then starts from that value (vit_from_spec)."""
     T, F, E, h, ff = spec["T"], spec["F"], spec["E"], spec["h"], spec["ff"]
-    nodes, inits = [], []
+    nodes, inits = (list(front[0]), list(front[1])) if front else ([], [])
     i64 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.int64)))  # noqa: E731
     f32 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.float32)))  # noqa: E731
 
@@ -1209,8 +1210,8 @@ def transformer_from_spec(spec: dict, flat: bool = True, qkv: str = "separate", 
     def layer_norm(x, g, b, out, name):
         return layernorm_nodes(nodes, inits, x, g, b, out, name, spec["eps"], layernorm)
 
-    x = "X"
-    if flat:
+    x = front[2] if front else "X"
+    if flat and not front:
         i64("flat_shape", [-1, T, F])
         nodes.append(node("Reshape", [x, "flat_shape"], ["X3"]))
         x = "X3"
@@ -1278,7 +1279,7 @@ def transformer_from_spec(spec: dict, flat: bool = True, qkv: str = "separate", 
             nodes.append(node("Identity", [v], [name]))
         outs.append(value_info(name, dims))
     in_dims = ["N", T * F] if flat else ["N", T, F]
-    return model("transformer", nodes, inits, [value_info("X", in_dims)], outs, opset=opset)
+    return model("transformer", nodes, inits, list(front[3]) if front else [value_info("X", in_dims)], outs, opset=opset)
 
 
 # ------------------------------------------------------------------------------------------
@@ -3223,3 +3224,182 @@ def _unet_small_group(in_ch, out_ch, size, base, seed, groups) -> tuple[bytes, d
     dec = gs(net.conv(net.concat([up, e1]), 2 * base, base, 3, 1, 1), base)
     head = net.convt(dec, base, out_ch, 2, 2)                             # size
     return net.finish("unet_small_group", value_info("X", ["N", in_ch, size, size]), head, ["N", out_ch, size, size], opset=21, extra={"in_shape": (in_ch, size, size)})
+
+
+# ------------------------------------------------------------------------------------------
+# Vision Transformers: the crossing from an [N, C, H, W] tensor to a token window [N, T, E] (Tokens step) and the models around it
+# ------------------------------------------------------------------------------------------
+
+def token_nodes(nodes: list, inits: list, src: str, c: int, hw, prefix=None, pos=None, view: str = "flatten", expand: str = "subgraph",
+                batch: int | str = "N", batch_from: str = "X", p: str = "tok_", pos_rank: int = 3, prefix_behind: bool = False,
+                second_reader: bool = False) -> str:
+    """Appends the Hugging Face spelling of the crossing behind the [N, c, *hw] value `src` and returns the name of the [N, P + S, c] result:
+    the view -- "flatten" (Flatten(axis = 2), torch's flatten(2) kept as one node), "reshape" (Reshape to the constant [0, c, S]) or
+    "shape_subgraph" (Reshape to Shape(src)[0:2] ++ [-1], what the exporter writes for flatten(2)) --, Transpose(0, 2, 1), then per array of
+    `prefix` (each [p, c]: class / distillation tokens) an Expand -- expand = "subgraph" (target Shape(batch_from) -> Gather(0) -> Unsqueeze
+    -> Concat with [p, c]), "literal" (a constant target, with a fixed `batch`) or "none" (the [1, p, c] constant itself) -- joined in front
+    by one Concat(axis = 1), then Add(pos [1, P + S, c], or [P + S, c] with pos_rank = 2).  prefix_behind: the constants behind the tokens.
+    second_reader: the result is Max(tokens + pos, tokens), so that the position Add is not the only reader of the tokens."""
+    i64 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.int64)))  # noqa: E731
+    f32 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.float32)))  # noqa: E731
+    S = int(np.prod(hw))
+    if view == "flatten":
+        nodes.append(node("Flatten", [src], [p + "view"], [attr_i("axis", 2)], name=p + "flatten"))
+    elif view == "reshape":
+        i64(p + "view_shape", [0, c, S])
+        nodes.append(node("Reshape", [src, p + "view_shape"], [p + "view"], name=p + "reshape"))
+    elif view == "shape_subgraph":
+        i64(p + "b0", [0]); i64(p + "b2", [2]); i64(p + "m1", [-1])  # noqa: E702
+        nodes += [node("Shape", [src], [p + "src_shape"]), node("Slice", [p + "src_shape", p + "b0", p + "b2", p + "b0"], [p + "nc"]),
+                  node("Concat", [p + "nc", p + "m1"], [p + "view_shape"], [attr_i("axis", 0)]),
+                  node("Reshape", [src, p + "view_shape"], [p + "view"], name=p + "reshape")]
+    elif view != "none":
+        raise ValueError(view)
+    cur = p + "seq"
+    nodes.append(node("Transpose", [src if view == "none" else p + "view"], [cur], [attr_ints("perm", [0, 2, 1])], name=p + "transpose"))
+    parts = []
+    for j, rows in enumerate(prefix or ()):
+        rows = np.asarray(rows, dtype=np.float32).reshape(1, -1, np.asarray(rows).shape[-1])
+        f32(f"{p}cls{j}", rows)
+        if expand == "none":
+            parts.append(f"{p}cls{j}")
+            continue
+        if expand == "subgraph":
+            if j == 0:
+                i64(p + "i0", 0); i64(p + "ax0", [0])  # noqa: E702
+                nodes += [node("Shape", [batch_from], [p + "in_shape"]), node("Gather", [p + "in_shape", p + "i0"], [p + "n"], [attr_i("axis", 0)]),
+                          node("Unsqueeze", [p + "n", p + "ax0"], [p + "n1"])]
+            i64(f"{p}pe{j}", list(rows.shape[1:]))
+            nodes.append(node("Concat", [p + "n1", f"{p}pe{j}"], [f"{p}target{j}"], [attr_i("axis", 0)]))
+        elif expand == "literal":
+            i64(f"{p}target{j}", [int(batch), rows.shape[1], rows.shape[2]])
+        else:
+            raise ValueError(expand)
+        nodes.append(node("Expand", [f"{p}cls{j}", f"{p}target{j}"], [f"{p}cls{j}_n"], name=f"{p}expand{j}"))
+        parts.append(f"{p}cls{j}_n")
+    if parts:
+        nodes.append(node("Concat", [cur] + parts if prefix_behind else parts + [cur], [p + "cat"], [attr_i("axis", 1)], name=p + "concat"))
+        cur = p + "cat"
+    if pos is not None:
+        pos = np.asarray(pos, dtype=np.float32)
+        f32(p + "pos", pos.reshape((1,) + pos.shape[-2:]) if pos_rank == 3 else pos.reshape(pos.shape[-2:]))
+        nodes.append(node("Add", [cur, p + "pos"], [p + "emb"], name=p + "pos_add"))
+        if second_reader:
+            nodes.append(node("Max", [p + "emb", cur], [p + "both"], name=p + "second_reader"))
+        cur = p + "both" if second_reader else p + "emb"
+    return cur
+
+
+def tokens_model(c: int = 8, hw=(4, 4), prefix: int = 0, pos: bool = False, front: str = "relu", view: str = "flatten", expand: str = "subgraph",
+                 batch: int | str = "N", seed: int = 5, **kw) -> tuple[bytes, dict]:
+    """The Tokens step alone: X [N, c, *hw] -> front -> view -> Transpose(0, 2, 1) [-> Concat(`prefix` expanded constant rows, .)] [-> Add(pos)],
+    output [N, prefix + S, c].  front "relu": Relu(X), exact, read in NCHW order; "neg": Neg(X), likewise, and a NaN stays a NaN; "conv": a 1x1 Conv whose weight is twice the identity
+    (exact products; the scheduler keeps its result in channel quads when c % 4 == 0).  hw = (L,): the [N, c, L] form.  The constants are
+    small integers over 4, so prefix + pos is exact in any order but still exercises the addition.  Returns (model, {"prefix", "pos"})."""
+    rng = np.random.default_rng(seed)
+    hw = tuple(hw)
+    S = int(np.prod(hw))
+    nodes, inits = [], []
+    if front == "relu":
+        nodes.append(node("Relu", ["X"], ["front"], name="front_relu"))
+    elif front == "neg":
+        nodes.append(node("Neg", ["X"], ["front"], name="front_neg"))
+    elif front == "conv":
+        w = 2.0 * np.eye(c, dtype=np.float32).reshape((c, c) + (1,) * len(hw))
+        inits.append(tensor("front_w", w))
+        nodes.append(node("Conv", ["X", "front_w"], ["front"], [attr_ints("kernel_shape", [1] * len(hw))], name="front_conv"))
+    else:
+        raise ValueError(front)
+    cls = (rng.integers(-64, 64, (prefix, c)) / 4.0).astype(np.float32) if prefix else None
+    table = (rng.integers(-64, 64, (prefix + S, c)) / 4.0).astype(np.float32) if pos else None
+    out = token_nodes(nodes, inits, "front", c, hw, [cls[j:j + 1] for j in range(prefix)] if prefix else None, table, view=view, expand=expand, batch=batch, **kw)
+    blob = model("tokens", nodes, inits, [value_info("X", [batch, c] + list(hw))], [value_info(out, [batch, prefix + S, c])], opset=13)
+    return blob, {"c": c, "hw": hw, "prefix": cls, "pos": table, "front": front, "second_reader": bool(kw.get("second_reader"))}
+
+
+def tokens_reference(spec: dict, x) -> np.ndarray:
+    """What tokens_model computes, in float32 numpy: exact movement and one IEEE addition per element."""
+    x = np.asarray(x, dtype=np.float32)
+    n, c = x.shape[:2]
+    f = np.maximum(x, 0) if spec["front"] == "relu" else -x if spec["front"] == "neg" else np.float32(2.0) * x
+    tok = f.reshape(n, c, -1).transpose(0, 2, 1)
+    if spec["prefix"] is not None:
+        tok = np.concatenate([np.broadcast_to(spec["prefix"][None], (n,) + spec["prefix"].shape), tok], axis=1)
+    if spec["pos"] is None:
+        return np.ascontiguousarray(tok)
+    emb = (tok + spec["pos"][None]).astype(np.float32)
+    return np.maximum(emb, tok) if spec.get("second_reader") else emb
+
+
+def vit_spec(img=(3, 16, 16), patch: int = 4, E: int = 32, h: int = 4, ff: int = 64, layers: int = 2, classes: int = 5, prefix: int = 1,
+             weight_scale: float = 1.0, seed: int = 33) -> dict:
+    """A seeded ViT / DeiT in the Hugging Face spelling: a patch x patch stride-patch Conv with bias img[0] -> E, `prefix` class /
+    distillation tokens, a position table [prefix + S, E], `layers` pre-norm encoder layers with Erf GELU (transformer_spec), the final
+    LayerNorm and a classifier on the first token."""
+    rng = np.random.default_rng(seed)
+    c, H, W = img
+    S = (H // patch) * (W // patch)
+    k = weight_scale / np.sqrt(c * patch * patch)
+    enc = transformer_spec(T=prefix + S, F=E, E=E, h=h, ff=ff, layers=layers, norm_first=True, act="Gelu", outputs=classes, weight_scale=weight_scale, seed=seed + 1)
+    enc.update(Win=None, bin=None, pos=None)
+    return {"img": tuple(img), "patch": patch, "E": E, "grid": (H // patch, W // patch), "enc": enc,
+            "patch_W": rng.uniform(-k, k, (E, c, patch, patch)).astype(np.float32), "patch_b": rng.uniform(-k, k, (E,)).astype(np.float32),
+            "cls": (0.5 * rng.standard_normal((prefix, E))).astype(np.float32), "pos": (0.5 * rng.standard_normal((prefix + S, E))).astype(np.float32)}
+
+
+def vit_from_spec(spec: dict, view: str = "flatten", expand: str = "subgraph", batch: int | str = "N", second_reader: bool = False,
+                  heads: Sequence[str] = ("first",), **kw) -> bytes:
+    """The ONNX model of a vit_spec() dict, input X [N, C, H, W]: Conv(patch, with bias) -> view -> Transpose -> Concat(expanded class tokens, .) ->
+    Add(position table) -> transformer_from_spec(spec["enc"], separate Q / K / V) -> the first token -> classifier (output "first").
+    view, expand, second_reader: token_nodes (second_reader changes what the model computes: for plan checks).  kw: transformer_from_spec (gelu = "decomposed", shape = "subgraph" ...)."""
+    c, H, W = spec["img"]
+    pt, E = spec["patch"], spec["E"]
+    nodes = [node("Conv", ["X", "patch_W", "patch_b"], ["patches"], [attr_ints("kernel_shape", [pt, pt]), attr_ints("strides", [pt, pt])], name="patch_embed")]
+    inits = [tensor("patch_W", spec["patch_W"]), tensor("patch_b", spec["patch_b"])]
+    P = spec["cls"].shape[0]
+    x = token_nodes(nodes, inits, "patches", E, spec["grid"], [spec["cls"][j:j + 1] for j in range(P)], spec["pos"], view=view, expand=expand, batch=batch,
+                    second_reader=second_reader)
+    return transformer_from_spec(spec["enc"], heads=heads, front=(nodes, inits, x, [value_info("X", [batch, c, H, W])]), **kw)
+
+
+def vit_reference(spec: dict, x, heads: Sequence[str] = ("first",)) -> dict:
+    """float64 numpy restatement of vit_from_spec(spec): x [N, C, H, W] -> {output name: array}."""
+    pt = spec["patch"]
+    x = np.asarray(x, dtype=np.float64).reshape((-1,) + tuple(spec["img"]))
+    f = _conv_taps(x, np.asarray(spec["patch_W"], np.float64), (pt, pt), (0, 0, 0, 0), (1, 1), 1, 0.0) + np.asarray(spec["patch_b"], np.float64).reshape(1, -1, 1, 1)
+    n, E = f.shape[:2]
+    tok = f.reshape(n, E, -1).transpose(0, 2, 1)
+    tok = np.concatenate([np.broadcast_to(np.asarray(spec["cls"], np.float64)[None], (n,) + spec["cls"].shape), tok], axis=1) + np.asarray(spec["pos"], np.float64)[None]
+    return transformer_reference(spec["enc"], tok, heads)
+
+
+def cnn_stem_encoder_spec(img=(3, 12, 12), base: int = 8, E: int = 16, h: int = 2, ff: int = 32, classes: int = 4, weight_scale: float = 1.0, seed: int = 61) -> dict:
+    """A CNN stem in front of an encoder: Conv 3x3 stride 2 (img[0] -> base) -> Relu -> Conv 3x3 stride 2 (base -> E) -> tokens (no class
+    token) -> position table -> one post-norm encoder layer (Relu) -> mean over time -> classifier."""
+    rng = np.random.default_rng(seed)
+    c, H, W = img
+    g = ((H + 1) // 2 + 1) // 2, ((W + 1) // 2 + 1) // 2
+    S = g[0] * g[1]
+    enc = transformer_spec(T=S, F=E, E=E, h=h, ff=ff, layers=1, norm_first=False, act="Relu", outputs=classes, weight_scale=weight_scale, seed=seed + 1)
+    enc.update(Win=None, bin=None, pos=None)
+    u = lambda shape, fan: rng.uniform(-weight_scale / np.sqrt(fan), weight_scale / np.sqrt(fan), shape).astype(np.float32)  # noqa: E731
+    return {"img": tuple(img), "grid": g, "E": E, "enc": enc, "W1": u((base, c, 3, 3), 9 * c), "b1": u((base,), 9 * c), "W2": u((E, base, 3, 3), 9 * base),
+            "b2": u((E,), 9 * base), "pos": (0.5 * rng.standard_normal((S, E))).astype(np.float32)}
+
+
+def cnn_stem_encoder_from_spec(spec: dict, view: str = "reshape", **kw) -> bytes:
+    c, H, W = spec["img"]
+    conv = lambda x, w, b, out, name: node("Conv", [x, w, b], [out], [attr_ints("kernel_shape", [3, 3]), attr_ints("strides", [2, 2]), attr_ints("pads", [1, 1, 1, 1])], name=name)  # noqa: E731
+    nodes = [conv("X", "W1", "b1", "c1", "stem1"), node("Relu", ["c1"], ["r1"], name="stem_relu"), conv("r1", "W2", "b2", "c2", "stem2")]
+    inits = [tensor(k, spec[k]) for k in ("W1", "b1", "W2", "b2")]
+    x = token_nodes(nodes, inits, "c2", spec["E"], spec["grid"], None, spec["pos"], view=view)
+    return transformer_from_spec(spec["enc"], heads=("mean",), front=(nodes, inits, x, [value_info("X", ["N", c, H, W])]), **kw)
+
+
+def cnn_stem_encoder_reference(spec: dict, x) -> dict:
+    f64 = lambda a: np.asarray(a, dtype=np.float64)  # noqa: E731
+    x = f64(x).reshape((-1,) + tuple(spec["img"]))
+    conv = lambda a, w, b: _conv_taps(a, f64(w), (2, 2), (1, 1, 1, 1), (1, 1), 1, 0.0) + f64(b).reshape(1, -1, 1, 1)  # noqa: E731
+    f = conv(np.maximum(conv(x, spec["W1"], spec["b1"]), 0.0), spec["W2"], spec["b2"])
+    n, E = f.shape[:2]
+    return transformer_reference(spec["enc"], f.reshape(n, E, -1).transpose(0, 2, 1) + f64(spec["pos"])[None], ("mean",))
