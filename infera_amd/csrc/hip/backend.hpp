@@ -70,6 +70,7 @@ struct ConvTKernelTables { const float *W = nullptr, *bias = nullptr; const int 
 struct ResizeTables { const int *row_idx = nullptr, *col_idx = nullptr; const float *row_wgt = nullptr, *col_wgt = nullptr; };  // Resize2d
 struct SpatialNormTables { const float *gamma = nullptr, *beta = nullptr; };  // SpatialNorm (per channel: the same in either layout)
 struct TokensTables { const float *prefix = nullptr, *pos = nullptr; };  // Tokens (row-major [P, E] and [T, E]: the window's own order)
+struct ChannelNormTables { const float *gamma = nullptr, *beta = nullptr; };  // ChannelNorm (per channel: the same in either layout; beta may be absent)
 struct RnnTables { const float *wr = nullptr, *bias = nullptr, *bias2 = nullptr, *h0 = nullptr, *c0 = nullptr; };
 struct DeviceStep {  // (a step fills the one struct of its family)
   PlainTables plain;
@@ -85,6 +86,7 @@ struct DeviceStep {  // (a step fills the one struct of its family)
   ConvTKernelTables convt;
   ResizeTables resize;
   SpatialNormTables spatialnorm;
+  ChannelNormTables channelnorm;
   TokensTables tokens;
 };
 

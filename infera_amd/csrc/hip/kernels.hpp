@@ -357,4 +357,10 @@ bool spatialnorm_apply(hipStream_t s, const float *X, const float *stats, const 
 // X: NCHW order or (cq) channel-quad planes; prefix [P, C] (P = 0: none), pos [P + S, C] or null: added in the store.  false: beyond the caps
 bool tokens(hipStream_t s, const float *X, const float *prefix, const float *pos, float *Y, int64_t rows, int C, int S, int P, bool cq);
 
+// ---- LayerNorm over the channel axis at each pixel (channelnorm.hip; host/channelnorm.hpp) --------------
+// X, Y: [rows, C, S] in NCHW order or (cq) channel-quad planes, the same layout; gamma [C], beta [C] or null.  regs: the register form
+// (C <= kChannelNormRegsMaxC), else the re-read form.  y = act(d / sqrtf(var + eps) * gamma + beta).  false: beyond the kernel's caps
+bool channelnorm(hipStream_t s, const float *X, const float *gamma, const float *beta, float *Y, int64_t rows, int C, int S, bool cq, bool regs, float eps,
+                 ActParam act);
+
 }  // namespace infera_hip::kern

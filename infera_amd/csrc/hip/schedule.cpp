@@ -4,6 +4,7 @@
 // packs, uploads and launches what is decided here, step by step (model.cpp's loop at load, exec.cpp's per pass).
 #include <sstream>
 
+#include "../host/channelnorm.hpp"
 #include "../host/deconv.hpp"
 #include "../host/spatialnorm.hpp"
 #include "runtime.hpp"
@@ -243,6 +244,7 @@ void Scheduler::decide_layout(bool commit) {
                              s.kind == StepKind::CopyCols || s.kind == StepKind::SliceCols || s.kind == StepKind::LRN ||
                              s.kind == StepKind::ChannelShuffle ||
                              s.kind == StepKind::SpatialNorm || s.kind == StepKind::SpatialStats ||  // (gamma and beta are indexed by channel: no permutation)
+                             s.kind == StepKind::ChannelNorm ||                                      // (likewise)
                              s.kind == StepKind::BinaryConst;  // (its per-row constant is permuted to channel-quad order below)
     // A channel slice is one contiguous block per sample in channel-quad planes only when it starts on a quad
     // boundary (its length is covered by the whole-quads check on the output tensor below): channels 2..5 of an
@@ -627,6 +629,9 @@ void schedule(LoadedModel &m) {
   s.choose_conv_arithmetic();
   s.fold_projection_shortcuts();
   const ScheduleKnobs knobs = ScheduleKnobs::read();
+  // ChannelNorm layers: the register form where C fits it, else (or with INFERA_CHANNELNORM_REGS=0: everywhere) the re-read form
+  for (Step &c : m.plan.steps)
+    if (c.kind == StepKind::ChannelNorm) c.out_mode = channelnorm_regs_form(c.C, knobs.channelnorm_regs) ? 0 : 1;
   s.narrow_edges(StepKind::QDense, knobs.qdense_bytes, true, [](const Step &p, const Step &c) { return c.qx == p.qy; }, m.q_in_bytes, m.q_out_bytes);
   s.narrow_edges(StepKind::HDense, knobs.hdense_half, false, [](const Step &, const Step &) { return true; }, m.h_in_half, m.h_out_half);
   const auto eff = effective_steps(m);
@@ -725,6 +730,17 @@ std::string LoadedModel::describe_json() const {
            ",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\",\"act\":\"" + acts[int(x.act)] + "\"}";
     }
     if (!c.empty()) o << ",\"spatialnorm\":[" << c << "]";
+  }
+  {  // per ChannelNorm step: the form of the kernel that runs it and the layout it reads and writes
+    std::string c;
+    for (size_t i = 0; i < exec.size(); i++) {
+      const Step &x = plan.steps[i];
+      if (x.kind != StepKind::ChannelNorm) continue;
+      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)], out_cq = cq_mode && !nchw_buf[size_t(x.out)];
+      c += std::string(c.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"kernel\":\"" + (x.out_mode == 0 ? "channelnorm_regs" : "channelnorm_reread") +
+           "\",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\"}";
+    }
+    if (!c.empty()) o << ",\"channelnorm\":[" << c << "]";
   }
   {  // per Tokens step: the kernel that runs it and the layout it reads (its result is a flat window)
     std::string c;

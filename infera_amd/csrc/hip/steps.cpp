@@ -5,6 +5,7 @@
 
 #include "../host/deconv.hpp"
 #include "../host/nearest.hpp"
+#include "../host/channelnorm.hpp"
 #include "../host/onnx_model.hpp"
 #include "../host/prep.hpp"
 #include "../host/recurrent.hpp"
@@ -399,6 +400,18 @@ void launch_spatialstats(const PassRunner &r, const Step &x) {
     throw InferaError::onnx("SpatialStats kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
 }
 
+// ---- ChannelNorm (host/channelnorm.hpp, channelnorm.hip): gamma and, where the layer has one, beta per channel ----
+void upload_channelnorm(const Step &s, ChannelNormTables &t, const Upload &up) {
+  t.gamma = up(s.scale);
+  t.beta = s.shift.empty() ? nullptr : up(s.shift);
+}
+void launch_channelnorm(const PassRunner &r, const Step &x, const ChannelNormTables &t) {
+  if (r.cq(x.in0) != r.cq(x.out)) throw InferaError::onnx("ChannelNorm '" + x.origin + "' would have to change the tensor's layout; there is no such kernel");
+  const bool cq = r.cq(x.in0) && x.S > 1;  // (an [N,C,1,1] tensor is the same floats in either layout)
+  if (!kern::channelnorm(r.stream, r.buf(x.in0), t.gamma, t.beta, r.buf(x.out), r.nr, int(x.C), int(x.S), cq, x.out_mode == 0, x.ln_eps, act_of(x)))
+    throw InferaError::onnx("ChannelNorm kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+
 // ---- Tokens (host/tokens.hpp, tokens.hip): the constant rows and the position table, either may be absent ----
 void upload_tokens(const Step &s, TokensTables &t, const Upload &up) {
   t.prefix = s.prefix.empty() ? nullptr : up(s.prefix);
@@ -466,6 +479,7 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::SpatialNorm: launch_spatialnorm(*this, x, d.spatialnorm); break;
     case StepKind::SpatialStats: launch_spatialstats(*this, x); break;
     case StepKind::Tokens: launch_tokens(*this, x, d.tokens); break;
+    case StepKind::ChannelNorm: launch_channelnorm(*this, x, d.channelnorm); break;
     // the steps without tables
     case StepKind::Unary: kern::unary(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], act_of(x)); break;
     case StepKind::BinaryAct:
@@ -531,6 +545,7 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::Resize2d: return upload_resize(s, d.resize, up);
     case StepKind::SpatialNorm: return upload_spatialnorm(s, d.spatialnorm, up);
     case StepKind::Tokens: return upload_tokens(s, d.tokens, up);
+    case StepKind::ChannelNorm: return upload_channelnorm(s, d.channelnorm, up);
     default: return;  // (no tables)
   }
 }

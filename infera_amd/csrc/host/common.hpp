@@ -128,6 +128,7 @@ struct ScheduleKnobs {
   bool nearest;      // INFERA_NEAREST=0|1 (default 1; read when a model is LOWERED)  distance sub-graphs (KMeans, CDist) become one Nearest step (0: operator by operator -- RowReduce, Dense, BinaryAct; same bits on exact data)
   bool convt_mfma;   // INFERA_CONVT_MFMA=0|1 (default 1)  transposed convolutions on the MFMA phase kernel where it applies (0: the generic VALU kernel; same bits on exact data)
   bool spatialnorm_fused;  // INFERA_SPATIALNORM_FUSED=0|1 (default 1)  InstanceNormalization / GroupNormalization layers on the one-pass register kernel where a unit fits (0: SpatialStats + SpatialNorm everywhere; tests, A/B)
+  bool channelnorm_regs;   // INFERA_CHANNELNORM_REGS=0|1 (default 1)  ChannelNorm layers on the register form where C fits (0: the re-read form everywhere; tests, A/B)
   static ScheduleKnobs read();
 };
 // Read per launch inside the kernel launchers, for the bit-identity TESTS only (no effect on results; defaults are the shipped paths):

@@ -21,6 +21,7 @@
 #include <sstream>
 
 #include "attention.hpp"
+#include "channelnorm.hpp"
 #include "common.hpp"
 #include "deconv.hpp"
 #include "spatialnorm.hpp"
@@ -86,6 +87,9 @@ struct Val {
   // set: the distances of the rows to a constant set (buf = -1), not computed yet -- whoever reads the value decides what the Nearest step
   // serves (a label, the best k, the matrix); `rooted`: this value is sqrt(d2)
   std::shared_ptr<struct NearestPending> nn;
+  // set: a CHANNELS-LAST VIEW: `shape` is [N,H,W,C] and `buf` is the [N,C,H,W] tensor a step wrote, untouched -- what a
+  // Transpose(0,2,3,1) of that tensor yields.  Only the operators lower_on_view lists read it
+  bool cl = false;
   bool padded() const { return pend[0] || pend[1] || pend[2] || pend[3]; }
 };
 
@@ -630,6 +634,17 @@ struct Lowerer {
           set_act(n, act.buf, act_shape, true);
           return;
         }
+        if (p && p->kind == StepKind::ChannelNorm && p->act == Act::None && size_t(p->C) == C && size_t(p->S) == S) {  // into gamma and beta (beta may be absent)
+          const bool shifts = !p->shift.empty() || std::any_of(sh.begin(), sh.end(), [](double v) { return v != 0.0; });
+          if (shifts && p->shift.empty()) p->shift.assign(C, 0.f);
+          for (size_t k = 0; k < C; k++) {
+            if (shifts) p->shift[k] = float(sc[k] * double(p->shift[k]) + sh[k]);
+            p->scale[k] = float(sc[k] * double(p->scale[k]));
+          }
+          p->origin += "+" + label;
+          set_act(n, act.buf, act_shape, true);
+          return;
+        }
         if (p && p->kind == StepKind::ConvTranspose2d && p->act == Act::None && size_t(p->Mo) == C) {
           convt_fold_affine(*p, sc, sh, label);
           set_act(n, act.buf, act_shape, true);
@@ -998,6 +1013,10 @@ struct Lowerer {
       if (decomposed_layer_norm(n, x)) return;
       return row_reduce(n);
     }
+    if (!a.is_const && a.shape.size() == 4) {
+      const Val x = a;
+      if (channels_first_norm(n, x)) return;
+    }
     if (a.is_const || a.shape.size() < 3) unsupported(n, "only spatial means of [N,C,...] activations");
     std::vector<int64_t> axes;
     if (has_input(n, 1)) axes = const_ints(n, 1, "axes");
@@ -1177,7 +1196,7 @@ struct Lowerer {
       const bool qdense_act = quantised_layer(*p) && !p->qy.on && (act == Act::Relu || act == Act::Clip);  // on `real`, before the requantisation
       const bool hdense_act = p->kind == StepKind::HDense && cur_half && int(act) >= 1 && int(act) <= kMaxMfmaFusedAct;  // r = half(act(float(r)))
       const bool convt_act = p->kind == StepKind::ConvTranspose2d && int(act) >= 1 && int(act) <= kMaxMfmaFusedAct;  // kinds 1..5 in its epilogue
-      const bool norm_act = p->kind == StepKind::SpatialNorm && mfma_fusable(act);  // the kinds the convolution epilogues take
+      const bool norm_act = (p->kind == StepKind::SpatialNorm || p->kind == StepKind::ChannelNorm) && mfma_fusable(act);  // the kinds the convolution epilogues take
       if (p->act == Act::None && (takes_act || qdense_act || hdense_act || convt_act || norm_act) && (!mfma_step || mfma_fusable(act))) {
         p->act = act;
         p->act_a = pa;
@@ -1950,6 +1969,14 @@ struct Lowerer {
       vals[n.outputs[0]] = const_f32(std::move(t), {Cc, R});
       return;
     }
+    // Transpose(0,2,3,1) of the [N,C,H,W] tensor a step wrote moves nothing: the result is a channels-last view of that tensor (lower_on_view)
+    if (rank == 4 && perm == std::vector<int64_t>{0, 2, 3, 1} && nchw_tensor(a)) {
+      const int buf = a.buf;
+      const std::vector<int64_t> shape = {a.shape[0], a.shape[2], a.shape[3], a.shape[1]};
+      set_act(n, buf, shape, true);
+      vals[n.outputs[0]].cl = true;
+      return;
+    }
     const bool shuffle = a.ra == 0 && rank >= 4 && perm[0] == 0 && perm[1] == 2 && perm[2] == 1 && [&] {
       for (int64_t i = 3; i < rank; i++)
         if (perm[size_t(i)] != i) return false;
@@ -1994,6 +2021,229 @@ struct Lowerer {
     std::swap(vshape[1], vshape[2]);
     s.origin = node_label(n);
     set_act(n, push_step(std::move(s), bshape), vshape);
+  }
+
+  // ---- channels-last views and ChannelNorm (host/channelnorm.hpp): ConvNeXt's permute -> LayerNorm -> Linear -> GELU ->
+  // Linear -> permute.  Transpose(0,2,3,1) of an [N,C,H,W] tensor a step wrote emits nothing: its result is a VIEW (Val::cl) that names the
+  // same buffer.  The operators below read a view as the NCHW tensor it is and lower as they do on one; Transpose(0,3,1,2) ends it ----
+  // Is the rank-4 rows-first value `a` the [N,C,H,W] tensor a step wrote?  (The model input is not: buffer 0 has no producer.)
+  bool nchw_tensor(const Val &a) const {
+    if (a.is_const || a.pv || a.nn || a.q || a.cl || a.ra != 0 || a.padded() || a.buf <= 0 || a.shape.size() != 4 || !producer.count(a.buf)) return false;
+    const auto &bs = plan.buf_shape[size_t(a.buf)];
+    return bs.size() == 4 && bs[1] == a.shape[1] && bs[2] == a.shape[2] && bs[3] == a.shape[3] && bs[1] > 0 && bs[2] > 0 && bs[3] > 0;
+  }
+  bool reads_view(const NodeDef &n) const {
+    for (const auto &in_name : n.inputs) {
+      auto it = vals.find(in_name);
+      if (it != vals.end() && it->second.cl) return true;
+    }
+    return false;
+  }
+  // lowers `n` (by `body`) with every view among its inputs presented as the [N,C,H,W] tensor it names; the result is a view again
+  template <class F>
+  void as_nchw(const NodeDef &n, F body) {
+    std::map<std::string, std::vector<int64_t>> was;
+    for (const auto &in_name : n.inputs) {
+      auto it = vals.find(in_name);
+      if (it == vals.end() || !it->second.cl) continue;
+      Val &v = it->second;
+      was[in_name] = v.shape;
+      v.shape = {v.shape[0], v.shape[3], v.shape[1], v.shape[2]};
+      v.cl = false;
+    }
+    body();
+    for (const auto &w : was) {
+      Val &v = vals[w.first];
+      v.shape = w.second;
+      v.cl = true;
+    }
+    auto it = vals.find(n.outputs[0]);
+    if (it == vals.end() || it->second.is_const || it->second.shape.size() != 4) bad_form(n, "its result on a channels-last view is not an [N,C,H,W] tensor");
+    Val &o = it->second;
+    o.shape = {o.shape[0], o.shape[2], o.shape[3], o.shape[1]};
+    o.cl = true;
+  }
+  // a copy of `n` whose input `i` is the constant `c`
+  NodeDef with_const_input(const NodeDef &n, size_t i, Val c) {
+    NodeDef r = n;
+    r.inputs[i] = n.inputs[i] + "#" + std::to_string(view_consts++);
+    vals[r.inputs[i]] = std::move(c);
+    return r;
+  }
+  int view_consts = 0;
+  // the constant `c` with the dims `dims` (the same elements: type and half tag kept)
+  static Val redimensioned(const Val &c, std::vector<int64_t> dims, std::vector<float> f32) {
+    auto t = std::make_shared<TensorData>();
+    t->dtype = c.c->dtype;
+    t->elem = c.c->elem;
+    t->dims = std::move(dims);
+    t->f32 = std::move(f32);
+    return const_val(std::move(t));
+  }
+  void lower_on_view(const NodeDef &n) {
+    const std::string &op = n.op;
+    static const std::set<std::string> unary_ops = {"Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
+                                                    "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Round"};
+    static const std::map<std::string, char> binary_ops = {{"Add", '+'}, {"Sub", '-'}, {"Mul", '*'}, {"Div", '/'}};
+    if (op == "Transpose") {
+      const Val a = get(n, 0);
+      const auto *perm = n.attr_ints("perm");
+      if (!perm || *perm != std::vector<int64_t>{0, 3, 1, 2})
+        bad_form(n, "it reads the channels-last view '" + n.inputs[0] + "' " + shape_str(a.shape) + "; only Transpose(0,3,1,2), which ends the view, moves no data");
+      set_act(n, a.buf, {a.shape[0], a.shape[3], a.shape[1], a.shape[2]}, true);
+      return;
+    }
+    if (op == "LayerNormalization") return channel_norm_node(n);
+    if (op == "MatMul") return view_matmul(n);
+    if (unary_ops.count(op)) {
+      if (!get(n, 0).cl) bad_form(n, "it reads the channels-last view among its parameters");
+      return as_nchw(n, [&] { unary(n); });
+    }
+    if (auto bo = binary_ops.find(op); bo != binary_ops.end() && n.inputs.size() == 2) {
+      const Val a = get(n, 0), b = get(n, 1);
+      if (!a.is_const && !b.is_const) {
+        if (!(a.cl && b.cl)) {
+          const bool a_view = a.cl;
+          bad_form(n, "it mixes the channels-last view '" + n.inputs[a_view ? 0 : 1] + "' " + shape_str((a_view ? a : b).shape) + " with '" + n.inputs[a_view ? 1 : 0] + "' " +
+                          shape_str((a_view ? b : a).shape) + ", which is not one; Transpose(0,3,1,2) ends a view");
+        }
+        if (a.shape != b.shape) bad_form(n, "two channels-last views must have one shape, got " + shape_str(a.shape) + " and " + shape_str(b.shape));
+        return as_nchw(n, [&] { binary(n, bo->second); });
+      }
+      const size_t ci = a.is_const ? 0 : 1;
+      const Val &v = a.is_const ? b : a, &c = a.is_const ? a : b;
+      if (c.c->dtype != onnx::kFloat) bad_form(n, "the constant operand of an operator on a channels-last view must be f32");
+      const int64_t C = v.shape[3];
+      if (c.c->f32.size() == 1) return as_nchw(n, [&] { binary(n, bo->second); });  // a scalar
+      const bool per_channel = int64_t(c.c->f32.size()) == C && !c.shape.empty() && c.shape.back() == C && c.shape.size() <= 4;
+      if (!per_channel)
+        bad_form(n, "the constant " + shape_str(c.shape) + " is neither a scalar nor one value per channel ([" + std::to_string(C) + "] or [1,1,1," + std::to_string(C) +
+                        "]) of the channels-last view " + shape_str(v.shape));
+      // one value per channel, read as [C,1,1]: the per-channel rule of an [N,C,H,W] tensor
+      const NodeDef r = with_const_input(n, ci, redimensioned(c, {C, 1, 1}, c.c->f32));
+      return as_nchw(r, [&] { binary(r, bo->second); });
+    }
+    for (size_t i = 0; i < n.inputs.size(); i++)
+      if (auto it = vals.find(n.inputs[i]); it != vals.end() && it->second.cl)
+        bad_form(n, "it reads the channels-last view '" + n.inputs[i] + "' " + shape_str(it->second.shape) + " (a Transpose(0,2,3,1) that moved no data); only LayerNormalization(axis = -1), "
+                    "MatMul by a constant, elementwise operators and Transpose(0,3,1,2) read one");
+  }
+  // ONE ChannelNorm step on the [N,C,H,W] tensor `x`; the result is bound to `out_name`, as a view or not
+  void channel_norm_step(const NodeDef &n, const Val &x, std::vector<float> scale, std::vector<float> shift, bool has_shift, float eps, const std::string &origin,
+                         const std::string &out_name, bool as_view) {
+    const int64_t C = x.shape[1], S = x.shape[2] * x.shape[3];
+    if (const std::string why = channelnorm_refusal(C, S, int64_t(scale.size()), has_shift ? int64_t(shift.size()) : -1, eps); !why.empty()) bad_form(n, why);
+    Step s;
+    s.kind = StepKind::ChannelNorm;
+    s.in0 = x.buf;
+    s.C = C;
+    s.S = S;
+    s.H = x.shape[2];
+    s.Wd = x.shape[3];
+    s.scale = std::move(scale);
+    if (has_shift) s.shift = std::move(shift);
+    s.ln_eps = eps;
+    s.origin = origin;
+    const std::vector<int64_t> shape = x.shape;
+    Val v;
+    v.buf = push_step(std::move(s), shape);
+    v.shape = as_view ? std::vector<int64_t>{shape[0], shape[2], shape[3], shape[1]} : shape;
+    v.cl = as_view;
+    vals[out_name] = v;
+    buf_names[v.buf].push_back(out_name);
+  }
+  // LayerNormalization(axis = -1) on a view: over the channels at each pixel
+  void channel_norm_node(const NodeDef &n) {
+    const Val a = get(n, 0);
+    if (!a.cl) bad_form(n, "it reads the channels-last view among its parameters");
+    int64_t axis = n.attr_i("axis", -1);
+    if (axis < 0) axis += 4;
+    if (axis != 3)
+      bad_form(n, "on the channels-last view " + shape_str(a.shape) + " only normalisation over the channel axis (axis = -1) is supported, got axis " + std::to_string(n.attr_i("axis", -1)));
+    for (size_t o = 1; o < n.outputs.size(); o++)
+      if (!n.outputs[o].empty() && uses.count(n.outputs[o]) && uses[n.outputs[o]] > 0)
+        bad_form(n, std::string("output ") + (o == 1 ? "Mean" : "InvStdDev") + " is consumed; only Y is served");
+    if (!has_input(n, 1)) bad_form(n, "Scale is required");
+    const Val &g = get(n, 1);
+    if (!g.is_const || g.c->dtype != onnx::kFloat) bad_form(n, "Scale and B must be constant f32 tensors");
+    std::vector<float> scale = g.c->f32, shift;
+    const bool has_b = has_input(n, 2);
+    if (has_b) {
+      const Val &b = get(n, 2);
+      if (!b.is_const || b.c->dtype != onnx::kFloat) bad_form(n, "Scale and B must be constant f32 tensors");
+      shift = b.c->f32;
+    }
+    Val x = a;
+    x.shape = {a.shape[0], a.shape[3], a.shape[1], a.shape[2]};
+    x.cl = false;
+    channel_norm_step(n, x, std::move(scale), std::move(shift), has_b, n.attr_f("epsilon", 1e-5f), node_label(n), n.outputs[0], true);
+  }
+  // MatMul of a view by a constant [C, M]: the 1x1 convolution [M, C, 1, 1] it is, through the path a Conv node takes
+  void view_matmul(const NodeDef &n) {
+    const Val a = get(n, 0);
+    const Val &b = get(n, 1);
+    if (!a.cl) bad_form(n, "the channels-last view '" + n.inputs[1] + "' is its right operand; only view x constant [C, M] is supported");
+    const int64_t C = a.shape[3];
+    if (!b.is_const || b.c->dtype != onnx::kFloat || b.shape.size() != 2 || b.shape[0] != C || b.c->q_data)
+      bad_form(n, "a MatMul on the channels-last view " + shape_str(a.shape) + " needs a constant f32 [" + std::to_string(C) + ", M] right operand" +
+                      (b.is_const ? ", got " + shape_str(b.shape) : ", got an activation"));
+    const int64_t M = b.shape[1];
+    std::vector<float> w(size_t(M * C));
+    for (int64_t c = 0; c < C; c++)
+      for (int64_t mo = 0; mo < M; mo++) w[size_t(mo * C + c)] = b.c->f32[size_t(c * M + mo)];
+    NodeDef r = with_const_input(n, 1, redimensioned(b, {M, C, 1, 1}, std::move(w)));
+    r.attrs.clear();
+    as_nchw(r, [&] { conv(r); });
+  }
+  // Hugging Face's ConvNextLayerNorm(data_format = "channels_first") on an [N,C,H,W] tensor a step wrote:
+  //   ReduceMean(axes = [1]) -> Sub -> Pow(2) | Mul(d, d) -> ReduceMean(axes = [1]) -> Add(eps) -> Sqrt -> Div [-> Mul(w [C,1,1])] [-> Add(b [C,1,1])]
+  // matched forward from the first ReduceMean as decomposed_layer_norm matches the [N,E] form; the nodes up to the Div emit nothing, and the
+  // Mul / Add behind it compose into gamma and beta by the per-channel rule (binary).  false: not that chain
+  bool channel_axis_mean(const NodeDef &n) {
+    if (n.op != "ReduceMean" || n.attr_i("keepdims", 1) == 0) return false;
+    std::vector<int64_t> axes;
+    if (has_input(n, 1)) {
+      const Val *c = find_value(n.inputs[1]);
+      if (!c || !c->is_const || c->c->dtype != onnx::kInt64) return false;
+      axes = c->c->i64;
+    } else if (auto *p = n.attr_ints("axes")) axes = *p;
+    return axes.size() == 1 && (axes[0] == 1 || axes[0] == -3);
+  }
+  bool channels_first_norm(const NodeDef &mean, const Val &x) {
+    if (!nchw_tensor(x) || !channel_axis_mean(mean)) return false;
+    const NodeDef *sub = only_reader(mean.outputs[0]);
+    if (!sub || sub->op != "Sub" || sub->inputs.size() != 2 || sub->inputs[0] != mean.inputs[0] || sub->inputs[1] != mean.outputs[0]) return false;
+    const std::string &d = sub->outputs[0];
+    for (const auto &o : m.outputs)
+      if (o.name == d) return false;
+    auto dit = consumers_of.find(d);
+    if (dit == consumers_of.end()) return false;
+    const std::set<size_t> readers(dit->second.begin(), dit->second.end());
+    if (readers.size() != 2) return false;
+    const NodeDef *sq = nullptr, *div = nullptr;
+    for (size_t c : readers) {
+      const NodeDef &r = m.nodes[c];
+      if (r.op == "Div" && r.inputs.size() == 2 && r.inputs[0] == d) div = &r;
+      else if (r.op == "Mul" && r.inputs.size() == 2 && r.inputs[0] == d && r.inputs[1] == d) sq = &r;
+      else if (r.op == "Pow") {
+        const Val *e = const_operand(r, d, true);
+        if (e && e->c->f32.size() == 1 && e->c->f32[0] == 2.f) sq = &r;
+      }
+    }
+    if (!sq || !div) return false;
+    const NodeDef *var = only_reader(sq->outputs[0]);
+    if (!var || !channel_axis_mean(*var)) return false;
+    const NodeDef *add = only_reader(var->outputs[0]);
+    const Val *eps = add && add->op == "Add" ? const_operand(*add, var->outputs[0]) : nullptr;
+    if (!eps || eps->c->f32.size() != 1 || !(eps->c->f32[0] >= 0.f) || !std::isfinite(eps->c->f32[0])) return false;
+    const NodeDef *sq_rt = only_reader(add->outputs[0]);
+    if (!sq_rt || sq_rt->op != "Sqrt" || only_reader(sq_rt->outputs[0]) != div || div->inputs[1] != sq_rt->outputs[0]) return false;
+    const int64_t C = x.shape[1];
+    if (!channelnorm_refusal(C, x.shape[2] * x.shape[3], C, -1, eps->c->f32[0]).empty()) return false;
+    for (const NodeDef *q : {sub, sq, var, add, sq_rt, div}) absorbed[size_t(q - m.nodes.data())] = 1;
+    channel_norm_step(mean, x, std::vector<float>(size_t(C), 1.f), {}, false, eps->c->f32[0], node_label(mean) + "+...+" + node_label(*div), div->outputs[0], false);
+    if (cur_half) mark_half(div->outputs[0]);
+    return true;
   }
 
   // ---- the crossing from the image path to the table path (host/tokens.hpp): Conv -> Flatten(2) / Reshape [N,E,S] ->
@@ -3245,6 +3495,7 @@ struct Lowerer {
         if (it != vals.end() && it->second.q) bad_form(n, "it reads the quantised tensor '" + in_name + "'; only DequantizeLinear, QLinearMatMul and QLinearConv do");
       }
     if ((op == "ArgMin" || op == "TopK" || op == "Sqrt" || op == "Identity") && nearest_reader(n)) return;
+    if (reads_view(n)) return lower_on_view(n);
     if (op == "QuantizeLinear") quantize_linear(n);
     else if (op == "DequantizeLinear") dequantize_linear(n);
     else if (op == "QLinearMatMul") qlinear_matmul(n);
@@ -4456,6 +4707,11 @@ struct Lowerer {
     if (it->second.pv) materialize(out.name, nullptr);
     if (it->second.nn) materialize_nearest(out.name);
     if (it->second.q) bad_form(*quant_node.at(out.name), "its quantised result is the graph output '" + out.name + "'; end the graph with DequantizeLinear");
+    if (it->second.cl) {
+      for (const auto &nd : m.nodes)
+        if (std::find(nd.outputs.begin(), nd.outputs.end(), out.name) != nd.outputs.end())
+          bad_form(nd, "its result " + shape_str(it->second.shape) + " is a channels-last view and the graph output '" + out.name + "'; results are served in [N,C,H,W] order: end the graph with Transpose(0,3,1,2)");
+    }
     if (it->second.is_const) throw InferaError::onnx("output '" + out.name + "' is a constant; nothing to run");
     if (it->second.padded()) throw InferaError::onnx("output '" + out.name + "' is a Pad result; padding is only folded into a following Conv");
     if (it->second.ra != 0)
@@ -4517,7 +4773,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -4612,6 +4868,14 @@ std::string Plan::describe_json() const {
         return json_int_array(b);
       };
       o << ",\"scale_bits\":" << bits(s.scale) << ",\"shift_bits\":" << bits(s.shift);
+    }
+    if (s.kind == StepKind::ChannelNorm) {  // gamma and beta as their f32 bit patterns, as for SpatialNorm
+      auto bits = [](const std::vector<float> &v) {
+        std::vector<uint32_t> b(v.size());
+        if (!v.empty()) std::memcpy(b.data(), v.data(), v.size() * sizeof(float));
+        return json_int_array(b);
+      };
+      o << ",\"C\":" << s.C << ",\"hw\":[" << s.H << "," << s.Wd << "],\"epsilon\":" << double(s.ln_eps) << ",\"scale_bits\":" << bits(s.scale) << ",\"shift_bits\":" << bits(s.shift);
     }
     if (s.kind == StepKind::Tokens) {  // the tables as one hash over their f32 bit patterns: equal spellings give equal plans
       uint64_t h = 1469598103934665603ull;

@@ -73,6 +73,7 @@ enum class StepKind : int {
   SpatialNorm = 36,   // InstanceNormalization / GroupNormalization over the (C / groups) * S elements of each of `groups` channel groups of in0 [rows, C, S]: y = act((x - mean) / sqrt(var + ln_eps) * scale[c] + shift[c]); in1 = -1: the fused kernel, else in1 = a SpatialStats result (host/spatialnorm.hpp, spatialnorm.hip)
   SpatialStats = 37,  // out [rows, groups, 3] = (mean, resid, 1 / sqrt(var + ln_eps)) of each group of in0: the first half of the general SpatialNorm plan (the scheduler inserts it, schedule.cpp)
   Tokens = 38,        // out [rows, rep = P + S, K = C] = the window of in0 [rows, C, S] (NCHW or channel quads): out[r, P + s, c] = in0[r, c, s] (+ cst[P + s, c]); rows p < P = prefix[p, c] (+ cst[p, c]) (host/tokens.hpp, tokens.hip)
+  ChannelNorm = 39,   // LayerNorm over the C channels at each of the S pixels of in0 [rows, C, S] (NCHW or channel quads, never changed): y = act((x - mean) / sqrt(var + ln_eps) * scale[c] + shift[c]), shift may be empty; out_mode (set by the scheduler): 0 the register form, 1 the re-read form (host/channelnorm.hpp, channelnorm.hip)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum

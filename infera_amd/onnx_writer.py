@@ -3403,3 +3403,299 @@ def cnn_stem_encoder_reference(spec: dict, x) -> dict:
     f = conv(np.maximum(conv(x, spec["W1"], spec["b1"]), 0.0), spec["W2"], spec["b2"])
     n, E = f.shape[:2]
     return transformer_reference(spec["enc"], f.reshape(n, E, -1).transpose(0, 2, 1) + f64(spec["pos"])[None], ("mean",))
+
+
+# ------------------------------------------------------------------------------------------
+# ConvNeXt: LayerNorm over the channel axis at each pixel (ChannelNorm step) and the channels-last detour around it
+# ------------------------------------------------------------------------------------------
+def channelnorm_reference(x, gamma, beta, eps: float) -> np.ndarray:
+    """x [N, C, H, W] normalised over the C channels at each pixel (the biased variance), then gamma[c] * . + beta[c] (beta None: none): float64."""
+    x = np.asarray(x, np.float64)
+    mean = x.mean(axis=1, keepdims=True)
+    d = x - mean
+    var = (d * d).mean(axis=1, keepdims=True)
+    y = d / np.sqrt(var + float(eps)) * np.asarray(gamma, np.float64).reshape(1, -1, 1, 1)
+    return y if beta is None else y + np.asarray(beta, np.float64).reshape(1, -1, 1, 1)
+
+
+def _gelu64(a):
+    from math import erf
+    return 0.5 * a * (1.0 + np.vectorize(erf)(a / math.sqrt(2.0)))
+
+
+class _ConvNextNet:
+    """Appends the nodes of ConvNeXt layers in one of the spellings exporters write.  Values are named [N, C, H, W] tensors between layers;
+    style "torchvision" / "hf" take the channels-last detour (Transpose(0,2,3,1) ... Transpose(0,3,1,2)), "nchw" spells the same layers
+    with the channels-first norm and 1x1 Conv nodes."""
+
+    def __init__(self, dtype=np.float32):
+        self.nodes, self.inits, self.dtype, self.count = [], [], dtype, 0
+
+    def f(self, name, v):
+        self.inits.append(tensor(name, np.asarray(v, dtype=self.dtype)))
+        return name
+
+    def i64(self, name, v):
+        self.inits.append(tensor(name, np.asarray(v, dtype=np.int64)))
+        return name
+
+    def op(self, op, ins, out, attrs=(), name=None):
+        self.nodes.append(node(op, list(ins), [out], list(attrs), name=name or out))
+        return out
+
+    def to_last(self, x, p):
+        return self.op("Transpose", [x], p + "_nhwc", [attr_ints("perm", [0, 2, 3, 1])], name=p + "_to_last")
+
+    def to_first(self, x, p, out=None):
+        return self.op("Transpose", [x], out or p + "_nchw", [attr_ints("perm", [0, 3, 1, 2])], name=p + "_to_first")
+
+    def norm_op(self, x_last, g, b, eps, p, axis=-1, outputs=1):
+        """LayerNormalization on a channels-last value; the result is channels-last"""
+        ins = [x_last, self.f(p + "_g", g)] + ([self.f(p + "_b", b)] if b is not None else [])
+        outs = [p + "_ln"] + [p + "_mean", p + "_isd"][:outputs - 1]
+        self.nodes.append(node("LayerNormalization", ins, outs, [attr_i("axis", axis), attr_f("epsilon", eps)], name=p + "_ln"))
+        return outs[0]
+
+    def norm_first(self, x, g, b, eps, p, square="pow"):
+        """Hugging Face's channels-first ConvNextLayerNorm on an [N, C, H, W] value"""
+        c = len(g)
+        self.i64(p + "_ax", [1])
+        self.f(p + "_eps", np.asarray(eps))
+        ax = [attr_ints("axes", [1]), attr_i("keepdims", 1)]
+        self.op("ReduceMean", [x], p + "_mu", ax, name=p + "_mean")
+        self.op("Sub", [x, p + "_mu"], p + "_d", name=p + "_sub")
+        if square == "pow":
+            self.op("Pow", [p + "_d", self.f(p + "_two", np.asarray(2.0))], p + "_sq", name=p + "_pow")
+        else:
+            self.op("Mul", [p + "_d", p + "_d"], p + "_sq", name=p + "_square")
+        self.op("ReduceMean", [p + "_sq"], p + "_var", ax, name=p + "_varmean")
+        self.op("Add", [p + "_var", p + "_eps"], p + "_ve", name=p + "_addeps")
+        self.op("Sqrt", [p + "_ve"], p + "_sd", name=p + "_sqrt")
+        cur = self.op("Div", [p + "_d", p + "_sd"], p + "_nrm", name=p + "_div")
+        cur = self.op("Mul", [self.f(p + "_g", np.asarray(g).reshape(c, 1, 1)), cur], p + "_sc", name=p + "_gamma")
+        if b is not None:
+            cur = self.op("Add", [cur, self.f(p + "_b", np.asarray(b).reshape(c, 1, 1))], p + "_cf", name=p + "_beta")
+        return cur
+
+    def norm2d(self, x, g, b, eps, p, style):
+        """the norm of an [N, C, H, W] value, [N, C, H, W] again: torchvision's LayerNorm2d or the channels-first chain"""
+        if style == "torchvision":
+            return self.to_first(self.norm_op(self.to_last(x, p), g, b, eps, p), p)
+        return self.norm_first(x, g, b, eps, p)
+
+    def gelu(self, x, p, form):
+        if form == "op":
+            return self.op("Gelu", [x], p + "_gelu")
+        self.f(p + "_sqrt2", np.asarray(math.sqrt(2.0))); self.f(p + "_one", np.asarray(1.0)); self.f(p + "_half", np.asarray(0.5))  # noqa: E702
+        self.op("Div", [x, p + "_sqrt2"], p + "_g0")
+        self.op("Erf", [p + "_g0"], p + "_g1")
+        self.op("Add", [p + "_g1", p + "_one"], p + "_g2")
+        self.op("Mul", [x, p + "_g2"], p + "_g3")
+        return self.op("Mul", [p + "_g3", p + "_half"], p + "_gelu")
+
+    def block(self, x, L, eps, p, style, gelu="op"):
+        """depthwise 7x7 -> norm -> Linear 4C -> GELU -> Linear C -> layer scale -> + x.  L: dw_W [C,1,7,7], dw_b, g, b, W1 [C,4C], b1, W2 [4C,C], b2, ls [C] | None"""
+        c = len(L["g"])
+        dw = self.op("Conv", [x, self.f(p + "_dwW", L["dw_W"]), self.f(p + "_dwb", L["dw_b"])], p + "_dw",
+                     [attr_ints("kernel_shape", [7, 7]), attr_ints("pads", [3, 3, 3, 3]), attr_i("group", c)])
+        if style == "nchw":
+            h = self.norm_first(dw, L["g"], L["b"], eps, p + "_norm")
+            k1 = [attr_ints("kernel_shape", [1, 1])]
+            h = self.op("Conv", [h, self.f(p + "_W1", np.asarray(L["W1"]).T.reshape(4 * c, c, 1, 1)), self.f(p + "_b1", L["b1"])], p + "_fc1", k1)
+            h = self.gelu(h, p, gelu)
+            h = self.op("Conv", [h, self.f(p + "_W2", np.asarray(L["W2"]).T.reshape(c, 4 * c, 1, 1)), self.f(p + "_b2", L["b2"])], p + "_fc2", k1)
+            if L.get("ls") is not None:
+                h = self.op("Mul", [self.f(p + "_ls", np.asarray(L["ls"]).reshape(c, 1, 1)), h], p + "_scaled")
+            return self.op("Add", [x, h], p + "_out", name=p + "_residual")
+        h = self.norm_op(self.to_last(dw, p), L["g"], L["b"], eps, p + "_norm")
+        h = self.op("Add", [self.op("MatMul", [h, self.f(p + "_W1", L["W1"])], p + "_mm1"), self.f(p + "_b1", L["b1"])], p + "_fc1")
+        h = self.gelu(h, p, gelu)
+        h = self.op("Add", [self.op("MatMul", [h, self.f(p + "_W2", L["W2"])], p + "_mm2"), self.f(p + "_b2", L["b2"])], p + "_fc2")
+        if style == "hf":
+            if L.get("ls") is not None:
+                h = self.op("Mul", [self.f(p + "_ls", L["ls"]), h], p + "_scaled")
+            h = self.to_first(h, p)
+        else:
+            h = self.to_first(h, p)
+            if L.get("ls") is not None:
+                h = self.op("Mul", [self.f(p + "_ls", np.asarray(L["ls"]).reshape(c, 1, 1)), h], p + "_scaled")
+        return self.op("Add", [x, h], p + "_out", name=p + "_residual")
+
+
+def _block_params(rng, c, scale=1.0, layer_scale=True):
+    u = lambda shape, fan: (rng.uniform(-1, 1, shape) * scale / math.sqrt(fan)).astype(np.float32)  # noqa: E731
+    return {"dw_W": u((c, 1, 7, 7), 49), "dw_b": u((c,), 49), "g": rng.uniform(0.5, 1.5, c).astype(np.float32), "b": rng.uniform(-0.5, 0.5, c).astype(np.float32),
+            "W1": u((c, 4 * c), c), "b1": u((4 * c,), c), "W2": u((4 * c, c), 4 * c), "b2": u((c,), 4 * c),
+            "ls": rng.uniform(0.25, 1.0, c).astype(np.float32) if layer_scale else None}
+
+
+def _block_reference(x, L, eps):
+    f64 = lambda a: np.asarray(a, np.float64)  # noqa: E731
+    c = x.shape[1]
+    h = _conv_taps(x, f64(L["dw_W"]), (1, 1), (3, 3, 3, 3), (1, 1), c, 0.0) + f64(L["dw_b"]).reshape(1, -1, 1, 1)
+    h = channelnorm_reference(h, L["g"], L["b"], eps).transpose(0, 2, 3, 1)
+    h = _gelu64(h @ f64(L["W1"]) + f64(L["b1"])) @ f64(L["W2"]) + f64(L["b2"])
+    if L.get("ls") is not None:
+        h = h * f64(L["ls"])
+    return x + h.transpose(0, 3, 1, 2)
+
+
+def channel_norm_model(c: int = 8, hw=(5, 7), spelling: str = "nhwc_op", act: str | None = None, front: str = "relu", eps: float = 1e-6, bias: bool = True,
+                       post_affine: bool = False, square: str = "pow", offset: float = 0.0, integer: bool = False, seed: int = 7) -> tuple[bytes, dict]:
+    """One norm over the channels of [N, c, H, W] behind `front` -- "relu": Relu(X), an NCHW tensor; "conv": an identity 1x1 Conv in front
+    and an identity 1x1 ConvTranspose behind, which put the layer on channel-quad tensors where c % 4 == 0 (exact: X passes unchanged).
+    spelling "nhwc_op": Transpose(0,2,3,1) -> LayerNormalization -> [post_affine: Mul([c]) -> Add([c])] -> [act] -> Transpose(0,3,1,2), all
+    on the channels-last value; "layernorm2d" (torchvision): Transpose -> LayerNormalization -> Transpose back -> [Mul([c,1,1]) -> Add] -> [act];
+    "channels_first" (Hugging Face): the ReduceMean(axes = [1]) chain (square: "pow" | "mul") -> [Mul -> Add] -> [act].  integer: gamma and
+    beta are small integers over 8.  Returns (model, spec) for channel_norm_reference."""
+    rng = np.random.default_rng(seed)
+    H, W = hw
+    if integer:
+        g, b = (rng.integers(1, 16, c) / 8.0).astype(np.float32), (rng.integers(-16, 16, c) / 8.0).astype(np.float32)
+    else:
+        g, b = rng.uniform(0.5, 1.5, c).astype(np.float32), rng.uniform(-0.5, 0.5, c).astype(np.float32)
+    if not bias:
+        b = None
+    g2, b2 = (rng.uniform(0.5, 1.5, c).astype(np.float32), rng.uniform(-0.5, 0.5, c).astype(np.float32)) if post_affine else (None, None)
+    net = _ConvNextNet()
+    eye = np.eye(c, dtype=np.float32).reshape(c, c, 1, 1)
+    if front == "relu":
+        cur = net.op("Relu", ["X"], "front", name="front_relu")
+    elif front == "conv":
+        cur = net.op("Conv", ["X", net.f("front_w", eye)], "front", [attr_ints("kernel_shape", [1, 1])], name="front_conv")
+    else:
+        raise ValueError(front)
+    last = spelling == "nhwc_op"
+    if spelling in ("nhwc_op", "layernorm2d"):
+        cur = net.norm_op(net.to_last(cur, "norm"), g, b, eps, "norm")
+        if not last:
+            cur = net.to_first(cur, "norm")
+    elif spelling == "channels_first":
+        cur = net.norm_first(cur, g, b, eps, "norm", square)
+    else:
+        raise ValueError(spelling)
+    if post_affine:
+        sh = (c,) if last else (c, 1, 1)
+        cur = net.op("Mul", [cur, net.f("post_g", g2.reshape(sh))], "post_mul")
+        cur = net.op("Add", [cur, net.f("post_b", b2.reshape(sh))], "post_add")
+    if act:
+        cur = net.op(act, [cur], "act")
+    if last:
+        cur = net.to_first(cur, "norm_back")
+    if front == "conv":
+        cur = net.op("ConvTranspose", [cur, net.f("back_w", eye)], "back", [attr_ints("strides", [1, 1]), attr_ints("pads", [0, 0, 0, 0])], name="back_convt")
+    blob = model("channel_norm", net.nodes, net.inits, [value_info("X", ["N", c, H, W])], [value_info(cur, ["N", c, H, W])], opset=20)
+    return blob, {"c": c, "hw": (H, W), "in_shape": (c, H, W), "gamma": g, "beta": b, "eps": float(np.float32(eps)), "post": (g2, b2), "act": act, "front": front,
+                  "offset": float(offset)}
+
+
+def channel_norm_inputs(spec: dict, rows: int, seed: int = 0) -> np.ndarray:
+    """x = offset + U(-1, 1), f32"""
+    rng = np.random.default_rng(seed)
+    return (spec.get("offset", 0.0) + rng.uniform(-1, 1, size=(rows,) + tuple(spec["in_shape"]))).astype(np.float32)
+
+
+def channel_norm_reference(spec: dict, x) -> np.ndarray:
+    """What channel_norm_model computes, in float64"""
+    x = np.asarray(x, np.float64).reshape((-1,) + tuple(spec["in_shape"]))
+    f = np.maximum(x, 0.0) if spec["front"] == "relu" else x
+    y = channelnorm_reference(f, spec["gamma"], spec["beta"], spec["eps"])
+    if spec["post"][0] is not None:
+        y = y * np.asarray(spec["post"][0], np.float64).reshape(1, -1, 1, 1) + np.asarray(spec["post"][1], np.float64).reshape(1, -1, 1, 1)
+    if spec["act"] == "Relu":
+        y = np.maximum(y, 0.0)
+    elif spec["act"] == "Sigmoid":
+        y = 1.0 / (1.0 + np.exp(-y))
+    elif spec["act"]:
+        raise ValueError(spec["act"])
+    return y
+
+
+def convnext_block_model(c: int = 8, hw=(7, 7), style: str = "torchvision", gelu: str = "op", layer_scale: bool = True, eps: float = 1e-6, seed: int = 11,
+                         weight_scale: float = 1.0) -> tuple[bytes, dict]:
+    """One ConvNeXt block on [N, c, H, W] between a 1x1 Conv with bias (so that the block reads a tensor a step wrote, in channel quads when
+    c % 4 == 0) and an identity 1x1 ConvTranspose (which stores the served NCHW tensor).  style: "torchvision" ([c,1,1] layer scale after the
+    permute back), "hf" ([c] layer scale before it), "nchw" (the same block with the channels-first norm and Conv 1x1 nodes, no Transpose).
+    gelu: "op" | "decomposed".  Returns (model, spec) for convnext_block_reference."""
+    rng = np.random.default_rng(seed)
+    H, W = hw
+    stem_W = (rng.uniform(-1, 1, (c, c, 1, 1)) * weight_scale / math.sqrt(c)).astype(np.float32)
+    stem_b = (rng.uniform(-1, 1, c) * weight_scale).astype(np.float32)
+    L = _block_params(rng, c, weight_scale, layer_scale)
+    net = _ConvNextNet()
+    cur = net.op("Conv", ["X", net.f("stem_W", stem_W), net.f("stem_b", stem_b)], "stem", [attr_ints("kernel_shape", [1, 1])])
+    cur = net.block(cur, L, eps, "blk", style, gelu)
+    cur = net.op("ConvTranspose", [cur, net.f("back_w", np.eye(c, dtype=np.float32).reshape(c, c, 1, 1))], "back", [attr_ints("strides", [1, 1]), attr_ints("pads", [0, 0, 0, 0])])
+    blob = model("convnext_block", net.nodes, net.inits, [value_info("X", ["N", c, H, W])], [value_info(cur, ["N", c, H, W])], opset=20)
+    return blob, {"c": c, "hw": (H, W), "in_shape": (c, H, W), "stem_W": stem_W, "stem_b": stem_b, "block": L, "eps": float(np.float32(eps))}
+
+
+def convnext_block_reference(spec: dict, x) -> np.ndarray:
+    x = np.asarray(x, np.float64).reshape((-1,) + tuple(spec["in_shape"]))
+    f = _conv_taps(x, np.asarray(spec["stem_W"], np.float64), (1, 1), (0, 0, 0, 0), (1, 1), 1, 0.0) + np.asarray(spec["stem_b"], np.float64).reshape(1, -1, 1, 1)
+    return _block_reference(f, spec["block"], spec["eps"])
+
+
+def convnext_spec(img=(3, 32, 32), widths: Sequence[int] = (8, 16), depths: Sequence[int] = (1, 1), classes: int = 5, weight_scale: float = 1.0,
+                  layer_scale: bool = True, eps: float = 1e-6, seed: int = 71) -> dict:
+    """A seeded ConvNeXt in small: stem Conv k4 s4 + LayerNorm2d; per stage `depths[i]` blocks of width `widths[i]` (depthwise 7x7 -> norm ->
+    Linear 4C -> GELU -> Linear C -> layer scale -> residual); LayerNorm2d + Conv k2 s2 between stages; global pool -> norm -> Linear."""
+    rng = np.random.default_rng(seed)
+    u = lambda shape, fan: (rng.uniform(-1, 1, shape) * weight_scale / math.sqrt(fan)).astype(np.float32)  # noqa: E731
+    nrm = lambda c: (rng.uniform(0.5, 1.5, c).astype(np.float32), rng.uniform(-0.5, 0.5, c).astype(np.float32))  # noqa: E731
+    c0 = img[0]
+    spec = {"img": tuple(img), "widths": tuple(widths), "depths": tuple(depths), "classes": classes, "eps": float(np.float32(eps)),
+            "stem_W": u((widths[0], c0, 4, 4), 16 * c0), "stem_b": u((widths[0],), 16 * c0), "stem_norm": nrm(widths[0]), "stages": [], "down": []}
+    for i, (c, d) in enumerate(zip(widths, depths)):
+        if i > 0:
+            spec["down"].append({"norm": nrm(widths[i - 1]), "W": u((c, widths[i - 1], 2, 2), 4 * widths[i - 1]), "b": u((c,), 4 * widths[i - 1])})
+        spec["stages"].append([_block_params(rng, c, weight_scale, layer_scale) for _ in range(d)])
+    spec["head_norm"] = nrm(widths[-1])
+    spec["head_W"], spec["head_b"] = u((widths[-1], classes), widths[-1]), u((classes,), widths[-1])
+    return spec
+
+
+def convnext_norm_count(spec: dict) -> int:
+    return 1 + sum(spec["depths"]) + len(spec["down"]) + 1
+
+
+def convnext_from_spec(spec: dict, style: str = "torchvision", gelu: str = "op", half: bool = False, batch: int | str = "N") -> bytes:
+    """The ONNX model of a convnext_spec() dict, input X [N, C, H, W], output "logits" [N, classes].  style "torchvision": every norm is
+    Transpose(0,2,3,1) -> LayerNormalization -> Transpose(0,3,1,2) (the head's on the pooled [N, C, 1, 1] tensor), [C,1,1] layer scale; "hf":
+    the channels-first chain for the stem and downsampling norms and the head's, the channels-last detour with [C] layer scale in the blocks;
+    "nchw": no Transpose anywhere.  half: a float16 graph (float16 input, weights and output)."""
+    net = _ConvNextNet(np.float16 if half else np.float32)
+    eps, t = spec["eps"], FLOAT16 if half else FLOAT
+    cur = net.op("Conv", ["X", net.f("stem_W", spec["stem_W"]), net.f("stem_b", spec["stem_b"])], "stem", [attr_ints("kernel_shape", [4, 4]), attr_ints("strides", [4, 4])])
+    nstyle = "torchvision" if style == "torchvision" else "nchw"
+    cur = net.norm2d(cur, spec["stem_norm"][0], spec["stem_norm"][1], eps, "stem_norm", nstyle)
+    for i, blocks in enumerate(spec["stages"]):
+        if i > 0:
+            D = spec["down"][i - 1]
+            cur = net.norm2d(cur, D["norm"][0], D["norm"][1], eps, f"down{i}_norm", nstyle)
+            cur = net.op("Conv", [cur, net.f(f"down{i}_W", D["W"]), net.f(f"down{i}_b", D["b"])], f"down{i}", [attr_ints("kernel_shape", [2, 2]), attr_ints("strides", [2, 2])])
+        for j, L in enumerate(blocks):
+            cur = net.block(cur, L, eps, f"s{i}b{j}", style, gelu)
+    cur = net.op("GlobalAveragePool", [cur], "pool")
+    cur = net.norm2d(cur, spec["head_norm"][0], spec["head_norm"][1], eps, "head_norm", nstyle)
+    cur = net.op("Flatten", [cur], "flat", [attr_i("axis", 1)])
+    net.op("Gemm", [cur, net.f("head_W", spec["head_W"]), net.f("head_b", spec["head_b"])], "logits")
+    c, H, W = spec["img"]
+    return model("convnext", net.nodes, net.inits, [value_info("X", [batch, c, H, W], t)], [value_info("logits", [batch, spec["classes"]], t)], opset=20)
+
+
+def convnext_reference(spec: dict, x) -> np.ndarray:
+    """float64 numpy restatement of convnext_from_spec(spec): x [N, C, H, W] -> logits [N, classes]."""
+    f64 = lambda a: np.asarray(a, np.float64)  # noqa: E731
+    eps = spec["eps"]
+    conv = lambda a, w, b, k: _conv_taps(a, f64(w), (k, k), (0, 0, 0, 0), (1, 1), 1, 0.0) + f64(b).reshape(1, -1, 1, 1)  # noqa: E731
+    x = f64(x).reshape((-1,) + tuple(spec["img"]))
+    h = channelnorm_reference(conv(x, spec["stem_W"], spec["stem_b"], 4), spec["stem_norm"][0], spec["stem_norm"][1], eps)
+    for i, blocks in enumerate(spec["stages"]):
+        if i > 0:
+            D = spec["down"][i - 1]
+            h = conv(channelnorm_reference(h, D["norm"][0], D["norm"][1], eps), D["W"], D["b"], 2)
+        for L in blocks:
+            h = _block_reference(h, L, eps)
+    h = channelnorm_reference(h.mean(axis=(2, 3), keepdims=True), spec["head_norm"][0], spec["head_norm"][1], eps)
+    return h.reshape(len(h), -1) @ f64(spec["head_W"]) + f64(spec["head_b"])
