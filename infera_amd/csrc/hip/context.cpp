@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 
 #include "runtime.hpp"
 
@@ -45,6 +46,27 @@ int slot_of_ordinal(int ordinal) {
   throw InferaError::onnx("HIP device " + std::to_string(ordinal) + " is not among the selected devices");
 }
 
+ThreadCtx *new_context(int slot) {
+  auto n = std::make_unique<ThreadCtx>();
+  n->device = devices().ids[size_t(slot)];
+  n->slot = slot;
+  hipError_t e = hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) hip_fail(e, "hipStreamCreateWithFlags");
+  const size_t bytes = size_t(ThreadCtx::kMaxLanes) * ThreadCtx::kMlpQueueStride * sizeof(unsigned);
+  {
+    UnsafeOpGuard guard;  // (an allocation: not while another thread captures a graph)
+    e = hipMalloc(reinterpret_cast<void **>(&n->mlp_queues), bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(n->mlp_queues, 0, bytes, n->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(n->stream);
+  }
+  if (e != hipSuccess) {
+    if (n->mlp_queues) (void)hipFree(n->mlp_queues);
+    (void)hipStreamDestroy(n->stream);
+    hip_fail(e, "tile queue of a new context");
+  }
+  return n.release();
+}
+
 ThreadCtx &ctx_for_slot(int slot) {
   const auto &ds = devices();
   if (t_holder.by_slot.size() < ds.ids.size()) t_holder.by_slot.resize(ds.ids.size(), nullptr);
@@ -59,17 +81,7 @@ ThreadCtx &ctx_for_slot(int slot) {
         g_pool[size_t(slot)].pop_back();
       }
     }
-    if (!c) {
-      auto *n = new ThreadCtx();
-      n->device = ds.ids[size_t(slot)];
-      n->slot = slot;
-      hipError_t e = hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking);
-      if (e != hipSuccess) {
-        delete n;
-        hip_fail(e, "hipStreamCreateWithFlags");
-      }
-      c = n;
-    }
+    if (!c) c = new_context(slot);
   }
   return *c;
 }
@@ -112,20 +124,16 @@ HostLease::HostLease(int slot) : pool(host_pool(slot)) {
     }
     pool.created++;
   }
-  auto *n = new ThreadCtx();
-  n->device = ds.ids[size_t(slot)];
-  n->slot = slot;
-  const hipError_t e = hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete n;
+  try {
+    c = new_context(slot);
+  } catch (...) {
     {
       std::lock_guard<std::mutex> lk(pool.mu);
       pool.created--;
     }
     pool.cv.notify_one();
-    hip_fail(e, "hipStreamCreateWithFlags");
+    throw;
   }
-  c = n;
   if (size_t(slot) < 64) t_last_ctx[slot] = c;
 }
 HostLease::~HostLease() {

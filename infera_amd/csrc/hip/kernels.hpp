@@ -220,8 +220,11 @@ void mlp3_pack(const Mlp3Shape &sh, const float *W1, const float *b1, const floa
                const float *b3, float *packed);
 // x_colmajor: X is a column-major chunk [d0][rows] (the host path's staging of flat DuckDB columns); only for the chains
 // mlp3_colmajor_supported() names.
+// queue: kMlp3QueueWords zeroed unsigneds in device memory that belong to the launches of stream `s` alone (never to two kernels
+// that may run at once): the tile queue of mlp3_split_kernel, which leaves them zero again at the end of every launch.
+constexpr size_t kMlp3QueueWords = 2;  // head, done
 bool mlp3(hipStream_t s, const Mlp3Shape &sh, const float *X, const float *packed, float *Y, int64_t rows, int num_cus,
-          std::string *why = nullptr, bool x_colmajor = false);
+          unsigned *queue, std::string *why = nullptr, bool x_colmajor = false);
 bool mlp3_colmajor_supported(const Mlp3Shape &sh);
 int64_t mlp3_colmajor_max_rows(const Mlp3Shape &sh);  // longest column-major chunk the chain's kernels read themselves (0: none)
 std::string mlp3_kernel_name(const Mlp3Shape &sh);

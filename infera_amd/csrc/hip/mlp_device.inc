@@ -294,9 +294,25 @@ __global__ __launch_bounds__(C::WAVES * 64) void mlp3_kernel(const float *__rest
 // layer 2 (a partial sum over that half's k range) before the next half is computed, so only
 // MT1/SPLIT accumulator tiles are live at a time.  X stays in registers across the halves.  The narrow
 // head runs on the VALU at the end of the tile (no cross-tile software pipelining needed here).
-template <class C, int SPLIT, int P2S, int NW, bool XCM = false>
+//
+// TQ (tile queue): the waves of a launch do not run at equal speed (the two waves of a SIMD are arbitrated by age, and there
+// is no barrier in the loop to re-align them), so a fixed share of the tiles leaves the faster ones gone while the slower
+// ones still work alone on their SIMD.  With TQ a wave's FIRST tile is still blockIdx.x * NW + wave (no atomic before the
+// first MFMA); every later one is W + atomicAdd(queue[0], 1), W = gridDim.x * NW, claimed by one lane at the top of the tile
+// before -- it is the oldest entry of the in-order vmcnt counter by the time its value is needed, at the unit that requests
+// the next tile's rows, a whole tile later, so it is never waited on.  Which wave computes a tile does not enter the
+// arithmetic: same bits as the static form.
+// queue[0] = head, queue[1] = done: both zero between launches.  A wave adds 1 to `done` when it leaves (also one that got
+// no first tile); the wave that completes the count W has seen every claim of the launch return, and zeroes both words: no
+// memset, no extra launch.  The two words belong to ONE stream's launches (they are not shared between concurrent kernels).
+// TQ = false is the static form (tile += W), kept for within-process A/B runs.
+template <class C, int SPLIT, int P2S, int NW, bool XCM = false, bool TQ = true>
 __global__ __launch_bounds__(NW * 64) void mlp3_split_kernel(const float *__restrict__ X, const float *__restrict__ packed,
-                                                        float *__restrict__ Y, i64 rows) {
+                                                        float *__restrict__ Y, i64 rows, unsigned *queue
+#ifdef INFERA_MLP3_PROBES
+                                                        , unsigned long long *probe  // [gridDim.x * NW][4], or null (tools/mlp_wave_residency.py)
+#endif
+) {
   static_assert(C::L3V && C::MT1 % SPLIT == 0 && C::G1 % SPLIT == 0, "split kernel: VALU head, even split");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -310,6 +326,11 @@ __global__ __launch_bounds__(NW * 64) void mlp3_split_kernel(const float *__rest
     for (int i = threadIdx.x; i < C::N_SMALL / 4; i += NW * 64) sdst[i] = ssrc[i];
   }
   __syncthreads();
+#ifdef INFERA_MLP3_PROBES
+  // (the entry stamp is stored at once: held to the exit it would cost the tile loop two scalar registers)
+  if (probe && lane == 0) probe[(i64(blockIdx.x) * NW + wave) * 4 + 1] = __builtin_amdgcn_s_memrealtime();  // 100 MHz
+  unsigned probe_tiles = 0;
+#endif
   const f32x4 *w1 = reinterpret_cast<const f32x4 *>(lds + C::L_W1) + lane;
   const f32x4 *w2l = reinterpret_cast<const f32x4 *>(lds + C::L_W2) + lane;
   const float *small = lds + C::L_SMALL;
@@ -322,7 +343,6 @@ __global__ __launch_bounds__(NW * 64) void mlp3_split_kernel(const float *__rest
   const i64 ntiles = (rows + 31) >> 5;
   const i64 tstride = i64(gridDim.x) * NW;
   i64 tile = i64(blockIdx.x) * NW + wave;
-  if (tile >= ntiles) return;
 
   auto load_x = [&](f32x4(&x)[C::G0], i64 t) {
     i64 row = (t << 5) + r;
@@ -333,6 +353,15 @@ __global__ __launch_bounds__(NW * 64) void mlp3_split_kernel(const float *__rest
       for (int g = 0; g < C::G0; g++)
 #pragma unroll
         for (int j = 0; j < 4; j++) x[g][j] = p[i64(8 * g + j) * rows];
+    } else if constexpr (TQ) {
+      // the same rows from a wave-uniform tile base plus a 32-bit lane offset (tail rows clamped as above): the lane-wide 64-bit
+      // address of the static form costs the three-output kernel two spilled registers once the claim holds one
+      const i64 lim = rows - 1 - (t << 5);
+      const int rl = lim < 31 ? int(lim) : 31;
+      const unsigned off = unsigned((r < rl ? r : rl) * C::D0 + 4 * h);
+      const f32x4 *p = reinterpret_cast<const f32x4 *>(X + (t << 5) * C::D0 + off);
+#pragma unroll
+      for (int g = 0; g < C::G0; g++) x[g] = p[2 * g];
     } else {
       const f32x4 *p = reinterpret_cast<const f32x4 *>(X + row * C::D0 + 4 * h);
 #pragma unroll
@@ -352,9 +381,18 @@ __global__ __launch_bounds__(NW * 64) void mlp3_split_kernel(const float *__rest
   static_assert(U1H >= P1 && U2H >= P2, "chain too small for the pipeline depths");
 
   f32x4 x[C::G0];
-  load_x(x, tile);
-  for (; tile < ntiles; tile += tstride) {
-    const bool has_next = tile + tstride < ntiles;
+  if (tile < ntiles) load_x(x, tile);
+  while (tile < ntiles) {
+    i64 next = tile + tstride;
+    // the claim for the NEXT tile: one lane, issued before this tile's ring loads, read at u == XPF
+    unsigned claim = 0;
+    if constexpr (TQ) {
+      // (the offset in a vector register: with a wave-uniform address hipcc rewrites the atomic as a wave reduction and waits
+      // for its result on the spot)
+      unsigned lane_off = 0;
+      asm volatile("" : "+v"(lane_off));
+      if (lane == 0) claim = __hip_atomic_fetch_add(queue + lane_off, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     int zero = 0;
     asm volatile("" : "+s"(zero));
     const f32x4 *w2g = w2g_base + zero;
@@ -407,7 +445,10 @@ __global__ __launch_bounds__(NW * 64) void mlp3_split_kernel(const float *__rest
           const int u = g * C::MT2 + mt;
           const f32x4 a = ring2[u % P2];
           if (u + P2 < U2) ring2[u % P2] = frag2(u + P2);
-          if (u == XPF && has_next) load_x(x, tile + tstride);  // x is dead in the last split
+          if (u == XPF) {  // x is dead in the last split
+            if constexpr (TQ) next = tstride + i64(unsigned(__builtin_amdgcn_readfirstlane(int(claim))));
+            if (next < ntiles) load_x(x, next);
+          }
 #pragma unroll
           for (int j = 0; j < 4; j++) acc2[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], hv[j], acc2[mt], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
@@ -435,7 +476,33 @@ __global__ __launch_bounds__(NW * 64) void mlp3_split_kernel(const float *__rest
       const float tot = yacc[m] + __shfl_xor(yacc[m], 32);
       if (h == 0 && row < rows) Y[row * C::D3 + m] = act_c<C::A3>(tot + b3[m]);
     }
+#ifdef INFERA_MLP3_PROBES
+    probe_tiles++;
+#endif
+    tile = next;
   }
+  // ---- leave: count this wave out; the last one of the launch hands the queue back as it found it ----
+  // (lane 0 found anew: keeping `lane` alive across the loop for this costs the row-major kernel its 257th register)
+  const bool first_lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u;
+  if constexpr (TQ) {
+    if (first_lane) {
+      const unsigned nwaves = gridDim.x * NW;
+      if (__hip_atomic_fetch_add(queue + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nwaves - 1) {
+        __hip_atomic_store(queue, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(queue + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+#ifdef INFERA_MLP3_PROBES
+  if (probe && first_lane) {  // one lane per wave, once per launch, plain vector stores
+    const unsigned long long hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_REG_HW_ID: simd 5:4, cu 11:8, sh 12, se 15:13
+    const unsigned long long xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // HW_REG_XCC_ID 3:0
+    unsigned long long *p = probe + (i64(blockIdx.x) * NW + wave) * 4;
+    p[0] = (unsigned long long)blockIdx.x | ((unsigned long long)wave << 20) | (xcc << 24) | ((hw & 0xffffull) << 32);
+    p[2] = __builtin_amdgcn_s_memrealtime();
+    p[3] = probe_tiles;
+  }
+#endif
 }
 
 // ---- latency-shaped variant for SHORT launches (one DataChunk through the host ABI) --------------------------------------

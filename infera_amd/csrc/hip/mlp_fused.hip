@@ -33,6 +33,13 @@
 //   * X is read with one 16-byte load per lane per 8 k-indices directly in B-fragment shape; the
 //     next tile's rows are requested right after this tile's last layer-2 L2 load, so nothing in
 //     this tile ever queues behind HBM latency on the in-order vmcnt counter.
+//   * The shipped kernel for narrow heads is the two-waves-per-SIMD form of this (mlp3_split_kernel, mlp_device.inc).  Its waves
+//     do not run at equal speed, so they do not get equal shares: a wave's first tile is fixed, every later one is claimed from a
+//     TILE QUEUE -- one returning atomicAdd on a head word, issued by one lane at the top of the tile before and read a tile
+//     later, so it is never waited on -- and every wave stays busy until the table is done.  The last wave out of a launch zeroes
+//     the queue's two words (head, done) again: no memset, no extra launch.  The words belong to the launching stream's context
+//     (runtime.hpp, ThreadCtx::mlp_queues).  Which wave computes a tile does not enter the arithmetic: same bits as fixed shares
+//     (tests/test_mlp_tile_queue_gpu.py).
 #include <atomic>
 
 #include "../host/common.hpp"
@@ -50,13 +57,19 @@ namespace {
 
 using namespace mlpdev;
 
-template <class C, int SPLIT, int P2S, int NW = 8, bool XCM = false>
-void launch_split(hipStream_t s, const float *X, const float *packed, float *Y, int64_t rows, int num_cus) {
+#ifdef INFERA_MLP3_PROBES
+// probe build only: the side buffer every wave of mlp3_split_kernel stamps (null: no stamps), set by tools/mlp_wave_residency.py
+std::atomic<unsigned long long *> g_probe_buf{nullptr};
+#endif
+
+// TQ: waves claim their tiles from `queue` (mlp_device.inc); false: the static share, for A/B runs of the probe build
+template <class C, int SPLIT, int P2S, int NW = 8, bool XCM = false, bool TQ = true>
+void launch_split(hipStream_t s, const float *X, const float *packed, float *Y, int64_t rows, int num_cus, unsigned *queue) {
   static std::atomic<uint64_t> attr_done{0};
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (!((attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&mlp3_split_kernel<C, SPLIT, P2S, NW, XCM>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&mlp3_split_kernel<C, SPLIT, P2S, NW, XCM, TQ>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, C::N_LDS * 4);
     attr_done.fetch_or(uint64_t(1) << (dev & 63), std::memory_order_release);
   }
@@ -64,7 +77,12 @@ void launch_split(hipStream_t s, const float *X, const float *packed, float *Y, 
   int64_t blocks = (ntiles + NW - 1) / NW;
   if (blocks > num_cus) blocks = num_cus;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL((mlp3_split_kernel<C, SPLIT, P2S, NW, XCM>), dim3((unsigned)blocks), dim3(NW * 64), C::N_LDS * 4, s, X, packed, Y, rows);
+#ifdef INFERA_MLP3_PROBES
+  hipLaunchKernelGGL((mlp3_split_kernel<C, SPLIT, P2S, NW, XCM, TQ>), dim3((unsigned)blocks), dim3(NW * 64), C::N_LDS * 4, s, X, packed, Y, rows,
+                     queue, g_probe_buf.load(std::memory_order_relaxed));
+#else
+  hipLaunchKernelGGL((mlp3_split_kernel<C, SPLIT, P2S, NW, XCM, TQ>), dim3((unsigned)blocks), dim3(NW * 64), C::N_LDS * 4, s, X, packed, Y, rows, queue);
+#endif
 }
 
 // ---- host side ----------------------------------------------------------------------------------
@@ -230,20 +248,24 @@ bool tile_kernel_enabled() { return true; }
 }  // namespace
 
 bool mlp3(hipStream_t s, const Mlp3Shape &sh, const float *X, const float *packed, float *Y, int64_t rows, int num_cus,
-          std::string *why, bool x_colmajor) {
+          unsigned *queue, std::string *why, bool x_colmajor) {
   if (rows <= 0) return true;
+  if (!queue && rows > kTileKernelMaxRows) {
+    if (why) *why = "internal: no tile queue for this stream";
+    return false;
+  }
   if (x_colmajor) {  // the host path's column-major chunks (ahead-of-time configurations only)
 #define X_(C)                                                                        \
   if (matches<C>(sh)) {                                                              \
     if constexpr (C::L3V) {                                                          \
       if (rows <= kTileKernelMaxRows && tile_kernel_enabled()) launch_tile<C, true>(s, X, packed, Y, rows); \
-      else launch_split<C, 4, 8, 8, true>(s, X, packed, Y, rows, num_cus);           \
+      else launch_split<C, 4, 8, 8, true>(s, X, packed, Y, rows, num_cus, queue);    \
     } else launch_cfg<C, true>(s, X, packed, Y, rows, num_cus);                      \
     return true;                                                                     \
   }
     INFERA_MLP3_CONFIGS(X_)
 #undef X_
-    return mlp3_jit_launch(s, sh, X, packed, Y, rows, num_cus, why, true);
+    return mlp3_jit_launch(s, sh, X, packed, Y, rows, num_cus, queue, why, true);
   }
 #ifdef INFERA_MLP3_PROBES
   if (matches<CfgC2>(sh)) {
@@ -254,14 +276,17 @@ bool mlp3(hipStream_t s, const Mlp3Shape &sh, const float *X, const float *packe
       case 3: launch_cfg<CfgC2_v3>(s, X, packed, Y, rows, num_cus); return true;
       case 4: launch_cfg<CfgC2_v4>(s, X, packed, Y, rows, num_cus); return true;
       case 5: launch_cfg<CfgC2_v5>(s, X, packed, Y, rows, num_cus); return true;
-      case 6: launch_split<CfgC2, 2, 8>(s, X, packed, Y, rows, num_cus); return true;
-      case 7: launch_split<CfgC2, 2, 4>(s, X, packed, Y, rows, num_cus); return true;
-      case 8: launch_split<CfgC2, 4, 8>(s, X, packed, Y, rows, num_cus); return true;
-      case 9: launch_split<CfgC2, 8, 8>(s, X, packed, Y, rows, num_cus); return true;
-      case 10: launch_split<CfgC2, 8, 4, 12>(s, X, packed, Y, rows, num_cus); return true;
-      case 11: launch_split<CfgC2, 4, 4, 12>(s, X, packed, Y, rows, num_cus); return true;
-      case 12: launch_split<CfgC2, 4, 4>(s, X, packed, Y, rows, num_cus); return true;
+      case 6: launch_split<CfgC2, 2, 8, 8, false, false>(s, X, packed, Y, rows, num_cus, queue); return true;
+      case 7: launch_split<CfgC2, 2, 4, 8, false, false>(s, X, packed, Y, rows, num_cus, queue); return true;
+      case 8: launch_split<CfgC2, 4, 8, 8, false, false>(s, X, packed, Y, rows, num_cus, queue); return true;
+      case 9: launch_split<CfgC2, 8, 8, 8, false, false>(s, X, packed, Y, rows, num_cus, queue); return true;
+      case 10: launch_split<CfgC2, 8, 4, 12, false, false>(s, X, packed, Y, rows, num_cus, queue); return true;
+      case 11: launch_split<CfgC2, 4, 4, 12, false, false>(s, X, packed, Y, rows, num_cus, queue); return true;
+      case 12: launch_split<CfgC2, 4, 4, 8, false, false>(s, X, packed, Y, rows, num_cus, queue); return true;
       case 13: launch_cfg<CfgC2>(s, X, packed, Y, rows, num_cus); return true;  // the one-wave-per-SIMD kernel
+      // 6-12 take their tiles in the static share (variant 8 = the kernel shipped until the tile queue); the queue forms:
+      case 14: launch_split<CfgC2, 4, 8>(s, X, packed, Y, rows, num_cus, queue); return true;  // = variant 0
+      case 15: launch_split<CfgC2, 4, 4>(s, X, packed, Y, rows, num_cus, queue); return true;
       default: break;
     }
   }
@@ -272,13 +297,13 @@ bool mlp3(hipStream_t s, const Mlp3Shape &sh, const float *X, const float *packe
   if (matches<C>(sh)) {                                                        \
     if constexpr (C::L3V) {                                                    \
       if (rows <= kTileKernelMaxRows && tile_kernel_enabled()) launch_tile<C, false>(s, X, packed, Y, rows); \
-      else launch_split<C, 4, 8, 8>(s, X, packed, Y, rows, num_cus);           \
+      else launch_split<C, 4, 8, 8>(s, X, packed, Y, rows, num_cus, queue);    \
     } else launch_cfg<C>(s, X, packed, Y, rows, num_cus);                      \
     return true;                                                               \
   }
   INFERA_MLP3_CONFIGS(X_)
 #undef X_
-  return mlp3_jit_launch(s, sh, X, packed, Y, rows, num_cus, why);
+  return mlp3_jit_launch(s, sh, X, packed, Y, rows, num_cus, queue, why);
 }
 
 std::string mlp3_kernel_name(const Mlp3Shape &sh) {
@@ -289,3 +314,10 @@ std::string mlp3_kernel_name(const Mlp3Shape &sh) {
 }
 
 }  // namespace infera_hip::kern
+
+#ifdef INFERA_MLP3_PROBES
+// probe build only: `buf` = 32 bytes per wave of the launch ([workgroup, wave, XCD, hardware id], entry stamp, exit stamp, tiles), or null
+extern "C" void infera_hip_mlp3_probe_buffer(void *buf) {
+  infera_hip::kern::g_probe_buf.store(static_cast<unsigned long long *>(buf), std::memory_order_relaxed);
+}
+#endif

@@ -195,6 +195,7 @@ struct Compiled {
   std::string why, expr, lowered, cfg;
   std::vector<char> code;
   int threads = 256, lds_bytes = 0;
+  bool queue = false;  // the persistent kernel is mlp3_split_kernel: it takes the tile queue as its fifth argument
   std::map<int, hipFunction_t> fn_by_device;
   Variant tile, tile_xcm;
   Variant tile16, tile16_xcm;  // mlp3_tile16_kernel (chunks up to kTile16MaxRows rows: 16-row tiles on the 16x16x4 instruction)
@@ -265,6 +266,7 @@ Compiled &compile_locked(const Mlp3Shape &s, std::unique_lock<std::mutex> &held)
   if (c.ok || !c.why.empty()) return c;
   const Mlp3Layout L = mlp3_layout(s.d0, s.d1, s.d2, s.d3);
   if (!plan_kernel(s, L, c.expr, c.cfg, c.threads, c.why)) return c;
+  c.queue = c.expr.find("mlp3_split_kernel<") != std::string::npos;
   c.lds_bytes = L.N_LDS * 4;
   c.ok = jit_compile(kMlpDeviceSrc, "infera_mlp_jit.hip", c.expr, c.code, c.lowered, c.why);
   // the tile kernel's preconditions (mlp_device.inc: VALU head, at most four layer-2 tiles, at most six layer-1 tiles per wave, its
@@ -335,10 +337,10 @@ int64_t mlp3_jit_colmajor_max_rows(const Mlp3Shape &sh) {
 }
 
 bool mlp3_jit_launch(hipStream_t s, const Mlp3Shape &sh, const float *X, const float *packed, float *Y, int64_t rows,
-                     int num_cus, std::string *why, bool x_colmajor) {
+                     int num_cus, unsigned *queue, std::string *why, bool x_colmajor) {
   hipFunction_t fn = nullptr;
   int threads = 256, lds = 0;
-  bool tile = false, tile16 = false;
+  bool tile = false, tile16 = false, with_queue = false;
   {
     std::unique_lock<std::mutex> lk;
     Compiled &c = compile_locked(sh, lk);
@@ -363,6 +365,7 @@ bool mlp3_jit_launch(hipStream_t s, const Mlp3Shape &sh, const float *X, const f
       fn = function_on_device(c.code, c.lowered, c.fn_by_device, c.lds_bytes, why);
       threads = c.threads;
       lds = c.lds_bytes;
+      with_queue = c.queue;
     }
     if (!fn) return false;
   }
@@ -374,7 +377,11 @@ bool mlp3_jit_launch(hipStream_t s, const Mlp3Shape &sh, const float *X, const f
     if (blocks > num_cus) blocks = num_cus;
     if (blocks < 1) blocks = 1;
   }
-  void *args[] = {(void *)&X, (void *)&packed, (void *)&Y, (void *)&rows};
+  if (with_queue && !queue) {
+    if (why) *why = "internal: no tile queue for this stream";
+    return false;
+  }
+  void *args[] = {(void *)&X, (void *)&packed, (void *)&Y, (void *)&rows, (void *)&queue};  // (the fifth: mlp3_split_kernel only)
   hipError_t e = hipModuleLaunchKernel(fn, unsigned(blocks), 1, 1, unsigned(threads), 1, 1, unsigned(lds), s, args, nullptr);
   if (e != hipSuccess) {
     if (why) *why = std::string("hipModuleLaunchKernel: ") + hipGetErrorString(e);

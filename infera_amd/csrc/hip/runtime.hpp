@@ -48,11 +48,22 @@ struct HipFault : InferaError {
 // break them hold it exclusively.  In the default direct-enqueue mode nobody captures and the guards
 // are not taken.
 extern std::shared_mutex g_capture_mu;
+// Re-entrant per thread: a guarded operation may need another one (a model's upload creates the thread's context, which allocates).
 struct UnsafeOpGuard {
   std::unique_lock<std::shared_mutex> lk;
-  UnsafeOpGuard() {
-    if (Config::get().use_hipgraph) lk = std::unique_lock<std::shared_mutex>(g_capture_mu);
+  const bool on = Config::get().use_hipgraph;
+  static int &depth() {
+    static thread_local int d = 0;
+    return d;
   }
+  UnsafeOpGuard() {
+    if (on && depth()++ == 0) lk = std::unique_lock<std::shared_mutex>(g_capture_mu);
+  }
+  ~UnsafeOpGuard() {
+    if (on) depth()--;
+  }
+  UnsafeOpGuard(const UnsafeOpGuard &) = delete;
+  UnsafeOpGuard &operator=(const UnsafeOpGuard &) = delete;
 };
 
 constexpr size_t kHostPassBytes = 64ull << 20;     // pinned staging per direction per thread
@@ -204,6 +215,18 @@ struct ThreadCtx {
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), bytes));
     cap = bytes;
   }
+  // The tile queues of the fused MLP's split kernel (kernels.hpp, mlp3): per stream of this context a head and a done word on a
+  // 128-byte line of their own, allocated and zeroed when the context is created (so never inside a stream capture); every launch
+  // leaves them zero.  Launches of one stream run one after the other, and no other context shares the words: two host threads
+  // scanning the same model at once claim from different queues.
+  unsigned *mlp_queues = nullptr;
+  static constexpr size_t kMlpQueueStride = 32;  // unsigneds
+  unsigned *mlp_queue_of(hipStream_t s) const {
+    size_t lane = 0;
+    for (int l = 1; l < kMaxLanes; l++)
+      if (lane_stream[l - 1] && s == lane_stream[l - 1]) lane = size_t(l);
+    return mlp_queues ? mlp_queues + lane * kMlpQueueStride : nullptr;
+  }
   // the failure word of a call through a plan with a zeros = 0 OneHotEncoder (exec_plan clears, prep.hip sets, exec_plan reads it)
   int *prep_err = nullptr;
   size_t prep_err_cap = 0;
@@ -218,6 +241,8 @@ struct ThreadCtx {
 int slot_of_ordinal(int ordinal);
 // the calling thread's own context on device slot `slot` (device-resident entry points, weight uploads); makes the slot's device current
 ThreadCtx &ctx_for_slot(int slot);
+// a new context on device slot `slot` (current): its stream and its zeroed tile queues
+ThreadCtx *new_context(int slot);
 
 // Host-ABI calls do not own a context per caller thread: a DuckDB scan on a 256-thread host would pin 256 sets of
 // staging buffers and per-model scratch (ResNet-18: ~1 GB each) and create 256 streams, for no throughput -- the path

@@ -43,7 +43,9 @@ void upload_mlp3(const Upload &up, size_t i) {
 void launch_mlp3(const PassRunner &r, size_t i, bool cm) {
   const Step &x = r.st[i];
   std::string why;
-  if (!kern::mlp3(r.stream, r.m.mlp3_shape, r.buf(x.in0), r.dm.mlp3_packed, r.buf(r.st[i + 2].out), r.nr * x.rep, r.dm.num_cus, &why, cm))
+  // (the tile queue of the stream this pass runs on: the context's own, or one of its lanes')
+  if (!kern::mlp3(r.stream, r.m.mlp3_shape, r.buf(x.in0), r.dm.mlp3_packed, r.buf(r.st[i + 2].out), r.nr * x.rep, r.dm.num_cus,
+                  r.ctx.mlp_queue_of(r.stream), &why, cm))
     throw InferaError::onnx("fused MLP kernel launch failed: " + why);
 }
 
