@@ -28,7 +28,7 @@ __device__ __forceinline__ float apply_act_c(float v, float a, float b) {
   if constexpr (KIND == 10) return fabsf(v);
   if constexpr (KIND == 11) return v >= 0.f ? v : a * (expf(v) - 1.0f);             // Elu
   if constexpr (KIND == 12) return v > 0.f ? b * v : b * (a * expf(v) - a);          // Selu (b = gamma)
-  if constexpr (KIND == 13) return logf(expf(v) + 1.0f);                             // Softplus
+  if constexpr (KIND == 13) return fmaxf(v, 0.f) + log1pf(expf(-fabsf(v)));          // Softplus (expf(v) + 1 overflows from v = 88.73)
   if constexpr (KIND == 14) return fmaxf(0.f, fminf(1.f, a * v + b));                // HardSigmoid
   if constexpr (KIND == 15) return v * fmaxf(0.f, fminf(1.f, v * (1.0f / 6.0f) + 0.5f));  // HardSwish
   if constexpr (KIND == 16) return erff(v);

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(kBlock) void softmax_small_kernel(const float *__re
         d = mode == 2 ? fmaxf(d, a) : mode == 3 ? d + a : fmaf(u, u, d);
       }
       if (mode == 4) d = sqrtf(d);
-      d = fmaxf(d, 1e-30f);
+      d = d < 1e-30f ? 1e-30f : d;  // (the oracle's comparison: a NaN sum stays NaN -- fmaxf would turn it into the floor)
       for (int64_t j = 0; j < len; j++) dst[j * inner] = src[j * inner] / d;
       continue;
     }
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(kBlock) void softmax_wave_kernel(const float *__res
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) d = mode == 2 ? fmaxf(d, __shfl_xor(d, o)) : d + __shfl_xor(d, o);
       if (mode == 4) d = sqrtf(d);
-      d = fmaxf(d, 1e-30f);
+      d = d < 1e-30f ? 1e-30f : d;  // (the oracle's comparison: a NaN sum stays NaN -- fmaxf would turn it into the floor)
       for (int64_t j = lane; j < len; j += 64) dst[j] = src[j] / d;
       continue;
     }
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(kBlock) void softmax_rows_kernel(const float *__res
     }
     if (mode >= 2) {
       if (mode == 4) red = sqrtf(red);
-      red = fmaxf(red, 1e-30f);
+      red = red < 1e-30f ? 1e-30f : red;  // (a NaN sum stays NaN)
 #pragma unroll
       for (int j = 0; j < EPL; j++) e[j] = e[j] / red;
     } else {

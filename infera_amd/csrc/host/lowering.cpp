@@ -598,7 +598,10 @@ struct Lowerer {
     // [N,C,H,W] tensor (a bias Add / scale Mul an exporter left behind a convolution, in-graph pixel normalisation) is
     // one multiply-add per element however many nodes spell it: consecutive ones compose into a single AffineChannel
     // pass, fold into the convolution that produced the tensor, and the Dense fold above still finds them.
-    if (act_shape.size() >= 2 && (op == '+' || op == '-' || op == '*' || (op == '/' && !const_left))) {
+    // (a divisor whose reciprocal is no normal f32 -- zero, a subnormal, anything above 2^126 -- stays a division: x * (1 / c) would be
+    // x * inf, or x times a reciprocal that has lost bits)
+    const bool reciprocal_ok = op != '/' || const_left || std::all_of(cf32(n, cst).begin(), cf32(n, cst).end(), [](float c) { return std::isnormal(c) && std::isnormal(1.0f / c); });
+    if (act_shape.size() >= 2 && (op == '+' || op == '-' || op == '*' || (op == '/' && !const_left && reciprocal_ok))) {
       const std::vector<float> cv = broadcast_const(n, cst, act_shape);
       const size_t C = size_t(act_shape[1]), S = size_t(prod(act_shape, 2));
       bool per_channel = cv.size() == C * S;

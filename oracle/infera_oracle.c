@@ -852,7 +852,7 @@ static int op_unary(Exec *x, const Node *nd) {
     ORC_UN("Sqrt", sqrtf(v))
     ORC_UN("Neg", -v)
     ORC_UN("Abs", fabsf(v))
-    ORC_UN("Softplus", logf(expf(v) + 1.0f))
+    ORC_UN("Softplus", fmaxf(v, 0.0f) + log1pf(expf(-fabsf(v)))) /* (logf(expf(v) + 1) is +inf from v = 88.73) */
     ORC_UN("HardSwish", v * fmaxf(0.0f, fminf(1.0f, v * (1.0f / 6.0f) + 0.5f)))
     ORC_UN("Erf", erff(v))
     ORC_UN("Reciprocal", 1.0f / v)
