@@ -1019,11 +1019,12 @@ def from_torch_encoder(encoder, T: int, head=None, causal: bool = False) -> dict
 
 
 def attention_nodes(nodes: list, inits: list, p: str, q: str, k: str, v: str, x_for_shape: str, T: int, E: int, h: int, scale: str = "scores_div",
-                    k_transpose: str = "direct", mask=None, shape: str = "const", scale_value: float | None = None, softmax_axis: int = -1) -> str:
+                    k_transpose: str = "direct", mask=None, shape: str = "const", scale_value: float | None = None, softmax_axis: int = -1,
+                    mask_left: bool = False) -> str:
     """Appends the batch-first self-attention sub-graph over q, k, v [N, T, E] (names) and returns the name of its [N, T, E] result.
     scale: "scores_div" (Div by sqrt(dh)), "scores_mul", "q" (Mul of Q) or "sqrt_both" (Q and K^T by sqrt(scale) each, what
     scaled_dot_product_attention exports); k_transpose: "direct" (0,2,3,1) or "two_step" ((0,2,1,3) then (0,1,3,2)); mask: None or an f32
-    array added to the scores; shape: "const" targets or the exporter's Shape -> Gather -> Unsqueeze -> Concat sub-graph."""
+    array added to the scores (mask_left: as the Add's first operand); shape: "const" targets or the exporter's Shape -> Gather -> Unsqueeze -> Concat sub-graph."""
     dh = E // h
     sv = (1.0 / math.sqrt(dh)) if scale_value is None else scale_value
     i64 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.int64)))  # noqa: E731
@@ -1069,7 +1070,7 @@ def attention_nodes(nodes: list, inits: list, p: str, q: str, k: str, v: str, x_
         cur = p + "s1"
     if mask is not None:
         f32(p + "mask", mask)
-        nodes.append(node("Add", [cur, p + "mask"], [p + "s2"], name=p + "mask_add"))
+        nodes.append(node("Add", [p + "mask", cur] if mask_left else [cur, p + "mask"], [p + "s2"], name=p + "mask_add"))
         cur = p + "s2"
     nodes += [node("Softmax", [cur], [p + "p"], [attr_i("axis", softmax_axis)], name=p + "softmax"),
               node("MatMul", [p + "p", heads["v"]], [p + "o4"], name=p + "pv"),
