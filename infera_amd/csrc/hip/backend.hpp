@@ -71,6 +71,7 @@ struct ResizeTables { const int *row_idx = nullptr, *col_idx = nullptr; const fl
 struct SpatialNormTables { const float *gamma = nullptr, *beta = nullptr; };  // SpatialNorm (per channel: the same in either layout)
 struct TokensTables { const float *prefix = nullptr, *pos = nullptr; };  // Tokens (row-major [P, E] and [T, E]: the window's own order)
 struct ChannelNormTables { const float *gamma = nullptr, *beta = nullptr; };  // ChannelNorm (per channel: the same in either layout; beta may be absent)
+struct EmbedTables { const int32_t *desc = nullptr; const uint16_t *map = nullptr; const float *tab = nullptr; };  // Embed (host/embed.hpp: piece descriptors, column -> piece map or null, the tables)
 struct RnnTables { const float *wr = nullptr, *bias = nullptr, *bias2 = nullptr, *h0 = nullptr, *c0 = nullptr; };
 struct DeviceStep {  // (a step fills the one struct of its family)
   PlainTables plain;
@@ -88,6 +89,7 @@ struct DeviceStep {  // (a step fills the one struct of its family)
   SpatialNormTables spatialnorm;
   ChannelNormTables channelnorm;
   TokensTables tokens;
+  EmbedTables embed;
 };
 
 // How the executor runs a step.

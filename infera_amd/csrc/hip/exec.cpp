@@ -77,7 +77,8 @@ void exec_plan(const LoadedModel &m, const DeviceModel &dm, ThreadCtx &ctx, cons
     return;
   }
   const int64_t rows_pass = prepare_scratch(m, ctx, rows);
-  // a plan with a zeros = 0 OneHotEncoder: the call's failure word, cleared on the call's stream and read back with the result
+  // a plan with a zeros = 0 OneHotEncoder or an embedding lookup: the call's failure word, cleared on the call's stream and read back with
+  // the result
   const bool strict = !p.prep_strict_nodes.empty();
   if (strict) {
     ctx.ensure_prep_err();
@@ -123,9 +124,10 @@ void exec_plan(const LoadedModel &m, const DeviceModel &dm, ThreadCtx &ctx, cons
     int word = 0;
     HIP_TRY(hipMemcpyAsync(&word, ctx.prep_err, sizeof(int), hipMemcpyDeviceToHost, ctx.stream));
     HIP_TRY(hipStreamSynchronize(ctx.stream));
-    if (word > 0)
-      throw InferaError::onnx(p.prep_strict_nodes[size_t(std::min<int>(word, int(p.prep_strict_nodes.size()))) - 1] +
-                              ": a value is not in cats_int64s (zeros = 0)");
+    if (word > 0) {
+      const Plan::StrictNode &sn = p.prep_strict_nodes[size_t(std::min<int>(word, int(p.prep_strict_nodes.size()))) - 1];
+      throw InferaError::onnx(sn.node + sn.message);
+    }
   }
 }
 

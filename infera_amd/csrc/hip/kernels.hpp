@@ -360,6 +360,14 @@ bool spatialnorm_apply(hipStream_t s, const float *X, const float *stats, const 
 // X: NCHW order or (cq) channel-quad planes; prefix [P, C] (P = 0: none), pos [P + S, C] or null: added in the store.  false: beyond the caps
 bool tokens(hipStream_t s, const float *X, const float *prefix, const float *pos, float *Y, int64_t rows, int C, int S, int P, bool cq);
 
+// ---- Embed: table lookups by runtime indices, column copies and their Concat as one pass (embed.hip; host/embed.hpp) --------------
+// x [rows, W] row-major; desc: kEmbedDescInts per piece (P pieces); map: the piece of every output column (map_entries 16-bit entries, a
+// multiple of 8) or null: a search; tab: the tables; y [rows, F]; R rows per work group; staged: the source tile goes through LDS; err: the
+// call's failure word, set to a piece's node id on an index outside its table (that load goes to row 0); nt: non-temporal stores for the full
+// quads.  false: beyond the caps
+bool embed(hipStream_t s, const float *x, int W, const int32_t *desc, int P, const uint16_t *map, int map_entries, const float *tab, float *y, int64_t F,
+           int64_t rows, int R, bool staged, int *err, bool nt = false);
+
 // ---- LayerNorm over the channel axis at each pixel (channelnorm.hip; host/channelnorm.hpp) --------------
 // X, Y: [rows, C, S] in NCHW order or (cq) channel-quad planes, the same layout; gamma [C], beta [C] or null.  regs: the register form
 // (C <= kChannelNormRegsMaxC), else the re-read form.  y = act(d / sqrtf(var + eps) * gamma + beta).  false: beyond the kernel's caps

@@ -7,6 +7,7 @@
 #include "../host/channelnorm.hpp"
 #include "../host/deconv.hpp"
 #include "../host/spatialnorm.hpp"
+#include "../host/embed.hpp"
 #include "runtime.hpp"
 
 namespace infera_hip {
@@ -519,7 +520,10 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
                               (sk == StepKind::RowReduce && st[size_t(e.idx)].out_mode == kReduceLogSumExp) ||  // (two passes: the maximum, then the sum)
                               sk == StepKind::Attention ||  // (every query tile walks all keys and values)
                               sk == StepKind::ConvTranspose2d || sk == StepKind::Resize2d ||  // (every input pixel is fetched once per tap / per copy)
-                              sk == StepKind::Recurrent;  // (one dependent fetch per time step: from HBM, not over PCIe)
+                              sk == StepKind::Recurrent ||  // (one dependent fetch per time step: from HBM, not over PCIe)
+                              // (staged, an Embed step loads each row tile of the input once: a streaming reader; a source row too wide
+                              // for the tile is read where it lies, its index once per quad of a lookup piece)
+                              (sk == StepKind::Embed && !st[size_t(e.idx)].embed->staged);
         m.in_single_reader = !windowed;
         break;
       }

@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "../host/deconv.hpp"
+#include "../host/embed.hpp"
 #include "../host/nearest.hpp"
 #include "../host/channelnorm.hpp"
 #include "../host/onnx_model.hpp"
@@ -425,6 +426,23 @@ void launch_tokens(const PassRunner &r, const Step &x, const TokensTables &t) {
     throw InferaError::onnx("Tokens kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
 }
 
+// ---- Embed (host/embed.hpp EmbedPack, embed.hip): the piece descriptors, the column -> piece map (short rows) and the tables ----
+void upload_embed(const Step &s, EmbedTables &t, const Upload &up) {
+  t.desc = up(s.embed->desc);
+  t.map = s.embed->map.empty() ? nullptr : up(s.embed->map);
+  t.tab = up(s.embed->tab);
+}
+void launch_embed(const PassRunner &r, const Step &x, const EmbedTables &t) {
+  const EmbedPack &q = *x.embed;
+  if (r.in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: an Embed step reads its input row-major");
+  // non-temporal stores: 4-8 % off an Embed -> Relu model where a pass writes more than the caches hold, no difference where it does not
+  // (profiles/r19_embed.txt); INFERA_EMBED_NT=0: plain stores, the same bits (A/B: tools/embed_time.py)
+  static const bool nt = !(getenv("INFERA_EMBED_NT") && atoi(getenv("INFERA_EMBED_NT")) == 0);
+  if (!kern::embed(r.stream, r.buf(x.in0), int(q.W), t.desc, int(q.pieces.size()), t.map, int(q.map.size()), t.tab, r.buf(x.out), q.F, r.nr, q.R, q.staged,
+                   r.ctx.prep_err, nt))
+    throw InferaError::onnx("Embed kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+
 // ---- the plain family: the step's constants as the lowering left them (Conv2d: packed for the generic kernel); its launches are the head
 // of PassRunner::launch_plain, right below ----
 void upload_plain(const Step &s, PlainTables &t, const Upload &up) {
@@ -482,6 +500,7 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::SpatialStats: launch_spatialstats(*this, x); break;
     case StepKind::Tokens: launch_tokens(*this, x, d.tokens); break;
     case StepKind::ChannelNorm: launch_channelnorm(*this, x, d.channelnorm); break;
+    case StepKind::Embed: launch_embed(*this, x, d.embed); break;
     // the steps without tables
     case StepKind::Unary: kern::unary(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], act_of(x)); break;
     case StepKind::BinaryAct:
@@ -548,6 +567,7 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::SpatialNorm: return upload_spatialnorm(s, d.spatialnorm, up);
     case StepKind::Tokens: return upload_tokens(s, d.tokens, up);
     case StepKind::ChannelNorm: return upload_channelnorm(s, d.channelnorm, up);
+    case StepKind::Embed: return upload_embed(s, d.embed, up);
     default: return;  // (no tables)
   }
 }

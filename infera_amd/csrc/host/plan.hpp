@@ -21,6 +21,7 @@ struct PrepPack;  // host/prep.hpp
 struct RnnPack;   // host/recurrent.hpp
 struct NearestPack;  // host/nearest.hpp
 struct DeconvPack;   // host/deconv.hpp
+struct EmbedPack;    // host/embed.hpp
 
 // Kinds 1..5 may be fused into the epilogue of a Dense / Conv2d step (the MFMA kernels resolve them at
 // compile time); the rest run in the elementwise kernels (fused into Binary*/AffineChannel or as a Unary step).
@@ -74,6 +75,7 @@ enum class StepKind : int {
   SpatialStats = 37,  // out [rows, groups, 3] = (mean, resid, 1 / sqrt(var + ln_eps)) of each group of in0: the first half of the general SpatialNorm plan (the scheduler inserts it, schedule.cpp)
   Tokens = 38,        // out [rows, rep = P + S, K = C] = the window of in0 [rows, C, S] (NCHW or channel quads): out[r, P + s, c] = in0[r, c, s] (+ cst[P + s, c]); rows p < P = prefix[p, c] (+ cst[p, c]) (host/tokens.hpp, tokens.hip)
   ChannelNorm = 39,   // LayerNorm over the C channels at each of the S pixels of in0 [rows, C, S] (NCHW or channel quads, never changed): y = act((x - mean) / sqrt(var + ln_eps) * scale[c] + shift[c]), shift may be empty; out_mode (set by the scheduler): 0 the register form, 1 the re-read form (host/channelnorm.hpp, channelnorm.hip)
+  Embed = 40,         // out [rows, F] = pieces in output order: rows of constant tables chosen by index columns of in0 [rows, W] (truncated toward zero, + an offset) and runs of in0's columns as they are; a window [rows, k, d] when the pack says so (EmbedPack, host/embed.hpp, embed.hip)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
@@ -149,6 +151,7 @@ struct Step {
   std::shared_ptr<const PrepPack> prep;
   std::shared_ptr<const RnnPack> rnn;
   std::shared_ptr<const NearestPack> nearest;
+  std::shared_ptr<const EmbedPack> embed;
   std::shared_ptr<const DeconvPack> deconv;  // ConvTranspose2d: phase tap lists; Resize2d: source tables
   int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut, RowReduce: ReduceOp, TopK: 0 values / 1 indices, Nearest*: NearestOut
   // Attention: Q = in0, K = in1, V = in2 (the same buffer three times when the projections are merged), each [rows, T, ld] with the head
@@ -183,9 +186,13 @@ struct Plan {
   std::string output_declared_type;  // "" for f32; "int64" / "int32" / "float16" when the graph declares such an output that is served as f32 VALUES
   std::string input_declared_type;   // "float16" when the graph declares a half input: the f32 values of a call are rounded to half first
   bool output_zipmap = false;        // the served output is a ZipMap's: its input [rows, C] is served, one column per class label
-  // "node 'name' (OneHotEncoder)" of each zeros = 0 one-hot encoder (1-based ids in the Prep descriptors); a call whose failure word is set
-  // fails naming it
-  std::vector<std::string> prep_strict_nodes;
+  // the checks a call can fail on the device, by 1-based id (the ids in the Prep and Embed descriptors): a call whose failure word is set
+  // fails with `node` + `message` of that entry.  node: "node 'name' (OneHotEncoder)" of a zeros = 0 one-hot encoder, "node 'name' (Gather)"
+  // of an embedding lookup
+  struct StrictNode {
+    std::string node, message;
+  };
+  std::vector<StrictNode> prep_strict_nodes;
 
   int64_t in_per_row() const { return buf_per_row[0]; }
   int64_t out_per_row() const { return buf_per_row[out_buf]; }

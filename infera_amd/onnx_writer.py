@@ -3700,3 +3700,205 @@ def convnext_reference(spec: dict, x) -> np.ndarray:
             h = _block_reference(h, L, eps)
     h = channelnorm_reference(h.mean(axis=(2, 3), keepdims=True), spec["head_norm"][0], spec["head_norm"][1], eps)
     return h.reshape(len(h), -1) @ f64(spec["head_W"]) + f64(spec["head_b"])
+
+
+# ------------------------------------------------------------------------------------------
+# Embedding lookups (Gather of a constant table by runtime indices) in front of MLPs and Transformer encoders
+# ------------------------------------------------------------------------------------------
+
+EMBED_SPELLINGS = ("a", "b", "c", "d")
+
+
+def embedding_spec(cards: Sequence[int] = (7, 11, 5), dims: Sequence[int] | int = (3, 4, 2), numeric: int = 2, hidden: Sequence[int] = (16, 8),
+                   outputs: int = 1, seed: int = 71, weight_scale: float = 1.0, table_rank1: bool = False) -> dict:
+    """Seeded categorical front end: column j has cards[j] categories and a table [cards[j], dims[j]] (N(0, 1), like nn.Embedding); `numeric`
+    f32 columns beside them; an MLP sum(dims) + numeric -> hidden... -> outputs (U(+-1/sqrt(fan_in)) like nn.Linear, scaled by weight_scale;
+    hidden = (): no MLP).  With equal dims the spec also holds the one shared table of spelling (b): the tables one below the other and the
+    per-column row offsets.  table_rank1: dims are all 1 and the tables have no trailing axis ([V])."""
+    rng = np.random.default_rng(seed)
+    k = len(cards)
+    dims = [int(dims)] * k if isinstance(dims, (int, np.integer)) else [int(d) for d in dims]
+    assert len(dims) == k and (not table_rank1 or all(d == 1 for d in dims))
+    tables = [rng.standard_normal((int(v), d)).astype(np.float32) for v, d in zip(cards, dims)]
+    spec = {"cards": [int(v) for v in cards], "dims": dims, "numeric": int(numeric), "tables": tables, "rank1": bool(table_rank1), "mlp": [], "act": "Relu"}
+    if len(set(dims)) == 1:
+        spec["shared"] = np.concatenate(tables, axis=0)
+        spec["offsets"] = np.concatenate([[0], np.cumsum(spec["cards"])[:-1]]).astype(np.int64)
+    widths = [sum(dims) + int(numeric)] + [int(h) for h in hidden] + ([int(outputs)] if hidden else [])
+    for i, o in zip(widths[:-1], widths[1:]):
+        b = weight_scale / np.sqrt(i)
+        spec["mlp"].append((rng.uniform(-b, b, (i, o)).astype(np.float32), rng.uniform(-b, b, (o,)).astype(np.float32)))
+    return spec
+
+
+def from_torch_tabular(module) -> dict:
+    """The embedding_spec() dict of a torch.nn model built from nn.Embedding tables (one per categorical column, in module order) and
+    nn.Linear layers (in module order, ReLU between them): the first Linear reads cat(embeddings..., numeric columns)."""
+    import torch
+
+    embs = [mod for mod in module.modules() if isinstance(mod, torch.nn.Embedding)]
+    lins = [mod for mod in module.modules() if isinstance(mod, torch.nn.Linear)]
+    assert embs and lins
+    tables = [e.weight.detach().cpu().numpy().astype(np.float32).copy() for e in embs]
+    dims = [int(t.shape[1]) for t in tables]
+    spec = {"cards": [int(t.shape[0]) for t in tables], "dims": dims, "numeric": int(lins[0].in_features) - sum(dims), "tables": tables, "rank1": False,
+            "mlp": [(lin.weight.detach().cpu().numpy().astype(np.float32).T.copy(), lin.bias.detach().cpu().numpy().astype(np.float32).copy()) for lin in lins],
+            "act": "Relu"}
+    assert spec["numeric"] >= 0
+    if len(set(dims)) == 1:
+        spec["shared"] = np.concatenate(tables, axis=0)
+        spec["offsets"] = np.concatenate([[0], np.cumsum(spec["cards"])[:-1]]).astype(np.int64)
+    return spec
+
+
+def embedding_nodes(spec: dict, spelling: str = "a", pick: str = "gather", flatten: str = "reshape", int_type: int = INT64, concat: bool = True,
+                    offsets_rank: int = 1, batch: int | str = "N"):
+    """The front end of an embedding_spec() as (nodes, initializers, name of its result, dims of the result, graph inputs).
+    (a): inputs x_cat [N, k] (int_type) and x_num [N, m]; column j picked by Gather(axis = 1, scalar) (pick "gather") or Slice + Squeeze
+         ("slice"), looked up in table j (node 'emb<j>'), the results and x_num joined by Concat -> 'features' [N, sum(d) + m].
+    (b): one shared table, x_cat + offsets ([k], or [1, k] with offsets_rank 2) -> Gather (node 'emb') -> [N, k, d]; flatten: "reshape" /
+         "flatten" -> [N, k * d] (then Concat with x_num, if any), "window": the [N, k, d] value itself.
+    (c): Gather(table 0, ids [N, T = len(cards)]) -> the window [N, T, d] (node 'emb').
+    (d): (a) on ONE f32 input X [N, k + m]: column j -> Cast(int_type) -> lookup; the numeric columns are Slice(X, k : k + m).
+    concat = False (one lookup, no numeric columns): no Concat node."""
+    assert spelling in EMBED_SPELLINGS
+    k, m, dims = len(spec["cards"]), spec["numeric"], spec["dims"]
+    nodes, inits, inputs = [], [], []
+    i64 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.int64)))  # noqa: E731
+    table = lambda t: t.reshape(-1) if spec["rank1"] else t  # noqa: E731
+    mixed = spelling == "d"
+    if mixed:
+        inputs.append(value_info("X", [batch, k + m]))
+    else:
+        inputs.append(value_info("x_cat", [batch, k], int_type))
+        if m and spelling != "c":
+            inputs.append(value_info("x_num", [batch, m]))
+    src = "X" if mixed else "x_cat"
+    if spelling in ("a", "d"):
+        parts = []
+        i64("ax1", [1])
+        for j in range(k):
+            if pick == "gather":
+                i64(f"col{j}_i", j)
+                nodes.append(node("Gather", [src, f"col{j}_i"], [f"col{j}"], [attr_i("axis", 1)], name=f"pick{j}"))
+            else:
+                i64(f"col{j}_b", [j]); i64(f"col{j}_e", [j + 1])  # noqa: E702
+                nodes.append(node("Slice", [src, f"col{j}_b", f"col{j}_e", "ax1"], [f"col{j}_s"], name=f"pick{j}"))
+                nodes.append(node("Squeeze", [f"col{j}_s", "ax1"], [f"col{j}"], name=f"squeeze{j}"))
+            idx = f"col{j}"
+            if mixed:
+                nodes.append(node("Cast", [idx], [f"col{j}_int"], [attr_i("to", int_type)], name=f"cast{j}"))
+                idx = f"col{j}_int"
+            inits.append(tensor(f"table{j}", table(spec["tables"][j])))
+            nodes.append(node("Gather", [f"table{j}", idx], [f"e{j}"] if not spec["rank1"] else [f"e{j}_flat"], name=f"emb{j}"))
+            if spec["rank1"]:  # [N] -> [N, 1] for the Concat
+                nodes.append(node("Unsqueeze", [f"e{j}_flat", "ax1"], [f"e{j}"], name=f"unsq{j}"))
+            parts.append(f"e{j}")
+        if m:
+            if mixed:
+                i64("num_b", [k]); i64("num_e", [k + m])  # noqa: E702
+                nodes.append(node("Slice", ["X", "num_b", "num_e", "ax1"], ["x_num"], name="numeric"))
+            parts.append("x_num")
+        if len(parts) == 1 and not concat:
+            return nodes, inits, parts[0], [batch, dims[0]], inputs
+        nodes.append(node("Concat", parts, ["features"], [attr_i("axis", 1)], name="join"))
+        return nodes, inits, "features", [batch, sum(dims) + m], inputs
+    d = dims[0]
+    if spelling == "b":
+        inits.append(tensor("table", spec["shared"]))
+        i64("offsets", spec["offsets"].reshape((1, k) if offsets_rank == 2 else (k,)))
+        nodes.append(node("Add", ["x_cat", "offsets"], ["idx"], name="offset"))
+        nodes.append(node("Gather", ["table", "idx"], ["tokens"], name="emb"))
+    else:
+        inits.append(tensor("table", spec["tables"][0]))
+        nodes.append(node("Gather", ["table", "x_cat"], ["tokens"], name="emb"))
+    if flatten == "window" or spelling == "c":
+        return nodes, inits, "tokens", [batch, k, d], inputs
+    if flatten == "flatten":
+        nodes.append(node("Flatten", ["tokens"], ["flat"], [attr_i("axis", 1)], name="flatten"))
+    else:
+        i64("flat_shape", [-1, k * d])
+        nodes.append(node("Reshape", ["tokens", "flat_shape"], ["flat"], name="flatten"))
+    if not m:
+        return nodes, inits, "flat", [batch, k * d], inputs
+    nodes.append(node("Concat", ["flat", "x_num"], ["features"], [attr_i("axis", 1)], name="join"))
+    return nodes, inits, "features", [batch, k * d + m], inputs
+
+
+def embedding_from_spec(spec: dict, spelling: str = "a", tail: str = "mlp", encoder: dict | None = None, heads: Sequence[str] = ("mean",), **front) -> bytes:
+    """The ONNX model of an embedding_spec() in one of EMBED_SPELLINGS (embedding_nodes; **front: its options).
+    tail: "mlp" (the spec's Linear layers, MatMul + Add with Relu between; output 'Y'), "none" (the front end's result is the output 'Y'),
+    "encoder": a transformer_spec() / from_torch_encoder() dict `encoder` with T = k and F = E = d behind the window (its positional constant,
+    layers and head; outputs as transformer_from_spec names them)."""
+    nodes, inits, cur, dims, inputs = embedding_nodes(spec, spelling, **front)
+    if tail == "encoder":
+        return transformer_from_spec(encoder, flat=False, heads=heads, front=(nodes, inits, cur, inputs))
+    if tail == "mlp":
+        for i, (W, b) in enumerate(spec["mlp"]):
+            inits += [tensor(f"W{i}", W), tensor(f"B{i}", b)]
+            nodes += [node("MatMul", [cur, f"W{i}"], [f"Z{i}"], name=f"fc{i}"), node("Add", [f"Z{i}", f"B{i}"], [f"H{i}"], name=f"fc{i}_bias")]
+            cur = f"H{i}"
+            if i + 1 < len(spec["mlp"]):
+                nodes.append(node(spec["act"], [cur], [f"A{i}"], name=f"act{i}"))
+                cur = f"A{i}"
+        if spec["mlp"]:
+            dims = dims[:-1] + [int(spec["mlp"][-1][0].shape[1])]
+    nodes.append(node("Identity", [cur], ["Y"]))
+    return model("embedding_" + spelling, nodes, inits, inputs, [value_info("Y", dims)], opset=13)
+
+
+def embedding_lookup_reference(table, idx, offset=0) -> np.ndarray:
+    """table[i] for i = trunc(idx) + offset with ONNX's negative indices (i in [-V, -1] counts from the end); raises IndexError beyond that."""
+    t = np.asarray(table)
+    i = np.trunc(np.asarray(idx, dtype=np.float64))
+    if not np.all(np.isfinite(i)):
+        raise IndexError("an index is not finite")
+    i = i.astype(np.int64) + np.asarray(offset, dtype=np.int64)
+    if np.any(i < -len(t)) or np.any(i >= len(t)):
+        raise IndexError("an index is out of range")
+    return t[np.where(i < 0, i + len(t), i)]
+
+
+def embedding_reference(spec: dict, x_cat, x_num=None, spelling: str = "a", tail: str = "mlp", flatten: str = "reshape", encoder: dict | None = None,
+                        heads: Sequence[str] = ("mean",)) -> dict:
+    """numpy restatement of embedding_from_spec: {"features": the front end's result (f32, exact copies: table[idx], concatenation),
+    "output": what follows it in float64 (the MLP, or the encoder's outputs as transformer_reference names them)}.  x_cat [N, k] index values
+    (any real dtype: truncated toward zero), x_num [N, m] f32 or None."""
+    x_cat = np.asarray(x_cat)
+    k = len(spec["cards"])
+    if spelling in ("a", "d"):
+        parts = [embedding_lookup_reference(spec["tables"][j], x_cat[:, j]).reshape(len(x_cat), -1) for j in range(k)]
+        feats = np.concatenate(parts + ([np.asarray(x_num, np.float32)] if spec["numeric"] else []), axis=1)
+    else:
+        tok = embedding_lookup_reference(spec["shared"], x_cat, spec["offsets"]) if spelling == "b" else embedding_lookup_reference(spec["tables"][0], x_cat)
+        if spelling == "c" or flatten == "window":
+            feats = tok
+        else:
+            feats = tok.reshape(len(tok), -1)
+            if spec["numeric"]:
+                feats = np.concatenate([feats, np.asarray(x_num, np.float32)], axis=1)
+    feats = np.ascontiguousarray(feats, dtype=np.float32)
+    out = {"features": feats}
+    if tail == "encoder":
+        out["output"] = transformer_reference(encoder, feats, heads)
+    elif tail == "mlp":
+        h = feats.astype(np.float64)
+        for i, (W, b) in enumerate(spec["mlp"]):
+            h = h @ np.asarray(W, np.float64) + np.asarray(b, np.float64)
+            if i + 1 < len(spec["mlp"]):
+                h = np.maximum(h, 0.0)
+        out["output"] = h
+    else:
+        out["output"] = feats.astype(np.float64)
+    return out
+
+
+def embedding_inputs(spec: dict, rows: int, seed: int = 0, spelling: str = "a"):
+    """Valid inputs of an embedding_spec(): (x_cat [rows, k] int64 with every column inside its table, x_num [rows, m] f32, and the one
+    f32 table [rows, k + m] a call passes: x_cat's values beside x_num in input order).  Spelling (c): every column indexes table 0."""
+    rng = np.random.default_rng(seed)
+    cards = [spec["cards"][0]] * len(spec["cards"]) if spelling == "c" else spec["cards"]
+    x_cat = np.stack([rng.integers(0, v, rows) for v in cards], axis=1).astype(np.int64)
+    x_num = rng.standard_normal((rows, spec["numeric"])).astype(np.float32)
+    m = 0 if spelling == "c" else spec["numeric"]
+    return x_cat, x_num, np.ascontiguousarray(np.concatenate([x_cat.astype(np.float32), x_num[:, :m]], axis=1))
