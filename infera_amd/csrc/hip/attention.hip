@@ -26,7 +26,16 @@
 // measured is this one form (tools/transformer_time.py, profiles/r11_transformer.txt): its rate, its fraction of the f32 MFMA peak, and
 // its time beside torch-ROCm's float32 scaled_dot_product_attention on the same tensors: 0.10 of the peak at T = 24 and 0.30 at T = 128
 // (dh = 16: four MFMAs per product between shuffles and expf, nothing overlapped), 0.64 x / 0.83 x torch's time -- slower on neither.
+//
+// Row masks (attention_kernel<DT, true>; INTEGRATION.md 2.6 "Padded sequences"): a row's own key mask is T values of the
+// model's input buffer.  The workgroup first turns them into a kept-bitmap in LDS (one ballot per 64 keys, at most 32 words).  With an
+// excluding fill, in a row that keeps a key, a masked key is a key beyond T: staged as zeros without being read, its score -inf before
+// the maximum; a 32-key tile whose word is 0 is skipped before its staging loads and a 16-key sub-tile whose half-word is 0 before its
+// MFMAs -- both branches are the same in every thread of the workgroup.  Otherwise (a bias fill, or a row that keeps no key) the fill goes
+// into the score and nothing is skipped.  The <DT, false> kernels are the code above, unchanged.
 #include "device_common.hpp"
+
+#include <cstdlib>
 
 #include "../host/attention.hpp"
 
@@ -42,13 +51,23 @@ struct AttnArgs {
   int T, H, dh, ldq, ldk, ldv, offq, offk, offv;
   float scale;
   bool vec;
+  // the row's own key mask (ROWMASK kernels; INTEGRATION.md 2.6 "Padded sequences"): key j of a row is kept iff rm[row * rm_ld + rm_off + j]
+  // (truncated toward zero first when rm_int) != rm_cmp.  rm_excl: a masked key is a key beyond T (in rows that keep a key); else its
+  // score is sc + rm_fill (rm_mode kRowMaskAdd) or rm_fill (kRowMaskReplace).  rm_skip: wholly masked tiles are not visited
+  const float *rm;
+  int64_t rm_ld;
+  int rm_off;
+  float rm_cmp, rm_fill;
+  int rm_mode;
+  bool rm_excl, rm_int, rm_skip;
 };
 
-template <int DT>
+template <int DT, bool ROWMASK>
 __global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs a) {
   constexpr int DP = DT * 16, LS = DP + 4, QPR = DP / 4;
   __shared__ __attribute__((aligned(16))) float ks[kAttnKeyTile * LS];
   __shared__ __attribute__((aligned(16))) float vs[kAttnKeyTile * LS];
+  __shared__ unsigned kept[ROWMASK ? kAttnMaxT / 32 : 1];  // ROWMASK: bit (j & 31) of word j / 32 = key j is kept
   const int tid = int(threadIdx.x), nth = int(blockDim.x), nw = nth >> 6, wave = tid >> 6, lane = tid & 63, n = lane & 15, kq = lane >> 4;
   const int64_t row = int64_t(blockIdx.x) / a.H;
   const int head = int(int64_t(blockIdx.x) - row * a.H), T = a.T, dh = a.dh;
@@ -79,12 +98,44 @@ __global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs 
   }
   float m_run = -INFINITY, l_run = 0.f;
 
+  // ROWMASK: the kept bitmap of the row (64 keys per ballot, so a wave writes two words at a time), and whether its masked keys are
+  // excluded: only with an excluding fill AND a kept key.  Both are the same in every thread of the workgroup
+  bool excl = false, skip = false;
+  if constexpr (ROWMASK) {
+    const float *mp = a.rm + row * a.rm_ld + a.rm_off;
+    for (int base = wave * 64; base < T; base += nw * 64) {
+      const int key = base + lane;
+      bool kp = false;
+      if (key < T) {
+        const float mv = mp[key];
+        kp = (a.rm_int ? truncf(mv) : mv) != a.rm_cmp;  // (a NaN is unequal: kept)
+      }
+      const unsigned long long b = __ballot(kp);
+      if (lane == 0) {
+        kept[base >> 5] = unsigned(b);
+        kept[(base >> 5) + 1] = unsigned(b >> 32);
+      }
+    }
+    __syncthreads();
+    unsigned any = 0;
+    for (int w = 0; w < (T + 31) >> 5; w++) any |= kept[w];
+    excl = a.rm_excl && any != 0;
+    skip = excl && a.rm_skip;
+  }
+
   for (int k0 = 0; k0 < T; k0 += kAttnKeyTile) {
+    unsigned kw = 0xffffffffu;
+    if constexpr (ROWMASK) {
+      kw = kept[k0 >> 5];
+      if (skip && kw == 0) continue;  // (the same branch in every thread: the barriers below stay matched)
+    }
     __syncthreads();  // the previous tile has been read by every wave
     for (int e = tid; e < kAttnKeyTile * QPR; e += nth) {
       const int key = e / QPR, d = (e - key * QPR) * 4;
       f32x4 kk = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-      if (k0 + key < T) {
+      bool in = k0 + key < T;
+      if constexpr (ROWMASK) in = in && (!excl || ((kw >> key) & 1u));  // an excluded key is never read
+      if (in) {
         kk = load4(kp + int64_t(k0 + key) * a.ldk, d);
         vv = load4(vp + int64_t(k0 + key) * a.ldv, d);
       }
@@ -95,6 +146,8 @@ __global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs 
 #pragma unroll
     for (int sub = 0; sub < kAttnKeyTile / 16; sub++) {
       if (k0 + 16 * sub >= T) break;
+      if constexpr (ROWMASK)
+        if (skip && ((kw >> (16 * sub)) & 0xffffu) == 0) continue;
       f32x4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int c = 0; c < DT; c++) {
@@ -110,6 +163,8 @@ __global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs 
         if (key < T) {
           sc[i] = s[i] * a.scale;
           if (a.mask && qi < T) sc[i] += a.mask[int64_t(qi) * T + key];
+          if constexpr (ROWMASK)
+            if (!((kw >> (16 * sub + 4 * kq + i)) & 1u)) sc[i] = excl ? -INFINITY : a.rm_mode == kRowMaskAdd ? sc[i] + a.rm_fill : a.rm_fill;
         }
         mx = fmaxf(mx, sc[i]);
       }
@@ -153,19 +208,32 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 }  // namespace
 
 bool attention(hipStream_t s, const float *q, const float *k, const float *v, const float *mask, float *y, int64_t rows, int T, int heads, int dh,
-               const int64_t ld[3], const int64_t off[3], float scale) {
+               const int64_t ld[3], const int64_t off[3], float scale, const float *rm, int64_t rm_ld, int rm_off, float rm_cmp, float rm_fill, int rm_mode,
+               bool rm_excl, bool rm_int) {
   if (rows <= 0) return true;
   if (T < 1 || T > kAttnMaxT || dh < 1 || dh > kAttnMaxDh || heads < 1 || heads > kAttnMaxHeads || rows * heads > INT32_MAX) return false;
-  AttnArgs a{q, k, v, mask, y, T, heads, dh, int(ld[0]), int(ld[1]), int(ld[2]), int(off[0]), int(off[1]), int(off[2]), scale, false};
+  if (rm && (mask || rm_off < 0 || int64_t(rm_off) + T > rm_ld)) return false;
+  // INFERA_ATTN_SKIP=0 (read once per process): wholly masked tiles are visited like the others, with zeros staged and -inf scores -- the
+  // same results; the A/B of tools/padded_time.py
+  static const bool skip_tiles = !(getenv("INFERA_ATTN_SKIP") && atoi(getenv("INFERA_ATTN_SKIP")) == 0);
+  AttnArgs a{q, k, v, mask, y, T, heads, dh, int(ld[0]), int(ld[1]), int(ld[2]), int(off[0]), int(off[1]), int(off[2]), scale, false,
+             rm, rm_ld, rm_off, rm_cmp, rm_fill, rm_mode, rm_excl, rm_int, skip_tiles};
   a.vec = dh % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v);
   for (int i = 0; i < 3; i++) a.vec = a.vec && ld[i] % 4 == 0 && off[i] % 4 == 0;
   const int tiles = (T + 15) / 16, nw = tiles < kAttnMaxWaves ? tiles : kAttnMaxWaves;
   const dim3 grid(unsigned(rows * heads), unsigned((tiles + nw - 1) / nw)), block(unsigned(64 * nw));
   const int dt = (dh + 15) / 16;
-  if (dt <= 1) hipLaunchKernelGGL(attention_kernel<1>, grid, block, 0, s, a);
-  else if (dt <= 2) hipLaunchKernelGGL(attention_kernel<2>, grid, block, 0, s, a);
-  else if (dt <= 4) hipLaunchKernelGGL(attention_kernel<4>, grid, block, 0, s, a);
-  else hipLaunchKernelGGL(attention_kernel<8>, grid, block, 0, s, a);
+  if (rm) {
+    if (dt <= 1) hipLaunchKernelGGL((attention_kernel<1, true>), grid, block, 0, s, a);
+    else if (dt <= 2) hipLaunchKernelGGL((attention_kernel<2, true>), grid, block, 0, s, a);
+    else if (dt <= 4) hipLaunchKernelGGL((attention_kernel<4, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((attention_kernel<8, true>), grid, block, 0, s, a);
+    return true;
+  }
+  if (dt <= 1) hipLaunchKernelGGL((attention_kernel<1, false>), grid, block, 0, s, a);
+  else if (dt <= 2) hipLaunchKernelGGL((attention_kernel<2, false>), grid, block, 0, s, a);
+  else if (dt <= 4) hipLaunchKernelGGL((attention_kernel<4, false>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((attention_kernel<8, false>), grid, block, 0, s, a);
   return true;
 }
 

@@ -103,13 +103,21 @@ bool rnn(hipStream_t s, const float *x, const float *wr, const float *bias, cons
 // ---- Transformer encoders (attention.hip, layernorm.hip) -------------------------------------------------------------------------
 // y [rows, T, heads * dh] = softmax(scale . Q K^T + mask) V per row and head; q / k / v: [rows, T, ld[i]] with head g at columns
 // off[i] + g * dh of a step (the same pointer three times for a packed projection); mask: [T, T] or null, -inf = no weight.
+// rm: null, or the buffer that holds the rows' own key masks ([rows, rm_ld]; no constant mask beside it): key j of a row is kept iff
+// rm[row, rm_off + j] (rm_int: truncated toward zero) != rm_cmp; a masked key is excluded like a key beyond T (rm_excl, in rows that keep a
+// key) or scored sc + rm_fill / rm_fill (rm_mode: RowMaskMode).
 // false: a size is beyond the caps of host/attention.hpp (the lowering refuses those at load)
 bool attention(hipStream_t s, const float *q, const float *k, const float *v, const float *mask, float *y, int64_t rows, int T, int heads, int dh,
-               const int64_t ld[3], const int64_t off[3], float scale);
+               const int64_t ld[3], const int64_t off[3], float scale, const float *rm = nullptr, int64_t rm_ld = 0, int rm_off = 0, float rm_cmp = 0.f,
+               float rm_fill = 0.f, int rm_mode = 0, bool rm_excl = false, bool rm_int = false);
 // y = (x - mean) / sqrt(var + eps) * gamma + beta over each of nvec vectors of E elements (beta may be null); false: E beyond the cap
 bool layernorm(hipStream_t s, const float *x, const float *gamma, const float *beta, float *y, int64_t nvec, int E, float eps);
 // y[r, e] = mean over t of x[r, t, e]
 void mean_time(hipStream_t s, const float *x, float *y, int64_t rows, int T, int E);
+// y[r, e] = (sum in order over the kept t of x[r, t, e]) / max(float(kept steps of row r), clip); step t is kept iff rm[r, rm_off + t]
+// (rm_int: truncated toward zero) != rm_cmp; a masked step is not read
+void mean_time_masked(hipStream_t s, const float *x, float *y, int64_t rows, int T, int E, const float *rm, int64_t rm_ld, int rm_off, float rm_cmp,
+                      bool rm_int, float clip);
 
 // ---- dense layer, fp32 MFMA (dense.hip) -------------------------------------------------------
 // Y[rows, M] = act(X[rows, K] . W[K, M] + bias[M]); W row-major, bias may be null.

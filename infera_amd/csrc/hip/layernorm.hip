@@ -10,6 +10,7 @@
 // Sums are per-lane partial sums (lane l of the group takes quads l, l + G, ...) joined by an xor butterfly: fixed order,
 // deterministic, but not the left-to-right order of a numpy restatement.
 // mean_time_kernel: out[r, e] = (sum over t in order of x[r, t, e]) / T, one thread per (row, e): coalesced over e.
+// mean_time_masked_kernel: the same under a row's own mask (INTEGRATION.md 2.6 "Padded sequences"): the sum over the kept steps / max(count, clip).
 #include "device_common.hpp"
 
 #include "../host/attention.hpp"
@@ -117,6 +118,43 @@ __global__ __launch_bounds__(256) void mean_time_kernel(const float *__restrict_
   y[i] = sum / float(T);
 }
 
+// one thread per (row, e) as above; the mask value of step t is the same address in all lanes of a row, and the branch is per row
+__global__ __launch_bounds__(256) void mean_time_masked_kernel(const float *__restrict__ x, float *__restrict__ y, int64_t n, int T, int E,
+                                                               const float *__restrict__ rm, int64_t rm_ld, int rm_off, float rm_cmp, bool rm_int, float clip) {
+  const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t row = i / E;
+  const float *xp = x + row * T * E + (i - row * E);
+  const float *mp = rm + row * rm_ld + rm_off;
+  float sum = 0.f;
+  int count = 0;
+  auto keeps = [&](int t) {
+    const float mv = mp[t];
+    return (rm_int ? truncf(mv) : mv) != rm_cmp;
+  };
+  int t = 0;
+  for (; t + 4 <= T; t += 4) {  // four steps' loads in flight; a masked step's load is not issued, and the sum keeps its order
+    bool k[4];
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) k[j] = keeps(t + j);
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = k[j] ? xp[int64_t(t + j) * E] : 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      if (k[j]) {
+        sum += v[j];
+        count++;
+      }
+  }
+  for (; t < T; t++)
+    if (keeps(t)) {
+      sum += xp[int64_t(t) * E];
+      count++;
+    }
+  y[i] = sum / fmaxf(float(count), clip);
+}
+
 }  // namespace
 
 bool layernorm(hipStream_t s, const float *x, const float *gamma, const float *beta, float *y, int64_t nvec, int E, float eps) {
@@ -135,6 +173,13 @@ void mean_time(hipStream_t s, const float *x, float *y, int64_t rows, int T, int
   const int64_t n = rows * E;
   if (n <= 0) return;
   hipLaunchKernelGGL(mean_time_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, x, y, n, T, E);
+}
+
+void mean_time_masked(hipStream_t s, const float *x, float *y, int64_t rows, int T, int E, const float *rm, int64_t rm_ld, int rm_off, float rm_cmp,
+                      bool rm_int, float clip) {
+  const int64_t n = rows * E;
+  if (n <= 0) return;
+  hipLaunchKernelGGL(mean_time_masked_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, s, x, y, n, T, E, rm, rm_ld, rm_off, rm_cmp, rm_int, clip);
 }
 
 }  // namespace infera_hip::kern

@@ -37,6 +37,7 @@ std::vector<EffStep> effective_steps(const LoadedModel &m) {
         EffStep e{int(i), {st[i].in0}, st[i].out};
         if (st[i].in1 >= 0) e.reads.push_back(st[i].in1);
         if (st[i].in2 >= 0) e.reads.push_back(st[i].in2);
+        if (st[i].in3 >= 0) e.reads.push_back(st[i].in3);
         out.push_back(e);
       }
     }
@@ -58,6 +59,7 @@ struct Scheduler {
       if (s.in0 >= 0) uses[size_t(s.in0)]++;
       if (s.in1 >= 0) uses[size_t(s.in1)]++;
       if (s.in2 >= 0) uses[size_t(s.in2)]++;
+      if (s.in3 >= 0) uses[size_t(s.in3)]++;
     }
     uses[size_t(m.plan.out_buf)]++;
   }
@@ -213,7 +215,7 @@ void Scheduler::decide_layout(bool commit) {
     for (const auto &s : st) {
       writers += s.out == m.plan.out_buf;
       convt_writers += s.out == m.plan.out_buf && s.kind == StepKind::ConvTranspose2d;
-      readers += s.in0 == m.plan.out_buf || s.in1 == m.plan.out_buf || s.in2 == m.plan.out_buf;
+      readers += s.in0 == m.plan.out_buf || s.in1 == m.plan.out_buf || s.in2 == m.plan.out_buf || s.in3 == m.plan.out_buf;
     }
     out_by_convt = writers == 1 && convt_writers == 1 && readers == 0;
     if (out_by_convt) m.nchw_buf[size_t(m.plan.out_buf)] = 1;
@@ -228,7 +230,7 @@ void Scheduler::decide_layout(bool commit) {
     int writers = 0, readers = 0, flat_readers = 0;
     for (const auto &s : st) {
       writers += s.out == c.out;
-      const bool reads = s.in0 == c.out || s.in1 == c.out || s.in2 == c.out;
+      const bool reads = s.in0 == c.out || s.in1 == c.out || s.in2 == c.out || s.in3 == c.out;
       readers += reads;
       flat_readers += reads && flat_pair(s, c.out);
     }
@@ -474,7 +476,7 @@ void Scheduler::narrow_edges(StepKind kind, bool enabled, bool needs_qy, bool (*
     bool ok = true;
     for (size_t j = 0; j < n; j++) {
       const Step &c = st[j];
-      if (c.in0 != p.out && c.in1 != p.out && c.in2 != p.out) continue;
+      if (c.in0 != p.out && c.in1 != p.out && c.in2 != p.out && c.in3 != p.out) continue;
       readers++;
       ok = ok && j > i && c.kind == kind && c.in0 == p.out && same_format(p, c) && c.K == p.M && c.rep == p.rep;
     }
@@ -553,6 +555,12 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
       return st[i].kind == StepKind::Dense && st[i].rep > 1;
     };
     if (!eff.empty() && eff[0].reads[0] == 0 && window_dense_at(size_t(eff[0].idx))) {
+      m.in_colmajor_ok = false;
+      m.in_colmajor_max_rows = INT64_MAX;
+    }
+    // a row mask is read from the input buffer as T consecutive columns of a row: such plans take their chunk row-major, like window and
+    // Embed plans
+    if (std::any_of(st.begin(), st.end(), [](const Step &s) { return s.in3 >= 0; })) {
       m.in_colmajor_ok = false;
       m.in_colmajor_max_rows = INT64_MAX;
     }

@@ -480,7 +480,8 @@ void PassRunner::launch_plain(size_t i) {
       break;
     case StepKind::Attention:
       if (!kern::attention(stream, buf(x.in0), buf(x.in1), buf(x.in2), t.cst, buf(x.out), nr, int(x.attn_T), int(x.attn_heads), int(x.attn_dh), x.attn_ld,
-                           x.attn_off, x.attn_scale))
+                           x.attn_off, x.attn_scale, x.in3 >= 0 ? buf(x.in3) : nullptr, x.in3 >= 0 ? p.buf_per_row[size_t(x.in3)] : 0, int(x.rm_off), x.rm_cmp,
+                           x.rm_fill, x.rm_mode, x.rm_excl, x.rm_int))
         throw InferaError::onnx("attention kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
       break;
     // the other families: their pairs above
@@ -524,7 +525,12 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::ChannelShuffle: kern::channel_shuffle(stream, buf(x.in0), buf(x.out), nr, int(x.C), int(x.S), int(x.groups), cq(x.in0)); break;
     case StepKind::SliceCols: kern::copy_cols(stream, buf(x.in0), buf(x.out), nr, x.K, p.buf_per_row[size_t(x.in0)], x.col_off, x.K, 0); break;
     case StepKind::ArgMax: kern::argmax_rows(stream, buf(x.in0), buf(x.out), nr, x.K); break;
-    case StepKind::MeanTime: kern::mean_time(stream, buf(x.in0), buf(x.out), nr, int(x.rep), int(x.K)); break;
+    case StepKind::MeanTime:
+      if (x.in3 >= 0)
+        kern::mean_time_masked(stream, buf(x.in0), buf(x.out), nr, int(x.rep), int(x.K), buf(x.in3), p.buf_per_row[size_t(x.in3)], int(x.rm_off), x.rm_cmp, x.rm_int,
+                               x.rm_clip);
+      else kern::mean_time(stream, buf(x.in0), buf(x.out), nr, int(x.rep), int(x.K));
+      break;
     case StepKind::FakeQuant:
       kern::fake_quant(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], x.qx.scale, x.qx.zp, x.qx.qmin(), x.qx.qmax());
       break;

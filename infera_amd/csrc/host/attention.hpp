@@ -9,6 +9,10 @@ namespace infera_hip {
 constexpr int64_t kAttnMaxT = 1024;   // window length: the [T, T] mask constant and the 32-bit score indices
 constexpr int64_t kAttnMaxDh = 128;   // head width: Q and the output tile of a wave live in registers (8 + 8 fragments of 16 columns)
 constexpr int64_t kAttnMaxHeads = 1024;
+// how a row mask's fill reaches a masked key's score (Step::rm_mode): added to the scaled score (BERT) or in its place (masked_fill)
+enum RowMaskMode : int { kRowMaskAdd = 0, kRowMaskReplace = 1 };
+// a fill at or below this (the finfo.min family and -inf) excludes its keys; anything above it is a bias that goes through the softmax
+constexpr float kRowMaskExcludingFill = -1e30f;
 constexpr int64_t kLnMaxE = 4096;     // LayerNorm vector length: one vector is held in the registers of one wave (64 floats per lane)
 
 }  // namespace infera_hip

@@ -20,6 +20,8 @@
 #include <numeric>
 #include <sstream>
 
+#include <iomanip>
+
 #include "attention.hpp"
 #include "channelnorm.hpp"
 #include "common.hpp"
@@ -2495,10 +2497,24 @@ struct Lowerer {
     const NodeDef *cut = nullptr;  // that Split / Slice on the last axis
     size_t cut_out = 0;
   };
+  // A row's own key mask (INTEGRATION.md 2.6 "Padded sequences"): T consecutive columns of the input buffer and a compare value, traced
+  // back from where it meets the scores (or the masked mean) through Cast / Unsqueeze / Reshape / Expand / Equal / Not to a graph input
+  struct RowMask {
+    int64_t src0 = 0, k = 0;     // columns [src0, src0 + k) of the input buffer
+    bool is_int = false;         // the graph sees them as integers: truncated toward zero before the comparison
+    float cmp = 0.f;             // kept iff value != cmp
+    int state = 0;               // the traced value: 0 the source's own values (kept iff != 0), 1 a bool true = masked, 2 a bool true = kept
+    std::vector<int64_t> shape;  // of the traced value in front of any Expand; shape[0] = -1, the rows
+    std::vector<size_t> nodes, aux;  // the nodes between the graph input and the value; aux: the Shape sub-graph that sizes an Expand
+    float fill = 0.f;            // Attention: the negative constant of masked keys, and how it reaches the score (RowMaskMode)
+    int mode = kRowMaskAdd;
+    const NodeDef *at = nullptr;  // the Add / Where on the scores
+  };
   struct AttnMatch {
     AttnSide side[3];  // Q, K, V
     std::vector<AttnScale> scales;
     std::string mask;
+    std::shared_ptr<RowMask> rm;
     const NodeDef *qk = nullptr;
     std::vector<size_t> nodes;
   };
@@ -2507,6 +2523,196 @@ struct Lowerer {
   std::map<const NodeDef *, std::string> attn_fail;  // MatMul(activation, activation) nodes outside one: why
   std::map<std::string, std::vector<size_t>> consumers_of;  // live consumers of every value
   std::map<std::string, size_t> producer_of;
+
+  std::set<std::string> attn_row_data;  // values computed from a graph input (find_attention)
+  struct MaskedMean {
+    std::string x;  // the window [N, T, E]
+    RowMask rm;
+    float clip = 0.f;
+    size_t mul = 0;
+  };
+  std::map<size_t, MaskedMean> mmean_at;  // the Div that closes a masked mean over time -> the pattern
+
+  // a constant known before the walk (an initializer or a Constant node): its first element and its element count
+  bool graph_const_scalar(const std::string &name, double *v, size_t *count = nullptr) const {
+    const TensorData *t = nullptr;
+    if (auto ci = m.initializers.find(name); ci != m.initializers.end()) {
+      t = ci->second.get();
+    } else {
+      auto pi = producer_of.find(name);
+      if (pi == producer_of.end() || m.nodes[pi->second].op != "Constant") return false;
+      const NodeDef &c = m.nodes[pi->second];
+      if (auto *a = c.attr("value"); a && a->t) t = a->t.get();
+      else if (auto *i = c.attr("value_int")) { *v = double(i->i); if (count) *count = 1; return true; }
+      else if (auto *f = c.attr("value_float")) { *v = double(f->f); if (count) *count = 1; return true; }
+      else return false;
+    }
+    const size_t n = t->count();
+    if (count) *count = n;
+    if (n < 1) return false;
+    *v = t->dtype == onnx::kInt64 ? double(t->i64[0]) : double(t->f32[0]);
+    return true;
+  }
+  // `v0` as a row mask; "" or why it is none
+  std::string trace_row_mask(const std::string &v0, RowMask *rm) const {
+    auto std_dom = [](const NodeDef &n) { return n.domain.empty() || n.domain == "ai.onnx"; };
+    std::vector<size_t> chain;
+    std::string v = v0;
+    for (int hop = 0; hop < 32; hop++) {
+      auto pi = producer_of.find(v);
+      if (pi == producer_of.end()) break;
+      const NodeDef &p = m.nodes[pi->second];
+      if (!std_dom(p) || p.inputs.empty()) break;
+      double c;
+      if (p.op == "Unsqueeze" || p.op == "Reshape" || p.op == "Cast" || p.op == "Expand" || p.op == "Not") v = p.inputs[0];
+      else if (p.op == "Equal" && p.inputs.size() == 2) v = p.inputs[graph_const_scalar(p.inputs[0], &c) ? 1 : 0];
+      else break;
+      chain.push_back(pi->second);
+    }
+    if (auto pi = producer_of.find(v); pi != producer_of.end() && m.nodes[pi->second].op == "Transpose")
+      return "a time-major mask source (the Transpose '" + node_label(m.nodes[pi->second]) + "' in front of it); only a rows-first [N, T] graph input";
+    EmbedCols cols;
+    if (!embed_cols(v, &cols).empty() || !cols.rank2 || !cols.off.empty())
+      return "the mask source '" + v + "' is not a column range of a graph input (a mask computed from activations is not supported)";
+    rm->src0 = cols.src0, rm->k = cols.k;
+    rm->is_int = cols.int_input || cols.truncated;
+    rm->nodes = cols.chain;
+    rm->shape = {-1, cols.k};
+    rm->state = 0;
+    rm->cmp = 0.f;
+    bool expanded = false;
+    for (auto it = chain.rbegin(); it != chain.rend(); ++it) {
+      const NodeDef &p = m.nodes[*it];
+      const std::string at = "'" + node_label(p) + "' in the mask sub-graph: ";
+      rm->nodes.push_back(*it);
+      std::vector<int64_t> &sh = rm->shape;
+      if (p.op == "Cast") {
+        const int64_t to = p.attr_i("to", onnx::kFloat);
+        if (rm->state == 0 && (to == onnx::kInt64 || to == onnx::kInt32)) rm->is_int = true;
+      } else if (p.op == "Not") {
+        if (rm->state == 0) return at + "Not of a value that no Equal produced";
+        rm->state = 3 - rm->state;
+      } else if (p.op == "Equal") {
+        double c = 0;
+        size_t cnt = 0;
+        const bool c0 = graph_const_scalar(p.inputs[0], &c, &cnt);
+        if (rm->state != 0 || (!c0 && !graph_const_scalar(p.inputs[1], &c, &cnt)) || cnt != 1) return at + "only Equal(source, one constant)";
+        if (double(float(c)) != c) return at + "the compare value is no f32 number (values arrive as f32)";
+        rm->cmp = float(c);
+        rm->state = 1;
+      } else if (expanded) {
+        return at + "a " + p.op + " behind the Expand";
+      } else if (p.op == "Unsqueeze") {
+        std::vector<int64_t> ax;
+        if (!graph_ints_arg(p, 1, "axes", &ax) || ax.empty()) return at + "axes must be constant";
+        const int64_t r = int64_t(sh.size() + ax.size());
+        for (auto &a : ax) a = a < 0 ? a + r : a;
+        std::sort(ax.begin(), ax.end());
+        for (int64_t a : ax) {
+          if (a < 1 || a > int64_t(sh.size())) return at + "an axis in front of the rows or out of range";
+          sh.insert(sh.begin() + a, 1);
+        }
+      } else if (p.op == "Reshape") {
+        std::vector<int64_t> tgt, tdims;
+        if (p.inputs.size() != 2 || !graph_const_ints(p.inputs[1], &tgt, &tdims) || tgt.empty()) return at + "the target shape must be constant";
+        if (!(tgt[0] == 0 || tgt[0] == -1 || (tgt[0] > 0 && tgt[0] == plan.input_shape[0]))) return at + "the target " + shape_str(tgt) + " does not keep the row axis";
+        int64_t per = 1, known = 1, neg = -1;
+        for (size_t i = 1; i < sh.size(); i++) per *= sh[i];
+        for (size_t i = 1; i < tgt.size(); i++) {
+          if (tgt[i] == 0 && i < sh.size()) tgt[i] = sh[i];
+          if (tgt[i] == -1 && neg < 0 && tgt[0] != -1) neg = int64_t(i);
+          else if (tgt[i] <= 0) return at + "the target " + shape_str(tgt);
+          else known *= tgt[i];
+        }
+        if (neg >= 0) {
+          if (per % known) return at + "the target " + shape_str(tgt);
+          tgt[size_t(neg)] = per / known, known = per;
+        }
+        if (known != per) return at + "the target " + shape_str(tgt) + " does not keep the " + std::to_string(per) + " mask values of a row";
+        tgt[0] = -1;
+        sh = tgt;
+      } else {  // Expand: a constant target is checked; one computed from a Shape broadcasts to its reader's shape, as ONNX would anyway
+        std::vector<int64_t> tgt, tdims;
+        if (p.inputs.size() != 2) return at + "no target";
+        if (graph_const_ints(p.inputs[1], &tgt, &tdims)) {
+          if (tgt.size() < sh.size()) return at + "the target " + shape_str(tgt) + " has a lower rank than the mask";
+          const size_t lead = tgt.size() - sh.size();
+          for (size_t i = 1; i < sh.size(); i++)
+            if (tgt[lead + i] != 1 && tgt[lead + i] != sh[i] && sh[i] != 1) return at + "the target " + shape_str(tgt) + " does not broadcast from " + shape_str(sh);
+        } else {
+          if (attn_row_data.count(p.inputs[1])) return at + "the target depends on the rows";
+          std::vector<std::string> work{p.inputs[1]};
+          while (!work.empty()) {  // the Shape sub-graph behind the target: it emits nothing either
+            const std::string w = work.back();
+            work.pop_back();
+            auto pi = producer_of.find(w);
+            if (pi == producer_of.end() || m.nodes[pi->second].op == "Constant" || std::count(rm->aux.begin(), rm->aux.end(), pi->second)) continue;
+            rm->aux.push_back(pi->second);
+            if (m.nodes[pi->second].op != "Shape")
+              for (const auto &in : m.nodes[pi->second].inputs) work.push_back(in);
+          }
+        }
+        expanded = true;
+      }
+    }
+    return "";
+  }
+  // the negative constant scalar b of masked keys
+  float row_mask_fill(const NodeDef &n, const std::string &name, bool add) {
+    double b = 0;
+    size_t cnt = 0;
+    if (attn_row_data.count(name) || !graph_const_scalar(name, &b, &cnt)) bad_form(n, "the fill '" + name + "' of masked keys is not a constant");
+    if (cnt != 1) bad_form(n, "the fill '" + name + "' of masked keys has " + std::to_string(cnt) + " elements; only one scalar");
+    const float f = float(b);
+    if (!(f < 0.f)) bad_form(n, "the fill of masked keys is " + std::to_string(b) + "; only a negative number or -inf");
+    if (add && f == -INFINITY) bad_form(n, "the fill of masked keys is -inf in the additive form (1 - mask) * fill, which is NaN at every kept key; use a finite fill or Where");
+    return f;
+  }
+  // Add(scores, other): other = Mul(Sub(1, float(mask [N,1,1,T])), b) (BERT); false: no such form
+  bool match_add_row_mask(const NodeDef &add, const std::string &other, AttnMatch &am) {
+    auto pi = producer_of.find(other);
+    if (pi == producer_of.end()) return false;
+    const NodeDef &mul = m.nodes[pi->second];
+    if (mul.op != "Mul" || mul.inputs.size() != 2) return false;
+    int side = -1;
+    const NodeDef *sub = nullptr;
+    for (int j = 0; j < 2; j++) {
+      auto si = producer_of.find(mul.inputs[size_t(j)]);
+      double one = 0;
+      size_t cnt = 0;
+      if (si != producer_of.end() && m.nodes[si->second].op == "Sub" && m.nodes[si->second].inputs.size() == 2 &&
+          graph_const_scalar(m.nodes[si->second].inputs[0], &one, &cnt) && cnt == 1 && one == 1.0)
+        side = j, sub = &m.nodes[si->second];
+    }
+    if (!sub) return false;
+    auto rm = std::make_shared<RowMask>();
+    rm->at = &add;
+    rm->mode = kRowMaskAdd;
+    rm->fill = row_mask_fill(add, mul.inputs[size_t(1 - side)], true);
+    if (const std::string why = trace_row_mask(sub->inputs[1], rm.get()); !why.empty()) bad_form(add, why);
+    if (rm->state == 1) bad_form(add, "(1 - Equal(source, c)) * fill puts the fill on the keys that differ from c; write Not(Equal(...)) or mask the equal ones with Where");
+    rm->nodes.push_back(producer_of.at(mul.inputs[size_t(side)]));
+    rm->nodes.push_back(pi->second);
+    if (!am.mask.empty() || am.rm) bad_form(add, "a row mask and another mask on one attention (causal and padding masks together are not supported)");
+    am.rm = std::move(rm);
+    return true;
+  }
+  // Where(masked, b, scores) or Where(kept, scores, b) (masked_fill)
+  void match_where_row_mask(const NodeDef &wh, const std::string &scores, AttnMatch &am) {
+    const bool scores_last = wh.inputs[2] == scores;
+    auto rm = std::make_shared<RowMask>();
+    rm->at = &wh;
+    rm->mode = kRowMaskReplace;
+    rm->fill = row_mask_fill(wh, wh.inputs[scores_last ? 1 : 2], false);
+    if (const std::string why = trace_row_mask(wh.inputs[0], rm.get()); !why.empty()) bad_form(wh, why);
+    if (rm->state == 0) {  // the mask itself as the condition (a Cast to bool): true = kept
+      if (scores_last) bad_form(wh, "the condition is the mask itself, so the fill would land on the kept keys");
+    } else if ((rm->state == 1) != scores_last) {
+      bad_form(wh, "the condition is true at the kept keys, so the fill would land on them");
+    }
+    if (!am.mask.empty() || am.rm) bad_form(wh, "a row mask and another mask on one attention (causal and padding masks together are not supported)");
+    am.rm = std::move(rm);
+  }
 
   void find_attention(const std::vector<char> &live) {
     const size_t N = m.nodes.size();
@@ -2528,6 +2734,7 @@ struct Lowerer {
       if (any)
         for (const auto &o : m.nodes[i].outputs) row_data.insert(o);
     }
+    attn_row_data = row_data;
     auto is_const = [&](const std::string &v) { return row_data.count(v) == 0; };
     auto perm_of = [&](const NodeDef &t) {
       std::vector<int64_t> p;
@@ -2619,11 +2826,26 @@ struct Lowerer {
       const NodeDef *sm = nullptr;
       while (ok && !sm) {
         const NodeDef *c = sole_reader(cur);
+        size_t ci = c ? consumers_of[cur][0] : 0;
+        if (!c && !graph_outs.count(cur) && consumers_of.count(cur)) {  // a Where beside the Shape nodes that size its condition's Expand
+          std::set<size_t> others;
+          for (size_t r : consumers_of[cur])
+            if (m.nodes[r].op != "Shape") others.insert(r);
+          if (others.size() == 1 && m.nodes[*others.begin()].op == "Where") c = &m.nodes[*others.begin()], ci = *others.begin();
+        }
         if (!c || !(c->domain.empty() || c->domain == "ai.onnx")) { ok = false; why = generic; break; }
-        const size_t ci = consumers_of[cur][0];
-        if ((c->op == "Mul" || c->op == "Div" || c->op == "Add") && c->inputs.size() == 2) {
+        if (c->op == "Where" && c->inputs.size() == 3 && c->inputs[0] != cur && (c->inputs[1] == cur) != (c->inputs[2] == cur)) {
+          match_where_row_mask(*c, cur, am);
+          am.nodes.push_back(ci);
+          cur = c->outputs[0];
+        } else if ((c->op == "Mul" || c->op == "Div" || c->op == "Add") && c->inputs.size() == 2) {
           const bool left = c->inputs[0] == cur;
           const std::string &other = c->inputs[left ? 1 : 0];
+          if (!is_const(other) && c->op == "Add" && match_add_row_mask(*c, other, am)) {
+            am.nodes.push_back(ci);
+            cur = c->outputs[0];
+            continue;
+          }
           if (!is_const(other)) {
             ok = false;
             why = c->op == "Add" ? "the attention mask '" + other + "' is not a constant (a mask computed in the graph or depending on the row is not supported)"
@@ -2632,6 +2854,7 @@ struct Lowerer {
           }
           if (c->op == "Add") {
             if (!am.mask.empty()) { ok = false; why = "more than one mask is added to the attention scores"; break; }
+            if (am.rm) bad_form(*c, "a row mask and a constant mask on one attention (causal and padding masks together are not supported)");
             am.mask = other;
           } else {
             if (c->op == "Div" && !left) { ok = false; why = generic; break; }
@@ -2710,6 +2933,123 @@ struct Lowerer {
           if (!all) absorbed[size_t(sd.cut - m.nodes.data())] = 0;
         }
       }
+    find_masked_means(live);
+    // The nodes of the mask sub-graphs emit nothing.  The mask value may feed every layer (exporters compute it once), so a node counts
+    // once; what a node reads is read by the steps from the input buffer itself (a mask input nothing else reads gets no SliceCols).
+    std::set<size_t> rm_nodes, rm_aux;
+    auto collect = [&](const RowMask &r) {
+      rm_nodes.insert(r.nodes.begin(), r.nodes.end());
+      rm_aux.insert(r.aux.begin(), r.aux.end());
+    };
+    for (auto &kv : attn_at)
+      if (kv.second.rm) collect(*kv.second.rm);
+    for (auto &kv : mmean_at) collect(kv.second.rm);
+    for (size_t i : rm_nodes) absorbed[i] = 1;
+    for (size_t i : rm_aux) absorbed[i] = 1;
+    auto readers_absorbed = [&](size_t i) {
+      bool all = true;
+      for (const auto &o : m.nodes[i].outputs) {
+        all = all && !graph_outs.count(o);
+        if (auto it = consumers_of.find(o); it != consumers_of.end())
+          for (size_t c : it->second) all = all && (absorbed[c] || mmean_at.count(c));  // (the closing Div emits the step)
+      }
+      return all;
+    };
+    for (auto it = rm_aux.rbegin(); it != rm_aux.rend(); ++it)
+      if (!rm_nodes.count(*it) && !readers_absorbed(*it)) absorbed[*it] = 0;  // (a Shape something else reads too is lowered for that reader)
+    for (auto it = rm_nodes.rbegin(); it != rm_nodes.rend(); ++it)
+      if (!readers_absorbed(*it)) bad_form(m.nodes[*it], "this node of a row mask's sub-graph also feeds nodes outside the attention / masked mean patterns");
+    rm_nodes.insert(rm_aux.begin(), rm_aux.end());
+    for (size_t i : rm_nodes) {
+      if (!absorbed[i]) continue;
+      for (const auto &in : m.nodes[i].inputs)
+        if (!in.empty()) uses[in]--;
+      region[i] = 0;
+    }
+  }
+
+  // The masked mean over time (the sentence-embedding head): Div(ReduceSum(Mul(x, m), 1), Clip(ReduceSum(m or mask, 1), min = c)) with
+  // m = float(mask [N, T, 1]), traced like an attention's row mask, becomes ONE MeanTime step with a row mask (lower_masked_mean)
+  void find_masked_means(const std::vector<char> &live) {
+    auto std_dom = [](const NodeDef &n) { return n.domain.empty() || n.domain == "ai.onnx"; };
+    auto sum_over_time = [&](const NodeDef &r) {
+      std::vector<int64_t> ax;
+      return r.op == "ReduceSum" && std_dom(r) && !r.inputs.empty() && graph_ints_arg(r, 1, "axes", &ax) && ax == std::vector<int64_t>{1};
+    };
+    auto made_by = [&](const std::string &v) -> const NodeDef * {
+      auto it = producer_of.find(v);
+      return it == producer_of.end() ? nullptr : &m.nodes[it->second];
+    };
+    auto idx = [&](const NodeDef *n) { return size_t(n - m.nodes.data()); };
+    for (size_t i = 0; i < m.nodes.size(); i++) {
+      const NodeDef &mul = m.nodes[i];
+      if (!live[i] || absorbed[i] || mul.op != "Mul" || !std_dom(mul) || mul.inputs.size() != 2 || mul.outputs.empty()) continue;
+      const NodeDef *rs = only_reader(mul.outputs[0]);
+      if (!rs || !sum_over_time(*rs) || rs->attr_i("keepdims", 1) != 0 || rs->inputs[0] != mul.outputs[0]) continue;
+      const NodeDef *div = only_reader(rs->outputs[0]);
+      if (!div || div->op != "Div" || !std_dom(*div) || div->inputs.size() != 2 || div->inputs[0] != rs->outputs[0]) continue;
+      const NodeDef *clip = made_by(div->inputs[1]);
+      if (!clip || clip->op != "Clip" || !std_dom(*clip) || only_reader(clip->outputs[0]) != div) continue;
+      MaskedMean mm;
+      double lo = 0;
+      size_t cnt = 0;
+      if (has_input(*clip, 2)) continue;
+      if (has_input(*clip, 1)) {
+        if (!graph_const_scalar(clip->inputs[1], &lo, &cnt) || cnt != 1) continue;
+      } else if (clip->attr("min") && !clip->attr("max")) {
+        lo = double(clip->attr_f("min", 0.f));
+      } else {
+        continue;
+      }
+      int side = -1;
+      for (int j = 0; j < 2 && side < 0; j++) {
+        RowMask r;
+        if (attn_row_data.count(mul.inputs[size_t(1 - j)]) && trace_row_mask(mul.inputs[size_t(j)], &r).empty() && r.state != 1 && r.shape.size() == 3 && r.shape[2] == 1)
+          side = j, mm.rm = std::move(r);
+      }
+      if (side < 0) continue;
+      // from here on the pattern is a masked mean, served or refused in its own words
+      std::vector<size_t> tail{i, idx(rs), idx(clip)};
+      const NodeDef *cs = made_by(clip->inputs[0]);
+      if (cs && cs->op == "Cast" && only_reader(cs->outputs[0]) == clip) tail.push_back(idx(cs)), cs = made_by(cs->inputs[0]);
+      RowMask cr;
+      if (!cs || !sum_over_time(*cs) || !only_reader(cs->outputs[0])) bad_form(*div, "the divisor of a masked mean must be Clip(ReduceSum(mask, axis 1), min = c)");
+      if (const std::string why = trace_row_mask(cs->inputs[0], &cr); !why.empty()) bad_form(*div, why);
+      if (cr.src0 != mm.rm.src0 || cr.k != mm.rm.k || cr.state == 1 || cr.cmp != mm.rm.cmp || (cr.state == 0) != (mm.rm.state == 0))
+        bad_form(*div, "the divisor of a masked mean counts another mask than the one that multiplies the window");
+      if (!(lo > 0) || !std::isfinite(lo)) bad_form(*clip, "the lower bound of a masked mean's count must be a positive finite constant");
+      tail.push_back(idx(cs));
+      mm.rm.nodes.insert(mm.rm.nodes.end(), cr.nodes.begin(), cr.nodes.end());
+      mm.rm.aux.insert(mm.rm.aux.end(), cr.aux.begin(), cr.aux.end());
+      mm.rm.nodes.insert(mm.rm.nodes.end(), tail.begin(), tail.end());
+      mm.rm.at = div;
+      mm.x = mul.inputs[size_t(1 - side)];
+      mm.clip = float(lo);
+      mm.mul = i;
+      mmean_at[idx(div)] = std::move(mm);
+    }
+  }
+  void lower_masked_mean(const MaskedMean &mm, const NodeDef &div) {
+    const Val *x = find_value(mm.x);
+    if (!x) bad_form(div, "the window '" + mm.x + "' of the masked mean is produced by no earlier node");
+    if (x->pv) materialize(mm.x, &div), x = find_value(mm.x);
+    if (x->is_const || x->ra != 0 || x->shape.size() != 3 || x->padded() || x->buf < 0)
+      bad_form(div, "the masked mean reads " + shape_str(x->shape) + (x->ra ? " (time-major)" : "") + "; only a rows-first window [N, T, E]");
+    const int64_t T = x->shape[1], E = x->shape[2];
+    if (mm.rm.k != T) bad_form(div, "the row mask has T = " + std::to_string(mm.rm.k) + ", the window T = " + std::to_string(T));
+    if (plan.input_declared_type == "float16") bad_form(div, "a row mask taken from a float16 graph input");
+    Step s;
+    s.kind = StepKind::MeanTime;
+    s.in0 = x->buf;
+    s.rep = T;
+    s.K = E;
+    s.in3 = 0;
+    s.rm_off = mm.rm.src0;
+    s.rm_cmp = mm.rm.cmp;
+    s.rm_int = mm.rm.is_int;
+    s.rm_clip = mm.clip;
+    s.origin = node_label(m.nodes[mm.mul]) + "+...+" + node_label(div);
+    emit_window(std::move(s), div, {x->shape[0], E});
   }
 
   const Val *find_value(const std::string &name) {
@@ -2832,6 +3172,25 @@ struct Lowerer {
         }
         if (!any) bad("row " + std::to_string(q) + " of the attention mask is -inf everywhere (a fully masked query has no softmax)");
       }
+    }
+    if (am.rm) {
+      const RowMask &r = *am.rm;
+      const NodeDef &at = *r.at;
+      if (!am.mask.empty()) bad_form(at, "a row mask and a constant mask on one attention (causal and padding masks together are not supported)");
+      const std::vector<int64_t> &sh = r.shape;
+      if (sh.size() == 4 && sh[3] == T && (sh[1] != 1 || sh[2] != 1))
+        bad_form(at, "the mask " + shape_str(sh) + " depends on the head or the query; only one key mask per row, [N,1,1,T]");
+      if (sh.size() != 4 || sh[1] != 1 || sh[2] != 1) bad_form(at, "the row mask meets the scores as " + shape_str(sh) + "; only [N,1,1,T]");
+      if (sh[3] != T) bad_form(at, "the row mask has T = " + std::to_string(sh[3]) + ", the attention T = " + std::to_string(T));
+      if (plan.input_declared_type == "float16") bad_form(at, "a row mask taken from a float16 graph input");
+      if (r.src0 < 0 || r.src0 + T > plan.buf_per_row[0]) bad_form(at, "the row mask's columns lie outside the input");
+      s.in3 = 0;
+      s.rm_off = r.src0;
+      s.rm_cmp = r.cmp;
+      s.rm_fill = r.fill;
+      s.rm_mode = r.mode;
+      s.rm_int = r.is_int;
+      s.rm_excl = r.fill <= kRowMaskExcludingFill;
     }
     {  // the merge Reshape must give [N, T, E]
       const std::vector<int64_t> tgt = const_ints(anchor, 1, "shape");
@@ -3411,7 +3770,7 @@ struct Lowerer {
     std::vector<Step> out;
     for (size_t i = 0; i < plan.steps.size(); i++) {
       Step s = std::move(plan.steps[i]);
-      s.in0 = at(s.in0), s.in1 = at(s.in1), s.in2 = at(s.in2);
+      s.in0 = at(s.in0), s.in1 = at(s.in1), s.in2 = at(s.in2);  // (in3 is the model input: never a rounded buffer)
       const bool round = half_bufs.count(s.out) && last_writer[s.out] == i && !half_exact(s);
       Step r;
       if (round) {
@@ -5101,6 +5460,7 @@ struct Lowerer {
       } else if (attn_at.count(ni)) lower_typed(n, [&] { lower_attention(attn_at.at(ni), n); });
       else if (nearest_at.count(ni)) lower_nearest(nearest_at.at(ni));
       else if (embed_at.count(ni)) lower_embed(embed_at.at(ni), n);
+      else if (mmean_at.count(ni)) lower_typed(n, [&] { lower_masked_mean(mmean_at.at(ni), n); });
       else if (absorbed[ni]) continue;
       else if (gn_at.count(ni)) lower_typed(n, [&] { if (!exporter_group_norm(gn_at.at(ni), n)) lower_node(n); });
       else lower_typed(n, [&] { lower_node(n); });
@@ -5153,7 +5513,7 @@ struct Lowerer {
   void drop_unread_fake_quants() {
     std::set<int> read = {plan.out_buf};
     for (const Step &s : plan.steps)
-      for (int b : {s.in0, s.in1, s.in2}) read.insert(b);
+      for (int b : {s.in0, s.in1, s.in2, s.in3}) read.insert(b);
     plan.steps.erase(std::remove_if(plan.steps.begin(), plan.steps.end(), [&](const Step &s) { return s.kind == StepKind::FakeQuant && !read.count(s.out); }),
                      plan.steps.end());
   }
@@ -5225,6 +5585,9 @@ std::string Plan::describe_json() const {
     }
     if (s.kind == StepKind::LayerNorm) o << ",\"E\":" << s.K << ",\"T\":" << s.rep << ",\"epsilon\":" << double(s.ln_eps) << ",\"bias\":" << (s.shift.empty() ? "false" : "true");
     if (s.kind == StepKind::MeanTime) o << ",\"E\":" << s.K << ",\"T\":" << s.rep;
+    auto json_f32 = [](float f) { return std::isnan(f) ? std::string("NaN") : std::isinf(f) ? std::string(f < 0 ? "-Infinity" : "Infinity") : ([&] { std::ostringstream q; q << std::setprecision(9) << double(f); return q.str(); })(); };
+    if (s.kind == StepKind::MeanTime && s.in3 >= 0)
+      o << ",\"row_mask\":{\"src_col\":" << s.rm_off << ",\"cmp\":" << json_f32(s.rm_cmp) << ",\"clip\":" << json_f32(s.rm_clip) << "}";
     if (s.kind == StepKind::RowReduce) {
       static const char *ops[] = {"Sum", "Mean", "Max", "Min", "Prod", "L1", "L2", "SumSquare", "LogSum", "LogSumExp"};
       o << ",\"op\":\"" << ops[s.out_mode] << "\",\"E\":" << s.K << ",\"T\":" << s.rep;
@@ -5241,6 +5604,9 @@ std::string Plan::describe_json() const {
     if (s.kind == StepKind::Attention)
       o << ",\"T\":" << s.attn_T << ",\"heads\":" << s.attn_heads << ",\"dh\":" << s.attn_dh << ",\"scale\":" << double(s.attn_scale) << ",\"mask\":" << (s.cst.empty() ? "false" : "true")
         << ",\"packed_qkv\":" << (s.in0 == s.in1 && s.in1 == s.in2 ? "true" : "false");
+    if (s.kind == StepKind::Attention && s.in3 >= 0)
+      o << ",\"row_mask\":{\"src_col\":" << s.rm_off << ",\"cmp\":" << json_f32(s.rm_cmp) << ",\"fill\":" << json_f32(s.rm_fill) << ",\"mode\":\""
+        << (s.rm_mode == kRowMaskAdd ? "add" : "replace") << "\",\"excluding\":" << (s.rm_excl ? "true" : "false") << "}";
     if (s.kind == StepKind::Conv2d) o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"k\":[" << s.kh << "," << s.kw << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
     if (s.kind == StepKind::ConvTranspose2d) {
       const DeconvPack &q = *s.deconv;

@@ -157,6 +157,15 @@ struct Step {
   // Attention: Q = in0, K = in1, V = in2 (the same buffer three times when the projections are merged), each [rows, T, ld] with the head
   // block of head g at columns off + g * dh of a step; mask (cst): [T, T] added to the scaled scores, -inf = no weight, empty = none
   int in2 = -1;
+  // A row mask (Attention, MeanTime; INTEGRATION.md 2.6 "Padded sequences"): in3 = the buffer that holds the mask's source (the model input;
+  // -1: none), step t of a row is kept iff in3[r, rm_off + t] (rm_int: an integer graph input, truncated toward zero) != rm_cmp.
+  // Attention: rm_fill reaches a masked key's score by rm_mode (RowMaskMode, host/attention.hpp); rm_excl: the fill excludes the key.
+  // MeanTime: the sum over the kept steps is divided by max(count, rm_clip)
+  int in3 = -1;
+  int64_t rm_off = 0;
+  float rm_cmp = 0.f, rm_fill = 0.f, rm_clip = 0.f;
+  int rm_mode = 0;
+  bool rm_excl = false, rm_int = false;
   int64_t attn_T = 0, attn_heads = 0, attn_dh = 0, attn_ld[3] = {0, 0, 0}, attn_off[3] = {0, 0, 0};
   float attn_scale = 1.f, ln_eps = 1e-5f;
   // FakeQuant: qx.  QDense: qx = how the f32 input is quantised, qy = how the result is (off: the step returns `real`, f32);

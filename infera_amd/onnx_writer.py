@@ -1020,11 +1020,14 @@ def from_torch_encoder(encoder, T: int, head=None, causal: bool = False) -> dict
 
 def attention_nodes(nodes: list, inits: list, p: str, q: str, k: str, v: str, x_for_shape: str, T: int, E: int, h: int, scale: str = "scores_div",
                     k_transpose: str = "direct", mask=None, shape: str = "const", scale_value: float | None = None, softmax_axis: int = -1,
-                    mask_left: bool = False) -> str:
+                    mask_left: bool = False, row_mask: dict | None = None) -> str:
     """Appends the batch-first self-attention sub-graph over q, k, v [N, T, E] (names) and returns the name of its [N, T, E] result.
     scale: "scores_div" (Div by sqrt(dh)), "scores_mul", "q" (Mul of Q) or "sqrt_both" (Q and K^T by sqrt(scale) each, what
     scaled_dot_product_attention exports); k_transpose: "direct" (0,2,3,1) or "two_step" ((0,2,1,3) then (0,1,3,2)); mask: None or an f32
-    array added to the scores (mask_left: as the Add's first operand); shape: "const" targets or the exporter's Shape -> Gather -> Unsqueeze -> Concat sub-graph."""
+    array added to the scores (mask_left: as the Add's first operand); shape: "const" targets or the exporter's Shape -> Gather -> Unsqueeze -> Concat sub-graph.
+    row_mask: None or a per-row key mask, dict(src=<name of an [N, T] value>, form="add" | "replace", fill=<negative float>, from_ids=None | pad_id,
+    unsqueeze="one" | "two" | "reshape", expand="none" | "const" | "shape", value=None | <what row_mask_value() returned>); see row_mask_value and
+    row_mask_on_scores (mask_left: the mask term as the Add's first operand)."""
     dh = E // h
     sv = (1.0 / math.sqrt(dh)) if scale_value is None else scale_value
     i64 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.int64)))  # noqa: E731
@@ -1072,6 +1075,8 @@ def attention_nodes(nodes: list, inits: list, p: str, q: str, k: str, v: str, x_
         f32(p + "mask", mask)
         nodes.append(node("Add", [p + "mask", cur] if mask_left else [cur, p + "mask"], [p + "s2"], name=p + "mask_add"))
         cur = p + "s2"
+    if row_mask is not None:
+        cur = row_mask_on_scores(nodes, inits, p, cur, T, h, row_mask, mask_left=mask_left)
     nodes += [node("Softmax", [cur], [p + "p"], [attr_i("axis", softmax_axis)], name=p + "softmax"),
               node("MatMul", [p + "p", heads["v"]], [p + "o4"], name=p + "pv"),
               node("Transpose", [p + "o4"], [p + "ot"], [attr_ints("perm", [0, 2, 1, 3])], name=p + "tr_o"),
@@ -1079,15 +1084,114 @@ def attention_nodes(nodes: list, inits: list, p: str, q: str, k: str, v: str, x_
     return p + "o"
 
 
+def row_mask_value(nodes: list, inits: list, p: str, T: int, row_mask: dict) -> str:
+    """Appends the part of a row mask's sub-graph that does not depend on the layer and returns its [N, 1, 1, T] value.
+    The source row_mask["src"] is an [N, T] graph input: a 0 / 1 mask (HF's attention_mask), or with from_ids = pad_id the token ids.
+    form "add" (BERT): kept = src or Not(Equal(ids, pad)) -> Unsqueeze to [N, 1, 1, T] ("one" node, "two" nodes or a "reshape") -> Cast(FLOAT)
+        -> Sub(1, .) -> Mul(., fill): the float term added to the scores.
+    form "replace" (DistilBERT's masked_fill): masked = Equal(src, 0) or Equal(ids, pad) -> Reshape / Unsqueeze to [N, 1, 1, T]: the condition."""
+    form, pad, how = row_mask.get("form", "add"), row_mask.get("from_ids"), row_mask.get("unsqueeze", "one")
+    src = row_mask["src"]
+    i64 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.int64)))  # noqa: E731
+    i64(p + "rm_c", 0 if pad is None else pad)
+
+    def lift(v):
+        if how == "reshape":
+            i64(p + "rm_s4", [-1, 1, 1, T])
+            nodes.append(node("Reshape", [v, p + "rm_s4"], [p + "rm_4"], name=p + "rm_reshape"))
+        elif how == "two":
+            i64(p + "rm_a1", [1]); i64(p + "rm_a2", [2])  # noqa: E702
+            nodes.extend([node("Unsqueeze", [v, p + "rm_a1"], [p + "rm_3"], name=p + "rm_unsq1"),
+                          node("Unsqueeze", [p + "rm_3", p + "rm_a2"], [p + "rm_4"], name=p + "rm_unsq2")])
+        else:
+            i64(p + "rm_a12", [1, 2])
+            nodes.append(node("Unsqueeze", [v, p + "rm_a12"], [p + "rm_4"], name=p + "rm_unsq"))
+        return p + "rm_4"
+
+    if form == "replace":
+        nodes.append(node("Equal", [src, p + "rm_c"], [p + "rm_eq"], name=p + "rm_equal"))
+        return lift(p + "rm_eq")
+    kept = src
+    if pad is not None:
+        nodes += [node("Equal", [src, p + "rm_c"], [p + "rm_eq"], name=p + "rm_equal"), node("Not", [p + "rm_eq"], [p + "rm_keep"], name=p + "rm_not")]
+        kept = p + "rm_keep"
+    inits.append(tensor(p + "rm_one", np.asarray(1.0, dtype=np.float32)))
+    inits.append(tensor(p + "rm_fill", np.asarray(row_mask["fill"], dtype=np.float32)))
+    nodes += [node("Cast", [lift(kept)], [p + "rm_f"], [attr_i("to", FLOAT)], name=p + "rm_cast"),
+              node("Sub", [p + "rm_one", p + "rm_f"], [p + "rm_inv"], name=p + "rm_sub"),
+              node("Mul", [p + "rm_inv", p + "rm_fill"], [p + "rm_term"], name=p + "rm_mul")]
+    return p + "rm_term"
+
+
+def row_mask_on_scores(nodes: list, inits: list, p: str, scores: str, T: int, h: int, row_mask: dict, mask_left: bool = False) -> str:
+    """Applies a row mask (row_mask_value; built here unless row_mask["value"] names one built before, the way exporters compute it once for
+    every layer) to the scores [N, h, T, T] and returns the masked scores.  "add": Add(scores, term), node '<p>mask_add'; "replace": the
+    condition, through an optional Expand to the scores' shape (expand "const": the target [1, h, T, T]; "shape": Shape(scores)), into
+    Where(condition, fill, scores), node '<p>mask_where'."""
+    val = row_mask.get("value") or row_mask_value(nodes, inits, p, T, row_mask)
+    if row_mask.get("form", "add") == "add":
+        nodes.append(node("Add", [val, scores] if mask_left else [scores, val], [p + "s3"], name=p + "mask_add"))
+        return p + "s3"
+    expand = row_mask.get("expand", "none")
+    if expand == "const":
+        inits.append(tensor(p + "rm_tgt", np.asarray([1, h, T, T], dtype=np.int64)))
+        nodes.append(node("Expand", [val, p + "rm_tgt"], [p + "rm_x"], name=p + "rm_expand"))
+        val = p + "rm_x"
+    elif expand == "shape":
+        nodes += [node("Shape", [scores], [p + "rm_tgt"], name=p + "rm_shape"), node("Expand", [val, p + "rm_tgt"], [p + "rm_x"], name=p + "rm_expand")]
+        val = p + "rm_x"
+    inits.append(tensor(p + "rm_wfill", np.asarray(row_mask["fill"], dtype=np.float32)))
+    nodes.append(node("Where", [val, p + "rm_wfill", scores], [p + "s3"], name=p + "mask_where"))
+    return p + "s3"
+
+
+def masked_mean_nodes(nodes: list, inits: list, p: str, x: str, src: str, T: int, E: int, from_ids=None, expand: str = "none", count: str = "m",
+                      clip: float = 1e-9) -> str:
+    """Appends the masked mean over time of x [N, T, E] (the sentence-embedding head) and returns its [N, E] result, node '<p>div':
+    kept = src (a 0 / 1 mask [N, T]) or Not(Equal(ids, from_ids)); m = Cast(FLOAT)(Unsqueeze(kept, -1) [-> Expand to x's shape: "const" target
+    [1, T, E] or "shape": Shape(x)]); Mul(x, m) -> ReduceSum(axis 1, keepdims 0); the count: ReduceSum(m, axis 1) (count "m") or
+    ReduceSum(Cast(FLOAT)(kept), axis 1, keepdims 1) (count "mask") -> Clip(min = clip); Div."""
+    i64 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.int64)))  # noqa: E731
+    kept = src
+    if from_ids is not None:
+        i64(p + "pad", from_ids)
+        nodes += [node("Equal", [src, p + "pad"], [p + "eq"], name=p + "equal"), node("Not", [p + "eq"], [p + "keep"], name=p + "not")]
+        kept = p + "keep"
+    i64(p + "last", [-1]); i64(p + "t_axis", [1])  # noqa: E702
+    nodes.append(node("Unsqueeze", [kept, p + "last"], [p + "k3"], name=p + "unsq"))
+    cur = p + "k3"
+    if expand == "const":
+        i64(p + "tgt", [1, T, E])
+        nodes.append(node("Expand", [cur, p + "tgt"], [p + "kx"], name=p + "expand"))
+        cur = p + "kx"
+    elif expand == "shape":
+        nodes += [node("Shape", [x], [p + "tgt"], name=p + "shape"), node("Expand", [cur, p + "tgt"], [p + "kx"], name=p + "expand")]
+        cur = p + "kx"
+    nodes += [node("Cast", [cur], [p + "m"], [attr_i("to", FLOAT)], name=p + "cast"), node("Mul", [x, p + "m"], [p + "xm"], name=p + "mul"),
+              node("ReduceSum", [p + "xm", p + "t_axis"], [p + "sum"], [attr_i("keepdims", 0)], name=p + "sum_x")]
+    if count == "m":
+        nodes.append(node("ReduceSum", [p + "m", p + "t_axis"], [p + "cnt"], [attr_i("keepdims", 0)], name=p + "sum_m"))
+    else:
+        nodes += [node("Cast", [kept], [p + "kf"], [attr_i("to", FLOAT)], name=p + "cast_mask"),
+                  node("ReduceSum", [p + "kf", p + "t_axis"], [p + "cnt"], [attr_i("keepdims", 1)], name=p + "sum_m")]
+    inits.append(tensor(p + "lo", np.asarray(clip, dtype=np.float32)))
+    nodes += [node("Clip", [p + "cnt", p + "lo"], [p + "den"], name=p + "clip"), node("Div", [p + "sum", p + "den"], [p + "out"], name=p + "div")]
+    return p + "out"
+
+
 def causal_mask(T: int, rank: int = 2) -> np.ndarray:
     mk = np.triu(np.full((T, T), -np.inf, dtype=np.float32), 1)
     return mk.reshape((1,) * (rank - 2) + (T, T))
 
 
-def attention_only(T: int, E: int, h: int, form: str = "packed", **kw) -> bytes:
+def attention_only(T: int, E: int, h: int, form: str = "packed", row_mask: dict | None = None, mask_type: int = INT64, **kw) -> bytes:
     """Self-attention alone over a flat input: form "packed": X [N, T*3E] -> Reshape [N, T, 3E] -> Split on the last axis -> q, k, v;
-    "three": inputs Q, K, V [N, T*E] each (the call's columns in that order), each reshaped to [N, T, E].  Output [N, T, E]."""
+    "three": inputs Q, K, V [N, T*E] each (the call's columns in that order), each reshaped to [N, T, E].  Output [N, T, E].
+    row_mask (attention_nodes; its src defaults to "M"): one more input M [N, T] (mask_type: INT64, INT32 or FLOAT) behind the others, the
+    0 / 1 mask or, with from_ids, the token ids."""
     nodes, inits = [], []
+    if row_mask is not None:
+        kw["row_mask"] = dict(row_mask, src=row_mask.get("src", "M"))
     if form == "packed":
         inits += [tensor("x_shape", np.asarray([-1, T, 3 * E], dtype=np.int64)), tensor("sp", np.asarray([E, E, E], dtype=np.int64))]
         nodes += [node("Reshape", ["X", "x_shape"], ["X3"]), node("Split", ["X3", "sp"], ["q", "k", "v"], [attr_i("axis", 2)], name="split_qkv")]
@@ -1099,8 +1203,36 @@ def attention_only(T: int, E: int, h: int, form: str = "packed", **kw) -> bytes:
             nodes.append(node("Reshape", [nm.upper(), "x_shape"], [nm]))
         ins = [value_info(nm, ["N", T * E]) for nm in "QKV"]
         xs = "q"
+    if row_mask is not None:
+        ins.append(value_info("M", ["N", T], mask_type))
     out = attention_nodes(nodes, inits, "a_", "q", "k", "v", xs, T, E, h, **kw)
     return model("attention", nodes, inits, ins, [value_info(out, ["N", T, E])], opset=20)
+
+
+def masked_attention_reference(q, k, v, h: int, keep, fill: float, mode: str = "add", scale: float | None = None, dtype=np.float64) -> np.ndarray:
+    """numpy restatement of attention under a per-row key mask keep [N, T] (bool).  float64 (the reference) with the two f32 roundings of the
+    operator's definition: the score is fl32(scale . q . k); a masked key's is fl32(that + fill) ("add") or fill ("replace").  float32: the
+    same formula evaluated in that format throughout."""
+    q, k, v = (np.asarray(a, dtype=dtype) for a in (q, k, v))
+    N, T, E = q.shape
+    dh = E // h
+    sp = lambda a: a.reshape(N, T, h, dh).transpose(0, 2, 1, 3)  # noqa: E731
+    keep = np.asarray(keep, dtype=bool).reshape(N, 1, 1, T)
+    r32 = (lambda a: a.astype(np.float32).astype(np.float64)) if dtype == np.float64 else (lambda a: a)
+    b = dtype(np.float32(fill))
+    with np.errstate(all="ignore"):
+        s = r32(sp(q) @ sp(k).transpose(0, 1, 3, 2) * dtype((1.0 / math.sqrt(dh)) if scale is None else scale))
+        s = np.where(keep, s, r32(s + b) if mode == "add" else np.full_like(s, b))
+        s = s - s.max(axis=-1, keepdims=True)
+        pr = np.exp(s)
+        pr /= pr.sum(axis=-1, keepdims=True)
+        return (pr @ sp(v)).transpose(0, 2, 1, 3).reshape(N, T, E)
+
+
+def masked_mean_reference(x, keep, clip: float = 1e-9) -> np.ndarray:
+    """[N, T, E], keep [N, T] -> [N, E] in float64: the sum over the kept steps / max(count, clip)"""
+    x, keep = np.asarray(x, dtype=np.float64), np.asarray(keep, dtype=bool)
+    return np.where(keep[:, :, None], x, 0.0).sum(axis=1) / np.maximum(keep.sum(axis=1, keepdims=True).astype(np.float64), np.float64(np.float32(clip)))
 
 
 def attention_reference(q, k, v, h: int, scale: float | None = None, mask=None) -> np.ndarray:
@@ -1188,14 +1320,17 @@ def layernorm_nodes(nodes: list, inits: list, x: str, g, b, out: str, name: str,
 
 def transformer_from_spec(spec: dict, flat: bool = True, qkv: str = "separate", scale: str = "scores_div", k_transpose: str = "direct",
                           mask_rank: int = 2, shape: str = "const", gelu: str = "op", heads: Sequence[str] = ("mean",), keepdims: int = 0,
-                          opset: int = 20, layernorm: str = "op", pos_rank: int = 3, front: tuple | None = None) -> bytes:
+                          opset: int = 20, layernorm: str = "op", pos_rank: int = 3, front: tuple | None = None, row_mask: dict | None = None,
+                          mean_mask: dict | None = None) -> bytes:
     """The ONNX model of a transformer_spec() / from_torch_encoder() dict, input X [N, T, F] (flat: [N, T*F] -> Reshape).
     qkv: "separate" (three MatMul + Add), "packed_split" / "packed_slice" (one [E, 3E] projection, then Split / three Slices on the last axis);
     scale, k_transpose, shape: see attention_nodes; a causal spec adds the [T, T] mask (mask_rank 4: [1, 1, T, T]); gelu: "op" (opset 20) or
     "decomposed" (Div(sqrt 2) -> Erf -> Add(1) -> Mul(x) -> Mul(0.5)).  heads: the graph outputs, any of "mean" (mean over time -> Linear,
     output "pooled"), "first" / "last" (that step -> Linear), "seq" (the full sequence [N, T, E] -> per-step Linear); without a head matrix
     in the spec the encoder output itself is served.  layernorm: see layernorm_nodes ("op" is the default); pos_rank: the positional constant as [1, T, E] or [T, E].
-    front: (nodes, initializers, name of the [N, T, E] value they compute, graph inputs) -- the encoder then starts from that value (vit_from_spec)."""
+    front: (nodes, initializers, name of the [N, T, E] value they compute, graph inputs) -- the encoder then starts from that value (vit_from_spec).
+    row_mask: every layer's attention under that per-row key mask (attention_nodes); its layer-independent part is computed once, the way
+    exporters write it.  mean_mask: the keyword arguments of masked_mean_nodes behind x, for the head "masked_mean" (output "sentence")."""
     T, F, E, h, ff = spec["T"], spec["F"], spec["E"], spec["h"], spec["ff"]
     nodes, inits = (list(front[0]), list(front[1])) if front else ([], [])
     i64 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.int64)))  # noqa: E731
@@ -1223,6 +1358,9 @@ def transformer_from_spec(spec: dict, flat: bool = True, qkv: str = "separate", 
         nodes.append(node("Add", [x, "pos"], ["emb_pos"], name="pos_add"))
         x = "emb_pos"
     mask = causal_mask(T, mask_rank) if spec.get("causal") else None
+    attn_kw = {}
+    if row_mask is not None:
+        attn_kw["row_mask"] = dict(row_mask, value=row_mask_value(nodes, inits, "rm_", T, row_mask))
     for i, L in enumerate(spec["layers"]):
         p = f"l{i}_"
         a_in = layer_norm(x, L["g1"], L["be1"], p + "n1", p + "norm1") if spec["norm_first"] else x
@@ -1239,7 +1377,7 @@ def transformer_from_spec(spec: dict, flat: bool = True, qkv: str = "separate", 
                 for j, nm in enumerate((q, k, v)):
                     i64(nm + "_b", [j * E]); i64(nm + "_e", [(j + 1) * E])  # noqa: E702
                     nodes.append(node("Slice", [p + "qkv", nm + "_b", nm + "_e", p + "ax2"], [nm], name=nm + "_slice"))
-        a = attention_nodes(nodes, inits, p + "a_", q, k, v, a_in, T, E, h, scale=scale, k_transpose=k_transpose, mask=mask, shape=shape)
+        a = attention_nodes(nodes, inits, p + "a_", q, k, v, a_in, T, E, h, scale=scale, k_transpose=k_transpose, mask=mask, shape=shape, **attn_kw)
         a = linear(a, L["Wo"], L["bo"], p + "ao", p + "out_proj")
         nodes.append(node("Add", [x, a], [p + "r1"], name=p + "res1"))
         x = p + "r1"
@@ -1267,6 +1405,8 @@ def transformer_from_spec(spec: dict, flat: bool = True, qkv: str = "separate", 
             i64("t_axis", [1])
             nodes.append(node("ReduceMean", [x, "t_axis"], ["mean_t"], [attr_i("keepdims", keepdims)], name="mean_over_time"))
             v, dims, name = "mean_t", (["N", 1, E] if keepdims else ["N", E]), "pooled"
+        elif hd == "masked_mean":
+            v, dims, name = masked_mean_nodes(nodes, inits, "mm_", x, T=T, E=E, **mean_mask), ["N", E], "sentence"
         elif hd in ("first", "last"):
             i64(hd + "_i", 0 if hd == "first" else -1)
             nodes.append(node("Gather", [x, hd + "_i"], [hd + "_t"], [attr_i("axis", 1)], name=hd + "_step"))
@@ -3902,3 +4042,89 @@ def embedding_inputs(spec: dict, rows: int, seed: int = 0, spelling: str = "a"):
     x_num = rng.standard_normal((rows, spec["numeric"])).astype(np.float32)
     m = 0 if spelling == "c" else spec["numeric"]
     return x_cat, x_num, np.ascontiguousarray(np.concatenate([x_cat.astype(np.float32), x_num[:, :m]], axis=1))
+
+
+# ------------------------------------------------------------------------------------------
+# Text encoders over padded token sequences (Embed window, per-row key masks, masked mean)
+# ------------------------------------------------------------------------------------------
+
+def text_encoder_spec(T: int = 16, V: int = 50, E: int = 32, h: int = 4, ff: int = 64, layers: int = 2, outputs: int = 3, pad_id: int = 0,
+                      weight_scale: float = 1.0, seed: int = 91) -> dict:
+    """Seeded BERT-shaped encoder: a token table [V, E] (N(0, 1) like nn.Embedding), a position table [T, E], LayerNorm, `layers` post-norm
+    encoder layers (transformer_spec: its 'enc' entry, without input projection and positional constant of its own) and one Linear
+    E -> outputs behind each head."""
+    rng = np.random.default_rng(seed)
+    enc = transformer_spec(T=T, F=E, E=E, h=h, ff=ff, layers=layers, norm_first=False, outputs=outputs, weight_scale=weight_scale, seed=seed + 1)
+    enc["Win"] = enc["bin"] = enc["pos"] = None
+    f32 = lambda a: np.asarray(a, dtype=np.float32)  # noqa: E731
+    return {"T": T, "V": V, "E": E, "pad_id": int(pad_id), "table": f32(rng.standard_normal((V, E))), "pos": f32(0.5 * rng.standard_normal((T, E))),
+            "emb_ln": (f32(1.0 + 0.1 * rng.standard_normal(E)), f32(0.1 * rng.standard_normal(E))), "enc": enc}
+
+
+def text_encoder_from_spec(spec: dict, form: str = "add", fill: float = float(np.finfo(np.float32).min), from_ids: bool = False,
+                           heads: Sequence[str] = ("first", "masked_mean"), int_type: int = INT64, **mask_kw) -> bytes:
+    """The ONNX model of a text_encoder_spec(): int64 input_ids [N, T] and, unless from_ids, attention_mask [N, T] (a call's columns in that
+    order) -> Gather(table, ids) (node 'emb') -> Add(position table [T, E]) -> LayerNorm -> the encoder layers, every attention under the
+    row mask (form, fill, from_ids: the mask is ids != pad_id written in the graph; **mask_kw: unsqueeze, expand) -> heads "first" (output
+    'first') and "masked_mean" (output 'sentence'), each through the head Linear."""
+    T, E = spec["T"], spec["E"]
+    nodes = [node("Gather", ["table", "input_ids"], ["tokens"], name="emb"), node("Add", ["tokens", "pos_table"], ["tok_pos"], name="pos_add")]
+    inits = [tensor("table", spec["table"]), tensor("pos_table", spec["pos"])]
+    x = layernorm_nodes(nodes, inits, "tok_pos", spec["emb_ln"][0], spec["emb_ln"][1], "emb_norm", "emb_ln", spec["enc"]["eps"])
+    inputs = [value_info("input_ids", ["N", T], int_type)] + ([] if from_ids else [value_info("attention_mask", ["N", T], int_type)])
+    src = "input_ids" if from_ids else "attention_mask"
+    pad = spec["pad_id"] if from_ids else None
+    rm = dict(src=src, form=form, fill=fill, from_ids=pad, **mask_kw)
+    return transformer_from_spec(spec["enc"], flat=False, heads=heads, front=(nodes, inits, x, inputs), row_mask=rm,
+                                 mean_mask=dict(src=src, from_ids=pad))
+
+
+def text_encoder_reference(spec: dict, ids, keep, form: str = "add", fill: float = float(np.finfo(np.float32).min),
+                           heads: Sequence[str] = ("first", "masked_mean"), dtype=np.float64) -> dict:
+    """numpy restatement of text_encoder_from_spec in `dtype` (float64: the reference; float32: what that format itself costs): ids [N, T]
+    integers, keep [N, T] bool -> {output name: array}."""
+    from math import erf
+    enc, T, E = spec["enc"], spec["T"], spec["E"]
+    fx = lambda a: np.asarray(a, dtype=dtype)  # noqa: E731
+    keep = np.asarray(keep, dtype=bool)
+    ln = lambda a, g, b: fx(layernorm_reference(a, g, b, enc["eps"])) if dtype == np.float64 else _layernorm32(a, g, b, enc["eps"])  # noqa: E731
+    x = ln(fx(spec["table"])[np.asarray(ids, dtype=np.int64)] + fx(spec["pos"]).reshape(1, T, E), spec["emb_ln"][0], spec["emb_ln"][1])
+    act = (lambda a: np.maximum(a, 0)) if enc["act"] == "Relu" else (lambda a: fx(0.5 * a * (1.0 + np.vectorize(erf)(a / math.sqrt(2.0)))))
+    for L in enc["layers"]:
+        q, k, v = (x @ fx(L["W" + c]) + fx(L["b" + c]) for c in "qkv")
+        a = masked_attention_reference(q, k, v, enc["h"], keep, fill, form, dtype=dtype)
+        x = ln(x + (a @ fx(L["Wo"]) + fx(L["bo"])), L["g1"], L["be1"])
+        x = ln(x + (act(x @ fx(L["W1"]) + fx(L["b1"])) @ fx(L["W2"]) + fx(L["b2"])), L["g2"], L["be2"])
+    out = {}
+    for hd in heads:
+        v = x[:, 0] if hd == "first" else fx(masked_mean_reference(x, keep)) if dtype == np.float64 else _masked_mean32(x, keep)
+        out["first" if hd == "first" else "sentence"] = v @ fx(enc["head_W"]) + fx(enc["head_b"])
+    return out
+
+
+def _layernorm32(x, g, b, eps):
+    x = np.asarray(x, np.float32)
+    n = np.float32(x.shape[-1])
+    d = x - x.sum(axis=-1, keepdims=True, dtype=np.float32) / n
+    var = (d * d).sum(axis=-1, keepdims=True, dtype=np.float32) / n
+    return d / np.sqrt(var + np.float32(eps)) * np.asarray(g, np.float32) + np.asarray(b, np.float32)
+
+
+def _masked_mean32(x, keep, clip: float = 1e-9):
+    s = np.where(keep[:, :, None], np.asarray(x, np.float32), np.float32(0)).sum(axis=1, dtype=np.float32)
+    return s / np.maximum(keep.sum(axis=1, keepdims=True).astype(np.float32), np.float32(clip))
+
+
+def text_encoder_inputs(spec: dict, lengths, seed: int = 0, left: bool = False):
+    """(ids [N, T] int64 with pad_id outside each row's length and never inside it, keep [N, T] bool, the f32 table of a call with a mask
+    input [N, 2T]: ids beside the 0 / 1 mask, the one of a from_ids model [N, T]); left: padded on the left."""
+    T, V, pad = spec["T"], spec["V"], spec["pad_id"]
+    rng = np.random.default_rng(seed)
+    lengths = np.asarray(lengths, dtype=np.int64)
+    pos = np.arange(T)[None, :]
+    keep = pos >= (T - lengths)[:, None] if left else pos < lengths[:, None]
+    ids = rng.integers(0, V - 1, (len(lengths), T))
+    ids = np.where(ids >= pad, ids + 1, ids)  # (every value but pad_id)
+    ids = np.where(keep, ids, pad).astype(np.int64)
+    both = np.ascontiguousarray(np.concatenate([ids, keep.astype(np.int64)], axis=1).astype(np.float32))
+    return ids, keep, both, np.ascontiguousarray(ids.astype(np.float32))
