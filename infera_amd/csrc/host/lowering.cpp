@@ -143,6 +143,87 @@ Val const_i64(std::vector<int64_t> i, std::vector<int64_t> dims) {
   return const_val(std::move(t));
 }
 
+// What the matchers that run before the walk (Lowerer::find_*) read of the graph: built once, for the served output, and never changed.
+// Only live nodes are indexed.  (A live node's inputs have live producers and ONNX names are assigned once, so a lookup that starts at a
+// live node finds what a map over all nodes would.)
+struct GraphIndex {
+  const onnx::Model &m;
+  std::vector<char> live;  // node index -> it feeds the served output
+  std::map<std::string, size_t> producer_of;
+  std::map<std::string, std::vector<size_t>> consumers_of;  // live consumers of every value, one entry per input that reads it
+  std::set<std::string> row_data;    // values that hold row data: computed from a graph input (Shape's result is not); everything else folds to a constant
+  std::set<std::string> graph_outs;  // the names of all graph outputs, served or not
+
+  GraphIndex(const onnx::Model &model, const std::string &served) : m(model), live(model.nodes.size(), 0) {
+    const size_t N = m.nodes.size();
+    {
+      // Only one output is served (engine.rs:146-149): nodes that do not feed it are dead -- a second
+      // output (e.g. the probabilities next to a label) must neither cost kernels nor block loading.
+      std::map<std::string, size_t> any_producer;
+      for (size_t i = 0; i < N; i++)
+        for (const auto &o : m.nodes[i].outputs) any_producer[o] = i;
+      std::vector<std::string> work{served};
+      while (!work.empty()) {
+        const std::string v = work.back();
+        work.pop_back();
+        auto it = any_producer.find(v);
+        if (it == any_producer.end() || live[it->second]) continue;
+        live[it->second] = 1;
+        for (const auto &i : m.nodes[it->second].inputs) work.push_back(i);
+      }
+    }
+    for (size_t i = 0; i < N; i++) {
+      if (!live[i]) continue;
+      for (const auto &o : m.nodes[i].outputs) producer_of[o] = i;
+      for (const auto &in : m.nodes[i].inputs) consumers_of[in].push_back(i);
+    }
+    for (const auto &o : m.outputs) graph_outs.insert(o.name);
+    for (const auto &v : m.inputs) row_data.insert(v.name);
+    for (size_t i = 0; i < N; i++) {
+      if (!live[i] || m.nodes[i].op == "Shape") continue;
+      bool any = false;
+      for (const auto &in : m.nodes[i].inputs) any = any || row_data.count(in);
+      if (any)
+        for (const auto &o : m.nodes[i].outputs) row_data.insert(o);
+    }
+  }
+
+  // the node that computes `v` (null: a graph input, an initializer, or nothing)
+  const NodeDef *producer(const std::string &v, size_t *idx = nullptr) const {
+    auto pi = producer_of.find(v);
+    if (pi == producer_of.end()) return nullptr;
+    if (idx) *idx = pi->second;
+    return &m.nodes[pi->second];
+  }
+  // the node that alone reads `v` (null: several readers, none, or a graph output); allow_repeat: it may read `v` twice, as in Mul(d, d)
+  const NodeDef *sole_reader(const std::string &v, bool allow_repeat) const {
+    auto it = consumers_of.find(v);
+    if (it == consumers_of.end() || it->second.empty() || graph_outs.count(v)) return nullptr;
+    if (!allow_repeat && it->second.size() != 1) return nullptr;
+    for (size_t c : it->second)
+      if (c != it->second[0]) return nullptr;
+    return &m.nodes[it->second[0]];
+  }
+  static bool std_dom(const NodeDef &n) { return n.domain.empty() || n.domain == "ai.onnx"; }
+  // A constant known before the walk: an initializer, or the result of a Constant node -- the tensor of its `value`, or the node
+  // itself where the value stands in another attribute (value_int, value_float, value_ints).  Neither: `v` is no such constant.
+  struct Const {
+    std::shared_ptr<TensorData> t;
+    const NodeDef *node = nullptr;
+    explicit operator bool() const { return t || node; }
+  };
+  Const constant(const std::string &v) const {
+    Const c;
+    if (auto ci = m.initializers.find(v); ci != m.initializers.end()) {
+      c.t = ci->second;
+    } else if (const NodeDef *p = producer(v); p && p->op == "Constant") {
+      if (auto *a = p->attr("value"); a && a->t) c.t = a->t;
+      else c.node = p;
+    }
+    return c;
+  }
+};
+
 struct Lowerer {
   const onnx::Model &m;
   Plan plan;
@@ -183,6 +264,7 @@ struct Lowerer {
     }
   }
   size_t out_index = 0;
+  std::unique_ptr<const GraphIndex> graph;  // the graph as the served output sees it (run)
 
   int new_buf(const std::vector<int64_t> &shape) {
     // [N,C,L] tensors (1-D convolutional nets) are laid out and scheduled as [N,C,1,L]; values keep their 3-D shape
@@ -1816,14 +1898,14 @@ struct Lowerer {
     size_t inorm = 0, back = 0;
   };
   std::map<size_t, GnMatch> gn_at;  // index of the first Reshape -> the chain behind it
-  void find_group_norms(const std::vector<char> &live) {
+  void find_group_norms() {
     for (size_t i = 0; i < m.nodes.size(); i++) {
       const NodeDef &r = m.nodes[i];
-      if (!live[i] || absorbed[i] || r.op != "Reshape" || r.inputs.size() != 2 || r.outputs.empty()) continue;
-      const NodeDef *in = only_reader(r.outputs[0]);
-      if (!in || in->op != "InstanceNormalization" || in->inputs.size() != 3 || in->inputs[0] != r.outputs[0] || consumers_of[r.outputs[0]].size() != 1) continue;
-      const NodeDef *back = only_reader(in->outputs[0]);
-      if (!back || back->op != "Reshape" || back->inputs.size() != 2 || back->inputs[0] != in->outputs[0] || consumers_of[in->outputs[0]].size() != 1) continue;
+      if (!graph->live[i] || absorbed[i] || r.op != "Reshape" || r.inputs.size() != 2 || r.outputs.empty()) continue;
+      const NodeDef *in = graph->sole_reader(r.outputs[0], false);
+      if (!in || in->op != "InstanceNormalization" || in->inputs.size() != 3 || in->inputs[0] != r.outputs[0]) continue;
+      const NodeDef *back = graph->sole_reader(in->outputs[0], false);
+      if (!back || back->op != "Reshape" || back->inputs.size() != 2 || back->inputs[0] != in->outputs[0]) continue;
       gn_at[i] = GnMatch{size_t(in - m.nodes.data()), size_t(back - m.nodes.data())};
     }
   }
@@ -1859,21 +1941,21 @@ struct Lowerer {
       for (size_t i = 1; i < b.size(); i++)
         if (b[i] != x.shape[i] && b[i] != 0) return false;
     } else {
-      auto pit = producer_of.find(back.inputs[1]);
-      if (pit == producer_of.end()) return false;
-      const NodeDef &sh = m.nodes[pit->second];
+      const NodeDef *shp = graph->producer(back.inputs[1]);
+      if (!shp) return false;
+      const NodeDef &sh = *shp;
       const Val *of = sh.op == "Shape" && sh.inputs.size() == 1 && sh.attrs.empty() ? find_value(sh.inputs[0]) : nullptr;
       if (!of || of->is_const || of->buf != x.buf || of->shape != x.shape) return false;
     }
     std::vector<const NodeDef *> nodes = {&inorm, &back};
     const NodeDef *last = &back;
     std::vector<float> gamma, beta;
-    if (const NodeDef *mul = only_reader(last->outputs[0]); mul && mul->op == "Mul" && consumers_of[last->outputs[0]].size() == 1)
+    if (const NodeDef *mul = graph->sole_reader(last->outputs[0], false); mul && mul->op == "Mul")
       if (const std::vector<float> *g = per_channel_const(const_operand(*mul, last->outputs[0]), x.shape)) {
         gamma = *g;
         nodes.push_back(last = mul);
       }
-    if (const NodeDef *add = only_reader(last->outputs[0]); add && add->op == "Add" && consumers_of[last->outputs[0]].size() == 1)
+    if (const NodeDef *add = graph->sole_reader(last->outputs[0], false); add && add->op == "Add")
       if (const std::vector<float> *b = per_channel_const(const_operand(*add, last->outputs[0]), x.shape)) {
         beta = *b;
         nodes.push_back(last = add);
@@ -2222,8 +2304,8 @@ struct Lowerer {
     const std::string &d = sub->outputs[0];
     for (const auto &o : m.outputs)
       if (o.name == d) return false;
-    auto dit = consumers_of.find(d);
-    if (dit == consumers_of.end()) return false;
+    auto dit = graph->consumers_of.find(d);
+    if (dit == graph->consumers_of.end()) return false;
     const std::set<size_t> readers(dit->second.begin(), dit->second.end());
     if (readers.size() != 2) return false;
     const NodeDef *sq = nullptr, *div = nullptr;
@@ -2266,8 +2348,8 @@ struct Lowerer {
   // stands for (the [N*C, H*W] matrix the operator specification gives has the same elements in the same order)
   bool token_view_of_flatten(const NodeDef &n, const Val &a) const {
     if (a.is_const || a.pv || a.ra != 0 || a.buf <= 0 || !producer.count(a.buf) || plan.buf_shape[size_t(a.buf)].size() != 4) return false;
-    auto it = consumers_of.find(n.outputs[0]);
-    if (it == consumers_of.end() || it->second.empty()) return false;
+    auto it = graph->consumers_of.find(n.outputs[0]);
+    if (it == graph->consumers_of.end() || it->second.empty()) return false;
     for (const auto &o : m.outputs)
       if (o.name == n.outputs[0]) return false;
     for (size_t c : it->second) {
@@ -2362,15 +2444,7 @@ struct Lowerer {
   // ---- the decomposed LayerNorm older exporters write, on [rows, E] (where nothing else serves it):
   //   ReduceMean(-1) -> Sub -> Pow(2) | Mul(d, d) -> ReduceMean(-1) -> Add(eps) -> Sqrt -> Div [-> Mul(gamma)] [-> Add(beta)]
   // matched forward from the first ReduceMean when it is met; the nodes behind it emit nothing and the last one's output is the step's.
-  const NodeDef *only_reader(const std::string &v) const {
-    auto it = consumers_of.find(v);
-    if (it == consumers_of.end() || it->second.empty()) return nullptr;
-    for (size_t c : it->second)
-      if (c != it->second[0]) return nullptr;
-    for (const auto &o : m.outputs)
-      if (o.name == v) return nullptr;
-    return &m.nodes[it->second[0]];
-  }
+  const NodeDef *only_reader(const std::string &v) const { return graph->sole_reader(v, true); }
   bool last_axis_mean(const NodeDef &n, int64_t rank) {
     if (n.op != "ReduceMean" || n.attr_i("keepdims", 1) == 0) return false;
     std::vector<int64_t> axes;
@@ -2398,8 +2472,8 @@ struct Lowerer {
     const std::string &d = sub->outputs[0];
     for (const auto &o : m.outputs)
       if (o.name == d) return false;
-    auto dit = consumers_of.find(d);
-    if (dit == consumers_of.end()) return false;
+    auto dit = graph->consumers_of.find(d);
+    if (dit == graph->consumers_of.end()) return false;
     const std::set<size_t> readers(dit->second.begin(), dit->second.end());
     if (readers.size() != 2) return false;
     const NodeDef *sq = nullptr, *div = nullptr;
@@ -2521,10 +2595,6 @@ struct Lowerer {
   std::map<size_t, AttnMatch> attn_at;            // anchor node index -> the pattern it closes
   std::vector<char> absorbed;                // nodes inside a recognised pattern (attention, or the decomposed LayerNorm): they emit nothing
   std::map<const NodeDef *, std::string> attn_fail;  // MatMul(activation, activation) nodes outside one: why
-  std::map<std::string, std::vector<size_t>> consumers_of;  // live consumers of every value
-  std::map<std::string, size_t> producer_of;
-
-  std::set<std::string> attn_row_data;  // values computed from a graph input (find_attention)
   struct MaskedMean {
     std::string x;  // the window [N, T, E]
     RowMask rm;
@@ -2535,16 +2605,12 @@ struct Lowerer {
 
   // a constant known before the walk (an initializer or a Constant node): its first element and its element count
   bool graph_const_scalar(const std::string &name, double *v, size_t *count = nullptr) const {
-    const TensorData *t = nullptr;
-    if (auto ci = m.initializers.find(name); ci != m.initializers.end()) {
-      t = ci->second.get();
-    } else {
-      auto pi = producer_of.find(name);
-      if (pi == producer_of.end() || m.nodes[pi->second].op != "Constant") return false;
-      const NodeDef &c = m.nodes[pi->second];
-      if (auto *a = c.attr("value"); a && a->t) t = a->t.get();
-      else if (auto *i = c.attr("value_int")) { *v = double(i->i); if (count) *count = 1; return true; }
-      else if (auto *f = c.attr("value_float")) { *v = double(f->f); if (count) *count = 1; return true; }
+    const GraphIndex::Const c = graph->constant(name);
+    const TensorData *t = c.t.get();
+    if (!t) {
+      if (!c.node) return false;
+      if (auto *i = c.node->attr("value_int")) { *v = double(i->i); if (count) *count = 1; return true; }
+      else if (auto *f = c.node->attr("value_float")) { *v = double(f->f); if (count) *count = 1; return true; }
       else return false;
     }
     const size_t n = t->count();
@@ -2555,21 +2621,20 @@ struct Lowerer {
   }
   // `v0` as a row mask; "" or why it is none
   std::string trace_row_mask(const std::string &v0, RowMask *rm) const {
-    auto std_dom = [](const NodeDef &n) { return n.domain.empty() || n.domain == "ai.onnx"; };
     std::vector<size_t> chain;
     std::string v = v0;
     for (int hop = 0; hop < 32; hop++) {
-      auto pi = producer_of.find(v);
-      if (pi == producer_of.end()) break;
+      auto pi = graph->producer_of.find(v);
+      if (pi == graph->producer_of.end()) break;
       const NodeDef &p = m.nodes[pi->second];
-      if (!std_dom(p) || p.inputs.empty()) break;
+      if (!graph->std_dom(p) || p.inputs.empty()) break;
       double c;
       if (p.op == "Unsqueeze" || p.op == "Reshape" || p.op == "Cast" || p.op == "Expand" || p.op == "Not") v = p.inputs[0];
       else if (p.op == "Equal" && p.inputs.size() == 2) v = p.inputs[graph_const_scalar(p.inputs[0], &c) ? 1 : 0];
       else break;
       chain.push_back(pi->second);
     }
-    if (auto pi = producer_of.find(v); pi != producer_of.end() && m.nodes[pi->second].op == "Transpose")
+    if (auto pi = graph->producer_of.find(v); pi != graph->producer_of.end() && m.nodes[pi->second].op == "Transpose")
       return "a time-major mask source (the Transpose '" + node_label(m.nodes[pi->second]) + "' in front of it); only a rows-first [N, T] graph input";
     EmbedCols cols;
     if (!embed_cols(v, &cols).empty() || !cols.rank2 || !cols.off.empty())
@@ -2640,13 +2705,13 @@ struct Lowerer {
           for (size_t i = 1; i < sh.size(); i++)
             if (tgt[lead + i] != 1 && tgt[lead + i] != sh[i] && sh[i] != 1) return at + "the target " + shape_str(tgt) + " does not broadcast from " + shape_str(sh);
         } else {
-          if (attn_row_data.count(p.inputs[1])) return at + "the target depends on the rows";
+          if (graph->row_data.count(p.inputs[1])) return at + "the target depends on the rows";
           std::vector<std::string> work{p.inputs[1]};
           while (!work.empty()) {  // the Shape sub-graph behind the target: it emits nothing either
             const std::string w = work.back();
             work.pop_back();
-            auto pi = producer_of.find(w);
-            if (pi == producer_of.end() || m.nodes[pi->second].op == "Constant" || std::count(rm->aux.begin(), rm->aux.end(), pi->second)) continue;
+            auto pi = graph->producer_of.find(w);
+            if (pi == graph->producer_of.end() || m.nodes[pi->second].op == "Constant" || std::count(rm->aux.begin(), rm->aux.end(), pi->second)) continue;
             rm->aux.push_back(pi->second);
             if (m.nodes[pi->second].op != "Shape")
               for (const auto &in : m.nodes[pi->second].inputs) work.push_back(in);
@@ -2661,7 +2726,7 @@ struct Lowerer {
   float row_mask_fill(const NodeDef &n, const std::string &name, bool add) {
     double b = 0;
     size_t cnt = 0;
-    if (attn_row_data.count(name) || !graph_const_scalar(name, &b, &cnt)) bad_form(n, "the fill '" + name + "' of masked keys is not a constant");
+    if (graph->row_data.count(name) || !graph_const_scalar(name, &b, &cnt)) bad_form(n, "the fill '" + name + "' of masked keys is not a constant");
     if (cnt != 1) bad_form(n, "the fill '" + name + "' of masked keys has " + std::to_string(cnt) + " elements; only one scalar");
     const float f = float(b);
     if (!(f < 0.f)) bad_form(n, "the fill of masked keys is " + std::to_string(b) + "; only a negative number or -inf");
@@ -2670,17 +2735,17 @@ struct Lowerer {
   }
   // Add(scores, other): other = Mul(Sub(1, float(mask [N,1,1,T])), b) (BERT); false: no such form
   bool match_add_row_mask(const NodeDef &add, const std::string &other, AttnMatch &am) {
-    auto pi = producer_of.find(other);
-    if (pi == producer_of.end()) return false;
+    auto pi = graph->producer_of.find(other);
+    if (pi == graph->producer_of.end()) return false;
     const NodeDef &mul = m.nodes[pi->second];
     if (mul.op != "Mul" || mul.inputs.size() != 2) return false;
     int side = -1;
     const NodeDef *sub = nullptr;
     for (int j = 0; j < 2; j++) {
-      auto si = producer_of.find(mul.inputs[size_t(j)]);
+      auto si = graph->producer_of.find(mul.inputs[size_t(j)]);
       double one = 0;
       size_t cnt = 0;
-      if (si != producer_of.end() && m.nodes[si->second].op == "Sub" && m.nodes[si->second].inputs.size() == 2 &&
+      if (si != graph->producer_of.end() && m.nodes[si->second].op == "Sub" && m.nodes[si->second].inputs.size() == 2 &&
           graph_const_scalar(m.nodes[si->second].inputs[0], &one, &cnt) && cnt == 1 && one == 1.0)
         side = j, sub = &m.nodes[si->second];
     }
@@ -2691,7 +2756,7 @@ struct Lowerer {
     rm->fill = row_mask_fill(add, mul.inputs[size_t(1 - side)], true);
     if (const std::string why = trace_row_mask(sub->inputs[1], rm.get()); !why.empty()) bad_form(add, why);
     if (rm->state == 1) bad_form(add, "(1 - Equal(source, c)) * fill puts the fill on the keys that differ from c; write Not(Equal(...)) or mask the equal ones with Where");
-    rm->nodes.push_back(producer_of.at(mul.inputs[size_t(side)]));
+    rm->nodes.push_back(graph->producer_of.at(mul.inputs[size_t(side)]));
     rm->nodes.push_back(pi->second);
     if (!am.mask.empty() || am.rm) bad_form(add, "a row mask and another mask on one attention (causal and padding masks together are not supported)");
     am.rm = std::move(rm);
@@ -2714,43 +2779,18 @@ struct Lowerer {
     am.rm = std::move(rm);
   }
 
-  void find_attention(const std::vector<char> &live) {
+  void find_attention() {
     const size_t N = m.nodes.size();
-    absorbed.assign(N, 0);
-    for (size_t i = 0; i < N; i++) {
-      if (!live[i]) continue;
-      for (const auto &o : m.nodes[i].outputs) producer_of[o] = i;
-      for (const auto &in : m.nodes[i].inputs) consumers_of[in].push_back(i);
-    }
-    std::set<std::string> graph_outs;
-    for (const auto &o : m.outputs) graph_outs.insert(o.name);
-    // values that hold row data: computed from a graph input (Shape's result is not); everything else folds to a constant
-    std::set<std::string> row_data;
-    for (const auto &v : m.inputs) row_data.insert(v.name);
-    for (size_t i = 0; i < N; i++) {
-      if (!live[i] || m.nodes[i].op == "Shape") continue;
-      bool any = false;
-      for (const auto &in : m.nodes[i].inputs) any = any || row_data.count(in);
-      if (any)
-        for (const auto &o : m.nodes[i].outputs) row_data.insert(o);
-    }
-    attn_row_data = row_data;
-    auto is_const = [&](const std::string &v) { return row_data.count(v) == 0; };
+    const std::vector<char> &live = graph->live;
+    const std::set<std::string> &graph_outs = graph->graph_outs;
+    auto is_const = [&](const std::string &v) { return graph->row_data.count(v) == 0; };
     auto perm_of = [&](const NodeDef &t) {
       std::vector<int64_t> p;
       if (auto *q = t.attr_ints("perm")) p = *q;
       return p;
     };
-    // the node that alone reads `v` (null: several readers, none, or a graph output)
-    auto sole_reader = [&](const std::string &v) -> const NodeDef * {
-      auto it = consumers_of.find(v);
-      if (it == consumers_of.end() || it->second.size() != 1 || graph_outs.count(v)) return nullptr;
-      return &m.nodes[it->second[0]];
-    };
-    auto producer = [&](const std::string &v) -> const NodeDef * {
-      auto it = producer_of.find(v);
-      return it == producer_of.end() ? nullptr : &m.nodes[it->second];
-    };
+    auto sole_reader = [&](const std::string &v) { return graph->sole_reader(v, false); };
+    auto producer = [&](const std::string &v) { return graph->producer(v); };
     const std::string generic = "MatMul of two activations outside a recognised self-attention pattern (Reshape [N,T,h,dh] -> Transpose(0,2,1,3), Q K^T, "
                                 "scale, constant mask, Softmax(-1), P V, Transpose(0,2,1,3) -> Reshape [N,T,E]); the right operand must otherwise be a constant weight matrix";
     for (size_t qi = 0; qi < N; qi++) {
@@ -2769,7 +2809,7 @@ struct Lowerer {
           const bool c0 = is_const(p->inputs[0]), c1 = is_const(p->inputs[1]);
           if (c0 == c1 || (p->op == "Div" && c0)) return v;
           am.scales.push_back({p->op == "Mul" ? '*' : '/', p->inputs[c0 ? 0 : 1]});
-          am.nodes.push_back(producer_of[v]);
+          am.nodes.push_back(graph->producer_of.at(v));
           v = p->inputs[c0 ? 1 : 0];
         }
       };
@@ -2784,12 +2824,12 @@ struct Lowerer {
                        "export batch-first projections with the head split Reshape [N,T,h,dh] -> Transpose(0,2,1,3)", false;
         if (perm == std::vector<int64_t>{2, 0, 3, 1, 4})
           return why = "the packed head split [N,T,3,h,dh] -> Transpose(2,0,3,1,4) is not supported yet; split Q, K and V on the last axis first", false;
-        am.nodes.push_back(producer_of[v]);
+        am.nodes.push_back(graph->producer_of.at(v));
         if (kt && perm == std::vector<int64_t>{0, 1, 3, 2}) {  // (0,2,1,3) first, then the last two axes
           v = strip_scales(t->inputs[0]);
           t = producer(v);
           if (!t || t->op != "Transpose" || !sole_reader(v) || perm_of(*t) != std::vector<int64_t>{0, 2, 1, 3}) return why = generic, false;
-          am.nodes.push_back(producer_of[v]);
+          am.nodes.push_back(graph->producer_of.at(v));
         } else if (perm != (kt ? std::vector<int64_t>{0, 2, 3, 1} : std::vector<int64_t>{0, 2, 1, 3})) {
           return why = generic, false;
         }
@@ -2800,7 +2840,7 @@ struct Lowerer {
             return why = "the packed head split [N,T,3,h,dh] -> Transpose(2,0,3,1,4) is not supported yet; split Q, K and V on the last axis first", false;
           return why = generic, false;
         }
-        am.nodes.push_back(producer_of[v]);
+        am.nodes.push_back(graph->producer_of.at(v));
         side.src = r->inputs[0];
         side.shape = r->inputs[1];
         const NodeDef *c = producer(side.src);
@@ -2815,7 +2855,7 @@ struct Lowerer {
             side.cut = c;
             side.cut_out = size_t(std::find(c->outputs.begin(), c->outputs.end(), side.src) - c->outputs.begin());
             side.src = c->inputs[0];
-            am.nodes.push_back(producer_of[r->inputs[0]]);
+            am.nodes.push_back(graph->producer_of.at(r->inputs[0]));
           }
         }
         return true;
@@ -2826,10 +2866,10 @@ struct Lowerer {
       const NodeDef *sm = nullptr;
       while (ok && !sm) {
         const NodeDef *c = sole_reader(cur);
-        size_t ci = c ? consumers_of[cur][0] : 0;
-        if (!c && !graph_outs.count(cur) && consumers_of.count(cur)) {  // a Where beside the Shape nodes that size its condition's Expand
+        size_t ci = c ? graph->consumers_of.at(cur)[0] : 0;
+        if (!c && !graph_outs.count(cur) && graph->consumers_of.count(cur)) {  // a Where beside the Shape nodes that size its condition's Expand
           std::set<size_t> others;
-          for (size_t r : consumers_of[cur])
+          for (size_t r : graph->consumers_of.at(cur))
             if (m.nodes[r].op != "Shape") others.insert(r);
           if (others.size() == 1 && m.nodes[*others.begin()].op == "Where") c = &m.nodes[*others.begin()], ci = *others.begin();
         }
@@ -2881,17 +2921,17 @@ struct Lowerer {
         const NodeDef *pv = sole_reader(sm->outputs[0]);
         if (!pv || pv->op != "MatMul" || pv->inputs.size() != 2 || pv->inputs[0] != sm->outputs[0] || is_const(pv->inputs[1])) ok = false, why = generic;
         if (ok) {
-          am.nodes.push_back(consumers_of[sm->outputs[0]][0]);
+          am.nodes.push_back(graph->consumers_of.at(sm->outputs[0])[0]);
           ok = match_head(pv->inputs[1], am.side[2], false);
         }
         if (ok) {
           const NodeDef *t = sole_reader(pv->outputs[0]);
           if (!t || t->op != "Transpose" || perm_of(*t) != std::vector<int64_t>{0, 2, 1, 3}) ok = false, why = generic;
           else {
-            am.nodes.push_back(consumers_of[pv->outputs[0]][0]);
+            am.nodes.push_back(graph->consumers_of.at(pv->outputs[0])[0]);
             const NodeDef *r = sole_reader(t->outputs[0]);
             if (!r || r->op != "Reshape" || r->inputs.size() != 2 || r->inputs[0] != t->outputs[0]) ok = false, why = generic;
-            else anchor = consumers_of[t->outputs[0]][0];
+            else anchor = graph->consumers_of.at(t->outputs[0])[0];
           }
         }
       }
@@ -2926,14 +2966,14 @@ struct Lowerer {
       for (const AttnSide &sd : kv.second.side) {
         if (!sd.cut) continue;
         for (const auto &o : sd.cut->outputs) {
-          auto it = consumers_of.find(o);
+          auto it = graph->consumers_of.find(o);
           bool all = !graph_outs.count(o);
-          if (it != consumers_of.end())
+          if (it != graph->consumers_of.end())
             for (size_t c : it->second) all = all && absorbed[c];
           if (!all) absorbed[size_t(sd.cut - m.nodes.data())] = 0;
         }
       }
-    find_masked_means(live);
+    find_masked_means();
     // The nodes of the mask sub-graphs emit nothing.  The mask value may feed every layer (exporters compute it once), so a node counts
     // once; what a node reads is read by the steps from the input buffer itself (a mask input nothing else reads gets no SliceCols).
     std::set<size_t> rm_nodes, rm_aux;
@@ -2950,7 +2990,7 @@ struct Lowerer {
       bool all = true;
       for (const auto &o : m.nodes[i].outputs) {
         all = all && !graph_outs.count(o);
-        if (auto it = consumers_of.find(o); it != consumers_of.end())
+        if (auto it = graph->consumers_of.find(o); it != graph->consumers_of.end())
           for (size_t c : it->second) all = all && (absorbed[c] || mmean_at.count(c));  // (the closing Div emits the step)
       }
       return all;
@@ -2970,26 +3010,22 @@ struct Lowerer {
 
   // The masked mean over time (the sentence-embedding head): Div(ReduceSum(Mul(x, m), 1), Clip(ReduceSum(m or mask, 1), min = c)) with
   // m = float(mask [N, T, 1]), traced like an attention's row mask, becomes ONE MeanTime step with a row mask (lower_masked_mean)
-  void find_masked_means(const std::vector<char> &live) {
-    auto std_dom = [](const NodeDef &n) { return n.domain.empty() || n.domain == "ai.onnx"; };
+  void find_masked_means() {
     auto sum_over_time = [&](const NodeDef &r) {
       std::vector<int64_t> ax;
-      return r.op == "ReduceSum" && std_dom(r) && !r.inputs.empty() && graph_ints_arg(r, 1, "axes", &ax) && ax == std::vector<int64_t>{1};
+      return r.op == "ReduceSum" && graph->std_dom(r) && !r.inputs.empty() && graph_ints_arg(r, 1, "axes", &ax) && ax == std::vector<int64_t>{1};
     };
-    auto made_by = [&](const std::string &v) -> const NodeDef * {
-      auto it = producer_of.find(v);
-      return it == producer_of.end() ? nullptr : &m.nodes[it->second];
-    };
+    auto made_by = [&](const std::string &v) { return graph->producer(v); };
     auto idx = [&](const NodeDef *n) { return size_t(n - m.nodes.data()); };
     for (size_t i = 0; i < m.nodes.size(); i++) {
       const NodeDef &mul = m.nodes[i];
-      if (!live[i] || absorbed[i] || mul.op != "Mul" || !std_dom(mul) || mul.inputs.size() != 2 || mul.outputs.empty()) continue;
+      if (!graph->live[i] || absorbed[i] || mul.op != "Mul" || !graph->std_dom(mul) || mul.inputs.size() != 2 || mul.outputs.empty()) continue;
       const NodeDef *rs = only_reader(mul.outputs[0]);
       if (!rs || !sum_over_time(*rs) || rs->attr_i("keepdims", 1) != 0 || rs->inputs[0] != mul.outputs[0]) continue;
       const NodeDef *div = only_reader(rs->outputs[0]);
-      if (!div || div->op != "Div" || !std_dom(*div) || div->inputs.size() != 2 || div->inputs[0] != rs->outputs[0]) continue;
+      if (!div || div->op != "Div" || !graph->std_dom(*div) || div->inputs.size() != 2 || div->inputs[0] != rs->outputs[0]) continue;
       const NodeDef *clip = made_by(div->inputs[1]);
-      if (!clip || clip->op != "Clip" || !std_dom(*clip) || only_reader(clip->outputs[0]) != div) continue;
+      if (!clip || clip->op != "Clip" || !graph->std_dom(*clip) || only_reader(clip->outputs[0]) != div) continue;
       MaskedMean mm;
       double lo = 0;
       size_t cnt = 0;
@@ -3004,7 +3040,7 @@ struct Lowerer {
       int side = -1;
       for (int j = 0; j < 2 && side < 0; j++) {
         RowMask r;
-        if (attn_row_data.count(mul.inputs[size_t(1 - j)]) && trace_row_mask(mul.inputs[size_t(j)], &r).empty() && r.state != 1 && r.shape.size() == 3 && r.shape[2] == 1)
+        if (graph->row_data.count(mul.inputs[size_t(1 - j)]) && trace_row_mask(mul.inputs[size_t(j)], &r).empty() && r.state != 1 && r.shape.size() == 3 && r.shape[2] == 1)
           side = j, mm.rm = std::move(r);
       }
       if (side < 0) continue;
@@ -3212,8 +3248,8 @@ struct Lowerer {
       if (p.kind != StepKind::Dense || p.rep != T || p.act != Act::None || p.out != v.buf || p.M != E) return -1;
       for (const auto &nm : buf_names[v.buf]) {
         if (nm == m.outputs[out_index].name) return -1;
-        auto it = consumers_of.find(nm);
-        if (it == consumers_of.end()) continue;
+        auto it = graph->consumers_of.find(nm);
+        if (it == graph->consumers_of.end()) continue;
         for (size_t c : it->second) {  // readers: THIS pattern's nodes, Shape, and nodes folded into the step (its bias Add)
           const NodeDef &cn = m.nodes[c];
           auto ov = cn.outputs.empty() ? vals.end() : vals.find(cn.outputs[0]);
@@ -4273,21 +4309,13 @@ struct Lowerer {
   static bool prep_encoder(const std::string &op) {
     return op == "Imputer" || op == "Binarizer" || op == "OneHotEncoder" || op == "LabelEncoder" || op == "FeatureVectorizer";
   }
-  bool const_name(const std::string &v, const std::map<std::string, size_t> &prod_of) const {
-    if (m.initializers.count(v)) return true;
-    auto it = prod_of.find(v);
-    return it != prod_of.end() && m.nodes[it->second].op == "Constant";
-  }
   // marks `region`; returns the graph inputs that start inside a region
-  std::set<std::string> find_regions(const std::vector<char> &live) {
+  std::set<std::string> find_regions() {
     const size_t N = m.nodes.size(), M = m.inputs.size();
-    std::map<std::string, size_t> prod_of;
-    for (size_t i = 0; i < N; i++)
-      for (const auto &o : m.nodes[i].outputs) prod_of[o] = i;
+    const std::map<std::string, size_t> &prod_of = graph->producer_of;
     std::map<std::string, size_t> input_of;
     for (size_t j = 0; j < M; j++) input_of[m.inputs[j].name] = j;
-    std::set<std::string> act;  // names that hold row data
-    for (const auto &v : m.inputs) act.insert(v.name);
+    const std::set<std::string> &act = graph->row_data;  // names that hold row data
     std::vector<char> elig(N, 0), trig(N + M, 0);
     std::vector<size_t> uf(N + M);
     std::iota(uf.begin(), uf.end(), size_t(0));
@@ -4297,18 +4325,16 @@ struct Lowerer {
       return input_of.count(v) || (p != prod_of.end() && elig[p->second]);
     };
     for (size_t i = 0; i < N; i++) {
-      if (!live[i]) continue;
+      if (!graph->live[i]) continue;
       const NodeDef &n = m.nodes[i];
       bool any_act = false;
       for (const auto &in : n.inputs) any_act = any_act || act.count(in);
       if (!any_act) continue;
-      if (n.op != "Shape")
-        for (const auto &o : n.outputs) act.insert(o);
-      const bool ml = n.domain == "ai.onnx.ml", std_dom = n.domain.empty() || n.domain == "ai.onnx";
+      const bool ml = n.domain == "ai.onnx.ml", std_dom = graph->std_dom(n);
       const bool data_act = !n.inputs.empty() && act.count(n.inputs[0]);
       bool e = false, t = false;
       if (ml && n.op == "ArrayFeatureExtractor") {
-        e = data_act && n.inputs.size() == 2 && const_name(n.inputs[1], prod_of);
+        e = data_act && n.inputs.size() == 2 && bool(graph->constant(n.inputs[1]));
         if (e) {  // non-contiguous constant indices: nothing else serves them
           auto ci = m.initializers.find(n.inputs[1]);
           if (ci != m.initializers.end() && ci->second->dtype == onnx::kInt64) {
@@ -4663,23 +4689,13 @@ struct Lowerer {
 
   // a constant f32 tensor known before the walk: an initializer or a Constant node's value
   std::shared_ptr<TensorData> const_tensor(const std::string &name) const {
-    auto ci = m.initializers.find(name);
-    if (ci != m.initializers.end()) return ci->second->dtype == onnx::kFloat ? ci->second : nullptr;
-    auto pi = producer_of.find(name);
-    if (pi == producer_of.end() || m.nodes[pi->second].op != "Constant") return nullptr;
-    const onnx::Attribute *a = m.nodes[pi->second].attr("value");
-    return a && a->t && a->t->dtype == onnx::kFloat ? a->t : nullptr;
-  }
-  const NodeDef *producer_node(const std::string &v, size_t *idx) const {
-    auto pi = producer_of.find(v);
-    if (pi == producer_of.end()) return nullptr;
-    *idx = pi->second;
-    return &m.nodes[pi->second];
+    const std::shared_ptr<TensorData> t = graph->constant(name).t;
+    return t && t->dtype == onnx::kFloat ? t : nullptr;
   }
   // g = -2 X C^T read by one node: the set (and its orientation) and the nodes of the chain
   bool match_minus_two_dot(const std::string &g, const std::string &x, NearestMatch *mt) {
     size_t gi = 0;
-    const NodeDef *p = producer_node(g, &gi);
+    const NodeDef *p = graph->producer(g, &gi);
     if (!p || !only_reader(g) || !p->domain.empty()) return false;
     if (p->op == "Gemm") {
       if (p->inputs.size() < 2 || p->inputs[0] != x || p->attr_i("transA", 0) != 0 || p->attr_f("alpha", 1.f) != -2.f) return false;
@@ -4700,7 +4716,7 @@ struct Lowerer {
       auto k = const_tensor(p->inputs[size_t(1 - side)]);
       if (!k || k->f32.size() != 1 || k->f32[0] != -2.f) continue;
       size_t mi = 0;
-      const NodeDef *mm = producer_node(p->inputs[size_t(side)], &mi);
+      const NodeDef *mm = graph->producer(p->inputs[size_t(side)], &mi);
       if (!mm || mm->op != "MatMul" || !mm->domain.empty() || mm->inputs.size() != 2 || mm->inputs[0] != x || !only_reader(mm->outputs[0])) return false;
       auto c = const_tensor(mm->inputs[1]);
       if (!c || c->dims.size() != 2) return false;
@@ -4713,10 +4729,10 @@ struct Lowerer {
     }
     return false;
   }
-  void find_nearest(const std::vector<char> &live) {
+  void find_nearest() {
     for (size_t i = 0; i < m.nodes.size(); i++) {
       const NodeDef &rs = m.nodes[i];
-      if (!live[i] || absorbed[i] || region[i] || rs.op != "ReduceSumSquare" || !rs.domain.empty() || rs.inputs.empty() || rs.attr_i("keepdims", 1) == 0) continue;
+      if (!graph->live[i] || absorbed[i] || region[i] || rs.op != "ReduceSumSquare" || !rs.domain.empty() || rs.inputs.empty() || rs.attr_i("keepdims", 1) == 0) continue;
       std::vector<int64_t> axes;
       if (rs.inputs.size() > 1 && !rs.inputs[1].empty()) {
         auto ci = m.initializers.find(rs.inputs[1]);
@@ -4740,7 +4756,7 @@ struct Lowerer {
         mt.d2 = a2->outputs[0];
       } else {  // rs + (g + C2)
         size_t bi = 0;
-        const NodeDef *b = producer_node(other, &bi);
+        const NodeDef *b = graph->producer(other, &bi);
         if (!b || b->op != "Add" || !b->domain.empty() || b->inputs.size() != 2 || !only_reader(other)) continue;
         int gs = -1;
         for (int side = 0; side < 2 && gs < 0; side++)
@@ -4973,16 +4989,12 @@ struct Lowerer {
 
   // an integer constant known before the walk: an initializer or a Constant node
   bool graph_const_ints(const std::string &name, std::vector<int64_t> *v, std::vector<int64_t> *dims) const {
-    const TensorData *t = nullptr;
-    if (auto ci = m.initializers.find(name); ci != m.initializers.end()) {
-      t = ci->second.get();
-    } else {
-      auto pi = producer_of.find(name);
-      if (pi == producer_of.end() || m.nodes[pi->second].op != "Constant") return false;
-      const NodeDef &c = m.nodes[pi->second];
-      if (auto *a = c.attr("value"); a && a->t) t = a->t.get();
-      else if (auto *i = c.attr("value_int")) { *v = {i->i}; dims->clear(); return true; }
-      else if (auto *is = c.attr_ints("value_ints")) { *v = *is; *dims = {int64_t(is->size())}; return true; }
+    const GraphIndex::Const c = graph->constant(name);
+    const TensorData *t = c.t.get();
+    if (!t) {
+      if (!c.node) return false;
+      if (auto *i = c.node->attr("value_int")) { *v = {i->i}; dims->clear(); return true; }
+      else if (auto *is = c.node->attr_ints("value_ints")) { *v = *is; *dims = {int64_t(is->size())}; return true; }
       else return false;
     }
     if (t->dtype != onnx::kInt64) return false;
@@ -5011,8 +5023,8 @@ struct Lowerer {
       }
       off += w;
     }
-    auto pi = producer_of.find(v);
-    if (pi == producer_of.end()) return "indices that are not computed from a graph input";
+    auto pi = graph->producer_of.find(v);
+    if (pi == graph->producer_of.end()) return "indices that are not computed from a graph input";
     const NodeDef &p = m.nodes[pi->second];
     const std::string by = "indices computed by " + p.op + (p.name.empty() ? "" : " '" + p.name + "'") +
                            "; only columns of a graph input, picked by Gather(axis = 1) / Slice / Squeeze, Cast to an integer type, plus a constant integer offset";
@@ -5081,26 +5093,13 @@ struct Lowerer {
     return "";
   }
 
-  void find_embeds(const std::vector<char> &live) {
+  void find_embeds() {
     const size_t N = m.nodes.size();
-    std::set<std::string> row_data;
-    for (const auto &v : m.inputs) row_data.insert(v.name);
-    for (size_t i = 0; i < N; i++) {
-      if (!live[i] || m.nodes[i].op == "Shape") continue;
-      bool any = false;
-      for (const auto &in : m.nodes[i].inputs) any = any || row_data.count(in);
-      if (any)
-        for (const auto &o : m.nodes[i].outputs) row_data.insert(o);
-    }
-    auto std_dom = [](const NodeDef &n) { return n.domain.empty() || n.domain == "ai.onnx"; };
     std::vector<EmbedLookup> found;
     for (size_t i = 0; i < N; i++) {
       const NodeDef &n = m.nodes[i];
-      if (!live[i] || absorbed[i] || n.op != "Gather" || !std_dom(n) || n.inputs.size() != 2 || n.outputs.empty() || !row_data.count(n.inputs[1])) continue;
-      std::shared_ptr<TensorData> t;
-      if (auto ci = m.initializers.find(n.inputs[0]); ci != m.initializers.end()) t = ci->second;
-      else if (auto pi = producer_of.find(n.inputs[0]); pi != producer_of.end() && m.nodes[pi->second].op == "Constant")
-        if (auto *a = m.nodes[pi->second].attr("value"); a && a->t) t = a->t;
+      if (!graph->live[i] || absorbed[i] || n.op != "Gather" || !graph->std_dom(n) || n.inputs.size() != 2 || n.outputs.empty() || !graph->row_data.count(n.inputs[1])) continue;
+      const std::shared_ptr<TensorData> t = graph->constant(n.inputs[0]).t;
       if (!t) continue;  // (data that is no plain constant: Lowerer::gather says what it serves)
       // from here on the node is an embedding lookup, served or refused in its own words
       static const std::map<int, const char *> type_names = {{onnx::kFloat16, "float16"}, {onnx::kDouble, "float64"}, {onnx::kInt64, "int64"}, {onnx::kInt32, "int32"},
@@ -5127,7 +5126,7 @@ struct Lowerer {
       if (t->dims.size() == 2) L.shape.push_back(L.d);
       // [N, k, d] -> [N, k * d] by the Flatten / Reshape that alone reads it
       if (L.shape.size() == 3)
-        if (const NodeDef *r = only_reader(L.out); r && std_dom(*r) && !r->outputs.empty() && r->inputs[0] == L.out) {
+        if (const NodeDef *r = only_reader(L.out); r && graph->std_dom(*r) && !r->outputs.empty() && r->inputs[0] == L.out) {
           bool flat = r->op == "Flatten" && r->attr_i("axis", 1) == 1;
           std::vector<int64_t> tgt, tdims;
           if (r->op == "Reshape" && r->inputs.size() == 2 && graph_const_ints(r->inputs[1], &tgt, &tdims) && tgt.size() == 2)
@@ -5140,7 +5139,7 @@ struct Lowerer {
         }
       // [N] (a rank-1 table by one index column) -> [N, 1] by the Unsqueeze(axis 1) that alone reads it: what a Concat wants
       if (L.shape.size() == 1)
-        if (const NodeDef *r = only_reader(L.out); r && std_dom(*r) && r->op == "Unsqueeze" && !r->outputs.empty() && r->inputs[0] == L.out) {
+        if (const NodeDef *r = only_reader(L.out); r && graph->std_dom(*r) && r->op == "Unsqueeze" && !r->outputs.empty() && r->inputs[0] == L.out) {
           std::vector<int64_t> ax;
           if (graph_ints_arg(*r, 1, "axes", &ax) && ax.size() == 1 && (ax[0] == 1 || ax[0] == -1)) {
             L.tail.push_back(size_t(r - m.nodes.data()));
@@ -5155,16 +5154,15 @@ struct Lowerer {
     // and an input that another step computes (a Scaler on the numeric columns, a Relu of a lookup) is a gap that one CopyCols behind the
     // step fills.  A lookup is looked up again by every such Concat that reads it -- that costs nothing -- and is a step of its own only
     // where something else reads it too.
-    std::set<std::string> graph_outs;
-    for (const auto &o : m.outputs) graph_outs.insert(o.name);
+    const std::set<std::string> &graph_outs = graph->graph_outs;
     std::set<size_t> concats;
     for (size_t li = 0; li < found.size(); li++) {
       if (found[li].shape.size() != 2) continue;
-      auto it = consumers_of.find(found[li].out);
-      if (it == consumers_of.end()) continue;
+      auto it = graph->consumers_of.find(found[li].out);
+      if (it == graph->consumers_of.end()) continue;
       for (size_t c : it->second) {
         const NodeDef &r = m.nodes[c];
-        if (r.op == "Concat" && std_dom(r) && !r.outputs.empty() && !absorbed[c] && (r.attr_i("axis", 1) == 1 || r.attr_i("axis", 1) == -1)) concats.insert(c);
+        if (r.op == "Concat" && graph->std_dom(r) && !r.outputs.empty() && !absorbed[c] && (r.attr_i("axis", 1) == 1 || r.attr_i("axis", 1) == -1)) concats.insert(c);
       }
     }
     for (size_t ci : concats) {
@@ -5197,8 +5195,8 @@ struct Lowerer {
     }
     for (size_t li = 0; li < found.size(); li++) {
       bool own = graph_outs.count(found[li].out) > 0;
-      auto it = consumers_of.find(found[li].out);
-      if (it == consumers_of.end() || it->second.empty()) own = true;
+      auto it = graph->consumers_of.find(found[li].out);
+      if (it == graph->consumers_of.end() || it->second.empty()) own = true;
       else
         for (size_t c : it->second) own = own || !concats.count(c);
       if (!own) continue;
@@ -5228,7 +5226,7 @@ struct Lowerer {
       bool all = true;
       for (const auto &o : m.nodes[i].outputs) {
         all = all && !graph_outs.count(o);
-        if (auto it = consumers_of.find(o); it != consumers_of.end())
+        if (auto it = graph->consumers_of.find(o); it != graph->consumers_of.end())
           for (size_t c : it->second) all = all && (owner[c] >= 0 || gone[c]);
       }
       gone[i] = all;
@@ -5342,6 +5340,7 @@ struct Lowerer {
   }
 
   Plan run() {
+    graph = std::make_unique<const GraphIndex>(m, m.outputs[out_index].name);
     plan.opset = m.opset;
     const onnx::ValueDef &in = m.inputs[0];
     if (!in.has_shape) throw InferaError::onnx("input '" + in.name + "' has no declared shape");
@@ -5391,33 +5390,20 @@ struct Lowerer {
       }
     }
     auto int_input = [](const onnx::ValueDef &v) { return v.elem_type == onnx::kInt64 || v.elem_type == onnx::kInt32; };
-    // Only the first output is served (engine.rs:146-149): nodes that do not feed it are dead -- a second
-    // output (e.g. the probabilities next to a label) must neither cost kernels nor block loading.
-    std::vector<char> live(m.nodes.size(), 0);
-    {
-      std::map<std::string, size_t> producer_of;
-      for (size_t i = 0; i < m.nodes.size(); i++)
-        for (const auto &o : m.nodes[i].outputs) producer_of[o] = i;
-      std::vector<std::string> work{m.outputs[out_index].name};
-      while (!work.empty()) {
-        const std::string v = work.back();
-        work.pop_back();
-        auto it = producer_of.find(v);
-        if (it == producer_of.end() || live[it->second]) continue;
-        live[it->second] = 1;
-        for (const auto &i : m.nodes[it->second].inputs) work.push_back(i);
-      }
-    }
+    const std::vector<char> &live = graph->live;
     for (size_t i = 0; i < m.nodes.size(); i++)
       if (live[i])
         for (const auto &in_name : m.nodes[i].inputs) uses[in_name]++;
     uses[m.outputs[out_index].name]++;
+    // The matchers below claim nodes through `region` and `absorbed` and otherwise read the index alone: a later one skips what an
+    // earlier one claimed, and none depends on another having run.
+    absorbed.assign(m.nodes.size(), 0);
     // preprocessing regions: their graph inputs start as identity columns over the input buffer (integer inputs truncated)
-    const std::set<std::string> region_inputs = find_regions(live);
-    find_attention(live);
-    if (nearest_enabled) find_nearest(live);
-    find_group_norms(live);
-    find_embeds(live);
+    const std::set<std::string> region_inputs = find_regions();
+    find_attention();
+    if (nearest_enabled) find_nearest();
+    find_group_norms();
+    find_embeds();
     {
       int64_t off = 0;
       for (const auto &v : m.inputs) {
@@ -5522,195 +5508,5 @@ struct Lowerer {
 }  // namespace
 
 Plan lower_model(const onnx::Model &m, const std::string &output_select) { return Lowerer(m, output_select).run(); }
-
-double Plan::flops_per_row() const {
-  double f = 0;
-  for (const auto &s : steps) {
-    if (s.kind == StepKind::Dense || s.kind == StepKind::QDense || s.kind == StepKind::HDense) f += 2.0 * double(s.rep) * double(s.K) * double(s.M);
-    else if (s.kind == StepKind::Attention) f += 4.0 * double(s.attn_T) * double(s.attn_T) * double(s.attn_heads * s.attn_dh);
-    else if (s.kind == StepKind::Conv2d || s.kind == StepKind::QConv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
-    else if (s.kind == StepKind::ConvTranspose2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.H) * double(s.Wd);  // (C/g) kh kw taps per input pixel and output channel
-    else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
-    else if (s.kind == StepKind::Nearest) f += 2.0 * double(s.nearest->F) * double(s.nearest->M);
-    else if (s.kind == StepKind::Recurrent) f += 2.0 * double(s.rnn->T * s.rnn->D * s.rnn->G * s.rnn->H) * double(s.rnn->F + s.rnn->H);
-  }
-  return f;
-}
-
-std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed"};
-  static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
-                               "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
-  std::ostringstream o;
-  o << "{\"input_shape\":" << json_int_array(input_shape) << ",\"output_shape\":" << json_int_array(output_shape)
-    << ",\"flops_per_row\":" << (long long)flops_per_row();
-  if (!input_declared_type.empty()) o << ",\"input_type\":" << json_str(input_declared_type);
-  if (output_declared_type == "float16") o << ",\"output_type\":" << json_str(output_declared_type);  // (integer outputs: infera_get_model_info says so)
-  o << ",\"steps\":[";
-  for (size_t i = 0; i < steps.size(); i++) {
-    const Step &s = steps[i];
-    if (i) o << ",";
-    o << "{\"kind\":\"" << kinds[int(s.kind)] << "\",\"in\":" << s.in0 << ",\"out\":" << s.out;
-    if (s.in1 >= 0) o << ",\"in1\":" << s.in1;
-    if (s.in2 >= 0) o << ",\"in2\":" << s.in2;
-    if (s.kind == StepKind::Dense) o << ",\"K\":" << s.K << ",\"M\":" << s.M << ",\"bias\":" << (s.bias.empty() ? "false" : "true");
-    if (s.kind == StepKind::Dense && s.rep > 1) o << ",\"T\":" << s.rep;
-    auto qtype = [](const Quant &q) { return !q.on ? "f32" : q.is_signed ? "int8" : "uint8"; };
-    if (s.kind == StepKind::FakeQuant) o << ",\"type\":\"" << qtype(s.qx) << "\",\"scale\":" << double(s.qx.scale) << ",\"zero_point\":" << s.qx.zp;
-    if (s.kind == StepKind::QDense || s.kind == StepKind::QConv2d) {
-      o << ",\"K\":" << s.K << ",\"M\":" << s.M << ",\"bias\":\"" << (!s.q_bias.empty() ? "int32" : !s.bias.empty() ? "f32" : "none") << "\",\"x_type\":\"" << qtype(s.qx)
-        << "\",\"w_type\":\"" << (s.q_w_signed ? "int8" : "uint8") << "\",\"y_type\":\"" << qtype(s.qy) << "\",\"per_channel\":" << (s.q_per_channel ? "true" : "false");
-      if (s.rep > 1) o << ",\"T\":" << s.rep;
-      // what the parser read, for checks without a GPU: sums over the weights in their own type and over the int32 bias
-      long long wsum = 0, whash = 0, bsum = 0;
-      for (size_t k = 0; k < s.qW.size(); k++) {
-        const long long w = s.qW[k] + (s.q_w_signed ? 0 : 128);
-        wsum += w;
-        whash += w * (long long)(k % 251 + 1);
-      }
-      for (int32_t b : s.q_bias) bsum += b;
-      o << ",\"w_sum\":" << wsum << ",\"w_hash\":" << whash << ",\"bias_sum\":" << bsum << ",\"x_zero_point\":" << s.qx.zp;
-    }
-    if (s.kind == StepKind::HDense) {
-      static const char *modes[] = {"none", "gemm", "matmul_add"};
-      o << ",\"K\":" << s.K << ",\"M\":" << s.M << ",\"bias\":\"" << modes[s.h_bias_mode] << "\"";
-      if (s.rep > 1) o << ",\"T\":" << s.rep;
-      long long wsum = 0, whash = 0, bsum = 0;  // over the 16-bit patterns the parser read
-      for (size_t k = 0; k < s.hW.size(); k++) {
-        wsum += s.hW[k];
-        whash += (long long)(s.hW[k]) * (long long)(k % 251 + 1);
-      }
-      for (uint16_t b : s.h_bias) bsum += b;
-      o << ",\"w_sum\":" << wsum << ",\"w_hash\":" << whash << ",\"bias_sum\":" << bsum;
-    }
-    if (s.kind == StepKind::LayerNorm) o << ",\"E\":" << s.K << ",\"T\":" << s.rep << ",\"epsilon\":" << double(s.ln_eps) << ",\"bias\":" << (s.shift.empty() ? "false" : "true");
-    if (s.kind == StepKind::MeanTime) o << ",\"E\":" << s.K << ",\"T\":" << s.rep;
-    auto json_f32 = [](float f) { return std::isnan(f) ? std::string("NaN") : std::isinf(f) ? std::string(f < 0 ? "-Infinity" : "Infinity") : ([&] { std::ostringstream q; q << std::setprecision(9) << double(f); return q.str(); })(); };
-    if (s.kind == StepKind::MeanTime && s.in3 >= 0)
-      o << ",\"row_mask\":{\"src_col\":" << s.rm_off << ",\"cmp\":" << json_f32(s.rm_cmp) << ",\"clip\":" << json_f32(s.rm_clip) << "}";
-    if (s.kind == StepKind::RowReduce) {
-      static const char *ops[] = {"Sum", "Mean", "Max", "Min", "Prod", "L1", "L2", "SumSquare", "LogSum", "LogSumExp"};
-      o << ",\"op\":\"" << ops[s.out_mode] << "\",\"E\":" << s.K << ",\"T\":" << s.rep;
-    }
-    if (s.kind == StepKind::ArgMin) o << ",\"K\":" << s.K;
-    if (s.kind == StepKind::TopK) o << ",\"M\":" << s.K << ",\"k\":" << s.M << ",\"largest\":" << (s.is_max ? "true" : "false") << ",\"output\":\"" << (s.out_mode ? "indices" : "values") << "\"";
-    if (s.kind == StepKind::BinaryAct && s.K > 0) o << ",\"row_scalar\":\"" << (s.const_left ? "left" : "right") << "\",\"E\":" << s.K << ",\"T\":" << s.rep;
-    if (s.kind == StepKind::Nearest || s.kind == StepKind::NearestReduce) {
-      static const char *modes[] = {"lists", "d2", "sqrt_d2", "label", "indices", "values", "sqrt_values"};
-      const NearestPack &q = *s.nearest;
-      o << ",\"nearest\":{\"F\":" << q.F << ",\"M\":" << q.M << ",\"k\":" << s.M << ",\"outputs\":\"" << modes[s.out_mode] << "\",\"slices\":" << q.slices
-        << ",\"slice_tile\":" << json_int_array(std::vector<int64_t>(q.slice_tile.begin(), q.slice_tile.end())) << ",\"spelling\":\"" << q.spelling << "\",\"centred\":true}";
-    }
-    if (s.kind == StepKind::Attention)
-      o << ",\"T\":" << s.attn_T << ",\"heads\":" << s.attn_heads << ",\"dh\":" << s.attn_dh << ",\"scale\":" << double(s.attn_scale) << ",\"mask\":" << (s.cst.empty() ? "false" : "true")
-        << ",\"packed_qkv\":" << (s.in0 == s.in1 && s.in1 == s.in2 ? "true" : "false");
-    if (s.kind == StepKind::Attention && s.in3 >= 0)
-      o << ",\"row_mask\":{\"src_col\":" << s.rm_off << ",\"cmp\":" << json_f32(s.rm_cmp) << ",\"fill\":" << json_f32(s.rm_fill) << ",\"mode\":\""
-        << (s.rm_mode == kRowMaskAdd ? "add" : "replace") << "\",\"excluding\":" << (s.rm_excl ? "true" : "false") << "}";
-    if (s.kind == StepKind::Conv2d) o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"k\":[" << s.kh << "," << s.kw << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
-    if (s.kind == StepKind::ConvTranspose2d) {
-      const DeconvPack &q = *s.deconv;
-      o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"group\":" << s.groups << ",\"k\":[" << s.kh << "," << s.kw << "],\"strides\":[" << s.sh << "," << s.sw << "],\"pads\":[" << s.pt
-        << "," << s.pl << "," << s.pb << "," << s.pr << "],\"dilations\":[" << s.dh << "," << s.dw << "],\"output_padding\":[" << q.out_pad_h << "," << q.out_pad_w
-        << "],\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "],\"bias\":" << (s.bias.empty() ? "false" : "true") << ",\"phases\":[";
-      for (size_t a = 0; a < q.hphase.size(); a++)
-        for (size_t b = 0; b < q.wphase.size(); b++) {
-          const ConvTAxisPhase &hp = q.hphase[a], &wp = q.wphase[b];
-          o << (a + b ? "," : "") << "{\"phase\":[" << a << "," << b << "],\"first\":[" << hp.out0 << "," << wp.out0 << "],\"pixels\":[" << hp.count << "," << wp.count << "],\"taps\":[";
-          for (size_t i = 0; i < hp.tap.size(); i++)
-            for (size_t j = 0; j < wp.tap.size(); j++) o << (i + j ? "," : "") << "[" << hp.tap[i] << "," << wp.tap[j] << "]";
-          o << "],\"source_offsets\":[";  // per tap: the input pixel of the phase's pixel (j, i) is (j, i) + this
-          for (size_t i = 0; i < hp.tap.size(); i++)
-            for (size_t j = 0; j < wp.tap.size(); j++) o << (i + j ? "," : "") << "[" << hp.q[i] << "," << wp.q[j] << "]";
-          o << "]}";
-        }
-      o << "]";
-    }
-    if (s.kind == StepKind::Resize2d)
-      o << ",\"C\":" << s.C << ",\"mode\":\"" << (s.deconv->linear ? "linear" : "nearest") << "\",\"coordinate_transformation_mode\":\"" << s.deconv->coord_mode << "\""
-        << (s.deconv->linear ? std::string() : ",\"nearest_mode\":\"" + s.deconv->nearest_mode + "\"") << ",\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
-    if (s.kind == StepKind::SpatialNorm || s.kind == StepKind::SpatialStats)
-      o << ",\"C\":" << s.C << ",\"groups\":" << s.groups << ",\"E\":" << (s.C / s.groups) * s.S << ",\"hw\":[" << (s.H > 0 ? s.H : 1) << "," << (s.H > 0 ? s.Wd : s.S)
-        << "],\"epsilon\":" << double(s.ln_eps);
-    if (s.kind == StepKind::SpatialNorm) {  // gamma and beta as their f32 bit patterns: what the lowering folded, for checks without a GPU
-      auto bits = [](const std::vector<float> &v) {
-        std::vector<uint32_t> b(v.size());
-        if (!v.empty()) std::memcpy(b.data(), v.data(), v.size() * sizeof(float));
-        return json_int_array(b);
-      };
-      o << ",\"scale_bits\":" << bits(s.scale) << ",\"shift_bits\":" << bits(s.shift);
-    }
-    if (s.kind == StepKind::ChannelNorm) {  // gamma and beta as their f32 bit patterns, as for SpatialNorm
-      auto bits = [](const std::vector<float> &v) {
-        std::vector<uint32_t> b(v.size());
-        if (!v.empty()) std::memcpy(b.data(), v.data(), v.size() * sizeof(float));
-        return json_int_array(b);
-      };
-      o << ",\"C\":" << s.C << ",\"hw\":[" << s.H << "," << s.Wd << "],\"epsilon\":" << double(s.ln_eps) << ",\"scale_bits\":" << bits(s.scale) << ",\"shift_bits\":" << bits(s.shift);
-    }
-    if (s.kind == StepKind::Tokens) {  // the tables as one hash over their f32 bit patterns: equal spellings give equal plans
-      uint64_t h = 1469598103934665603ull;
-      for (const auto *v : {&s.prefix, &s.cst})
-        for (float f : *v) {
-          uint32_t b;
-          std::memcpy(&b, &f, sizeof b);
-          h = (h ^ b) * 1099511628211ull;
-        }
-      o << ",\"C\":" << s.C << ",\"S\":" << s.S << ",\"prefix\":" << s.rep - s.S << ",\"pos\":" << (s.cst.empty() ? "false" : "true") << ",\"T\":" << s.rep << ",\"E\":" << s.K
-        << ",\"tables_hash\":" << (h >> 11);
-    }
-    if (s.kind == StepKind::Embed) {
-      const EmbedPack &q = *s.embed;
-      o << ",\"W\":" << q.W << ",\"out_cols\":" << q.F << ",\"window\":";
-      if (q.win_k > 0) o << "[" << q.win_k << "," << q.win_d << "]";
-      else o << "null";
-      o << ",\"tables\":" << q.n_tables << ",\"rows_per_tile\":" << q.R << ",\"staged\":" << (q.staged ? "true" : "false") << ",\"bytes_per_row\":" << q.bytes_per_row()
-        << ",\"pieces\":[";
-      for (size_t k = 0; k < q.pieces.size(); k++) {
-        const EmbedPiece &e = q.pieces[k];
-        o << (k ? "," : "");
-        if (e.table >= 0)
-          o << "{\"table\":" << e.table << ",\"src\":" << e.src << ",\"V\":" << e.V << ",\"d\":" << e.d << ",\"offset\":" << e.offset << ",\"out\":" << e.out << "}";
-        else if (e.table == -2)
-          o << "{\"gap\":" << e.d << ",\"out\":" << e.out << "}";
-        else
-          o << "{\"copy\":" << e.d << ",\"src\":" << e.src << ",\"out\":" << e.out << "}";
-      }
-      o << "]";
-    }
-    if (s.kind == StepKind::QConv2d)
-      o << ",\"C\":" << s.C << ",\"k\":[" << s.kh << "," << s.kw << "],\"strides\":[" << s.sh << "," << s.sw << "],\"pads\":[" << s.pt << "," << s.pl << "," << s.pb << "," << s.pr
-        << "],\"dilations\":[" << s.dh << "," << s.dw << "],\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
-    if (s.kind == StepKind::TreeEnsemble || s.kind == StepKind::TreeReduce) {
-      static const char *modes[] = {"scores", "label", "binary_scores", "binary_label"};
-      const TreePack &t = *s.tree;
-      o << ",\"E\":" << t.E << ",\"slices\":" << t.slices << ",\"output\":\"" << modes[s.out_mode] << "\"";
-      if (s.kind == StepKind::TreeEnsemble)
-        o << ",\"trees\":" << t.trees << ",\"nodes\":" << t.nodes << ",\"max_depth\":" << t.max_depth << ",\"walk_width\":" << t.W
-          << ",\"aggregate\":\"" << (t.average ? "AVERAGE" : "SUM") << "\"";
-    }
-    if (s.kind == StepKind::SvmKernel || s.kind == StepKind::SvmReduce) {
-      static const char *kernels[] = {"LINEAR", "POLY", "RBF", "SIGMOID"}, *modes[] = {"value", "one_class", "label", "decision", "probabilities"};
-      const SvmPack &v = *s.svm;
-      o << ",\"kernel\":\"" << kernels[v.kernel] << "\",\"support_vectors\":" << v.n_sv << ",\"F\":" << v.F << ",\"classes\":" << v.classes
-        << ",\"slices\":" << v.slices << ",\"output\":\"" << modes[s.out_mode] << "\",\"probabilities\":" << (v.probabilities ? "true" : "false");
-    }
-    if (s.kind == StepKind::Prep)
-      o << ",\"F_in\":" << s.prep->F_in << ",\"F\":" << s.prep->F << ",\"onehot_cols\":" << s.prep->onehot << ",\"lookup_cols\":" << s.prep->lookup
-        << ",\"rows_per_tile\":" << s.prep->R << ",\"strict\":" << (s.prep->strict ? "true" : "false");
-    if (s.kind == StepKind::Recurrent) {
-      static const char *ops[] = {"LSTM", "GRU", "RNN"}, *modes[] = {"Y", "Y_h", "Y_c"};
-      const RnnPack &r = *s.rnn;
-      o << ",\"op\":\"" << ops[r.op] << "\",\"T\":" << r.T << ",\"F\":" << r.F << ",\"H\":" << r.H << ",\"D\":" << r.D << ",\"direction\":\""
-        << (r.D == 2 ? "bidirectional" : r.reverse ? "reverse" : "forward") << "\",\"output\":\"" << modes[s.out_mode] << "\"";
-      if (r.op == kRnnGru) o << ",\"linear_before_reset\":" << (r.lbr ? 1 : 0);
-      if (r.op == kRnnPlain) o << ",\"activation\":\"" << (r.relu ? "Relu" : "Tanh") << "\"";
-    }
-    if (s.act != Act::None) o << ",\"act\":\"" << acts[int(s.act)] << "\"";
-    o << ",\"origin\":" << json_str(s.origin) << "}";
-  }
-  o << "]}";
-  return o.str();
-}
 
 }  // namespace infera_hip
