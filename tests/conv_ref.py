@@ -4,8 +4,11 @@ feature map element by element, the inputs on which a correct kernel has exactly
 to.  A helper module (tests/test_conv_ref.py checks it without a GPU, tests/test_conv_exact_gpu.py uses it on one), not a conftest.
 
 A case is {"id", "inp": (C0, H, W), "ops": [...], "env": {...}, "expect": [exec kinds], "kinds": (...), "rows": (...)}; an op is a dict
-{"op": "conv" | "maxpool" | "avgpool" | "gap" | "gmp" | "concat" | "slice" | "shuffle", ...}; tensor 0 is the caller's NCHW input, tensor i the
-result of op i - 1; "src" names what an op reads (default: the previous tensor), "add" the tensor a convolution's residual Add takes.
+{"op": "conv" | "maxpool" | "avgpool" | "gap" | "gmp" | "concat" | "slice" | "shuffle" | "lrn" | "gate" | "bn", ...}; tensor 0 is the caller's NCHW
+input, tensor i the result of op i - 1; "src" names what an op reads (default: the previous tensor), "add" the tensor a convolution's residual Add
+takes, "gate" the [C, 1, 1] tensor a gate multiplies its "src" by.  A case may name the probe it is served through ("probe", default "A") and the
+layout its plan must have ("layout", default "NC/4HW4"): probe "" serves the tensor itself, which keeps the plan in NCHW on conv2d_generic_kernel,
+pool2d_kernel and the NCHW branches of the element-wise kernels (GENERIC_NCHW, NEIGHBOURS_NCHW, and the second run of every PER_CHANNEL case).
 
 The probes.  A served [C, H, W] tensor forces the whole plan to NCHW and the generic kernel (schedule.cpp decide_layout), so the fast kernels were
 only ever seen through a GlobalAveragePool -- which divides a wrong border pixel by H W before anyone compares.  Probe A ends the graph in a
@@ -34,7 +37,13 @@ bf16x6: six partial products per term, each exact, each added to the f32 accumul
 8 significant bits, so |mid| <= |v - hi| < 2^-7 |v|, and |lo| < 2^-7 |v - hi| < 2^-14 |v|: |x_mid w_lo| + |x_lo w_mid| + |x_lo w_lo| <
 (2^-21 + 2^-21 + 2^-28) |x| |w| < 2^-19.99 |x w|, summed over the terms: (2^-20 + 2^-28) mag.  Activations: Relu, Clip, LeakyRelu 1-Lipschitz (LeakyRelu
 one more rounding), Sigmoid (1/4) and Tanh 2 ulp of the value (device_common.hpp).  Max pools pass the largest error of the window on, average pools
-the mean plus (n + 1) roundings of the window's |x| sum."""
+the mean plus (n + 1) roundings of the window's |x| sum.  The generic kernel's chain is one MFMA fma per term: the same (K + 3) 2^-24 mag.
+
+Per-channel operators.  gate y = x g: |g| e_x + |x| e_g + U |x g| (one product).  bn y = s x + t (fused or not): |s| e_x + 2 U (|s x| + |t|).
+lrn y = x / (bias + alpha / size * sum v^2)^beta: the window sum is `size` fmas, (size + 1) U sum v^2, plus 2 |v| e_v from the input, carried to y
+through d y / d sum; powf and the division have no accuracy figure in device_common.hpp or in the ROCm documents, so LRN's generic data is held
+to the project's parity bar |got - ref| <= 1e-4 |ref| + 1e-6 against float64 (lrn_bar) and that bar is what forward64 adds for them.  Its exact
+checks need none: alpha = 0, bias = 1 gives pow(1, beta) == 1 and y == x to the bit (lrn_identity), and the two layouts give the same bits."""
 from __future__ import annotations
 
 import math
@@ -152,6 +161,24 @@ def shuffle64(x, groups):
     return x.reshape(n, groups, c // groups, h, w).transpose(0, 2, 1, 3, 4).reshape(n, c, h, w)
 
 
+def lrn64(x, size, alpha, beta, bias, parts=False):
+    """ONNX LRN over the channel axis: the window [c - (size - 1) // 2, c + size - 1 - (size - 1) // 2] clipped to the channels, alpha / size of
+    its sum of squares whatever the clipping; `parts`: (the window sums of squares, bias + alpha / size * them) as well"""
+    x = np.asarray(x, np.float64)
+    C = x.shape[1]
+    lo = (size - 1) // 2
+    hi = size - 1 - lo
+    sq = np.stack([(x[:, max(c - lo, 0):min(c + hi, C - 1) + 1] ** 2).sum(1) for c in range(C)], 1)
+    base = bias + alpha / size * sq
+    y = x / base ** beta
+    return (y, sq, base) if parts else y
+
+
+def lrn_bar(ref):
+    """the project's parity bar, for what powf and the division add (module docstring)"""
+    return 1e-4 * np.abs(ref) + 1e-6
+
+
 # ---- ops, shapes, reference, bound --------------------------------------------------------------------------------------------------
 
 def conv(M, k=1, s=1, p=0, d=1, g=1, bias=True, act="", add=None, src=None):
@@ -160,6 +187,21 @@ def conv(M, k=1, s=1, p=0, d=1, g=1, bias=True, act="", add=None, src=None):
 
 def pool(kind, k, s=1, p=0, d=1, ceil=False, cip=False, src=None):
     return {"op": kind + "pool", "k": _pair(k), "s": _pair(s), "p": _pads(p), "d": _pair(d), "ceil": ceil, "cip": cip, "src": src}
+
+
+def lrn(size, alpha=1e-4, beta=0.75, bias=1.0, src=None):
+    f = lambda v: float(np.float32(v))  # (the attributes are f32)
+    return {"op": "lrn", "size": size, "alpha": f(alpha), "beta": f(beta), "bias": f(bias), "src": src}
+
+
+def gate(src, gate):
+    """tensor `src` [C, H, W] times tensor `gate` [C, 1, 1] (squeeze and excitation)"""
+    return {"op": "gate", "src": src, "gate": gate}
+
+
+def bn(src=None):
+    """a BatchNormalization with mean 0, variance 1 and epsilon 0: y = scale x + shift with (scale, shift) = weights[op index], as they are"""
+    return {"op": "bn", "src": src}
 
 
 def shapes(case):
@@ -178,7 +220,7 @@ def shapes(case):
         elif o["op"] == "slice":
             sh.append((o["c1"] - o["c0"], h, w))
         else:
-            assert o["op"] == "shuffle", o
+            assert o["op"] in ("shuffle", "lrn", "gate", "bn"), o
             sh.append((c, h, w))
     return sh
 
@@ -232,8 +274,22 @@ def forward64(case, weights, x, bound: bool = False, split=()):
             y, ez = np.concatenate([t[s] for s in o["srcs"]], 1), np.concatenate([e[s] for s in o["srcs"]], 1)
         elif o["op"] == "slice":
             y, ez = h[:, o["c0"]:o["c1"]], eh[:, o["c0"]:o["c1"]]
-        else:
+        elif o["op"] == "shuffle":
             y, ez = shuffle64(h, o["groups"]), shuffle64(eh, o["groups"])
+        elif o["op"] == "gate":
+            g, eg = t[o["gate"]], e[o["gate"]]
+            y = h * g
+            ez = np.abs(g) * eh + np.abs(h) * eg + U * np.abs(y)
+        elif o["op"] == "bn":
+            sc, sf = (np.asarray(v, np.float64)[None, :, None, None] for v in weights[i])
+            y = sc * h + sf
+            ez = np.abs(sc) * eh + 2 * U * (np.abs(sc * h) + np.abs(sf))
+        else:
+            assert o["op"] == "lrn", o
+            y, sq, base = lrn64(h, o["size"], o["alpha"], o["beta"], o["bias"], parts=True)
+            _, cross, _ = lrn64(np.sqrt(np.abs(h) * eh), o["size"], o["alpha"], o["beta"], o["bias"], parts=True)  # the window's sum of |v| e_v
+            e_sq = (o["size"] + 1) * U * sq + 2 * cross
+            ez = eh / base ** o["beta"] + np.abs(y) * o["beta"] * (o["alpha"] / o["size"]) * e_sq / base + lrn_bar(y)
         t.append(y)
         e.append(ez)
     return {"t": t, "out": t[-1], "e": e[-1], "mag": mags}
@@ -241,7 +297,7 @@ def forward64(case, weights, x, bound: bool = False, split=()):
 
 def split_ops(case, plan_exec=None):
     """the op indices of the convolutions the case expects on the bf16x6 kernels"""
-    kinds = [k for k in case["expect"] if k != "convt_phase"]
+    kinds = [k for k in case["expect"] or () if k != "convt_phase"]  # (no list: an NCHW plan, nothing on bf16x6)
     return {i for i, k in enumerate(kinds[:len(case["ops"])]) if k in ("conv_split_bf16x6", "conv_patch_pool_bf16x6")}
 
 
@@ -252,6 +308,12 @@ def error_bound(case, weights, x):
 
 
 # ---- the graph ----------------------------------------------------------------------------------------------------------------------
+
+def through_probe(ref, probe: str):
+    """the f32 tensor `ref` as the probe hands it on: probe A's transposed convolution adds the other channels' 0 * x to 1 * x, so a -0.0 (a negative
+    value times a gate of zero) leaves it as +0.0 and everything else to the bit; probe "" is the tensor itself, the sign of a zero included"""
+    return ref + np.float32(0.0) if probe == "A" and ref.shape[-1] * ref.shape[-2] > 1 else ref
+
 
 def probe_positions(shape, n: int = 48):
     """flat NCHW indices probe B reads: the four corners of the first and the last channel, then a stride through the tensor"""
@@ -306,7 +368,16 @@ def graph(case, weights, probe: str = "A") -> bytes:
         elif o["op"] == "slice":
             inits += [W.tensor(f"s0_{i}", np.array([o["c0"]], np.int64)), W.tensor(f"s1_{i}", np.array([o["c1"]], np.int64)), W.tensor(f"sa_{i}", np.array([1], np.int64))]
             nodes.append(W.node("Slice", [src, f"s0_{i}", f"s1_{i}", f"sa_{i}"], [out]))
+        elif o["op"] == "lrn":
+            nodes.append(W.node("LRN", [src], [out], [W.attr_i("size", o["size"]), W.attr_f("alpha", o["alpha"]), W.attr_f("beta", o["beta"]), W.attr_f("bias", o["bias"])]))
+        elif o["op"] == "gate":
+            nodes.append(W.node("Mul", [src, names[o["gate"]]], [out]))
+        elif o["op"] == "bn":
+            sc, sf = (np.ascontiguousarray(v, np.float32) for v in weights[i])
+            inits += [W.tensor(f"bs{i}", sc), W.tensor(f"bb{i}", sf), W.tensor(f"bm{i}", np.zeros_like(sc)), W.tensor(f"bv{i}", np.ones_like(sc))]
+            nodes.append(W.node("BatchNormalization", [src, f"bs{i}", f"bb{i}", f"bm{i}", f"bv{i}"], [out], [W.attr_f("epsilon", 0.0)]))
         else:
+            assert o["op"] == "shuffle", o
             c, h, w_ = sh[i + 1]
             inits += [W.tensor(f"r5_{i}", np.array([0, o["groups"], c // o["groups"], h, w_], np.int64)), W.tensor(f"r4_{i}", np.array([0, c, h, w_], np.int64))]
             nodes += [W.node("Reshape", [src, f"r5_{i}"], [f"p5_{i}"]), W.node("Transpose", [f"p5_{i}"], [f"q5_{i}"], [W.attr_ints("perm", [0, 2, 1, 3, 4])]),
@@ -382,6 +453,11 @@ def exact_case(case, kind: str, rows: int, seed: int = 0):
     C0, H, Wd = case["inp"]
     weights = {}
     convs = [i for i, o in enumerate(case["ops"]) if o["op"] == "conv"]
+    for i, o in enumerate(case["ops"]):
+        if o["op"] == "bn":  # powers of two and small integers: exact on a grid
+            assert kind == "grid", "s x + t has a rounding"
+            c = sh[i + 1][0]
+            weights[i] = (np.resize(np.array([2, -1, 0.5, 3, -4, 1, -0.25, 5], np.float32), c), ((np.arange(c) * 5) % 11 - 5).astype(np.float32))
     for n, i in enumerate(convs):
         o = case["ops"][i]
         Cin = sh[o["src"] if o.get("src") is not None else i][0]
@@ -414,8 +490,10 @@ def exact_case(case, kind: str, rows: int, seed: int = 0):
                 x[r, :7, y, xx] = (c >> np.arange(7)) & 1
                 x[r, 7, y, xx] = 1.0
         else:
-            for n, (r, y, xx, c) in enumerate(_lattice((H, Wd), last, rows, C0)):
-                x[r, c, y, xx] = np.ldexp(1.0, n % 7 - 3)
+            g, Cg = last["g"], C0 // last["g"]  # one lit channel in EVERY group: each receptive field holds at most one activation per group
+            for n, (r, y, xx, c) in enumerate(_lattice((H, Wd), last, rows, Cg)):
+                for grp in range(g):
+                    x[r, grp * Cg + (c + grp) % Cg, y, xx] = np.ldexp(1.0, (n + grp) % 7 - 3)
         x = x.reshape(rows, -1)
     return weights, x
 
@@ -428,7 +506,13 @@ def assert_exact(case, weights, x, kind: str):
         assert np.array_equal(t.astype(np.float32).astype(np.float64), t), "a tensor of the reference is no f32 value"
     convs = [i for i, o in enumerate(case["ops"]) if o["op"] == "conv"]
     if kind == "grid":
-        assert all(m.max() < 2 ** 24 for m in r["mag"]), [m.max() for m in r["mag"]]
+        # (behind a global average pool of 2^j pixels the values are integers / 2^j: the partial sums stay exact below 2^24 / 2^j)
+        px = [int(np.prod(r["t"][o["src"] if o.get("src") is not None else j].shape[2:])) if o["op"] == "gap" else 1 for j, o in enumerate(case["ops"])]
+        denom = [int(np.prod(px[:i])) for i in convs]
+        assert all(d & (d - 1) == 0 and m.max() * d < 2 ** 24 for d, m in zip(denom, r["mag"])), [m.max() for m in r["mag"]]
+        for i, o in enumerate(case["ops"]):
+            if o["op"] in ("gate", "bn"):  # one product (and one sum) of such values: an f32 value (checked above) with nothing rounded before it
+                assert np.abs(r["t"][i + 1]).max() * max(denom) < 2 ** 24
         for i in convs:
             w, b = weights[i]
             assert np.array_equal(w, np.round(w)) and np.abs(w).max() <= 8 and (b is None or np.array_equal(b, np.round(b)))
@@ -445,8 +529,8 @@ def assert_exact(case, weights, x, kind: str):
                 nz = np.abs(w[w != 0])
                 assert np.array_equal(np.log2(nz), np.round(np.log2(nz)))
             else:
-                ones = conv2d64((src != 0).astype(np.float64), np.ones((1, src.shape[1], *o["k"])), None, o["s"], o["p"], o["d"])
-                assert ones.max() <= 1, "two lit activations in one receptive field"
+                ones = conv2d64((src != 0).astype(np.float64), np.ones((o["g"], src.shape[1] // o["g"], *o["k"])), None, o["s"], o["p"], o["d"], o["g"])
+                assert ones.max() <= 1, "two lit activations in one receptive field of one group"
                 nz = src[src != 0]
                 assert np.array_equal(np.log2(np.abs(nz)), np.round(np.log2(np.abs(nz))))  # one bf16 part each
     return r["out"].astype(np.float32)
@@ -545,6 +629,27 @@ def stem_split6_supported(C, M, k, s) -> bool:
     return M == 64 and k[1] == 7 and s == (2, 2) and (C * k[0] + 1) // 2 == 11
 
 
+def depthwise_supported(C, M, groups) -> bool:
+    return groups == C and M == C and C % 4 == 0
+
+
+GENERIC_CAP = 8192  # conv2d_generic_supported: the k table of (C / groups) kh kw 8-byte entries lives in 64 KiB of LDS
+
+
+def generic_kernel(C, M, groups=1) -> str:
+    """conv2d(): feature tiles of 32 per workgroup by Mg = M / groups -- <= 32: 1, <= 64: 2, else 4 with ceil(Mg / 128) workgroups per group"""
+    Mg = M // groups
+    return f"conv2d_generic_kernel<{1 if Mg <= 32 else 2 if Mg <= 64 else 4}>"
+
+
+def generic_served(C, M, k, groups=1, nchw_in=False) -> bool:
+    """whether a convolution of a channel-quad plan stays on the generic kernel (schedule.cpp assign_conv_kernels): a stem the patch kernel refuses,
+    or a layer that is neither tiled nor depthwise"""
+    if nchw_in:
+        return not patch_supported(C, M, groups)
+    return not tiled_supported(C, M, k, groups) and not depthwise_supported(C, M, groups)
+
+
 # ---- the cases ------------------------------------------------------------------------------------------------------------------------
 
 MAP = (5, 7)       # 35 pixels: 1 / 3 / 5 rows = 35 / 105 / 175 pixels -- under one 128-pixel block, one ragged block, two images astride a block edge
@@ -554,12 +659,12 @@ FP32 = {"INFERA_PRECISION": "fp32", "INFERA_CONV_WS": "0"}
 ALL = ("grid", "select", "onehot")
 
 
-def _under_test(name, C, M, k=1, s=1, p=0, d=1, act="", add=False, ohw=MAP, rows=ROWS, env=FP32, kinds=None, expect="conv_tiled_cq", bias=True):
+def _under_test(name, C, M, k=1, s=1, p=0, d=1, act="", add=False, ohw=MAP, rows=ROWS, env=FP32, kinds=None, expect="conv_tiled_cq", bias=True, g=1):
     """8 -> C 1x1 stem (Relu), then the convolution under test with an `ohw` map; `add`: a residual Add of a second 1x1 branch 8 -> M ... here the
     stem's own output where C == M and the geometry keeps the extent"""
     k, s, d, p = _pair(k), _pair(s), _pair(d), _pads(p)
     hw = in_hw(ohw, k, s, p, d)
-    ops = [conv(C, 1, act="Relu"), conv(M, k, s, p, d, bias=bias, act=act, add=1 if add else None)]
+    ops = [conv(C, 1, act="Relu"), conv(M, k, s, p, d, g=g, bias=bias, act=act, add=1 if add else None)]
     if kinds is None:
         kinds = ("grid",) if add or act not in ("", "Relu") else ALL
     return {"id": name, "inp": (8, *hw), "ops": ops, "env": dict(env), "expect": ["conv_patch", expect] + (["skipped"] if add else []) + ["convt_phase"],
@@ -634,9 +739,9 @@ def shortcut_case(stride=1):
 SPLIT += [shortcut_case(1), shortcut_case(2)]
 
 
-def _stem(name, C, M, k, s=1, p=0, act="", ohw=MAP, rows=ROWS, env=FP32, tail=None, expect="conv_patch", kinds=ALL):
+def _stem(name, C, M, k, s=1, p=0, act="", ohw=MAP, rows=ROWS, env=FP32, tail=None, expect="conv_patch", kinds=ALL, g=1):
     k, s, p = _pair(k), _pair(s), _pads(p)
-    ops = [conv(M, k, s, p, act=act)] + ([tail] if tail else [])
+    ops = [conv(M, k, s, p, g=g, act=act)] + ([tail] if tail else [])
     return {"id": name, "inp": (C, *in_hw(ohw, k, s, p)), "ops": ops, "env": dict(env), "expect": [expect] + (["skipped"] if tail else []) + ["convt_phase"],
             "kinds": kinds, "rows": rows}
 
@@ -734,11 +839,134 @@ GENERIC = [
 ]
 
 
+# ---- conv2d_generic_kernel<MT> and the NCHW forms of its neighbours (tests/test_conv_generic_gpu.py) -----------------------------------
+
+def _plain(case, expect=None):
+    """the case served as the tensor itself: an NCHW plan, every step on the generic kernels"""
+    return dict(case, probe="", layout="NCHW", expect=expect)  # (expect None: every exec kind "normal", however many steps)
+
+
+def _nchw(name, C, M, k=3, s=1, p=1, d=1, g=1, act="", bias=True, ohw=MAP, rows=ROWS, kinds=None):
+    """ONE convolution of the caller's NCHW input, served as it is"""
+    k, s, d, p = _pair(k), _pair(s), _pair(d), _pads(p)
+    if kinds is None:
+        kinds = ALL if act in ("", "Relu") and bias else ("grid",)
+    return _plain({"id": name, "inp": (C, *in_hw(ohw, k, s, p, d)), "ops": [conv(M, k, s, p, d, g=g, bias=bias, act=act)], "env": dict(FP32), "kinds": kinds, "rows": rows})
+
+
+GENERIC_NCHW = [
+    # feature tiles by Mg: <1> to 32, <2> to 64, <4> beyond with ceil(Mg / 128) workgroups per group; 33, 65 and 132 leave a tile almost empty
+    *[_nchw(f"nchw-m{M}", 6, M, rows=(1, 3) if M > 128 else ROWS) for M in (1, 5, 32, 33, 64, 65, 128, 132, 160)],
+    # the k loop takes two taps per step: an odd KK = Cg kh kw and KK = 1 leave the upper lane half on the k < KK guard alone
+    _nchw("nchw-kk27", 3, 8), _nchw("nchw-kk1", 1, 8, 1, p=0), _nchw("nchw-kk5", 5, 8, 1, p=0),
+    # the receptive field: the corner pointer before the image, guarded by the (iy, ix) test alone
+    _nchw("nchw-3x3d2", 6, 8, 3, 1, 2, 2), _nchw("nchw-5x5s2-pads", 6, 8, 5, 2, (2, 1, 0, 2)), _nchw("nchw-1x3-left", 6, 8, (1, 3), 1, (0, 2, 0, 0)),
+    _nchw("nchw-3x1-bottom", 6, 8, (3, 1), 1, (0, 0, 2, 0)), _nchw("nchw-9x9-larger-than-the-map", 6, 8, 9, 1, 4), _nchw("nchw-2x2", 6, 8, 2, 1, 0),
+    # groups: Cg = Mg = 2; Cg = 4, Mg = 6; a depth multiplier of 2; depthwise where the plan is NCHW
+    _nchw("nchw-g3-c6-m6", 6, 6, g=3), _nchw("nchw-g3-c12-m18", 12, 18, g=3), _nchw("nchw-g5-c5-m10", 5, 10, g=5), _nchw("nchw-g6-depthwise", 6, 6, g=6),
+    # epilogues (grid; Sigmoid and Tanh belong to the bound: GENERIC_G)
+    _nchw("nchw-relu", 6, 8, act="Relu", kinds=("grid",)), _nchw("nchw-leaky", 6, 8, act="LeakyRelu"), _nchw("nchw-clip", 6, 8, act="Clip"),
+    _nchw("nchw-nobias", 6, 8, bias=False, kinds=("grid",)),
+    # the LDS cap: KK = 512 x 4 x 4 = 8192 entries of 8 bytes are the whole 64 KiB (no lattice of lit pixels on a 4 x 4 image under a 4 x 4 filter: no onehot)
+    # (a [4, 1, 1] result has no layout to keep NCHW: the plan is in channel quads, its one step the generic kernel with NCHW in and one quad out)
+    dict(_nchw("nchw-kk8192-cap", 512, 4, 4, 1, 0, ohw=(1, 1), rows=(1, 3), kinds=("grid", "select")), layout="NC/4HW4", expect=["normal"]),
+]
+OVER_CAP = dict(_nchw("nchw-kk8256-over-the-cap", 516, 4, 4, 1, 0, ohw=(1, 1), rows=(1,), kinds=("grid",)), layout="NC/4HW4", expect=["normal"])
+
+
+def _quads(name, C, M, k=3, p=1, g=1, kinds=ALL, rows=ROWS):
+    """8 -> C 1x1 stem, then the convolution under test, which the fast channel-quad kernels refuse"""
+    return dict(_under_test(name, C, M, k, 1, p, g=g, kinds=kinds, rows=rows, expect="normal"), probe="A", layout="NC/4HW4")
+
+
+GENERIC_CQ_GROUPED = [
+    _quads("cq-g4-c8-m8-shared-quads", 8, 8, g=4),             # Cg = Mg = 2: two groups in one input quad, scalar stores into quads two groups share
+    _quads("cq-g4-c24-m24-straddling", 24, 24, g=4),           # Cg = Mg = 6: groups straddle quads on both sides
+    _quads("cq-g4-c16-m16-quad-store", 16, 16, g=4),           # Mg = 4: the 16-byte store at grp * Mg + ml
+    _quads("cq-g2-c32-m256-mt4", 32, 256, g=2, rows=(1, 3)),   # Mg = 128: <4>, one full workgroup of features per group
+    _quads("cq-g2-c8-m264-two-tiles", 8, 264, g=2, rows=(1, 3)),  # Mg = 132: two feature workgroups per group, the second almost empty
+    _quads("cq-g8-c8-m16-depth-multiplier", 8, 16, g=8),       # groups == C, M == 2 C: not the depthwise kernel's
+]
+GENERIC_CQ = GENERIC_CQ_GROUPED + [
+    _quads("cq-9x9-81-taps", 8, 8, 9, 4),                      # more than the tiled kernel's 64-bit tap mask
+    # stems the patch kernel refuses: NCHW in, channel quads out
+    dict(_stem("cq-stem-c12-m32", 12, 32, 3, 1, 1, expect="normal"), probe="A", layout="NC/4HW4"),
+    dict(_stem("cq-stem-c3-m160", 3, 160, 3, 1, 1, expect="normal", rows=(1, 3)), probe="A", layout="NC/4HW4"),
+    dict(_stem("cq-stem-c4-m32-g2", 4, 32, 3, 1, 1, expect="normal", g=2), probe="A", layout="NC/4HW4"),
+    # the head: a 1x1 convolution with 10 features on the [C, 1, 1] of a global pool (8 x 8: an exact mean), stored in plain order
+    {"id": "cq-head-m10", "inp": (3, 8, 8), "ops": [conv(12, 1), {"op": "gap"}, conv(10, 1)], "env": dict(FP32), "expect": ["conv_patch", "normal", "normal"],
+     "kinds": ("grid",), "rows": (1, 3), "probe": "A", "layout": "NC/4HW4"},
+]
+
+
+def _neighbour_nchw(name, C, ohw, tail, kinds=("grid", "select"), rows=(1, 3)):
+    """3 -> C 1x1 stem with C no multiple of 4 (or a slice off a quad boundary), so that the plan is NCHW, then `tail`; served as it is"""
+    return _plain(_neighbour(name, C, ohw, tail, [], rows=rows, kinds=kinds))
+
+
+# the geometries of NEIGHBOURS and AVG on pool2d_kernel, the NCHW branches of global_avgpool_kernel, copy_cols and channel_shuffle_planes_kernel<false>
+NEIGHBOURS_NCHW = [
+    _neighbour_nchw("nchw-max3x3s2", 6, (11, 13), [pool("max", 3, 2, 1)]), _neighbour_nchw("nchw-max2x2s2-ceil", 6, (11, 13), [pool("max", 2, 2, 0, ceil=True)]),
+    _neighbour_nchw("nchw-max3x3d2", 6, (11, 13), [pool("max", 3, 1, 2, d=2)]), _neighbour_nchw("nchw-max2x3-pads", 6, (19, 17), [pool("max", (2, 3), 1, (1, 0, 0, 2))]),
+    _neighbour_nchw("nchw-gmp", 6, (5, 7), [{"op": "gmp"}]), _neighbour_nchw("nchw-gap", 6, (8, 8), [{"op": "gap"}], kinds=("grid",)),
+    _neighbour_nchw("nchw-concat", 6, (5, 7), [conv(12, 1, src=0), {"op": "concat", "srcs": [1, 2, 1]}]),
+    _neighbour_nchw("nchw-slice-off-quad", 8, (5, 7), [{"op": "slice", "c0": 2, "c1": 6}]),  # channels 2..5 of 8
+    _neighbour_nchw("nchw-shuffle", 6, (5, 7), [{"op": "shuffle", "groups": 3}]),
+]
+AVG_NCHW = [
+    _neighbour_nchw("nchw-avg3x3s2", 6, (11, 13), [pool("avg", 3, 2, 1)], kinds=("grid",)),
+    _neighbour_nchw("nchw-avg3x3s2-cip", 6, (11, 13), [pool("avg", 3, 2, (1, 0, 1, 2), cip=True)], kinds=("grid",)),
+    _neighbour_nchw("nchw-avg3x3s2-ceil", 6, (12, 14), [pool("avg", 3, 2, 1, ceil=True)], kinds=("grid",)),
+]
+
+
+def _per_channel(name, C, tail, expect, ohw=MAP, kinds=(), rows=(1, 3)):
+    """3 -> C 1x1 stem, then the per-channel operator(s): served in channel quads through probe A and, as_nchw(), in NCHW as it is"""
+    return dict(_neighbour(name, C, ohw, tail, expect, rows=rows, kinds=kinds), probe="A", layout="NC/4HW4")
+
+
+def as_nchw(case):
+    return _plain(case)
+
+
+def lrn_identity(case):
+    """the LRN case with alpha = 0 and bias = 1: pow(1, beta) == 1, y == x to the bit -- pins the element index in either layout"""
+    return dict(case, id=case["id"] + "-identity", ops=[dict(o, alpha=0.0, bias=1.0) if o["op"] == "lrn" else o for o in case["ops"]], kinds=("grid", "select"))
+
+
+_PC = ["normal", "convt_phase"]
+# LRN with an alpha that matters (AlexNet's 1e-4 would hide a wrong window under the bar); generic data and the layout identity only (kinds ())
+LRN = [
+    _per_channel("lrn-size3", 8, [lrn(3, 1.0, 0.75, 1.0)], _PC), _per_channel("lrn-size5", 8, [lrn(5, 2.0, 0.5, 2.0)], _PC),
+    _per_channel("lrn-size5-c4-clipped-both-ends", 4, [lrn(5, 1.0, 0.75, 1.0)], _PC), _per_channel("lrn-size4-even", 8, [lrn(4, 1.5, 0.75, 1.0)], _PC),
+]
+PER_CHANNEL_EXACT = [lrn_identity(c) for c in LRN] + [
+    # squeeze and excitation on an 8 x 8 map (an exact mean): stem, gap, 1x1 convolution, stem * gate
+    _per_channel("gate", 8, [{"op": "gap"}, conv(8, 1, src=2), gate(1, 3)], ["normal", "conv_tiled_cq", "normal", "convt_phase"], ohw=(8, 8), kinds=("grid",)),
+    # a BatchNormalization behind a max pool cannot fold into a convolution: an AffineChannel step
+    _per_channel("bn-behind-maxpool", 8, [pool("max", 3, 2, 1), bn()], ["normal", "normal", "convt_phase"], ohw=(11, 13), kinds=("grid",)),
+]
+PER_CHANNEL = LRN + [
+    _per_channel("g-gate-sigmoid", 8, [{"op": "gap"}, conv(8, 1, src=2, act="Sigmoid"), gate(1, 3)], ["normal", "conv_tiled_cq", "normal", "convt_phase"], ohw=(8, 8)),
+    _per_channel("g-bn-behind-maxpool", 8, [pool("max", 3, 2, 1), bn()], ["normal", "normal", "convt_phase"], ohw=(11, 13)),
+]
+
+# generic data on the generic kernel: NCHW groups 1, grouped in quads, 9x9, a depth multiplier, the Sigmoid and Tanh epilogues
+GENERIC_G = [
+    dict(_nchw("g-nchw-m65", 6, 65, act="Relu", rows=(3,)), kinds=()), dict(_nchw("g-nchw-sigmoid", 6, 33, act="Sigmoid", rows=(3,)), kinds=()),
+    dict(_nchw("g-nchw-g3-tanh", 12, 18, g=3, act="Tanh", rows=(3,)), kinds=()),
+    dict(_quads("g-cq-g4-c24-m24", 24, 24, g=4, rows=(3,)), kinds=()), dict(_quads("g-cq-9x9", 8, 8, 9, 4, rows=(3,)), kinds=()),
+    dict(_quads("g-cq-depth-multiplier", 8, 16, g=8, rows=(3,)), kinds=()),
+]
+
+
 def generic_weights(case, seed: int = 31):
     """U(-1, 1) / sqrt(fan-in) weights and U(-0.1, 0.1) biases"""
     rng = np.random.default_rng([seed, *case["inp"]])
     sh, out = shapes(case), {}
     for i, o in enumerate(case["ops"]):
+        if o["op"] == "bn":
+            out[i] = (rng.uniform(0.5, 2.0, sh[i + 1][0]).astype(np.float32) * rng.choice([-1, 1], sh[i + 1][0]).astype(np.float32), rng.uniform(-1, 1, sh[i + 1][0]).astype(np.float32))
         if o["op"] != "conv":
             continue
         Cg = sh[o["src"] if o.get("src") is not None else i][0] // o["g"]

@@ -134,6 +134,150 @@ def test_the_oracle_serves_the_bits_of_every_exact_case(built, tmp_path, table):
             assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (case["id"], kind)
 
 
+# ---- conv2d_generic_kernel<MT>, the NCHW plans and the per-channel operators (tests/test_conv_generic_gpu.py) ----------------------------
+
+NEW_EXACT = R.GENERIC_NCHW + R.GENERIC_CQ + R.NEIGHBOURS_NCHW + R.PER_CHANNEL_EXACT
+NEW_CASES = NEW_EXACT + R.AVG_NCHW + R.PER_CHANNEL + R.GENERIC_G + [R.OVER_CAP]
+NEW_CASES = NEW_CASES + [R.as_nchw(c) for c in R.GENERIC_CQ_GROUPED + R.PER_CHANNEL_EXACT + R.PER_CHANNEL]  # (the layout bit identity's second run)
+
+
+@pytest.mark.parametrize("size,C", [(3, 8), (5, 8), (5, 4), (4, 8), (1, 5), (9, 6)])
+def test_lrn_reference_agrees_with_torch_float64(size, C):
+    """torch pads size // 2 channels in front, ONNX (size - 1) // 2: the same window for an odd size, the mirrored one for an even size"""
+    import torch
+
+    x = np.random.default_rng(size).standard_normal((2, C, 3, 4))
+    flip = (lambda a: a[:, ::-1].copy()) if size % 2 == 0 else (lambda a: a)
+    want = flip(torch.nn.functional.local_response_norm(torch.from_numpy(flip(x)), size, alpha=0.7, beta=0.6, k=1.5).numpy())
+    _close(R.lrn64(x, size, 0.7, 0.6, 1.5), want)
+    y, sq, base = R.lrn64(x, size, 0.7, 0.6, 1.5, parts=True)
+    lo = (size - 1) // 2
+    assert np.allclose(sq[:, 0], (x[:, :size - lo] ** 2).sum(1)) and np.allclose(base, 1.5 + 0.7 / size * sq)  # (clipped windows still divide by size)
+
+
+def test_gate_and_bn_references_agree_with_torch_float64():
+    import torch
+    import torch.nn.functional as F
+
+    rng = np.random.default_rng(11)
+    x = rng.standard_normal((2, 8, 11, 13))
+    w, b, s, t = rng.standard_normal((8, 8, 1, 1)), rng.standard_normal(8), rng.standard_normal(8).astype(np.float32), rng.standard_normal(8).astype(np.float32)
+    case = {"inp": (8, 11, 13), "ops": [{"op": "gap"}, R.conv(8, 1, act="Sigmoid"), R.gate(0, 2), R.pool("max", 3, 2, 1), R.bn()]}
+    r = R.forward64(case, {1: (w, b), 4: (s, t)}, x.reshape(2, -1), bound=True)
+    xt = torch.from_numpy(x)
+    g = torch.sigmoid(F.conv2d(xt.mean((2, 3), keepdim=True), torch.from_numpy(w), torch.from_numpy(b)))
+    _close(r["t"][3], (xt * g).numpy())
+    want = F.batch_norm(F.max_pool2d(xt * g, 3, 2, 1), torch.zeros(8, dtype=torch.float64), torch.ones(8, dtype=torch.float64) - 2.0 ** -20, torch.from_numpy(s.astype(np.float64)),
+                        torch.from_numpy(t.astype(np.float64)), training=False, eps=2.0 ** -20).numpy()  # (torch wants eps > 0: variance + eps == 1 exactly)
+    _close(r["out"], want)
+    assert R.shapes(case)[-1] == want.shape[1:] and (r["e"] > 0).all()
+
+
+@pytest.mark.parametrize("case", [c for c in R.GENERIC_NCHW + R.GENERIC_CQ if c["ops"][-1]["op"] == "conv"], ids=lambda c: c["id"])
+def test_grouped_conv_reference_agrees_with_torch_float64_on_the_new_geometries(case):
+    import torch
+    import torch.nn.functional as F
+
+    o, sh = case["ops"][-1], R.shapes(case)
+    C, H, Wd = sh[-2]
+    rng = np.random.default_rng(13)
+    x, w, b = rng.standard_normal((2, C, H, Wd)), rng.standard_normal((o["M"], C // o["g"], *o["k"])), rng.standard_normal(o["M"])
+    p = o["p"]
+    want = F.conv2d(F.pad(torch.from_numpy(x), (p[1], p[3], p[0], p[2])), torch.from_numpy(w), torch.from_numpy(b), stride=o["s"], dilation=o["d"], groups=o["g"]).numpy()
+    _close(R.conv2d64(x, w, b, o["s"], o["p"], o["d"], o["g"]), want)
+    assert want.shape[1:] == sh[-1]
+
+
+@pytest.mark.parametrize("case", NEW_EXACT, ids=lambda c: c["id"])
+def test_every_new_exact_case_is_exact(case):
+    assert case["kinds"]
+    for kind in case["kinds"]:
+        w, x = R.exact_case(case, kind, max(case["rows"]))
+        ref = R.assert_exact(case, w, x, kind)
+        assert ref.shape[1:] == R.shapes(case)[-1] and np.count_nonzero(ref) > ref.size // 64, kind
+        if kind != "grid":
+            nz = ref[ref != 0].view(np.uint32)
+            assert (nz & 1).mean() > 0.9, kind
+        if kind == "onehot" and case["ops"][-1]["g"] > 1:  # every group has its lit pixels: no feature's map is all zeros
+            assert (np.abs(ref).sum((0, 2, 3)) > 0).all()
+    if case in R.PER_CHANNEL_EXACT and case["ops"][-1]["op"] == "lrn":  # y == x: the reference of the identity IS its input tensor
+        r = R.forward64(case, w, x)
+        assert np.array_equal(r["t"][-1], r["t"][-2])
+
+
+@pytest.mark.parametrize("case", R.AVG_NCHW, ids=lambda c: c["id"])
+def test_new_average_pool_cases_have_exact_sums(case):
+    w, x = R.exact_case(case, "grid", max(case["rows"]))
+    want = R.avg_exact(case, w, x)
+    ref, bound = R.error_bound(case, w, x)
+    assert (np.abs(want - ref) <= bound).all()
+
+
+@pytest.mark.parametrize("case", NEW_CASES, ids=lambda c: c["id"] + "-" + c["layout"][:4])
+def test_every_new_case_plans_in_the_asserted_layout_on_the_asserted_kernels(built, tmp_path, case):
+    from infera_amd import capi
+
+    w = R.exact_case(case, "grid", 1)[0] if "grid" in case["kinds"] else R.generic_weights(case)
+    path = W.write(str(tmp_path / "m.onnx"), R.graph(case, w, case["probe"]))
+    old = R.set_env(case["env"])
+    try:
+        capi.load_model("conv_ref_plan", path)
+    finally:
+        R.restore_env(old)
+    try:
+        plan = capi.get_plan("conv_ref_plan")
+    finally:
+        capi.unload_model("conv_ref_plan")
+    assert plan["activation_layout"] == case["layout"], plan
+    if case["expect"] is None:
+        assert case["layout"] == "NCHW" and plan["exec"] and all(k == "normal" for k in plan["exec"]), plan["exec"]
+    else:
+        assert plan["exec"] == case["expect"], (plan["exec"], case["expect"])
+
+
+@pytest.mark.parametrize("table", ["GENERIC_NCHW", "GENERIC_CQ", "NEIGHBOURS_NCHW", "PER_CHANNEL_EXACT"])
+def test_the_oracle_serves_the_bits_of_every_new_exact_case(built, tmp_path, table):
+    from oracle import oracle
+
+    for case in getattr(R, table):
+        for kind in case["kinds"]:
+            r = max(case["rows"])
+            w, x = R.exact_case(case, kind, r)
+            want = R.assert_exact(case, w, x, kind)
+            got = oracle.Model(W.write(str(tmp_path / "m.onnx"), R.graph(case, w, ""))).predict_blob(x.tobytes()).reshape(want.shape)
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (case["id"], kind)
+
+
+def _conv_under_test(case):
+    """(C, M, k, groups, the convolution reads the caller's NCHW input) of the case's last convolution"""
+    i = max(j for j, o in enumerate(case["ops"]) if o["op"] == "conv")
+    o = case["ops"][i]
+    return R.shapes(case)[o["src"] if o.get("src") is not None else i][0], o["M"], o["k"], o["g"], i == 0
+
+
+def test_the_new_tables_reach_every_generic_instantiation_and_edge():
+    """from the restated rules (conv.hip conv2d(), schedule.cpp assign_conv_kernels): which instantiation serves each case and why it stays generic"""
+    by_id = {c["id"]: c for c in R.GENERIC_NCHW + R.GENERIC_CQ}
+    kern = {i: R.generic_kernel(*_conv_under_test(c)[:2], _conv_under_test(c)[3]) for i, c in by_id.items()}
+    assert {kern[f"nchw-m{M}"] for M in (1, 5, 32)} == {"conv2d_generic_kernel<1>"} and {kern[f"nchw-m{M}"] for M in (33, 64)} == {"conv2d_generic_kernel<2>"}
+    assert {kern[f"nchw-m{M}"] for M in (65, 128, 132, 160)} == {"conv2d_generic_kernel<4>"}
+    assert kern["cq-g2-c32-m256-mt4"] == kern["cq-g2-c8-m264-two-tiles"] == kern["cq-stem-c3-m160"] == "conv2d_generic_kernel<4>"
+    assert {kern[i] for i in by_id if i.startswith("cq-g4") or i.startswith("cq-g8")} == {"conv2d_generic_kernel<1>"}
+    for c in R.GENERIC_CQ:  # every channel-quad case stays on the generic kernel by the restated rule
+        C, M, k, g, stem = _conv_under_test(c)
+        assert R.generic_served(C, M, k, g, stem), c["id"]
+    assert not R.generic_served(8, 8, (3, 3)) and not R.generic_served(8, 8, (3, 3), 8) and R.generic_served(8, 16, (3, 3), 8) and not R.generic_served(3, 32, (3, 3), 1, True)
+    KK = {i: (lambda C, M, k, g, _: C // g * k[0] * k[1])(*_conv_under_test(c)) for i, c in by_id.items()}
+    assert KK["nchw-kk27"] == 27 and KK["nchw-kk1"] == 1 and KK["nchw-kk5"] == 5 and any(v % 2 for v in KK.values())
+    # Mg & 3 != 0 in channel quads (scalar stores into shared quads), Mg == 4 (the 16-byte store), groups that straddle input quads
+    Mg = {i: c["ops"][-1]["M"] // c["ops"][-1]["g"] for i, c in by_id.items() if i.startswith("cq-g")}
+    assert Mg["cq-g4-c8-m8-shared-quads"] == 2 and Mg["cq-g4-c24-m24-straddling"] == 6 and Mg["cq-g4-c16-m16-quad-store"] == 4 and Mg["cq-g2-c8-m264-two-tiles"] == 132
+    # both sides of the cap
+    assert KK["nchw-kk8192-cap"] == R.GENERIC_CAP and (lambda C, M, k, g, _: C // g * k[0] * k[1])(*_conv_under_test(R.OVER_CAP)) == R.GENERIC_CAP + 64
+    # pixel tails: 35, 105 and 175 pixels -- under one 128-pixel block, one ragged block, images astride a block edge
+    assert [r * R.MAP[0] * R.MAP[1] for r in R.ROWS] == [35, 105, 175] and all(c["rows"] == R.ROWS for i, c in by_id.items() if i in ("nchw-m33", "cq-g4-c8-m8-shared-quads"))
+
+
 def test_the_tables_reach_every_instantiation():
     """from the restated rules (conv.hip conv2d_tiled / launch_ws, conv_split.hip conv2d_split6, conv2d_patch): what each table's launches are"""
     tiled = {R.tiled_kernel(*R.conv_under_test(c), R.total_pix(c, r)) for c in R.TILED for r in c["rows"]}
