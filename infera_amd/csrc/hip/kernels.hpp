@@ -376,6 +376,13 @@ bool tokens(hipStream_t s, const float *X, const float *prefix, const float *pos
 bool embed(hipStream_t s, const float *x, int W, const int32_t *desc, int P, const uint16_t *map, int map_entries, const float *tab, float *y, int64_t F,
            int64_t rows, int R, bool staged, int *err, bool nt = false);
 
+// ---- Interact: DLRM's pairwise dot products and the FM bi-interaction term of a window T [rows, k, d] (interact.hip; host/interact.hpp) ----
+// dot: out [rows, F]; map [F]: per output column >= 0 the entry i * tile + j of Z = T . T^T, < 0: -(column of T's flat row) - 1, a bit copy;
+// tile: 16, 32 or 64 >= k.  fm: out [rows, d] = h * ((sum_f T)^2 - sum_f T^2) (has_h = false: no multiply), sum_last: [rows, 1], its sum
+// over the d columns (h_after: multiplied by h after the sum, not before).  false: beyond the caps
+bool interact_dot(hipStream_t s, const float *T, int k, int d, int tile, const int32_t *map, int64_t F, float *out, int64_t rows);
+bool interact_fm(hipStream_t s, const float *T, int k, int d, float h, bool has_h, bool h_after, bool sum_last, float *out, int64_t rows);
+
 // ---- LayerNorm over the channel axis at each pixel (channelnorm.hip; host/channelnorm.hpp) --------------
 // X, Y: [rows, C, S] in NCHW order or (cq) channel-quad planes, the same layout; gamma [C], beta [C] or null.  regs: the register form
 // (C <= kChannelNormRegsMaxC), else the re-read form.  y = act(d / sqrtf(var + eps) * gamma + beta).  false: beyond the kernel's caps

@@ -8,6 +8,7 @@
 #include "../host/deconv.hpp"
 #include "../host/spatialnorm.hpp"
 #include "../host/embed.hpp"
+#include "../host/interact.hpp"
 #include "runtime.hpp"
 
 namespace infera_hip {
@@ -525,7 +526,9 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
                               sk == StepKind::Recurrent ||  // (one dependent fetch per time step: from HBM, not over PCIe)
                               // (staged, an Embed step loads each row tile of the input once: a streaming reader; a source row too wide
                               // for the tile is read where it lies, its index once per quad of a lookup piece)
-                              (sk == StepKind::Embed && !st[size_t(e.idx)].embed->staged);
+                              (sk == StepKind::Embed && !st[size_t(e.idx)].embed->staged) ||
+                              // (an Interact step streams T once; its pass-through columns are fetched a second time)
+                              (sk == StepKind::Interact && !st[size_t(e.idx)].interact->passes.empty());
         m.in_single_reader = !windowed;
         break;
       }

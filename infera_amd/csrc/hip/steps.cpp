@@ -5,6 +5,7 @@
 
 #include "../host/deconv.hpp"
 #include "../host/embed.hpp"
+#include "../host/interact.hpp"
 #include "../host/nearest.hpp"
 #include "../host/channelnorm.hpp"
 #include "../host/onnx_model.hpp"
@@ -443,6 +444,18 @@ void launch_embed(const PassRunner &r, const Step &x, const EmbedTables &t) {
     throw InferaError::onnx("Embed kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
 }
 
+// ---- Interact (host/interact.hpp InteractPack, interact.hip): dot mode's output column map; fm mode has no tables ----
+void upload_interact(const Step &s, InteractTables &t, const Upload &up) {
+  if (s.interact->mode == kInteractDot) t.map = up(s.interact->map);
+}
+void launch_interact(const PassRunner &r, const Step &x, const InteractTables &t) {
+  const InteractPack &q = *x.interact;
+  if (r.in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: an Interact step reads its input row-major");
+  const bool ok = q.mode == kInteractDot ? kern::interact_dot(r.stream, r.buf(x.in0), int(q.k), int(q.d), q.tile, t.map, q.F, r.buf(x.out), r.nr)
+                                         : kern::interact_fm(r.stream, r.buf(x.in0), int(q.k), int(q.d), q.h, q.has_h, q.h_after, q.sum_last, r.buf(x.out), r.nr);
+  if (!ok) throw InferaError::onnx("Interact kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+
 // ---- the plain family: the step's constants as the lowering left them (Conv2d: packed for the generic kernel); its launches are the head
 // of PassRunner::launch_plain, right below ----
 void upload_plain(const Step &s, PlainTables &t, const Upload &up) {
@@ -502,6 +515,7 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::Tokens: launch_tokens(*this, x, d.tokens); break;
     case StepKind::ChannelNorm: launch_channelnorm(*this, x, d.channelnorm); break;
     case StepKind::Embed: launch_embed(*this, x, d.embed); break;
+    case StepKind::Interact: launch_interact(*this, x, d.interact); break;
     // the steps without tables
     case StepKind::Unary: kern::unary(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], act_of(x)); break;
     case StepKind::BinaryAct:
@@ -574,6 +588,7 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::Tokens: return upload_tokens(s, d.tokens, up);
     case StepKind::ChannelNorm: return upload_channelnorm(s, d.channelnorm, up);
     case StepKind::Embed: return upload_embed(s, d.embed, up);
+    case StepKind::Interact: return upload_interact(s, d.interact, up);
     default: return;  // (no tables)
   }
 }

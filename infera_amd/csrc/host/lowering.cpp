@@ -27,6 +27,7 @@
 #include "common.hpp"
 #include "deconv.hpp"
 #include "embed.hpp"
+#include "interact.hpp"
 #include "spatialnorm.hpp"
 #include "tokens.hpp"
 #include "nearest.hpp"
@@ -2796,7 +2797,7 @@ struct Lowerer {
     for (size_t qi = 0; qi < N; qi++) {
       const NodeDef &qk = m.nodes[qi];
       if (!live[qi] || qk.op != "MatMul" || !(qk.domain.empty() || qk.domain == "ai.onnx") || qk.inputs.size() != 2 || is_const(qk.inputs[0]) || is_const(qk.inputs[1])) continue;
-      if (absorbed[qi]) continue;  // (the P V product of a pattern already matched)
+      if (absorbed[qi] || interact_at.count(qi)) continue;  // (the P V product of a pattern already matched; T . T^T of an Interact step)
       AttnMatch am;
       am.qk = &qk;
       am.nodes.push_back(qi);
@@ -5339,6 +5340,518 @@ struct Lowerer {
     set_act(anchor, out_buf, shape);
   }
 
+  // ---- feature interactions (host/interact.hpp; INTEGRATION.md 2.6 "Feature interactions") ---------------------------------------------
+  // dot: MatMul(T, Transpose(T, perm = [0,2,1])) of ONE value T [N, k, d], read whole or through Flatten / Reshape -> Gather(axis = 1) by a
+  // constant list; the axis-1 Concat that alone reads the selection beside inputs of the Concat that built T joins the step (pass-through).
+  // fm: Sub(square(ReduceSum(T, [1])), ReduceSum(square(T), [1])), the constant scalar Mul and the last-axis ReduceSum behind it.
+  // Found before the walk by structure (find_interactions); shapes are known, and the caps checked, where the step is emitted
+  // (lower_interact).  A graph without either pattern is lowered exactly as before.
+  struct InteractView {
+    size_t node = 0;
+    std::vector<int64_t> target;  // Reshape: its constant target; Flatten: {axis}; Identity: empty
+    bool back = false;            // the advanced-index form: behind its Transpose(1,0), where the value is [N, P] (else [P, N])
+  };
+  struct InteractMatch {
+    int mode = kInteractDot;
+    std::string T;
+    std::vector<size_t> nodes;  // every node the step stands for but the anchor
+    size_t product = 0;         // dot: the MatMul; fm: the Sub
+    // dot
+    std::vector<InteractView> views;  // between the product and the Gather
+    size_t gather = SIZE_MAX;         // SIZE_MAX: the whole matrix
+    std::vector<int64_t> idx;
+    // TorchScript's advanced-index form: Gather(axis = 0) of the transposed, flattened matrix by `index_value` (evaluated once k is known)
+    bool advanced = false;
+    std::string index_value, selection_value;  // selection_value: the name of the selection [N, P] a pass-through Concat reads
+    std::vector<InteractView> views_after;     // behind its Gather: in front of the Transpose(1,0) and behind it (InteractView::back)
+    size_t out_concat = SIZE_MAX, t_concat = SIZE_MAX;  // pass-through: the Concat that reads the selection, the Concat that built T
+    // fm
+    bool keep = false;  // keepdims of the two field sums
+    double h = 1.0;
+    bool has_h = false, h_after = false;
+    size_t last_sum = SIZE_MAX;  // the trailing ReduceSum
+  };
+  std::map<size_t, InteractMatch> interact_at;  // anchor (the last node of the pattern) -> the pattern
+
+  // lax: a Reshape whose target is computed (from Shape nodes) counts too; lower_interact evaluates it
+  bool interact_is_view(const NodeDef &r, const std::string &cur, InteractView *v, bool lax = false) const {
+    if (!graph->std_dom(r) || r.outputs.empty() || r.inputs.empty() || r.inputs[0] != cur) return false;
+    v->target.clear();
+    if (r.op == "Identity") return true;
+    if (r.op == "Flatten") return v->target = {r.attr_i("axis", 1)}, true;
+    std::vector<int64_t> dims;
+    if (r.op != "Reshape" || r.inputs.size() != 2) return false;
+    return (graph_const_ints(r.inputs[1], &v->target, &dims) && !v->target.empty()) || (lax && !graph->row_data.count(r.inputs[1]));
+  }
+  // x * x or x ^ 2: the value squared ("" = n is no square)
+  std::string interact_squared(const NodeDef &n) const {
+    if (!graph->std_dom(n) || n.inputs.size() != 2) return "";
+    if (n.op == "Mul" && n.inputs[0] == n.inputs[1]) return n.inputs[0];
+    double e = 0;
+    size_t cnt = 0;
+    if (n.op == "Pow" && graph_const_scalar(n.inputs[1], &e, &cnt) && cnt == 1 && e == 2.0) return n.inputs[0];
+    return "";
+  }
+  // ReduceSum over exactly `axis_a` or `axis_b`
+  bool interact_sum_over(const NodeDef &n, int64_t axis_a, int64_t axis_b) const {
+    std::vector<int64_t> ax;
+    if (!graph->std_dom(n) || n.op != "ReduceSum" || n.inputs.empty() || n.attr_i("noop_with_empty_axes", 0) != 0 || !graph_ints_arg(n, 1, "axes", &ax)) return false;
+    return ax.size() == 1 && (ax[0] == axis_a || ax[0] == axis_b);
+  }
+
+  // the node that alone reads the DATA of `v`: Shape nodes read its shape only and do not count (null: several, none, a graph output)
+  const NodeDef *interact_data_reader(const std::string &v) const {
+    auto it = graph->consumers_of.find(v);
+    if (it == graph->consumers_of.end() || graph->graph_outs.count(v)) return nullptr;
+    const NodeDef *one = nullptr;
+    for (size_t c : it->second) {
+      if (m.nodes[c].op == "Shape") continue;
+      if (one) return nullptr;
+      one = &m.nodes[c];
+    }
+    return one;
+  }
+  // The values the step absorbs exist nowhere: the Shape nodes that read them, and everything computed from those and constants alone (the
+  // targets of the pattern's Reshapes, TorchScript's li * k + lj), must feed the pattern only.  They join im.nodes.  false: something else reads one
+  bool interact_shape_closure(InteractMatch &im, size_t anchor) const {
+    std::set<size_t> mine(im.nodes.begin(), im.nodes.end());
+    std::set<std::string> gone, derived;
+    for (size_t i : im.nodes)
+      for (const auto &o : m.nodes[i].outputs) gone.insert(o);
+    std::set<size_t> extra;
+    for (size_t i = 0; i < m.nodes.size(); i++) {
+      const NodeDef &n = m.nodes[i];
+      if (!graph->live[i] || mine.count(i) || i == anchor || n.inputs.empty()) continue;
+      bool any = false, all = true;
+      if (n.op == "Shape") {
+        any = gone.count(n.inputs[0]) > 0 || derived.count(n.inputs[0]) > 0;
+      } else {
+        for (const auto &in : n.inputs) {
+          if (in.empty()) continue;
+          any = any || derived.count(in);
+          all = all && (derived.count(in) || !graph->row_data.count(in));
+        }
+      }
+      if (!any || !all) continue;
+      extra.insert(i);
+      for (const auto &o : n.outputs) derived.insert(o);
+    }
+    for (const auto &v : gone)  // an absorbed value: read by the pattern, or by a Shape node of the closure
+      if (auto it = graph->consumers_of.find(v); it != graph->consumers_of.end())
+        for (size_t c : it->second)
+          if (!mine.count(c) && c != anchor && !extra.count(c)) return false;
+    for (const auto &v : derived) {
+      if (graph->graph_outs.count(v)) return false;
+      if (auto it = graph->consumers_of.find(v); it != graph->consumers_of.end())
+        for (size_t c : it->second)
+          if (!mine.count(c) && c != anchor && !extra.count(c)) return false;
+    }
+    im.nodes.insert(im.nodes.end(), extra.begin(), extra.end());
+    return true;
+  }
+  // an integer tensor known at load once k is: constants, Shape of the product ([rows, k, k], rows = kInteractDyn), Gather / Concat /
+  // Mul / Add / Sub and the shape-preserving operators over those.  false: something else
+  static constexpr int64_t kInteractDyn = INT64_MIN;
+  bool interact_eval(const std::string &v, const std::string &z, int64_t k, std::vector<int64_t> *out, int depth = 0) const {
+    std::vector<int64_t> dims;
+    if (graph_const_ints(v, out, &dims)) return true;
+    const NodeDef *p = graph->producer(v);
+    if (!p || depth > 32 || !graph->std_dom(*p) || p->inputs.empty()) return false;
+    std::vector<int64_t> a, b;
+    if (p->op == "Shape") {
+      if (p->inputs[0] == z) return *out = {kInteractDyn, k, k}, true;
+      if (!interact_eval(p->inputs[0], z, k, &a, depth + 1)) return false;
+      return *out = {int64_t(a.size())}, true;  // (of a list)
+    }
+    if (p->op == "Cast" || p->op == "Identity" || p->op == "Unsqueeze" || p->op == "Squeeze" || p->op == "Reshape") return interact_eval(p->inputs[0], z, k, out, depth + 1);
+    if (p->op == "Concat") {
+      out->clear();
+      for (const auto &in : p->inputs) {
+        if (!interact_eval(in, z, k, &a, depth + 1)) return false;
+        out->insert(out->end(), a.begin(), a.end());
+      }
+      return true;
+    }
+    if (p->inputs.size() != 2 || !interact_eval(p->inputs[0], z, k, &a, depth + 1) || !interact_eval(p->inputs[1], z, k, &b, depth + 1)) return false;
+    out->clear();
+    if (p->op == "Gather") {
+      if (p->attr_i("axis", 0) != 0) return false;
+      for (int64_t ix : b) {
+        if (ix < 0) ix += int64_t(a.size());
+        if (ix < 0 || ix >= int64_t(a.size())) return false;
+        out->push_back(a[size_t(ix)]);
+      }
+      return true;
+    }
+    if (p->op != "Mul" && p->op != "Add" && p->op != "Sub") return false;
+    if (a.size() != b.size() && a.size() != 1 && b.size() != 1) return false;
+    for (size_t i = 0; i < std::max(a.size(), b.size()); i++) {
+      const int64_t x = a[a.size() == 1 ? 0 : i], y = b[b.size() == 1 ? 0 : i];
+      int64_t r = 0;
+      if (x == kInteractDyn || y == kInteractDyn) return false;
+      if (p->op == "Mul" ? __builtin_mul_overflow(x, y, &r) : p->op == "Add" ? __builtin_add_overflow(x, y, &r) : __builtin_sub_overflow(x, y, &r)) return false;
+      out->push_back(r);
+    }
+    return true;
+  }
+
+  void find_interactions() {
+    const size_t N = m.nodes.size();
+    auto claim = [&](const InteractMatch &im, size_t anchor) {
+      for (size_t i : im.nodes) absorbed[i] = 1, region[i] = 0;
+      region[anchor] = 0;
+    };
+    for (size_t i = 0; i < N; i++) {
+      const NodeDef &n = m.nodes[i];
+      if (!graph->live[i] || absorbed[i] || !graph->std_dom(n) || n.inputs.size() != 2 || n.outputs.empty()) continue;
+      if (n.op == "MatMul" && graph->row_data.count(n.inputs[0]) && graph->row_data.count(n.inputs[1])) {
+        size_t ti = 0;
+        const NodeDef *tp = graph->producer(n.inputs[1], &ti);
+        const auto *perm = tp ? tp->attr_ints("perm") : nullptr;
+        // both operands are one value, the right one through Transpose(0,2,1) that nothing else reads: anything else keeps its refusal
+        if (!tp || tp->op != "Transpose" || !graph->std_dom(*tp) || tp->inputs.size() != 1 || tp->inputs[0] != n.inputs[0] || !perm ||
+            *perm != std::vector<int64_t>{0, 2, 1} || graph->sole_reader(n.inputs[1], false) != &n)
+          continue;
+        InteractMatch im;
+        im.T = n.inputs[0];
+        im.product = i;
+        im.nodes = {ti};
+        // Flatten / Reshape / Identity hops to a Gather(axis = 1) by a constant list, or TorchScript's Z[:, li, lj]: Transpose(1,2,0) ->
+        // Flatten(2) -> Gather(axis = 0) -> Reshape -> Transpose(1,0) -> Reshape, matched by the data it moves (the Shape sub-graphs that
+        // feed its Reshapes and its index are checked below).  Without either the product itself is the step
+        std::string cur = n.outputs[0];
+        std::vector<InteractView> views;
+        size_t anchor = i;
+        auto hop_views = [&](std::vector<InteractView> *vs, bool lax = false) {
+          for (;;) {
+            const NodeDef *r = interact_data_reader(cur);
+            InteractView v;
+            if (!r || !interact_is_view(*r, cur, &v, lax)) return r;
+            v.node = size_t(r - m.nodes.data());
+            vs->push_back(v);
+            cur = r->outputs[0];
+          }
+        };
+        auto is_gather = [&](const NodeDef *r) { return r && r->op == "Gather" && graph->std_dom(*r) && r->inputs.size() == 2 && r->inputs[0] == cur && !r->outputs.empty(); };
+        auto is_transpose = [&](const NodeDef *r, const std::vector<int64_t> &want) {
+          const auto *pm = r && r->op == "Transpose" && graph->std_dom(*r) && r->inputs.size() == 1 && r->inputs[0] == cur && !r->outputs.empty() ? r->attr_ints("perm") : nullptr;
+          return pm && *pm == want;
+        };
+        const NodeDef *r = hop_views(&views);
+        std::vector<int64_t> dims;
+        if (is_gather(r) && graph_const_ints(r->inputs[1], &im.idx, &dims) && dims.size() == 1) {
+          im.gather = size_t(r - m.nodes.data());
+          im.views = views;
+          im.nodes.push_back(i);
+          for (const InteractView &w : views) im.nodes.push_back(w.node);
+          anchor = im.gather;
+        } else if (views.empty() && is_transpose(r, {1, 2, 0})) {
+          InteractMatch t3 = im;
+          t3.nodes.push_back(i);
+          t3.nodes.push_back(size_t(r - m.nodes.data()));
+          cur = r->outputs[0];
+          const NodeDef *g = hop_views(&t3.views, true);
+          if (is_gather(g) && !graph->row_data.count(g->inputs[1])) {
+            t3.gather = size_t(g - m.nodes.data());
+            t3.index_value = g->inputs[1];
+            cur = g->outputs[0];
+            const NodeDef *tb = hop_views(&t3.views_after, true);
+            if (is_transpose(tb, {1, 0})) {
+              for (const InteractView &w : t3.views) t3.nodes.push_back(w.node);
+              t3.nodes.push_back(t3.gather);
+              for (const InteractView &w : t3.views_after) t3.nodes.push_back(w.node);
+              size_t last = size_t(tb - m.nodes.data());
+              cur = tb->outputs[0];
+              // the Reshape to [N, P] behind it (and nothing that flattens further)
+              for (;;) {
+                const NodeDef *v = interact_data_reader(cur);
+                InteractView w;
+                if (!v || (v->op != "Reshape" && v->op != "Identity") || !graph->std_dom(*v) || v->inputs.empty() || v->inputs[0] != cur || v->outputs.empty()) break;
+                w.node = size_t(v - m.nodes.data());
+                w.back = true;
+                t3.views_after.push_back(w);
+                t3.nodes.push_back(last);
+                last = w.node;
+                cur = v->outputs[0];
+              }
+              t3.advanced = true;
+              im = std::move(t3);
+              anchor = last;
+              im.selection_value = cur;
+            }
+          }
+        }
+        if (im.gather != SIZE_MAX) {
+          // pass-through: the selection's only reader is an axis-1 Concat whose other inputs are inputs of the Concat that built T
+          const std::string selv = im.advanced ? im.selection_value : m.nodes[im.gather].outputs[0];
+          const NodeDef *oc = graph->sole_reader(selv, false);
+          std::string tv = im.T;
+          size_t tci = 0;
+          const NodeDef *tc = graph->producer(tv, &tci);
+          InteractView ignore;
+          while (tc && tc->op != "Concat" && !tc->inputs.empty() && interact_is_view(*tc, tc->inputs[0], &ignore)) tc = graph->producer(tc->inputs[0], &tci);
+          auto axis1 = [&](const NodeDef *c) { return c && c->op == "Concat" && graph->std_dom(*c) && !c->outputs.empty() && (c->attr_i("axis", 1) == 1 || c->attr_i("axis", 1) == -1); };
+          if (axis1(oc) && axis1(tc) && oc->inputs.size() > 1) {
+            bool ok = true;
+            int mine = 0;
+            for (const auto &in : oc->inputs) {
+              if (in == selv) mine++;
+              else ok = ok && std::find(tc->inputs.begin(), tc->inputs.end(), in) != tc->inputs.end();
+            }
+            if (ok && mine == 1) {
+              im.out_concat = size_t(oc - m.nodes.data());
+              im.t_concat = tci;
+              im.nodes.push_back(anchor);
+              anchor = im.out_concat;
+              im.selection_value = selv;
+            }
+          }
+        }
+        if (!interact_shape_closure(im, anchor)) continue;  // (an absorbed value has a reader the step does not stand for)
+        claim(im, anchor);
+        interact_at[anchor] = std::move(im);
+        continue;
+      }
+      if (n.op != "Sub") continue;
+      // fm: Sub(square(S), QS), S = ReduceSum(T, [1]), QS = ReduceSum(square(T), [1]); every inner value has this one reader
+      size_t ssi = 0, qsi = 0, si = 0, qi = 0;
+      const NodeDef *ss = graph->producer(n.inputs[0], &ssi), *qs = graph->producer(n.inputs[1], &qsi);
+      if (!ss || !qs || !interact_sum_over(*qs, 1, -2)) continue;
+      const std::string sv = interact_squared(*ss);
+      const NodeDef *s = sv.empty() ? nullptr : graph->producer(sv, &si);
+      const NodeDef *q = graph->producer(qs->inputs[0], &qi);
+      if (!s || !q || !interact_sum_over(*s, 1, -2)) continue;
+      const std::string tv = interact_squared(*q);
+      if (tv.empty() || tv != s->inputs[0] || !graph->row_data.count(tv)) continue;
+      if (s->attr_i("keepdims", 1) != qs->attr_i("keepdims", 1)) continue;
+      if (graph->sole_reader(sv, true) != ss || graph->sole_reader(n.inputs[0], false) != &n || graph->sole_reader(n.inputs[1], false) != &n ||
+          graph->sole_reader(qs->inputs[0], false) != qs)
+        continue;  // (an inner value with a second reader: the operators keep their own lowering and refusals)
+      InteractMatch im;
+      im.mode = kInteractFm;
+      im.T = tv;
+      im.product = i;
+      im.keep = s->attr_i("keepdims", 1) != 0;
+      im.nodes = {si, ssi, qi, qsi};
+      size_t anchor = i;
+      // behind it: a constant scalar Mul and a ReduceSum over the last axis, in either order, each at most once
+      for (;;) {
+        const NodeDef &a = m.nodes[anchor];
+        const NodeDef *r = graph->sole_reader(a.outputs[0], false);
+        if (!r || !graph->std_dom(*r) || r->outputs.empty()) break;
+        const size_t ri = size_t(r - m.nodes.data());
+        double hv = 0;
+        size_t cnt = 0;
+        if (!im.has_h && r->op == "Mul" && r->inputs.size() == 2 && r->inputs[0] != r->inputs[1] &&
+            graph_const_scalar(r->inputs[r->inputs[0] == a.outputs[0] ? 1 : 0], &hv, &cnt) && cnt == 1) {
+          im.has_h = true, im.h = hv, im.h_after = im.last_sum != SIZE_MAX;
+        } else if (im.last_sum == SIZE_MAX && interact_sum_over(*r, -1, im.keep ? 2 : 1) && r->inputs[0] == a.outputs[0]) {
+          im.last_sum = ri;
+        } else {
+          break;
+        }
+        im.nodes.push_back(anchor);
+        anchor = ri;
+      }
+      claim(im, anchor);
+      interact_at[anchor] = std::move(im);
+    }
+  }
+
+  // The fm pattern is claimed by structure, before any shape is known.  On anything but a plain rank-3 activation it is not the
+  // bi-interaction of a window -- on [N, k] axis 1 is the last axis and the same operators are the FM term over scalar fields, which the
+  // single-operator lowering serves (RowReduce, BinaryAct) -- so the claim is given up and the nodes lower as they always did.  (T . T^T
+  // has no such reading: Transpose(0,2,1) needs rank 3.)
+  bool interact_released(const InteractMatch &im) const {
+    if (im.mode != kInteractFm) return false;
+    auto it = vals.find(im.T);
+    if (it == vals.end()) return true;
+    const Val &t = it->second;
+    return t.is_const || t.pv || t.nn || t.q || t.cl || t.padded() || t.half || t.buf < 0 || t.shape.size() != 3;
+  }
+
+  void lower_interact(const InteractMatch &im, const NodeDef &anchor) {
+    const NodeDef &pn = m.nodes[im.product];
+    auto it = vals.find(im.T);
+    if (it == vals.end()) unsupported(pn, "input '" + im.T + "' is not produced by any earlier node");
+    if (it->second.pv) materialize(im.T, &pn);
+    if (it->second.nn) materialize_nearest(im.T);
+    const Val t = vals.at(im.T);
+    const char *what = im.mode == kInteractDot ? "T . T^T" : "the bi-interaction term";
+    if (t.is_const || t.q || t.cl || t.padded() || t.half || t.buf < 0) bad_form(pn, std::string(what) + " of a value that is no plain f32 activation");
+    if (t.shape.size() != 3)
+      bad_form(pn, std::string(what) + " of " + shape_str(t.shape) + "; T must be a window [N, k, d]" + (t.shape.size() == 2 ? " ([N,F] x [F,N] mixes rows)" : ""));
+    if (t.ra != 0)
+      bad_form(pn, std::string(what) + " of a time-major value " + shape_str(t.shape) + " (its row axis is axis " + std::to_string(t.ra) + "); T must be rows first, [N, k, d]");
+    const int64_t N = t.shape[0], k = t.shape[1], d = t.shape[2];
+    if (t.buf > 0 && plan.buf_shape[size_t(t.buf)].size() != 2) {
+      // [N, k, d] built by an axis-1 Concat is registered as an [N, C, 1, L] tensor: its rows are flat, and it is a window from here on
+      for (const Step &s : plan.steps)
+        if (s.out == t.buf && s.kind != StepKind::CopyCols) bad_form(pn, std::string(what) + " of an [N,C,L] tensor a " + s.origin + " step wrote, not a window of a flat table");
+      plan.buf_shape[size_t(t.buf)] = {N, k * d};
+    }
+    auto pack = std::make_shared<InteractPack>();
+    pack->mode = im.mode, pack->k = k, pack->d = d;
+    Step s;
+    s.kind = StepKind::Interact;
+    s.in0 = t.buf;
+    s.rep = k, s.K = d;
+    std::vector<size_t> all = im.nodes;
+    all.push_back(size_t(&anchor - m.nodes.data()));
+    std::sort(all.begin(), all.end());
+    for (size_t i : all) s.origin += (s.origin.empty() ? "" : "+") + node_label(m.nodes[i]);
+    std::vector<int64_t> shape;
+    if (im.mode == kInteractFm) {
+      if (const std::string why = interact_refusal(k, d, 0); !why.empty()) bad_form(pn, why);
+      pack->has_h = im.has_h, pack->h = float(im.h), pack->sum_last = im.last_sum != SIZE_MAX, pack->h_after = im.h_after;
+      shape = im.keep ? std::vector<int64_t>{N, 1, d} : std::vector<int64_t>{N, d};
+      if (pack->sum_last) {
+        if (m.nodes[im.last_sum].attr_i("keepdims", 1) != 0) shape.back() = 1;
+        else shape.pop_back();
+      }
+    } else if (im.gather == SIZE_MAX) {
+      if (const std::string why = interact_refusal(k, d, 0); !why.empty()) bad_form(pn, why);
+      pack->whole = true;
+      pack->sel.resize(size_t(k * k));
+      std::iota(pack->sel.begin(), pack->sel.end(), int64_t(0));
+      shape = {N, k, k};
+    } else if (im.advanced) {
+      // Transpose(1,2,0) -> [k, k, N]; the views arrive at [k * k, N]; Gather(axis = 0) -> [P, N]; views of rank 2; Transpose(1,0) ->
+      // [N, P]; views of rank 2
+      const NodeDef &gn = m.nodes[im.gather];
+      const std::string &zname = pn.outputs[0];
+      int flattened = 0;
+      auto target_rank = [&](const InteractView &v, std::vector<int64_t> *tgt) {
+        const NodeDef &vn = m.nodes[v.node];
+        return vn.op == "Reshape" && vn.inputs.size() == 2 && interact_eval(vn.inputs[1], zname, k, tgt);
+      };
+      // a Reshape in front of the Gather names [k * k, N] and nothing else: k * k or -1, then the rows (of Shape(Z)) or -1, not both -1
+      auto flat_target = [&](const std::vector<int64_t> &tgt) {
+        return tgt.size() == 2 && (tgt[0] == k * k || tgt[0] == -1) && (tgt[1] == kInteractDyn || tgt[1] == -1) && !(tgt[0] == -1 && tgt[1] == -1);
+      };
+      for (const InteractView &v : im.views) {
+        const NodeDef &vn = m.nodes[v.node];
+        std::vector<int64_t> tgt;
+        if (vn.op == "Identity") continue;
+        if (vn.op == "Flatten" && v.target[0] == 2 && !flattened) flattened++;
+        else if (vn.op == "Reshape" && target_rank(v, &tgt) && flat_target(tgt)) flattened += flattened ? 0 : 1;  // ([k * k, N] stays [k * k, N])
+        else bad_form(vn, "between Transpose(1,2,0) of the products and their Gather(axis = 0) only the flattening of [k, k, N] to [k * k, N] is matched");
+      }
+      if (flattened != 1 || (gn.attr_i("axis", 0) != 0 && gn.attr_i("axis", 0) != -2))
+        bad_form(gn, "Gather(axis = " + std::to_string(gn.attr_i("axis", 0)) + ") behind Transpose(1,2,0) of the products; only axis 0 of the flattened [k * k, N] matrix");
+      std::vector<int64_t> idx;
+      if (!interact_eval(im.index_value, zname, k, &idx) || idx.empty())
+        bad_form(gn, "its index list is not a constant (constants, Shape of the products, Gather, Mul, Add, Concat over them are folded)");
+      const int64_t P = int64_t(idx.size());
+      for (const InteractView &v : im.views_after) {  // [P, N] in front of the Transpose(1,0), [N, P] behind it: a Reshape keeps that
+        const NodeDef &vn = m.nodes[v.node];
+        std::vector<int64_t> tgt;
+        if (vn.op == "Identity") continue;
+        auto rows_dim = [](int64_t x) { return x == kInteractDyn || x == -1; };
+        auto p_dim = [&](int64_t x) { return x == P || x == -1; };
+        const bool ok = vn.op == "Reshape" && target_rank(v, &tgt) && tgt.size() == 2 && !(tgt[0] == -1 && tgt[1] == -1) &&
+                        (v.back ? (rows_dim(tgt[0]) || tgt[0] == 0) && p_dim(tgt[1]) : p_dim(tgt[0]) && rows_dim(tgt[1]));
+        if (!ok) bad_form(vn, std::string("behind the Gather of the products only a Reshape that keeps ") + (v.back ? "[N, P]" : "[P, N]") + " is matched");
+      }
+      if (const std::string why = interact_refusal(k, d, int64_t(idx.size())); !why.empty()) bad_form(gn, why);
+      for (int64_t ix : idx) {
+        if (ix < -k * k || ix >= k * k)
+          bad_form(gn, "index " + std::to_string(ix) + " is outside [-" + std::to_string(k * k) + ", " + std::to_string(k * k) + ") of the flattened " + std::to_string(k) + " x " +
+                           std::to_string(k) + " products");
+        pack->sel.push_back(ix < 0 ? ix + k * k : ix);
+      }
+      shape = {N, P};
+    } else {
+      const NodeDef &gn = m.nodes[im.gather];
+      // the views between the product and the Gather must arrive at [N, k * k]
+      std::vector<int64_t> cur = {N, k, k};
+      for (const InteractView &v : im.views) {
+        const NodeDef &vn = m.nodes[v.node];
+        if (vn.op == "Flatten") {
+          if (v.target[0] != 1 && v.target[0] != 1 - int64_t(cur.size())) bad_form(vn, "only axis = 1 keeps the row axis");
+          cur = {N, prod(cur, 1)};
+        } else if (vn.op == "Reshape") {
+          std::vector<int64_t> tgt = v.target;
+          int64_t rest = 1;
+          int neg = -1;
+          for (size_t i = 1; i < tgt.size(); i++) {
+            if (tgt[i] == 0 && i < cur.size()) tgt[i] = cur[i];
+            if (tgt[i] == -1 && neg < 0) neg = int(i);
+            else rest *= tgt[i];
+          }
+          if (neg >= 0 && rest > 0 && k * k % rest == 0) tgt[size_t(neg)] = k * k / rest;
+          if (!(tgt[0] == 0 || tgt[0] == -1 || (N > 0 && tgt[0] == N)) || prod(tgt, 1) != k * k || (tgt[0] == -1 && neg >= 0))
+            bad_form(vn, "target shape " + shape_str(v.target) + " does not keep the row axis of " + shape_str(cur));
+          tgt[0] = N;
+          cur = tgt;
+        }
+      }
+      int64_t axis = gn.attr_i("axis", 0);
+      if (axis < 0) axis += int64_t(cur.size());
+      if (cur.size() != 2 || axis != 1)
+        bad_form(gn, "Gather(axis = " + std::to_string(gn.attr_i("axis", 0)) + ") of the products " + shape_str(cur) + "; only a constant list on axis 1 of the flattened matrix [N, k * k]");
+      if (const std::string why = interact_refusal(k, d, int64_t(im.idx.size())); !why.empty()) bad_form(gn, why);
+      for (int64_t ix : im.idx) {
+        if (ix < -k * k || ix >= k * k)
+          bad_form(gn, "index " + std::to_string(ix) + " is outside [-" + std::to_string(k * k) + ", " + std::to_string(k * k) + ") of the flattened " + std::to_string(k) + " x " +
+                           std::to_string(k) + " products");
+        pack->sel.push_back(ix < 0 ? ix + k * k : ix);
+      }
+      shape = {N, int64_t(im.idx.size())};
+    }
+    if (im.out_concat != SIZE_MAX) {
+      // the other inputs of the Concat as column ranges of T's row: the columns in front of each in the Concat that built T
+      const NodeDef &tc = m.nodes[im.t_concat];
+      const NodeDef &sel_node = *graph->producer(im.selection_value);
+      const int64_t P = shape[1];
+      auto width = [&](const std::string &v) -> int64_t {
+        if (auto vi = vals.find(v); vi != vals.end() && !vi->second.is_const && vi->second.ra == 0 && !vi->second.shape.empty()) return prod(vi->second.shape, 1);
+        if (auto eg = embed_at.find(im.t_concat); eg != embed_at.end())
+          for (const EmbedLookup &L : eg->second.lookups)
+            if (L.out == v) return prod(L.shape, 1);
+        return -1;
+      };
+      bool known = true;
+      int64_t out = 0;
+      for (const auto &in : anchor.inputs) {
+        if (in == im.selection_value) {
+          pack->sel_out = out;
+          out += P;
+          continue;
+        }
+        int64_t off = 0;
+        for (const auto &ti : tc.inputs) {
+          if (ti == in) break;
+          const int64_t w = width(ti);
+          known = known && w > 0;
+          off += w;
+        }
+        const int64_t w = width(in);
+        known = known && w > 0 && off + w <= k * d;
+        pack->passes.push_back({off, w, out});
+        out += w;
+      }
+      if (known) {
+        shape = {N, out};
+      } else {
+        // (a column range that cannot be told at load: the selection alone is the step and the Concat copies, as before)
+        pack->passes.clear();
+        pack->sel_out = 0;
+        if (const std::string why = pack_interact(*pack); !why.empty()) bad_form(sel_node, why);
+        s.interact = pack;
+        s.M = pack->F;
+        s.origin.erase(s.origin.rfind('+'));
+        set_act(sel_node, push_step(std::move(s), shape), shape);
+        return concat(anchor);
+      }
+    }
+    if (const std::string why = pack_interact(*pack); !why.empty()) bad_form(pn, why);
+    s.interact = pack;
+    s.M = pack->F;
+    if (shape.size() == 3) return emit_window(std::move(s), anchor, shape);
+    set_act(anchor, push_step(std::move(s), shape), shape);
+  }
+
   Plan run() {
     graph = std::make_unique<const GraphIndex>(m, m.outputs[out_index].name);
     plan.opset = m.opset;
@@ -5400,6 +5913,7 @@ struct Lowerer {
     absorbed.assign(m.nodes.size(), 0);
     // preprocessing regions: their graph inputs start as identity columns over the input buffer (integer inputs truncated)
     const std::set<std::string> region_inputs = find_regions();
+    find_interactions();
     find_attention();
     if (nearest_enabled) find_nearest();
     find_group_norms();
@@ -5446,6 +5960,17 @@ struct Lowerer {
       } else if (attn_at.count(ni)) lower_typed(n, [&] { lower_attention(attn_at.at(ni), n); });
       else if (nearest_at.count(ni)) lower_nearest(nearest_at.at(ni));
       else if (embed_at.count(ni)) lower_embed(embed_at.at(ni), n);
+      else if (interact_at.count(ni)) {
+        const InteractMatch &im = interact_at.at(ni);
+        if (interact_released(im)) {  // the operators one by one, as without the matcher: their inputs all stand in front of the first of them
+          std::vector<size_t> all = im.nodes;
+          all.push_back(ni);
+          std::sort(all.begin(), all.end());
+          for (size_t i : all) lower_typed(m.nodes[i], [&] { lower_node(m.nodes[i]); });
+        } else {
+          lower_typed(n, [&] { lower_interact(im, n); });
+        }
+      }
       else if (mmean_at.count(ni)) lower_typed(n, [&] { lower_masked_mean(mmean_at.at(ni), n); });
       else if (absorbed[ni]) continue;
       else if (gn_at.count(ni)) lower_typed(n, [&] { if (!exporter_group_norm(gn_at.at(ni), n)) lower_node(n); });

@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "deconv.hpp"
 #include "embed.hpp"
+#include "interact.hpp"
 #include "spatialnorm.hpp"
 #include "tokens.hpp"
 #include "nearest.hpp"
@@ -28,13 +29,14 @@ double Plan::flops_per_row() const {
     else if (s.kind == StepKind::ConvTranspose2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.H) * double(s.Wd);  // (C/g) kh kw taps per input pixel and output channel
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
     else if (s.kind == StepKind::Nearest) f += 2.0 * double(s.nearest->F) * double(s.nearest->M);
+    else if (s.kind == StepKind::Interact) f += s.interact->mode == kInteractDot ? 2.0 * double(s.interact->k * s.interact->k * s.interact->d) : 4.0 * double(s.interact->k * s.interact->d);
     else if (s.kind == StepKind::Recurrent) f += 2.0 * double(s.rnn->T * s.rnn->D * s.rnn->G * s.rnn->H) * double(s.rnn->F + s.rnn->H);
   }
   return f;
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -173,6 +175,22 @@ std::string Plan::describe_json() const {
           o << "{\"copy\":" << e.d << ",\"src\":" << e.src << ",\"out\":" << e.out << "}";
       }
       o << "]";
+    }
+    if (s.kind == StepKind::Interact) {
+      const InteractPack &q = *s.interact;
+      o << ",\"mode\":\"" << (q.mode == kInteractDot ? "dot" : "fm") << "\",\"k\":" << q.k << ",\"d\":" << q.d << ",\"P\":" << q.P << ",\"out_cols\":" << q.F
+        << ",\"bytes_per_row\":" << q.bytes_per_row();
+      if (q.mode == kInteractDot) {
+        o << ",\"whole\":" << (q.whole ? "true" : "false") << ",\"tile\":" << q.tile << ",\"selection_out\":" << q.sel_out << ",\"selection\":" << json_int_array(q.sel) << ",\"pass_through\":[";
+        for (size_t k = 0; k < q.passes.size(); k++)
+          o << (k ? "," : "") << "{\"src\":" << q.passes[k].src << ",\"len\":" << q.passes[k].len << ",\"out\":" << q.passes[k].out << "}";
+        o << "]";
+      } else {
+        o << ",\"h\":";
+        if (q.has_h) o << json_f32(q.h);
+        else o << "null";
+        o << ",\"sum_last\":" << (q.sum_last ? "true" : "false") << ",\"h_after_sum\":" << (q.h_after ? "true" : "false");
+      }
     }
     if (s.kind == StepKind::QConv2d)
       o << ",\"C\":" << s.C << ",\"k\":[" << s.kh << "," << s.kw << "],\"strides\":[" << s.sh << "," << s.sw << "],\"pads\":[" << s.pt << "," << s.pl << "," << s.pb << "," << s.pr

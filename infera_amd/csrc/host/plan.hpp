@@ -22,6 +22,7 @@ struct RnnPack;   // host/recurrent.hpp
 struct NearestPack;  // host/nearest.hpp
 struct DeconvPack;   // host/deconv.hpp
 struct EmbedPack;    // host/embed.hpp
+struct InteractPack;  // host/interact.hpp
 
 // Kinds 1..5 may be fused into the epilogue of a Dense / Conv2d step (the MFMA kernels resolve them at
 // compile time); the rest run in the elementwise kernels (fused into Binary*/AffineChannel or as a Unary step).
@@ -76,6 +77,7 @@ enum class StepKind : int {
   Tokens = 38,        // out [rows, rep = P + S, K = C] = the window of in0 [rows, C, S] (NCHW or channel quads): out[r, P + s, c] = in0[r, c, s] (+ cst[P + s, c]); rows p < P = prefix[p, c] (+ cst[p, c]) (host/tokens.hpp, tokens.hip)
   ChannelNorm = 39,   // LayerNorm over the C channels at each of the S pixels of in0 [rows, C, S] (NCHW or channel quads, never changed): y = act((x - mean) / sqrt(var + ln_eps) * scale[c] + shift[c]), shift may be empty; out_mode (set by the scheduler): 0 the register form, 1 the re-read form (host/channelnorm.hpp, channelnorm.hip)
   Embed = 40,         // out [rows, F] = pieces in output order: rows of constant tables chosen by index columns of in0 [rows, W] (truncated toward zero, + an offset) and runs of in0's columns as they are; a window [rows, k, d] when the pack says so (EmbedPack, host/embed.hpp, embed.hip)
+  Interact = 41,      // feature interactions of in0 [rows, k, d] (rows first, flat): dot mode, out [rows, F] = chosen entries of T . T^T beside bit copies of columns of T; fm mode, out [rows, d] or [rows, 1] = h * ((sum_f T)^2 - sum_f T^2) (InteractPack, host/interact.hpp, interact.hip)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
@@ -152,6 +154,7 @@ struct Step {
   std::shared_ptr<const RnnPack> rnn;
   std::shared_ptr<const NearestPack> nearest;
   std::shared_ptr<const EmbedPack> embed;
+  std::shared_ptr<const InteractPack> interact;
   std::shared_ptr<const DeconvPack> deconv;  // ConvTranspose2d: phase tap lists; Resize2d: source tables
   int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut, RowReduce: ReduceOp, TopK: 0 values / 1 indices, Nearest*: NearestOut
   // Attention: Q = in0, K = in1, V = in2 (the same buffer three times when the projections are merged), each [rows, T, ld] with the head

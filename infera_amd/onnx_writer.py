@@ -4128,3 +4128,294 @@ def text_encoder_inputs(spec: dict, lengths, seed: int = 0, left: bool = False):
     ids = np.where(keep, ids, pad).astype(np.int64)
     both = np.ascontiguousarray(np.concatenate([ids, keep.astype(np.int64)], axis=1).astype(np.float32))
     return ids, keep, both, np.ascontiguousarray(ids.astype(np.float32))
+
+
+# ------------------------------------------------------------------------------------------
+# Feature interactions of recommender models (DLRM's pairwise dots, the FM / DeepFM / NFM bi-interaction term)
+# ------------------------------------------------------------------------------------------
+INTERACT_SOURCES = ("input", "embed", "reshape", "concat")
+
+
+def interact_window_nodes(k: int, d: int, source: str = "reshape", table=None, batch: int | str = "N"):
+    """A window T [N, k, d] as (nodes, initializers, its name 'T', graph inputs, width of the f32 table a call passes).
+    "input": the graph input X [N, k, d] itself.  "reshape": Reshape of the input X [N, k * d] (DLRM's .view(N, -1, d)).  "concat": the k
+    column blocks of X [N, k * d], each Slice -> Unsqueeze(1) -> [N, 1, d], joined by Concat(axis = 1).  "embed": Gather(table [V, d],
+    x_cat [N, k] int64), an Embed window; the call passes the k index values."""
+    assert source in INTERACT_SOURCES
+    nodes, inits = [], []
+    i64 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.int64)))  # noqa: E731
+    if source == "input":
+        nodes.append(node("Identity", ["X"], ["T"], name="window"))
+        return nodes, inits, "T", [value_info("X", [batch, k, d])], k * d
+    if source == "embed":
+        assert table is not None and table.shape[1] == d
+        inits.append(tensor("table", np.asarray(table, np.float32)))
+        nodes.append(node("Gather", ["table", "x_cat"], ["T"], name="emb"))
+        return nodes, inits, "T", [value_info("x_cat", [batch, k], INT64)], k
+    inputs = [value_info("X", [batch, k * d])]
+    if source == "reshape":
+        i64("window_shape", [-1, k, d])
+        nodes.append(node("Reshape", ["X", "window_shape"], ["T"], name="window"))
+        return nodes, inits, "T", inputs, k * d
+    i64("ax1", [1])
+    for j in range(k):
+        i64(f"b{j}", [j * d]); i64(f"e{j}", [(j + 1) * d])  # noqa: E702
+        nodes.append(node("Slice", ["X", f"b{j}", f"e{j}", "ax1"], [f"f{j}"], name=f"field{j}"))
+        nodes.append(node("Unsqueeze", [f"f{j}", "ax1"], [f"u{j}"], name=f"unsq{j}"))
+    nodes.append(node("Concat", [f"u{j}" for j in range(k)], ["T"], [attr_i("axis", 1)], name="stack"))
+    return nodes, inits, "T", inputs, k * d
+
+
+def interact_dot_nodes(nodes: list, inits: list, T: str, k: int, form: str = "gather", sel=None, flatten: str = "flatten", perm=(0, 2, 1),
+                       right: str | None = None) -> tuple[str, list]:
+    """Appends Z = MatMul(T, Transpose(T, perm)) (nodes 'tr', 'dot') and what reads it; returns (result name, its dims behind the row axis).
+    form "matrix": Z [N, k, k] itself; "flat": Flatten / Reshape (`flatten`) to [N, k * k]; "gather": that, then Gather(axis = 1) by the
+    constant list `sel` (node 'pairs'); "index" / "index_folded": the TorchScript exporter's Z[:, li, lj] (_advanced_index_nodes).
+    right: the value the Transpose reads (default T: a Gram matrix)."""
+    nodes.append(node("Transpose", [right or T], ["Tt"], [attr_ints("perm", perm)], name="tr"))
+    nodes.append(node("MatMul", [T, "Tt"], ["Z"], name="dot"))
+    if form == "matrix":
+        return "Z", [k, k]
+    if form in ("index", "index_folded"):
+        return _advanced_index_nodes(nodes, inits, k, np.asarray(sel, dtype=np.int64).reshape(-1), form == "index_folded")
+    if flatten == "flatten":
+        nodes.append(node("Flatten", ["Z"], ["Zflat"], [attr_i("axis", 1)], name="zflat"))
+    else:
+        inits.append(tensor("zflat_shape", np.asarray([-1, k * k], dtype=np.int64)))
+        nodes.append(node("Reshape", ["Z", "zflat_shape"], ["Zflat"], name="zflat"))
+    if form == "flat":
+        return "Zflat", [k * k]
+    sel = np.asarray(sel, dtype=np.int64).reshape(-1)
+    inits.append(tensor("pairs_i", sel))
+    nodes.append(node("Gather", ["Zflat", "pairs_i"], ["Zsel"], [attr_i("axis", 1)], name="pairs"))
+    return "Zsel", [len(sel)]
+
+
+def _advanced_index_nodes(nodes: list, inits: list, k: int, sel: np.ndarray, folded: bool) -> tuple[str, list]:
+    """Z[:, li, lj] as the TorchScript exporter writes it, node for node as torch/onnx/symbolic_opset9.py::index builds it for two index
+    tensors on axes 1 and 2 of a rank-3 value (read from that source, not exported): the three dims by Shape -> Gather, Transpose(1,2,0),
+    Flatten(2), the index lj + li * dim2 by Mul and Add, Gather(axis = 0), Reshape to [-1, dim0], Transpose(1,0), Reshape to
+    Concat(dim0, Shape(index)).  li, lj = divmod(sel, k), so sel must be non-negative.  folded: what constant folding leaves where the dims
+    are static -- the index one constant, the Reshape targets [P, -1] and [-1, P]."""
+    assert np.all(sel >= 0)
+    i64 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.int64)))  # noqa: E731
+    P = len(sel)
+    nodes.append(node("Transpose", ["Z"], ["Zt"], [attr_ints("perm", [1, 2, 0])], name="idx_front"))
+    nodes.append(node("Flatten", ["Zt"], ["Zf"], [attr_i("axis", 2)], name="idx_flat"))
+    if folded:
+        i64("cum", sel); i64("fold_shape", [P, -1]); i64("final_shape", [-1, P])  # noqa: E702
+    else:
+        i64("li", sel // k); i64("lj", sel % k); i64("minus1", [-1])  # noqa: E702
+        nodes.append(node("Shape", ["Z"], ["zshape"], name="zshape"))
+        for a in range(3):
+            i64(f"dim{a}_i", [a])
+            nodes.append(node("Gather", ["zshape", f"dim{a}_i"], [f"dim{a}"], [attr_i("axis", 0)], name=f"dim{a}"))
+        nodes.append(node("Mul", ["li", "dim2"], ["li_scaled"], name="idx_mul"))
+        nodes.append(node("Add", ["lj", "li_scaled"], ["cum"], name="idx_add"))
+    nodes.append(node("Gather", ["Zf", "cum"], ["Zg"], [attr_i("axis", 0)], name="pairs"))
+    if not folded:
+        nodes.append(node("Shape", ["cum"], ["cum_shape"], name="cum_shape"))
+        nodes.append(node("Concat", ["minus1", "dim0"], ["fold_shape"], [attr_i("axis", 0)], name="fold_shape"))
+        nodes.append(node("Concat", ["dim0", "cum_shape"], ["final_shape"], [attr_i("axis", 0)], name="final_shape"))
+    nodes.append(node("Reshape", ["Zg", "fold_shape"], ["Zr"], name="idx_fold"))
+    nodes.append(node("Transpose", ["Zr"], ["Zb"], [attr_ints("perm", [1, 0])], name="idx_back"))
+    nodes.append(node("Reshape", ["Zb", "final_shape"], ["Zsel"], name="idx_final"))
+    return "Zsel", [P]
+
+
+def interact_triangle(k: int, diagonal: bool = False) -> np.ndarray:
+    """li * k + lj over the lower triangle (i > j; diagonal: i >= j), row by row: DLRM's Z[:, li, lj]."""
+    return np.asarray([i * k + j for i in range(k) for j in range(i + 1 if diagonal else i)], dtype=np.int64)
+
+
+def interact_dot_model(k: int, d: int, form: str = "gather", sel=None, source: str = "reshape", table=None, batch: int | str = "N", **kw) -> bytes:
+    nodes, inits, T, inputs, _ = interact_window_nodes(k, d, source, table, batch)
+    cur, dims = interact_dot_nodes(nodes, inits, T, k, form, sel, **kw)
+    nodes.append(node("Identity", [cur], ["Y"]))
+    return model("interact_dot", nodes, inits, inputs, [value_info("Y", [batch] + dims)], opset=13)
+
+
+def interact_fm_nodes(nodes: list, inits: list, T: str, d: int, square: str = "mul", h=None, h_side: str = "right", sum_last: bool = False,
+                      keepdims: int = 0, last_keepdims: int = 1, h_after: bool = False, axes_input: bool = True) -> tuple[str, list]:
+    """Appends the bi-interaction term of T [N, k, d] as written: S = ReduceSum(T, [1]) ('fsum'), S * S or S ^ 2 ('sq_sum'), T * T or T ^ 2
+    ('sq'), its ReduceSum ('sum_sq'), Sub ('diff'), then Mul by the constant scalar h on h_side ('half') and, with sum_last, ReduceSum over
+    the last axis ('total'); h_after: the Mul follows that sum.  Returns (result name, its dims behind the row axis)."""
+    def rsum(x, y, axes, keep, name):
+        if axes_input:
+            inits.append(tensor(name + "_axes", np.asarray(axes, dtype=np.int64)))
+            nodes.append(node("ReduceSum", [x, name + "_axes"], [y], [attr_i("keepdims", keep)], name=name))
+        else:
+            nodes.append(node("ReduceSum", [x], [y], [attr_ints("axes", axes), attr_i("keepdims", keep)], name=name))
+
+    def sq(x, y, name):
+        if square == "mul":
+            nodes.append(node("Mul", [x, x], [y], name=name))
+        else:
+            if not any(b"two" in t[:8] for t in inits):
+                inits.append(tensor("two", np.asarray(2.0, dtype=np.float32)))
+            nodes.append(node("Pow", [x, "two"], [y], name=name))
+
+    rsum(T, "S", [1], keepdims, "fsum")
+    sq("S", "SS", "sq_sum")
+    sq(T, "Q", "sq")
+    rsum("Q", "QS", [1], keepdims, "sum_sq")
+    nodes.append(node("Sub", ["SS", "QS"], ["D"], name="diff"))
+    cur, dims = "D", ([1, d] if keepdims else [d])
+
+    def mul_h(cur):
+        inits.append(tensor("h", np.asarray(h, dtype=np.float32)))
+        nodes.append(node("Mul", [cur, "h"] if h_side == "right" else ["h", cur], ["Dh"], name="half"))
+        return "Dh"
+
+    if h is not None and not h_after:
+        cur = mul_h(cur)
+    if sum_last:
+        rsum(cur, "Dsum", [-1], last_keepdims, "total")
+        cur, dims = "Dsum", (dims[:-1] + [1] if last_keepdims else dims[:-1])
+    if h is not None and h_after:
+        cur = mul_h(cur)
+    return cur, dims
+
+
+def interact_fm_model(k: int, d: int, source: str = "reshape", table=None, batch: int | str = "N", opset: int = 13, **kw) -> bytes:
+    nodes, inits, T, inputs, _ = interact_window_nodes(k, d, source, table, batch)
+    cur, dims = interact_fm_nodes(nodes, inits, T, d, **kw)
+    nodes.append(node("Identity", [cur], ["Y"]))
+    return model("interact_fm", nodes, inits, inputs, [value_info("Y", [batch] + dims)], opset=opset)
+
+
+def interact_dot_reference(T, sel=None) -> np.ndarray:
+    """float64: Z = T T^T per row, [N, k, k]; with sel, Z.reshape(N, k * k)[:, sel] (negative indices count from the end)."""
+    t = np.asarray(T, np.float64)
+    z = np.einsum("nic,njc->nij", t, t)
+    return z if sel is None else z.reshape(len(t), -1)[:, np.asarray(sel, dtype=np.int64)]
+
+
+def interact_fm_reference(T, h=None, sum_last: bool = False) -> np.ndarray:
+    """float64: h * ((sum_f T)^2 - sum_f T^2), [N, d]; sum_last: its sum over the last axis, [N, 1]."""
+    t = np.asarray(T, np.float64)
+    v = t.sum(axis=1) ** 2 - (t * t).sum(axis=1)
+    if h is not None:
+        v = v * float(h)
+    return v.sum(axis=1, keepdims=True) if sum_last else v
+
+
+def _mlp_layers(rng, widths, scale):
+    out = []
+    for i, o in zip(widths[:-1], widths[1:]):
+        b = scale / np.sqrt(i)
+        out.append((rng.uniform(-b, b, (i, o)).astype(np.float32), rng.uniform(-b, b, (o,)).astype(np.float32)))
+    return out
+
+
+def _mlp_nodes(nodes, inits, cur, layers, p, last_act):
+    for i, (W, b) in enumerate(layers):
+        inits += [tensor(f"{p}W{i}", W), tensor(f"{p}B{i}", b)]
+        nodes += [node("MatMul", [cur, f"{p}W{i}"], [f"{p}Z{i}"], name=f"{p}fc{i}"), node("Add", [f"{p}Z{i}", f"{p}B{i}"], [f"{p}H{i}"], name=f"{p}fc{i}_bias")]
+        cur = f"{p}H{i}"
+        if i + 1 < len(layers) or last_act:
+            nodes.append(node("Relu", [cur], [f"{p}A{i}"], name=f"{p}act{i}"))
+            cur = f"{p}A{i}"
+    return cur
+
+
+def _mlp64(h, layers, last_act):
+    for i, (W, b) in enumerate(layers):
+        h = h @ np.asarray(W, np.float64) + np.asarray(b, np.float64)
+        if i + 1 < len(layers) or last_act:
+            h = np.maximum(h, 0.0)
+    return h
+
+
+def dlrm_spec(cards: Sequence[int] = (7, 11, 5), d: int = 4, numeric: int = 3, bottom: Sequence[int] = (8,), top: Sequence[int] = (8,), seed: int = 81,
+              weight_scale: float = 1.0, diagonal: bool = False) -> dict:
+    """Seeded DLRM: `numeric` dense columns -> bottom MLP (... -> d, Relu after every layer) = x; one table [cards[j], d] per categorical
+    column; T = cat([x] + lookups, 1).view(N, -1, d); Z = bmm(T, T^T); R = cat([x, Z.flatten(1)[:, li * K + lj]], 1) over the strict lower
+    triangle (diagonal: with it); top MLP R -> ... -> 1 (Relu between the layers).  Weights U(+-weight_scale / sqrt(fan_in))."""
+    rng = np.random.default_rng(seed)
+    K = len(cards) + 1
+    sel = interact_triangle(K, diagonal)
+    return {"cards": [int(v) for v in cards], "d": int(d), "numeric": int(numeric), "sel": sel,
+            "tables": [rng.standard_normal((int(v), d)).astype(np.float32) for v in cards],
+            "bottom": _mlp_layers(rng, [numeric] + list(bottom) + [d], weight_scale), "top": _mlp_layers(rng, [d + len(sel)] + list(top) + [1], weight_scale)}
+
+
+def from_torch_dlrm(embeddings, bottom, top, diagonal: bool = False) -> dict:
+    """The dlrm_spec() dict of torch modules: nn.Embedding tables, the nn.Linear layers of the bottom and of the top MLP, in order."""
+    lin = lambda m: (m.weight.detach().cpu().numpy().astype(np.float32).T.copy(), m.bias.detach().cpu().numpy().astype(np.float32).copy())  # noqa: E731
+    tables = [e.weight.detach().cpu().numpy().astype(np.float32).copy() for e in embeddings]
+    return {"cards": [int(t.shape[0]) for t in tables], "d": int(tables[0].shape[1]), "numeric": int(bottom[0].in_features), "tables": tables,
+            "sel": interact_triangle(len(tables) + 1, diagonal), "bottom": [lin(m) for m in bottom], "top": [lin(m) for m in top]}
+
+
+def dlrm_from_spec(spec: dict, batch: int | str = "N", extra_outputs: bool = False, form: str = "gather") -> bytes:
+    """Inputs x_cat [N, k] int64 and x_num [N, m] (a call passes the k index values beside the m dense columns).  Output 'Y' [N, 1];
+    extra_outputs: also 'R' (the top MLP's input: x beside the chosen products) and 'xb' (the bottom MLP's result)."""
+    k, d, m = len(spec["cards"]), spec["d"], spec["numeric"]
+    nodes, inits = [], []
+    inputs = [value_info("x_cat", [batch, k], INT64), value_info("x_num", [batch, m])]
+    x = _mlp_nodes(nodes, inits, "x_num", spec["bottom"], "bot_", True)
+    parts = [x]
+    for j in range(k):
+        inits += [tensor(f"col{j}_i", np.asarray(j, dtype=np.int64)), tensor(f"table{j}", spec["tables"][j])]
+        nodes.append(node("Gather", ["x_cat", f"col{j}_i"], [f"col{j}"], [attr_i("axis", 1)], name=f"pick{j}"))
+        nodes.append(node("Gather", [f"table{j}", f"col{j}"], [f"e{j}"], name=f"emb{j}"))
+        parts.append(f"e{j}")
+    nodes.append(node("Concat", parts, ["features"], [attr_i("axis", 1)], name="join"))
+    inits.append(tensor("window_shape", np.asarray([-1, k + 1, d], dtype=np.int64)))
+    nodes.append(node("Reshape", ["features", "window_shape"], ["T"], name="window"))
+    zsel, _ = interact_dot_nodes(nodes, inits, "T", k + 1, form, spec["sel"])
+    nodes.append(node("Concat", [x, zsel], ["R"], [attr_i("axis", 1)], name="cat_r"))
+    y = _mlp_nodes(nodes, inits, "R", spec["top"], "top_", False)
+    nodes.append(node("Identity", [y], ["Y"]))
+    outputs = [value_info("Y", [batch, 1])]
+    if extra_outputs:
+        nodes.append(node("Identity", [x], ["xb"]))
+        outputs += [value_info("R", [batch, d + len(spec["sel"])]), value_info("xb", [batch, d])]
+    return model("dlrm", nodes, inits, inputs, outputs, opset=13)
+
+
+def dlrm_reference(spec: dict, x_cat, x_num) -> dict:
+    """float64 restatement of dlrm_from_spec: {"x": the bottom MLP's result, "T", "R", "output"}."""
+    x = _mlp64(np.asarray(x_num, np.float64), spec["bottom"], True)
+    T = np.stack([x] + [np.asarray(t, np.float64)[np.asarray(x_cat)[:, j]] for j, t in enumerate(spec["tables"])], axis=1)
+    R = np.concatenate([x, interact_dot_reference(T, spec["sel"])], axis=1)
+    return {"x": x, "T": T, "R": R, "output": _mlp64(R, spec["top"], False)}
+
+
+def deepfm_spec(cards: Sequence[int] = (7, 11, 5, 3), d: int = 4, hidden: Sequence[int] = (8,), seed: int = 83, weight_scale: float = 1.0) -> dict:
+    """Seeded DeepFM over len(cards) categorical fields: one shared table [sum(cards), d] and a first-order table [sum(cards), 1] indexed by
+    x_cat + offsets; y = sum_f w[f] + 0.5 * sum_c((sum_f v)^2 - sum_f v^2) + MLP(flatten(v))."""
+    rng = np.random.default_rng(seed)
+    V, k = int(sum(cards)), len(cards)
+    return {"cards": [int(v) for v in cards], "d": int(d), "table": rng.standard_normal((V, d)).astype(np.float32),
+            "first": (rng.standard_normal((V, 1)) * weight_scale).astype(np.float32),
+            "offsets": np.concatenate([[0], np.cumsum(cards)[:-1]]).astype(np.int64), "mlp": _mlp_layers(rng, [k * d] + list(hidden) + [1], weight_scale)}
+
+
+def deepfm_from_spec(spec: dict, batch: int | str = "N") -> bytes:
+    """Input x_cat [N, k] int64; output 'Y' [N, 1] = first-order sum + FM second-order term + deep MLP."""
+    k, d = len(spec["cards"]), spec["d"]
+    nodes, inits = [], []
+    inits += [tensor("offsets", spec["offsets"]), tensor("table", spec["table"]), tensor("first", spec["first"])]
+    nodes.append(node("Add", ["x_cat", "offsets"], ["idx"], name="offset"))
+    nodes.append(node("Gather", ["table", "idx"], ["T"], name="emb"))
+    nodes.append(node("Gather", ["first", "idx"], ["w"], name="emb_first"))
+    nodes.append(node("Flatten", ["w"], ["wflat"], [attr_i("axis", 1)], name="first_flat"))
+    inits.append(tensor("last_axis", np.asarray([-1], dtype=np.int64)))
+    nodes.append(node("ReduceSum", ["wflat", "last_axis"], ["y1"], [attr_i("keepdims", 1)], name="first_sum"))
+    y2, _ = interact_fm_nodes(nodes, inits, "T", d, square="mul", h=0.5, sum_last=True, keepdims=0, last_keepdims=1, h_after=True)
+    nodes.append(node("Flatten", ["T"], ["deep_in"], [attr_i("axis", 1)], name="deep_flat"))
+    y3 = _mlp_nodes(nodes, inits, "deep_in", spec["mlp"], "deep_", False)
+    nodes.append(node("Add", ["y1", y2], ["y12"], name="add_fm"))
+    nodes.append(node("Add", ["y12", y3], ["Y"], name="add_deep"))
+    return model("deepfm", nodes, inits, [value_info("x_cat", [batch, k], INT64)], [value_info("Y", [batch, 1])], opset=13)
+
+
+def deepfm_reference(spec: dict, x_cat) -> dict:
+    """float64 restatement of deepfm_from_spec: {"T", "fm", "output"}."""
+    idx = np.asarray(x_cat, dtype=np.int64) + spec["offsets"]
+    T = np.asarray(spec["table"], np.float64)[idx]
+    y1 = np.asarray(spec["first"], np.float64)[idx][:, :, 0].sum(axis=1, keepdims=True)
+    fm = interact_fm_reference(T, None, True) * 0.5
+    return {"T": T, "fm": fm, "output": y1 + fm + _mlp64(T.reshape(len(T), -1), spec["mlp"], False)}
