@@ -16,7 +16,8 @@
 // 128 workgroups of a 2048-row chunk share it), not held in LDS.
 //   GRU linear_before_reset = 0 needs r before R_h (r (.) h): r (.) h_{t-1} is exchanged through the not-yet-written h copy and gate
 //   h's recurrent product runs as a second phase (two more barriers per step).
-// Directions of a bidirectional layer are blockIdx.y.  Padded units (H..Hp) have zero weights, biases and state and stay exactly 0.
+// Directions of a bidirectional layer are blockIdx.y.  Padded units (H..Hp) have zero weights, biases and state, and their h is written
+// as 0 whatever their accumulators hold (0 . inf = NaN under an infinite reading), so a row's padded units never reach its real ones.
 // Input: row-major [rows, T, F], or ONE column-major staged chunk [T * F][rows] (x_colmajor): the same loads with another index.
 // A row's bits depend on the model and the row only: no atomics, the k order is fixed, rows never mix (a NaN poisons its own column).
 //
@@ -155,7 +156,8 @@ __global__ __launch_bounds__(kRnnMaxWaves * 64) void rnn_kernel(const float *__r
         if (tile >= HT) continue;
         const f32x4 br = *reinterpret_cast<const f32x4 *>(bias + 1 * Hp + 16 * tile + 4 * kq);
 #pragma unroll
-        for (int i = 0; i < 4; i++) hn[(16 * tile + 4 * kq + i) * 16 + n] = apply_act_c<2>(acc[q][1][i] + br[i], 0.f, 0.f) * hp[q][i];
+        for (int i = 0; i < 4; i++)  // (a padded unit: 0, not sigma(0 . inf) . 0)
+          hn[(16 * tile + 4 * kq + i) * 16 + n] = 16 * tile + 4 * kq + i < H ? apply_act_c<2>(acc[q][1][i] + br[i], 0.f, 0.f) * hp[q][i] : 0.f;
       }
       __syncthreads();
 #pragma unroll
@@ -207,6 +209,10 @@ __global__ __launch_bounds__(kRnnMaxWaves * 64) void rnn_kernel(const float *__r
           h[i] = relu ? apply_act_c<1>(v, 0.f, 0.f) : apply_act_c<3>(v, 0.f, 0.f);
         }
       }
+      // A padded unit's zero weights meet an infinite reading as 0 . inf = NaN: its h is 0 by definition, not by arithmetic, or the NaN
+      // would reach every unit of the row through the next step's B operand (0 . NaN).
+#pragma unroll
+      for (int i = 0; i < 4; i++) h[i] = j0 + i < H ? h[i] : 0.f;
       hp[q] = h;
 #pragma unroll
       for (int i = 0; i < 4; i++) {

@@ -305,6 +305,8 @@ def test_references_agree():
     import importlib.util
     import os
 
+    from tests import recurrent_ref
+
     spec_ = importlib.util.spec_from_file_location("recurrent_gpu_refs", os.path.join(os.path.dirname(__file__), "test_recurrent_gpu.py"))
     g = importlib.util.module_from_spec(spec_)
     spec_.loader.exec_module(g)
@@ -315,6 +317,6 @@ def test_references_agree():
             x = g._x(11, T, F)
             y_t, h_t = g.torch_ref(m, x, torch.float64)
             spec64 = dict(spec, layers=[{k: (v if v is None else np.asarray(v)) for k, v in L.items()} for L in spec["layers"]])
-            y_n, h_n, _ = g.np_recurrent(spec64, x)
+            y_n, h_n, _ = recurrent_ref.recurrent(spec64, x)
             # (the ONNX weights are the module's float32 parameters, which float64 holds exactly)
             assert np.max(np.abs(y_t - y_n)) <= 1e-12 and np.max(np.abs(h_t - h_n)) <= 1e-12, (op, relu, T, F, H, layers, D)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from infera_amd import onnx_writer as W
+from tests.recurrent_ref import recurrent as np_recurrent  # the float64 restatement of the ONNX operator specification
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -19,48 +20,6 @@ def api(built):
 
     assert capi.device_count() >= 1, capi.get_devices()
     return capi
-
-
-# ---- float64 restatement of the ONNX operator specification --------------------------------------------------
-
-def np_recurrent(spec, x):
-    """x [N, T, F] -> (Y [N, T, D*H] of the last layer, Y_h [N, D*H], Y_c [N, D*H] or None), all float64."""
-    op, H, D = spec["op"], spec["H"], spec["D"]
-    G = {"LSTM": 4, "GRU": 3, "RNN": 1}[op]
-    sig = lambda v: 1.0 / (1.0 + np.exp(-v))  # noqa: E731
-    x = np.asarray(x, dtype=np.float64)
-    N, T, _ = x.shape
-    for L in spec["layers"]:
-        ys, hs, cs = [], [], []
-        for d in range(D):
-            Wm, Rm = L["W"][d].astype(np.float64), L["R"][d].astype(np.float64)
-            B = L["B"][d].astype(np.float64) if L["B"] is not None else np.zeros(2 * G * H)
-            Wb, Rb = B[:G * H], B[G * H:]
-            h = np.tile(L["h0"][d].astype(np.float64), (N, 1)) if L.get("h0") is not None else np.zeros((N, H))
-            c = np.tile(L["c0"][d].astype(np.float64), (N, 1)) if L.get("c0") is not None else np.zeros((N, H))
-            rev = spec["direction"] == "reverse" or d == 1
-            y = np.zeros((N, T, H))
-            g = lambda a, k: a[..., k * H:(k + 1) * H]  # noqa: E731
-            for t in (range(T - 1, -1, -1) if rev else range(T)):
-                xw, hr = x[:, t] @ Wm.T + Wb, h @ Rm.T + Rb
-                if op == "LSTM":
-                    i, o, f, cc = sig(g(xw, 0) + g(hr, 0)), sig(g(xw, 1) + g(hr, 1)), sig(g(xw, 2) + g(hr, 2)), np.tanh(g(xw, 3) + g(hr, 3))
-                    c = f * c + i * cc
-                    h = o * np.tanh(c)
-                elif op == "GRU":
-                    z, r = sig(g(xw, 0) + g(hr, 0)), sig(g(xw, 1) + g(hr, 1))
-                    if spec["linear_before_reset"]:
-                        hh = np.tanh(g(xw, 2) + r * g(hr, 2))
-                    else:
-                        hh = np.tanh(g(xw, 2) + (r * h) @ g(Rm.T, 2) + g(Rb, 2))
-                    h = (1 - z) * hh + z * h
-                else:
-                    v = xw + hr
-                    h = np.maximum(v, 0) if spec["activation"] == "Relu" else np.tanh(v)
-                y[:, t] = h
-            ys.append(y), hs.append(h), cs.append(c)
-        x = np.concatenate(ys, axis=2)
-    return x, np.concatenate(hs, axis=1), (np.concatenate(cs, axis=1) if op == "LSTM" else None)
 
 
 def w_scale(op, relu, shape):
