@@ -97,8 +97,13 @@ void prep(hipStream_t s, const float *x, int F_in, const uint32_t *desc, const f
 // ---- recurrent layers (rnn.hip) -------------------------------------------------------------------
 // LSTM / GRU / RNN over x [rows, T, F] (x_colmajor: ONE column-major chunk [T * F][rows]); tables: host/recurrent.hpp RnnPack (op: RnnOp).
 // mode (RnnOut): y = Y [rows, T, D, H], or the last state Y_h / Y_c [rows, D, H].  false: the kernel could not be given its LDS
+// lens (null: every row holds T steps): row r holds lens[r * lens_ld + lens_off] valid steps (lens_int: truncated toward zero first) and
+// gives what the layer gives on those steps alone: Y is 0 behind them, the states are those after the last of them, what lies behind
+// them in x is not read.  A length outside 0 .. T (a NaN included) counts as 0 and sets the call's failure word *err to err_node.
+// Never with x_colmajor (false)
 bool rnn(hipStream_t s, const float *x, const float *wr, const float *bias, const float *bias2, const float *h0, const float *c0, float *y, int64_t rows,
-         int op, int T, int F, int H, int D, bool reverse, bool lbr, bool relu, int mode, bool x_colmajor);
+         int op, int T, int F, int H, int D, bool reverse, bool lbr, bool relu, int mode, bool x_colmajor, const float *lens = nullptr, int64_t lens_ld = 0,
+         int lens_off = 0, bool lens_int = false, int *err = nullptr, int err_node = 0);
 
 // ---- Transformer encoders (attention.hip, layernorm.hip) -------------------------------------------------------------------------
 // y [rows, T, heads * dh] = softmax(scale . Q K^T + mask) V per row and head; q / k / v: [rows, T, ld[i]] with head g at columns

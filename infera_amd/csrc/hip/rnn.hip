@@ -20,6 +20,7 @@
 // as 0 whatever their accumulators hold (0 . inf = NaN under an infinite reading), so a row's padded units never reach its real ones.
 // Input: row-major [rows, T, F], or ONE column-major staged chunk [T * F][rows] (x_colmajor): the same loads with another index.
 // A row's bits depend on the model and the row only: no atomics, the k order is fixed, rows never mix (a NaN poisons its own column).
+// Per-row sequence lengths (sequence_lens, a column of the row-major input buffer) are the LENS = true instantiations: see rnn_kernel.
 //
 // Occupancy: a 2048-row DataChunk is 128 tiles = 128 workgroups per direction on 256 CUs -- half the chip, one workgroup per CU,
 // min(H / 16, 8) waves each.  The recurrence is serial in T, so a chunk's time is T x (MFMA chain + sigma / tanh tail + 2 barriers);
@@ -34,16 +35,36 @@ namespace {
 
 constexpr int kRnnMaxWaves = 8, kRnnTilesPerWave = 4, kRnnPrefetch = 2;
 
-template <int OP>
+// Per-row sequence lengths (LENS kernels; INTEGRATION.md 2.6 "Padded windows"): row r holds len = src[r * ld + off] valid steps (truncated
+// toward zero first when is_int), 0 <= len <= T.  Any other value (NaN included) counts as 0 and sets the call's failure word to `node`.
+struct RnnLens {
+  const float *src;
+  int64_t ld;
+  int off;
+  bool is_int;
+  int *err;
+  int node;
+};
+
+// LENS = false is the fixed-length kernel: every lengths statement below stands behind `if constexpr (LENS)`, and the lengths argument
+// exists in the LENS = true signature alone (LA: one RnnLens, or nothing).
+// LENS = true: a row with length L gives what the layer gives on its first L steps alone.  The tile's 16 lengths lie in 16 words of LDS
+// behind the h copies (x_t is fetched by element, so a thread needs the length of any of the 16 rows); the step loop runs to the tile's
+// longest row (the same value in every wave: the barriers stay uniform).  At step s a row is active iff s < L and stands at t = s
+// (forward) or L - 1 - s (reverse); an inactive row is not read (its x_t is 0 without a load), keeps h and c by selects, still writes its
+// kept h to the other LDS copy (the double buffer flips every step) and writes Y[s] = 0 (s >= L in both directions).
+template <int OP, bool LENS, typename... LA>
 __global__ __launch_bounds__(kRnnMaxWaves * 64) void rnn_kernel(const float *__restrict__ x, const f32x4 *__restrict__ wr, const float *__restrict__ bias,
                                                                const float *__restrict__ bias2, const float *__restrict__ h0,
                                                                const float *__restrict__ c0, float *__restrict__ y, int64_t nr, int T, int F, int H,
-                                                               int Fp, int Hp, int D, bool reverse1, bool lbr, bool relu, int mode, bool xcm) {
+                                                               int Fp, int Hp, int D, bool reverse1, bool lbr, bool relu, int mode, bool xcm, LA... la) {
+  static_assert(sizeof...(LA) == (LENS ? 1 : 0), "LENS: one RnnLens argument");
   constexpr int G = OP == kRnnLstm ? 4 : OP == kRnnGru ? 3 : 1;
   constexpr int NA = OP == kRnnGru ? 4 : G;  // GRU: z, r, W_h x, R_h h
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float *xb = lds;            // [Fp][16]
   float *hb = lds + Fp * 16;  // [2][Hp][16]
+  [[maybe_unused]] int *ln = reinterpret_cast<int *>(hb + 2 * Hp * 16);  // LENS: [16]
   const int tid = int(threadIdx.x), nth = int(blockDim.x), nw = nth >> 6, wave = tid >> 6, lane = tid & 63, n = lane & 15, kq = lane >> 4;
   const int d = int(blockIdx.y);
   const bool rev = D == 2 ? d == 1 : reverse1;
@@ -55,13 +76,39 @@ __global__ __launch_bounds__(kRnnMaxWaves * 64) void rnn_kernel(const float *__r
   h0 += d * Hp;
   c0 += d * Hp;
 
-  // element e of the 16 x F values of step t: its value and its LDS word
+  [[maybe_unused]] int Ln = 0, Tmax = T;  // LENS: this lane's row's length, the tile's longest
+  if constexpr (LENS) {
+    const RnnLens lens = (la, ...);
+    if (tid < 16) {
+      int L = 0;
+      if (row0 + tid < nr) {
+        float v = lens.src[(row0 + tid) * lens.ld + lens.off];
+        if (lens.is_int) v = truncf(v);
+        if (v >= 0.f && v <= float(T)) L = int(v);  // (a NaN fails both)
+        else *lens.err = lens.node;
+      }
+      ln[tid] = L;
+    }
+    __syncthreads();
+    Ln = ln[n];
+    Tmax = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) Tmax = ln[i] > Tmax ? ln[i] : Tmax;
+  }
+
+  // element e of the 16 x F values of step t: its value and its LDS word.  LENS: t is the step count s, the element's own row's position
+  // follows from its length, and an inactive row's element is 0 without a load
   auto xload = [&](int e, int t) -> float {
     int f, nn;
     if (xcm) f = e >> 4, nn = e & 15;
     else nn = e / F, f = e - nn * F;
     const int64_t g = row0 + nn;
     if (g >= nr) return 0.f;
+    if constexpr (LENS) {
+      const int L = ln[nn];
+      if (t >= L) return 0.f;
+      if (rev) t = L - 1 - t;
+    }
     return xcm ? x[(int64_t(t) * F + f) * nr + g] : x[(g * T + t) * F + f];
   };
   auto xslot = [&](int e) -> int {
@@ -86,7 +133,7 @@ __global__ __launch_bounds__(kRnnMaxWaves * 64) void rnn_kernel(const float *__r
     for (int e = tid + kRnnPrefetch * nth; e < NE; e += nth) xb[xslot(e)] = xload(e, t);
   };
 
-  const int t_first = rev ? T - 1 : 0;
+  const int t_first = LENS ? 0 : rev ? T - 1 : 0;
   prefetch(t_first);
   commit(t_first);
   for (int e = NE + tid; e < Fp * 16; e += nth) xb[e] = 0.f;  // padded features
@@ -103,11 +150,13 @@ __global__ __launch_bounds__(kRnnMaxWaves * 64) void rnn_kernel(const float *__r
   }
   __syncthreads();
 
-  for (int s = 0; s < T; s++) {
-    const int t = rev ? T - 1 - s : s, cur = s & 1;
+  const int TS = LENS ? Tmax : T;
+  for (int s = 0; s < TS; s++) {
+    const int t = LENS ? (rev ? Ln - 1 - s : s) : rev ? T - 1 - s : s, cur = s & 1;
+    [[maybe_unused]] const bool active = s < Ln;
     const float *hc = hb + cur * Hp * 16;
     float *hn = hb + (cur ^ 1) * Hp * 16;
-    if (s + 1 < T) prefetch(rev ? t - 1 : t + 1);
+    if (s + 1 < TS) prefetch(LENS ? s + 1 : rev ? t - 1 : t + 1);
 
     f32x4 acc[kRnnTilesPerWave][NA];
 #pragma unroll
@@ -189,8 +238,17 @@ __global__ __launch_bounds__(kRnnMaxWaves * 64) void rnn_kernel(const float *__r
         for (int i = 0; i < 4; i++) {
           const float gi = apply_act_c<2>(acc[q][0][i] + bg[0][i], 0.f, 0.f), go = apply_act_c<2>(acc[q][1][i] + bg[1][i], 0.f, 0.f);
           const float gf = apply_act_c<2>(acc[q][2][i] + bg[2][i], 0.f, 0.f), gc = apply_act_c<3>(acc[q][3][i] + bg[3][i], 0.f, 0.f);
-          c[q][i] = gf * c[q][i] + gi * gc;
-          h[i] = go * apply_act_c<3>(c[q][i], 0.f, 0.f);
+          float cn;
+          if constexpr (LENS) {
+            // fma(f, c, i . g), written out: it is how the fixed-length instantiation contracts the line below, and around the select
+            // the compiler would not (tests/test_recurrent_lens_gpu.py compares the two instantiations bit for bit)
+            cn = __builtin_fmaf(gf, c[q][i], gi * gc);
+            cn = active ? cn : c[q][i];
+          } else {
+            cn = gf * c[q][i] + gi * gc;
+          }
+          c[q][i] = cn;
+          h[i] = go * apply_act_c<3>(cn, 0.f, 0.f);
         }
       } else if constexpr (OP == kRnnGru) {
         const f32x4 b2 = *reinterpret_cast<const f32x4 *>(bias2 + j0);
@@ -213,17 +271,34 @@ __global__ __launch_bounds__(kRnnMaxWaves * 64) void rnn_kernel(const float *__r
       // would reach every unit of the row through the next step's B operand (0 . NaN).
 #pragma unroll
       for (int i = 0; i < 4; i++) h[i] = j0 + i < H ? h[i] : 0.f;
+      if constexpr (LENS) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) h[i] = active ? h[i] : hp[q][i];
+      }
       hp[q] = h;
 #pragma unroll
       for (int i = 0; i < 4; i++) {
         hn[(j0 + i) * 16 + n] = h[i];
-        if (mode == kRnnY && j0 + i < H && row < nr) y[((row * T + t) * D + d) * H + j0 + i] = h[i];
+        if constexpr (LENS) {
+          if (mode == kRnnY && j0 + i < H && row < nr) y[((row * T + (active ? t : s)) * D + d) * H + j0 + i] = active ? h[i] : 0.f;
+        } else {
+          if (mode == kRnnY && j0 + i < H && row < nr) y[((row * T + t) * D + d) * H + j0 + i] = h[i];
+        }
       }
     }
     __syncthreads();  // h_t is complete; nobody reads x_t or h_{t-1} any more
-    if (s + 1 < T) {
-      commit(rev ? t - 1 : t + 1);
+    if (s + 1 < TS) {
+      commit(LENS ? s + 1 : rev ? t - 1 : t + 1);
       __syncthreads();
+    }
+  }
+  if constexpr (LENS) {  // no row of the tile reaches the steps Tmax .. T - 1: written zeros (the buffer is not cleared)
+    if (mode == kRnnY) {
+      const int64_t HR = int64_t(H) * 16;
+      for (int64_t e = tid; e < HR * (T - Tmax); e += nth) {
+        const int64_t tt = Tmax + e / HR, r = row0 + (e % HR) / H;
+        if (r < nr) y[((r * T + tt) * D + d) * H + e % H] = 0.f;
+      }
     }
   }
 
@@ -241,18 +316,19 @@ __global__ __launch_bounds__(kRnnMaxWaves * 64) void rnn_kernel(const float *__r
   }
 }
 
-template <int OP>
+// la: the RnnLens of a LENS launch, or nothing
+template <int OP, bool LENS, typename... LA>
 bool launch(hipStream_t s, const float *x, const float *wr, const float *bias, const float *bias2, const float *h0, const float *c0, float *y, int64_t rows,
-            int T, int F, int H, int D, bool reverse, bool lbr, bool relu, int mode, bool xcm) {
+            int T, int F, int H, int D, bool reverse, bool lbr, bool relu, int mode, bool xcm, LA... la) {
   const int Fp = (F + 15) / 16 * 16, Hp = (H + 15) / 16 * 16, HT = Hp / 16;
   const int nw = HT < kRnnMaxWaves ? HT : kRnnMaxWaves;
-  const size_t lds = size_t(Fp + 2 * Hp) * 16 * 4;
-  auto kernel = rnn_kernel<OP>;
+  const size_t lds = size_t(Fp + 2 * Hp) * 16 * 4 + (LENS ? 16 * 4 : 0);
+  auto kernel = rnn_kernel<OP, LENS, LA...>;
   if (lds > 64 * 1024 &&  // dynamic LDS beyond 64 KB is opt-in (128 KB at the caps)
       hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
     return false;
   hipLaunchKernelGGL(kernel, dim3(unsigned((rows + 15) / 16), unsigned(D)), dim3(unsigned(64 * nw)), lds, s, x, reinterpret_cast<const f32x4 *>(wr), bias,
-                     bias2, h0, c0, y, rows, T, F, H, Fp, Hp, D, reverse, lbr, relu, mode, xcm);
+                     bias2, h0, c0, y, rows, T, F, H, Fp, Hp, D, reverse, lbr, relu, mode, xcm, la...);
   return true;
 }
 
@@ -261,11 +337,19 @@ bool launch(hipStream_t s, const float *x, const float *wr, const float *bias, c
 static_assert(kRnnMaxH <= 16 * kRnnMaxWaves * kRnnTilesPerWave, "the hidden units of the cap fit the workgroup");
 
 bool rnn(hipStream_t s, const float *x, const float *wr, const float *bias, const float *bias2, const float *h0, const float *c0, float *y, int64_t rows,
-         int op, int T, int F, int H, int D, bool reverse, bool lbr, bool relu, int mode, bool x_colmajor) {
+         int op, int T, int F, int H, int D, bool reverse, bool lbr, bool relu, int mode, bool x_colmajor, const float *lens, int64_t lens_ld, int lens_off,
+         bool lens_int, int *err, int err_node) {
   if (rows <= 0) return true;
-  if (op == kRnnLstm) return launch<kRnnLstm>(s, x, wr, bias, bias2, h0, c0, y, rows, T, F, H, D, reverse, lbr, relu, mode, x_colmajor);
-  if (op == kRnnGru) return launch<kRnnGru>(s, x, wr, bias, bias2, h0, c0, y, rows, T, F, H, D, reverse, lbr, relu, mode, x_colmajor);
-  return launch<kRnnPlain>(s, x, wr, bias, bias2, h0, c0, y, rows, T, F, H, D, reverse, lbr, relu, mode, x_colmajor);
+  // (lengths are read as a column of a row-major buffer beside a row-major x; the failure word is theirs)
+  if (lens && (x_colmajor || !err || lens_off < 0 || lens_off >= lens_ld)) return false;
+  const RnnLens ln{lens, lens_ld, lens_off, lens_int, err, err_node};
+#define INFERA_RNN_LAUNCH(OP) \
+  (lens ? launch<OP, true>(s, x, wr, bias, bias2, h0, c0, y, rows, T, F, H, D, reverse, lbr, relu, mode, x_colmajor, ln) \
+        : launch<OP, false>(s, x, wr, bias, bias2, h0, c0, y, rows, T, F, H, D, reverse, lbr, relu, mode, x_colmajor))
+  if (op == kRnnLstm) return INFERA_RNN_LAUNCH(kRnnLstm);
+  if (op == kRnnGru) return INFERA_RNN_LAUNCH(kRnnGru);
+  return INFERA_RNN_LAUNCH(kRnnPlain);
+#undef INFERA_RNN_LAUNCH
 }
 
 }  // namespace infera_hip::kern

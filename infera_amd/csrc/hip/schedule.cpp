@@ -561,8 +561,8 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
       m.in_colmajor_ok = false;
       m.in_colmajor_max_rows = INT64_MAX;
     }
-    // a row mask is read from the input buffer as T consecutive columns of a row: such plans take their chunk row-major, like window and
-    // Embed plans
+    // a row mask is read from the input buffer as T consecutive columns of a row (a recurrent layer's sequence_lens: as one column): such
+    // plans take their chunk row-major, like window and Embed plans
     if (std::any_of(st.begin(), st.end(), [](const Step &s) { return s.in3 >= 0; })) {
       m.in_colmajor_ok = false;
       m.in_colmajor_max_rows = INT64_MAX;

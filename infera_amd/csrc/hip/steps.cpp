@@ -343,8 +343,11 @@ void upload_rnn(const Step &s, RnnTables &t, const Upload &up) {
 }
 void launch_rnn(const PassRunner &r, const Step &x, const RnnTables &t) {
   const RnnPack &k = *x.rnn;
+  const bool lens = x.in3 >= 0;  // per-row sequence lengths: a column of the input buffer, which such plans take row-major (schedule.cpp)
+  if (lens && r.in_colmajor) throw InferaError::onnx("internal: '" + x.origin + "' reads sequence_lens from a column-major chunk");
   if (!kern::rnn(r.stream, r.buf(x.in0), t.wr, t.bias, t.bias2, t.h0, t.c0, r.buf(x.out), r.nr, k.op, int(k.T), int(k.F), int(k.H), int(k.D), k.reverse, k.lbr,
-                 k.relu, x.out_mode, r.in_colmajor && x.in0 == 0))
+                 k.relu, x.out_mode, r.in_colmajor && x.in0 == 0, lens ? r.buf(x.in3) : nullptr, lens ? r.p.buf_per_row[size_t(x.in3)] : 0, int(x.rm_off),
+                 x.rm_int, lens ? r.ctx.prep_err : nullptr, x.rnn_node))
     throw InferaError::onnx("recurrent kernel launch failed: '" + x.origin + "' could not be given its LDS");
 }
 

@@ -879,7 +879,7 @@ struct Lowerer {
     auto pit = producer.find(a.buf);
     Step *p = pit == producer.end() ? nullptr : &plan.steps[size_t(pit->second)];
     if (p && p->kind == StepKind::Recurrent && p->out == a.buf && p->out_mode == kRnnY && p->rnn->D == 1 && !p->rnn->reverse && t == T - 1 &&
-        C == p->rnn->H && live_uses(a.buf) == 1) {
+        C == p->rnn->H && live_uses(a.buf) == 1 && p->in3 < 0) {  // (with sequence_lens Y[T - 1] is 0 for a short row, not its Y_h)
       p->out_mode = kRnnYh;
       p->origin += "+" + node_label(n);
       plan.buf_per_row[size_t(a.buf)] = C;
@@ -2620,8 +2620,10 @@ struct Lowerer {
     *v = t->dtype == onnx::kInt64 ? double(t->i64[0]) : double(t->f32[0]);
     return true;
   }
-  // `v0` as a row mask; "" or why it is none
-  std::string trace_row_mask(const std::string &v0, RowMask *rm) const {
+  // `v0` as a row mask; "" or why it is none.  lens: as the length column of a recurrent layer's sequence_lens (find_seq_lens): the same
+  // source tracing through Cast / Reshape / Flatten only, and the source may be a rank-1 value
+  std::string trace_row_mask(const std::string &v0, RowMask *rm, bool lens = false) const {
+    const std::string what = lens ? "sequence_lens" : "mask";
     std::vector<size_t> chain;
     std::string v = v0;
     for (int hop = 0; hop < 32; hop++) {
@@ -2630,26 +2632,32 @@ struct Lowerer {
       const NodeDef &p = m.nodes[pi->second];
       if (!graph->std_dom(p) || p.inputs.empty()) break;
       double c;
-      if (p.op == "Unsqueeze" || p.op == "Reshape" || p.op == "Cast" || p.op == "Expand" || p.op == "Not") v = p.inputs[0];
+      if (lens) {
+        if (p.op != "Reshape" && p.op != "Cast" && p.op != "Flatten") break;
+        v = p.inputs[0];
+      } else if (p.op == "Unsqueeze" || p.op == "Reshape" || p.op == "Cast" || p.op == "Expand" || p.op == "Not") v = p.inputs[0];
       else if (p.op == "Equal" && p.inputs.size() == 2) v = p.inputs[graph_const_scalar(p.inputs[0], &c) ? 1 : 0];
       else break;
       chain.push_back(pi->second);
     }
     if (auto pi = graph->producer_of.find(v); pi != graph->producer_of.end() && m.nodes[pi->second].op == "Transpose")
-      return "a time-major mask source (the Transpose '" + node_label(m.nodes[pi->second]) + "' in front of it); only a rows-first [N, T] graph input";
+      return "a time-major " + what + " source (the Transpose '" + node_label(m.nodes[pi->second]) + "' in front of it); only a rows-first " +
+             (lens ? "[N] or [N, 1]" : "[N, T]") + " graph input";
+    if (auto pi = graph->producer_of.find(v); lens && pi != graph->producer_of.end() && m.nodes[pi->second].op == "ReduceSum")
+      return "sequence_lens computed by the ReduceSum '" + node_label(m.nodes[pi->second]) + "' (lengths derived from a mask are not supported; pass the length column itself)";
     EmbedCols cols;
-    if (!embed_cols(v, &cols).empty() || !cols.rank2 || !cols.off.empty())
-      return "the mask source '" + v + "' is not a column range of a graph input (a mask computed from activations is not supported)";
+    if (!embed_cols(v, &cols).empty() || (!cols.rank2 && !lens) || !cols.off.empty())
+      return "the " + what + " source '" + v + "' is not a column range of a graph input (a " + (lens ? "length" : "mask") + " computed from activations is not supported)";
     rm->src0 = cols.src0, rm->k = cols.k;
     rm->is_int = cols.int_input || cols.truncated;
     rm->nodes = cols.chain;
-    rm->shape = {-1, cols.k};
+    rm->shape = cols.rank2 ? std::vector<int64_t>{-1, cols.k} : std::vector<int64_t>{-1};
     rm->state = 0;
     rm->cmp = 0.f;
     bool expanded = false;
     for (auto it = chain.rbegin(); it != chain.rend(); ++it) {
       const NodeDef &p = m.nodes[*it];
-      const std::string at = "'" + node_label(p) + "' in the mask sub-graph: ";
+      const std::string at = "'" + node_label(p) + "' in the " + what + " sub-graph: ";
       rm->nodes.push_back(*it);
       std::vector<int64_t> &sh = rm->shape;
       if (p.op == "Cast") {
@@ -2668,6 +2676,9 @@ struct Lowerer {
         rm->state = 1;
       } else if (expanded) {
         return at + "a " + p.op + " behind the Expand";
+      } else if (p.op == "Flatten") {  // (lens only) [N, k] stays [N, k]
+        const int64_t axis = p.attr_i("axis", 1);
+        if (sh.size() != 2 || (axis != 1 && axis != -1)) return at + "only Flatten(axis = 1) of an [N, k] value";
       } else if (p.op == "Unsqueeze") {
         std::vector<int64_t> ax;
         if (!graph_ints_arg(p, 1, "axes", &ax) || ax.empty()) return at + "axes must be constant";
@@ -2694,7 +2705,7 @@ struct Lowerer {
           if (per % known) return at + "the target " + shape_str(tgt);
           tgt[size_t(neg)] = per / known, known = per;
         }
-        if (known != per) return at + "the target " + shape_str(tgt) + " does not keep the " + std::to_string(per) + " mask values of a row";
+        if (known != per) return at + "the target " + shape_str(tgt) + " does not keep the " + std::to_string(per) + " " + (lens ? "length" : "mask") + " values of a row";
         tgt[0] = -1;
         sh = tgt;
       } else {  // Expand: a constant target is checked; one computed from a Shape broadcasts to its reader's shape, as ONNX would anyway
@@ -4016,6 +4027,57 @@ struct Lowerer {
     if (expand && dims.size() == 3 && lead >= 0) expanded_lead[n.outputs[0]] = lead;
     vals[n.outputs[0]] = const_f32(std::move(o), dims);
   }
+  // ---- per-row sequence lengths (INTEGRATION.md 2.6 "Padded windows") ----------------------------------------------------------------
+  // Input 4 of LSTM / GRU / RNN, sequence_lens, traced back to ONE column of a graph input before the walk: an [N] integer input, an
+  // [N, 1] one through Squeeze / Reshape([-1]) / Flatten, a column of a wider input picked by Slice / Gather(axis = 1), with or without
+  // Cast (PyTorch: Cast(lengths, INT32)).  The tracing nodes emit nothing and the value may feed every layer of a stack; the steps read the
+  // column from the input buffer (Step::in3, rm_off, rm_int).  A constant sequence_lens is left to pack_recurrent, which refuses it.
+  struct SeqLens {
+    int64_t col = 0;
+    bool is_int = false;
+    int node = 0;  // 1-based id in plan.prep_strict_nodes
+  };
+  std::map<size_t, SeqLens> seq_lens_at;  // recurrent node -> its lengths
+
+  void find_seq_lens() {
+    std::set<size_t> chain;
+    for (size_t i = 0; i < m.nodes.size(); i++) {
+      const NodeDef &n = m.nodes[i];
+      if (!graph->live[i] || !graph->std_dom(n) || (n.op != "LSTM" && n.op != "GRU" && n.op != "RNN") || !has_input(n, 4) || !graph->row_data.count(n.inputs[4])) continue;
+      RowMask r;
+      if (const std::string why = trace_row_mask(n.inputs[4], &r, true); !why.empty()) bad_form(n, why);
+      if (r.k != 1 || r.shape != std::vector<int64_t>{-1})
+        bad_form(n, "sequence_lens traced to " + std::to_string(r.k) + " column" + (r.k == 1 ? "" : "s") + " of a graph input as " + shape_str(r.shape) +
+                        "; only one length per row, [N]");
+      if (!r.is_int) bad_form(n, "sequence_lens read from a float graph input without a Cast to an integer type");
+      if (plan.input_declared_type == "float16") bad_form(n, "sequence_lens taken from a float16 graph input");
+      if (r.src0 < 0 || r.src0 >= plan.buf_per_row[0]) bad_form(n, "the sequence_lens column lies outside the input");
+      plan.prep_strict_nodes.push_back({"node '" + (n.name.empty() ? n.op : n.name) + "' (" + n.op + ")", ": sequence_lens outside 0…T"});
+      seq_lens_at[i] = {r.src0, r.is_int, int(plan.prep_strict_nodes.size())};
+      chain.insert(r.nodes.begin(), r.nodes.end());
+    }
+    // what a tracing node computes is read by recurrent layers as sequence_lens and by nothing else
+    const std::string &served = m.outputs[out_index].name;
+    for (size_t i : chain)
+      for (const auto &o : m.nodes[i].outputs) {
+        bool ok = o != served;
+        if (auto it = graph->consumers_of.find(o); it != graph->consumers_of.end())
+          for (size_t c : it->second) {
+            const NodeDef &r = m.nodes[c];
+            const bool as_lens = seq_lens_at.count(c) && std::count(r.inputs.begin(), r.inputs.end(), o) == 1 && r.inputs[4] == o;
+            ok = ok && (chain.count(c) || as_lens);
+          }
+        if (!ok) bad_form(m.nodes[i], "this node of a sequence_lens sub-graph also feeds nodes outside the recurrent layers' sequence_lens");
+      }
+    for (size_t i : chain) {
+      absorbed[i] = 1;
+      region[i] = 0;
+      for (const auto &in : m.nodes[i].inputs)
+        if (!in.empty()) uses[in]--;
+    }
+    for (const auto &kv : seq_lens_at) uses[m.nodes[kv.first].inputs[4]]--;
+  }
+
   // LSTM / GRU / RNN: one Recurrent step per output that is read.  X is [T, rows, F] (layout 0: time-major, row-axis tag 1) or
   // [rows, T, F] (layout 1); the step writes Y as [rows, T, D, H] and the last states as [rows, D, H], and the values carry ONNX's shapes
   // with the row-axis tag that makes them so
@@ -4036,9 +4098,11 @@ struct Lowerer {
       return r;
     };
     const bool lstm = n.op == "LSTM";
+    auto sl = seq_lens_at.find(size_t(&n - m.nodes.data()));  // (traced: the value itself was never produced)
+    const bool lens = sl != seq_lens_at.end();
     std::shared_ptr<const RnnPack> rp;
     try {
-      rp = std::make_shared<const RnnPack>(pack_recurrent(n, x.shape[size_t(layout)], x.shape[2], arg(1), arg(2), arg(3), arg(4), arg(5),
+      rp = std::make_shared<const RnnPack>(pack_recurrent(n, x.shape[size_t(layout)], x.shape[2], arg(1), arg(2), arg(3), lens ? RnnInput{} : arg(4), arg(5),
                                                           lstm ? arg(6) : RnnInput{}, lstm ? arg(7) : RnnInput{}));
     } catch (const RnnError &e) {
       unsupported(n, e.what());
@@ -4051,6 +4115,12 @@ struct Lowerer {
       s.in0 = x.buf;
       s.rnn = rp;
       s.out_mode = o == 0 ? kRnnY : o == 1 ? kRnnYh : kRnnYc;
+      if (lens) {
+        s.in3 = 0;
+        s.rm_off = sl->second.col;
+        s.rm_int = sl->second.is_int;
+        s.rnn_node = sl->second.node;
+      }
       s.origin = node_label(n);
       Val v;
       v.buf = push_step(std::move(s), {N, o == 0 ? T * D * H : D * H});
@@ -5011,14 +5081,17 @@ struct Lowerer {
     if (auto *p = n.attr_ints(attr)) *v = *p;
     return true;
   }
+  // the columns an input of a multi-input model takes in the input buffer: k of [rows, k]; a rank-1 [rows] integer input is one column
+  static int64_t input_cols(const onnx::ValueDef &v) { return v.dims.size() == 1 ? 1 : v.dims[1]; }
   // `v` as columns of the input buffer; "" or why it is none
   std::string embed_cols(const std::string &v, EmbedCols *c, int depth = 0) const {
     int64_t off = 0;
     for (const auto &in : m.inputs) {
-      const int64_t w = m.inputs.size() == 1 ? (in.dims.size() == 2 ? in.dims[1] : 0) : in.dims[1];
+      const int64_t w = m.inputs.size() == 1 ? (in.dims.size() == 2 ? in.dims[1] : 0) : input_cols(in);
       if (in.name == v) {
-        if (in.dims.size() != 2) return "indices of rank " + std::to_string(in.dims.size()) + " (graph input '" + v + "'); only [N] and [N, k]";
-        c->src0 = off, c->k = w, c->rank2 = true;
+        const bool one_col = m.inputs.size() > 1 && in.dims.size() == 1;  // (a rank-1 integer input: run())
+        if (in.dims.size() != 2 && !one_col) return "indices of rank " + std::to_string(in.dims.size()) + " (graph input '" + v + "'); only [N] and [N, k]";
+        c->src0 = off, c->k = w, c->rank2 = !one_col;
         c->int_input = in.elem_type == onnx::kInt64 || in.elem_type == onnx::kInt32;
         return "";
       }
@@ -5042,6 +5115,10 @@ struct Lowerer {
       if (p.op == "Cast" && !to_int && to != onnx::kFloat && to != onnx::kDouble) return by;
       if (!(why = embed_cols(p.inputs[0], c, depth + 1)).empty()) return why;
       c->truncated = c->truncated || to_int;
+    } else if (p.op == "Flatten") {  // [N, k] stays [N, k]
+      const int64_t axis = p.attr_i("axis", 1);
+      if (!(why = embed_cols(p.inputs[0], c, depth + 1)).empty()) return why;
+      if (!c->rank2 || (axis != 1 && axis != -1)) return by;
     } else if (p.op == "Gather") {
       std::vector<int64_t> iv, idims;
       if (p.inputs.size() != 2 || !graph_const_ints(p.inputs[1], &iv, &idims) || idims.size() > 1 || iv.empty()) return by;
@@ -5872,14 +5949,16 @@ struct Lowerer {
     if (m.inputs.size() > 1) {
       // Several runtime inputs (the reference feeds input 0 only, engine.rs:139-145, so such a model cannot run
       // there at all): the feature columns of the call are split across the inputs in declaration order.  Every
-      // input must be an f32 [rows, k_i] matrix with the same leading dimension.
+      // input must be an f32 [rows, k_i] matrix with the same leading dimension.  A rank-1 [rows] int32 / int64 input counts as one
+      // column (the length column of padded windows: sequence_lens is rank 1).
       int64_t total = 0;
       for (const auto &v : m.inputs) {
-        if (!v.has_shape || v.dims.size() != 2 || v.dims[1] <= 0 || !served_type(v.elem_type) ||
+        const bool one_col = v.has_shape && v.dims.size() == 1 && (v.elem_type == onnx::kInt64 || v.elem_type == onnx::kInt32);
+        if (!v.has_shape || (v.dims.size() != 2 && !one_col) || (!one_col && v.dims[1] <= 0) || !served_type(v.elem_type) ||
             (v.dims[0] > 0 ? v.dims[0] : -1) != plan.input_shape[0])
           throw InferaError::onnx("multi-input models need f32 [rows, k] inputs with one common leading dimension; input '" + v.name + "' is " +
                                   (v.has_shape ? shape_str(v.dims) : std::string("unshaped")));
-        total += v.dims[1];
+        total += input_cols(v);
       }
       plan.input_shape[1] = total;
     }
@@ -5918,16 +5997,17 @@ struct Lowerer {
     if (nearest_enabled) find_nearest();
     find_group_norms();
     find_embeds();
+    find_seq_lens();
     {
       int64_t off = 0;
       for (const auto &v : m.inputs) {
-        const int64_t w = m.inputs.size() == 1 ? prod(plan.input_shape, 1) : v.dims[1];
+        const int64_t w = m.inputs.size() == 1 ? prod(plan.input_shape, 1) : input_cols(v);
         if (region_inputs.count(v.name)) {
           if (m.inputs.size() == 1 && plan.input_shape.size() != 2 && int_input(v))
             throw InferaError::onnx("integer input '" + v.name + "' must be [rows, k]");
           PrepVal p = prep_identity(0, off, w, int_input(v), false);
           if (int_input(v)) p.origin.push_back("input:" + v.name);
-          set_prep(v.name, std::move(p), m.inputs.size() == 1 ? plan.input_shape : std::vector<int64_t>{plan.input_shape[0], w});
+          set_prep(v.name, std::move(p), m.inputs.size() == 1 ? plan.input_shape : v.dims.size() == 1 ? std::vector<int64_t>{plan.input_shape[0]} : std::vector<int64_t>{plan.input_shape[0], w});
         }
         off += w;
       }
@@ -5939,9 +6019,11 @@ struct Lowerer {
       all.shape = plan.input_shape;
       int64_t off = 0;
       for (const auto &v : m.inputs) {
-        if (uses.count(v.name) && uses[v.name] > 0 && !region_inputs.count(v.name))
-          emit_slice_cols("input:" + v.name, all, off, off + v.dims[1], v.name);
-        off += v.dims[1];
+        if (uses.count(v.name) && uses[v.name] > 0 && !region_inputs.count(v.name)) {
+          emit_slice_cols("input:" + v.name, all, off, off + input_cols(v), v.name);
+          if (v.dims.size() == 1) vals[v.name].shape = {plan.input_shape[0]};
+        }
+        off += input_cols(v);
       }
     }
     for (size_t ni = 0; ni < m.nodes.size(); ni++) {

@@ -219,6 +219,7 @@ std::string Plan::describe_json() const {
         << (r.D == 2 ? "bidirectional" : r.reverse ? "reverse" : "forward") << "\",\"output\":\"" << modes[s.out_mode] << "\"";
       if (r.op == kRnnGru) o << ",\"linear_before_reset\":" << (r.lbr ? 1 : 0);
       if (r.op == kRnnPlain) o << ",\"activation\":\"" << (r.relu ? "Relu" : "Tanh") << "\"";
+      if (s.in3 >= 0) o << ",\"seq_lens\":{\"src_col\":" << s.rm_off << "}";
     }
     if (s.act != Act::None) o << ",\"act\":\"" << acts[int(s.act)] << "\"";
     o << ",\"origin\":" << json_str(s.origin) << "}";

@@ -164,7 +164,10 @@ struct Step {
   // -1: none), step t of a row is kept iff in3[r, rm_off + t] (rm_int: an integer graph input, truncated toward zero) != rm_cmp.
   // Attention: rm_fill reaches a masked key's score by rm_mode (RowMaskMode, host/attention.hpp); rm_excl: the fill excludes the key.
   // MeanTime: the sum over the kept steps is divided by max(count, rm_clip)
+  // Recurrent with sequence_lens (INTEGRATION.md 2.6 "Padded windows"): in3 = the same buffer, row r holds in3[r, rm_off] valid steps (rm_int
+  // as above); rnn_node = the node's 1-based id in Plan::prep_strict_nodes, the failure word of a length outside 0 .. T
   int in3 = -1;
+  int rnn_node = 0;
   int64_t rm_off = 0;
   float rm_cmp = 0.f, rm_fill = 0.f, rm_clip = 0.f;
   int rm_mode = 0;
@@ -200,7 +203,7 @@ struct Plan {
   bool output_zipmap = false;        // the served output is a ZipMap's: its input [rows, C] is served, one column per class label
   // the checks a call can fail on the device, by 1-based id (the ids in the Prep and Embed descriptors): a call whose failure word is set
   // fails with `node` + `message` of that entry.  node: "node 'name' (OneHotEncoder)" of a zeros = 0 one-hot encoder, "node 'name' (Gather)"
-  // of an embedding lookup
+  // of an embedding lookup, "node 'name' (LSTM)" of a recurrent layer with sequence_lens
   struct StrictNode {
     std::string node, message;
   };

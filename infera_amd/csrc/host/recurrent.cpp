@@ -83,6 +83,8 @@ RnnPack pack_recurrent(const onnx::NodeDef &n, int64_t T, int64_t F, const RnnIn
     for (size_t i = 0; ok && i < a->strings.size(); i++) ok = a->strings[i] == dflt[i % per];
     if (!ok) fail("activations (" + got + ") other than the defaults" + (p.op == kRnnPlain ? " (Tanh or Relu, the same for both directions)" : ""));
   }
+  // (lengths that are a column of a graph input never come here: the lowering traces them, find_seq_lens; what is left is a constant, which
+  // cannot match a symbolic row count)
   if (seq_lens.present && !(seq_lens.c && seq_lens.c->count() == 0)) fail("sequence_lens (per-row sequence lengths)");
 
   const std::vector<float> &w = f32_const(W, "W", {D, G * H, F});

@@ -835,7 +835,8 @@ def torch_recurrent_spec(module) -> dict:
 
 def recurrent_from_spec(spec: dict, T: int | None = None, form: str = "batch_first", tail: str = "seq", flat: bool = False,
                         head: tuple | None = None, scaler: tuple | None = None, initial: str = "const", opset: int = 14,
-                        extra_attrs: Sequence[bytes] = (), last_index: int = -1, state_outputs: bool = False) -> bytes:
+                        extra_attrs: Sequence[bytes] = (), last_index: int = -1, state_outputs: bool = False,
+                        seq_lens: dict | None = None) -> bytes:
     """The ONNX model of a recurrent_spec() / torch_recurrent_spec() dict, input X [N, T, F] (flat: [N, T*F] -> Reshape).
     form: "batch_first" (Transpose(1,0,2) -> time-major layers -> Transpose back, what PyTorch writes for batch_first=True) or "layout1"
     (layout = 1, no Transpose).  Layers are stacked through Squeeze(axes 1) (one direction) or Transpose(0,2,1,3) + Reshape [0,0,-1].
@@ -844,12 +845,81 @@ def recurrent_from_spec(spec: dict, T: int | None = None, form: str = "batch_fir
     (+ activation) behind a 2-D tail.  scaler = (offset, scale) over the flat T*F columns (needs flat).  initial: how a layer's constant initial
     state is written: "const" ([D, 1, H] initializer), "expand" (Shape(X) -> Gather -> Unsqueeze -> Concat -> Expand) or "fill" (the
     same shape sub-graph -> ConstantOfShape: a state of one value, as PyTorch writes its zeros).  state_outputs: the
-    last layer's Y_h (and Y_c) are graph outputs too, under the names "Y_h" / "Y_c"."""
+    last layer's Y_h (and Y_c) are graph outputs too, under the names "Y_h" / "Y_c".
+    seq_lens (None: no input 4, the bytes of every model so far): per-row sequence lengths as input 4 of EVERY layer; X is then flat
+    ([N, T*F]).  A dict with "form": where the lengths come from: "rank1" (one more input len [N]), "col" (len [N, 1]), "wide" (meta [N, k],
+    column "col" of it) or "single" (no second input: X is [N, T*F + 1], the readings are Slice(X, 0:T*F) and the length is its last column);
+    "type": INT32 / INT64 / FLOAT (/ FLOAT16, single) of that input (default INT64; single: FLOAT); "cast": Cast(to = INT32) behind it
+    (default: unless the type is INT32, as PyTorch writes Cast(lengths, INT32)); "squeeze": how [N, 1] becomes [N]: "squeeze"
+    (Squeeze(axes = [1])), "reshape" (Reshape([-1])) or "flatten" (Flatten -> Squeeze); "pick" (wide): "slice" (Slice on axis 1, then the
+    squeeze) or "gather" (Gather(axis = 1) by a scalar index: [N] at once).  Forms that are refused: "source": "transpose" (an [N, 1] input
+    transposed to [1, N] and reshaped), "reduce_sum" (ReduceSum of an [N, T] mask), "activation" (ArgMax over X), "two_cols" (an [N, 2]
+    input as it is); "shared": True (needs a 2-D tail: the length also multiplies the served output).  "extra_output": True adds the
+    length as a second graph output "len_out", which is not the served one."""
     op, H, D, F = spec["op"], spec["H"], spec["D"], spec["F"]
     T = spec["T"] if T is None else T
     nodes, inits = [], []
     i64 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.int64)))  # noqa: E731
     x = "X"
+    lens_value, lens_input, sl = "", None, None
+    if seq_lens is not None:
+        flat = True
+        sl = dict(form="rank1", squeeze="squeeze", pick="slice", k=3, col=1, source="input", shared=False, extra_output=False)
+        sl.update(seq_lens)
+        sl.setdefault("type", FLOAT if sl["form"] == "single" else INT64)
+        cast = sl.get("cast", sl["type"] != INT32)
+        i64("sl_ax1", [1])
+        v, shape1 = "len", False  # shape1: v is [N] already
+        if sl["source"] == "transpose":
+            lens_input = value_info("len", ["N", 1], sl["type"])
+            nodes.append(node("Transpose", ["len"], ["len_t"], [attr_ints("perm", [1, 0])], name="sl_transpose"))
+            v, sl["squeeze"] = "len_t", "reshape"
+        elif sl["source"] == "reduce_sum":
+            lens_input = value_info("len", ["N", T], sl["type"])
+            nodes.append(node("ReduceSum", ["len", "sl_ax1"], ["len_s"], [attr_i("keepdims", 0)], name="sl_sum"))
+            v, shape1 = "len_s", True
+        elif sl["source"] == "activation":
+            lens_input = value_info("len", ["N", 1], sl["type"])  # (declared and not read)
+            nodes.append(node("ArgMax", ["X"], ["len_a"], [attr_i("axis", 1), attr_i("keepdims", 0)], name="sl_argmax"))
+            v, shape1, cast = "len_a", True, True
+        elif sl["source"] == "two_cols":
+            lens_input = value_info("len", ["N", 2], sl["type"])
+            shape1 = True
+        elif sl["form"] == "rank1":
+            lens_input = value_info("len", ["N"], sl["type"])
+            shape1 = True
+        elif sl["form"] == "col":
+            lens_input = value_info("len", ["N", 1], sl["type"])
+        elif sl["form"] == "single":
+            i64("sl_x0", [0]); i64("sl_x1", [T * F]); i64("sl_c1", [T * F + 1])  # noqa: E702
+            nodes += [node("Slice", ["X", "sl_x0", "sl_x1", "sl_ax1"], ["X_readings"], name="sl_readings"),
+                      node("Slice", ["X", "sl_x1", "sl_c1", "sl_ax1"], ["len_c"], name="sl_slice")]
+            x, v = "X_readings", "len_c"
+        else:
+            lens_input = value_info("meta", ["N", sl["k"]], sl["type"])
+            v = "meta"
+            if sl["pick"] == "gather":
+                i64("sl_ix", sl["col"])
+                nodes.append(node("Gather", [v, "sl_ix"], ["len_g"], [attr_i("axis", 1)], name="sl_gather"))
+                v, shape1 = "len_g", True
+            else:
+                i64("sl_c0", [sl["col"]]); i64("sl_c1", [sl["col"] + 1])  # noqa: E702
+                nodes.append(node("Slice", [v, "sl_c0", "sl_c1", "sl_ax1"], ["len_c"], name="sl_slice"))
+                v = "len_c"
+        if not shape1:
+            if sl["squeeze"] == "reshape":
+                i64("sl_flat", [-1])
+                nodes.append(node("Reshape", [v, "sl_flat"], ["len_1"], name="sl_reshape"))
+            else:
+                if sl["squeeze"] == "flatten":
+                    nodes.append(node("Flatten", [v], ["len_f"], [attr_i("axis", 1)], name="sl_flatten"))
+                    v = "len_f"
+                nodes.append(node("Squeeze", [v, "sl_ax1"], ["len_1"], name="sl_squeeze"))
+            v = "len_1"
+        if cast:
+            nodes.append(node("Cast", [v], ["len_i32"], [attr_i("to", INT32)], name="sl_cast"))
+            v = "len_i32"
+        lens_value = v
     if scaler is not None:
         nodes.append(node("Scaler", [x], ["Xs"], [attr_floats("offset", scaler[0]), attr_floats("scale", scaler[1])], domain=ML_DOMAIN))
         x = "Xs"
@@ -866,7 +936,7 @@ def recurrent_from_spec(spec: dict, T: int | None = None, form: str = "batch_fir
     for i, L in enumerate(spec["layers"]):
         p = f"l{i}_"
         inits += [tensor(p + "W", L["W"]), tensor(p + "R", L["R"])]
-        ins = [x, p + "W", p + "R", "", "", "", ""]
+        ins = [x, p + "W", p + "R", "", lens_value, "", ""]
         if L["B"] is not None:
             inits.append(tensor(p + "B", L["B"]))
             ins[3] = p + "B"
@@ -945,7 +1015,18 @@ def recurrent_from_spec(spec: dict, T: int | None = None, form: str = "batch_fir
             nodes.append(node(act, [out], ["prob"]))
             out = "prob"
     in_dims = ["N", T * F] if (flat or scaler is not None) else ["N", T, F]
+    x_type = FLOAT
+    if sl is not None:
+        if sl["form"] == "single":
+            in_dims, x_type = ["N", T * F + 1], sl["type"]
+        if sl["shared"]:  # the length reaches the served output a second way
+            nodes += [node("Cast", [lens_value], ["len_f32"], [attr_i("to", FLOAT)], name="sl_share_cast"),
+                      node("Unsqueeze", ["len_f32", "sl_ax1"], ["len_f32c"], name="sl_share_col"), node("Mul", [out, "len_f32c"], ["out_scaled"], name="sl_share")]
+            out = "out_scaled"
     outs = [value_info(out, dims)]
+    if sl is not None and sl["extra_output"]:
+        nodes.append(node("Cast", [lens_value], ["len_out"], [attr_i("to", INT64)], name="sl_out"))
+        outs.append(value_info("len_out", ["N"], INT64))
     if state_outputs:
         sdims = ["N", D, H] if lay1 else [D, "N", H]
         nodes.append(node("Identity", [yh], ["Y_h"]))
@@ -953,7 +1034,8 @@ def recurrent_from_spec(spec: dict, T: int | None = None, form: str = "batch_fir
         if op == "LSTM":
             nodes.append(node("Identity", [yc], ["Y_c"]))
             outs.append(value_info("Y_c", sdims))
-    return model("recurrent", nodes, inits, [value_info("X", in_dims)], outs, opset=opset, ml_opset=1 if scaler is not None else None)
+    ins_info = [value_info("X", in_dims, x_type)] + ([lens_input] if lens_input is not None else [])
+    return model("recurrent", nodes, inits, ins_info, outs, opset=opset, ml_opset=1 if scaler is not None else None)
 
 
 # ------------------------------------------------------------------------------------------
