@@ -242,6 +242,172 @@ struct Lowerer {
   // plan the bit-identity tests compare the Nearest kernel against
   const bool nearest_enabled = ScheduleKnobs::read().nearest;
   std::set<int> int_bufs;  // buffers whose f32 values are whole numbers by construction (ArgMax, integer Cast, label arithmetic)
+  size_t out_index = 0;
+  std::unique_ptr<const GraphIndex> graph;  // the graph as the served output sees it (run)
+
+  // ---- Instance / Group norm, the channels-last view, Tokens, LayerNorm ----
+  // The exporter's spelling of nn.GroupNorm below opset 18: Reshape(x, [0, G, -1]) -> InstanceNormalization(scale[G], B[G]) -> Reshape(back to
+  // x's shape, a constant or the folded Shape(x)) [-> Mul(gamma [C,1,1])] [-> Add(beta)].  The chain is found structurally before the walk
+  // (find_group_norms: operators and sole readers), anchored at the first Reshape; shapes and constants are checked when the walk reaches
+  // the anchor (false: every node lowers by its own rule), and the nodes behind it emit nothing.
+  struct GnMatch {
+    size_t inorm = 0, back = 0;
+  };
+  std::map<size_t, GnMatch> gn_at;  // index of the first Reshape -> the chain behind it
+  int view_consts = 0;
+  std::map<std::string, int64_t> expanded_lead;  // results of Expand over constants -> the leading entry of the target shape as the graph had it
+
+  // ---- self-attention (INTEGRATION.md section 2.6) ----------------------------------------------------------------------------
+  // The batch-first graph exporters write is matched structurally before the walk (find_attention: by operator, perm and which operands
+  // are constants), anchored at the merge Reshape; the nodes inside emit nothing, and the anchor validates shapes and constants and emits
+  // ONE Attention step (lower_attention).  A MatMul of two activations that starts no such pattern is rejected with the reason kept here.
+  struct AttnScale {
+    char op;  // '*' or '/'
+    std::string cst;
+  };
+  struct AttnSide {
+    std::string src, shape;   // the [N, T, E] value the head split reads (behind an absorbed Split / Slice: its input) and the Reshape's target
+    const NodeDef *cut = nullptr;  // that Split / Slice on the last axis
+    size_t cut_out = 0;
+  };
+  // A row's own key mask (INTEGRATION.md 2.6 "Padded sequences"): T consecutive columns of the input buffer and a compare value, traced
+  // back from where it meets the scores (or the masked mean) through Cast / Unsqueeze / Reshape / Expand / Equal / Not to a graph input
+  struct RowMask {
+    int64_t src0 = 0, k = 0;     // columns [src0, src0 + k) of the input buffer
+    bool is_int = false;         // the graph sees them as integers: truncated toward zero before the comparison
+    float cmp = 0.f;             // kept iff value != cmp
+    int state = 0;               // the traced value: 0 the source's own values (kept iff != 0), 1 a bool true = masked, 2 a bool true = kept
+    std::vector<int64_t> shape;  // of the traced value in front of any Expand; shape[0] = -1, the rows
+    std::vector<size_t> nodes, aux;  // the nodes between the graph input and the value; aux: the Shape sub-graph that sizes an Expand
+    float fill = 0.f;            // Attention: the negative constant of masked keys, and how it reaches the score (RowMaskMode)
+    int mode = kRowMaskAdd;
+    const NodeDef *at = nullptr;  // the Add / Where on the scores
+  };
+  struct AttnMatch {
+    AttnSide side[3];  // Q, K, V
+    std::vector<AttnScale> scales;
+    std::string mask;
+    std::shared_ptr<RowMask> rm;
+    const NodeDef *qk = nullptr;
+    std::vector<size_t> nodes;
+  };
+  std::map<size_t, AttnMatch> attn_at;            // anchor node index -> the pattern it closes
+  std::vector<char> absorbed;                // nodes inside a recognised pattern (attention, or the decomposed LayerNorm): they emit nothing
+  std::map<const NodeDef *, std::string> attn_fail;  // MatMul(activation, activation) nodes outside one: why
+  struct MaskedMean {
+    std::string x;  // the window [N, T, E]
+    RowMask rm;
+    float clip = 0.f;
+    size_t mul = 0;
+  };
+  std::map<size_t, MaskedMean> mmean_at;  // the Div that closes a masked mean over time -> the pattern
+
+  // ---- quantised and float16 graphs ----
+  // the constant scale / zero point inputs (`si`, `zi`) of a quantisation node: one scale per tensor, or one per index of an axis
+  struct QArgs {
+    std::vector<float> scale;
+    std::vector<int64_t> zp;
+    int elem = onnx::kUint8;  // the quantised element type (the zero point's; uint8 without one)
+  };
+  std::map<std::string, const NodeDef *> quant_node;  // quantised value -> the node that made it
+
+  // ---- per-row sequence lengths (INTEGRATION.md 2.6 "Padded windows") ----------------------------------------------------------------
+  // Input 4 of LSTM / GRU / RNN, sequence_lens, traced back to ONE column of a graph input before the walk: an [N] integer input, an
+  // [N, 1] one through Squeeze / Reshape([-1]) / Flatten, a column of a wider input picked by Slice / Gather(axis = 1), with or without
+  // Cast (PyTorch: Cast(lengths, INT32)).  The tracing nodes emit nothing and the value may feed every layer of a stack; the steps read the
+  // column from the input buffer (Step::in3, rm_off, rm_int).  A constant sequence_lens is left to pack_recurrent, which refuses it.
+  struct SeqLens {
+    int64_t col = 0;
+    bool is_int = false;
+    int node = 0;  // 1-based id in plan.prep_strict_nodes
+  };
+  std::map<size_t, SeqLens> seq_lens_at;  // recurrent node -> its lengths
+
+  // ---- ai.onnx.ml preprocessing regions (host/prep.hpp).  A region is a connected set of Imputer / Scaler / Binarizer / OneHotEncoder /
+  // LabelEncoder / FeatureVectorizer / ArrayFeatureExtractor (constant indices) / Cast / Reshape / Flatten / Squeeze / Concat / Identity
+  // nodes and graph inputs that holds at least one thing nothing else serves: one of the five encoder nodes, a non-contiguous
+  // ArrayFeatureExtractor or an integer graph input.  Graphs without one lower exactly as before.  Inside a region every value is a
+  // list of column programs over one source buffer (PrepVal); where anything else reads a region value it becomes ONE Prep step.
+  std::vector<char> region;                           // node index -> lowered as part of a region
+  std::vector<std::shared_ptr<PrepTable>> prep_tables;  // LabelEncoder tables and strict one-hot category sets, by id
+  int64_t prep_cats = 0, prep_keys = 0;                 // one-hot categories / LabelEncoder keys in all (caps)
+
+  // ---- distance models (INTEGRATION.md section 2.6): |x - c|^2 of each row against a constant set C [M, F] ----------------------------
+  // Recognised before the walk (find_nearest) in the spellings exporters write,
+  //   rs = ReduceSumSquare(X, axes = [1], keepdims = 1);  g = Gemm(X, C, alpha = -2 [, transB]) | Mul(MatMul(X, C^T), -2);
+  //   D2 = Add(Add(rs, g), C2) | Add(rs, Add(g, C2))     (either operand order; C2[m] = |C[m]|^2 within rounding)
+  // when no intermediate has another reader; the contrib operator CDist(X, C) is the same value in one node.  The nodes emit nothing: the
+  // last one binds D2 to a pending value (Val::nn), and what reads it decides what the Nearest step serves -- ArgMin the label, TopK the
+  // best k, Sqrt the rooted distances, anything else (the graph output included) the [rows, M] matrix.
+  struct NearestMatch {
+    std::string x, d2, spelling;
+    std::shared_ptr<TensorData> c;
+    bool c_fm = false;  // C is stored [F, M]
+    std::vector<size_t> nodes;  // ascending; the last is the anchor
+  };
+  std::map<size_t, NearestMatch> nearest_at;  // anchor node index -> the pattern it closes
+
+  // ---- embedding lookups (host/embed.hpp; INTEGRATION.md 2.6 "Embedding lookups") ------------------------------------------------------
+  // Gather(axis = 0) of a constant f32 table [V, d] / [V] by indices that are columns of a graph input: the column picks (Gather(axis = 1) /
+  // Slice / Squeeze), Casts and constant offset Adds in front of it, the Reshape / Flatten of [N, k, d] to [N, k * d] and the feature-axis
+  // Concat that alone reads the lookups (with numeric columns of a graph input beside them) become ONE Embed step that reads the input
+  // buffer.  Found before the walk (find_embeds): a graph without such a Gather is lowered exactly as before.
+  struct EmbedCols {  // a value that is columns [src0, src0 + k) of the input buffer: [N, k] (rank2) or [N]
+    int64_t src0 = 0, k = 0;
+    bool rank2 = true, truncated = false, int_input = false;
+    std::vector<int64_t> off;   // the constant added to each column (empty: none)
+    std::vector<size_t> chain;  // the nodes between the graph input and the value
+  };
+  struct EmbedLookup {
+    size_t gather = 0;
+    std::shared_ptr<TensorData> table;
+    EmbedCols ix;
+    int64_t V = 0, d = 0;
+    std::vector<size_t> tail;  // the Reshape / Flatten behind it
+    std::string out;
+    std::vector<int64_t> shape;
+  };
+  struct EmbedGroup {
+    std::vector<EmbedLookup> lookups;
+    std::vector<std::pair<int, EmbedCols>> parts;  // in output order: (lookup, -) or (-1, columns to copy)
+    std::vector<size_t> nodes;                     // every node the step stands for, ascending (filled by find_embeds)
+  };
+  std::map<size_t, EmbedGroup> embed_at;  // anchor node (the last of the group) -> the group
+  int64_t embed_elems = 0;                // table elements of the model so far
+  std::map<size_t, int> embed_node_id;    // Gather node -> its 1-based id in plan.prep_strict_nodes
+
+  // ---- feature interactions (host/interact.hpp; INTEGRATION.md 2.6 "Feature interactions") ---------------------------------------------
+  // dot: MatMul(T, Transpose(T, perm = [0,2,1])) of ONE value T [N, k, d], read whole or through Flatten / Reshape -> Gather(axis = 1) by a
+  // constant list; the axis-1 Concat that alone reads the selection beside inputs of the Concat that built T joins the step (pass-through).
+  // fm: Sub(square(ReduceSum(T, [1])), ReduceSum(square(T), [1])), the constant scalar Mul and the last-axis ReduceSum behind it.
+  // Found before the walk by structure (find_interactions); shapes are known, and the caps checked, where the step is emitted
+  // (lower_interact).  A graph without either pattern is lowered exactly as before.
+  struct InteractView {
+    size_t node = 0;
+    std::vector<int64_t> target;  // Reshape: its constant target; Flatten: {axis}; Identity: empty
+    bool back = false;            // the advanced-index form: behind its Transpose(1,0), where the value is [N, P] (else [P, N])
+  };
+  struct InteractMatch {
+    int mode = kInteractDot;
+    std::string T;
+    std::vector<size_t> nodes;  // every node the step stands for but the anchor
+    size_t product = 0;         // dot: the MatMul; fm: the Sub
+    // dot
+    std::vector<InteractView> views;  // between the product and the Gather
+    size_t gather = SIZE_MAX;         // SIZE_MAX: the whole matrix
+    std::vector<int64_t> idx;
+    // TorchScript's advanced-index form: Gather(axis = 0) of the transposed, flattened matrix by `index_value` (evaluated once k is known)
+    bool advanced = false;
+    std::string index_value, selection_value;  // selection_value: the name of the selection [N, P] a pass-through Concat reads
+    std::vector<InteractView> views_after;     // behind its Gather: in front of the Transpose(1,0) and behind it (InteractView::back)
+    size_t out_concat = SIZE_MAX, t_concat = SIZE_MAX;  // pass-through: the Concat that reads the selection, the Concat that built T
+    // fm
+    bool keep = false;  // keepdims of the two field sums
+    double h = 1.0;
+    bool has_h = false, h_after = false;
+    size_t last_sum = SIZE_MAX;  // the trailing ReduceSum
+  };
+  std::map<size_t, InteractMatch> interact_at;  // anchor (the last node of the pattern) -> the pattern
 
   Lowerer(const onnx::Model &model, const std::string &output_select_in) : m(model) {
     // Which graph output is served.  Default: the first (engine.rs:146-149).  A selector names another one, by output
@@ -264,8 +430,6 @@ struct Lowerer {
       }
     }
   }
-  size_t out_index = 0;
-  std::unique_ptr<const GraphIndex> graph;  // the graph as the served output sees it (run)
 
   int new_buf(const std::vector<int64_t> &shape) {
     // [N,C,L] tensors (1-D convolutional nets) are laid out and scheduled as [N,C,1,L]; values keep their 3-D shape
@@ -1891,14 +2055,6 @@ struct Lowerer {
     spatial_norm_step(n, a, G, std::move(scale), std::move(shift), n.attr_f("epsilon", 1e-5f), node_label(n), n.outputs[0]);
   }
 
-  // The exporter's spelling of nn.GroupNorm below opset 18: Reshape(x, [0, G, -1]) -> InstanceNormalization(scale[G], B[G]) -> Reshape(back to
-  // x's shape, a constant or the folded Shape(x)) [-> Mul(gamma [C,1,1])] [-> Add(beta)].  The chain is found structurally before the walk
-  // (find_group_norms: operators and sole readers), anchored at the first Reshape; shapes and constants are checked when the walk reaches
-  // the anchor (false: every node lowers by its own rule), and the nodes behind it emit nothing.
-  struct GnMatch {
-    size_t inorm = 0, back = 0;
-  };
-  std::map<size_t, GnMatch> gn_at;  // index of the first Reshape -> the chain behind it
   void find_group_norms() {
     for (size_t i = 0; i < m.nodes.size(); i++) {
       const NodeDef &r = m.nodes[i];
@@ -2159,7 +2315,6 @@ struct Lowerer {
     vals[r.inputs[i]] = std::move(c);
     return r;
   }
-  int view_consts = 0;
   // the constant `c` with the dims `dims` (the same elements: type and half tag kept)
   static Val redimensioned(const Val &c, std::vector<int64_t> dims, std::vector<float> f32) {
     auto t = std::make_shared<TensorData>();
@@ -2440,7 +2595,6 @@ struct Lowerer {
     else set_act(n, tok.buf, {N, T, E}, true);
     return true;
   }
-  std::map<std::string, int64_t> expanded_lead;  // results of Expand over constants -> the leading entry of the target shape as the graph had it
 
   // ---- the decomposed LayerNorm older exporters write, on [rows, E] (where nothing else serves it):
   //   ReduceMean(-1) -> Sub -> Pow(2) | Mul(d, d) -> ReduceMean(-1) -> Add(eps) -> Sqrt -> Div [-> Mul(gamma)] [-> Add(beta)]
@@ -2558,51 +2712,6 @@ struct Lowerer {
     if (rank == 3) emit_window(std::move(s), n, a.shape);
     else emit(std::move(s), n, a.shape);
   }
-
-  // ---- self-attention (INTEGRATION.md section 2.6) ----------------------------------------------------------------------------
-  // The batch-first graph exporters write is matched structurally before the walk (find_attention: by operator, perm and which operands
-  // are constants), anchored at the merge Reshape; the nodes inside emit nothing, and the anchor validates shapes and constants and emits
-  // ONE Attention step (lower_attention).  A MatMul of two activations that starts no such pattern is rejected with the reason kept here.
-  struct AttnScale {
-    char op;  // '*' or '/'
-    std::string cst;
-  };
-  struct AttnSide {
-    std::string src, shape;   // the [N, T, E] value the head split reads (behind an absorbed Split / Slice: its input) and the Reshape's target
-    const NodeDef *cut = nullptr;  // that Split / Slice on the last axis
-    size_t cut_out = 0;
-  };
-  // A row's own key mask (INTEGRATION.md 2.6 "Padded sequences"): T consecutive columns of the input buffer and a compare value, traced
-  // back from where it meets the scores (or the masked mean) through Cast / Unsqueeze / Reshape / Expand / Equal / Not to a graph input
-  struct RowMask {
-    int64_t src0 = 0, k = 0;     // columns [src0, src0 + k) of the input buffer
-    bool is_int = false;         // the graph sees them as integers: truncated toward zero before the comparison
-    float cmp = 0.f;             // kept iff value != cmp
-    int state = 0;               // the traced value: 0 the source's own values (kept iff != 0), 1 a bool true = masked, 2 a bool true = kept
-    std::vector<int64_t> shape;  // of the traced value in front of any Expand; shape[0] = -1, the rows
-    std::vector<size_t> nodes, aux;  // the nodes between the graph input and the value; aux: the Shape sub-graph that sizes an Expand
-    float fill = 0.f;            // Attention: the negative constant of masked keys, and how it reaches the score (RowMaskMode)
-    int mode = kRowMaskAdd;
-    const NodeDef *at = nullptr;  // the Add / Where on the scores
-  };
-  struct AttnMatch {
-    AttnSide side[3];  // Q, K, V
-    std::vector<AttnScale> scales;
-    std::string mask;
-    std::shared_ptr<RowMask> rm;
-    const NodeDef *qk = nullptr;
-    std::vector<size_t> nodes;
-  };
-  std::map<size_t, AttnMatch> attn_at;            // anchor node index -> the pattern it closes
-  std::vector<char> absorbed;                // nodes inside a recognised pattern (attention, or the decomposed LayerNorm): they emit nothing
-  std::map<const NodeDef *, std::string> attn_fail;  // MatMul(activation, activation) nodes outside one: why
-  struct MaskedMean {
-    std::string x;  // the window [N, T, E]
-    RowMask rm;
-    float clip = 0.f;
-    size_t mul = 0;
-  };
-  std::map<size_t, MaskedMean> mmean_at;  // the Div that closes a masked mean over time -> the pattern
 
   // a constant known before the walk (an initializer or a Constant node): its first element and its element count
   bool graph_const_scalar(const std::string &name, double *v, size_t *count = nullptr) const {
@@ -3339,7 +3448,6 @@ struct Lowerer {
     emit(std::move(s), n, shape);
   }
 
-
   // ------------------------------------------------------------------------------------------
   // Quantised graphs.  A QuantizeLinear of an activation emits nothing: its output is a quantised value over the
   // same buffer (Val::q).  DequantizeLinear of a constant folds to f32 and remembers its integers; of a quantised activation it becomes
@@ -3347,12 +3455,6 @@ struct Lowerer {
   // quantised QDense) and dequantised int8 weights, and QLinearMatMul, become QDense.
   [[noreturn]] void bad_form(const NodeDef &n, const std::string &why) { unsupported(n, "unsupported operator form: " + why); }
 
-  // the constant scale / zero point inputs (`si`, `zi`) of a quantisation node: one scale per tensor, or one per index of an axis
-  struct QArgs {
-    std::vector<float> scale;
-    std::vector<int64_t> zp;
-    int elem = onnx::kUint8;  // the quantised element type (the zero point's; uint8 without one)
-  };
   QArgs quant_args(const NodeDef &n, size_t si, size_t zi, const char *what) {
     QArgs qa;
     if (n.attr_i("block_size", 0) != 0) bad_form(n, "block_size (blocked quantisation) is not supported");
@@ -3387,7 +3489,6 @@ struct Lowerer {
     return q;
   }
 
-  std::map<std::string, const NodeDef *> quant_node;  // quantised value -> the node that made it
   void set_quant(const NodeDef &n, int buf, const std::vector<int64_t> &shape, int ra, const Quant &q, bool done, bool folded) {
     set_act(n, buf, shape, folded, ra);
     Val &v = vals[n.outputs[0]];
@@ -4027,17 +4128,6 @@ struct Lowerer {
     if (expand && dims.size() == 3 && lead >= 0) expanded_lead[n.outputs[0]] = lead;
     vals[n.outputs[0]] = const_f32(std::move(o), dims);
   }
-  // ---- per-row sequence lengths (INTEGRATION.md 2.6 "Padded windows") ----------------------------------------------------------------
-  // Input 4 of LSTM / GRU / RNN, sequence_lens, traced back to ONE column of a graph input before the walk: an [N] integer input, an
-  // [N, 1] one through Squeeze / Reshape([-1]) / Flatten, a column of a wider input picked by Slice / Gather(axis = 1), with or without
-  // Cast (PyTorch: Cast(lengths, INT32)).  The tracing nodes emit nothing and the value may feed every layer of a stack; the steps read the
-  // column from the input buffer (Step::in3, rm_off, rm_int).  A constant sequence_lens is left to pack_recurrent, which refuses it.
-  struct SeqLens {
-    int64_t col = 0;
-    bool is_int = false;
-    int node = 0;  // 1-based id in plan.prep_strict_nodes
-  };
-  std::map<size_t, SeqLens> seq_lens_at;  // recurrent node -> its lengths
 
   void find_seq_lens() {
     std::set<size_t> chain;
@@ -4367,15 +4457,6 @@ struct Lowerer {
       unsupported(n, "unsupported operator");
     }
   }
-
-  // ---- ai.onnx.ml preprocessing regions (host/prep.hpp).  A region is a connected set of Imputer / Scaler / Binarizer / OneHotEncoder /
-  // LabelEncoder / FeatureVectorizer / ArrayFeatureExtractor (constant indices) / Cast / Reshape / Flatten / Squeeze / Concat / Identity
-  // nodes and graph inputs that holds at least one thing nothing else serves: one of the five encoder nodes, a non-contiguous
-  // ArrayFeatureExtractor or an integer graph input.  Graphs without one lower exactly as before.  Inside a region every value is a
-  // list of column programs over one source buffer (PrepVal); where anything else reads a region value it becomes ONE Prep step.
-  std::vector<char> region;                           // node index -> lowered as part of a region
-  std::vector<std::shared_ptr<PrepTable>> prep_tables;  // LabelEncoder tables and strict one-hot category sets, by id
-  int64_t prep_cats = 0, prep_keys = 0;                 // one-hot categories / LabelEncoder keys in all (caps)
 
   static bool prep_encoder(const std::string &op) {
     return op == "Imputer" || op == "Binarizer" || op == "OneHotEncoder" || op == "LabelEncoder" || op == "FeatureVectorizer";
@@ -4743,21 +4824,6 @@ struct Lowerer {
     set_prep(n.outputs[0], std::move(p), out_shape);
   }
 
-  // ---- distance models (INTEGRATION.md section 2.6): |x - c|^2 of each row against a constant set C [M, F] ----------------------------
-  // Recognised before the walk (find_nearest) in the spellings exporters write,
-  //   rs = ReduceSumSquare(X, axes = [1], keepdims = 1);  g = Gemm(X, C, alpha = -2 [, transB]) | Mul(MatMul(X, C^T), -2);
-  //   D2 = Add(Add(rs, g), C2) | Add(rs, Add(g, C2))     (either operand order; C2[m] = |C[m]|^2 within rounding)
-  // when no intermediate has another reader; the contrib operator CDist(X, C) is the same value in one node.  The nodes emit nothing: the
-  // last one binds D2 to a pending value (Val::nn), and what reads it decides what the Nearest step serves -- ArgMin the label, TopK the
-  // best k, Sqrt the rooted distances, anything else (the graph output included) the [rows, M] matrix.
-  struct NearestMatch {
-    std::string x, d2, spelling;
-    std::shared_ptr<TensorData> c;
-    bool c_fm = false;  // C is stored [F, M]
-    std::vector<size_t> nodes;  // ascending; the last is the anchor
-  };
-  std::map<size_t, NearestMatch> nearest_at;  // anchor node index -> the pattern it closes
-
   // a constant f32 tensor known before the walk: an initializer or a Constant node's value
   std::shared_ptr<TensorData> const_tensor(const std::string &name) const {
     const std::shared_ptr<TensorData> t = graph->constant(name).t;
@@ -5028,35 +5094,6 @@ struct Lowerer {
     }
     return true;
   }
-
-  // ---- embedding lookups (host/embed.hpp; INTEGRATION.md 2.6 "Embedding lookups") ------------------------------------------------------
-  // Gather(axis = 0) of a constant f32 table [V, d] / [V] by indices that are columns of a graph input: the column picks (Gather(axis = 1) /
-  // Slice / Squeeze), Casts and constant offset Adds in front of it, the Reshape / Flatten of [N, k, d] to [N, k * d] and the feature-axis
-  // Concat that alone reads the lookups (with numeric columns of a graph input beside them) become ONE Embed step that reads the input
-  // buffer.  Found before the walk (find_embeds): a graph without such a Gather is lowered exactly as before.
-  struct EmbedCols {  // a value that is columns [src0, src0 + k) of the input buffer: [N, k] (rank2) or [N]
-    int64_t src0 = 0, k = 0;
-    bool rank2 = true, truncated = false, int_input = false;
-    std::vector<int64_t> off;   // the constant added to each column (empty: none)
-    std::vector<size_t> chain;  // the nodes between the graph input and the value
-  };
-  struct EmbedLookup {
-    size_t gather = 0;
-    std::shared_ptr<TensorData> table;
-    EmbedCols ix;
-    int64_t V = 0, d = 0;
-    std::vector<size_t> tail;  // the Reshape / Flatten behind it
-    std::string out;
-    std::vector<int64_t> shape;
-  };
-  struct EmbedGroup {
-    std::vector<EmbedLookup> lookups;
-    std::vector<std::pair<int, EmbedCols>> parts;  // in output order: (lookup, -) or (-1, columns to copy)
-    std::vector<size_t> nodes;                     // every node the step stands for, ascending (filled by find_embeds)
-  };
-  std::map<size_t, EmbedGroup> embed_at;  // anchor node (the last of the group) -> the group
-  int64_t embed_elems = 0;                // table elements of the model so far
-  std::map<size_t, int> embed_node_id;    // Gather node -> its 1-based id in plan.prep_strict_nodes
 
   // an integer constant known before the walk: an initializer or a Constant node
   bool graph_const_ints(const std::string &name, std::vector<int64_t> *v, std::vector<int64_t> *dims) const {
@@ -5416,39 +5453,6 @@ struct Lowerer {
     }
     set_act(anchor, out_buf, shape);
   }
-
-  // ---- feature interactions (host/interact.hpp; INTEGRATION.md 2.6 "Feature interactions") ---------------------------------------------
-  // dot: MatMul(T, Transpose(T, perm = [0,2,1])) of ONE value T [N, k, d], read whole or through Flatten / Reshape -> Gather(axis = 1) by a
-  // constant list; the axis-1 Concat that alone reads the selection beside inputs of the Concat that built T joins the step (pass-through).
-  // fm: Sub(square(ReduceSum(T, [1])), ReduceSum(square(T), [1])), the constant scalar Mul and the last-axis ReduceSum behind it.
-  // Found before the walk by structure (find_interactions); shapes are known, and the caps checked, where the step is emitted
-  // (lower_interact).  A graph without either pattern is lowered exactly as before.
-  struct InteractView {
-    size_t node = 0;
-    std::vector<int64_t> target;  // Reshape: its constant target; Flatten: {axis}; Identity: empty
-    bool back = false;            // the advanced-index form: behind its Transpose(1,0), where the value is [N, P] (else [P, N])
-  };
-  struct InteractMatch {
-    int mode = kInteractDot;
-    std::string T;
-    std::vector<size_t> nodes;  // every node the step stands for but the anchor
-    size_t product = 0;         // dot: the MatMul; fm: the Sub
-    // dot
-    std::vector<InteractView> views;  // between the product and the Gather
-    size_t gather = SIZE_MAX;         // SIZE_MAX: the whole matrix
-    std::vector<int64_t> idx;
-    // TorchScript's advanced-index form: Gather(axis = 0) of the transposed, flattened matrix by `index_value` (evaluated once k is known)
-    bool advanced = false;
-    std::string index_value, selection_value;  // selection_value: the name of the selection [N, P] a pass-through Concat reads
-    std::vector<InteractView> views_after;     // behind its Gather: in front of the Transpose(1,0) and behind it (InteractView::back)
-    size_t out_concat = SIZE_MAX, t_concat = SIZE_MAX;  // pass-through: the Concat that reads the selection, the Concat that built T
-    // fm
-    bool keep = false;  // keepdims of the two field sums
-    double h = 1.0;
-    bool has_h = false, h_after = false;
-    size_t last_sum = SIZE_MAX;  // the trailing ReduceSum
-  };
-  std::map<size_t, InteractMatch> interact_at;  // anchor (the last node of the pattern) -> the pattern
 
   // lax: a Reshape whose target is computed (from Shape nodes) counts too; lower_interact evaluates it
   bool interact_is_view(const NodeDef &r, const std::string &cur, InteractView *v, bool lax = false) const {
