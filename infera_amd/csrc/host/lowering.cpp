@@ -12,404 +12,30 @@
 //   ReduceMean over the spatial axes -> GlobalAvgPool;  Concat(axis=1) -> one CopyCols step per input
 // Dense chains are kept as consecutive Dense steps; the device executor decides whether a chain
 // runs as one whole-chain fused kernel or layer by layer.
+//
+// struct Lowerer is declared in lowerer.hpp, which lists every member function under the file that defines it.  This file defines the
+// core (constructor, buffer and value helpers, lower_node, run) and the dense, shape, conv, norm, attention, quantised and interaction
+// families, indented one level as members of Lowerer; the recurrent, ai.onnx.ml, preprocessing, distance and embedding families are in
+// lower_<family>.cpp.
 #include <algorithm>
 #include <cmath>
-#include <functional>
-#include <map>
-#include <set>
 #include <numeric>
-#include <sstream>
-
-#include <iomanip>
 
 #include "attention.hpp"
 #include "channelnorm.hpp"
-#include "common.hpp"
 #include "deconv.hpp"
-#include "embed.hpp"
 #include "interact.hpp"
+#include "lowerer.hpp"
+#include "nearest.hpp"
+#include "recurrent.hpp"
 #include "spatialnorm.hpp"
 #include "tokens.hpp"
-#include "nearest.hpp"
-#include "plan.hpp"
-#include "prep.hpp"
-#include "recurrent.hpp"
-#include "svm.hpp"
-#include "trees.hpp"
 
 namespace infera_hip {
 
-namespace {
+namespace lowering {
 
-using onnx::NodeDef;
-using onnx::TensorData;
-
-// A value inside a preprocessing region (host/prep.hpp): not computed yet -- one column program per column over the rows of buffer
-// `src`.  It becomes a buffer (one Prep step, a SliceCols, or the source itself) where something outside the region reads it.
-struct PrepVal {
-  int src = -1;
-  std::vector<PrepCol> cols;
-  std::vector<std::string> origin;  // the ONNX nodes absorbed so far
-  void add_origin(const std::string &o) {
-    if (std::find(origin.begin(), origin.end(), o) == origin.end()) origin.push_back(o);
-  }
-  // q's columns after these (q reads the same source)
-  void append(const PrepVal &q) {
-    cols.insert(cols.end(), q.cols.begin(), q.cols.end());
-    for (const auto &o : q.origin) add_origin(o);
-  }
-};
-
-struct NearestPending {
-  std::shared_ptr<const NearestPack> pack;
-  int in_buf = -1;
-  int64_t rows = -1;  // the row extent of the input's shape
-  bool rooted = false;
-  std::string origin;
-  std::map<int64_t, int> part_of_k;  // k -> the buffer of the best-k lists already emitted
-};
-
-struct Val {
-  bool is_const = false;
-  std::shared_ptr<const PrepVal> pv;  // set: a preprocessing-region value (buf = -1)
-  std::shared_ptr<TensorData> c;
-  int buf = -1;
-  std::vector<int64_t> shape;  // activations: dim[ra] = -1 (symbolic rows) or fixed batch
-  // row-axis tag: where the row axis stands in `shape`.  The buffer is always [rows, the other axes in the order of `shape`]; 0 for
-  // everything but the time-major values around a recurrent layer ([T, rows, F], Y [T, D, rows, H], Y_h [D, rows, H])
-  int ra = 0;
-  // zero padding (top, left, bottom, right) a Pad node asked for and the consuming Conv still has to apply; `shape`
-  // is the UNPADDED tensor that `buf` holds
-  int64_t pend[4] = {0, 0, 0, 0};
-  // set: the value is a QUANTISED activation (uint8 / int8 in the graph).  q_done: `buf` holds the dequantised values (q - zp) * s (a
-  // QLinearMatMul's result); else `buf` is the f32 tensor a QuantizeLinear read and the rounding is still to be done by whoever reads this
-  std::shared_ptr<const Quant> q;
-  bool q_done = false;
-  // an ACTIVATION the graph types float16: `buf` holds f32 values that are halves once the plan's RoundHalf steps
-  // have run (insert_half_roundings).  A constant is half when its tensor says so (TensorData::elem)
-  bool half = false;
-  // set: the distances of the rows to a constant set (buf = -1), not computed yet -- whoever reads the value decides what the Nearest step
-  // serves (a label, the best k, the matrix); `rooted`: this value is sqrt(d2)
-  std::shared_ptr<struct NearestPending> nn;
-  // set: a CHANNELS-LAST VIEW: `shape` is [N,H,W,C] and `buf` is the [N,C,H,W] tensor a step wrote, untouched -- what a
-  // Transpose(0,2,3,1) of that tensor yields.  Only the operators lower_on_view lists read it
-  bool cl = false;
-  bool padded() const { return pend[0] || pend[1] || pend[2] || pend[3]; }
-};
-
-int64_t prod(const std::vector<int64_t> &v, size_t from = 0, size_t to = SIZE_MAX) {
-  // Shapes come from a model file: a product that leaves int64 is an error, not a wrapped number.
-  int64_t p = 1;
-  for (size_t i = from; i < std::min(to, v.size()); i++)
-    if (__builtin_mul_overflow(p, v[i], &p)) throw InferaError::onnx("tensor shape too large");
-  return p;
-}
-
-// Largest activation row the planner accepts (elements): 2^31 floats = 8 GiB per table row is beyond anything the
-// staging or scratch sizing could serve, and keeping per-row counts in 31 bits keeps rows*per_row inside int64.
-constexpr int64_t kMaxPerRow = int64_t(1) << 31;
-
-std::string shape_str(const std::vector<int64_t> &s) {
-  std::string o = "[";
-  for (size_t i = 0; i < s.size(); i++) o += (i ? "," : "") + std::to_string(s[i]);
-  return o + "]";
-}
-
-[[noreturn]] void unsupported(const NodeDef &n, const std::string &why) {
-  throw InferaError::onnx("node '" + (n.name.empty() ? n.op : n.name) + "' (" + n.op + "): " + why);
-}
-
-// "Op:name" (or "Op"): how a step's origin names a node
-std::string node_label(const NodeDef &n) { return n.op + (n.name.empty() ? "" : ":" + n.name); }
-
-Val const_val(std::shared_ptr<TensorData> t) {
-  Val v;
-  v.is_const = true;
-  v.c = std::move(t);
-  v.shape = v.c->dims;
-  return v;
-}
-Val const_f32(std::vector<float> f, std::vector<int64_t> dims) {
-  auto t = std::make_shared<TensorData>();
-  t->dtype = onnx::kFloat;
-  t->dims = std::move(dims);
-  t->f32 = std::move(f);
-  return const_val(std::move(t));
-}
-Val const_i64(std::vector<int64_t> i, std::vector<int64_t> dims) {
-  auto t = std::make_shared<TensorData>();
-  t->dtype = onnx::kInt64;
-  t->dims = std::move(dims);
-  t->i64 = std::move(i);
-  return const_val(std::move(t));
-}
-
-// What the matchers that run before the walk (Lowerer::find_*) read of the graph: built once, for the served output, and never changed.
-// Only live nodes are indexed.  (A live node's inputs have live producers and ONNX names are assigned once, so a lookup that starts at a
-// live node finds what a map over all nodes would.)
-struct GraphIndex {
-  const onnx::Model &m;
-  std::vector<char> live;  // node index -> it feeds the served output
-  std::map<std::string, size_t> producer_of;
-  std::map<std::string, std::vector<size_t>> consumers_of;  // live consumers of every value, one entry per input that reads it
-  std::set<std::string> row_data;    // values that hold row data: computed from a graph input (Shape's result is not); everything else folds to a constant
-  std::set<std::string> graph_outs;  // the names of all graph outputs, served or not
-
-  GraphIndex(const onnx::Model &model, const std::string &served) : m(model), live(model.nodes.size(), 0) {
-    const size_t N = m.nodes.size();
-    {
-      // Only one output is served (engine.rs:146-149): nodes that do not feed it are dead -- a second
-      // output (e.g. the probabilities next to a label) must neither cost kernels nor block loading.
-      std::map<std::string, size_t> any_producer;
-      for (size_t i = 0; i < N; i++)
-        for (const auto &o : m.nodes[i].outputs) any_producer[o] = i;
-      std::vector<std::string> work{served};
-      while (!work.empty()) {
-        const std::string v = work.back();
-        work.pop_back();
-        auto it = any_producer.find(v);
-        if (it == any_producer.end() || live[it->second]) continue;
-        live[it->second] = 1;
-        for (const auto &i : m.nodes[it->second].inputs) work.push_back(i);
-      }
-    }
-    for (size_t i = 0; i < N; i++) {
-      if (!live[i]) continue;
-      for (const auto &o : m.nodes[i].outputs) producer_of[o] = i;
-      for (const auto &in : m.nodes[i].inputs) consumers_of[in].push_back(i);
-    }
-    for (const auto &o : m.outputs) graph_outs.insert(o.name);
-    for (const auto &v : m.inputs) row_data.insert(v.name);
-    for (size_t i = 0; i < N; i++) {
-      if (!live[i] || m.nodes[i].op == "Shape") continue;
-      bool any = false;
-      for (const auto &in : m.nodes[i].inputs) any = any || row_data.count(in);
-      if (any)
-        for (const auto &o : m.nodes[i].outputs) row_data.insert(o);
-    }
-  }
-
-  // the node that computes `v` (null: a graph input, an initializer, or nothing)
-  const NodeDef *producer(const std::string &v, size_t *idx = nullptr) const {
-    auto pi = producer_of.find(v);
-    if (pi == producer_of.end()) return nullptr;
-    if (idx) *idx = pi->second;
-    return &m.nodes[pi->second];
-  }
-  // the node that alone reads `v` (null: several readers, none, or a graph output); allow_repeat: it may read `v` twice, as in Mul(d, d)
-  const NodeDef *sole_reader(const std::string &v, bool allow_repeat) const {
-    auto it = consumers_of.find(v);
-    if (it == consumers_of.end() || it->second.empty() || graph_outs.count(v)) return nullptr;
-    if (!allow_repeat && it->second.size() != 1) return nullptr;
-    for (size_t c : it->second)
-      if (c != it->second[0]) return nullptr;
-    return &m.nodes[it->second[0]];
-  }
-  static bool std_dom(const NodeDef &n) { return n.domain.empty() || n.domain == "ai.onnx"; }
-  // A constant known before the walk: an initializer, or the result of a Constant node -- the tensor of its `value`, or the node
-  // itself where the value stands in another attribute (value_int, value_float, value_ints).  Neither: `v` is no such constant.
-  struct Const {
-    std::shared_ptr<TensorData> t;
-    const NodeDef *node = nullptr;
-    explicit operator bool() const { return t || node; }
-  };
-  Const constant(const std::string &v) const {
-    Const c;
-    if (auto ci = m.initializers.find(v); ci != m.initializers.end()) {
-      c.t = ci->second;
-    } else if (const NodeDef *p = producer(v); p && p->op == "Constant") {
-      if (auto *a = p->attr("value"); a && a->t) c.t = a->t;
-      else c.node = p;
-    }
-    return c;
-  }
-};
-
-struct Lowerer {
-  const onnx::Model &m;
-  Plan plan;
-  std::map<std::string, Val> vals;
-  std::map<std::string, int> uses;
-  std::map<int, int> producer;  // buffer id -> index of the step that wrote it
-  std::map<int, std::vector<std::string>> buf_names;  // value names that denote each buffer
-  std::map<int, int> alias_edges;  // nodes folded away whose input AND output denote the buffer
-  std::set<int> half_bufs;  // buffers written by float16-typed nodes: their steps' results are rounded to half (insert_half_roundings)
-  bool cur_half = false;    // the node being lowered is float16-typed
-  // INFERA_HDENSE=0 (read when a model is loaded): float16 MatMul / Gemm layers stay on the float path (Dense + RoundHalf) -- the
-  // switch the bit-identity tests compare the HDense kernel against
-  const bool hdense_enabled = ScheduleKnobs::read().hdense;
-  // INFERA_NEAREST=0 (read when a model is loaded): distance sub-graphs lower operator by operator (RowReduce, Dense, BinaryAct ...), the
-  // plan the bit-identity tests compare the Nearest kernel against
-  const bool nearest_enabled = ScheduleKnobs::read().nearest;
-  std::set<int> int_bufs;  // buffers whose f32 values are whole numbers by construction (ArgMax, integer Cast, label arithmetic)
-  size_t out_index = 0;
-  std::unique_ptr<const GraphIndex> graph;  // the graph as the served output sees it (run)
-
-  // ---- Instance / Group norm, the channels-last view, Tokens, LayerNorm ----
-  // The exporter's spelling of nn.GroupNorm below opset 18: Reshape(x, [0, G, -1]) -> InstanceNormalization(scale[G], B[G]) -> Reshape(back to
-  // x's shape, a constant or the folded Shape(x)) [-> Mul(gamma [C,1,1])] [-> Add(beta)].  The chain is found structurally before the walk
-  // (find_group_norms: operators and sole readers), anchored at the first Reshape; shapes and constants are checked when the walk reaches
-  // the anchor (false: every node lowers by its own rule), and the nodes behind it emit nothing.
-  struct GnMatch {
-    size_t inorm = 0, back = 0;
-  };
-  std::map<size_t, GnMatch> gn_at;  // index of the first Reshape -> the chain behind it
-  int view_consts = 0;
-  std::map<std::string, int64_t> expanded_lead;  // results of Expand over constants -> the leading entry of the target shape as the graph had it
-
-  // ---- self-attention ----------------------------------------------------------------------------
-  // The batch-first graph exporters write is matched structurally before the walk (find_attention: by operator, perm and which operands
-  // are constants), anchored at the merge Reshape; the nodes inside emit nothing, and the anchor validates shapes and constants and emits
-  // ONE Attention step (lower_attention).  A MatMul of two activations that starts no such pattern is rejected with the reason kept here.
-  struct AttnScale {
-    char op;  // '*' or '/'
-    std::string cst;
-  };
-  struct AttnSide {
-    std::string src, shape;   // the [N, T, E] value the head split reads (behind an absorbed Split / Slice: its input) and the Reshape's target
-    const NodeDef *cut = nullptr;  // that Split / Slice on the last axis
-    size_t cut_out = 0;
-  };
-  // A row's own key mask (INTEGRATION.md 2.6 "Padded sequences"): T consecutive columns of the input buffer and a compare value, traced
-  // back from where it meets the scores (or the masked mean) through Cast / Unsqueeze / Reshape / Expand / Equal / Not to a graph input
-  struct RowMask {
-    int64_t src0 = 0, k = 0;     // columns [src0, src0 + k) of the input buffer
-    bool is_int = false;         // the graph sees them as integers: truncated toward zero before the comparison
-    float cmp = 0.f;             // kept iff value != cmp
-    int state = 0;               // the traced value: 0 the source's own values (kept iff != 0), 1 a bool true = masked, 2 a bool true = kept
-    std::vector<int64_t> shape;  // of the traced value in front of any Expand; shape[0] = -1, the rows
-    std::vector<size_t> nodes, aux;  // the nodes between the graph input and the value; aux: the Shape sub-graph that sizes an Expand
-    float fill = 0.f;            // Attention: the negative constant of masked keys, and how it reaches the score (RowMaskMode)
-    int mode = kRowMaskAdd;
-    const NodeDef *at = nullptr;  // the Add / Where on the scores
-  };
-  struct AttnMatch {
-    AttnSide side[3];  // Q, K, V
-    std::vector<AttnScale> scales;
-    std::string mask;
-    std::shared_ptr<RowMask> rm;
-    const NodeDef *qk = nullptr;
-    std::vector<size_t> nodes;
-  };
-  std::map<size_t, AttnMatch> attn_at;            // anchor node index -> the pattern it closes
-  std::vector<char> absorbed;                // nodes inside a recognised pattern (attention, or the decomposed LayerNorm): they emit nothing
-  std::map<const NodeDef *, std::string> attn_fail;  // MatMul(activation, activation) nodes outside one: why
-  struct MaskedMean {
-    std::string x;  // the window [N, T, E]
-    RowMask rm;
-    float clip = 0.f;
-    size_t mul = 0;
-  };
-  std::map<size_t, MaskedMean> mmean_at;  // the Div that closes a masked mean over time -> the pattern
-
-  // ---- quantised and float16 graphs ----
-  // the constant scale / zero point inputs (`si`, `zi`) of a quantisation node: one scale per tensor, or one per index of an axis
-  struct QArgs {
-    std::vector<float> scale;
-    std::vector<int64_t> zp;
-    int elem = onnx::kUint8;  // the quantised element type (the zero point's; uint8 without one)
-  };
-  std::map<std::string, const NodeDef *> quant_node;  // quantised value -> the node that made it
-
-  // ---- per-row sequence lengths (INTEGRATION.md 2.6 "Padded windows") ----------------------------------------------------------------
-  // Input 4 of LSTM / GRU / RNN, sequence_lens, traced back to ONE column of a graph input before the walk: an [N] integer input, an
-  // [N, 1] one through Squeeze / Reshape([-1]) / Flatten, a column of a wider input picked by Slice / Gather(axis = 1), with or without
-  // Cast (PyTorch: Cast(lengths, INT32)).  The tracing nodes emit nothing and the value may feed every layer of a stack; the steps read the
-  // column from the input buffer (Step::in3, rm_off, rm_int).  A constant sequence_lens is left to pack_recurrent, which refuses it.
-  struct SeqLens {
-    int64_t col = 0;
-    bool is_int = false;
-    int node = 0;  // 1-based id in plan.prep_strict_nodes
-  };
-  std::map<size_t, SeqLens> seq_lens_at;  // recurrent node -> its lengths
-
-  // ---- ai.onnx.ml preprocessing regions (host/prep.hpp).  A region is a connected set of Imputer / Scaler / Binarizer / OneHotEncoder /
-  // LabelEncoder / FeatureVectorizer / ArrayFeatureExtractor (constant indices) / Cast / Reshape / Flatten / Squeeze / Concat / Identity
-  // nodes and graph inputs that holds at least one thing nothing else serves: one of the five encoder nodes, a non-contiguous
-  // ArrayFeatureExtractor or an integer graph input.  Graphs without one lower exactly as before.  Inside a region every value is a
-  // list of column programs over one source buffer (PrepVal); where anything else reads a region value it becomes ONE Prep step.
-  std::vector<char> region;                           // node index -> lowered as part of a region
-  std::vector<std::shared_ptr<PrepTable>> prep_tables;  // LabelEncoder tables and strict one-hot category sets, by id
-  int64_t prep_cats = 0, prep_keys = 0;                 // one-hot categories / LabelEncoder keys in all (caps)
-
-  // ---- distance models: |x - c|^2 of each row against a constant set C [M, F] ----------------------------
-  // Recognised before the walk (find_nearest) in the spellings exporters write,
-  //   rs = ReduceSumSquare(X, axes = [1], keepdims = 1);  g = Gemm(X, C, alpha = -2 [, transB]) | Mul(MatMul(X, C^T), -2);
-  //   D2 = Add(Add(rs, g), C2) | Add(rs, Add(g, C2))     (either operand order; C2[m] = |C[m]|^2 within rounding)
-  // when no intermediate has another reader; the contrib operator CDist(X, C) is the same value in one node.  The nodes emit nothing: the
-  // last one binds D2 to a pending value (Val::nn), and what reads it decides what the Nearest step serves -- ArgMin the label, TopK the
-  // best k, Sqrt the rooted distances, anything else (the graph output included) the [rows, M] matrix.
-  struct NearestMatch {
-    std::string x, d2, spelling;
-    std::shared_ptr<TensorData> c;
-    bool c_fm = false;  // C is stored [F, M]
-    std::vector<size_t> nodes;  // ascending; the last is the anchor
-  };
-  std::map<size_t, NearestMatch> nearest_at;  // anchor node index -> the pattern it closes
-
-  // ---- embedding lookups (host/embed.hpp; INTEGRATION.md 2.6 "Embedding lookups") ------------------------------------------------------
-  // Gather(axis = 0) of a constant f32 table [V, d] / [V] by indices that are columns of a graph input: the column picks (Gather(axis = 1) /
-  // Slice / Squeeze), Casts and constant offset Adds in front of it, the Reshape / Flatten of [N, k, d] to [N, k * d] and the feature-axis
-  // Concat that alone reads the lookups (with numeric columns of a graph input beside them) become ONE Embed step that reads the input
-  // buffer.  Found before the walk (find_embeds): a graph without such a Gather is lowered exactly as before.
-  struct EmbedCols {  // a value that is columns [src0, src0 + k) of the input buffer: [N, k] (rank2) or [N]
-    int64_t src0 = 0, k = 0;
-    bool rank2 = true, truncated = false, int_input = false;
-    std::vector<int64_t> off;   // the constant added to each column (empty: none)
-    std::vector<size_t> chain;  // the nodes between the graph input and the value
-  };
-  struct EmbedLookup {
-    size_t gather = 0;
-    std::shared_ptr<TensorData> table;
-    EmbedCols ix;
-    int64_t V = 0, d = 0;
-    std::vector<size_t> tail;  // the Reshape / Flatten behind it
-    std::string out;
-    std::vector<int64_t> shape;
-  };
-  struct EmbedGroup {
-    std::vector<EmbedLookup> lookups;
-    std::vector<std::pair<int, EmbedCols>> parts;  // in output order: (lookup, -) or (-1, columns to copy)
-    std::vector<size_t> nodes;                     // every node the step stands for, ascending (filled by find_embeds)
-  };
-  std::map<size_t, EmbedGroup> embed_at;  // anchor node (the last of the group) -> the group
-  int64_t embed_elems = 0;                // table elements of the model so far
-  std::map<size_t, int> embed_node_id;    // Gather node -> its 1-based id in plan.prep_strict_nodes
-
-  // ---- feature interactions (host/interact.hpp; INTEGRATION.md 2.6 "Feature interactions") ---------------------------------------------
-  // dot: MatMul(T, Transpose(T, perm = [0,2,1])) of ONE value T [N, k, d], read whole or through Flatten / Reshape -> Gather(axis = 1) by a
-  // constant list; the axis-1 Concat that alone reads the selection beside inputs of the Concat that built T joins the step (pass-through).
-  // fm: Sub(square(ReduceSum(T, [1])), ReduceSum(square(T), [1])), the constant scalar Mul and the last-axis ReduceSum behind it.
-  // Found before the walk by structure (find_interactions); shapes are known, and the caps checked, where the step is emitted
-  // (lower_interact).  A graph without either pattern is lowered exactly as before.
-  struct InteractView {
-    size_t node = 0;
-    std::vector<int64_t> target;  // Reshape: its constant target; Flatten: {axis}; Identity: empty
-    bool back = false;            // the advanced-index form: behind its Transpose(1,0), where the value is [N, P] (else [P, N])
-  };
-  struct InteractMatch {
-    int mode = kInteractDot;
-    std::string T;
-    std::vector<size_t> nodes;  // every node the step stands for but the anchor
-    size_t product = 0;         // dot: the MatMul; fm: the Sub
-    // dot
-    std::vector<InteractView> views;  // between the product and the Gather
-    size_t gather = SIZE_MAX;         // SIZE_MAX: the whole matrix
-    std::vector<int64_t> idx;
-    // TorchScript's advanced-index form: Gather(axis = 0) of the transposed, flattened matrix by `index_value` (evaluated once k is known)
-    bool advanced = false;
-    std::string index_value, selection_value;  // selection_value: the name of the selection [N, P] a pass-through Concat reads
-    std::vector<InteractView> views_after;     // behind its Gather: in front of the Transpose(1,0) and behind it (InteractView::back)
-    size_t out_concat = SIZE_MAX, t_concat = SIZE_MAX;  // pass-through: the Concat that reads the selection, the Concat that built T
-    // fm
-    bool keep = false;  // keepdims of the two field sums
-    double h = 1.0;
-    bool has_h = false, h_after = false;
-    size_t last_sum = SIZE_MAX;  // the trailing ReduceSum
-  };
-  std::map<size_t, InteractMatch> interact_at;  // anchor (the last node of the pattern) -> the pattern
-
-  Lowerer(const onnx::Model &model, const std::string &output_select_in) : m(model) {
+  Lowerer::Lowerer(const onnx::Model &model, const std::string &output_select_in) : m(model) {
     // Which graph output is served.  Default: the first (engine.rs:146-149).  A selector names another one, by output
     // name or by decimal index (infera_load_model(name, "model.onnx#probabilities"), SURVEY.md 8f-3 "named / multi outputs").
     if (m.outputs.empty()) throw InferaError::onnx("model has no outputs");
@@ -431,7 +57,7 @@ struct Lowerer {
     }
   }
 
-  int new_buf(const std::vector<int64_t> &shape) {
+  int Lowerer::new_buf(const std::vector<int64_t> &shape) {
     // [N,C,L] tensors (1-D convolutional nets) are laid out and scheduled as [N,C,1,L]; values keep their 3-D shape
     plan.buf_shape.push_back(shape.size() == 3 ? std::vector<int64_t>{shape[0], shape[1], 1, shape[2]} : shape);
     const int64_t per_row = prod(shape, 1);
@@ -441,13 +67,13 @@ struct Lowerer {
   }
 
   // input i of n; a preprocessing-region value is materialised first (get_raw: as it is)
-  const Val &get(const NodeDef &n, size_t i) {
+  const Val &Lowerer::get(const NodeDef &n, size_t i) {
     const Val &v = get_raw(n, i);
     if (v.pv) materialize(n.inputs[i], &n);
     if (v.nn) materialize_nearest(n.inputs[i]);
     return v;
   }
-  const Val &get_raw(const NodeDef &n, size_t i) {
+  const Val &Lowerer::get_raw(const NodeDef &n, size_t i) {
     if (i >= n.inputs.size() || n.inputs[i].empty()) unsupported(n, "missing input " + std::to_string(i));
     auto it = vals.find(n.inputs[i]);
     if (it != vals.end()) {
@@ -460,16 +86,16 @@ struct Lowerer {
     if (ci != m.initializers.end()) return vals[n.inputs[i]] = const_val(ci->second);
     unsupported(n, "input '" + n.inputs[i] + "' is not produced by any earlier node");
   }
-  bool has_input(const NodeDef &n, size_t i) const { return i < n.inputs.size() && !n.inputs[i].empty(); }
+  bool Lowerer::has_input(const NodeDef &n, size_t i) const { return i < n.inputs.size() && !n.inputs[i].empty(); }
 
-  const std::vector<float> &cf32(const NodeDef &n, const Val &v) {
+  const std::vector<float> &Lowerer::cf32(const NodeDef &n, const Val &v) {
     if (!v.is_const || v.c->dtype != onnx::kFloat) unsupported(n, "expected a constant f32 tensor");
     return v.c->f32;
   }
 
   // Binds the node's first output to `buf`.  `folded` = the node itself emitted no step (alias or
   // fused into its producer), i.e. it is an edge inside the buffer rather than a consumer of it.
-  void set_act(const NodeDef &n, int buf, const std::vector<int64_t> &shape, bool folded = false, int ra = 0) {
+  void Lowerer::set_act(const NodeDef &n, int buf, const std::vector<int64_t> &shape, bool folded, int ra) {
     Val v;
     v.buf = buf;
     v.shape = shape;
@@ -480,14 +106,14 @@ struct Lowerer {
   }
 
   // Number of not-yet-folded consumers (incl. graph outputs) of a buffer across all its names.
-  int live_uses(int buf) {
+  int Lowerer::live_uses(int buf) {
     int total = 0;
     for (const auto &nm : buf_names[buf]) total += uses[nm];
     return total - alias_edges[buf];
   }
 
   // The step that produced `v` if it can still absorb a trailing op: sole consumer is this node.
-  Step *fusable_producer(const NodeDef &n, size_t in_idx) {
+  Step *Lowerer::fusable_producer(const NodeDef &n, size_t in_idx) {
     const Val &v = get(n, in_idx);
     if (v.is_const || v.buf <= 0) return nullptr;
     if (live_uses(v.buf) != 1) return nullptr;
@@ -496,24 +122,24 @@ struct Lowerer {
     return &plan.steps[size_t(it->second)];
   }
   // The last step, if it wrote `buf` and nothing but this node reads `buf`: it can be folded into this node and removed (drop_tail)
-  const Step *sole_tail(int buf) {
+  const Step *Lowerer::sole_tail(int buf) {
     auto pit = producer.find(buf);
     if (buf <= 0 || pit == producer.end() || pit->second != int(plan.steps.size()) - 1 || live_uses(buf) != 1) return nullptr;
     return &plan.steps.back();
   }
-  void drop_tail() {
+  void Lowerer::drop_tail() {
     producer.erase(plan.steps.back().out);
     plan.steps.pop_back();
   }
 
   // Appends `s` writing a new buffer of `shape`; returns the buffer.
-  int push_step(Step s, const std::vector<int64_t> &shape) {
+  int Lowerer::push_step(Step s, const std::vector<int64_t> &shape) {
     s.out = new_buf(shape);
     plan.steps.push_back(std::move(s));
     producer[plan.steps.back().out] = int(plan.steps.size()) - 1;
     return plan.steps.back().out;
   }
-  Step &emit(Step s, const NodeDef &n, const std::vector<int64_t> &out_shape) {
+  Step &Lowerer::emit(Step s, const NodeDef &n, const std::vector<int64_t> &out_shape) {
     s.origin = node_label(n);
     // a rank-3 value computed elementwise from a window [rows, T, C] that a step wrote into a flat [rows, T * C] buffer (a recurrent,
     // window Dense, LayerNorm or attention step) is a window itself, not an [N, C, L] tensor: its buffer stays flat, so time steps can
@@ -523,15 +149,15 @@ struct Lowerer {
     set_act(n, push_step(std::move(s), window ? flat_shape(out_shape) : out_shape), out_shape);
     return plan.steps.back();
   }
-  static std::vector<int64_t> flat_shape(const std::vector<int64_t> &shape) { return {shape[0], prod(shape, 1)}; }
+  std::vector<int64_t> Lowerer::flat_shape(const std::vector<int64_t> &shape) { return {shape[0], prod(shape, 1)}; }
   // ... the same for a step whose output is a window by construction
-  void emit_window(Step s, const NodeDef &n, const std::vector<int64_t> &out_shape) {
+  void Lowerer::emit_window(Step s, const NodeDef &n, const std::vector<int64_t> &out_shape) {
     if (s.origin.empty()) s.origin = node_label(n);
     set_act(n, push_step(std::move(s), flat_shape(out_shape)), out_shape);
   }
 
   // ------------------------------------------------------------------------------------------
-  void dense(const NodeDef &n, bool gemm) {
+  void Lowerer::dense(const NodeDef &n, bool gemm) {
     const Val &a = get(n, 0);
     const Val &b = get(n, 1);
     if (a.is_const) unsupported(n, "constant left operand is not supported");
@@ -640,7 +266,7 @@ struct Lowerer {
 
   // MatMul of a window [rows, T, K] by a constant [K, M]: the flat buffer IS the [rows * T, K] matrix, so this is a Dense step with a
   // repeat count (Step::rep), served by the Dense kernels over rows * T rows.  The bias Add and the activation behind it fuse as usual.
-  void dense_window(const NodeDef &n) {
+  void Lowerer::dense_window(const NodeDef &n) {
     const Val a = get(n, 0);
     const Val &b = get(n, 1);
     const auto &w = cf32(n, b);
@@ -672,7 +298,7 @@ struct Lowerer {
   }
 
   // Broadcast a constant against an activation's per-row shape; returns per_row floats.
-  std::vector<float> broadcast_const(const NodeDef &n, const Val &c, const std::vector<int64_t> &act_shape) {
+  std::vector<float> Lowerer::broadcast_const(const NodeDef &n, const Val &c, const std::vector<int64_t> &act_shape) {
     const auto &cv = cf32(n, c);
     std::vector<int64_t> cs = c.shape;
     if (cs.size() > act_shape.size()) unsupported(n, "constant operand has higher rank than the activation");
@@ -696,7 +322,7 @@ struct Lowerer {
     return out;
   }
 
-  static float fold_bop(char op, float u, float v) {
+  float Lowerer::fold_bop(char op, float u, float v) {
     switch (op) {
       case '+': return u + v;
       case '-': return u - v;
@@ -709,7 +335,7 @@ struct Lowerer {
     }
   }
 
-  void binary(const NodeDef &n, char op) {
+  void Lowerer::binary(const NodeDef &n, char op) {
     if (n.inputs.size() != 2) unsupported(n, "exactly two inputs are supported");
     const Val &a = get(n, 0);
     const Val &b = get(n, 1);
@@ -942,10 +568,10 @@ struct Lowerer {
   }
 
   // ---- constant folding of the integer (shape) sub-graphs exporters emit around Reshape ----
-  void set_const_i64(const NodeDef &n, std::vector<int64_t> v, std::vector<int64_t> dims) {
+  void Lowerer::set_const_i64(const NodeDef &n, std::vector<int64_t> v, std::vector<int64_t> dims) {
     vals[n.outputs[0]] = const_i64(std::move(v), std::move(dims));
   }
-  void fold_int_binary(const NodeDef &n, char op, const Val &a, const Val &b) {
+  void Lowerer::fold_int_binary(const NodeDef &n, char op, const Val &a, const Val &b) {
     const auto &x = a.c->i64, &y = b.c->i64;
     if (x.size() != y.size() && x.size() != 1 && y.size() != 1) unsupported(n, "integer folding needs equal sizes or a scalar");
     std::vector<int64_t> o(std::max(x.size(), y.size()));
@@ -956,7 +582,7 @@ struct Lowerer {
     }
     set_const_i64(n, o, x.size() >= y.size() ? a.shape : b.shape);
   }
-  void shape_op(const NodeDef &n) {
+  void Lowerer::shape_op(const NodeDef &n) {
     const Val &a = get(n, 0);
     std::vector<int64_t> d = a.shape;
     // the symbolic row count is carried as 0, which Reshape reads as "copy this dim from the input"
@@ -970,12 +596,12 @@ struct Lowerer {
     const int64_t cnt = int64_t(o.size());
     set_const_i64(n, std::move(o), {cnt});
   }
-  std::vector<int64_t> const_ints(const NodeDef &n, size_t i, const char *what) {
+  std::vector<int64_t> Lowerer::const_ints(const NodeDef &n, size_t i, const char *what) {
     const Val &v = get(n, i);
     if (!v.is_const || v.c->dtype != onnx::kInt64) unsupported(n, std::string(what) + " must be a constant integer tensor");
     return v.c->i64;
   }
-  void gather(const NodeDef &n) {
+  void Lowerer::gather(const NodeDef &n) {
     const Val &d = get(n, 0);
     const Val &ix = get(n, 1);
     // column pick out of a [rows, K] activation (the probability of one class, a feature subset): a contiguous range
@@ -1027,13 +653,13 @@ struct Lowerer {
   // May one time step be cut out of `a` as a contiguous column range?  Only a rank-3 value [rows, T, C] / [T, rows, C] whose buffer is
   // registered as a flat [rows, per_row] matrix: what a recurrent step writes, or a Reshape of a flat table.  Every other rank-3 activation
   // (Conv1d tensors, which may live in the channel-quad layout) keeps the channel-slice path and its layout rules.
-  bool time_steppable(const Val &a) const {
+  bool Lowerer::time_steppable(const Val &a) const {
     return !a.is_const && a.buf >= 0 && a.shape.size() == 3 && a.ra <= 1 && plan.buf_shape[size_t(a.buf)].size() == 2;
   }
   // Step `t` of the time axis of a rank-3 activation `a` (rows first or time-major) as output 0 of n: a SliceCols of C columns, or -- the
   // schedule fold -- nothing at all when `a` is the whole forward Y of a unidirectional recurrent step that nothing else reads and t is
   // the last step: that step then stores Y_h (H values per row, not T * H).  drop_axis: the time axis disappears (a scalar Gather index)
-  void time_step(const NodeDef &n, const Val &a, int64_t t, bool drop_axis) {
+  void Lowerer::time_step(const NodeDef &n, const Val &a, int64_t t, bool drop_axis) {
     const int64_t T = a.shape[size_t(1 - a.ra)], C = a.shape[2], N = a.shape[size_t(a.ra)];
     if (t < 0) t += T;
     if (t < 0 || t >= T) unsupported(n, "time step out of range");
@@ -1065,7 +691,7 @@ struct Lowerer {
   // feature-axis slice of a [rows, K] activation: out = in[:, b:e]
   // ... or a channel range of an [N,C,H,W] activation: channels [b, e) are one contiguous block of every sample, in
   // NCHW and (whole quads) in the channel-quad layout alike
-  void emit_slice_cols(const std::string &origin, const Val &a, int64_t b, int64_t e, const std::string &out_name) {
+  void Lowerer::emit_slice_cols(const std::string &origin, const Val &a, int64_t b, int64_t e, const std::string &out_name) {
     const int64_t inner = prod(a.shape, 2);
     std::vector<int64_t> oshape = a.shape;
     oshape[1] = e - b;
@@ -1081,7 +707,7 @@ struct Lowerer {
     vals[out_name] = v;
     buf_names[v.buf].push_back(out_name);
   }
-  void split(const NodeDef &n) {
+  void Lowerer::split(const NodeDef &n) {
     const Val &a = get(n, 0);
     if (a.is_const || a.shape.size() < 2) unsupported(n, "only [rows, K] or [N,C,...] activations");
     int64_t axis = n.attr_i("axis", 0);
@@ -1104,7 +730,7 @@ struct Lowerer {
       off += sizes[size_t(i)];
     }
   }
-  void slice(const NodeDef &n) {
+  void Lowerer::slice(const NodeDef &n) {
     const Val &d = get(n, 0);
     if (!d.is_const && d.shape.size() >= 2) {  // activation: feature / channel axis slice with step 1
       std::vector<int64_t> st, en, ax, sp;
@@ -1155,7 +781,7 @@ struct Lowerer {
     const int64_t cnt = int64_t(o.size());
     set_const_i64(n, std::move(o), {cnt});
   }
-  void cast(const NodeDef &n) {
+  void Lowerer::cast(const NodeDef &n) {
     const Val &a = get(n, 0);
     const int64_t to = n.attr_i("to", onnx::kFloat);
     const bool to_int = to == onnx::kInt64 || to == onnx::kInt32, to_h = to == onnx::kFloat16, to_f = to == onnx::kFloat || to == onnx::kDouble || to_h;
@@ -1211,7 +837,7 @@ struct Lowerer {
     std::vector<int64_t> shape = a.shape;
     int_bufs.insert(emit(std::move(s), n, shape).out);
   }
-  void concat(const NodeDef &n) {
+  void Lowerer::concat(const NodeDef &n) {
     if (n.inputs.empty()) unsupported(n, "no inputs");
     bool all_const = true;
     for (size_t i = 0; i < n.inputs.size(); i++) all_const = all_const && get(n, i).is_const;
@@ -1259,7 +885,7 @@ struct Lowerer {
     producer[out] = int(plan.steps.size()) - 1;
     set_act(n, out, out_shape);
   }
-  void reduce_mean(const NodeDef &n) {
+  void Lowerer::reduce_mean(const NodeDef &n) {
     const Val &a = get(n, 0);
     if (!a.is_const && a.shape.size() == 2) {
       const Val x = a;
@@ -1305,7 +931,7 @@ struct Lowerer {
     emit(std::move(s), n, shape);
   }
   // The Reduce* family over the last axis of [rows, F] or of a window [rows, T, E]: one RowReduce step (hip/reduce.hip)
-  void row_reduce(const NodeDef &n) {
+  void Lowerer::row_reduce(const NodeDef &n) {
     static const std::map<std::string, int> ops = {{"ReduceSum", kReduceSum}, {"ReduceMean", kReduceMean}, {"ReduceMax", kReduceMax}, {"ReduceMin", kReduceMin},
                                                    {"ReduceProd", kReduceProd}, {"ReduceL1", kReduceL1}, {"ReduceL2", kReduceL2},
                                                    {"ReduceSumSquare", kReduceSumSquare}, {"ReduceLogSum", kReduceLogSum}, {"ReduceLogSumExp", kReduceLogSumExp}};
@@ -1333,7 +959,7 @@ struct Lowerer {
     else emit(std::move(s), n, shape);
   }
   // ArgMin: the twin of ArgMax
-  void argmin(const NodeDef &n) {
+  void Lowerer::argmin(const NodeDef &n) {
     const Val &a = get(n, 0);
     if (a.is_const || a.shape.size() != 2) unsupported(n, "only [rows, K] activations");
     int64_t axis = n.attr_i("axis", 0);
@@ -1349,7 +975,7 @@ struct Lowerer {
     int_bufs.insert(emit(std::move(s), n, shape).out);
   }
   // k of a TopK node (a constant input from opset 10 on, an attribute before); -1: not a constant
-  int64_t topk_k(const NodeDef &n) {
+  int64_t Lowerer::topk_k(const NodeDef &n) {
     if (has_input(n, 1)) {
       const Val *v = find_value(n.inputs[1]);
       return v && v->is_const && v->c->dtype == onnx::kInt64 && v->c->i64.size() == 1 ? v->c->i64[0] : -1;
@@ -1357,7 +983,7 @@ struct Lowerer {
     return n.attr_i("k", -1);
   }
   // binds output o of n to a new buffer written by step s
-  int bind_output(const NodeDef &n, size_t o, Step s, const std::vector<int64_t> &shape, bool whole) {
+  int Lowerer::bind_output(const NodeDef &n, size_t o, Step s, const std::vector<int64_t> &shape, bool whole) {
     Val v;
     v.buf = push_step(std::move(s), shape);
     v.shape = shape;
@@ -1367,7 +993,7 @@ struct Lowerer {
     return v.buf;
   }
   // TopK over the last axis of [rows, M]: one step per output that is read (Values, Indices as f32 values)
-  void topk(const NodeDef &n) {
+  void Lowerer::topk(const NodeDef &n) {
     const Val a = get(n, 0);
     if (a.is_const || a.shape.size() != 2 || a.ra != 0) bad_form(n, "the input must be a [rows, M] activation, got " + shape_str(a.shape));
     int64_t axis = n.attr_i("axis", -1);
@@ -1391,7 +1017,7 @@ struct Lowerer {
     }
   }
 
-  void argmax(const NodeDef &n) {
+  void Lowerer::argmax(const NodeDef &n) {
     const Val &a = get(n, 0);
     if (a.is_const || a.shape.size() != 2) unsupported(n, "only [rows, classes] activations");
     int64_t axis = n.attr_i("axis", 0);
@@ -1407,7 +1033,7 @@ struct Lowerer {
     int_bufs.insert(emit(std::move(s), n, shape).out);
   }
 
-  void unary(const NodeDef &n) {
+  void Lowerer::unary(const NodeDef &n) {
     Act act;
     float pa = 0.f, pb = 0.f;
     static const std::map<std::string, Act> simple = {
@@ -1438,7 +1064,7 @@ struct Lowerer {
   }
   // activation `act` on input `idx` of node n: into the epilogue of the step that produced it when that step takes one
   // and nothing else reads the value, else an elementwise pass
-  void apply_unary(const NodeDef &n, size_t idx, Act act, float pa, float pb, const std::string &label) {
+  void Lowerer::apply_unary(const NodeDef &n, size_t idx, Act act, float pa, float pb, const std::string &label) {
     const Val &a = get(n, idx);
     if (a.is_const) unsupported(n, "activation of a constant");
     std::vector<int64_t> shape = a.shape;
@@ -1468,7 +1094,7 @@ struct Lowerer {
     emit(std::move(s), n, shape);
   }
 
-  void alias(const NodeDef &n, const std::vector<int64_t> &new_shape) {
+  void Lowerer::alias(const NodeDef &n, const std::vector<int64_t> &new_shape) {
     const Val &a = get_raw(n, 0);
     if (prod(new_shape, 1) != prod(a.shape, 1) || new_shape.empty() || new_shape[0] != a.shape[0])
       unsupported(n, "reshape " + shape_str(a.shape) + " -> " + shape_str(new_shape) + " does not preserve the row axis");
@@ -1487,7 +1113,7 @@ struct Lowerer {
     set_act(n, buf, new_shape, true);
   }
 
-  void reshape_like(const NodeDef &n) {
+  void Lowerer::reshape_like(const NodeDef &n) {
     const Val &a = get_raw(n, 0);
     if (a.is_const) {
       if (n.op == "Identity") { vals[n.outputs[0]] = a; return; }
@@ -1573,7 +1199,7 @@ struct Lowerer {
 
   // Identity / Squeeze / Unsqueeze / Reshape of a value whose row axis is not axis 0: an alias when the axes in front of the row axis keep
   // their total extent (then the other axes keep their order in the rows-first buffer), else rejected -- it would need data moved
-  void reshape_tagged(const NodeDef &n) {
+  void Lowerer::reshape_tagged(const NodeDef &n) {
     const Val a = get_raw(n, 0);
     const int64_t rank = int64_t(a.shape.size());
     std::vector<int64_t> out;
@@ -1659,7 +1285,7 @@ struct Lowerer {
     set_act(n, a.buf, out, true, ra);
   }
 
-  void softmax(const NodeDef &n, bool logsm) {
+  void Lowerer::softmax(const NodeDef &n, bool logsm) {
     const Val &a = get(n, 0);
     if (a.is_const) unsupported(n, "softmax of a constant");
     const int64_t rank = int64_t(a.shape.size());
@@ -1682,7 +1308,7 @@ struct Lowerer {
     emit(std::move(s), n, shape);
   }
 
-  void spatial(const NodeDef &n, Step &s, int64_t H, int64_t W, const int64_t *extra_pad = nullptr) {
+  void Lowerer::spatial(const NodeDef &n, Step &s, int64_t H, int64_t W, const int64_t *extra_pad) {
     s.sh = s.sw = s.dh = s.dw = 1;
     s.pt = s.pl = s.pb = s.pr = 0;
     // (1-D operators run as [N,C,1,L]: one stride / dilation, two pads, all on the W axis)
@@ -1730,7 +1356,7 @@ struct Lowerer {
     if (s.OH <= 0 || s.OW <= 0) unsupported(n, "empty spatial output");
   }
 
-  void conv(const NodeDef &n) {
+  void Lowerer::conv(const NodeDef &n) {
     const Val &a = get(n, 0);
     const Val &w = get(n, 1);
     const bool one_d = a.shape.size() == 3 && w.shape.size() == 3;  // Conv1d: [N,C,L] as [N,C,1,L], kernel [M,C/g,k] as [M,C/g,1,k]
@@ -1749,7 +1375,7 @@ struct Lowerer {
     emit(std::move(s), n, conv_out_shape(s, a));
   }
   // the geometry fields of a Conv / QLinearConv node over activation `a` with a kernel of shape `ws` ([M,C/g,kh,kw], or [M,C/g,k]: Conv1d)
-  void conv_geometry(const NodeDef &n, Step &s, const Val &a, const std::vector<int64_t> &ws) {
+  void Lowerer::conv_geometry(const NodeDef &n, Step &s, const Val &a, const std::vector<int64_t> &ws) {
     const bool one_d = a.shape.size() == 3;
     s.C = a.shape[1]; s.H = one_d ? 1 : a.shape[2]; s.Wd = one_d ? a.shape[2] : a.shape[3];
     s.Mo = ws[0]; s.kh = one_d ? 1 : ws[2]; s.kw = one_d ? ws[2] : ws[3];
@@ -1759,14 +1385,14 @@ struct Lowerer {
     s.K = (s.C / s.groups) * s.kh * s.kw;
     s.M = s.Mo;
   }
-  static std::vector<int64_t> conv_out_shape(const Step &s, const Val &a) {
+  std::vector<int64_t> Lowerer::conv_out_shape(const Step &s, const Val &a) {
     if (a.shape.size() == 3) return {a.shape[0], s.Mo, s.OW};
     return {a.shape[0], s.Mo, s.OH, s.OW};
   }
 
   // ---- ConvTranspose / Resize / Upsample: the operators that make a tensor spatially larger (host/deconv.hpp) ----
   // scale / shift per output channel into a transposed convolution's weights [C, M/g, kh, kw] and bias, in f64, rounded once
-  static void convt_fold_affine(Step &p, const std::vector<double> &sc, const std::vector<double> &sh, const std::string &label) {
+  void Lowerer::convt_fold_affine(Step &p, const std::vector<double> &sc, const std::vector<double> &sh, const std::string &label) {
     const int64_t Cg = p.C / p.groups, Mg = p.Mo / p.groups, taps = p.kh * p.kw;
     for (int64_t c = 0; c < p.C; c++)
       for (int64_t ml = 0; ml < Mg; ml++) {
@@ -1778,7 +1404,7 @@ struct Lowerer {
     for (int64_t mo = 0; mo < p.Mo; mo++) p.bias[size_t(mo)] = float(sc[size_t(mo)] * double(p.bias[size_t(mo)]) + sh[size_t(mo)]);
     p.origin += "+" + label;
   }
-  void conv_transpose(const NodeDef &n) {
+  void Lowerer::conv_transpose(const NodeDef &n) {
     const Val &a = get(n, 0);
     if (a.is_const || (a.shape.size() != 3 && a.shape.size() != 4)) bad_form(n, "the input must be an [N,C,L] or [N,C,H,W] activation (rank 3 or 4), got " + shape_str(a.shape));
     const bool one_d = a.shape.size() == 3;
@@ -1865,7 +1491,7 @@ struct Lowerer {
     emit(std::move(s), n, shape);
   }
 
-  void resize(const NodeDef &n) {
+  void Lowerer::resize(const NodeDef &n) {
     const bool upsample = n.op == "Upsample";
     const Val &a = get(n, 0);
     if (a.is_const || (a.shape.size() != 3 && a.shape.size() != 4)) bad_form(n, "the input must be an [N,C,L] or [N,C,H,W] activation, got " + shape_str(a.shape));
@@ -1939,7 +1565,7 @@ struct Lowerer {
     emit(std::move(s), n, shape);
   }
 
-  void batchnorm(const NodeDef &n) {
+  void Lowerer::batchnorm(const NodeDef &n) {
     const Val &a = get(n, 0);
     if (a.is_const || a.shape.size() < 2) unsupported(n, "bad input");
     const auto &sc = cf32(n, get(n, 1)), &bi = cf32(n, get(n, 2)), &mu = cf32(n, get(n, 3)), &var = cf32(n, get(n, 4));
@@ -1997,8 +1623,8 @@ struct Lowerer {
 
   // ---- InstanceNormalization / GroupNormalization (host/spatialnorm.hpp): one SpatialNorm step ----------------------
   // `a` [N,C,L] / [N,C,H,W] normalised over each of G channel groups with per-channel scale / shift; the result is bound to `out_name`
-  void spatial_norm_step(const NodeDef &n, const Val &a, int64_t G, std::vector<float> scale, std::vector<float> shift, float eps, const std::string &origin,
-                         const std::string &out_name) {
+  void Lowerer::spatial_norm_step(const NodeDef &n, const Val &a, int64_t G, std::vector<float> scale, std::vector<float> shift, float eps, const std::string &origin,
+                                  const std::string &out_name) {
     if (const std::string why = spatialnorm_refusal(a.shape, G, int64_t(scale.size()), int64_t(shift.size()), eps); !why.empty()) bad_form(n, why);
     if (plan.buf_shape[size_t(a.buf)].size() != 4) bad_form(n, "the input " + shape_str(a.shape) + " is a window of a flat table, not an [N,C,L] / [N,C,H,W] tensor");
     Step s;
@@ -2021,7 +1647,7 @@ struct Lowerer {
     buf_names[v.buf].push_back(out_name);
   }
   // the activation input of a normalisation node and its constant scale / B
-  Val spatial_norm_input(const NodeDef &n, std::vector<float> *scale, std::vector<float> *bias) {
+  Val Lowerer::spatial_norm_input(const NodeDef &n, std::vector<float> *scale, std::vector<float> *bias) {
     const Val a = get(n, 0);
     if (a.is_const) bad_form(n, "the input must be an activation");
     if (a.ra != 0) bad_form(n, "the input " + shape_str(a.shape) + " is a time-major value (its row axis is axis " + std::to_string(a.ra) + ")");
@@ -2033,7 +1659,7 @@ struct Lowerer {
     }
     return a;
   }
-  void instance_norm(const NodeDef &n) {
+  void Lowerer::instance_norm(const NodeDef &n) {
     std::vector<float> sc, bi;
     const Val a = spatial_norm_input(n, &sc, &bi);
     const int64_t C = a.shape.size() >= 2 ? a.shape[1] : 0;
@@ -2041,7 +1667,7 @@ struct Lowerer {
   }
   // GroupNormalization: scale / bias per group under opset 18 (broadcast over the group's channels here), per channel under opset 21;
   // stash_type only names the precision of the statistics, which is f32 here
-  void group_norm(const NodeDef &n) {
+  void Lowerer::group_norm(const NodeDef &n) {
     std::vector<float> sc, bi, scale, shift;
     const Val a = spatial_norm_input(n, &sc, &bi);
     if (m.opset < 18) bad_form(n, "GroupNormalization needs opset 18 or later");
@@ -2055,7 +1681,7 @@ struct Lowerer {
     spatial_norm_step(n, a, G, std::move(scale), std::move(shift), n.attr_f("epsilon", 1e-5f), node_label(n), n.outputs[0]);
   }
 
-  void find_group_norms() {
+  void Lowerer::find_group_norms() {
     for (size_t i = 0; i < m.nodes.size(); i++) {
       const NodeDef &r = m.nodes[i];
       if (!graph->live[i] || absorbed[i] || r.op != "Reshape" || r.inputs.size() != 2 || r.outputs.empty()) continue;
@@ -2067,7 +1693,7 @@ struct Lowerer {
     }
   }
   // a constant that multiplies / shifts x [N,C,...] per channel: C values shaped [C,1,1] / [1,C,1,1] (one spatial axis: [C,1] / [1,C,1])
-  const std::vector<float> *per_channel_const(const Val *c, const std::vector<int64_t> &x_shape) {
+  const std::vector<float> *Lowerer::per_channel_const(const Val *c, const std::vector<int64_t> &x_shape) {
     if (!c || !c->is_const || c->c->dtype != onnx::kFloat) return nullptr;
     const size_t r = x_shape.size(), cr = c->shape.size();
     if (cr != r && cr != r - 1) return nullptr;
@@ -2075,7 +1701,7 @@ struct Lowerer {
       if (c->shape[i] != (i + (r - cr) == 1 ? x_shape[1] : 1)) return nullptr;
     return &c->c->f32;
   }
-  bool exporter_group_norm(const GnMatch &gm, const NodeDef &first) {
+  bool Lowerer::exporter_group_norm(const GnMatch &gm, const NodeDef &first) {
     const NodeDef &inorm = m.nodes[gm.inorm], &back = m.nodes[gm.back];
     const Val *xp = find_value(first.inputs[0]);
     if (!xp || xp->is_const || xp->pv || xp->ra != 0 || xp->buf < 0 || (xp->shape.size() != 3 && xp->shape.size() != 4)) return false;
@@ -2131,7 +1757,7 @@ struct Lowerer {
     return true;
   }
 
-  void pool(const NodeDef &n, bool is_max) {
+  void Lowerer::pool(const NodeDef &n, bool is_max) {
     const Val &a = get(n, 0);
     const bool one_d = a.shape.size() == 3;
     if (a.is_const || (a.shape.size() != 4 && !one_d)) unsupported(n, "only [N,C,L] / [N,C,H,W] activations");
@@ -2153,7 +1779,7 @@ struct Lowerer {
 
   // Pad with zeros on the two spatial axes of an [N,C,H,W] activation: no kernel -- the value keeps its buffer and
   // the Conv that consumes it widens its own padding (the form TF / Keras exporters write for 'same' convolutions).
-  void pad(const NodeDef &n) {
+  void Lowerer::pad(const NodeDef &n) {
     const Val &a = get(n, 0);
     if (a.is_const || a.shape.size() != 4) unsupported(n, "only [N,C,H,W] activations");
     if (n.attr_s("mode", "constant") != "constant") unsupported(n, "only constant (zero) padding");
@@ -2178,7 +1804,7 @@ struct Lowerer {
     buf_names[v.buf].push_back(n.outputs[0]);
     alias_edges[v.buf]++;
   }
-  void lrn(const NodeDef &n) {
+  void Lowerer::lrn(const NodeDef &n) {
     const Val &a = get(n, 0);
     if (a.is_const || a.shape.size() < 3) unsupported(n, "only [N,C,...] activations");
     Step s;
@@ -2197,7 +1823,7 @@ struct Lowerer {
   }
   // Transpose: constants are folded (2-D weight matrices); on activations only the channel shuffle of ShuffleNet-style
   // blocks -- Reshape [N,C,H,W] -> [N,g,C/g,H,W], Transpose(0,2,1,3,4), Reshape back -- which is a channel permutation.
-  void transpose(const NodeDef &n) {
+  void Lowerer::transpose(const NodeDef &n) {
     const Val &a = get(n, 0);
     const int64_t rank = int64_t(a.shape.size());
     std::vector<int64_t> perm;
@@ -2272,51 +1898,27 @@ struct Lowerer {
   // Linear -> permute.  Transpose(0,2,3,1) of an [N,C,H,W] tensor a step wrote emits nothing: its result is a VIEW (Val::cl) that names the
   // same buffer.  The operators below read a view as the NCHW tensor it is and lower as they do on one; Transpose(0,3,1,2) ends it ----
   // Is the rank-4 rows-first value `a` the [N,C,H,W] tensor a step wrote?  (The model input is not: buffer 0 has no producer.)
-  bool nchw_tensor(const Val &a) const {
+  bool Lowerer::nchw_tensor(const Val &a) const {
     if (a.is_const || a.pv || a.nn || a.q || a.cl || a.ra != 0 || a.padded() || a.buf <= 0 || a.shape.size() != 4 || !producer.count(a.buf)) return false;
     const auto &bs = plan.buf_shape[size_t(a.buf)];
     return bs.size() == 4 && bs[1] == a.shape[1] && bs[2] == a.shape[2] && bs[3] == a.shape[3] && bs[1] > 0 && bs[2] > 0 && bs[3] > 0;
   }
-  bool reads_view(const NodeDef &n) const {
+  bool Lowerer::reads_view(const NodeDef &n) const {
     for (const auto &in_name : n.inputs) {
       auto it = vals.find(in_name);
       if (it != vals.end() && it->second.cl) return true;
     }
     return false;
   }
-  // lowers `n` (by `body`) with every view among its inputs presented as the [N,C,H,W] tensor it names; the result is a view again
-  template <class F>
-  void as_nchw(const NodeDef &n, F body) {
-    std::map<std::string, std::vector<int64_t>> was;
-    for (const auto &in_name : n.inputs) {
-      auto it = vals.find(in_name);
-      if (it == vals.end() || !it->second.cl) continue;
-      Val &v = it->second;
-      was[in_name] = v.shape;
-      v.shape = {v.shape[0], v.shape[3], v.shape[1], v.shape[2]};
-      v.cl = false;
-    }
-    body();
-    for (const auto &w : was) {
-      Val &v = vals[w.first];
-      v.shape = w.second;
-      v.cl = true;
-    }
-    auto it = vals.find(n.outputs[0]);
-    if (it == vals.end() || it->second.is_const || it->second.shape.size() != 4) bad_form(n, "its result on a channels-last view is not an [N,C,H,W] tensor");
-    Val &o = it->second;
-    o.shape = {o.shape[0], o.shape[2], o.shape[3], o.shape[1]};
-    o.cl = true;
-  }
   // a copy of `n` whose input `i` is the constant `c`
-  NodeDef with_const_input(const NodeDef &n, size_t i, Val c) {
+  NodeDef Lowerer::with_const_input(const NodeDef &n, size_t i, Val c) {
     NodeDef r = n;
     r.inputs[i] = n.inputs[i] + "#" + std::to_string(view_consts++);
     vals[r.inputs[i]] = std::move(c);
     return r;
   }
   // the constant `c` with the dims `dims` (the same elements: type and half tag kept)
-  static Val redimensioned(const Val &c, std::vector<int64_t> dims, std::vector<float> f32) {
+  Val Lowerer::redimensioned(const Val &c, std::vector<int64_t> dims, std::vector<float> f32) {
     auto t = std::make_shared<TensorData>();
     t->dtype = c.c->dtype;
     t->elem = c.c->elem;
@@ -2324,7 +1926,7 @@ struct Lowerer {
     t->f32 = std::move(f32);
     return const_val(std::move(t));
   }
-  void lower_on_view(const NodeDef &n) {
+  void Lowerer::lower_on_view(const NodeDef &n) {
     const std::string &op = n.op;
     static const std::set<std::string> unary_ops = {"Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                                     "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Round"};
@@ -2373,8 +1975,8 @@ struct Lowerer {
                     "MatMul by a constant, elementwise operators and Transpose(0,3,1,2) read one");
   }
   // ONE ChannelNorm step on the [N,C,H,W] tensor `x`; the result is bound to `out_name`, as a view or not
-  void channel_norm_step(const NodeDef &n, const Val &x, std::vector<float> scale, std::vector<float> shift, bool has_shift, float eps, const std::string &origin,
-                         const std::string &out_name, bool as_view) {
+  void Lowerer::channel_norm_step(const NodeDef &n, const Val &x, std::vector<float> scale, std::vector<float> shift, bool has_shift, float eps, const std::string &origin,
+                                  const std::string &out_name, bool as_view) {
     const int64_t C = x.shape[1], S = x.shape[2] * x.shape[3];
     if (const std::string why = channelnorm_refusal(C, S, int64_t(scale.size()), has_shift ? int64_t(shift.size()) : -1, eps); !why.empty()) bad_form(n, why);
     Step s;
@@ -2397,7 +1999,7 @@ struct Lowerer {
     buf_names[v.buf].push_back(out_name);
   }
   // LayerNormalization(axis = -1) on a view: over the channels at each pixel
-  void channel_norm_node(const NodeDef &n) {
+  void Lowerer::channel_norm_node(const NodeDef &n) {
     const Val a = get(n, 0);
     if (!a.cl) bad_form(n, "it reads the channels-last view among its parameters");
     int64_t axis = n.attr_i("axis", -1);
@@ -2423,7 +2025,7 @@ struct Lowerer {
     channel_norm_step(n, x, std::move(scale), std::move(shift), has_b, n.attr_f("epsilon", 1e-5f), node_label(n), n.outputs[0], true);
   }
   // MatMul of a view by a constant [C, M]: the 1x1 convolution [M, C, 1, 1] it is, through the path a Conv node takes
-  void view_matmul(const NodeDef &n) {
+  void Lowerer::view_matmul(const NodeDef &n) {
     const Val a = get(n, 0);
     const Val &b = get(n, 1);
     if (!a.cl) bad_form(n, "the channels-last view '" + n.inputs[1] + "' is its right operand; only view x constant [C, M] is supported");
@@ -2443,7 +2045,7 @@ struct Lowerer {
   //   ReduceMean(axes = [1]) -> Sub -> Pow(2) | Mul(d, d) -> ReduceMean(axes = [1]) -> Add(eps) -> Sqrt -> Div [-> Mul(w [C,1,1])] [-> Add(b [C,1,1])]
   // matched forward from the first ReduceMean as decomposed_layer_norm matches the [N,E] form; the nodes up to the Div emit nothing, and the
   // Mul / Add behind it compose into gamma and beta by the per-channel rule (binary).  false: not that chain
-  bool channel_axis_mean(const NodeDef &n) {
+  bool Lowerer::channel_axis_mean(const NodeDef &n) {
     if (n.op != "ReduceMean" || n.attr_i("keepdims", 1) == 0) return false;
     std::vector<int64_t> axes;
     if (has_input(n, 1)) {
@@ -2453,7 +2055,7 @@ struct Lowerer {
     } else if (auto *p = n.attr_ints("axes")) axes = *p;
     return axes.size() == 1 && (axes[0] == 1 || axes[0] == -3);
   }
-  bool channels_first_norm(const NodeDef &mean, const Val &x) {
+  bool Lowerer::channels_first_norm(const NodeDef &mean, const Val &x) {
     if (!nchw_tensor(x) || !channel_axis_mean(mean)) return false;
     const NodeDef *sub = only_reader(mean.outputs[0]);
     if (!sub || sub->op != "Sub" || sub->inputs.size() != 2 || sub->inputs[0] != mean.inputs[0] || sub->inputs[1] != mean.outputs[0]) return false;
@@ -2495,14 +2097,14 @@ struct Lowerer {
   // Add behind it move their constants into its tables (tokens_concat, binary) ----
   // Is the rank-3 rows-first value `a` the [N, C, S] tensor a step wrote -- itself ([N,C,L], held as [N,C,1,L]) or a view of [N,C,H,W]?
   // (The model input and its views are not: buffer 0 has no producer.)
-  bool conv_tensor_view(const Val &a) const {
+  bool Lowerer::conv_tensor_view(const Val &a) const {
     if (a.is_const || a.pv || a.nn || a.ra != 0 || a.buf <= 0 || a.shape.size() != 3 || !producer.count(a.buf)) return false;
     const auto &bs = plan.buf_shape[size_t(a.buf)];
     return bs.size() == 4 && bs[1] == a.shape[1] && bs[2] > 0 && bs[3] > 0 && bs[2] * bs[3] == a.shape[2];
   }
   // Flatten(axis = 2) of an [N,C,H,W] tensor a step wrote, read by Transpose(0,2,1) nodes only: the [N, C, H*W] view torch's flatten(2)
   // stands for (the [N*C, H*W] matrix the operator specification gives has the same elements in the same order)
-  bool token_view_of_flatten(const NodeDef &n, const Val &a) const {
+  bool Lowerer::token_view_of_flatten(const NodeDef &n, const Val &a) const {
     if (a.is_const || a.pv || a.ra != 0 || a.buf <= 0 || !producer.count(a.buf) || plan.buf_shape[size_t(a.buf)].size() != 4) return false;
     auto it = graph->consumers_of.find(n.outputs[0]);
     if (it == graph->consumers_of.end() || it->second.empty()) return false;
@@ -2515,7 +2117,7 @@ struct Lowerer {
     }
     return true;
   }
-  void tokens_step(const NodeDef &n, const Val &a) {
+  void Lowerer::tokens_step(const NodeDef &n, const Val &a) {
     const auto &bs = plan.buf_shape[size_t(a.buf)];
     if (const std::string why = tokens_refusal(bs); !why.empty()) bad_form(n, why);
     Step s;
@@ -2526,7 +2128,7 @@ struct Lowerer {
     emit_window(std::move(s), n, {a.shape[0], a.shape[2], a.shape[1]});
   }
   // the Tokens step whose result `v` is, as that step left it
-  Step *tokens_producer(const Val &v) {
+  Step *Lowerer::tokens_producer(const Val &v) {
     if (v.is_const || v.buf <= 0 || v.ra != 0 || v.shape.size() != 3) return nullptr;
     auto it = producer.find(v.buf);
     if (it == producer.end()) return nullptr;
@@ -2534,7 +2136,7 @@ struct Lowerer {
     return p.kind == StepKind::Tokens && p.out == v.buf && v.shape[1] == p.rep && v.shape[2] == p.K ? &p : nullptr;
   }
   // Concat with a token value among its operands: constants per row in front of it become the step's prefix rows.  false: no operand is one
-  bool tokens_concat(const NodeDef &n) {
+  bool Lowerer::tokens_concat(const NodeDef &n) {
     size_t at = SIZE_MAX;
     for (size_t i = 0; i < n.inputs.size(); i++)
       if (const Val *v = find_value(n.inputs[i]); v && tokens_producer(*v)) at = i;
@@ -2599,8 +2201,8 @@ struct Lowerer {
   // ---- the decomposed LayerNorm older exporters write, on [rows, E] (where nothing else serves it):
   //   ReduceMean(-1) -> Sub -> Pow(2) | Mul(d, d) -> ReduceMean(-1) -> Add(eps) -> Sqrt -> Div [-> Mul(gamma)] [-> Add(beta)]
   // matched forward from the first ReduceMean when it is met; the nodes behind it emit nothing and the last one's output is the step's.
-  const NodeDef *only_reader(const std::string &v) const { return graph->sole_reader(v, true); }
-  bool last_axis_mean(const NodeDef &n, int64_t rank) {
+  const NodeDef *Lowerer::only_reader(const std::string &v) const { return graph->sole_reader(v, true); }
+  bool Lowerer::last_axis_mean(const NodeDef &n, int64_t rank) {
     if (n.op != "ReduceMean" || n.attr_i("keepdims", 1) == 0) return false;
     std::vector<int64_t> axes;
     if (has_input(n, 1)) {
@@ -2611,14 +2213,14 @@ struct Lowerer {
     return axes.size() == 1 && (axes[0] == -1 || axes[0] == rank - 1);
   }
   // the f32 constant other operand of a two-input node reading `v`, or null
-  const Val *const_operand(const NodeDef &n, const std::string &v, bool second_only = false) {
+  const Val *Lowerer::const_operand(const NodeDef &n, const std::string &v, bool second_only) {
     if (n.inputs.size() != 2) return nullptr;
     const bool left = n.inputs[0] == v;
     if (!left && (second_only || n.inputs[1] != v)) return nullptr;
     const Val *c = find_value(n.inputs[left ? 1 : 0]);
     return c && c->is_const && c->c->dtype == onnx::kFloat ? c : nullptr;
   }
-  bool decomposed_layer_norm(const NodeDef &mean, const Val &x) {
+  bool Lowerer::decomposed_layer_norm(const NodeDef &mean, const Val &x) {
     const int64_t rank = int64_t(x.shape.size()), E = x.shape.back();
     if (rank != 2 || x.ra != 0 || E < 1 || E > kLnMaxE || !last_axis_mean(mean, rank)) return false;
     std::vector<const NodeDef *> nodes;
@@ -2684,7 +2286,7 @@ struct Lowerer {
   }
 
   // LayerNormalization (opset 17) over the last axis of [rows, E] / [rows, T, E]: one LayerNorm step (hip/layernorm.hip)
-  void layer_norm(const NodeDef &n) {
+  void Lowerer::layer_norm(const NodeDef &n) {
     const Val a = get(n, 0);
     const int64_t rank = int64_t(a.shape.size());
     if (a.is_const || rank < 2) unsupported(n, "unsupported operator form: the input must be a [rows, E] or [rows, T, E] activation");
@@ -2714,7 +2316,7 @@ struct Lowerer {
   }
 
   // a constant known before the walk (an initializer or a Constant node): its first element and its element count
-  bool graph_const_scalar(const std::string &name, double *v, size_t *count = nullptr) const {
+  bool Lowerer::graph_const_scalar(const std::string &name, double *v, size_t *count) const {
     const GraphIndex::Const c = graph->constant(name);
     const TensorData *t = c.t.get();
     if (!t) {
@@ -2731,7 +2333,7 @@ struct Lowerer {
   }
   // `v0` as a row mask; "" or why it is none.  lens: as the length column of a recurrent layer's sequence_lens (find_seq_lens): the same
   // source tracing through Cast / Reshape / Flatten only, and the source may be a rank-1 value
-  std::string trace_row_mask(const std::string &v0, RowMask *rm, bool lens = false) const {
+  std::string Lowerer::trace_row_mask(const std::string &v0, RowMask *rm, bool lens) const {
     const std::string what = lens ? "sequence_lens" : "mask";
     std::vector<size_t> chain;
     std::string v = v0;
@@ -2844,7 +2446,7 @@ struct Lowerer {
     return "";
   }
   // the negative constant scalar b of masked keys
-  float row_mask_fill(const NodeDef &n, const std::string &name, bool add) {
+  float Lowerer::row_mask_fill(const NodeDef &n, const std::string &name, bool add) {
     double b = 0;
     size_t cnt = 0;
     if (graph->row_data.count(name) || !graph_const_scalar(name, &b, &cnt)) bad_form(n, "the fill '" + name + "' of masked keys is not a constant");
@@ -2855,7 +2457,7 @@ struct Lowerer {
     return f;
   }
   // Add(scores, other): other = Mul(Sub(1, float(mask [N,1,1,T])), b) (BERT); false: no such form
-  bool match_add_row_mask(const NodeDef &add, const std::string &other, AttnMatch &am) {
+  bool Lowerer::match_add_row_mask(const NodeDef &add, const std::string &other, AttnMatch &am) {
     auto pi = graph->producer_of.find(other);
     if (pi == graph->producer_of.end()) return false;
     const NodeDef &mul = m.nodes[pi->second];
@@ -2884,7 +2486,7 @@ struct Lowerer {
     return true;
   }
   // Where(masked, b, scores) or Where(kept, scores, b) (masked_fill)
-  void match_where_row_mask(const NodeDef &wh, const std::string &scores, AttnMatch &am) {
+  void Lowerer::match_where_row_mask(const NodeDef &wh, const std::string &scores, AttnMatch &am) {
     const bool scores_last = wh.inputs[2] == scores;
     auto rm = std::make_shared<RowMask>();
     rm->at = &wh;
@@ -2900,7 +2502,7 @@ struct Lowerer {
     am.rm = std::move(rm);
   }
 
-  void find_attention() {
+  void Lowerer::find_attention() {
     const size_t N = m.nodes.size();
     const std::vector<char> &live = graph->live;
     const std::set<std::string> &graph_outs = graph->graph_outs;
@@ -3131,7 +2733,7 @@ struct Lowerer {
 
   // The masked mean over time (the sentence-embedding head): Div(ReduceSum(Mul(x, m), 1), Clip(ReduceSum(m or mask, 1), min = c)) with
   // m = float(mask [N, T, 1]), traced like an attention's row mask, becomes ONE MeanTime step with a row mask (lower_masked_mean)
-  void find_masked_means() {
+  void Lowerer::find_masked_means() {
     auto sum_over_time = [&](const NodeDef &r) {
       std::vector<int64_t> ax;
       return r.op == "ReduceSum" && graph->std_dom(r) && !r.inputs.empty() && graph_ints_arg(r, 1, "axes", &ax) && ax == std::vector<int64_t>{1};
@@ -3186,7 +2788,7 @@ struct Lowerer {
       mmean_at[idx(div)] = std::move(mm);
     }
   }
-  void lower_masked_mean(const MaskedMean &mm, const NodeDef &div) {
+  void Lowerer::lower_masked_mean(const MaskedMean &mm, const NodeDef &div) {
     const Val *x = find_value(mm.x);
     if (!x) bad_form(div, "the window '" + mm.x + "' of the masked mean is produced by no earlier node");
     if (x->pv) materialize(mm.x, &div), x = find_value(mm.x);
@@ -3209,7 +2811,7 @@ struct Lowerer {
     emit_window(std::move(s), div, {x->shape[0], E});
   }
 
-  const Val *find_value(const std::string &name) {
+  const Val *Lowerer::find_value(const std::string &name) {
     auto it = vals.find(name);
     if (it != vals.end()) {
       if (it->second.nn) materialize_nearest(name);
@@ -3220,7 +2822,7 @@ struct Lowerer {
     return nullptr;
   }
 
-  void lower_attention(const AttnMatch &am, const NodeDef &anchor) {
+  void Lowerer::lower_attention(const AttnMatch &am, const NodeDef &anchor) {
     const NodeDef &qk = *am.qk;
     auto bad = [&](const std::string &why) { unsupported(qk, "unsupported operator form: " + why); };
     static const char *names[3] = {"Q", "K", "V"};
@@ -3422,7 +3024,7 @@ struct Lowerer {
   }
 
   // Sum of any number of equal-shaped activations: a chain of residual adds
-  void sum(const NodeDef &n) {
+  void Lowerer::sum(const NodeDef &n) {
     if (n.inputs.empty()) unsupported(n, "no inputs");
     if (n.inputs.size() == 1) { lower_node(std_node(n, "Identity", {n.inputs[0]}, n.outputs[0])); return; }
     std::string cur = n.inputs[0];
@@ -3434,7 +3036,7 @@ struct Lowerer {
       cur = out;
     }
   }
-  void global_avgpool(const NodeDef &n, bool is_max) {
+  void Lowerer::global_avgpool(const NodeDef &n, bool is_max) {
     const Val &a = get(n, 0);
     if (a.is_const || a.shape.size() < 3) unsupported(n, "bad input");
     Step s;
@@ -3453,9 +3055,9 @@ struct Lowerer {
   // same buffer (Val::q).  DequantizeLinear of a constant folds to f32 and remembers its integers; of a quantised activation it becomes
   // a FakeQuant step -- or the output quantisation of the QDense step in front of it.  MatMul / Gemm between a FakeQuant (or a
   // quantised QDense) and dequantised int8 weights, and QLinearMatMul, become QDense.
-  [[noreturn]] void bad_form(const NodeDef &n, const std::string &why) { unsupported(n, "unsupported operator form: " + why); }
+  [[noreturn]] void Lowerer::bad_form(const NodeDef &n, const std::string &why) { unsupported(n, "unsupported operator form: " + why); }
 
-  QArgs quant_args(const NodeDef &n, size_t si, size_t zi, const char *what) {
+  Lowerer::QArgs Lowerer::quant_args(const NodeDef &n, size_t si, size_t zi, const char *what) {
     QArgs qa;
     if (n.attr_i("block_size", 0) != 0) bad_form(n, "block_size (blocked quantisation) is not supported");
     const Val &sv = get(n, si);
@@ -3478,7 +3080,7 @@ struct Lowerer {
     }
     return qa;
   }
-  Quant act_quant(const NodeDef &n, const QArgs &qa, const char *what) {
+  Quant Lowerer::act_quant(const NodeDef &n, const QArgs &qa, const char *what) {
     if (qa.scale.size() != 1) bad_form(n, std::string("per-axis quantisation of an activation (") + what + ") is not supported");
     if (qa.elem != onnx::kUint8 && qa.elem != onnx::kInt8) bad_form(n, std::string(what) + " has element type " + std::to_string(qa.elem) + "; only uint8 and int8 are supported");
     Quant q;
@@ -3489,7 +3091,7 @@ struct Lowerer {
     return q;
   }
 
-  void set_quant(const NodeDef &n, int buf, const std::vector<int64_t> &shape, int ra, const Quant &q, bool done, bool folded) {
+  void Lowerer::set_quant(const NodeDef &n, int buf, const std::vector<int64_t> &shape, int ra, const Quant &q, bool done, bool folded) {
     set_act(n, buf, shape, folded, ra);
     Val &v = vals[n.outputs[0]];
     v.q = std::make_shared<const Quant>(q);
@@ -3497,7 +3099,7 @@ struct Lowerer {
     quant_node[n.outputs[0]] = &n;
   }
 
-  void quantize_linear(const NodeDef &n) {
+  void Lowerer::quantize_linear(const NodeDef &n) {
     const Val x = get(n, 0);
     if (x.is_const) bad_form(n, "quantising a constant is not supported");
     if (x.q) bad_form(n, "the input is a quantised tensor already");
@@ -3507,7 +3109,7 @@ struct Lowerer {
     set_quant(n, x.buf, x.shape, x.ra, q, false, true);
   }
 
-  void dequantize_linear(const NodeDef &n) {
+  void Lowerer::dequantize_linear(const NodeDef &n) {
     const Val x = get_raw(n, 0);
     if (x.pv) bad_form(n, "the input is not a quantised tensor");
     const QArgs qa = quant_args(n, 1, 2, x.is_const ? "constant's" : "activation");
@@ -3566,15 +3168,15 @@ struct Lowerer {
   }
 
   // QDense and QConv2d share their quantisation fields and the helpers below
-  static bool quantised_layer(const Step &s) { return s.kind == StepKind::QDense || s.kind == StepKind::QConv2d; }
+  bool Lowerer::quantised_layer(const Step &s) { return s.kind == StepKind::QDense || s.kind == StepKind::QConv2d; }
 
   // A Relu in front of a quantisation whose range starts at 0 (zp == qmin) changes nothing: sat() does the same.  Dropping it makes
   // the QDQ spelling (which writes the Relu) and the QLinear spelling (which cannot) one plan.
-  static void qdense_canonical_act(Step &s) {
+  void Lowerer::qdense_canonical_act(Step &s) {
     if (s.qy.on && s.act == Act::Relu && s.qy.zp == s.qy.qmin()) s.act = Act::None;
   }
 
-  void qdense_check_k(const NodeDef &n, const Step &s) {
+  void Lowerer::qdense_check_k(const NodeDef &n, const Step &s) {
     int64_t mb = 0;
     for (int32_t b : s.q_bias) mb = std::max<int64_t>(mb, std::llabs(int64_t(b)));
     if (!qdense_k_fits(s.K, mb))
@@ -3583,7 +3185,7 @@ struct Lowerer {
 
   // the bias of a QDense step: DequantizeLinear(int32, scale = x_scale * w_scale[m], zero point 0) is added to the accumulator as it
   // is; any other f32 constant after the scaling
-  void qdense_take_bias(const NodeDef &n, Step &s, const Val &c) {
+  void Lowerer::qdense_take_bias(const NodeDef &n, Step &s, const Val &c) {
     const auto &cv = cf32(n, c);
     const TensorData &t = *c.c;
     bool as_int = t.q_data && t.q_data->elem == onnx::kInt32 && int64_t(t.q_data->i64.size()) == s.M && (t.q_scale.size() == 1 || int64_t(t.q_scale.size()) == s.M);
@@ -3603,8 +3205,8 @@ struct Lowerer {
 
   // the QDense step of X[.., K] (quantised as xq) times the integer matrix `w` ([K, M], or [M, K] under trans) with scales ws and zero
   // points wz (one, or M of them)
-  Step make_qdense(const NodeDef &n, int in_buf, int64_t rep, const TensorData &w, bool trans, const std::vector<float> &ws, const std::vector<int64_t> &wz,
-                   const Quant &xq) {
+  Step Lowerer::make_qdense(const NodeDef &n, int in_buf, int64_t rep, const TensorData &w, bool trans, const std::vector<float> &ws, const std::vector<int64_t> &wz,
+                            const Quant &xq) {
     if (w.elem != onnx::kUint8 && w.elem != onnx::kInt8) bad_form(n, "the weights have element type " + std::to_string(w.elem) + "; only uint8 and int8 are supported");
     if (w.dims.size() != 2) bad_form(n, "the weights must be a [K, M] matrix");
     Step s;
@@ -3618,7 +3220,7 @@ struct Lowerer {
   }
   // the quantisation fields of a QDense / QConv2d step whose K and M are set: `w` holds K * M integers as [K, M] (or [M, K] under trans: a
   // Gemm's transB, a convolution's [M, C, kh, kw])
-  void take_quant_weights(const NodeDef &n, Step &s, const TensorData &w, bool trans, const std::vector<float> &ws, const std::vector<int64_t> &wz, const Quant &xq) {
+  void Lowerer::take_quant_weights(const NodeDef &n, Step &s, const TensorData &w, bool trans, const std::vector<float> &ws, const std::vector<int64_t> &wz, const Quant &xq) {
     if (w.elem != onnx::kUint8 && w.elem != onnx::kInt8) bad_form(n, "the weights have element type " + std::to_string(w.elem) + "; only uint8 and int8 are supported");
     const int64_t K = s.K, M = s.M;
     if (K <= 0 || M <= 0 || int64_t(w.i64.size()) != K * M) bad_form(n, "weight tensor " + shape_str(w.dims) + " does not match its data");
@@ -3643,7 +3245,7 @@ struct Lowerer {
 
   // MatMul / Gemm whose weights were dequantised from int8 / uint8 and whose input was just quantised: QDense.  false: not that
   // pattern (a weight-only model, a per-row weight scale ...) -- the float layer on the dequantised weights serves it
-  bool qdense_from_qdq(const NodeDef &n, bool gemm) {
+  bool Lowerer::qdense_from_qdq(const NodeDef &n, bool gemm) {
     const Val a = get(n, 0);
     const Val &b = get(n, 1);
     const TensorData &bt = *b.c;
@@ -3688,7 +3290,7 @@ struct Lowerer {
   }
 
   // QLinearMatMul(a, a_scale, a_zp, b, b_scale, b_zp, y_scale, y_zp): the same step, spelled in one node; its result stays a quantised value
-  void qlinear_matmul(const NodeDef &n) {
+  void Lowerer::qlinear_matmul(const NodeDef &n) {
     if (n.inputs.size() != 8) bad_form(n, "needs its eight inputs");
     const Val a = get_raw(n, 0);
     if (a.is_const || a.pv || !a.q) bad_form(n, "input a must be a quantised activation (the output of QuantizeLinear or QLinearMatMul)");
@@ -3713,7 +3315,7 @@ struct Lowerer {
   }
 
   // A QConv2d step over activation `a` (read from in_buf, quantised as xq) with the integer kernel `w` [M, C, kh, kw] (or [M, C, k])
-  Step make_qconv(const NodeDef &n, const Val &a, int in_buf, const TensorData &w, const std::vector<float> &ws, const std::vector<int64_t> &wz, const Quant &xq) {
+  Step Lowerer::make_qconv(const NodeDef &n, const Val &a, int in_buf, const TensorData &w, const std::vector<float> &ws, const std::vector<int64_t> &wz, const Quant &xq) {
     Step s;
     s.kind = StepKind::QConv2d;
     s.in0 = in_buf;
@@ -3725,7 +3327,7 @@ struct Lowerer {
   // Conv whose kernel was dequantised from int8 / uint8 (per tensor or per output channel) and whose input was just quantised: QConv2d.
   // false: not that pattern (weight-only quantisation, a grouped or depthwise layer, scales along another axis) -- the float
   // convolution on the dequantised kernel serves it
-  bool qconv_from_qdq(const NodeDef &n) {
+  bool Lowerer::qconv_from_qdq(const NodeDef &n) {
     const Val a = get(n, 0);
     const Val &w = get(n, 1);
     const TensorData &wt = *w.c;
@@ -3763,7 +3365,7 @@ struct Lowerer {
 
   // QLinearConv(x, x_scale, x_zp, w, w_scale, w_zp, y_scale, y_zp[, B]): QConv2d spelled in one node; its result stays a quantised value.
   // A grouped / depthwise one keeps float semantics, as its QDQ spelling does: FakeQuant -> Conv2d on the dequantised kernel -> FakeQuant
-  void qlinear_conv(const NodeDef &n) {
+  void Lowerer::qlinear_conv(const NodeDef &n) {
     if (n.inputs.size() < 8) bad_form(n, "needs at least its eight inputs (x, x_scale, x_zero_point, w, w_scale, w_zero_point, y_scale, y_zero_point)");
     const Val a = get_raw(n, 0);
     if (a.is_const || a.pv || !a.q) bad_form(n, "input x must be a quantised activation (the output of QuantizeLinear, QLinearConv or QLinearMatMul)");
@@ -3839,12 +3441,12 @@ struct Lowerer {
   // float16 graphs.  Activations stay f32 buffers; a value the graph types float16 carries Val::half, and the
   // result of every plan step that yields such a value is rounded once to half by a RoundHalf step (insert_half_roundings, after all
   // fusions have been made).  MatMul / Gemm on half weights become HDense, which rounds for itself.
-  static std::vector<uint16_t> half_bits(const std::vector<float> &v) {
+  std::vector<uint16_t> Lowerer::half_bits(const std::vector<float> &v) {
     std::vector<uint16_t> o(v.size());
     for (size_t i = 0; i < v.size(); i++) o[i] = onnx::float_to_half(v[i]);
     return o;
   }
-  void mark_half(const std::string &name) {
+  void Lowerer::mark_half(const std::string &name) {
     auto it = vals.find(name);
     if (it == vals.end()) return;
     Val &v = it->second;
@@ -3860,32 +3462,9 @@ struct Lowerer {
     v.half = true;
     if (v.buf >= 0) half_bufs.insert(v.buf);
   }
-  // lowers one node (by `body`) under the float16 typing rules: a node whose floating inputs are half yields half values
-  template <class F>
-  void lower_typed(const NodeDef &n, F body) {
-    int n_half = 0, n_float_act = 0;
-    for (const auto &in_name : n.inputs) {
-      if (in_name.empty()) continue;
-      const Val *v = nullptr;
-      Val from_init;
-      if (auto it = vals.find(in_name); it != vals.end()) v = &it->second;
-      else if (auto ci = m.initializers.find(in_name); ci != m.initializers.end()) v = &(from_init = const_val(ci->second));
-      if (!v) continue;
-      if (v->is_const) n_half += v->c->dtype == onnx::kFloat && v->c->elem == onnx::kFloat16;
-      else if (v->half) n_half++;
-      else if (!int_bufs.count(v->buf) && !v->q) n_float_act++;
-    }
-    if (n_half && n_float_act) bad_form(n, "it mixes float16 and float activations; cast one side (Cast) so that the operator has one type");
-    static const std::set<std::string> own_type = {"Cast", "ArgMax", "ArgMin", "Shape", "Size"};  // (their result type is not their input's)
-    cur_half = n_half > 0 && !own_type.count(n.op);
-    body();
-    if (cur_half)
-      for (const auto &o : n.outputs) mark_half(o);
-    cur_half = false;
-  }
 
   // does the result of this step need a rounding to be a half value, given half inputs?  Not when it only selects, moves or negates them
-  static bool half_exact(const Step &s) {
+  bool Lowerer::half_exact(const Step &s) {
     auto is_half_value = [](float v) { return std::isinf(v) || onnx::round_to_half(v) == v; };
     switch (s.kind) {
       case StepKind::RoundHalf:
@@ -3910,7 +3489,7 @@ struct Lowerer {
   // A RoundHalf step behind every step that writes a float16-typed buffer and is not exact on halves; the readers (and the served
   // output) move to the rounded buffer.  Runs once, after the last node: fusions into a producing step (an activation, a folded
   // BatchNormalization, a scaler) have happened by then, so a fused step is rounded once, at its result.
-  void insert_half_roundings() {
+  void Lowerer::insert_half_roundings() {
     if (half_bufs.empty()) return;
     std::map<int, size_t> last_writer;
     for (size_t i = 0; i < plan.steps.size(); i++) last_writer[plan.steps[i].out] = i;
@@ -3940,7 +3519,7 @@ struct Lowerer {
 
   // MatMul / Gemm of a float16 activation by constant float16 weights: the HDense step (plan.hpp, hip/hdense.hip).  false: not that
   // form (alpha / beta other than 1, a float bias, INFERA_HDENSE=0 ...) -- the float path serves it: Dense on the widened weights + RoundHalf
-  bool hdense(const NodeDef &n, bool gemm) {
+  bool Lowerer::hdense(const NodeDef &n, bool gemm) {
     if (!cur_half || !hdense_enabled) return false;
     const Val a = get(n, 0);
     const Val &b = get(n, 1);
@@ -3988,7 +3567,7 @@ struct Lowerer {
   }
 
   // ------------------------------------------------------------------------------------------
-  void lower_node(const NodeDef &n) {
+  void Lowerer::lower_node(const NodeDef &n) {
     const std::string &op = n.op;
     if (op != "Conv")
       for (const auto &in_name : n.inputs) {
@@ -4073,7 +3652,7 @@ struct Lowerer {
   }
 
   // every operator but the few that understand the row-axis tag reads rows-first values only
-  void check_row_axis(const NodeDef &n, bool understands) {
+  void Lowerer::check_row_axis(const NodeDef &n, bool understands) {
     if (understands) return;
     for (const auto &in_name : n.inputs) {
       auto it = vals.find(in_name);
@@ -4086,7 +3665,7 @@ struct Lowerer {
   // [D, rows, H] with the row count taken from Shape(X).  The symbolic row count (0 in a folded shape) becomes extent 1: one row, the same
   // for all.  (An extent that is 0 in the model file itself -- an empty tensor -- cannot be told from the folded row count and would become
   // one element too; the only consumer of these constants, a recurrent layer's initial state, checks the shape it gets.)
-  void constant_fill(const NodeDef &n) {
+  void Lowerer::constant_fill(const NodeDef &n) {
     const bool expand = n.op == "Expand";
     std::vector<int64_t> dims = const_ints(n, expand ? 1 : 0, "shape");
     const int64_t lead = dims.size() == 3 ? dims[0] : -1;  // (a [batch, p, E] target: tokens_concat)
@@ -4128,1334 +3707,11 @@ struct Lowerer {
     if (expand && dims.size() == 3 && lead >= 0) expanded_lead[n.outputs[0]] = lead;
     vals[n.outputs[0]] = const_f32(std::move(o), dims);
   }
-
-  void find_seq_lens() {
-    std::set<size_t> chain;
-    for (size_t i = 0; i < m.nodes.size(); i++) {
-      const NodeDef &n = m.nodes[i];
-      if (!graph->live[i] || !graph->std_dom(n) || (n.op != "LSTM" && n.op != "GRU" && n.op != "RNN") || !has_input(n, 4) || !graph->row_data.count(n.inputs[4])) continue;
-      RowMask r;
-      if (const std::string why = trace_row_mask(n.inputs[4], &r, true); !why.empty()) bad_form(n, why);
-      if (r.k != 1 || r.shape != std::vector<int64_t>{-1})
-        bad_form(n, "sequence_lens traced to " + std::to_string(r.k) + " column" + (r.k == 1 ? "" : "s") + " of a graph input as " + shape_str(r.shape) +
-                        "; only one length per row, [N]");
-      if (!r.is_int) bad_form(n, "sequence_lens read from a float graph input without a Cast to an integer type");
-      if (plan.input_declared_type == "float16") bad_form(n, "sequence_lens taken from a float16 graph input");
-      if (r.src0 < 0 || r.src0 >= plan.buf_per_row[0]) bad_form(n, "the sequence_lens column lies outside the input");
-      plan.prep_strict_nodes.push_back({"node '" + (n.name.empty() ? n.op : n.name) + "' (" + n.op + ")", ": sequence_lens outside 0…T"});
-      seq_lens_at[i] = {r.src0, r.is_int, int(plan.prep_strict_nodes.size())};
-      chain.insert(r.nodes.begin(), r.nodes.end());
-    }
-    // what a tracing node computes is read by recurrent layers as sequence_lens and by nothing else
-    const std::string &served = m.outputs[out_index].name;
-    for (size_t i : chain)
-      for (const auto &o : m.nodes[i].outputs) {
-        bool ok = o != served;
-        if (auto it = graph->consumers_of.find(o); it != graph->consumers_of.end())
-          for (size_t c : it->second) {
-            const NodeDef &r = m.nodes[c];
-            const bool as_lens = seq_lens_at.count(c) && std::count(r.inputs.begin(), r.inputs.end(), o) == 1 && r.inputs[4] == o;
-            ok = ok && (chain.count(c) || as_lens);
-          }
-        if (!ok) bad_form(m.nodes[i], "this node of a sequence_lens sub-graph also feeds nodes outside the recurrent layers' sequence_lens");
-      }
-    for (size_t i : chain) {
-      absorbed[i] = 1;
-      region[i] = 0;
-      for (const auto &in : m.nodes[i].inputs)
-        if (!in.empty()) uses[in]--;
-    }
-    for (const auto &kv : seq_lens_at) uses[m.nodes[kv.first].inputs[4]]--;
-  }
-
-  // LSTM / GRU / RNN: one Recurrent step per output that is read.  X is [T, rows, F] (layout 0: time-major, row-axis tag 1) or
-  // [rows, T, F] (layout 1); the step writes Y as [rows, T, D, H] and the last states as [rows, D, H], and the values carry ONNX's shapes
-  // with the row-axis tag that makes them so
-  void recurrent(const NodeDef &n) {
-    if (n.inputs.size() < 3 || n.inputs[0].empty() || n.inputs[1].empty() || n.inputs[2].empty())
-      unsupported(n, "unsupported operator form: needs the three inputs X, W, R");
-    const Val x = get(n, 0);
-    const int64_t layout = n.attr_i("layout", 0) == 1 ? 1 : 0;
-    if (x.is_const || x.shape.size() != 3 || x.ra != 1 - layout)
-      unsupported(n, std::string("unsupported operator form: X must be ") + (layout ? "[rows, T, F] (layout 1)" : "[T, rows, F] (layout 0: a Transpose(1,0,2) of the rows-first input)") +
-                         ", got " + shape_str(x.shape) + " with the row axis at " + std::to_string(x.ra));
-    auto arg = [&](size_t i) {
-      RnnInput r;
-      if (!has_input(n, i)) return r;
-      r.present = true;
-      const Val &v = get(n, i);
-      if (v.is_const) r.c = v.c.get();
-      return r;
-    };
-    const bool lstm = n.op == "LSTM";
-    auto sl = seq_lens_at.find(size_t(&n - m.nodes.data()));  // (traced: the value itself was never produced)
-    const bool lens = sl != seq_lens_at.end();
-    std::shared_ptr<const RnnPack> rp;
-    try {
-      rp = std::make_shared<const RnnPack>(pack_recurrent(n, x.shape[size_t(layout)], x.shape[2], arg(1), arg(2), arg(3), lens ? RnnInput{} : arg(4), arg(5),
-                                                          lstm ? arg(6) : RnnInput{}, lstm ? arg(7) : RnnInput{}));
-    } catch (const RnnError &e) {
-      unsupported(n, e.what());
-    }
-    const int64_t N = x.shape[size_t(x.ra)], T = rp->T, D = rp->D, H = rp->H;
-    for (size_t o = 0; o < (lstm ? 3u : 2u); o++) {
-      if (!wanted(n, o)) continue;
-      Step s;
-      s.kind = StepKind::Recurrent;
-      s.in0 = x.buf;
-      s.rnn = rp;
-      s.out_mode = o == 0 ? kRnnY : o == 1 ? kRnnYh : kRnnYc;
-      if (lens) {
-        s.in3 = 0;
-        s.rm_off = sl->second.col;
-        s.rm_int = sl->second.is_int;
-        s.rnn_node = sl->second.node;
-      }
-      s.origin = node_label(n);
-      Val v;
-      v.buf = push_step(std::move(s), {N, o == 0 ? T * D * H : D * H});
-      if (o == 0) v.shape = layout ? std::vector<int64_t>{N, T, D, H} : std::vector<int64_t>{T, D, N, H};
-      else v.shape = layout ? std::vector<int64_t>{N, D, H} : std::vector<int64_t>{D, N, H};
-      v.ra = layout ? 0 : (o == 0 ? 2 : 1);
-      vals[n.outputs[o]] = v;
-      buf_names[v.buf].push_back(n.outputs[o]);
-    }
-  }
-
-  // ---- ai.onnx.ml: the classical-ML nodes sklearn exporters write (tract-onnx 0.22 ops/ml is what serves them for
-  // the reference, engine.rs:49-56).  Each is rewritten into the standard operators above, so a Scaler folds into the
-  // linear model behind it and a LinearClassifier's scores go through the Dense (+Softmax) kernels; semantics follow
-  // the ONNX-ML operator specification (tract's sources are not in /root/reference).
-  static NodeDef std_node(const NodeDef &from, const char *op, std::vector<std::string> in, std::string out) {
-    NodeDef d;
-    d.op = op;
-    d.name = from.name.empty() ? from.op : from.op + ":" + from.name;
-    d.inputs = std::move(in);
-    d.outputs = {std::move(out)};
-    return d;
-  }
-  static void set_i(NodeDef &d, const char *k, int64_t v) {
-    onnx::Attribute a;
-    a.name = k;
-    a.type = 2;
-    a.i = v;
-    d.attrs[k] = a;
-  }
-  bool wanted(const NodeDef &n, size_t i) const {
-    if (i >= n.outputs.size() || n.outputs[i].empty()) return false;
-    auto it = uses.find(n.outputs[i]);
-    return it != uses.end() && it->second > 0;
-  }
-  std::vector<float> ml_floats(const NodeDef &n, const char *k, int64_t want, float dflt, bool allow_scalar) {
-    const onnx::Attribute *a = n.attr(k);
-    std::vector<float> v = a ? a->floats : std::vector<float>{};
-    if (v.empty()) return std::vector<float>(size_t(want), dflt);
-    if (allow_scalar && v.size() == 1) return std::vector<float>(size_t(want), v[0]);
-    if (int64_t(v.size()) != want) unsupported(n, std::string(k) + " holds " + std::to_string(v.size()) + " values, expected " + std::to_string(want));
-    return v;
-  }
-  // post_transform over raw scores `raw` -> value `out`
-  void ml_post_transform(const NodeDef &n, const std::string &raw, const std::string &out) {
-    const std::string pt = n.attr_s("post_transform", "NONE");
-    if (pt == "NONE") lower_node(std_node(n, "Identity", {raw}, out));
-    else if (pt == "LOGISTIC") lower_node(std_node(n, "Sigmoid", {raw}, out));
-    else if (pt == "SOFTMAX") {
-      NodeDef d = std_node(n, "Softmax", {raw}, out);
-      set_i(d, "axis", 1);
-      lower_node(d);
-    } else unsupported(n, "post_transform " + pt);
-  }
-  // output 0 of n = a0 + step * index (the label of an evenly spaced class table; not both a0 = 0 and step = 1): a Mul and / or an Add on the
-  // whole-numbered `index`.  (Tables of int64 labels pass their a0 and step as doubles: float(double(v)) == float(v) for |v| < 2^53.)
-  void label_from_index(const NodeDef &n, std::string index, double a0, double step) {
-    const std::string tmp = n.outputs[0] + "\x01";
-    if (step != 1.0) {
-      vals[tmp + "step"] = const_f32({float(step)}, {});
-      const std::string nxt = a0 == 0.0 ? n.outputs[0] : tmp + "scaled";
-      if (nxt != n.outputs[0]) uses[nxt] = 1;
-      lower_node(std_node(n, "Mul", {index, tmp + "step"}, nxt));
-      index = nxt;
-    }
-    if (a0 != 0.0) {
-      vals[tmp + "first"] = const_f32({float(a0)}, {});
-      lower_node(std_node(n, "Add", {index, tmp + "first"}, n.outputs[0]));
-    }
-  }
-  // ArrayFeatureExtractor: Y = X[..., indices].  Two forms occur in exported pipelines: a constant class table indexed
-  // by the ArgMax of the scores (label lookup; the table must be evenly spaced, then it is one multiply-add on the
-  // index), and a contiguous column range picked out of the feature matrix.
-  void array_feature_extractor(const NodeDef &n) {
-    const Val &x = get(n, 0);
-    const Val &ix = get(n, 1);
-    if (x.is_const && !ix.is_const) {
-      if (!int_bufs.count(ix.buf)) unsupported(n, "indices must be whole numbers (an ArgMax output)");
-      if (x.shape.size() != 1) unsupported(n, "only a 1-D class table");
-      std::vector<double> tab;
-      if (x.c->dtype == onnx::kInt64) tab.assign(x.c->i64.begin(), x.c->i64.end());
-      else tab.assign(x.c->f32.begin(), x.c->f32.end());
-      if (tab.size() < 2) unsupported(n, "class table needs two entries");
-      const double a0 = tab[0], step = tab[1] - tab[0];
-      for (size_t i = 0; i < tab.size(); i++)
-        if (tab[i] != a0 + step * double(i)) unsupported(n, "class table must be evenly spaced (label = a + b * index)");
-      if (step == 1.0 && a0 == 0.0) lower_node(std_node(n, "Identity", {n.inputs[1]}, n.outputs[0]));
-      else label_from_index(n, n.inputs[1], a0, step);
-      return;
-    }
-    if (!x.is_const && ix.is_const && x.shape.size() == 2 && ix.c->dtype == onnx::kInt64 && !ix.c->i64.empty()) {
-      const auto &v = ix.c->i64;
-      for (size_t i = 1; i < v.size(); i++)
-        if (v[i] != v[0] + int64_t(i)) unsupported(n, "only a contiguous column range");
-      if (v[0] < 0 || v[0] + int64_t(v.size()) > x.shape[1]) unsupported(n, "column index out of range");
-      const Val src = x;
-      emit_slice_cols(node_label(n), src, v[0], v[0] + int64_t(v.size()), n.outputs[0]);
-      return;
-    }
-    unsupported(n, "only (constant table, index activation) or (activation, constant contiguous indices)");
-  }
-  // The two-stage head of a tree ensemble / SVM node: kernel step `k` writes its partials [rows, part_cols]; a copy of `r` (the reduce
-  // step's kind and pack) turns them into a classifier's label (output 0, when read) with `label_mode`, and another into the raw scores
-  // [rows, score_cols] with `score_mode`, which post_transform turns into the scores output
-  void ml_head(const NodeDef &n, bool cls, Step k, int64_t part_cols, Step r, int label_mode, int score_mode, int64_t score_cols) {
-    const int64_t rows = get_raw(n, 0).shape[0];
-    const bool want_label = cls && wanted(n, 0), want_scores = cls ? wanted(n, 1) : true;
-    const std::string tmp = n.outputs[0] + "\x01";
-    k.out_mode = want_scores ? score_mode : label_mode;
-    NodeDef kn = n;
-    kn.outputs = {tmp + "partial"};
-    r.in0 = emit(std::move(k), kn, {rows, part_cols}).out;
-    auto reduce = [&](int mode, const std::string &out, const std::vector<int64_t> &shape) {
-      Step s = r;
-      s.out_mode = mode;
-      NodeDef d = n;
-      d.outputs = {out};
-      return emit(std::move(s), d, shape).out;
-    };
-    if (want_label) int_bufs.insert(reduce(label_mode, n.outputs[0], {rows}));
-    if (want_scores) {
-      const std::string raw = tmp + "raw";
-      uses[raw] = 1;
-      reduce(score_mode, raw, {rows, score_cols});
-      ml_post_transform(n, raw, cls ? n.outputs[1] : n.outputs[0]);
-    }
-  }
-  // TreeEnsembleRegressor / TreeEnsembleClassifier: a TreeEnsemble step (walk, per-slice partial sums) and a TreeReduce step (slices
-  // summed in fixed order, AVERAGE, base_values, binary expansion or the label), then post_transform on the scores
-  void tree_ensemble(const NodeDef &n) {
-    std::shared_ptr<const TreePack> tp;
-    const Val &x = get(n, 0);
-    if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, features] activations");
-    try {
-      tp = std::make_shared<const TreePack>(pack_tree_ensemble(n, x.shape[1]));
-    } catch (const TreeError &e) {
-      unsupported(n, e.what());
-    }
-    Step w, r;
-    w.kind = StepKind::TreeEnsemble;
-    w.in0 = x.buf;
-    r.kind = StepKind::TreeReduce;
-    w.tree = r.tree = tp;
-    // (the partials are f64, as f32 pairs)
-    ml_head(n, tp->classifier, std::move(w), 2 * tp->slices * tp->W, std::move(r), tp->binary ? kTreeBinaryLabel : kTreeLabel,
-            tp->binary ? kTreeBinaryScores : kTreeScores, tp->E);
-  }
-  // SVMRegressor / SVMClassifier: an SvmKernel step (X . S^T on the matrix cores, the kernel function, times the coefficients: per-slice
-  // partial sums) and an SvmReduce step (slices summed in fixed order, rho, then the value, one-class sign, pairwise decisions, votes and
-  // label, or Platt + pairwise coupling), then post_transform on the scores
-  void svm(const NodeDef &n) {
-    std::shared_ptr<const SvmPack> sp;
-    const Val &x = get(n, 0);
-    if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, features] activations");
-    try {
-      sp = std::make_shared<const SvmPack>(pack_svm(n, x.shape[1]));
-    } catch (const SvmError &e) {
-      unsupported(n, e.what());
-    }
-    const int64_t C = sp->classes, P = C * (C - 1) / 2;
-    const bool cls = sp->classifier;
-    const int score_mode = !cls ? (sp->one_class ? kSvmOneClass : kSvmValue) : sp->probabilities ? kSvmProb : kSvmDecision;
-    const int64_t score_cols = !cls ? 1 : sp->probabilities ? C : (C == 2 ? 2 : P);
-    Step k, r;
-    k.kind = StepKind::SvmKernel;
-    k.in0 = x.buf;
-    r.kind = StepKind::SvmReduce;
-    k.svm = r.svm = sp;
-    ml_head(n, cls, std::move(k), sp->slices * sp->Q, std::move(r), kSvmLabel, score_mode, score_cols);
-  }
-  // ZipMap (probabilities -> a sequence of maps), when its output is the one served: the C ABI carries f32 rows, so the probabilities
-  // [rows, C] it reads are served, one column per class in classlabels order (get_model_info says so)
-  void zipmap(const NodeDef &n) {
-    const Val &x = get(n, 0);
-    if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, classes] probabilities");
-    size_t labels = 0;
-    if (const onnx::Attribute *a = n.attr("classlabels_int64s")) labels = a->ints.size();
-    if (const onnx::Attribute *a = n.attr("classlabels_strings")) labels = std::max(labels, a->strings.size());
-    if (int64_t(labels) != x.shape[1])
-      unsupported(n, "classlabels hold " + std::to_string(labels) + " labels for " + std::to_string(x.shape[1]) + " probability columns");
-    const std::vector<int64_t> shape = x.shape;
-    set_act(n, x.buf, shape, true);
-    if (n.outputs[0] == m.outputs[out_index].name) plan.output_zipmap = true;
-  }
-  void ml_node(const NodeDef &n) {
-    if (n.op == "ArrayFeatureExtractor") return array_feature_extractor(n);
-    if (n.op == "TreeEnsembleRegressor" || n.op == "TreeEnsembleClassifier") return tree_ensemble(n);
-    if (n.op == "SVMRegressor" || n.op == "SVMClassifier") return svm(n);
-    if (n.op == "ZipMap") return zipmap(n);
-    const Val &x = get(n, 0);
-    if (x.is_const || x.shape.size() != 2) unsupported(n, "only [rows, features] activations");
-    const int64_t F = x.shape[1];
-    const std::string tmp = n.outputs[0] + "\x01";
-    if (n.op == "Scaler") {
-      vals[tmp + "offset"] = const_f32(ml_floats(n, "offset", F, 0.f, true), {F});
-      vals[tmp + "scale"] = const_f32(ml_floats(n, "scale", F, 1.f, true), {F});
-      uses[tmp + "centered"] = 1;
-      lower_node(std_node(n, "Sub", {n.inputs[0], tmp + "offset"}, tmp + "centered"));
-      lower_node(std_node(n, "Mul", {tmp + "centered", tmp + "scale"}, n.outputs[0]));
-    } else if (n.op == "LinearRegressor" || n.op == "LinearClassifier") {
-      const bool cls = n.op == "LinearClassifier";
-      std::vector<int64_t> labels;
-      if (cls) {
-        if (n.attr("classlabels_strings")) unsupported(n, "string class labels cannot be returned as numbers");
-        if (auto *p = n.attr_ints("classlabels_ints")) labels = *p;
-        if (labels.size() < 2) unsupported(n, "needs at least two classlabels_ints");
-      }
-      const int64_t E = cls ? int64_t(labels.size()) : n.attr_i("targets", 1);
-      if (E < 1) unsupported(n, "targets must be positive");
-      vals[tmp + "coef"] = const_f32(ml_floats(n, "coefficients", E * F, 0.f, false), {E, F});
-      vals[tmp + "icpt"] = const_f32(ml_floats(n, "intercepts", E, 0.f, false), {E});
-      const bool want_label = cls && wanted(n, 0), want_scores = cls ? wanted(n, 1) : true;
-      const std::string raw = tmp + "raw";
-      uses[raw] = int(want_label) + int(want_scores);
-      NodeDef g = std_node(n, "Gemm", {n.inputs[0], tmp + "coef", tmp + "icpt"}, raw);
-      set_i(g, "transB", 1);
-      lower_node(g);
-      if (want_label) {
-        // label = classlabels_ints[argmax(raw scores)]; the class table must be an arithmetic progression
-        // (0..E-1, 1..E, {-1, 1}, ...), which is then one multiply-add on the index
-        const int64_t a0 = labels[0], step = labels[1] - labels[0];
-        for (size_t i = 0; i < labels.size(); i++)
-          if (labels[i] != a0 + step * int64_t(i)) unsupported(n, "classlabels_ints must be evenly spaced (label = a + b * index)");
-        const std::string index = (step == 1 && a0 == 0) ? n.outputs[0] : tmp + "index";
-        if (index != n.outputs[0]) uses[index] = 1;
-        NodeDef am = std_node(n, "ArgMax", {raw}, index);
-        set_i(am, "axis", 1);
-        set_i(am, "keepdims", 0);
-        lower_node(am);
-        if (step != 1 || a0 != 0) label_from_index(n, index, double(a0), double(step));
-      }
-      if (want_scores) ml_post_transform(n, raw, cls ? n.outputs[1] : n.outputs[0]);
-    } else if (n.op == "Normalizer") {
-      const std::string norm = n.attr_s("norm", "MAX");
-      Step s;
-      s.kind = StepKind::Softmax;
-      s.in0 = x.buf;
-      s.sm_norm = norm == "MAX" ? 1 : norm == "L1" ? 2 : norm == "L2" ? 3 : 0;
-      if (!s.sm_norm) unsupported(n, "norm " + norm);
-      s.sm_len = F;
-      std::vector<int64_t> shape = x.shape;
-      emit(std::move(s), n, shape);
-    } else {
-      unsupported(n, "unsupported operator");
-    }
-  }
-
-  static bool prep_encoder(const std::string &op) {
-    return op == "Imputer" || op == "Binarizer" || op == "OneHotEncoder" || op == "LabelEncoder" || op == "FeatureVectorizer";
-  }
-  // marks `region`; returns the graph inputs that start inside a region
-  std::set<std::string> find_regions() {
-    const size_t N = m.nodes.size(), M = m.inputs.size();
-    const std::map<std::string, size_t> &prod_of = graph->producer_of;
-    std::map<std::string, size_t> input_of;
-    for (size_t j = 0; j < M; j++) input_of[m.inputs[j].name] = j;
-    const std::set<std::string> &act = graph->row_data;  // names that hold row data
-    std::vector<char> elig(N, 0), trig(N + M, 0);
-    std::vector<size_t> uf(N + M);
-    std::iota(uf.begin(), uf.end(), size_t(0));
-    std::function<size_t(size_t)> find = [&](size_t a) { return uf[a] == a ? a : uf[a] = find(uf[a]); };
-    auto from_region = [&](const std::string &v) {  // a graph input or an eligible node's output
-      auto p = prod_of.find(v);
-      return input_of.count(v) || (p != prod_of.end() && elig[p->second]);
-    };
-    for (size_t i = 0; i < N; i++) {
-      if (!graph->live[i]) continue;
-      const NodeDef &n = m.nodes[i];
-      bool any_act = false;
-      for (const auto &in : n.inputs) any_act = any_act || act.count(in);
-      if (!any_act) continue;
-      const bool ml = n.domain == "ai.onnx.ml", std_dom = graph->std_dom(n);
-      const bool data_act = !n.inputs.empty() && act.count(n.inputs[0]);
-      bool e = false, t = false;
-      if (ml && n.op == "ArrayFeatureExtractor") {
-        e = data_act && n.inputs.size() == 2 && bool(graph->constant(n.inputs[1]));
-        if (e) {  // non-contiguous constant indices: nothing else serves them
-          auto ci = m.initializers.find(n.inputs[1]);
-          if (ci != m.initializers.end() && ci->second->dtype == onnx::kInt64) {
-            const auto &v = ci->second->i64;
-            for (size_t k = 1; k < v.size(); k++) t = t || v[k] != v[0] + int64_t(k);
-          } else {
-            t = true;  // (a Constant node's list: checked when lowered)
-          }
-        }
-      } else if (ml && (prep_encoder(n.op) || n.op == "Scaler")) {
-        e = data_act;
-        t = e && n.op != "Scaler";
-      } else if (std_dom && (n.op == "Cast" || n.op == "Reshape" || n.op == "Flatten" || n.op == "Squeeze" || n.op == "Identity")) {
-        e = data_act;
-      } else if (std_dom && n.op == "Concat") {
-        e = true;
-        for (const auto &in : n.inputs) e = e && act.count(in) && from_region(in);
-      }
-      if (!e) continue;
-      elig[i] = 1;
-      if (t) trig[i] = 1;
-      for (const auto &in : n.inputs) {
-        if (!act.count(in)) continue;
-        auto ij = input_of.find(in);
-        auto p = prod_of.find(in);
-        if (ij != input_of.end()) uf[find(i)] = find(N + ij->second);
-        else if (p != prod_of.end() && elig[p->second]) uf[find(i)] = find(p->second);
-      }
-    }
-    for (size_t j = 0; j < M; j++)
-      if (m.inputs[j].elem_type == onnx::kInt64 || m.inputs[j].elem_type == onnx::kInt32) trig[N + j] = 1;
-    std::vector<char> hot(N + M, 0);
-    for (size_t a = 0; a < N + M; a++)
-      if (trig[a]) hot[find(a)] = 1;
-    region.assign(N, 0);
-    for (size_t i = 0; i < N; i++) region[i] = elig[i] && hot[find(i)];
-    std::set<std::string> ins;
-    for (size_t j = 0; j < M; j++)
-      if (hot[find(N + j)]) ins.insert(m.inputs[j].name);
-    return ins;
-  }
-
-  // identity columns over buffer `buf` (a region value's source); is_int: whole numbers already
-  static PrepVal prep_identity(int buf, int64_t off, int64_t width, bool trunc, bool is_int) {
-    PrepVal p;
-    p.src = buf;
-    for (int64_t j = 0; j < width; j++) {
-      PrepCol c;
-      c.src = off + j;
-      c.trunc = trunc;
-      c.is_int = is_int || trunc;
-      p.cols.push_back(c);
-    }
-    return p;
-  }
-  void set_prep(const std::string &name, PrepVal p, std::vector<int64_t> shape) {
-    if (int64_t(p.cols.size()) > kPrepMaxOut)
-      throw InferaError::onnx("value '" + name + "' has " + std::to_string(p.cols.size()) + " columns; a preprocessing step writes at most " +
-                              std::to_string(kPrepMaxOut));
-    Val v;
-    v.pv = std::make_shared<const PrepVal>(std::move(p));
-    v.shape = std::move(shape);
-    vals[name] = v;
-  }
-  // input i of a region node as columns: a region value as it is, an activation as identity columns over its buffer.  Columns that
-  // already went past `stage` (an Imputer behind a Scaler, ...) are materialised first, and the program starts again on that buffer.
-  PrepVal prep_in(const NodeDef &n, size_t i, int stage) {
-    const Val *v = &get_raw(n, i);
-    if (v->is_const) unsupported(n, "expected row data, got a constant");
-    if (v->pv) {
-      bool clash = false;
-      for (const PrepCol &c : v->pv->cols) clash = clash || c.stage() >= stage;
-      if (!clash) return *v->pv;
-      v = &get(n, i);
-    }
-    if (v->padded()) unsupported(n, "the output of a Pad node can only feed a Conv");
-    PrepVal p = prep_identity(v->buf, 0, plan.buf_per_row[size_t(v->buf)], false, int_bufs.count(v->buf) > 0);
-    return p;
-  }
-  // the region value `name` becomes a buffer: the source itself, a SliceCols, or one Prep step
-  void materialize(const std::string &name, const NodeDef *at) {
-    Val &v = vals[name];
-    const std::shared_ptr<const PrepVal> keep = v.pv;
-    const PrepVal &p = *keep;
-    const std::vector<int64_t> shape = v.shape;
-    const int64_t F = int64_t(p.cols.size()), src_w = plan.buf_per_row[size_t(p.src)];
-    bool plain = true, contiguous = true;
-    for (int64_t j = 0; j < F; j++) {
-      plain = plain && p.cols[size_t(j)].plain();
-      contiguous = contiguous && p.cols[size_t(j)].src == p.cols[0].src + j;
-    }
-    Val r;
-    r.shape = shape;
-    if (plain && contiguous && p.cols[0].src == 0 && F == src_w) {  // the source as it is
-      r.buf = p.src;
-      v = r;
-      buf_names[r.buf].push_back(name);
-      alias_edges[r.buf]++;
-      return;
-    }
-    Step s;
-    s.in0 = p.src;
-    if (plain && contiguous) {
-      s.kind = StepKind::SliceCols;
-      s.col_off = p.cols[0].src;
-      s.K = F;
-    } else {
-      try {
-        s.prep = std::make_shared<const PrepPack>(pack_prep(p.cols, prep_tables, src_w));
-      } catch (const PrepError &e) {
-        if (at) unsupported(*at, std::string("preprocessing step: ") + e.what());
-        throw InferaError::onnx("output '" + name + "': preprocessing step: " + e.what());
-      }
-      s.kind = StepKind::Prep;
-    }
-    for (const auto &o : p.origin) s.origin += (s.origin.empty() ? "" : "+") + o;
-    if (s.origin.empty()) s.origin = "input:" + name;  // (only a graph input's columns as they are absorb no node)
-    r.buf = push_step(std::move(s), {shape[0], F});
-    bool all_int = true;
-    for (const PrepCol &c : p.cols) all_int = all_int && c.is_int;
-    if (all_int) int_bufs.insert(r.buf);
-    v = r;
-    buf_names[r.buf].push_back(name);
-  }
-
-  std::vector<int64_t> afe_indices(const NodeDef &n) {
-    const Val &ix = get_raw(n, 1);
-    if (!ix.is_const || ix.c->dtype != onnx::kInt64 || ix.c->i64.empty()) unsupported(n, "indices must be a constant int64 list");
-    return ix.c->i64;
-  }
-  // the inputs of n as they are (stage 5: nothing is materialised), their columns side by side in *out; false: an input reads another
-  // source than input 0
-  bool prep_side_by_side(const NodeDef &n, PrepVal *out) {
-    *out = prep_in(n, 0, 5);
-    for (size_t i = 1; i < n.inputs.size(); i++) {
-      const PrepVal q = prep_in(n, i, 5);
-      if (q.src != out->src) return false;
-      out->append(q);
-    }
-    out->add_origin(node_label(n));
-    return true;
-  }
-  // columns of region values with one source side by side (Concat / FeatureVectorizer); false: the sources differ
-  bool prep_concat(const NodeDef &n, std::vector<int64_t> out_shape) {
-    PrepVal out;
-    for (size_t i = 0; i < n.inputs.size(); i++) {
-      const Val &v = get_raw(n, i);
-      if (v.is_const || !v.pv) return false;
-      if (i && v.pv->src != out.src) return false;
-      if (!i) out.src = v.pv->src;
-    }
-    for (size_t i = 0; i < n.inputs.size(); i++) out.append(*get_raw(n, i).pv);
-    out.add_origin(node_label(n));
-    out_shape[1] = int64_t(out.cols.size()) / std::max<int64_t>(1, prod(out_shape, 2));
-    set_prep(n.outputs[0], std::move(out), out_shape);
-    return true;
-  }
-  void prep_node(const NodeDef &n) {
-    const std::string &op = n.op;
-    if (op == "Identity" || op == "Reshape" || op == "Flatten" || op == "Squeeze") return reshape_like(n);
-    if (op == "Cast") {
-      const Val &a = get_raw(n, 0);
-      const int64_t to = n.attr_i("to", onnx::kFloat);
-      if (!a.pv || !(to == onnx::kInt64 || to == onnx::kInt32)) return cast(n);  // (to float: an alias)
-      PrepVal p = *a.pv;
-      bool clash = false;  // a column that is not whole yet and went past the truncation stage: materialised first
-      for (const PrepCol &c : p.cols) clash = clash || (!c.is_int && c.stage() >= 1);
-      if (clash) p = prep_in(n, 0, 1);
-      for (PrepCol &c : p.cols)
-        if (!c.is_int) c.trunc = true, c.is_int = true;
-      p.add_origin(node_label(n));
-      return set_prep(n.outputs[0], std::move(p), a.shape);
-    }
-    if (op == "Concat") {
-      const Val &first = get_raw(n, 0);
-      const int64_t rank = int64_t(first.shape.size());
-      int64_t axis = n.attr_i("axis", 1);
-      if (axis < 0) axis += rank;
-      bool flat = axis >= 1 && axis < rank;  // a flat concatenation of rows: every axis between the row axis and `axis` has extent 1
-      std::vector<int64_t> out_shape = first.shape;
-      for (size_t i = 0; i < n.inputs.size() && flat; i++) {
-        const Val &v = get_raw(n, i);
-        flat = !v.is_const && int64_t(v.shape.size()) == rank;
-        for (int64_t d = 1; d < rank && flat; d++) flat = d == axis || v.shape[size_t(d)] == first.shape[size_t(d)];
-        for (int64_t d = 1; d < axis && flat; d++) flat = v.shape[size_t(d)] == 1;
-      }
-      if (flat && axis != 1) {  // [N, 1, a] ++ [N, 1, b] -> [N, 1, a + b]
-        int64_t total = 0;
-        for (size_t i = 0; i < n.inputs.size(); i++) total += get_raw(n, i).shape[size_t(axis)];
-        out_shape[size_t(axis)] = total;
-        PrepVal p;
-        if (!prep_side_by_side(n, &p)) unsupported(n, "a preprocessing Concat over the last axis reads one source");
-        return set_prep(n.outputs[0], std::move(p), out_shape);
-      }
-      if (axis == 1 && flat && prep_concat(n, out_shape)) return;
-      return concat(n);
-    }
-    if (op == "FeatureVectorizer") {
-      const std::vector<int64_t> *dims = n.attr_ints("inputdimensions");
-      if (!dims || dims->size() != n.inputs.size())
-        unsupported(n, "inputdimensions must hold one entry per input (" + std::to_string(n.inputs.size()) + ")");
-      int64_t total = 0;
-      for (size_t i = 0; i < n.inputs.size(); i++) {
-        const Val &v = get_raw(n, i);
-        if (v.is_const || v.shape.empty()) unsupported(n, "inputs must be row data");
-        const int64_t w = prod(v.shape, 1);
-        if ((*dims)[i] != w)
-          unsupported(n, "inputdimensions[" + std::to_string(i) + "] = " + std::to_string((*dims)[i]) + " but input '" + n.inputs[i] + "' has " +
-                             std::to_string(w) + " columns");
-        total += w;
-      }
-      const std::vector<int64_t> out_shape = {get_raw(n, 0).shape[0], total};
-      // (each input as [rows, width]; the sources differ: materialised and copied side by side)
-      const Val &v0 = get_raw(n, 0);
-      bool one_src = v0.pv != nullptr;
-      for (size_t i = 1; i < n.inputs.size() && one_src; i++) {
-        const Val &v = get_raw(n, i);
-        one_src = v.pv && v.pv->src == v0.pv->src;
-      }
-      PrepVal cat;
-      if (one_src && prep_side_by_side(n, &cat)) return set_prep(n.outputs[0], std::move(cat), out_shape);
-      std::vector<std::string> flat;
-      for (size_t i = 0; i < n.inputs.size(); i++) {
-        const Val &v = get(n, i);
-        const std::string f = n.outputs[0] + "\x01" + std::to_string(i);
-        Val a = v;
-        a.shape = {v.shape[0], prod(v.shape, 1)};
-        vals[f] = a;
-        uses[f] = 1;
-        flat.push_back(f);
-      }
-      NodeDef c = std_node(n, "Concat", flat, n.outputs[0]);
-      set_i(c, "axis", 1);
-      return concat(c);
-    }
-    // the per-column nodes: rows of [N, F] (LabelEncoder: any shape)
-    const Val &x = get_raw(n, 0);
-    const std::vector<int64_t> xshape = x.shape;
-    if (x.is_const) unsupported(n, "expected row data, got a constant");
-    if (op != "LabelEncoder" && xshape.size() != 2) unsupported(n, "only [rows, features] inputs");
-    const int64_t F = prod(xshape, 1);
-    PrepVal p;
-    std::vector<int64_t> out_shape = xshape;
-    if (op == "ArrayFeatureExtractor") {
-      const std::vector<int64_t> ix = afe_indices(n);
-      const PrepVal in = prep_in(n, 0, 5);
-      p.src = in.src;
-      p.origin = in.origin;
-      for (int64_t k : ix) {
-        if (k < 0) unsupported(n, "negative column index " + std::to_string(k));
-        if (k >= F) unsupported(n, "column index " + std::to_string(k) + " out of range for " + std::to_string(F) + " columns");
-        p.cols.push_back(in.cols[size_t(k)]);
-      }
-      out_shape = {xshape[0], int64_t(ix.size())};
-    } else if (op == "Imputer") {
-      ImputerSpec sp;
-      try {
-        sp = parse_imputer(n, F);
-      } catch (const PrepError &e) {
-        unsupported(n, e.what());
-      }
-      p = prep_in(n, 0, 2);
-      for (int64_t j = 0; j < F; j++) {
-        PrepCol &c = p.cols[size_t(j)];
-        c.impute = true;
-        c.imp_nan = std::isnan(sp.replaced);
-        c.repl = sp.replaced;
-        c.imp = sp.imputed[size_t(j)];
-        c.is_int = c.is_int && std::nearbyint(c.imp) == c.imp;
-      }
-    } else if (op == "Scaler") {
-      const std::vector<float> off = ml_floats(n, "offset", F, 0.f, true), sc = ml_floats(n, "scale", F, 1.f, true);
-      p = prep_in(n, 0, 3);
-      for (int64_t j = 0; j < F; j++) {
-        PrepCol &c = p.cols[size_t(j)];
-        c.affine = true;
-        c.off = off[size_t(j)];
-        c.scale = sc[size_t(j)];
-        c.is_int = false;
-      }
-    } else if (op == "Binarizer") {
-      const float thr = parse_binarizer(n);
-      p = prep_in(n, 0, 4);
-      for (PrepCol &c : p.cols) c.kind = kPrepBin, c.c = thr, c.is_int = true;
-    } else if (op == "OneHotEncoder") {
-      OneHotSpec sp;
-      try {
-        sp = parse_onehot(n);
-      } catch (const PrepError &e) {
-        unsupported(n, e.what());
-      }
-      const int64_t C = int64_t(sp.cats.size());
-      prep_cats += C;
-      if (prep_cats > kPrepMaxCats) unsupported(n, "more than " + std::to_string(kPrepMaxCats) + " one-hot categories in all");
-      if (F * C > kPrepMaxOut)
-        unsupported(n, std::to_string(F) + " x " + std::to_string(C) + " one-hot columns; a preprocessing step writes at most " + std::to_string(kPrepMaxOut));
-      int table = -1, strict = 0;
-      if (!sp.zeros) {
-        prep_tables.push_back(std::make_shared<PrepTable>(onehot_table(sp.cats)));
-        table = int(prep_tables.size()) - 1;
-        plan.prep_strict_nodes.push_back({"node '" + (n.name.empty() ? n.op : n.name) + "' (" + n.op + ")", ": a value is not in cats_int64s (zeros = 0)"});
-        strict = int(std::min<size_t>(plan.prep_strict_nodes.size(), size_t(kPrepMaxStrictIds)));
-      }
-      const PrepVal in = prep_in(n, 0, 4);
-      p.src = in.src;
-      p.origin = in.origin;
-      for (const PrepCol &base : in.cols)
-        for (int64_t k = 0; k < C; k++) {
-          PrepCol c = base;
-          c.kind = kPrepOneHot;
-          c.c = sp.cats[size_t(k)];
-          c.is_int = true;
-          if (k == 0) c.table = table, c.strict = strict;
-          p.cols.push_back(c);
-        }
-      out_shape = {xshape[0], F, C};
-    } else if (op == "LabelEncoder") {
-      bool int_values = false;
-      PrepTable t;
-      try {
-        t = parse_label_encoder(n, &int_values);
-      } catch (const PrepError &e) {
-        unsupported(n, e.what());
-      }
-      prep_keys += int64_t(t.keys.size()) + (t.has_nan ? 1 : 0);
-      if (prep_keys > kPrepMaxKeys) unsupported(n, "more than " + std::to_string(kPrepMaxKeys) + " LabelEncoder keys in all");
-      const float dflt = t.dflt;
-      prep_tables.push_back(std::make_shared<PrepTable>(std::move(t)));
-      p = prep_in(n, 0, 4);
-      for (PrepCol &c : p.cols) c.kind = kPrepLookup, c.c = dflt, c.table = int(prep_tables.size()) - 1, c.is_int = int_values;
-    } else {
-      unsupported(n, "unsupported operator");
-    }
-    p.add_origin(node_label(n));
-    set_prep(n.outputs[0], std::move(p), out_shape);
-  }
-
-  // a constant f32 tensor known before the walk: an initializer or a Constant node's value
-  std::shared_ptr<TensorData> const_tensor(const std::string &name) const {
-    const std::shared_ptr<TensorData> t = graph->constant(name).t;
-    return t && t->dtype == onnx::kFloat ? t : nullptr;
-  }
-  // g = -2 X C^T read by one node: the set (and its orientation) and the nodes of the chain
-  bool match_minus_two_dot(const std::string &g, const std::string &x, NearestMatch *mt) {
-    size_t gi = 0;
-    const NodeDef *p = graph->producer(g, &gi);
-    if (!p || !only_reader(g) || !p->domain.empty()) return false;
-    if (p->op == "Gemm") {
-      if (p->inputs.size() < 2 || p->inputs[0] != x || p->attr_i("transA", 0) != 0 || p->attr_f("alpha", 1.f) != -2.f) return false;
-      auto c = const_tensor(p->inputs[1]);
-      if (!c || c->dims.size() != 2) return false;
-      if (p->inputs.size() > 2 && !p->inputs[2].empty()) {
-        auto z = const_tensor(p->inputs[2]);
-        if (!z || std::any_of(z->f32.begin(), z->f32.end(), [](float v) { return v != 0.f; })) return false;
-      }
-      mt->c = c;
-      mt->c_fm = p->attr_i("transB", 0) == 0;
-      mt->spelling = "gemm";
-      mt->nodes.push_back(gi);
-      return true;
-    }
-    if (p->op != "Mul" || p->inputs.size() != 2) return false;
-    for (int side = 0; side < 2; side++) {
-      auto k = const_tensor(p->inputs[size_t(1 - side)]);
-      if (!k || k->f32.size() != 1 || k->f32[0] != -2.f) continue;
-      size_t mi = 0;
-      const NodeDef *mm = graph->producer(p->inputs[size_t(side)], &mi);
-      if (!mm || mm->op != "MatMul" || !mm->domain.empty() || mm->inputs.size() != 2 || mm->inputs[0] != x || !only_reader(mm->outputs[0])) return false;
-      auto c = const_tensor(mm->inputs[1]);
-      if (!c || c->dims.size() != 2) return false;
-      mt->c = c;
-      mt->c_fm = true;
-      mt->spelling = "matmul_mul";
-      mt->nodes.push_back(mi);
-      mt->nodes.push_back(gi);
-      return true;
-    }
-    return false;
-  }
-  void find_nearest() {
-    for (size_t i = 0; i < m.nodes.size(); i++) {
-      const NodeDef &rs = m.nodes[i];
-      if (!graph->live[i] || absorbed[i] || region[i] || rs.op != "ReduceSumSquare" || !rs.domain.empty() || rs.inputs.empty() || rs.attr_i("keepdims", 1) == 0) continue;
-      std::vector<int64_t> axes;
-      if (rs.inputs.size() > 1 && !rs.inputs[1].empty()) {
-        auto ci = m.initializers.find(rs.inputs[1]);
-        if (ci == m.initializers.end() || ci->second->dtype != onnx::kInt64) continue;
-        axes = ci->second->i64;
-      } else if (auto *p = rs.attr_ints("axes")) axes = *p;
-      if (axes.size() != 1 || (axes[0] != 1 && axes[0] != -1)) continue;
-      NearestMatch mt;
-      mt.x = rs.inputs[0];
-      const NodeDef *a1 = only_reader(rs.outputs[0]);
-      if (!a1 || a1->op != "Add" || !a1->domain.empty() || a1->inputs.size() != 2 || a1->inputs[0] == a1->inputs[1]) continue;
-      const std::string other = a1->inputs[a1->inputs[0] == rs.outputs[0] ? 1 : 0];
-      std::shared_ptr<TensorData> c2;
-      mt.nodes.push_back(i);
-      mt.nodes.push_back(size_t(a1 - m.nodes.data()));
-      if (match_minus_two_dot(other, mt.x, &mt)) {  // (rs + g) + C2
-        const NodeDef *a2 = only_reader(a1->outputs[0]);
-        if (!a2 || a2->op != "Add" || !a2->domain.empty() || a2->inputs.size() != 2) continue;
-        c2 = const_tensor(a2->inputs[a2->inputs[0] == a1->outputs[0] ? 1 : 0]);
-        mt.nodes.push_back(size_t(a2 - m.nodes.data()));
-        mt.d2 = a2->outputs[0];
-      } else {  // rs + (g + C2)
-        size_t bi = 0;
-        const NodeDef *b = graph->producer(other, &bi);
-        if (!b || b->op != "Add" || !b->domain.empty() || b->inputs.size() != 2 || !only_reader(other)) continue;
-        int gs = -1;
-        for (int side = 0; side < 2 && gs < 0; side++)
-          if ((c2 = const_tensor(b->inputs[size_t(1 - side)])) && match_minus_two_dot(b->inputs[size_t(side)], mt.x, &mt)) gs = side;
-        if (gs < 0) continue;
-        mt.nodes.push_back(bi);
-        mt.d2 = a1->outputs[0];
-      }
-      if (!c2 || !mt.c) continue;
-      const int64_t M = mt.c->dims[mt.c_fm ? 1 : 0], F = mt.c->dims[mt.c_fm ? 0 : 1];
-      if (M < 1 || F < 1 || int64_t(mt.c->f32.size()) != M * F || int64_t(c2->f32.size()) != M) continue;
-      if (!(c2->dims.size() == 1 || (c2->dims.size() == 2 && c2->dims[0] == 1))) continue;
-      bool norms = true;  // C2[m] = sum_f C[m, f]^2 within F 2^-23 of it
-      for (int64_t j = 0; j < M && norms; j++) {
-        double a = 0.0;
-        for (int64_t k = 0; k < F; k++) {
-          const double v = mt.c->f32[size_t(mt.c_fm ? k * M + j : j * F + k)];
-          a += v * v;
-        }
-        norms = std::fabs(double(c2->f32[size_t(j)]) - a) <= double(F) * std::ldexp(1.0, -23) * a;
-      }
-      if (!norms) continue;
-      std::sort(mt.nodes.begin(), mt.nodes.end());
-      bool fresh = true;
-      for (size_t q : mt.nodes) fresh = fresh && !absorbed[q] && !region[q] && !attn_at.count(q);
-      if (!fresh) continue;
-      for (size_t q : mt.nodes) absorbed[q] = 1;
-      nearest_at[mt.nodes.back()] = std::move(mt);
-    }
-  }
-  // the pending value of a recognised set; a form the kernel does not take (a time-major, half or quantised X, another width) returns false
-  bool bind_nearest(const NodeDef &anchor, const std::string &x_name, const std::string &out, const float *C, int64_t M, int64_t F, const std::string &spelling,
-                    bool rooted, const std::string &origin) {
-    const Val *xp = find_value(x_name);
-    if (!xp) unsupported(anchor, "input '" + x_name + "' is not produced by any earlier node");
-    if (xp->pv) materialize(x_name, &anchor);
-    if (xp->nn) materialize_nearest(x_name);
-    const Val x = *find_value(x_name);
-    if (x.is_const || x.q || x.half || x.ra != 0 || x.padded() || x.shape.size() != 2 || x.shape[1] != F) return false;
-    auto np = std::make_shared<NearestPending>();
-    try {
-      np->pack = std::make_shared<const NearestPack>(pack_nearest(C, M, F, spelling));
-    } catch (const NearestError &e) {
-      unsupported(anchor, e.what());
-    }
-    np->in_buf = x.buf;
-    np->rows = x.shape[0];
-    np->rooted = rooted;
-    np->origin = origin;
-    Val v;
-    v.nn = np;
-    v.shape = {x.shape[0], M};
-    vals[out] = v;
-    return true;
-  }
-  void lower_nearest(const NearestMatch &mt) {
-    const NodeDef &anchor = m.nodes[mt.nodes.back()];
-    const int64_t M = mt.c->dims[mt.c_fm ? 1 : 0], F = mt.c->dims[mt.c_fm ? 0 : 1];
-    std::vector<float> c(size_t(M * F));
-    for (int64_t j = 0; j < M; j++)
-      for (int64_t k = 0; k < F; k++) c[size_t(j * F + k)] = mt.c->f32[size_t(mt.c_fm ? k * M + j : j * F + k)];
-    if (bind_nearest(anchor, mt.x, mt.d2, c.data(), M, F, mt.spelling, false, node_label(m.nodes[mt.nodes.front()]) + "+...+" + node_label(anchor))) return;
-    for (size_t q : mt.nodes) lower_typed(m.nodes[q], [&] { lower_node(m.nodes[q]); });  // not the kernel's form: operator by operator
-  }
-  static void set_f(NodeDef &d, const char *k, float v) {
-    onnx::Attribute a;
-    a.name = k;
-    a.type = 1;
-    a.f = v;
-    d.attrs[k] = a;
-  }
-  // com.microsoft CDist(X, C, metric): the distances in one node (what skl2onnx writes for neighbour models under optim = 'cdist')
-  void cdist(const NodeDef &n) {
-    const std::string metric = n.attr_s("metric", "sqeuclidean");
-    if (metric != "sqeuclidean" && metric != "euclidean") bad_form(n, "metric '" + metric + "' (only sqeuclidean and euclidean)");
-    if (n.inputs.size() != 2) bad_form(n, "needs the two inputs X and the reference set");
-    const Val &cv = get(n, 1);
-    if (!cv.is_const || cv.c->dtype != onnx::kFloat || cv.shape.size() != 2) bad_form(n, "the reference set must be a constant f32 [M, F] matrix");
-    const int64_t M = cv.shape[0], F = cv.shape[1];
-    const bool rooted = metric == "euclidean";
-    const std::shared_ptr<TensorData> ct = cv.c;
-    if (int64_t(ct->f32.size()) != M * F || M < 1 || F < 1) bad_form(n, "the reference set " + shape_str(cv.shape) + " does not match its data");
-    const Val &x0 = get(n, 0);
-    if (x0.is_const || x0.shape.size() != 2 || x0.shape[1] != F) bad_form(n, "X must be a [rows, " + std::to_string(F) + "] activation, got " + shape_str(x0.shape));
-    if (nearest_enabled && bind_nearest(n, n.inputs[0], n.outputs[0], ct->f32.data(), M, F, "cdist", rooted, node_label(n))) return;
-    try {
-      (void)pack_nearest(ct->f32.data(), M, F, "cdist");  // (the caps hold for either lowering)
-    } catch (const NearestError &e) {
-      unsupported(n, e.what());
-    }
-    // operator by operator: |x|^2 - 2 x . C^T + |c|^2 [, Sqrt]
-    const std::string tmp = n.outputs[0] + "\x01";
-    std::vector<float> c2(static_cast<size_t>(M));
-    for (int64_t j = 0; j < M; j++) {
-      double a = 0.0;
-      for (int64_t k = 0; k < F; k++) a += double(ct->f32[size_t(j * F + k)]) * double(ct->f32[size_t(j * F + k)]);
-      c2[size_t(j)] = float(a);
-    }
-    vals[tmp + "c2"] = const_f32(std::move(c2), {M});
-    vals[tmp + "axes"] = const_i64({1}, {1});
-    for (const char *t : {"rs", "g", "z", "d2"}) uses[tmp + t] = 1;
-    NodeDef rs = std_node(n, "ReduceSumSquare", {n.inputs[0], tmp + "axes"}, tmp + "rs");
-    set_i(rs, "keepdims", 1);
-    lower_node(rs);
-    NodeDef g = std_node(n, "Gemm", {n.inputs[0], n.inputs[1]}, tmp + "g");
-    set_f(g, "alpha", -2.f);
-    set_i(g, "transB", 1);
-    lower_node(g);
-    lower_node(std_node(n, "Add", {tmp + "rs", tmp + "g"}, tmp + "z"));
-    lower_node(std_node(n, "Add", {tmp + "z", tmp + "c2"}, rooted ? tmp + "d2" : n.outputs[0]));
-    if (rooted) lower_node(std_node(n, "Sqrt", {tmp + "d2"}, n.outputs[0]));
-  }
-  // the [rows, M] matrix of a pending distance value, for a reader that takes it as it is
-  void materialize_nearest(const std::string &name) {
-    Val &v = vals.at(name);
-    const std::shared_ptr<NearestPending> np = v.nn;
-    Step s;
-    s.kind = StepKind::Nearest;
-    s.in0 = np->in_buf;
-    s.nearest = np->pack;
-    s.out_mode = np->rooted ? kNearestMatrixSqrt : kNearestMatrix;
-    s.origin = np->origin;
-    const std::vector<int64_t> shape = v.shape;
-    Val b;
-    b.buf = push_step(std::move(s), shape);
-    b.shape = shape;
-    vals[name] = b;
-    buf_names[b.buf].push_back(name);
-  }
-  // the best-k lists of a pending distance value (one Nearest step per k)
-  int nearest_lists(NearestPending &np, int64_t k) {
-    auto it = np.part_of_k.find(k);
-    if (it != np.part_of_k.end()) return it->second;
-    Step s;
-    s.kind = StepKind::Nearest;
-    s.in0 = np.in_buf;
-    s.nearest = np.pack;
-    s.M = k;
-    s.out_mode = kNearestSelect;
-    s.origin = np.origin;
-    return np.part_of_k[k] = push_step(std::move(s), {np.rows, np.pack->slices * 2 * nearest_list_width(k)});
-  }
-  // ArgMin / TopK / Sqrt / Identity reading a pending distance value: the Nearest step serves them itself.  false: not such a reader (or a form the
-  // selection does not take -- the matrix is computed and the operator runs on it)
-  bool nearest_reader(const NodeDef &n) {
-    if (n.inputs.empty()) return false;
-    auto it = vals.find(n.inputs[0]);
-    if (it == vals.end() || !it->second.nn) return false;
-    const Val d = it->second;
-    NearestPending &np = *d.nn;
-    if (n.op == "Identity") {  // the same pending value under another name
-      vals[n.outputs[0]] = d;
-      return true;
-    }
-    if (n.op == "Sqrt") {
-      if (np.rooted) return false;
-      auto r = std::make_shared<NearestPending>(np);
-      r->rooted = true;
-      r->origin += "+" + node_label(n);
-      r->part_of_k.clear();
-      Val v;
-      v.nn = r;
-      v.shape = d.shape;
-      vals[n.outputs[0]] = v;
-      return true;
-    }
-    if (n.op == "ArgMin") {
-      int64_t axis = n.attr_i("axis", 0);
-      if (axis < 0) axis += 2;
-      if (axis != 1 || n.attr_i("select_last_index", 0) != 0) return false;
-      Step s;
-      s.kind = StepKind::NearestReduce;
-      s.in0 = nearest_lists(np, 1);
-      s.nearest = np.pack;
-      s.M = 1;
-      s.out_mode = kNearestLabel;
-      s.origin = np.origin + "+" + node_label(n);
-      std::vector<int64_t> shape = {d.shape[0]};
-      if (n.attr_i("keepdims", 1) != 0) shape.push_back(1);
-      bind_output(n, 0, std::move(s), shape, true);
-      return true;
-    }
-    // TopK
-    int64_t axis = n.attr_i("axis", -1);
-    if (axis < 0) axis += 2;
-    const int64_t k = topk_k(n);
-    if (axis != 1 || n.attr_i("largest", 1) != 0 || k < 1 || k > kNearestMaxK || k > np.pack->M) return false;
-    for (size_t o = 0; o < 2; o++) {
-      if (!wanted(n, o)) continue;
-      Step s;
-      s.kind = StepKind::NearestReduce;
-      s.in0 = nearest_lists(np, k);
-      s.nearest = np.pack;
-      s.M = k;
-      s.out_mode = o == 1 ? kNearestIndices : np.rooted ? kNearestValuesSqrt : kNearestValues;
-      s.origin = np.origin + "+" + node_label(n);
-      bind_output(n, o, std::move(s), {d.shape[0], k}, o == 1);
-    }
-    return true;
-  }
-
-  // an integer constant known before the walk: an initializer or a Constant node
-  bool graph_const_ints(const std::string &name, std::vector<int64_t> *v, std::vector<int64_t> *dims) const {
-    const GraphIndex::Const c = graph->constant(name);
-    const TensorData *t = c.t.get();
-    if (!t) {
-      if (!c.node) return false;
-      if (auto *i = c.node->attr("value_int")) { *v = {i->i}; dims->clear(); return true; }
-      else if (auto *is = c.node->attr_ints("value_ints")) { *v = *is; *dims = {int64_t(is->size())}; return true; }
-      else return false;
-    }
-    if (t->dtype != onnx::kInt64) return false;
-    *v = t->i64;
-    *dims = t->dims;
-    return true;
-  }
-  // the integer list input `i` (or, in older opsets, attribute `attr`) of n; false: not constant
-  bool graph_ints_arg(const NodeDef &n, size_t i, const char *attr, std::vector<int64_t> *v) const {
-    v->clear();
-    std::vector<int64_t> dims;
-    if (has_input(n, i)) return graph_const_ints(n.inputs[i], v, &dims);
-    if (auto *p = n.attr_ints(attr)) *v = *p;
-    return true;
-  }
   // the columns an input of a multi-input model takes in the input buffer: k of [rows, k]; a rank-1 [rows] integer input is one column
-  static int64_t input_cols(const onnx::ValueDef &v) { return v.dims.size() == 1 ? 1 : v.dims[1]; }
-  // `v` as columns of the input buffer; "" or why it is none
-  std::string embed_cols(const std::string &v, EmbedCols *c, int depth = 0) const {
-    int64_t off = 0;
-    for (const auto &in : m.inputs) {
-      const int64_t w = m.inputs.size() == 1 ? (in.dims.size() == 2 ? in.dims[1] : 0) : input_cols(in);
-      if (in.name == v) {
-        const bool one_col = m.inputs.size() > 1 && in.dims.size() == 1;  // (a rank-1 integer input: run())
-        if (in.dims.size() != 2 && !one_col) return "indices of rank " + std::to_string(in.dims.size()) + " (graph input '" + v + "'); only [N] and [N, k]";
-        c->src0 = off, c->k = w, c->rank2 = !one_col;
-        c->int_input = in.elem_type == onnx::kInt64 || in.elem_type == onnx::kInt32;
-        return "";
-      }
-      off += w;
-    }
-    auto pi = graph->producer_of.find(v);
-    if (pi == graph->producer_of.end()) return "indices that are not computed from a graph input";
-    const NodeDef &p = m.nodes[pi->second];
-    const std::string by = "indices computed by " + p.op + (p.name.empty() ? "" : " '" + p.name + "'") +
-                           "; only columns of a graph input, picked by Gather(axis = 1) / Slice / Squeeze, Cast to an integer type, plus a constant integer offset";
-    if (depth > 64 || (!p.domain.empty() && p.domain != "ai.onnx") || p.inputs.empty()) return by;
-    auto narrow = [&](int64_t b, int64_t n) {
-      c->src0 += b;
-      if (!c->off.empty()) c->off = std::vector<int64_t>(c->off.begin() + b, c->off.begin() + b + n);
-      c->k = n;
-    };
-    std::string why;
-    if (p.op == "Cast" || p.op == "Identity") {
-      const int64_t to = p.attr_i("to", onnx::kFloat);
-      const bool to_int = p.op == "Cast" && (to == onnx::kInt64 || to == onnx::kInt32);
-      if (p.op == "Cast" && !to_int && to != onnx::kFloat && to != onnx::kDouble) return by;
-      if (!(why = embed_cols(p.inputs[0], c, depth + 1)).empty()) return why;
-      c->truncated = c->truncated || to_int;
-    } else if (p.op == "Flatten") {  // [N, k] stays [N, k]
-      const int64_t axis = p.attr_i("axis", 1);
-      if (!(why = embed_cols(p.inputs[0], c, depth + 1)).empty()) return why;
-      if (!c->rank2 || (axis != 1 && axis != -1)) return by;
-    } else if (p.op == "Gather") {
-      std::vector<int64_t> iv, idims;
-      if (p.inputs.size() != 2 || !graph_const_ints(p.inputs[1], &iv, &idims) || idims.size() > 1 || iv.empty()) return by;
-      if (!(why = embed_cols(p.inputs[0], c, depth + 1)).empty()) return why;
-      int64_t axis = p.attr_i("axis", 0);
-      if (!c->rank2 || (axis != 1 && axis != -1)) return by;
-      for (auto &i : iv)
-        if (i < 0) i += c->k;
-      for (size_t i = 1; i < iv.size(); i++)
-        if (iv[i] != iv[0] + int64_t(i)) return "index columns picked out of order; only a contiguous column range";
-      if (iv[0] < 0 || iv[0] + int64_t(iv.size()) > c->k) return "an index column out of range";
-      narrow(iv[0], int64_t(iv.size()));
-      if (idims.empty()) c->rank2 = false;
-    } else if (p.op == "Slice") {
-      std::vector<int64_t> st, en, ax, sp;
-      if (!graph_ints_arg(p, 1, "starts", &st) || !graph_ints_arg(p, 2, "ends", &en) || !graph_ints_arg(p, 3, "axes", &ax) || !graph_ints_arg(p, 4, "steps", &sp)) return by;
-      if (!(why = embed_cols(p.inputs[0], c, depth + 1)).empty()) return why;
-      if (!c->rank2 || st.size() != 1 || en.size() != 1 || ax.size() != 1 || (ax[0] != 1 && ax[0] != -1) || (!sp.empty() && sp[0] != 1)) return by;
-      int64_t b = st[0] < 0 ? st[0] + c->k : st[0], e = en[0] < 0 ? en[0] + c->k : en[0];
-      b = std::clamp<int64_t>(b, 0, c->k);
-      e = std::clamp<int64_t>(e, b, c->k);
-      if (e == b) return "an empty column range";
-      narrow(b, e - b);
-    } else if (p.op == "Squeeze" || p.op == "Unsqueeze") {
-      std::vector<int64_t> ax;
-      if (!graph_ints_arg(p, 1, "axes", &ax)) return by;
-      if (!(why = embed_cols(p.inputs[0], c, depth + 1)).empty()) return why;
-      const bool sq = p.op == "Squeeze";
-      if (c->rank2 != sq || c->k != 1 || ax.size() > 1 || (ax.empty() && !sq) || (!ax.empty() && ax[0] != 1 && ax[0] != -1)) return by;
-      c->rank2 = !sq;
-    } else if (p.op == "Add") {
-      std::vector<int64_t> ov, odims;
-      if (p.inputs.size() != 2) return by;
-      const bool left = graph_const_ints(p.inputs[0], &ov, &odims);
-      if (!left && !graph_const_ints(p.inputs[1], &ov, &odims)) return by;
-      if (!(why = embed_cols(p.inputs[left ? 1 : 0], c, depth + 1)).empty()) return why;
-      const bool shape_ok = odims.empty() || odims.size() == 1 || (odims.size() == 2 && odims[0] == 1);
-      if (!shape_ok || ov.empty() || (ov.size() != 1 && (!c->rank2 || int64_t(ov.size()) != c->k)))
-        return "an offset tensor " + shape_str(odims) + " added to " + std::to_string(c->k) + " index column" + (c->k == 1 ? "" : "s") + "; only a scalar, [k] or [1, k]";
-      if (c->off.empty()) c->off.assign(size_t(c->k), 0);
-      for (int64_t j = 0; j < c->k; j++) {
-        int64_t &o = c->off[size_t(j)];
-        if (__builtin_add_overflow(o, ov[ov.size() == 1 ? 0 : size_t(j)], &o) || o > kEmbedMaxV || o < -kEmbedMaxV)
-          return "an index offset beyond 2^24 (indices arrive as f32 values)";
-      }
-    } else {
-      return by;
-    }
-    c->chain.push_back(pi->second);
-    return "";
-  }
-
-  void find_embeds() {
-    const size_t N = m.nodes.size();
-    std::vector<EmbedLookup> found;
-    for (size_t i = 0; i < N; i++) {
-      const NodeDef &n = m.nodes[i];
-      if (!graph->live[i] || absorbed[i] || n.op != "Gather" || !graph->std_dom(n) || n.inputs.size() != 2 || n.outputs.empty() || !graph->row_data.count(n.inputs[1])) continue;
-      const std::shared_ptr<TensorData> t = graph->constant(n.inputs[0]).t;
-      if (!t) continue;  // (data that is no plain constant: Lowerer::gather says what it serves)
-      // from here on the node is an embedding lookup, served or refused in its own words
-      static const std::map<int, const char *> type_names = {{onnx::kFloat16, "float16"}, {onnx::kDouble, "float64"}, {onnx::kInt64, "int64"}, {onnx::kInt32, "int32"},
-                                                             {onnx::kInt8, "int8"}, {onnx::kUint8, "uint8"}};
-      const int elem = t->elem ? t->elem : t->dtype;
-      if (t->dtype != onnx::kFloat || elem != onnx::kFloat || t->q_data)
-        bad_form(n, std::string("a table of type ") + (type_names.count(elem) ? type_names.at(elem) : "other than f32") +
-                        "; only f32 tables are looked up (float16, integer and quantised tables are not)");
-      if (const std::string why = embed_table_refusal(t->dims); !why.empty()) bad_form(n, why);
-      int64_t axis = n.attr_i("axis", 0);
-      if (axis < 0) axis += int64_t(t->dims.size());
-      if (axis != 0) bad_form(n, "axis = " + std::to_string(n.attr_i("axis", 0)) + " of a constant table; a lookup takes whole rows (axis = 0)");
-      EmbedLookup L;
-      L.gather = i;
-      L.table = t;
-      L.V = t->dims[0];
-      L.d = t->dims.size() == 2 ? t->dims[1] : 1;
-      if (t->f32.size() != size_t(L.V) * size_t(L.d)) bad_form(n, "a table whose data disagrees with its dims " + shape_str(t->dims));
-      if (plan.input_declared_type == "float16") bad_form(n, "indices taken from a float16 graph input");
-      if (const std::string why = embed_cols(n.inputs[1], &L.ix); !why.empty()) bad_form(n, why);
-      L.out = n.outputs[0];
-      L.shape = {plan.input_shape[0]};
-      if (L.ix.rank2) L.shape.push_back(L.ix.k);
-      if (t->dims.size() == 2) L.shape.push_back(L.d);
-      // [N, k, d] -> [N, k * d] by the Flatten / Reshape that alone reads it
-      if (L.shape.size() == 3)
-        if (const NodeDef *r = only_reader(L.out); r && graph->std_dom(*r) && !r->outputs.empty() && r->inputs[0] == L.out) {
-          bool flat = r->op == "Flatten" && r->attr_i("axis", 1) == 1;
-          std::vector<int64_t> tgt, tdims;
-          if (r->op == "Reshape" && r->inputs.size() == 2 && graph_const_ints(r->inputs[1], &tgt, &tdims) && tgt.size() == 2)
-            flat = (tgt[0] == 0 || tgt[0] == -1 || (tgt[0] > 0 && tgt[0] == L.shape[0])) && (tgt[1] == L.ix.k * L.d || (tgt[1] == -1 && tgt[0] != -1));
-          if (flat) {
-            L.tail.push_back(size_t(r - m.nodes.data()));
-            L.out = r->outputs[0];
-            L.shape = {L.shape[0], L.ix.k * L.d};
-          }
-        }
-      // [N] (a rank-1 table by one index column) -> [N, 1] by the Unsqueeze(axis 1) that alone reads it: what a Concat wants
-      if (L.shape.size() == 1)
-        if (const NodeDef *r = only_reader(L.out); r && graph->std_dom(*r) && r->op == "Unsqueeze" && !r->outputs.empty() && r->inputs[0] == L.out) {
-          std::vector<int64_t> ax;
-          if (graph_ints_arg(*r, 1, "axes", &ax) && ax.size() == 1 && (ax[0] == 1 || ax[0] == -1)) {
-            L.tail.push_back(size_t(r - m.nodes.data()));
-            L.out = r->outputs[0];
-            L.shape = {L.shape[0], 1};
-          }
-        }
-      found.push_back(std::move(L));
-    }
-    if (found.empty()) return;
-    // A feature-axis Concat that reads lookups is one step: its lookups and the numeric columns of a graph input among its inputs are pieces,
-    // and an input that another step computes (a Scaler on the numeric columns, a Relu of a lookup) is a gap that one CopyCols behind the
-    // step fills.  A lookup is looked up again by every such Concat that reads it -- that costs nothing -- and is a step of its own only
-    // where something else reads it too.
-    const std::set<std::string> &graph_outs = graph->graph_outs;
-    std::set<size_t> concats;
-    for (size_t li = 0; li < found.size(); li++) {
-      if (found[li].shape.size() != 2) continue;
-      auto it = graph->consumers_of.find(found[li].out);
-      if (it == graph->consumers_of.end()) continue;
-      for (size_t c : it->second) {
-        const NodeDef &r = m.nodes[c];
-        if (r.op == "Concat" && graph->std_dom(r) && !r.outputs.empty() && !absorbed[c] && (r.attr_i("axis", 1) == 1 || r.attr_i("axis", 1) == -1)) concats.insert(c);
-      }
-    }
-    for (size_t ci : concats) {
-      const NodeDef &cn = m.nodes[ci];
-      EmbedGroup g;
-      std::map<size_t, int> slot;  // lookup -> its place in g.lookups
-      for (size_t i = 0; i < cn.inputs.size(); i++) {
-        const std::string &in = cn.inputs[i];
-        size_t li = SIZE_MAX;
-        for (size_t q = 0; q < found.size(); q++)
-          if (found[q].shape.size() == 2 && found[q].out == in) li = q;
-        if (li != SIZE_MAX) {
-          if (!slot.count(li)) {
-            slot[li] = int(g.lookups.size());
-            g.lookups.push_back(found[li]);
-          }
-          g.parts.push_back({slot[li], EmbedCols()});
-          continue;
-        }
-        EmbedCols c;
-        if (embed_cols(in, &c).empty() && c.rank2 && c.off.empty() && !c.truncated && !c.int_input) {
-          g.parts.push_back({-1, std::move(c)});
-        } else {
-          EmbedCols gap;
-          gap.src0 = int64_t(i);  // (a gap: the Concat's input i, whatever computes it)
-          g.parts.push_back({-2, std::move(gap)});
-        }
-      }
-      embed_at[ci] = std::move(g);
-    }
-    for (size_t li = 0; li < found.size(); li++) {
-      bool own = graph_outs.count(found[li].out) > 0;
-      auto it = graph->consumers_of.find(found[li].out);
-      if (it == graph->consumers_of.end() || it->second.empty()) own = true;
-      else
-        for (size_t c : it->second) own = own || !concats.count(c);
-      if (!own) continue;
-      EmbedGroup g;
-      g.lookups.push_back(found[li]);
-      g.parts.push_back({0, EmbedCols()});
-      embed_at[found[li].tail.empty() ? found[li].gather : found[li].tail.back()] = std::move(g);
-    }
-    // the nodes each step stands for: its lookups and their tails, its Concat, and every node of an index / column chain that nothing
-    // outside the steps reads (a chain node with another reader is lowered as before, for that reader)
-    std::vector<int> owner(N, -1);  // node -> anchor
-    std::set<size_t> chain_nodes;
-    for (auto &ag : embed_at) {
-      for (const EmbedLookup &L : ag.second.lookups) {
-        const size_t last = L.tail.empty() ? L.gather : L.tail.back();
-        const int who = embed_at.count(last) ? int(last) : int(ag.first);  // (a lookup that is also a step of its own is lowered there)
-        owner[L.gather] = who;
-        for (size_t t : L.tail) owner[t] = who;
-        chain_nodes.insert(L.ix.chain.begin(), L.ix.chain.end());
-      }
-      owner[ag.first] = int(ag.first);
-      for (const auto &p : ag.second.parts) chain_nodes.insert(p.second.chain.begin(), p.second.chain.end());
-    }
-    std::vector<char> gone(N, 0);
-    for (size_t i = N; i-- > 0;) {
-      if (!chain_nodes.count(i) || owner[i] >= 0) continue;
-      bool all = true;
-      for (const auto &o : m.nodes[i].outputs) {
-        all = all && !graph_outs.count(o);
-        if (auto it = graph->consumers_of.find(o); it != graph->consumers_of.end())
-          for (size_t c : it->second) all = all && (owner[c] >= 0 || gone[c]);
-      }
-      gone[i] = all;
-    }
-    for (auto &ag : embed_at) {
-      std::set<size_t> nodes;
-      for (const EmbedLookup &L : ag.second.lookups) {
-        nodes.insert(L.gather);
-        nodes.insert(L.tail.begin(), L.tail.end());
-        for (size_t c : L.ix.chain)
-          if (gone[c]) nodes.insert(c);
-      }
-      for (const auto &p : ag.second.parts)
-        for (size_t c : p.second.chain)
-          if (gone[c]) nodes.insert(c);
-      nodes.insert(ag.first);
-      ag.second.nodes.assign(nodes.begin(), nodes.end());
-    }
-    // the steps read the input buffer itself: what their nodes read counts no longer (a graph input nothing else reads gets no SliceCols)
-    for (size_t i = 0; i < N; i++) {
-      if (owner[i] < 0 && !gone[i]) continue;
-      std::set<size_t> kept;  // (a gap's value is still read: by the CopyCols that fills it)
-      if (auto ag = embed_at.find(i); ag != embed_at.end())
-        for (const auto &part : ag->second.parts)
-          if (part.first == -2) kept.insert(size_t(part.second.src0));
-      for (size_t k = 0; k < m.nodes[i].inputs.size(); k++)
-        if (!kept.count(k)) uses[m.nodes[i].inputs[k]]--;
-      region[i] = 0;
-      if (owner[i] != int(i)) absorbed[i] = 1;
-    }
-  }
-
-  void lower_embed(const EmbedGroup &g, const NodeDef &anchor) {
-    auto pack = std::make_shared<EmbedPack>();
-    pack->W = plan.buf_per_row[0];
-    std::map<const TensorData *, int> table_id;
-    int64_t out = 0;
-    struct Gap { int buf; int64_t out; size_t input; };
-    std::vector<Gap> gaps;  // the Concat inputs other steps compute: their buffer, first output column and place among the inputs
-    for (const auto &part : g.parts) {
-      if (part.first == -2) {
-        const Val &v = get(anchor, size_t(part.second.src0));
-        if (v.is_const) unsupported(anchor, "mixing constants and activations");
-        if (v.shape.size() != 2 || v.ra != 0 || v.shape[0] != plan.input_shape[0] || v.shape[1] <= 0 || v.half)
-          unsupported(anchor, "shape mismatch " + shape_str(v.shape) + " beside embedding lookups [rows, d]");
-        EmbedPiece q;
-        q.table = -2, q.d = v.shape[1], q.out = out;
-        gaps.push_back({v.buf, out, size_t(part.second.src0)});
-        out += q.d;
-        pack->pieces.push_back(q);
-        continue;
-      }
-      if (part.first < 0) {
-        EmbedPiece q;
-        q.src = part.second.src0, q.d = part.second.k, q.out = out;
-        out += q.d;
-        pack->pieces.push_back(q);
-        continue;
-      }
-      const EmbedLookup &L = g.lookups[size_t(part.first)];
-      const NodeDef &gn = m.nodes[L.gather];
-      if (!table_id.count(L.table.get())) {
-        table_id[L.table.get()] = int(pack->tables.size());
-        pack->tables.push_back(std::shared_ptr<const std::vector<float>>(L.table, &L.table->f32));
-        embed_elems += L.V * L.d;  // (every step packs and uploads its own copy, so a table counts once per step that reads it)
-        if (embed_elems > kEmbedMaxTableElems)
-          bad_form(gn, "the model's Embed steps hold more than 2^27 table elements (" + std::to_string(embed_elems) + "); 512 MiB is the cap");
-      }
-      if (!embed_node_id.count(L.gather)) {
-        plan.prep_strict_nodes.push_back({"node '" + (gn.name.empty() ? gn.op : gn.name) + "' (" + gn.op + ")",
-                                          ": an index is out of range for a table of " + std::to_string(L.V) + " rows"});
-        embed_node_id[L.gather] = int(plan.prep_strict_nodes.size());
-      }
-      for (int64_t j = 0; j < L.ix.k; j++) {
-        EmbedPiece q;
-        q.table = table_id[L.table.get()];
-        q.src = L.ix.src0 + j, q.V = L.V, q.d = L.d, q.out = out;
-        q.offset = L.ix.off.empty() ? 0 : L.ix.off[size_t(j)];
-        q.node = embed_node_id[L.gather];
-        out += q.d;
-        pack->pieces.push_back(q);
-      }
-    }
-    const NodeDef &first = m.nodes[g.lookups[0].gather];
-    if (const std::string why = pack_embed(*pack); !why.empty()) bad_form(first, why);
-    Step s;
-    s.kind = StepKind::Embed;
-    s.in0 = 0;
-    s.K = pack->W, s.M = pack->F;
-    for (size_t i : g.nodes) s.origin += (s.origin.empty() ? "" : "+") + node_label(m.nodes[i]);
-    std::vector<int64_t> shape = anchor.op == "Concat" ? std::vector<int64_t>{plan.input_shape[0], pack->F} : g.lookups[0].shape;
-    if (shape.size() == 3) {
-      pack->win_k = shape[1], pack->win_d = shape[2];
-      s.rep = shape[1];
-      s.embed = pack;
-      return emit_window(std::move(s), anchor, shape);
-    }
-    s.embed = pack;
-    const int out_buf = push_step(std::move(s), shape);
-    for (const Gap &gp : gaps) {  // the computed inputs, each into its columns
-      Step c;
-      c.kind = StepKind::CopyCols;
-      c.in0 = gp.buf;
-      c.out = out_buf;
-      c.col_off = gp.out;
-      c.origin = node_label(anchor) + "[" + std::to_string(gp.input) + "]";
-      plan.steps.push_back(std::move(c));
-      producer[out_buf] = int(plan.steps.size()) - 1;
-    }
-    set_act(anchor, out_buf, shape);
-  }
+  int64_t Lowerer::input_cols(const onnx::ValueDef &v) { return v.dims.size() == 1 ? 1 : v.dims[1]; }
 
   // lax: a Reshape whose target is computed (from Shape nodes) counts too; lower_interact evaluates it
-  bool interact_is_view(const NodeDef &r, const std::string &cur, InteractView *v, bool lax = false) const {
+  bool Lowerer::interact_is_view(const NodeDef &r, const std::string &cur, InteractView *v, bool lax) const {
     if (!graph->std_dom(r) || r.outputs.empty() || r.inputs.empty() || r.inputs[0] != cur) return false;
     v->target.clear();
     if (r.op == "Identity") return true;
@@ -5465,7 +3721,7 @@ struct Lowerer {
     return (graph_const_ints(r.inputs[1], &v->target, &dims) && !v->target.empty()) || (lax && !graph->row_data.count(r.inputs[1]));
   }
   // x * x or x ^ 2: the value squared ("" = n is no square)
-  std::string interact_squared(const NodeDef &n) const {
+  std::string Lowerer::interact_squared(const NodeDef &n) const {
     if (!graph->std_dom(n) || n.inputs.size() != 2) return "";
     if (n.op == "Mul" && n.inputs[0] == n.inputs[1]) return n.inputs[0];
     double e = 0;
@@ -5474,14 +3730,14 @@ struct Lowerer {
     return "";
   }
   // ReduceSum over exactly `axis_a` or `axis_b`
-  bool interact_sum_over(const NodeDef &n, int64_t axis_a, int64_t axis_b) const {
+  bool Lowerer::interact_sum_over(const NodeDef &n, int64_t axis_a, int64_t axis_b) const {
     std::vector<int64_t> ax;
     if (!graph->std_dom(n) || n.op != "ReduceSum" || n.inputs.empty() || n.attr_i("noop_with_empty_axes", 0) != 0 || !graph_ints_arg(n, 1, "axes", &ax)) return false;
     return ax.size() == 1 && (ax[0] == axis_a || ax[0] == axis_b);
   }
 
   // the node that alone reads the DATA of `v`: Shape nodes read its shape only and do not count (null: several, none, a graph output)
-  const NodeDef *interact_data_reader(const std::string &v) const {
+  const NodeDef *Lowerer::interact_data_reader(const std::string &v) const {
     auto it = graph->consumers_of.find(v);
     if (it == graph->consumers_of.end() || graph->graph_outs.count(v)) return nullptr;
     const NodeDef *one = nullptr;
@@ -5494,7 +3750,7 @@ struct Lowerer {
   }
   // The values the step absorbs exist nowhere: the Shape nodes that read them, and everything computed from those and constants alone (the
   // targets of the pattern's Reshapes, TorchScript's li * k + lj), must feed the pattern only.  They join im.nodes.  false: something else reads one
-  bool interact_shape_closure(InteractMatch &im, size_t anchor) const {
+  bool Lowerer::interact_shape_closure(InteractMatch &im, size_t anchor) const {
     std::set<size_t> mine(im.nodes.begin(), im.nodes.end());
     std::set<std::string> gone, derived;
     for (size_t i : im.nodes)
@@ -5532,8 +3788,7 @@ struct Lowerer {
   }
   // an integer tensor known at load once k is: constants, Shape of the product ([rows, k, k], rows = kInteractDyn), Gather / Concat /
   // Mul / Add / Sub and the shape-preserving operators over those.  false: something else
-  static constexpr int64_t kInteractDyn = INT64_MIN;
-  bool interact_eval(const std::string &v, const std::string &z, int64_t k, std::vector<int64_t> *out, int depth = 0) const {
+  bool Lowerer::interact_eval(const std::string &v, const std::string &z, int64_t k, std::vector<int64_t> *out, int depth) const {
     std::vector<int64_t> dims;
     if (graph_const_ints(v, out, &dims)) return true;
     const NodeDef *p = graph->producer(v);
@@ -5576,7 +3831,7 @@ struct Lowerer {
     return true;
   }
 
-  void find_interactions() {
+  void Lowerer::find_interactions() {
     const size_t N = m.nodes.size();
     auto claim = [&](const InteractMatch &im, size_t anchor) {
       for (size_t i : im.nodes) absorbed[i] = 1, region[i] = 0;
@@ -5743,7 +3998,7 @@ struct Lowerer {
   // bi-interaction of a window -- on [N, k] axis 1 is the last axis and the same operators are the FM term over scalar fields, which the
   // single-operator lowering serves (RowReduce, BinaryAct) -- so the claim is given up and the nodes lower as they always did.  (T . T^T
   // has no such reading: Transpose(0,2,1) needs rank 3.)
-  bool interact_released(const InteractMatch &im) const {
+  bool Lowerer::interact_released(const InteractMatch &im) const {
     if (im.mode != kInteractFm) return false;
     auto it = vals.find(im.T);
     if (it == vals.end()) return true;
@@ -5751,7 +4006,7 @@ struct Lowerer {
     return t.is_const || t.pv || t.nn || t.q || t.cl || t.padded() || t.half || t.buf < 0 || t.shape.size() != 3;
   }
 
-  void lower_interact(const InteractMatch &im, const NodeDef &anchor) {
+  void Lowerer::lower_interact(const InteractMatch &im, const NodeDef &anchor) {
     const NodeDef &pn = m.nodes[im.product];
     auto it = vals.find(im.T);
     if (it == vals.end()) unsupported(pn, "input '" + im.T + "' is not produced by any earlier node");
@@ -5933,7 +4188,7 @@ struct Lowerer {
     set_act(anchor, push_step(std::move(s), shape), shape);
   }
 
-  Plan run() {
+  Plan Lowerer::run() {
     graph = std::make_unique<const GraphIndex>(m, m.outputs[out_index].name);
     plan.opset = m.opset;
     const onnx::ValueDef &in = m.inputs[0];
@@ -6107,17 +4362,16 @@ struct Lowerer {
   }
   // A FakeQuant whose every reader was a quantised layer that rounds its input itself (two convolutions of a residual block reading one
   // tensor) is read by nothing: its step goes.  (One with a single such reader went when that reader was lowered, sole_tail.)
-  void drop_unread_fake_quants() {
+  void Lowerer::drop_unread_fake_quants() {
     std::set<int> read = {plan.out_buf};
     for (const Step &s : plan.steps)
       for (int b : {s.in0, s.in1, s.in2, s.in3}) read.insert(b);
     plan.steps.erase(std::remove_if(plan.steps.begin(), plan.steps.end(), [&](const Step &s) { return s.kind == StepKind::FakeQuant && !read.count(s.out); }),
                      plan.steps.end());
   }
-};
 
-}  // namespace
+}  // namespace lowering
 
-Plan lower_model(const onnx::Model &m, const std::string &output_select) { return Lowerer(m, output_select).run(); }
+Plan lower_model(const onnx::Model &m, const std::string &output_select) { return lowering::Lowerer(m, output_select).run(); }
 
 }  // namespace infera_hip

@@ -2,7 +2,7 @@
 
 tract-onnx serves these for the reference (engine.rs:49-56).  Its sources are not in /root/reference, so the three
 layers below are pinned on the ONNX-ML operator specification: a float64 numpy restatement written here, the C oracle
-(oracle/infera_oracle.c op_ml_*) and the product (lowering.cpp ml_node -> Dense / ArgMax / Softmax kernels).
+(oracle/infera_oracle.c op_ml_*) and the product (lower_ml.cpp ml_node -> Dense / ArgMax / Softmax kernels).
 """
 from __future__ import annotations
 
