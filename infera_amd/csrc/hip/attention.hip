@@ -33,6 +33,21 @@
 // the maximum; a 32-key tile whose word is 0 is skipped before its staging loads and a 16-key sub-tile whose half-word is 0 before its
 // MFMAs -- both branches are the same in every thread of the workgroup.  Otherwise (a bias fill, or a row that keeps no key) the fill goes
 // into the score and nothing is skipped.  The <DT, false> kernels are the code above, unchanged.
+//
+// The Attention operator (attention_kernel<DT, ROWMASK, FORM>; INTEGRATION.md 2.6 "The Attention operator").  FORM 0 is the
+// kernel described above, instruction for instruction what it was before the operator came (its two extra arguments stand at the end of
+// AttnArgs and are not read), so every model that loaded before returns the same bits at the same speed.  FORM 1: T queries against Tk
+// keys (Q rows are T * ldq apart, K / V rows Tk * ldk / Tk * ldv, the constant mask is [T, Tk]) and grouped heads: query head g reads the
+// K / V head g / G.  One workgroup still serves one query head: letting it serve the G heads of a group from one staged K / V tile was NOT
+// built, so there is no A/B for it; what grouping saves today is K / V traffic through the cache (tools/attention_op_time.py).
+// FORM 2 adds is_causal (key j counts for query i iff j <= i, top-left aligned): the workgroup's key loop ends at min(Tk, its last query
+// + 1) -- one bound for all its threads, so the barriers stay matched -- a wave leaves the sub-tile loop at the first 16-key sub-tile that
+// lies wholly above its last query (wave-uniform, no barrier inside that loop), and inside the diagonal tiles a key j > i gets the score
+// -inf before the maximum, after any row-mask fill: exactly what a constant -inf mask entry gets.  A tile that is not visited contributes
+// corr = 1, p = 0, so for finite inputs the result has the bits of the constant [T, T] causal mask through FORM 0 (tests/
+// test_attention_op_gpu.py; the sign of an accumulator that underflowed to -0 is the one thing a visited all-masked tile would change).
+// A NaN in K / V at step j reaches the queries i >= j as the definition says; a query i < j sees it (0 . NaN) only where its wave visited
+// the key's tile.  The row-mask bitmap, its tile skipping and the causal bounds compose; no LDS beyond what ROWMASK has, no spills.
 #include "device_common.hpp"
 
 #include <cstdlib>
@@ -60,21 +75,35 @@ struct AttnArgs {
   float rm_cmp, rm_fill;
   int rm_mode;
   bool rm_excl, rm_int, rm_skip;
+  // the operator form (FORM > 0; INTEGRATION.md 2.6 "The Attention operator"): T queries against Tk keys, query head g reads K / V head
+  // g / G (G = query heads per K / V head).  FORM 0 reads neither: Tk = T, G = 1
+  int Tk, G;
 };
 
-template <int DT, bool ROWMASK>
+// FORM 0: the pattern form's kernel, as it was; 1: the operator with Tk != T or grouped heads; 2: the operator under is_causal
+template <int DT, bool ROWMASK, int FORM>
 __global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs a) {
   constexpr int DP = DT * 16, LS = DP + 4, QPR = DP / 4;
+  constexpr bool CAUSAL = FORM == 2;
   __shared__ __attribute__((aligned(16))) float ks[kAttnKeyTile * LS];
   __shared__ __attribute__((aligned(16))) float vs[kAttnKeyTile * LS];
   __shared__ unsigned kept[ROWMASK ? kAttnMaxT / 32 : 1];  // ROWMASK: bit (j & 31) of word j / 32 = key j is kept
   const int tid = int(threadIdx.x), nth = int(blockDim.x), nw = nth >> 6, wave = tid >> 6, lane = tid & 63, n = lane & 15, kq = lane >> 4;
   const int64_t row = int64_t(blockIdx.x) / a.H;
-  const int head = int(int64_t(blockIdx.x) - row * a.H), T = a.T, dh = a.dh;
+  const int head = int(int64_t(blockIdx.x) - row * a.H), T = a.T, Tk = FORM ? a.Tk : a.T, dh = a.dh;
   const int qi = (int(blockIdx.y) * nw + wave) * 16 + n;
   const float *qp = a.q + row * T * a.ldq + a.offq + head * dh;
-  const float *kp = a.k + row * T * a.ldk + a.offk + head * dh;
-  const float *vp = a.v + row * T * a.ldv + a.offv + head * dh;
+  const int kv_head = FORM ? head / a.G : head;
+  const float *kp = a.k + row * Tk * a.ldk + a.offk + kv_head * dh;
+  const float *vp = a.v + row * Tk * a.ldv + a.offv + kv_head * dh;
+  // CAUSAL: key j counts for query i iff j <= i.  No query of the workgroup reads a key beyond its last query (the same bound in every
+  // thread), and a wave visits no 16-key sub-tile that lies wholly above its own last query
+  int kend = Tk;
+  if constexpr (CAUSAL) {
+    const int wg_last = (int(blockIdx.y) + 1) * nw * 16 < T ? (int(blockIdx.y) + 1) * nw * 16 : T;  // one past the workgroup's last query
+    kend = wg_last < Tk ? wg_last : Tk;
+  }
+  [[maybe_unused]] const int wave_last = (int(blockIdx.y) * nw + wave) * 16 + 15;
 
   // up to four consecutive head columns of one step: zero beyond dh
   auto load4 = [&](const float *p, int d) -> f32x4 {
@@ -103,10 +132,10 @@ __global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs 
   bool excl = false, skip = false;
   if constexpr (ROWMASK) {
     const float *mp = a.rm + row * a.rm_ld + a.rm_off;
-    for (int base = wave * 64; base < T; base += nw * 64) {
+    for (int base = wave * 64; base < Tk; base += nw * 64) {
       const int key = base + lane;
       bool kp = false;
-      if (key < T) {
+      if (key < Tk) {
         const float mv = mp[key];
         kp = (a.rm_int ? truncf(mv) : mv) != a.rm_cmp;  // (a NaN is unequal: kept)
       }
@@ -118,12 +147,12 @@ __global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs 
     }
     __syncthreads();
     unsigned any = 0;
-    for (int w = 0; w < (T + 31) >> 5; w++) any |= kept[w];
+    for (int w = 0; w < (Tk + 31) >> 5; w++) any |= kept[w];
     excl = a.rm_excl && any != 0;
     skip = excl && a.rm_skip;
   }
 
-  for (int k0 = 0; k0 < T; k0 += kAttnKeyTile) {
+  for (int k0 = 0; k0 < kend; k0 += kAttnKeyTile) {
     unsigned kw = 0xffffffffu;
     if constexpr (ROWMASK) {
       kw = kept[k0 >> 5];
@@ -133,7 +162,7 @@ __global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs 
     for (int e = tid; e < kAttnKeyTile * QPR; e += nth) {
       const int key = e / QPR, d = (e - key * QPR) * 4;
       f32x4 kk = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-      bool in = k0 + key < T;
+      bool in = k0 + key < Tk;
       if constexpr (ROWMASK) in = in && (!excl || ((kw >> key) & 1u));  // an excluded key is never read
       if (in) {
         kk = load4(kp + int64_t(k0 + key) * a.ldk, d);
@@ -145,7 +174,9 @@ __global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs 
     __syncthreads();
 #pragma unroll
     for (int sub = 0; sub < kAttnKeyTile / 16; sub++) {
-      if (k0 + 16 * sub >= T) break;
+      if (k0 + 16 * sub >= Tk) break;
+      if constexpr (CAUSAL)
+        if (k0 + 16 * sub > wave_last) break;  // (the same in every lane of the wave; no barrier inside this loop)
       if constexpr (ROWMASK)
         if (skip && ((kw >> (16 * sub)) & 0xffffu) == 0) continue;
       f32x4 s = {0.f, 0.f, 0.f, 0.f};
@@ -160,11 +191,13 @@ __global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs 
       for (int i = 0; i < 4; i++) {
         const int key = k0 + 16 * sub + 4 * kq + i;
         sc[i] = -INFINITY;
-        if (key < T) {
+        if (key < Tk) {
           sc[i] = s[i] * a.scale;
-          if (a.mask && qi < T) sc[i] += a.mask[int64_t(qi) * T + key];
+          if (a.mask && qi < T) sc[i] += a.mask[int64_t(qi) * Tk + key];
           if constexpr (ROWMASK)
             if (!((kw >> (16 * sub + 4 * kq + i)) & 1u)) sc[i] = excl ? -INFINITY : a.rm_mode == kRowMaskAdd ? sc[i] + a.rm_fill : a.rm_fill;
+          if constexpr (CAUSAL)
+            if (key > qi) sc[i] = -INFINITY;  // (what a constant -inf mask entry gives)
         }
         mx = fmaxf(mx, sc[i]);
       }
@@ -205,35 +238,45 @@ __global__ __launch_bounds__(kAttnMaxWaves * 64) void attention_kernel(AttnArgs 
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+template <int DT>
+void launch_attention(hipStream_t s, dim3 grid, dim3 block, const AttnArgs &a, bool rowmask, bool causal) {
+  const int form = causal ? 2 : a.Tk != a.T || a.G != 1 ? 1 : 0;
+  if (rowmask) {
+    if (form == 2) hipLaunchKernelGGL((attention_kernel<DT, true, 2>), grid, block, 0, s, a);
+    else if (form == 1) hipLaunchKernelGGL((attention_kernel<DT, true, 1>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((attention_kernel<DT, true, 0>), grid, block, 0, s, a);
+  } else {
+    if (form == 2) hipLaunchKernelGGL((attention_kernel<DT, false, 2>), grid, block, 0, s, a);
+    else if (form == 1) hipLaunchKernelGGL((attention_kernel<DT, false, 1>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((attention_kernel<DT, false, 0>), grid, block, 0, s, a);
+  }
+}
+
 }  // namespace
 
 bool attention(hipStream_t s, const float *q, const float *k, const float *v, const float *mask, float *y, int64_t rows, int T, int heads, int dh,
                const int64_t ld[3], const int64_t off[3], float scale, const float *rm, int64_t rm_ld, int rm_off, float rm_cmp, float rm_fill, int rm_mode,
-               bool rm_excl, bool rm_int) {
+               bool rm_excl, bool rm_int, int Tk, int kv_heads, bool causal) {
   if (rows <= 0) return true;
-  if (T < 1 || T > kAttnMaxT || dh < 1 || dh > kAttnMaxDh || heads < 1 || heads > kAttnMaxHeads || rows * heads > INT32_MAX) return false;
-  if (rm && (mask || rm_off < 0 || int64_t(rm_off) + T > rm_ld)) return false;
+  if (Tk <= 0) Tk = T;
+  if (kv_heads <= 0) kv_heads = heads;
+  if (T < 1 || T > kAttnMaxT || Tk > kAttnMaxT || dh < 1 || dh > kAttnMaxDh || heads < 1 || heads > kAttnMaxHeads || heads % kv_heads != 0 || rows * heads > INT32_MAX)
+    return false;
+  if (rm && (mask || rm_off < 0 || int64_t(rm_off) + Tk > rm_ld)) return false;
   // INFERA_ATTN_SKIP=0 (read once per process): wholly masked tiles are visited like the others, with zeros staged and -inf scores -- the
   // same results; the A/B of tools/padded_time.py
   static const bool skip_tiles = !(getenv("INFERA_ATTN_SKIP") && atoi(getenv("INFERA_ATTN_SKIP")) == 0);
   AttnArgs a{q, k, v, mask, y, T, heads, dh, int(ld[0]), int(ld[1]), int(ld[2]), int(off[0]), int(off[1]), int(off[2]), scale, false,
-             rm, rm_ld, rm_off, rm_cmp, rm_fill, rm_mode, rm_excl, rm_int, skip_tiles};
+             rm, rm_ld, rm_off, rm_cmp, rm_fill, rm_mode, rm_excl, rm_int, skip_tiles, Tk, heads / kv_heads};
   a.vec = dh % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v);
   for (int i = 0; i < 3; i++) a.vec = a.vec && ld[i] % 4 == 0 && off[i] % 4 == 0;
   const int tiles = (T + 15) / 16, nw = tiles < kAttnMaxWaves ? tiles : kAttnMaxWaves;
   const dim3 grid(unsigned(rows * heads), unsigned((tiles + nw - 1) / nw)), block(unsigned(64 * nw));
   const int dt = (dh + 15) / 16;
-  if (rm) {
-    if (dt <= 1) hipLaunchKernelGGL((attention_kernel<1, true>), grid, block, 0, s, a);
-    else if (dt <= 2) hipLaunchKernelGGL((attention_kernel<2, true>), grid, block, 0, s, a);
-    else if (dt <= 4) hipLaunchKernelGGL((attention_kernel<4, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((attention_kernel<8, true>), grid, block, 0, s, a);
-    return true;
-  }
-  if (dt <= 1) hipLaunchKernelGGL((attention_kernel<1, false>), grid, block, 0, s, a);
-  else if (dt <= 2) hipLaunchKernelGGL((attention_kernel<2, false>), grid, block, 0, s, a);
-  else if (dt <= 4) hipLaunchKernelGGL((attention_kernel<4, false>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((attention_kernel<8, false>), grid, block, 0, s, a);
+  if (dt <= 1) launch_attention<1>(s, grid, block, a, rm != nullptr, causal);
+  else if (dt <= 2) launch_attention<2>(s, grid, block, a, rm != nullptr, causal);
+  else if (dt <= 4) launch_attention<4>(s, grid, block, a, rm != nullptr, causal);
+  else launch_attention<8>(s, grid, block, a, rm != nullptr, causal);
   return true;
 }
 

@@ -111,10 +111,14 @@ bool rnn(hipStream_t s, const float *x, const float *wr, const float *bias, cons
 // rm: null, or the buffer that holds the rows' own key masks ([rows, rm_ld]; no constant mask beside it): key j of a row is kept iff
 // rm[row, rm_off + j] (rm_int: truncated toward zero) != rm_cmp; a masked key is excluded like a key beyond T (rm_excl, in rows that keep a
 // key) or scored sc + rm_fill / rm_fill (rm_mode: RowMaskMode).
+// The operator form: Tk > 0: k / v are [rows, Tk, ld] and mask [T, Tk] (0: Tk = T); kv_heads > 0: query head g reads K / V head
+// g / (heads / kv_heads) (0: kv_heads = heads); causal: key j counts for query i iff j <= i, beside either mask.
 // false: a size is beyond the caps of host/attention.hpp (the lowering refuses those at load)
 bool attention(hipStream_t s, const float *q, const float *k, const float *v, const float *mask, float *y, int64_t rows, int T, int heads, int dh,
                const int64_t ld[3], const int64_t off[3], float scale, const float *rm = nullptr, int64_t rm_ld = 0, int rm_off = 0, float rm_cmp = 0.f,
-               float rm_fill = 0.f, int rm_mode = 0, bool rm_excl = false, bool rm_int = false);
+               float rm_fill = 0.f, int rm_mode = 0, bool rm_excl = false, bool rm_int = false, int Tk = 0, int kv_heads = 0, bool causal = false);
+// y = x / sqrtf(mean(x^2) + eps) * gamma over each of nvec vectors of E elements (RMSNormalization); false: E beyond the cap
+bool rmsnorm(hipStream_t s, const float *x, const float *gamma, float *y, int64_t nvec, int E, float eps);
 // y = (x - mean) / sqrt(var + eps) * gamma + beta over each of nvec vectors of E elements (beta may be null); false: E beyond the cap
 bool layernorm(hipStream_t s, const float *x, const float *gamma, const float *beta, float *y, int64_t nvec, int E, float eps);
 // y[r, e] = mean over t of x[r, t, e]

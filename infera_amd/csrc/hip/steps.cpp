@@ -494,10 +494,14 @@ void PassRunner::launch_plain(size_t i) {
       if (!kern::layernorm(stream, buf(x.in0), t.scale, t.shift, buf(x.out), nr * x.rep, int(x.K), x.ln_eps))
         throw InferaError::onnx("LayerNorm kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
       break;
+    case StepKind::RmsNorm:
+      if (!kern::rmsnorm(stream, buf(x.in0), t.scale, buf(x.out), nr * x.rep, int(x.K), x.ln_eps))
+        throw InferaError::onnx("RmsNorm kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+      break;
     case StepKind::Attention:
       if (!kern::attention(stream, buf(x.in0), buf(x.in1), buf(x.in2), t.cst, buf(x.out), nr, int(x.attn_T), int(x.attn_heads), int(x.attn_dh), x.attn_ld,
                            x.attn_off, x.attn_scale, x.in3 >= 0 ? buf(x.in3) : nullptr, x.in3 >= 0 ? p.buf_per_row[size_t(x.in3)] : 0, int(x.rm_off), x.rm_cmp,
-                           x.rm_fill, x.rm_mode, x.rm_excl, x.rm_int))
+                           x.rm_fill, x.rm_mode, x.rm_excl, x.rm_int, int(x.attn_Tk), int(x.attn_kv_heads), x.attn_causal))
         throw InferaError::onnx("attention kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
       break;
     // the other families: their pairs above
@@ -574,7 +578,7 @@ void upload_step(const Upload &up, size_t i) {
   }
   switch (s.kind) {
     case StepKind::Dense: case StepKind::Conv2d: case StepKind::AffineChannel: case StepKind::BinaryConst: case StepKind::LayerNorm:
-    case StepKind::Attention: return upload_plain(s, d.plain, up);
+    case StepKind::Attention: case StepKind::RmsNorm: return upload_plain(s, d.plain, up);
     case StepKind::QDense: return upload_qdense(s, d.quant, up);
     case StepKind::QConv2d: return upload_qconv(s, d.quant, up);
     case StepKind::HDense: return upload_hdense(s, d.half, up);

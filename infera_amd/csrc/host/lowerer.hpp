@@ -271,6 +271,10 @@ struct Lowerer {
     std::shared_ptr<RowMask> rm;
     const NodeDef *qk = nullptr;
     std::vector<size_t> nodes;
+    // the standard-domain Attention operator (lower_attention_op.cpp): `op` is the node (= qk: what refusals name); form3: Q, K, V are
+    // [N, T, h dh] values and the node is its own anchor, else each comes through a head split and the anchor is the merge Reshape
+    const NodeDef *op = nullptr;
+    bool form3 = false;
   };
   std::map<size_t, AttnMatch> attn_at;            // anchor node index -> the pattern it closes
   std::vector<char> absorbed;                // nodes inside a recognised pattern (attention, or the decomposed LayerNorm): they emit nothing
@@ -561,6 +565,11 @@ struct Lowerer {
   void lower_masked_mean(const MaskedMean &mm, const NodeDef &div);
   const Val *find_value(const std::string &name);
   void lower_attention(const AttnMatch &am, const NodeDef &anchor);
+
+  // ---- lower_attention_op.cpp: the opset-23 Attention and RMSNormalization operators ----
+  void find_attention_ops();
+  // RMSNormalization over the last axis of [rows, E] / [rows, T, E]: one RmsNorm step (hip/layernorm.hip)
+  void rms_norm(const NodeDef &n);
 
   // ---- lowering.cpp: quantised and float16 graphs ----
   QArgs quant_args(const NodeDef &n, size_t si, size_t zi, const char *what);

@@ -2830,7 +2830,8 @@ namespace lowering {
       int buf;
       int64_t N, T, E, ld, off;
     } vw[3];
-    int64_t heads = 0, dh = 0;
+    int64_t heads = 0, dh = 0, kv_heads = 0;
+    const NodeDef *op = am.op;  // the Attention operator (lower_attention_op.cpp); null: the pattern form
     for (int i = 0; i < 3; i++) {
       const AttnSide &sd = am.side[i];
       const Val *src = find_value(sd.src);
@@ -2867,6 +2868,15 @@ namespace lowering {
         v.off = b;
         v.E = e - b;
       }
+      if (op && am.form3) {  // the 3-D operands of the operator: the head counts are its attributes
+        const int64_t h = op->attr_i(i == 0 ? "q_num_heads" : "kv_num_heads", 0);
+        if (h < 1 || v.E % h != 0) bad("E = " + std::to_string(v.E) + " of " + names[i] + " is not divisible by " + (i == 0 ? "q_num_heads" : "kv_num_heads") + " = " + std::to_string(h));
+        if (i == 0) heads = h, dh = v.E / h;
+        else if (i == 1) kv_heads = h;
+        if (i == 1 && v.E / h != dh) bad("K has heads of " + std::to_string(v.E / h) + " columns, Q of " + std::to_string(dh));
+        if (i == 2 && v.E / h != dh) bad("v_head_size = " + std::to_string(v.E / h) + " differs from head_size = " + std::to_string(dh));
+        continue;
+      }
       // the head split [N, T, h, dh]
       const Val *sh = find_value(sd.shape);
       if (!sh || !sh->is_const || sh->c->dtype != onnx::kInt64) bad("the head split of " + std::string(names[i]) + " needs a constant target shape");
@@ -2889,17 +2899,28 @@ namespace lowering {
       if (h <= 0 || d <= 0 || v.E / h != d || v.E % h != 0)
         bad("E = " + std::to_string(v.E) + " is not divisible by h = " + std::to_string(tgt[2] > 0 ? tgt[2] : h) + " (head split " + shape_str(sh->c->i64) + ")");
       if (i == 0) heads = h, dh = d;
-      else if (h != heads || d != dh) bad(std::string(names[i]) + " is split into " + std::to_string(h) + " heads of " + std::to_string(d) + ", Q into " + std::to_string(heads) + " of " + std::to_string(dh));
+      else if (op) {
+        if (i == 2 && d != dh) bad("v_head_size = " + std::to_string(d) + " differs from head_size = " + std::to_string(dh));
+        if (d != dh) bad("K has heads of " + std::to_string(d) + " columns, Q of " + std::to_string(dh));
+        if (i == 1) kv_heads = h;
+        else if (h != kv_heads) bad("V has " + std::to_string(h) + " heads, K " + std::to_string(kv_heads));
+      } else if (h != heads || d != dh) bad(std::string(names[i]) + " is split into " + std::to_string(h) + " heads of " + std::to_string(d) + ", Q into " + std::to_string(heads) + " of " + std::to_string(dh));
     }
-    if (vw[1].T != vw[0].T || vw[2].T != vw[0].T)
+    if (op) {
+      if (vw[2].T != vw[1].T) bad("K and V have different window lengths (" + std::to_string(vw[1].T) + ", " + std::to_string(vw[2].T) + ")");
+      if (kv_heads < 1 || heads % kv_heads != 0)
+        bad("q_num_heads = " + std::to_string(heads) + " is no multiple of kv_num_heads = " + std::to_string(kv_heads));
+    } else if (vw[1].T != vw[0].T || vw[2].T != vw[0].T)
       bad("Q, K and V have different window lengths T (" + std::to_string(vw[0].T) + ", " + std::to_string(vw[1].T) + ", " + std::to_string(vw[2].T) +
           "): cross-attention is not supported");
-    const int64_t N = vw[0].N, T = vw[0].T, E = vw[0].E;
+    const int64_t N = vw[0].N, T = vw[0].T, E = vw[0].E, Tk = vw[1].T;  // (the pattern form: Tk = T)
+    const bool causal = op && op->attr_i("is_causal", 0) != 0;
+    if (Tk < 1 || Tk > kAttnMaxT) bad("Tk = " + std::to_string(Tk) + " is beyond the attention kernel's cap of " + std::to_string(kAttnMaxT) + " steps");
     if (T < 1 || T > kAttnMaxT) bad("T = " + std::to_string(T) + " is beyond the attention kernel's cap of " + std::to_string(kAttnMaxT) + " steps");
     if (dh > kAttnMaxDh) bad("dh = " + std::to_string(dh) + " is beyond the attention kernel's cap of " + std::to_string(kAttnMaxDh) + " columns per head");
     if (heads > kAttnMaxHeads) bad("h = " + std::to_string(heads) + " is beyond the attention kernel's cap of " + std::to_string(kAttnMaxHeads) + " heads");
     for (const View &v : vw)
-      if (v.ld * T > kMaxPerRow) bad("window too large");
+      if (v.ld * std::max(T, Tk) > kMaxPerRow) bad("window too large");
     // the scale: every constant scalar Mul / Div on Q, K^T and the scores, folded into one factor applied to the f32 scores
     double scale = 1.0;
     for (const AttnScale &sc : am.scales) {
@@ -2908,26 +2929,38 @@ namespace lowering {
         bad("the scale '" + sc.cst + "' must be one positive finite f32 constant");
       scale = sc.op == '*' ? scale * double(c->c->f32[0]) : scale / double(c->c->f32[0]);
     }
+    if (op) {  // ONE f32 factor on the f32 scores: the attribute, or 1 / sqrt(dh)
+      const float sc = op->attr("scale") ? op->attr_f("scale", 0.f) : float(1.0 / std::sqrt(double(dh)));
+      if (!(sc > 0.f) || !std::isfinite(sc)) bad("scale must be a positive finite f32 number");
+      scale = double(sc);
+    }
     if (!(float(scale) > 0.f) || !std::isfinite(float(scale))) bad("the folded scale is not a positive finite f32 number");
     Step s;
     s.kind = StepKind::Attention;
     if (!am.mask.empty()) {
       const Val *c = find_value(am.mask);
-      if (!c || !c->is_const || c->c->dtype != onnx::kFloat) bad("the attention mask '" + am.mask + "' must be an f32 constant");
+      const bool bool_mask = op && c && c->is_const && c->c->elem == onnx::kBool;  // true = kept: 0, false: -inf
+      if (!c || !c->is_const || (c->c->dtype != onnx::kFloat && !bool_mask)) bad("the attention mask '" + am.mask + "' must be an f32 " + (op ? "or bool " : "") + "constant");
+      std::vector<float> from_bool;
+      if (bool_mask)
+        for (int64_t b : c->c->i64) from_bool.push_back(b ? 0.f : -INFINITY);
+      const std::vector<float> &mvals = bool_mask ? from_bool : c->c->f32;
+      if (op && c->shape.size() > 2 && std::any_of(c->shape.begin(), c->shape.end() - 2, [](int64_t x) { return x != 1; }))
+        bad("the attention mask " + shape_str(c->shape) + " depends on the row or the head; only [Tq,Tk], [1,Tq,Tk] or [1,1,Tq,Tk]");
       std::vector<int64_t> d = c->shape;
       while (d.size() > 2 && d[0] == 1) d.erase(d.begin());
       while (d.size() < 2) d.insert(d.begin(), 1);
-      if (d.size() != 2 || (d[0] != 1 && d[0] != T) || (d[1] != 1 && d[1] != T) || int64_t(c->c->f32.size()) != d[0] * d[1])
-        bad("the attention mask " + shape_str(c->shape) + " does not broadcast to [T, T] = [" + std::to_string(T) + "," + std::to_string(T) +
+      if (d.size() != 2 || (d[0] != 1 && d[0] != T) || (d[1] != 1 && d[1] != Tk) || int64_t(mvals.size()) != d[0] * d[1])
+        bad("the attention mask " + shape_str(c->shape) + " does not broadcast to [T, T] = [" + std::to_string(T) + "," + std::to_string(Tk) +
             "] (a mask that depends on the row or the head is not supported)");
-      s.cst.resize(size_t(T * T));
+      s.cst.resize(size_t(T * Tk));
       for (int64_t q = 0; q < T; q++) {
         bool any = false;
-        for (int64_t k = 0; k < T; k++) {
-          const float mv = c->c->f32[size_t((d[0] == 1 ? 0 : q) * d[1] + (d[1] == 1 ? 0 : k))];
+        for (int64_t k = 0; k < Tk; k++) {
+          const float mv = mvals[size_t((d[0] == 1 ? 0 : q) * d[1] + (d[1] == 1 ? 0 : k))];
           if (std::isnan(mv) || mv == INFINITY) bad("the attention mask holds NaN or +inf");
-          any = any || mv != -INFINITY;
-          s.cst[size_t(q * T + k)] = mv;
+          any = any || (mv != -INFINITY && !(causal && k > q));
+          s.cst[size_t(q * Tk + k)] = mv;
         }
         if (!any) bad("row " + std::to_string(q) + " of the attention mask is -inf everywhere (a fully masked query has no softmax)");
       }
@@ -2937,12 +2970,12 @@ namespace lowering {
       const NodeDef &at = *r.at;
       if (!am.mask.empty()) bad_form(at, "a row mask and a constant mask on one attention (causal and padding masks together are not supported)");
       const std::vector<int64_t> &sh = r.shape;
-      if (sh.size() == 4 && sh[3] == T && (sh[1] != 1 || sh[2] != 1))
+      if (sh.size() == 4 && sh[3] == Tk && (sh[1] != 1 || sh[2] != 1))
         bad_form(at, "the mask " + shape_str(sh) + " depends on the head or the query; only one key mask per row, [N,1,1,T]");
       if (sh.size() != 4 || sh[1] != 1 || sh[2] != 1) bad_form(at, "the row mask meets the scores as " + shape_str(sh) + "; only [N,1,1,T]");
-      if (sh[3] != T) bad_form(at, "the row mask has T = " + std::to_string(sh[3]) + ", the attention T = " + std::to_string(T));
+      if (sh[3] != Tk) bad_form(at, "the row mask has T = " + std::to_string(sh[3]) + ", the attention T = " + std::to_string(Tk));
       if (plan.input_declared_type == "float16") bad_form(at, "a row mask taken from a float16 graph input");
-      if (r.src0 < 0 || r.src0 + T > plan.buf_per_row[0]) bad_form(at, "the row mask's columns lie outside the input");
+      if (r.src0 < 0 || r.src0 + Tk > plan.buf_per_row[0]) bad_form(at, "the row mask's columns lie outside the input");
       s.in3 = 0;
       s.rm_off = r.src0;
       s.rm_cmp = r.cmp;
@@ -2951,7 +2984,7 @@ namespace lowering {
       s.rm_int = r.is_int;
       s.rm_excl = r.fill <= kRowMaskExcludingFill;
     }
-    {  // the merge Reshape must give [N, T, E]
+    if (!(op && am.form3)) {  // the merge Reshape must give [N, T, E]
       const std::vector<int64_t> tgt = const_ints(anchor, 1, "shape");
       bool okm = tgt.size() == 3 && (tgt[0] == 0 || tgt[0] == -1 || (tgt[0] == N && N > 0)) && (tgt[1] == 0 || tgt[1] == T || tgt[1] == -1) &&
                  (tgt[2] == E || tgt[2] == -1) && !(tgt[0] == -1 && (tgt[1] == -1 || tgt[2] == -1)) && !(tgt[1] == -1 && tgt[2] == -1);
@@ -2961,6 +2994,7 @@ namespace lowering {
     s.attn_heads = heads;
     s.attn_dh = dh;
     s.attn_scale = float(scale);
+    if (op) s.attn_Tk = Tk, s.attn_kv_heads = kv_heads, s.attn_causal = causal;
     // Three window Dense projections of ONE value, each read by this pattern alone: merged into one Dense of width 3E, so the value is
     // read once and the kernel reads one packed [rows, T, 3E] buffer
     const std::set<size_t> mine(am.nodes.begin(), am.nodes.end());  // (another pattern over the same q, k, v must still find its buffers)
@@ -3019,7 +3053,7 @@ namespace lowering {
     s.in1 = vw[1].buf;
     s.in2 = vw[2].buf;
     for (int j = 0; j < 3; j++) s.attn_ld[j] = vw[j].ld, s.attn_off[j] = vw[j].off;
-    s.origin = node_label(qk) + "+...+" + node_label(anchor);
+    s.origin = &qk == &anchor ? node_label(qk) : node_label(qk) + "+...+" + node_label(anchor);
     emit_window(std::move(s), anchor, {N, T, E});
   }
 
@@ -3621,6 +3655,7 @@ namespace lowering {
     else if (op == "ArgMin") argmin(n);
     else if (op == "TopK") topk(n);
     else if (op == "LayerNormalization") layer_norm(n);
+    else if (op == "RMSNormalization") rms_norm(n);
     else if (op == "InstanceNormalization") instance_norm(n);
     else if (op == "GroupNormalization") group_norm(n);
     else if (op == "ArgMax") argmax(n);
@@ -4252,6 +4287,7 @@ namespace lowering {
     // preprocessing regions: their graph inputs start as identity columns over the input buffer (integer inputs truncated)
     const std::set<std::string> region_inputs = find_regions();
     find_interactions();
+    find_attention_ops();  // (before find_attention, whose tail absorbs the row-mask sub-graphs of every match)
     find_attention();
     if (nearest_enabled) find_nearest();
     find_group_norms();

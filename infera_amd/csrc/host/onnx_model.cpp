@@ -223,6 +223,18 @@ std::shared_ptr<TensorData> read_tensor(Wire w) {
       }
       break;
     }
+    case kBool:  // one byte per element in raw_data, one int32 per element in int32_data: widened to 0 / 1 (elem says it was a bool)
+      t->dtype = kInt64;
+      if (raw) {
+        if (rawlen != n) throw size_err();
+        t->i64.resize(n);
+        for (size_t i = 0; i < n; i++) t->i64[i] = raw[i] != 0;
+      } else {
+        if (idata.size() != n) throw size_err();
+        for (auto &v : idata) v = v != 0;
+        t->i64 = std::move(idata);
+      }
+      break;
     case kFloat16:  // two bytes per element in raw_data (little endian), one 16-bit pattern per element in int32_data; widened exactly
       t->dtype = kFloat;
       t->f32.resize(0);

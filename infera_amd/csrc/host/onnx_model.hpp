@@ -15,7 +15,7 @@
 
 namespace infera_hip::onnx {
 
-enum DataType : int { kFloat = 1, kUint8 = 2, kInt8 = 3, kInt32 = 6, kInt64 = 7, kFloat16 = 10, kDouble = 11 };
+enum DataType : int { kFloat = 1, kUint8 = 2, kInt8 = 3, kInt32 = 6, kInt64 = 7, kBool = 9, kFloat16 = 10, kDouble = 11 };
 
 // IEEE binary16 <-> binary32 on the host: widening is exact (subnormals, infinities, NaN); narrowing rounds to nearest, ties to even,
 // keeps subnormal halves, sends |x| >= 65520 to +-inf and a NaN to a quiet NaN of the same sign
@@ -57,7 +57,7 @@ inline float round_to_half(float x) { return half_to_float(float_to_half(x)); }
 
 struct TensorData {
   std::string name;
-  int dtype = 0;  // kFloat or kInt64 after decoding (uint8 / int8 / int32 widened, double narrowed, float16 widened exactly)
+  int dtype = 0;  // kFloat or kInt64 after decoding (uint8 / int8 / int32 / bool widened, double narrowed, float16 widened exactly)
   int elem = 0;   // the data_type as the file declares it (quantised graphs tell uint8, int8 and int32 apart; kFloat16: a half tensor, its f32 values are halves)
   std::vector<int64_t> dims;
   std::vector<float> f32;

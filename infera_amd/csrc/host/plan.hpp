@@ -59,7 +59,7 @@ enum class StepKind : int {
   Prep = 19,          // ai.onnx.ml preprocessing region: out[r, j] = column program j over in0[r, :] (host/prep.hpp, prep.hip)
   Recurrent = 20,     // ONNX LSTM / GRU / RNN over in0 [rows, T, F]: out = Y [rows, T, D, H] or the last state [rows, D, H] (RnnOut; RnnPack, rnn.hip)
   LayerNorm = 21,     // y = (x - mean) / sqrt(var + eps) * scale[K] + shift[K] over each of the `rep` vectors of K elements of a row (layernorm.hip)
-  Attention = 22,     // self-attention over the T steps of a row: out [rows, T, heads * dh] = softmax(attn_scale . Q K^T + mask) V per head (attention.hip)
+  Attention = 22,     // attention over the T steps of a row: out [rows, T, heads * dh] = softmax(attn_scale . Q K^T + mask) V per head; the Attention operator adds attn_Tk, attn_kv_heads, attn_causal (attention.hip)
   MeanTime = 23,      // out[r, e] = mean over t of in0[r, t, e]   (ReduceMean over the time axis of [rows, T = rep, K])
   FakeQuant = 24,     // y = (sat(rne(x / s) + zp) - zp) * s   (QuantizeLinear -> DequantizeLinear on an activation; Step::qx)
   QDense = 25,        // quantised MatMul / Gemm on the int8 matrix cores, f32 in and out (Step::qx, qy, qW ...; qdense.hip)
@@ -78,6 +78,7 @@ enum class StepKind : int {
   ChannelNorm = 39,   // LayerNorm over the C channels at each of the S pixels of in0 [rows, C, S] (NCHW or channel quads, never changed): y = act((x - mean) / sqrt(var + ln_eps) * scale[c] + shift[c]), shift may be empty; out_mode (set by the scheduler): 0 the register form, 1 the re-read form (host/channelnorm.hpp, channelnorm.hip)
   Embed = 40,         // out [rows, F] = pieces in output order: rows of constant tables chosen by index columns of in0 [rows, W] (truncated toward zero, + an offset) and runs of in0's columns as they are; a window [rows, k, d] when the pack says so (EmbedPack, host/embed.hpp, embed.hip)
   Interact = 41,      // feature interactions of in0 [rows, k, d] (rows first, flat): dot mode, out [rows, F] = chosen entries of T . T^T beside bit copies of columns of T; fm mode, out [rows, d] or [rows, 1] = h * ((sum_f T)^2 - sum_f T^2) (InteractPack, host/interact.hpp, interact.hip)
+  RmsNorm = 42,       // y = x / sqrt(mean(x^2) + ln_eps) * scale[K] over each of the `rep` vectors of K elements of a row (RMSNormalization; layernorm.hip)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
@@ -173,6 +174,11 @@ struct Step {
   int rm_mode = 0;
   bool rm_excl = false, rm_int = false;
   int64_t attn_T = 0, attn_heads = 0, attn_dh = 0, attn_ld[3] = {0, 0, 0}, attn_off[3] = {0, 0, 0};
+  // the Attention operator: attn_Tk keys per row (K / V are [rows, attn_Tk, ld], cst [attn_T, attn_Tk]; 0: attn_T),
+  // attn_kv_heads heads in K / V (query head g reads head g / (attn_heads / attn_kv_heads); 0: attn_heads), attn_causal: key j counts
+  // for query i iff j <= i
+  int64_t attn_Tk = 0, attn_kv_heads = 0;
+  bool attn_causal = false;
   float attn_scale = 1.f, ln_eps = 1e-5f;
   // FakeQuant: qx.  QDense: qx = how the f32 input is quantised, qy = how the result is (off: the step returns `real`, f32);
   // qW [K, M] = the weights as signed bytes (uint8 data shifted by 128), q_wzp[M] = their zero points shifted the same way, q_mult[M] =

@@ -56,6 +56,7 @@ def _s(field: int, s: str) -> bytes:
 
 
 UINT8, INT8, INT32 = 2, 3, 6
+BOOL = 9
 FLOAT16, BFLOAT16 = 10, 16
 _SMALL_INTS = {np.dtype(np.uint8): (UINT8, "u1"), np.dtype(np.int8): (INT8, "i1"), np.dtype(np.int32): (INT32, "<i4")}
 
@@ -72,6 +73,13 @@ def tensor(name: str, arr: np.ndarray, float_data: bool = False, int32_data: boo
             out += _ld(5, b"".join(_varint(int(v)) for v in arr.reshape(-1)))
         else:
             out += _ld(9, arr.astype(fmt).tobytes())
+        return out + _s(8, name)
+    if arr.dtype == np.bool_:  # one byte per element in raw_data, or one int32 each in int32_data
+        out += _vi(2, BOOL)
+        if int32_data:
+            out += _ld(5, b"".join(_varint(int(v)) for v in arr.reshape(-1)))
+        else:
+            out += _ld(9, arr.astype("u1").tobytes())
         return out + _s(8, name)
     if arr.dtype == np.float16:  # two bytes per element in raw_data, or one 16-bit pattern per element in int32_data
         out += _vi(2, FLOAT16)
@@ -4501,3 +4509,217 @@ def deepfm_reference(spec: dict, x_cat) -> dict:
     y1 = np.asarray(spec["first"], np.float64)[idx][:, :, 0].sum(axis=1, keepdims=True)
     fm = interact_fm_reference(T, None, True) * 0.5
     return {"T": T, "fm": fm, "output": y1 + fm + _mlp64(T.reshape(len(T), -1), spec["mlp"], False)}
+
+
+# ------------------------------------------------------------------------------------------
+# The opset-23 operators Attention and RMSNormalization, and a pre-norm decoder block over them
+# ------------------------------------------------------------------------------------------
+
+def attention_op_nodes(nodes: list, inits: list, p: str, q: str, k: str, v: str, Tq: int, Tk: int, hq: int, hkv: int, dh: int, form: str = "4d",
+                       causal: bool = False, mask=None, mask_value: str | None = None, scale: float | None = None, extra_attrs: Sequence[bytes] = (),
+                       extra_inputs: Sequence[str] = (), extra_outputs: Sequence[str] = ()) -> str:
+    """Appends one standard-domain Attention node '<p>attn' over q [N, Tq, hq dh], k, v [N, Tk, hkv dh] (names) and returns the name of its
+    [N, Tq, hq dh] result.  form "3d": the operands as they are, beside q_num_heads / kv_num_heads; "4d" (what torch's exporter writes): each
+    through Reshape [0, T, h, dh] -> Transpose(0,2,1,3), and Y back through Transpose(0,2,1,3) -> Reshape [0, Tq, hq dh].
+    mask: a constant attn_mask (float32 additive or bool, true = kept); mask_value: the name of a value computed in the graph instead;
+    scale: the attribute (None: left out, the operator's 1 / sqrt(dh)); extra_inputs follow attn_mask (past_key, past_value,
+    nonpad_kv_seqlen; "" = absent), extra_outputs follow Y."""
+    i64 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.int64)))  # noqa: E731
+    attrs = [attr_i("is_causal", 1)] if causal else []
+    if scale is not None:
+        attrs.append(attr_f("scale", scale))
+    ops = [q, k, v]
+    if form == "4d":
+        for j, (nm, T, h) in enumerate((("q", Tq, hq), ("k", Tk, hkv), ("v", Tk, hkv))):
+            i64(p + nm + "_split", [0, T, h, dh])
+            nodes += [node("Reshape", [ops[j], p + nm + "_split"], [p + nm + "4"], name=p + "split_" + nm),
+                      node("Transpose", [p + nm + "4"], [p + nm + "h"], [attr_ints("perm", [0, 2, 1, 3])], name=p + "tr_" + nm)]
+            ops[j] = p + nm + "h"
+    else:
+        attrs += [attr_i("q_num_heads", hq), attr_i("kv_num_heads", hkv)]
+    if mask is not None:
+        inits.append(tensor(p + "mask", np.asarray(mask)))
+        mask_value = p + "mask"
+    ins = ops + ([mask_value] if mask_value is not None else [""] if extra_inputs else []) + list(extra_inputs)
+    y = p + ("y4" if form == "4d" else "o")
+    nodes.append(node("Attention", ins, [y] + list(extra_outputs), list(attrs) + list(extra_attrs), name=p + "attn"))
+    if form == "4d":
+        i64(p + "merge", [0, Tq, hq * dh])
+        nodes += [node("Transpose", [y], [p + "ot"], [attr_ints("perm", [0, 2, 1, 3])], name=p + "tr_o"),
+                  node("Reshape", [p + "ot", p + "merge"], [p + "o"], name=p + "merge_heads")]
+    return p + "o"
+
+
+def bool_row_mask_value(nodes: list, inits: list, p: str, T: int, src: str = "M", kind: str = "cast", pad: int = 0, lift: str = "unsqueeze") -> str:
+    """Appends a per-row bool key mask [N, 1, 1, T], true = kept, from the [N, T] graph input src: kind "cast": Cast(to = BOOL) of HF's 0 / 1
+    attention_mask; "ids": Not(Equal(ids, pad)); "equal": Equal(ids, pad) alone (true = MASKED: refused); "float": Cast(to = FLOAT) (refused).
+    lift: "unsqueeze" (axes [1, 2]) or "reshape" ([-1, 1, 1, T])."""
+    i64 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.int64)))  # noqa: E731
+    if kind in ("cast", "float"):
+        nodes.append(node("Cast", [src], [p + "keep"], [attr_i("to", BOOL if kind == "cast" else FLOAT)], name=p + "cast"))
+    else:
+        i64(p + "pad", pad)
+        nodes.append(node("Equal", [src, p + "pad"], [p + ("eq" if kind == "ids" else "keep")], name=p + "equal"))
+        if kind == "ids":
+            nodes.append(node("Not", [p + "eq"], [p + "keep"], name=p + "not"))
+    if lift == "reshape":
+        i64(p + "s4", [-1, 1, 1, T])
+        nodes.append(node("Reshape", [p + "keep", p + "s4"], [p + "keep4"], name=p + "reshape"))
+    else:
+        i64(p + "a12", [1, 2])
+        nodes.append(node("Unsqueeze", [p + "keep", p + "a12"], [p + "keep4"], name=p + "unsqueeze"))
+    return p + "keep4"
+
+
+def attention_op_model(Tq: int, Tk: int, hq: int, hkv: int, dh: int, form: str = "4d", causal: bool = False, mask=None, row_mask: dict | None = None,
+                       scale: float | None = None, opset: int = 23, packed: bool = False, mask_type: int = INT64, **kw) -> bytes:
+    """The Attention operator alone over flat inputs Q [N, Tq hq dh], K, V [N, Tk hkv dh] (the call's columns in that order), each reshaped to
+    [N, T, E]; packed (Tq = Tk, hq = hkv): X [N, T 3E] -> Reshape -> Split on the last axis.  row_mask: the keyword arguments of
+    bool_row_mask_value, for one more input M [N, Tk] (mask_type) behind the others.  Output [N, Tq, hq dh].  kw: attention_op_nodes, and
+    graph_outputs: names of further graph outputs."""
+    nodes, inits = [], []
+    Eq, Ekv = hq * dh, hkv * dh
+    if packed:
+        assert Tq == Tk and hq == hkv
+        inits += [tensor("x_shape", np.asarray([-1, Tq, 3 * Eq], dtype=np.int64)), tensor("sp", np.asarray([Eq, Eq, Eq], dtype=np.int64))]
+        nodes += [node("Reshape", ["X", "x_shape"], ["X3"]), node("Split", ["X3", "sp"], ["q", "k", "v"], [attr_i("axis", 2)], name="split_qkv")]
+        ins = [value_info("X", ["N", Tq * 3 * Eq])]
+    else:
+        for nm, T, E in (("q", Tq, Eq), ("k", Tk, Ekv), ("v", Tk, Ekv)):
+            inits.append(tensor(nm + "_shape", np.asarray([-1, T, E], dtype=np.int64)))
+            nodes.append(node("Reshape", [nm.upper(), nm + "_shape"], [nm]))
+        ins = [value_info("Q", ["N", Tq * Eq]), value_info("K", ["N", Tk * Ekv]), value_info("V", ["N", Tk * Ekv])]
+    if row_mask is not None:
+        ins.append(value_info("M", ["N", Tk], mask_type))
+        kw["mask_value"] = bool_row_mask_value(nodes, inits, "rm_", Tk, **row_mask)
+    more_outputs = [value_info(o, ["N"]) for o in kw.pop("graph_outputs", ())]  # further graph outputs (never served: the first one is)
+    out = attention_op_nodes(nodes, inits, "a_", "q", "k", "v", Tq, Tk, hq, hkv, dh, form=form, causal=causal, mask=mask, scale=scale, **kw)
+    return model("attention_op", nodes, inits, ins, [value_info(out, ["N", Tq, Eq])] + more_outputs, opset=opset)
+
+
+def attention_op_reference(q, k, v, hq: int, hkv: int, scale: float | None = None, causal: bool = False, mask=None, keep=None) -> np.ndarray:
+    """float64 numpy restatement of the operator over q [N, Tq, hq dh], k, v [N, Tk, hkv dh]: query head g reads K / V head g // (hq // hkv);
+    causal: key j counts iff j <= i (top-left aligned); mask: additive [Tq, Tk] (broadcast) or bool, true = kept; keep: [N, Tk] bool per row."""
+    q, k, v = (np.asarray(a, dtype=np.float64) for a in (q, k, v))
+    N, Tq, Eq = q.shape
+    Tk, dh, g = k.shape[1], Eq // hq, hq // hkv
+    sp = lambda a, T, h: a.reshape(N, T, h, dh).transpose(0, 2, 1, 3)  # noqa: E731
+    kh, vh = (np.repeat(sp(a, Tk, hkv), g, axis=1) for a in (k, v))
+    with np.errstate(all="ignore"):
+        s = sp(q, Tq, hq) @ kh.transpose(0, 1, 3, 2) * ((1.0 / math.sqrt(dh)) if scale is None else float(np.float32(scale)))
+        if mask is not None:
+            mk = np.asarray(mask)
+            mk = np.where(mk, 0.0, -np.inf) if mk.dtype == np.bool_ else mk.astype(np.float64)
+            s = s + np.broadcast_to(mk.reshape(mk.shape[-2:]), (Tq, Tk))
+        if causal:
+            s = np.where(np.arange(Tk)[None, :] <= np.arange(Tq)[:, None], s, -np.inf)
+        if keep is not None:
+            s = np.where(np.asarray(keep, dtype=bool).reshape(N, 1, 1, Tk), s, -np.inf)
+        s = s - s.max(axis=-1, keepdims=True)
+        pr = np.exp(s)
+        pr = pr / pr.sum(axis=-1, keepdims=True)
+        return (pr @ vh).transpose(0, 2, 1, 3).reshape(N, Tq, Eq)
+
+
+def rmsnorm_reference(x, g, eps: float) -> np.ndarray:
+    x = np.asarray(x, dtype=np.float64)
+    return x / np.sqrt((x * x).mean(axis=-1, keepdims=True) + np.float64(np.float32(eps))) * np.asarray(g, dtype=np.float64)
+
+
+def rmsnorm_model(E: int, eps: float, g, T: int = 0, axis: int = -1, opset: int = 23, extra_attrs: Sequence[bytes] = (), scale_input: bool = False) -> bytes:
+    """RMSNormalization(axis -1) on [N, E] (T = 0) or on [N, T, E] behind a Reshape; node 'rms'.  scale_input: the scale is a second graph
+    input (refused: only a constant)."""
+    inits = [] if scale_input else [tensor("g", np.asarray(g, np.float32))]
+    nodes = []
+    if T:
+        inits.append(tensor("s", np.asarray([-1, T, E], np.int64)))
+        nodes.append(node("Reshape", ["X", "s"], ["x3"]))
+    nodes.append(node("RMSNormalization", ["x3" if T else "X", "g"], ["out"], [attr_i("axis", axis), attr_f("epsilon", eps)] + list(extra_attrs), name="rms"))
+    ins = [value_info("X", ["N", max(T, 1) * E])] + ([value_info("g", ["N", E])] if scale_input else [])
+    return model("rms", nodes, inits, ins, [value_info("out", ["N", T, E] if T else ["N", E])], opset=opset)
+
+
+def decoder_block_spec(T: int = 16, E: int = 32, hq: int = 4, hkv: int = 2, ff: int = 64, layers: int = 2, outputs: int = 3, eps: float = 1e-6,
+                       weight_scale: float = 1.0, seed: int = 91) -> dict:
+    """Seeded pre-norm Llama-style decoder blocks over a window [N, T, E]: RMSNorm -> Q (E -> E), K, V (E -> hkv dh) -> causal grouped attention ->
+    projection -> residual -> RMSNorm -> SwiGLU (Swish(x Wg) * (x Wu)) Wd -> residual; a final RMSNorm and a Linear head on the last step.
+    Matrices are [in, out], no biases but the head's."""
+    rng = np.random.default_rng(seed)
+    f32 = lambda a: np.asarray(a, dtype=np.float32)  # noqa: E731
+    lin = lambda i, o: f32(rng.uniform(-1, 1, (i, o)) * weight_scale / np.sqrt(i))  # noqa: E731
+    dh = E // hq
+    ls = [{"Wq": lin(E, E), "Wk": lin(E, hkv * dh), "Wv": lin(E, hkv * dh), "Wo": lin(E, E), "Wg": lin(E, ff), "Wu": lin(E, ff), "Wd": lin(ff, E),
+           "g1": f32(1.0 + 0.1 * rng.standard_normal(E)), "g2": f32(1.0 + 0.1 * rng.standard_normal(E))} for _ in range(layers)]
+    return {"T": T, "E": E, "hq": hq, "hkv": hkv, "ff": ff, "eps": eps, "layers": ls, "g_final": f32(1.0 + 0.1 * rng.standard_normal(E)),
+            "head_W": lin(E, outputs), "head_b": f32(rng.uniform(-1, 1, outputs) / np.sqrt(E))}
+
+
+def from_torch_decoder_block(blocks, final_norm, head, T: int, hq: int, hkv: int) -> dict:
+    """The decoder_block_spec() dict of torch modules: each block has the bias-free Linears q_proj, k_proj, v_proj, o_proj, gate, up, down and the
+    nn.RMSNorm modules norm1, norm2; final_norm an nn.RMSNorm, head an nn.Linear."""
+    w = lambda lin: lin.weight.detach().cpu().numpy().astype(np.float32).T.copy()  # noqa: E731
+    g = lambda nrm: nrm.weight.detach().cpu().numpy().astype(np.float32)  # noqa: E731
+    ls = [{"Wq": w(b.q_proj), "Wk": w(b.k_proj), "Wv": w(b.v_proj), "Wo": w(b.o_proj), "Wg": w(b.gate), "Wu": w(b.up), "Wd": w(b.down), "g1": g(b.norm1),
+           "g2": g(b.norm2)} for b in blocks]
+    E = ls[0]["Wq"].shape[0]
+    return {"T": T, "E": E, "hq": hq, "hkv": hkv, "ff": ls[0]["Wg"].shape[1], "eps": float(blocks[0].norm1.eps), "layers": ls, "g_final": g(final_norm),
+            "head_W": w(head), "head_b": head.bias.detach().cpu().numpy().astype(np.float32)}
+
+
+def decoder_block_from_spec(spec: dict, form: str = "4d", opset: int = 23) -> bytes:
+    """The ONNX model of a decoder_block_spec(): X [N, T E] -> Reshape [N, T, E] -> the blocks -> the last step -> Linear: output "last" [N, outputs]."""
+    T, E, hq, hkv = spec["T"], spec["E"], spec["hq"], spec["hkv"]
+    nodes, inits = [], []
+    f32 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.float32)))  # noqa: E731
+
+    def matmul(x, W, out, name):
+        f32(name + "_W", W)
+        nodes.append(node("MatMul", [x, name + "_W"], [out], name=name))
+        return out
+
+    def rms(x, g, out, name):
+        f32(name + "_g", g)
+        nodes.append(node("RMSNormalization", [x, name + "_g"], [out], [attr_i("axis", -1), attr_f("epsilon", spec["eps"])], name=name))
+        return out
+
+    inits.append(tensor("flat_shape", np.asarray([-1, T, E], dtype=np.int64)))
+    nodes.append(node("Reshape", ["X", "flat_shape"], ["X3"]))
+    x = "X3"
+    for i, L in enumerate(spec["layers"]):
+        p = f"l{i}_"
+        a_in = rms(x, L["g1"], p + "n1", p + "norm1")
+        q, k, v = (matmul(a_in, L["W" + c], p + c, p + c + "_proj") for c in "qkv")
+        a = attention_op_nodes(nodes, inits, p + "a_", q, k, v, T, T, hq, hkv, E // hq, form=form, causal=True)
+        a = matmul(a, L["Wo"], p + "ao", p + "out_proj")
+        nodes.append(node("Add", [x, a], [p + "r1"], name=p + "res1"))
+        x = p + "r1"
+        f_in = rms(x, L["g2"], p + "n2", p + "norm2")
+        gate, up = matmul(f_in, L["Wg"], p + "gate", p + "gate_proj"), matmul(f_in, L["Wu"], p + "up", p + "up_proj")
+        nodes += [node("Sigmoid", [gate], [p + "sg"], name=p + "sigmoid"), node("Mul", [gate, p + "sg"], [p + "sw"], name=p + "swish"),
+                  node("Mul", [p + "sw", up], [p + "glu"], name=p + "glu_mul")]
+        f = matmul(p + "glu", L["Wd"], p + "down", p + "down_proj")
+        nodes.append(node("Add", [x, f], [p + "r2"], name=p + "res2"))
+        x = p + "r2"
+    x = rms(x, spec["g_final"], "dec", "final_norm")
+    inits.append(tensor("last_i", np.asarray(-1, dtype=np.int64)))
+    nodes.append(node("Gather", [x, "last_i"], ["last_t"], [attr_i("axis", 1)], name="last_step"))
+    f32("head_b", spec["head_b"])
+    matmul("last_t", spec["head_W"], "last_mm", "last_head")
+    nodes.append(node("Add", ["last_mm", "head_b"], ["last"], name="last_head_bias"))
+    return model("decoder", nodes, inits, [value_info("X", ["N", T * E])], [value_info("last", ["N", int(np.asarray(spec["head_W"]).shape[1])])], opset=opset)
+
+
+def decoder_block_reference(spec: dict, x) -> np.ndarray:
+    """float64 numpy restatement of decoder_block_from_spec(spec): x [N, T E] -> [N, outputs]."""
+    T, E, hq, hkv = spec["T"], spec["E"], spec["hq"], spec["hkv"]
+    f64 = lambda a: np.asarray(a, dtype=np.float64)  # noqa: E731
+    x = f64(x).reshape(-1, T, E)
+    for L in spec["layers"]:
+        a_in = rmsnorm_reference(x, L["g1"], spec["eps"])
+        a = attention_op_reference(a_in @ f64(L["Wq"]), a_in @ f64(L["Wk"]), a_in @ f64(L["Wv"]), hq, hkv, causal=True)
+        x = x + a @ f64(L["Wo"])
+        f_in = rmsnorm_reference(x, L["g2"], spec["eps"])
+        gate = f_in @ f64(L["Wg"])
+        x = x + (gate / (1.0 + np.exp(-gate)) * (f_in @ f64(L["Wu"]))) @ f64(L["Wd"])
+    x = rmsnorm_reference(x, spec["g_final"], spec["eps"])
+    return x[:, -1] @ f64(spec["head_W"]) + f64(spec["head_b"])
