@@ -73,6 +73,7 @@ struct TokensTables { const float *prefix = nullptr, *pos = nullptr; };  // Toke
 struct ChannelNormTables { const float *gamma = nullptr, *beta = nullptr; };  // ChannelNorm (per channel: the same in either layout; beta may be absent)
 struct EmbedTables { const int32_t *desc = nullptr; const uint16_t *map = nullptr; const float *tab = nullptr; };  // Embed (host/embed.hpp: piece descriptors, column -> piece map or null, the tables)
 struct InteractTables { const int32_t *map = nullptr; };  // Interact, dot mode (host/interact.hpp: output column -> Z entry or column of T)
+struct RotaryTables { const float *A = nullptr, *B = nullptr; };  // Rotary (row-major [T, rd] each: the factor of x[j] and of x[partner(j)])
 struct RnnTables { const float *wr = nullptr, *bias = nullptr, *bias2 = nullptr, *h0 = nullptr, *c0 = nullptr; };
 struct DeviceStep {  // (a step fills the one struct of its family)
   PlainTables plain;
@@ -92,6 +93,7 @@ struct DeviceStep {  // (a step fills the one struct of its family)
   TokensTables tokens;
   EmbedTables embed;
   InteractTables interact;
+  RotaryTables rotary;
 };
 
 // How the executor runs a step.

@@ -119,6 +119,11 @@ bool attention(hipStream_t s, const float *q, const float *k, const float *v, co
                float rm_fill = 0.f, int rm_mode = 0, bool rm_excl = false, bool rm_int = false, int Tk = 0, int kv_heads = 0, bool causal = false);
 // y = x / sqrtf(mean(x^2) + eps) * gamma over each of nvec vectors of E elements (RMSNormalization); false: E beyond the cap
 bool rmsnorm(hipStream_t s, const float *x, const float *gamma, float *y, int64_t nvec, int E, float eps);
+// Rotary position embedding (rotary.hip): y [rows, T, heads * dh] dense; x: [rows, T, ld] with head g at columns off + g * dh of a step.
+// Column j < rd of a head: y[j] = fl(fl(x[j] * A[t, j]) + fl(x[partner(j)] * B[t, j])), partner(j) = j +- rd / 2, or j ^ 1 (interleaved);
+// columns j >= rd are bit copies.  A, B: [T, rd].  false: a size is beyond the caps of host/attention.hpp, rd is odd or the view leaves ld
+bool rotary(hipStream_t s, const float *x, int64_t ld, int64_t off, const float *A, const float *B, float *y, int64_t rows, int T, int heads, int dh, int rd,
+            bool interleaved);
 // y = (x - mean) / sqrt(var + eps) * gamma + beta over each of nvec vectors of E elements (beta may be null); false: E beyond the cap
 bool layernorm(hipStream_t s, const float *x, const float *gamma, const float *beta, float *y, int64_t nvec, int E, float eps);
 // y[r, e] = mean over t of x[r, t, e]

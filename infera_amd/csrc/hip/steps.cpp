@@ -459,6 +459,18 @@ void launch_interact(const PassRunner &r, const Step &x, const InteractTables &t
   if (!ok) throw InferaError::onnx("Interact kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
 }
 
+// ---- Rotary (rotary.hip): the two [T, rd] factor tables, as the lowering built them ----
+void upload_rotary(const Step &s, RotaryTables &t, const Upload &up) {
+  t.A = up(s.scale);
+  t.B = up(s.shift);
+}
+void launch_rotary(const PassRunner &r, const Step &x, const RotaryTables &t) {
+  if (r.in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: a Rotary step reads its input row-major");
+  if (!kern::rotary(r.stream, r.buf(x.in0), x.attn_ld[0], x.attn_off[0], t.A, t.B, r.buf(x.out), r.nr, int(x.attn_T), int(x.attn_heads), int(x.attn_dh), int(x.rot_rd),
+                    x.rot_interleaved))
+    throw InferaError::onnx("Rotary kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+
 // ---- the plain family: the step's constants as the lowering left them (Conv2d: packed for the generic kernel); its launches are the head
 // of PassRunner::launch_plain, right below ----
 void upload_plain(const Step &s, PlainTables &t, const Upload &up) {
@@ -523,6 +535,7 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::ChannelNorm: launch_channelnorm(*this, x, d.channelnorm); break;
     case StepKind::Embed: launch_embed(*this, x, d.embed); break;
     case StepKind::Interact: launch_interact(*this, x, d.interact); break;
+    case StepKind::Rotary: launch_rotary(*this, x, d.rotary); break;
     // the steps without tables
     case StepKind::Unary: kern::unary(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], act_of(x)); break;
     case StepKind::BinaryAct:
@@ -596,6 +609,7 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::ChannelNorm: return upload_channelnorm(s, d.channelnorm, up);
     case StepKind::Embed: return upload_embed(s, d.embed, up);
     case StepKind::Interact: return upload_interact(s, d.interact, up);
+    case StepKind::Rotary: return upload_rotary(s, d.rotary, up);
     default: return;  // (no tables)
   }
 }

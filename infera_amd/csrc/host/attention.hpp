@@ -13,6 +13,11 @@ constexpr int64_t kAttnMaxHeads = 1024;
 enum RowMaskMode : int { kRowMaskAdd = 0, kRowMaskReplace = 1 };
 // a fill at or below this (the finfo.min family and -inf) excludes its keys; anything above it is a bias that goes through the softmax
 constexpr float kRowMaskExcludingFill = -1e30f;
+// The Rotary step (hip/rotary.hip) shares kAttnMaxT, kAttnMaxDh and kAttnMaxHeads.  Whether a view (ld, off) of heads of dh columns, rd of them
+// rotated, takes the kernel's 16-byte form (the launcher also wants 16-byte aligned pointers); else the scalar form: the same bits
+inline bool rotary_vec4(int64_t ld, int64_t off, int64_t dh, int64_t rd, bool interleaved) {
+  return ld % 4 == 0 && off % 4 == 0 && dh % 4 == 0 && (interleaved ? rd % 4 == 0 : rd % 8 == 0);
+}
 constexpr int64_t kLnMaxE = 4096;     // LayerNorm vector length: one vector is held in the registers of one wave (64 floats per lane)
 
 }  // namespace infera_hip

@@ -45,10 +45,16 @@ void Lowerer::find_attention_ops() {
     am.nodes.push_back(ni);
     // an operand behind its head split: Reshape [N,T,h,dh] -> Transpose(0,2,1,3), each read by the next alone
     auto head_split = [&](const std::string &operand, AttnSide &side) {
-      const NodeDef *t = graph->producer(operand);
-      if (!t || t->op != "Transpose" || !graph->std_dom(*t) || perm_of(*t) != split_perm || graph->sole_reader(operand, true) != &n) return false;
+      if (graph->sole_reader(operand, true) != &n) return false;
+      // (a rotary embedding on the head-major value, lower_rotary.cpp: the split is looked for behind it, and its readers are the embedding's)
+      std::shared_ptr<const RotaryMatch> rot;
+      const std::string v = behind_rotary(operand, &rot);
+      const NodeDef *t = graph->producer(v);
+      if (!t || t->op != "Transpose" || !graph->std_dom(*t) || perm_of(*t) != split_perm) return false;
       const NodeDef *r = graph->producer(t->inputs[0]);
       if (!r || r->op != "Reshape" || !graph->std_dom(*r) || r->inputs.size() != 2 || graph->sole_reader(t->inputs[0], false) != t) return false;
+      if (rot) am.nodes.insert(am.nodes.end(), rot->nodes.begin(), rot->nodes.end());
+      side.rot = rot;
       am.nodes.push_back(idx(t));
       am.nodes.push_back(idx(r));
       side.src = r->inputs[0];

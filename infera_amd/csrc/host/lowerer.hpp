@@ -246,10 +246,23 @@ struct Lowerer {
     char op;  // '*' or '/'
     std::string cst;
   };
+  // ---- rotary position embeddings (lower_rotary.cpp; INTEGRATION.md 2.6 "Rotary position embeddings") -------------------------------------
+  // A rotary embedding on a head-major value [N, h, T, dh], recognised by structure before the walk (match_rotary) where an attention front
+  // end walks an operand back to its head split: the RotaryEmbedding operator, or the rotate_half spelling Add(Mul(x, cos), Mul(Concat(Neg(x2),
+  // x1), sin)) with x1, x2 the two halves of x's last axis (two Slices or one Split).  Its nodes emit nothing; lower_attention emits one Rotary
+  // step per rotated operand in front of the Attention step (rotary_step: constants and shapes are checked there, refusals name `at`).
+  struct RotaryMatch {
+    const NodeDef *at = nullptr;   // the RotaryEmbedding node, or the Add that closes the spelling
+    std::string x;                 // the value it rotates
+    std::string cos, sin, pos;     // the constants' names (pos: position_ids or "")
+    bool spelling = false;         // rotate_half: cos / sin are whole [T, dh] factor tables, the pairing is `half`
+    std::vector<size_t> nodes;
+  };
   struct AttnSide {
     std::string src, shape;   // the [N, T, E] value the head split reads (behind an absorbed Split / Slice: its input) and the Reshape's target
     const NodeDef *cut = nullptr;  // that Split / Slice on the last axis
     size_t cut_out = 0;
+    std::shared_ptr<const RotaryMatch> rot;  // the rotary embedding between the head split and the attention (null: none)
   };
   // A row's own key mask (INTEGRATION.md 2.6 "Padded sequences"): T consecutive columns of the input buffer and a compare value, traced
   // back from where it meets the scores (or the masked mean) through Cast / Unsqueeze / Reshape / Expand / Equal / Not to a graph input
@@ -570,6 +583,21 @@ struct Lowerer {
   void find_attention_ops();
   // RMSNormalization over the last axis of [rows, E] / [rows, T, E]: one RmsNorm step (hip/layernorm.hip)
   void rms_norm(const NodeDef &n);
+
+  // ---- lower_rotary.cpp: RotaryEmbedding and the rotate_half spelling ----
+  // `v` [N, h, T, dh] as a rotary embedding of another value; null: it is none (nothing is claimed).  Only structure is looked at
+  std::shared_ptr<const RotaryMatch> match_rotary(const std::string &v) const;
+  // every reader of the rotated value `rm.x` is a node of the match
+  bool rotary_reads_alone(const RotaryMatch &rm) const;
+  // the Rotary step of `rm` over [N, T, h * dh] (in0 and the view are the caller's); refusals name rm.at
+  Step rotary_step(const RotaryMatch &rm, int64_t T, int64_t h, int64_t dh);
+  // `v` behind a rotary embedding, for an attention front end that walks an operand back: returns the rotated value (and sets *rot), or `v`
+  // itself where match_rotary finds none or the spelling's x has other readers.  An operator whose X is no head split is refused by name
+  std::string behind_rotary(const std::string &v, std::shared_ptr<const RotaryMatch> *rot) const;
+  // refuses, by name, the head-major RotaryEmbedding nodes that no attention front end absorbed (run: after find_attention)
+  void check_rotary_ops();
+  // RotaryEmbedding met by the walk: the 3-D form, one window step
+  void rotary_embedding(const NodeDef &n);
 
   // ---- lowering.cpp: quantised and float16 graphs ----
   QArgs quant_args(const NodeDef &n, size_t si, size_t zi, const char *what);

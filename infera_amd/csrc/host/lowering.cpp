@@ -2539,8 +2539,12 @@ namespace lowering {
       // one operand back to its head split; kt: the K^T operand
       auto match_head = [&](const std::string &operand, AttnSide &side, bool kt) -> bool {
         std::string v = strip_scales(operand);
+        if (!sole_reader(v)) return why = generic, false;
+        // (a rotary embedding on the head-major value, lower_rotary.cpp: the split is looked for behind it, and its readers are the embedding's)
+        std::shared_ptr<const RotaryMatch> rot;
+        v = behind_rotary(v, &rot);
         const NodeDef *t = producer(v);
-        if (!t || t->op != "Transpose" || !sole_reader(v)) return why = generic, false;
+        if (!t || t->op != "Transpose") return why = generic, false;
         std::vector<int64_t> perm = perm_of(*t);
         if (perm.size() == 3)
           return why = "PyTorch nn.MultiheadAttention's time-major export (heads folded into the row axis, [T, N*h, dh]) is not supported yet; "
@@ -2550,8 +2554,10 @@ namespace lowering {
         am.nodes.push_back(graph->producer_of.at(v));
         if (kt && perm == std::vector<int64_t>{0, 1, 3, 2}) {  // (0,2,1,3) first, then the last two axes
           v = strip_scales(t->inputs[0]);
+          if (!sole_reader(v)) return why = generic, false;
+          if (!rot) v = behind_rotary(v, &rot);
           t = producer(v);
-          if (!t || t->op != "Transpose" || !sole_reader(v) || perm_of(*t) != std::vector<int64_t>{0, 2, 1, 3}) return why = generic, false;
+          if (!t || t->op != "Transpose" || perm_of(*t) != std::vector<int64_t>{0, 2, 1, 3}) return why = generic, false;
           am.nodes.push_back(graph->producer_of.at(v));
         } else if (perm != (kt ? std::vector<int64_t>{0, 2, 3, 1} : std::vector<int64_t>{0, 2, 1, 3})) {
           return why = generic, false;
@@ -2564,6 +2570,8 @@ namespace lowering {
           return why = generic, false;
         }
         am.nodes.push_back(graph->producer_of.at(v));
+        if (rot) am.nodes.insert(am.nodes.end(), rot->nodes.begin(), rot->nodes.end());
+        side.rot = rot;
         side.src = r->inputs[0];
         side.shape = r->inputs[1];
         const NodeDef *c = producer(side.src);
@@ -2830,7 +2838,7 @@ namespace lowering {
       int buf;
       int64_t N, T, E, ld, off;
     } vw[3];
-    int64_t heads = 0, dh = 0, kv_heads = 0;
+    int64_t heads = 0, dh = 0, kv_heads = 0, split_h[3] = {0, 0, 0};  // split_h: the heads each operand's own split gives it
     const NodeDef *op = am.op;  // the Attention operator (lower_attention_op.cpp); null: the pattern form
     for (int i = 0; i < 3; i++) {
       const AttnSide &sd = am.side[i];
@@ -2898,6 +2906,7 @@ namespace lowering {
       if (neg == 3 && v.E % h == 0) d = v.E / h;
       if (h <= 0 || d <= 0 || v.E / h != d || v.E % h != 0)
         bad("E = " + std::to_string(v.E) + " is not divisible by h = " + std::to_string(tgt[2] > 0 ? tgt[2] : h) + " (head split " + shape_str(sh->c->i64) + ")");
+      split_h[i] = h;
       if (i == 0) heads = h, dh = d;
       else if (op) {
         if (i == 2 && d != dh) bad("v_head_size = " + std::to_string(d) + " differs from head_size = " + std::to_string(dh));
@@ -3048,6 +3057,23 @@ namespace lowering {
         plan.buf_shape[size_t(vw[j].buf)] = {N, 0};
       }
       for (int j = 0; j < 3; j++) vw[j].buf = vw[0].buf, vw[j].ld = 3 * E, vw[j].off = j * E;
+    }
+    // A rotary embedding between a head split and the attention (lower_rotary.cpp): one Rotary step per rotated operand reads the operand's
+    // view -- a cut of a packed projection where it lies -- and the attention reads its dense [N, T, h * dh] result
+    for (int j = 0; j < 3; j++) {
+      const std::shared_ptr<const RotaryMatch> &rot = am.side[j].rot;
+      if (!rot) continue;
+      bool seen = false;
+      for (int i = 0; i < j && !seen; i++)
+        if (am.side[i].rot && am.side[i].rot->at == rot->at) vw[j] = vw[i], seen = true;  // (one rotated value read as two operands: matched once per operand)
+      if (seen) continue;
+      Step r = rotary_step(*rot, vw[j].T, split_h[j], dh);
+      r.in0 = vw[j].buf;
+      r.attn_ld[0] = vw[j].ld, r.attn_off[0] = vw[j].off;
+      const size_t first = *std::min_element(rot->nodes.begin(), rot->nodes.end());
+      r.origin = rot->spelling ? node_label(m.nodes[first]) + "+...+" + node_label(*rot->at) : node_label(*rot->at);
+      vw[j].buf = push_step(std::move(r), {vw[j].N, vw[j].T * vw[j].E});
+      vw[j].ld = vw[j].E, vw[j].off = 0;
     }
     s.in0 = vw[0].buf;
     s.in1 = vw[1].buf;
@@ -3656,6 +3682,7 @@ namespace lowering {
     else if (op == "TopK") topk(n);
     else if (op == "LayerNormalization") layer_norm(n);
     else if (op == "RMSNormalization") rms_norm(n);
+    else if (op == "RotaryEmbedding") rotary_embedding(n);
     else if (op == "InstanceNormalization") instance_norm(n);
     else if (op == "GroupNormalization") group_norm(n);
     else if (op == "ArgMax") argmax(n);
@@ -4289,6 +4316,7 @@ namespace lowering {
     find_interactions();
     find_attention_ops();  // (before find_attention, whose tail absorbs the row-mask sub-graphs of every match)
     find_attention();
+    check_rotary_ops();
     if (nearest_enabled) find_nearest();
     find_group_norms();
     find_embeds();
@@ -4333,6 +4361,8 @@ namespace lowering {
         if (n.op == "Attention" || n.op == "MultiHeadAttention" || n.op == "SkipLayerNormalization")
           unsupported(n, "unsupported operator form: the contrib fused operator of domain '" + n.domain +
                              "' is not supported; export the standard-domain graph (MatMul / Softmax / LayerNormalization)");
+        if (n.op == "RotaryEmbedding")
+          unsupported(n, "unsupported operator form: the contrib RotaryEmbedding of domain '" + n.domain + "' is not supported; export the standard-domain RotaryEmbedding (opset 23)");
         unsupported(n, "operator domain '" + n.domain + "'");
       } else if (attn_at.count(ni)) lower_typed(n, [&] { lower_attention(attn_at.at(ni), n); });
       else if (nearest_at.count(ni)) lower_nearest(nearest_at.at(ni));

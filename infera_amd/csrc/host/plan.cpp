@@ -30,13 +30,14 @@ double Plan::flops_per_row() const {
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
     else if (s.kind == StepKind::Nearest) f += 2.0 * double(s.nearest->F) * double(s.nearest->M);
     else if (s.kind == StepKind::Interact) f += s.interact->mode == kInteractDot ? 2.0 * double(s.interact->k * s.interact->k * s.interact->d) : 4.0 * double(s.interact->k * s.interact->d);
+    else if (s.kind == StepKind::Rotary) f += 3.0 * double(s.attn_T * s.attn_heads * s.rot_rd);  // two products and a sum per rotated column
     else if (s.kind == StepKind::Recurrent) f += 2.0 * double(s.rnn->T * s.rnn->D * s.rnn->G * s.rnn->H) * double(s.rnn->F + s.rnn->H);
   }
   return f;
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -84,6 +85,18 @@ std::string Plan::describe_json() const {
     if (s.kind == StepKind::LayerNorm) o << ",\"E\":" << s.K << ",\"T\":" << s.rep << ",\"epsilon\":" << double(s.ln_eps) << ",\"bias\":" << (s.shift.empty() ? "false" : "true");
     if (s.kind == StepKind::RmsNorm) o << ",\"E\":" << s.K << ",\"T\":" << s.rep << ",\"eps\":" << double(s.ln_eps);
     if (s.kind == StepKind::MeanTime) o << ",\"E\":" << s.K << ",\"T\":" << s.rep;
+    if (s.kind == StepKind::Rotary) {  // the tables as one hash over their f32 bit patterns: equal spellings give equal plans
+      uint64_t h = 1469598103934665603ull;
+      for (const auto *v : {&s.scale, &s.shift})
+        for (float f : *v) {
+          uint32_t b;
+          std::memcpy(&b, &f, sizeof b);
+          h = (h ^ b) * 1099511628211ull;
+        }
+      o << ",\"T\":" << s.attn_T << ",\"heads\":" << s.attn_heads << ",\"dh\":" << s.attn_dh << ",\"rd\":" << s.rot_rd << ",\"interleaved\":" << (s.rot_interleaved ? "true" : "false")
+        << ",\"positions\":\"" << (s.rot_const_pos ? "constant" : "arange") << "\",\"ld\":" << s.attn_ld[0] << ",\"off\":" << s.attn_off[0] << ",\"form\":\""
+        << (rotary_vec4(s.attn_ld[0], s.attn_off[0], s.attn_dh, s.rot_rd, s.rot_interleaved) ? "vec4" : "scalar") << "\",\"tables_hash\":" << (h >> 11);
+    }
     auto json_f32 = [](float f) { return std::isnan(f) ? std::string("NaN") : std::isinf(f) ? std::string(f < 0 ? "-Infinity" : "Infinity") : ([&] { std::ostringstream q; q << std::setprecision(9) << double(f); return q.str(); })(); };
     if (s.kind == StepKind::MeanTime && s.in3 >= 0)
       o << ",\"row_mask\":{\"src_col\":" << s.rm_off << ",\"cmp\":" << json_f32(s.rm_cmp) << ",\"clip\":" << json_f32(s.rm_clip) << "}";

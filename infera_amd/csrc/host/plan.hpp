@@ -79,6 +79,7 @@ enum class StepKind : int {
   Embed = 40,         // out [rows, F] = pieces in output order: rows of constant tables chosen by index columns of in0 [rows, W] (truncated toward zero, + an offset) and runs of in0's columns as they are; a window [rows, k, d] when the pack says so (EmbedPack, host/embed.hpp, embed.hip)
   Interact = 41,      // feature interactions of in0 [rows, k, d] (rows first, flat): dot mode, out [rows, F] = chosen entries of T . T^T beside bit copies of columns of T; fm mode, out [rows, d] or [rows, 1] = h * ((sum_f T)^2 - sum_f T^2) (InteractPack, host/interact.hpp, interact.hip)
   RmsNorm = 42,       // y = x / sqrt(mean(x^2) + ln_eps) * scale[K] over each of the `rep` vectors of K elements of a row (RMSNormalization; layernorm.hip)
+  Rotary = 43,        // rotary position embedding of in0 [rows, attn_T, ld] read through the view (attn_ld[0], attn_off[0]) into a dense [rows, attn_T, attn_heads * attn_dh]: column j < rot_rd of a head, y[j] = fl(fl(x[j] * scale[t, j]) + fl(x[partner(j)] * shift[t, j])), partner(j) = j +- rot_rd / 2 or j ^ 1 (rot_interleaved); the other columns are bit copies (RotaryEmbedding and the rotate_half spelling; rotary.hip)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
@@ -180,6 +181,10 @@ struct Step {
   int64_t attn_Tk = 0, attn_kv_heads = 0;
   bool attn_causal = false;
   float attn_scale = 1.f, ln_eps = 1e-5f;
+  // Rotary: the window and its view in attn_T, attn_heads, attn_dh, attn_ld[0], attn_off[0]; rot_rd rotated columns per head; the tables
+  // A = scale, B = shift, [attn_T, rot_rd] each; rot_const_pos: they were gathered by a constant position_ids (else positions 0 .. T - 1)
+  int64_t rot_rd = 0;
+  bool rot_interleaved = false, rot_const_pos = false;
   // FakeQuant: qx.  QDense: qx = how the f32 input is quantised, qy = how the result is (off: the step returns `real`, f32);
   // qW [K, M] = the weights as signed bytes (uint8 data shifted by 128), q_wzp[M] = their zero points shifted the same way, q_mult[M] =
   // x_scale * w_scale[m] in f32, q_bias[M] = the int32 bias added to the accumulator (else `bias`: f32, added after the scaling).

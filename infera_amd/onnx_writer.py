@@ -1110,15 +1110,19 @@ def from_torch_encoder(encoder, T: int, head=None, causal: bool = False) -> dict
 
 def attention_nodes(nodes: list, inits: list, p: str, q: str, k: str, v: str, x_for_shape: str, T: int, E: int, h: int, scale: str = "scores_div",
                     k_transpose: str = "direct", mask=None, shape: str = "const", scale_value: float | None = None, softmax_axis: int = -1,
-                    mask_left: bool = False, row_mask: dict | None = None) -> str:
+                    mask_left: bool = False, row_mask: dict | None = None, rotary=None) -> str:
     """Appends the batch-first self-attention sub-graph over q, k, v [N, T, E] (names) and returns the name of its [N, T, E] result.
     scale: "scores_div" (Div by sqrt(dh)), "scores_mul", "q" (Mul of Q) or "sqrt_both" (Q and K^T by sqrt(scale) each, what
     scaled_dot_product_attention exports); k_transpose: "direct" (0,2,3,1) or "two_step" ((0,2,1,3) then (0,1,3,2)); mask: None or an f32
     array added to the scores (mask_left: as the Add's first operand); shape: "const" targets or the exporter's Shape -> Gather -> Unsqueeze -> Concat sub-graph.
     row_mask: None or a per-row key mask, dict(src=<name of an [N, T] value>, form="add" | "replace", fill=<negative float>, from_ids=None | pad_id,
     unsqueeze="one" | "two" | "reshape", expand="none" | "const" | "shape", value=None | <what row_mask_value() returned>); see row_mask_value and
-    row_mask_on_scores (mask_left: the mask term as the Add's first operand)."""
+    row_mask_on_scores (mask_left: the mask term as the Add's first operand).
+    rotary: None, True or the options of rotary_options(): a rotary embedding on the head-major Q and K (K: in front of the second Transpose of
+    k_transpose "two_step", the only place where K is [N, h, T, dh])."""
     dh = E // h
+    rot = rotary_options(rotary)
+    assert rot is None or k_transpose == "two_step", "rotary needs K as [N, h, T, dh]: k_transpose='two_step'"
     sv = (1.0 / math.sqrt(dh)) if scale_value is None else scale_value
     i64 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.int64)))  # noqa: E731
     f32 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.float32)))  # noqa: E731
@@ -1138,11 +1142,14 @@ def attention_nodes(nodes: list, inits: list, p: str, q: str, k: str, v: str, x_
         if nm == "k" and k_transpose == "direct":
             nodes.append(node("Transpose", [p + "k4"], [p + "kh"], [attr_ints("perm", [0, 2, 3, 1])], name=p + "tr_k"))
         elif nm == "k":
-            nodes += [node("Transpose", [p + "k4"], [p + "kh0"], [attr_ints("perm", [0, 2, 1, 3])], name=p + "tr_k0"),
-                      node("Transpose", [p + "kh0"], [p + "kh"], [attr_ints("perm", [0, 1, 3, 2])], name=p + "tr_k")]
+            nodes.append(node("Transpose", [p + "k4"], [p + "kh0"], [attr_ints("perm", [0, 2, 1, 3])], name=p + "tr_k0"))
+            kh0 = p + "kh0" if rot is None or "k" not in rot["on"] else rotary_nodes(nodes, inits, p + "k_", p + "kh0", T, dh, rot)
+            nodes.append(node("Transpose", [kh0], [p + "kh"], [attr_ints("perm", [0, 1, 3, 2])], name=p + "tr_k"))
         else:
             nodes.append(node("Transpose", [p + nm + "4"], [p + nm + "h"], [attr_ints("perm", [0, 2, 1, 3])], name=p + "tr_" + nm))
         heads[nm] = p + nm + "h"
+        if rot is not None and nm != "k" and nm in rot["on"]:
+            heads[nm] = rotary_nodes(nodes, inits, p + nm + "_", heads[nm], T, dh, rot)
     if scale == "q":
         f32(p + "sc", sv)
         nodes.append(node("Mul", [heads["q"], p + "sc"], [p + "qs"], name=p + "scale_q"))
@@ -1274,11 +1281,11 @@ def causal_mask(T: int, rank: int = 2) -> np.ndarray:
     return mk.reshape((1,) * (rank - 2) + (T, T))
 
 
-def attention_only(T: int, E: int, h: int, form: str = "packed", row_mask: dict | None = None, mask_type: int = INT64, **kw) -> bytes:
+def attention_only(T: int, E: int, h: int, form: str = "packed", row_mask: dict | None = None, mask_type: int = INT64, opset: int = 20, **kw) -> bytes:
     """Self-attention alone over a flat input: form "packed": X [N, T*3E] -> Reshape [N, T, 3E] -> Split on the last axis -> q, k, v;
     "three": inputs Q, K, V [N, T*E] each (the call's columns in that order), each reshaped to [N, T, E].  Output [N, T, E].
     row_mask (attention_nodes; its src defaults to "M"): one more input M [N, T] (mask_type: INT64, INT32 or FLOAT) behind the others, the
-    0 / 1 mask or, with from_ids, the token ids."""
+    0 / 1 mask or, with from_ids, the token ids.  kw: attention_nodes (rotary = ...: with the operator form the model needs opset 23)."""
     nodes, inits = [], []
     if row_mask is not None:
         kw["row_mask"] = dict(row_mask, src=row_mask.get("src", "M"))
@@ -1296,7 +1303,7 @@ def attention_only(T: int, E: int, h: int, form: str = "packed", row_mask: dict 
     if row_mask is not None:
         ins.append(value_info("M", ["N", T], mask_type))
     out = attention_nodes(nodes, inits, "a_", "q", "k", "v", xs, T, E, h, **kw)
-    return model("attention", nodes, inits, ins, [value_info(out, ["N", T, E])], opset=20)
+    return model("attention", nodes, inits, ins, [value_info(out, ["N", T, E])], opset=opset)
 
 
 def masked_attention_reference(q, k, v, h: int, keep, fill: float, mode: str = "add", scale: float | None = None, dtype=np.float64) -> np.ndarray:
@@ -4517,14 +4524,17 @@ def deepfm_reference(spec: dict, x_cat) -> dict:
 
 def attention_op_nodes(nodes: list, inits: list, p: str, q: str, k: str, v: str, Tq: int, Tk: int, hq: int, hkv: int, dh: int, form: str = "4d",
                        causal: bool = False, mask=None, mask_value: str | None = None, scale: float | None = None, extra_attrs: Sequence[bytes] = (),
-                       extra_inputs: Sequence[str] = (), extra_outputs: Sequence[str] = ()) -> str:
+                       extra_inputs: Sequence[str] = (), extra_outputs: Sequence[str] = (), rotary=None) -> str:
     """Appends one standard-domain Attention node '<p>attn' over q [N, Tq, hq dh], k, v [N, Tk, hkv dh] (names) and returns the name of its
     [N, Tq, hq dh] result.  form "3d": the operands as they are, beside q_num_heads / kv_num_heads; "4d" (what torch's exporter writes): each
     through Reshape [0, T, h, dh] -> Transpose(0,2,1,3), and Y back through Transpose(0,2,1,3) -> Reshape [0, Tq, hq dh].
     mask: a constant attn_mask (float32 additive or bool, true = kept); mask_value: the name of a value computed in the graph instead;
     scale: the attribute (None: left out, the operator's 1 / sqrt(dh)); extra_inputs follow attn_mask (past_key, past_value,
-    nonpad_kv_seqlen; "" = absent), extra_outputs follow Y."""
+    nonpad_kv_seqlen; "" = absent), extra_outputs follow Y.
+    rotary: None, True or the options of rotary_options(): a rotary embedding on the operands named in its "on" ("qk"), head-major behind the
+    head split (form "4d") or as the 3-D operator beside num_heads in front of the node (form "3d": the operator form only)."""
     i64 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.int64)))  # noqa: E731
+    rot = rotary_options(rotary)
     attrs = [attr_i("is_causal", 1)] if causal else []
     if scale is not None:
         attrs.append(attr_f("scale", scale))
@@ -4535,8 +4545,13 @@ def attention_op_nodes(nodes: list, inits: list, p: str, q: str, k: str, v: str,
             nodes += [node("Reshape", [ops[j], p + nm + "_split"], [p + nm + "4"], name=p + "split_" + nm),
                       node("Transpose", [p + nm + "4"], [p + nm + "h"], [attr_ints("perm", [0, 2, 1, 3])], name=p + "tr_" + nm)]
             ops[j] = p + nm + "h"
+            if rot is not None and nm in rot["on"]:
+                ops[j] = rotary_nodes(nodes, inits, p + nm + "_", ops[j], T, dh, rot)
     else:
         attrs += [attr_i("q_num_heads", hq), attr_i("kv_num_heads", hkv)]
+        for j, (nm, T, h) in enumerate((("q", Tq, hq), ("k", Tk, hkv), ("v", Tk, hkv))):
+            if rot is not None and nm in rot["on"]:
+                ops[j] = rotary_nodes(nodes, inits, p + nm + "_", ops[j], T, dh, rot, num_heads=h)
     if mask is not None:
         inits.append(tensor(p + "mask", np.asarray(mask)))
         mask_value = p + "mask"
@@ -4575,8 +4590,8 @@ def attention_op_model(Tq: int, Tk: int, hq: int, hkv: int, dh: int, form: str =
                        scale: float | None = None, opset: int = 23, packed: bool = False, mask_type: int = INT64, **kw) -> bytes:
     """The Attention operator alone over flat inputs Q [N, Tq hq dh], K, V [N, Tk hkv dh] (the call's columns in that order), each reshaped to
     [N, T, E]; packed (Tq = Tk, hq = hkv): X [N, T 3E] -> Reshape -> Split on the last axis.  row_mask: the keyword arguments of
-    bool_row_mask_value, for one more input M [N, Tk] (mask_type) behind the others.  Output [N, Tq, hq dh].  kw: attention_op_nodes, and
-    graph_outputs: names of further graph outputs."""
+    bool_row_mask_value, for one more input M [N, Tk] (mask_type) behind the others.  Output [N, Tq, hq dh].  kw: attention_op_nodes (rotary =
+    ... among them), and graph_outputs: names of further graph outputs."""
     nodes, inits = [], []
     Eq, Ekv = hq * dh, hkv * dh
     if packed:
@@ -4640,18 +4655,22 @@ def rmsnorm_model(E: int, eps: float, g, T: int = 0, axis: int = -1, opset: int 
 
 
 def decoder_block_spec(T: int = 16, E: int = 32, hq: int = 4, hkv: int = 2, ff: int = 64, layers: int = 2, outputs: int = 3, eps: float = 1e-6,
-                       weight_scale: float = 1.0, seed: int = 91) -> dict:
+                       weight_scale: float = 1.0, seed: int = 91, rotary=None) -> dict:
     """Seeded pre-norm Llama-style decoder blocks over a window [N, T, E]: RMSNorm -> Q (E -> E), K, V (E -> hkv dh) -> causal grouped attention ->
     projection -> residual -> RMSNorm -> SwiGLU (Swish(x Wg) * (x Wu)) Wd -> residual; a final RMSNorm and a Linear head on the last step.
-    Matrices are [in, out], no biases but the head's."""
+    Matrices are [in, out], no biases but the head's.  rotary: None, True or the options of rotary_options(): Q and K of every layer are
+    rotated (spec["rotary"]; absent when off)."""
     rng = np.random.default_rng(seed)
     f32 = lambda a: np.asarray(a, dtype=np.float32)  # noqa: E731
     lin = lambda i, o: f32(rng.uniform(-1, 1, (i, o)) * weight_scale / np.sqrt(i))  # noqa: E731
     dh = E // hq
     ls = [{"Wq": lin(E, E), "Wk": lin(E, hkv * dh), "Wv": lin(E, hkv * dh), "Wo": lin(E, E), "Wg": lin(E, ff), "Wu": lin(E, ff), "Wd": lin(ff, E),
            "g1": f32(1.0 + 0.1 * rng.standard_normal(E)), "g2": f32(1.0 + 0.1 * rng.standard_normal(E))} for _ in range(layers)]
-    return {"T": T, "E": E, "hq": hq, "hkv": hkv, "ff": ff, "eps": eps, "layers": ls, "g_final": f32(1.0 + 0.1 * rng.standard_normal(E)),
+    spec = {"T": T, "E": E, "hq": hq, "hkv": hkv, "ff": ff, "eps": eps, "layers": ls, "g_final": f32(1.0 + 0.1 * rng.standard_normal(E)),
             "head_W": lin(E, outputs), "head_b": f32(rng.uniform(-1, 1, outputs) / np.sqrt(E))}
+    if rotary_options(rotary) is not None:
+        spec["rotary"] = rotary_options(rotary)
+    return spec
 
 
 def from_torch_decoder_block(blocks, final_norm, head, T: int, hq: int, hkv: int) -> dict:
@@ -4666,8 +4685,10 @@ def from_torch_decoder_block(blocks, final_norm, head, T: int, hq: int, hkv: int
             "head_W": w(head), "head_b": head.bias.detach().cpu().numpy().astype(np.float32)}
 
 
-def decoder_block_from_spec(spec: dict, form: str = "4d", opset: int = 23) -> bytes:
-    """The ONNX model of a decoder_block_spec(): X [N, T E] -> Reshape [N, T, E] -> the blocks -> the last step -> Linear: output "last" [N, outputs]."""
+def decoder_block_from_spec(spec: dict, form: str = "4d", opset: int = 23, rotary=None) -> bytes:
+    """The ONNX model of a decoder_block_spec(): X [N, T E] -> Reshape [N, T, E] -> the blocks -> the last step -> Linear: output "last" [N, outputs].
+    rotary: overrides spec["rotary"] (the same tables, another spelling)."""
+    rot = rotary_options(rotary) if rotary is not None else spec.get("rotary")
     T, E, hq, hkv = spec["T"], spec["E"], spec["hq"], spec["hkv"]
     nodes, inits = [], []
     f32 = lambda name, v: inits.append(tensor(name, np.asarray(v, dtype=np.float32)))  # noqa: E731
@@ -4689,7 +4710,7 @@ def decoder_block_from_spec(spec: dict, form: str = "4d", opset: int = 23) -> by
         p = f"l{i}_"
         a_in = rms(x, L["g1"], p + "n1", p + "norm1")
         q, k, v = (matmul(a_in, L["W" + c], p + c, p + c + "_proj") for c in "qkv")
-        a = attention_op_nodes(nodes, inits, p + "a_", q, k, v, T, T, hq, hkv, E // hq, form=form, causal=True)
+        a = attention_op_nodes(nodes, inits, p + "a_", q, k, v, T, T, hq, hkv, E // hq, form=form, causal=True, **({} if rot is None else {"rotary": rot}))
         a = matmul(a, L["Wo"], p + "ao", p + "out_proj")
         nodes.append(node("Add", [x, a], [p + "r1"], name=p + "res1"))
         x = p + "r1"
@@ -4709,17 +4730,167 @@ def decoder_block_from_spec(spec: dict, form: str = "4d", opset: int = 23) -> by
     return model("decoder", nodes, inits, [value_info("X", ["N", T * E])], [value_info("last", ["N", int(np.asarray(spec["head_W"]).shape[1])])], opset=opset)
 
 
-def decoder_block_reference(spec: dict, x) -> np.ndarray:
+def decoder_block_reference(spec: dict, x, rotary=None) -> np.ndarray:
     """float64 numpy restatement of decoder_block_from_spec(spec): x [N, T E] -> [N, outputs]."""
     T, E, hq, hkv = spec["T"], spec["E"], spec["hq"], spec["hkv"]
+    rot = rotary_options(rotary) if rotary is not None else spec.get("rotary")
+    rope = (lambda a, h: a) if rot is None else (lambda a, h: rotary_apply(a, T, h, E // hq, rot, np.float64))  # noqa: E731
     f64 = lambda a: np.asarray(a, dtype=np.float64)  # noqa: E731
     x = f64(x).reshape(-1, T, E)
     for L in spec["layers"]:
         a_in = rmsnorm_reference(x, L["g1"], spec["eps"])
-        a = attention_op_reference(a_in @ f64(L["Wq"]), a_in @ f64(L["Wk"]), a_in @ f64(L["Wv"]), hq, hkv, causal=True)
+        a = attention_op_reference(rope(a_in @ f64(L["Wq"]), hq), rope(a_in @ f64(L["Wk"]), hkv), a_in @ f64(L["Wv"]), hq, hkv, causal=True)
         x = x + a @ f64(L["Wo"])
         f_in = rmsnorm_reference(x, L["g2"], spec["eps"])
         gate = f_in @ f64(L["Wg"])
         x = x + (gate / (1.0 + np.exp(-gate)) * (f_in @ f64(L["Wu"]))) @ f64(L["Wd"])
     x = rmsnorm_reference(x, spec["g_final"], spec["eps"])
     return x[:, -1] @ f64(spec["head_W"]) + f64(spec["head_b"])
+
+
+# ------------------------------------------------------------------------------------------
+# Rotary position embeddings: the opset-23 operator RotaryEmbedding and the rotate_half spelling
+# ------------------------------------------------------------------------------------------
+
+def rotary_tables(T: int, rd: int, base: float = 10000.0, positions=None) -> tuple[np.ndarray, np.ndarray]:
+    """(cos, sin), each [T, rd / 2] float32 (or one row per entry of positions): the angle p * base ** (-2 i / rd) of position p and pair i in
+    float64, its cosine and sine in float64, rounded once to float32."""
+    assert rd >= 2 and rd % 2 == 0
+    pos = np.arange(T, dtype=np.float64) if positions is None else np.asarray(positions, dtype=np.float64)
+    ang = pos[:, None] * np.float64(base) ** (-2.0 * np.arange(rd // 2, dtype=np.float64) / rd)[None, :]
+    return np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
+
+
+def rotary_options(rotary) -> dict | None:
+    """The rotary= keyword of the attention and decoder writers, normalised: None / False: off; True: the defaults; a dict: over the defaults.
+    form: "op" (RotaryEmbedding), "slice" or "split" (the rotate_half spelling with two Slices / one Split); interleaved, rd (0 = dh), base;
+    positions: None (0 .. T - 1) or a list of T constant positions into caches of cache_rows rows (the operator's position_ids);
+    on: which operands are rotated, "qk"; slice_end: "exact" or "max" (INT64_MAX as the second Slice's end); table_rank: 2, 3 or 4 (the
+    spelling's tables as [T, dh], [1, T, dh] or [1, 1, T, dh]); swap: the spelling's Add and Mul operands in the other order; break_:
+    rotate_half_nodes."""
+    if rotary is None or rotary is False:
+        return None
+    o = {"form": "op", "interleaved": False, "rd": 0, "base": 10000.0, "positions": None, "cache_rows": None, "on": "qk", "slice_end": "exact",
+         "table_rank": 2, "swap": False, "break_": None}
+    if isinstance(rotary, dict):
+        assert not set(rotary) - set(o), set(rotary) - set(o)
+        o.update(rotary)
+    return o
+
+
+def rotary_factors(cos, sin, interleaved: bool = False) -> tuple[np.ndarray, np.ndarray]:
+    """The step's factor tables A, B [T, rd] of cos, sin [T, rd / 2]: A = cos over both members of a pair, B = -sin on the first member and
+    +sin on the second (pairs (j, j + rd / 2), or (2 i, 2 i + 1) when interleaved)."""
+    cos, sin = np.asarray(cos), np.asarray(sin)
+    if interleaved:
+        return np.repeat(cos, 2, axis=1), np.stack([-sin, sin], axis=2).reshape(len(sin), -1)
+    return np.concatenate([cos, cos], axis=1), np.concatenate([-sin, sin], axis=1)
+
+
+def rotary_reference(x, A, B, h: int, dh: int, interleaved: bool = False, dtype=np.float32) -> np.ndarray:
+    """The Rotary step's definition over x [N, T, h dh] with factor tables A, B [T, rd]: for column j < rd of every head
+    out[j] = fl(fl(x[j] A[t, j]) + fl(x[partner(j)] B[t, j])), partner(j) = j +- rd / 2 or j ^ 1 (interleaved); columns j >= rd are copies.
+    dtype float32: three separately rounded operations (the step's bits); float64: the same formula on the same float32 tables."""
+    x = np.asarray(x, dtype=dtype)
+    N, T = x.shape[:2]
+    A, B = np.asarray(A, dtype=dtype), np.asarray(B, dtype=dtype)
+    rd = A.shape[1]
+    x4 = x.reshape(N, T, h, dh)
+    j = np.arange(rd)
+    partner = (j ^ 1) if interleaved else np.where(j < rd // 2, j + rd // 2, j - rd // 2)
+    out = x4.copy()
+    with np.errstate(all="ignore"):
+        out[..., :rd] = x4[..., :rd] * A[None, :, None, :] + x4[..., partner] * B[None, :, None, :]
+    return out.reshape(N, T, h * dh)
+
+
+def _rotary_caches(T: int, dh: int, rot: dict):
+    """(cos, sin, positions or None) of the options: the caches as the operator reads them ([T, rd/2], or [cache_rows, rd/2] beside positions)."""
+    rd = rot["rd"] or dh
+    if rot["positions"] is None:
+        return rotary_tables(T, rd, rot["base"]) + (None,)
+    pos = [int(p) for p in rot["positions"]]
+    assert len(pos) == T
+    return rotary_tables(rot["cache_rows"] or max(pos) + 1, rd, rot["base"]) + (pos,)
+
+
+def rotary_apply(x, T: int, h: int, dh: int, rotary, dtype=np.float32) -> np.ndarray:
+    """rotary_reference over x [N, T, h dh] (or [N, T h dh]) with the tables of the options."""
+    rot = rotary_options(rotary)
+    cos, sin, pos = _rotary_caches(T, dh, rot)
+    if pos is not None:
+        cos, sin = cos[pos], sin[pos]
+    A, B = rotary_factors(cos, sin, rot["interleaved"])
+    return rotary_reference(np.asarray(x).reshape(-1, T, h * dh), A, B, h, dh, rot["interleaved"], dtype)
+
+
+def rotary_op_nodes(nodes: list, inits: list, p: str, x: str, cos, sin, interleaved: bool = False, rd: int = 0, num_heads: int = 0, positions=None,
+                    extra_attrs: Sequence[bytes] = (), domain: str = "") -> str:
+    """Appends one RotaryEmbedding node '<p>rope' over x ([N, h, T, dh], or [N, T, h dh] beside num_heads) and returns its result.  cos, sin:
+    [T, rd/2] arrays, stored as [1, T, rd/2]; beside positions (a list, stored as position_ids int64 [1, T]) as they are, [P, rd/2]."""
+    cos, sin = np.asarray(cos, dtype=np.float32), np.asarray(sin, dtype=np.float32)
+    if positions is None:
+        cos, sin = cos[None], sin[None]
+    inits += [tensor(p + "cos", cos), tensor(p + "sin", sin)]
+    ins = [x, p + "cos", p + "sin"]
+    if positions is not None:
+        inits.append(tensor(p + "pos", np.asarray(positions, dtype=np.int64).reshape(1, -1)))
+        ins.append(p + "pos")
+    attrs = ([attr_i("interleaved", 1)] if interleaved else []) + ([attr_i("num_heads", num_heads)] if num_heads else []) + \
+            ([attr_i("rotary_embedding_dim", rd)] if rd else [])
+    nodes.append(node("RotaryEmbedding", ins, [p + "rot"], attrs + list(extra_attrs), name=p + "rope", domain=domain))
+    return p + "rot"
+
+
+def rotate_half_nodes(nodes: list, inits: list, p: str, x: str, cos_full, sin_full, halves: str = "slice", slice_end: str = "exact", table_rank: int = 2,
+                      swap: bool = False, break_: str | None = None) -> str:
+    """Appends Hugging Face's apply_rotary_pos_emb over x [N, h, T, dh], x * cos + rotate_half(x) * sin with rotate_half(x) = cat(-x2, x1), and
+    returns its result (node '<p>add').  cos_full, sin_full: [T, dh]; halves: two Slices of the last axis or one Split; swap: Add and Mul
+    operands in the other order.  break_: a sub-graph that is NOT the embedding -- "bounds" (the second Slice starts one column late) or
+    "order" (cat(x1, -x2))."""
+    cos_full, sin_full = np.asarray(cos_full, dtype=np.float32), np.asarray(sin_full, dtype=np.float32)
+    d = cos_full.shape[-1]
+    lead = (1,) * (table_rank - 2)
+    inits += [tensor(p + "cos", cos_full.reshape(lead + cos_full.shape)), tensor(p + "sin", sin_full.reshape(lead + sin_full.shape))]
+    i64 = lambda name, val: inits.append(tensor(name, np.asarray(val, dtype=np.int64)))  # noqa: E731
+    if halves == "split":
+        i64(p + "sp", [d // 2, d // 2])
+        nodes.append(node("Split", [x, p + "sp"], [p + "x1", p + "x2"], [attr_i("axis", -1)], name=p + "split"))
+    else:
+        i64(p + "b0", [0]); i64(p + "b1", [d // 2 + (1 if break_ == "bounds" else 0)]); i64(p + "e1", [d // 2])  # noqa: E702
+        i64(p + "e2", [np.iinfo(np.int64).max if slice_end == "max" else d]); i64(p + "ax", [-1])  # noqa: E702
+        nodes += [node("Slice", [x, p + "b0", p + "e1", p + "ax"], [p + "x1"], name=p + "slice1"),
+                  node("Slice", [x, p + "b1", p + "e2", p + "ax"], [p + "x2"], name=p + "slice2")]
+    if break_ == "order":
+        nodes += [node("Neg", [p + "x2"], [p + "nx2"], name=p + "neg"), node("Concat", [p + "x1", p + "nx2"], [p + "rh"], [attr_i("axis", -1)], name=p + "cat")]
+    else:
+        nodes += [node("Neg", [p + "x2"], [p + "nx2"], name=p + "neg"), node("Concat", [p + "nx2", p + "x1"], [p + "rh"], [attr_i("axis", -1)], name=p + "cat")]
+    pair = lambda a, b: [b, a] if swap else [a, b]  # noqa: E731
+    nodes += [node("Mul", pair(x, p + "cos"), [p + "xc"], name=p + "mul_cos"), node("Mul", pair(p + "rh", p + "sin"), [p + "rs"], name=p + "mul_sin"),
+              node("Add", pair(p + "xc", p + "rs"), [p + "rot"], name=p + "add")]
+    return p + "rot"
+
+
+def rotary_nodes(nodes: list, inits: list, p: str, x: str, T: int, dh: int, rotary, num_heads: int = 0) -> str:
+    """The rotary embedding of the options (rotary_options) over x: head-major [N, h, T, dh], or [N, T, h dh] beside num_heads (form "op" only)."""
+    rot = rotary_options(rotary)
+    cos, sin, pos = _rotary_caches(T, dh, rot)
+    if rot["form"] == "op":
+        return rotary_op_nodes(nodes, inits, p, x, cos, sin, rot["interleaved"], rot["rd"], num_heads, pos)
+    assert not num_heads and not rot["interleaved"] and (rot["rd"] or dh) == dh, "the rotate_half spelling: head-major, half pairing, whole heads"
+    if pos is not None:
+        cos, sin = cos[pos], sin[pos]
+    return rotate_half_nodes(nodes, inits, p, x, np.concatenate([cos, cos], axis=1), np.concatenate([sin, sin], axis=1), rot["form"], rot["slice_end"],
+                             rot["table_rank"], rot["swap"], rot["break_"])
+
+
+def rotary_model(T: int, h: int, dh: int, rotary=True, opset: int = 23, batch: int | str = "N", **kw) -> bytes:
+    """The 3-D operator alone: X [N, T h dh] -> Reshape [N, T, h dh] -> RotaryEmbedding(num_heads = h) -> output [N, T, h dh]; node 'r_rope'.
+    kw: rotary_op_nodes (extra_attrs, domain, num_heads = another count or 0)."""
+    rot = rotary_options(rotary)
+    assert rot["form"] == "op"
+    E = h * dh
+    cos, sin, pos = _rotary_caches(T, dh, rot)
+    nodes, inits = [node("Reshape", ["X", "x_shape"], ["x3"])], [tensor("x_shape", np.asarray([-1, T, E], dtype=np.int64))]
+    out = rotary_op_nodes(nodes, inits, "r_", "x3", cos, sin, rot["interleaved"], rot["rd"], kw.pop("num_heads", h), pos, **kw)
+    return model("rotary", nodes, inits, [value_info("X", [batch, T * E])], [value_info(out, [batch, T, E])], opset=opset)
