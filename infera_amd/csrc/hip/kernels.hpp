@@ -368,6 +368,15 @@ void convt2d_phase(hipStream_t s, const float *X, const float *Wp, const float *
 void resize2d(hipStream_t s, const float *X, float *Y, int64_t rows, int C, int H, int W, int OH, int OW, const int *row_idx, const int *col_idx,
               const float *row_wgt, const float *col_wgt, bool linear, bool cq);
 
+// ---- DepthToSpace / SpaceToDepth (pixelshuffle.hip; the four forms: host/pixelshuffle.hpp) ------
+// C, H, W = the input; OC, OH, OW = the output; b = the block size
+struct PixelShuffleGeom {
+  int b, C, H, W, OC, OH, OW;
+  bool to_space, channel_major;
+};
+// `kernel`: the PixelShuffleKernel the scheduler chose for these layouts; false: it does not serve them (nothing was launched)
+bool pixel_shuffle(hipStream_t s, const float *X, float *Y, int64_t rows, const PixelShuffleGeom &g, int kernel, bool in_cq, bool out_cq);
+
 // ---- InstanceNormalization / GroupNormalization (spatialnorm.hip; host/spatialnorm.hpp) --------------
 // X, Y: [rows, C, S] in NCHW order or (cq) channel-quad planes; G groups of C / G channels; gamma, beta: [C].  false: beyond the kernel's caps
 // fused: where spatialnorm_fused_unit(C, S, G, cq) names a unit -- one pass, y = act(d / sqrtf(var + eps) * gamma + beta)

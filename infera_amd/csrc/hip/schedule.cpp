@@ -6,6 +6,7 @@
 
 #include "../host/channelnorm.hpp"
 #include "../host/deconv.hpp"
+#include "../host/pixelshuffle.hpp"
 #include "../host/spatialnorm.hpp"
 #include "../host/embed.hpp"
 #include "../host/interact.hpp"
@@ -207,19 +208,23 @@ void Scheduler::decide_layout(bool commit) {
   // (a transposed convolution reads and writes either layout, deconv.hip)
   auto reads_nchw = [&](const Step &s) { return convolution(s) || s.kind == StepKind::ConvTranspose2d; };
   // (so does the crossing to a window, tokens.hip; its flat result has no layout, and alone it does not make a plan convolutional)
-  auto reads_either = [&](const Step &s) { return reads_nchw(s) || s.kind == StepKind::Tokens; };
-  // A served [C,H,W] result leaves in the caller's NCHW order.  When a transposed convolution -- the last layer of a decoder -- is its only
-  // writer and nothing reads it, that layer stores NCHW itself and the plan before it stays in channel quads; anything else keeps the plan NCHW.
-  bool out_by_convt = false;
+  // (and so does a PixelShuffle, pixelshuffle.hip: the SpaceToDepth stem reads the caller's image)
+  auto reads_either = [&](const Step &s) { return reads_nchw(s) || s.kind == StepKind::Tokens || s.kind == StepKind::PixelShuffle; };
+  // the steps that store NCHW from a channel-quad input where their result has to lie so
+  auto stores_nchw = [](const Step &s) { return s.kind == StepKind::ConvTranspose2d || s.kind == StepKind::PixelShuffle; };
+  // A served [C,H,W] result leaves in the caller's NCHW order.  When such a step -- a transposed convolution or a sub-pixel shuffle, the last
+  // layer of a decoder -- is its only writer and nothing reads it, that layer stores NCHW itself and the plan before it stays in channel quads;
+  // anything else keeps the plan NCHW.
+  bool out_by_writer = false;
   if (spatial(m.plan.out_buf) > 1 && m.plan.out_buf != 0) {
-    int writers = 0, convt_writers = 0, readers = 0;
+    int writers = 0, nchw_writers = 0, readers = 0;
     for (const auto &s : st) {
       writers += s.out == m.plan.out_buf;
-      convt_writers += s.out == m.plan.out_buf && s.kind == StepKind::ConvTranspose2d;
+      nchw_writers += s.out == m.plan.out_buf && stores_nchw(s);
       readers += s.in0 == m.plan.out_buf || s.in1 == m.plan.out_buf || s.in2 == m.plan.out_buf || s.in3 == m.plan.out_buf;
     }
-    out_by_convt = writers == 1 && convt_writers == 1 && readers == 0;
-    if (out_by_convt) m.nchw_buf[size_t(m.plan.out_buf)] = 1;
+    out_by_writer = writers == 1 && nchw_writers == 1 && readers == 0;
+    if (out_by_writer) m.nchw_buf[size_t(m.plan.out_buf)] = 1;
   }
   // Likewise a transposed convolution whose result only meets flat [rows, C*H*W] tensors element by element -- a reconstruction against the
   // table's columns, which lie in NCHW element order: that layer stores NCHW and the plan before it stays in channel quads.
@@ -279,7 +284,7 @@ void Scheduler::decide_layout(bool commit) {
       }
     }
   }
-  if (spatial(m.plan.out_buf) > 1 && !out_by_convt) refuse("the served output is a [C,H,W] tensor (results leave in the caller's NCHW order)");
+  if (spatial(m.plan.out_buf) > 1 && !out_by_writer) refuse("the served output is a [C,H,W] tensor (results leave in the caller's NCHW order)");
   // channel-quad planes need whole quads in every internal 4-D tensor (the caller's input stays NCHW)
   // (a buffer no step writes any more -- that of a FakeQuant its QConv2d absorbed -- has no layout)
   std::vector<char> written(m.plan.buf_shape.size(), 0);
@@ -647,6 +652,11 @@ void schedule(LoadedModel &m) {
   // ChannelNorm layers: the register form where C fits it, else (or with INFERA_CHANNELNORM_REGS=0: everywhere) the re-read form
   for (Step &c : m.plan.steps)
     if (c.kind == StepKind::ChannelNorm) c.out_mode = channelnorm_regs_form(c.C, knobs.channelnorm_regs) ? 0 : 1;
+  // PixelShuffle layers: the form of the kernel that fits the layouts of the two tensors (INFERA_PIXELSHUFFLE_FAST=0: the generic form everywhere)
+  for (Step &c : m.plan.steps)
+    if (c.kind == StepKind::PixelShuffle)
+      c.out_mode = pixelshuffle_kernel(c.ps_block, c.ps_to_space, c.ps_channel_major, c.C, m.cq_mode && !m.nchw_buf[size_t(c.in0)], m.cq_mode && !m.nchw_buf[size_t(c.out)],
+                                       knobs.pixelshuffle_fast);
   s.narrow_edges(StepKind::QDense, knobs.qdense_bytes, true, [](const Step &p, const Step &c) { return c.qx == p.qy; }, m.q_in_bytes, m.q_out_bytes);
   s.narrow_edges(StepKind::HDense, knobs.hdense_half, false, [](const Step &, const Step &) { return true; }, m.h_in_half, m.h_out_half);
   const auto eff = effective_steps(m);
@@ -756,6 +766,18 @@ std::string LoadedModel::describe_json() const {
            "\",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\"}";
     }
     if (!c.empty()) o << ",\"channelnorm\":[" << c << "]";
+  }
+  {  // per PixelShuffle step: its form and block, the kernel that runs it and the layouts it reads and writes
+    std::string c;
+    for (size_t i = 0; i < exec.size(); i++) {
+      const Step &x = plan.steps[i];
+      if (x.kind != StepKind::PixelShuffle) continue;
+      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)], out_cq = cq_mode && !nchw_buf[size_t(x.out)];
+      c += std::string(c.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"kernel\":\"" + pixelshuffle_kernel_name(x.out_mode) + "\",\"form\":\"" +
+           pixelshuffle_form_name(x.ps_to_space, x.ps_channel_major) + "\",\"block\":" + std::to_string(x.ps_block) + ",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") +
+           "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\"}";
+    }
+    if (!c.empty()) o << ",\"pixelshuffle\":[" << c << "]";
   }
   {  // per Tokens step: the kernel that runs it and the layout it reads (its result is a flat window)
     std::string c;

@@ -9,6 +9,7 @@
 #include "../host/nearest.hpp"
 #include "../host/channelnorm.hpp"
 #include "../host/onnx_model.hpp"
+#include "../host/pixelshuffle.hpp"
 #include "../host/prep.hpp"
 #include "../host/recurrent.hpp"
 #include "../host/spatialnorm.hpp"
@@ -471,6 +472,14 @@ void launch_rotary(const PassRunner &r, const Step &x, const RotaryTables &t) {
     throw InferaError::onnx("Rotary kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
 }
 
+// ---- PixelShuffle (pixelshuffle.hip): no tables; the scheduler chose the form for the two layouts (Step::out_mode) ----
+void launch_pixelshuffle(const PassRunner &r, const Step &x) {
+  if (r.in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: a PixelShuffle step reads its input row-major");
+  const kern::PixelShuffleGeom g{int(x.ps_block), int(x.C), int(x.H), int(x.Wd), int(x.Mo), int(x.OH), int(x.OW), x.ps_to_space, x.ps_channel_major};
+  if (!kern::pixel_shuffle(r.stream, r.buf(x.in0), r.buf(x.out), r.nr, g, x.out_mode, r.cq(x.in0), r.cq(x.out)))
+    throw InferaError::onnx("PixelShuffle kernel launch failed: '" + x.origin + "' was scheduled as " + pixelshuffle_kernel_name(x.out_mode) + " for other layouts than it meets");
+}
+
 // ---- the plain family: the step's constants as the lowering left them (Conv2d: packed for the generic kernel); its launches are the head
 // of PassRunner::launch_plain, right below ----
 void upload_plain(const Step &s, PlainTables &t, const Upload &up) {
@@ -536,6 +545,7 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::Embed: launch_embed(*this, x, d.embed); break;
     case StepKind::Interact: launch_interact(*this, x, d.interact); break;
     case StepKind::Rotary: launch_rotary(*this, x, d.rotary); break;
+    case StepKind::PixelShuffle: launch_pixelshuffle(*this, x); break;
     // the steps without tables
     case StepKind::Unary: kern::unary(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], act_of(x)); break;
     case StepKind::BinaryAct:
@@ -610,6 +620,7 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::Embed: return upload_embed(s, d.embed, up);
     case StepKind::Interact: return upload_interact(s, d.interact, up);
     case StepKind::Rotary: return upload_rotary(s, d.rotary, up);
+    case StepKind::PixelShuffle: return;  // (a copy by index arithmetic: no tables)
     default: return;  // (no tables)
   }
 }

@@ -111,7 +111,7 @@ ScheduleKnobs ScheduleKnobs::read() {
   return ScheduleKnobs{env_flag("INFERA_STEM_POOL", true), env_flag("INFERA_CHAIN_XCM", true), env_flag("INFERA_DENSE_XCM", true), prec != "fp32",
                        env_flag("INFERA_CONV_FOLD_SHORTCUT", true), env_flag("INFERA_QDENSE_BYTES", true), env_flag("INFERA_HDENSE_HALF", true),
                        env_flag("INFERA_HDENSE", true), env_flag("INFERA_NEAREST", true), env_flag("INFERA_CONVT_MFMA", true),
-                       env_flag("INFERA_SPATIALNORM_FUSED", true), env_flag("INFERA_CHANNELNORM_REGS", true)};
+                       env_flag("INFERA_SPATIALNORM_FUSED", true), env_flag("INFERA_CHANNELNORM_REGS", true), env_flag("INFERA_PIXELSHUFFLE_FAST", true)};
 }
 
 void log_msg(int level, const std::string &msg) {

@@ -129,6 +129,7 @@ struct ScheduleKnobs {
   bool convt_mfma;   // INFERA_CONVT_MFMA=0|1 (default 1)  transposed convolutions on the MFMA phase kernel where it applies (0: the generic VALU kernel; same bits on exact data)
   bool spatialnorm_fused;  // INFERA_SPATIALNORM_FUSED=0|1 (default 1)  InstanceNormalization / GroupNormalization layers on the one-pass register kernel where a unit fits (0: SpatialStats + SpatialNorm everywhere; tests, A/B)
   bool channelnorm_regs;   // INFERA_CHANNELNORM_REGS=0|1 (default 1)  ChannelNorm layers on the register form where C fits (0: the re-read form everywhere; tests, A/B)
+  bool pixelshuffle_fast;  // INFERA_PIXELSHUFFLE_FAST=0|1 (default 1)  PixelShuffle steps on the quad-copy, register-transpose and layout-crossing forms where they apply (0: the generic form everywhere; same bits; tests, A/B)
   static ScheduleKnobs read();
 };
 // Read per launch inside the kernel launchers, for the bit-identity TESTS only (no effect on results; defaults are the shipped paths):

@@ -235,6 +235,15 @@ struct Lowerer {
     size_t inorm = 0, back = 0;
   };
   std::map<size_t, GnMatch> gn_at;  // index of the first Reshape -> the chain behind it
+  // ---- sub-pixel layers (lower_shuffle.cpp; INTEGRATION.md 2.6 "Sub-pixel layers") ----
+  // Reshape(x, 6-D) -> Transpose(one of four perms) -> Reshape(4-D) with sole readers in between: DepthToSpace / SpaceToDepth spelled out.
+  // Found structurally before the walk (find_pixel_shuffles), anchored at the LAST Reshape -- both targets are constants by then; the first
+  // two nodes emit nothing.  Shapes are checked at the anchor (false: the three nodes lower by their own rules, as without the matcher)
+  struct ShuffleMatch {
+    size_t first = 0, transpose = 0;
+    int form = 0;  // index into lower_shuffle.cpp's table of spellings
+  };
+  std::map<size_t, ShuffleMatch> shuffle_at;  // index of the last Reshape -> the two nodes in front of it
   int view_consts = 0;
   std::map<std::string, int64_t> expanded_lead;  // results of Expand over constants -> the leading entry of the target shape as the graph had it
 
@@ -598,6 +607,17 @@ struct Lowerer {
   void check_rotary_ops();
   // RotaryEmbedding met by the walk: the 3-D form, one window step
   void rotary_embedding(const NodeDef &n);
+
+  // ---- lower_shuffle.cpp: DepthToSpace, SpaceToDepth and their Reshape -> Transpose -> Reshape spellings ----
+  void find_pixel_shuffles();
+  // a live DepthToSpace / SpaceToDepth node that reads the rank-4 graph input `in` whose C, H or W is symbolic: refused by its name (run: before
+  // the general rule that only the row axis of an input may be symbolic)
+  void check_shuffle_extents(const onnx::ValueDef &in) const;
+  // the spelling closed by the Reshape `last`: ONE PixelShuffle step (or, with b = 1, an alias); false: not exactly a spelling, nothing was done
+  bool pixel_shuffle_spelling(const ShuffleMatch &sm, const NodeDef &last);
+  void depth_space(const NodeDef &n);
+  // the step over the [N,C,H,W] activation `a`, bound to out_node's first output; refusals name `at`
+  void pixel_shuffle_step(const NodeDef &at, const NodeDef &out_node, const Val &a, int64_t b, bool to_space, bool channel_major, const std::string &origin);
 
   // ---- lowering.cpp: quantised and float16 graphs ----
   QArgs quant_args(const NodeDef &n, size_t si, size_t zi, const char *what);

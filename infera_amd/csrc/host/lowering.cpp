@@ -3533,6 +3533,7 @@ namespace lowering {
       case StepKind::SliceCols:
       case StepKind::PadCols:
       case StepKind::ChannelShuffle:
+      case StepKind::PixelShuffle:
       case StepKind::ArgMax:
       case StepKind::ArgMin:
       case StepKind::TopK:
@@ -3692,6 +3693,7 @@ namespace lowering {
     else if (op == "Conv") conv(n);
     else if (op == "ConvTranspose") conv_transpose(n);
     else if (op == "Resize" || op == "Upsample") resize(n);
+    else if (op == "DepthToSpace" || op == "SpaceToDepth") depth_space(n);
     else if (op == "BatchNormalization") batchnorm(n);
     else if (op == "MaxPool") pool(n, true);
     else if (op == "AveragePool") pool(n, false);
@@ -4262,6 +4264,7 @@ namespace lowering {
       if (!served_type(v.elem_type) && !half_input)
         throw InferaError::onnx("input '" + v.name + "' is not f32, int64 or int32 (element type " + std::to_string(v.elem_type) + ")");
     if (in.dims.size() < 2) throw InferaError::onnx("input rank " + std::to_string(in.dims.size()) + " has no row axis + feature axis; rank >= 2 is required");
+    check_shuffle_extents(in);  // (a DepthToSpace / SpaceToDepth on a symbolic image: refused by the node's name)
     for (size_t i = 1; i < in.dims.size(); i++)
       if (in.dims[i] <= 0) throw InferaError::onnx("only the leading (row/batch) dimension of the input may be symbolic, got " + shape_str(in.dims));
     plan.input_shape = in.dims;
@@ -4319,6 +4322,7 @@ namespace lowering {
     check_rotary_ops();
     if (nearest_enabled) find_nearest();
     find_group_norms();
+    find_pixel_shuffles();
     find_embeds();
     find_seq_lens();
     {
@@ -4381,6 +4385,11 @@ namespace lowering {
       else if (mmean_at.count(ni)) lower_typed(n, [&] { lower_masked_mean(mmean_at.at(ni), n); });
       else if (absorbed[ni]) continue;
       else if (gn_at.count(ni)) lower_typed(n, [&] { if (!exporter_group_norm(gn_at.at(ni), n)) lower_node(n); });
+      else if (shuffle_at.count(ni)) {
+        const ShuffleMatch &sm = shuffle_at.at(ni);
+        if (!pixel_shuffle_spelling(sm, n))  // the operators one by one, as without the matcher
+          for (size_t i : {sm.first, sm.transpose, ni}) lower_typed(m.nodes[i], [&] { lower_node(m.nodes[i]); });
+      }
       else lower_typed(n, [&] { lower_node(n); });
     }
     // one output is served: the first (engine.rs:146-149) unless the load call selected another

@@ -12,6 +12,7 @@
 #include "spatialnorm.hpp"
 #include "tokens.hpp"
 #include "nearest.hpp"
+#include "pixelshuffle.hpp"
 #include "plan.hpp"
 #include "prep.hpp"
 #include "recurrent.hpp"
@@ -37,7 +38,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary", "PixelShuffle"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -144,6 +145,9 @@ std::string Plan::describe_json() const {
     if (s.kind == StepKind::Resize2d)
       o << ",\"C\":" << s.C << ",\"mode\":\"" << (s.deconv->linear ? "linear" : "nearest") << "\",\"coordinate_transformation_mode\":\"" << s.deconv->coord_mode << "\""
         << (s.deconv->linear ? std::string() : ",\"nearest_mode\":\"" + s.deconv->nearest_mode + "\"") << ",\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
+    if (s.kind == StepKind::PixelShuffle)  // (a copy: no flops; every element is read once and written once)
+      o << ",\"form\":\"" << pixelshuffle_form_name(s.ps_to_space, s.ps_channel_major) << "\",\"block\":" << s.ps_block << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"in_hw\":[" << s.H << "," << s.Wd
+        << "],\"out_hw\":[" << s.OH << "," << s.OW << "],\"bytes_per_row\":" << 8 * s.C * s.H * s.Wd;
     if (s.kind == StepKind::SpatialNorm || s.kind == StepKind::SpatialStats)
       o << ",\"C\":" << s.C << ",\"groups\":" << s.groups << ",\"E\":" << (s.C / s.groups) * s.S << ",\"hw\":[" << (s.H > 0 ? s.H : 1) << "," << (s.H > 0 ? s.Wd : s.S)
         << "],\"epsilon\":" << double(s.ln_eps);

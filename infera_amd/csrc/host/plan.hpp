@@ -80,6 +80,7 @@ enum class StepKind : int {
   Interact = 41,      // feature interactions of in0 [rows, k, d] (rows first, flat): dot mode, out [rows, F] = chosen entries of T . T^T beside bit copies of columns of T; fm mode, out [rows, d] or [rows, 1] = h * ((sum_f T)^2 - sum_f T^2) (InteractPack, host/interact.hpp, interact.hip)
   RmsNorm = 42,       // y = x / sqrt(mean(x^2) + ln_eps) * scale[K] over each of the `rep` vectors of K elements of a row (RMSNormalization; layernorm.hip)
   Rotary = 43,        // rotary position embedding of in0 [rows, attn_T, ld] read through the view (attn_ld[0], attn_off[0]) into a dense [rows, attn_T, attn_heads * attn_dh]: column j < rot_rd of a head, y[j] = fl(fl(x[j] * scale[t, j]) + fl(x[partner(j)] * shift[t, j])), partner(j) = j +- rot_rd / 2 or j ^ 1 (rot_interleaved); the other columns are bit copies (RotaryEmbedding and the rotate_half spelling; rotary.hip)
+  PixelShuffle = 44,  // DepthToSpace / SpaceToDepth of in0 [rows, C, H, Wd] to [rows, Mo, OH, OW] with block ps_block: a bit copy of every element, in one of four forms (ps_to_space, ps_channel_major: host/pixelshuffle.hpp); out_mode (set by the scheduler): the PixelShuffleKernel that runs it (pixelshuffle.hip)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
@@ -185,6 +186,9 @@ struct Step {
   // A = scale, B = shift, [attn_T, rot_rd] each; rot_const_pos: they were gathered by a constant position_ids (else positions 0 .. T - 1)
   int64_t rot_rd = 0;
   bool rot_interleaved = false, rot_const_pos = false;
+  // PixelShuffle: the block size, depth to space (else space to depth), channel-major (CRD / pixel_unshuffle; else block-major: DCR / SpaceToDepth)
+  int64_t ps_block = 0;
+  bool ps_to_space = false, ps_channel_major = false;
   // FakeQuant: qx.  QDense: qx = how the f32 input is quantised, qy = how the result is (off: the step returns `real`, f32);
   // qW [K, M] = the weights as signed bytes (uint8 data shifted by 128), q_wzp[M] = their zero points shifted the same way, q_mult[M] =
   // x_scale * w_scale[m] in f32, q_bias[M] = the int32 bias added to the accumulator (else `bias`: f32, added after the scaling).

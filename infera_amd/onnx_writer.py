@@ -3208,6 +3208,39 @@ class _DecoderNet:
         self.layers.append(("gnorm", nm, [x], dict(groups=groups, gamma=np.repeat(s.astype(np.float64), rep) * g64, beta=np.repeat(b.astype(np.float64), rep) * g64 + b64, eps=e32)))
         return nm
 
+    def shuffle(self, x, c, hw, form="crd", b=2, spelling=False, mode_attr=True, lead=0, target="const", perm=None, name=None, attrs_extra=()):
+        """One sub-pixel layer over x [N, c, *hw].  form: "dcr" / "crd" (DepthToSpace), "s2d" (SpaceToDepth), "unshuffle" (F.pixel_unshuffle:
+        a spelling only).  spelling: Reshape -> Transpose -> Reshape (nodes <name>_split, <name>_perm, <name>_merge) in place of the operator;
+        b: the block size, or (b_h, b_w) in a spelling; lead: the targets' row entry (0 or -1); target = "shape": the first target's row entry
+        is cut from Shape(x); perm: another permutation than the form's.  mode_attr = False: DepthToSpace without its mode (DCR).
+        Returns (result, its (C, H, W))."""
+        nm = name or self._name("shuffle")
+        bh, bw = _pair(b)
+        h, w = hw
+        to_space = form in ("dcr", "crd")
+        oshape = (c // (bh * bw), h * bh, w * bw) if to_space else (c * bh * bw, h // bh, w // bw)
+        if not spelling:
+            if form == "unshuffle":
+                raise ValueError("pixel_unshuffle has no operator")
+            attrs = [attr_i("blocksize", bh)] + ([attr_s("mode", form.upper())] if to_space and (mode_attr or form == "crd") else [])
+            self.nodes.append(node("DepthToSpace" if to_space else "SpaceToDepth", [x], [nm], attrs + list(attrs_extra), name=nm))
+        else:
+            six, pm = PIXEL_SHUFFLE_SPELLINGS[form]
+            dims = dict(N=lead, b1=bh, b2=bw, Cs=oshape[0], C=c, H=h, W=w, Hb=h // bh, Wb=w // bw)
+            t1 = [dims[k] for k in six]
+            if target == "shape":
+                self.nodes.append(node("Shape", [x], [nm + "_shape"], name=nm + "_shape"))
+                self.nodes.append(node("Gather", [nm + "_shape", self.const(nm + "_zero", np.asarray([0], np.int64))], [nm + "_n"], [attr_i("axis", 0)], name=nm + "_n"))
+                self.nodes.append(node("Concat", [nm + "_n", self.const(nm + "_rest", np.asarray(t1[1:], np.int64))], [nm + "_t1"], [attr_i("axis", 0)], name=nm + "_t1"))
+                t1_in = nm + "_t1"
+            else:
+                t1_in = self.const(nm + "_t1", np.asarray(t1, np.int64))
+            self.nodes.append(node("Reshape", [x, t1_in], [nm + "_6d"], name=nm + "_split"))
+            self.nodes.append(node("Transpose", [nm + "_6d"], [nm + "_t"], [attr_ints("perm", perm or pm)], name=nm + "_perm"))
+            self.nodes.append(node("Reshape", [nm + "_t", self.const(nm + "_t2", np.asarray([lead] + list(oshape), np.int64))], [nm], name=nm + "_merge"))
+        self.layers.append(("shuffle", nm, [x], dict(form=form, b=(bh, bw))))
+        return nm, oshape
+
     def finish(self, name, x_info, out, out_dims, opset=13, extra=None):
         spec = {"layers": self.layers, "output": out}
         spec.update(extra or {})
@@ -3249,6 +3282,8 @@ def decoder_reference(spec: dict, x, upto: str | None = None) -> np.ndarray:
             y = resize_reference(a, sizes=p["sizes"], scales=p["scales"], mode=p["mode"], coord=p["coord"], nearest_mode=p["nearest_mode"])
         elif op == "reshape":
             y = a.reshape((len(a),) + tuple(p["shape"]))
+        elif op == "shuffle":
+            y = pixel_shuffle_apply(a, p["form"], p["b"])
         elif op in ("inorm", "gnorm"):
             y = spatialnorm_reference(a, p["groups"], p["gamma"], p["beta"], p["eps"])
         elif op == "silu":
@@ -3257,6 +3292,8 @@ def decoder_reference(spec: dict, x, upto: str | None = None) -> np.ndarray:
             y = a + vals[ins[1]]
         elif op == "sub":
             y = a - vals[ins[1]]
+        elif op == "gap":
+            y = a.mean(axis=(2, 3), keepdims=True)
         elif op == "sumsquare":
             y = (a * a).sum(axis=1)
         else:
@@ -4894,3 +4931,85 @@ def rotary_model(T: int, h: int, dh: int, rotary=True, opset: int = 23, batch: i
     nodes, inits = [node("Reshape", ["X", "x_shape"], ["x3"])], [tensor("x_shape", np.asarray([-1, T, E], dtype=np.int64))]
     out = rotary_op_nodes(nodes, inits, "r_", "x3", cos, sin, rot["interleaved"], rot["rd"], kw.pop("num_heads", h), pos, **kw)
     return model("rotary", nodes, inits, [value_info("X", [batch, T * E])], [value_info(out, [batch, T, E])], opset=opset)
+
+
+# ------------------------------------------------------------------------------------------
+# Sub-pixel layers: DepthToSpace, SpaceToDepth and their Reshape -> Transpose -> Reshape spellings
+# ------------------------------------------------------------------------------------------
+# form -> (the first Reshape's 6-D target, by name; the Transpose's perm).  b1 / b2 = the block's rows / columns, Cs = C / (b1 b2)
+PIXEL_SHUFFLE_SPELLINGS = {
+    "dcr": (("N", "b1", "b2", "Cs", "H", "W"), (0, 3, 4, 1, 5, 2)),
+    "crd": (("N", "Cs", "b1", "b2", "H", "W"), (0, 1, 4, 2, 5, 3)),
+    "s2d": (("N", "C", "Hb", "b1", "Wb", "b2"), (0, 3, 5, 1, 2, 4)),
+    "unshuffle": (("N", "C", "Hb", "b1", "Wb", "b2"), (0, 1, 3, 5, 2, 4)),
+}
+
+
+def pixel_shuffle_apply(x, form: str, b) -> np.ndarray:
+    """A sub-pixel layer over x [N, C, H, W] as the specification writes it: reshape to six axes, transpose, reshape.  The values are moved,
+    never changed, so the result has x's dtype.  b: the block size or (b_h, b_w)."""
+    x = np.asarray(x)
+    bh, bw = _pair(b)
+    n, c, h, w = x.shape
+    six, perm = PIXEL_SHUFFLE_SPELLINGS[form]
+    dims = dict(N=n, b1=bh, b2=bw, Cs=c // (bh * bw), C=c, H=h, W=w, Hb=h // bh, Wb=w // bw)
+    out = (n, c // (bh * bw), h * bh, w * bw) if form in ("dcr", "crd") else (n, c * bh * bw, h // bh, w // bw)
+    return x.reshape([dims[k] for k in six]).transpose(perm).reshape(out)
+
+
+def pixel_shuffle_model(form: str = "crd", b=2, c: int = 16, hw=(3, 5), spelling: bool = False, pre: bool = False, post: bool = False, opset: int = 13,
+                        extra_outputs: Sequence[str] = (), **kw) -> tuple[bytes, dict]:
+    """One sub-pixel layer 'ps' over X [N, c, *hw] (_DecoderNet.shuffle has the forms and the spelling's options).  pre: an identity 1x1 Conv in
+    front (the layer then reads a channel-quad tensor where c is whole quads); post: an identity 1x1 ConvTranspose behind it (the layer then
+    writes one).  extra_outputs: further graph outputs by value name ('ps_6d', 'ps_t': the spelling's intermediates).  Returns (model, spec)."""
+    net = _DecoderNet(0)
+    cur = "X"
+    if pre:
+        cur = net.conv(cur, c, c, 1, 1, 0, bias=False, w=np.eye(c, dtype=np.float32)[:, :, None, None])
+    cur, oshape = net.shuffle(cur, c, hw, form, b, spelling=spelling, name="ps", **kw)
+    if post:
+        cur = net.convt(cur, oshape[0], oshape[0], 1, 1, 0, bias=False, w=np.eye(oshape[0], dtype=np.float32)[:, :, None, None])
+    in_shape = (c,) + tuple(hw)
+    spec = {"layers": net.layers, "output": cur, "in_shape": in_shape, "out_shape": oshape}
+    outs = [value_info(cur, ["N"] + list(oshape))] + [value_info(o, []) for o in extra_outputs]
+    return model("pixel_shuffle", net.nodes, net.inits, [value_info("X", ["N"] + list(in_shape))], outs, opset=opset), spec
+
+
+def pixel_shuffle_pair_model(form: str = "crd", b: int = 2, c: int = 16, hw=(3, 5), pre: bool = False, post: bool = False) -> tuple[bytes, dict]:
+    """DepthToSpace of X [N, c, *hw] followed by the matching space-to-depth form (dcr: SpaceToDepth; crd: the pixel_unshuffle spelling): the
+    identity.  pre / post as in pixel_shuffle_model."""
+    net = _DecoderNet(0)
+    cur = "X"
+    if pre:
+        cur = net.conv(cur, c, c, 1, 1, 0, bias=False, w=np.eye(c, dtype=np.float32)[:, :, None, None])
+    cur, mid = net.shuffle(cur, c, hw, form, b, name="up")
+    cur, back = net.shuffle(cur, mid[0], mid[1:], "s2d" if form == "dcr" else "unshuffle", b, spelling=form != "dcr", name="down")
+    if post:
+        cur = net.convt(cur, c, c, 1, 1, 0, bias=False, w=np.eye(c, dtype=np.float32)[:, :, None, None])
+    in_shape = (c,) + tuple(hw)
+    return net.finish("pixel_shuffle_pair", value_info("X", ["N"] + list(in_shape)), cur, ["N"] + list(in_shape), extra={"in_shape": in_shape, "out_shape": tuple(back)})
+
+
+def espcn(b: int = 2, in_ch: int = 3, size: int = 12, widths: Sequence[int] = (16, 8), seed: int = 91, spelling: bool = False, opset: int = 13) -> tuple[bytes, dict]:
+    """ESPCN-shaped super-resolution: Conv 5x5 + Tanh -> Conv 3x3 + Tanh -> Conv 3x3 to in_ch * b^2 channels -> PixelShuffle (DepthToSpace CRD, what
+    torch writes for nn.PixelShuffle from opset 11 on; spelling: the Reshape -> Transpose -> Reshape form of older opsets)."""
+    net = _DecoderNet(seed)
+    cur = net.act(net.conv("X", in_ch, widths[0], 5, 1, 2), "Tanh")
+    cur = net.act(net.conv(cur, widths[0], widths[1], 3, 1, 1), "Tanh")
+    cur = net.conv(cur, widths[1], in_ch * b * b, 3, 1, 1)
+    cur, oshape = net.shuffle(cur, in_ch * b * b, (size, size), "crd", b, spelling=spelling, name="ps")
+    return net.finish("espcn", value_info("X", ["N", in_ch, size, size]), cur, ["N"] + list(oshape), opset=opset, extra={"in_shape": (in_ch, size, size), "out_shape": oshape})
+
+
+def pixel_unshuffle_stem(b: int = 2, in_ch: int = 3, size: int = 12, width: int = 16, classes: int = 8, seed: int = 93) -> tuple[bytes, dict]:
+    """The SpaceToDepth stem of TResNet / Real-ESRGAN: pixel_unshuffle of the image (its Reshape -> Transpose -> Reshape spelling) -> Conv 3x3 + Relu
+    -> Conv 1x1 to `classes` channels -> GlobalAveragePool -> Flatten: [N, classes]."""
+    net = _DecoderNet(seed)
+    cur, s = net.shuffle("X", in_ch, (size, size), "unshuffle", b, spelling=True, name="ps")
+    cur = net.act(net.conv(cur, s[0], width, 3, 1, 1), "Relu")
+    cur = net.conv(cur, width, classes, 1, 1, 0)
+    net.nodes.append(node("GlobalAveragePool", [cur], ["gap"], name="gap"))
+    net.layers.append(("gap", "gap", [cur], {}))
+    net.nodes.append(node("Flatten", ["gap"], ["scores"], [attr_i("axis", 1)], name="flatten"))
+    net.layers.append(("reshape", "scores", ["gap"], dict(shape=(classes,))))
+    return net.finish("pixel_unshuffle_stem", value_info("X", ["N", in_ch, size, size]), "scores", ["N", classes], extra={"in_shape": (in_ch, size, size)})
