@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from infera_amd import onnx_writer as W
+from tests import spatial_norm_cases as SC
 
 try:
     import torch
@@ -116,6 +117,26 @@ def test_parity_bar_at_offsets_0_and_1000(api, tmp_path, monkeypatch, c, layout,
 def norm_act(m):
     (s,) = [s for s in m.plan["plan"]["steps"] if s["kind"] == "ChannelNorm"]
     return s.get("act")
+
+
+@pytest.mark.parametrize("kind", list(SC.VALUE_KINDS))
+def test_value_edges(api, tmp_path, monkeypatch, kind):
+    """The same bar at the value edges of tests/spatial_norm_cases.py, one pixel's channels being one group: 2^40 U(-1, 1); 2^-20 U(-1, 1)
+    under epsilon = 1e-12, comparable to the variance; 2^-10 U(-1, 1), where epsilon is 30 times the variance; one channel of every pixel
+    at 1e4, also on a common offset of 1000.  (The Relu in front clips the negatives; the reference does the same.)"""
+    hw, n, worst = (5, 13), 3, 0.0
+    eps = SC.VALUE_KINDS[kind][1]
+    for c, layout, form in [p for p in PARITY if p[0] in (3, 8, 100, REGS_MAX_C + 4)]:
+        blob, spec = W.channel_norm_model(c, hw, spelling="layernorm2d", front=FRONTS[layout], eps=eps)
+        with serve(api, tmp_path, monkeypatch, blob, form) as m:
+            check_step(m, c, layout, form)
+            for offset in (0.0, 1000.0) if kind == "outlier" else (0.0,):
+                pixels = SC.value_groups(n * hw[0] * hw[1], c, kind, seed=400 + c, offset=offset)
+                x = np.ascontiguousarray(pixels.reshape((n,) + hw + (c,)).transpose(0, 3, 1, 2))
+                ratio = bar_ratio(m(x), W.channel_norm_reference(spec, x).reshape(n, -1))
+                worst = max(worst, ratio)
+                assert ratio <= 1.0, (c, layout, form, offset, ratio)
+    print(f"\n{kind}: worst max |err| / (rtol |ref| + atol) = {worst:.4f}")
 
 
 # ---- results known bit for bit -----------------------------------------------------------------------------------------------------
