@@ -65,6 +65,7 @@ struct TreeReduceTables { const float *base = nullptr, *labels = nullptr; };
 struct SvmKernelTables { const float *sv = nullptr, *coef = nullptr, *sv_norm = nullptr, *center = nullptr; const uint32_t *slice_tile = nullptr; };
 struct SvmReduceTables { const float *rho = nullptr, *labels = nullptr, *prob_a = nullptr, *prob_b = nullptr; const uint32_t *class_slice = nullptr; };
 struct NearestTables { const float *ref = nullptr, *ref_norm = nullptr, *center = nullptr; const uint32_t *slice_tile = nullptr; };
+struct NearestVoteTables { const int32_t *cls = nullptr; const float *target = nullptr, *class_value = nullptr; };  // NearestVote (host/nearest.hpp VotePack)
 struct PrepTables { const uint32_t *desc = nullptr; const float *cst = nullptr, *tab = nullptr; };
 struct ConvTKernelTables { const float *W = nullptr, *bias = nullptr; const int *tab = nullptr; };  // ConvTranspose2d (W: packed for the step's kernel; tab: the phase tap tables)
 struct ResizeTables { const int *row_idx = nullptr, *col_idx = nullptr; const float *row_wgt = nullptr, *col_wgt = nullptr; };  // Resize2d
@@ -84,6 +85,7 @@ struct DeviceStep {  // (a step fills the one struct of its family)
   SvmKernelTables svm_kernel;
   SvmReduceTables svm_reduce;
   NearestTables nearest;
+  NearestVoteTables nearest_vote;
   PrepTables prep;
   RnnTables rnn;
   ConvTKernelTables convt;

@@ -78,6 +78,11 @@ bool nearest(hipStream_t s, const float *x, int F, int F_pad, const float *cente
              float *out, int64_t rows, int S, int M, int k, int mode);
 // the slices merged in slice order -> the label [rows], the k nearest indices or their (sqrt) distances [rows, k]
 void nearest_reduce(hipStream_t s, const float *part, float *y, int64_t rows, int S, int k, int mode);
+// the k-NN vote over the same lists (host/nearest.hpp VotePack, VoteOut): cls [M] class indices in 0 .. C - 1 / target [M] (the one the
+// mode reads), class_value [C]; y = the label [rows], the probabilities [rows, C] or the value [rows, 1].  w = 1 (uniform) or
+// 1 / max(d, eps), d = d2 or sqrt(d2) (rooted).  false: the form is outside the kernel (C above kVoteMaxProbaClasses, k outside 1 .. min(16, M))
+bool nearest_vote(hipStream_t s, const float *part, const int *cls, const float *target, const float *class_value, float *y, int64_t rows, int S, int M, int k,
+                  int C, int mode, bool weighted, bool rooted, float eps);
 
 // ---- reductions along the feature axis (reduce.hip) ----------------------------------------------
 // y[v] = reduction op (host/plan.hpp ReduceOp) over the E elements of each of nvec vectors

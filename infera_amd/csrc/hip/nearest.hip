@@ -137,6 +137,115 @@ __global__ __launch_bounds__(64) void nearest_reduce_kernel(const float *__restr
   }
 }
 
+// The k-NN vote (INTEGRATION.md section 2.6 "The k-NN vote"): the merge of nearest_reduce_kernel, then the neighbours' classes / targets
+// from the constant tables (plain 4-byte gathers, the tables stay in L2), the weights and the tally.  One lane per row; a block is ONE
+// wave, which walks 64-row tiles with a stride.  Every sum runs over ascending neighbour j from 0.f and nothing is contracted into an
+// FMA, so an f32 restatement reproduces the bits.  The tally keeps no per-class array: tot[j] = the total of neighbour j's class is k
+// compare-adds over the list in VGPRs (K^2 after unrolling), the class-0 total starts the first-maximum scan (as the ArgMax step's scan
+// starts at element 0: a NaN there stays) and a later class wins where its total compares greater, ties to the lower class.
+// Probabilities: the wave zeroes a [64, C] tile in LDS (64 C 4 B <= 64 KB: C <= 256, host/nearest.hpp), every lane drops its <= k
+// totals into its row, and the tile -- which is one contiguous run of the [rows, C] output -- leaves linearly, a 16-byte piece per lane
+// (scalar where the run is not 16-byte aligned or ends), each element divided by its row's weight sum fetched from the owning lane.
+// Bound designed for: the bytes of the lists read (8 K S per row) plus the output written (4, or 4 C), at the HBM rate.  Known cost
+// outside that bound: a lane reads its own row's lists (row-strided 4-byte loads, as nearest_reduce_kernel), and the <= k scattered
+// LDS writes of a row conflict when C is even (row stride C floats).  Measured: DESIGN.md section 3.13.
+constexpr unsigned kVoteGridCap = 4096;
+
+template <int K>
+__global__ __launch_bounds__(64) void nearest_vote_kernel(const float *__restrict__ part, const int *__restrict__ cls, const float *__restrict__ target,
+                                                         const float *__restrict__ class_value, float *__restrict__ y, int64_t nr, int S, int M, int k, int C,
+                                                         int mode, bool weighted, bool rooted, float eps) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int lane = int(threadIdx.x);
+  for (int64_t base = int64_t(blockIdx.x) * 64; base < nr; base += int64_t(gridDim.x) * 64) {
+    const int64_t row = base + lane;
+    const bool live = row < nr;
+    BestList<K> best;
+    best.clear();
+    if (live)
+      for (int s = 0; s < S; s++) {
+        const float *p = part + (row * S + s) * (2 * K);
+#pragma unroll
+        for (int j = 0; j < K; j++) best.insert(p[j], __float_as_int(p[K + j]));
+      }
+    // k <= M of the entries are reference vectors; the guard keeps a gather inside its table whatever the lists hold
+    int at[K];
+    float w[K], sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      at[j] = unsigned(best.i[j]) < unsigned(M) ? best.i[j] : 0;
+      const float d = rooted ? sqrtf(best.v[j]) : best.v[j];
+      w[j] = !weighted ? 1.f : d != d ? d : 1.f / fmaxf(d, eps);  // (a NaN distance is a NaN weight: ONNX Max keeps the NaN, fmaxf would drop it)
+      if (j < k) sum += w[j];
+    }
+    if (mode == kVoteValue) {
+      float a = 0.f;
+#pragma unroll
+      for (int j = 0; j < K; j++)
+        if (j < k) {
+          const float t = live ? target[at[j]] : 0.f;
+          a += weighted ? w[j] * t : t;
+        }
+      if (live) y[row] = a / (weighted ? sum : float(k));
+      continue;
+    }
+    int c[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) c[j] = live && j < k ? cls[at[j]] : -1;
+    float tot[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      float a = 0.f;
+#pragma unroll
+      for (int i = 0; i < K; i++)
+        if (i < k && c[i] == c[j]) a += w[i];
+      tot[j] = a;
+    }
+    if (mode == kVoteLabel) {
+      float bv = 0.f;  // the total of class 0 (0.f when no neighbour carries it)
+#pragma unroll
+      for (int j = 0; j < K; j++)
+        if (j < k && c[j] == 0) bv = tot[j];
+      int bc = 0;
+#pragma unroll
+      for (int j = 0; j < K; j++)
+        if (j < k && (tot[j] > bv || (tot[j] == bv && c[j] < bc))) bv = tot[j], bc = c[j];
+      if (live) y[row] = class_value[bc];
+      continue;
+    }
+    // kVoteProba: rows base .. base + n - 1 are one run of n C floats of the output
+    const int n = int(nr - base < 64 ? nr - base : 64), total = n * C;
+    for (int e = 4 * lane; e < total; e += 256) *reinterpret_cast<f32x4 *>(lds + e) = f32x4{0.f, 0.f, 0.f, 0.f};  // (64 C is a multiple of 4: e + 3 stays inside)
+    __syncthreads();
+    if (live) {
+#pragma unroll
+      for (int j = 0; j < K; j++)
+        if (j < k) lds[lane * C + c[j]] = tot[j];  // (neighbours of one class write the same total)
+    }
+    __syncthreads();
+    float *out = y + base * C;
+    const bool wide = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    for (int e0 = 0; e0 < total; e0 += 256) {  // (the same trip count in every lane: each takes part in the shuffles)
+      const int e = e0 + 4 * lane;
+      f32x4 v = e < total ? *reinterpret_cast<const f32x4 *>(lds + e) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int r = (e + q) / C;
+        v[q] = v[q] / __shfl(sum, r < 63 ? r : 63);
+      }
+      if (wide && e + 3 < total) {
+        *reinterpret_cast<f32x4 *>(out + e) = v;
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+          if (e + q < total) out[e + q] = v[q];
+      }
+    }
+    __syncthreads();  // (the next tile zeroes what this one still reads)
+  }
+}
+
 template <int K>
 bool launch(hipStream_t s, const float *x, int F, int F_pad, const float *center, const float *ref, const float *ref_norm, const uint32_t *slice_tile,
             float *out, int64_t rows, int S, int M, bool rooted) {
@@ -172,6 +281,19 @@ void nearest_reduce(hipStream_t s, const float *part, float *y, int64_t rows, in
     case 1: hipLaunchKernelGGL(nearest_reduce_kernel<1>, dim3(g), dim3(64), 0, s, part, y, rows, S, k, mode); break;
     default: hipLaunchKernelGGL(nearest_reduce_kernel<16>, dim3(g), dim3(64), 0, s, part, y, rows, S, k, mode); break;
   }
+}
+
+bool nearest_vote(hipStream_t s, const float *part, const int *cls, const float *target, const float *class_value, float *y, int64_t rows, int S, int M, int k,
+                  int C, int mode, bool weighted, bool rooted, float eps) {
+  if (rows <= 0) return true;
+  const size_t lds = mode == kVoteProba ? size_t(64) * size_t(C) * 4 : 0;
+  if (lds > size_t(kLdsBudget) || k < 1 || k > M || k > int(kNearestMaxK)) return false;
+  const unsigned g = unsigned(std::min<int64_t>(kVoteGridCap, (rows + 63) / 64));
+  switch (nearest_list_width(k)) {
+    case 1: hipLaunchKernelGGL(nearest_vote_kernel<1>, dim3(g), dim3(64), lds, s, part, cls, target, class_value, y, rows, S, M, k, C, mode, weighted, rooted, eps); break;
+    default: hipLaunchKernelGGL(nearest_vote_kernel<16>, dim3(g), dim3(64), lds, s, part, cls, target, class_value, y, rows, S, M, k, C, mode, weighted, rooted, eps); break;
+  }
+  return true;
 }
 
 }  // namespace infera_hip::kern

@@ -322,6 +322,19 @@ void launch_nearest(const PassRunner &r, const Step &x, const NearestTables &t) 
     throw InferaError::onnx("nearest kernel launch failed: '" + x.origin + "' could not be given its LDS");
 }
 
+// the k-NN vote over a Nearest step's lists (host/nearest.hpp VotePack)
+void upload_nearest_vote(const Step &s, NearestVoteTables &t, const Upload &up) {
+  t.cls = up(s.vote->cls);
+  t.target = up(s.vote->target);
+  t.class_value = up(s.vote->class_value);
+}
+void launch_nearest_vote(const PassRunner &r, const Step &x, const NearestVoteTables &t) {
+  const VotePack &v = *x.vote;
+  if (!kern::nearest_vote(r.stream, r.buf(x.in0), t.cls, t.target, t.class_value, r.buf(x.out), r.nr, int(x.nearest->slices), int(x.nearest->M), int(x.M),
+                          int(v.classes), x.out_mode, v.weighted, v.rooted, v.eps))
+    throw InferaError::onnx("nearest vote kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+
 // ---- preprocessing regions (host/prep.hpp PrepPack, prep.hip) ----
 void upload_prep(const Step &s, PrepTables &t, const Upload &up) {
   t.desc = up(s.prep->desc);
@@ -534,6 +547,7 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::SvmKernel: launch_svm_kernel(*this, x, d.svm_kernel); break;
     case StepKind::SvmReduce: launch_svm_reduce(*this, x, d.svm_reduce); break;
     case StepKind::Nearest: launch_nearest(*this, x, d.nearest); break;
+    case StepKind::NearestVote: launch_nearest_vote(*this, x, d.nearest_vote); break;
     case StepKind::Prep: launch_prep(*this, x, d.prep); break;
     case StepKind::Recurrent: launch_rnn(*this, x, d.rnn); break;
     case StepKind::ConvTranspose2d: launch_convt(*this, i, d.convt); break;
@@ -610,6 +624,7 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::SvmKernel: return upload_svm_kernel(s, d.svm_kernel, up);
     case StepKind::SvmReduce: return upload_svm_reduce(s, d.svm_reduce, up);
     case StepKind::Nearest: return upload_nearest(s, d.nearest, up);
+    case StepKind::NearestVote: return upload_nearest_vote(s, d.nearest_vote, up);
     case StepKind::Prep: return upload_prep(s, d.prep, up);
     case StepKind::Recurrent: return upload_rnn(s, d.rnn, up);
     case StepKind::ConvTranspose2d: return upload_convt(up, i, d.convt);

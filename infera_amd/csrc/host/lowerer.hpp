@@ -353,6 +353,36 @@ struct Lowerer {
     std::vector<size_t> nodes;  // ascending; the last is the anchor
   };
   std::map<size_t, NearestMatch> nearest_at;  // anchor node index -> the pattern it closes
+  // The k-NN vote (KNeighborsClassifier / KNeighborsRegressor; INTEGRATION.md 2.6 "The k-NN vote"): behind TopK(largest = 0) over such a
+  // distance value, the neighbours' labels / targets looked up in a constant table (ArrayFeatureExtractor | Gather, [Reshape] [Cast]
+  // [Squeeze]), the weights Reciprocal | Div(1, .) of Max(values, eps), and
+  //   classifier: per class c, Equal(lab, c) -> Cast -> [Mul(., wei)] -> ReduceSum(axes = [1]) [-> Unsqueeze], joined by Concat(axis = 1)
+  //               (or Concat(axis = 0) -> Transpose); closed by ArgMax (-> the class table lookup [-> Reshape / Cast]) or by
+  //               Div(all, ReduceSum(all, axes = [1], keepdims = 1));
+  //   regressor:  ReduceMean(lab, axes = [1]) | Div(ReduceSum(Mul(lab, wei)), ReduceSum(wei)) [-> Reshape([-1, 1])].
+  // Found structurally before the walk (find_votes: operators, constants and sole readers), anchored at the closing node.  The nodes
+  // inside emit nothing.  When the walk reaches the TopK and its input is a pending distance value, the vote is taken (vote_begin: Values
+  // / Indices keep only their readers outside the pattern); otherwise the nodes are given back and lower by their own rules, as without
+  // the matcher.  The anchor checks the constants and emits ONE NearestVote step on the best-k lists (lower_vote).
+  struct VoteMatch {
+    size_t topk = 0, anchor = 0, lookup = 0;
+    size_t reshape = SIZE_MAX, clamp = SIZE_MAX, concat = SIZE_MAX, class_lookup = SIZE_MAX;  // nodes the checks name (SIZE_MAX: absent)
+    int mode = 0;  // VoteOut
+    bool weighted = false, sqrt_values = false;  // sqrt_values: a Sqrt stands on the TopK values
+    std::string table, eps, classes;             // constants: the lookup's table, Max's bound, the class values ("": 0 .. C - 1)
+    std::vector<size_t> equals;                  // the Equal node of each branch, in Concat order
+    std::vector<std::string> equal_consts;
+    std::string out;                             // the value the step is bound to
+    bool out_col = false;                        // ... has shape [N, 1] (else [N]; probabilities: [N, C])
+    std::vector<size_t> nodes;                   // the nodes that emit nothing (neither the TopK nor the anchor)
+    // set by vote_begin
+    std::shared_ptr<NearestPending> np;
+    int lists = -1;
+    int64_t k = 0;
+  };
+  std::map<size_t, VoteMatch> vote_at;      // anchor node index -> the pattern it closes
+  std::map<size_t, size_t> vote_of_topk;    // TopK node index -> that anchor
+  std::vector<char> vote_inside;            // nodes inside a vote pattern
 
   // ---- embedding lookups (host/embed.hpp; INTEGRATION.md 2.6 "Embedding lookups") ------------------------------------------------------
   // Gather(axis = 0) of a constant f32 table [V, d] / [V] by indices that are columns of a graph input: the column picks (Gather(axis = 1) /
@@ -723,6 +753,14 @@ struct Lowerer {
   // the best-k lists of a pending distance value (one Nearest step per k)
   int nearest_lists(NearestPending &np, int64_t k);
   bool nearest_reader(const NodeDef &n);
+  // the k-NN vote: the matcher, the decision at the TopK (take the pattern or give its nodes back) and the step at the anchor
+  bool vote_axis1(const NodeDef &n) const;
+  bool match_vote_lookup(const std::string &lab, VoteMatch *vm) const;
+  bool match_vote_weights(const std::string &wei, VoteMatch *vm) const;
+  bool match_vote_tally(const std::string &all, VoteMatch *vm, std::string *wei) const;
+  void find_votes();
+  void vote_begin(size_t anchor);
+  void lower_vote(const VoteMatch &vm);
 
   // ---- lower_embed.cpp: embedding lookups ----
   // an integer constant known before the walk: an initializer or a Constant node

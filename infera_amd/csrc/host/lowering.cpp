@@ -3538,6 +3538,7 @@ namespace lowering {
       case StepKind::ArgMin:
       case StepKind::TopK:
       case StepKind::NearestReduce: return true;
+      case StepKind::NearestVote: return s.out_mode == kVoteLabel;  // (a class value picked from a table; the other modes divide)
       case StepKind::Tokens: return s.cst.empty();  // (movement alone; a half graph's position Add is never folded)
       case StepKind::RowReduce: return s.out_mode == kReduceMax || s.out_mode == kReduceMin;
       case StepKind::Pool2d:
@@ -4321,6 +4322,7 @@ namespace lowering {
     find_attention();
     check_rotary_ops();
     if (nearest_enabled) find_nearest();
+    if (nearest_enabled) find_votes();  // (INFERA_NEAREST=0 has no plan for the vote: Equal stays unsupported, the load is refused as without the matcher)
     find_group_norms();
     find_pixel_shuffles();
     find_embeds();
@@ -4357,6 +4359,8 @@ namespace lowering {
       if (!live[ni]) continue;
       const auto &n = m.nodes[ni];
       if (n.outputs.empty()) throw InferaError::onnx("node " + n.op + " has no outputs");
+      if (auto vt = vote_of_topk.find(ni); vt != vote_of_topk.end()) vote_begin(vt->second);  // (takes the k-NN vote behind this TopK, or gives its nodes back)
+      if (!vote_inside.empty() && vote_inside[ni]) continue;
       if (region[ni] || n.domain == "ai.onnx.ml") check_row_axis(n, false);
       if (region[ni]) prep_node(n);
       else if (n.domain == "ai.onnx.ml") ml_node(n);
@@ -4370,6 +4374,7 @@ namespace lowering {
         unsupported(n, "operator domain '" + n.domain + "'");
       } else if (attn_at.count(ni)) lower_typed(n, [&] { lower_attention(attn_at.at(ni), n); });
       else if (nearest_at.count(ni)) lower_nearest(nearest_at.at(ni));
+      else if (vote_at.count(ni) && vote_at.at(ni).np) lower_vote(vote_at.at(ni));
       else if (embed_at.count(ni)) lower_embed(embed_at.at(ni), n);
       else if (interact_at.count(ni)) {
         const InteractMatch &im = interact_at.at(ni);

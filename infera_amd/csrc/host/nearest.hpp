@@ -50,4 +50,26 @@ struct NearestPack {
 // Packs the reference set C [M, F] (row-major).  Throws NearestError with the reason when a cap is exceeded.
 NearestPack pack_nearest(const float *C, int64_t M, int64_t F, const std::string &spelling);
 
+// ---- the k-NN vote (KNeighborsClassifier / KNeighborsRegressor; definition: INTEGRATION.md section 2.6 "The k-NN vote") ----
+// NearestVote output modes (Step::out_mode)
+enum VoteOut : int {
+  kVoteLabel = 0,  // class_value of the first maximum of the class totals [rows]
+  kVoteProba = 1,  // the class totals over their sum [rows, C]
+  kVoteValue = 2,  // the (weighted) mean of the neighbours' targets [rows, 1]
+};
+// Probability rows leave a wave through LDS, 64 rows x C floats at a time within the kernel's 64 KB: C <= 256 (rejected above it at
+// load).  The label and the regression value are tallied in registers and have no class cap.
+constexpr int64_t kVoteMaxProbaClasses = 256;
+constexpr float kVoteMaxClassValue = 16777216.f;  // 2^24: labels are served as f32 values
+
+struct VotePack {
+  std::vector<int32_t> cls;        // class index of each reference vector [M] (classifier)
+  std::vector<float> target;       // target of each reference vector [M] (regressor)
+  std::vector<float> class_value;  // the served label of each class [C]
+  int64_t classes = 0;
+  float eps = 0.f;        // w = 1 / max(d, eps) (weighted)
+  bool weighted = false;  // distance weights (else uniform)
+  bool rooted = false;    // d = sqrt(d2) (else d2)
+};
+
 }  // namespace infera_hip

@@ -30,6 +30,7 @@ double Plan::flops_per_row() const {
     else if (s.kind == StepKind::ConvTranspose2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.H) * double(s.Wd);  // (C/g) kh kw taps per input pixel and output channel
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
     else if (s.kind == StepKind::Nearest) f += 2.0 * double(s.nearest->F) * double(s.nearest->M);
+    else if (s.kind == StepKind::NearestVote) f += 2.0 * double(s.M);  // a weight and an add per neighbour
     else if (s.kind == StepKind::Interact) f += s.interact->mode == kInteractDot ? 2.0 * double(s.interact->k * s.interact->k * s.interact->d) : 4.0 * double(s.interact->k * s.interact->d);
     else if (s.kind == StepKind::Rotary) f += 3.0 * double(s.attn_T * s.attn_heads * s.rot_rd);  // two products and a sum per rotated column
     else if (s.kind == StepKind::Recurrent) f += 2.0 * double(s.rnn->T * s.rnn->D * s.rnn->G * s.rnn->H) * double(s.rnn->F + s.rnn->H);
@@ -38,7 +39,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary", "PixelShuffle"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary", "PixelShuffle", "NearestVote"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -113,6 +114,12 @@ std::string Plan::describe_json() const {
       const NearestPack &q = *s.nearest;
       o << ",\"nearest\":{\"F\":" << q.F << ",\"M\":" << q.M << ",\"k\":" << s.M << ",\"outputs\":\"" << modes[s.out_mode] << "\",\"slices\":" << q.slices
         << ",\"slice_tile\":" << json_int_array(std::vector<int64_t>(q.slice_tile.begin(), q.slice_tile.end())) << ",\"spelling\":\"" << q.spelling << "\",\"centred\":true}";
+    }
+    if (s.kind == StepKind::NearestVote) {
+      static const char *outs[] = {"label", "probabilities", "value"};
+      o << ",\"k\":" << s.M << ",\"classes\":" << s.vote->classes << ",\"weights\":\"" << (s.vote->weighted ? "distance" : "uniform") << "\",\"outputs\":\"" << outs[s.out_mode]
+        << "\",\"rooted\":" << (s.vote->rooted ? "true" : "false") << ",\"M\":" << s.nearest->M << ",\"slices\":" << s.nearest->slices;
+      if (s.vote->weighted) o << ",\"eps\":" << json_f32(s.vote->eps);
     }
     if (s.kind == StepKind::Attention)
       o << ",\"T\":" << s.attn_T << ",\"heads\":" << s.attn_heads << ",\"dh\":" << s.attn_dh << ",\"scale\":" << double(s.attn_scale) << ",\"mask\":" << (s.cst.empty() ? "false" : "true")

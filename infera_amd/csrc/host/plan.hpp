@@ -20,6 +20,7 @@ struct SvmPack;   // host/svm.hpp
 struct PrepPack;  // host/prep.hpp
 struct RnnPack;   // host/recurrent.hpp
 struct NearestPack;  // host/nearest.hpp
+struct VotePack;     // host/nearest.hpp
 struct DeconvPack;   // host/deconv.hpp
 struct EmbedPack;    // host/embed.hpp
 struct InteractPack;  // host/interact.hpp
@@ -70,6 +71,7 @@ enum class StepKind : int {
   TopK = 31,          // the M (<= 16) smallest / largest (is_max) of in0[r, 0:K], sorted, equal values by lower index, NaN last: out [rows, M] = the values (out_mode 0) or the indices as f32 values (1)
   Nearest = 32,       // distances of in0 [rows, F] to a constant set (NearestPack, nearest.hip): out = d2 / sqrt(d2) [rows, set size], or the per-slice best-M lists (out_mode: host/nearest.hpp NearestOut)
   NearestReduce = 33, // in0 = those lists -> the label [rows], the M nearest indices or their distances [rows, M]
+  NearestVote = 45,   // in0 = those lists -> the k-NN vote of the M nearest (VotePack, host/nearest.hpp): the class label [rows], the class probabilities [rows, C] or the regression value [rows, 1] (out_mode: VoteOut)
   HDense = 28,        // float16 MatMul / Gemm on the f16 matrix cores: half operands, f32 accumulation, half results served as f32 values (Step::hW, h_bias_mode; hdense.hip)
   ConvTranspose2d = 34,  // transposed convolution by stride phases (the Conv2d geometry fields: C, H, Wd = the input, Mo, OH, OW = the output; W = the ONNX weights [C, M/g, kh, kw]; DeconvPack: the phase tap lists; deconv.hip)
   SpatialNorm = 36,   // InstanceNormalization / GroupNormalization over the (C / groups) * S elements of each of `groups` channel groups of in0 [rows, C, S]: y = act((x - mean) / sqrt(var + ln_eps) * scale[c] + shift[c]); in1 = -1: the fused kernel, else in1 = a SpatialStats result (host/spatialnorm.hpp, spatialnorm.hip)
@@ -156,10 +158,11 @@ struct Step {
   std::shared_ptr<const PrepPack> prep;
   std::shared_ptr<const RnnPack> rnn;
   std::shared_ptr<const NearestPack> nearest;
+  std::shared_ptr<const VotePack> vote;  // NearestVote (beside `nearest`, the set whose lists it reads)
   std::shared_ptr<const EmbedPack> embed;
   std::shared_ptr<const InteractPack> interact;
   std::shared_ptr<const DeconvPack> deconv;  // ConvTranspose2d: phase tap lists; Resize2d: source tables
-  int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut, RowReduce: ReduceOp, TopK: 0 values / 1 indices, Nearest*: NearestOut
+  int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut, RowReduce: ReduceOp, TopK: 0 values / 1 indices, Nearest / NearestReduce: NearestOut, NearestVote: VoteOut
   // Attention: Q = in0, K = in1, V = in2 (the same buffer three times when the projections are merged), each [rows, T, ld] with the head
   // block of head g at columns off + g * dh of a step; mask (cst): [T, T] added to the scaled scores, -inf = no weight, empty = none
   int in2 = -1;

@@ -2818,6 +2818,168 @@ def knn_search_from_spec(spec: dict, k: int = 5, output: str = "indices", spelli
     return _model_ms("knn", nodes, inits, [value_info("X", ["N", F])], outs)
 
 
+def _knn_vote_front(spec: dict, y, k: int, weights: str, spelling: str, lookup: str, reshape, cast_to, eps: float, reciprocal: str, table_dtype):
+    """The part the classifier and the regressor share: the search head of knn_search_from_spec (Euclidean values: CDist's own metric, or
+    Sqrt on the TopK values of a gemm spelling), the lookup of `y` by the indices -> "knn_lab" [N, k] and, for weights = "distance", the
+    weights "knn_wei" [N, k].  Returns (nodes, inits)."""
+    if weights not in ("uniform", "distance"):
+        raise ValueError(weights)
+    if spelling == "cdist":
+        nodes, inits = _distance_nodes(spec, spelling, "X", "nn_d", metric="euclidean")
+        val = "distances"
+    else:
+        nodes, inits = _distance_nodes(spec, spelling, "X", "nn_d")
+        val = "nn_v2"
+    inits.append(tensor("nn_k", np.array([k], np.int64)))
+    nodes.append(node("TopK", ["nn_d", "nn_k"], [val, "indices"], [attr_i("axis", -1), attr_i("largest", 0), attr_i("sorted", 1)], name="topk"))
+    if val != "distances":
+        nodes.append(node("Sqrt", [val], ["distances"], name="sqrt_v"))
+    inits.append(tensor("knn_y", np.asarray(y).astype(table_dtype)))
+    if lookup == "afe":  # the ai.onnx.ml operator flattens: [1, N * k]
+        nodes.append(node("ArrayFeatureExtractor", ["knn_y", "indices"], ["knn_picked"], name="lookup", domain=ML_DOMAIN))
+        reshape = "k" if reshape is None else reshape
+    elif lookup == "gather":
+        nodes.append(node("Gather", ["knn_y", "indices"], ["knn_picked"], [attr_i("axis", 0)], name="lookup"))
+    else:
+        raise ValueError(lookup)
+    cur = "knn_picked"
+    if reshape in ("k", "k1"):
+        inits.append(tensor("knn_lab_shape", np.array([-1, k] if reshape == "k" else [-1, k, 1], np.int64)))
+        nodes.append(node("Reshape", [cur, "knn_lab_shape"], ["knn_shaped"], name="lookup_reshape"))
+        cur = "knn_shaped"
+    elif reshape not in (None, "none"):
+        raise ValueError(reshape)
+    if cast_to is not None:
+        nodes.append(node("Cast", [cur], ["knn_cast"], [attr_i("to", cast_to)], name="lookup_cast"))
+        cur = "knn_cast"
+    if reshape == "k1":
+        inits.append(tensor("knn_sq_axes", np.array([2], np.int64)))
+        nodes.append(node("Squeeze", [cur, "knn_sq_axes"], ["knn_squeezed"], name="lookup_squeeze"))
+        cur = "knn_squeezed"
+    lab = cur
+    if weights == "distance":
+        inits.append(tensor("knn_eps", np.array([eps], np.float32)))
+        nodes.append(node("Max", ["distances", "knn_eps"], ["knn_clamped"], name="clamp"))
+        if reciprocal == "reciprocal":
+            nodes.append(node("Reciprocal", ["knn_clamped"], ["knn_wei"], name="weights"))
+        elif reciprocal == "div":
+            inits.append(tensor("knn_one", np.array([1.0], np.float32)))
+            nodes.append(node("Div", ["knn_one", "knn_clamped"], ["knn_wei"], name="weights"))
+        else:
+            raise ValueError(reciprocal)
+    return nodes, inits, lab
+
+
+def knn_classifier_from_spec(spec: dict, y, classes, k: int = 5, weights: str = "uniform", output: str = "label", spelling: str = "cdist", zipmap: bool = False,
+                             lookup: str = "afe", keepdims: int = 1, join: str = "concat", reshape=None, cast: bool = False, eps: float = 1e-6,
+                             reciprocal: str = "reciprocal", final: str | None = None, also: Sequence[str] = (), equal_values=None,
+                             extra_reader: str | None = None) -> bytes:
+    """KNeighborsClassifier as skl2onnx writes it, restated: `y` [M] are the CLASS INDICES (0 .. C - 1) of the training rows, `classes` [C]
+    the int64 class values (classes_).  Outputs `label` [N] int64 and `probabilities` [N, C]; `output` names the first (served by default).
+
+    Recalled from the exporter's converter (convert_nearest_neighbors_classifier): the search head shared with NearestNeighbors; the
+    training labels looked up by ArrayFeatureExtractor and reshaped to [-1, k]; one Equal -> Cast -> [Mul by the weights] -> ReduceSum branch
+    per class joined by Concat(axis = 1); ArgMax, the class table looked up by ArrayFeatureExtractor; the probabilities as the Concat over its
+    row sum; weights = "distance" as Reciprocal(Max(distances, 1e-6)); ZipMap behind the probabilities unless the zipmap option is off.
+    Where the recollection is loose, the variants are parameters and the lowering recognises all of them: `lookup` ("afe" | "gather") for both
+    table lookups, `keepdims` of the branch ReduceSum (0: an Unsqueeze per branch in front of the Concat, or with join = "transpose" an
+    Unsqueeze(0), Concat(axis = 0) and Transpose), `reshape` of the looked-up labels (None: the lookup's natural one; "none", "k" = [-1, k],
+    "k1" = [-1, k, 1] and a Squeeze), `cast` (a Cast of the labels to INT64 behind the lookup), `reciprocal` ("reciprocal" | "div" = Div(1, .)),
+    `final` (what follows the class lookup: None = the lookup's natural Reshape([-1]), "none", "reshape", "cast", "reshape_cast").
+    Test hooks: `also` lists search outputs ("indices", "distances") declared as graph outputs too; `equal_values` replaces the branch
+    constants 0 .. C - 1; `extra_reader` names an intermediate ("knn_all", "knn_lab" = the looked-up labels, "knn_wei") declared as one
+    more graph output, which keeps the graph from being the pattern."""
+    F, C = spec["features"], len(classes)
+    nodes, inits, lab = _knn_vote_front(spec, y, k, weights, spelling, lookup, reshape, INT64 if cast else None, eps, reciprocal, np.int64)
+    consts = list(range(C)) if equal_values is None else list(equal_values)
+    inits.append(tensor("knn_axes1", np.array([1], np.int64)))
+    if keepdims == 0:
+        inits.append(tensor("knn_unsq", np.array([0 if join == "transpose" else 1], np.int64)))
+    branches = []
+    for c in range(C):
+        inits.append(tensor(f"knn_c{c}", np.array(consts[c], np.int64)))
+        nodes += [node("Equal", [lab, f"knn_c{c}"], [f"knn_eq{c}"], name=f"equal{c}"),
+                  node("Cast", [f"knn_eq{c}"], [f"knn_f{c}"], [attr_i("to", FLOAT)], name=f"cast{c}")]
+        cur = f"knn_f{c}"
+        if weights == "distance":
+            nodes.append(node("Mul", [cur, "knn_wei"], [f"knn_w{c}"], name=f"mul{c}"))
+            cur = f"knn_w{c}"
+        nodes.append(node("ReduceSum", [cur, "knn_axes1"], [f"knn_s{c}"], [attr_i("keepdims", keepdims)], name=f"sum{c}"))
+        cur = f"knn_s{c}"
+        if keepdims == 0:
+            nodes.append(node("Unsqueeze", [cur, "knn_unsq"], [f"knn_u{c}"], name=f"unsqueeze{c}"))
+            cur = f"knn_u{c}"
+        branches.append(cur)
+    if keepdims == 0 and join == "transpose":
+        nodes += [node("Concat", branches, ["knn_all_t"], [attr_i("axis", 0)], name="concat"),
+                  node("Transpose", ["knn_all_t"], ["knn_all"], [attr_ints("perm", [1, 0])], name="transpose")]
+    else:
+        nodes.append(node("Concat", branches, ["knn_all"], [attr_i("axis", 1)], name="concat"))
+    nodes.append(node("ArgMax", ["knn_all"], ["knn_arg"], [attr_i("axis", 1), attr_i("keepdims", 0)], name="argmax"))
+    inits.append(tensor("knn_classes", np.asarray(classes, np.int64)))
+    if final is None:
+        final = "reshape" if lookup == "afe" else "none"
+    steps = {"none": [], "reshape": ["Reshape"], "cast": ["Cast"], "reshape_cast": ["Reshape", "Cast"]}[final]
+    names = [f"knn_label{i}" for i in range(len(steps))] + ["label"]
+    if lookup == "afe":
+        nodes.append(node("ArrayFeatureExtractor", ["knn_classes", "knn_arg"], [names[0]], name="class_lookup", domain=ML_DOMAIN))
+    else:
+        nodes.append(node("Gather", ["knn_classes", "knn_arg"], [names[0]], [attr_i("axis", 0)], name="class_lookup"))
+    for i, op in enumerate(steps):
+        if op == "Reshape":
+            inits.append(tensor("knn_label_shape", np.array([-1], np.int64)))
+            nodes.append(node("Reshape", [names[i], "knn_label_shape"], [names[i + 1]], name="label_reshape"))
+        else:
+            nodes.append(node("Cast", [names[i]], [names[i + 1]], [attr_i("to", INT64)], name="label_cast"))
+    nodes += [node("ReduceSum", ["knn_all", "knn_axes1"], ["knn_norm"], [attr_i("keepdims", 1)], name="norm"),
+              node("Div", ["knn_all", "knn_norm"], ["probabilities"], name="proba")]
+    proba = value_info("probabilities", ["N", C])
+    if zipmap:
+        nodes.append(node("ZipMap", ["probabilities"], ["output_probability"], [attr_ints("classlabels_int64s", [int(v) for v in classes])], name="zipmap", domain=ML_DOMAIN))
+        proba = value_info("output_probability", ["N", C])
+    outs = [value_info("label", ["N"], INT64), proba]
+    if output == "probabilities":
+        outs.reverse()
+    elif output != "label":
+        raise ValueError(output)
+    for nm in also:
+        outs.append(value_info(nm, ["N", k], INT64 if nm == "indices" else FLOAT))
+    if extra_reader:
+        nm = lab if extra_reader == "knn_lab" else extra_reader
+        outs.append(value_info(nm, ["N", C] if nm == "knn_all" else ["N", k], INT64 if extra_reader == "knn_lab" else FLOAT))
+    return _model_ms("knn_classifier", nodes, inits, [value_info("X", ["N", F])], outs) + _ld(8, _s(1, ML_DOMAIN) + _vi(2, 1))
+
+
+def knn_regressor_from_spec(spec: dict, y, k: int = 5, weights: str = "uniform", spelling: str = "cdist", lookup: str = "afe", keepdims: int = 0,
+                            reshape=None, eps: float = 1e-6, reciprocal: str = "reciprocal", final: str = "reshape") -> bytes:
+    """KNeighborsRegressor as skl2onnx writes it, restated: `y` [M] are the training targets, float32 or an integer type (int64 in the graph,
+    cast to FLOAT behind the lookup).  One output, `variable` [N, 1] (final = "none": the reduction's own shape).
+
+    Recalled from the exporter's converter (convert_nearest_neighbors_regressor): the search head, the targets looked up by
+    ArrayFeatureExtractor and reshaped to [-1, k], ReduceMean over axis 1 for uniform weights, ReduceSum(targets * weights) over ReduceSum(weights)
+    for distance weights, a closing Reshape to [-1, 1].  Loose: `lookup`, `keepdims`, `reshape`, `reciprocal` as in knn_classifier_from_spec."""
+    F = spec["features"]
+    y = np.asarray(y)
+    if final not in ("reshape", "none"):
+        raise ValueError(final)
+    integer = y.dtype.kind in "iu"  # (a 2-D y, the multi-output form [M, T], is written as it is: the lowering refuses it)
+    nodes, inits, lab = _knn_vote_front(spec, y, k, weights, spelling, lookup, reshape, FLOAT if integer else None, eps, reciprocal, np.int64 if integer else np.float32)
+    value = "variable" if final == "none" else "knn_value"
+    if weights == "uniform":
+        nodes.append(node("ReduceMean", [lab], [value], [attr_ints("axes", [1]), attr_i("keepdims", keepdims)], name="mean"))
+    else:
+        inits.append(tensor("knn_axes1", np.array([1], np.int64)))
+        nodes += [node("Mul", [lab, "knn_wei"], ["knn_wt"], name="weighted"),
+                  node("ReduceSum", ["knn_wt", "knn_axes1"], ["knn_num"], [attr_i("keepdims", keepdims)], name="num"),
+                  node("ReduceSum", ["knn_wei", "knn_axes1"], ["knn_den"], [attr_i("keepdims", keepdims)], name="den"),
+                  node("Div", ["knn_num", "knn_den"], [value], name="mean")]
+    out = value_info("variable", ["N", 1] if final == "reshape" or keepdims else ["N"])
+    if final == "reshape":
+        inits.append(tensor("knn_out_shape", np.array([-1, 1], np.int64)))
+        nodes.append(node("Reshape", ["knn_value", "knn_out_shape"], ["variable"], name="out_reshape"))
+    return _model_ms("knn_regressor", nodes, inits, [value_info("X", ["N", F])], [out]) + _ld(8, _s(1, ML_DOMAIN) + _vi(2, 1))
+
+
 def nearest_reference(spec: dict, x, k: int = 1) -> dict:
     """float64 restatement: d2 [N, M] (NaN rows stay NaN), label, the k nearest `indices` (stable: equal distances by lower index, NaN after
     every number) and `values` (d2), `gap_out` = d2 of the (k+1)-th minus the k-th (inf when k = M), `gap_in` = the smallest gap between
