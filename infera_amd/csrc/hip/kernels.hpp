@@ -63,8 +63,9 @@ void tree_reduce(hipStream_t s, const float *part, const float *base, const floa
                  bool average, int mode, bool is_signed);
 
 // ---- support-vector machines (svm.hip) ---------------------------------------------------------
-// part[S][rows][Q] = per-slice sums  sum_s coef[q][s] * K(x, s)  for x [rows, F]; tables: host/svm.hpp SvmPack (kernel: SvmKernelType)
-void svm_kernel(hipStream_t s, const float *x, int F, int F_pad, int kernel, const float *center, const float *sv, const float *sv_norm, const float *coef,
+// part[S][rows][Q] = per-slice sums  sum_s coef[q][s] * K(x, s)  for x [rows, F]; tables: host/svm.hpp SvmPack (kernel: SvmKernelType).
+// false: the kernel could not be given its LDS (F > 504 opts in to more than 64 KB) and nothing was launched
+bool svm_kernel(hipStream_t s, const float *x, int F, int F_pad, int kernel, const float *center, const float *sv, const float *sv_norm, const float *coef,
                 const uint32_t *slice_tile, float *part, int64_t rows, int S, int Q, int QW, float gamma, float coef0, int degree);
 // the slices of each class summed in slice order, + rho -> a host/plan.hpp SvmOut form
 void svm_reduce(hipStream_t s, const float *part, const uint32_t *class_slice, const float *rho, const float *labels, const float *prob_a,
@@ -73,7 +74,7 @@ void svm_reduce(hipStream_t s, const float *part, const uint32_t *class_slice, c
 // ---- distance models (nearest.hip) -------------------------------------------------------------
 // x [rows, F] against the packed set of host/nearest.hpp NearestPack.  mode (NearestOut) kNearestMatrix / kNearestMatrixSqrt: out = d2 /
 // sqrt(d2) [rows, M]; kNearestSelect: out = the per-slice best lists [rows][S][2 * nearest_list_width(k)] (host/nearest.hpp) (values, then index patterns)
-// false: the kernel could not be given its LDS (F > 508 needs the opt-in beyond 64 KB)
+// false: the kernel could not be given its LDS (F > 504 needs the opt-in beyond 64 KB)
 bool nearest(hipStream_t s, const float *x, int F, int F_pad, const float *center, const float *ref, const float *ref_norm, const uint32_t *slice_tile,
              float *out, int64_t rows, int S, int M, int k, int mode);
 // the slices merged in slice order -> the label [rows], the k nearest indices or their (sqrt) distances [rows, k]

@@ -2,7 +2,7 @@
 // centroid labels, k-NN search) on gfx950 (semantics: INTEGRATION.md section 2.6; tables: host/nearest.hpp).
 //
 // nearest_kernel: the structure of svm.hip stage 1.  A wave owns 32 rows, a workgroup 1, 2 or 4 waves (as many as keep the row tiles
-// within 64 KB of LDS; one wave and up to 129 KB for F > 508).  The rows are staged in LDS once (row stride F_pad + 4 floats:
+// within 64 KB of LDS; one wave and up to 129 KB for F > 504).  The rows are staged in LDS once (row stride F_pad + 4 floats:
 // conflict-free ds_read_b128), centred on the load-time mean of the reference set, and their squared norms summed in a fixed order.
 // Block b works on row tile b / S and reference slice b % S; a slice is a run of 32-vector tiles fixed at load from the model alone.
 // Per tile:
@@ -253,7 +253,7 @@ bool launch(hipStream_t s, const float *x, int F, int F_pad, const float *center
   while (nw > 1 && size_t(nw) * 32 * size_t(F_pad + 4) * 4 > size_t(kLdsBudget)) nw /= 2;
   const size_t lds = size_t(nw) * 32 * size_t(F_pad + 4) * 4;
   auto kernel = nearest_kernel<K>;
-  if (lds > size_t(kLdsBudget) &&  // F > 508: one wave, dynamic LDS beyond 64 KB is opt-in
+  if (lds > size_t(kLdsBudget) &&  // F > 504: one wave, dynamic LDS beyond 64 KB is opt-in
       hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
     return false;
   const int64_t tiles = (rows + 32 * nw - 1) / (32 * nw);

@@ -294,8 +294,9 @@ void upload_svm_kernel(const Step &s, SvmKernelTables &t, const Upload &up) {
 }
 void launch_svm_kernel(const PassRunner &r, const Step &x, const SvmKernelTables &t) {
   const SvmPack &v = *x.svm;
-  kern::svm_kernel(r.stream, r.buf(x.in0), int(r.p.buf_per_row[size_t(x.in0)]), int(v.F_pad), v.kernel, t.center, t.sv, t.sv_norm, t.coef, t.slice_tile,
-                   r.buf(x.out), r.nr, int(v.slices), int(v.Q), int(v.QW), v.gamma, v.coef0, v.degree);
+  if (!kern::svm_kernel(r.stream, r.buf(x.in0), int(r.p.buf_per_row[size_t(x.in0)]), int(v.F_pad), v.kernel, t.center, t.sv, t.sv_norm, t.coef,
+                        t.slice_tile, r.buf(x.out), r.nr, int(v.slices), int(v.Q), int(v.QW), v.gamma, v.coef0, v.degree))
+    throw InferaError::onnx("SVM kernel launch failed: '" + x.origin + "' (F = " + std::to_string(v.F) + ") could not be given its LDS");
 }
 void upload_svm_reduce(const Step &s, SvmReduceTables &t, const Upload &up) {
   t.rho = up(s.svm->rho);

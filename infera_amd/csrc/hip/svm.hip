@@ -1,9 +1,11 @@
 // svm.hip -- ai.onnx.ml SVMRegressor / SVMClassifier on gfx950 (semantics: INTEGRATION.md section 2.6; tables: host/svm.hpp).
 //
 // svm_kernel_kernel: a wave owns 32 table rows, a workgroup 1, 2 or 4 waves (as many as keep the row tiles within 64 KB of LDS;
-// one wave and up to 129 KB for F > 508).  The rows are staged in LDS once (row stride F_pad + 4 floats: conflict-free
-// ds_read_b128), centered on the load-time SV mean for RBF, and their squared norms summed in a fixed order.  Block b works on row
-// tile b / S and SV slice b % S; a slice is a run of 32-SV tiles inside one class block, fixed at load from the model alone.
+// one wave and up to 129 KB for F > 504).  The rows are staged in LDS once (row stride F_pad + 4 floats: conflict-free
+// ds_read_b128), centered on the load-time SV mean for RBF, a NaN or +-Inf feature staged as NaN (0 . NaN = NaN against every SV, the
+// padding ones included: such a row is NaN throughout, whatever the class sizes), and their squared norms summed in a fixed order.
+// Block b works on row tile b / S and SV slice b % S; a slice is a run of 32-SV tiles inside one class block, fixed at load from the
+// model alone.
 // Per SV tile:
 //   stage 1  K^T[sv, row] = S . X^T on v_mfma_f32_32x32x2_f32 (exact f32: a k-ordered fma chain), A = S straight from L2 in
 //            fragment order (one 16-B load per lane feeds four k-steps), B = X from LDS.  k order inside each group of 8 features
@@ -75,6 +77,7 @@ __global__ __launch_bounds__(kMaxWaves * 64) void svm_kernel_kernel(const float 
     if (k < F && g < nr) {
       v = x[g * F + k];
       if constexpr (KT == kSvmRbf) v -= center[k];
+      if (!(fabsf(v) < INFINITY)) v = NAN;  // the non-finite rule of INTEGRATION.md 2.6: NaN and +-Inf alike poison their row
     }
     tile[rr * stride + k] = v;
   }
@@ -266,38 +269,41 @@ __global__ __launch_bounds__(kReduceBlock) void svm_reduce_kernel(const float *_
 }
 
 template <int KT, int QW>
-void kernel_launch(hipStream_t s, const float *x, int F, int F_pad, const float *center, const float *sv, const float *sv_norm, const float *coef,
+bool kernel_launch(hipStream_t s, const float *x, int F, int F_pad, const float *center, const float *sv, const float *sv_norm, const float *coef,
                    const uint32_t *slice_tile, float *part, int64_t rows, int S, int Q, float gamma, float coef0, int degree) {
   int nw = kMaxWaves;
   while (nw > 1 && size_t(nw) * 32 * size_t(F_pad + 4) * 4 > size_t(kLdsBudget)) nw /= 2;
   const size_t lds = size_t(nw) * 32 * size_t(F_pad + 4) * 4;
   auto kernel = svm_kernel_kernel<KT, QW>;
-  if (lds > size_t(kLdsBudget))  // F > 508: one wave, dynamic LDS beyond 64 KB is opt-in
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (lds > size_t(kLdsBudget) &&  // F > 504: one wave, dynamic LDS beyond 64 KB is opt-in
+      hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+    return false;
   const int64_t tiles = (rows + 32 * nw - 1) / (32 * nw);
   hipLaunchKernelGGL(kernel, dim3(unsigned(tiles * S)), dim3(unsigned(64 * nw)), lds, s, x, F, F_pad, center, reinterpret_cast<const f32x4 *>(sv),
                      sv_norm, coef, slice_tile, part, rows, S, Q, gamma, coef0, degree);
+  return true;
 }
 
 template <int KT>
-void kernel_dispatch(hipStream_t s, const float *x, int F, int F_pad, const float *center, const float *sv, const float *sv_norm, const float *coef,
+bool kernel_dispatch(hipStream_t s, const float *x, int F, int F_pad, const float *center, const float *sv, const float *sv_norm, const float *coef,
                      const uint32_t *slice_tile, float *part, int64_t rows, int S, int Q, int QW, float gamma, float coef0, int degree) {
 #define INFERA_SVM_QW(W) \
   if (QW == W) return kernel_launch<KT, W>(s, x, F, F_pad, center, sv, sv_norm, coef, slice_tile, part, rows, S, Q, gamma, coef0, degree);
   INFERA_SVM_QW(1) INFERA_SVM_QW(2) INFERA_SVM_QW(4) INFERA_SVM_QW(8) INFERA_SVM_QW(32) INFERA_SVM_QW(64)
 #undef INFERA_SVM_QW
+  return false;  // (no such stage-2 width: host/svm.cpp writes 1, 2, 4, 8, 32 or 64)
 }
 
 }  // namespace
 
-void svm_kernel(hipStream_t s, const float *x, int F, int F_pad, int kernel, const float *center, const float *sv, const float *sv_norm, const float *coef,
+bool svm_kernel(hipStream_t s, const float *x, int F, int F_pad, int kernel, const float *center, const float *sv, const float *sv_norm, const float *coef,
                 const uint32_t *slice_tile, float *part, int64_t rows, int S, int Q, int QW, float gamma, float coef0, int degree) {
-  if (rows <= 0) return;
+  if (rows <= 0) return true;
   switch (kernel) {
-    case kSvmPoly: kernel_dispatch<kSvmPoly>(s, x, F, F_pad, center, sv, sv_norm, coef, slice_tile, part, rows, S, Q, QW, gamma, coef0, degree); break;
-    case kSvmRbf: kernel_dispatch<kSvmRbf>(s, x, F, F_pad, center, sv, sv_norm, coef, slice_tile, part, rows, S, Q, QW, gamma, coef0, degree); break;
-    case kSvmSigmoid: kernel_dispatch<kSvmSigmoid>(s, x, F, F_pad, center, sv, sv_norm, coef, slice_tile, part, rows, S, Q, QW, gamma, coef0, degree); break;
-    default: kernel_dispatch<kSvmLinear>(s, x, F, F_pad, center, sv, sv_norm, coef, slice_tile, part, rows, S, Q, QW, gamma, coef0, degree); break;
+    case kSvmPoly: return kernel_dispatch<kSvmPoly>(s, x, F, F_pad, center, sv, sv_norm, coef, slice_tile, part, rows, S, Q, QW, gamma, coef0, degree);
+    case kSvmRbf: return kernel_dispatch<kSvmRbf>(s, x, F, F_pad, center, sv, sv_norm, coef, slice_tile, part, rows, S, Q, QW, gamma, coef0, degree);
+    case kSvmSigmoid: return kernel_dispatch<kSvmSigmoid>(s, x, F, F_pad, center, sv, sv_norm, coef, slice_tile, part, rows, S, Q, QW, gamma, coef0, degree);
+    default: return kernel_dispatch<kSvmLinear>(s, x, F, F_pad, center, sv, sv_norm, coef, slice_tile, part, rows, S, Q, QW, gamma, coef0, degree);
   }
 }
 

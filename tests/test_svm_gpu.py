@@ -1,4 +1,4 @@
-"""SVMRegressor / SVMClassifier on the GPU (hip/svm.hip) against a float64 numpy restatement of the contract written here
+"""SVMRegressor / SVMClassifier on the GPU (hip/svm.hip) against the float64 numpy restatement of the contract in tests/svm_ref.py
 (INTEGRATION.md section 2.6), and bit-reproducibility across every call path."""
 from __future__ import annotations
 
@@ -7,6 +7,7 @@ import pytest
 
 from infera_amd import onnx_writer as W
 from infera_amd import synth
+from tests.svm_ref import check, np_svm, tol_of
 
 pytestmark = pytest.mark.gpu
 
@@ -17,153 +18,6 @@ def api(built):
 
     assert capi.device_count() >= 1, capi.get_devices()
     return capi
-
-
-# ---- the restatement -----------------------------------------------------------------------------------------------------------
-
-def np_kernel(spec, x):
-    S = np.asarray(spec["support_vectors"], dtype=np.float64).reshape(spec["n_sv"], spec["features"])
-    g, c0, deg = (float(v) for v in spec["kernel_params"])
-    dot = x @ S.T
-    k = spec["kernel"]
-    if k == "LINEAR":
-        return dot
-    if k == "POLY":
-        return (g * dot + c0) ** int(deg)
-    if k == "RBF":
-        d2 = ((x[:, None, :] - S[None, :, :]) ** 2).sum(-1) if x.shape[0] * S.shape[0] * S.shape[1] < 2e7 else \
-            np.maximum((x * x).sum(1)[:, None] + (S * S).sum(1)[None, :] - 2 * dot, 0)
-        return np.exp(-g * d2)
-    return np.tanh(g * dot + c0)
-
-
-def platt(d, A, B):
-    f = d * A + B
-    e = np.exp(-np.abs(f))  # libsvm's overflow-safe form: exp(-f) / (1 + exp(-f)) for f >= 0, else 1 / (1 + exp(f))
-    p = np.where(f >= 0, e / (1 + e), 1 / (1 + e))
-    p = np.where(p < 1e-7, 1e-7, p)
-    return np.where(p > 1 - 1e-7, 1 - 1e-7, p)
-
-
-def coupling(r, C):
-    """libsvm multiclass_probability for one row: r[i][j] pairwise; returns (p, margin of the stopping tests to eps)"""
-    Q = np.zeros((C, C))
-    for t in range(C):
-        for j in range(C):
-            if j != t:
-                Q[t, t] += r[j, t] * r[j, t]
-                Q[t, j] = -r[j, t] * r[t, j]
-    p = np.full(C, 1.0 / C)
-    eps, margin = 0.005 / C, np.inf
-    for _ in range(max(100, C)):
-        Qp = Q @ p
-        pQp = p @ Qp
-        err = np.abs(Qp - pQp).max()
-        margin = min(margin, abs(err - eps) / eps)
-        if err < eps:
-            break
-        for t in range(C):
-            diff = (-Qp[t] + pQp) / Q[t, t]
-            p[t] += diff
-            pQp = (pQp + diff * (diff * Q[t, t] + 2 * Qp[t])) / (1 + diff) / (1 + diff)
-            Qp = (Qp + diff * Q[t, :]) / (1 + diff)
-            p /= 1 + diff
-    return p, margin
-
-
-def np_svm(spec, x32):
-    """dict: d [N, P] decisions (regressor: [N, 1]) with their magnitudes sum_s |coef K|, label, scores as served before post_transform"""
-    x = x32.astype(np.float64)
-    K = np_kernel(spec, x)
-    coef = np.asarray(spec["coefficients"], dtype=np.float64)
-    rho = np.asarray(spec["rho"], dtype=np.float64)
-    out = {}
-    if spec["kind"] != "classifier":
-        t = K * coef[0][None, :]
-        d = t.sum(1) + rho[0]
-        out["d"], out["mag"] = d[:, None], np.abs(t).sum(1)[:, None]
-        out["scores"] = np.where(d > 0, 1.0, -1.0)[:, None] if spec["kind"] == "one_class" else d[:, None]
-        return out
-    C = spec["classes"]
-    b = np.concatenate([[0], np.cumsum(spec["vectors_per_class"])])
-    ds, mags, pairs = [], [], []
-    for i in range(C):
-        for j in range(i + 1, C):
-            ti = K[:, b[i]:b[i + 1]] * coef[j - 1, b[i]:b[i + 1]]
-            tj = K[:, b[j]:b[j + 1]] * coef[i, b[j]:b[j + 1]]
-            ds.append(ti.sum(1) + tj.sum(1) + rho[len(pairs)])
-            mags.append(np.abs(ti).sum(1) + np.abs(tj).sum(1))
-            pairs.append((i, j))
-    d, mag = np.stack(ds, 1), np.stack(mags, 1)
-    votes = np.zeros((x.shape[0], C), dtype=np.int64)
-    for p, (i, j) in enumerate(pairs):
-        win = d[:, p] > 0
-        votes[:, i] += win
-        votes[:, j] += ~win
-    out.update(d=d, mag=mag, label=np.asarray(spec["labels"], dtype=np.float64)[np.argmax(votes, 1)])
-    if spec.get("prob_a") is None:
-        out["scores"] = np.stack([d[:, 0], -d[:, 0]], 1) if C == 2 else d
-        return out
-    A, B = np.asarray(spec["prob_a"], np.float64), np.asarray(spec["prob_b"], np.float64)
-    r = platt(d, A[None, :], B[None, :])
-    if C == 2:
-        out["scores"] = np.stack([r[:, 0], 1 - r[:, 0]], 1)
-        out["coupling_margin"] = np.full(x.shape[0], np.inf)
-        return out
-    prob = np.full((x.shape[0], C), np.nan)
-    margin = np.full(x.shape[0], np.inf)
-    for n in range(x.shape[0]):
-        if np.isnan(r[n]).any():
-            continue
-        R = np.zeros((C, C))
-        for p, (i, j) in enumerate(pairs):
-            R[i, j], R[j, i] = r[n, p], 1 - r[n, p]
-        prob[n], margin[n] = coupling(R, C)
-    out["scores"], out["coupling_margin"] = prob, margin
-    return out
-
-
-def tol_of(ref):
-    return 1e-4 * (np.abs(ref["d"]) + ref["mag"]) + 1e-6
-
-
-def check(spec, ref, got, what):
-    """`what`: 'label', 'scores' (decisions / values / probabilities as served, post_transform NONE)"""
-    tol = tol_of(ref)
-    if what == "label":
-        near = (np.abs(ref["d"]) <= tol).any(1)
-        print(f"{int(near.sum())} of {near.size} rows excluded (a decision within the tolerance of 0)")
-        assert near.mean() < 0.01
-        got = got.reshape(-1)
-        assert np.array_equal(got[~near], ref["label"][~near].astype(np.float32))
-        return
-    want = ref["scores"]
-    assert got.shape == want.shape, (got.shape, want.shape)
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan)
-    g, w = got.astype(np.float64)[~nan], want[~nan]
-    if spec["kind"] == "one_class":
-        near = (np.abs(ref["d"][:, 0]) <= tol[:, 0])
-        ok = (got[:, 0] == want[:, 0]) | near
-        assert ok[~np.isnan(want[:, 0])].all()
-        return
-    if spec["kind"] != "classifier" or spec.get("prob_a") is None:
-        if spec["kind"] == "classifier" and spec["classes"] == 2:
-            tol = np.concatenate([tol, tol], 1)
-        err = np.abs(g - w)
-        bad = err > tol[~nan]
-        assert not bad.any(), f"{bad.sum()} / {bad.size} out of tolerance; worst {err.max():.3e}"
-        return
-    # probabilities: a decision error e moves r_ij by at most |A| e / 4; the coupling keeps that order unless its stopping test
-    # falls within that error of eps (those rows are counted and excluded)
-    A = np.abs(np.asarray(spec["prob_a"], np.float64))
-    etol = (tol * A[None, :] / 4).max(1, keepdims=True) * 10 + 1e-6
-    err = np.abs(got.astype(np.float64) - want)
-    unstable = ref["coupling_margin"] < 1e-3
-    print(f"{int(unstable.sum())} of {unstable.size} rows excluded (coupling stop within 1e-3 of eps)")
-    assert unstable.sum() <= max(2, 0.01 * unstable.size)
-    bad = (err > etol) & ~unstable[:, None] & ~nan
-    assert not bad.any(), f"{bad.sum()} / {bad.size} out of tolerance; worst {np.nanmax(err):.3e}"
 
 
 def _table(rows, F, seed=23, nan_frac=0.0, offset=0.0):
