@@ -136,6 +136,15 @@ int32_t infera_hip_choose_slot(const int32_t *slot_numa, uintptr_t nslots, int32
  * 5 s (a wedged GPU) -- it is no longer served, but its pages stay pinned and may still be read; keep it mapped. */
 int32_t infera_hip_register_host_memory(const void *base, uint64_t bytes);
 int32_t infera_hip_unregister_host_memory(const void *base);
+/* Not every system can pin pages a process already has (a GPU passed through to a virtual machine: hipHostRegister fails with "invalid
+ * value", and so does infera_hip_register_host_memory on ordinary memory).  Memory that was ALLOCATED pinned -- these two (hipHostMalloc,
+ * portable + mapped; whole pages), hipHostMalloc itself, a framework's pinned allocator -- registers everywhere: its pages are served as
+ * they are and nothing is pinned or unpinned for them.  Unregister a range before the allocation it lies in is freed.  NULL / -1 on failure. */
+void *infera_hip_host_malloc(uint64_t bytes);
+int32_t infera_hip_host_free(void *ptr);
+/* 1: ordinary memory registers here (hipHostRegister works; probed once on a page of the library's own); 0: only memory allocated pinned does,
+ * or there is no GPU. */
+int32_t infera_hip_pins_application_memory(void);
 /* infera_predict_columns calls served zero-copy so far (tests, bench) */
 uint64_t infera_hip_zero_copy_calls(void);
 

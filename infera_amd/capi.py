@@ -30,6 +30,7 @@ EXTENSION_SYMBOLS = [
     "infera_predict_into", "infera_predict_columns", "infera_predict_from_blob_batch", "infera_gather_columns",
     "infera_hip_sha256_hex", "infera_hip_shape_rows_cols", "infera_hip_h2d_probe", "infera_hip_choose_slot",
     "infera_gather_columns_colmajor", "infera_hip_choose_slot_balanced", "infera_hip_register_host_memory", "infera_hip_unregister_host_memory", "infera_hip_zero_copy_calls",
+    "infera_hip_host_malloc", "infera_hip_host_free", "infera_hip_pins_application_memory",
 ]
 
 
@@ -130,6 +131,12 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.infera_hip_register_host_memory.restype = C.c_int32
     L.infera_hip_unregister_host_memory.argtypes = [C.c_void_p]
     L.infera_hip_unregister_host_memory.restype = C.c_int32
+    L.infera_hip_host_malloc.argtypes = [C.c_uint64]
+    L.infera_hip_host_malloc.restype = C.c_void_p
+    L.infera_hip_host_free.argtypes = [C.c_void_p]
+    L.infera_hip_host_free.restype = C.c_int32
+    L.infera_hip_pins_application_memory.argtypes = []
+    L.infera_hip_pins_application_memory.restype = C.c_int32
     L.infera_hip_zero_copy_calls.argtypes = []
     L.infera_hip_zero_copy_calls.restype = C.c_uint64
     L.infera_hip_h2d_probe.argtypes = [C.c_int32, C.c_uint64, C.c_int32, C.c_int32]
@@ -254,6 +261,49 @@ def register_host_memory(arr: np.ndarray) -> None:
 def unregister_host_memory(arr: np.ndarray) -> None:
     if load_library().infera_hip_unregister_host_memory(arr.ctypes.data) != 0:
         raise InferaError(last_error())
+
+
+def pins_application_memory() -> bool:
+    """Whether register_host_memory takes ordinary memory here (False: only memory allocated pinned -- pinned_empty -- or no GPU)."""
+    return bool(load_library().infera_hip_pins_application_memory())
+
+
+class _PinnedBlock:
+    """One infera_hip_host_malloc allocation, given back when the last array over it is collected."""
+
+    def __init__(self, nbytes: int):
+        self.ptr = load_library().infera_hip_host_malloc(nbytes)
+        if not self.ptr:
+            raise InferaError(last_error() or "hipHostMalloc failed")
+
+    def __del__(self):
+        try:
+            load_library().infera_hip_host_free(self.ptr)
+        except Exception:
+            pass
+
+
+def pinned_empty(shape, dtype=np.float32) -> np.ndarray:
+    """A page-aligned array in memory ALLOCATED pinned (infera_hip_host_malloc; whole 4 KiB pages): what register_host_memory accepts on
+    every system, including those that cannot pin memory a process already has.  Unregister it before the last reference goes."""
+    n = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
+    nbytes = max(4096, (n + 4095) // 4096 * 4096)
+    block = _PinnedBlock(nbytes)
+    buf = (C.c_uint8 * nbytes).from_address(block.ptr)
+    buf._infera_block = block  # (the array's base is `buf`, which keeps the allocation)
+    return np.frombuffer(buf, np.uint8)[:n].view(dtype).reshape(shape)
+
+
+def pinned_copy(arr: np.ndarray) -> np.ndarray:
+    """`arr` (C order) in memory allocated pinned: see pinned_empty."""
+    out = pinned_empty(arr.shape, arr.dtype)
+    out[...] = arr
+    return out
+
+
+def registrable(arr: np.ndarray) -> np.ndarray:
+    """`arr` itself where ordinary memory can be registered, else a copy of it in memory allocated pinned."""
+    return arr if pins_application_memory() else pinned_copy(arr)
 
 
 def zero_copy_calls() -> int:

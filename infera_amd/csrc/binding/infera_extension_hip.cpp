@@ -485,6 +485,9 @@ struct InferaAllocatorData : PrivateAllocatorData {
   idx_t min_bytes = 128 * 1024;
   idx_t block_bytes = 256 * 1024;
   bool arena = true;
+  // Not every system can pin memory the process already has (a GPU passed through to a virtual machine: include/infera_hip.h).  There the slabs
+  // and the blocks worth registering are ALLOCATED pinned (infera_hip_host_malloc) and registered as they are; fixed when the allocator is installed.
+  bool pinned_allocs = false;
   static constexpr int kSlabBlocks = 256;
   std::mutex mu;
   std::vector<unique_ptr<Slab>> slabs;      // creation order
@@ -492,8 +495,12 @@ struct InferaAllocatorData : PrivateAllocatorData {
   ~InferaAllocatorData() override {
     for (auto &sl : slabs) {
       if (sl->registered) (void)infera::infera_hip_unregister_host_memory(sl->base);
-      std::free(sl->base);
+      FreeSlab(sl->base);
     }
+  }
+  void FreeSlab(data_ptr_t base) {
+    if (pinned_allocs) (void)infera::infera_hip_host_free(base);
+    else std::free(base);
   }
   Slab *SlabOf(data_ptr_t p) {  // (under mu)
     auto it = by_base.upper_bound(p);
@@ -517,7 +524,9 @@ struct InferaAllocatorData : PrivateAllocatorData {
     // no room: a new slab, made and pinned OUTSIDE the lock (pinning 64 MiB takes milliseconds; other threads keep allocating and freeing)
     auto fresh = make_uniq<Slab>();
     void *mem = nullptr;
-    if (posix_memalign(&mem, size_t(2) << 20, size_t(kSlabBlocks) * block_bytes) != 0) return nullptr;
+    if (pinned_allocs) mem = infera::infera_hip_host_malloc(uint64_t(kSlabBlocks) * block_bytes);
+    else if (posix_memalign(&mem, size_t(2) << 20, size_t(kSlabBlocks) * block_bytes) != 0) mem = nullptr;
+    if (!mem) return nullptr;
     fresh->base = static_cast<data_ptr_t>(mem);
     // (a failed registration -- no GPU, pinning limit reached -- only means the slab's chunks are staged like any other memory)
     fresh->registered = infera::infera_hip_register_host_memory(mem, uint64_t(kSlabBlocks) * block_bytes) == 0;
@@ -557,7 +566,7 @@ struct InferaAllocatorData : PrivateAllocatorData {
         const char *e = infera::infera_last_error();
         release = !(e && std::strstr(e, "still in use"));  // (a wedged GPU may still read it: leaked, include/infera_hip.h)
       }
-      if (release) std::free(retired->base);
+      if (release) FreeSlab(retired->base);
     }
     return true;
   }
@@ -565,13 +574,14 @@ struct InferaAllocatorData : PrivateAllocatorData {
 inline InferaAllocatorData *Data(PrivateAllocatorData *pd) { return static_cast<InferaAllocatorData *>(pd); }
 inline bool WorthRegistering(PrivateAllocatorData *pd, idx_t size) { return size >= Data(pd)->min_bytes; }
 inline bool FromArena(PrivateAllocatorData *pd, idx_t size) { return Data(pd)->arena && size == Data(pd)->block_bytes; }
+inline bool AllocatedPinned(PrivateAllocatorData *pd, idx_t size) { return Data(pd)->pinned_allocs && WorthRegistering(pd, size); }
 #if defined(__GNUC__) && !defined(__clang__)
 #pragma GCC diagnostic push
 #pragma GCC diagnostic ignored "-Wmaybe-uninitialized"  // (the fresh block's CONTENTS are uninitialised; only its address range is registered)
 #endif
 data_ptr_t RegisteringAllocate(PrivateAllocatorData *pd, idx_t size) {
   if (FromArena(pd, size)) return Data(pd)->Take();
-  const data_ptr_t p = Allocator::DefaultAllocate(pd, size);
+  const data_ptr_t p = AllocatedPinned(pd, size) ? static_cast<data_ptr_t>(infera::infera_hip_host_malloc(size)) : Allocator::DefaultAllocate(pd, size);
   // (a failed registration -- no GPU, pinning limit reached -- only means the block's chunks are staged like any other memory)
   if (p && WorthRegistering(pd, size)) (void)infera::infera_hip_register_host_memory(p, size);
   return p;
@@ -591,13 +601,15 @@ void RegisteringFree(PrivateAllocatorData *pd, data_ptr_t p, idx_t size) {
   if (!p) return;
   if (FromArena(pd, size) && Data(pd)->GiveBack(p)) return;
   if (WorthRegistering(pd, size) && !ReleasedForFree(p)) return;
-  Allocator::DefaultFree(pd, p, size);
+  if (AllocatedPinned(pd, size)) (void)infera::infera_hip_host_free(p);
+  else Allocator::DefaultFree(pd, p, size);
 }
 data_ptr_t RegisteringReallocate(PrivateAllocatorData *pd, data_ptr_t p, idx_t old_size, idx_t size) {
   if (!p) return RegisteringAllocate(pd, size);
   const idx_t keep = old_size < size ? old_size : size;
-  if (FromArena(pd, old_size) || FromArena(pd, size)) {
-    // a slab block cannot grow in place, and a block of the arena's size has to come out of a slab: allocate, copy, release the old one
+  if (FromArena(pd, old_size) || FromArena(pd, size) || AllocatedPinned(pd, old_size) || AllocatedPinned(pd, size)) {
+    // a slab block cannot grow in place, and a block of the arena's size has to come out of a slab (nor can a block that was allocated pinned, or
+    // has to be, go through realloc): allocate, copy, release the old one
     const data_ptr_t fresh = RegisteringAllocate(pd, size);
     if (!fresh) return nullptr;
     std::memcpy(fresh, p, keep);
@@ -639,6 +651,7 @@ DUCKDB_EXTENSION_API bool infera_install_zero_copy_allocator(duckdb::DBConfig &c
   auto data = duckdb::make_uniq<duckdb::InferaAllocatorData>();
   const char *arena = std::getenv("INFERA_ZERO_COPY_ARENA");
   data->arena = !(arena && std::atoi(arena) == 0);
+  data->pinned_allocs = infera::infera_hip_device_count() > 0 && infera::infera_hip_pins_application_memory() == 0;
   config.allocator = duckdb::make_uniq<duckdb::Allocator>(duckdb::RegisteringAllocate, duckdb::RegisteringFree, duckdb::RegisteringReallocate, std::move(data));
   return true;
 }

@@ -205,6 +205,9 @@ struct ZeroCopyPins {
 bool lookup_host_memory_many(size_t n, const void *const *ptrs, const size_t *bytes, const void **out, ZeroCopyPins &pins);
 const void *lookup_host_memory(const void *p, size_t bytes);  // (address only, no pin: tests / diagnostics)
 size_t registered_host_ranges();
+// whether this system pins memory the process already has (hipHostRegister; probed once on a page of the library's own).  Where it does not --
+// a GPU passed through to a virtual machine -- only memory ALLOCATED pinned (hipHostMalloc) registers.  false without a GPU.
+bool pins_application_memory();
 // `height` runs of `width` bytes, `src_pitch` bytes apart in REGISTERED host memory -> one column-major chunk at dst, as ONE 2-D copy on `stream`
 void copy_rect_to_device(hipStream_t stream, float *dst, const void *src, size_t src_pitch, size_t width, size_t height);
 bool zero_copy_rect_enabled();  // Config::zero_copy_rect

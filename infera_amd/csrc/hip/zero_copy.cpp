@@ -1,5 +1,7 @@
 // zero_copy.cpp -- registered host memory: the GPU reads an application's column storage in place (infera_hip_register_host_memory,
 // the reference's ROADMAP.md:44 "zero-copy").  Ranges -> page blocks -> reader pins; see the comment below and DESIGN.md 6.2.
+#include <cstdlib>
+#include <cstring>
 #include <exception>
 #include <map>
 #include <thread>
@@ -23,6 +25,7 @@ namespace {
 struct PageBlock {
   uintptr_t pb, pe;              // page-aligned span handed to hipHostRegister
   intptr_t dev_delta;            // device-visible address = host address + dev_delta (the same on every selected GPU: checked)
+  bool owned = true;             // pinned by this registry (false: the application allocated the pages pinned; they are never unregistered here)
   int refs = 0;                  // registered ranges that touch these pages (under g_reg_mu)
   std::atomic<int> readers{0};   // zero-copy calls in flight that resolved an address inside this block
 };
@@ -53,12 +56,37 @@ struct DeviceRestore {
   }
 };
 
-intptr_t hip_register_span(uintptr_t pb, uintptr_t pe) {
+// Memory the application ALLOCATED pinned (hipHostMalloc, a framework's pinned allocator) is mapped into the GPUs already: such pages are
+// served as they are and never (un)registered here.  Not every system can pin pages a process already has -- a GPU passed through to a
+// virtual machine cannot -- and there an application's column storage has to come from a pinned allocation (infera_hip_host_malloc).
+bool pinned_by_application(uintptr_t pb, uintptr_t pe) {
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof at);
+  void *base = nullptr;
+  size_t size = 0;
+  const bool known = hipPointerGetAttributes(&at, reinterpret_cast<void *>(pb)) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer &&
+                     hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t *>(&base), &size, at.devicePointer) == hipSuccess;
+  (void)hipGetLastError();  // (ordinary memory is an error to some of these queries: it must not surface at the next launch check)
+  if (!known) return false;
+  const uintptr_t ab = reinterpret_cast<uintptr_t>(base) - (reinterpret_cast<uintptr_t>(at.devicePointer) - pb);  // the allocation, as host addresses
+  return ab <= pb && pe <= ((ab + size + 4095) & ~uintptr_t(4095));  // (allocations are whole pages)
+}
+
+intptr_t hip_register_span(uintptr_t pb, uintptr_t pe, bool &owned) {
   const auto &ds = devices();
   DeviceRestore restore;
-  // portable + mapped: visible to every selected GPU; the pages stay where they are (no copy), pinned until unregistered
   HIP_TRY(hipSetDevice(ds.ids[0]));
-  HIP_TRY(hipHostRegister(reinterpret_cast<void *>(pb), pe - pb, hipHostRegisterPortable | hipHostRegisterMapped));
+  owned = !pinned_by_application(pb, pe);
+  if (owned) {
+    // portable + mapped: visible to every selected GPU; the pages stay where they are (no copy), pinned until unregistered
+    const hipError_t re = hipHostRegister(reinterpret_cast<void *>(pb), pe - pb, hipHostRegisterPortable | hipHostRegisterMapped);
+    if (re != hipSuccess) {
+      (void)hipGetLastError();  // (the runtime keeps the error for the next launch check of this thread otherwise)
+      throw InferaError::onnx(std::string("HIP: hipHostRegister: ") + hipGetErrorString(re) +
+                              " (a system that cannot pin memory the process already has registers only storage that was allocated pinned: "
+                              "infera_hip_host_malloc, hipHostMalloc)");
+    }
+  }
   intptr_t delta = 0;
   for (size_t i = 0; i < ds.ids.size(); i++) {
     void *dptr = nullptr;
@@ -66,7 +94,7 @@ intptr_t hip_register_span(uintptr_t pb, uintptr_t pe) {
     if (ge == hipSuccess) ge = hipHostGetDevicePointer(&dptr, reinterpret_cast<void *>(pb), 0);
     const intptr_t d = intptr_t(reinterpret_cast<uintptr_t>(dptr)) - intptr_t(pb);
     if (ge != hipSuccess || (i > 0 && d != delta)) {
-      (void)hipHostUnregister(reinterpret_cast<void *>(pb));
+      if (owned) (void)hipHostUnregister(reinterpret_cast<void *>(pb));
       if (ge != hipSuccess) hip_fail(ge, "hipHostGetDevicePointer");
       throw InferaError::onnx("registered host memory has different device addresses on different GPUs");
     }
@@ -115,8 +143,10 @@ bool unmap_dead_blocks(const std::vector<std::shared_ptr<PageBlock>> &dead) {
       }
     }
     if (drained) {
-      UnsafeOpGuard guard;
-      (void)hipHostUnregister(reinterpret_cast<void *>(blk->pb));
+      if (blk->owned) {
+        UnsafeOpGuard guard;
+        (void)hipHostUnregister(reinterpret_cast<void *>(blk->pb));
+      }
     } else {
       all_drained = false;
       // the stuck readers hold RAW pointers to the block object (ZeroCopyPins) and will decrement its reader count if they ever return: the
@@ -199,10 +229,11 @@ void register_host_memory(const void *base, size_t bytes) {
   {
     UnsafeOpGuard guard;
     try {
-      for (; pinned < fresh.size(); pinned++) fresh[pinned]->dev_delta = hip_register_span(fresh[pinned]->pb, fresh[pinned]->pe);
+      for (; pinned < fresh.size(); pinned++) fresh[pinned]->dev_delta = hip_register_span(fresh[pinned]->pb, fresh[pinned]->pe, fresh[pinned]->owned);
     } catch (...) {
       failure = std::current_exception();
-      for (size_t i = 0; i < pinned; i++) (void)hipHostUnregister(reinterpret_cast<void *>(fresh[i]->pb));
+      for (size_t i = 0; i < pinned; i++)
+        if (fresh[i]->owned) (void)hipHostUnregister(reinterpret_cast<void *>(fresh[i]->pb));
     }
   }
   // ---- publish (or take the plan back)
@@ -350,6 +381,23 @@ const void *lookup_host_memory(const void *p, size_t bytes) {
 }
 
 size_t registered_host_ranges() { return g_nranges.load(std::memory_order_acquire); }
+
+bool pins_application_memory() {
+  static const bool works = [] {
+    const auto &ds = devices();
+    void *page = nullptr;
+    if (ds.ids.empty() || posix_memalign(&page, 4096, 4096) != 0) return false;
+    std::memset(page, 0, 4096);
+    DeviceRestore restore;
+    UnsafeOpGuard guard;
+    bool ok = hipSetDevice(ds.ids[0]) == hipSuccess && hipHostRegister(page, 4096, hipHostRegisterPortable | hipHostRegisterMapped) == hipSuccess;
+    if (ok) (void)hipHostUnregister(page);
+    (void)hipGetLastError();
+    std::free(page);
+    return ok;
+  }();
+  return works;
+}
 
 void copy_rect_to_device(hipStream_t stream, float *dst, const void *src, size_t src_pitch, size_t width, size_t height) {
   HIP_TRY(hipMemcpy2DAsync(dst, width, src, src_pitch, width, height, hipMemcpyHostToDevice, stream));

@@ -434,6 +434,39 @@ int32_t infera_hip_free(int32_t device, void *ptr) {
              : -1;
 }
 
+void *infera_hip_host_malloc(uint64_t bytes) {
+  void *p = nullptr;
+  guarded([&] {
+    const auto &ds = devices();
+    if (ds.ids.empty()) throw InferaError::onnx("HIP backend unavailable: " + ds.why);
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;  // (called from the application's threads: their current device is put back)
+    hipError_t e = hipSetDevice(ds.ids[0]);
+    if (e == hipSuccess) e = hipHostMalloc(&p, bytes, hipHostMallocPortable | hipHostMallocMapped);
+    if (prev >= 0) (void)hipSetDevice(prev);
+    if (e != hipSuccess) {
+      p = nullptr;
+      (void)hipGetLastError();
+      throw InferaError::onnx(std::string("HIP: hipHostMalloc: ") + hipGetErrorString(e));
+    }
+  });
+  return p;
+}
+
+int32_t infera_hip_pins_application_memory(void) { return pins_application_memory() ? 1 : 0; }
+
+int32_t infera_hip_host_free(void *ptr) {
+  return guarded([&] {
+           if (!ptr) return;
+           if (hipHostFree(ptr) != hipSuccess) {
+             (void)hipGetLastError();
+             throw InferaError::onnx("HIP: hipHostFree failed");
+           }
+         })
+             ? 0
+             : -1;
+}
+
 int32_t infera_hip_memcpy_h2d(int32_t device, void *dst, const void *src, uint64_t bytes) {
   return guarded([&] {
            if (!dst || !src) throw InferaError::null_pointer();

@@ -283,9 +283,15 @@ def aligned_empty(n: int, dtype, align: int = 4096, huge: bool = False) -> np.nd
 def synth_table(rows: int, ncols: int, seed: int = 42, threads: int = 8, dtype=np.float32, align: int = 0, huge: bool = False) -> np.ndarray:
     """A materialised columnar table in host memory (row groups of 122,880 rows, one contiguous run per column inside a
     group), filled with the generator of SURVEY.md 8d.  Flat array of rows*ncols elements, float32 (FLOAT columns) or
-    float64 (DOUBLE columns, the same values widened).  align / huge: see aligned_empty (default: wherever numpy puts it)."""
+    float64 (DOUBLE columns, the same values widened).  align / huge: see aligned_empty (default: wherever numpy puts it -- or, with a GPU on a system where
+    only memory allocated pinned can be registered, a pinned allocation, so that the table can serve the registered scans as well)."""
     n = int(lib().infera_sql_table_floats(rows, ncols))
-    t = aligned_empty(n, dtype, align or 4096, huge) if (align or huge) else np.empty(n, dtype)
+    if align or huge:
+        t = aligned_empty(n, dtype, align or 4096, huge)
+    elif capi.device_count() > 0 and not capi.pins_application_memory():
+        t = capi.pinned_empty(n, dtype)  # (ordinary memory cannot be registered on this system: a table that may be has to be allocated pinned)
+    else:
+        t = np.empty(n, dtype)
     if t.dtype == np.float64:
         lib().infera_sql_synth_table_f64(t.ctypes.data, seed, rows, ncols, threads)
     else:

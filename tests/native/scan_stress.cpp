@@ -33,6 +33,16 @@ void fail(const std::string &what) {
   const char *e = infera_last_error();
   std::fprintf(stderr, "FAIL: %s (last error on this thread: %s)\n", what.c_str(), e ? e : "<none>");
 }
+// Page-aligned memory that can be registered: ordinary memory where the system pins what a process already has, allocated pinned where it does
+// not (include/infera_hip.h: infera_hip_host_malloc).  Lives until the process exits.
+void *registrable_alloc(size_t bytes) {
+  void *p = infera_hip_pins_application_memory() ? std::aligned_alloc(4096, bytes) : infera_hip_host_malloc(bytes);
+  if (!p) {
+    std::fprintf(stderr, "FAIL: cannot allocate %zu bytes\n", bytes);
+    std::exit(1);
+  }
+  return p;
+}
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 }  // namespace
 
@@ -53,7 +63,7 @@ int main(int argc, char **argv) {
   }
   // the table: [NCHUNKS] row groups of CHUNK rows, one contiguous run per column inside a group (a columnar store's layout)
   const size_t table_floats = size_t(NCHUNKS) * K * CHUNK;
-  float *table = static_cast<float *>(std::aligned_alloc(4096, table_floats * 4));
+  float *table = static_cast<float *>(registrable_alloc(table_floats * 4));
   uint64_t s = 42;
   for (size_t i = 0; i < table_floats; i++) {
     s = s * 6364136223846793005ull + 1442695040888963407ull;
@@ -80,7 +90,7 @@ int main(int argc, char **argv) {
   std::vector<float *> blocks(size_t(CHURN_CHUNKS) * BLOCKS_PER_CHUNK);
   for (int j = 0; j < CHURN_CHUNKS; j++)
     for (int b = 0; b < BLOCKS_PER_CHUNK; b++) {
-      float *blk = static_cast<float *>(std::aligned_alloc(4096, BLOCK_BYTES));
+      float *blk = static_cast<float *>(registrable_alloc(BLOCK_BYTES));
       std::memcpy(blk, table + (size_t(j) * K + size_t(b) * BLOCK_COLS) * CHUNK, BLOCK_BYTES);
       blocks[size_t(j) * BLOCKS_PER_CHUNK + size_t(b)] = blk;
     }

@@ -366,6 +366,7 @@ def test_bits_independent_of_call_path(api, tmp_path):
         assert np.array_equal(m(x[1000:1017]), ref[1000:1017])  # a slice from the middle
         cols = [np.ascontiguousarray(x_cat[:, j]) for j in range(4)] + [np.ascontiguousarray(x_num[:, j]) for j in range(3)]  # int64 and f32 columns
         assert np.array_equal(api.predict_columns("paths", cols), ref)  # the column-major staged chunk is handed over row-major
+        x = api.registrable(x)  # (where ordinary memory cannot be registered: a copy in memory allocated pinned)
         api.register_host_memory(x)
         try:
             assert np.array_equal(api.predict("paths", x), ref)  # zero-copy == staged

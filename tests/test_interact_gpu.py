@@ -215,6 +215,7 @@ def test_bits_independent_of_call_path(api, tmp_path):
         assert np.array_equal(m(x[1000:1017]), ref[1000:1017])  # a slice from the middle
         cols = [np.ascontiguousarray(x_cat[:, j]) for j in range(4)] + [np.ascontiguousarray(x_num[:, j]) for j in range(3)]  # int64 and f32 columns
         assert np.array_equal(api.predict_columns("paths", cols), ref)
+        x = api.registrable(x)  # (where ordinary memory cannot be registered: a copy in memory allocated pinned)
         api.register_host_memory(x)
         try:
             assert np.array_equal(api.predict("paths", x), ref)  # zero-copy == staged
@@ -234,6 +235,7 @@ def test_bits_independent_of_call_path(api, tmp_path):
             for n in (1, 17, 333, 2048):
                 assert np.array_equal(m(flat[:n]), ref[:n]), n
             assert np.array_equal(m(flat[1000:1017]), ref[1000:1017])
+            flat = api.registrable(flat)  # (where ordinary memory cannot be registered: a copy in memory allocated pinned)
             api.register_host_memory(flat)
             try:
                 assert np.array_equal(api.predict("direct", flat), ref)

@@ -274,6 +274,7 @@ def test_bits_independent_of_call_path(api, tmp_path):
         assert np.array_equal(api.predict("paths", np.ascontiguousarray(flat[perm])), ref[perm])
         cols = [np.ascontiguousarray(flat[:, j]) for j in range(2 * T)]
         assert np.array_equal(api.predict_columns("paths", cols), ref)  # column-major staged chunks == row-major
+        flat = api.registrable(flat)  # (where ordinary memory cannot be registered: a copy in memory allocated pinned)
         api.register_host_memory(flat)
         try:
             assert np.array_equal(api.predict("paths", flat), ref)  # zero-copy == staged

@@ -155,6 +155,7 @@ def test_mlp_bit_for_bit_and_call_paths(api, tmp_path, monkeypatch):
             assert same_bits(api.predict("net", np.ascontiguousarray(x[:n])), ref[:n]), n
         assert same_bits(api.predict("net", np.ascontiguousarray(x[100:117])), ref[100:117])
         assert same_bits(api.predict_columns("net", [np.ascontiguousarray(x[:, j]) for j in range(dims[0])]), ref)
+        x = api.registrable(x)  # (where ordinary memory cannot be registered: a copy in memory allocated pinned)
         api.register_host_memory(x)
         try:
             assert same_bits(api.predict("net", x), ref)

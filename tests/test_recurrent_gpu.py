@@ -175,6 +175,7 @@ def test_bits_independent_of_call_path(api, tmp_path):
             assert np.array_equal(np.concatenate(parts).reshape(n, T, H), ref[:n]), step
         cols = [np.ascontiguousarray(flat[:, j]) for j in range(T * F)]
         assert np.array_equal(api.predict_columns("rep", cols).reshape(rows, T, H), ref)  # column-major staged == row-major
+        flat = api.registrable(flat)  # (where ordinary memory cannot be registered: a copy in memory allocated pinned)
         api.register_host_memory(flat)
         try:
             assert np.array_equal(api.predict("rep", flat).reshape(rows, T, H), ref)  # zero-copy == staged

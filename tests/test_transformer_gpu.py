@@ -226,6 +226,7 @@ def test_bits_independent_of_call_path(api, tmp_path):
         assert np.array_equal(api.predict("paths", np.ascontiguousarray(flat[1000:1017])), ref[1000:1017])
         cols = [np.ascontiguousarray(flat[:, j]) for j in range(T * F)]
         assert np.array_equal(api.predict_columns("paths", cols), ref)  # column-major staged chunks == row-major
+        flat = api.registrable(flat)  # (where ordinary memory cannot be registered: a copy in memory allocated pinned)
         api.register_host_memory(flat)
         try:
             assert np.array_equal(api.predict("paths", flat), ref)  # zero-copy == staged

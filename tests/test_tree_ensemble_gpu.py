@@ -251,6 +251,7 @@ def test_bits_independent_of_call_path(api, tmp_path):
         assert np.array_equal(api.predict_from_blob("rep", x[:20000].tobytes()), ref[:20000])
         cols = [np.ascontiguousarray(x[:, j]) for j in range(F)]
         assert np.array_equal(api.predict_columns("rep", cols), ref)
+        x = api.registrable(x)  # (where ordinary memory cannot be registered: a copy in memory allocated pinned)
         api.register_host_memory(x)
         try:
             assert np.array_equal(api.predict("rep", x), ref)

@@ -17,6 +17,13 @@ from infera_amd import synth
 
 def _page_aligned(shape, dtype):
     """An array that owns whole 4 KiB pages (registration is per page: two registered ranges must not share one)."""
+    from infera_amd import capi
+
+    if not capi.pins_application_memory():  # this system registers only memory that was ALLOCATED pinned (include/infera_hip.h)
+        a = capi.pinned_empty(shape, dtype)
+        a[...] = 0
+        assert a.ctypes.data % 4096 == 0 and a.flags.c_contiguous
+        return a
     n = int(np.prod(shape)) * np.dtype(dtype).itemsize
     raw = np.zeros((n + 4095) // 4096 * 4096 + 4096, np.uint8)
     off = (-raw.ctypes.data) % 4096
@@ -216,6 +223,7 @@ raw = np.zeros(k * rows * 4 + 8192, np.uint8)
 off = (-raw.ctypes.data) %% 4096
 big = raw[off:off + k * rows * 4].view(np.float32).reshape(k, rows)
 big[...] = synth.table(3, 0, rows, k).T
+big = capi.registrable(big)  # (where ordinary memory cannot be registered: a copy in memory allocated pinned, page-aligned as well)
 capi.register_host_memory(big)
 h = hashlib.sha256()
 z0 = capi.zero_copy_calls()
