@@ -75,6 +75,7 @@ struct ChannelNormTables { const float *gamma = nullptr, *beta = nullptr; };  //
 struct EmbedTables { const int32_t *desc = nullptr; const uint16_t *map = nullptr; const float *tab = nullptr; };  // Embed (host/embed.hpp: piece descriptors, column -> piece map or null, the tables)
 struct InteractTables { const int32_t *map = nullptr; };  // Interact, dot mode (host/interact.hpp: output column -> Z entry or column of T)
 struct RotaryTables { const float *A = nullptr, *B = nullptr; };  // Rotary (row-major [T, rd] each: the factor of x[j] and of x[partner(j)])
+struct SpectrumTables { const float *window = nullptr, *twiddle = nullptr, *split = nullptr; };  // Spectrum (host/spectrum.hpp: the window [n], the n/2-point twiddles, the split factors)
 struct RnnTables { const float *wr = nullptr, *bias = nullptr, *bias2 = nullptr, *h0 = nullptr, *c0 = nullptr; };
 struct DeviceStep {  // (a step fills the one struct of its family)
   PlainTables plain;
@@ -95,6 +96,7 @@ struct DeviceStep {  // (a step fills the one struct of its family)
   TokensTables tokens;
   EmbedTables embed;
   InteractTables interact;
+  SpectrumTables spectrum;
   RotaryTables rotary;
 };
 

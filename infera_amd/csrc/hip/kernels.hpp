@@ -8,6 +8,10 @@
 #include <string>
 #include <vector>
 
+namespace infera_hip {
+struct SpectrumPack;  // host/spectrum.hpp
+}
+
 namespace infera_hip::kern {
 
 // Activation codes shared with plan.hpp (Act enum values).
@@ -376,6 +380,11 @@ void resize2d(hipStream_t s, const float *X, float *Y, int64_t rows, int C, int 
 
 // ---- DepthToSpace / SpaceToDepth (pixelshuffle.hip; the four forms: host/pixelshuffle.hpp) ------
 // C, H, W = the input; OC, OH, OW = the output; b = the block size
+// ---- Spectrum: the real DFT / STFT of x [rows, C, L] (spectrum.hip; host/spectrum.hpp has the definition and the pack) ----
+// y: [rows, C, frames, bins (, 2)] or, bins_major, [rows, C, bins, frames (, 2)]; win [n], tw [n / 2][2], split [n / 2 + 1][2] as pack_spectrum
+// built them.  false: the geometry is beyond the kernel's caps (nothing was launched)
+bool spectrum(hipStream_t s, const float *x, float *y, const SpectrumPack &p, const float *win, const float *tw, const float *split, int64_t rows);
+
 struct PixelShuffleGeom {
   int b, C, H, W, OC, OH, OW;
   bool to_space, channel_major;

@@ -244,6 +244,10 @@ void Scheduler::decide_layout(bool commit) {
   }
   for (const auto &s : st)
     if (elementwise(s) && s.in0 >= 0 && m.nchw_buf[size_t(s.in0)] && is4d(s.out) && s.out != m.plan.out_buf) m.nchw_buf[size_t(s.out)] = 1;
+  // A spectrogram (spectrum.hip) and the elementwise chain behind it (Add eps, Log) are flat windows in plain element order: a convolution
+  // that reads one as a [1, bins, frames] image reads it like the caller's own
+  for (const auto &s : st)
+    if (s.kind == StepKind::Spectrum || (elementwise(s) && s.in0 > 0 && !is4d(s.in0) && !is4d(s.out) && m.nchw_buf[size_t(s.in0)])) m.nchw_buf[size_t(s.out)] = 1;
   for (const auto &s : st) {
     any_conv = any_conv || reads_nchw(s);
     // (CopyCols = channel concat: a contiguous per-row block in NCHW and in channel-quad planes alike)

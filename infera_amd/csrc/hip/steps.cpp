@@ -6,6 +6,7 @@
 #include "../host/deconv.hpp"
 #include "../host/embed.hpp"
 #include "../host/interact.hpp"
+#include "../host/spectrum.hpp"
 #include "../host/nearest.hpp"
 #include "../host/channelnorm.hpp"
 #include "../host/onnx_model.hpp"
@@ -486,6 +487,18 @@ void launch_rotary(const PassRunner &r, const Step &x, const RotaryTables &t) {
     throw InferaError::onnx("Rotary kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
 }
 
+// ---- Spectrum (host/spectrum.hpp SpectrumPack, spectrum.hip): the window, the twiddles of the half-length transform, the split factors ----
+void upload_spectrum(const Step &s, SpectrumTables &t, const Upload &up) {
+  t.window = up(s.spectrum->window);
+  t.twiddle = up(s.spectrum->twiddle);
+  t.split = up(s.spectrum->split);
+}
+void launch_spectrum(const PassRunner &r, const Step &x, const SpectrumTables &t) {
+  if (r.in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: a Spectrum step reads its input row-major");
+  if (!kern::spectrum(r.stream, r.buf(x.in0), r.buf(x.out), *x.spectrum, t.window, t.twiddle, t.split, r.nr))
+    throw InferaError::onnx("Spectrum kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+
 // ---- PixelShuffle (pixelshuffle.hip): no tables; the scheduler chose the form for the two layouts (Step::out_mode) ----
 void launch_pixelshuffle(const PassRunner &r, const Step &x) {
   if (r.in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: a PixelShuffle step reads its input row-major");
@@ -561,6 +574,7 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::Interact: launch_interact(*this, x, d.interact); break;
     case StepKind::Rotary: launch_rotary(*this, x, d.rotary); break;
     case StepKind::PixelShuffle: launch_pixelshuffle(*this, x); break;
+    case StepKind::Spectrum: launch_spectrum(*this, x, d.spectrum); break;
     // the steps without tables
     case StepKind::Unary: kern::unary(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], act_of(x)); break;
     case StepKind::BinaryAct:
@@ -637,6 +651,7 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::Interact: return upload_interact(s, d.interact, up);
     case StepKind::Rotary: return upload_rotary(s, d.rotary, up);
     case StepKind::PixelShuffle: return;  // (a copy by index arithmetic: no tables)
+    case StepKind::Spectrum: return upload_spectrum(s, d.spectrum, up);
     default: return;  // (no tables)
   }
 }

@@ -649,6 +649,17 @@ struct Lowerer {
   // the step over the [N,C,H,W] activation `a`, bound to out_node's first output; refusals name `at`
   void pixel_shuffle_step(const NodeDef &at, const NodeDef &out_node, const Val &a, int64_t b, bool to_space, bool channel_major, const std::string &origin);
 
+  // ---- lower_spectrum.cpp: DFT and STFT on real signals (INTEGRATION.md 2.6 "Spectral front ends") ----
+  // the nodes behind the transform `n` that its step stands for -- [Transpose] -> magnitude -> [Transpose], sole readers each: sets p's mode
+  // and layout, marks them absorbed (they emit nothing) and returns the last (n: none); *keep: the magnitude kept its trailing axis
+  const NodeDef *spectrum_tail(const NodeDef &n, bool stft, SpectrumPack &p, bool *keep);
+  // ONE Spectrum step over the signals of `a`, bound to the last absorbed node's output; lead: the axes in front of the transform's own
+  void spectrum_step(const NodeDef &n, const Val &a, SpectrumPack p, const std::vector<int64_t> &lead);
+  // refuses, in the node's name, every operand but a rows-first f32 activation
+  void spectrum_input(const NodeDef &n, const Val &a, const char *what);
+  void dft(const NodeDef &n);
+  void stft(const NodeDef &n);
+
   // ---- lowering.cpp: quantised and float16 graphs ----
   QArgs quant_args(const NodeDef &n, size_t si, size_t zi, const char *what);
   Quant act_quant(const NodeDef &n, const QArgs &qa, const char *what);

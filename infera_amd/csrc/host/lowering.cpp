@@ -3638,7 +3638,7 @@ namespace lowering {
       }
     static const std::set<std::string> reads_time_major = {"Transpose", "Squeeze", "Unsqueeze", "Reshape", "Identity", "Dropout", "Flatten", "Shape",
                                                            "Gather", "Slice", "LSTM", "GRU", "RNN",
-                                                           "InstanceNormalization", "GroupNormalization"};  // (refused in their own words)
+                                                           "InstanceNormalization", "GroupNormalization", "DFT", "STFT"};  // (refused in their own words)
     check_row_axis(n, reads_time_major.count(op) > 0);
     if (op == "DynamicQuantizeLinear")
       bad_form(n, "its scale spans all rows of a call, so a row's result would depend on its chunk; quantise statically (QuantizeLinear with constant scales)");
@@ -3695,6 +3695,8 @@ namespace lowering {
     else if (op == "ConvTranspose") conv_transpose(n);
     else if (op == "Resize" || op == "Upsample") resize(n);
     else if (op == "DepthToSpace" || op == "SpaceToDepth") depth_space(n);
+    else if (op == "DFT") dft(n);
+    else if (op == "STFT") stft(n);
     else if (op == "BatchNormalization") batchnorm(n);
     else if (op == "MaxPool") pool(n, true);
     else if (op == "AveragePool") pool(n, false);

@@ -10,6 +10,7 @@
 #include "embed.hpp"
 #include "interact.hpp"
 #include "spatialnorm.hpp"
+#include "spectrum.hpp"
 #include "tokens.hpp"
 #include "nearest.hpp"
 #include "pixelshuffle.hpp"
@@ -31,6 +32,7 @@ double Plan::flops_per_row() const {
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
     else if (s.kind == StepKind::Nearest) f += 2.0 * double(s.nearest->F) * double(s.nearest->M);
     else if (s.kind == StepKind::NearestVote) f += 2.0 * double(s.M);  // a weight and an add per neighbour
+    else if (s.kind == StepKind::Spectrum) f += 2.5 * double(s.spectrum->C * s.spectrum->frames * s.spectrum->n) * std::log2(double(s.spectrum->n));  // the usual count of a real transform
     else if (s.kind == StepKind::Interact) f += s.interact->mode == kInteractDot ? 2.0 * double(s.interact->k * s.interact->k * s.interact->d) : 4.0 * double(s.interact->k * s.interact->d);
     else if (s.kind == StepKind::Rotary) f += 3.0 * double(s.attn_T * s.attn_heads * s.rot_rd);  // two products and a sum per rotated column
     else if (s.kind == StepKind::Recurrent) f += 2.0 * double(s.rnn->T * s.rnn->D * s.rnn->G * s.rnn->H) * double(s.rnn->F + s.rnn->H);
@@ -39,7 +41,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary", "PixelShuffle", "NearestVote"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary", "PixelShuffle", "NearestVote", "Spectrum"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -203,6 +205,13 @@ std::string Plan::describe_json() const {
           o << "{\"copy\":" << e.d << ",\"src\":" << e.src << ",\"out\":" << e.out << "}";
       }
       o << "]";
+    }
+    if (s.kind == StepKind::Spectrum) {
+      const SpectrumPack &q = *s.spectrum;
+      static const char *modes[] = {"complex", "power", "magnitude"};
+      o << ",\"op\":\"" << (q.stft ? "STFT" : "DFT") << "\",\"L\":" << q.L << ",\"C\":" << q.C << ",\"n\":" << q.n << ",\"hop\":" << q.hop << ",\"frames\":" << q.frames << ",\"bins\":" << q.bins
+        << ",\"onesided\":" << (q.onesided ? "true" : "false") << ",\"mode\":\"" << modes[q.mode] << "\",\"layout\":\"" << (q.bins_major ? "bins_major" : "frames_major") << "\",\"form\":\"" << q.form
+        << "\",\"frames_per_group\":" << q.Fw << ",\"lds_bytes\":" << q.lds_bytes;
     }
     if (s.kind == StepKind::Interact) {
       const InteractPack &q = *s.interact;

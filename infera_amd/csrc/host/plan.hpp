@@ -24,6 +24,7 @@ struct VotePack;     // host/nearest.hpp
 struct DeconvPack;   // host/deconv.hpp
 struct EmbedPack;    // host/embed.hpp
 struct InteractPack;  // host/interact.hpp
+struct SpectrumPack;  // host/spectrum.hpp
 
 // Kinds 1..5 may be fused into the epilogue of a Dense / Conv2d step (the MFMA kernels resolve them at
 // compile time); the rest run in the elementwise kernels (fused into Binary*/AffineChannel or as a Unary step).
@@ -83,6 +84,7 @@ enum class StepKind : int {
   RmsNorm = 42,       // y = x / sqrt(mean(x^2) + ln_eps) * scale[K] over each of the `rep` vectors of K elements of a row (RMSNormalization; layernorm.hip)
   Rotary = 43,        // rotary position embedding of in0 [rows, attn_T, ld] read through the view (attn_ld[0], attn_off[0]) into a dense [rows, attn_T, attn_heads * attn_dh]: column j < rot_rd of a head, y[j] = fl(fl(x[j] * scale[t, j]) + fl(x[partner(j)] * shift[t, j])), partner(j) = j +- rot_rd / 2 or j ^ 1 (rot_interleaved); the other columns are bit copies (RotaryEmbedding and the rotate_half spelling; rotary.hip)
   PixelShuffle = 44,  // DepthToSpace / SpaceToDepth of in0 [rows, C, H, Wd] to [rows, Mo, OH, OW] with block ps_block: a bit copy of every element, in one of four forms (ps_to_space, ps_channel_major: host/pixelshuffle.hpp); out_mode (set by the scheduler): the PixelShuffleKernel that runs it (pixelshuffle.hip)
+  Spectrum = 46,      // the real DFT / STFT of in0 [rows, C, L]: frames of n samples `hop` apart times a window, out [rows, C, frames, bins (, 2)] or, bins_major, [rows, C, bins, frames (, 2)] as complex pairs, power or magnitude (SpectrumPack, host/spectrum.hpp, spectrum.hip)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
@@ -161,6 +163,7 @@ struct Step {
   std::shared_ptr<const VotePack> vote;  // NearestVote (beside `nearest`, the set whose lists it reads)
   std::shared_ptr<const EmbedPack> embed;
   std::shared_ptr<const InteractPack> interact;
+  std::shared_ptr<const SpectrumPack> spectrum;
   std::shared_ptr<const DeconvPack> deconv;  // ConvTranspose2d: phase tap lists; Resize2d: source tables
   int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut, RowReduce: ReduceOp, TopK: 0 values / 1 indices, Nearest / NearestReduce: NearestOut, NearestVote: VoteOut
   // Attention: Q = in0, K = in1, V = in2 (the same buffer three times when the projections are merged), each [rows, T, ld] with the head

@@ -5175,3 +5175,135 @@ def pixel_unshuffle_stem(b: int = 2, in_ch: int = 3, size: int = 12, width: int 
     net.nodes.append(node("Flatten", ["gap"], ["scores"], [attr_i("axis", 1)], name="flatten"))
     net.layers.append(("reshape", "scores", ["gap"], dict(shape=(classes,))))
     return net.finish("pixel_unshuffle_stem", value_info("X", ["N", in_ch, size, size]), "scores", ["N", classes], extra={"in_shape": (in_ch, size, size)})
+
+
+# ------------------------------------------------------------------------------------------
+# Spectral front ends: DFT / STFT on real signals (INTEGRATION.md 2.6 "Spectral front ends")
+# ------------------------------------------------------------------------------------------
+
+def _spectrum_reader(nodes: list, inits: list, cur: str, dims: list, reader: str | None, keepdims: int, opset: int) -> tuple[str, list]:
+    """The magnitude behind a transform `cur` [..., 2]: "sumsq" (ReduceSumSquare), "l2" (ReduceL2), "pow" (Pow 2 -> ReduceSum), "pow_sqrt"
+    (... -> Sqrt), "relu" (a reader that is none of them), None.  Returns the value and its dims."""
+    if reader is None:
+        return cur, dims
+    if reader == "relu":
+        nodes.append(node("Relu", [cur], ["spec_relu"], name="spec_relu"))
+        return "spec_relu", dims
+    inits.append(tensor("spec_axes", np.array([-1], np.int64)))
+    out_dims = dims[:-1] + ([1] if keepdims else [])
+    if reader in ("sumsq", "l2"):
+        op = "ReduceSumSquare" if reader == "sumsq" else "ReduceL2"
+        by_input = opset >= 18
+        nodes.append(node(op, [cur] + (["spec_axes"] if by_input else []), ["spec_mag"],
+                          [attr_i("keepdims", keepdims)] + ([] if by_input else [attr_ints("axes", [-1])]), name="spec_mag"))
+        return "spec_mag", out_dims
+    inits.append(tensor("spec_two", np.array(2.0, np.float32).reshape(())))
+    nodes += [node("Pow", [cur, "spec_two"], ["spec_sq"], name="spec_pow"),
+              node("ReduceSum", ["spec_sq", "spec_axes"], ["spec_pw"], [attr_i("keepdims", keepdims)], name="spec_sum")]
+    if reader == "pow_sqrt":
+        nodes.append(node("Sqrt", ["spec_pw"], ["spec_abs"], name="spec_sqrt"))
+        return "spec_abs", out_dims
+    return "spec_pw", out_dims
+
+
+def dft_model(L: int = 64, n: int | None = None, C: int | None = None, onesided: int = 1, opset: int = 17, axis: int | None = None,
+              reader: str | None = None, keepdims: int = 0, inverse: int = 0, last: int = 1, nonconst: str = "", elem: int = FLOAT,
+              time_major: bool = False) -> bytes:
+    """DFT of X [N, L, last] (C: [N, C, L, last]); n: dft_length (None: absent).  opset 17 carries `axis` as an attribute, opset 20 as a
+    constant input.  nonconst = "dft_length": that input is computed; time_major: X reaches the node through Transpose(1,0,2)."""
+    dims = ["N"] + ([C] if C else []) + [L, last]
+    nodes, inits, cur = [], [], "X"
+    if time_major:
+        nodes.append(node("Transpose", ["X"], ["Xt"], [attr_ints("perm", [1, 0, 2])], name="tm"))
+        cur = "Xt"
+    ins, attrs = [cur], [attr_i("onesided", onesided)] + ([attr_i("inverse", 1)] if inverse else [])
+    if nonconst == "dft_length":
+        nodes.append(node("Cast", ["X"], ["len_x"], [attr_i("to", INT64)], name="len_cast"))
+        ins.append("len_x")
+    elif n is not None:
+        inits.append(tensor("dft_len", np.array(n, np.int64).reshape(())))
+        ins.append("dft_len")
+    if axis is not None and opset >= 20:
+        inits.append(tensor("dft_axis", np.array(axis, np.int64).reshape(())))
+        ins += [""] * (2 - len(ins)) + ["dft_axis"]
+    elif axis is not None:
+        attrs.append(attr_i("axis", axis))
+    nodes.append(node("DFT", ins, ["spec"], attrs, name="dft"))
+    nn = L if n is None else n
+    out, odims = _spectrum_reader(nodes, inits, "spec", ["N"] + ([C] if C else []) + [nn // 2 + 1 if onesided else nn, 2], reader, keepdims, opset)
+    return model("dft", nodes, inits, [value_info("X", dims, elem)], [value_info(out, odims, elem)], opset=opset)
+
+
+def stft_nodes(nodes: list, inits: list, x: str, n: int, hop: int, window=None, onesided: int = 1, frame_length: bool | int = False,
+               nonconst: str = "") -> str:
+    """STFT of `x` [N, L, 1] -> "spec" [N, frames, bins, 2].  window: None or n values; frame_length: True (n) or another number."""
+    inits.append(tensor("stft_step", np.array(hop, np.int64).reshape(())))
+    ins = [x, "stft_step", "", ""]
+    if window is not None:
+        inits.append(tensor("stft_window", np.asarray(window, np.float32)))
+        ins[2] = "stft_window"
+    if frame_length is not False:
+        inits.append(tensor("stft_len", np.array(n if frame_length is True else frame_length, np.int64).reshape(())))
+        ins[3] = "stft_len"
+    if nonconst:
+        nodes.append(node("Relu" if nonconst == "window" else "Cast", ["X"], ["computed"], [] if nonconst == "window" else [attr_i("to", INT64)], name="computed"))
+        ins[{"frame_step": 1, "window": 2, "frame_length": 3}[nonconst]] = "computed"
+    while ins[-1] == "":
+        ins.pop()
+    nodes.append(node("STFT", ins, ["spec"], [attr_i("onesided", onesided)], name="stft"))
+    return "spec"
+
+
+def stft_model(L: int = 256, n: int = 64, hop: int = 16, window=None, onesided: int = 1, frame_length: bool | int = False, reader: str | None = None,
+               keepdims: int = 0, transpose: str | None = None, last: int = 1, nonconst: str = "", elem: int = FLOAT, opset: int = 17) -> bytes:
+    """STFT of X [N, L, 1] and what torch writes behind it: transpose = "before" (Transpose(0,2,1,3) behind STFT) or "after" (Transpose behind
+    the magnitude)."""
+    nodes, inits = [], []
+    cur = stft_nodes(nodes, inits, "X", n, hop, window, onesided, frame_length or window is None, nonconst)
+    frames, bins = (L - n) // hop + 1, (n // 2 + 1 if onesided else n)
+    dims = ["N", frames, bins, 2]
+    if transpose == "before":
+        nodes.append(node("Transpose", [cur], ["spec_t"], [attr_ints("perm", [0, 2, 1, 3])], name="spec_t"))
+        cur, dims = "spec_t", ["N", bins, frames, 2]
+    cur, dims = _spectrum_reader(nodes, inits, cur, dims, reader, keepdims, opset)
+    if transpose == "after":
+        nodes.append(node("Transpose", [cur], ["mag_t"], [attr_ints("perm", [0, 2, 1, 3][:len(dims)])], name="mag_t"))
+        cur, dims = "mag_t", [dims[0], dims[2], dims[1]] + dims[3:]
+    return model("stft", nodes, inits, [value_info("X", ["N", L, last], elem)], [value_info(cur, dims, elem)], opset=opset)
+
+
+def spectrogram_model(L: int = 400, n: int = 64, hop: int = 16, mels: int = 12, eps: float = 1e-3, head: str = "lstm", hidden: int = 16, classes: int = 4,
+                      seed: int = 77) -> tuple[bytes, dict]:
+    """A log-spectrogram classifier on X [N, L, 1]: STFT (Hann window) -> power (Pow 2 -> ReduceSum) -> ... -> head.
+    head = "lstm": -> MatMul(mel [bins, mels]) -> Add eps -> Log -> LSTM (layout = 1) -> Y_h -> Gemm: [N, classes].
+    head = "cnn":  the bins-before-frames form (Transpose(0,2,1,3) behind STFT) -> Add eps -> Log -> Unsqueeze(1) -> Conv 3x3 + Relu ->
+    GlobalAveragePool -> Flatten -> Gemm.  Returns the model and the constants a reference needs."""
+    ws = _WeightStream(seed)
+    frames, bins = (L - n) // hop + 1, n // 2 + 1
+    window = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)).astype(np.float32)
+    nodes, inits = [], []
+    cur = stft_nodes(nodes, inits, "X", n, hop, window, 1, True)
+    w = dict(window=window, n=n, hop=hop, eps=np.float32(eps), head=head, frames=frames, bins=bins)
+    if head == "cnn":
+        nodes.append(node("Transpose", [cur], ["spec_t"], [attr_ints("perm", [0, 2, 1, 3])], name="spec_t"))
+        cur = "spec_t"
+    cur, _ = _spectrum_reader(nodes, inits, cur, ["N", 0, 0, 2], "pow", 0, 17)
+    inits.append(tensor("eps", np.array(eps, np.float32).reshape(())))
+    if head == "lstm":
+        w["mel"] = np.abs(ws.take((bins, mels), 1)) / bins
+        inits.append(tensor("mel", w["mel"]))
+        nodes += [node("MatMul", [cur, "mel"], ["mel_pw"], name="mel"), node("Add", ["mel_pw", "eps"], ["pw_eps"], name="add_eps"), node("Log", ["pw_eps"], ["logmel"], name="log")]
+        w.update(W=ws.take((1, 4 * hidden, mels), mels), R=ws.take((1, 4 * hidden, hidden), hidden), B=ws.take((1, 8 * hidden), hidden),
+                 head_W=ws.take((hidden, classes), hidden), head_b=ws.take((classes,), hidden), hidden=hidden)
+        inits += [tensor(k, w[k]) for k in ("W", "R", "B", "head_W", "head_b")] + [tensor("flat2", np.array([-1, hidden], np.int64))]
+        nodes += [node("LSTM", ["logmel", "W", "R", "B"], ["Y", "Y_h"], [attr_i("hidden_size", hidden), attr_i("layout", 1)], name="lstm"),
+                  node("Reshape", ["Y_h", "flat2"], ["last_h"], name="last_h"), node("Gemm", ["last_h", "head_W", "head_b"], ["scores"], name="head")]
+    else:
+        w.update(conv_W=ws.take((8, 1, 3, 3), 9), conv_b=ws.take((8,), 9), head_W=ws.take((8, classes), 8), head_b=ws.take((classes,), 8))
+        inits += [tensor(k, w[k]) for k in ("conv_W", "conv_b", "head_W", "head_b")] + [tensor("ax1", np.array([1], np.int64))]
+        nodes += [node("Add", [cur, "eps"], ["pw_eps"], name="add_eps"), node("Log", ["pw_eps"], ["logspec"], name="log"),
+                  node("Unsqueeze", ["logspec", "ax1"], ["image"], name="image"),
+                  node("Conv", ["image", "conv_W", "conv_b"], ["conv"], [attr_ints("kernel_shape", [3, 3]), attr_ints("pads", [1, 1, 1, 1])], name="conv"),
+                  node("Relu", ["conv"], ["conv_r"], name="conv_relu"), node("GlobalAveragePool", ["conv_r"], ["gap"], name="gap"),
+                  node("Flatten", ["gap"], ["feat"], [attr_i("axis", 1)], name="flatten"), node("Gemm", ["feat", "head_W", "head_b"], ["scores"], name="head")]
+    return model("spectrogram", nodes, inits, [value_info("X", ["N", L, 1])], [value_info("scores", ["N", classes])], opset=17), w
