@@ -383,6 +383,7 @@ void resize2d(hipStream_t s, const float *X, float *Y, int64_t rows, int C, int 
 // ---- Spectrum: the real DFT / STFT of x [rows, C, L] (spectrum.hip; host/spectrum.hpp has the definition and the pack) ----
 // y: [rows, C, frames, bins (, 2)] or, bins_major, [rows, C, bins, frames (, 2)]; win [n], tw [n / 2][2], split [n / 2 + 1][2] as pack_spectrum
 // built them.  false: the geometry is beyond the kernel's caps (nothing was launched)
+// n / 2 a power of two: the kernel per log2(n / 2); else p.passes drives the mixed-radix kernel.  p.pad_*: the absorbed Pad of an STFT
 bool spectrum(hipStream_t s, const float *x, float *y, const SpectrumPack &p, const float *win, const float *tw, const float *split, int64_t rows);
 
 struct PixelShuffleGeom {

@@ -69,7 +69,7 @@ const NodeDef *Lowerer::spectrum_tail(const NodeDef &n, bool stft, SpectrumPack 
 void Lowerer::spectrum_step(const NodeDef &n, const Val &a, SpectrumPack p, const std::vector<int64_t> &lead) {
   bool keep = false;
   const NodeDef *last = spectrum_tail(n, p.stft, p, &keep);
-  const std::string why = spectrum_refusal(p.n, p.C, p.frames, p.bins, p.mode == kSpectrumComplex);
+  const std::string why = spectrum_refusal(p.stft, p.n, p.C, p.frames, p.bins, p.mode == kSpectrumComplex);
   if (!why.empty()) bad_form(n, why);
   pack_spectrum(p);
   std::vector<int64_t> shape = lead;  // [N (, C)]
@@ -119,16 +119,113 @@ void Lowerer::dft(const NodeDef &n) {
   spectrum_step(n, a, std::move(p), rank == 4 ? std::vector<int64_t>{a.shape[0], a.shape[1]} : std::vector<int64_t>{a.shape[0]});
 }
 
+bool Lowerer::pad_signal(const NodeDef &n) {
+  const Val a = get(n, 0);
+  const int64_t rank = int64_t(a.shape.size());
+  if (a.is_const || rank == 4) return false;
+  const std::string only = "only the time axis of a rows-first f32 signal [N, L], [N, 1, L] or [1, N, L] in front of an STFT (and [N,C,H,W] in front of a Conv)";
+  if (a.half || cur_half) bad_form(n, "float16 operands are not supported; cast the signal to float in front of it");
+  if (a.q) bad_form(n, "quantised operands are not supported");
+  if (a.cl || a.pv || a.nn || a.buf < 0 || a.padded()) bad_form(n, "its data is not a rows-first f32 activation; " + only);
+  const bool lead1 = rank == 3 && a.ra == 1 && a.shape[0] == 1;  // [1, N, L]
+  if (!(rank == 2 && a.ra == 0) && !(rank == 3 && a.ra == 0 && a.shape[1] == 1) && !lead1) bad_form(n, "its data is " + shape_str(a.shape) + " (row axis " + std::to_string(a.ra) + "); " + only);
+  const int64_t L = a.shape.back();
+  const std::string mode = n.attr_s("mode", "constant");
+  if (mode != "constant" && mode != "reflect") bad_form(n, "mode = \"" + mode + "\" (only reflect and constant zero padding are absorbed into an STFT)");
+  std::vector<int64_t> pads, axes;
+  if (has_input(n, 1)) {
+    if (!graph_ints_arg(n, 1, "pads", &pads)) bad_form(n, "pads is not a constant");
+  } else if (auto *pp = n.attr_ints("pads")) pads = *pp;
+  if (has_input(n, 3) && !graph_ints_arg(n, 3, "axes", &axes)) bad_form(n, "axes is not a constant");
+  if (axes.empty())
+    for (int64_t i = 0; i < rank; i++) axes.push_back(i);
+  if (pads.size() != 2 * axes.size()) bad_form(n, "pads must hold " + std::to_string(2 * axes.size()) + " entries, got " + std::to_string(pads.size()));
+  int64_t left = 0, right = 0;
+  for (size_t i = 0; i < axes.size(); i++) {
+    const int64_t ax = axes[i] < 0 ? axes[i] + rank : axes[i], lo = pads[i], hi = pads[i + axes.size()];
+    if (lo < 0 || hi < 0) bad_form(n, "negative pads (cropping)");
+    if (ax == rank - 1) left += lo, right += hi;
+    else if (lo || hi) bad_form(n, "pads on axis " + std::to_string(ax) + " of " + shape_str(a.shape) + "; only the time axis (the last) is padded");
+  }
+  double value = double(n.attr_f("value", 0.f));
+  size_t cnt = 1;
+  if (has_input(n, 2) && (!graph_const_scalar(n.inputs[2], &value, &cnt) || cnt != 1)) bad_form(n, "constant_value is not one constant");
+  if (mode == "constant" && value != 0.0) bad_form(n, "a constant_value of " + std::to_string(value) + " (only zero padding is absorbed into an STFT)");
+  if (mode == "reflect" && (left >= L || right >= L)) bad_form(n, "reflect pads (" + std::to_string(left) + ", " + std::to_string(right) + ") reach beyond a signal of L = " + std::to_string(L) + " samples (at most L - 1)");
+  // the readers up to the STFT: the shape holds only the rows (-1), the padded length and 1s, so these nodes move nothing
+  std::vector<int64_t> shape(size_t(rank), 1);
+  shape[size_t(a.ra)] = -1, shape.back() = L + left + right;
+  std::vector<const NodeDef *> chain;
+  const NodeDef *r = graph->sole_reader(n.outputs[0], false);
+  for (; r && GraphIndex::std_dom(*r) && (r->op == "Reshape" || r->op == "Squeeze" || r->op == "Unsqueeze"); r = graph->sole_reader(r->outputs[0], false)) {
+    if (r->inputs.empty() || r->inputs[0] != (chain.empty() ? n : *chain.back()).outputs[0]) break;  // (it reads the signal as a shape operand)
+    std::vector<int64_t> arg, out;
+    if (!graph_ints_arg(*r, 1, r->op == "Reshape" ? "shape" : "axes", &arg)) bad_form(n, "its reader '" + r->name + "' (" + r->op + ") has no constant " + (r->op == "Reshape" ? "shape" : "axes"));
+    const int64_t cur = int64_t(shape.size());
+    if (r->op == "Reshape") {
+      // the entries that are not 1 must be the rows (-1, 0 or the fixed batch) and then the padded length
+      std::vector<int64_t> big;
+      for (int64_t v : arg)
+        if (v != 1) big.push_back(v);
+      const int64_t rows = a.shape[size_t(a.ra)];
+      if (big.size() != 2 || (big[0] != -1 && big[0] != 0 && big[0] != rows) || big[1] != L + left + right)
+        bad_form(n, "its reader '" + r->name + "' reshapes the padded signal to " + shape_str(arg) + "; only [rows, L'] with axes of extent 1 around them");
+      bool seen = false;
+      for (int64_t v : arg) out.push_back(v == 1 ? 1 : seen ? v : (seen = true, -1));
+    } else if (r->op == "Squeeze") {
+      for (int64_t i = 0; i < cur; i++) {
+        bool drop = arg.empty() && shape[size_t(i)] == 1;
+        for (int64_t ax : arg) drop = drop || (ax < 0 ? ax + cur : ax) == i;
+        if (drop && shape[size_t(i)] != 1) bad_form(n, "its reader '" + r->name + "' squeezes an axis of the padded signal that is not 1");
+        if (!drop) out.push_back(shape[size_t(i)]);
+      }
+    } else {
+      const int64_t nr = cur + int64_t(arg.size());
+      size_t src = 0;
+      for (int64_t i = 0; i < nr; i++) {
+        bool ins = false;
+        for (int64_t ax : arg) ins = ins || (ax < 0 ? ax + nr : ax) == i;
+        if (!ins && src >= shape.size()) bad_form(n, "its reader '" + r->name + "' has axes out of range");
+        out.push_back(ins ? 1 : shape[src++]);
+      }
+    }
+    shape = out;
+    chain.push_back(r);
+  }
+  if (!r || !GraphIndex::std_dom(*r) || r->op != "STFT" || r->inputs.empty() || r->inputs[0] != (chain.empty() ? n : *chain.back()).outputs[0])
+    bad_form(n, "the output of a Pad node can only feed a Conv, or -- the time axis of a signal -- one STFT through Reshape / Squeeze / Unsqueeze nodes" +
+                    (r ? "; it reaches '" + r->name + "' (" + r->op + ")" : std::string("; it has several readers or is a model output")));
+  const bool r2 = shape == std::vector<int64_t>{-1, L + left + right}, r3 = shape == std::vector<int64_t>{-1, L + left + right, 1};
+  if (!r2 && !r3) bad_form(n, "the padded signal reaches '" + r->name + "' (STFT) as " + shape_str(shape) + " (-1: the rows); only [N, L'] or [N, L', 1]");
+  for (const NodeDef *c : chain) {
+    size_t idx = 0;
+    graph->producer(c->outputs[0], &idx);
+    absorbed[idx] = 1;
+  }
+  TimePad tp;
+  tp.src = a, tp.left = left, tp.right = right, tp.mode = mode == "reflect" ? kSpectrumPadReflect : kSpectrumPadConstant;
+  shape[0] = a.shape[size_t(a.ra)];
+  tp.shape = shape;
+  time_pads[r->inputs[0]] = tp;
+  return true;
+}
+
 void Lowerer::stft(const NodeDef &n) {
   if (n.inputs.size() < 2) bad_form(n, "signal and frame_step are required");
-  const Val a = get(n, 0);
+  const auto tp = time_pads.find(n.inputs[0]);
+  Val a = tp != time_pads.end() ? tp->second.src : get(n, 0);
+  SpectrumPack p;
+  if (tp != time_pads.end()) {  // (pad_signal has checked the operand; the shape is the padded signal's as this node reads it)
+    p.pad_left = tp->second.left, p.pad_right = tp->second.right, p.pad_mode = tp->second.mode;
+    a.shape = tp->second.shape, a.ra = 0;
+  }
   spectrum_input(n, a, "the signal");
+  if (a.shape.size() == 2) a.shape.push_back(1);  // (torch's exporter passes the rank-2 [N, L] signal)
   if (a.shape.size() != 3) bad_form(n, "the signal must be a real [N, L, 1] value, got " + shape_str(a.shape));
   if (a.shape[2] == 2) bad_form(n, "a complex signal (last axis 2) is not supported; only real signals");
   if (a.shape[2] != 1) bad_form(n, "the signal must be a real [N, L, 1] value, got " + shape_str(a.shape));
-  SpectrumPack p;
   p.stft = true;
-  p.L = a.shape[1];
+  p.L = a.shape[1] - p.pad_left - p.pad_right;
   p.hop = one_int(*this, n, 1, "frame_step");
   if (p.hop < 1) bad_form(n, "frame_step = " + std::to_string(p.hop) + " must be at least 1");
   if (has_input(n, 2)) {
@@ -147,10 +244,10 @@ void Lowerer::stft(const NodeDef &n) {
   if (p.n == 0) bad_form(n, "neither window nor frame_length is given");
   p.onesided = n.attr_i("onesided", 1) != 0;
   p.bins = p.onesided ? p.n / 2 + 1 : p.n;
-  const std::string why = spectrum_refusal(p.n, 1, 1, p.bins, true);  // (the length first: L < n below speaks of a served length)
+  const std::string why = spectrum_refusal(true, p.n, 1, 1, p.bins, true);  // (the length first: L < n below speaks of a served length)
   if (!why.empty()) bad_form(n, why);
-  if (p.L < p.n) bad_form(n, "the signal has L = " + std::to_string(p.L) + " samples, fewer than a frame of " + std::to_string(p.n) + " (no frame)");
-  p.frames = (p.L - p.n) / p.hop + 1;
+  if (p.padded() < p.n) bad_form(n, "the signal has L = " + std::to_string(p.padded()) + " samples, fewer than a frame of " + std::to_string(p.n) + " (no frame)");
+  p.frames = (p.padded() - p.n) / p.hop + 1;
   spectrum_step(n, a, std::move(p), {a.shape[0]});
 }
 

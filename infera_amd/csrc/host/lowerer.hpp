@@ -659,6 +659,17 @@ struct Lowerer {
   void spectrum_input(const NodeDef &n, const Val &a, const char *what);
   void dft(const NodeDef &n);
   void stft(const NodeDef &n);
+  // A Pad of the time axis of a rows-first signal [N, L], [N, 1, L] or [1, N, L] (torch.stft(center=True)) whose only reader, through Reshape /
+  // Squeeze / Unsqueeze nodes, is an STFT: nothing is emitted, the reshapes are marked absorbed and the STFT finds the pad under its signal's
+  // name (time_pads).  false: `n` pads an [N,C,H,W] activation (pad()); every other Pad is refused by name
+  bool pad_signal(const NodeDef &n);
+  struct TimePad {
+    Val src;               // the unpadded signal
+    std::vector<int64_t> shape;  // the padded signal as the STFT reads it: [N, L'] or [N, L', 1]
+    int64_t left = 0, right = 0;
+    int mode = 0;          // SpectrumPad
+  };
+  std::map<std::string, TimePad> time_pads;  // the STFT's signal input -> the Pad absorbed into it
 
   // ---- lowering.cpp: quantised and float16 graphs ----
   QArgs quant_args(const NodeDef &n, size_t si, size_t zi, const char *what);

@@ -1160,6 +1160,8 @@ namespace lowering {
         rest *= d;
       }
       bool lead_ok = tgt[0] == 0 || (tgt[0] == a.shape[0] && a.shape[0] > 0) || (tgt[0] == -1 && neg < 0 && rest == per_row);
+      // (an axis of extent 1 in front of the rows -- the [1, N, L] view torch.stft makes of a 2-D signal: the row axis becomes axis 1)
+      if (!lead_ok && tgt[0] == 1 && tgt.size() == a.shape.size() + 1) return reshape_tagged(n);
       if (!lead_ok) unsupported(n, "target shape " + shape_str(tgt) + " does not keep the row axis of " + shape_str(a.shape));
       if (neg >= 0) {
         if (rest == 0 || per_row % rest) unsupported(n, "cannot infer -1");
@@ -1780,8 +1782,9 @@ namespace lowering {
   // Pad with zeros on the two spatial axes of an [N,C,H,W] activation: no kernel -- the value keeps its buffer and
   // the Conv that consumes it widens its own padding (the form TF / Keras exporters write for 'same' convolutions).
   void Lowerer::pad(const NodeDef &n) {
+    if (pad_signal(n)) return;  // (the time axis of a signal in front of an STFT: lower_spectrum.cpp)
     const Val &a = get(n, 0);
-    if (a.is_const || a.shape.size() != 4) unsupported(n, "only [N,C,H,W] activations");
+    if (a.is_const || a.shape.size() != 4 || a.ra != 0) unsupported(n, "only [N,C,H,W] activations");
     if (n.attr_s("mode", "constant") != "constant") unsupported(n, "only constant (zero) padding");
     std::vector<int64_t> pads;
     if (has_input(n, 1)) pads = const_ints(n, 1, "pads");
@@ -3638,7 +3641,7 @@ namespace lowering {
       }
     static const std::set<std::string> reads_time_major = {"Transpose", "Squeeze", "Unsqueeze", "Reshape", "Identity", "Dropout", "Flatten", "Shape",
                                                            "Gather", "Slice", "LSTM", "GRU", "RNN",
-                                                           "InstanceNormalization", "GroupNormalization", "DFT", "STFT"};  // (refused in their own words)
+                                                           "InstanceNormalization", "GroupNormalization", "DFT", "STFT", "Pad"};  // (refused in their own words)
     check_row_axis(n, reads_time_major.count(op) > 0);
     if (op == "DynamicQuantizeLinear")
       bad_form(n, "its scale spans all rows of a call, so a row's result would depend on its chunk; quantise statically (QuantizeLinear with constant scales)");

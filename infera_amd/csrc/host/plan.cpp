@@ -212,6 +212,17 @@ std::string Plan::describe_json() const {
       o << ",\"op\":\"" << (q.stft ? "STFT" : "DFT") << "\",\"L\":" << q.L << ",\"C\":" << q.C << ",\"n\":" << q.n << ",\"hop\":" << q.hop << ",\"frames\":" << q.frames << ",\"bins\":" << q.bins
         << ",\"onesided\":" << (q.onesided ? "true" : "false") << ",\"mode\":\"" << modes[q.mode] << "\",\"layout\":\"" << (q.bins_major ? "bins_major" : "frames_major") << "\",\"form\":\"" << q.form
         << "\",\"frames_per_group\":" << q.Fw << ",\"lds_bytes\":" << q.lds_bytes;
+      if (q.stft) {
+        static const char *pads[] = {"none", "constant", "reflect"};
+        o << ",\"pad_left\":" << q.pad_left << ",\"pad_right\":" << q.pad_right << ",\"pad_mode\":\"" << pads[q.pad_mode] << "\"";
+      }
+      if (!q.passes.empty()) {  // the mixed-radix schedule with its index reciprocals
+        o << ",\"passes\":[";
+        for (size_t k = 0; k < q.passes.size(); k++)
+          o << (k ? "," : "") << "{\"radix\":" << q.passes[k].radix << ",\"ns\":" << q.passes[k].ns << ",\"hr\":" << q.passes[k].hr << ",\"magic_ns\":" << q.passes[k].magic_ns
+            << ",\"magic_hr\":" << q.passes[k].magic_hr << "}";
+        o << "]";
+      }
     }
     if (s.kind == StepKind::Interact) {
       const InteractPack &q = *s.interact;

@@ -5254,13 +5254,73 @@ def stft_nodes(nodes: list, inits: list, x: str, n: int, hop: int, window=None, 
     return "spec"
 
 
+def centred_signal(nodes: list, inits: list, L: int, center: dict, signal_rank: int = 3) -> tuple[str, int]:
+    """What torch.stft(center=True) puts in front of STFT, on X [N, L].  center: pads = (left, right); mode = "reflect" | "constant" (| others,
+    refused); spelling = "NL" (Pad on [N, L]), "N1L" (Unsqueeze(1) -> Pad -> Squeeze(1)) or "1NL" (Reshape [1, -1, L] -> Pad -> Reshape
+    [-1, L'], the view torch makes of a 2-D input); for the refusals: value (the constant), rows (pads of the row axis), nonconst (pads are
+    computed), tap (the padded signal has a second reader: a Relu added back onto it), quant (the Pad reads a QuantizeLinear result); attr:
+    pads stand in the attribute (the spelling before opset 11).  Returns the signal as STFT reads it ([N, L'] or, signal_rank = 3, [N, L', 1])
+    and L'."""
+    pl, pr = center.get("pads", (0, 0))
+    spelling, Lp = center.get("spelling", "NL"), L + pl + pr
+    cur, rank = "X", 2
+    if spelling == "N1L":
+        inits.append(tensor("pad_ax1", np.array([1], np.int64)))
+        nodes.append(node("Unsqueeze", ["X", "pad_ax1"], ["x_n1l"], name="pad_unsqueeze"))
+        cur, rank = "x_n1l", 3
+    elif spelling == "1NL":
+        inits.append(tensor("pad_view", np.array([1, -1, L], np.int64)))
+        nodes.append(node("Reshape", ["X", "pad_view"], ["x_1nl"], name="pad_view"))
+        cur, rank = "x_1nl", 3
+    rows = center.get("rows", 0)
+    pads = [0] * (2 * rank)
+    pads[rank - 1], pads[2 * rank - 1] = pl, pr
+    pads[1 if spelling == "1NL" else 0] = rows
+    if center.get("quant"):
+        inits += [tensor("pad_qs", np.array(0.05, np.float32).reshape(())), tensor("pad_qz", np.array(0, np.int8).reshape(()))]
+        nodes.append(node("QuantizeLinear", [cur, "pad_qs", "pad_qz"], ["x_q"], name="pad_quant"))
+        cur = "x_q"
+    ins = [cur] if center.get("attr") else [cur, "pad_pads"]
+    if center.get("attr"):
+        pass
+    elif center.get("nonconst"):
+        nodes.append(node("Cast", ["X"], ["pad_pads"], [attr_i("to", INT64)], name="pad_computed"))
+    else:
+        inits.append(tensor("pad_pads", np.array(pads, np.int64)))
+    if "value" in center:
+        inits.append(tensor("pad_value", np.array(center["value"], np.float32).reshape(())))
+        ins.append("pad_value")
+    nodes.append(node("Pad", ins, ["x_padded"], [attr_s("mode", center.get("mode", "reflect"))] + ([attr_ints("pads", pads)] if center.get("attr") else []), name="pad"))
+    cur = "x_padded"
+    if center.get("tap"):
+        nodes += [node("Relu", [cur], ["pad_tap"], name="pad_tap"), node("Add", [cur, "pad_tap"], ["pad_sum"], name="pad_sum")]
+        cur = "pad_sum"
+    if spelling == "N1L":
+        nodes.append(node("Squeeze", [cur, "pad_ax1"], ["x_back"], name="pad_squeeze"))
+        cur = "x_back"
+    elif spelling == "1NL":
+        inits.append(tensor("pad_back", np.array([-1, Lp], np.int64)))
+        nodes.append(node("Reshape", [cur, "pad_back"], ["x_back"], name="pad_back"))
+        cur = "x_back"
+    if signal_rank == 3:
+        inits.append(tensor("pad_last", np.array([-1], np.int64)))
+        nodes.append(node("Unsqueeze", [cur, "pad_last"], ["x_sig"], name="pad_signal"))
+        cur = "x_sig"
+    return cur, Lp
+
+
 def stft_model(L: int = 256, n: int = 64, hop: int = 16, window=None, onesided: int = 1, frame_length: bool | int = False, reader: str | None = None,
-               keepdims: int = 0, transpose: str | None = None, last: int = 1, nonconst: str = "", elem: int = FLOAT, opset: int = 17) -> bytes:
+               keepdims: int = 0, transpose: str | None = None, last: int = 1, nonconst: str = "", elem: int = FLOAT, opset: int = 17,
+               center: dict | None = None, signal_rank: int = 3) -> bytes:
     """STFT of X [N, L, 1] and what torch writes behind it: transpose = "before" (Transpose(0,2,1,3) behind STFT) or "after" (Transpose behind
-    the magnitude)."""
+    the magnitude).  center: the Pad torch.stft(center=True) puts in front (centred_signal; X is then [N, L]); signal_rank = 2: STFT reads
+    a rank-2 [N, L] signal, as torch's exporter passes it."""
     nodes, inits = [], []
-    cur = stft_nodes(nodes, inits, "X", n, hop, window, onesided, frame_length or window is None, nonconst)
-    frames, bins = (L - n) // hop + 1, (n // 2 + 1 if onesided else n)
+    sig, Lp = "X", L
+    if center is not None:
+        sig, Lp = centred_signal(nodes, inits, L, center, signal_rank)
+    cur = stft_nodes(nodes, inits, sig, n, hop, window, onesided, frame_length or window is None, nonconst)
+    frames, bins = (Lp - n) // hop + 1, (n // 2 + 1 if onesided else n)
     dims = ["N", frames, bins, 2]
     if transpose == "before":
         nodes.append(node("Transpose", [cur], ["spec_t"], [attr_ints("perm", [0, 2, 1, 3])], name="spec_t"))
@@ -5269,20 +5329,24 @@ def stft_model(L: int = 256, n: int = 64, hop: int = 16, window=None, onesided: 
     if transpose == "after":
         nodes.append(node("Transpose", [cur], ["mag_t"], [attr_ints("perm", [0, 2, 1, 3][:len(dims)])], name="mag_t"))
         cur, dims = "mag_t", [dims[0], dims[2], dims[1]] + dims[3:]
-    return model("stft", nodes, inits, [value_info("X", ["N", L, last], elem)], [value_info(cur, dims, elem)], opset=opset)
+    xdims = ["N", L, last] if center is None and signal_rank == 3 else ["N", L]
+    return model("stft", nodes, inits, [value_info("X", xdims, elem)], [value_info(cur, dims, elem)], opset=opset)
 
 
 def spectrogram_model(L: int = 400, n: int = 64, hop: int = 16, mels: int = 12, eps: float = 1e-3, head: str = "lstm", hidden: int = 16, classes: int = 4,
-                      seed: int = 77) -> tuple[bytes, dict]:
+                      seed: int = 77, center: bool = False) -> tuple[bytes, dict]:
     """A log-spectrogram classifier on X [N, L, 1]: STFT (Hann window) -> power (Pow 2 -> ReduceSum) -> ... -> head.
     head = "lstm": -> MatMul(mel [bins, mels]) -> Add eps -> Log -> LSTM (layout = 1) -> Y_h -> Gemm: [N, classes].
     head = "cnn":  the bins-before-frames form (Transpose(0,2,1,3) behind STFT) -> Add eps -> Log -> Unsqueeze(1) -> Conv 3x3 + Relu ->
-    GlobalAveragePool -> Flatten -> Gemm.  Returns the model and the constants a reference needs."""
+    GlobalAveragePool -> Flatten -> Gemm.  center: X is [N, L] and reaches STFT as torch.stft(center=True, pad_mode="reflect") writes it (the
+    [1, N, L] view, a reflect Pad of n / 2 on both sides, the view back); n = 400, hop = 160, mels = 80 is the torchaudio-shaped log-mel.
+    Returns the model and the constants a reference needs."""
     ws = _WeightStream(seed)
-    frames, bins = (L - n) // hop + 1, n // 2 + 1
+    frames, bins = (L + (2 * (n // 2) if center else 0) - n) // hop + 1, n // 2 + 1
     window = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)).astype(np.float32)
     nodes, inits = [], []
-    cur = stft_nodes(nodes, inits, "X", n, hop, window, 1, True)
+    sig = centred_signal(nodes, inits, L, dict(pads=(n // 2, n // 2), spelling="1NL"), 2)[0] if center else "X"
+    cur = stft_nodes(nodes, inits, sig, n, hop, window, 1, True)
     w = dict(window=window, n=n, hop=hop, eps=np.float32(eps), head=head, frames=frames, bins=bins)
     if head == "cnn":
         nodes.append(node("Transpose", [cur], ["spec_t"], [attr_ints("perm", [0, 2, 1, 3])], name="spec_t"))
@@ -5306,4 +5370,4 @@ def spectrogram_model(L: int = 400, n: int = 64, hop: int = 16, mels: int = 12, 
                   node("Conv", ["image", "conv_W", "conv_b"], ["conv"], [attr_ints("kernel_shape", [3, 3]), attr_ints("pads", [1, 1, 1, 1])], name="conv"),
                   node("Relu", ["conv"], ["conv_r"], name="conv_relu"), node("GlobalAveragePool", ["conv_r"], ["gap"], name="gap"),
                   node("Flatten", ["gap"], ["feat"], [attr_i("axis", 1)], name="flatten"), node("Gemm", ["feat", "head_W", "head_b"], ["scores"], name="head")]
-    return model("spectrogram", nodes, inits, [value_info("X", ["N", L, 1])], [value_info("scores", ["N", classes])], opset=17), w
+    return model("spectrogram", nodes, inits, [value_info("X", ["N", L] if center else ["N", L, 1])], [value_info("scores", ["N", classes])], opset=17), w
