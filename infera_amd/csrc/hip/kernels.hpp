@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 
+#include "../host/conv3d.hpp"
+
 namespace infera_hip {
 struct SpectrumPack;  // host/spectrum.hpp
 }
@@ -212,6 +214,20 @@ size_t qconv_packed_floats(int C, int taps, int M);
 void qconv_pack(int C, int taps, int M, const int8_t *W, float *packed);  // W: [K, M] signed bytes, k = (c, tap)
 bool qconv_stages_in_lds(QConvLaunch p);  // does the launch stage its quantised input window in LDS (else: per tap from global memory)
 void qconv(hipStream_t s, QConvLaunch p);
+
+// ---- 3-D convolutions and pooling (conv3d.hip) ---------------------------------------------------
+// One Conv3d step (host/plan.hpp) over `rows` volumes: X f32 [rows, C, D, H, W], Y [rows, M, OD, OH, OW], both in plain NCDHW order.
+// conv3d_mfma (groups == 1): Wp = conv3d_pack() of the ONNX weights [M, C, kd, kh, kw], bias = conv3d_split(g).Mp entries (zero beyond M);
+// staged: the input window goes through LDS (only where conv3d_split(g).fits), else every tap is read from global memory -- the same bits.
+// false: the form is outside the kernel and nothing was launched.  conv3d_generic: W = the ONNX weights [M, C/g, kd, kh, kw] as they are,
+// bias [M] or null.
+size_t conv3d_packed_floats(const Conv3dGeom &g);
+void conv3d_pack(const Conv3dGeom &g, const float *W, float *packed);
+bool conv3d_mfma(hipStream_t s, const float *X, const float *Wp, const float *bias, float *Y, int64_t rows, const Conv3dGeom &g, bool staged, ActParam act);
+void conv3d_generic(hipStream_t s, const float *X, const float *W, const float *bias, float *Y, int64_t rows, const Conv3dGeom &g, ActParam act);
+// MaxPool / AveragePool over [rows, C, D, H, W] (g.M is not read): taps outside the volume are ignored; the average divides by the taps
+// inside it, or (count_pad) by kd * kh * kw
+void pool3d(hipStream_t s, const float *X, float *Y, int64_t rows, const Conv3dGeom &g, bool is_max, bool count_pad);
 
 // ---- float16 dense layer, f16 MFMA (hdense.hip) -----------------------------------------------
 // One HDense step (host/plan.hpp) over `rows` rows.  X: f32 [rows, K] (rounded to half on load), or (in_half) halves; Y: f32 [rows, M]

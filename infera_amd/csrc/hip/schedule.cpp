@@ -200,6 +200,12 @@ void Scheduler::decide_layout(bool commit) {
   // buffers that keep the caller's NCHW order: the input, and elementwise preprocessing of it (in-graph normalisation)
   m.nchw_buf.assign(m.plan.buf_shape.size(), 0);
   m.nchw_buf[0] = 1;
+  // A plan with a 3-D convolution or pooling step stays in plain element order throughout: conv3d.hip reads and writes NCDHW, and a rank-5
+  // buffer is no [N,C,H,W] tensor to any test below.  Nothing is logged: there is no faster layout it is kept out of.
+  if (std::any_of(st.begin(), st.end(), [](const Step &s) { return s.kind == StepKind::Conv3d || s.kind == StepKind::Pool3d; })) {
+    m.cq_mode = false;
+    return;
+  }
   auto elementwise = [](const Step &s) {
     return s.kind == StepKind::Unary || s.kind == StepKind::BinaryConst || s.kind == StepKind::AffineChannel || s.kind == StepKind::FakeQuant ||
            s.kind == StepKind::RoundHalf;
@@ -526,6 +532,7 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
         const StepKind sk = st[size_t(e.idx)].kind;
         // (a tree walk reads its row tile once per tree slice, and wide rows feature by feature; an SVM once per SV slice)
         const bool windowed = (sk == StepKind::Conv2d && m.exec[size_t(e.idx)] != ExecKind::ConvPatch) || sk == StepKind::QConv2d || sk == StepKind::Pool2d || sk == StepKind::LRN ||
+                              sk == StepKind::Conv3d || sk == StepKind::Pool3d ||
                               sk == StepKind::TreeEnsemble || sk == StepKind::SvmKernel ||
                               sk == StepKind::Nearest ||  // (once per slice of the reference set)
                               sk == StepKind::TopK ||     // (one lane per row: row-strided loads)

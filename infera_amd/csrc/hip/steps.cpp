@@ -507,6 +507,28 @@ void launch_pixelshuffle(const PassRunner &r, const Step &x) {
     throw InferaError::onnx("PixelShuffle kernel launch failed: '" + x.origin + "' was scheduled as " + pixelshuffle_kernel_name(x.out_mode) + " for other layouts than it meets");
 }
 
+// ---- 3-D convolutions (host/conv3d.hpp, conv3d.hip): the MFMA form takes the weights in the order its lanes load them and a bias padded to whole
+// channel tiles; the generic form takes both as the lowering left them.  Pool3d has no tables ----
+void upload_conv3d(const Step &s, PlainTables &t, const Upload &up) {
+  if (s.out_mode == kConv3dGeneric) {
+    t.W = up(s.W);
+    t.bias = up(s.bias);
+    return;
+  }
+  const Conv3dGeom g = conv3d_geom(s);
+  std::vector<float> packed(kern::conv3d_packed_floats(g));
+  kern::conv3d_pack(g, s.W.data(), packed.data());
+  t.W = up(packed);
+  t.bias = up(zero_padded(s.bias, size_t(conv3d_split(g).Mp)));
+}
+void launch_conv3d(const PassRunner &r, const Step &x, const PlainTables &t) {
+  if (r.in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: a Conv3d step reads its input row-major");
+  const Conv3dGeom g = conv3d_geom(x);
+  if (x.out_mode == kConv3dGeneric) kern::conv3d_generic(r.stream, r.buf(x.in0), t.W, t.bias, r.buf(x.out), r.nr, g, act_of(x));
+  else if (!kern::conv3d_mfma(r.stream, r.buf(x.in0), t.W, t.bias, r.buf(x.out), r.nr, g, x.out_mode == kConv3dMfmaStaged, act_of(x)))
+    throw InferaError::onnx("Conv3d kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+
 // ---- the plain family: the step's constants as the lowering left them (Conv2d: packed for the generic kernel); its launches are the head
 // of PassRunner::launch_plain, right below ----
 void upload_plain(const Step &s, PlainTables &t, const Upload &up) {
@@ -575,6 +597,11 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::Rotary: launch_rotary(*this, x, d.rotary); break;
     case StepKind::PixelShuffle: launch_pixelshuffle(*this, x); break;
     case StepKind::Spectrum: launch_spectrum(*this, x, d.spectrum); break;
+    case StepKind::Conv3d: launch_conv3d(*this, x, t); break;
+    case StepKind::Pool3d:
+      if (in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: a Pool3d step reads its input row-major");
+      kern::pool3d(stream, buf(x.in0), buf(x.out), nr, conv3d_geom(x), x.is_max, x.count_pad);
+      break;
     // the steps without tables
     case StepKind::Unary: kern::unary(stream, buf(x.in0), buf(x.out), nr * p.buf_per_row[size_t(x.out)], act_of(x)); break;
     case StepKind::BinaryAct:
@@ -652,6 +679,7 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::Rotary: return upload_rotary(s, d.rotary, up);
     case StepKind::PixelShuffle: return;  // (a copy by index arithmetic: no tables)
     case StepKind::Spectrum: return upload_spectrum(s, d.spectrum, up);
+    case StepKind::Conv3d: return upload_conv3d(s, d.plain, up);
     default: return;  // (no tables)
   }
 }

@@ -649,6 +649,11 @@ struct Lowerer {
   // the step over the [N,C,H,W] activation `a`, bound to out_node's first output; refusals name `at`
   void pixel_shuffle_step(const NodeDef &at, const NodeDef &out_node, const Val &a, int64_t b, bool to_space, bool channel_major, const std::string &origin);
 
+  // ---- lower_conv3d.cpp: Conv, MaxPool and AveragePool on [N,C,D,H,W] activations (INTEGRATION.md 2.6 "3-D convolutions") ----
+  void spatial3d(const NodeDef &n, Step &s);
+  void conv3d(const NodeDef &n);
+  void pool3d(const NodeDef &n, bool is_max);
+
   // ---- lower_spectrum.cpp: DFT and STFT on real signals (INTEGRATION.md 2.6 "Spectral front ends") ----
   // the nodes behind the transform `n` that its step stands for -- [Transpose] -> magnitude -> [Transpose], sole readers each: sets p's mode
   // and layout, marks them absorbed (they emit nothing) and returns the last (n: none); *keep: the magnitude kept its trailing axis

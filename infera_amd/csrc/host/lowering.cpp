@@ -1069,8 +1069,8 @@ namespace lowering {
     if (a.is_const) unsupported(n, "activation of a constant");
     std::vector<int64_t> shape = a.shape;
     if (Step *p = fusable_producer(n, idx)) {
-      const bool mfma_step = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d;
-      const bool takes_act = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d || p->kind == StepKind::AffineChannel ||
+      const bool mfma_step = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d || p->kind == StepKind::Conv3d;
+      const bool takes_act = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d || p->kind == StepKind::Conv3d || p->kind == StepKind::AffineChannel ||
                              p->kind == StepKind::BinaryConst || p->kind == StepKind::BinaryAct;
       const bool qdense_act = quantised_layer(*p) && !p->qy.on && (act == Act::Relu || act == Act::Clip);  // on `real`, before the requantisation
       const bool hdense_act = p->kind == StepKind::HDense && cur_half && int(act) >= 1 && int(act) <= kMaxMfmaFusedAct;  // r = half(act(float(r)))
@@ -1361,6 +1361,7 @@ namespace lowering {
   void Lowerer::conv(const NodeDef &n) {
     const Val &a = get(n, 0);
     const Val &w = get(n, 1);
+    if (!a.is_const && a.shape.size() == 5) return conv3d(n);  // [N,C,D,H,W]: lower_conv3d.cpp
     const bool one_d = a.shape.size() == 3 && w.shape.size() == 3;  // Conv1d: [N,C,L] as [N,C,1,L], kernel [M,C/g,k] as [M,C/g,1,k]
     if (a.is_const || (a.shape.size() != 4 && !one_d)) unsupported(n, "only [N,C,L] / [N,C,H,W] activations");
     if (!w.is_const || (w.shape.size() != 4 && !one_d)) unsupported(n, "weights must be a constant [M,C/g,kh,kw] (or [M,C/g,k])");
@@ -1593,6 +1594,17 @@ namespace lowering {
         set_act(n, a.buf, shape, true);
         return;
       }
+      if (p->kind == StepKind::Conv3d && p->act == Act::None && p->Mo == C) {  // fold into the 3-D convolution (f64, one rounding)
+        for (int64_t mo = 0; mo < C; mo++) {
+          const double dsc = double(sc[size_t(mo)]) / std::sqrt(double(var[size_t(mo)]) + double(eps));
+          for (int64_t k = 0; k < p->K; k++) p->W[size_t(mo * p->K + k)] = float(dsc * double(p->W[size_t(mo * p->K + k)]));
+          if (p->bias.empty()) p->bias.assign(size_t(C), 0.f);
+          p->bias[size_t(mo)] = float(dsc * (double(p->bias[size_t(mo)]) - double(mu[size_t(mo)])) + double(bi[size_t(mo)]));
+        }
+        p->origin += "+BatchNormalization";
+        set_act(n, a.buf, shape, true);
+        return;
+      }
       if (p->kind == StepKind::Conv2d && p->act == Act::None) {  // fold into conv
         const int64_t per_m = p->K;
         for (int64_t mo = 0; mo < p->Mo; mo++)
@@ -1761,6 +1773,7 @@ namespace lowering {
 
   void Lowerer::pool(const NodeDef &n, bool is_max) {
     const Val &a = get(n, 0);
+    if (!a.is_const && a.shape.size() == 5) return pool3d(n, is_max);  // [N,C,D,H,W]: lower_conv3d.cpp
     const bool one_d = a.shape.size() == 3;
     if (a.is_const || (a.shape.size() != 4 && !one_d)) unsupported(n, "only [N,C,L] / [N,C,H,W] activations");
     auto *ks = n.attr_ints("kernel_shape");

@@ -28,6 +28,7 @@ double Plan::flops_per_row() const {
     if (s.kind == StepKind::Dense || s.kind == StepKind::QDense || s.kind == StepKind::HDense) f += 2.0 * double(s.rep) * double(s.K) * double(s.M);
     else if (s.kind == StepKind::Attention) f += 4.0 * double(s.attn_T) * double(s.attn_Tk > 0 ? s.attn_Tk : s.attn_T) * double(s.attn_heads * s.attn_dh);  // (an upper bound under attn_causal, as for padded rows)
     else if (s.kind == StepKind::Conv2d || s.kind == StepKind::QConv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
+    else if (s.kind == StepKind::Conv3d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OD) * double(s.OH) * double(s.OW);
     else if (s.kind == StepKind::ConvTranspose2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.H) * double(s.Wd);  // (C/g) kh kw taps per input pixel and output channel
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
     else if (s.kind == StepKind::Nearest) f += 2.0 * double(s.nearest->F) * double(s.nearest->M);
@@ -41,7 +42,7 @@ double Plan::flops_per_row() const {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary", "PixelShuffle", "NearestVote", "Spectrum"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary", "PixelShuffle", "NearestVote", "Spectrum", "Conv3d", "Pool3d"};
   static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
                                "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
   std::ostringstream o;
@@ -133,6 +134,20 @@ std::string Plan::describe_json() const {
       o << ",\"row_mask\":{\"src_col\":" << s.rm_off << ",\"cmp\":" << json_f32(s.rm_cmp) << ",\"fill\":" << json_f32(s.rm_fill) << ",\"mode\":\""
         << (s.rm_mode == kRowMaskAdd ? "add" : "replace") << "\",\"excluding\":" << (s.rm_excl ? "true" : "false") << "}";
     if (s.kind == StepKind::Conv2d) o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"k\":[" << s.kh << "," << s.kw << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
+    if (s.kind == StepKind::Conv3d || s.kind == StepKind::Pool3d) {
+      o << ",\"C\":" << s.C << ",\"in_dhw\":[" << s.D << "," << s.H << "," << s.Wd << "],\"out_dhw\":[" << s.OD << "," << s.OH << "," << s.OW << "],\"k\":[" << s.kd << "," << s.kh << ","
+        << s.kw << "],\"strides\":[" << s.sd << "," << s.sh << "," << s.sw << "],\"pads\":[" << s.pf << "," << s.pt << "," << s.pl << "," << s.pk << "," << s.pb << "," << s.pr
+        << "],\"dilations\":[" << s.dd << "," << s.dh << "," << s.dw << "]";
+      if (s.kind == StepKind::Pool3d) {
+        o << ",\"mode\":\"" << (s.is_max ? "max" : s.count_pad ? "average_include_pad" : "average") << "\"";
+      } else {
+        o << ",\"groups\":" << s.groups << ",\"K\":" << s.K << ",\"M\":" << s.Mo << ",\"bias\":" << (s.bias.empty() ? "false" : "true") << ",\"exec\":\""
+          << (s.out_mode == kConv3dGeneric ? "conv3d_generic" : "conv3d_mfma") << "\"";
+        if (s.out_mode != kConv3dGeneric)  // the MFMA form: where its input window is staged, and the LDS that takes
+          o << ",\"input_window\":\"" << (s.out_mode == kConv3dMfmaStaged ? "lds" : "global") << "\",\"lds_bytes\":"
+            << (s.out_mode == kConv3dMfmaStaged ? conv3d_split(conv3d_geom(s)).lds_bytes : 0);
+      }
+    }
     if (s.kind == StepKind::ConvTranspose2d) {
       const DeconvPack &q = *s.deconv;
       o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"group\":" << s.groups << ",\"k\":[" << s.kh << "," << s.kw << "],\"strides\":[" << s.sh << "," << s.sw << "],\"pads\":[" << s.pt

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "conv3d.hpp"
 #include "onnx_model.hpp"
 
 namespace infera_hip {
@@ -85,6 +86,8 @@ enum class StepKind : int {
   Rotary = 43,        // rotary position embedding of in0 [rows, attn_T, ld] read through the view (attn_ld[0], attn_off[0]) into a dense [rows, attn_T, attn_heads * attn_dh]: column j < rot_rd of a head, y[j] = fl(fl(x[j] * scale[t, j]) + fl(x[partner(j)] * shift[t, j])), partner(j) = j +- rot_rd / 2 or j ^ 1 (rot_interleaved); the other columns are bit copies (RotaryEmbedding and the rotate_half spelling; rotary.hip)
   PixelShuffle = 44,  // DepthToSpace / SpaceToDepth of in0 [rows, C, H, Wd] to [rows, Mo, OH, OW] with block ps_block: a bit copy of every element, in one of four forms (ps_to_space, ps_channel_major: host/pixelshuffle.hpp); out_mode (set by the scheduler): the PixelShuffleKernel that runs it (pixelshuffle.hip)
   Spectrum = 46,      // the real DFT / STFT of in0 [rows, C, L]: frames of n samples `hop` apart times a window, out [rows, C, frames, bins (, 2)] or, bins_major, [rows, C, bins, frames (, 2)] as complex pairs, power or magnitude (SpectrumPack, host/spectrum.hpp, spectrum.hip)
+  Conv3d = 47,        // NCDHW convolution of in0 [rows, C, D, H, Wd] to [rows, Mo, OD, OH, OW] (the Conv2d geometry fields + the depth axis: D, OD, kd, sd, dd, pf / pk = the front / back pads); W = the ONNX weights [M, C/g, kd, kh, kw], BatchNormalization folded when adjacent; out_mode = the kernel (Conv3dExec, host/conv3d.hpp; conv3d.hip)
+  Pool3d = 48,        // MaxPool / AveragePool over [rows, C, D, H, Wd] (the same geometry fields; is_max, count_pad)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
@@ -150,6 +153,8 @@ struct Step {
   int64_t C = 0, H = 0, Wd = 0, Mo = 0, OH = 0, OW = 0;
   int64_t kh = 1, kw = 1, sh = 1, sw = 1, pt = 0, pl = 0, pb = 0, pr = 0, dh = 1, dw = 1, groups = 1;
   bool is_max = false, count_pad = false;
+  // Conv3d / Pool3d: the depth axis beside them (pf / pk: the pads in front of and behind the volume)
+  int64_t D = 1, OD = 1, kd = 1, sd = 1, dd = 1, pf = 0, pk = 0;
   // LRN: window `lrn_size` channels, y = x / (lrn_bias + lrn_alpha / lrn_size * sum x^2)^lrn_beta
   int64_t lrn_size = 0;
   float lrn_alpha = 1e-4f, lrn_beta = 0.75f, lrn_bias = 1.f;
@@ -165,7 +170,7 @@ struct Step {
   std::shared_ptr<const InteractPack> interact;
   std::shared_ptr<const SpectrumPack> spectrum;
   std::shared_ptr<const DeconvPack> deconv;  // ConvTranspose2d: phase tap lists; Resize2d: source tables
-  int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut, RowReduce: ReduceOp, TopK: 0 values / 1 indices, Nearest / NearestReduce: NearestOut, NearestVote: VoteOut
+  int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut, RowReduce: ReduceOp, TopK: 0 values / 1 indices, Nearest / NearestReduce: NearestOut, NearestVote: VoteOut, Conv3d: Conv3dExec
   // Attention: Q = in0, K = in1, V = in2 (the same buffer three times when the projections are merged), each [rows, T, ld] with the head
   // block of head g at columns off + g * dh of a step; mask (cst): [T, T] added to the scaled scores, -inf = no weight, empty = none
   int in2 = -1;
@@ -209,6 +214,12 @@ struct Step {
   int h_bias_mode = kHalfBiasNone;
   std::string origin;  // ONNX node names/ops this step came from (diagnostics)
 };
+
+// the geometry of a Conv3d / Pool3d step as the kernels take it (the lowering keeps every field inside int)
+inline Conv3dGeom conv3d_geom(const Step &s) {
+  return Conv3dGeom{int(s.C), int(s.D), int(s.H), int(s.Wd), int(s.Mo), int(s.OD), int(s.OH), int(s.OW), int(s.kd), int(s.kh), int(s.kw), int(s.sd), int(s.sh), int(s.sw),
+                    int(s.pf), int(s.pt), int(s.pl), int(s.dd), int(s.dh), int(s.dw), int(s.groups)};
+}
 
 struct Plan {
   std::vector<int64_t> input_shape, output_shape;  // -1 = symbolic (engine.rs:64-73)

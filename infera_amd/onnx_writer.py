@@ -5371,3 +5371,89 @@ def spectrogram_model(L: int = 400, n: int = 64, hop: int = 16, mels: int = 12, 
                   node("Relu", ["conv"], ["conv_r"], name="conv_relu"), node("GlobalAveragePool", ["conv_r"], ["gap"], name="gap"),
                   node("Flatten", ["gap"], ["feat"], [attr_i("axis", 1)], name="flatten"), node("Gemm", ["feat", "head_W", "head_b"], ["scores"], name="head")]
     return model("spectrogram", nodes, inits, [value_info("X", ["N", L] if center else ["N", L, 1])], [value_info("scores", ["N", classes])], opset=17), w
+
+
+# ------------------------------------------------------------------------------------------
+# 3-D convolutional nets on [N, C, D, H, W] (INTEGRATION.md 2.6 "3-D convolutions")
+# ------------------------------------------------------------------------------------------
+
+def _attrs3d(a: dict) -> list[bytes]:
+    """strides / pads / dilations / kernel_shape as integer lists, auto_pad as a string, everything else (group, ceil_mode ...) as an integer"""
+    return [attr_s(k, v) if isinstance(v, str) else attr_i(k, v) if isinstance(v, int) else attr_ints(k, v) for k, v in a.items()]
+
+
+def conv3d_layer(w: np.ndarray, b: np.ndarray | None, in_dhw: Sequence[int], act: str = "", elem: int = FLOAT, **attrs) -> bytes:
+    """One Conv of X [N, C, D, H, W] with the kernel w [M, C/g, kd, kh, kw] (+ bias, + `act`); attrs: strides, pads, dilations, group, auto_pad"""
+    g = attrs.get("group", 1)
+    nodes = [node("Conv", ["X", "w"] + (["b"] if b is not None else []), ["c" if act else "Y"], _attrs3d(attrs), name="conv")]
+    if act:
+        nodes.append(node(act, ["c"], ["Y"], name="act"))
+    inits = [tensor("w", w)] + ([tensor("b", b)] if b is not None else [])
+    return model("conv3d", nodes, inits, [value_info("X", ["N", w.shape[1] * g, *in_dhw], elem)], [value_info("Y", ["N", w.shape[0], "d", "h", "w"], elem)], opset=17)
+
+
+def pool3d_layer(op: str, c: int, in_dhw: Sequence[int], **attrs) -> bytes:
+    """One MaxPool / AveragePool of X [N, c, D, H, W]; attrs: kernel_shape, strides, pads, ceil_mode, count_include_pad"""
+    return model("pool3d", [node(op, ["X"], ["Y"], _attrs3d(attrs), name="pool")], [], [value_info("X", ["N", c, *in_dhw])],
+                 [value_info("Y", ["N", c, "d", "h", "w"])], opset=17)
+
+
+def r2plus1d_pair(cin: int = 4, mid: int = 5, cout: int = 8, in_dhw: Sequence[int] = (4, 6, 6), seed: int = 31, ints: bool = False) -> tuple[bytes, dict]:
+    """The R(2+1)D factorisation of a 3x3x3 layer: Conv (1,3,3) -> Relu -> Conv (3,1,1); returns the graph and its weights.  ints: small whole
+    numbers (every sum exact in f32)"""
+    ws, rng = _WeightStream(seed), np.random.default_rng(seed)
+    take = (lambda shape, fan: rng.integers(-3, 4, size=shape).astype(np.float32)) if ints else ws.take
+    w = dict(w1=take((mid, cin, 1, 3, 3), cin * 9), b1=take((mid,), cin * 9), w2=take((cout, mid, 3, 1, 1), mid * 3), b2=take((cout,), mid * 3))
+    nodes = [node("Conv", ["X", "w1", "b1"], ["s"], [attr_ints("kernel_shape", [1, 3, 3]), attr_ints("pads", [0, 1, 1, 0, 1, 1])], name="spatial"),
+             node("Relu", ["s"], ["sr"], name="relu"),
+             node("Conv", ["sr", "w2", "b2"], ["Y"], [attr_ints("kernel_shape", [3, 1, 1]), attr_ints("pads", [1, 0, 0, 1, 0, 0])], name="temporal")]
+    return model("r2plus1d_pair", nodes, [tensor(k, v) for k, v in w.items()], [value_info("X", ["N", cin, *in_dhw])],
+                 [value_info("Y", ["N", cout, *in_dhw])], opset=17), w
+
+
+def r3d_net(widths: Sequence[int] = (4, 8), blocks: int = 1, in_dhw: Sequence[int] = (4, 10, 10), classes: int = 3, stem_k: Sequence[int] = (3, 3, 3),
+            stem_stride: Sequence[int] = (1, 2, 2), pool: bool = True, cin: int = 3, seed: int = 11) -> tuple[bytes, list]:
+    """The R3D topology: stem Conv + BN + Relu [-> MaxPool 3/2], then per width `blocks` basic blocks (Conv3 + BN + Relu, Conv3 + BN, a 1x1x1
+    Conv + BN projection shortcut where the stride or the width changes, Add, Relu), GlobalAveragePool, Flatten, Gemm.  BatchNormalization
+    stays a node of its own.  widths = (64, 128, 256, 512), blocks = 2, stem_k = (3, 7, 7), pool = False is torchvision's r3d_18.  Returns
+    the graph and its operations in order, as tuples a float64 reference can walk: ("conv", w, bn, stride, pad, relu, src) with bn = (scale,
+    B, mean, var), ("pool",), ("add", a, b), ("head", w, b); src / a / b index earlier results (0 = the input)."""
+    ws = _WeightStream(seed)
+    nodes, inits, ops = [], [], []
+
+    def conv_bn(x: int, ci: int, co: int, k, stride, relu: bool) -> int:
+        i = len(ops) + 1
+        w = ws.take((co, ci, *k), ci * int(np.prod(k)))
+        bn = [(1.0 + 0.1 * ws.take((co,), 1)).astype(np.float32), 0.1 * ws.take((co,), 1), 0.1 * ws.take((co,), 1), (1.0 + 0.5 * np.abs(ws.take((co,), 1))).astype(np.float32)]
+        pad = [e // 2 for e in k]
+        inits.extend([tensor(f"w{i}", w)] + [tensor(f"bn{i}_{j}", a) for j, a in enumerate(bn)])
+        nodes.append(node("Conv", [f"v{x}", f"w{i}"], [f"c{i}"], [attr_ints("kernel_shape", k), attr_ints("strides", stride), attr_ints("pads", pad * 2)], name=f"conv{i}"))
+        nodes.append(node("BatchNormalization", [f"c{i}"] + [f"bn{i}_{j}" for j in range(4)], [f"v{i}" if not relu else f"n{i}"], [attr_f("epsilon", 1e-5)], name=f"bn{i}"))
+        if relu:
+            nodes.append(node("Relu", [f"n{i}"], [f"v{i}"], name=f"relu{i}"))
+        ops.append(("conv", w, bn, list(stride), pad, relu, x))
+        return i
+
+    nodes.append(node("Identity", ["X"], ["v0"]))
+    x = conv_bn(0, cin, widths[0], list(stem_k), list(stem_stride), True)
+    if pool:
+        nodes.append(node("MaxPool", [f"v{x}"], [f"v{x + 1}"], [attr_ints("kernel_shape", [3, 3, 3]), attr_ints("strides", [2, 2, 2]), attr_ints("pads", [1] * 6)], name="pool"))
+        ops.append(("pool",))
+        x += 1
+    ci = widths[0]
+    for stage, co in enumerate(widths):
+        for blk in range(blocks):
+            stride = [2, 2, 2] if stage > 0 and blk == 0 else [1, 1, 1]
+            y = conv_bn(x, ci, co, [3, 3, 3], stride, True)
+            y = conv_bn(y, co, co, [3, 3, 3], [1, 1, 1], False)
+            sc = conv_bn(x, ci, co, [1, 1, 1], stride, False) if stride[0] != 1 or ci != co else x
+            i = len(ops) + 1
+            nodes += [node("Add", [f"v{y}", f"v{sc}"], [f"s{i}"], name=f"add{i}"), node("Relu", [f"s{i}"], [f"v{i}"], name=f"relu{i}")]
+            ops.append(("add", y, sc))
+            x, ci = i, co
+    hw, hb = ws.take((ci, classes), ci), ws.take((classes,), ci)
+    inits += [tensor("fc_w", hw), tensor("fc_b", hb)]
+    nodes += [node("GlobalAveragePool", [f"v{x}"], ["gap"], name="gap"), node("Flatten", ["gap"], ["feat"], [attr_i("axis", 1)], name="flatten"),
+              node("Gemm", ["feat", "fc_w", "fc_b"], ["Y"], name="head")]
+    ops.append(("head", hw, hb))
+    return model("r3d", nodes, inits, [value_info("X", ["N", cin, *in_dhw])], [value_info("Y", ["N", classes])], opset=17), ops
