@@ -103,6 +103,30 @@ struct DeviceStep {  // (a step fills the one struct of its family)
 // How the executor runs a step.
 enum class ExecKind : int { Normal = 0, Skipped = 1, Mlp3Head = 2, DenseSoftmax = 3, ConvTiled = 4, ConvPatch = 5, ConvDepthwise = 6, DenseTiled = 7, DenseArgMax = 8, ChainHead = 9, ConvTPhase = 10 };
 
+// What schedule() decided for one plan step (device independent).  Every step has a record from the start of scheduling on: a field no pass
+// has written yet reads as "nothing decided".
+struct StepSchedule {
+  ExecKind kind = ExecKind::Normal;
+  int fused_pool = -1;  // ConvPatch: the MaxPool 3x3/2 step the stem computes in its own kernel, or -1
+  // ConvTiled: the residual Add (+ activation) step carried in its epilogue -- the launch takes that step's activation and output -- or -1 ...
+  int fused_add = -1;
+  int residual_buf = -1;  // ... and the buffer of the Add's other operand, the skip tensor (-1 under a folded shortcut: the sum forms in the accumulator)
+  int fold = -1;  // ConvTiled: the 1x1 projection-shortcut step computed inside it as extra K stages (conv_split.hip SecondInput), or -1
+  // ConvTiled: on conv2d_split6; ConvPatch + fused MaxPool: on conv2d_stem_split6, the same arithmetic (default; INFERA_PRECISION=fp32 leaves
+  // both on the exact-fp32 kernels)
+  bool bf16x6 = false;
+  // QDense: the input / output buffer holds quantised bytes, HDense: halves, instead of the f32 values they stand for (schedule.cpp narrow_edges)
+  bool in_narrow = false, out_narrow = false;
+  int form = 0;  // ChannelNorm: 0 the register form, 1 the re-read form (host/channelnorm.hpp); PixelShuffle: its PixelShuffleKernel (host/pixelshuffle.hpp)
+
+  bool tiled_bf16x6() const { return kind == ExecKind::ConvTiled && bf16x6; }
+  // This step's convolution is folded into `to`: the Add it carried, with its activation and output, now belongs to `to`, which has no residual to read
+  void hand_fused_add_to(StepSchedule &to) {
+    to.fused_add = fused_add, to.residual_buf = -1;
+    fused_add = residual_buf = -1;
+  }
+};
+
 struct DeviceModel {
   int device = -1;  // HIP ordinal
   int num_cus = 0;
@@ -119,7 +143,7 @@ class LoadedModel {
   std::string name;
   Plan plan;
   // execution schedule (device independent)
-  std::vector<ExecKind> exec;
+  std::vector<StepSchedule> sched;  // one record per plan step
   kern::Mlp3Shape mlp3_shape{};
   // Runs of small Dense layers (optionally behind a PadCols, optionally ending in Softmax / ArgMax) executed by one
   // load-time specialised kernel: steps [first, first + nsteps) of the plan; `pad` = 1 when the first one is a PadCols.
@@ -147,18 +171,8 @@ class LoadedModel {
   // ... except the caller's input and what elementwise preprocessing makes of it (x/255, (x - mean) / std in the graph):
   // those few-channel tensors stay NCHW and the first convolution reads them with the patch kernel.
   std::vector<char> nchw_buf;
-  // A ConvTiled step that absorbed the residual Add (+ activation) following it: per conv step, the
-  // index of the fused BinaryAct step (-1: none) and which of its operands is the skip tensor.
-  std::vector<int> conv_fused_pool;  // per step: the MaxPool 3x3/2 step a ConvPatch stem computes in its own kernel, or -1
-  std::vector<int> conv_fused_add;
-  std::vector<int> conv_residual_buf;
-  std::vector<int> conv_fold;  // per ConvTiled step: the 1x1 projection-shortcut step computed inside it as extra K stages (conv_split.hip SecondInput), or -1
-  std::vector<char> conv_split6;  // ConvTiled steps on conv2d_split6 (default; INFERA_PRECISION=fp32 leaves them on the exact-fp32 kernels)
-  std::vector<char> stem_split6;  // ConvPatch + fused MaxPool steps that run conv2d_stem_split6 (same arithmetic)
-  // QDense steps whose input / output buffer holds quantised bytes instead of the f32 values they stand for (schedule.cpp narrow_edges)
-  std::vector<char> q_in_bytes, q_out_bytes;
-  // HDense steps whose input / output buffer holds halves instead of f32 values (schedule.cpp narrow_edges)
-  std::vector<char> h_in_half, h_out_half;
+  bool cq(int buf) const { return cq_mode && !nchw_buf[size_t(buf)]; }  // a channel-quad tensor (not the caller's NCHW one)
+  const char *layout_name(int buf) const { return cq(buf) ? "NC/4HW4" : "NCHW"; }
   std::vector<int> slot_of_buf;        // scratch slot per activation buffer (-1: external in/out)
   std::vector<int64_t> slot_per_row;   // floats per row of each scratch slot
   int64_t scratch_per_row = 0;         // sum over slots

@@ -323,7 +323,9 @@ struct EffStep {
   int writes;
 };
 std::vector<EffStep> effective_steps(const LoadedModel &m);
-// fills m.exec and every fusion / layout / scratch decision from m.plan (may permute weights of m.plan for the chosen layout)
+// fills m.sched and every layout / scratch decision from m.plan.  It writes m.plan in two places only: a general-plan SpatialNorm layer becomes
+// SpatialStats -> SpatialNorm (expand_spatial_norms, before anything indexes steps), and under the channel-quad layout the weight rows of a
+// Dense layer behind a flattened [C,H,W] tensor and the per-element constants of BinaryConst steps are permuted to that order (decide_layout)
 void schedule(LoadedModel &m);
 
 // ---- model.cpp --------------------------------------------------------------------------------------------------------------
@@ -372,7 +374,7 @@ struct PassRunner {
     if (b == p.out_buf) return d_out + r0 * p.out_per_row();
     return ctx.scratch + slot_base[size_t(m.slot_of_buf[size_t(b)])];
   }
-  bool cq(int b) const { return m.cq_mode && !m.nchw_buf[size_t(b)]; }  // a channel-quad tensor (not the caller's NCHW one)
+  bool cq(int b) const { return m.cq(b); }
   // scratch slots sized for slot_rows rows, from scratch_off floats into the scratch
   void run(hipStream_t s, int64_t first_row, int64_t rows, int64_t slot_rows, int64_t scratch_off);
   // steps.cpp

@@ -19,19 +19,18 @@ std::vector<EffStep> effective_steps(const LoadedModel &m) {
   std::vector<EffStep> out;
   const auto &st = m.plan.steps;
   for (size_t i = 0; i < st.size(); i++) {
-    switch (m.exec[i]) {
+    const StepSchedule &d = m.sched[i];
+    switch (d.kind) {
       case ExecKind::Skipped: break;
       case ExecKind::Mlp3Head: out.push_back({int(i), {st[i].in0}, st[i + 2].out}); break;
       case ExecKind::DenseSoftmax: out.push_back({int(i), {st[i].in0}, st[i + 1].out}); break;
       case ExecKind::ChainHead: out.push_back({int(i), {st[i].in0}, st[i + size_t(m.chain_at(i)->nsteps) - 1].out}); break;
-      case ExecKind::ConvPatch:
-        out.push_back({int(i), {st[i].in0}, i < m.conv_fused_pool.size() && m.conv_fused_pool[i] >= 0 ? st[size_t(m.conv_fused_pool[i])].out : st[i].out});
-        break;
+      case ExecKind::ConvPatch: out.push_back({int(i), {st[i].in0}, d.fused_pool >= 0 ? st[size_t(d.fused_pool)].out : st[i].out}); break;
       case ExecKind::ConvTiled:
-        if (i < m.conv_fold.size() && m.conv_fold[i] >= 0)  // the block's projection shortcut rides in this convolution: it reads that layer's input too
-          out.push_back({int(i), {st[i].in0, st[size_t(m.conv_fold[i])].in0}, st[size_t(m.conv_fused_add[i])].out});
-        else if (i < m.conv_fused_add.size() && m.conv_fused_add[i] >= 0)
-          out.push_back({int(i), {st[i].in0, m.conv_residual_buf[i]}, st[size_t(m.conv_fused_add[i])].out});
+        if (d.fold >= 0)  // the block's projection shortcut rides in this convolution: it reads that layer's input too
+          out.push_back({int(i), {st[i].in0, st[size_t(d.fold)].in0}, st[size_t(d.fused_add)].out});
+        else if (d.fused_add >= 0)
+          out.push_back({int(i), {st[i].in0, d.residual_buf}, st[size_t(d.fused_add)].out});
         else
           out.push_back({int(i), {st[i].in0}, st[i].out});
         break;
@@ -52,11 +51,12 @@ struct Scheduler {
   LoadedModel &m;
   const std::vector<Step> &st;
   const size_t n;
+  std::vector<StepSchedule> &sc;  // m.sched: the record of every step, readable by every pass
   std::vector<int> uses;  // readers per buffer (the served output counts as read)
   const Config &cfg = Config::get();
 
-  explicit Scheduler(LoadedModel &model) : m(model), st(model.plan.steps), n(model.plan.steps.size()), uses(model.plan.buf_per_row.size(), 0) {
-    m.exec.assign(n, ExecKind::Normal);
+  explicit Scheduler(LoadedModel &model) : m(model), st(model.plan.steps), n(model.plan.steps.size()), sc(model.sched), uses(model.plan.buf_per_row.size(), 0) {
+    sc.assign(n, StepSchedule{});
     for (const auto &s : st) {
       if (s.in0 >= 0) uses[size_t(s.in0)]++;
       if (s.in1 >= 0) uses[size_t(s.in1)]++;
@@ -67,6 +67,13 @@ struct Scheduler {
   }
   bool is4d(int b) const { return b >= 0 && m.plan.buf_shape[size_t(b)].size() == 4; }
   int64_t spatial(int b) const { return is4d(b) ? m.plan.buf_shape[size_t(b)][2] * m.plan.buf_shape[size_t(b)][3] : int64_t(1); }
+  // per buffer: the last step that writes it among those not Skipped so far, or -1
+  std::vector<int> last_writer() const {
+    std::vector<int> prod(m.plan.buf_per_row.size(), -1);
+    for (size_t i = 0; i < n; i++)
+      if (sc[i].kind != ExecKind::Skipped) prod[size_t(st[i].out)] = int(i);
+    return prod;
+  }
 
   void fuse_tabular();               // Dense x3 -> fused MLP, runs of small layers -> chain kernel, Dense + Softmax / ArgMax epilogues, tiled Dense
   // channel-quad planes for convolutional plans (+ the weight / constant permutations that follow from it; commit = false: the decision alone)
@@ -77,8 +84,7 @@ struct Scheduler {
   void choose_conv_arithmetic();     // bf16 x three exact parts (default) or exact fp32
   void fold_projection_shortcuts();  // a block's 1x1 shortcut as extra K stages of its second convolution
   // QDense -> QDense edges that carry the quantised bytes, HDense -> HDense edges that carry halves
-  void narrow_edges(StepKind kind, bool enabled, bool needs_qy, bool (*same_format)(const Step &p, const Step &c), std::vector<char> &in_narrow,
-                    std::vector<char> &out_narrow);
+  void narrow_edges(StepKind kind, bool enabled, bool needs_qy, bool (*same_format)(const Step &p, const Step &c));
   void classify_io(const std::vector<EffStep> &eff);   // may the result be stored into pinned memory, the input be read from it / column-major?
   void place_scratch(const std::vector<EffStep> &eff); // scratch slots by liveness
 };
@@ -86,7 +92,7 @@ struct Scheduler {
 void Scheduler::fuse_tabular() {
   bool have_mlp3 = false;
   for (size_t i = 0; i < n; i++) {
-    if (m.exec[i] != ExecKind::Normal) continue;
+    if (sc[i].kind != ExecKind::Normal) continue;
     // Dense -> Dense -> Dense with private intermediates: whole-chain fused kernel
     if (cfg.fused_mlp && !have_mlp3 && i + 2 < n && st[i].kind == StepKind::Dense && st[i + 1].kind == StepKind::Dense &&
         st[i + 2].kind == StepKind::Dense && st[i + 1].in0 == st[i].out && st[i + 2].in0 == st[i + 1].out &&
@@ -97,8 +103,8 @@ void Scheduler::fuse_tabular() {
       // only parameter-free activations can be baked into the fused chain (LeakyRelu/Clip carry arguments)
       const bool acts_ok = sh.act1 <= 3 && sh.act2 <= 3 && sh.act3 <= 3;
       if (acts_ok && kern::mlp3_supported(sh, &why)) {
-        m.exec[i] = ExecKind::Mlp3Head;
-        m.exec[i + 1] = m.exec[i + 2] = ExecKind::Skipped;
+        sc[i].kind = ExecKind::Mlp3Head;
+        sc[i + 1].kind = sc[i + 2].kind = ExecKind::Skipped;
         m.mlp3_shape = sh;
         have_mlp3 = true;
         i += 2;
@@ -114,14 +120,14 @@ void Scheduler::fuse_tabular() {
       size_t j = i;
       int pad = 0;
       if (st[j].kind == StepKind::PadCols && j + 1 < n && st[j + 1].kind == StepKind::Dense && st[j + 1].in0 == st[j].out &&
-          uses[size_t(st[j].out)] == 1 && m.exec[j + 1] == ExecKind::Normal && st[j].rep == st[j + 1].rep) {
+          uses[size_t(st[j].out)] == 1 && sc[j + 1].kind == ExecKind::Normal && st[j].rep == st[j + 1].rep) {
         pad = 1;
         j++;
       }
       kern::ChainShape sh;
       sh.k0 = pad ? int(st[i].K) : int(st[j].K);
       const size_t d0 = j;
-      while (j < n && st[j].kind == StepKind::Dense && m.exec[j] == ExecKind::Normal && int(st[j].act) <= kMaxMfmaFusedAct &&
+      while (j < n && st[j].kind == StepKind::Dense && sc[j].kind == ExecKind::Normal && int(st[j].act) <= kMaxMfmaFusedAct &&
              st[j].K <= 128 && st[j].M <= 128 && (j == d0 || (st[j].in0 == st[j - 1].out && uses[size_t(st[j - 1].out)] == 1 && st[j].rep == st[d0].rep))) {
         sh.dims.push_back(int(st[j].M));
         sh.acts.push_back(int(st[j].act));
@@ -136,7 +142,7 @@ void Scheduler::fuse_tabular() {
       // ... and a single 17..128-wide layer whose Softmax / ArgMax would otherwise cost two more passes over its scores
       const bool lone_gap = layers == 1 && !pad && st[d0].M > 16 && ((st[d0].M <= 32 && st[d0].K % 8 != 0) || tail_next);  // (layers == 1: d0 is a Dense step)
       if (layers >= 2 || (layers == 1 && pad) || lone_gap) {
-        if (j < n && st[d0].rep == 1 && st[j].in0 == st[j - 1].out && uses[size_t(st[j - 1].out)] == 1 && m.exec[j] == ExecKind::Normal) {
+        if (j < n && st[d0].rep == 1 && st[j].in0 == st[j - 1].out && uses[size_t(st[j - 1].out)] == 1 && sc[j].kind == ExecKind::Normal) {
           if (st[j].kind == StepKind::Softmax && st[j].sm_norm == 0 && st[j].sm_outer == 1 && st[j].sm_inner == 1 && st[j].sm_len == st[j - 1].M) {
             sh.sm = st[j].log_softmax ? 2 : 1;
             j++;
@@ -153,8 +159,8 @@ void Scheduler::fuse_tabular() {
           run.pad = pad;
           run.shape = sh;
           m.chains.push_back(run);
-          m.exec[i] = ExecKind::ChainHead;
-          for (size_t k = i + 1; k < j; k++) m.exec[k] = ExecKind::Skipped;
+          sc[i].kind = ExecKind::ChainHead;
+          for (size_t k = i + 1; k < j; k++) sc[k].kind = ExecKind::Skipped;
           i = j - 1;
           continue;
         }
@@ -165,8 +171,8 @@ void Scheduler::fuse_tabular() {
     if (i + 1 < n && st[i].kind == StepKind::Dense && st[i + 1].kind == StepKind::Softmax && st[i + 1].in0 == st[i].out &&
         uses[size_t(st[i].out)] == 1 && st[i].rep == 1 && st[i + 1].sm_outer == 1 && st[i + 1].sm_inner == 1 && st[i + 1].sm_len == st[i].M &&
         kern::dense_can_fuse_softmax(int(st[i].K), int(st[i].M)) && st[i + 1].sm_norm == 0) {
-      m.exec[i] = ExecKind::DenseSoftmax;
-      m.exec[i + 1] = ExecKind::Skipped;
+      sc[i].kind = ExecKind::DenseSoftmax;
+      sc[i + 1].kind = ExecKind::Skipped;
       i += 1;
       continue;
     }
@@ -176,16 +182,16 @@ void Scheduler::fuse_tabular() {
     if (i + 1 < n && st[i].kind == StepKind::Dense && st[i + 1].kind == StepKind::ArgMax && st[i + 1].in0 == st[i].out &&
         uses[size_t(st[i].out)] == 1 && st[i].rep == 1 && st[i + 1].K == st[i].M && st[i].M <= 64 &&
         kern::dense_can_fuse_argmax(nullptr, int(st[i].K), int(st[i].M))) {
-      m.exec[i] = ExecKind::DenseArgMax;
+      sc[i].kind = ExecKind::DenseArgMax;
       i += 1;
     }
   }
   // Remaining Dense layers with K % 32 == 0 and M % 32 == 0 -> the tiled kernel (the generic dense kernel fetches
   // one weight per lane per MFMA from L2 and measured 13-16 TFLOP/s; narrow heads keep their streaming kernels)
   for (size_t i = 0; i < n; i++)
-    if (m.exec[i] == ExecKind::Normal && st[i].kind == StepKind::Dense && st[i].M > 32 && st[i].K % 4 == 0 &&
+    if (sc[i].kind == ExecKind::Normal && st[i].kind == StepKind::Dense && st[i].M > 32 && st[i].K % 4 == 0 &&
         mfma_fusable(st[i].act) && kern::conv2d_tiled_supported(dense_as_conv(st[i])))
-      m.exec[i] = ExecKind::DenseTiled;
+      sc[i].kind = ExecKind::DenseTiled;
 }
 
 void Scheduler::decide_layout(bool commit) {
@@ -336,15 +342,14 @@ void Scheduler::decide_layout(bool commit) {
 }
 
 void Scheduler::assign_conv_kernels() {
-  m.conv_fused_pool.assign(n, -1);
   if (m.cq_mode)
     for (size_t i = 0; i < n; i++) {
       const Step &s = st[i];
-      if (m.exec[i] != ExecKind::Normal || s.kind != StepKind::Conv2d) continue;
+      if (sc[i].kind != ExecKind::Normal || s.kind != StepKind::Conv2d) continue;
       kern::ConvGeom g = conv_geom(s);
       if (m.nchw_buf[size_t(s.in0)]) {  // the caller's NCHW blob (or its normalised copy): few channels -> LDS patch kernel
         if (!kern::conv2d_patch_supported(kern::conv2d_patch_geom(g))) continue;
-        m.exec[i] = ExecKind::ConvPatch;
+        sc[i].kind = ExecKind::ConvPatch;
         // stem -> MaxPool 3x3 / 2 (ResNet, DenseNet, SqueezeNet): pooled in the stem's kernel, the stem's own output is never stored
         // (INFERA_STEM_POOL=0, read at load time: the two kernels)
         if (ScheduleKnobs::read().stem_pool && uses[size_t(s.out)] == 1 && s.out != m.plan.out_buf)
@@ -352,17 +357,17 @@ void Scheduler::assign_conv_kernels() {
             const Step &q = st[j];
             if (q.in0 != s.out && q.in1 != s.out) continue;
             const kern::PoolTail tail{int(q.OH), int(q.OW), int(q.pt), int(q.pl)};
-            if (q.kind == StepKind::Pool2d && m.exec[j] == ExecKind::Normal && q.is_max && q.kh == 3 && q.kw == 3 && q.sh == 2 && q.sw == 2 &&
+            if (q.kind == StepKind::Pool2d && sc[j].kind == ExecKind::Normal && q.is_max && q.kh == 3 && q.kw == 3 && q.sh == 2 && q.sw == 2 &&
                 q.dh == 1 && q.dw == 1 && kern::conv2d_patch_pool_supported(kern::conv2d_patch_geom(g), tail)) {
-              m.conv_fused_pool[i] = int(j);
-              m.exec[j] = ExecKind::Skipped;
+              sc[i].fused_pool = int(j);
+              sc[j].kind = ExecKind::Skipped;
             }
             break;
           }
         continue;
       }
-      if (kern::conv2d_tiled_supported(g)) m.exec[i] = ExecKind::ConvTiled;
-      else if (kern::conv2d_depthwise_supported(g)) m.exec[i] = ExecKind::ConvDepthwise;
+      if (kern::conv2d_tiled_supported(g)) sc[i].kind = ExecKind::ConvTiled;
+      else if (kern::conv2d_depthwise_supported(g)) sc[i].kind = ExecKind::ConvDepthwise;
     }
 }
 
@@ -371,34 +376,30 @@ void Scheduler::assign_convt_kernels() {
   if (!m.cq_mode || !ScheduleKnobs::read().convt_mfma) return;
   for (size_t i = 0; i < n; i++) {
     const Step &s = st[i];
-    if (m.exec[i] != ExecKind::Normal || s.kind != StepKind::ConvTranspose2d || m.nchw_buf[size_t(s.in0)]) continue;
-    if (kern::convt2d_phase_supported(convt_geom(s), s.deconv->tab.data())) m.exec[i] = ExecKind::ConvTPhase;
+    if (sc[i].kind != ExecKind::Normal || s.kind != StepKind::ConvTranspose2d || m.nchw_buf[size_t(s.in0)]) continue;
+    if (kern::convt2d_phase_supported(convt_geom(s), s.deconv->tab.data())) sc[i].kind = ExecKind::ConvTPhase;
   }
 }
 
 void Scheduler::fuse_residual_adds() {
   // Residual Add (+ activation) of a ResNet block -> epilogue of whichever of its two producers runs LAST
   // (conv2, or the 1x1 downsample conv when the block has one), the other operand being the skip tensor.
-  m.conv_fused_add.assign(n, -1);
-  m.conv_residual_buf.assign(n, -1);
   if (m.cq_mode) {
-    std::vector<int> prod(m.plan.buf_per_row.size(), -1);
-    for (size_t i = 0; i < n; i++)
-      if (m.exec[i] != ExecKind::Skipped) prod[size_t(st[i].out)] = int(i);
+    const std::vector<int> prod = last_writer();
     for (size_t j = 0; j < n; j++) {
       const Step &a = st[j];
-      if (m.exec[j] != ExecKind::Normal || a.kind != StepKind::BinaryAct || a.bop != '+' || !is4d(a.out) || a.S > 1) continue;
+      if (sc[j].kind != ExecKind::Normal || a.kind != StepKind::BinaryAct || a.bop != '+' || !is4d(a.out) || a.S > 1) continue;
       if (!mfma_fusable(a.act)) continue;  // the conv epilogue resolves only the MFMA-fusable kinds
       const int pa = prod[size_t(a.in0)], pb = prod[size_t(a.in1)];
       const int late = std::max(pa, pb);
       if (late < 0 || a.in0 == a.in1) continue;
       const int fused_in = late == pa ? a.in0 : a.in1, skip = late == pa ? a.in1 : a.in0;
       const Step &c = st[size_t(late)];
-      if (m.exec[size_t(late)] != ExecKind::ConvTiled || c.act != Act::None || uses[size_t(fused_in)] != 1) continue;
-      if (m.conv_fused_add[size_t(late)] >= 0) continue;
-      m.conv_fused_add[size_t(late)] = int(j);
-      m.conv_residual_buf[size_t(late)] = skip;
-      m.exec[j] = ExecKind::Skipped;
+      if (sc[size_t(late)].kind != ExecKind::ConvTiled || c.act != Act::None || uses[size_t(fused_in)] != 1) continue;
+      if (sc[size_t(late)].fused_add >= 0) continue;
+      sc[size_t(late)].fused_add = int(j);
+      sc[size_t(late)].residual_buf = skip;
+      sc[j].kind = ExecKind::Skipped;
     }
   }
 
@@ -406,21 +407,19 @@ void Scheduler::fuse_residual_adds() {
 
 void Scheduler::choose_conv_arithmetic() {
   // the default arithmetic of the tiled convolutions and the 7x7 / stride-2 stem: bf16 x three exact parts (conv_split.hip)
-  m.conv_split6.assign(n, 0);
-  m.stem_split6.assign(n, 0);
   if (ScheduleKnobs::read().conv_bf16x6 && m.cq_mode) {
     for (size_t i = 0; i < n; i++) {
-      if (m.exec[i] != ExecKind::ConvTiled) continue;
+      if (sc[i].kind != ExecKind::ConvTiled) continue;
       const Step &c = st[i];
       const kern::ConvGeom g = conv_geom(c);
-      if (kern::conv2d_split6_supported(kern::conv2d_tiled_geom(g)) && !m.nchw_buf[size_t(c.in0)]) m.conv_split6[i] = 1;
+      if (kern::conv2d_split6_supported(kern::conv2d_tiled_geom(g)) && !m.nchw_buf[size_t(c.in0)]) sc[i].bf16x6 = true;
     }
     for (size_t i = 0; i < n; i++) {  // the 7x7 / stride-2 stem + max-pool in the same arithmetic
-      if (m.exec[i] != ExecKind::ConvPatch || m.conv_fused_pool[i] < 0) continue;
-      const Step &c = st[i], &q = st[size_t(m.conv_fused_pool[i])];
+      if (sc[i].kind != ExecKind::ConvPatch || sc[i].fused_pool < 0) continue;
+      const Step &c = st[i], &q = st[size_t(sc[i].fused_pool)];
       const kern::ConvGeom g = conv_geom(c);
       const kern::ConvGeom gp = kern::conv2d_patch_geom(g);
-      if (gp.mvalid == 0 && kern::conv2d_stem_split6_supported(gp, pool_tail(q))) m.stem_split6[i] = 1;
+      if (gp.mvalid == 0 && kern::conv2d_stem_split6_supported(gp, pool_tail(q))) sc[i].bf16x6 = true;
     }
   }
 }
@@ -432,11 +431,8 @@ void Scheduler::fold_projection_shortcuts() {
   // tensor passes less per block.  Conditions: both layers on the split form, the 1x1 layer unpadded and undilated, the other one a
   // 128-feature launch with no activation and no residual of its own, its output read by the Add alone.  INFERA_CONV_FOLD_SHORTCUT=0 (read when
   // a model is scheduled): two launches (tests, A/B).
-  m.conv_fold.assign(n, -1);
   if (m.cq_mode && ScheduleKnobs::read().conv_fold_shortcut) {
-    std::vector<int> prod(m.plan.buf_per_row.size(), -1);
-    for (size_t i = 0; i < n; i++)
-      if (m.exec[i] != ExecKind::Skipped) prod[size_t(st[i].out)] = int(i);
+    const std::vector<int> prod = last_writer();
     // which EXECUTED step writes each buffer once the fusions so far are applied: the output of a fused epilogue (conv + Add, stem + pool, a
     // fused head) belongs to the kernel that carries it, not to its Skipped Add / Pool step -- `prod` above knows nothing of those buffers
     // (the ordering check below was vacuous for them).  Rebuilt after every fold: a folded block's output moves to its second conv.
@@ -447,12 +443,11 @@ void Scheduler::fold_projection_shortcuts() {
     };
     rebuild_writers();
     for (size_t late = 0; late < n; late++) {
-      const int j = m.conv_fused_add[late];
-      if (j < 0 || !m.conv_split6[late]) continue;
+      if (sc[late].fused_add < 0 || !sc[late].tiled_bf16x6()) continue;
       const Step &d = st[late];
       if (d.kh != 1 || d.kw != 1 || d.pt != 0 || d.pl != 0 || d.groups != 1 || d.C % 32 != 0 || d.act != Act::None) continue;
-      const int skip = m.conv_residual_buf[late], early = skip >= 0 ? prod[size_t(skip)] : -1;
-      if (early < 0 || size_t(early) >= late || !m.conv_split6[size_t(early)] || m.conv_fused_add[size_t(early)] >= 0) continue;
+      const int skip = sc[late].residual_buf, early = skip >= 0 ? prod[size_t(skip)] : -1;
+      if (early < 0 || size_t(early) >= late || !sc[size_t(early)].tiled_bf16x6() || sc[size_t(early)].fused_add >= 0) continue;
       const Step &c = st[size_t(early)];
       const kern::ConvGeom gc = conv_geom(c);
       if (!kern::conv2d_split6_takes_second_input(kern::conv2d_tiled_geom(gc)) || c.act != Act::None || uses[size_t(c.out)] != 1) continue;
@@ -462,12 +457,9 @@ void Scheduler::fold_projection_shortcuts() {
       // tensor, buffer 0, is excluded above as NCHW).  y = Conv3x3(A); P = Relu(Conv(B) + C); out = Relu(y + Conv1x1(P)) is a valid ONNX order
       // in which P is produced BETWEEN the two convolutions: no fold.
       if (m.nchw_buf[size_t(d.in0)] || writer[size_t(d.in0)] < 0 || writer[size_t(d.in0)] >= early) continue;
-      m.conv_fold[size_t(early)] = int(late);
-      m.conv_fused_add[size_t(early)] = j;   // the Add's activation and output now belong to the second convolution ...
-      m.conv_residual_buf[size_t(early)] = -1;  // ... which has no residual to read
-      m.conv_fused_add[late] = -1;
-      m.conv_residual_buf[late] = -1;
-      m.exec[late] = ExecKind::Skipped;
+      sc[size_t(early)].fold = int(late);
+      sc[late].hand_fused_add_to(sc[size_t(early)]);
+      sc[late].kind = ExecKind::Skipped;
       rebuild_writers();
     }
   }
@@ -480,10 +472,7 @@ void Scheduler::fold_projection_shortcuts() {
 // the results are bit-identical (tests/test_quantized_gpu.py) and the edge moves a quarter of the bytes; INFERA_QDENSE_BYTES=0: f32 on every
 // edge.  HDense: the halves themselves, which the readers load instead of rounding f32 values -- the f32 buffer would hold exactly these
 // halves (tests/test_half_gpu.py); INFERA_HDENSE_HALF=0.  (`enabled`: the knob, read when a model is scheduled.)
-void Scheduler::narrow_edges(StepKind kind, bool enabled, bool needs_qy, bool (*same_format)(const Step &p, const Step &c), std::vector<char> &in_narrow,
-                             std::vector<char> &out_narrow) {
-  in_narrow.assign(n, 0);
-  out_narrow.assign(n, 0);
+void Scheduler::narrow_edges(StepKind kind, bool enabled, bool needs_qy, bool (*same_format)(const Step &p, const Step &c)) {
   if (!enabled) return;
   for (size_t i = 0; i < n; i++) {
     const Step &p = st[i];
@@ -497,9 +486,9 @@ void Scheduler::narrow_edges(StepKind kind, bool enabled, bool needs_qy, bool (*
       ok = ok && j > i && c.kind == kind && c.in0 == p.out && same_format(p, c) && c.K == p.M && c.rep == p.rep;
     }
     if (!ok || readers == 0) continue;
-    out_narrow[i] = 1;
+    sc[i].out_narrow = true;
     for (size_t j = i + 1; j < n; j++)
-      if (st[j].in0 == p.out) in_narrow[j] = 1;
+      if (st[j].in0 == p.out) sc[j].in_narrow = true;
   }
 }
 
@@ -513,7 +502,7 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
         // every tabular head qualifies: fused chains, Dense with or without a fused Softmax / ArgMax epilogue, a row Softmax or
         // ArgMax kernel -- each stores every result element exactly once (convolutional plans keep the D2H copy: their
         // outputs leave in strided channel-quad order)
-        const ExecKind k = m.exec[size_t(e.idx)];
+        const ExecKind k = sc[size_t(e.idx)].kind;
         const StepKind sk = st[size_t(e.idx)].kind;
         streaming = k == ExecKind::Mlp3Head || k == ExecKind::ChainHead || k == ExecKind::DenseSoftmax || k == ExecKind::DenseArgMax ||
                     k == ExecKind::DenseTiled || (k == ExecKind::Normal && (sk == StepKind::Dense || sk == StepKind::Softmax || sk == StepKind::ArgMax));
@@ -531,7 +520,7 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
         // ... and that kernel streams it about once (a windowed kernel would fetch a small image over PCIe once per tap)
         const StepKind sk = st[size_t(e.idx)].kind;
         // (a tree walk reads its row tile once per tree slice, and wide rows feature by feature; an SVM once per SV slice)
-        const bool windowed = (sk == StepKind::Conv2d && m.exec[size_t(e.idx)] != ExecKind::ConvPatch) || sk == StepKind::QConv2d || sk == StepKind::Pool2d || sk == StepKind::LRN ||
+        const bool windowed = (sk == StepKind::Conv2d && sc[size_t(e.idx)].kind != ExecKind::ConvPatch) || sk == StepKind::QConv2d || sk == StepKind::Pool2d || sk == StepKind::LRN ||
                               sk == StepKind::Conv3d || sk == StepKind::Pool3d ||
                               sk == StepKind::TreeEnsemble || sk == StepKind::SvmKernel ||
                               sk == StepKind::Nearest ||  // (once per slice of the reference set)
@@ -549,18 +538,18 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
         break;
       }
     m.in_colmajor_max_rows = INT64_MAX;
-    m.in_colmajor_ok = !eff.empty() && in_readers == 1 && m.exec[size_t(eff[0].idx)] == ExecKind::Mlp3Head && eff[0].reads[0] == 0 &&
+    m.in_colmajor_ok = !eff.empty() && in_readers == 1 && sc[size_t(eff[0].idx)].kind == ExecKind::Mlp3Head && eff[0].reads[0] == 0 &&
                        kern::mlp3_colmajor_supported(m.mlp3_shape);
     if (m.in_colmajor_ok) m.in_colmajor_max_rows = kern::mlp3_colmajor_max_rows(m.mlp3_shape);
     // the fused small-MLP chain reads a column-major chunk too (a run-time flag of the same kernel); INFERA_CHAIN_XCM=0: transpose first
     const ScheduleKnobs knobs = ScheduleKnobs::read();
-    if (knobs.chain_xcm && !eff.empty() && in_readers == 1 && m.exec[size_t(eff[0].idx)] == ExecKind::ChainHead && eff[0].reads[0] == 0)
+    if (knobs.chain_xcm && !eff.empty() && in_readers == 1 && sc[size_t(eff[0].idx)].kind == ExecKind::ChainHead && eff[0].reads[0] == 0)
       m.in_colmajor_ok = true;
     // ... and so do the two as-it-lies streaming kernels of single narrow layers (linear / logistic regression, with or without the
     // softmax / label epilogue); INFERA_DENSE_XCM=0: transpose first
     if (knobs.dense_xcm && !eff.empty() && in_readers == 1 && eff[0].reads[0] == 0) {
       const size_t i0 = size_t(eff[0].idx);
-      const ExecKind k0 = m.exec[i0];
+      const ExecKind k0 = sc[i0].kind;
       if (st[i0].kind == StepKind::Dense && (k0 == ExecKind::Normal || k0 == ExecKind::DenseSoftmax || k0 == ExecKind::DenseArgMax) &&
           kern::dense_colmajor_supported(int(st[i0].K), int(st[i0].M)))
         m.in_colmajor_ok = true;
@@ -660,16 +649,16 @@ void schedule(LoadedModel &m) {
   s.choose_conv_arithmetic();
   s.fold_projection_shortcuts();
   const ScheduleKnobs knobs = ScheduleKnobs::read();
-  // ChannelNorm layers: the register form where C fits it, else (or with INFERA_CHANNELNORM_REGS=0: everywhere) the re-read form
-  for (Step &c : m.plan.steps)
-    if (c.kind == StepKind::ChannelNorm) c.out_mode = channelnorm_regs_form(c.C, knobs.channelnorm_regs) ? 0 : 1;
-  // PixelShuffle layers: the form of the kernel that fits the layouts of the two tensors (INFERA_PIXELSHUFFLE_FAST=0: the generic form everywhere)
-  for (Step &c : m.plan.steps)
+  for (size_t i = 0; i < m.sched.size(); i++) {
+    const Step &c = m.plan.steps[i];
+    // ChannelNorm layers: the register form where C fits it, else (or with INFERA_CHANNELNORM_REGS=0: everywhere) the re-read form
+    if (c.kind == StepKind::ChannelNorm) m.sched[i].form = channelnorm_regs_form(c.C, knobs.channelnorm_regs) ? 0 : 1;
+    // PixelShuffle layers: the form of the kernel that fits the layouts of the two tensors (INFERA_PIXELSHUFFLE_FAST=0: the generic form everywhere)
     if (c.kind == StepKind::PixelShuffle)
-      c.out_mode = pixelshuffle_kernel(c.ps_block, c.ps_to_space, c.ps_channel_major, c.C, m.cq_mode && !m.nchw_buf[size_t(c.in0)], m.cq_mode && !m.nchw_buf[size_t(c.out)],
-                                       knobs.pixelshuffle_fast);
-  s.narrow_edges(StepKind::QDense, knobs.qdense_bytes, true, [](const Step &p, const Step &c) { return c.qx == p.qy; }, m.q_in_bytes, m.q_out_bytes);
-  s.narrow_edges(StepKind::HDense, knobs.hdense_half, false, [](const Step &, const Step &) { return true; }, m.h_in_half, m.h_out_half);
+      m.sched[i].form = pixelshuffle_kernel(c.ps_block, c.ps_to_space, c.ps_channel_major, c.C, m.cq(c.in0), m.cq(c.out), knobs.pixelshuffle_fast);
+  }
+  s.narrow_edges(StepKind::QDense, knobs.qdense_bytes, true, [](const Step &p, const Step &c) { return c.qx == p.qy; });
+  s.narrow_edges(StepKind::HDense, knobs.hdense_half, false, [](const Step &, const Step &) { return true; });
   const auto eff = effective_steps(m);
   s.classify_io(eff);
   s.place_scratch(eff);
@@ -678,129 +667,103 @@ void schedule(LoadedModel &m) {
 }  // namespace rt
 using namespace rt;
 
+// the "exec" entry of a step (no default: a new ExecKind without a name is a compiler warning)
+static const char *exec_name(const StepSchedule &s) {
+  switch (s.kind) {
+    case ExecKind::Normal: return "normal";
+    case ExecKind::Skipped: return "skipped";
+    case ExecKind::Mlp3Head: return "mlp3_fused";
+    case ExecKind::DenseSoftmax: return "dense_softmax";
+    case ExecKind::ConvTiled: return s.bf16x6 ? "conv_split_bf16x6" : "conv_tiled_cq";
+    case ExecKind::ConvPatch: return s.fused_pool < 0 ? "conv_patch" : s.bf16x6 ? "conv_patch_pool_bf16x6" : "conv_patch_pool";
+    case ExecKind::ConvDepthwise: return "conv_depthwise";
+    case ExecKind::DenseTiled: return "dense_tiled";
+    case ExecKind::DenseArgMax: return "dense_argmax";
+    case ExecKind::ChainHead: return "chain_fused";
+    case ExecKind::ConvTPhase: return "convt_phase";
+  }
+  return "";
+}
+
 std::string LoadedModel::describe_json() const {
-  static const char *ek[] = {"normal", "skipped", "mlp3_fused", "dense_softmax", "conv_tiled_cq", "conv_patch", "conv_depthwise", "dense_tiled", "dense_argmax", "chain_fused", "convt_phase"};
+  const size_t n = sched.size();
   std::ostringstream o;
   o << "{\"name\":" << json_str(name) << ",\"plan\":" << plan.describe_json() << ",\"exec\":[";
-  for (size_t i = 0; i < exec.size(); i++)
-    o << (i ? "," : "") << "\"" << (exec[i] == ExecKind::Skipped ? "skipped" : i < stem_split6.size() && stem_split6[i] ? "conv_patch_pool_bf16x6" : i < conv_fused_pool.size() && conv_fused_pool[i] >= 0 ? "conv_patch_pool" : i < conv_split6.size() && conv_split6[i] ? "conv_split_bf16x6" : ek[int(exec[i])]) << "\"";
+  for (size_t i = 0; i < n; i++) o << (i ? "," : "") << "\"" << exec_name(sched[i]) << "\"";
   o << "],\"activation_layout\":\"" << (cq_mode ? "NC/4HW4" : "NCHW") << "\",\"scratch_floats_per_row\":" << scratch_per_row << ",\"devices\":[";
   for (size_t i = 0; i < dev.size(); i++) o << (i ? "," : "") << dev[i]->device;
   o << "]";
-  if (std::find(conv_split6.begin(), conv_split6.end(), char(1)) != conv_split6.end())
+  // ,"key":[...]: what `entry(i, step)` gives for every step of one of `kinds`, comma separated; nothing for a plan without such steps
+  auto per_step = [&](const char *key, std::initializer_list<StepKind> kinds, auto entry) {
+    std::string all;
+    for (size_t i = 0; i < n; i++)
+      if (std::find(kinds.begin(), kinds.end(), plan.steps[i].kind) != kinds.end()) all += (all.empty() ? "" : ",") + entry(i, plan.steps[i]);
+    if (!all.empty()) o << ",\"" << key << "\":[" << all << "]";
+  };
+  auto step_obj = [](size_t i, const std::string &fields) { return "{\"step\":" + std::to_string(i) + fields + "}"; };
+  auto layouts = [](const char *in, const char *out) { return std::string(",\"in_layout\":\"") + in + "\",\"out_layout\":\"" + out + "\""; };
+  if (std::any_of(sched.begin(), sched.end(), [](const StepSchedule &s) { return s.tiled_bf16x6(); }))  // (a split stem alone does not say so)
     o << ",\"conv_precision\":\"bf16x6 (bf16 matrix cores, operands cut exactly into three parts, six partial products, fp32 accumulate)\"";
   {
     std::string folded;
-    for (size_t i = 0; i < conv_fold.size(); i++)
-      if (conv_fold[i] >= 0) folded += std::string(folded.empty() ? "" : ",") + std::to_string(conv_fold[i]);
+    for (const StepSchedule &s : sched)
+      if (s.fold >= 0) folded += std::string(folded.empty() ? "" : ",") + std::to_string(s.fold);
     if (!folded.empty()) o << ",\"folded_shortcuts\":[" << folded << "]";
   }
-  for (size_t i = 0; i < exec.size(); i++)
-    if (exec[i] == ExecKind::Mlp3Head)
-      o << ",\"fused_kernel\":" << json_str(kern::mlp3_kernel_name(mlp3_shape)) << ",\"precision\":\"fp32\"";
+  for (const StepSchedule &s : sched)
+    if (s.kind == ExecKind::Mlp3Head) o << ",\"fused_kernel\":" << json_str(kern::mlp3_kernel_name(mlp3_shape)) << ",\"precision\":\"fp32\"";
   {  // kernel family of every Dense layer that runs on the streaming / generic Dense kernels, for a large aligned device-resident scan
     std::string dk;
-    for (size_t i = 0; i < exec.size(); i++) {
+    for (size_t i = 0; i < n; i++) {
       const Step &x = plan.steps[i];
       if (x.kind != StepKind::Dense) continue;
       int sm = -1;
-      if (exec[i] == ExecKind::DenseSoftmax) sm = plan.steps[i + 1].log_softmax ? 2 : 1;
-      else if (exec[i] == ExecKind::DenseArgMax) sm = 3;
-      else if (exec[i] == ExecKind::Normal) sm = 0;
+      if (sched[i].kind == ExecKind::DenseSoftmax) sm = plan.steps[i + 1].log_softmax ? 2 : 1;
+      else if (sched[i].kind == ExecKind::DenseArgMax) sm = 3;
+      else if (sched[i].kind == ExecKind::Normal) sm = 0;
       if (sm < 0) continue;
       dk += std::string(dk.empty() ? "" : ",") + json_str(kern::dense_kernel_family(int64_t(1) << 20, int(x.K), int(x.M), sm, false, true));
     }
     if (!dk.empty()) o << ",\"dense_kernels\":[" << dk << "]";
   }
-  {  // per QDense step: does its input / output edge carry bytes
-    std::string q;
-    for (size_t i = 0; i < exec.size(); i++)
-      if (plan.steps[i].kind == StepKind::QDense)
-        q += std::string(q.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"in_bytes\":" + (q_in_bytes[i] ? "true" : "false") + ",\"out_bytes\":" +
-             (q_out_bytes[i] ? "true" : "false") + "}";
-    if (!q.empty()) o << ",\"qdense\":[" << q << "]";
-  }
-  {  // per QConv2d step: the layouts it reads and writes, and whether it stages its quantised input window in LDS
-    std::string q;
-    for (size_t i = 0; i < exec.size(); i++) {
-      const Step &x = plan.steps[i];
-      if (x.kind != StepKind::QConv2d) continue;
-      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)], out_cq = cq_mode && !nchw_buf[size_t(x.out)];
-      q += std::string(q.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"C\":" + std::to_string(x.C) + ",\"M\":" + std::to_string(x.Mo) + ",\"k\":[" +
-           std::to_string(x.kh) + "," + std::to_string(x.kw) + "],\"out_hw\":[" + std::to_string(x.OH) + "," + std::to_string(x.OW) + "],\"in_layout\":\"" +
-           (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\",\"input_window\":\"" +
-           (kern::qconv_stages_in_lds(qconv_launch(x)) ? "lds" : "global") + "\"}";
-    }
-    if (!q.empty()) o << ",\"qconv\":[" << q << "]";
-  }
-  {  // per HDense step: what its input / output edge carries
-    std::string h;
-    for (size_t i = 0; i < exec.size(); i++)
-      if (plan.steps[i].kind == StepKind::HDense)
-        h += std::string(h.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"in\":\"" + (h_in_half[i] ? "half" : "f32") + "\",\"out\":\"" +
-             (h_out_half[i] ? "half" : "f32") + "\"}";
-    if (!h.empty()) o << ",\"hdense\":[" << h << "]";
-  }
-  {  // per ConvTranspose2d step: the kernel that runs it and the layouts it reads and writes
-    std::string c;
-    for (size_t i = 0; i < exec.size(); i++) {
-      const Step &x = plan.steps[i];
-      if (x.kind != StepKind::ConvTranspose2d) continue;
-      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)], out_cq = cq_mode && !nchw_buf[size_t(x.out)];
-      c += std::string(c.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"kernel\":\"" + (exec[i] == ExecKind::ConvTPhase ? "convt2d_phase" : "convt2d_generic") +
-           "\",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\"}";
-    }
-    if (!c.empty()) o << ",\"convt\":[" << c << "]";
-  }
-  {  // per SpatialNorm / SpatialStats step: the kernel that runs it, its groups, the layouts it reads and writes and the fused activation
-    static const char *acts[] = {"", "Relu", "Sigmoid", "Tanh", "LeakyRelu", "Clip", "Exp", "Log", "Sqrt", "Neg", "Abs", "Elu", "Selu", "Softplus",
-                                 "HardSigmoid", "HardSwish", "Erf", "Gelu", "Reciprocal", "Floor", "Ceil", "Softsign", "Trunc", "Round", "Swish"};
-    std::string c;
-    for (size_t i = 0; i < exec.size(); i++) {
-      const Step &x = plan.steps[i];
-      if (x.kind != StepKind::SpatialNorm && x.kind != StepKind::SpatialStats) continue;
-      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)];
-      const bool out_cq = x.kind == StepKind::SpatialStats ? in_cq : cq_mode && !nchw_buf[size_t(x.out)];
-      c += std::string(c.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"kernel\":\"" +
-           (x.kind == StepKind::SpatialStats ? "spatialnorm_stats" : x.in1 < 0 ? "spatialnorm_fused" : "spatialnorm_apply") + "\",\"groups\":" + std::to_string(x.groups) +
-           ",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\",\"act\":\"" + acts[int(x.act)] + "\"}";
-    }
-    if (!c.empty()) o << ",\"spatialnorm\":[" << c << "]";
-  }
-  {  // per ChannelNorm step: the form of the kernel that runs it and the layout it reads and writes
-    std::string c;
-    for (size_t i = 0; i < exec.size(); i++) {
-      const Step &x = plan.steps[i];
-      if (x.kind != StepKind::ChannelNorm) continue;
-      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)], out_cq = cq_mode && !nchw_buf[size_t(x.out)];
-      c += std::string(c.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"kernel\":\"" + (x.out_mode == 0 ? "channelnorm_regs" : "channelnorm_reread") +
-           "\",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") + "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\"}";
-    }
-    if (!c.empty()) o << ",\"channelnorm\":[" << c << "]";
-  }
-  {  // per PixelShuffle step: its form and block, the kernel that runs it and the layouts it reads and writes
-    std::string c;
-    for (size_t i = 0; i < exec.size(); i++) {
-      const Step &x = plan.steps[i];
-      if (x.kind != StepKind::PixelShuffle) continue;
-      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)], out_cq = cq_mode && !nchw_buf[size_t(x.out)];
-      c += std::string(c.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"kernel\":\"" + pixelshuffle_kernel_name(x.out_mode) + "\",\"form\":\"" +
-           pixelshuffle_form_name(x.ps_to_space, x.ps_channel_major) + "\",\"block\":" + std::to_string(x.ps_block) + ",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") +
-           "\",\"out_layout\":\"" + (out_cq ? "NC/4HW4" : "NCHW") + "\"}";
-    }
-    if (!c.empty()) o << ",\"pixelshuffle\":[" << c << "]";
-  }
-  {  // per Tokens step: the kernel that runs it and the layout it reads (its result is a flat window)
-    std::string c;
-    for (size_t i = 0; i < exec.size(); i++) {
-      const Step &x = plan.steps[i];
-      if (x.kind != StepKind::Tokens) continue;
-      const bool in_cq = cq_mode && !nchw_buf[size_t(x.in0)] && x.S > 1;
-      c += std::string(c.empty() ? "" : ",") + "{\"step\":" + std::to_string(i) + ",\"kernel\":\"" + (in_cq ? "tokens_cq" : "tokens_nchw") + "\",\"in_layout\":\"" +
-           (in_cq ? "NC/4HW4" : "NCHW") + "\"}";
-    }
-    if (!c.empty()) o << ",\"tokens\":[" << c << "]";
-  }
+  // per QDense step: does its input / output edge carry bytes
+  per_step("qdense", {StepKind::QDense}, [&](size_t i, const Step &) {
+    return step_obj(i, std::string(",\"in_bytes\":") + (sched[i].in_narrow ? "true" : "false") + ",\"out_bytes\":" + (sched[i].out_narrow ? "true" : "false"));
+  });
+  // per QConv2d step: the layouts it reads and writes, and whether it stages its quantised input window in LDS
+  per_step("qconv", {StepKind::QConv2d}, [&](size_t i, const Step &x) {
+    return step_obj(i, ",\"C\":" + std::to_string(x.C) + ",\"M\":" + std::to_string(x.Mo) + ",\"k\":[" + std::to_string(x.kh) + "," + std::to_string(x.kw) + "],\"out_hw\":[" +
+                           std::to_string(x.OH) + "," + std::to_string(x.OW) + "]" + layouts(layout_name(x.in0), layout_name(x.out)) + ",\"input_window\":\"" +
+                           (kern::qconv_stages_in_lds(qconv_launch(x)) ? "lds" : "global") + "\"");
+  });
+  // per HDense step: what its input / output edge carries
+  per_step("hdense", {StepKind::HDense}, [&](size_t i, const Step &) {
+    return step_obj(i, std::string(",\"in\":\"") + (sched[i].in_narrow ? "half" : "f32") + "\",\"out\":\"" + (sched[i].out_narrow ? "half" : "f32") + "\"");
+  });
+  // per ConvTranspose2d step: the kernel that runs it and the layouts it reads and writes
+  per_step("convt", {StepKind::ConvTranspose2d}, [&](size_t i, const Step &x) {
+    return step_obj(i, std::string(",\"kernel\":\"") + (sched[i].kind == ExecKind::ConvTPhase ? "convt2d_phase" : "convt2d_generic") + "\"" + layouts(layout_name(x.in0), layout_name(x.out)));
+  });
+  // per SpatialNorm / SpatialStats step: the kernel that runs it, its groups, the layouts it reads and writes and the fused activation
+  per_step("spatialnorm", {StepKind::SpatialNorm, StepKind::SpatialStats}, [&](size_t i, const Step &x) {
+    const bool stats = x.kind == StepKind::SpatialStats;  // (its flat result is reported in its input's layout)
+    return step_obj(i, std::string(",\"kernel\":\"") + (stats ? "spatialnorm_stats" : x.in1 < 0 ? "spatialnorm_fused" : "spatialnorm_apply") + "\",\"groups\":" + std::to_string(x.groups) +
+                           layouts(layout_name(x.in0), layout_name(stats ? x.in0 : x.out)) + ",\"act\":\"" + act_name(x.act) + "\"");
+  });
+  // per ChannelNorm step: the form of the kernel that runs it and the layout it reads and writes
+  per_step("channelnorm", {StepKind::ChannelNorm}, [&](size_t i, const Step &x) {
+    return step_obj(i, std::string(",\"kernel\":\"") + (sched[i].form == 0 ? "channelnorm_regs" : "channelnorm_reread") + "\"" + layouts(layout_name(x.in0), layout_name(x.out)));
+  });
+  // per PixelShuffle step: its form and block, the kernel that runs it and the layouts it reads and writes
+  per_step("pixelshuffle", {StepKind::PixelShuffle}, [&](size_t i, const Step &x) {
+    return step_obj(i, std::string(",\"kernel\":\"") + pixelshuffle_kernel_name(sched[i].form) + "\",\"form\":\"" + pixelshuffle_form_name(x.ps_to_space, x.ps_channel_major) +
+                           "\",\"block\":" + std::to_string(x.ps_block) + layouts(layout_name(x.in0), layout_name(x.out)));
+  });
+  // per Tokens step: the kernel that runs it and the layout it reads (its result is a flat window)
+  per_step("tokens", {StepKind::Tokens}, [&](size_t i, const Step &x) {
+    const bool in_cq = cq(x.in0) && x.S > 1;  // (an [N,C,1,1] tensor is the same floats in either layout)
+    return step_obj(i, std::string(",\"kernel\":\"") + (in_cq ? "tokens_cq" : "tokens_nchw") + "\",\"in_layout\":\"" + (in_cq ? "NC/4HW4" : "NCHW") + "\"");
+  });
   if (!chains.empty()) {
     o << ",\"chain_kernels\":[";
     for (size_t i = 0; i < chains.size(); i++) o << (i ? "," : "") << json_str(kern::chain_kernel_name(chains[i].shape));

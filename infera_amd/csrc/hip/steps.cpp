@@ -89,13 +89,13 @@ void upload_conv_tiled(const Upload &up, size_t i, PlainTables &t) {
     return;
   }
   std::vector<float> bias(s.bias);
-  if (!up.m.conv_split6[i]) {
+  if (!up.m.sched[i].bf16x6) {
     kern::conv2d_tiled_pack(g, s.W.data(), packed.data());
   } else {
     const size_t main_floats = kern::conv2d_split6_packed_floats(g);
     packed.resize(main_floats);
     kern::conv2d_split6_pack(g, s.W.data(), packed.data());
-    if (const int fl = up.m.conv_fold[i]; fl >= 0) {  // the folded 1x1 shortcut: its chunks behind the main filter's, its bias added to this layer's
+    if (const int fl = up.m.sched[i].fold; fl >= 0) {  // the folded 1x1 shortcut: its chunks behind the main filter's, its bias added to this layer's
       const Step &q = up.m.plan.steps[size_t(fl)];
       const kern::ConvGeom gq{int(q.C), int(q.H), int(q.Wd), int(q.Mo), int(q.OH), int(q.OW), 1, 1, int(q.sh), int(q.sw), 0, 0, 1, 1, 1};
       packed.resize(main_floats + kern::conv2d_split6_packed_floats(gq));
@@ -108,17 +108,18 @@ void upload_conv_tiled(const Upload &up, size_t i, PlainTables &t) {
 }
 void launch_conv_tiled(const PassRunner &r, size_t i, const PlainTables &t) {
   const Step &x = r.st[i];
-  const int fj = r.m.conv_fused_add[i];
+  const StepSchedule &d = r.m.sched[i];
+  const int fj = d.fused_add;
   const kern::ConvGeom gp = kern::conv2d_tiled_geom(conv_geom(x));
   const Step &last = fj >= 0 ? r.st[size_t(fj)] : x;  // whose activation and output the launch carries (a fused residual Add's)
-  if (r.m.conv_split6[i] && r.m.conv_fold[i] >= 0) {
-    const Step &q = r.st[size_t(r.m.conv_fold[i])];
+  if (d.bf16x6 && d.fold >= 0) {
+    const Step &q = r.st[size_t(d.fold)];
     const kern::SecondInput x2{r.buf(q.in0), int(q.C), int(q.H), int(q.Wd), int(q.sh), int(q.sw)};
     kern::conv2d_split6(r.stream, r.buf(x.in0), t.W, t.bias, nullptr, r.buf(last.out), r.nr, gp, act_of(last), x2);
     return;
   }
-  const float *residual = fj >= 0 ? r.buf(r.m.conv_residual_buf[i]) : nullptr;
-  if (r.m.conv_split6[i]) kern::conv2d_split6(r.stream, r.buf(x.in0), t.W, t.bias, residual, r.buf(last.out), r.nr, gp, act_of(last));
+  const float *residual = fj >= 0 ? r.buf(d.residual_buf) : nullptr;
+  if (d.bf16x6) kern::conv2d_split6(r.stream, r.buf(x.in0), t.W, t.bias, residual, r.buf(last.out), r.nr, gp, act_of(last));
   else kern::conv2d_tiled(r.stream, r.buf(x.in0), t.W, t.bias, residual, r.buf(last.out), r.nr, gp, act_of(last));
 }
 
@@ -147,10 +148,10 @@ void upload_conv_patch(const Upload &up, size_t i, PlainTables &t) {
     if (!s.bias.empty()) t.bias = up(zero_padded(s.bias, size_t(gp.M)));
     return;
   }
-  if (const int fj = up.m.conv_fused_pool[i]; fj >= 0) {
+  if (const int fj = up.m.sched[i].fused_pool; fj >= 0) {
     const kern::PoolTail tail = pool_tail(up.m.plan.steps[size_t(fj)]);
     kern::conv2d_patch_pack(g, s.W.data(), packed.data(), &tail);
-    if (up.m.stem_split6[i]) {  // (the exact-fp32 blob stays: INFERA_STEM_SPLIT=0 at run time compares the two)
+    if (up.m.sched[i].bf16x6) {  // (the exact-fp32 blob stays: INFERA_STEM_SPLIT=0 at run time compares the two)
       std::vector<float> sp(kern::conv2d_stem_split6_packed_floats());
       kern::conv2d_stem_split6_pack(g, s.W.data(), sp.data());
       t.stem_split = up(sp);
@@ -164,14 +165,14 @@ void upload_conv_patch(const Upload &up, size_t i, PlainTables &t) {
 void launch_conv_patch(const PassRunner &r, size_t i, const PlainTables &t) {
   const Step &x = r.st[i];
   const kern::ConvGeom gp = kern::conv2d_patch_geom(conv_geom(x));
-  const int fj = r.m.conv_fused_pool[i];
+  const int fj = r.m.sched[i].fused_pool;
   if (fj < 0) {
     kern::conv2d_patch(r.stream, r.buf(x.in0), t.W, t.bias, r.buf(x.out), r.nr, gp, act_of(x), r.dm.num_cus);
     return;
   }
   const Step &q = r.st[size_t(fj)];
   const char *sse = getenv("INFERA_STEM_SPLIT");  // 0: the exact-fp32 stem kernels under a split plan (read per launch: tests, A/B)
-  if (r.m.stem_split6[i] && t.stem_split && !(sse && atoi(sse) == 0))
+  if (r.m.sched[i].bf16x6 && t.stem_split && !(sse && atoi(sse) == 0))
     kern::conv2d_stem_split6(r.stream, r.buf(x.in0), t.stem_split, t.bias, r.buf(q.out), r.nr, gp, act_of(x), pool_tail(q), r.dm.num_cus);
   else
     kern::conv2d_patch_pool(r.stream, r.buf(x.in0), t.W, t.bias, r.buf(q.out), r.nr, gp, act_of(x), pool_tail(q), r.dm.num_cus);
@@ -223,7 +224,7 @@ void launch_qdense(const PassRunner &r, size_t i, const QuantTables &t) {
   q.X = r.buf(x.in0), q.Y = r.buf(x.out), q.rows = r.nr * x.rep;
   q.Wp = t.Wfrag, q.mult = t.mult, q.bias = t.bias, q.c0 = t.c0, q.wz = t.wz;
   q.K = int(x.K), q.M = int(x.M);
-  q.in_bytes = r.m.q_in_bytes[i] != 0, q.out_bytes = r.m.q_out_bytes[i] != 0;
+  q.in_bytes = r.m.sched[i].in_narrow, q.out_bytes = r.m.sched[i].out_narrow;
   kern::qdense(r.stream, q);
 }
 // (the weight fragments in the kernel's (channel chunk, tap, channel) order)
@@ -263,7 +264,7 @@ void launch_hdense(const PassRunner &r, size_t i, const HalfTables &t) {
   h.Wp = t.Wp, h.bias = t.bias, h.bias_mode = x.h_bias_mode;
   h.K = int(x.K), h.M = int(x.M);
   h.act = int(x.act), h.act_a = x.act_a, h.act_b = x.act_b;
-  h.in_half = r.m.h_in_half[i] != 0, h.out_half = r.m.h_out_half[i] != 0;
+  h.in_half = r.m.sched[i].in_narrow, h.out_half = r.m.sched[i].out_narrow;
   kern::hdense(r.stream, h);
 }
 
@@ -373,7 +374,7 @@ void upload_convt(const Upload &up, size_t i, ConvTKernelTables &t) {
   const Step &s = up.m.plan.steps[i];
   const kern::ConvTGeom g = convt_geom(s);
   std::vector<int32_t> tab = s.deconv->tab;
-  if (up.m.exec[i] == ExecKind::ConvTPhase) {
+  if (up.m.sched[i].kind == ExecKind::ConvTPhase) {
     std::vector<float> packed(kern::convt2d_phase_packed_floats(g, tab.data()));
     std::vector<int32_t> off(size_t(g.sh) * g.sw, 0);
     kern::convt2d_phase_pack(g, tab.data(), s.W.data(), packed.data(), off.data());
@@ -389,7 +390,7 @@ void upload_convt(const Upload &up, size_t i, ConvTKernelTables &t) {
 }
 void launch_convt(const PassRunner &r, size_t i, const ConvTKernelTables &t) {
   const Step &x = r.st[i];
-  if (r.m.exec[i] == ExecKind::ConvTPhase)
+  if (r.m.sched[i].kind == ExecKind::ConvTPhase)
     kern::convt2d_phase(r.stream, r.buf(x.in0), t.W, t.bias, r.buf(x.out), t.tab, r.nr, convt_geom(x), x.deconv->max_phase_pixels, act_of(x), r.cq(x.out));
   else
     kern::convt2d_generic(r.stream, r.buf(x.in0), t.W, t.bias, r.buf(x.out), t.tab, r.nr, convt_geom(x), act_of(x), r.cq(x.in0), r.cq(x.out));
@@ -428,10 +429,11 @@ void upload_channelnorm(const Step &s, ChannelNormTables &t, const Upload &up) {
   t.gamma = up(s.scale);
   t.beta = s.shift.empty() ? nullptr : up(s.shift);
 }
-void launch_channelnorm(const PassRunner &r, const Step &x, const ChannelNormTables &t) {
+void launch_channelnorm(const PassRunner &r, size_t i, const ChannelNormTables &t) {
+  const Step &x = r.st[i];
   if (r.cq(x.in0) != r.cq(x.out)) throw InferaError::onnx("ChannelNorm '" + x.origin + "' would have to change the tensor's layout; there is no such kernel");
   const bool cq = r.cq(x.in0) && x.S > 1;  // (an [N,C,1,1] tensor is the same floats in either layout)
-  if (!kern::channelnorm(r.stream, r.buf(x.in0), t.gamma, t.beta, r.buf(x.out), r.nr, int(x.C), int(x.S), cq, x.out_mode == 0, x.ln_eps, act_of(x)))
+  if (!kern::channelnorm(r.stream, r.buf(x.in0), t.gamma, t.beta, r.buf(x.out), r.nr, int(x.C), int(x.S), cq, r.m.sched[i].form == 0, x.ln_eps, act_of(x)))
     throw InferaError::onnx("ChannelNorm kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
 }
 
@@ -499,12 +501,14 @@ void launch_spectrum(const PassRunner &r, const Step &x, const SpectrumTables &t
     throw InferaError::onnx("Spectrum kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
 }
 
-// ---- PixelShuffle (pixelshuffle.hip): no tables; the scheduler chose the form for the two layouts (Step::out_mode) ----
-void launch_pixelshuffle(const PassRunner &r, const Step &x) {
+// ---- PixelShuffle (pixelshuffle.hip): no tables; the scheduler chose the form for the two layouts (StepSchedule::form) ----
+void launch_pixelshuffle(const PassRunner &r, size_t i) {
+  const Step &x = r.st[i];
+  const int form = r.m.sched[i].form;
   if (r.in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: a PixelShuffle step reads its input row-major");
   const kern::PixelShuffleGeom g{int(x.ps_block), int(x.C), int(x.H), int(x.Wd), int(x.Mo), int(x.OH), int(x.OW), x.ps_to_space, x.ps_channel_major};
-  if (!kern::pixel_shuffle(r.stream, r.buf(x.in0), r.buf(x.out), r.nr, g, x.out_mode, r.cq(x.in0), r.cq(x.out)))
-    throw InferaError::onnx("PixelShuffle kernel launch failed: '" + x.origin + "' was scheduled as " + pixelshuffle_kernel_name(x.out_mode) + " for other layouts than it meets");
+  if (!kern::pixel_shuffle(r.stream, r.buf(x.in0), r.buf(x.out), r.nr, g, form, r.cq(x.in0), r.cq(x.out)))
+    throw InferaError::onnx("PixelShuffle kernel launch failed: '" + x.origin + "' was scheduled as " + pixelshuffle_kernel_name(form) + " for other layouts than it meets");
 }
 
 // ---- 3-D convolutions (host/conv3d.hpp, conv3d.hip): the MFMA form takes the weights in the order its lanes load them and a bias padded to whole
@@ -591,11 +595,11 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::SpatialNorm: launch_spatialnorm(*this, x, d.spatialnorm); break;
     case StepKind::SpatialStats: launch_spatialstats(*this, x); break;
     case StepKind::Tokens: launch_tokens(*this, x, d.tokens); break;
-    case StepKind::ChannelNorm: launch_channelnorm(*this, x, d.channelnorm); break;
+    case StepKind::ChannelNorm: launch_channelnorm(*this, i, d.channelnorm); break;
     case StepKind::Embed: launch_embed(*this, x, d.embed); break;
     case StepKind::Interact: launch_interact(*this, x, d.interact); break;
     case StepKind::Rotary: launch_rotary(*this, x, d.rotary); break;
-    case StepKind::PixelShuffle: launch_pixelshuffle(*this, x); break;
+    case StepKind::PixelShuffle: launch_pixelshuffle(*this, i); break;
     case StepKind::Spectrum: launch_spectrum(*this, x, d.spectrum); break;
     case StepKind::Conv3d: launch_conv3d(*this, x, t); break;
     case StepKind::Pool3d:
@@ -645,7 +649,7 @@ void PassRunner::launch_plain(size_t i) {
 void upload_step(const Upload &up, size_t i) {
   const Step &s = up.m.plan.steps[i];
   DeviceStep &d = up.dm.steps[i];
-  switch (up.m.exec[i]) {
+  switch (up.m.sched[i].kind) {
     case ExecKind::Skipped: return;
     case ExecKind::Mlp3Head: return upload_mlp3(up, i);
     case ExecKind::ChainHead: return upload_chain(up, i);
@@ -688,7 +692,7 @@ bool PassRunner::launch_fused(size_t i, size_t *skip) {
   const Step &x = st[i];
   const PlainTables &t = dm.steps[i].plain;
   const bool cm = in_colmajor && x.in0 == 0;  // this step reads the caller's column-major chunk
-  switch (m.exec[i]) {
+  switch (m.sched[i].kind) {
     case ExecKind::Skipped: return true;
     case ExecKind::Mlp3Head: launch_mlp3(*this, i, cm); return true;
     case ExecKind::ChainHead: launch_chain(*this, i, cm); return true;

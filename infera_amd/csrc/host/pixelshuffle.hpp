@@ -14,7 +14,7 @@ namespace infera_hip {
 constexpr int64_t kPixelShuffleMaxC = 65536;                // channels of the wider side
 constexpr int64_t kPixelShuffleMaxS = int64_t(1) << 20;     // pixels of the larger plane
 
-// The forms of the kernel (pixelshuffle.hip), Step::out_mode of a scheduled PixelShuffle step
+// The forms of the kernel (pixelshuffle.hip), StepSchedule::form of a PixelShuffle step (hip/backend.hpp)
 enum PixelShuffleKernel : int {
   kPixelShuffleGeneric = 0,    // any block, channel count and layout pairing: one output element (NCHW) or one gathered output quad per lane
   kPixelShuffleQuadCopy = 1,   // block-major, channel quads to channel quads: an output quad is an input quad -- one 16-byte load and store per lane

@@ -35,6 +35,7 @@ enum class Act : int {
   Erf = 16, Gelu = 17, Reciprocal = 18, Floor = 19, Ceil = 20, Softsign = 21, Trunc = 22, Round = 23,
   Swish = 24,  // x * sigmoid(x): recognised from Mul(x, Sigmoid(x)) (EfficientNet / YOLO exports)
 };
+const char *act_name(Act a);  // the ONNX operator's name as the plan reports print it ("" for None)
 constexpr int kMaxMfmaFusedAct = 5;  // the load-time specialised chain kernels resolve kinds 0..5
 // what the ahead-of-time MFMA epilogues resolve (device_common.hpp dispatch_act): the above + the mobile-net gates
 inline bool mfma_fusable(Act a) { return int(a) <= kMaxMfmaFusedAct || a == Act::HardSigmoid || a == Act::HardSwish || a == Act::Swish; }
@@ -79,12 +80,12 @@ enum class StepKind : int {
   SpatialNorm = 36,   // InstanceNormalization / GroupNormalization over the (C / groups) * S elements of each of `groups` channel groups of in0 [rows, C, S]: y = act((x - mean) / sqrt(var + ln_eps) * scale[c] + shift[c]); in1 = -1: the fused kernel, else in1 = a SpatialStats result (host/spatialnorm.hpp, spatialnorm.hip)
   SpatialStats = 37,  // out [rows, groups, 3] = (mean, resid, 1 / sqrt(var + ln_eps)) of each group of in0: the first half of the general SpatialNorm plan (the scheduler inserts it, schedule.cpp)
   Tokens = 38,        // out [rows, rep = P + S, K = C] = the window of in0 [rows, C, S] (NCHW or channel quads): out[r, P + s, c] = in0[r, c, s] (+ cst[P + s, c]); rows p < P = prefix[p, c] (+ cst[p, c]) (host/tokens.hpp, tokens.hip)
-  ChannelNorm = 39,   // LayerNorm over the C channels at each of the S pixels of in0 [rows, C, S] (NCHW or channel quads, never changed): y = act((x - mean) / sqrt(var + ln_eps) * scale[c] + shift[c]), shift may be empty; out_mode (set by the scheduler): 0 the register form, 1 the re-read form (host/channelnorm.hpp, channelnorm.hip)
+  ChannelNorm = 39,   // LayerNorm over the C channels at each of the S pixels of in0 [rows, C, S] (NCHW or channel quads, never changed): y = act((x - mean) / sqrt(var + ln_eps) * scale[c] + shift[c]), shift may be empty; the scheduler picks the register or the re-read form (StepSchedule::form, hip/backend.hpp; host/channelnorm.hpp, channelnorm.hip)
   Embed = 40,         // out [rows, F] = pieces in output order: rows of constant tables chosen by index columns of in0 [rows, W] (truncated toward zero, + an offset) and runs of in0's columns as they are; a window [rows, k, d] when the pack says so (EmbedPack, host/embed.hpp, embed.hip)
   Interact = 41,      // feature interactions of in0 [rows, k, d] (rows first, flat): dot mode, out [rows, F] = chosen entries of T . T^T beside bit copies of columns of T; fm mode, out [rows, d] or [rows, 1] = h * ((sum_f T)^2 - sum_f T^2) (InteractPack, host/interact.hpp, interact.hip)
   RmsNorm = 42,       // y = x / sqrt(mean(x^2) + ln_eps) * scale[K] over each of the `rep` vectors of K elements of a row (RMSNormalization; layernorm.hip)
   Rotary = 43,        // rotary position embedding of in0 [rows, attn_T, ld] read through the view (attn_ld[0], attn_off[0]) into a dense [rows, attn_T, attn_heads * attn_dh]: column j < rot_rd of a head, y[j] = fl(fl(x[j] * scale[t, j]) + fl(x[partner(j)] * shift[t, j])), partner(j) = j +- rot_rd / 2 or j ^ 1 (rot_interleaved); the other columns are bit copies (RotaryEmbedding and the rotate_half spelling; rotary.hip)
-  PixelShuffle = 44,  // DepthToSpace / SpaceToDepth of in0 [rows, C, H, Wd] to [rows, Mo, OH, OW] with block ps_block: a bit copy of every element, in one of four forms (ps_to_space, ps_channel_major: host/pixelshuffle.hpp); out_mode (set by the scheduler): the PixelShuffleKernel that runs it (pixelshuffle.hip)
+  PixelShuffle = 44,  // DepthToSpace / SpaceToDepth of in0 [rows, C, H, Wd] to [rows, Mo, OH, OW] with block ps_block: a bit copy of every element, in one of four forms (ps_to_space, ps_channel_major: host/pixelshuffle.hpp); the scheduler picks the PixelShuffleKernel that runs it (StepSchedule::form, hip/backend.hpp; pixelshuffle.hip)
   Spectrum = 46,      // the real DFT / STFT of in0 [rows, C, L]: frames of n samples `hop` apart times a window, out [rows, C, frames, bins (, 2)] or, bins_major, [rows, C, bins, frames (, 2)] as complex pairs, power or magnitude (SpectrumPack, host/spectrum.hpp, spectrum.hip)
   Conv3d = 47,        // NCDHW convolution of in0 [rows, C, D, H, Wd] to [rows, Mo, OD, OH, OW] (the Conv2d geometry fields + the depth axis: D, OD, kd, sd, dd, pf / pk = the front / back pads); W = the ONNX weights [M, C/g, kd, kh, kw], BatchNormalization folded when adjacent; out_mode = the kernel (Conv3dExec, host/conv3d.hpp; conv3d.hip)
   Pool3d = 48,        // MaxPool / AveragePool over [rows, C, D, H, Wd] (the same geometry fields; is_max, count_pad)
@@ -170,7 +171,7 @@ struct Step {
   std::shared_ptr<const InteractPack> interact;
   std::shared_ptr<const SpectrumPack> spectrum;
   std::shared_ptr<const DeconvPack> deconv;  // ConvTranspose2d: phase tap lists; Resize2d: source tables
-  int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut, RowReduce: ReduceOp, TopK: 0 values / 1 indices, Nearest / NearestReduce: NearestOut, NearestVote: VoteOut, Conv3d: Conv3dExec
+  int out_mode = 0;  // Tree*: TreeOut, Svm*: SvmOut, Recurrent: RnnOut, RowReduce: ReduceOp, TopK: 0 values / 1 indices, Nearest / NearestReduce: NearestOut, NearestVote: VoteOut, Conv3d: Conv3dExec; written by the lowering alone (the scheduler's choices per step: StepSchedule, hip/backend.hpp)
   // Attention: Q = in0, K = in1, V = in2 (the same buffer three times when the projections are merged), each [rows, T, ld] with the head
   // block of head g at columns off + g * dh of a step; mask (cst): [T, T] added to the scaled scores, -inf = no weight, empty = none
   int in2 = -1;

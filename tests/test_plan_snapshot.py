@@ -20,7 +20,7 @@ from tests.test_conv_split_plan import shortcut_block
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plans")
 
 # (each one a model a CPU test of its family already loads: test_quantized, test_half, test_quantized_conv, test_conv_split_plan, test_prep,
-# test_recurrent, test_transformer, test_nearest)
+# test_recurrent, test_transformer, test_nearest, test_pixel_shuffle, test_conv3d, test_spectrum)
 MODELS = {
     "qdense_chain": lambda: W.quantized_from_spec(W.quantized_mlp_spec((128, 256, 64, 1))),  # the two middle edges carry bytes
     "hdense_chain": lambda: W.half_from_spec(W.half_mlp_spec((128, 256, 64, 1))),            # ... halves
@@ -34,11 +34,14 @@ MODELS = {
     "lstm": lambda: W.recurrent_from_spec(W.recurrent_spec("LSTM", T=6, F=4, H=8, initial=0.5)),
     "encoder": lambda: W.transformer_from_spec(W.transformer_spec(T=24, F=8, E=64, h=4, ff=256, layers=1, causal=True)),
     "kmeans": lambda: W.kmeans_from_spec(W.kmeans_spec(30, 100, seed=3), "gemm", "label"),
+    "espcn": lambda: W.espcn()[0],        # a patch stem, two tiled convolutions and the PixelShuffle that stores the served NCHW result
+    "r3d_net": lambda: W.r3d_net()[0],    # Conv3d and Pool3d: a plan in plain element order
+    "stft": lambda: W.stft_model(),       # Spectrum
 }
 
 # The plan alone, for the families the reload test's random rows cannot feed (indices, masks) or need not: again each one a model a CPU test
 # of its family already loads (test_deconv, test_spatial_norm, test_vit, test_channel_norm, test_embed, test_nearest,
-# test_recurrent, test_onnx_ml_domain, test_onnx_breadth, test_half).  The writers that also return what they drew give (bytes, ...).
+# test_recurrent, test_onnx_ml_domain, test_onnx_breadth, test_half, test_pixel_shuffle, test_rotary).  The writers that also return what they drew give (bytes, ...).
 # (No padded text encoder: its small feed-forward layers are a load-time compiled chain where a GPU is visible, see above.)
 PLAN_ONLY = {
     "conv_autoencoder": lambda: W.conv_autoencoder()[0],
@@ -57,6 +60,8 @@ PLAN_ONLY = {
     "reduce_zoo": lambda: W.reduce_zoo()[0],
     "half_cnn": lambda: W.half_cnn_from_spec(W.half_cnn_spec()),
     "unary_zoo": lambda: W.unary_zoo(),
+    "pixel_unshuffle_stem": lambda: W.pixel_unshuffle_stem()[0],  # a PixelShuffle that reads the caller's image
+    "rotary": lambda: W.rotary_model(T=6, h=2, dh=8),
 }
 
 
