@@ -409,6 +409,18 @@ struct PixelShuffleGeom {
 // `kernel`: the PixelShuffleKernel the scheduler chose for these layouts; false: it does not serve them (nothing was launched)
 bool pixel_shuffle(hipStream_t s, const float *X, float *Y, int64_t rows, const PixelShuffleGeom &g, int kernel, bool in_cq, bool out_cq);
 
+// ---- GridSample / AffineGrid (gridsample.hip; the coordinate function, the forms and the caps: host/gridsample.hpp) ------
+// C, H, W = the sampled tensor X; OH, OW = the grid and the result; mode, pad, coords: GridSampleMode, GridSamplePad, GridSampleCoords
+struct GridSampleGeom {
+  int C, H, W, OH, OW, mode, pad, coords;
+  bool align_corners;
+};
+// Y [rows, C, OH, OW] = X [rows, C, H, W] sampled at the coordinates G holds: [rows, OH, OW, 2] (grid), [rows, 2, OH, OW] (planar) or the six
+// affine numbers of each image [rows, 6] (affine).  in_cq / out_cq: X / Y lie in channel-quad planes.  false: beyond the caps (nothing was launched)
+bool grid_sample(hipStream_t s, const float *X, const float *G, float *Y, int64_t rows, const GridSampleGeom &g, bool in_cq, bool out_cq);
+// Y [rows, OH, OW, 2] = the sampling grid of theta [rows, 6]
+bool affine_grid(hipStream_t s, const float *theta, float *Y, int64_t rows, int OH, int OW, bool align_corners);
+
 // ---- InstanceNormalization / GroupNormalization (spatialnorm.hip; host/spatialnorm.hpp) --------------
 // X, Y: [rows, C, S] in NCHW order or (cq) channel-quad planes; G groups of C / G channels; gamma, beta: [C].  false: beyond the kernel's caps
 // fused: where spatialnorm_fused_unit(C, S, G, cq) names a unit -- one pass, y = act(d / sqrtf(var + eps) * gamma + beta)

@@ -6,6 +6,7 @@
 
 #include "../host/channelnorm.hpp"
 #include "../host/deconv.hpp"
+#include "../host/gridsample.hpp"
 #include "../host/pixelshuffle.hpp"
 #include "../host/spatialnorm.hpp"
 #include "../host/embed.hpp"
@@ -221,9 +222,10 @@ void Scheduler::decide_layout(bool commit) {
   auto reads_nchw = [&](const Step &s) { return convolution(s) || s.kind == StepKind::ConvTranspose2d; };
   // (so does the crossing to a window, tokens.hip; its flat result has no layout, and alone it does not make a plan convolutional)
   // (and so does a PixelShuffle, pixelshuffle.hip: the SpaceToDepth stem reads the caller's image)
-  auto reads_either = [&](const Step &s) { return reads_nchw(s) || s.kind == StepKind::Tokens || s.kind == StepKind::PixelShuffle; };
+  // (and a GridSample, gridsample.hip: a warp of the caller's image, in front of or in the middle of a CNN)
+  auto reads_either = [&](const Step &s) { return reads_nchw(s) || s.kind == StepKind::Tokens || s.kind == StepKind::PixelShuffle || s.kind == StepKind::GridSample; };
   // the steps that store NCHW from a channel-quad input where their result has to lie so
-  auto stores_nchw = [](const Step &s) { return s.kind == StepKind::ConvTranspose2d || s.kind == StepKind::PixelShuffle; };
+  auto stores_nchw = [](const Step &s) { return s.kind == StepKind::ConvTranspose2d || s.kind == StepKind::PixelShuffle || s.kind == StepKind::GridSample; };
   // A served [C,H,W] result leaves in the caller's NCHW order.  When such a step -- a transposed convolution or a sub-pixel shuffle, the last
   // layer of a decoder -- is its only writer and nothing reads it, that layer stores NCHW itself and the plan before it stays in channel quads;
   // anything else keeps the plan NCHW.
@@ -254,8 +256,11 @@ void Scheduler::decide_layout(bool commit) {
     }
     if (writers == 1 && readers > 0 && readers == flat_readers) m.nchw_buf[size_t(c.out)] = 1;
   }
+  // (likewise a warp of such an image whose channels are no whole quads -- a spatial transformer in front of a CNN: the convolution behind
+  // it reads the warped image as it would read the caller's)
   for (const auto &s : st)
-    if (elementwise(s) && s.in0 >= 0 && m.nchw_buf[size_t(s.in0)] && is4d(s.out) && s.out != m.plan.out_buf) m.nchw_buf[size_t(s.out)] = 1;
+    if ((elementwise(s) || (s.kind == StepKind::GridSample && s.C % 4 != 0)) && s.in0 >= 0 && m.nchw_buf[size_t(s.in0)] && is4d(s.out) && s.out != m.plan.out_buf)
+      m.nchw_buf[size_t(s.out)] = 1;
   // A spectrogram (spectrum.hip) and the elementwise chain behind it (Add eps, Log) are flat windows in plain element order: a convolution
   // that reads one as a [1, bins, frames] image reads it like the caller's own
   for (const auto &s : st)
@@ -274,6 +279,10 @@ void Scheduler::decide_layout(bool commit) {
     // A channel slice is one contiguous block per sample in channel-quad planes only when it starts on a quad
     // boundary (its length is covered by the whole-quads check on the output tensor below): channels 2..5 of an
     // 8-channel tensor are NOT floats [2HW, 6HW) of the interleaved buffer.
+    // A GridSample reads its grid (or theta) as a flat row, whatever the plan's layout: one that a step wrote as a 4-D tensor would lie in
+    // channel quads.  (The lowering registers the buffers it controls flat; a flow field has two channels, never whole quads.)
+    if (s.kind == StepKind::GridSample && s.gs_coords != kGridCoordsPlanar && is4d(s.in1) && spatial(s.in1) > 1 && !m.nchw_buf[size_t(s.in1)])
+      refuse("'" + s.origin + "' reads its grid from a 4-D tensor a step wrote (a grid is read as a flat row)");
     if (s.kind == StepKind::SliceCols && is4d(s.in0) && spatial(s.in0) > 1 && !m.nchw_buf[size_t(s.in0)] &&
         s.col_off % (4 * spatial(s.in0)) != 0)
       refuse("'" + s.origin + "' slices channels from an offset that is not a whole quad");
@@ -522,6 +531,7 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
         // (a tree walk reads its row tile once per tree slice, and wide rows feature by feature; an SVM once per SV slice)
         const bool windowed = (sk == StepKind::Conv2d && sc[size_t(e.idx)].kind != ExecKind::ConvPatch) || sk == StepKind::QConv2d || sk == StepKind::Pool2d || sk == StepKind::LRN ||
                               sk == StepKind::Conv3d || sk == StepKind::Pool3d ||
+                              sk == StepKind::GridSample ||  // (a gather: up to four fetches per sample, wherever the grid points)
                               sk == StepKind::TreeEnsemble || sk == StepKind::SvmKernel ||
                               sk == StepKind::Nearest ||  // (once per slice of the reference set)
                               sk == StepKind::TopK ||     // (one lane per row: row-strided loads)
@@ -657,6 +667,12 @@ void schedule(LoadedModel &m) {
     if (c.kind == StepKind::PixelShuffle)
       m.sched[i].form = pixelshuffle_kernel(c.ps_block, c.ps_to_space, c.ps_channel_major, c.C, m.cq(c.in0), m.cq(c.out), knobs.pixelshuffle_fast);
   }
+  // GridSample layers: which of the two tensors lie in channel quads (bit 0: X, bit 1: Y); a flat or one-pixel tensor is plain in any plan
+  for (size_t i = 0; i < m.sched.size(); i++) {
+    const Step &c = m.plan.steps[i];
+    auto quads = [&](int b) { return m.cq(b) && s.is4d(b) && s.spatial(b) > 1; };
+    if (c.kind == StepKind::GridSample) m.sched[i].form = (quads(c.in0) ? 1 : 0) | (quads(c.out) ? 2 : 0);
+  }
   s.narrow_edges(StepKind::QDense, knobs.qdense_bytes, true, [](const Step &p, const Step &c) { return c.qx == p.qy; });
   s.narrow_edges(StepKind::HDense, knobs.hdense_half, false, [](const Step &, const Step &) { return true; });
   const auto eff = effective_steps(m);
@@ -758,6 +774,12 @@ std::string LoadedModel::describe_json() const {
   per_step("pixelshuffle", {StepKind::PixelShuffle}, [&](size_t i, const Step &x) {
     return step_obj(i, std::string(",\"kernel\":\"") + pixelshuffle_kernel_name(sched[i].form) + "\",\"form\":\"" + pixelshuffle_form_name(x.ps_to_space, x.ps_channel_major) +
                            "\",\"block\":" + std::to_string(x.ps_block) + layouts(layout_name(x.in0), layout_name(x.out)));
+  });
+  // per GridSample step: the kernel variant that runs it and the layouts it reads and writes
+  per_step("gridsample", {StepKind::GridSample}, [&](size_t i, const Step &x) {
+    const bool in_cq = sched[i].form & 1, out_cq = sched[i].form & 2;
+    return step_obj(i, std::string(",\"exec\":\"") + gridsample_exec_name(x.gs_mode, in_cq, out_cq) + "\",\"coords\":\"" + gridsample_coords_name(x.gs_coords) + "\"" +
+                           layouts(in_cq ? "NC/4HW4" : "NCHW", out_cq ? "NC/4HW4" : "NCHW"));
   });
   // per Tokens step: the kernel that runs it and the layout it reads (its result is a flat window)
   per_step("tokens", {StepKind::Tokens}, [&](size_t i, const Step &x) {

@@ -10,6 +10,7 @@
 #include "../host/nearest.hpp"
 #include "../host/channelnorm.hpp"
 #include "../host/onnx_model.hpp"
+#include "../host/gridsample.hpp"
 #include "../host/pixelshuffle.hpp"
 #include "../host/prep.hpp"
 #include "../host/recurrent.hpp"
@@ -511,6 +512,21 @@ void launch_pixelshuffle(const PassRunner &r, size_t i) {
     throw InferaError::onnx("PixelShuffle kernel launch failed: '" + x.origin + "' was scheduled as " + pixelshuffle_kernel_name(form) + " for other layouts than it meets");
 }
 
+// ---- GridSample / AffineGrid (gridsample.hip): no tables; the scheduler recorded which of X and Y lie in channel quads (StepSchedule::form) ----
+void launch_gridsample(const PassRunner &r, size_t i) {
+  const Step &x = r.st[i];
+  const int form = r.m.sched[i].form;
+  if (r.in_colmajor && (x.in0 == 0 || x.in1 == 0)) throw InferaError::onnx("internal: a GridSample step reads its input row-major");
+  const kern::GridSampleGeom g{int(x.C), int(x.H), int(x.Wd), int(x.OH), int(x.OW), x.gs_mode, x.gs_pad, x.gs_coords, x.gs_align};
+  if (!kern::grid_sample(r.stream, r.buf(x.in0), r.buf(x.in1), r.buf(x.out), r.nr, g, (form & 1) != 0, (form & 2) != 0))
+    throw InferaError::onnx("GridSample kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+void launch_affinegrid(const PassRunner &r, const Step &x) {
+  if (r.in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: an AffineGrid step reads its input row-major");
+  if (!kern::affine_grid(r.stream, r.buf(x.in0), r.buf(x.out), r.nr, int(x.OH), int(x.OW), x.gs_align))
+    throw InferaError::onnx("AffineGrid kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+
 // ---- 3-D convolutions (host/conv3d.hpp, conv3d.hip): the MFMA form takes the weights in the order its lanes load them and a bias padded to whole
 // channel tiles; the generic form takes both as the lowering left them.  Pool3d has no tables ----
 void upload_conv3d(const Step &s, PlainTables &t, const Upload &up) {
@@ -601,6 +617,8 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::Rotary: launch_rotary(*this, x, d.rotary); break;
     case StepKind::PixelShuffle: launch_pixelshuffle(*this, i); break;
     case StepKind::Spectrum: launch_spectrum(*this, x, d.spectrum); break;
+    case StepKind::GridSample: launch_gridsample(*this, i); break;
+    case StepKind::AffineGrid: launch_affinegrid(*this, x); break;
     case StepKind::Conv3d: launch_conv3d(*this, x, t); break;
     case StepKind::Pool3d:
       if (in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: a Pool3d step reads its input row-major");

@@ -649,6 +649,22 @@ struct Lowerer {
   // the step over the [N,C,H,W] activation `a`, bound to out_node's first output; refusals name `at`
   void pixel_shuffle_step(const NodeDef &at, const NodeDef &out_node, const Val &a, int64_t b, bool to_space, bool channel_major, const std::string &origin);
 
+  // ---- lower_gridsample.cpp: GridSample and AffineGrid (INTEGRATION.md 2.6 "Grid sampling") ----
+  // An AffineGrid whose only reader is one GridSample (as its grid): nothing is emitted, the GridSample finds it under the grid's name and
+  // becomes ONE step that reads theta
+  struct AffinePending {
+    Val theta;  // [N,2,3] or [N,6]
+    int64_t OH = 0, OW = 0;
+    bool align = false;
+    std::string origin;
+  };
+  std::map<std::string, AffinePending> affine_pending;
+  // a live GridSample node that reads a rank-4 graph input with a symbolic extent behind the batch axis, or two of them whose fixed batch
+  // extents differ: refused by its name (run: before the general rules on input shapes)
+  void check_grid_extents() const;
+  void affine_grid(const NodeDef &n);
+  void grid_sample(const NodeDef &n);
+
   // ---- lower_conv3d.cpp: Conv, MaxPool and AveragePool on [N,C,D,H,W] activations (INTEGRATION.md 2.6 "3-D convolutions") ----
   void spatial3d(const NodeDef &n, Step &s);
   void conv3d(const NodeDef &n);

@@ -24,6 +24,7 @@
 #include "attention.hpp"
 #include "channelnorm.hpp"
 #include "deconv.hpp"
+#include "gridsample.hpp"
 #include "interact.hpp"
 #include "lowerer.hpp"
 #include "nearest.hpp"
@@ -1957,6 +1958,7 @@ namespace lowering {
     }
     if (op == "LayerNormalization") return channel_norm_node(n);
     if (op == "MatMul") return view_matmul(n);
+    if (op == "GridSample") return grid_sample(n);  // (its grid operand: a flow field [N,2,Ho,Wo] read as [N,Ho,Wo,2], lower_gridsample.cpp)
     if (unary_ops.count(op)) {
       if (!get(n, 0).cl) bad_form(n, "it reads the channels-last view among its parameters");
       return as_nchw(n, [&] { unary(n); });
@@ -1978,6 +1980,16 @@ namespace lowering {
       const int64_t C = v.shape[3];
       if (c.c->f32.size() == 1) return as_nchw(n, [&] { binary(n, bo->second); });  // a scalar
       const bool per_channel = int64_t(c.c->f32.size()) == C && !c.shape.empty() && c.shape.back() == C && c.shape.size() <= 4;
+      // one value per element of a row, [H,W,C] or [1,H,W,C] (the identity grid added to a flow field): read as [C,H,W], an ordinary step
+      const int64_t Hv = v.shape[1], Wv = v.shape[2];
+      const size_t cr = c.shape.size();
+      if (!per_channel && (cr == 3 || (cr == 4 && c.shape[0] == 1)) && c.shape[cr - 3] == Hv && c.shape[cr - 2] == Wv && c.shape[cr - 1] == C) {
+        std::vector<float> t(c.c->f32.size());
+        for (int64_t p = 0; p < Hv * Wv; p++)
+          for (int64_t ch = 0; ch < C; ch++) t[size_t(ch * Hv * Wv + p)] = c.c->f32[size_t(p * C + ch)];
+        const NodeDef r = with_const_input(n, ci, redimensioned(c, {C, Hv, Wv}, std::move(t)));
+        return as_nchw(r, [&] { binary(r, bo->second); });
+      }
       if (!per_channel)
         bad_form(n, "the constant " + shape_str(c.shape) + " is neither a scalar nor one value per channel ([" + std::to_string(C) + "] or [1,1,1," + std::to_string(C) +
                         "]) of the channels-last view " + shape_str(v.shape));
@@ -3555,6 +3567,7 @@ namespace lowering {
       case StepKind::TopK:
       case StepKind::NearestReduce: return true;
       case StepKind::NearestVote: return s.out_mode == kVoteLabel;  // (a class value picked from a table; the other modes divide)
+      case StepKind::GridSample: return s.gs_mode == kGridNearest;  // (a pixel picked, or +0; bilinear blends)
       case StepKind::Tokens: return s.cst.empty();  // (movement alone; a half graph's position Add is never folded)
       case StepKind::RowReduce: return s.out_mode == kReduceMax || s.out_mode == kReduceMin;
       case StepKind::Pool2d:
@@ -3711,6 +3724,8 @@ namespace lowering {
     else if (op == "ConvTranspose") conv_transpose(n);
     else if (op == "Resize" || op == "Upsample") resize(n);
     else if (op == "DepthToSpace" || op == "SpaceToDepth") depth_space(n);
+    else if (op == "GridSample") grid_sample(n);
+    else if (op == "AffineGrid") affine_grid(n);
     else if (op == "DFT") dft(n);
     else if (op == "STFT") stft(n);
     else if (op == "BatchNormalization") batchnorm(n);
@@ -4283,6 +4298,7 @@ namespace lowering {
       if (!served_type(v.elem_type) && !half_input)
         throw InferaError::onnx("input '" + v.name + "' is not f32, int64 or int32 (element type " + std::to_string(v.elem_type) + ")");
     if (in.dims.size() < 2) throw InferaError::onnx("input rank " + std::to_string(in.dims.size()) + " has no row axis + feature axis; rank >= 2 is required");
+    check_grid_extents();  // (a GridSample on a symbolic image or grid: refused by the node's name)
     check_shuffle_extents(in);  // (a DepthToSpace / SpaceToDepth on a symbolic image: refused by the node's name)
     for (size_t i = 1; i < in.dims.size(); i++)
       if (in.dims[i] <= 0) throw InferaError::onnx("only the leading (row/batch) dimension of the input may be symbolic, got " + shape_str(in.dims));

@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "deconv.hpp"
 #include "embed.hpp"
+#include "gridsample.hpp"
 #include "interact.hpp"
 #include "spatialnorm.hpp"
 #include "spectrum.hpp"
@@ -48,7 +49,7 @@ const char *act_name(Act a) {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary", "PixelShuffle", "NearestVote", "Spectrum", "Conv3d", "Pool3d"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary", "PixelShuffle", "NearestVote", "Spectrum", "Conv3d", "Pool3d", "GridSample", "AffineGrid"};
   std::ostringstream o;
   o << "{\"input_shape\":" << json_int_array(input_shape) << ",\"output_shape\":" << json_int_array(output_shape)
     << ",\"flops_per_row\":" << (long long)flops_per_row();
@@ -173,6 +174,10 @@ std::string Plan::describe_json() const {
     if (s.kind == StepKind::Resize2d)
       o << ",\"C\":" << s.C << ",\"mode\":\"" << (s.deconv->linear ? "linear" : "nearest") << "\",\"coordinate_transformation_mode\":\"" << s.deconv->coord_mode << "\""
         << (s.deconv->linear ? std::string() : ",\"nearest_mode\":\"" + s.deconv->nearest_mode + "\"") << ",\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
+    if (s.kind == StepKind::GridSample)  // (a gather: eight flops per bilinear sample, none counted)
+      o << ",\"mode\":\"" << gridsample_mode_name(s.gs_mode) << "\",\"padding\":\"" << gridsample_pad_name(s.gs_pad) << "\",\"align_corners\":" << int(s.gs_align) << ",\"coords\":\""
+        << gridsample_coords_name(s.gs_coords) << "\",\"C\":" << s.C << ",\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
+    if (s.kind == StepKind::AffineGrid) o << ",\"align_corners\":" << int(s.gs_align) << ",\"out_hw\":[" << s.OH << "," << s.OW << "]";
     if (s.kind == StepKind::PixelShuffle)  // (a copy: no flops; every element is read once and written once)
       o << ",\"form\":\"" << pixelshuffle_form_name(s.ps_to_space, s.ps_channel_major) << "\",\"block\":" << s.ps_block << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"in_hw\":[" << s.H << "," << s.Wd
         << "],\"out_hw\":[" << s.OH << "," << s.OW << "],\"bytes_per_row\":" << 8 * s.C * s.H * s.Wd;

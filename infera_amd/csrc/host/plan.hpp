@@ -89,6 +89,8 @@ enum class StepKind : int {
   Spectrum = 46,      // the real DFT / STFT of in0 [rows, C, L]: frames of n samples `hop` apart times a window, out [rows, C, frames, bins (, 2)] or, bins_major, [rows, C, bins, frames (, 2)] as complex pairs, power or magnitude (SpectrumPack, host/spectrum.hpp, spectrum.hip)
   Conv3d = 47,        // NCDHW convolution of in0 [rows, C, D, H, Wd] to [rows, Mo, OD, OH, OW] (the Conv2d geometry fields + the depth axis: D, OD, kd, sd, dd, pf / pk = the front / back pads); W = the ONNX weights [M, C/g, kd, kh, kw], BatchNormalization folded when adjacent; out_mode = the kernel (Conv3dExec, host/conv3d.hpp; conv3d.hip)
   Pool3d = 48,        // MaxPool / AveragePool over [rows, C, D, H, Wd] (the same geometry fields; is_max, count_pad)
+  GridSample = 49,    // out [rows, C, OH, OW] = in0 [rows, C, H, Wd] sampled at the coordinates in1 holds (gs_coords: a [rows, OH, OW, 2] grid, a [rows, 2, OH, OW] flow field, or six affine numbers per row -- AffineGrid absorbed); gs_mode, gs_pad, gs_align as the operator's attributes; either tensor in NCHW or channel quads (host/gridsample.hpp, gridsample.hip)
+  AffineGrid = 50,    // out [rows, OH, OW, 2] (a flat row) = the sampling grid of theta in0 [rows, 6]: an AffineGrid whose result something else than one GridSample reads (gs_align; gridsample.hip)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
@@ -201,6 +203,9 @@ struct Step {
   // PixelShuffle: the block size, depth to space (else space to depth), channel-major (CRD / pixel_unshuffle; else block-major: DCR / SpaceToDepth)
   int64_t ps_block = 0;
   bool ps_to_space = false, ps_channel_major = false;
+  // GridSample / AffineGrid: GridSampleMode, GridSamplePad, GridSampleCoords (host/gridsample.hpp) and align_corners
+  int gs_mode = 0, gs_pad = 0, gs_coords = 0;
+  bool gs_align = false;
   // FakeQuant: qx.  QDense: qx = how the f32 input is quantised, qy = how the result is (off: the step returns `real`, f32);
   // qW [K, M] = the weights as signed bytes (uint8 data shifted by 128), q_wzp[M] = their zero points shifted the same way, q_mult[M] =
   // x_scale * w_scale[m] in f32, q_bias[M] = the int32 bias added to the accumulator (else `bias`: f32, added after the scaling).

@@ -5457,3 +5457,151 @@ def r3d_net(widths: Sequence[int] = (4, 8), blocks: int = 1, in_dhw: Sequence[in
               node("Gemm", ["feat", "fc_w", "fc_b"], ["Y"], name="head")]
     ops.append(("head", hw, hb))
     return model("r3d", nodes, inits, [value_info("X", ["N", cin, *in_dhw])], [value_info("Y", ["N", classes])], opset=17), ops
+
+
+# ------------------------------------------------------------------------------------------
+# Grid sampling: GridSample and AffineGrid (INTEGRATION.md 2.6 "Grid sampling")
+# ------------------------------------------------------------------------------------------
+
+def grid_sample_base(out_hw) -> np.ndarray:
+    """The identity grid [Ho, Wo, 2] a flow field is added to (pixel centres, f32): x = (2 j + 1) / Wo - 1, y likewise"""
+    Ho, Wo = out_hw
+    xs = ((2 * np.arange(Wo) + 1).astype(np.float32) / np.float32(Wo) - np.float32(1)).astype(np.float32)
+    ys = ((2 * np.arange(Ho) + 1).astype(np.float32) / np.float32(Ho) - np.float32(1)).astype(np.float32)
+    return np.stack(np.broadcast_arrays(xs[None, :], ys[:, None]), axis=-1).astype(np.float32)
+
+
+def grid_sample_model(coords: str = "grid", c: int = 3, hw=(5, 7), out_hw=(6, 11), mode: str = "bilinear", padding: str = "zeros", align_corners: int = 0,
+                      values=None, pre: bool = False, post: bool = False, flow_order: str = "add_first", opset: int = 20, affine_readers: int = 1,
+                      loc: str = "conv", size=None, affine_align=None, name: str = "warp") -> bytes:
+    """One GridSample node `name` over an image [N, c, *hw], its coordinates in one of the three forms the lowering knows:
+      grid     an [N, Ho, Wo, 2] tensor;   planar   a flow field [N, 2, Ho, Wo] read through Transpose(0,2,3,1), with the Add of the constant identity
+      grid (grid_sample_base) in front of the Transpose (flow_order "add_first") or behind it;   affine   AffineGrid(theta [N, 2, 3], size).
+    values None: a two-input model -- X [N, c*H*W] and the coordinates [N, k] as flat columns of the call, reshaped in the graph.  Else: a
+    one-input model over X [N, c, H, W] whose coordinates are the constant `values` (grid [Ho,Wo,2], flow [2,Ho,Wo] or theta [6]), handed to every
+    image by an STN-shaped localisation net with zero weights: Conv 1x1 -> GlobalAveragePool -> Flatten -> Gemm(0, values) (loc = "gap": without the
+    Conv, for images too large to convolve).  flow_order "conv": as add_first, the field written by an identity 1x1 Conv.  pre / post: an
+    identity 1x1 Conv in front of the node / identity 1x1 ConvTranspose behind it, so that it reads / writes a channel-quad tensor.
+    affine_readers = 2: the AffineGrid's result is also a graph output (it then writes the grid).  size: the AffineGrid's size instead of
+    [0, c, Ho, Wo], or "dynamic" (computed from a runtime value); affine_align: its align_corners where it differs from the GridSample's."""
+    (H, Wd), (Ho, Wo) = hw, out_hw
+    k = {"grid": Ho * Wo * 2, "planar": 2 * Ho * Wo, "affine": 6}[coords]
+    nodes, inits = [], []
+
+    def i64(nm, v):
+        inits.append(tensor(nm, np.asarray(v, np.int64)))
+        return nm
+
+    if values is None:
+        assert not pre and not post
+        inputs = [value_info("X", ["N", c * H * Wd]), value_info("G", ["N", k])]
+        nodes.append(node("Reshape", ["X", i64("x_shape", [-1, c, H, Wd])], ["img"], name="x_reshape"))
+        img, src = "img", "G"
+    else:
+        inputs = [value_info("X", ["N", c, H, Wd])]
+        inits += [tensor("fc_w", np.zeros((4 if loc == "conv" else c, k), np.float32)), tensor("fc_b", np.asarray(values, np.float32).reshape(-1))]
+        if loc == "conv":
+            inits.append(tensor("loc_w", np.zeros((4, c, 1, 1), np.float32)))
+            nodes.append(node("Conv", ["X", "loc_w"], ["loc"], [attr_ints("kernel_shape", [1, 1])], name="loc_conv"))
+        nodes += [node("GlobalAveragePool", ["loc" if loc == "conv" else "X"], ["loc_gap"], name="loc_gap"), node("Flatten", ["loc_gap"], ["loc_flat"], [attr_i("axis", 1)], name="loc_flatten"),
+                  node("Gemm", ["loc_flat", "fc_w", "fc_b"], ["coords"], name="loc_fc")]
+        img, src = "X", "coords"
+        if pre:
+            inits.append(tensor("pre_w", np.eye(c, dtype=np.float32)[:, :, None, None]))
+            nodes.append(node("Conv", ["X", "pre_w"], ["pre"], [attr_ints("kernel_shape", [1, 1])], name="pre"))
+            img = "pre"
+    outs = []
+    if coords == "grid":
+        nodes.append(node("Reshape", [src, i64("g_shape", [-1, Ho, Wo, 2])], ["grid"], name="g_reshape"))
+    elif coords == "planar":
+        nodes.append(node("Reshape", [src, i64("g_shape", [-1, 2, Ho, Wo])], ["flow"], name="g_reshape"))
+        if flow_order == "conv":
+            inits.append(tensor("flow_w", np.eye(2, dtype=np.float32)[:, :, None, None]))
+            nodes.append(node("Conv", ["flow", "flow_w"], ["flow_c"], [attr_ints("kernel_shape", [1, 1])], name="flow_conv"))
+        if flow_order != "transpose_first":
+            inits.append(tensor("base", grid_sample_base(out_hw).transpose(2, 0, 1)[None]))
+            nodes += [node("Add", ["flow_c" if flow_order == "conv" else "flow", "base"], ["field"], name="flow_add"), node("Transpose", ["field"], ["grid"], [attr_ints("perm", [0, 2, 3, 1])], name="to_last")]
+        else:
+            inits += [tensor("base", grid_sample_base(out_hw)[None]), tensor("one", np.ones((), np.float32))]
+            nodes += [node("Mul", ["flow", "one"], ["field"], name="flow_mul"), node("Transpose", ["field"], ["field_last"], [attr_ints("perm", [0, 2, 3, 1])], name="to_last"),
+                      node("Add", ["field_last", "base"], ["grid"], name="flow_add")]
+    else:
+        nodes.append(node("Reshape", [src, i64("t_shape", [-1, 2, 3])], ["theta"], name="t_reshape"))
+        if size == "dynamic":
+            nodes.append(node("Cast", [src], ["size"], [attr_i("to", INT64)], name="size_cast"))
+        else:
+            i64("size", [0, c, Ho, Wo] if size is None else size)
+        nodes.append(node("AffineGrid", ["theta", "size"], ["grid"], [attr_i("align_corners", align_corners if affine_align is None else affine_align)], name="affine"))
+        if affine_readers > 1:
+            outs.append(value_info("grid", ["N", Ho, Wo, 2]))
+    nodes.append(node("GridSample", [img, "grid"], ["warped"], [attr_s("mode", mode), attr_s("padding_mode", padding), attr_i("align_corners", align_corners)], name=name))
+    cur = "warped"
+    if post:
+        inits.append(tensor("post_w", np.eye(c, dtype=np.float32)[:, :, None, None]))
+        nodes.append(node("ConvTranspose", [cur, "post_w"], ["post"], [attr_ints("kernel_shape", [1, 1])], name="post"))
+        cur = "post"
+    return model("grid_sample", nodes, inits, inputs, [value_info(cur, ["N", c, Ho, Wo])] + outs, opset=opset)
+
+
+def grid_sample_bare(x_dims, g_dims, four_d: bool = False, x_const: bool = False, quantize: bool = False, opset: int = 20) -> bytes:
+    """GridSample 'warp' over operands of any declared dims (x_dims, g_dims: everything behind the batch axis; with four_d the full dims, batch
+    included, of two inputs declared as they are instead of flat [N, k] columns reshaped in the graph): the forms that are refused at load.
+    x_const: X is an initializer; quantize: X goes through QuantizeLinear first."""
+    inits, nodes, ins = [], [], []
+    for nm, dims, const in (("X", x_dims, x_const), ("G", g_dims, False)):
+        if const:
+            inits.append(tensor(nm.lower(), np.zeros([1] + list(dims), np.float32)))
+        elif four_d:
+            ins.append(value_info(nm.lower(), dims))
+        else:
+            ins.append(value_info(nm, ["N", int(np.prod(dims))]))
+            inits.append(tensor(nm.lower() + "_shape", np.array([-1] + list(dims), np.int64)))
+            nodes.append(node("Reshape", [nm, nm.lower() + "_shape"], [nm.lower()], name=nm.lower() + "_reshape"))
+    if x_const:
+        ins.insert(0, value_info("X", ["N", 1]))
+    src = "x"
+    if quantize:
+        inits += [tensor("q_scale", np.array(0.02, np.float32)), tensor("q_zp", np.array(128, np.uint8))]
+        nodes.append(node("QuantizeLinear", ["x", "q_scale", "q_zp"], ["xq"], name="quantize"))
+        src = "xq"
+    nodes.append(node("GridSample", [src, "g"], ["Y"], name="warp"))
+    return model("grid_sample_bare", nodes, inits, ins, [value_info("Y", ["N"] + [1] * (len(x_dims) - (1 if four_d else 0)))], opset=opset)
+
+
+def stn_reference(w: dict, x) -> np.ndarray:
+    """stn_model's scores in float64 (torch on the CPU)"""
+    import torch
+    import torch.nn.functional as F
+
+    t = {k: torch.from_numpy(np.asarray(v, np.float64)) for k, v in w.items()}
+    xt = torch.from_numpy(np.asarray(x, np.float64))
+    theta = F.max_pool2d(F.relu(F.conv2d(xt, t["loc_w"], t["loc_b"], padding=1)), 2).flatten(1) @ t["fc_w"] + t["fc_b"]
+    warped = F.grid_sample(xt, F.affine_grid(theta.reshape(-1, 2, 3), list(xt.shape), align_corners=False), mode="bilinear", padding_mode="zeros", align_corners=False)
+    return (F.relu(F.conv2d(warped, t["head_w"], t["head_b"], padding=1)).mean((2, 3)) @ t["cls_w"] + t["cls_b"]).numpy()
+
+
+def stn_model(c: int = 1, size: int = 12, classes: int = 5, seed: int = 97, mode: str = "bilinear", padding: str = "zeros", align_corners: int = 0) -> tuple[bytes, dict]:
+    """A spatial transformer in front of a classifier, as torch exports one at opset 20: the localisation net Conv 3x3 + Relu -> MaxPool 2 -> Flatten
+    -> Gemm to six numbers (zero weights' neighbourhood of the identity) -> Reshape [N,2,3] -> AffineGrid -> GridSample of the image -> Conv 3x3 +
+    Relu -> GlobalAveragePool -> Flatten -> Gemm.  Returns (model, the weights by name)."""
+    rng = np.random.default_rng(seed)
+    half = size // 2
+
+    def draw(shape, fan):
+        return (rng.uniform(-1, 1, size=shape) / math.sqrt(fan)).astype(np.float32)
+
+    w = {"loc_w": draw((8, c, 3, 3), c * 9), "loc_b": draw((8,), c * 9), "fc_w": 0.05 * draw((8 * half * half, 6), 8 * half * half),
+         "fc_b": np.array([1, 0, 0, 0, 1, 0], np.float32) + 0.1 * draw((6,), 1), "head_w": draw((8, c, 3, 3), c * 9), "head_b": draw((8,), c * 9),
+         "cls_w": draw((8, classes), 8), "cls_b": draw((classes,), 8)}
+    inits = [tensor(k, v) for k, v in w.items()] + [tensor("t_shape", np.array([-1, 2, 3], np.int64)), tensor("size", np.array([0, c, size, size], np.int64))]
+    conv = [attr_ints("kernel_shape", [3, 3]), attr_ints("pads", [1, 1, 1, 1])]
+    nodes = [node("Conv", ["X", "loc_w", "loc_b"], ["l1"], conv, name="loc_conv"), node("Relu", ["l1"], ["l2"], name="loc_relu"),
+             node("MaxPool", ["l2"], ["l3"], [attr_ints("kernel_shape", [2, 2]), attr_ints("strides", [2, 2])], name="loc_pool"),
+             node("Flatten", ["l3"], ["l4"], [attr_i("axis", 1)], name="loc_flatten"), node("Gemm", ["l4", "fc_w", "fc_b"], ["t6"], name="loc_fc"),
+             node("Reshape", ["t6", "t_shape"], ["theta"], name="t_reshape"),
+             node("AffineGrid", ["theta", "size"], ["grid"], [attr_i("align_corners", align_corners)], name="affine"),
+             node("GridSample", ["X", "grid"], ["warped"], [attr_s("mode", mode), attr_s("padding_mode", padding), attr_i("align_corners", align_corners)], name="warp"),
+             node("Conv", ["warped", "head_w", "head_b"], ["h1"], conv, name="head_conv"), node("Relu", ["h1"], ["h2"], name="head_relu"),
+             node("GlobalAveragePool", ["h2"], ["h3"], name="gap"), node("Flatten", ["h3"], ["h4"], [attr_i("axis", 1)], name="flatten"),
+             node("Gemm", ["h4", "cls_w", "cls_b"], ["scores"], name="cls")]
+    return model("stn", nodes, inits, [value_info("X", ["N", c, size, size])], [value_info("scores", ["N", classes])], opset=20), w
