@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../host/conv3d.hpp"
+#include "../host/deformconv.hpp"
 
 namespace infera_hip {
 struct SpectrumPack;  // host/spectrum.hpp
@@ -420,6 +421,19 @@ struct GridSampleGeom {
 bool grid_sample(hipStream_t s, const float *X, const float *G, float *Y, int64_t rows, const GridSampleGeom &g, bool in_cq, bool out_cq);
 // Y [rows, OH, OW, 2] = the sampling grid of theta [rows, 6]
 bool affine_grid(hipStream_t s, const float *theta, float *Y, int64_t rows, int OH, int OW, bool align_corners);
+
+// ---- DeformConv (deformconv.hip; the coordinate function, the split and the form flags: host/deformconv.hpp) ------
+// One DeformConv2d step over `rows` images: Y [rows, M, OH, OW] = the convolution of X [rows, C, H, W] sampled at the fixed grid + Off
+// [rows, og * kh * kw * 2, OH, OW], each sample times Mask [rows, og * kh * kw, OH, OW] (null without g.has_mask).  flags (DeformForm): which
+// of the four tensors lie in channel-quad planes.  deformconv_mfma (group == 1, kh * kw <= kDeformMaxTaps): Wp = deformconv_pack() of the ONNX
+// weights [M, C, kh, kw], bias = deform_split(g).Mp entries (zero beyond M).  deformconv_generic: W = the ONNX weights [M, C/g, kh, kw] as they
+// are, bias [M] or null.  false: the form is outside the kernel and nothing was launched.
+size_t deformconv_packed_floats(const DeformGeom &g);
+void deformconv_pack(const DeformGeom &g, const float *W, float *packed);
+bool deformconv_mfma(hipStream_t s, const float *X, const float *Off, const float *Mask, const float *Wp, const float *bias, float *Y, int64_t rows, const DeformGeom &g,
+                     int flags, ActParam act);
+bool deformconv_generic(hipStream_t s, const float *X, const float *Off, const float *Mask, const float *W, const float *bias, float *Y, int64_t rows,
+                        const DeformGeom &g, int flags, ActParam act);
 
 // ---- InstanceNormalization / GroupNormalization (spatialnorm.hip; host/spatialnorm.hpp) --------------
 // X, Y: [rows, C, S] in NCHW order or (cq) channel-quad planes; G groups of C / G channels; gamma, beta: [C].  false: beyond the kernel's caps

@@ -6,6 +6,7 @@
 
 #include "../host/channelnorm.hpp"
 #include "../host/deconv.hpp"
+#include "../host/deformconv.hpp"
 #include "../host/gridsample.hpp"
 #include "../host/pixelshuffle.hpp"
 #include "../host/spatialnorm.hpp"
@@ -223,7 +224,10 @@ void Scheduler::decide_layout(bool commit) {
   // (so does the crossing to a window, tokens.hip; its flat result has no layout, and alone it does not make a plan convolutional)
   // (and so does a PixelShuffle, pixelshuffle.hip: the SpaceToDepth stem reads the caller's image)
   // (and a GridSample, gridsample.hip: a warp of the caller's image, in front of or in the middle of a CNN)
-  auto reads_either = [&](const Step &s) { return reads_nchw(s) || s.kind == StepKind::Tokens || s.kind == StepKind::PixelShuffle || s.kind == StepKind::GridSample; };
+  // (and a DeformConv2d, deformconv.hip: X, the offsets and the mask each in the layout their buffer has)
+  auto reads_either = [&](const Step &s) {
+    return reads_nchw(s) || s.kind == StepKind::Tokens || s.kind == StepKind::PixelShuffle || s.kind == StepKind::GridSample || s.kind == StepKind::DeformConv2d;
+  };
   // the steps that store NCHW from a channel-quad input where their result has to lie so
   auto stores_nchw = [](const Step &s) { return s.kind == StepKind::ConvTranspose2d || s.kind == StepKind::PixelShuffle || s.kind == StepKind::GridSample; };
   // A served [C,H,W] result leaves in the caller's NCHW order.  When such a step -- a transposed convolution or a sub-pixel shuffle, the last
@@ -532,6 +536,7 @@ void Scheduler::classify_io(const std::vector<EffStep> &eff) {
         const bool windowed = (sk == StepKind::Conv2d && sc[size_t(e.idx)].kind != ExecKind::ConvPatch) || sk == StepKind::QConv2d || sk == StepKind::Pool2d || sk == StepKind::LRN ||
                               sk == StepKind::Conv3d || sk == StepKind::Pool3d ||
                               sk == StepKind::GridSample ||  // (a gather: up to four fetches per sample, wherever the grid points)
+                              sk == StepKind::DeformConv2d ||  // (likewise, per tap)
                               sk == StepKind::TreeEnsemble || sk == StepKind::SvmKernel ||
                               sk == StepKind::Nearest ||  // (once per slice of the reference set)
                               sk == StepKind::TopK ||     // (one lane per row: row-strided loads)
@@ -673,6 +678,14 @@ void schedule(LoadedModel &m) {
     auto quads = [&](int b) { return m.cq(b) && s.is4d(b) && s.spatial(b) > 1; };
     if (c.kind == StepKind::GridSample) m.sched[i].form = (quads(c.in0) ? 1 : 0) | (quads(c.out) ? 2 : 0);
   }
+  // DeformConv2d layers: which of the four tensors lie in channel quads, and the kernel (INFERA_DEFORMCONV_MFMA=0: the generic one everywhere)
+  for (size_t i = 0; i < m.sched.size(); i++) {
+    const Step &c = m.plan.steps[i];
+    if (c.kind != StepKind::DeformConv2d) continue;
+    auto quads = [&](int b) { return b >= 0 && m.cq(b) && s.is4d(b) && s.spatial(b) > 1; };
+    m.sched[i].form = (quads(c.in0) ? kDeformXcq : 0) | (quads(c.out) ? kDeformYcq : 0) | (quads(c.in1) ? kDeformOffCq : 0) | (quads(c.in2) ? kDeformMaskCq : 0) |
+                      (deform_takes_mfma(deform_geom(c), knobs.deformconv_mfma) ? kDeformMfma : 0);
+  }
   s.narrow_edges(StepKind::QDense, knobs.qdense_bytes, true, [](const Step &p, const Step &c) { return c.qx == p.qy; });
   s.narrow_edges(StepKind::HDense, knobs.hdense_half, false, [](const Step &, const Step &) { return true; });
   const auto eff = effective_steps(m);
@@ -780,6 +793,13 @@ std::string LoadedModel::describe_json() const {
     const bool in_cq = sched[i].form & 1, out_cq = sched[i].form & 2;
     return step_obj(i, std::string(",\"exec\":\"") + gridsample_exec_name(x.gs_mode, in_cq, out_cq) + "\",\"coords\":\"" + gridsample_coords_name(x.gs_coords) + "\"" +
                            layouts(in_cq ? "NC/4HW4" : "NCHW", out_cq ? "NC/4HW4" : "NCHW"));
+  });
+  // per DeformConv2d step: the kernel that runs it, the layouts of X, Y and the offsets, and the LDS of its column tile
+  per_step("deformconv", {StepKind::DeformConv2d}, [&](size_t i, const Step &x) {
+    const int f = sched[i].form;
+    auto lay = [&](int bit) { return (f & bit) ? "NC/4HW4" : "NCHW"; };
+    return step_obj(i, std::string(",\"exec\":\"") + ((f & kDeformMfma) ? "deformconv_mfma" : "deformconv_generic") + "\"" + layouts(lay(kDeformXcq), lay(kDeformYcq)) + ",\"offset_layout\":\"" +
+                           lay(kDeformOffCq) + "\",\"lds_bytes\":" + std::to_string((f & kDeformMfma) ? deform_split(deform_geom(x)).lds_bytes : 0));
   });
   // per Tokens step: the kernel that runs it and the layout it reads (its result is a flat window)
   per_step("tokens", {StepKind::Tokens}, [&](size_t i, const Step &x) {

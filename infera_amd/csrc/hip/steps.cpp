@@ -549,6 +549,33 @@ void launch_conv3d(const PassRunner &r, const Step &x, const PlainTables &t) {
     throw InferaError::onnx("Conv3d kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
 }
 
+// ---- DeformConv (host/deformconv.hpp, deformconv.hip): the scheduler recorded the kernel and the layouts of the four tensors (StepSchedule::form).
+// The MFMA form takes the weights in the order its lanes load them and a bias padded to whole channel tiles; the generic form takes both as
+// the lowering left them ----
+void upload_deformconv(const Upload &up, size_t i, PlainTables &t) {
+  const Step &s = up.m.plan.steps[i];
+  if (!(up.m.sched[i].form & kDeformMfma)) {
+    t.W = up(s.W);
+    t.bias = up(s.bias);
+    return;
+  }
+  const DeformGeom g = deform_geom(s);
+  std::vector<float> packed(kern::deformconv_packed_floats(g));
+  kern::deformconv_pack(g, s.W.data(), packed.data());
+  t.W = up(packed);
+  t.bias = up(zero_padded(s.bias, size_t(deform_split(g).Mp)));
+}
+void launch_deformconv(const PassRunner &r, size_t i, const PlainTables &t) {
+  const Step &x = r.st[i];
+  const int form = r.m.sched[i].form;
+  if (r.in_colmajor && (x.in0 == 0 || x.in1 == 0 || x.in2 == 0)) throw InferaError::onnx("internal: a DeformConv2d step reads its input row-major");
+  const DeformGeom g = deform_geom(x);
+  const float *mask = x.in2 >= 0 ? r.buf(x.in2) : nullptr;
+  const bool ok = (form & kDeformMfma) ? kern::deformconv_mfma(r.stream, r.buf(x.in0), r.buf(x.in1), mask, t.W, t.bias, r.buf(x.out), r.nr, g, form, act_of(x))
+                                       : kern::deformconv_generic(r.stream, r.buf(x.in0), r.buf(x.in1), mask, t.W, t.bias, r.buf(x.out), r.nr, g, form, act_of(x));
+  if (!ok) throw InferaError::onnx("DeformConv kernel launch failed: '" + x.origin + "' is beyond the kernel's caps");
+}
+
 // ---- the plain family: the step's constants as the lowering left them (Conv2d: packed for the generic kernel); its launches are the head
 // of PassRunner::launch_plain, right below ----
 void upload_plain(const Step &s, PlainTables &t, const Upload &up) {
@@ -620,6 +647,7 @@ void PassRunner::launch_plain(size_t i) {
     case StepKind::GridSample: launch_gridsample(*this, i); break;
     case StepKind::AffineGrid: launch_affinegrid(*this, x); break;
     case StepKind::Conv3d: launch_conv3d(*this, x, t); break;
+    case StepKind::DeformConv2d: launch_deformconv(*this, i, t); break;
     case StepKind::Pool3d:
       if (in_colmajor && x.in0 == 0) throw InferaError::onnx("internal: a Pool3d step reads its input row-major");
       kern::pool3d(stream, buf(x.in0), buf(x.out), nr, conv3d_geom(x), x.is_max, x.count_pad);
@@ -702,6 +730,7 @@ void upload_step(const Upload &up, size_t i) {
     case StepKind::PixelShuffle: return;  // (a copy by index arithmetic: no tables)
     case StepKind::Spectrum: return upload_spectrum(s, d.spectrum, up);
     case StepKind::Conv3d: return upload_conv3d(s, d.plain, up);
+    case StepKind::DeformConv2d: return upload_deformconv(up, i, d.plain);
     default: return;  // (no tables)
   }
 }

@@ -112,7 +112,8 @@ ScheduleKnobs ScheduleKnobs::read() {
                        env_flag("INFERA_CONV_FOLD_SHORTCUT", true), env_flag("INFERA_QDENSE_BYTES", true), env_flag("INFERA_HDENSE_HALF", true),
                        env_flag("INFERA_HDENSE", true), env_flag("INFERA_NEAREST", true), env_flag("INFERA_CONVT_MFMA", true),
                        env_flag("INFERA_SPATIALNORM_FUSED", true), env_flag("INFERA_CHANNELNORM_REGS", true), env_flag("INFERA_PIXELSHUFFLE_FAST", true),
-                       env_flag("INFERA_CONV3D_MFMA", true), env_flag("INFERA_CONV3D_STAGE", false)};
+                       env_flag("INFERA_CONV3D_MFMA", true), env_flag("INFERA_CONV3D_STAGE", false),
+                       env_flag("INFERA_DEFORMCONV_MFMA", true)};
 }
 
 void log_msg(int level, const std::string &msg) {

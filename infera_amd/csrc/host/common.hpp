@@ -132,6 +132,7 @@ struct ScheduleKnobs {
   bool pixelshuffle_fast;  // INFERA_PIXELSHUFFLE_FAST=0|1 (default 1)  PixelShuffle steps on the quad-copy, register-transpose and layout-crossing forms where they apply (0: the generic form everywhere; same bits; tests, A/B)
   bool conv3d_mfma;   // INFERA_CONV3D_MFMA=0|1 (default 1; read when a model is LOWERED)  Conv3d layers with group = 1 on the MFMA kernel (0: conv3d_generic everywhere; same bits on exact data; tests, A/B)
   bool conv3d_stage;  // INFERA_CONV3D_STAGE=0|1 (default 0; read when a model is LOWERED)  1: conv3d_mfma stages its input window in LDS where it fits (0: every tap from global memory, which measured faster on every R3D-18 layer; the same bits)
+  bool deformconv_mfma;  // INFERA_DEFORMCONV_MFMA=0|1 (default 1)  DeformConv2d layers with group = 1 and kh * kw <= 49 on the MFMA kernel (0: deformconv_generic everywhere; tests, A/B)
   static ScheduleKnobs read();
 };
 // Read per launch inside the kernel launchers, for the bit-identity TESTS only (no effect on results; defaults are the shipped paths):

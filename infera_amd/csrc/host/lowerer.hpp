@@ -665,6 +665,12 @@ struct Lowerer {
   void affine_grid(const NodeDef &n);
   void grid_sample(const NodeDef &n);
 
+  // ---- lower_deformconv.cpp: DeformConv (INTEGRATION.md 2.6 "Deformable convolutions") ----
+  // a live DeformConv node whose X is a rank-4 graph input with a symbolic extent behind the batch axis: refused by its name (run: before the
+  // general rules on input shapes)
+  void check_deform_extents() const;
+  void deform_conv(const NodeDef &n);
+
   // ---- lower_conv3d.cpp: Conv, MaxPool and AveragePool on [N,C,D,H,W] activations (INTEGRATION.md 2.6 "3-D convolutions") ----
   void spatial3d(const NodeDef &n, Step &s);
   void conv3d(const NodeDef &n);

@@ -1070,8 +1070,8 @@ namespace lowering {
     if (a.is_const) unsupported(n, "activation of a constant");
     std::vector<int64_t> shape = a.shape;
     if (Step *p = fusable_producer(n, idx)) {
-      const bool mfma_step = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d || p->kind == StepKind::Conv3d;
-      const bool takes_act = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d || p->kind == StepKind::Conv3d || p->kind == StepKind::AffineChannel ||
+      const bool mfma_step = p->kind == StepKind::Dense || p->kind == StepKind::Conv2d || p->kind == StepKind::Conv3d || p->kind == StepKind::DeformConv2d;
+      const bool takes_act = mfma_step || p->kind == StepKind::AffineChannel ||
                              p->kind == StepKind::BinaryConst || p->kind == StepKind::BinaryAct;
       const bool qdense_act = quantised_layer(*p) && !p->qy.on && (act == Act::Relu || act == Act::Clip);  // on `real`, before the requantisation
       const bool hdense_act = p->kind == StepKind::HDense && cur_half && int(act) >= 1 && int(act) <= kMaxMfmaFusedAct;  // r = half(act(float(r)))
@@ -1595,7 +1595,7 @@ namespace lowering {
         set_act(n, a.buf, shape, true);
         return;
       }
-      if (p->kind == StepKind::Conv3d && p->act == Act::None && p->Mo == C) {  // fold into the 3-D convolution (f64, one rounding)
+      if ((p->kind == StepKind::Conv3d || p->kind == StepKind::DeformConv2d) && p->act == Act::None && p->Mo == C) {  // fold into the 3-D / deformable convolution (f64, one rounding)
         for (int64_t mo = 0; mo < C; mo++) {
           const double dsc = double(sc[size_t(mo)]) / std::sqrt(double(var[size_t(mo)]) + double(eps));
           for (int64_t k = 0; k < p->K; k++) p->W[size_t(mo * p->K + k)] = float(dsc * double(p->W[size_t(mo * p->K + k)]));
@@ -3726,6 +3726,7 @@ namespace lowering {
     else if (op == "DepthToSpace" || op == "SpaceToDepth") depth_space(n);
     else if (op == "GridSample") grid_sample(n);
     else if (op == "AffineGrid") affine_grid(n);
+    else if (op == "DeformConv") deform_conv(n);
     else if (op == "DFT") dft(n);
     else if (op == "STFT") stft(n);
     else if (op == "BatchNormalization") batchnorm(n);
@@ -4299,6 +4300,7 @@ namespace lowering {
         throw InferaError::onnx("input '" + v.name + "' is not f32, int64 or int32 (element type " + std::to_string(v.elem_type) + ")");
     if (in.dims.size() < 2) throw InferaError::onnx("input rank " + std::to_string(in.dims.size()) + " has no row axis + feature axis; rank >= 2 is required");
     check_grid_extents();  // (a GridSample on a symbolic image or grid: refused by the node's name)
+    check_deform_extents();  // (a DeformConv on a symbolic image: likewise)
     check_shuffle_extents(in);  // (a DepthToSpace / SpaceToDepth on a symbolic image: refused by the node's name)
     for (size_t i = 1; i < in.dims.size(); i++)
       if (in.dims[i] <= 0) throw InferaError::onnx("only the leading (row/batch) dimension of the input may be symbolic, got " + shape_str(in.dims));

@@ -29,6 +29,7 @@ double Plan::flops_per_row() const {
     if (s.kind == StepKind::Dense || s.kind == StepKind::QDense || s.kind == StepKind::HDense) f += 2.0 * double(s.rep) * double(s.K) * double(s.M);
     else if (s.kind == StepKind::Attention) f += 4.0 * double(s.attn_T) * double(s.attn_Tk > 0 ? s.attn_Tk : s.attn_T) * double(s.attn_heads * s.attn_dh);  // (an upper bound under attn_causal, as for padded rows)
     else if (s.kind == StepKind::Conv2d || s.kind == StepKind::QConv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);
+    else if (s.kind == StepKind::DeformConv2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OH) * double(s.OW);  // (the multiply; the sampling is a gather)
     else if (s.kind == StepKind::Conv3d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.OD) * double(s.OH) * double(s.OW);
     else if (s.kind == StepKind::ConvTranspose2d) f += 2.0 * double(s.K) * double(s.Mo) * double(s.H) * double(s.Wd);  // (C/g) kh kw taps per input pixel and output channel
     else if (s.kind == StepKind::SvmKernel) f += 2.0 * double(s.svm->n_sv) * double(s.svm->F + s.svm->Q);  // X . S^T, then the coefficients
@@ -49,7 +50,7 @@ const char *act_name(Act a) {
 }
 
 std::string Plan::describe_json() const {
-  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary", "PixelShuffle", "NearestVote", "Spectrum", "Conv3d", "Pool3d", "GridSample", "AffineGrid"};
+  static const char *kinds[] = {"Dense", "Unary", "AffineChannel", "BinaryConst", "BinaryAct", "Softmax", "Conv2d", "Pool2d", "GlobalAvgPool", "CopyCols", "ArgMax", "SliceCols", "PadCols", "LRN", "ChannelShuffle", "TreeEnsemble", "TreeReduce", "SvmKernel", "SvmReduce", "Prep", "Recurrent", "LayerNorm", "Attention", "MeanTime", "FakeQuant", "QDense", "QConv2d", "RoundHalf", "HDense", "RowReduce", "ArgMin", "TopK", "Nearest", "NearestReduce", "ConvTranspose2d", "Resize2d", "SpatialNorm", "SpatialStats", "Tokens", "ChannelNorm", "Embed", "Interact", "RmsNorm", "Rotary", "PixelShuffle", "NearestVote", "Spectrum", "Conv3d", "Pool3d", "GridSample", "AffineGrid", "DeformConv2d"};
   std::ostringstream o;
   o << "{\"input_shape\":" << json_int_array(input_shape) << ",\"output_shape\":" << json_int_array(output_shape)
     << ",\"flops_per_row\":" << (long long)flops_per_row();
@@ -177,6 +178,10 @@ std::string Plan::describe_json() const {
     if (s.kind == StepKind::GridSample)  // (a gather: eight flops per bilinear sample, none counted)
       o << ",\"mode\":\"" << gridsample_mode_name(s.gs_mode) << "\",\"padding\":\"" << gridsample_pad_name(s.gs_pad) << "\",\"align_corners\":" << int(s.gs_align) << ",\"coords\":\""
         << gridsample_coords_name(s.gs_coords) << "\",\"C\":" << s.C << ",\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "]";
+    if (s.kind == StepKind::DeformConv2d)
+      o << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"in_hw\":[" << s.H << "," << s.Wd << "],\"out_hw\":[" << s.OH << "," << s.OW << "],\"k\":[" << s.kh << "," << s.kw << "],\"strides\":[" << s.sh
+        << "," << s.sw << "],\"pads\":[" << s.pt << "," << s.pl << "," << s.pb << "," << s.pr << "],\"dilations\":[" << s.dh << "," << s.dw << "],\"groups\":" << s.groups
+        << ",\"offset_groups\":" << s.offset_groups << ",\"mask\":" << (s.in2 >= 0 ? "true" : "false") << ",\"bias\":" << (s.bias.empty() ? "false" : "true");
     if (s.kind == StepKind::AffineGrid) o << ",\"align_corners\":" << int(s.gs_align) << ",\"out_hw\":[" << s.OH << "," << s.OW << "]";
     if (s.kind == StepKind::PixelShuffle)  // (a copy: no flops; every element is read once and written once)
       o << ",\"form\":\"" << pixelshuffle_form_name(s.ps_to_space, s.ps_channel_major) << "\",\"block\":" << s.ps_block << ",\"C\":" << s.C << ",\"M\":" << s.Mo << ",\"in_hw\":[" << s.H << "," << s.Wd

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "conv3d.hpp"
+#include "deformconv.hpp"
 #include "onnx_model.hpp"
 
 namespace infera_hip {
@@ -91,6 +92,7 @@ enum class StepKind : int {
   Pool3d = 48,        // MaxPool / AveragePool over [rows, C, D, H, Wd] (the same geometry fields; is_max, count_pad)
   GridSample = 49,    // out [rows, C, OH, OW] = in0 [rows, C, H, Wd] sampled at the coordinates in1 holds (gs_coords: a [rows, OH, OW, 2] grid, a [rows, 2, OH, OW] flow field, or six affine numbers per row -- AffineGrid absorbed); gs_mode, gs_pad, gs_align as the operator's attributes; either tensor in NCHW or channel quads (host/gridsample.hpp, gridsample.hip)
   AffineGrid = 50,    // out [rows, OH, OW, 2] (a flat row) = the sampling grid of theta in0 [rows, 6]: an AffineGrid whose result something else than one GridSample reads (gs_align; gridsample.hip)
+  DeformConv2d = 51,  // deformable convolution of in0 [rows, C, H, Wd] to [rows, Mo, OH, OW] (the Conv2d geometry fields + offset_groups): every tap is sampled bilinearly at its fixed position + the offset pair in1 [rows, og * kh * kw * 2, OH, OW] holds and multiplied by in2 [rows, og * kh * kw, OH, OW] (-1: no mask); W = the ONNX weights [M, C/g, kh, kw], BatchNormalization folded when adjacent; the scheduler picks the kernel and the layouts (StepSchedule::form, DeformForm; host/deformconv.hpp, deformconv.hip)
   Resize2d = 35,      // nearest / linear Resize (and Upsample) of an [N,C,H,W] tensor to [N,C,OH,OW] from the DeconvPack's row and column tables (resize.hip)
 };
 // how an HDense step adds its bias: Gemm rounds acc + b once; MatMul -> Add rounds the product first, then the sum
@@ -203,6 +205,7 @@ struct Step {
   // PixelShuffle: the block size, depth to space (else space to depth), channel-major (CRD / pixel_unshuffle; else block-major: DCR / SpaceToDepth)
   int64_t ps_block = 0;
   bool ps_to_space = false, ps_channel_major = false;
+  int64_t offset_groups = 1;  // DeformConv2d: the channel groups that share one offset pair (and mask value) per tap
   // GridSample / AffineGrid: GridSampleMode, GridSamplePad, GridSampleCoords (host/gridsample.hpp) and align_corners
   int gs_mode = 0, gs_pad = 0, gs_coords = 0;
   bool gs_align = false;
@@ -225,6 +228,12 @@ struct Step {
 inline Conv3dGeom conv3d_geom(const Step &s) {
   return Conv3dGeom{int(s.C), int(s.D), int(s.H), int(s.Wd), int(s.Mo), int(s.OD), int(s.OH), int(s.OW), int(s.kd), int(s.kh), int(s.kw), int(s.sd), int(s.sh), int(s.sw),
                     int(s.pf), int(s.pt), int(s.pl), int(s.dd), int(s.dh), int(s.dw), int(s.groups)};
+}
+
+// the geometry of a DeformConv2d step as the kernels take it
+inline DeformGeom deform_geom(const Step &s) {
+  return DeformGeom{int(s.C), int(s.H), int(s.Wd), int(s.Mo), int(s.OH), int(s.OW), int(s.kh), int(s.kw), int(s.sh), int(s.sw), int(s.pt), int(s.pl),
+                    int(s.dh), int(s.dw), int(s.groups), int(s.offset_groups), s.in2 >= 0};
 }
 
 struct Plan {

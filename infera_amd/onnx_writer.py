@@ -5605,3 +5605,83 @@ def stn_model(c: int = 1, size: int = 12, classes: int = 5, seed: int = 97, mode
              node("GlobalAveragePool", ["h2"], ["h3"], name="gap"), node("Flatten", ["h3"], ["h4"], [attr_i("axis", 1)], name="flatten"),
              node("Gemm", ["h4", "cls_w", "cls_b"], ["scores"], name="cls")]
     return model("stn", nodes, inits, [value_info("X", ["N", c, size, size])], [value_info("scores", ["N", classes])], opset=20), w
+
+
+# ------------------------------------------------------------------------------------------
+# Deformable convolutions: DeformConv (INTEGRATION.md 2.6 "Deformable convolutions")
+# ------------------------------------------------------------------------------------------
+
+def deform_conv_out_hw(in_hw, k, strides=(1, 1), pads=(0, 0, 0, 0), dilations=(1, 1)) -> tuple:
+    """The Conv formula on both axes"""
+    return tuple((in_hw[i] + pads[i] + pads[i + 2] - (dilations[i] * (k[i] - 1) + 1)) // strides[i] + 1 for i in range(2))
+
+
+def deform_conv_layer(w: np.ndarray, b: np.ndarray | None, in_hw: Sequence[int], mask: bool = False, act: str = "", off_dims=None, mask_dims=None,
+                      consts: Sequence[str] = (), elem: int = FLOAT, x_dims=None, w_input: bool = False, four_d: bool = False, quantize: bool = False,
+                      opset: int = 19, **attrs) -> bytes:
+    """One DeformConv 'dcn' of X [N, C, H, W] with the kernel w [M, C/group, kh, kw] (+ bias, + `act`); attrs: strides, pads, dilations, group,
+    offset_group, kernel_shape.  X, the offsets [N, og*kh*kw*2, OH, OW] and (mask) the mask [N, og*kh*kw, OH, OW] are flat [N, k] columns of the
+    call, in this order, reshaped in the graph.  The forms that are refused at load: off_dims / mask_dims / x_dims declare other extents
+    (everything behind the batch axis); four_d: X is a 4-D input of its own (x_dims may be symbolic) and the offsets and the mask are zero-weight
+    Convs of it; consts names operands that are initializers ("X", "O") or not constant ("B": the flat offset input itself); w_input makes W a
+    runtime input; elem is the element type of X and of every weight; quantize: X goes through QuantizeLinear first."""
+    g, og = attrs.get("group", 1), attrs.get("offset_group", 1)
+    kh, kw = w.shape[2:]
+    C = w.shape[1] * g
+    # (off_dims given: the attributes may be malformed on purpose)
+    OH, OW = (0, 0) if off_dims else deform_conv_out_hw(in_hw, (kh, kw), attrs.get("strides", (1, 1)), attrs.get("pads", (0, 0, 0, 0)), attrs.get("dilations", (1, 1)))
+    dims = {"X": list(x_dims or [C, *in_hw]), "O": list(off_dims or [og * kh * kw * 2, OH, OW]), "M": list(mask_dims or [og * kh * kw, OH, OW])}
+    nodes, ins = [], []
+    np_elem = np.float16 if elem == FLOAT16 else np.float32
+    inits = [tensor("w", w.astype(np_elem))] + ([tensor("b", b.astype(np_elem))] if b is not None and "B" not in consts else [])
+    for nm in ["X", "O"] + (["M"] if mask else []):
+        if nm in consts:
+            inits.append(tensor(nm.lower(), np.zeros([1] + dims[nm], np.float32)))
+        elif four_d:
+            if nm == "X":
+                ins.append(value_info("x", ["N"] + dims["X"], elem))
+            else:
+                inits.append(tensor(nm.lower() + "_w", np.zeros((dims[nm][0], C, kh, kw), np_elem)))
+                nodes.append(node("Conv", ["x", nm.lower() + "_w"], [nm.lower()], [attr_ints(k, v) for k, v in attrs.items() if k in ("strides", "pads", "dilations")], name=nm.lower() + "_conv"))
+        else:
+            ins.append(value_info(nm, ["N", int(np.prod(dims[nm]))], elem if nm == "X" else FLOAT))
+            inits.append(tensor(nm.lower() + "_shape", np.array([-1] + dims[nm], np.int64)))
+            nodes.append(node("Reshape", [nm, nm.lower() + "_shape"], [nm.lower()], name=nm.lower() + "_reshape"))
+    if not ins:
+        ins.append(value_info("X", ["N", 1]))
+    if w_input:
+        ins.append(value_info("Wt", ["N", int(np.prod(w.shape[1:]))]))
+        inits[0] = tensor("w_shape", np.array((-1,) + w.shape[1:], np.int64))
+        nodes.append(node("Reshape", ["Wt", "w_shape"], ["w"], name="w_reshape"))
+    if quantize:
+        inits += [tensor("q_scale", np.array(0.02, np.float32)), tensor("q_zp", np.array(128, np.uint8))]
+        nodes.append(node("QuantizeLinear", ["x", "q_scale", "q_zp"], ["xq"], name="quantize"))
+    operands = ["xq" if quantize else "x", "w", "o", ("O" if "B" in consts else "b") if b is not None else "", "m" if mask else ""]
+    while operands and not operands[-1]:
+        operands.pop()
+    nodes.append(node("DeformConv", operands, ["c" if act else "Y"], _attrs3d(attrs), name="dcn"))
+    if act:
+        nodes.append(node(act, ["c"], ["Y"], name="act"))
+    return model("deform_conv", nodes, inits, ins, [value_info("Y", ["N", w.shape[0], "h", "w"], elem)], opset=opset)
+
+
+def dcn_block(k: int = 3, c: int = 8, m: int = 8, hw: Sequence[int] = (6, 7), cin: int = 3, classes: int = 4, offset_group: int = 1, seed: int = 71,
+              offset_scale: float = 1.0) -> tuple[bytes, dict]:
+    """A modulated deformable block as torchvision's DeformConv2d exports it: Conv 3x3 + Relu (cin -> c) -> an offset Conv k x k (c -> og*k*k*2) and
+    a mask Conv k x k + Sigmoid (c -> og*k*k) -> DeformConv k x k (c -> m) + Relu -> Conv 1x1 (m -> classes) -> GlobalAveragePool -> Flatten.
+    All three k x k layers pad to the input's extents (an even k: behind only).  Returns (model, the weights by name)."""
+    ws = _WeightStream(seed)
+    taps, lo = k * k, (k - 1) // 2
+    pads = [lo, lo, k - 1 - lo, k - 1 - lo]
+    w = {"stem_w": ws.take((c, cin, 3, 3), cin * 9), "stem_b": ws.take((c,), cin * 9),
+         "off_w": (offset_scale * ws.take((offset_group * taps * 2, c, k, k), c * taps)).astype(np.float32), "off_b": ws.take((offset_group * taps * 2,), 4),
+         "mask_w": ws.take((offset_group * taps, c, k, k), c * taps), "mask_b": ws.take((offset_group * taps,), 4),
+         "dcn_w": ws.take((m, c, k, k), c * taps), "dcn_b": ws.take((m,), c * taps), "head_w": ws.take((classes, m, 1, 1), m), "head_b": ws.take((classes,), m)}
+    kk = [attr_ints("kernel_shape", [k, k]), attr_ints("pads", pads)]
+    nodes = [node("Conv", ["X", "stem_w", "stem_b"], ["s1"], [attr_ints("kernel_shape", [3, 3]), attr_ints("pads", [1, 1, 1, 1])], name="stem"), node("Relu", ["s1"], ["s2"], name="stem_relu"),
+             node("Conv", ["s2", "off_w", "off_b"], ["off"], kk, name="offset_conv"), node("Conv", ["s2", "mask_w", "mask_b"], ["m1"], kk, name="mask_conv"),
+             node("Sigmoid", ["m1"], ["mask"], name="mask_sigmoid"),
+             node("DeformConv", ["s2", "dcn_w", "off", "dcn_b", "mask"], ["d1"], kk + [attr_i("offset_group", offset_group)], name="dcn"), node("Relu", ["d1"], ["d2"], name="dcn_relu"),
+             node("Conv", ["d2", "head_w", "head_b"], ["h1"], [attr_ints("kernel_shape", [1, 1])], name="head"),
+             node("GlobalAveragePool", ["h1"], ["h2"], name="gap"), node("Flatten", ["h2"], ["scores"], [attr_i("axis", 1)], name="flatten")]
+    return model("dcn_block", nodes, [tensor(n_, v) for n_, v in w.items()], [value_info("X", ["N", cin, *hw])], [value_info("scores", ["N", classes])], opset=19), w
